@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the k-mer counting path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 21] [--ext-index]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 21] [--ext-index] [--dump-outputs DIR]
 
 Metric (BASELINE.json): distinct k-mers/sec, k=21, 150 bp synthetic reads.
 N=1 workload = BASELINE.json configs[1]: 10 M x 150 bp uniform reads (50x coverage of a
@@ -23,6 +23,12 @@ seconds of extension index -> unitigs -> GFA on the same reads; "e2e": wall seco
 (spades-kmercount, spades-gbuilder --gfa) on the same reads written as FASTA to tmpfs, with their phases, next to the
 CPU oracle run end to end (parse included) on a bounded sample; "cpu_baseline": the CPU oracle -- a port of the
 reference's split/sort/unique/merge algorithm -- timed on a bounded sample on this box's host cores.
+
+--dump-outputs DIR: after the timed steps, the result of the last one (the k-mer set; with --ext-index also the
+extension index) is written to DIR/*.npy as float64, a fixed sample of at most 2^19 records per output, every rank its
+own files, under 64 MB for all ranks together (dump_outputs).  The inputs are seeded, so two builds run with the same
+arguments can be compared file for file.  In this mode the last timed step's result is released after the timed
+region instead of inside it (one release of `steps`); the JSON line then carries "dump_outputs".
 """
 import argparse
 import json
@@ -30,6 +36,8 @@ import os
 import subprocess
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -68,7 +76,12 @@ def parse():
     ap.add_argument("--no-e2e", action="store_true", help="skip the CLI wall-time measurement on FASTA input")
     ap.add_argument("--no-k55", action="store_true", help="skip the k=55 (16-byte keys) object")
     ap.add_argument("--no-meta", action="store_true", help="skip the skewed-metagenome (configs[4] shape) object")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float64; large outputs sampled)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -348,7 +361,7 @@ def metagenome(ctx, args, B, fence):
         # released -- that is ~30 ms/GiB and was the "159.7 ms with 50.4 ms of kernels" of the round-2 driver run).
         # What mapping is left inside the timed steps is reported.
         map0 = ctx.memory_stats()["map_seconds"]
-        n, dt, prof = timed_steps(ctx, st, fence, 2, 2)
+        n, dt, prof, _ = timed_steps(ctx, st, fence, 2, 2)
         map_in_timed = ctx.memory_stats()["map_seconds"] - map0
         sv = {f: ctx.profile_get(f) for f in stats}
         rec = max(1.0, sv["stat_slot_records"]["bytes"])
@@ -399,10 +412,73 @@ def roofline_of(prof, steps, traffic_lookup=None, step_ms=None):
     return out
 
 
+DUMP_LIMIT = 64_000_000  # bytes of all dumped files of all ranks together, .npy headers included
+DUMP_RECORDS = 1 << 19   # records dumped per output at most
+DUMP_RUN = 2048          # consecutive records per sampled run
+
+
+def dump_runs(n, cap):
+    """(first, count) runs of the records of an n-record output that --dump-outputs writes: all of them up to cap,
+    else cap // DUMP_RUN runs of DUMP_RUN consecutive records, one at a seeded offset inside each of as many equal
+    strata (the same positions for the same n and cap on every run)."""
+    if n <= cap:
+        return [(0, n)] if n else []
+    length = min(DUMP_RUN, cap)
+    count = cap // length
+    stratum = n // count
+    offs = np.random.default_rng(0).integers(0, stratum - length + 1, size=count)
+    return [(i * stratum + int(o), length) for i, o in enumerate(offs)]
+
+
+def words_as_f64(keys):
+    """u64 records (n, words) -> float64 (n, 2 * words): the high and the low 32 bits of every word, exact."""
+    keys = np.ascontiguousarray(keys, dtype=np.uint64)
+    halves = np.stack([keys >> np.uint64(32), keys & np.uint64(0xFFFFFFFF)], axis=-1)
+    return halves.reshape(len(keys), 2 * keys.shape[1]).astype(np.float64)
+
+
+def dump_outputs(out_dir, keep, world, suffix=""):
+    """--dump-outputs: the result objects of the last timed step as the arrays a caller reads out of them.
+    k-mer set -> kmers.npy (records in the stored order), extension index -> extindex.npy + extindex_masks.npy; each
+    with <name>_index.npy (record positions of the sample) and <name>_size.npy (records in the whole output).
+    Every rank writes its own files and gets 1/world of DUMP_LIMIT; returns the bytes this rank wrote."""
+    os.makedirs(out_dir, exist_ok=True)
+    objs = keep if isinstance(keep, (list, tuple)) else [keep]
+    # bytes per sampled record over all outputs: 2 float64 per key word, its position, the mask of an index record
+    rec_bytes = sum(16 * ((o.k + 31) // 32) + 8 + (0 if hasattr(o, "get") else 8) for o in objs)
+    budget = DUMP_LIMIT // world
+    cap = min(DUMP_RECORDS, (budget - 4096) // rec_bytes)  # 4096: the .npy headers and the size arrays
+    arrays = {}
+    for obj in objs:
+        n = len(obj)
+        runs = dump_runs(n, cap)
+        index = np.concatenate([np.arange(a, a + c) for a, c in runs]) if runs else np.zeros(0, dtype=np.int64)
+        if hasattr(obj, "get"):  # KMerSet: only the sampled runs come to the host
+            name = "kmers"
+            keys = np.concatenate([obj.get(a, c) for a, c in runs]) if runs else \
+                np.zeros((0, (obj.k + 31) // 32), dtype=np.uint64)
+        else:  # ExtIndex: the whole index to host memory (no device memory is taken), sampled there
+            name = "extindex"
+            all_keys, all_masks = obj.export()
+            keys = all_keys[index]
+            arrays[name + "_masks"] = all_masks[index].astype(np.float64)
+            del all_keys, all_masks
+        arrays[name] = words_as_f64(keys)
+        arrays[name + "_index"] = index.astype(np.float64)
+        arrays[name + "_size"] = np.array([n], dtype=np.float64)
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, name + suffix + ".npy"))
+        np.save(paths[-1], a)
+    written = sum(os.path.getsize(p) for p in paths)
+    assert written <= budget, "dump of %d bytes over this rank's share %d" % (written, budget)
+    return written
+
+
 SETTLE_STEPS = 0
 
 
-def timed_steps(ctx, step, fence, warmup, steps, settle_allocator=False):
+def timed_steps(ctx, step, fence, warmup, steps, settle_allocator=False, keep_last=False):
     def drop(x):
         for y in (x if isinstance(x, (list, tuple)) else [x]):
             if hasattr(y, "free"):
@@ -434,16 +510,20 @@ def timed_steps(ctx, step, fence, warmup, steps, settle_allocator=False):
     ctx.profile_reset()
     fence()
     t0 = time.perf_counter()
-    for _ in range(steps):
+    last = None
+    for i in range(steps):
         n_rec, keep = step()
-        drop(keep)
+        if keep_last and i == steps - 1:
+            last = keep
+        else:
+            drop(keep)
         del keep
     fence()
     dt = time.perf_counter() - t0
     ctx.profile(False)
     prof = {f: ctx.profile_get(f) for f in FAMILIES}
     prof = {f: v for f, v in prof.items() if v["launches"]}
-    return n_rec, dt, prof
+    return n_rec, dt, prof, last
 
 
 def main():
@@ -510,8 +590,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    n_rec, dt, prof = timed_steps(ctx, step, fence, args.warmup, args.steps, settle_allocator=(2 if sharded else True))
+    n_rec, dt, prof, last = timed_steps(ctx, step, fence, args.warmup, args.steps,
+                                        settle_allocator=(2 if sharded else True), keep_last=bool(args.dump_outputs))
     settle_steps = SETTLE_STEPS
+    dump = None
+    if args.dump_outputs:
+        t0 = time.perf_counter()
+        dump_bytes = dump_outputs(args.dump_outputs, last, world, "_rank%d" % rank if world > 1 else "")
+        dump = {"dir": args.dump_outputs, "ranks": world, "seconds": time.perf_counter() - t0,
+                "note": "the release of the last timed step's result is outside the timed region in this mode"}
+        for obj in (last if isinstance(last, list) else [last]):
+            obj.free()
+        del last
 
     red_dev = dev if (not sharded or dist.get_backend() == "nccl") else torch.device("cpu")
     tt = torch.tensor([dt], dtype=torch.float64, device=red_dev)
@@ -521,6 +611,12 @@ def main():
         dist.all_reduce(nn, op=dist.ReduceOp.SUM)
     dt_max = float(tt.item())
     distinct_total = int(nn.item())
+    if dump:
+        db = torch.tensor([dump_bytes], dtype=torch.int64, device=red_dev)
+        if sharded:
+            dist.all_reduce(db, op=dist.ReduceOp.SUM)
+        dump["bytes"] = int(db.item())  # all ranks' files together
+        assert dump["bytes"] <= DUMP_LIMIT, "dump of %d bytes over %d" % (dump["bytes"], DUMP_LIMIT)
 
     # N>1: the second half of the metric over all ranks (configs[3] shape): sharded extension index -> gathered on
     # rank 0 -> unitigs + links -> GFA text on tmpfs; one un-timed-region measurement, every rank takes part
@@ -595,6 +691,8 @@ def main():
             "kernel_ms_per_step": {f: v["ms"] / args.steps for f, v in prof.items()},
             "roofline": roof,
         }
+        if dump:
+            line["dump_outputs"] = dump
         big = args.reads > 20_000_000
         # the CLIs first: they are separate processes on the same GPU, and with the tens of GB that the k = 55 and
         # metagenome objects leave mapped in this process their device phase was intermittently 0.3-0.5 s instead of 0.03 s
@@ -608,7 +706,7 @@ def main():
             def step55():
                 s = ctx.count(reads, 55, B.BOTH_STRANDS | B.REFERENCE_ORDER)
                 return len(s), s
-            n55, dt55, prof55 = timed_steps(ctx, step55, fence, 1, 2)
+            n55, dt55, prof55, _ = timed_steps(ctx, step55, fence, 1, 2)
             line["k55"] = {"workload": "the same %d reads, k=55 (16-byte keys), k-mer count only" % args.reads,
                            "steps": 2, "warmup": 1, "ms_per_step": dt55 / 2 * 1e3, "distinct_kmers": n55,
                            "value": n55 / (dt55 / 2), "unit": "distinct k-mers/s", "dtype": "u128",
