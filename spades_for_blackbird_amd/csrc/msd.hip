@@ -30,7 +30,7 @@
 // Buckets larger than CAP (a k-mer repeated thousands of times, skewed composition in KEYS mode)
 // are finished by the LSD path, per bucket; if too much overflows the caller falls back entirely.
 // Environment knobs (tests / diagnostics): BBK_DISABLE_MSD, BBK_NO_SLOTS, BBK_SLOTS_MIN, BBK_NO_DIST,
-// BBK_PASS_LIMIT, BBK_VERBOSE; -DBBK_PHASE_PROF builds per-phase shader clocks into the kernels.
+// BBK_PASS_LIMIT, BBK_NO_NARROW_B, BBK_VERBOSE; -DBBK_PHASE_PROF builds per-phase shader clocks into the kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -323,7 +323,7 @@ __device__ unsigned long long g_phase[6][8];
 // Common tail of the scatter kernels.  On entry lhist[b] = records of bin b in this tile and binrank[i] =
 // bin << 16 | rank-in-bin (0xFFFFFFFF: no record).  One global atomicAdd per non-empty bin reserves the
 // tile's run in that bin; the records are reordered through LDS (stage) so that a wave stores contiguous
-// per-bin runs.
+// per-bin runs.  NOUT (narrow stage B, 8-byte keys): the output holds only the keys' low words (spills stay 8-byte).
 // Inclusive prefix sum over the 64 lanes of a wave with DPP row shifts and row broadcasts: six v_add with a DPP operand.
 // (__shfl_up goes through ds_bpermute: an address register per distance, an LDS-pipe operation and a select per step.)
 __device__ __forceinline__ uint32_t wave_scan_incl(uint32_t v) {
@@ -352,7 +352,7 @@ __device__ __forceinline__ void wave_totals(const uint32_t *tmp, int lane, int w
     before = (uint32_t)__builtin_amdgcn_readlane((int)(inc - v), __builtin_amdgcn_readfirstlane(wave));
 }
 
-template <int W, int ITEMS, int THREADS, int MAXB, bool HAS_VAL>
+template <int W, int ITEMS, int THREADS, int MAXB, bool HAS_VAL, bool NOUT = false>
 __device__ __forceinline__ void part_tail(const Key<W> (&keys)[ITEMS], const uint32_t (&vals)[ITEMS],
                                           const uint32_t (&binrank)[ITEMS], uint32_t *lhist, uint32_t *lstart,
                                           uint32_t *goff, uint32_t *scan_tmp, Key<W> *stage, uint32_t *vstage,
@@ -454,7 +454,8 @@ __device__ __forceinline__ void part_tail(const Key<W> (&keys)[ITEMS], const uin
             if (L.slot_cap && (int32_t)pos >= (int32_t)lhist[b]) {
                 full |= 1u << i;
             } else {
-                key_store<W>(&out[g], key);
+                if constexpr (NOUT) reinterpret_cast<uint32_t *>(out)[g] = (uint32_t)key.w[0];
+                else key_store<W>(&out[g], key);
                 if (HAS_VAL) vout[g] = vstage[pos];
             }
         }
@@ -541,7 +542,8 @@ __device__ __forceinline__ void tile_load(const Key<W> *__restrict__ in, const u
 
 // One partition level over a key array.  HIST_ONLY: accumulate the level histogram; else scatter.
 // LVL1: level-1 kernels have at most 512 bins (smaller LDS tables: two workgroups per CU)
-template <int W, bool HAS_VAL, bool HIST_ONLY, bool LVL1>
+// NOUT: 4-byte output records (the keys' low words; level 2 of narrow stage B, see k_bucket_dist_nb)
+template <int W, bool HAS_VAL, bool HIST_ONLY, bool LVL1, bool NOUT = false>
 __global__ __launch_bounds__(PartCfg<W>::THREADS) void k_part(const Key<W> *__restrict__ in,
                                                               const uint32_t *__restrict__ vin, TileMap M, PartLevel L,
                                                               uint32_t *__restrict__ ghist,   // HIST_ONLY: [nseg * nb]
@@ -647,7 +649,8 @@ __global__ __launch_bounds__(PartCfg<W>::THREADS) void k_part(const Key<W> *__re
     }
     __syncthreads();
     BBK_PH(prof_kind, 1, t_prev);  // load + LDS ranking
-    part_tail<W, kPartItems, kPartThreads, MAXB, HAS_VAL>(keys, vals, binrank, lhist, lstart, goff, scan_tmp, stage, vstage,
+    static_assert(!NOUT || (W == 1 && !HIST_ONLY), "4-byte output records: 8-byte keys, scatter only");
+    part_tail<W, kPartItems, kPartThreads, MAXB, HAS_VAL, NOUT>(keys, vals, binrank, lhist, lstart, goff, scan_tmp, stage, vstage,
                                                         nb, gbin0, L, cursor, out, vout, prof_kind, t_prev);
 }
 
@@ -1540,6 +1543,258 @@ static size_t bucket_dist_smem() {
 template <int W, int NT, int ITEMS, int OP>
 static size_t bucket_smem() {
     return sizeof(uint32_t) * ((NT / 64) * 256 + 256 + 32) + (size_t)W * 8 * NT * ITEMS + (OP >= 2 ? 4 * NT * ITEMS : 0);
+}
+
+// ---- narrow stage B (8-byte keys, key slots, no payload): 4-byte records from level 2 on
+// The KEYS prefix is the key's top 32 bits, p = key >> (w0bits - 32).  Bucket g = bin j of the nb bins of segment s holds
+// exactly the keys whose prefix lies in [s*P + q_j, s*P + q_(j+1)), with P = 2^(32 - b1) and q_j = ceil(j * P / nb): the
+// inverse of bin_of, whose bin is umulhi(q << b1, nb) = floor(q * nb / P) for the low 32 - b1 prefix bits q.  Its smallest
+// key is base[g] = (s*P + q_j) << (w0bits - 32).  When no bucket spans more than 2^32 keys (ceil(P / nb) << (w0bits - 32)
+// <= 2^32 for every non-empty segment: the host checks) a key of bucket g is base[g] + (uint32_t)(lo - (uint32_t)base[g]),
+// lo being its low word.  So level 2 stores lo only (k_part<..., NOUT>) and k_bucket_dist_nb sorts the 32-bit offsets
+// lo - (uint32_t)base[g] and widens them on the way out.  (w0bits <= 32: the key is its low word, base 0.)
+__global__ void k_bucket_base(const uint32_t *__restrict__ seg_nb2, const uint32_t *__restrict__ seg_bin, uint32_t nseg,
+                              uint32_t nbuckets, int b1, int w0bits, uint64_t *__restrict__ base) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nbuckets) return;
+    uint32_t lo = 0, hi = nseg;  // largest s with seg_bin[s] <= g (every segment has at least one bin)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (seg_bin[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const uint64_t P = 1ull << (32 - b1), nb = seg_nb2[lo], j = g - seg_bin[lo];
+    const uint64_t p = lo * P + (j * P + nb - 1) / nb;
+    base[g] = w0bits > 32 ? p << (w0bits - 32) : 0ull;
+}
+
+// k_bucket_dist (OP 0, sorted result written directly) on those 4-byte records: the same distribution sort and in-bin
+// ranking over 32-bit offsets, with half the LDS (38 KB against 61 KB) and at most 80 registers (76: four records per
+// ranking round instead of six), so that three workgroups fit a CU instead of two.  A bucket it turns down, a duplicate or a spill
+// sends the call back to the exact mode, as on the 8-byte key slots, so no second-chance kernel needs this form.
+template <int NT, int ITEMS>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_bucket_dist_nb(const uint32_t *__restrict__ buf, const uint64_t *__restrict__ base,
+                                                       BucketArgs A) {
+    constexpr int CAP = NT * ITEMS;
+    constexpr int NWAVES = NT / 64;
+    constexpr int DB = DistBins<1, 0>::N;
+    constexpr int BPT = DB / NT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // layout: bins[DB] | scan[32] | mm[2 * NWAVES] | skeys[CAP] (offsets from the bucket's base)
+    uint32_t *bins = reinterpret_cast<uint32_t *>(smem);
+    uint32_t *scan_tmp = bins + DB;
+    uint32_t *mm = scan_tmp + 32;
+    uint32_t *skeys = mm + 2 * NWAVES;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t b = A.bucket_ids ? A.bucket_ids[blockIdx.x] : blockIdx.x;
+    uint32_t start, n;
+    bucket_range(A, b, &start, &n);
+    if (n == 0) {
+        if (tid == 0) A.dcount[b] = 0;
+        return;
+    }
+    if (n > (uint32_t)CAP) {
+        if (tid == 0) A.dcount[b] = 0xFFFFFFFFu;
+        return;
+    }
+    for (uint32_t q = tid; q < (uint32_t)DB; q += NT) bins[q] = 0;
+#ifdef BBK_PHASE_PROF
+    unsigned long long t_prev = clock64();
+#endif
+
+    const uint64_t kbase = base[b];
+    uint32_t keys[ITEMS];  // offsets from the base: the key order
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = (uint32_t)(i * NT + tid);
+        keys[i] = buf[start + (p < n ? p : n - 1u)];
+    }
+    uint32_t mn = ~0u, mx = 0;
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {  // clamped duplicates do not change min / max
+        keys[i] -= (uint32_t)kbase;
+        mn = keys[i] < mn ? keys[i] : mn;
+        mx = keys[i] > mx ? keys[i] : mx;
+    }
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) {
+        const uint32_t a = __shfl_xor(mn, dd, 64), c = __shfl_xor(mx, dd, 64);
+        mn = a < mn ? a : mn;
+        mx = c > mx ? c : mx;
+    }
+    if (lane == 0) {
+        mm[2 * wave] = mn;
+        mm[2 * wave + 1] = mx;
+    }
+    __syncthreads();  // bins zeroed, min / max of every wave visible
+    mn = ~0u;
+    mx = 0;
+#pragma unroll
+    for (int j = 0; j < NWAVES; ++j) {
+        mn = mm[2 * j] < mn ? mm[2 * j] : mn;
+        mx = mm[2 * j + 1] > mx ? mm[2 * j + 1] : mx;
+    }
+    BBK_PH(3, 0, t_prev);  // loads + min/max
+    const uint32_t kmin = mn;
+    const int rbits = 32 - __builtin_clz((mx - mn) | 1u);
+    const int sh = rbits > DistBins<1, 0>::LOG ? rbits - DistBins<1, 0>::LOG : 0;  // digit = (offset - min) >> sh < bins
+
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = (uint32_t)(i * NT + tid);
+        if (p < n) atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
+    }
+    __syncthreads();
+    BBK_PH(3, 1, t_prev);  // count
+    uint32_t c[BPT];
+    uint32_t sum = 0;
+    bool big = false;
+#pragma unroll
+    for (int q = 0; q < BPT; ++q) {
+        c[q] = bins[tid * BPT + q];
+        sum += c[q];
+        big = big || c[q] > kDistMaxBin;
+    }
+    uint32_t incl = sum;
+    incl = wave_scan_incl(incl);
+    if (lane == 63) scan_tmp[wave] = incl;
+    if (__syncthreads_or(big)) {
+        if (tid == 0) A.dcount[b] = 0xFFFFFFFFu;
+        return;
+    }
+    uint32_t first = incl - sum;
+    for (int j = 0; j < wave; ++j) first += scan_tmp[j];
+    {
+        uint32_t ex = first;
+#pragma unroll
+        for (int q = 0; q < BPT; ++q) {
+            bins[tid * BPT + q] = ex;
+            ex += c[q];
+        }
+    }
+    __syncthreads();
+    BBK_PH(3, 2, t_prev);  // scan
+    uint32_t at[ITEMS];  // where the scatter put the record (breaks ties between equal offsets), then its final place
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t p = (uint32_t)(i * NT + tid);
+        at[i] = 0xFFFFFFFFu;
+        if (p < n) {
+            const uint32_t pos = atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
+            skeys[pos] = keys[i];
+            at[i] = pos;
+        }
+    }
+    __syncthreads();
+    BBK_PH(3, 3, t_prev);  // scatter
+    // in-bin ranking as in k_bucket_dist: bin d = [bins[d-1], bins[d]) after the scatter, RB records per round with the
+    // first four candidates of every bin read unconditionally (one array for both places saves eleven registers)
+    constexpr int RB = 4;  // (6 as in k_bucket_dist: 93 registers, two workgroups per CU)
+#pragma unroll
+    for (int i0 = 0; i0 < ITEMS; i0 += RB) {
+        uint32_t sb[RB], e[RB];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+            const int i = i0 + u;
+            sb[u] = e[u] = 0;
+            if (i < ITEMS) {
+                const uint32_t p = (uint32_t)(i * NT + tid);
+                if (p < n) {
+                    const uint32_t d = (keys[i] - kmin) >> sh;
+                    sb[u] = d ? bins[d - 1] : 0u;
+                    e[u] = bins[d];
+                }
+            }
+        }
+        uint32_t o[RB][4];
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+#pragma unroll
+            for (int c4 = 0; c4 < 4; ++c4) {
+                const uint32_t y = sb[u] + c4;
+                o[u][c4] = skeys[y < e[u] ? y : (e[u] ? e[u] - 1u : 0u)];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < RB; ++u) {
+            const int i = i0 + u;
+            if (i < ITEMS) {
+                const uint32_t p = (uint32_t)(i * NT + tid);
+                if (p < n) {
+                    uint32_t before = 0;
+#pragma unroll
+                    for (int c4 = 0; c4 < 4; ++c4) {
+                        const uint32_t y = sb[u] + c4;
+                        if (y < e[u]) before += (o[u][c4] < keys[i] || (o[u][c4] == keys[i] && y < at[i])) ? 1u : 0u;
+                    }
+                    for (uint32_t y = sb[u] + 4; y < e[u]; ++y) {  // bins above four records
+                        const uint32_t ok = skeys[y];
+                        before += (ok < keys[i] || (ok == keys[i] && y < at[i])) ? 1u : 0u;
+                    }
+                    at[i] = sb[u] + before;
+                }
+            }
+        }
+    }
+    __syncthreads();  // every rank is computed from the scattered order: only now overwrite it
+    BBK_PH(3, 4, t_prev);  // rank
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i)
+        if (at[i] != 0xFFFFFFFFu) skeys[at[i]] = keys[i];
+    __syncthreads();
+    BBK_PH(3, 5, t_prev);  // write
+
+    // heads (blocked ownership: thread t owns [t*ITEMS, (t+1)*ITEMS)), the distinct offsets compacted in LDS, then
+    // widened and stored coalesced at the bucket's place in the result.  Every offset is a possible value: the first
+    // record of the bucket is a head by position, not by comparison with a sentinel.
+    uint32_t ostart = A.out_off ? A.out_off[b] : start;
+    const uint32_t p0 = (uint32_t)tid * ITEMS;
+    const uint32_t prev = (p0 > 0 && p0 - 1 < n) ? skeys[p0 - 1] : 0u;
+    uint32_t mine[ITEMS];
+    uint32_t nheads = 0, headbits = 0;
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        mine[i] = 0;
+        if (p0 + i < n) {
+            mine[i] = skeys[p0 + i];
+            const bool h = (i == 0) ? (p0 == 0 || mine[0] != prev) : mine[i] != mine[i - 1];
+            if (h) {
+                headbits |= 1u << i;
+                ++nheads;
+            }
+        }
+    }
+    uint32_t excl, total;
+    {
+        uint32_t hincl = wave_scan_incl(nheads);
+        __syncthreads();  // everyone has its offsets in registers: skeys may be reused below
+        if (lane == 63) scan_tmp[wave] = hincl;
+        __syncthreads();
+        uint32_t wbase, tot;
+        wave_totals<NWAVES>(scan_tmp, lane, wave, wbase, tot);
+        excl = wbase + hincl - nheads;
+        total = tot;
+        asm volatile("" : "+v"(ostart));  // awaited here, not inside the store loop (see bucket_reduce)
+    }
+    int seg = (int)excl - 1;
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i)
+        if (p0 + i < n && (headbits & (1u << i))) skeys[++seg] = mine[i];
+    __syncthreads();
+    uint64_t *dst = reinterpret_cast<uint64_t *>(A.sorted_keys) + ostart;
+    for (uint32_t s = tid; s < total; s += NT) dst[s] = (kbase + skeys[s]) & A.strip_mask;
+    if (tid == 0 && total != n) atomicOr(A.dup_flag, 1u);
+    if (tid == 0) A.dcount[b] = total;
+    BBK_PH(3, 6, t_prev);  // heads + output
+#ifdef BBK_PHASE_PROF
+    if (threadIdx.x == 0) atomicAdd(&g_phase[3][7], 1ull);
+#endif
+}
+
+template <int NT, int ITEMS>
+static size_t bucket_dist_nb_smem() {
+    return sizeof(uint32_t) * (DistBins<1, 0>::N + 32 + 2 * (NT / 64) + (size_t)NT * ITEMS);
 }
 
 // ---- dedup by an LDS hash table (8-byte keys): when the caller only needs the distinct set (the
@@ -2636,12 +2891,12 @@ struct MsdRunner {
         else launch_part_l<HAS_VAL, HIST, false>(fam, bytes, ntiles, in, vin, M, L, ghist, cursor, out, vout);
     }
 
-    template <bool HAS_VAL, bool HIST, bool LVL1>
+    template <bool HAS_VAL, bool HIST, bool LVL1, bool NOUT = false>
     void launch_part_l(const char *fam, double bytes, uint32_t ntiles, const Key<W> *in, const uint32_t *vin, TileMap M,
                        PartLevel L, uint32_t *ghist, uint32_t *cursor, Key<W> *out, uint32_t *vout) {
         if (ntiles == 0) return;
         const size_t sm = part_smem(W, PartCfg<W>::TILE, HAS_VAL, HIST, LVL1);
-        auto fn = k_part<W, HAS_VAL, HIST, LVL1>;
+        auto fn = k_part<W, HAS_VAL, HIST, LVL1, NOUT>;
         BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)sm));
         M.ntiles = ntiles;
@@ -3121,6 +3376,22 @@ struct MsdRunner {
         }
         const uint32_t nbuckets = sbin[nb1];
 
+        // narrow stage B (see k_bucket_base): key slots (which imply the direct output), one whole pass, no payload, KEYS
+        // prefix, and no bucket spanning more than 2^32 keys -- then only the keys' low words travel after level 1
+        static const bool no_narrow_b = getenv("BBK_NO_NARROW_B") != nullptr;  // A/B switch
+        uint64_t span_b = 0;  // widest bucket, in keys
+        for (uint32_t b = 0; b < nb1; ++b)
+            if (h1[b]) {
+                const uint64_t P = 1ull << (32 - b1), q = (P + snb2[b] - 1) / snb2[b];
+                span_b = std::max(span_b, w0bits > 32 ? q << (w0bits - 32) : q >> (32 - w0bits));
+            }
+        const bool narrow_b = W == 1 && kslots && !even_part && !ranged && !has_dst && !has_val && op == MSD_OP_NONE &&
+                              dmode == MSD_KEYS && span_b <= (1ull << 32) && !no_narrow_b;
+        if (kslots && verbose)
+            fprintf(stderr, "[bbk] msd key slots: %s records from level 2 (widest bucket 2^%.1f keys)\n",
+                    narrow_b ? "4-byte" : "8-byte", std::log2((double)std::max<uint64_t>(span_b, 1)));
+        const size_t rec_b = narrow_b ? 4 : rec_ab;  // record width of the level-2 output
+
         // ---- level 2
         DevBuf seg_tile(((size_t)nsub + 1) * 4), seg_off(((size_t)nsub + 1) * 4), seg_nb2((size_t)nb1 * 4 + 16),
             seg_bin(((size_t)nb1 + 1) * 4), seg_size((size_t)nsub * 4 + 16);
@@ -3176,7 +3447,7 @@ struct MsdRunner {
         DevBuf hist2((size_t)nbuckets * 4 + 16), boff(((size_t)nbuckets + 1) * 4 + 16);
         const uint64_t nB = slots ? (uint64_t)nbuckets * stride2 : N;
         if (slots) BBK_REQUIRE(nB + N < (1ull << 32), BBK_ERR_INTERNAL, "slot layout exceeds 32-bit offsets");
-        bufB.alloc(nB * rec_ab);
+        bufB.alloc(nB * rec_b);
         if (need_vbuf) valB.alloc(nB * 4);
         if (!slots) {
             BBK_HIP(hipMemsetAsync(hist2.p, 0, (size_t)nbuckets * 4 + 16, ctx->stream));
@@ -3228,6 +3499,10 @@ struct MsdRunner {
                 }
                 check_launch("k_part_narrow2");
             }
+        } else if (narrow_b) {
+            if constexpr (W == 1)
+                launch_part_l<false, false, false, true>("k_part_l2", (double)N * (rec + 4), nwg2, bufA.as<Key<W>>(), nullptr,
+                                                         M2, L2, nullptr, hist2.as<uint32_t>(), bufB.as<Key<W>>(), nullptr);
         } else {
             const double pb = 2.0 * (double)N * (rec + (has_val ? 4 : 0));
             if (has_val) launch_part<true, false>("k_part_l2", pb, nwg2, bufA.as<Key<W>>(), valA.as<uint32_t>(), M2, L2, nullptr, hist2.as<uint32_t>(), bufB.as<Key<W>>(), valB.as<uint32_t>());
@@ -3286,7 +3561,7 @@ struct MsdRunner {
             A.dup_flag = dupf.as<uint32_t>();
             A.strip_mask = strip_mask;
         }
-        DevBuf bseg;
+        DevBuf bseg, bbase;  // bbase: narrow stage B, the smallest key of every bucket
         std::vector<uint16_t> h_bseg;
         if (narrow) {
             if constexpr (W == 1) {
@@ -3309,6 +3584,25 @@ struct MsdRunner {
                     case MSD_OP_SUM: launch32(k_bucket_hash32<2>, bucket_hash32_smem<2>()); break;
                     case MSD_OP_OR: launch32(k_bucket_hash32<3>, bucket_hash32_smem<3>()); break;
                     default: BBK_REQUIRE(false, BBK_ERR_ARG, "bad reduce op");
+                }
+            }
+        } else if (narrow_b) {
+            if constexpr (W == 1) {
+                BBK_REQUIRE(direct, BBK_ERR_INTERNAL, "4-byte stage-B records need the direct output");
+                bbase.alloc(((size_t)nbuckets + 1) * 8);
+                if (nbuckets) {
+                    hipLaunchKernelGGL(k_bucket_base, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                       seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), nb1, nbuckets, b1, w0bits,
+                                       bbase.as<uint64_t>());
+                    check_launch("k_bucket_base");
+                    constexpr int NT = BktCfg<1>::NT, IT = BktCfg<1>::ITEMS;
+                    const size_t sm = bucket_dist_nb_smem<NT, IT>();
+                    auto fn = k_bucket_dist_nb<NT, IT>;
+                    BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                (int)sm));
+                    KernelTimer t(ctx, "k_bucket_dist", (double)N * (4 + rec));
+                    hipLaunchKernelGGL(fn, dim3(nbuckets), dim3(NT), sm, ctx->stream, bufB.as<uint32_t>(), bbase.as<uint64_t>(), A);
+                    check_launch("k_bucket_dist_nb");
                 }
             }
         } else {

@@ -17,7 +17,7 @@ import re
 import sys
 
 FAMILY = [  # rocprof kernel symbol -> the name bbk_ctx_profile_get / bench.py use for the same kernel
-    # k_part_reads<W, HAS_VAL, HIST_ONLY>, k_part<W, HAS_VAL, HIST_ONLY, LVL1> (LVL1 also serves the level-0 pass)
+    # k_part_reads<W, HAS_VAL, HIST_ONLY>, k_part<W, HAS_VAL, HIST_ONLY, LVL1, NOUT> (LVL1 also serves the level-0 pass)
     (r"k_sk_part1", "k_sk_part1"),
     (r"k_sk_part2<\d, true>", "k_sk_part2_hist"),
     (r"k_sk_part2<\d, false>", "k_sk_part2"),
@@ -28,13 +28,14 @@ FAMILY = [  # rocprof kernel symbol -> the name bbk_ctx_profile_get / bench.py u
     (r"k_bucket_hash32", "k_bucket_hash32"),
     (r"k_part_reads<\d, (true|false), false>", "k_part_reads"),
     (r"k_part_reads<\d, (true|false), true>", "k_part_reads_hist"),
-    (r"k_part<\d, (true|false), false, true>", "k_part_l1"),
-    (r"k_part<\d, (true|false), false, false>", "k_part_l2"),
-    (r"k_part<\d, (true|false), true, true>", "k_part_hist1"),
-    (r"k_part<\d, (true|false), true, false>", "k_part_hist2"),
+    (r"k_part<\d, (true|false), false, true, false>", "k_part_l1"),
+    (r"k_part<\d, (true|false), false, false, (true|false)>", "k_part_l2"),  # NOUT: narrow stage B
+    (r"k_part<\d, (true|false), true, true, false>", "k_part_hist1"),
+    (r"k_part<\d, (true|false), true, false, false>", "k_part_hist2"),
     (r"k_bucket_hashidx", "k_bucket_hashidx"),
     (r"k_bucket_hash", "k_bucket_hash"),
     (r"k_bucket_dist<", "k_bucket_dist"),
+    (r"k_bucket_dist_nb<", "k_bucket_dist"),
     (r"k_bucket<", "k_bucket"),
     (r"k_compact", "compact"),
     (r"k_scatter<", "scatter"),
