@@ -234,6 +234,24 @@ int bbk_extindex_export(bbk_ctx *ctx, const bbk_extindex *x, void *dst_keys, voi
  * *removed_kmers = isolated k-mers (the count the reference logs), *removed_links = links dropped afterwards. */
 int bbk_extindex_clip_tips(bbk_ctx *ctx, bbk_extindex *x, uint32_t length_bound, uint64_t *removed_kmers,
                            uint64_t *removed_links);
+/* Early poly-A/T clipping on the index, in place: EarlyLowComplexityClipperProcessor(index, ratio, min_len, max_len)
+ * (common/assembly_graph/construction/early_simplification.hpp:163-344; the main pipeline runs RemoveATEdges, then
+ * RemoveATTips with ratio 0.8, min_len 10, max_len 200 before the early tip clipper, stages/construction.cpp:320-331).
+ * A k-mer is of low complexity when its most frequent nucleotide count c satisfies !math::ls(c, L * ratio) (L = k for
+ * edges, max(tip length, min_len) for tips; math::ls treats values within 4 ULPs as equal, math/xmath.h:218-226,300-305).
+ * remove_at_edges (:183-257): every junction k-mer of low complexity, in either orientation, loses its outgoing links
+ * to junctions (dead ends included).  *removed_edges = collected (k-mer, nucleotide) pairs (both orientations of a link
+ * count when both qualify: the number the reference logs as "(k+1)-mers were removed"); *removed_links = 2 per removed
+ * link ("Links removed").
+ * remove_at_tips (:269-333): every dead end with a unique incoming edge is followed back to a junction over at most
+ * max_len k-mers; a low-complexity tip that ends at a junction which is not a dead start is isolated (mask 0) and the
+ * junction drops its links to it.  *removed_kmers = isolated k-mers, *clipped_links = links dropped ("Clipped tips").
+ * BBK_ERR_ARG: a NULL argument, ratio not finite or <= 0, an even k; for tips also max_len == 0 or min_len > k (the
+ * reference reads base k-1-i of the junction for i < min_len). */
+int bbk_extindex_remove_at_edges(bbk_ctx *ctx, bbk_extindex *x, double ratio, uint64_t *removed_edges,
+                                 uint64_t *removed_links);
+int bbk_extindex_remove_at_tips(bbk_ctx *ctx, bbk_extindex *x, double ratio, uint32_t min_len, uint32_t max_len,
+                                uint64_t *removed_kmers, uint64_t *clipped_links);
 void bbk_extindex_free(bbk_extindex *x);
 
 /* ---- unitigs + graph links: replaces UnbranchingPathExtractor::ExtractUnbranchingPathsAndLoops

@@ -165,6 +165,19 @@ __device__ inline Key<W> kmer_shl(const Key<W> &x, int k, uint32_t c) {
     return o;
 }
 
+// drop base k-1, put c in front as base 0 (RtSeq::operator>>=; the predecessor of GetIncoming,
+// kmer_extension_index.hpp:295-297)
+template <int W>
+__device__ inline Key<W> kmer_shr(const Key<W> &x, int k, uint32_t c) {
+    Key<W> o;
+#pragma unroll
+    for (int i = W - 1; i > 0; --i) o.w[i] = (x.w[i] << 2) | (x.w[i - 1] >> 62);
+    o.w[0] = (x.w[0] << 2) | (uint64_t)(c & 3u);
+    const int vb = 2 * k - 64 * (W - 1);  // populated bits of the last word (1..64)
+    if (vb < 64) o.w[W - 1] &= (1ull << vb) - 1ull;
+    return o;
+}
+
 template <int W>
 __device__ inline uint32_t kmer_base(const Key<W> &x, int i) {
     return (uint32_t)((x.w[i >> 5] >> ((i & 31) << 1)) & 3ull);

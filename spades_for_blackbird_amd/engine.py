@@ -22,7 +22,8 @@ SYMBOLS = [
     "bbk_extindex_abort", "bbk_extindex_finish_with_set", "bbk_count_extindex", "bbk_kmerset_from_device", "bbk_kmerset_from_device_ex", "bbk_kmerset_both_strands", "bbk_kmerset_both_strands_ex", "bbk_words", "bbk_kmerset_size", "bbk_kmerset_k", "bbk_kmerset_keys", "bbk_reads_median_filter",
     "bbk_kmerset_instances", "bbk_kmerset_export", "bbk_kmerset_export_by_owner", "bbk_kmerset_free",
     "bbk_kmerset_write_final_kmers",
-    "bbk_extindex_build", "bbk_extindex_size", "bbk_extindex_k", "bbk_extindex_export", "bbk_extindex_clip_tips", "bbk_extindex_free",
+    "bbk_extindex_build", "bbk_extindex_size", "bbk_extindex_k", "bbk_extindex_export", "bbk_extindex_clip_tips",
+    "bbk_extindex_remove_at_edges", "bbk_extindex_remove_at_tips", "bbk_extindex_free",
     "bbk_unitigs_build", "bbk_unitigs_build_ex", "bbk_unitigs_to_reads", "bbk_unitigs_add_coverage", "bbk_unitigs_add_coverage_counts", "bbk_unitigs_export_kc", "bbk_unitigs_count", "bbk_unitigs_loops", "bbk_unitigs_total_bases",
     "bbk_unitigs_vertices", "bbk_unitigs_links", "bbk_unitigs_export", "bbk_unitigs_export_links",
     "bbk_unitigs_write_gfa", "bbk_unitigs_write_fasta", "bbk_unitigs_write_fastg", "bbk_unitigs_write_spades", "bbk_unitigs_free",
@@ -144,6 +145,9 @@ def load_library():
         L.bbk_extindex_export_u32.argtypes = [vp, vp, vp, vp]
         L.bbk_extindex_from_device.argtypes = [vp, vp, vp, u64, C.c_uint, C.POINTER(vp)]
         L.bbk_extindex_clip_tips.argtypes = [vp, vp, C.c_uint32, C.POINTER(u64), C.POINTER(u64)]
+        L.bbk_extindex_remove_at_edges.argtypes = [vp, vp, C.c_double, C.POINTER(u64), C.POINTER(u64)]
+        L.bbk_extindex_remove_at_tips.argtypes = [vp, vp, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(u64),
+                                                  C.POINTER(u64)]
         L.bbk_extindex_free.argtypes = [vp]
     if hasattr(L, "bbk_unitigs_build"):
         L.bbk_unitigs_build.argtypes = [vp, vp, C.POINTER(vp)]
@@ -578,6 +582,19 @@ class ExtIndex(_Handle):
         """EarlyTipClipperProcessor(index, length_bound).ClipTips() in place; returns (isolated k-mers, removed links)."""
         a, b = C.c_uint64(0), C.c_uint64(0)
         _check(self._L.bbk_extindex_clip_tips(self.ctx._h, self._h, length_bound, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def remove_at_edges(self, ratio=0.8):
+        """EarlyLowComplexityClipperProcessor::RemoveATEdges in place; returns (collected edges, removed links)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(self._L.bbk_extindex_remove_at_edges(self.ctx._h, self._h, ratio, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def remove_at_tips(self, ratio=0.8, min_len=10, max_len=200):
+        """EarlyLowComplexityClipperProcessor::RemoveATTips in place; returns (isolated k-mers, clipped links)."""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        _check(self._L.bbk_extindex_remove_at_tips(self.ctx._h, self._h, ratio, min_len, max_len, C.byref(a),
+                                                   C.byref(b)))
         return int(a.value), int(b.value)
 
     def export_to_u32(self, dst_keys, dst_masks_u32):

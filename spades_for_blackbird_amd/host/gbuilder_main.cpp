@@ -7,6 +7,8 @@
 // bbk_extindex_begin / push / finish (and, with -c, a (k+1)-mer counter), so host and device memory are bounded as in
 // the reference (binary read chunks + bounded sort buffers); -tmp-dir is accepted (there are no temp files).
 // --spades writes <output>.grseq + <output>.cvr (io::binary::BasicGraphIO::Save, :221-222).
+// --early-at-clip / --early-tip-clip <bound> (ours) run the main pipeline's early simplifications on the index before
+// the unitig stage: poly-A/T edges and tips, then tips (stages/construction.cpp:292-331).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -31,14 +33,17 @@ static void usage(const char *argv0) {
            "        --spades    produce graph in SPAdes internal format\n"
            "        --device <value>  GPU to use (default 0)\n"
            "        --devices <a,b,...>  GPUs to use: extension-index records sharded by k-mer owner over one RCCL all-to-all,\n"
-           "                    the shards gathered on the first device for the unitig stage (--exchange copy: peer copies)\n",
+           "                    the shards gathered on the first device for the unitig stage (--exchange copy: peer copies)\n"
+           "        --early-at-clip  remove poly-A/T edges and tips from the k-mer index (ratio 0.8, tips of 10..200)\n"
+           "        --early-tip-clip <value>  clip tips of at most <value> k-mers from the k-mer index\n",
            argv0);
 }
 
 int main(int argc, char **argv) {
     unsigned k = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull;  // projects/gbuilder/main.cpp:47-52
-    bool coverage = false, bad = false;
+    unsigned long long tip_bound = 0;
+    bool coverage = false, bad = false, at_clip = false, tip_clip = false;
     enum { UNITIGS, FASTG, GFA, SPADES } mode = UNITIGS;
     int modes_given = 0;
     std::vector<std::string> pos;
@@ -55,6 +60,8 @@ int main(int argc, char **argv) {
         else if (a == "--devices") { if (i + 1 < argc) devices_arg = argv[++i]; else bad = true; }
         else if (a == "--exchange") { if (i + 1 < argc) exchange_arg = argv[++i]; else bad = true; }
         else if (a == "-tmp-dir") { if (i + 1 < argc) ++i; else bad = true; }
+        else if (a == "--early-at-clip") at_clip = true;
+        else if (a == "--early-tip-clip") { if (need(&tip_bound) && tip_bound <= 0xFFFFFFFFull) tip_clip = true; else bad = true; }
         else if (a == "--unitigs") { mode = UNITIGS; ++modes_given; }
         else if (a == "--fastg") { mode = FASTG; ++modes_given; }
         else if (a == "--gfa") { mode = GFA; ++modes_given; }
@@ -169,6 +176,29 @@ int main(int argc, char **argv) {
     }
     info("K-mer counting done. There are %llu kmers in total.", (unsigned long long)bbk_extindex_size(ext));
     info("Building k-mer extensions from k+1-mers finished.");
+
+    // Early simplification on the final index, in the reference's phase order (stages/construction.cpp:469-482):
+    // EarlyATClipper (:320-331), then EarlyTipClipper (:292-305); the log lines are those of
+    // early_simplification.hpp:47-49,93,176-179,254,262-265,331
+    if (at_clip) {
+        uint64_t edges = 0, links = 0;
+        info("Remove short poly A/T edges");
+        check(bbk_extindex_remove_at_edges(ctx, ext, 0.8, &edges, &links), "bbk_extindex_remove_at_edges");
+        info("Links removed: %llu", (unsigned long long)links);
+        info("%llu %u-mers were removed by early poly A/T remover", (unsigned long long)edges, k + 1);
+        uint64_t kmers = 0;
+        info("Remove poly A/T tips");
+        check(bbk_extindex_remove_at_tips(ctx, ext, 0.8, 10, 200, &kmers, &links), "bbk_extindex_remove_at_tips");
+        info("Clipped tips: %llu", (unsigned long long)links);
+        info("%llu %u-mers were removed by early poly A/T tip clipper", (unsigned long long)kmers, k + 1);
+    }
+    if (tip_clip) {
+        uint64_t kmers = 0, links = 0;
+        info("Early tip clipping");
+        check(bbk_extindex_clip_tips(ctx, ext, (uint32_t)tip_bound, &kmers, &links), "bbk_extindex_clip_tips");
+        info("Clipped tips: %llu", (unsigned long long)links);
+        info("%llu %u-mers were removed by early tip clipper", (unsigned long long)kmers, k + 1);
+    }
 
     // Step 2: extract unbranching paths (:175-181)
     bbk_unitigs *u = nullptr;
