@@ -29,8 +29,8 @@
 // remaining prefix bits monotonically onto nb2 bins, so bucket order == prefix order.
 // Buckets larger than CAP (a k-mer repeated thousands of times, skewed composition in KEYS mode)
 // are finished by the LSD path, per bucket; if too much overflows the caller falls back entirely.
-// Environment knobs (tests / diagnostics): BBK_DISABLE_MSD, BBK_NO_SLOTS, BBK_SLOTS_MIN, BBK_NO_DIST,
-// BBK_PASS_LIMIT, BBK_NO_NARROW_B, BBK_VERBOSE; -DBBK_PHASE_PROF builds per-phase shader clocks into the kernels.
+// Environment knobs (tests / diagnostics): MsdKnobs lists them all; -DBBK_PHASE_PROF builds per-phase shader clocks
+// into the kernels.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -39,6 +39,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
+#include <type_traits>
 #include <vector>
 
 #include "bbk_internal.h"
@@ -2868,98 +2870,133 @@ struct BktCfg {
 // coverage), so its size varies far more than Poisson on the record count would suggest
 constexpr double kBucketFill = 0.70;
 
+static double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+static uint64_t env_u64(const char *v, uint64_t unset) { return v ? strtoull(v, nullptr, 10) : unset; }
+
+// Environment knobs of this file (tests, diagnostics and A/B switches); this is where all of them are read.
+struct MsdKnobs {
+    // Read once per process: the tests that change them start a fresh process.
+    struct PerProcess {
+        bool no_dist = getenv("BBK_NO_DIST") != nullptr;  // first bucket pass by the radix kernel, not k_bucket_dist
+        // tests: force the LDS table give-up on half-empty slots
+        uint32_t hash_max_probes = (uint32_t)env_u64(getenv("BBK_HASH_MAX_PROBES"), kHashMaxProbes);
+        uint64_t pass_limit = env_u64(getenv("BBK_PASS_LIMIT"), 0);  // records of one pass (0: from the bucket capacity);
+                                                                     // tests force range passes on small inputs
+        bool no_narrow = getenv("BBK_NO_NARROW") != nullptr;      // 8-byte records between the levels of stage A
+        bool xcd_slots = env_u64(getenv("BBK_XCD_SLOTS"), 1) != 0;  // 0: one level-1 fill front per segment, not per XCD
+        bool xcd_tiles = env_u64(getenv("BBK_XCD_TILES"), 1) != 0;  // 0: level-2 workgroups in plain tile order
+        bool no_narrow_b = getenv("BBK_NO_NARROW_B") != nullptr;  // 8-byte records after level 1 of stage B
+        // k_part_reads_narrow as that many persistent workgroups per CU (0: one workgroup per tile)
+        uint32_t nw_wgs_per_cu = (uint32_t)env_u64(getenv("BBK_NW_WGS_PER_CU"), 0);
+    };
+    const PerProcess &once = *[] {
+        static const PerProcess p;
+        return &p;
+    }();
+    // Read on every call: tests change them inside one process.
+    bool no_slots = getenv("BBK_NO_SLOTS") != nullptr;    // no histogram-free slot mode (HASH prefix)
+    bool no_kslots = getenv("BBK_NO_KSLOTS") != nullptr;  // no key slots (ordering pass of a distinct key array)
+    uint64_t slots_min = env_u64(getenv("BBK_SLOTS_MIN"), 1ull << 22);  // records below which neither slot mode runs
+    bool verbose = getenv("BBK_VERBOSE") != nullptr;      // "[bbk] msd ..." lines on stderr
+    bool no_direct = getenv("BBK_NO_DIRECT") != nullptr;  // no sorted output written by the bucket kernels (nor key slots)
+    bool no_level0 = getenv("BBK_NO_LEVEL0") != nullptr;  // key ranges selected from the whole input, no level-0 pass
+    bool no_part_kslots = getenv("BBK_NO_PART_KSLOTS") != nullptr;  // no key slots for the ranges level 0 materialised
+};
+
+// How one pass (MsdRunner::run) ended
+enum class Outcome {
+    Declined,        // not an input for this path: the caller uses the LSD path
+    Done,
+    TooBig,          // more records than one pass takes: run_all splits the input into ranges of the prefix space
+    SlotsGaveUp,     // the hash slot mode overflowed: exact histograms
+    KeySlotsGaveUp,  // the key slots of the ordering pass did not hold (skewed key space): exact histograms
+};
+
+// Records of a call: reads (rd, see msd_sort_reduce) or a key array (keys[, vals], n)
+struct MsdInput {
+    const bbk_reads *rd;
+    const void *keys;
+    const uint32_t *vals;
+    uint64_t n;
+    bool with_mask;
+};
+
+// f(std::integral_constant<int, OP>) for the runtime reduce op
+template <class F>
+static void with_op(int op, F &&f) {
+    switch (op) {
+        case MSD_OP_NONE: f(std::integral_constant<int, MSD_OP_NONE>()); break;
+        case MSD_OP_COUNT: f(std::integral_constant<int, MSD_OP_COUNT>()); break;
+        case MSD_OP_SUM: f(std::integral_constant<int, MSD_OP_SUM>()); break;
+        case MSD_OP_OR: f(std::integral_constant<int, MSD_OP_OR>()); break;
+        default: BBK_REQUIRE(false, BBK_ERR_ARG, "bad reduce op");
+    }
+}
+
 template <int W>
 struct MsdRunner {
+    static constexpr size_t rec = (size_t)W * 8;
+    static constexpr uint32_t kPartTileK = PartCfg<W>::TILE;
     bbk_ctx *ctx;
     unsigned k;
     int dmode;
-    int op;        // MSD_OP_*
-    bool in_vals;  // records carry a payload from the start (mask extraction or input counts)
+    int op;  // MSD_OP_*
     uint64_t strip_mask = ~0ull;  // tagged sort: bits of word 0 that survive in the output
-    bool slots_ok = getenv("BBK_NO_SLOTS") == nullptr;  // histogram-free slot mode allowed (HASH prefix)
-    bool kslots_ok = getenv("BBK_NO_KSLOTS") == nullptr;  // ... and for the ordering pass of a distinct key array
-    bool never_decline = false;  // finish whatever overflows bucket by bucket on the LSD path instead of declining
-    bool even_part = false;      // the call sorts a materialised range of an expanded input (run_level0): key slots apply
     bool assume_distinct = false;  // caller's hint (key arrays, KEYS / REF prefix): duplicates are not expected
     unsigned expand_k = 0;         // key-array input holds CANONICAL k-mers of this length: both strands are generated
     bool expand_tag = false;       // ... with the XXH3 bucket tag above the k-mer (the runner's k is then k + 2)
+    MsdKnobs knobs;
+    bool slots_ok = !knobs.no_slots;    // histogram-free slot mode allowed (HASH prefix)
+    bool kslots_ok = !knobs.no_kslots;  // ... and for the ordering pass of a distinct key array
+    bool never_decline = false;  // finish whatever overflows bucket by bucket on the LSD path instead of declining
+    bool even_part = false;      // the call sorts a materialised range of an expanded input (run_level0): key slots apply
 
-    template <bool HAS_VAL, bool HIST>
-    void launch_part(const char *fam, double bytes, uint32_t ntiles, const Key<W> *in, const uint32_t *vin, TileMap M,
-                     PartLevel L, uint32_t *ghist, uint32_t *cursor, Key<W> *out, uint32_t *vout) {
-        if (L.level == 1) launch_part_l<HAS_VAL, HIST, true>(fam, bytes, ntiles, in, vin, M, L, ghist, cursor, out, vout);
-        else launch_part_l<HAS_VAL, HIST, false>(fam, bytes, ntiles, in, vin, M, L, ghist, cursor, out, vout);
+    int w0bits() const { return (W == 1) ? (int)(2 * k) : 64; }
+
+    // Every timed kernel launch: LDS limit, timer, launch, check
+    template <class K, class... Args>
+    void launch(K fn, const char *name, double bytes, uint32_t grid, uint32_t threads, size_t lds, Args... args) {
+        if (lds)
+            BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds));
+        KernelTimer t(ctx, name, bytes);
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, ctx->stream, args...);
+        check_launch(name);
     }
 
+    // Partition pass over a key array at level 1 (LVL1; also the level-0 and planning passes) or 2: HIST only counts the
+    // bins into ghist, otherwise the records go to `cursor`, with their payloads when HAS_VAL
     template <bool HAS_VAL, bool HIST, bool LVL1, bool NOUT = false>
-    void launch_part_l(const char *fam, double bytes, uint32_t ntiles, const Key<W> *in, const uint32_t *vin, TileMap M,
-                       PartLevel L, uint32_t *ghist, uint32_t *cursor, Key<W> *out, uint32_t *vout) {
+    void launch_part(const char *fam, double bytes, uint32_t ntiles, const Key<W> *in, const uint32_t *vin, TileMap M,
+                     PartLevel L, uint32_t *ghist, uint32_t *cursor, Key<W> *out, uint32_t *vout) {
         if (ntiles == 0) return;
-        const size_t sm = part_smem(W, PartCfg<W>::TILE, HAS_VAL, HIST, LVL1);
-        auto fn = k_part<W, HAS_VAL, HIST, LVL1, NOUT>;
-        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)sm));
         M.ntiles = ntiles;
         M.group = HIST ? 16u : 1u;
         const uint32_t grid = (ntiles + M.group - 1) / M.group;
-        KernelTimer t(ctx, fam, bytes);
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(PartCfg<W>::THREADS), sm, ctx->stream, in, vin, M, L, ghist, cursor, out,
-                           vout);
-        check_launch(fam);
+        launch(k_part<W, HAS_VAL, HIST, LVL1, NOUT>, fam, bytes, grid, PartCfg<W>::THREADS,
+               part_smem(W, PartCfg<W>::TILE, HAS_VAL, HIST, LVL1), in, vin, M, L, ghist, cursor, out, vout);
     }
 
-    template <bool HAS_VAL, bool HIST>
-    void launch_part_reads(const char *fam, double bytes, uint32_t ntiles, ReadSrc S, PartLevel L, uint32_t *ghist,
-                           uint32_t *cursor, Key<W> *out, uint32_t *vout) {
+    // scatter of a key array, with the payloads when has_val
+    template <bool LVL1>
+    void scatter_keys(bool has_val, const char *fam, double bytes, uint32_t ntiles, const Key<W> *in, const uint32_t *vin,
+                      TileMap M, PartLevel L, uint32_t *cursor, Key<W> *out, uint32_t *vout) {
+        if (has_val) launch_part<true, false, LVL1>(fam, bytes, ntiles, in, vin, M, L, nullptr, cursor, out, vout);
+        else launch_part<false, false, LVL1>(fam, bytes, ntiles, in, nullptr, M, L, nullptr, cursor, out, nullptr);
+    }
+
+    // level-1 histogram (HIST, no payload) or scatter of reads
+    template <bool HIST>
+    void launch_part_reads(const char *fam, double bytes, uint32_t ntiles, bool has_val, ReadSrc S, PartLevel L,
+                           uint32_t *ghist, uint32_t *cursor, Key<W> *out, uint32_t *vout) {
         if (ntiles == 0) return;
-        const size_t sm = part_reads_smem(W, HAS_VAL, HIST);
-        auto fn = k_part_reads<W, HAS_VAL, HIST>;
-        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)sm));
+        auto fn = HIST ? k_part_reads<W, false, true> : has_val ? k_part_reads<W, true, false> : k_part_reads<W, false, false>;
         // histogram: ~8 resident-workgroup rounds, each workgroup walks its tiles and flushes once
         const uint32_t grid = HIST ? std::min<uint32_t>(ntiles, 8192u) : ntiles;
-        KernelTimer t(ctx, fam, bytes);
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(HIST ? kRdHistThreads : kRdThreads), sm, ctx->stream, S, L, ghist, cursor,
-                           out, vout);
-        check_launch(fam);
+        launch(fn, fam, bytes, grid, HIST ? kRdHistThreads : kRdThreads, part_reads_smem(W, has_val, HIST), S, L, ghist,
+               cursor, out, has_val ? vout : nullptr);
     }
 
-    // first pass: the one-pass distribution sort; second chance (SECOND): ballot-ranked radix passes, which
-    // take any key distribution and twice the records
-    template <bool SECOND, int OP>
-    void launch_bucket(uint32_t nblocks, Key<W> *buf, uint32_t *vals, BucketArgs A, double bytes) {
-        if (nblocks == 0) return;
-        constexpr int NT = SECOND ? BktCfg<W>::NT2 : BktCfg<W>::NT;
-        constexpr int IT = SECOND ? BktCfg<W>::ITEMS2 : BktCfg<W>::ITEMS;
-        static const bool no_dist = getenv("BBK_NO_DIST") != nullptr;  // A/B switch
-        const bool dist = !SECOND && !no_dist;
-        const size_t sm = dist ? bucket_dist_smem<W, NT, IT, OP>() : bucket_smem<W, NT, IT, OP>();
-        auto fn = dist ? k_bucket_dist<W, NT, IT, OP> : k_bucket<W, NT, IT, OP>;
-        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)sm));
-        KernelTimer t(ctx, dist ? "k_bucket_dist" : "k_bucket", bytes);
-        hipLaunchKernelGGL(fn, dim3(nblocks), dim3(NT), sm, ctx->stream, buf, vals, A);
-        check_launch("k_bucket");
-    }
-
-    template <int OP>
-    void launch_bucket_hash(uint32_t nblocks, Key<W> *buf, uint32_t *vals, BucketArgs A, double bytes) {
-        if constexpr (W == 1) {
-            if (nblocks == 0) return;
-            const size_t sm = bucket_hash_smem<OP>();
-            auto fn = k_bucket_hash<OP>;
-            BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)sm));
-            KernelTimer t(ctx, "k_bucket_hash", bytes);
-            hipLaunchKernelGGL(fn, dim3(nblocks), dim3(kHashThreads), sm, ctx->stream, buf, vals, A);
-            check_launch("k_bucket_hash");
-        }
-    }
-
-    static uint32_t hash_max_probes() {
-        static const char *e = getenv("BBK_HASH_MAX_PROBES");  // tests: force the table give-up on half-empty slots
-        return e ? (uint32_t)strtoul(e, nullptr, 10) : kHashMaxProbes;
-    }
     // unsorted dedup is enough when a later stage sorts the distinct records (HASH mode)
     bool use_hash_dedup() const { return W == 1 && dmode == MSD_HASH && 2 * k < 64; }
     bool use_hashidx_dedup() const { return W >= 2 && dmode == MSD_HASH; }
@@ -2970,58 +3007,40 @@ struct MsdRunner {
         return BktCfg<W>::CAP;
     }
 
-    template <int OP>
-    void launch_bucket_hashidx(uint32_t nblocks, Key<W> *buf, uint32_t *vals, BucketArgs A, double bytes) {
-        if constexpr (W >= 2) {
-            if (nblocks == 0) return;
-            const size_t sm = bucket_hashidx_smem<W, OP>();
-            auto fn = k_bucket_hashidx<W, OP>;
-            BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)sm));
-            KernelTimer t(ctx, "k_bucket_hashidx", bytes);
-            hipLaunchKernelGGL(fn, dim3(nblocks), dim3(kHashIdxThreads), sm, ctx->stream, buf, vals, A);
-            check_launch("k_bucket_hashidx");
-        }
-    }
-
+    // One workgroup per bucket: the LDS hash dedup (HASH prefix, allow_hash), else the sort -- first pass: the one-pass
+    // distribution sort; second chance (SECOND): ballot-ranked radix passes, which take any key distribution and twice
+    // the records
     template <bool SECOND>
     void bucket_dispatch(uint32_t nblocks, Key<W> *buf, uint32_t *vals, BucketArgs A, double bytes,
                          bool allow_hash = true) {
-        if (allow_hash && use_hashidx_dedup()) {
-            switch (op) {
-                case MSD_OP_NONE: launch_bucket_hashidx<0>(nblocks, buf, vals, A, bytes); return;
-                case MSD_OP_COUNT: launch_bucket_hashidx<1>(nblocks, buf, vals, A, bytes); return;
-                case MSD_OP_SUM: launch_bucket_hashidx<2>(nblocks, buf, vals, A, bytes); return;
-                case MSD_OP_OR: launch_bucket_hashidx<3>(nblocks, buf, vals, A, bytes); return;
-                default: BBK_REQUIRE(false, BBK_ERR_ARG, "bad reduce op");
+        with_op(op, [&](auto o) {
+            constexpr int OP = decltype(o)::value;
+            if (nblocks == 0) return;
+            if (allow_hash && use_hashidx_dedup()) {
+                if constexpr (W >= 2)
+                    launch(k_bucket_hashidx<W, OP>, "k_bucket_hashidx", bytes, nblocks, kHashIdxThreads,
+                           bucket_hashidx_smem<W, OP>(), buf, vals, A);
+            } else if (allow_hash && use_hash_dedup()) {
+                if constexpr (W == 1)
+                    launch(k_bucket_hash<OP>, "k_bucket_hash", bytes, nblocks, kHashThreads, bucket_hash_smem<OP>(), buf,
+                           vals, A);
+            } else {
+                constexpr int NT = SECOND ? BktCfg<W>::NT2 : BktCfg<W>::NT;
+                constexpr int IT = SECOND ? BktCfg<W>::ITEMS2 : BktCfg<W>::ITEMS;
+                const bool dist = !SECOND && !knobs.once.no_dist;
+                launch(dist ? k_bucket_dist<W, NT, IT, OP> : k_bucket<W, NT, IT, OP>, dist ? "k_bucket_dist" : "k_bucket",
+                       bytes, nblocks, NT, dist ? bucket_dist_smem<W, NT, IT, OP>() : bucket_smem<W, NT, IT, OP>(), buf,
+                       vals, A);
             }
-        }
-        if (allow_hash && use_hash_dedup()) {
-            switch (op) {
-                case MSD_OP_NONE: launch_bucket_hash<0>(nblocks, buf, vals, A, bytes); return;
-                case MSD_OP_COUNT: launch_bucket_hash<1>(nblocks, buf, vals, A, bytes); return;
-                case MSD_OP_SUM: launch_bucket_hash<2>(nblocks, buf, vals, A, bytes); return;
-                case MSD_OP_OR: launch_bucket_hash<3>(nblocks, buf, vals, A, bytes); return;
-                default: BBK_REQUIRE(false, BBK_ERR_ARG, "bad reduce op");
-            }
-        }
-        switch (op) {
-            case MSD_OP_NONE: launch_bucket<SECOND, 0>(nblocks, buf, vals, A, bytes); break;
-            case MSD_OP_COUNT: launch_bucket<SECOND, 1>(nblocks, buf, vals, A, bytes); break;
-            case MSD_OP_SUM: launch_bucket<SECOND, 2>(nblocks, buf, vals, A, bytes); break;
-            case MSD_OP_OR: launch_bucket<SECOND, 3>(nblocks, buf, vals, A, bytes); break;
-            default: BBK_REQUIRE(false, BBK_ERR_ARG, "bad reduce op");
-        }
+        });
     }
 
-    // returns false if the caller should use the LSD path instead (too much overflow)
     // records two partition levels can take in one pass (bins <= 512 x ~768 of 0.7 CAP records)
     // mean bucket fill the bin plan aims at.  Key arrays deduplicated through the LDS hash table (merge of received
     // shards / pushed batches: multiplicity 1..few) are nearly all distinct: keep the table's load around 0.5 there
     double plan_fill(bool from_reads) const { return (!from_reads && use_hash_dedup()) ? 0.52 : kBucketFill; }
     uint64_t pass_limit(bool from_reads) const {
-        static const char *e = getenv("BBK_PASS_LIMIT");  // tests force range passes on small inputs
-        if (e) return strtoull(e, nullptr, 10);
+        if (knobs.once.pass_limit) return knobs.once.pass_limit;
         return (uint64_t)(plan_fill(from_reads) * 512 * 0.75 * kMaxBins * bucket_cap() * 0.98);
     }
 
@@ -3046,142 +3065,80 @@ struct MsdRunner {
         uint32_t *vals = nullptr;
     };
 
-    // Returns 1 = done, 0 = declined (caller uses the LSD path), 2 = the input holds more records than one
-    // pass takes (*too_big set): run_all splits it into ranges of the prefix space.
-    int run(const bbk_reads *rd, const void *d_keys, const uint32_t *d_vals, uint64_t n_in, bool with_mask,
-            MsdOutput &out, Sel sel = Sel(), bool *too_big = nullptr, Dst dst = Dst()) {
-        constexpr uint32_t kPartTileK = PartCfg<W>::TILE;
-        const bool from_reads = rd != nullptr;
-        const bool has_val = with_mask || d_vals != nullptr;
-        const size_t rec = (size_t)W * 8;
-        const int w0bits = (W == 1) ? (int)(2 * k) : 64;
+    // What a pass decides before its first launch
+    struct Plan {
+        uint64_t N;     // records of the pass (a range: the planning estimate of its share)
+        uint64_t Ntot;  // instance space of the level-1 tiles
+        double target;  // bucket size the bin plan aims at
+        uint32_t nb1 = 1;  // level-1 bins, 2^b1
+        int b1 = 0;
+        bool too_deep;  // would need a third level: declined
+        int nw_hb;      // key bits above the low word (8-byte keys)
+        bool narrow, hslots, kslots, slots;
+        uint32_t rd_tile, ntiles1, ntiles1h;  // chunks of a read tile; level-1 tiles (scatter, reads histogram)
+        int xs;         // log2 of the level-1 sub-slots per segment (one per XCD)
+        uint32_t nsub, sub_cap, seg_cap, cap2, stride2, spill_cap;
+        size_t rec_ab;  // record width between the levels
+    };
 
-        // ---- instance space (reads: k-mers for the sizes, chunks for the level-1 tiles)
-        DevBuf coff, tile_read, unordered;
-        uint64_t N = (expand_k && rd == nullptr) ? 2 * n_in : n_in, n_chunks = 0;
-        if (from_reads) {
-            BBK_REQUIRE(dmode == MSD_HASH, BBK_ERR_INTERNAL, "reads are partitioned by hash prefix only");
-            DevBuf nk((rd->n + 1) * sizeof(uint64_t));
-            coff.alloc((rd->n + 1) * sizeof(uint64_t));
-            unordered.alloc(16);
-            BBK_HIP(hipMemsetAsync(unordered.p, 0, 16, ctx->stream));
-            if (rd->n) {
-                hipLaunchKernelGGL(k_kmers_per_read2, bbk::grid_blocks((rd->n + 255) / 256), dim3(256), 0, ctx->stream,
-                                   rd->d_len, rd->d_woff, rd->n, k, (uint32_t)RdCfg<W>::CH, nk.as<uint64_t>(),
-                                   coff.as<uint64_t>(), unordered.as<uint32_t>());
-                check_launch("k_kmers_per_read2");
-            }
-            N = exclusive_scan_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), rd->n);
-            n_chunks = exclusive_scan_u64(ctx, coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n);
-            BBK_HIP(hipMemcpyAsync(coff.as<uint64_t>() + rd->n, &n_chunks, sizeof(uint64_t), hipMemcpyHostToDevice,
-                                   ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));  // n_chunks is a stack variable
-        }
-        out.instances = N;
-        out.n = 0;
-        const bool has_dst = dst.keys != nullptr;
-        auto empty_out = [&]() {
-            if (!has_dst) {
-                out.keys.alloc(16);
-                out.vals.alloc(16);
-            }
-        };
-        if (N == 0) {
-            empty_out();
-            return 1;
-        }
+    // The bin plan and the mode of a pass of N records (n_chunks read chunks).  No HIP calls.
+    Plan plan(uint64_t N, uint64_t n_chunks, bool from_reads, bool has_val, const Sel &sel, bool has_dst) const {
+        Plan P;
         const bool ranged = sel.span != 0;
-        if (!ranged && N > pass_limit(from_reads) && too_big) {
-            *too_big = true;
-            return 2;
-        }
-        const uint64_t Ntot = N;        // instance space of the level-1 tiles
-        if (ranged) N = sel.est;        // planning estimate of this range's share (exact for KEYS / REF ranges)
+        P.Ntot = N;
+        P.N = N = ranged ? sel.est : N;
         // record offsets inside one pass are 32-bit; the input of a call may hold more (range passes walk the
         // 64-bit instance space once per range)
         BBK_REQUIRE(N < (1ull << 32) - kPartTileK, BBK_ERR_ARG,
                     "batch holds %llu records%s; one pass is limited to 2^32-1 (split the input)",
                     (unsigned long long)N, ranged ? " in one range of the prefix space" : "");
 
-        // ---- bin plan: nb1 (power of two) level-1 bins; level-2 bin counts are chosen per segment below
+        // ---- bin plan: nb1 (power of two) level-1 bins; level-2 bin counts are chosen per segment later
         const double fill = plan_fill(from_reads);
-        const double target = fill * bucket_cap();
-        const double want = std::max(1.0, std::ceil((double)N / target));
-        uint32_t nb1 = 1;
-        int b1 = 0;
-        while (nb1 < 512 && (double)nb1 * nb1 < want) {
-            nb1 <<= 1;
-            ++b1;
+        P.target = fill * bucket_cap();
+        const double want = std::max(1.0, std::ceil((double)N / P.target));
+        while (P.nb1 < 512 && (double)P.nb1 * P.nb1 < want) {
+            P.nb1 <<= 1;
+            ++P.b1;
         }
         // REF prefix: the 4 XXH3 bucket bits must be consumed before the buckets (a bucket is sorted by key alone
         // and may not hold records of two XXH3 buckets) -- by the range selection (a range inside one XXH3 bucket
         // shifts them all out: shl >= 4; run_all only makes wider ranges as aligned groups of 2^j whole buckets,
         // shl = 4 - j) and, for what is left, by level 1
         const int ref_bits = dmode == MSD_REF ? std::max(0, 4 - (ranged ? sel.shl : 0)) : 0;
-        if (b1 < ref_bits) {
-            b1 = ref_bits;
-            nb1 = 1u << b1;
+        if (P.b1 < ref_bits) {
+            P.b1 = ref_bits;
+            P.nb1 = 1u << P.b1;
         }
+        const bool u32_slots = (double)N / fill * 1.1 + (double)N < 4.2e9;  // slot offsets stay 32-bit
         // narrow stage A: reads, 8-byte keys of 33..42 bits, slot mode, one pass -> 4-byte records between the levels
         // (1024 level-1 segments whatever the size: the segment carries the key bits the record drops)
-        const char *smin_nw = getenv("BBK_SLOTS_MIN");
-        const uint64_t slots_min_nw = smin_nw ? strtoull(smin_nw, nullptr, 10) : (1ull << 22);
-        const int nw_hb = (int)(2 * k) - 32;
-        static const bool no_narrow = getenv("BBK_NO_NARROW") != nullptr;  // A/B switch
-        const bool narrow = W == 1 && from_reads && !ranged && !has_dst && nw_hb >= 1 && nw_hb <= 10 && slots_ok &&
-                            dmode == MSD_HASH && use_hash_dedup() && N >= slots_min_nw && !no_narrow &&
-                            (double)N / fill * 1.1 + (double)N < 4.2e9 && (double)N / kNwBins1 / target < 0.75 * kMaxBins;
-        if (narrow) {
-            b1 = 10;
-            nb1 = kNwBins1;
+        P.nw_hb = (int)(2 * k) - 32;
+        P.narrow = W == 1 && from_reads && !ranged && !has_dst && P.nw_hb >= 1 && P.nw_hb <= 10 && slots_ok &&
+                   dmode == MSD_HASH && use_hash_dedup() && N >= knobs.slots_min && !knobs.once.no_narrow && u32_slots &&
+                   (double)N / kNwBins1 / P.target < 0.75 * kMaxBins;
+        if (P.narrow) {
+            P.b1 = 10;
+            P.nb1 = kNwBins1;
         }
-        const bool verbose = getenv("BBK_VERBOSE") != nullptr;
-        if (want / nb1 > 0.75 * kMaxBins) {  // would need a third level: leave to the LSD path
-            if (verbose) fprintf(stderr, "[bbk] msd declines: N=%llu needs more than two levels\n", (unsigned long long)N);
-            return 0;
-        }
-        PartLevel L1{1, b1, nb1, dmode, w0bits, nullptr, nullptr, sel.lo, sel.span, sel.shl, sel.mul};
+        P.too_deep = want / P.nb1 > 0.75 * kMaxBins;
+        if (P.too_deep) return P;
 
         // level-1 tiles cover the whole instance space; a range pass keeps its share of every tile.  Reads:
         // a tile is `threads` chunks, so the histogram (512 threads) and the scatter (1024) have their own tables
-        const uint32_t rd_tile = narrow ? (uint32_t)(has_val ? NwCfg<true>::CHUNKS : NwCfg<false>::CHUNKS)
-                                        : (uint32_t)kRdThreads;  // chunks of a level-1 tile
-        const uint32_t ntiles1 = from_reads ? (uint32_t)((n_chunks + rd_tile - 1) / rd_tile)
-                                            : (uint32_t)((Ntot + kPartTileK - 1) / kPartTileK);
-        const uint32_t ntiles1h = (uint32_t)((n_chunks + kRdHistThreads - 1) / kRdHistThreads);
-        DevBuf tiles_h;
-        ReadSrc S{}, Sh{};
-        if (from_reads) {
-            tile_read.alloc(((size_t)ntiles1 + 1) * sizeof(RdTile));
-            tiles_h.alloc(((size_t)ntiles1h + 1) * sizeof(RdTile));
-            if (ntiles1) {
-                hipLaunchKernelGGL(k_tile_reads, dim3((ntiles1 + 255) / 256), dim3(256), 0, ctx->stream, coff.as<uint64_t>(),
-                                   rd->d_woff, rd->d_len, rd->n, (uint64_t)ntiles1, rd_tile,
-                                   (uint32_t)RdCfg<W>::CH, k, (uint32_t)kRdSlots, (uint32_t)kRdWords,
-                                   unordered.as<uint32_t>(), tile_read.as<RdTile>());
-                hipLaunchKernelGGL(k_tile_reads, dim3((ntiles1h + 255) / 256), dim3(256), 0, ctx->stream,
-                                   coff.as<uint64_t>(), rd->d_woff, rd->d_len, rd->n, (uint64_t)ntiles1h,
-                                   (uint32_t)kRdHistThreads, (uint32_t)RdCfg<W>::CH, k, (uint32_t)kRdSlots,
-                                   (uint32_t)kRdWords, unordered.as<uint32_t>(), tiles_h.as<RdTile>());
-                check_launch("k_tile_reads");
-            }
-            S = ReadSrc{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tile_read.as<RdTile>(), rd->n, n_chunks,
-                        (int)k};
-            Sh = S;
-            Sh.tiles = tiles_h.as<RdTile>();
-        }
-        TileMap M1{nullptr, nullptr, nullptr, 1, Ntot, 0, 1, nullptr, (int)expand_k, expand_tag ? 1 : 0};
+        P.rd_tile = P.narrow ? (uint32_t)(has_val ? NwCfg<true>::CHUNKS : NwCfg<false>::CHUNKS) : (uint32_t)kRdThreads;
+        P.ntiles1 = from_reads ? (uint32_t)((n_chunks + P.rd_tile - 1) / P.rd_tile)
+                               : (uint32_t)((P.Ntot + kPartTileK - 1) / kPartTileK);
+        P.ntiles1h = (uint32_t)((n_chunks + kRdHistThreads - 1) / kRdHistThreads);
 
         // ---- slot mode (HASH prefix + LDS hash dedup): no histogram passes.  The hash spreads the records evenly,
         // so every level-1 segment gets a fixed slot of the mean size + 1 % and every bucket a slot of the dedup
         // kernel's capacity; the scatter kernels reserve space with the same per-(tile, bin) atomics, records
         // that do not fit their slot go to a spill list, and whatever overflowed (spill list + the contents of the
         // overflowing segments / buckets, i.e. every record of the affected keys) is reprocessed by the exact path
-        // below on a key array.  Heavy repeats therefore cost a second pass over a small part of the data.
-        const char *smin = getenv("BBK_SLOTS_MIN");  // tests lower it to run the slot mode on small inputs
-        const uint64_t slots_min = smin ? strtoull(smin, nullptr, 10) : (1ull << 22);
-        const bool hslots = slots_ok && !has_dst && dmode == MSD_HASH && (use_hash_dedup() || use_hashidx_dedup()) && nb1 > 1 &&
-                            N >= slots_min && (double)N / fill * 1.1 + (double)N < 4.2e9;  // u32 slot offsets
+        // on a key array.  Heavy repeats therefore cost a second pass over a small part of the data.
+        P.hslots = slots_ok && !has_dst && dmode == MSD_HASH && (use_hash_dedup() || use_hashidx_dedup()) && P.nb1 > 1 &&
+                   N >= knobs.slots_min && u32_slots;
         // Stage B (ordering a distinct key array, KEYS / REF prefix, sorted result written directly): the same slots
         // instead of the two histogram passes.  The prefix is the key itself, so the spread is only as even as the
         // data: ANY record that misses its slot, any bucket the sort kernel turns down, any duplicate sends the call
@@ -3191,134 +3148,269 @@ struct MsdRunner {
         // extension-index build: 3.8 ms of a 30 ms build spent on an attempt that never holds)
         // (even_part: a materialised range of an expanded input -- run_level0 -- is as evenly spread, holds exactly
         // sel.est records and writes into its place of the final array)
-        const bool kslots = kslots_ok && slots_ok && (even_part || (!has_dst && !ranged && expand_k != 0)) && !from_reads &&
-                            assume_distinct && (dmode == MSD_KEYS || dmode == MSD_REF) && nb1 > 1 && N >= slots_min &&
-                            getenv("BBK_NO_DIRECT") == nullptr && (double)N / fill * 1.1 + (double)N < 4.2e9;
-        const bool slots = hslots || kslots;
-        BBK_REQUIRE(!narrow || slots, BBK_ERR_INTERNAL, "narrow records need the slot mode");
+        P.kslots = kslots_ok && slots_ok && (even_part || (!has_dst && !ranged && expand_k != 0)) && !from_reads &&
+                   assume_distinct && (dmode == MSD_KEYS || dmode == MSD_REF) && P.nb1 > 1 && N >= knobs.slots_min &&
+                   !knobs.no_direct && u32_slots;
+        P.slots = P.hslots || P.kslots;
+        BBK_REQUIRE(!P.narrow || P.slots, BBK_ERR_INTERNAL, "narrow records need the slot mode");
         // narrow level 1: one sub-slot (and cursor) per XCD inside every segment slot (PartLevel::xcd_shift); the XCDs do
         // not take exactly equal shares of the tiles, so the sub-slots get 6 % + 2048 records of slack.
         // A 128-byte line of a segment that workgroups on DIFFERENT XCDs fill (their ~60-byte runs are adjacent) is
         // what makes this kernel's store pattern slow: tools/probes/reserve_scatter_probe.hip replays the pattern
         // without any arithmetic -- 3.8 ms with one fill front per segment, 2.1 ms with one per (segment, XCD), 6.4 ms
         // when adjacent runs ALWAYS come from different XCDs.  The kernel itself: 3.64 -> 2.94 ms (same call, round 3;
-        // in round 2 its arithmetic took as long as the stores and hid the gain: 3.96 -> 3.79).  BBK_XCD_SLOTS=0: A/B.
-        static const bool use_xcd = !(getenv("BBK_XCD_SLOTS") && atoi(getenv("BBK_XCD_SLOTS")) == 0);
-        const int xs = (slots && use_xcd && ctx->num_xcds == 8) ? 3 : 0;
-        const uint32_t nsub = nb1 << xs;  // level-1 cursors = level-2 input segments
-        const uint32_t sub_cap = xs ? ((uint32_t)((double)N / nsub * 1.06) + 2048u) | 1u : 0u;
-        const uint32_t seg_cap = !slots ? 0u
-                                 : xs ? sub_cap << xs
-                                      : ((uint32_t)((double)N / nb1 * (kslots ? 1.06 : 1.01)) + 8192u) | 1u;
-        const uint32_t cap2 = narrow ? (uint32_t)(kNwHashThreads * kNwHashItems) : bucket_cap();
+        // in round 2 its arithmetic took as long as the stores and hid the gain: 3.96 -> 3.79).
+        P.xs = (P.slots && knobs.once.xcd_slots && ctx->num_xcds == 8) ? 3 : 0;
+        P.nsub = P.nb1 << P.xs;  // level-1 cursors = level-2 input segments
+        P.sub_cap = P.xs ? ((uint32_t)((double)N / P.nsub * 1.06) + 2048u) | 1u : 0u;
+        P.seg_cap = !P.slots ? 0u
+                    : P.xs   ? P.sub_cap << P.xs
+                             : ((uint32_t)((double)N / P.nb1 * (P.kslots ? 1.06 : 1.01)) + 8192u) | 1u;
+        P.cap2 = P.narrow ? (uint32_t)(kNwHashThreads * kNwHashItems) : bucket_cap();
         // bucket slots 256 B further apart than their capacity: with a power-of-two-ish stride every bucket's
         // fill front sits in the same HBM channel (level-2 scatter measured 10 % slower)
-        const size_t rec_ab = narrow ? 4 : rec;  // record width between the levels
-        const uint32_t stride2 = cap2 + (uint32_t)(256 / rec_ab);
+        P.rec_ab = P.narrow ? 4 : rec;
+        P.stride2 = P.cap2 + (uint32_t)(256 / P.rec_ab);
+        P.spill_cap = P.slots ? (uint32_t)(N / 8 + 65536) : 0u;
+        return P;
+    }
+
+    // One pass: the buffers and host arrays that cross its phases.  The host arrays are also the sources of
+    // asynchronous copies and must live until a later synchronisation, so they live as long as the pass.
+    struct Pass {
+        static constexpr uint32_t kFlagCap = 65536;  // flagged buckets the first pass can list
+        MsdRunner &R;
+        bbk_ctx *ctx;
+        const MsdInput &in;
+        MsdOutput &out;
+        const Sel sel;
+        const Dst dst;
+        const bool from_reads, has_val, ranged, has_dst, out_vals, need_vbuf, verbose;
+        Plan P{};
+        uint64_t N = 0, n_chunks = 0;  // records of the pass (a range: exact once level 1 has counted them); read chunks
+        DevBuf coff, tile_read, unordered, tiles_h;
+        ReadSrc S{}, Sh{};
+        TileMap M1{}, M2{};
+        PartLevel L1{}, L2{};
         DevBuf spill_k, spill_v, spill_n;  // spill_n: u32 counters [0] spilled records [1] unused [2] buckets left to the caller
-        const uint32_t spill_cap = slots ? (uint32_t)(N / 8 + 65536) : 0u;
-        if (slots) {
-            spill_k.alloc((size_t)spill_cap * rec);
-            if (has_val) spill_v.alloc((size_t)spill_cap * 4);
-            spill_n.alloc(16);
-            BBK_HIP(hipMemsetAsync(spill_n.p, 0, 16, ctx->stream));
-            L1.slot_cap = seg_cap;
-            L1.slot_stride = seg_cap;
-            L1.spill_keys = spill_k.p;
-            L1.spill_vals = spill_v.as<uint32_t>();
-            L1.spill_count = spill_n.as<uint32_t>();
-            L1.spill_cap = spill_cap;
-            L1.narrow_hb = narrow ? nw_hb : 0;
-            L1.xcd_shift = xs;
-            L1.sub_cap = sub_cap;
-        }
-
-        // ---- level 1: histogram (exact mode), offsets, scatter
-        // (off1 / tstart / hsub are per level-1 CURSOR: per segment, or per (segment, XCD) sub-slot on the narrow path)
-        DevBuf hist1((size_t)nb1 * 4 + 16), cur1((size_t)nsub * 4 + 16);
-        const Key<W> *kin = (const Key<W> *)d_keys;
-        std::vector<uint32_t> h1(nb1), off1(nsub + 1), tstart(nsub + 1), snb2(nb1), sbin(nb1 + 1), hsub(nsub), fill1(nsub);
+        // level 1 (off1 / tstart / hsub are per level-1 CURSOR: per segment, or per (segment, XCD) sub-slot on the
+        // narrow path)
+        DevBuf hist1, cur1, bufA, valA;
+        uint32_t n32 = 0;
+        std::vector<uint32_t> h1, off1, tstart, snb2, sbin, hsub, fill1;
         std::vector<uint32_t> over_seg;  // slot mode: segments that ran over (reprocessed as a whole)
-        if (!slots) {
-            BBK_HIP(hipMemsetAsync(hist1.p, 0, (size_t)nb1 * 4 + 16, ctx->stream));
-            if (nb1 > 1 || ranged) {
-                const double hb = from_reads ? (double)rd->n_words * 8 : (double)N * rec;
-                if (from_reads) {
-                    launch_part_reads<false, true>("k_part_reads_hist", hb, ntiles1h, Sh, L1, hist1.as<uint32_t>(), nullptr, nullptr, nullptr);
-                } else {
-                    launch_part<false, true>("k_part_hist1", hb, ntiles1, kin, nullptr, M1, L1, hist1.as<uint32_t>(), nullptr, nullptr, nullptr);
-                }
-            } else {
-                const uint32_t n32 = (uint32_t)N;
-                BBK_HIP(hipMemcpyAsync(hist1.p, &n32, 4, hipMemcpyHostToDevice, ctx->stream));
-            }
-            BBK_HIP(hipMemcpyAsync(h1.data(), hist1.p, (size_t)nb1 * 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            off1[0] = 0;
-            for (uint32_t b = 0; b < nb1; ++b) off1[b + 1] = off1[b] + h1[b];
-            if (ranged) {
-                N = off1[nb1];  // the records of this range
-                out.instances = N;
-            }
-            BBK_REQUIRE(off1[nb1] == (uint32_t)N, BBK_ERR_INTERNAL, "level-1 histogram does not add up (%u vs %llu)",
-                        off1[nb1], (unsigned long long)N);
-            if (N == 0) {
-                empty_out();
-                return 1;
-            }
-        } else {
-            BBK_REQUIRE((uint64_t)nb1 * seg_cap + N < (1ull << 32), BBK_ERR_INTERNAL, "slot layout exceeds 32-bit offsets");
-            for (uint32_t s2 = 0; s2 <= nsub; ++s2)
-                off1[s2] = xs ? (s2 >> xs) * seg_cap + (s2 & ((1u << xs) - 1u)) * sub_cap : s2 * seg_cap;
-        }
-        BBK_HIP(hipMemcpyAsync(cur1.p, off1.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
+        // level 2
+        uint32_t nbuckets = 0, ntiles2 = 0, nwg2 = 0;
+        bool narrow_b = false;
+        DevBuf seg_tile, seg_off, seg_nb2, seg_bin, seg_size, xstart_d, desc2, desc2h, hist2, boff, bufB, valB;
+        std::vector<uint32_t> xstart;
+        // buckets
+        DevBuf dcount, dbg, dupf, slot_off, bseg, bbase, flag_ids, flag_n;  // bbase: narrow stage B, smallest key of a bucket
+        std::vector<uint16_t> h_bseg;
+        BucketArgs A{};
+        bool direct = false;
+        uint32_t ctr[4] = {0, 0, 0, 0};  // spilled, direct, flagged, duplicates seen by the direct pass
+        std::vector<uint32_t> flagged, hd, hb;  // exact mode with flagged buckets (or verbose): per-bucket counts / offsets
+        std::vector<uint32_t> big;
+        uint32_t hbo[2] = {0, 0};
+        MsdOutput extra;  // slot mode: distinct records of everything that overflowed
+        uint64_t novf = 0;
 
-        const uint64_t nA = slots ? (uint64_t)nb1 * seg_cap : N;  // records bufA holds (slot layout has gaps)
-        DevBuf bufA(nA * rec_ab), bufB, valA, valB;
-        const bool need_vbuf = has_val || op != MSD_OP_NONE;
-        if (has_val) valA.alloc(nA * 4);
-        {
-            const double pb = (from_reads ? (double)rd->n_words * 8 : (double)N * (rec + (has_val ? 4 : 0))) +
-                              (double)N * (rec + (has_val ? 4 : 0));
-            if (narrow) {
+        Pass(MsdRunner &r, const MsdInput &i, MsdOutput &o, const Sel &s, Dst d)
+            : R(r), ctx(r.ctx), in(i), out(o), sel(s), dst(d), from_reads(i.rd != nullptr),
+              has_val(i.with_mask || i.vals != nullptr), ranged(s.span != 0), has_dst(d.keys != nullptr),
+              out_vals(r.op != MSD_OP_NONE), need_vbuf(has_val || out_vals), verbose(r.knobs.verbose) {}
+
+        double rec_bytes(uint64_t n) const { return (double)n * (rec + (has_val ? 4 : 0)); }
+        uint32_t *vals_or_null(DevBuf &b) const { return has_val ? b.as<uint32_t>() : nullptr; }
+
+        // n_records: the whole input may be split into ranges; TooBig then gives its record count
+        Outcome run(uint64_t *n_records = nullptr) {
+            count_instances();
+            out.instances = N;
+            out.n = 0;
+            if (N == 0) return empty();
+            if (!ranged && n_records && N > R.pass_limit(from_reads)) {
+                *n_records = N;
+                return Outcome::TooBig;
+            }
+            P = R.plan(N, n_chunks, from_reads, has_val, sel, has_dst);
+            N = P.N;
+            if (P.too_deep) {  // leave to the LSD path
+                if (verbose) fprintf(stderr, "[bbk] msd declines: N=%llu needs more than two levels\n", (unsigned long long)N);
+                return Outcome::Declined;
+            }
+            level1_tiles();
+            if (auto r = level1()) return *r;
+            level2_layout();
+            level2_scatter();
+            if (auto r = first_pass()) return *r;
+            if (auto r = overflow()) return *r;
+            compact();
+            return Outcome::Done;
+        }
+
+        Outcome empty() {
+            if (!has_dst) {
+                out.keys.alloc(16);
+                out.vals.alloc(16);
+            }
+            return Outcome::Done;
+        }
+
+        // ---- instance space (reads: k-mers for the sizes, chunks for the level-1 tiles)
+        void count_instances() {
+            N = (R.expand_k && !from_reads) ? 2 * in.n : in.n;
+            if (!from_reads) return;
+            const bbk_reads *rd = in.rd;
+            BBK_REQUIRE(R.dmode == MSD_HASH, BBK_ERR_INTERNAL, "reads are partitioned by hash prefix only");
+            DevBuf nk((rd->n + 1) * sizeof(uint64_t));
+            coff.alloc((rd->n + 1) * sizeof(uint64_t));
+            unordered.alloc(16);
+            BBK_HIP(hipMemsetAsync(unordered.p, 0, 16, ctx->stream));
+            if (rd->n) {
+                hipLaunchKernelGGL(k_kmers_per_read2, bbk::grid_blocks((rd->n + 255) / 256), dim3(256), 0, ctx->stream,
+                                   rd->d_len, rd->d_woff, rd->n, R.k, (uint32_t)RdCfg<W>::CH, nk.as<uint64_t>(),
+                                   coff.as<uint64_t>(), unordered.as<uint32_t>());
+                check_launch("k_kmers_per_read2");
+            }
+            N = exclusive_scan_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), rd->n);
+            n_chunks = exclusive_scan_u64(ctx, coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n);
+            BBK_HIP(hipMemcpyAsync(coff.as<uint64_t>() + rd->n, &n_chunks, sizeof(uint64_t), hipMemcpyHostToDevice,
+                                   ctx->stream));
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+
+        // ---- level-1 tiles (reads) and the slot layout
+        void level1_tiles() {
+            L1 = PartLevel{1, P.b1, P.nb1, R.dmode, R.w0bits(), nullptr, nullptr, sel.lo, sel.span, sel.shl, sel.mul};
+            if (from_reads) {
+                const bbk_reads *rd = in.rd;
+                tile_read.alloc(((size_t)P.ntiles1 + 1) * sizeof(RdTile));
+                tiles_h.alloc(((size_t)P.ntiles1h + 1) * sizeof(RdTile));
+                if (P.ntiles1) {
+                    hipLaunchKernelGGL(k_tile_reads, dim3((P.ntiles1 + 255) / 256), dim3(256), 0, ctx->stream,
+                                       coff.as<uint64_t>(), rd->d_woff, rd->d_len, rd->n, (uint64_t)P.ntiles1, P.rd_tile,
+                                       (uint32_t)RdCfg<W>::CH, R.k, (uint32_t)kRdSlots, (uint32_t)kRdWords,
+                                       unordered.as<uint32_t>(), tile_read.as<RdTile>());
+                    hipLaunchKernelGGL(k_tile_reads, dim3((P.ntiles1h + 255) / 256), dim3(256), 0, ctx->stream,
+                                       coff.as<uint64_t>(), rd->d_woff, rd->d_len, rd->n, (uint64_t)P.ntiles1h,
+                                       (uint32_t)kRdHistThreads, (uint32_t)RdCfg<W>::CH, R.k, (uint32_t)kRdSlots,
+                                       (uint32_t)kRdWords, unordered.as<uint32_t>(), tiles_h.as<RdTile>());
+                    check_launch("k_tile_reads");
+                }
+                S = ReadSrc{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tile_read.as<RdTile>(), rd->n,
+                            n_chunks, (int)R.k};
+                Sh = S;
+                Sh.tiles = tiles_h.as<RdTile>();
+            }
+            M1 = TileMap{nullptr, nullptr, nullptr, 1, P.Ntot, 0, 1, nullptr, (int)R.expand_k, R.expand_tag ? 1 : 0};
+            if (P.slots) {
+                spill_k.alloc((size_t)P.spill_cap * rec);
+                if (has_val) spill_v.alloc((size_t)P.spill_cap * 4);
+                spill_n.alloc(16);
+                BBK_HIP(hipMemsetAsync(spill_n.p, 0, 16, ctx->stream));
+                use_slots(L1, P.seg_cap, P.seg_cap);
+                L1.xcd_shift = P.xs;
+                L1.sub_cap = P.sub_cap;
+            }
+        }
+
+        // slot mode: the bins of level L own slots of `cap` records, `stride` apart; what misses its slot is spilled
+        void use_slots(PartLevel &L, uint32_t cap, uint32_t stride) {
+            L.slot_cap = cap;
+            L.slot_stride = stride;
+            L.spill_keys = spill_k.p;
+            L.spill_vals = spill_v.as<uint32_t>();
+            L.spill_count = spill_n.as<uint32_t>();
+            L.spill_cap = P.spill_cap;
+            L.narrow_hb = P.narrow ? P.nw_hb : 0;
+        }
+
+        // ---- level 1: histogram (exact mode) or slot offsets, scatter
+        std::optional<Outcome> level1() {
+            const uint32_t nb1 = P.nb1, nsub = P.nsub;
+            hist1.alloc((size_t)nb1 * 4 + 16);
+            cur1.alloc((size_t)nsub * 4 + 16);
+            h1.resize(nb1);
+            off1.resize(nsub + 1);
+            tstart.resize(nsub + 1);
+            snb2.resize(nb1);
+            sbin.resize(nb1 + 1);
+            hsub.resize(nsub);
+            fill1.resize(nsub);
+            if (!P.slots) {
+                BBK_HIP(hipMemsetAsync(hist1.p, 0, (size_t)nb1 * 4 + 16, ctx->stream));
+                if (nb1 > 1 || ranged) {
+                    const double hb = from_reads ? (double)in.rd->n_words * 8 : (double)N * rec;
+                    if (from_reads)
+                        R.template launch_part_reads<true>("k_part_reads_hist", hb, P.ntiles1h, false, Sh, L1,
+                                                           hist1.as<uint32_t>(), nullptr, nullptr, nullptr);
+                    else
+                        R.template launch_part<false, true, true>("k_part_hist1", hb, P.ntiles1, (const Key<W> *)in.keys, nullptr,
+                                                            M1, L1, hist1.as<uint32_t>(), nullptr, nullptr, nullptr);
+                } else {
+                    n32 = (uint32_t)N;
+                    BBK_HIP(hipMemcpyAsync(hist1.p, &n32, 4, hipMemcpyHostToDevice, ctx->stream));
+                }
+                BBK_HIP(hipMemcpyAsync(h1.data(), hist1.p, (size_t)nb1 * 4, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                off1[0] = 0;
+                for (uint32_t b = 0; b < nb1; ++b) off1[b + 1] = off1[b] + h1[b];
+                if (ranged) {
+                    N = off1[nb1];  // the records of this range
+                    out.instances = N;
+                }
+                BBK_REQUIRE(off1[nb1] == (uint32_t)N, BBK_ERR_INTERNAL, "level-1 histogram does not add up (%u vs %llu)",
+                            off1[nb1], (unsigned long long)N);
+                if (N == 0) return empty();
+            } else {
+                BBK_REQUIRE((uint64_t)nb1 * P.seg_cap + N < (1ull << 32), BBK_ERR_INTERNAL,
+                            "slot layout exceeds 32-bit offsets");
+                for (uint32_t s2 = 0; s2 <= nsub; ++s2)
+                    off1[s2] = P.xs ? (s2 >> P.xs) * P.seg_cap + (s2 & ((1u << P.xs) - 1u)) * P.sub_cap : s2 * P.seg_cap;
+            }
+            BBK_HIP(hipMemcpyAsync(cur1.p, off1.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
+
+            const uint64_t nA = P.slots ? (uint64_t)nb1 * P.seg_cap : N;  // records bufA holds (slot layout has gaps)
+            bufA.alloc(nA * P.rec_ab);
+            if (has_val) valA.alloc(nA * 4);
+            if (P.narrow) {
                 if constexpr (W == 1) {
-                    const double pbn = (double)rd->n_words * 8 + (double)N * (4 + (has_val ? 4 : 0));
-                    const size_t sm = part_reads_narrow_smem(has_val);
+                    const double pbn = (double)in.rd->n_words * 8 + (double)N * (4 + (has_val ? 4 : 0));
                     // One tile per workgroup.  The kernel can also run as persistent workgroups that walk every grid-th
                     // tile and load the next tile's tables during the stores of the current one
                     // (BBK_NW_WGS_PER_CU=2): measured slower in the same call, 3.38-3.46 ms against 2.94 -- the wait
                     // for the loaded tables at the top of the loop is also a wait for the tile's stores, and the
                     // hardware dispatcher balances the tiles better than a static stride.
-                    static const uint32_t per_cu = getenv("BBK_NW_WGS_PER_CU") ? (uint32_t)atoi(getenv("BBK_NW_WGS_PER_CU")) : 0u;
-                    const uint32_t grid = per_cu ? std::min<uint32_t>(ntiles1, (uint32_t)ctx->num_cus * per_cu) : ntiles1;
-                    KernelTimer t(ctx, "k_part_reads_narrow", pbn);
-                    if (has_val) {
-                        auto fn = k_part_reads_narrow<true>;
-                        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-                        hipLaunchKernelGGL(fn, dim3(grid), dim3(kNwThreads), sm, ctx->stream, S, L1, ntiles1, S.tiles, cur1.as<uint32_t>(), bufA.as<uint32_t>(), valA.as<uint32_t>());
-                    } else {
-                        auto fn = k_part_reads_narrow<false>;
-                        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-                        hipLaunchKernelGGL(fn, dim3(grid), dim3(kNwThreads), sm, ctx->stream, S, L1, ntiles1, S.tiles, cur1.as<uint32_t>(), bufA.as<uint32_t>(), (uint32_t *)nullptr);
-                    }
-                    check_launch("k_part_reads_narrow");
+                    const uint32_t per_cu = R.knobs.once.nw_wgs_per_cu;
+                    const uint32_t grid = per_cu ? std::min<uint32_t>(P.ntiles1, (uint32_t)ctx->num_cus * per_cu) : P.ntiles1;
+                    R.launch(has_val ? k_part_reads_narrow<true> : k_part_reads_narrow<false>, "k_part_reads_narrow", pbn,
+                             grid, kNwThreads, part_reads_narrow_smem(has_val), S, L1, P.ntiles1, S.tiles,
+                             cur1.as<uint32_t>(), bufA.as<uint32_t>(), vals_or_null(valA));
                 }
-            } else if (from_reads) {
-                if (has_val) launch_part_reads<true, false>("k_part_reads", pb, ntiles1, S, L1, nullptr, cur1.as<uint32_t>(), bufA.as<Key<W>>(), valA.as<uint32_t>());
-                else launch_part_reads<false, false>("k_part_reads", pb, ntiles1, S, L1, nullptr, cur1.as<uint32_t>(), bufA.as<Key<W>>(), nullptr);
             } else {
-                if (has_val) launch_part<true, false>("k_part_l1", pb, ntiles1, kin, d_vals, M1, L1, nullptr, cur1.as<uint32_t>(), bufA.as<Key<W>>(), valA.as<uint32_t>());
-                else launch_part<false, false>("k_part_l1", pb, ntiles1, kin, nullptr, M1, L1, nullptr, cur1.as<uint32_t>(), bufA.as<Key<W>>(), nullptr);
+                const double pb = (from_reads ? (double)in.rd->n_words * 8 : rec_bytes(N)) + rec_bytes(N);
+                if (from_reads)
+                    R.template launch_part_reads<false>("k_part_reads", pb, P.ntiles1, has_val, S, L1, nullptr,
+                                                        cur1.as<uint32_t>(), bufA.as<Key<W>>(), valA.as<uint32_t>());
+                else
+                    R.template scatter_keys<true>(has_val, "k_part_l1", pb, P.ntiles1, (const Key<W> *)in.keys, in.vals, M1, L1,
+                                   cur1.as<uint32_t>(), bufA.as<Key<W>>(), valA.as<uint32_t>());
             }
+            if (P.slots) return slot_fills();
+            return std::nullopt;
         }
-        if (slots) {
-            // the cursors tell what every segment received
+
+        // slot mode: the level-1 cursors tell what every segment received
+        std::optional<Outcome> slot_fills() {
+            const uint32_t nsub = P.nsub, xs = P.xs;
             std::vector<uint32_t> c1(nsub);
             BBK_HIP(hipMemcpyAsync(c1.data(), cur1.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, ctx->stream));
             BBK_HIP(hipStreamSynchronize(ctx->stream));
             uint64_t got = 0;
-            const uint32_t cap1 = xs ? sub_cap : seg_cap;
-            for (uint32_t b = 0; b < nb1; ++b) {
+            const uint32_t cap1 = xs ? P.sub_cap : P.seg_cap;
+            for (uint32_t b = 0; b < P.nb1; ++b) {
                 bool over = false;
                 uint32_t tot = 0;
                 for (uint32_t s2 = b << xs; s2 < (b + 1) << xs; ++s2) {
@@ -3333,21 +3425,21 @@ struct MsdRunner {
                 h1[b] = over ? 0u : tot;
                 for (uint32_t s2 = b << xs; s2 < (b + 1) << xs; ++s2) hsub[s2] = over ? 0u : fill1[s2];
             }
-            if (got > Ntot) {  // cannot be: every instance reserves one place.  Say what was read before failing
+            if (got > P.Ntot) {  // cannot be: every instance reserves one place.  Say what was read before failing
                 std::vector<uint32_t> c2(nsub);
                 BBK_HIP(hipMemcpyAsync(c2.data(), cur1.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, ctx->stream));
                 BBK_HIP(hipStreamSynchronize(ctx->stream));
                 uint32_t shown = 0, differ = 0;
                 for (uint32_t b = 0; b < nsub; ++b) differ += c1[b] != c2[b];
                 for (uint32_t b = 0; b < nsub && shown < 8; ++b)
-                    if (c1[b] - off1[b] > 2 * seg_cap) {
+                    if (c1[b] - off1[b] > 2 * P.seg_cap) {
                         fprintf(stderr, "[bbk] level-1 cursor %u: start %u now %u (second read %u), slot capacity %u\n", b,
-                                off1[b], c1[b], c2[b], seg_cap);
+                                off1[b], c1[b], c2[b], P.seg_cap);
                         ++shown;
                     }
                 fprintf(stderr, "[bbk] level-1 cursors: %u of %u differ between two reads; cur1 at %p\n", differ, nsub, cur1.p);
                 BBK_REQUIRE(false, BBK_ERR_INTERNAL, "level-1 reservations exceed the instance space (%llu vs %llu)",
-                            (unsigned long long)got, (unsigned long long)Ntot);
+                            (unsigned long long)got, (unsigned long long)P.Ntot);
             }
             if (ranged) {
                 N = got;
@@ -3355,297 +3447,211 @@ struct MsdRunner {
             }
             BBK_REQUIRE(got == N, BBK_ERR_INTERNAL, "level-1 reservations do not add up (%llu vs %llu)",
                         (unsigned long long)got, (unsigned long long)N);
-            if (N == 0) {
-                empty_out();
-                return 1;
-            }
-            if (kslots && !over_seg.empty()) {
+            if (N == 0) return empty();
+            if (P.kslots && !over_seg.empty()) {
                 if (verbose) fprintf(stderr, "[bbk] msd key slots: %zu segments overflow, exact mode\n", over_seg.size());
-                return 4;
+                return Outcome::KeySlotsGaveUp;
             }
+            return std::nullopt;
         }
-        if (!slots)
-            for (uint32_t b = 0; b < nb1; ++b) hsub[b] = h1[b];  // exact mode: one dense run per segment
-        tstart[0] = 0;
-        sbin[0] = 0;
-        const uint32_t tile2 = narrow ? (uint32_t)(has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE) : kPartTileK;
-        for (uint32_t s2 = 0; s2 < nsub; ++s2) tstart[s2 + 1] = tstart[s2] + (hsub[s2] + tile2 - 1) / tile2;
-        for (uint32_t b = 0; b < nb1; ++b) {
-            snb2[b] = (uint32_t)std::min<double>(kMaxBins, std::max(1.0, std::ceil((double)h1[b] / target)));
-            sbin[b + 1] = sbin[b] + snb2[b];
-        }
-        const uint32_t nbuckets = sbin[nb1];
 
-        // narrow stage B (see k_bucket_base): key slots (which imply the direct output), one whole pass, no payload, KEYS
-        // prefix, and no bucket spanning more than 2^32 keys -- then only the keys' low words travel after level 1
-        static const bool no_narrow_b = getenv("BBK_NO_NARROW_B") != nullptr;  // A/B switch
-        uint64_t span_b = 0;  // widest bucket, in keys
-        for (uint32_t b = 0; b < nb1; ++b)
-            if (h1[b]) {
-                const uint64_t P = 1ull << (32 - b1), q = (P + snb2[b] - 1) / snb2[b];
-                span_b = std::max(span_b, w0bits > 32 ? q << (w0bits - 32) : q >> (32 - w0bits));
+        // ---- level-2 layout: bins per segment, tile descriptors
+        void level2_layout() {
+            const uint32_t nb1 = P.nb1, nsub = P.nsub, xs = P.xs;
+            if (!P.slots)
+                for (uint32_t b = 0; b < nb1; ++b) hsub[b] = h1[b];  // exact mode: one dense run per segment
+            tstart[0] = 0;
+            sbin[0] = 0;
+            const uint32_t tile2 = P.narrow ? (uint32_t)(has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE) : kPartTileK;
+            for (uint32_t s2 = 0; s2 < nsub; ++s2) tstart[s2 + 1] = tstart[s2] + (hsub[s2] + tile2 - 1) / tile2;
+            for (uint32_t b = 0; b < nb1; ++b) {
+                snb2[b] = (uint32_t)std::min<double>(kMaxBins, std::max(1.0, std::ceil((double)h1[b] / P.target)));
+                sbin[b + 1] = sbin[b] + snb2[b];
             }
-        const bool narrow_b = W == 1 && kslots && !even_part && !ranged && !has_dst && !has_val && op == MSD_OP_NONE &&
-                              dmode == MSD_KEYS && span_b <= (1ull << 32) && !no_narrow_b;
-        if (kslots && verbose)
-            fprintf(stderr, "[bbk] msd key slots: %s records from level 2 (widest bucket 2^%.1f keys)\n",
-                    narrow_b ? "4-byte" : "8-byte", std::log2((double)std::max<uint64_t>(span_b, 1)));
-        const size_t rec_b = narrow_b ? 4 : rec_ab;  // record width of the level-2 output
+            nbuckets = sbin[nb1];
 
-        // ---- level 2
-        DevBuf seg_tile(((size_t)nsub + 1) * 4), seg_off(((size_t)nsub + 1) * 4), seg_nb2((size_t)nb1 * 4 + 16),
-            seg_bin(((size_t)nb1 + 1) * 4), seg_size((size_t)nsub * 4 + 16);
-        BBK_HIP(hipMemcpyAsync(seg_tile.p, tstart.data(), ((size_t)nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(seg_off.p, off1.data(), ((size_t)nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(seg_nb2.p, snb2.data(), (size_t)nb1 * 4, hipMemcpyHostToDevice, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(seg_bin.p, sbin.data(), ((size_t)nb1 + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(seg_size.p, hsub.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
-        PartLevel L2{2, b1, nb1, dmode, w0bits, seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), sel.lo, sel.span, sel.shl, sel.mul};
-        const uint32_t ntiles2 = tstart[nsub];
-        TileMap M2{seg_tile.as<uint32_t>(), seg_off.as<uint32_t>(), seg_size.as<uint32_t>(), nsub, N, ntiles2, 1, nullptr, 0, 0};
-        // narrow level 2: workgroups dealt to the XCDs by segment (k_tile_desc_narrow); BBK_XCD_TILES=0: A/B
-        static const bool xcd_tiles = !(getenv("BBK_XCD_TILES") && atoi(getenv("BBK_XCD_TILES")) == 0);
-        uint32_t nwg2 = ntiles2;  // workgroups of the level-2 kernel
-        DevBuf xstart_d;
-        std::vector<uint32_t> xstart;  // (lives to the end of the call: the copy below is asynchronous)
-        if (xcd_tiles && ntiles2) {  // (exact mode too: its histogram pass keeps the plain order, see desc2h)
-            xstart.resize(nsub);
-            uint32_t per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            for (uint32_t s2 = 0; s2 < nsub; ++s2) {
-                uint32_t &c = per_xcd[(s2 >> xs) & 7u];
-                xstart[s2] = c;
-                c += tstart[s2 + 1] - tstart[s2];
+            // narrow stage B (see k_bucket_base): key slots (which imply the direct output), one whole pass, no payload,
+            // KEYS prefix, and no bucket spanning more than 2^32 keys -- then only the keys' low words travel after level 1
+            const int w0bits = R.w0bits();
+            uint64_t span_b = 0;  // widest bucket, in keys
+            for (uint32_t b = 0; b < nb1; ++b)
+                if (h1[b]) {
+                    const uint64_t Q = 1ull << (32 - P.b1), q = (Q + snb2[b] - 1) / snb2[b];
+                    span_b = std::max(span_b, w0bits > 32 ? q << (w0bits - 32) : q >> (32 - w0bits));
+                }
+            narrow_b = W == 1 && P.kslots && !R.even_part && !ranged && !has_dst && !has_val && R.op == MSD_OP_NONE &&
+                       R.dmode == MSD_KEYS && span_b <= (1ull << 32) && !R.knobs.once.no_narrow_b;
+            if (P.kslots && verbose)
+                fprintf(stderr, "[bbk] msd key slots: %s records from level 2 (widest bucket 2^%.1f keys)\n",
+                        narrow_b ? "4-byte" : "8-byte", std::log2((double)std::max<uint64_t>(span_b, 1)));
+
+            seg_tile.alloc(((size_t)nsub + 1) * 4);
+            seg_off.alloc(((size_t)nsub + 1) * 4);
+            seg_nb2.alloc((size_t)nb1 * 4 + 16);
+            seg_bin.alloc(((size_t)nb1 + 1) * 4);
+            seg_size.alloc((size_t)nsub * 4 + 16);
+            BBK_HIP(hipMemcpyAsync(seg_tile.p, tstart.data(), ((size_t)nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(seg_off.p, off1.data(), ((size_t)nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(seg_nb2.p, snb2.data(), (size_t)nb1 * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(seg_bin.p, sbin.data(), ((size_t)nb1 + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(seg_size.p, hsub.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
+            L2 = PartLevel{2, P.b1, nb1, R.dmode, w0bits, seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(),
+                           sel.lo, sel.span, sel.shl, sel.mul};
+            ntiles2 = tstart[nsub];
+            M2 = TileMap{seg_tile.as<uint32_t>(), seg_off.as<uint32_t>(), seg_size.as<uint32_t>(), nsub, N, ntiles2, 1,
+                         nullptr, 0, 0};
+            // narrow level 2: workgroups dealt to the XCDs by segment (k_tile_desc_narrow); BBK_XCD_TILES=0: A/B
+            nwg2 = ntiles2;  // workgroups of the level-2 kernel
+            if (R.knobs.once.xcd_tiles && ntiles2) {  // (exact mode too: its histogram pass keeps the plain order, see desc2h)
+                xstart.resize(nsub);
+                uint32_t per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                for (uint32_t s2 = 0; s2 < nsub; ++s2) {
+                    uint32_t &c = per_xcd[(s2 >> xs) & 7u];
+                    xstart[s2] = c;
+                    c += tstart[s2 + 1] - tstart[s2];
+                }
+                nwg2 = 8u * *std::max_element(per_xcd, per_xcd + 8);
+                xstart_d.alloc((size_t)nsub * 4);
+                BBK_HIP(hipMemcpyAsync(xstart_d.p, xstart.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
             }
-            nwg2 = 8u * *std::max_element(per_xcd, per_xcd + 8);
-            xstart_d.alloc((size_t)nsub * 4);
-            BBK_HIP(hipMemcpyAsync(xstart_d.p, xstart.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-        DevBuf desc2((size_t)nwg2 * sizeof(uint4) + 16);
-        if (ntiles2) {
-            if (narrow) {
+            desc2.alloc((size_t)nwg2 * sizeof(uint4) + 16);
+            if (ntiles2) {
                 if (xstart_d.p) BBK_HIP(hipMemsetAsync(desc2.p, 0, (size_t)nwg2 * sizeof(uint4), ctx->stream));
-                hipLaunchKernelGGL(k_tile_desc_narrow, dim3((ntiles2 + 255) / 256), dim3(256), 0, ctx->stream, M2,
-                                   seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), tile2, xs,
+                hipLaunchKernelGGL(P.narrow ? k_tile_desc_narrow : k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0,
+                                   ctx->stream, M2, seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), tile2, xs,
                                    (const uint32_t *)xstart_d.p, desc2.as<uint4>());
+                check_launch("k_tile_desc");
             }
-            else {
-                if (xstart_d.p) BBK_HIP(hipMemsetAsync(desc2.p, 0, (size_t)nwg2 * sizeof(uint4), ctx->stream));
-                hipLaunchKernelGGL(k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0, ctx->stream, M2, seg_nb2.as<uint32_t>(),
-                                   seg_bin.as<uint32_t>(), kPartTileK, xs, (const uint32_t *)xstart_d.p, desc2.as<uint4>());
+            M2.desc = desc2.as<uint4>();
+            // exact mode: the histogram kernel walks 16 consecutive tiles per workgroup and wants them in plain order
+            if (!P.slots && xstart_d.p && !P.narrow) {
+                desc2h.alloc((size_t)ntiles2 * sizeof(uint4) + 16);
+                hipLaunchKernelGGL(k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0, ctx->stream, M2,
+                                   seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), kPartTileK, xs, (const uint32_t *)nullptr,
+                                   desc2h.as<uint4>());
+                check_launch("k_tile_desc");
             }
-            check_launch("k_tile_desc");
         }
-        M2.desc = desc2.as<uint4>();
-        // exact mode: the histogram kernel walks 16 consecutive tiles per workgroup and wants them in plain order
-        DevBuf desc2h;
-        if (!slots && xstart_d.p && !narrow) {
-            desc2h.alloc((size_t)ntiles2 * sizeof(uint4) + 16);
-            hipLaunchKernelGGL(k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0, ctx->stream, M2, seg_nb2.as<uint32_t>(),
-                               seg_bin.as<uint32_t>(), kPartTileK, xs, (const uint32_t *)nullptr, desc2h.as<uint4>());
-            check_launch("k_tile_desc");
-        }
-        DevBuf hist2((size_t)nbuckets * 4 + 16), boff(((size_t)nbuckets + 1) * 4 + 16);
-        const uint64_t nB = slots ? (uint64_t)nbuckets * stride2 : N;
-        if (slots) BBK_REQUIRE(nB + N < (1ull << 32), BBK_ERR_INTERNAL, "slot layout exceeds 32-bit offsets");
-        bufB.alloc(nB * rec_b);
-        if (need_vbuf) valB.alloc(nB * 4);
-        if (!slots) {
-            BBK_HIP(hipMemsetAsync(hist2.p, 0, (size_t)nbuckets * 4 + 16, ctx->stream));
-            {
+
+        // ---- level 2: bucket offsets (exact histogram, or the slots' cursors), scatter
+        void level2_scatter() {
+            hist2.alloc((size_t)nbuckets * 4 + 16);
+            boff.alloc(((size_t)nbuckets + 1) * 4 + 16);
+            const uint64_t nB = P.slots ? (uint64_t)nbuckets * P.stride2 : N;
+            if (P.slots) BBK_REQUIRE(nB + N < (1ull << 32), BBK_ERR_INTERNAL, "slot layout exceeds 32-bit offsets");
+            bufB.alloc(nB * (narrow_b ? 4 : P.rec_ab));
+            if (need_vbuf) valB.alloc(nB * 4);
+            if (!P.slots) {
+                BBK_HIP(hipMemsetAsync(hist2.p, 0, (size_t)nbuckets * 4 + 16, ctx->stream));
                 TileMap M2h = M2;
                 if (desc2h.p) M2h.desc = desc2h.as<uint4>();
-                launch_part<false, true>("k_part_hist2", (double)N * rec, ntiles2, bufA.as<Key<W>>(), nullptr, M2h, L2,
-                                         hist2.as<uint32_t>(), nullptr, nullptr, nullptr);
+                R.template launch_part<false, true, false>("k_part_hist2", (double)N * rec, ntiles2, bufA.as<Key<W>>(), nullptr,
+                                                    M2h, L2, hist2.as<uint32_t>(), nullptr, nullptr, nullptr);
+                DevBuf h64(((size_t)nbuckets + 1) * 8);
+                hipLaunchKernelGGL(k_u32_to_u64, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                   hist2.as<uint32_t>(), (uint64_t)nbuckets, h64.as<uint64_t>(), 0u);
+                check_launch("k_u32_to_u64");
+                const uint64_t tot = exclusive_scan_u64(ctx, h64.as<uint64_t>(), h64.as<uint64_t>(), nbuckets);
+                BBK_REQUIRE(tot == N, BBK_ERR_INTERNAL, "level-2 histogram does not add up");
+                hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
+                                   h64.as<uint64_t>(), (uint64_t)nbuckets, tot, boff.as<uint32_t>());
+                check_launch("k_scan_to_u32");
+                BBK_HIP(bbk::copy_async(hist2.p, boff.p, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                BBK_HIP(hipStreamSynchronize(ctx->stream));
+            } else {
+                // cursor of bucket g starts at its slot
+                hipLaunchKernelGGL(k_iota_mul, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                   hist2.as<uint32_t>(), nbuckets, P.stride2);
+                check_launch("k_iota_mul");
+                use_slots(L2, P.cap2, P.stride2);
             }
-            DevBuf h64(((size_t)nbuckets + 1) * 8);
-            hipLaunchKernelGGL(k_u32_to_u64, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                               hist2.as<uint32_t>(), (uint64_t)nbuckets, h64.as<uint64_t>(), 0u);
-            check_launch("k_u32_to_u64");
-            const uint64_t tot = exclusive_scan_u64(ctx, h64.as<uint64_t>(), h64.as<uint64_t>(), nbuckets);
-            BBK_REQUIRE(tot == N, BBK_ERR_INTERNAL, "level-2 histogram does not add up");
-            hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                               h64.as<uint64_t>(), (uint64_t)nbuckets, tot, boff.as<uint32_t>());
-            check_launch("k_scan_to_u32");
-            BBK_HIP(bbk::copy_async(hist2.p, boff.p, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-        } else {
-            // cursor of bucket g starts at its slot
-            hipLaunchKernelGGL(k_iota_mul, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream, hist2.as<uint32_t>(),
-                               nbuckets, stride2);
-            check_launch("k_iota_mul");
-            L2.slot_cap = cap2;
-            L2.slot_stride = stride2;
-            L2.spill_keys = spill_k.p;
-            L2.spill_vals = spill_v.as<uint32_t>();
-            L2.spill_count = spill_n.as<uint32_t>();
-            L2.spill_cap = spill_cap;
-            L2.narrow_hb = narrow ? nw_hb : 0;
-        }
-        if (narrow) {
-            if (ntiles2) {
-                const double pb = 2.0 * (double)N * (4 + (has_val ? 4 : 0));
-                const size_t sm = part_narrow2_smem(has_val);
-                KernelTimer t(ctx, "k_part_narrow2", pb);
-                if (has_val) {
-                    auto fn = k_part_narrow2<true>;
-                    BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-                    hipLaunchKernelGGL(fn, dim3(nwg2), dim3(kNw2Threads), sm, ctx->stream, bufA.as<uint32_t>(), valA.as<uint32_t>(),
-                                       desc2.as<uint4>(), L2, hist2.as<uint32_t>(), bufB.as<uint32_t>(), valB.as<uint32_t>());
-                } else {
-                    auto fn = k_part_narrow2<false>;
-                    BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-                    hipLaunchKernelGGL(fn, dim3(nwg2), dim3(kNw2Threads), sm, ctx->stream, bufA.as<uint32_t>(), (const uint32_t *)nullptr,
-                                       desc2.as<uint4>(), L2, hist2.as<uint32_t>(), bufB.as<uint32_t>(), (uint32_t *)nullptr);
-                }
-                check_launch("k_part_narrow2");
+            if (P.narrow) {
+                if (ntiles2)
+                    R.launch(has_val ? k_part_narrow2<true> : k_part_narrow2<false>, "k_part_narrow2",
+                             2.0 * (double)N * (4 + (has_val ? 4 : 0)), nwg2, kNw2Threads, part_narrow2_smem(has_val),
+                             bufA.as<uint32_t>(), vals_or_null(valA), desc2.as<uint4>(), L2, hist2.as<uint32_t>(),
+                             bufB.as<uint32_t>(), vals_or_null(valB));
+            } else if (narrow_b) {
+                if constexpr (W == 1)
+                    R.template launch_part<false, false, false, true>("k_part_l2", (double)N * (rec + 4), nwg2,
+                                                                        bufA.as<Key<W>>(), nullptr, M2, L2, nullptr,
+                                                                        hist2.as<uint32_t>(), bufB.as<Key<W>>(), nullptr);
+            } else {
+                R.template scatter_keys<false>(has_val, "k_part_l2", 2.0 * rec_bytes(N), nwg2, bufA.as<Key<W>>(), valA.as<uint32_t>(), M2,
+                               L2, hist2.as<uint32_t>(), bufB.as<Key<W>>(), valB.as<uint32_t>());
             }
-        } else if (narrow_b) {
-            if constexpr (W == 1)
-                launch_part_l<false, false, false, true>("k_part_l2", (double)N * (rec + 4), nwg2, bufA.as<Key<W>>(), nullptr,
-                                                         M2, L2, nullptr, hist2.as<uint32_t>(), bufB.as<Key<W>>(), nullptr);
-        } else {
-            const double pb = 2.0 * (double)N * (rec + (has_val ? 4 : 0));
-            if (has_val) launch_part<true, false>("k_part_l2", pb, nwg2, bufA.as<Key<W>>(), valA.as<uint32_t>(), M2, L2, nullptr, hist2.as<uint32_t>(), bufB.as<Key<W>>(), valB.as<uint32_t>());
-            else launch_part<false, false>("k_part_l2", pb, nwg2, bufA.as<Key<W>>(), nullptr, M2, L2, nullptr, hist2.as<uint32_t>(), bufB.as<Key<W>>(), nullptr);
         }
 
-        // ---- buckets in LDS
-        DevBuf dcount((size_t)nbuckets * 4 + 16);
-        DevBuf dbg(64);
-        BBK_HIP(hipMemsetAsync(dbg.p, 0, 64, ctx->stream));
-        // slot mode: the hash-dedup kernels write the distinct records straight into the (unordered) result
-        const bool out_vals = op != MSD_OP_NONE;
-        // (slot mode: the dedup kernels leave the distinct records at the head of every bucket slot, like the exact mode
-        // in its dense buckets; the compaction below makes the result.  BucketArgs::out_keys / out_total -- every bucket
-        // reserving its place in the result with an atomicAdd on one counter -- is no longer used: the counter served
-        // the 227 210 buckets of BASELINE configs[1] one after the other, 2.6 ms of 2.8.)
-        BucketArgs A{boff.as<uint32_t>(), dcount.as<uint32_t>(), nullptr, (int)k, verbose ? dbg.as<uint32_t>() : nullptr,
-                     slots ? cap2 : 0u, slots ? stride2 : 0u, hist2.as<uint32_t>(),
-                     nullptr, nullptr, nullptr, ~0ull, hash_max_probes(), nullptr};
-        const double bb = (double)N * (rec + (has_val ? 4 : 0));
-        // Sorted output of a key array that should hold no duplicates (both strands of a distinct canonical set, odd
-        // k): the dense result has the offsets of the input, so the sorting kernels write it directly -- no
-        // compaction pass.  Should a bucket remove a duplicate after all, or be left to the second chance, the pass
-        // is redone in place (the direct pass does not touch the buckets).
-        const bool direct = (!slots || kslots) && assume_distinct && (dmode == MSD_KEYS || dmode == MSD_REF) &&
-                            getenv("BBK_NO_DIRECT") == nullptr;
-        DevBuf dupf, slot_off;
-        if (kslots) {
-            // dense output offsets = exclusive scan of the slot fills; a total below N means a record missed its slot
-            DevBuf c64(((size_t)nbuckets + 1) * 8);
-            hipLaunchKernelGGL(k_slot_counts, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream, hist2.as<uint32_t>(),
-                               nbuckets, stride2, cap2, c64.as<uint64_t>());
-            check_launch("k_slot_counts");
-            const uint64_t tot = exclusive_scan_u64(ctx, c64.as<uint64_t>(), c64.as<uint64_t>(), nbuckets);
-            if (tot != N) {
-                if (verbose) fprintf(stderr, "[bbk] msd key slots: %llu of %llu records placed, exact mode\n",
-                                     (unsigned long long)tot, (unsigned long long)N);
-                return 4;
-            }
-            slot_off.alloc(((size_t)nbuckets + 1) * 4 + 16);
-            hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream, c64.as<uint64_t>(),
-                               (uint64_t)nbuckets, tot, slot_off.as<uint32_t>());
-            check_launch("k_scan_to_u32");
-            BBK_HIP(hipStreamSynchronize(ctx->stream));  // c64 goes out of scope
-            A.out_off = slot_off.as<uint32_t>();
-        }
-        if (direct) {
-            if (!has_dst) {
-                out.keys.alloc(N * rec + 16);
-                if (out_vals) out.vals.alloc(N * 4 + 16);
-            }
-            dupf.alloc(16);
-            BBK_HIP(hipMemsetAsync(dupf.p, 0, 16, ctx->stream));
-            A.sorted_keys = has_dst ? dst.keys : out.keys.p;
-            A.sorted_vals = has_dst ? dst.vals : out.vals.as<uint32_t>();
-            A.dup_flag = dupf.as<uint32_t>();
-            A.strip_mask = strip_mask;
-        }
-        DevBuf bseg, bbase;  // bbase: narrow stage B, the smallest key of every bucket
-        std::vector<uint16_t> h_bseg;
-        if (narrow) {
-            if constexpr (W == 1) {
-                h_bseg.resize((size_t)nbuckets + 1);
-                for (uint32_t b = 0; b < nb1; ++b)
-                    for (uint32_t g = sbin[b]; g < sbin[b + 1]; ++g) h_bseg[g] = (uint16_t)b;
-                bseg.alloc(((size_t)nbuckets + 1) * 2);
-                BBK_HIP(hipMemcpyAsync(bseg.p, h_bseg.data(), (size_t)nbuckets * 2, hipMemcpyHostToDevice, ctx->stream));
-                const double bbn = (double)N * (4 + (has_val ? 4 : 0));
-                auto launch32 = [&](auto fn, size_t sm) {
-                    BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-                    KernelTimer t(ctx, "k_bucket_hash32", bbn);
-                    hipLaunchKernelGGL(fn, dim3(nbuckets), dim3(kNwHashThreads), sm, ctx->stream, bufB.as<uint32_t>(),
-                                       valB.as<uint32_t>(), A, bseg.as<uint16_t>(), nw_hb);
-                    check_launch("k_bucket_hash32");
-                };
-                if (nbuckets) switch (op) {
-                    case MSD_OP_NONE: launch32(k_bucket_hash32<0>, bucket_hash32_smem<0>()); break;
-                    case MSD_OP_COUNT: launch32(k_bucket_hash32<1>, bucket_hash32_smem<1>()); break;
-                    case MSD_OP_SUM: launch32(k_bucket_hash32<2>, bucket_hash32_smem<2>()); break;
-                    case MSD_OP_OR: launch32(k_bucket_hash32<3>, bucket_hash32_smem<3>()); break;
-                    default: BBK_REQUIRE(false, BBK_ERR_ARG, "bad reduce op");
+        // ---- buckets in LDS: the first pass; the direct output's result, give-up or in-place redo
+        std::optional<Outcome> first_pass() {
+            dcount.alloc((size_t)nbuckets * 4 + 16);
+            dbg.alloc(64);
+            BBK_HIP(hipMemsetAsync(dbg.p, 0, 64, ctx->stream));
+            // (slot mode: the dedup kernels leave the distinct records at the head of every bucket slot, like the exact
+            // mode in its dense buckets; the compaction makes the result.  BucketArgs::out_keys / out_total -- every
+            // bucket reserving its place in the result with an atomicAdd on one counter -- is no longer used: the counter
+            // served the 227 210 buckets of BASELINE configs[1] one after the other, 2.6 ms of 2.8.)
+            A = BucketArgs{boff.as<uint32_t>(), dcount.as<uint32_t>(), nullptr, (int)R.k,
+                           verbose ? dbg.as<uint32_t>() : nullptr, P.slots ? P.cap2 : 0u, P.slots ? P.stride2 : 0u,
+                           hist2.as<uint32_t>(), nullptr, nullptr, nullptr, ~0ull, R.knobs.once.hash_max_probes, nullptr};
+            // Sorted output of a key array that should hold no duplicates (both strands of a distinct canonical set, odd
+            // k): the dense result has the offsets of the input, so the sorting kernels write it directly -- no
+            // compaction pass.  Should a bucket remove a duplicate after all, or be left to the second chance, the pass
+            // is redone in place (the direct pass does not touch the buckets).
+            direct = (!P.slots || P.kslots) && R.assume_distinct && (R.dmode == MSD_KEYS || R.dmode == MSD_REF) &&
+                     !R.knobs.no_direct;
+            if (P.kslots) {
+                // dense output offsets = exclusive scan of the slot fills; a total below N means a record missed its slot
+                DevBuf c64(((size_t)nbuckets + 1) * 8);
+                hipLaunchKernelGGL(k_slot_counts, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                   hist2.as<uint32_t>(), nbuckets, P.stride2, P.cap2, c64.as<uint64_t>());
+                check_launch("k_slot_counts");
+                const uint64_t tot = exclusive_scan_u64(ctx, c64.as<uint64_t>(), c64.as<uint64_t>(), nbuckets);
+                if (tot != N) {
+                    if (verbose) fprintf(stderr, "[bbk] msd key slots: %llu of %llu records placed, exact mode\n",
+                                         (unsigned long long)tot, (unsigned long long)N);
+                    return Outcome::KeySlotsGaveUp;
                 }
+                slot_off.alloc(((size_t)nbuckets + 1) * 4 + 16);
+                hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
+                                   c64.as<uint64_t>(), (uint64_t)nbuckets, tot, slot_off.as<uint32_t>());
+                check_launch("k_scan_to_u32");
+                BBK_HIP(hipStreamSynchronize(ctx->stream));  // c64 goes out of scope
+                A.out_off = slot_off.as<uint32_t>();
             }
-        } else if (narrow_b) {
-            if constexpr (W == 1) {
-                BBK_REQUIRE(direct, BBK_ERR_INTERNAL, "4-byte stage-B records need the direct output");
-                bbase.alloc(((size_t)nbuckets + 1) * 8);
-                if (nbuckets) {
-                    hipLaunchKernelGGL(k_bucket_base, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                                       seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), nb1, nbuckets, b1, w0bits,
-                                       bbase.as<uint64_t>());
-                    check_launch("k_bucket_base");
-                    constexpr int NT = BktCfg<1>::NT, IT = BktCfg<1>::ITEMS;
-                    const size_t sm = bucket_dist_nb_smem<NT, IT>();
-                    auto fn = k_bucket_dist_nb<NT, IT>;
-                    BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                (int)sm));
-                    KernelTimer t(ctx, "k_bucket_dist", (double)N * (4 + rec));
-                    hipLaunchKernelGGL(fn, dim3(nbuckets), dim3(NT), sm, ctx->stream, bufB.as<uint32_t>(), bbase.as<uint64_t>(), A);
-                    check_launch("k_bucket_dist_nb");
+            if (direct) {
+                if (!has_dst) {
+                    out.keys.alloc(N * rec + 16);
+                    if (out_vals) out.vals.alloc(N * 4 + 16);
                 }
+                dupf.alloc(16);
+                BBK_HIP(hipMemsetAsync(dupf.p, 0, 16, ctx->stream));
+                A.sorted_keys = has_dst ? dst.keys : out.keys.p;
+                A.sorted_vals = has_dst ? dst.vals : out.vals.as<uint32_t>();
+                A.dup_flag = dupf.as<uint32_t>();
+                A.strip_mask = R.strip_mask;
             }
-        } else {
-            bucket_dispatch<false>(nbuckets, bufB.as<Key<W>>(), valB.as<uint32_t>(), A, bb);
-        }
-
-        // buckets the first pass left alone: listed on the device, only the (short) list comes to the host
-        constexpr uint32_t kFlagCap = 65536;
-        DevBuf flag_ids((size_t)kFlagCap * 4), flag_n;
-        uint32_t *d_flag_n = nullptr;
-        if (slots) {
-            d_flag_n = spill_n.as<uint32_t>() + 2;
-        } else {
-            flag_n.alloc(16);
-            d_flag_n = flag_n.as<uint32_t>();
-        }
-        uint32_t ctr[4] = {0, 0, 0, 0};  // spilled, direct, flagged, duplicates seen by the direct pass
-        auto fetch_flags = [&]() {
-            if (!slots) BBK_HIP(hipMemsetAsync(flag_n.p, 0, 16, ctx->stream));
-            hipLaunchKernelGGL(k_flagged, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream, dcount.as<uint32_t>(),
-                               nbuckets, flag_ids.as<uint32_t>(), kFlagCap, d_flag_n);
-            check_launch("k_flagged");
-            if (slots) BBK_HIP(hipMemcpyAsync(ctr, spill_n.p, 12, hipMemcpyDeviceToHost, ctx->stream));
-            else BBK_HIP(hipMemcpyAsync(ctr + 2, flag_n.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            if (direct) BBK_HIP(hipMemcpyAsync(ctr + 3, dupf.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-        };
-        fetch_flags();
-        if (direct) {
-            if (ctr[2] == 0 && ctr[3] == 0 && (!kslots || ctr[0] == 0)) {  // every bucket sorted, nothing removed or
-                out.n = N;                                                  // spilled: the result is complete
+            launch_buckets();
+            // buckets the first pass left alone: listed on the device, only the (short) list comes to the host
+            flag_ids.alloc((size_t)kFlagCap * 4);
+            if (!P.slots) flag_n.alloc(16);
+            fetch_flags();
+            if (!direct) return std::nullopt;
+            if (ctr[2] == 0 && ctr[3] == 0 && (!P.kslots || ctr[0] == 0)) {  // every bucket sorted, nothing removed or
+                out.n = N;                                                    // spilled: the result is complete
                 out.nbuckets = 0;
                 out.overflow_buckets = 0;
-                if (kslots && verbose) fprintf(stderr, "[bbk] msd key slots N=%llu buckets=%u: ordered without histograms\n",
-                                               (unsigned long long)N, nbuckets);
-                return 1;
+                if (P.kslots && verbose)
+                    fprintf(stderr, "[bbk] msd key slots N=%llu buckets=%u: ordered without histograms\n",
+                            (unsigned long long)N, nbuckets);
+                return Outcome::Done;
             }
-            if (kslots) {
+            if (P.kslots) {
                 if (verbose) fprintf(stderr, "[bbk] msd key slots given up (spill=%u flagged=%u dup=%u), exact mode\n", ctr[0],
                                      ctr[2], ctr[3]);
                 out.keys.release();
                 out.vals.release();
-                return 4;
+                return Outcome::KeySlotsGaveUp;
             }
             if (verbose) fprintf(stderr, "[bbk] msd direct output withdrawn (flagged=%u dup=%u): in-place pass\n", ctr[2], ctr[3]);
             if (!has_dst) {
@@ -3656,48 +3662,111 @@ struct MsdRunner {
             A.sorted_vals = nullptr;
             A.dup_flag = nullptr;
             A.strip_mask = ~0ull;
-            bucket_dispatch<false>(nbuckets, bufB.as<Key<W>>(), valB.as<uint32_t>(), A, bb);
+            R.template bucket_dispatch<false>(nbuckets, bufB.as<Key<W>>(), valB.as<uint32_t>(), A, rec_bytes(N));
             fetch_flags();
+            return std::nullopt;
         }
-        const uint32_t n_spill = ctr[0], n_flag = ctr[2];
-        if (n_flag > kFlagCap) {  // tens of thousands of overflowing buckets: not an input for this path
-            if (verbose) fprintf(stderr, "[bbk] msd: %u buckets overflow\n", n_flag);
-            return slots ? 3 : 0;
+
+        // the first-pass bucket kernel of the mode
+        void launch_buckets() {
+            if (P.narrow) {
+                if constexpr (W == 1) {
+                    h_bseg.resize((size_t)nbuckets + 1);
+                    for (uint32_t b = 0; b < P.nb1; ++b)
+                        for (uint32_t g = sbin[b]; g < sbin[b + 1]; ++g) h_bseg[g] = (uint16_t)b;
+                    bseg.alloc(((size_t)nbuckets + 1) * 2);
+                    BBK_HIP(hipMemcpyAsync(bseg.p, h_bseg.data(), (size_t)nbuckets * 2, hipMemcpyHostToDevice, ctx->stream));
+                    if (nbuckets)
+                        with_op(R.op, [&](auto o) {
+                            constexpr int OP = decltype(o)::value;
+                            R.launch(k_bucket_hash32<OP>, "k_bucket_hash32", (double)N * (4 + (has_val ? 4 : 0)), nbuckets,
+                                     kNwHashThreads, bucket_hash32_smem<OP>(), bufB.as<uint32_t>(), valB.as<uint32_t>(), A,
+                                     bseg.as<uint16_t>(), P.nw_hb);
+                        });
+                }
+            } else if (narrow_b) {
+                if constexpr (W == 1) {
+                    BBK_REQUIRE(direct, BBK_ERR_INTERNAL, "4-byte stage-B records need the direct output");
+                    bbase.alloc(((size_t)nbuckets + 1) * 8);
+                    if (nbuckets) {
+                        hipLaunchKernelGGL(k_bucket_base, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                           seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), P.nb1, nbuckets, P.b1,
+                                           R.w0bits(), bbase.as<uint64_t>());
+                        check_launch("k_bucket_base");
+                        constexpr int NT = BktCfg<1>::NT, IT = BktCfg<1>::ITEMS;
+                        R.launch(k_bucket_dist_nb<NT, IT>, "k_bucket_dist", (double)N * (4 + rec), nbuckets, NT,
+                                 bucket_dist_nb_smem<NT, IT>(), bufB.as<uint32_t>(), bbase.as<uint64_t>(), A);
+                    }
+                }
+            } else {
+                R.template bucket_dispatch<false>(nbuckets, bufB.as<Key<W>>(), valB.as<uint32_t>(), A, rec_bytes(N));
+            }
         }
-        std::vector<uint32_t> flagged(n_flag);
-        if (n_flag) {
-            BBK_HIP(hipMemcpyAsync(flagged.data(), flag_ids.p, (size_t)n_flag * 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            std::sort(flagged.begin(), flagged.end());
-        }
-        std::vector<uint32_t> hd, hb;  // exact mode with flagged buckets (or verbose): per-bucket counts / offsets
-        if (!slots && (n_flag || verbose)) {
-            hd.resize(nbuckets);
-            hb.resize((size_t)nbuckets + 1);
-            BBK_HIP(hipMemcpyAsync(hd.data(), dcount.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(hb.data(), boff.p, ((size_t)nbuckets + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+
+        void fetch_flags() {
+            uint32_t *d_flag_n = P.slots ? spill_n.as<uint32_t>() + 2 : flag_n.as<uint32_t>();
+            if (!P.slots) BBK_HIP(hipMemsetAsync(flag_n.p, 0, 16, ctx->stream));
+            hipLaunchKernelGGL(k_flagged, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream, dcount.as<uint32_t>(),
+                               nbuckets, flag_ids.as<uint32_t>(), kFlagCap, d_flag_n);
+            check_launch("k_flagged");
+            if (P.slots) BBK_HIP(hipMemcpyAsync(ctr, spill_n.p, 12, hipMemcpyDeviceToHost, ctx->stream));
+            else BBK_HIP(hipMemcpyAsync(ctr + 2, flag_n.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+            if (direct) BBK_HIP(hipMemcpyAsync(ctr + 3, dupf.p, 4, hipMemcpyDeviceToHost, ctx->stream));
             BBK_HIP(hipStreamSynchronize(ctx->stream));
         }
 
-        MsdOutput extra;  // slot mode: distinct records of everything that overflowed
-        uint64_t novf = 0, ovf_rec = 0;
-        if (slots) {
-            if (n_spill > spill_cap) {  // more than an eighth of the input overflowed: not an input for this mode
+        // ---- what the first pass left: the slot mode's overflow, or the exact mode's oversized buckets
+        std::optional<Outcome> overflow() {
+            const uint32_t n_flag = ctr[2];
+            if (n_flag > kFlagCap) {  // tens of thousands of overflowing buckets: not an input for this path
+                if (verbose) fprintf(stderr, "[bbk] msd: %u buckets overflow\n", n_flag);
+                return P.slots ? Outcome::SlotsGaveUp : Outcome::Declined;
+            }
+            flagged.resize(n_flag);
+            if (n_flag) {
+                BBK_HIP(hipMemcpyAsync(flagged.data(), flag_ids.p, (size_t)n_flag * 4, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                std::sort(flagged.begin(), flagged.end());
+            }
+            const bool exact_check = !P.slots && (n_flag || verbose);
+            if (exact_check) {
+                hd.resize(nbuckets);
+                hb.resize((size_t)nbuckets + 1);
+                BBK_HIP(hipMemcpyAsync(hd.data(), dcount.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipMemcpyAsync(hb.data(), boff.p, ((size_t)nbuckets + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipStreamSynchronize(ctx->stream));
+            }
+            if (P.slots)
+                if (auto r = slot_overflow()) return r;
+            bufA.release();
+            valA.release();
+            if (exact_check)
+                if (auto r = exact_overflow()) return r;
+            out.overflow_buckets = novf;
+            return std::nullopt;
+        }
+
+        // slot mode: every record of the affected keys -- the spill list, the overflowing segments' and buckets'
+        // slots -- is gathered and reduced on its own; its distinct records go to `extra`
+        std::optional<Outcome> slot_overflow() {
+            const uint32_t n_spill = ctr[0];
+            if (n_spill > P.spill_cap) {  // more than an eighth of the input overflowed: not an input for this mode
                 if (verbose) fprintf(stderr, "[bbk] msd slots: spill list overflow (%u), exact mode\n", n_spill);
-                return 3;
+                return Outcome::SlotsGaveUp;
             }
             const std::vector<uint32_t> &over_bkt = flagged;
+            const uint32_t xs = P.xs;
             // records a flagged bucket's slot really holds: a bucket is also flagged when its LDS table gives up on a
             // slot that is NOT full (more distinct keys than the table takes), and the rest of such a slot is stale
             // pool memory -- never copy more than the level-2 cursor says was written
-            std::vector<uint32_t> bkt_fill(over_bkt.size(), cap2);
+            std::vector<uint32_t> bkt_fill(over_bkt.size(), P.cap2);
             if (!over_bkt.empty()) {
                 std::vector<uint32_t> cur2(nbuckets);
                 BBK_HIP(hipMemcpyAsync(cur2.data(), hist2.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
                 BBK_HIP(hipStreamSynchronize(ctx->stream));
                 for (size_t i = 0; i < over_bkt.size(); ++i) {
                     const uint32_t g = over_bkt[i];
-                    bkt_fill[i] = std::min<uint32_t>(cap2, cur2[g] - g * stride2);
+                    bkt_fill[i] = std::min<uint32_t>(P.cap2, cur2[g] - g * P.stride2);
                 }
             }
             uint64_t n_extra = (uint64_t)n_spill;
@@ -3706,7 +3775,7 @@ struct MsdRunner {
             for (uint32_t f : bkt_fill) n_extra += f;
             if (verbose)
                 fprintf(stderr, "[bbk] msd slots%s N=%llu nb1=%u seg_cap=%u buckets=%u spill=%u over_seg=%zu over_bkt=%zu\n",
-                        narrow ? " (narrow records)" : "", (unsigned long long)N, nb1, seg_cap, nbuckets, n_spill,
+                        P.narrow ? " (narrow records)" : "", (unsigned long long)N, P.nb1, P.seg_cap, nbuckets, n_spill,
                         over_seg.size(), over_bkt.size());
             ctx->add_stat("stat_slot_records", (double)N);
             ctx->add_stat("stat_slot_spilled", (double)n_spill);
@@ -3716,83 +3785,80 @@ struct MsdRunner {
             if (n_extra > N / 2) {  // most of the input overflowed (a handful of distinct k-mers): not for this mode
                 if (verbose) fprintf(stderr, "[bbk] msd slots: %llu of %llu records overflowed, exact mode\n",
                                      (unsigned long long)n_extra, (unsigned long long)N);
-                return 3;
-            }
-            if (n_extra) {
-                // every record of the affected keys: the spill list, the overflowing segments' and buckets' slots
-                const bool tiny = n_extra <= (uint64_t)BktCfg<W>::CAP2;  // fits one workgroup of the radix kernel
-                DevBuf ek(n_extra * rec), ev;
-                if (has_val || (tiny && op != MSD_OP_NONE)) ev.alloc(n_extra * 4 + 16);
-                uint64_t o = 0;
-                // narrow path: slots hold 4-byte records, widened with the segment they belong to (seg < 0: 8-byte keys)
-                auto put = [&](const void *ksrc, const uint32_t *vsrc, uint64_t first, uint64_t cnt, int seg = -1) {
-                    if (!cnt) return;
-                    if (seg >= 0) {
-                        hipLaunchKernelGGL(k_nw_widen, bbk::grid_blocks((cnt + 255) / 256), dim3(256), 0, ctx->stream,
-                                           (const uint32_t *)ksrc + first, (uint32_t)cnt, (uint32_t)seg, nw_hb,
-                                           ek.as<uint64_t>() + o);
-                        check_launch("k_nw_widen");
-                    } else
-                    BBK_HIP(bbk::copy_async(ek.as<char>() + o * rec, (const char *)ksrc + first * rec, cnt * rec,
-                                           hipMemcpyDeviceToDevice, ctx->stream));
-                    if (has_val)
-                        BBK_HIP(bbk::copy_async(ev.as<uint32_t>() + o, vsrc + first, cnt * 4, hipMemcpyDeviceToDevice,
-                                               ctx->stream));
-                    o += cnt;
-                };
-                put(spill_k.p, spill_v.as<uint32_t>(), 0, n_spill);
-                for (uint32_t b : over_seg)  // the written part of its slot (of every per-XCD sub-slot on the narrow path)
-                    for (uint32_t s2 = b << xs; s2 < (b + 1) << xs; ++s2)
-                        put(bufA.p, valA.as<uint32_t>(), (uint64_t)off1[s2], fill1[s2], narrow ? (int)b : -1);
-                for (size_t i = 0; i < over_bkt.size(); ++i)
-                    put(bufB.p, valB.as<uint32_t>(), (uint64_t)over_bkt[i] * stride2, bkt_fill[i],
-                        narrow ? (int)h_bseg[over_bkt[i]] : -1);
-                if (tiny) {
-                    // the usual case (one or two crowded buckets): ONE workgroup sorts + reduces all of it in LDS,
-                    // instead of a whole partition pipeline for a few thousand records
-                    DevBuf tb(16), tc(16);
-                    const uint32_t hbo[2] = {0u, (uint32_t)n_extra};
-                    BBK_HIP(hipMemcpyAsync(tb.p, hbo, 8, hipMemcpyHostToDevice, ctx->stream));
-                    BucketArgs At{tb.as<uint32_t>(), tc.as<uint32_t>(), nullptr, (int)k, nullptr, 0u, 0u,
-                                  nullptr, nullptr, nullptr, nullptr, ~0ull, hash_max_probes(), nullptr};
-                    MsdRunner<W> sorter = *this;
-                    sorter.dmode = MSD_KEYS;  // picks the sorting kernels in bucket_dispatch
-                    sorter.expand_k = 0;
-                    sorter.template bucket_dispatch<true>(1u, ek.as<Key<W>>(), ev.as<uint32_t>(), At,
-                                                          (double)n_extra * (rec + (has_val ? 4 : 0)),
-                                                          /*allow_hash=*/false);
-                    uint32_t d = 0;
-                    BBK_HIP(hipMemcpyAsync(&d, tc.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-                    BBK_HIP(hipStreamSynchronize(ctx->stream));
-                    BBK_REQUIRE(d != 0xFFFFFFFFu && d <= n_extra, BBK_ERR_INTERNAL, "overflow pass: bad count");
-                    extra.n = d;
-                    extra.keys = std::move(ek);
-                    if (op != MSD_OP_NONE) extra.vals = std::move(ev);
-                } else {
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
-                // The records were selected BY their hash bucket, so the same hash would pile them up again:
-                // partition them by key instead (the order of the result does not matter), and never decline --
-                // a k-mer with a million instances is finished by the per-bucket LSD fallback.
-                MsdRunner<W> exact = *this;
-                exact.slots_ok = false;
-                exact.dmode = MSD_KEYS;
-                exact.never_decline = true;
-                exact.expand_k = 0;
-                // declined (e.g. one k-mer makes up most of it): so does this call, the caller takes the LSD path
-                if (!exact.run_all(nullptr, ek.p, has_val ? ev.as<uint32_t>() : nullptr, n_extra, false, extra)) return 0;
-                extra.bucket_off.release();
-                }
+                return Outcome::SlotsGaveUp;
             }
             novf = over_bkt.size() + over_seg.size();
+            if (n_extra == 0) return std::nullopt;
+            const bool tiny = n_extra <= (uint64_t)BktCfg<W>::CAP2;  // fits one workgroup of the radix kernel
+            DevBuf ek(n_extra * rec), ev;
+            if (has_val || (tiny && out_vals)) ev.alloc(n_extra * 4 + 16);
+            uint64_t o = 0;
+            // narrow path: slots hold 4-byte records, widened with the segment they belong to (seg < 0: 8-byte keys)
+            auto put = [&](const void *ksrc, const uint32_t *vsrc, uint64_t first, uint64_t cnt, int seg = -1) {
+                if (!cnt) return;
+                if (seg >= 0) {
+                    hipLaunchKernelGGL(k_nw_widen, bbk::grid_blocks((cnt + 255) / 256), dim3(256), 0, ctx->stream,
+                                       (const uint32_t *)ksrc + first, (uint32_t)cnt, (uint32_t)seg, P.nw_hb,
+                                       ek.as<uint64_t>() + o);
+                    check_launch("k_nw_widen");
+                } else {
+                    BBK_HIP(bbk::copy_async(ek.as<char>() + o * rec, (const char *)ksrc + first * rec, cnt * rec,
+                                           hipMemcpyDeviceToDevice, ctx->stream));
+                }
+                if (has_val)
+                    BBK_HIP(bbk::copy_async(ev.as<uint32_t>() + o, vsrc + first, cnt * 4, hipMemcpyDeviceToDevice,
+                                           ctx->stream));
+                o += cnt;
+            };
+            put(spill_k.p, spill_v.as<uint32_t>(), 0, n_spill);
+            for (uint32_t b : over_seg)  // the written part of its slot (of every per-XCD sub-slot on the narrow path)
+                for (uint32_t s2 = b << xs; s2 < (b + 1) << xs; ++s2)
+                    put(bufA.p, valA.as<uint32_t>(), (uint64_t)off1[s2], fill1[s2], P.narrow ? (int)b : -1);
+            for (size_t i = 0; i < over_bkt.size(); ++i)
+                put(bufB.p, valB.as<uint32_t>(), (uint64_t)over_bkt[i] * P.stride2, bkt_fill[i],
+                    P.narrow ? (int)h_bseg[over_bkt[i]] : -1);
+            if (tiny) {
+                // the usual case (one or two crowded buckets): ONE workgroup sorts + reduces all of it in LDS,
+                // instead of a whole partition pipeline for a few thousand records
+                DevBuf tb(16), tc(16);
+                hbo[1] = (uint32_t)n_extra;
+                BBK_HIP(hipMemcpyAsync(tb.p, hbo, 8, hipMemcpyHostToDevice, ctx->stream));
+                BucketArgs At{tb.as<uint32_t>(), tc.as<uint32_t>(), nullptr, (int)R.k, nullptr, 0u, 0u,
+                              nullptr, nullptr, nullptr, nullptr, ~0ull, R.knobs.once.hash_max_probes, nullptr};
+                MsdRunner<W> sorter = R;
+                sorter.dmode = MSD_KEYS;  // picks the sorting kernels in bucket_dispatch
+                sorter.expand_k = 0;
+                sorter.template bucket_dispatch<true>(1u, ek.as<Key<W>>(), ev.as<uint32_t>(), At, rec_bytes(n_extra),
+                                                      /*allow_hash=*/false);
+                uint32_t d = 0;
+                BBK_HIP(hipMemcpyAsync(&d, tc.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                BBK_REQUIRE(d != 0xFFFFFFFFu && d <= n_extra, BBK_ERR_INTERNAL, "overflow pass: bad count");
+                extra.n = d;
+                extra.keys = std::move(ek);
+                if (out_vals) extra.vals = std::move(ev);
+                return std::nullopt;
+            }
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            // The records were selected BY their hash bucket, so the same hash would pile them up again:
+            // partition them by key instead (the order of the result does not matter), and never decline --
+            // a k-mer with a million instances is finished by the per-bucket LSD fallback.
+            MsdRunner<W> exact = R;
+            exact.slots_ok = false;
+            exact.dmode = MSD_KEYS;
+            exact.never_decline = true;
+            exact.expand_k = 0;
+            // declined (e.g. one k-mer makes up most of it): so does this call, the caller takes the LSD path
+            if (!exact.run_all(MsdInput{nullptr, ek.p, has_val ? ev.as<uint32_t>() : nullptr, n_extra, false}, extra))
+                return Outcome::Declined;
+            extra.bucket_off.release();
+            return std::nullopt;
         }
-        bufA.release();
-        valA.release();
 
-        if (!slots && (n_flag || verbose)) {
-            // ---- buckets above CAP: a second pass with 512-thread workgroups (2 x CAP); what still does not
-            // fit (a k-mer repeated > 12 k times in one bucket) is finished by the LSD path, one by one
-            std::vector<uint32_t> big;
-            uint64_t big_rec = 0;
+        // ---- exact mode, buckets above CAP: a second pass with 512-thread workgroups (2 x CAP); what still does not
+        // fit (a k-mer repeated > 12 k times in one bucket) is finished by the LSD path, one by one
+        std::optional<Outcome> exact_overflow() {
+            uint64_t big_rec = 0, ovf_rec = 0;
             // second chance: the ballot-ranked radix kernel with 512 threads -- buckets above the first pass's
             // capacity (8-byte keys: 2 x CAP; wider keys: more than the 4096-record hash kernel) and buckets the
             // distribution sort turned down for a crowded bin
@@ -3805,11 +3871,10 @@ struct MsdRunner {
             if (!big.empty()) {
                 DevBuf ids(big.size() * 4);
                 BBK_HIP(hipMemcpyAsync(ids.p, big.data(), big.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-                BucketArgs A2{boff.as<uint32_t>(), dcount.as<uint32_t>(), ids.as<uint32_t>(), (int)k, nullptr, 0u, 0u,
-                              nullptr, nullptr, nullptr, nullptr, ~0ull, hash_max_probes(), nullptr};
-                const double b2 = (double)big_rec * (rec + (has_val ? 4 : 0));
-                bucket_dispatch<true>((uint32_t)big.size(), bufB.as<Key<W>>(), valB.as<uint32_t>(), A2, b2,
-                                      /*allow_hash=*/false);
+                BucketArgs A2{boff.as<uint32_t>(), dcount.as<uint32_t>(), ids.as<uint32_t>(), (int)R.k, nullptr, 0u, 0u,
+                              nullptr, nullptr, nullptr, nullptr, ~0ull, R.knobs.once.hash_max_probes, nullptr};
+                R.template bucket_dispatch<true>((uint32_t)big.size(), bufB.as<Key<W>>(), valB.as<uint32_t>(), A2,
+                                                 rec_bytes(big_rec), /*allow_hash=*/false);
                 BBK_HIP(hipMemcpyAsync(hd.data(), dcount.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
                 BBK_HIP(hipStreamSynchronize(ctx->stream));
             }
@@ -3826,112 +3891,104 @@ struct MsdRunner {
                 BBK_HIP(hipStreamSynchronize(ctx->stream));
                 fprintf(stderr, "[bbk] msd all-words-fallback buckets=%u\n", hdbg[0]);
                 fprintf(stderr, "[bbk] msd mode=%d N=%llu nb1=%u buckets=%u max_bucket=%u cap=%u big=%zu lsd=%llu (%llu rec)\n",
-                        dmode, (unsigned long long)N, nb1, nbuckets, mx, bucket_cap(), big.size(), (unsigned long long)novf,
-                        (unsigned long long)ovf_rec);
+                        R.dmode, (unsigned long long)N, P.nb1, nbuckets, mx, R.bucket_cap(), big.size(),
+                        (unsigned long long)novf, (unsigned long long)ovf_rec);
             }
-            if (!never_decline && (novf > 256 || ovf_rec > N / 4)) return 0;
-            if (novf) {
-                const ReduceOp rop = op == MSD_OP_OR ? REDUCE_OR : (op == MSD_OP_SUM ? REDUCE_SUM : REDUCE_COUNT);
-                for (uint32_t b = 0; b < nbuckets; ++b) {
-                    if (hd[b] != 0xFFFFFFFFu) continue;
-                    const uint64_t cnt = hb[b + 1] - hb[b];
-                    Key<W> *kb = bufB.as<Key<W>>() + hb[b];
-                    uint32_t *vb = need_vbuf ? valB.as<uint32_t>() + hb[b] : nullptr;
-                    DevBuf tk(cnt * rec), tv(cnt * 4), ok(cnt * rec), ov(cnt * 4);
-                    sort_records(ctx, W, kb, tk.p, has_val ? vb : nullptr, has_val ? tv.as<uint32_t>() : nullptr, cnt,
-                                 key_passes(k));
-                    const uint64_t d = unique_records(ctx, W, kb, has_val ? vb : nullptr, cnt, ok.p,
-                                                      op != MSD_OP_NONE ? ov.as<uint32_t>() : nullptr, rop, false);
-                    BBK_HIP(bbk::copy_async(kb, ok.p, d * rec, hipMemcpyDeviceToDevice, ctx->stream));
-                    if (op != MSD_OP_NONE)
-                        BBK_HIP(bbk::copy_async(vb, ov.p, d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    BBK_HIP(hipStreamSynchronize(ctx->stream));
-                    hd[b] = (uint32_t)d;
-                }
-                BBK_HIP(hipMemcpyAsync(dcount.p, hd.data(), (size_t)nbuckets * 4, hipMemcpyHostToDevice, ctx->stream));
+            if (!R.never_decline && (novf > 256 || ovf_rec > N / 4)) return Outcome::Declined;
+            if (novf == 0) return std::nullopt;
+            const int op = R.op;
+            const ReduceOp rop = op == MSD_OP_OR ? REDUCE_OR : (op == MSD_OP_SUM ? REDUCE_SUM : REDUCE_COUNT);
+            for (uint32_t b = 0; b < nbuckets; ++b) {
+                if (hd[b] != 0xFFFFFFFFu) continue;
+                const uint64_t cnt = hb[b + 1] - hb[b];
+                Key<W> *kb = bufB.as<Key<W>>() + hb[b];
+                uint32_t *vb = need_vbuf ? valB.as<uint32_t>() + hb[b] : nullptr;
+                DevBuf tk(cnt * rec), tv(cnt * 4), ok(cnt * rec), ov(cnt * 4);
+                sort_records(ctx, W, kb, tk.p, has_val ? vb : nullptr, has_val ? tv.as<uint32_t>() : nullptr, cnt,
+                             key_passes(R.k));
+                const uint64_t d = unique_records(ctx, W, kb, has_val ? vb : nullptr, cnt, ok.p,
+                                                  out_vals ? ov.as<uint32_t>() : nullptr, rop, false);
+                BBK_HIP(bbk::copy_async(kb, ok.p, d * rec, hipMemcpyDeviceToDevice, ctx->stream));
+                if (out_vals) BBK_HIP(bbk::copy_async(vb, ov.p, d * 4, hipMemcpyDeviceToDevice, ctx->stream));
+                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                hd[b] = (uint32_t)d;
             }
+            BBK_HIP(hipMemcpyAsync(dcount.p, hd.data(), (size_t)nbuckets * 4, hipMemcpyHostToDevice, ctx->stream));
+            return std::nullopt;
         }
-        out.overflow_buckets = novf;
 
         // ---- dense output: scan of the bucket counts + compaction.  (Slot mode: overflowing buckets wrote nothing and
-        // count 0 here; their records are in `extra`, appended below.)
-        uint64_t D = 0;
-        DevBuf d64;
-        {
-            d64.alloc(((size_t)nbuckets + 1) * 8);
+        // count 0 here; their records are in `extra`, appended.)  Exact HASH mode also gets the bucket table.
+        void compact() {
+            DevBuf d64(((size_t)nbuckets + 1) * 8);
             hipLaunchKernelGGL(k_u32_to_u64, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
                                dcount.as<uint32_t>(), (uint64_t)nbuckets, d64.as<uint64_t>(), 0u);
             check_launch("k_u32_to_u64");
-            D = exclusive_scan_u64(ctx, d64.as<uint64_t>(), d64.as<uint64_t>(), nbuckets);
-            if (slots) BBK_REQUIRE(D + extra.n <= N, BBK_ERR_INTERNAL, "more distinct records than records");
-            out.n = D + (slots ? extra.n : 0);
+            const uint64_t D = exclusive_scan_u64(ctx, d64.as<uint64_t>(), d64.as<uint64_t>(), nbuckets);
+            if (P.slots) BBK_REQUIRE(D + extra.n <= N, BBK_ERR_INTERNAL, "more distinct records than records");
+            out.n = D + (P.slots ? extra.n : 0);
             if (!has_dst) {
                 out.keys.alloc(out.n * rec + 16);
                 if (out_vals) out.vals.alloc(out.n * 4 + 16);
             }
             Key<W> *ck = has_dst ? (Key<W> *)dst.keys : out.keys.as<Key<W>>();
-            uint32_t *cv = has_dst ? dst.vals : out.vals.as<uint32_t>();
-            const uint32_t *cboff = slots ? nullptr : boff.as<uint32_t>();  // slot mode: bucket b starts at b * stride2
+            uint32_t *cv = !out_vals ? nullptr : has_dst ? dst.vals : out.vals.as<uint32_t>();
+            const uint32_t *vb = out_vals ? valB.as<uint32_t>() : nullptr;
+            const uint32_t *cboff = P.slots ? nullptr : boff.as<uint32_t>();  // slot mode: bucket b starts at b * stride2
             const unsigned blocks = (unsigned)(((uint64_t)nbuckets * 64 + 255) / 256);
-            if (narrow) {
-                if constexpr (W == 1) {
-                    KernelTimer t(ctx, "compact", (double)D * (4 + 8 + (out_vals ? 8 : 0)));
-                    if (out_vals)
-                        hipLaunchKernelGGL(k_compact_narrow<true>, dim3(blocks), dim3(256), 0, ctx->stream, bufB.as<uint32_t>(),
-                                           valB.as<uint32_t>(), dcount.as<uint32_t>(), d64.as<uint64_t>(), nbuckets, stride2,
-                                           bseg.as<uint16_t>(), nw_hb, reinterpret_cast<uint64_t *>(ck), cv);
-                    else
-                        hipLaunchKernelGGL(k_compact_narrow<false>, dim3(blocks), dim3(256), 0, ctx->stream, bufB.as<uint32_t>(),
-                                           (const uint32_t *)nullptr, dcount.as<uint32_t>(), d64.as<uint64_t>(), nbuckets,
-                                           stride2, bseg.as<uint16_t>(), nw_hb, reinterpret_cast<uint64_t *>(ck),
-                                           (uint32_t *)nullptr);
-                }
+            if (P.narrow) {
+                if constexpr (W == 1)
+                    R.launch(out_vals ? k_compact_narrow<true> : k_compact_narrow<false>, "compact",
+                             (double)D * (4 + 8 + (out_vals ? 8 : 0)), blocks, 256, 0, bufB.as<uint32_t>(), vb,
+                             dcount.as<uint32_t>(), d64.as<uint64_t>(), nbuckets, P.stride2, bseg.as<uint16_t>(), P.nw_hb,
+                             reinterpret_cast<uint64_t *>(ck), cv);
             } else {
-                KernelTimer t(ctx, "compact", 2.0 * (double)D * (rec + (out_vals ? 4 : 0)));
-                if (out_vals)
-                    hipLaunchKernelGGL((k_compact<W, true>), dim3(blocks), dim3(256), 0, ctx->stream, bufB.as<Key<W>>(),
-                                       valB.as<uint32_t>(), cboff, dcount.as<uint32_t>(), d64.as<uint64_t>(), nbuckets, ck, cv,
-                                       strip_mask, stride2);
-                else
-                    hipLaunchKernelGGL((k_compact<W, false>), dim3(blocks), dim3(256), 0, ctx->stream, bufB.as<Key<W>>(),
-                                       (const uint32_t *)nullptr, cboff, dcount.as<uint32_t>(), d64.as<uint64_t>(), nbuckets, ck,
-                                       (uint32_t *)nullptr, strip_mask, stride2);
+                R.launch(out_vals ? k_compact<W, true> : k_compact<W, false>, "compact",
+                         2.0 * (double)D * (rec + (out_vals ? 4 : 0)), blocks, 256, 0, bufB.as<Key<W>>(), vb, cboff,
+                         dcount.as<uint32_t>(), d64.as<uint64_t>(), nbuckets, ck, cv, R.strip_mask, P.stride2);
             }
-            check_launch("k_compact");
-        }
-        if (extra.n) {
-            BBK_HIP(bbk::copy_async(out.keys.as<char>() + D * rec, extra.keys.p, extra.n * rec, hipMemcpyDeviceToDevice,
-                                   ctx->stream));
-            if (out_vals)
-                BBK_HIP(bbk::copy_async(out.vals.as<uint32_t>() + D, extra.vals.p, extra.n * 4, hipMemcpyDeviceToDevice,
+            if (extra.n) {
+                BBK_HIP(bbk::copy_async(out.keys.as<char>() + D * rec, extra.keys.p, extra.n * rec, hipMemcpyDeviceToDevice,
                                        ctx->stream));
+                if (out_vals)
+                    BBK_HIP(bbk::copy_async(out.vals.as<uint32_t>() + D, extra.vals.p, extra.n * 4, hipMemcpyDeviceToDevice,
+                                           ctx->stream));
+            }
+            out.nbuckets = P.slots ? 0 : nbuckets;
+            if (!P.slots) {
+                out.bucket_off.alloc(((size_t)nbuckets + 1) * 4);
+                hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
+                                   d64.as<uint64_t>(), (uint64_t)nbuckets, D, out.bucket_off.as<uint32_t>());
+                check_launch("k_scan_to_u32");
+            }
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
         }
-        // bucket table (exact HASH mode only): offsets of every bucket in the dense output
-        out.nbuckets = slots ? 0 : nbuckets;
-        if (!slots) {
-            out.bucket_off.alloc(((size_t)nbuckets + 1) * 4);
-            hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                               d64.as<uint64_t>(), (uint64_t)nbuckets, D, out.bucket_off.as<uint32_t>());
-            check_launch("k_scan_to_u32");
+    };
+
+    // One pass over the input, or over one range of its prefix space (sel), under the retry policy: a slot mode that
+    // gave up stays off for the rest of the call, and the pass is rerun with exact histograms.  (The hash slots need
+    // the HASH prefix, the key slots KEYS / REF: a pass gives up at most one of them.)
+    Outcome run_retrying(const MsdInput &in, MsdOutput &out, const Sel &sel = Sel(), Dst dst = Dst(),
+                         uint64_t *n_records = nullptr) {
+        for (;;) {
+            const Outcome r = Pass(*this, in, out, sel, dst).run(n_records);
+            if (r == Outcome::SlotsGaveUp) slots_ok = false;
+            else if (r == Outcome::KeySlotsGaveUp) kslots_ok = false;
+            else return r;
         }
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
-        return 1;
     }
 
     // Histogram of the whole input over the top `bits` bits of the prefix (key arrays, KEYS / REF prefix): the
     // range passes of run_all are sized from it, so a skewed key space still gives passes that fit.
     std::vector<uint64_t> prefix_histogram(const void *d_keys, uint64_t n_records, int bits) {
-        constexpr uint32_t kPartTileK = PartCfg<W>::TILE;
         const uint32_t nb = 1u << bits;
-        const int w0bits = (W == 1) ? (int)(2 * k) : 64;
         DevBuf h((size_t)nb * 4 + 16);
         BBK_HIP(hipMemsetAsync(h.p, 0, (size_t)nb * 4 + 16, ctx->stream));
-        PartLevel L{1, bits, nb, dmode, w0bits, nullptr, nullptr, 0u, 0u, 0, 0u};
+        PartLevel L{1, bits, nb, dmode, w0bits(), nullptr, nullptr, 0u, 0u, 0, 0u};
         TileMap M{nullptr, nullptr, nullptr, 1, n_records, 0, 1, nullptr, (int)expand_k, expand_tag ? 1 : 0};
         const uint64_t nt = (n_records + kPartTileK - 1) / kPartTileK;
         BBK_REQUIRE(nt < (1ull << 32), BBK_ERR_ARG, "input of %llu records exceeds the tile space", (unsigned long long)n_records);
-        const size_t rec = (size_t)W * 8;
-        launch_part<false, true>("k_part_hist0", (double)(expand_k ? n_records / 2 : n_records) * rec, (uint32_t)nt,
+        launch_part<false, true, true>("k_part_hist0", (double)(expand_k ? n_records / 2 : n_records) * rec, (uint32_t)nt,
                                  (const Key<W> *)d_keys, nullptr, M, L, h.as<uint32_t>(), nullptr, nullptr, nullptr);
         std::vector<uint32_t> h32(nb);
         BBK_HIP(hipMemcpyAsync(h32.data(), h.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -3952,7 +4009,7 @@ struct MsdRunner {
     // 2^j whole buckets (see ref_bits in run()).
     bool plan_ranges(const bbk_reads *rd, const void *d_keys, uint64_t N, std::vector<Sel> &ranges) {
         const uint64_t limit = (uint64_t)((double)pass_limit(rd != nullptr) * 0.92);
-        const bool verbose = getenv("BBK_VERBOSE") != nullptr;
+        const bool verbose = knobs.verbose;
         ranges.clear();
         if (dmode == MSD_HASH) {
             // equal spans of the 32-bit hash space, as few as fit (not a power of two: 9.6 G records of 16-byte keys take
@@ -4077,20 +4134,15 @@ struct MsdRunner {
     // partition pass writes the records grouped by range once (the counts are already known from the planning
     // histogram), and every range is then an ordinary key array.  Level 0 runs in chunks of 2^j ranges that stay below
     // the 32-bit record offsets of one pass.  false: not applicable (the caller selects per pass as before).
-    bool level0_ranges(const void *d_keys, const uint32_t *d_vals, uint64_t n_in, uint64_t Nrec, const std::vector<Sel> &ranges,
-                       MsdOutput &out, uint64_t &D, uint64_t &inst) {
-        constexpr uint32_t kPartTileK = PartCfg<W>::TILE;
+    bool level0_ranges(const MsdInput &in, const std::vector<Sel> &ranges, MsdOutput &out, uint64_t &D, uint64_t &inst) {
         const size_t R = ranges.size();
-        if (R < 3 || (R & (R - 1)) || getenv("BBK_NO_LEVEL0")) return false;
+        if (R < 3 || (R & (R - 1)) || knobs.no_level0) return false;
         const uint32_t span = ranges[0].span;
         if (span == 0 || (span & (span - 1))) return false;
         for (size_t i = 0; i < R; ++i)
             if (ranges[i].span != span || ranges[i].lo != (uint32_t)(i * (uint64_t)span)) return false;
         if ((uint64_t)span * R != (1ull << 32)) return false;
-        const bool verbose = getenv("BBK_VERBOSE") != nullptr;
-        const bool has_val = d_vals != nullptr;
-        const size_t rec = (size_t)W * 8;
-        const int w0bits = (W == 1) ? (int)(2 * k) : 64;
+        const bool verbose = knobs.verbose, has_val = in.vals != nullptr;
         // ranges per chunk: the largest power of two whose chunks all stay below the pass's 32-bit offsets
         size_t m = R;
         for (; m > 1; m >>= 1) {
@@ -4105,12 +4157,14 @@ struct MsdRunner {
         if (m < 2) return false;
         int jbits = 0;
         while ((1u << jbits) < m) ++jbits;
-        const uint64_t Ntot = expand_k ? 2 * n_in : n_in;  // instance space of the level-0 tiles
+        const uint64_t Ntot = expand_k ? 2 * in.n : in.n;  // instance space of the level-0 tiles
         const uint64_t nt = (Ntot + kPartTileK - 1) / kPartTileK;
         if (nt >= (1ull << 32)) return false;
         const unsigned ek = expand_k;
         const bool et = expand_tag;
-        auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        // every range: an ordinary key array (its records are what the expansion generated)
+        expand_k = 0;
+        expand_tag = false;
         for (size_t c = 0; c < R; c += m) {
             std::vector<uint32_t> off(m + 1, 0);
             for (size_t j = 0; j < m; ++j) off[j + 1] = off[j] + (uint32_t)ranges[c + j].est;
@@ -4127,15 +4181,11 @@ struct MsdRunner {
                 cs.span = (uint32_t)cspan;
                 cs.finish();
             }
-            PartLevel L0{1, jbits, (uint32_t)m, dmode, w0bits, nullptr, nullptr, cs.lo, cs.span, cs.shl, cs.mul};
+            PartLevel L0{1, jbits, (uint32_t)m, dmode, w0bits(), nullptr, nullptr, cs.lo, cs.span, cs.shl, cs.mul};
             TileMap M0{nullptr, nullptr, nullptr, 1, Ntot, 0, 1, nullptr, (int)ek, et ? 1 : 0};
-            const double pb = (double)(ek ? n_in : Ntot) * (rec + (has_val ? 4 : 0)) + (double)nc * (rec + (has_val ? 4 : 0));
-            if (has_val)
-                launch_part<true, false>("k_part_l0", pb, (uint32_t)nt, (const Key<W> *)d_keys, d_vals, M0, L0, nullptr,
-                                         cur.as<uint32_t>(), buf0.as<Key<W>>(), val0.as<uint32_t>());
-            else
-                launch_part<false, false>("k_part_l0", pb, (uint32_t)nt, (const Key<W> *)d_keys, nullptr, M0, L0, nullptr,
-                                          cur.as<uint32_t>(), buf0.as<Key<W>>(), nullptr);
+            const double pb = (double)(ek ? in.n : Ntot) * (rec + (has_val ? 4 : 0)) + (double)nc * (rec + (has_val ? 4 : 0));
+            scatter_keys<true>(has_val, "k_part_l0", pb, (uint32_t)nt, (const Key<W> *)in.keys, in.vals, M0, L0, cur.as<uint32_t>(),
+                         buf0.as<Key<W>>(), val0.as<uint32_t>());
             std::vector<uint32_t> end(m);
             BBK_HIP(hipMemcpyAsync(end.data(), cur.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
             BBK_HIP(hipStreamSynchronize(ctx->stream));
@@ -4143,18 +4193,6 @@ struct MsdRunner {
                 BBK_REQUIRE(end[j] == off[j + 1], BBK_ERR_INTERNAL, "level 0: range %zu received %u records, planned %u", c + j,
                             end[j] - off[j], off[j + 1] - off[j]);
             if (verbose) fprintf(stderr, "[bbk] level 0: %llu records into %zu ranges: %.3f s\n", (unsigned long long)nc, m, wall() - t0);
-            // every range of the chunk: an ordinary key array (its records are what the expansion generated)
-            expand_k = 0;
-            expand_tag = false;
-            struct Restore {
-                MsdRunner *r;
-                unsigned ek;
-                bool et;
-                ~Restore() {
-                    r->expand_k = ek;
-                    r->expand_tag = et;
-                }
-            } restore{this, ek, et};
             for (size_t j = 0; j < m; ++j) {
                 const Sel &sr = ranges[c + j];
                 if (sr.est == 0) continue;
@@ -4163,97 +4201,62 @@ struct MsdRunner {
                 const double t1 = wall();
                 // ranges of an expanded (both-strand) input spread as evenly as the whole: the key slots of the ordering
                 // pass apply (no histogram passes, XCD-local fill fronts); should they not hold, the exact mode redoes it
-                even_part = ek != 0 && getenv("BBK_NO_PART_KSLOTS") == nullptr;
-                int rv = run(nullptr, buf0.as<char>() + (size_t)off[j] * rec, has_val ? val0.as<uint32_t>() + off[j] : nullptr,
-                             sr.est, false, part, sr, nullptr, dst);
-                if (rv == 4) {
-                    kslots_ok = false;
-                    rv = run(nullptr, buf0.as<char>() + (size_t)off[j] * rec, has_val ? val0.as<uint32_t>() + off[j] : nullptr,
-                             sr.est, false, part, sr, nullptr, dst);
-                }
+                even_part = ek != 0 && !knobs.no_part_kslots;
+                const MsdInput ri{nullptr, buf0.as<char>() + (size_t)off[j] * rec,
+                                  has_val ? val0.as<uint32_t>() + off[j] : nullptr, sr.est, false};
+                const Outcome rv = run_retrying(ri, part, sr, dst);
                 even_part = false;
                 if (verbose) fprintf(stderr, "[bbk] key range (materialised): %.3f s\n", wall() - t1);
-                BBK_REQUIRE(rv == 1, BBK_ERR_INTERNAL, "a materialised range did not sort (%d)", rv);
+                BBK_REQUIRE(rv == Outcome::Done, BBK_ERR_INTERNAL, "a materialised range did not sort (%d)", (int)rv);
                 D += part.n;
                 inst += part.instances;
             }
         }
-        (void)Nrec;
         return true;
     }
 
-    // run() plus the split into ranges of the prefix space when the input holds more records than one pass takes
-    // (what the reference does with bounded buffers, repeated DumpBuffers rounds and the run merge,
-    // kmer_splitter.hpp:73-167, kmer_index_builder.hpp:281-365).  HASH prefix: every hash range is deduplicated on
-    // its own (disjoint key sets) and the distinct records are concatenated.  KEYS / REF prefix: the ranges are
-    // consecutive in prefix order and every pass writes straight into the final array.
-    bool run_all(const bbk_reads *rd, const void *d_keys, const uint32_t *d_vals, uint64_t n_in, bool with_mask,
-                 MsdOutput &out) {
-        bool too_big = false;
-        int r = run(rd, d_keys, d_vals, n_in, with_mask, out, Sel(), &too_big);
-        if (r == 3) {  // the slot mode gave up (too much of the input overflowed its slots): exact histograms
-            slots_ok = false;
-            r = run(rd, d_keys, d_vals, n_in, with_mask, out, Sel(), &too_big);
-        }
-        if (r == 4) {  // the key slots of the ordering pass did not hold (skewed key space): exact histograms
-            kslots_ok = false;
-            r = run(rd, d_keys, d_vals, n_in, with_mask, out, Sel(), &too_big);
-        }
-        if (r != 2) return r == 1;
-        const size_t rec = (size_t)W * 8;
+    // KEYS / REF prefix: the ranges are consecutive in prefix order and every pass writes straight into one array
+    // (upper bound: every record distinct, which is the usual case -- stage B sorts a distinct set)
+    bool run_key_ranges(const MsdInput &in, uint64_t Nrec, const std::vector<Sel> &ranges, MsdOutput &out) {
         const bool out_vals = op != MSD_OP_NONE;
-        const uint64_t Nrec = out.instances;  // records of the whole input (run() counted them before it returned 2)
-        std::vector<Sel> ranges;
-        if (!plan_ranges(rd, d_keys, Nrec, ranges)) return false;
+        out.keys.alloc(Nrec * rec + 16);
+        if (out_vals) out.vals.alloc(Nrec * 4 + 16);
         uint64_t D = 0, inst = 0;
-        if (dmode != MSD_HASH) {
-            // ordered output: one array for all passes (upper bound: every record distinct, which is the usual case --
-            // stage B sorts a distinct set)
-            out.keys.alloc(Nrec * rec + 16);
-            if (out_vals) out.vals.alloc(Nrec * 4 + 16);
-            if (level0_ranges(d_keys, d_vals, n_in, Nrec, ranges, out, D, inst)) {
-                BBK_REQUIRE(inst == Nrec, BBK_ERR_INTERNAL, "range passes saw %llu of %llu records", (unsigned long long)inst,
-                            (unsigned long long)Nrec);
-                out.n = D;
-                out.instances = Nrec;
-                out.nbuckets = 0;
-                return true;
-            }
+        if (!level0_ranges(in, ranges, out, D, inst)) {
             D = 0;
             inst = 0;
             for (const Sel &sr : ranges) {
                 if (sr.est == 0) continue;
                 MsdOutput part;
                 Dst dst{out.keys.as<char>() + D * rec, out_vals ? out.vals.as<uint32_t>() + D : nullptr};
-                const double t0k = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-                const int rv = run(rd, d_keys, d_vals, n_in, with_mask, part, sr, nullptr, dst);
-                if (getenv("BBK_VERBOSE"))
-                    fprintf(stderr, "[bbk] key range: %.3f s\n",
-                            std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0k);
-                if (rv != 1) return false;
+                const double t0 = wall();
+                const Outcome rv = Pass(*this, in, part, sr, dst).run();
+                if (knobs.verbose) fprintf(stderr, "[bbk] key range: %.3f s\n", wall() - t0);
+                if (rv != Outcome::Done) return false;
                 D += part.n;
                 inst += part.instances;
             }
-            BBK_REQUIRE(inst == Nrec, BBK_ERR_INTERNAL, "range passes saw %llu of %llu records", (unsigned long long)inst,
-                        (unsigned long long)Nrec);
-            out.n = D;
-            out.instances = Nrec;
-            out.nbuckets = 0;
-            return true;
         }
+        BBK_REQUIRE(inst == Nrec, BBK_ERR_INTERNAL, "range passes saw %llu of %llu records", (unsigned long long)inst,
+                    (unsigned long long)Nrec);
+        out.n = D;
+        out.instances = Nrec;
+        out.nbuckets = 0;
+        return true;
+    }
+
+    // HASH prefix: every hash range is deduplicated on its own (disjoint key sets) and the distinct records are
+    // concatenated
+    bool run_hash_ranges(const MsdInput &in, const std::vector<Sel> &ranges, MsdOutput &out) {
+        const bool out_vals = op != MSD_OP_NONE;
         std::vector<MsdOutput> parts(ranges.size());
-        const bool verbose = getenv("BBK_VERBOSE") != nullptr;
-        auto wall = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        uint64_t D = 0, inst = 0;
         for (size_t v = 0; v < ranges.size(); ++v) {
             MsdOutput &pt = parts[v];
             const double t0 = wall();
-            int rv = run(rd, d_keys, d_vals, n_in, with_mask, pt, ranges[v], nullptr);
-            if (verbose) fprintf(stderr, "[bbk] hash range %zu/%zu: %.3f s\n", v + 1, ranges.size(), wall() - t0);
-            if (rv == 3) {
-                slots_ok = false;
-                rv = run(rd, d_keys, d_vals, n_in, with_mask, pt, ranges[v], nullptr);
-            }
-            if (rv != 1) return false;
+            const Outcome rv = run_retrying(in, pt, ranges[v]);
+            if (knobs.verbose) fprintf(stderr, "[bbk] hash range %zu/%zu: %.3f s\n", v + 1, ranges.size(), wall() - t0);
+            if (rv != Outcome::Done) return false;
             D += pt.n;
             inst += pt.instances;
             pt.bucket_off.release();
@@ -4291,6 +4294,18 @@ struct MsdRunner {
         out.nbuckets = 0;
         return true;
     }
+
+    // run() plus the split into ranges of the prefix space when the input holds more records than one pass takes
+    // (what the reference does with bounded buffers, repeated DumpBuffers rounds and the run merge,
+    // kmer_splitter.hpp:73-167, kmer_index_builder.hpp:281-365).
+    bool run_all(const MsdInput &in, MsdOutput &out) {
+        uint64_t Nrec = 0;  // records of the whole input, when it is too big for one pass
+        const Outcome r = run_retrying(in, out, Sel(), Dst(), &Nrec);
+        if (r != Outcome::TooBig) return r == Outcome::Done;
+        std::vector<Sel> ranges;
+        if (!plan_ranges(in.rd, in.keys, Nrec, ranges)) return false;
+        return dmode == MSD_HASH ? run_hash_ranges(in, ranges, out) : run_key_ranges(in, Nrec, ranges, out);
+    }
 };
 
 #ifdef BBK_PHASE_PROF
@@ -4310,51 +4325,35 @@ static void dump_phases() {
 }
 #endif
 
+template <int W>
+static bool msd_run(bbk_ctx *ctx, unsigned k, int dmode, int op, const MsdInput &in, MsdOutput &out, bool assume_distinct,
+                    unsigned expand_k, bool expand_tag = false, uint64_t strip_mask = ~0ull) {
+    return MsdRunner<W>{ctx, k, dmode, op, strip_mask, assume_distinct, expand_k, expand_tag}.run_all(in, out);
+}
+
 bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, int dmode, int op, const bbk_reads *rd, const void *d_keys,
                      const uint32_t *d_vals, uint64_t n, bool with_mask, MsdOutput &out, unsigned tag_bits,
                      bool assume_distinct, unsigned expand_k) {
-    const int W = (int)words_of(k);
+    const MsdInput in{rd, d_keys, d_vals, n, with_mask};
     if (tag_bits) {
         // the tag sits right above the k-mer (bits [2k, 2k + tag_bits)): sort as a (k + tag_bits/2)-mer, clear the
         // tag on the way out
-        BBK_REQUIRE(W == 1 && rd == nullptr && dmode == MSD_KEYS && tag_bits % 2 == 0 && 2 * k + tag_bits <= 64 &&
+        BBK_REQUIRE(words_of(k) == 1 && rd == nullptr && dmode == MSD_KEYS && tag_bits % 2 == 0 && 2 * k + tag_bits <= 64 &&
                         (expand_k == 0 || expand_k == k),
                     BBK_ERR_INTERNAL, "tagged sort needs 8-byte keys with %u spare bits", tag_bits);
-        MsdRunner<1> r{ctx, k + tag_bits / 2, dmode, op, d_vals != nullptr};
-        r.strip_mask = (2 * k >= 64) ? ~0ull : ((1ull << (2 * k)) - 1ull);
-        r.assume_distinct = assume_distinct;
-        r.expand_k = expand_k;
-        r.expand_tag = expand_k != 0;
-        return r.run_all(rd, d_keys, d_vals, n, with_mask, out);
+        return msd_run<1>(ctx, k + tag_bits / 2, dmode, op, in, out, assume_distinct, expand_k, expand_k != 0,
+                          (2 * k >= 64) ? ~0ull : ((1ull << (2 * k)) - 1ull));
     }
 #ifdef BBK_PHASE_PROF
     struct Dump {
         ~Dump() { dump_phases(); }
     } dump_on_exit;
 #endif
-    if (W == 1) {
-        MsdRunner<1> r{ctx, k, dmode, op, with_mask || d_vals != nullptr};
-        r.assume_distinct = assume_distinct;
-        r.expand_k = expand_k;
-        return r.run_all(rd, d_keys, d_vals, n, with_mask, out);
-    }
-    if (W == 2) {
-        MsdRunner<2> r{ctx, k, dmode, op, with_mask || d_vals != nullptr};
-        r.assume_distinct = assume_distinct;
-        r.expand_k = expand_k;
-        return r.run_all(rd, d_keys, d_vals, n, with_mask, out);
-    }
-    if (W == 3) {
-        MsdRunner<3> r{ctx, k, dmode, op, with_mask || d_vals != nullptr};
-        r.assume_distinct = assume_distinct;
-        r.expand_k = expand_k;
-        return r.run_all(rd, d_keys, d_vals, n, with_mask, out);
-    }
-    if (W == 4) {
-        MsdRunner<4> r{ctx, k, dmode, op, with_mask || d_vals != nullptr};
-        r.assume_distinct = assume_distinct;
-        r.expand_k = expand_k;
-        return r.run_all(rd, d_keys, d_vals, n, with_mask, out);
+    switch (words_of(k)) {
+        case 1: return msd_run<1>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
+        case 2: return msd_run<2>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
+        case 3: return msd_run<3>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
+        case 4: return msd_run<4>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
     }
     return false;
 }
