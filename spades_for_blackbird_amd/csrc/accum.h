@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "bbk_internal.h"
+#include "msd.h"
 
 namespace bbk {
 
@@ -19,10 +20,15 @@ struct Accum {
     unsigned k = 0;
     bool with_mask = false;  // payload = InOutMask bits (OR) instead of multiplicities (SUM)
     bool want_vals = false;
+    // a count whose first batch may leave its distinct set in stage A's buckets (BucketView): both strands, no payload,
+    // odd k (stage B then reads the buckets in place)
+    bool want_view = false;
     DevBuf keys, vals;       // the accumulated distinct canonical set (any order)
+    BucketView view;         // ... or that set still in stage A's buckets (keys empty)
     uint64_t n = 0;
     struct Run {
         DevBuf keys, vals;
+        BucketView view;
         uint64_t n = 0;
     };
     std::vector<Run> runs;
@@ -36,6 +42,7 @@ struct Accum {
     // a record array already in HBM (keys + payloads, duplicates allowed) becomes one more run
     void push_records(const void *d_keys, const uint32_t *d_vals, uint64_t n_rec);
     void merge();
+    void dense();  // every BucketView of the accumulator -> its dense array in keys
     uint64_t finish_sorted(DevBuf &out_keys, DevBuf &out_vals);
 };
 

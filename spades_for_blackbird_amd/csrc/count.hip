@@ -183,8 +183,9 @@ uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *v
 // payload: with_mask -> OR of the InOutMask bits of every occurrence; want_vals -> multiplicity.
 // MSD path (hash-partitioned dedup in LDS, hash-range passes above one device pass); LSD fallback = extract, sort,
 // unique (its output happens to be ascending).
+// view: the caller takes the result as a BucketView where the narrow MSD pass leaves one (out_keys then stays empty)
 void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, bool want_vals, DevBuf &out_keys,
-                 DevBuf &out_vals, uint64_t &n_distinct, uint64_t &n_instances) {
+                 DevBuf &out_vals, uint64_t &n_distinct, uint64_t &n_instances, BucketView *view = nullptr) {
     const int W = (int)words_of(k);
     n_distinct = 0;
     n_instances = 0;
@@ -194,9 +195,11 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
         n_distinct = 0;
         n_instances = 0;
         MsdOutput a;
+        a.want_view = view != nullptr;
         if (msd_sort_reduce(ctx, k, MSD_HASH, op1, rd, nullptr, nullptr, 0, with_mask, a)) {
             n_instances = a.instances;
             n_distinct = a.n;
+            if (a.view.live()) *view = std::move(a.view);
             out_keys = std::move(a.keys);
             if (op1 != MSD_OP_NONE) out_vals = std::move(a.vals);
             return;
@@ -328,10 +331,11 @@ bool Accum::has_vals() const { return with_mask || want_vals; }
 int Accum::merge_op() const { return with_mask ? MSD_OP_OR : (want_vals ? MSD_OP_SUM : MSD_OP_NONE); }
 
 void Accum::push(const bbk_reads *rd) {
-    auto one = [&](const bbk_reads *part) {
+    dense();  // a second batch: the first one's set is an ordinary run
+    auto one = [&](const bbk_reads *part, bool may_view) {
         Run r;
         uint64_t inst = 0;
-        dedup_reads(ctx, part, k, with_mask, want_vals, r.keys, r.vals, r.n, inst);
+        dedup_reads(ctx, part, k, with_mask, want_vals, r.keys, r.vals, r.n, inst, may_view ? &r.view : nullptr);
         instances += inst;
         if (r.n == 0) return;
         runs_n += r.n;
@@ -357,10 +361,10 @@ void Accum::push(const bbk_reads *rd) {
             v.d_words = rd->d_words;
             v.d_woff = rd->d_woff + r0;
             v.d_len = rd->d_len + r0;
-            one(&v);
+            one(&v, false);
         }
     } else {
-        one(rd);
+        one(rd, want_view && !has_vals() && batches == 0 && n == 0 && runs.empty());
     }
     ++batches;
     static const char *e = getenv("BBK_MERGE_MIN");  // tests force a merge after every push
@@ -379,16 +383,28 @@ void Accum::push_records(const void *d_keys, const uint32_t *d_vals, uint64_t n_
 }
 
 // accumulated set + runs -> accumulated set
+void Accum::dense() {
+    auto one = [&](BucketView &v, DevBuf &kb) {
+        if (!v.live()) return;
+        v.materialise(ctx);
+        kb = std::move(v.keys);
+    };
+    one(view, keys);
+    for (Run &r : runs) one(r.view, r.keys);
+}
+
 void Accum::merge() {
     if (runs.empty()) return;
     if (n == 0 && runs.size() == 1) {  // first batch: adopt
         keys = std::move(runs[0].keys);
         vals = std::move(runs[0].vals);
+        view = std::move(runs[0].view);
         n = runs[0].n;
         runs.clear();
         runs_n = 0;
         return;
     }
+    dense();
     const size_t rec = (size_t)words_of(k) * 8;
     const uint64_t total = n + runs_n;
     DevBuf ck(total * rec + 16), cv;
@@ -415,6 +431,7 @@ void Accum::merge() {
 // the accumulated set in ascending order (payloads alongside); the accumulator is left empty
 uint64_t Accum::finish_sorted(DevBuf &out_keys, DevBuf &out_vals) {
     merge();
+    dense();
     const uint64_t D = sort_distinct(ctx, k, keys.p, has_vals() ? vals.as<uint32_t>() : nullptr, n, merge_op(), out_keys,
                                      out_vals);
     keys.release();
@@ -427,8 +444,9 @@ uint64_t Accum::finish_sorted(DevBuf &out_keys, DevBuf &out_vals) {
 // and is merged by unique; its count doubles, as in the reference where both strands of such an
 // occurrence are counted.
 // want_ref: leave the set in the final_kmers order when that is free (tagged sort); s.ref_order tells.
+// view: the canonical set is still in stage A's buckets (ck empty, no payload); stage B's level 1 reads it there
 static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, const DevBuf *cv, uint64_t D,
-                                bbk_kmerset &s, bool want_ref = false) {
+                                bbk_kmerset &s, bool want_ref = false, BucketView *view = nullptr) {
     const bool wc = cv != nullptr;
     const int W = (int)words_of(k);
     const size_t rec = (size_t)W * 8;
@@ -448,10 +466,10 @@ static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, cons
         // REF prefix (XXH3 bucket above the key bits: the final_kmers order straight from the sort) for every key
         // width; BBK_NO_WIDE_REF=1: keys above 16 bytes are sorted ascending and take one more stable pass on the bucket
         const bool ref_prefix = want_ref && !tag && (W <= 2 || getenv("BBK_NO_WIDE_REF") == nullptr);
-        if (msd_sort_reduce(ctx, k, ref_prefix ? MSD_REF : MSD_KEYS, wc ? MSD_OP_SUM : MSD_OP_NONE, nullptr, ck.p,
-                            wc ? cv->as<uint32_t>() : nullptr, D, false, m, tag ? 4u : 0u,
+        if (msd_sort_reduce(ctx, k, ref_prefix ? MSD_REF : MSD_KEYS, wc ? MSD_OP_SUM : MSD_OP_NONE, nullptr,
+                            view ? nullptr : ck.p, wc ? cv->as<uint32_t>() : nullptr, D, false, m, tag ? 4u : 0u,
                             /*assume_distinct: odd k has no self-reverse-complementary k-mers*/ (k & 1) != 0,
-                            /*expand_k=*/k)) {
+                            /*expand_k=*/k, view)) {
             s.n = m.n;
             s.keys = std::move(m.keys);
             if (wc) s.counts = std::move(m.vals);
@@ -461,12 +479,14 @@ static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, cons
     }
     // general path: materialise the expanded array, sort, unique
     BBK_REQUIRE(2 * D < (1ull << 32), BBK_ERR_ARG, "too many distinct k-mers for the LSD path (%llu)", (unsigned long long)D);
+    if (view) view->materialise(ctx);
+    const void *ckp = view ? view->keys.p : ck.p;
     DevBuf e(2 * D * rec), et(2 * D * rec), ec, ect;
     if (wc) {
         ec.alloc(2 * D * 4);
         ect.alloc(2 * D * 4);
     }
-    BBK_DISPATCH_W(W, launch_expand<W_>(ctx, ck.p, wc ? cv->as<uint32_t>() : nullptr, D, (int)k, e.p,
+    BBK_DISPATCH_W(W, launch_expand<W_>(ctx, ckp, wc ? cv->as<uint32_t>() : nullptr, D, (int)k, e.p,
                                         wc ? ec.as<uint32_t>() : nullptr, false));
     sort_records(ctx, W, e.p, et.p, wc ? ec.as<uint32_t>() : nullptr, wc ? ect.as<uint32_t>() : nullptr, 2 * D,
                  key_passes(k));
@@ -504,9 +524,11 @@ static bbk_kmerset *finish_count(Accum &acc, unsigned flags) {
     s->instances = both ? 2 * acc.instances : acc.instances;
     acc.merge();
     if (both) {
-        expand_both_strands(ctx, k, acc.keys, wc ? &acc.vals : nullptr, acc.n, *s, want_ref);
+        expand_both_strands(ctx, k, acc.keys, wc ? &acc.vals : nullptr, acc.n, *s, want_ref,
+                            acc.view.live() ? &acc.view : nullptr);
         acc.keys.release();
         acc.vals.release();
+        acc.view = BucketView();
     } else if (flags & BBK_UNSORTED) {
         s->n = acc.n;
         s->sorted = false;
@@ -544,6 +566,7 @@ bbk_kmerset *both_strands_of(Accum &acc, unsigned flags) {
     s->has_counts = false;
     s->instances = 2 * acc.instances;
     acc.merge();
+    acc.dense();
     const bool want_ref = (flags & BBK_REFERENCE_ORDER) != 0;
     expand_both_strands(acc.ctx, acc.k, acc.keys, nullptr, acc.n, *s, want_ref);
     if (want_ref && !s->ref_order && s->sorted) {
@@ -556,6 +579,12 @@ bbk_kmerset *both_strands_of(Accum &acc, unsigned flags) {
         s->ref_order = true;
     }
     return s.release();
+}
+
+// a count whose stage B may read stage A's buckets in place: both strands without payload, 8-byte keys, odd k (the
+// ordering pass takes the key slots only for a distinct expanded set)
+static bool view_wanted(unsigned k, unsigned flags) {
+    return (flags & BBK_BOTH_STRANDS) && !(flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS)) && words_of(k) == 1 && (k & 1);
 }
 
 static void check_count_flags(unsigned flags) {
@@ -588,6 +617,7 @@ int bbk_count_begin(bbk_ctx *ctx, unsigned k, unsigned flags, bbk_counter **out)
         c->acc.k = k;
         c->acc.want_vals = (flags & BBK_WITH_COUNTS) != 0;
         c->acc.with_mask = (flags & BBK_WITH_MASKS) != 0;
+        c->acc.want_view = view_wanted(k, flags);
         c->flags = flags;
         *out = c.release();
     });
@@ -641,6 +671,7 @@ int bbk_count(bbk_ctx *ctx, const bbk_reads *reads, unsigned k, unsigned flags, 
         acc.k = k;
         acc.want_vals = (flags & BBK_WITH_COUNTS) != 0;
         acc.with_mask = (flags & BBK_WITH_MASKS) != 0;
+        acc.want_view = view_wanted(k, flags);
         acc.push(reads);
         *out = finish_count(acc, flags);
     });

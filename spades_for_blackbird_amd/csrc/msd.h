@@ -8,6 +8,35 @@ namespace bbk {
 enum { MSD_HASH = 0, MSD_KEYS = 1, MSD_REF = 2 };                      // partition prefix
 enum { MSD_OP_NONE = 0, MSD_OP_COUNT = 1, MSD_OP_SUM = 2, MSD_OP_OR = 3 };  // per-key reduction
 
+// Stage A's narrow distinct set left where the dedup kernel wrote it, instead of the dense 8-byte array
+// (MsdOutput::want_view): bucket b's distinct records are the 4-byte low words at the head of its level-2 slot,
+// slots[b * stride .. + count), and their high bits come from the bucket's level-1 segment (nw_key).  off is the
+// exclusive scan of the counts, so key c of the dense order is in the bucket b with off[b] <= c < off[b + 1].  The
+// records of the overflow path (already 8-byte keys) follow as `extra`.  Stage B's level 1 reads it as it stands
+// (msd_sort_reduce with view); every other consumer calls materialise() first.
+struct BucketView {
+    DevBuf slots;   // u32 [nbuckets * stride]
+    DevBuf dcount;  // u32 [nbuckets]: distinct records per bucket (0xFFFFFFFF: none here, see extra)
+    DevBuf off;     // u64 [nbuckets + 1]: exclusive scan of dcount
+    DevBuf seg;     // u16 [nbuckets]: level-1 segment of every bucket
+    DevBuf extra;   // u64 [n_extra]
+    uint32_t nbuckets = 0, stride = 0;
+    int hb = 0;     // key bits above the low word
+    uint64_t D = 0, n_extra = 0;
+    DevBuf keys;    // the dense array, once materialised
+    bool live() const { return slots.p != nullptr; }
+    uint64_t n() const { return D + n_extra; }
+    void release_slots() {
+        slots.release();
+        dcount.release();
+        off.release();
+        seg.release();
+        extra.release();
+    }
+    // the dense array of n() 8-byte keys into `keys` (what stage A's compaction writes); the slots are released
+    void materialise(bbk_ctx *ctx);
+};
+
 struct MsdOutput {
     DevBuf keys;        // distinct records: bucket-major in prefix order, ascending inside a bucket
     DevBuf vals;        // reduced payload (op != NONE)
@@ -16,6 +45,9 @@ struct MsdOutput {
     uint64_t instances = 0;
     uint64_t overflow_buckets = 0;
     uint32_t nbuckets = 0;
+    // caller: a narrow stage-A pass may leave its result as `view` (keys then stay empty); the pass decides
+    bool want_view = false;
+    BucketView view;
 };
 
 // Sort + reduce records that come either from reads (rd != null: canonical k-mers are extracted on
@@ -27,12 +59,16 @@ struct MsdOutput {
 // (tag, k-mer) and the tag is cleared in the output.
 bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, int dmode, int op, const bbk_reads *rd, const void *d_keys,
                      const uint32_t *d_vals, uint64_t n, bool with_mask, MsdOutput &out, unsigned tag_bits = 0,
-                     bool assume_distinct = false, unsigned expand_k = 0);
+                     bool assume_distinct = false, unsigned expand_k = 0, BucketView *view = nullptr);
 // expand_k = k (key array input): the array holds n CANONICAL k-mers and the records are generated on the fly -- 2n of
 // them: every key and its reverse complement, with the tag of tag_bits (the XXH3 bucket of 16) written by the
 // level-1 kernels themselves.
 // assume_distinct (key array, KEYS / REF prefix): the caller expects no duplicates, so the sorted result is written
 // directly at the offsets of the input (no compaction pass); verified on the fly, redone in place otherwise.
+// view (with expand_k, instead of d_keys; n = view->n()): the canonical array is a live BucketView.  The key-slot
+// level 1 reads it in place and releases its slots; a pass that needs the dense array materialises it, and a key-slot
+// give-up after the slots are gone rebuilds it from the level-1 records.  view->keys may hold the dense array after
+// the call.
 
 // superk.hip: stage A of a batch of reads for 16- and 24-byte keys through super-k-mer records (distinct canonical
 // k-mers + count / OR of edge masks, in any order).  false: not taken or given up -- use msd_sort_reduce.

@@ -2841,6 +2841,179 @@ __global__ void k_nw_widen(const uint32_t *__restrict__ in, uint32_t n, uint32_t
 }
 
 // ------------------------------------------------------------------------------------------
+// stage B's level 1 straight from stage A's buckets (BucketView, msd.h)
+// ------------------------------------------------------------------------------------------
+// Tile t of the both-strand records covers the canonical keys c in [t * TILE/2, (t+1) * TILE/2) of the dense order:
+// record 2c is key c, record 2c+1 its reverse complement, as in tile_load's expand_k branch.  Key c is the 4-byte word
+// slots[b * stride + c - off[b]] of the bucket b with off[b] <= c < off[b + 1], widened with the bucket's segment.
+// A tile spans ~6 buckets of ~690 keys at the flagship size; their offsets and segments are staged in LDS.
+constexpr int kViewSpan = 64;  // buckets of one tile staged in LDS (more: the lanes search the global table)
+
+// largest b in [lo, hi) with off[b] <= c (off[lo] <= c)
+__device__ inline uint32_t view_bucket(const uint64_t *__restrict__ off, uint32_t lo, uint32_t hi, uint64_t c) {
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (off[mid] <= c) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// one thread per tile: the buckets of its first and last key
+__global__ void k_view_tile_desc(const uint64_t *__restrict__ off, uint32_t nbuckets, uint64_t D, uint32_t keys_per_tile,
+                                 uint32_t ntiles, uint2 *__restrict__ desc) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntiles) return;
+    const uint64_t c0 = (uint64_t)t * keys_per_tile;
+    const uint64_t c1 = (c0 + keys_per_tile < D ? c0 + keys_per_tile : D) - 1u;
+    const uint32_t b0 = view_bucket(off, 0, nbuckets, c0);
+    desc[t] = make_uint2(b0, view_bucket(off, b0, nbuckets, c1));
+}
+
+// k_part (8-byte keys, level-1 scatter, no payload) whose tile comes from the view.  TAG: the XXH3 bucket of 16 above
+// the k-mer (M.expand_tag).  Each lane loads a key once and emits it and its reverse complement as its adjacent pair.
+template <bool TAG>
+__global__ __launch_bounds__(PartCfg<1>::THREADS) void k_part_view(const uint32_t *__restrict__ slots,
+                                                                   const uint64_t *__restrict__ off,
+                                                                   const uint16_t *__restrict__ seg,
+                                                                   const uint2 *__restrict__ vdesc, uint32_t stride,
+                                                                   int hb, TileMap M, PartLevel L,
+                                                                   uint32_t *__restrict__ cursor,
+                                                                   Key<1> *__restrict__ out) {
+    constexpr int kItems = PartCfg<1>::ITEMS, kTile = PartCfg<1>::TILE, kThreads = PartCfg<1>::THREADS, MAXB = 512;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // layout: k_part's (lhist | lstart | goff | scan | stage) | toff[kViewSpan] | tseg[kViewSpan]
+    uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
+    uint32_t *lstart = lhist + MAXB;
+    uint32_t *goff = lstart + MAXB;
+    uint32_t *scan_tmp = goff + MAXB;
+    Key<1> *stage = reinterpret_cast<Key<1> *>(scan_tmp + 32);
+    uint32_t *toff = reinterpret_cast<uint32_t *>(stage + kTile);
+    uint16_t *tseg = reinterpret_cast<uint16_t *>(toff + kViewSpan);
+    uint32_t *vals_unused = nullptr;
+
+    const int tid = threadIdx.x;
+    const TileInfo T = tile_info(M, L, blockIdx.x, (uint32_t)kTile);
+    const uint32_t count = T.count, nb = T.nb;  // count: records, even
+    const uint2 d = vdesc[blockIdx.x];
+    const uint32_t b0 = d.x, span = d.y - d.x + 1u;
+    const bool staged = span <= (uint32_t)kViewSpan;  // uniform
+    for (uint32_t b = tid; b < nb; b += kThreads) lhist[b] = 0;
+    if (staged && tid < (int)span) {
+        toff[tid] = (uint32_t)off[b0 + tid];  // key offsets < 2^32: one pass holds fewer records
+        tseg[tid] = seg[b0 + tid];
+    }
+    __syncthreads();
+
+    // item pair j of a lane = records 2c, 2c+1 of local key j * THREADS + tid (tile_local's pairs)
+    const uint32_t c0 = (uint32_t)(T.begin >> 1), nkeys = count >> 1;
+    uint32_t lo[kItems / 2], sg[kItems / 2];
+#pragma unroll
+    for (int j = 0; j < kItems / 2; ++j) {
+        const uint32_t cl = (uint32_t)(j * kThreads + tid);
+        const uint32_t c = c0 + (cl < nkeys ? cl : nkeys - 1u);  // clamped into the tile
+        uint32_t b, base;
+        if (staged) {
+            uint32_t i = 0, hi = span;
+            while (hi - i > 1) {
+                const uint32_t mid = (i + hi) >> 1;
+                if (toff[mid] <= c) i = mid;
+                else hi = mid;
+            }
+            b = b0 + i;
+            base = toff[i];
+            sg[j] = tseg[i];
+        } else {
+            b = view_bucket(off, b0, d.y + 1u, c);
+            base = (uint32_t)off[b];
+            sg[j] = seg[b];
+        }
+        lo[j] = slots[(size_t)b * stride + (c - base)];
+    }
+    Key<1> keys[kItems];
+    uint32_t binrank[kItems];
+#pragma unroll
+    for (int j = 0; j < kItems / 2; ++j) {
+        Key<1> x, r;
+        x.w[0] = nw_key(sg[j], lo[j], hb);
+        r = kmer_rc<1>(x, M.expand_k);
+        if (TAG) {
+            x.w[0] |= __umul64hi(xxh3_64<1>(x), 16ull) << (2 * M.expand_k);
+            r.w[0] |= __umul64hi(xxh3_64<1>(r), 16ull) << (2 * M.expand_k);
+        }
+        keys[2 * j] = x;
+        keys[2 * j + 1] = r;
+    }
+    // in registers through the LDS reorder (see k_part)
+#pragma unroll
+    for (int i = 0; i < kItems; ++i) asm volatile("" : "+v"(keys[i].w[0]));
+#pragma unroll
+    for (int i = 0; i < kItems; ++i) {
+        const uint32_t local = tile_local<1, kThreads>(i, tid);
+        binrank[i] = 0xFFFFFFFFu;
+        if (local < count) {
+            uint32_t pfx = prefix_of<1>(keys[i], L.dmode, L.w0bits);
+            if (select_prefix(pfx, L)) {
+                const uint32_t b = bin_of(pfx, L, nb);
+                const uint32_t rank = atomicAdd(&lhist[b], 1u);
+                binrank[i] = (b << 16) | rank;
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t vals[kItems] = {};
+    part_tail<1, kItems, kThreads, MAXB, false, false>(keys, vals, binrank, lhist, lstart, goff, scan_tmp, stage,
+                                                       vals_unused, nb, T.gbin0, L, cursor, out, nullptr, 0, 0ull);
+}
+
+static size_t part_view_smem() {
+    return part_smem(1, PartCfg<1>::TILE, false, false, true) + (size_t)kViewSpan * (4 + 2);
+}
+
+// A key-slot give-up after the view's slots were released: the canonical keys again, from the level-1 records
+// (both strands of every key, tag above bit 2k; odd k, so exactly one of a pair is canonical), in any order.  One
+// workgroup per level-1 sub-slot; cap bounds the writes.
+__global__ void k_view_recanon(const uint64_t *__restrict__ in, const uint32_t *__restrict__ seg_off,
+                               const uint32_t *__restrict__ seg_size, int k, uint64_t *__restrict__ out, uint64_t cap,
+                               uint32_t *__restrict__ count) {
+    const uint32_t o = seg_off[blockIdx.x], n = seg_size[blockIdx.x];
+    const uint64_t mask = (1ull << (2 * k)) - 1ull;
+    const int lane = threadIdx.x & 63;
+    for (uint32_t i0 = 0; i0 < n; i0 += blockDim.x) {  // uniform trip count: the ballot sees whole waves
+        const uint32_t i = i0 + threadIdx.x;
+        Key<1> x;
+        x.w[0] = 0;
+        bool keep = false;
+        if (i < n) {
+            x.w[0] = in[o + i] & mask;
+            keep = !kmer_less_nucl<1>(kmer_rc<1>(x, k), x);
+        }
+        const uint64_t bal = __ballot(keep);
+        uint32_t base = 0;
+        if (lane == 0 && bal) base = atomicAdd(count, (uint32_t)__popcll(bal));
+        base = __shfl(base, 0);
+        const uint64_t at = (uint64_t)base + __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && at < cap) out[at] = x.w[0];
+    }
+}
+
+void BucketView::materialise(bbk_ctx *ctx) {
+    if (!live()) return;
+    keys.alloc(n() * 8 + 16);
+    if (nbuckets) {
+        KernelTimer t(ctx, "compact", (double)D * (4 + 8));
+        hipLaunchKernelGGL(k_compact_narrow<false>, dim3((unsigned)(((uint64_t)nbuckets * 64 + 255) / 256)), dim3(256), 0,
+                           ctx->stream, slots.as<uint32_t>(), nullptr, dcount.as<uint32_t>(), off.as<uint64_t>(), nbuckets,
+                           stride, seg.as<uint16_t>(), hb, keys.as<uint64_t>(), nullptr);
+        check_launch("compact");
+    }
+    if (n_extra)
+        BBK_HIP(bbk::copy_async(keys.as<uint64_t>() + D, extra.p, n_extra * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    release_slots();
+}
+
+// ------------------------------------------------------------------------------------------
 // host orchestration
 // ------------------------------------------------------------------------------------------
 // ODD on purpose: in the blocked phases thread t reads records t*ITEMS + i, i.e. lanes are ITEMS*W*2
@@ -2886,6 +3059,8 @@ struct MsdKnobs {
         bool xcd_slots = env_u64(getenv("BBK_XCD_SLOTS"), 1) != 0;  // 0: one level-1 fill front per segment, not per XCD
         bool xcd_tiles = env_u64(getenv("BBK_XCD_TILES"), 1) != 0;  // 0: level-2 workgroups in plain tile order
         bool no_narrow_b = getenv("BBK_NO_NARROW_B") != nullptr;  // 8-byte records after level 1 of stage B
+        // stage A hands stage B the dense 8-byte array, not its buckets (BucketView)
+        bool no_bucket_handoff = getenv("BBK_NO_BUCKET_HANDOFF") != nullptr;
         // k_part_reads_narrow as that many persistent workgroups per CU (0: one workgroup per tile)
         uint32_t nw_wgs_per_cu = (uint32_t)env_u64(getenv("BBK_NW_WGS_PER_CU"), 0);
     };
@@ -2910,6 +3085,7 @@ enum class Outcome {
     TooBig,          // more records than one pass takes: run_all splits the input into ranges of the prefix space
     SlotsGaveUp,     // the hash slot mode overflowed: exact histograms
     KeySlotsGaveUp,  // the key slots of the ordering pass did not hold (skewed key space): exact histograms
+    NeedDense,       // the input is a BucketView and the pass cannot read it in place: materialise it, run again
 };
 
 // Records of a call: reads (rd, see msd_sort_reduce) or a key array (keys[, vals], n)
@@ -2919,6 +3095,7 @@ struct MsdInput {
     const uint32_t *vals;
     uint64_t n;
     bool with_mask;
+    BucketView *view = nullptr;  // keys == nullptr: the canonical keys of an expanded input, left in stage A's buckets
 };
 
 // f(std::integral_constant<int, OP>) for the runtime reduce op
@@ -3236,6 +3413,7 @@ struct MsdRunner {
             }
             P = R.plan(N, n_chunks, from_reads, has_val, sel, has_dst);
             N = P.N;
+            if (in.view && !view_level1()) return Outcome::NeedDense;
             if (P.too_deep) {  // leave to the LSD path
                 if (verbose) fprintf(stderr, "[bbk] msd declines: N=%llu needs more than two levels\n", (unsigned long long)N);
                 return Outcome::Declined;
@@ -3248,6 +3426,11 @@ struct MsdRunner {
             if (auto r = overflow()) return *r;
             compact();
             return Outcome::Done;
+        }
+
+        // the key-slot level 1 reads a BucketView in place (every other pass takes the dense array)
+        bool view_level1() const {
+            return W == 1 && !P.too_deep && P.kslots && R.expand_k && !ranged && !has_dst && !R.even_part && !has_val;
         }
 
         Outcome empty() {
@@ -3394,12 +3577,74 @@ struct MsdRunner {
                 if (from_reads)
                     R.template launch_part_reads<false>("k_part_reads", pb, P.ntiles1, has_val, S, L1, nullptr,
                                                         cur1.as<uint32_t>(), bufA.as<Key<W>>(), valA.as<uint32_t>());
+                else if (in.view)
+                    level1_from_view();
                 else
                     R.template scatter_keys<true>(has_val, "k_part_l1", pb, P.ntiles1, (const Key<W> *)in.keys, in.vals, M1, L1,
                                    cur1.as<uint32_t>(), bufA.as<Key<W>>(), valA.as<uint32_t>());
             }
-            if (P.slots) return slot_fills();
-            return std::nullopt;
+            if (!P.slots) return std::nullopt;
+            auto r = slot_fills();
+            if (in.view && !r) {  // level 1 holds: the buckets are no longer needed (a later give-up: rebuild_view)
+                in.view->release_slots();
+                if (verbose) fprintf(stderr, "[bbk] msd key slots: level 1 read stage A's buckets (%llu + %llu keys)\n",
+                                     (unsigned long long)in.view->D, (unsigned long long)in.view->n_extra);
+            }
+            return r;
+        }
+
+        // level 1 of the key slots over a BucketView: the buckets' keys, then the overflow path's (dense) into the same
+        // slots and cursors
+        void level1_from_view() {
+            if constexpr (W == 1) {
+                BucketView &v = *in.view;
+                const uint32_t half = kPartTileK / 2;
+                const uint32_t nt = (uint32_t)((v.D + half - 1) / half);
+                if (nt) {
+                    DevBuf vdesc((size_t)nt * sizeof(uint2) + 16);
+                    hipLaunchKernelGGL(k_view_tile_desc, dim3((nt + 255) / 256), dim3(256), 0, ctx->stream,
+                                       v.off.as<uint64_t>(), v.nbuckets, v.D, half, nt, vdesc.as<uint2>());
+                    check_launch("k_view_tile_desc");
+                    TileMap Mv = M1;
+                    Mv.n = 2 * v.D;
+                    Mv.ntiles = nt;
+                    R.launch(R.expand_tag ? k_part_view<true> : k_part_view<false>, "k_part_view",
+                             (double)v.D * 4 + 2.0 * (double)v.D * rec, nt, PartCfg<1>::THREADS, part_view_smem(),
+                             v.slots.as<uint32_t>(), v.off.as<uint64_t>(), v.seg.as<uint16_t>(), vdesc.as<uint2>(),
+                             v.stride, v.hb, Mv, L1, cur1.as<uint32_t>(), bufA.as<Key<1>>());
+                }
+                if (v.n_extra) {
+                    TileMap Me = M1;
+                    Me.n = 2 * v.n_extra;
+                    const uint32_t nte = (uint32_t)((Me.n + kPartTileK - 1) / kPartTileK);
+                    R.template scatter_keys<true>(false, "k_part_l1", rec_bytes(v.n_extra) + rec_bytes(Me.n), nte,
+                                                  v.extra.as<Key<W>>(), nullptr, Me, L1, cur1.as<uint32_t>(),
+                                                  bufA.as<Key<W>>(), nullptr);
+                }
+            }
+        }
+
+        // a key-slot give-up after level 1 released the view's buckets: the canonical keys again, from level 1's records
+        Outcome give_up_key_slots() {
+            if constexpr (W == 1) {
+                if (in.view && !in.view->live() && !in.view->keys.p) {
+                    BucketView &v = *in.view;
+                    const uint64_t n = v.n();
+                    v.keys.alloc(n * rec + 16);
+                    DevBuf cnt(16);
+                    BBK_HIP(hipMemsetAsync(cnt.p, 0, 16, ctx->stream));
+                    hipLaunchKernelGGL(k_view_recanon, dim3(P.nsub), dim3(256), 0, ctx->stream, bufA.as<uint64_t>(),
+                                       seg_off.as<uint32_t>(), seg_size.as<uint32_t>(), (int)R.expand_k,
+                                       v.keys.as<uint64_t>(), n, cnt.as<uint32_t>());
+                    check_launch("k_view_recanon");
+                    uint32_t got = 0;
+                    BBK_HIP(hipMemcpyAsync(&got, cnt.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+                    BBK_HIP(hipStreamSynchronize(ctx->stream));
+                    BBK_REQUIRE(got == n, BBK_ERR_INTERNAL, "canonical keys rebuilt from level 1: %u of %llu", got,
+                                (unsigned long long)n);
+                }
+            }
+            return Outcome::KeySlotsGaveUp;
         }
 
         // slot mode: the level-1 cursors tell what every segment received
@@ -3610,7 +3855,7 @@ struct MsdRunner {
                 if (tot != N) {
                     if (verbose) fprintf(stderr, "[bbk] msd key slots: %llu of %llu records placed, exact mode\n",
                                          (unsigned long long)tot, (unsigned long long)N);
-                    return Outcome::KeySlotsGaveUp;
+                    return give_up_key_slots();
                 }
                 slot_off.alloc(((size_t)nbuckets + 1) * 4 + 16);
                 hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
@@ -3651,7 +3896,7 @@ struct MsdRunner {
                                      ctr[2], ctr[3]);
                 out.keys.release();
                 out.vals.release();
-                return Outcome::KeySlotsGaveUp;
+                return give_up_key_slots();
             }
             if (verbose) fprintf(stderr, "[bbk] msd direct output withdrawn (flagged=%u dup=%u): in-place pass\n", ctr[2], ctr[3]);
             if (!has_dst) {
@@ -3917,6 +4162,40 @@ struct MsdRunner {
             return std::nullopt;
         }
 
+        // Narrow stage A whose caller asked for a BucketView: the buckets stay where they are, no compaction.  Not when
+        // the device could not hold the slots beside stage B's buffers (they take ~4x the dense array).
+        bool hand_off_view(uint64_t D, DevBuf &d64) {
+            if (!out.want_view) return false;
+            const char *why = nullptr;
+            if (W != 1 || !P.narrow || out_vals || has_dst || ranged) why = "not a narrow pass";
+            else if (R.knobs.once.no_bucket_handoff) why = "BBK_NO_BUCKET_HANDOFF";
+            size_t fr = 0, tot = 0;
+            const size_t more = bufB.bytes > D * rec ? bufB.bytes - D * rec : 0;
+            if (!why) {
+                BBK_HIP(hipMemGetInfo(&fr, &tot));
+                if (more > fr) why = "device memory";
+            }
+            if (verbose)
+                fprintf(stderr, "[bbk] msd hand-off to stage B: %s (%llu keys, buckets %.0f MB, dense %.0f MB)%s%s\n",
+                        why ? "dense array" : "bucket view", (unsigned long long)out.n, bufB.bytes / 1e6, out.n * rec / 1e6,
+                        why ? ": " : "", why ? why : "");
+            if (why) return false;
+            BucketView &v = out.view;
+            v.slots = std::move(bufB);
+            v.dcount = std::move(dcount);
+            v.off = std::move(d64);
+            v.seg = std::move(bseg);
+            v.nbuckets = nbuckets;
+            v.stride = P.stride2;
+            v.hb = P.nw_hb;
+            v.D = D;
+            v.n_extra = extra.n;
+            if (extra.n) v.extra = std::move(extra.keys);
+            out.nbuckets = 0;
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            return true;
+        }
+
         // ---- dense output: scan of the bucket counts + compaction.  (Slot mode: overflowing buckets wrote nothing and
         // count 0 here; their records are in `extra`, appended.)  Exact HASH mode also gets the bucket table.
         void compact() {
@@ -3927,6 +4206,7 @@ struct MsdRunner {
             const uint64_t D = exclusive_scan_u64(ctx, d64.as<uint64_t>(), d64.as<uint64_t>(), nbuckets);
             if (P.slots) BBK_REQUIRE(D + extra.n <= N, BBK_ERR_INTERNAL, "more distinct records than records");
             out.n = D + (P.slots ? extra.n : 0);
+            if (hand_off_view(D, d64)) return;
             if (!has_dst) {
                 out.keys.alloc(out.n * rec + 16);
                 if (out_vals) out.vals.alloc(out.n * 4 + 16);
@@ -3968,10 +4248,17 @@ struct MsdRunner {
     // One pass over the input, or over one range of its prefix space (sel), under the retry policy: a slot mode that
     // gave up stays off for the rest of the call, and the pass is rerun with exact histograms.  (The hash slots need
     // the HASH prefix, the key slots KEYS / REF: a pass gives up at most one of them.)
-    Outcome run_retrying(const MsdInput &in, MsdOutput &out, const Sel &sel = Sel(), Dst dst = Dst(),
+    // A BucketView input that a pass cannot (or no longer) read in place continues as the dense array.
+    Outcome run_retrying(const MsdInput &in0, MsdOutput &out, const Sel &sel = Sel(), Dst dst = Dst(),
                          uint64_t *n_records = nullptr) {
+        MsdInput in = in0;
         for (;;) {
             const Outcome r = Pass(*this, in, out, sel, dst).run(n_records);
+            if (in.view && r != Outcome::Done) {
+                if (knobs.verbose) fprintf(stderr, "[bbk] msd: stage A's buckets materialised (outcome %d)\n", (int)r);
+                in = dense_of(in);
+            }
+            if (r == Outcome::NeedDense) continue;
             if (r == Outcome::SlotsGaveUp) slots_ok = false;
             else if (r == Outcome::KeySlotsGaveUp) kslots_ok = false;
             else return r;
@@ -4298,10 +4585,21 @@ struct MsdRunner {
     // run() plus the split into ranges of the prefix space when the input holds more records than one pass takes
     // (what the reference does with bounded buffers, repeated DumpBuffers rounds and the run merge,
     // kmer_splitter.hpp:73-167, kmer_index_builder.hpp:281-365).
-    bool run_all(const MsdInput &in, MsdOutput &out) {
+    MsdInput dense_of(const MsdInput &in) {
+        if (!in.view) return in;
+        in.view->materialise(ctx);  // (no-op once the dense array exists)
+        BBK_REQUIRE(in.view->keys.p, BBK_ERR_INTERNAL, "bucket view neither live nor materialised");
+        MsdInput d = in;
+        d.keys = in.view->keys.p;
+        d.view = nullptr;
+        return d;
+    }
+
+    bool run_all(const MsdInput &in0, MsdOutput &out) {
         uint64_t Nrec = 0;  // records of the whole input, when it is too big for one pass
-        const Outcome r = run_retrying(in, out, Sel(), Dst(), &Nrec);
+        const Outcome r = run_retrying(in0, out, Sel(), Dst(), &Nrec);
         if (r != Outcome::TooBig) return r == Outcome::Done;
+        const MsdInput in = dense_of(in0);
         std::vector<Sel> ranges;
         if (!plan_ranges(in.rd, in.keys, Nrec, ranges)) return false;
         return dmode == MSD_HASH ? run_hash_ranges(in, ranges, out) : run_key_ranges(in, Nrec, ranges, out);
@@ -4333,8 +4631,12 @@ static bool msd_run(bbk_ctx *ctx, unsigned k, int dmode, int op, const MsdInput 
 
 bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, int dmode, int op, const bbk_reads *rd, const void *d_keys,
                      const uint32_t *d_vals, uint64_t n, bool with_mask, MsdOutput &out, unsigned tag_bits,
-                     bool assume_distinct, unsigned expand_k) {
-    const MsdInput in{rd, d_keys, d_vals, n, with_mask};
+                     bool assume_distinct, unsigned expand_k, BucketView *view) {
+    BBK_REQUIRE(!view || (!d_keys && !d_vals && !rd && expand_k && n == view->n() && (view->live() || view->keys.p)),
+                BBK_ERR_INTERNAL, "bucket view input: expanded canonical keys only");
+    MsdInput in{rd, d_keys, d_vals, n, with_mask};
+    if (view && !view->live()) in.keys = view->keys.p;  // already dense
+    else in.view = view;
     if (tag_bits) {
         // the tag sits right above the k-mer (bits [2k, 2k + tag_bits)): sort as a (k + tag_bits/2)-mer, clear the
         // tag on the way out

@@ -26,6 +26,9 @@ FAMILY = [  # rocprof kernel symbol -> the name bbk_ctx_profile_get / bench.py u
     (r"k_part_reads_narrow", "k_part_reads_narrow"),
     (r"k_part_narrow2", "k_part_narrow2"),
     (r"k_bucket_hash32", "k_bucket_hash32"),
+    (r"k_part_view", "k_part_view"),  # stage B's level 1 over stage A's buckets (BucketView)
+    (r"k_view_tile_desc", "k_view_tile_desc"),
+    (r"k_view_recanon", "k_view_recanon"),
     (r"k_part_reads<\d, (true|false), false>", "k_part_reads"),
     (r"k_part_reads<\d, (true|false), true>", "k_part_reads_hist"),
     (r"k_part<\d, (true|false), false, true, false>", "k_part_l1"),
