@@ -301,6 +301,36 @@ int bbk_unitigs_write_fastg(bbk_ctx *ctx, const bbk_unitigs *u, const char *path
 int bbk_unitigs_write_spades(bbk_ctx *ctx, const bbk_unitigs *u, const char *basename);
 void bbk_unitigs_free(bbk_unitigs *u);
 
+/* ---- per-sample edge abundance profiles: replaces unitig-coverage (projects/unitig_coverage/main.cpp:40-80):
+ *      the EdgeIndex of the (k+1)-mers of a graph (common/assembly_graph/index/edge_index_builders.hpp), the
+ *      BasicSequenceMapper that maps each read onto it (common/modules/alignment/sequence_mapper.hpp:288-404) and
+ *      EdgeProfileStorage::Fill / Save (projects/unitig_coverage/profile_storage.{hpp,cpp}) ------------------------- */
+typedef struct bbk_edgeindex bbk_edgeindex; /* every (k+1)-mer of every segment, canonical, with its place     */
+typedef struct bbk_profiles bbk_profiles;   /* raw abundances, segments x samples u64, in HBM                 */
+/* GFA1 graph (io/graph/gfa_reader.cpp): S lines are the segments in file order (a segment is the edge of its forward
+ * strand plus its conjugate; a palindromic segment is its own conjugate), L lines its links.  BBK_ERR_ARG (with a
+ * message) for an even k, a link overlap other than <k>M or one whose bases do not overlap, a segment shorter than
+ * k + 1, a base other than ACGT, and a (k+1)-mer held twice by the graph (counting both orientations): the mapping
+ * relies on each (k+1)-mer having one place, as the graphs spades-gbuilder writes do. */
+int bbk_edgeindex_from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out);
+/* the same from an in-process graph; segment i is named 3 + 2i as bbk_unitigs_write_gfa names it */
+int bbk_edgeindex_from_unitigs(bbk_ctx *ctx, const bbk_unitigs *u, bbk_edgeindex **out);
+uint64_t bbk_edgeindex_segments(const bbk_edgeindex *ix);
+uint64_t bbk_edgeindex_size(const bbk_edgeindex *ix); /* (k+1)-mers indexed */
+void bbk_edgeindex_free(bbk_edgeindex *ix);
+/* Profiles of n_samples samples over the segments of ix (which must outlive them), all zero.  push_reads maps one
+ * batch of reads of one sample: every read and, implicitly, its reverse complement (io::EasyStream followed_by_rc,
+ * io/reads/io_helper.cpp:19-32); the reads have gone through LongestValid already (bbk_reads).  raw[segment][sample]
+ * += the mapped-range sizes of MapSequence on the segment's edge and its conjugate. */
+int bbk_profiles_begin(bbk_ctx *ctx, const bbk_edgeindex *ix, unsigned n_samples, bbk_profiles **out);
+int bbk_profiles_push_reads(bbk_profiles *p, unsigned sample, const bbk_reads *reads);
+/* h_raw: segments x samples u64, segment-major */
+int bbk_profiles_export_raw(bbk_ctx *ctx, const bbk_profiles *p, uint64_t *h_raw);
+/* EdgeProfileStorage::Save (profile_storage.cpp:44-52): "<name>\t" then raw / (|seq| - k) of every sample as
+ * std::ostream prints a double (%g), each followed by "\t", then "\n"; one line per segment in S-line order. */
+int bbk_profiles_write(bbk_ctx *ctx, const bbk_profiles *p, const char *path);
+void bbk_profiles_free(bbk_profiles *p);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

@@ -1,0 +1,636 @@
+// edgeprof.hip -- per-sample edge abundance profiles: the device side of unitig-coverage.
+//
+// Replaces (reference projects/unitig_coverage/, common/modules/alignment/sequence_mapper.hpp:288-404):
+//   EdgeIndex over the (k+1)-mers of every edge and its conjugate -> k_ep_emit + radix sort + prefix table: one
+//     canonical (k+1)-mer per record with (segment, offset on the forward strand, offset on the reverse strand, flags)
+//   BasicSequenceMapper::MapSequence (FindKmer / TryThread / ProcessKmer), run read by read on one thread per sample
+//     -> k_ep_map: one lane per (k+1)-mer position, each position settled from its own lookup and its predecessor's
+//   EdgeProfileStorage::Fill / Save (profile_storage.hpp:71-93, profile_storage.cpp:44-52) -> 64-bit atomics per run of
+//     equal segment inside a wave, and a host writer of the reference's text.
+//
+// Position-local form of MapSequence.  With every (k+1)-mer present once in the graph (both orientations counted) and
+// every link a true k-overlap, TryThread succeeds exactly when FindKmer would find the next (k+1)-mer and merge it into
+// the current range, so the size the read adds to the range of position i depends only on positions i-1 and i:
+//   delta_i = 0                      position i not in the graph
+//           = off_i - off_{i-1}      i-1 found on the same oriented edge and off_i >= off_{i-1}
+//           = 1                      otherwise
+// One exception: a one-(k+1)-mer homopolymer edge c^(k+1) linked to itself.  Inside a run of c there, TryThread leaves
+// the end of the edge and re-enters it at offset 0 with a new range of size 1, where the merge rule says 0 (off_i ==
+// off_{i-1}).  Such edges carry a flag and take 1 (exact when every junction is an edge end, as in a condensed graph).
+// A read and its reverse complement (EasyStream followed_by_rc) map to conjugate edges: contrib(rc r, X) =
+// contrib(r, conj X), so one pass over the forward read adds both strands to the segment; a self-conjugate segment gets
+// both terms from the same edge and takes every delta twice.
+#include <hip/hip_runtime.h>
+
+#include <omp.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "bbk_internal.h"
+#include "kmer_ops.h"
+
+namespace bbk {
+
+// one record of the edge index, 16 bytes: one dwordx4 load per found position
+struct EdgePos {
+    uint32_t seg;     // segment (S-line order)
+    uint32_t off_fw;  // offset of the (k+1)-mer on the forward strand of the segment
+    uint32_t off_rc;  // offset of its reverse complement on the reverse strand (len - 1 - off_fw)
+    uint32_t flags;   // kEpCanonFw | kEpSelfConj | kEpLoop1
+};
+constexpr uint32_t kEpCanonFw = 1u;   // the canonical key is the forward window of the segment
+constexpr uint32_t kEpSelfConj = 2u;  // segment == its reverse complement
+constexpr uint32_t kEpLoop1 = 4u;     // segment is one homopolymer (k+1)-mer linked to itself
+
+unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
+                            bool *wide);
+unsigned unitigs_k(const bbk_unitigs *u);
+
+}  // namespace bbk
+
+struct bbk_edgeindex {
+    unsigned k = 0, k1 = 0, W = 0;
+    uint64_t n_seg = 0, n = 0;           // segments, indexed (k+1)-mers
+    std::vector<std::string> names;      // segment names
+    std::vector<uint64_t> len;           // (k+1)-mers per segment = |seq| - k (the reference's g.length(e))
+    bbk::DevBuf keys;                    // n * W u64, ascending canonical (k+1)-mers
+    bbk::DevBuf pos;                     // n EdgePos
+    bbk::DevBuf prefix;
+    unsigned prefix_bits = 0;
+    bool prefix_wide = false;
+};
+
+struct bbk_profiles {
+    bbk_ctx *ctx = nullptr;
+    const bbk_edgeindex *ix = nullptr;
+    unsigned samples = 0;
+    bbk::DevBuf raw;  // n_seg * samples u64, [segment][sample]
+};
+
+namespace bbk {
+
+// ---- index ------------------------------------------------------------------------------------------------------------
+
+// One lane per emitted (k+1)-mer.  A self-conjugate segment holds x at p and rc(x) at len-1-p, one key: only the
+// positions p <= len-1-p are emitted (emit_off counts them), so any equal keys left after the sort are duplicates.
+template <int W>
+__global__ __launch_bounds__(256) void k_ep_emit(const uint64_t *__restrict__ words, const uint64_t *__restrict__ woff,
+                                                const uint64_t *__restrict__ emit_off, const uint32_t *__restrict__ seg_len,
+                                                const uint32_t *__restrict__ seg_flags, uint64_t n_seg, uint64_t n, int k1,
+                                                Key<W> *__restrict__ keys, uint32_t *__restrict__ idx,
+                                                EdgePos *__restrict__ pos) {
+    const uint64_t j = BBK_GID();
+    if (j >= n) return;
+    uint64_t lo = 0, hi = n_seg - 1;  // last segment with emit_off[s] <= j (segments emit at least one record)
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (emit_off[mid] <= j) lo = mid;
+        else hi = mid - 1;
+    }
+    const uint32_t p = (uint32_t)(j - emit_off[lo]);
+    const Key<W> x = kmer_extract<W>(words + woff[lo], p, k1);
+    const Key<W> r = kmer_rc<W>(x, k1);
+    const bool fw = !kmer_less_nucl<W>(r, x);
+    key_store<W>(&keys[j], key_select<W>(fw, x, r));
+    idx[j] = (uint32_t)j;
+    EdgePos e;
+    e.seg = (uint32_t)lo;
+    e.off_fw = p;
+    e.off_rc = seg_len[lo] - 1u - p;
+    e.flags = seg_flags[lo] | (fw ? kEpCanonFw : 0u);
+    pos[j] = e;
+}
+
+// records in key order; equal neighbours are duplicated (k+1)-mers (the smallest such index is reported)
+template <int W>
+__global__ __launch_bounds__(256) void k_ep_gather(const Key<W> *__restrict__ keys, const uint32_t *__restrict__ idx,
+                                                  const EdgePos *__restrict__ pos, uint64_t n, EdgePos *__restrict__ out,
+                                                  unsigned long long *__restrict__ first_dup) {
+    const uint64_t i = BBK_GID();
+    if (i >= n) return;
+    out[i] = pos[idx[i]];
+    if (i > 0 && key_eq<W>(key_load<W>(&keys[i]), key_load<W>(&keys[i - 1]))) atomicMin(first_dup, (unsigned long long)i);
+}
+
+// ---- mapping ----------------------------------------------------------------------------------------------------------
+
+__global__ void k_ep_npos(const uint32_t *__restrict__ len, uint64_t n, uint32_t k1, uint64_t *__restrict__ npos) {
+    const uint64_t r = BBK_GID();
+    if (r < n) npos[r] = len[r] >= k1 ? (uint64_t)(len[r] - k1 + 1) : 0ull;
+}
+
+constexpr int kMapWaves = 4;     // waves per block
+constexpr int kMapStep = 63;     // new positions per wave: lane 0 is the predecessor of lane 1
+constexpr uint32_t kNoSeg = ~0u;
+
+// One wave = 63 consecutive (k+1)-mer positions of the concatenated reads (lanes 1..63) plus the position before the
+// first (lane 0, looked up only to be the predecessor).  Every lane finds its read in pos_off, extracts and
+// canonicalises its (k+1)-mer and looks it up; lane i takes (edge, offset, found) of lane i-1 by a shuffle and settles
+// delta_i (header comment).  The deltas are summed per segment inside the wave (peeling one segment at a time: a wave
+// usually covers one or two), and one 64-bit atomic per segment adds the sum to raw[segment * S + sample].
+template <int W>
+__global__ __launch_bounds__(256) void k_ep_map(const uint64_t *__restrict__ words, const uint64_t *__restrict__ woff,
+                                               const uint32_t *__restrict__ rlen, const uint64_t *__restrict__ pos_off,
+                                               uint64_t n_reads, uint64_t total, int k1, const Key<W> *__restrict__ keys,
+                                               const EdgePos *__restrict__ epos, PrefixTable P,
+                                               unsigned long long *__restrict__ raw, uint32_t samples, uint32_t sample) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (((uint64_t)blockIdx.y * gridDim.x) + blockIdx.x) * kMapWaves + (threadIdx.x >> 6);
+    const uint64_t g0 = wave * kMapStep;
+    if (g0 >= total) return;  // wave-uniform
+    const int64_t g = (int64_t)g0 + lane - 1;
+    const bool valid = g >= 0 && (uint64_t)g < total;
+
+    bool found = false;
+    uint32_t seg = kNoSeg, off = 0, flags = 0;
+    uint64_t oe = ~0ull;  // oriented edge: 2 * seg + (minus strand of a segment that is not self-conjugate)
+    uint32_t p = 0;       // position inside the read
+    if (valid) {
+        uint64_t lo = 0, hi = n_reads - 1;  // last read with pos_off[r] <= g: the read that holds position g
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (pos_off[mid] <= (uint64_t)g) lo = mid;
+            else hi = mid - 1;
+        }
+        p = (uint32_t)((uint64_t)g - pos_off[lo]);
+        const uint64_t *rw = words + woff[lo];
+        Key<W> q;
+        bool minimal;
+        if constexpr (W == 1) {
+            q = kmer_extract_canon1(rw, p, k1, (rlen[lo] - 1u) >> 5, &minimal);
+        } else {
+            const Key<W> x = kmer_extract<W>(rw, p, k1);
+            const Key<W> r = kmer_rc<W>(x, k1);
+            minimal = !kmer_less_nucl<W>(r, x);
+            q = key_select<W>(minimal, x, r);
+        }
+        const uint64_t j = table_find<W>(keys, P, q);
+        if (j != kNotFound) {
+            const EdgePos e = epos[j];
+            found = true;
+            seg = e.seg;
+            flags = e.flags;
+            // the read's (k+1)-mer is the segment's forward window when it is as canonical as the stored one
+            const bool minus = minimal != ((e.flags & kEpCanonFw) != 0);
+            off = minus ? e.off_rc : e.off_fw;
+            oe = 2ull * e.seg + ((minus && !(e.flags & kEpSelfConj)) ? 1u : 0u);
+        }
+    }
+    const uint64_t pred_oe = __shfl_up(oe, 1);
+    const uint32_t pred_off = __shfl_up(off, 1);
+    const int pred_found = __shfl_up((int)found, 1);
+    uint64_t c = 0;
+    if (lane > 0 && found) {
+        uint64_t d = 1;
+        if (p > 0 && pred_found && pred_oe == oe && off >= pred_off)
+            d = off > pred_off ? (uint64_t)(off - pred_off) : ((flags & kEpLoop1) ? 1u : 0u);
+        c = d << ((flags & kEpSelfConj) ? 1 : 0);
+    }
+    bool pending = c != 0;
+    uint64_t todo = __ballot(pending);
+    while (todo) {
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const uint32_t s0 = __shfl(seg, leader);
+        const bool mine = pending && seg == s0;
+        uint64_t v = mine ? c : 0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if (lane == leader) atomicAdd(&raw[(uint64_t)s0 * samples + sample], (unsigned long long)v);
+        pending = pending && !mine;
+        todo = __ballot(pending);
+    }
+}
+
+// ---- host side --------------------------------------------------------------------------------------------------------
+
+static inline char comp_base(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; }
+
+// link: segment a in orientation oa (true = '+') followed by segment b in orientation ob
+struct HostLink {
+    uint32_t a, b;
+    bool oa, ob;
+};
+
+// the graph on the host: segment names, their ACGT sequences back to back (off: n + 1 entries), links
+struct HostGraph {
+    std::vector<std::string> names;
+    std::string bases;
+    std::vector<uint64_t> off{0};
+    std::vector<HostLink> links;
+};
+
+template <int W>
+static void run_emit(bbk_ctx *ctx, const bbk_reads *sr, const DevBuf &emit_off, const DevBuf &slen, const DevBuf &sflags,
+                     uint64_t n_seg, uint64_t n, unsigned k1, DevBuf &keys, DevBuf &idx, DevBuf &pos) {
+    hipLaunchKernelGGL(k_ep_emit<W>, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, sr->d_words, sr->d_woff,
+                       emit_off.as<uint64_t>(), slen.as<uint32_t>(), sflags.as<uint32_t>(), n_seg, n, (int)k1,
+                       keys.as<Key<W>>(), idx.as<uint32_t>(), pos.as<EdgePos>());
+    check_launch("k_ep_emit");
+}
+
+template <int W>
+static void run_gather(bbk_ctx *ctx, const DevBuf &keys, const DevBuf &idx, const DevBuf &pos, uint64_t n, DevBuf &out,
+                       DevBuf &dup) {
+    hipLaunchKernelGGL(k_ep_gather<W>, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, keys.as<Key<W>>(),
+                       idx.as<uint32_t>(), pos.as<EdgePos>(), n, out.as<EdgePos>(), dup.as<unsigned long long>());
+    check_launch("k_ep_gather");
+}
+
+// the index of a graph held on the host, checked as the position-local form needs
+static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g) {
+    BBK_REQUIRE(k >= 1 && k < BBK_MAX_K && k % 2 == 1, BBK_ERR_ARG, "edge index: k = %u must be odd and < %d", k, BBK_MAX_K);
+    const uint64_t ns = g.names.size();
+    BBK_REQUIRE(ns > 0, BBK_ERR_ARG, "edge index: the graph has no segments");
+    BBK_REQUIRE(ns < (1ull << 32) - 1, BBK_ERR_ARG, "edge index: too many segments (%llu)", (unsigned long long)ns);
+    const unsigned k1 = k + 1;
+    auto ix = std::make_unique<bbk_edgeindex>();
+    ix->k = k;
+    ix->k1 = k1;
+    ix->W = words_of(k1);
+    ix->n_seg = ns;
+    ix->len.resize(ns);
+    std::vector<uint32_t> hflags(ns, 0), hlen(ns);
+    std::vector<uint64_t> hemit(ns + 1, 0);
+    int64_t bad = -1;
+#pragma omp parallel for schedule(static) num_threads(16)
+    for (int64_t s = 0; s < (int64_t)ns; ++s) {
+        const char *q = g.bases.data() + g.off[s];
+        const uint64_t n = g.off[s + 1] - g.off[s];
+        if (n < k1 || n - k >= (1ull << 32) - 1) {
+#pragma omp critical
+            bad = bad < 0 || s < bad ? s : bad;
+            continue;
+        }
+        const uint64_t L = n - k;
+        ix->len[s] = L;
+        hlen[s] = (uint32_t)L;
+        bool selfc = true;  // q == rc(q)
+        for (uint64_t i = 0; i < (n + 1) / 2 && selfc; ++i) selfc = q[i] == comp_base(q[n - 1 - i]);
+        if (selfc) hflags[s] |= kEpSelfConj;
+        hemit[s + 1] = selfc ? (L + 1) / 2 : L;
+    }
+    BBK_REQUIRE(bad < 0, BBK_ERR_ARG, "segment %s is %llu bp: shorter than k + 1 = %u or too long", g.names[bad].c_str(),
+                (unsigned long long)(g.off[bad + 1] - g.off[bad]), k1);
+    for (uint64_t s = 0; s < ns; ++s) hemit[s + 1] += hemit[s];
+    // a link is a true k-overlap: the last k bases of a (as oriented) are the first k bases of b
+    const int64_t nl = (int64_t)g.links.size();
+    int64_t bad_link = -1;
+#pragma omp parallel for schedule(static) num_threads(16)
+    for (int64_t j = 0; j < nl; ++j) {
+        const HostLink &l = g.links[j];
+        const char *A = g.bases.data() + g.off[l.a], *B = g.bases.data() + g.off[l.b];
+        const uint64_t la = g.off[l.a + 1] - g.off[l.a], lb = g.off[l.b + 1] - g.off[l.b];
+        bool ok = true;
+        for (unsigned i = 0; i < k && ok; ++i)
+            ok = (l.oa ? A[la - k + i] : comp_base(A[k - 1 - i])) == (l.ob ? B[i] : comp_base(B[lb - 1 - i]));
+        if (!ok) {
+#pragma omp critical
+            bad_link = bad_link < 0 || j < bad_link ? j : bad_link;
+        }
+    }
+    if (bad_link >= 0) {
+        const HostLink &l = g.links[bad_link];
+        BBK_REQUIRE(false, BBK_ERR_ARG, "link %s%c -> %s%c: the %uM overlap does not match the sequences",
+                    g.names[l.a].c_str(), l.oa ? '+' : '-', g.names[l.b].c_str(), l.ob ? '+' : '-', k);
+    }
+    for (const HostLink &l : g.links) {
+        if (l.a != l.b || l.oa != l.ob || ix->len[l.a] != 1) continue;
+        const char *q = g.bases.data() + g.off[l.a];
+        bool homo = true;
+        for (unsigned i = 1; i < k1; ++i) homo = homo && q[i] == q[0];
+        if (homo) hflags[l.a] |= kEpLoop1;
+    }
+    const uint64_t n = hemit[ns];
+    BBK_REQUIRE(n < (1ull << 32), BBK_ERR_ARG, "edge index: %llu (k+1)-mers, at most 2^32 - 1 supported",
+                (unsigned long long)n);
+    ix->n = n;
+    ix->names = std::move(g.names);
+
+    // the segments as a packed read set (one segment per read)
+    bbk_reads *sr = nullptr;
+    int rc = bbk_reads_from_ascii(ctx, g.bases.data(), g.off.data(), ns, &sr);
+    if (rc != BBK_OK) throw Error{rc};
+    std::unique_ptr<bbk_reads, void (*)(bbk_reads *)> sr_guard(sr, bbk_reads_free);
+    std::string().swap(g.bases);
+
+    const unsigned W = ix->W;
+    DevBuf d_emit((ns + 1) * 8), d_len(ns * 4), d_flags(ns * 4);
+    BBK_HIP(hipMemcpyAsync(d_emit.p, hemit.data(), (ns + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    BBK_HIP(hipMemcpyAsync(d_len.p, hlen.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    BBK_HIP(hipMemcpyAsync(d_flags.p, hflags.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    DevBuf tmp(n * W * 8), idx(n * 4), idx_tmp(n * 4), pos(n * sizeof(EdgePos)), dup(8);
+    ix->keys.alloc(n * W * 8);
+    ix->pos.alloc(n * sizeof(EdgePos));
+    {
+        KernelTimer t(ctx, "edgeindex", (double)n * (W * 8 + sizeof(EdgePos) + 4));
+        switch (W) {
+            case 1: run_emit<1>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
+            case 2: run_emit<2>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
+            case 3: run_emit<3>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
+            case 4: run_emit<4>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
+            default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", W);
+        }
+    }
+    sort_records(ctx, (int)W, ix->keys.p, tmp.p, idx.as<uint32_t>(), idx_tmp.as<uint32_t>(), n, key_passes(k1));
+    BBK_HIP(hipMemsetAsync(dup.p, 0xFF, 8, ctx->stream));
+    {
+        KernelTimer t(ctx, "edgeindex", (double)n * (2 * W * 8 + 2 * sizeof(EdgePos) + 4));
+        switch (W) {
+            case 1: run_gather<1>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
+            case 2: run_gather<2>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
+            case 3: run_gather<3>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
+            default: run_gather<4>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
+        }
+    }
+    uint64_t first_dup = ~0ull;
+    BBK_HIP(hipMemcpyAsync(&first_dup, dup.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    if (first_dup != ~0ull) {
+        EdgePos two[2];
+        BBK_HIP(hipMemcpy(two, ix->pos.as<EdgePos>() + first_dup - 1, sizeof(two), hipMemcpyDeviceToHost));
+        BBK_REQUIRE(false, BBK_ERR_ARG,
+                    "duplicated (k+1)-mer: segment %s offset %u and segment %s offset %u hold the same %u-mer (up to "
+                    "reverse complement); the mapping needs every (k+1)-mer of the graph once",
+                    ix->names[two[0].seg].c_str(), two[0].off_fw, ix->names[two[1].seg].c_str(), two[1].off_fw, k1);
+    }
+    ix->prefix_bits = build_prefix_index(ctx, ix->keys.as<uint64_t>(), W, k1, n, ix->prefix, &ix->prefix_wide);
+    return ix.release();
+}
+
+// GFA1 S and L lines (io/graph/gfa_reader.cpp): segment names and sequences in file order, links with a kM overlap
+static void parse_gfa(const char *path, unsigned k, HostGraph &g) {
+    std::string text;
+    {
+        FILE *f = fopen(path, "rb");
+        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open graph %s", path);
+        std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
+        char buf[1 << 20];
+        size_t got;
+        while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
+        BBK_REQUIRE(!ferror(f), BBK_ERR_IO, "reading graph %s failed", path);
+    }
+    static const auto code = [] {
+        std::vector<char> t(256, 0);
+        t['A'] = t['a'] = 'A';
+        t['C'] = t['c'] = 'C';
+        t['G'] = t['g'] = 'G';
+        t['T'] = t['t'] = 'T';
+        return t;
+    }();
+    struct RawLink {
+        const char *a, *b;
+        size_t na, nb;
+        bool oa, ob;
+        uint64_t line;
+    };
+    std::vector<RawLink> raw;
+    const std::string kM = std::to_string(k) + "M";
+    g.bases.reserve(text.size());
+    const char *p = text.data(), *end = p + text.size();
+    const char *fs[7], *fe[7];
+    for (uint64_t lineno = 1; p < end; ++lineno) {
+        const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
+        const char *le = nl ? nl : end;
+        const char *next = nl ? nl + 1 : end;
+        while (le > p && le[-1] == '\r') --le;
+        if (le - p >= 2 && p[1] == '\t' && (p[0] == 'S' || p[0] == 'L')) {
+            int nf = 0;
+            for (const char *f = p; nf < 7;) {
+                const char *t = static_cast<const char *>(memchr(f, '\t', (size_t)(le - f)));
+                fs[nf] = f;
+                fe[nf++] = t ? t : le;
+                if (!t) break;
+                f = t + 1;
+            }
+            auto fld = [&](int i) { return std::string(fs[i], (size_t)(fe[i] - fs[i])); };
+            if (p[0] == 'S') {
+                BBK_REQUIRE(nf >= 3, BBK_ERR_ARG, "%s:%llu: S line without a sequence", path, (unsigned long long)lineno);
+                for (const char *c = fs[2]; c < fe[2]; ++c) {
+                    const char u = code[(unsigned char)*c];
+                    BBK_REQUIRE(u, BBK_ERR_ARG, "%s:%llu: segment %s holds a base other than ACGT ('%c')", path,
+                                (unsigned long long)lineno, fld(1).c_str(), *c);
+                    g.bases.push_back(u);
+                }
+                g.off.push_back(g.bases.size());
+                g.names.push_back(fld(1));
+            } else {
+                BBK_REQUIRE(nf >= 6 && fe[2] - fs[2] == 1 && fe[4] - fs[4] == 1 && (*fs[2] == '+' || *fs[2] == '-') &&
+                                (*fs[4] == '+' || *fs[4] == '-'),
+                            BBK_ERR_ARG, "%s:%llu: malformed L line", path, (unsigned long long)lineno);
+                BBK_REQUIRE(fld(5) == kM, BBK_ERR_ARG,
+                            "%s:%llu: link overlap %s, only %s (a k-overlap at k = %u) is supported", path,
+                            (unsigned long long)lineno, fld(5).c_str(), kM.c_str(), k);
+                raw.push_back({fs[1], fs[3], (size_t)(fe[1] - fs[1]), (size_t)(fe[3] - fs[3]), *fs[2] == '+', *fs[4] == '+',
+                               lineno});
+            }
+        }
+        p = next;
+    }
+    // names: spades-gbuilder's are 3 + 2i in S-line order (graph_core.hpp:228,610-624), taken by value; others by map
+    const uint64_t ns = g.names.size();
+    std::unordered_map<std::string, uint32_t> id;
+    bool by_value = true;
+    for (uint64_t i = 0; i < ns && by_value; ++i) by_value = g.names[i] == std::to_string(3 + 2 * i);
+    if (!by_value) {
+        id.reserve(ns);
+        for (uint64_t i = 0; i < ns; ++i)
+            BBK_REQUIRE(id.emplace(g.names[i], (uint32_t)i).second, BBK_ERR_ARG, "%s: segment %s defined twice", path,
+                        g.names[i].c_str());
+    }
+    auto resolve = [&](const char *s, size_t n, uint32_t *out) {
+        if (by_value) {
+            uint64_t v = 0;
+            for (size_t i = 0; i < n; ++i) {
+                if (s[i] < '0' || s[i] > '9' || v > (1ull << 60)) return false;
+                v = v * 10 + (uint64_t)(s[i] - '0');
+            }
+            if (n == 0 || (n > 1 && s[0] == '0') || v < 3 || (v & 1) == 0 || (v - 3) / 2 >= ns) return false;
+            *out = (uint32_t)((v - 3) / 2);
+            return true;
+        }
+        auto it = id.find(std::string(s, n));
+        if (it == id.end()) return false;
+        *out = it->second;
+        return true;
+    };
+    g.links.resize(raw.size());
+    for (size_t j = 0; j < raw.size(); ++j) {
+        const RawLink &l = raw[j];
+        HostLink &h = g.links[j];
+        BBK_REQUIRE(resolve(l.a, l.na, &h.a) && resolve(l.b, l.nb, &h.b), BBK_ERR_ARG, "%s:%llu: link to an undefined segment",
+                    path, (unsigned long long)l.line);
+        h.oa = l.oa;
+        h.ob = l.ob;
+    }
+}
+
+static void d2h_sync(bbk_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    BBK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+}
+
+template <int W>
+static void run_map(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix,
+                    bbk_profiles *p, unsigned sample) {
+    const int w0bits = (W == 1) ? (int)(2 * ix->k1) : 64;
+    const uint64_t waves = (total + kMapStep - 1) / kMapStep;
+    // bytes the lookups need at the least: one prefix entry, the key and the record per position
+    KernelTimer t(ctx, "edgeprof_map", (double)total * (8.0 * W + sizeof(EdgePos) + 4));
+    hipLaunchKernelGGL(k_ep_map<W>, grid_blocks((waves + kMapWaves - 1) / kMapWaves), dim3(64 * kMapWaves), 0, ctx->stream,
+                       r->d_words, r->d_woff, r->d_len, pos_off.as<uint64_t>(), r->n, total, (int)ix->k1,
+                       ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(),
+                       PrefixTable{ix->prefix.p, w0bits - (int)ix->prefix_bits, ix->prefix_wide ? 1 : 0},
+                       p->raw.as<unsigned long long>(), p->samples, sample);
+    check_launch("k_ep_map");
+}
+
+static size_t fmt_line(char *dst, size_t cap, const std::string &name, const uint64_t *raw, unsigned S, uint64_t len) {
+    size_t o = 0;
+    o += (size_t)snprintf(dst + o, cap - o, "%s\t", name.c_str());
+    for (unsigned s = 0; s < S; ++s) o += (size_t)snprintf(dst + o, cap - o, "%g\t", (double)raw[s] / (double)len);
+    dst[o++] = '\n';
+    return o;
+}
+
+}  // namespace bbk
+
+using namespace bbk;
+
+extern "C" {
+
+int bbk_edgeindex_from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && path && out, BBK_ERR_ARG, "bbk_edgeindex_from_gfa: NULL argument");
+        BBK_REQUIRE(k >= 1 && k < BBK_MAX_K && k % 2 == 1, BBK_ERR_ARG, "bbk_edgeindex_from_gfa: k = %u must be odd and < %d",
+                    k, BBK_MAX_K);
+        BBK_HIP(hipSetDevice(ctx->device));
+        HostGraph g;
+        parse_gfa(path, k, g);
+        *out = build_index(ctx, k, g);
+    });
+}
+
+int bbk_edgeindex_from_unitigs(bbk_ctx *ctx, const bbk_unitigs *u, bbk_edgeindex **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && u && out, BBK_ERR_ARG, "bbk_edgeindex_from_unitigs: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        const uint64_t nu = bbk_unitigs_count(u), nl = bbk_unitigs_links(u);
+        HostGraph g;
+        g.bases.resize(bbk_unitigs_total_bases(u) + 1);
+        g.off.resize(nu + 1);
+        std::vector<uint32_t> hl(4 * nl + 1);
+        int rc = bbk_unitigs_export(ctx, u, &g.bases[0], g.off.data());
+        if (rc == BBK_OK) rc = bbk_unitigs_export_links(ctx, u, hl.data());
+        if (rc != BBK_OK) throw Error{rc};
+        g.names.resize(nu);
+        for (uint64_t i = 0; i < nu; ++i) g.names[i] = std::to_string(3 + 2 * i);  // as bbk_unitigs_write_gfa names them
+        g.links.resize(nl);
+        for (uint64_t l = 0; l < nl; ++l) g.links[l] = {hl[4 * l], hl[4 * l + 2], hl[4 * l + 1] == 1, hl[4 * l + 3] == 1};
+        *out = build_index(ctx, unitigs_k(u), g);
+    });
+}
+
+uint64_t bbk_edgeindex_segments(const bbk_edgeindex *ix) { return ix ? ix->n_seg : 0; }
+uint64_t bbk_edgeindex_size(const bbk_edgeindex *ix) { return ix ? ix->n : 0; }
+void bbk_edgeindex_free(bbk_edgeindex *ix) { delete ix; }
+
+int bbk_profiles_begin(bbk_ctx *ctx, const bbk_edgeindex *ix, unsigned n_samples, bbk_profiles **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && ix && out, BBK_ERR_ARG, "bbk_profiles_begin: NULL argument");
+        BBK_REQUIRE(n_samples >= 1, BBK_ERR_ARG, "bbk_profiles_begin: no samples");
+        BBK_HIP(hipSetDevice(ctx->device));
+        auto p = std::make_unique<bbk_profiles>();
+        p->ctx = ctx;
+        p->ix = ix;
+        p->samples = n_samples;
+        const size_t bytes = (size_t)ix->n_seg * n_samples * 8;
+        p->raw.alloc(bytes);
+        BBK_HIP(hipMemsetAsync(p->raw.p, 0, bytes, ctx->stream));
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        *out = p.release();
+    });
+}
+
+int bbk_profiles_push_reads(bbk_profiles *p, unsigned sample, const bbk_reads *reads) {
+    return guarded([&] {
+        BBK_REQUIRE(p && reads, BBK_ERR_ARG, "bbk_profiles_push_reads: NULL argument");
+        BBK_REQUIRE(sample < p->samples, BBK_ERR_ARG, "bbk_profiles_push_reads: sample %u of %u", sample, p->samples);
+        bbk_ctx *ctx = p->ctx;
+        const bbk_edgeindex *ix = p->ix;
+        BBK_HIP(hipSetDevice(ctx->device));
+        const uint64_t n = reads->n;
+        if (n == 0 || ix->n == 0) return;
+        DevBuf pos_off((n + 1) * 8);
+        hipLaunchKernelGGL(k_ep_npos, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, reads->d_len, n, ix->k1,
+                           pos_off.as<uint64_t>());
+        check_launch("k_ep_npos");
+        const uint64_t total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
+        if (total == 0) return;
+        BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
+        switch (ix->W) {
+            case 1: run_map<1>(ctx, reads, pos_off, total, ix, p, sample); break;
+            case 2: run_map<2>(ctx, reads, pos_off, total, ix, p, sample); break;
+            case 3: run_map<3>(ctx, reads, pos_off, total, ix, p, sample); break;
+            default: run_map<4>(ctx, reads, pos_off, total, ix, p, sample); break;
+        }
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // pos_off and the staged total are released on return
+    });
+}
+
+int bbk_profiles_export_raw(bbk_ctx *ctx, const bbk_profiles *p, uint64_t *h_raw) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && p && h_raw, BBK_ERR_ARG, "bbk_profiles_export_raw: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        d2h_sync(ctx, h_raw, p->raw.p, (size_t)p->ix->n_seg * p->samples * 8);
+    });
+}
+
+// EdgeProfileStorage::Save (profile_storage.cpp:44-52): one line per segment (the canonical edge of each S line), in
+// S-line order: name, then raw / length for every sample as std::ostream prints a double (%g), each followed by a tab
+int bbk_profiles_write(bbk_ctx *ctx, const bbk_profiles *p, const char *path) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && p && path, BBK_ERR_ARG, "bbk_profiles_write: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        const bbk_edgeindex *ix = p->ix;
+        const uint64_t ns = ix->n_seg;
+        const unsigned S = p->samples;
+        std::vector<uint64_t> raw((size_t)ns * S);
+        d2h_sync(ctx, raw.data(), p->raw.p, raw.size() * 8);
+        FILE *f = fopen(path, "wb");
+        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path);
+        std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
+        constexpr uint64_t kBlock = 1 << 14;  // segments formatted per task
+        const uint64_t nblocks = (ns + kBlock - 1) / kBlock;
+        const int nt = std::max(1, std::min(omp_get_max_threads(), 16));
+        for (uint64_t b0 = 0; b0 < nblocks; b0 += (uint64_t)nt) {
+            const uint64_t b1 = std::min(nblocks, b0 + (uint64_t)nt);
+            std::vector<std::string> text(b1 - b0);
+            bool fail = false;
+#pragma omp parallel for num_threads(nt) schedule(dynamic, 1)
+            for (int64_t b = (int64_t)b0; b < (int64_t)b1; ++b) {
+                std::string &t = text[(size_t)(b - (int64_t)b0)];
+                std::vector<char> line;
+                for (uint64_t s = (uint64_t)b * kBlock; s < std::min(ns, (uint64_t)(b + 1) * kBlock); ++s) {
+                    const size_t cap = ix->names[s].size() + 2 + (size_t)S * 32;
+                    if (line.size() < cap) line.resize(cap);
+                    t.append(line.data(), fmt_line(line.data(), cap, ix->names[s], &raw[s * S], S, ix->len[s]));
+                }
+            }
+            for (const std::string &t : text)
+                if (!t.empty() && fwrite(t.data(), 1, t.size(), f) != t.size()) fail = true;
+            BBK_REQUIRE(!fail, BBK_ERR_IO, "short write to %s", path);
+        }
+        FILE *fo = guard.release();
+        BBK_REQUIRE(fclose(fo) == 0, BBK_ERR_IO, "closing %s failed", path);
+    });
+}
+
+void bbk_profiles_free(bbk_profiles *p) { delete p; }
+
+}  // extern "C"

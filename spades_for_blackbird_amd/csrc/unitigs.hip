@@ -794,6 +794,8 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
 unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
                             bool *wide);
 
+unsigned unitigs_k(const bbk_unitigs *u) { return u->k; }  // for the edge index (edgeprof.hip)
+
 // One thread per unitig: roll the (k+1)-mers of the sequence, look the canonical form up in the
 // sorted (k+1)-mer count table, add the multiplicities (GraphCoverageFiller,
 // assembly_graph/graph_support/coverage_filling.hpp:44-62).

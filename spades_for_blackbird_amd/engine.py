@@ -27,6 +27,8 @@ SYMBOLS = [
     "bbk_unitigs_build", "bbk_unitigs_build_ex", "bbk_unitigs_to_reads", "bbk_unitigs_add_coverage", "bbk_unitigs_add_coverage_counts", "bbk_unitigs_export_kc", "bbk_unitigs_count", "bbk_unitigs_loops", "bbk_unitigs_total_bases",
     "bbk_unitigs_vertices", "bbk_unitigs_links", "bbk_unitigs_export", "bbk_unitigs_export_links",
     "bbk_unitigs_write_gfa", "bbk_unitigs_write_fasta", "bbk_unitigs_write_fastg", "bbk_unitigs_write_spades", "bbk_unitigs_free",
+    "bbk_edgeindex_from_gfa", "bbk_edgeindex_from_unitigs", "bbk_edgeindex_segments", "bbk_edgeindex_size", "bbk_edgeindex_free",
+    "bbk_profiles_begin", "bbk_profiles_push_reads", "bbk_profiles_export_raw", "bbk_profiles_write", "bbk_profiles_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -166,6 +168,18 @@ def load_library():
         L.bbk_unitigs_write_fastg.argtypes = [vp, vp, C.c_char_p]
         L.bbk_unitigs_write_spades.argtypes = [vp, vp, C.c_char_p]
         L.bbk_unitigs_free.argtypes = [vp]
+        L.bbk_edgeindex_from_gfa.argtypes = [vp, C.c_char_p, C.c_uint, C.POINTER(vp)]
+        L.bbk_edgeindex_from_unitigs.argtypes = [vp, vp, C.POINTER(vp)]
+        L.bbk_edgeindex_segments.restype = u64
+        L.bbk_edgeindex_segments.argtypes = [vp]
+        L.bbk_edgeindex_size.restype = u64
+        L.bbk_edgeindex_size.argtypes = [vp]
+        L.bbk_edgeindex_free.argtypes = [vp]
+        L.bbk_profiles_begin.argtypes = [vp, vp, C.c_uint, C.POINTER(vp)]
+        L.bbk_profiles_push_reads.argtypes = [vp, C.c_uint, vp]
+        L.bbk_profiles_export_raw.argtypes = [vp, vp, vp]
+        L.bbk_profiles_write.argtypes = [vp, vp, C.c_char_p]
+        L.bbk_profiles_free.argtypes = [vp]
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -367,6 +381,18 @@ class Context:
         h = C.c_void_p()
         _check(self._L.bbk_unitigs_build_ex(self._h, ext._h, ref_threads, C.byref(h)))
         return Unitigs(self, h)
+
+    def edgeindex_from_gfa(self, path, k):
+        """(k+1)-mer index of a GFA graph for unitig-coverage: S lines are the segments, L lines must be kM overlaps."""
+        h = C.c_void_p()
+        _check(self._L.bbk_edgeindex_from_gfa(self._h, path.encode(), k, C.byref(h)))
+        return EdgeIndex(self, h)
+
+    def edgeindex_from_unitigs(self, unitigs):
+        """the same index of an in-process graph (segment i named 3 + 2i, as in its GFA)"""
+        h = C.c_void_p()
+        _check(self._L.bbk_edgeindex_from_unitigs(self._h, unitigs._h, C.byref(h)))
+        return EdgeIndex(self, h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -676,3 +702,42 @@ class Unitigs(_Handle):
     def write_spades(self, basename):
         """<basename>.grseq + <basename>.cvr (the SPAdes binary graph of gbuilder --spades)"""
         _check(self._L.bbk_unitigs_write_spades(self.ctx._h, self._h, basename.encode()))
+
+
+class EdgeIndex(_Handle):
+    """every (k+1)-mer of a graph's segments with its place (unitig-coverage's EdgeIndex)"""
+    _free = "bbk_edgeindex_free"
+
+    @property
+    def segments(self):
+        return int(self._L.bbk_edgeindex_segments(self._h))
+
+    def __len__(self):
+        return int(self._L.bbk_edgeindex_size(self._h))
+
+    def profiles(self, n_samples):
+        h = C.c_void_p()
+        _check(self._L.bbk_profiles_begin(self.ctx._h, self._h, n_samples, C.byref(h)))
+        return Profiles(self, h, n_samples)
+
+
+class Profiles(_Handle):
+    """per-sample edge abundance profiles (EdgeProfileStorage): push the reads of each sample, then raw() or write()"""
+    _free = "bbk_profiles_free"
+
+    def __init__(self, index, h, n_samples):
+        super().__init__(index.ctx, h)
+        self.index, self.samples = index, n_samples  # the index must outlive the profiles
+
+    def push(self, sample, reads):
+        _check(self._L.bbk_profiles_push_reads(self._h, sample, reads._h))
+
+    def raw(self):
+        """np.uint64 [segments, samples]: summed mapped-range sizes of every segment's edge and its conjugate"""
+        a = np.zeros((self.index.segments, self.samples), dtype=np.uint64)
+        _check(self._L.bbk_profiles_export_raw(self.ctx._h, self._h, _ptr(a)))
+        return a
+
+    def write(self, path):
+        """the unitig-coverage output file (EdgeProfileStorage::Save)"""
+        _check(self._L.bbk_profiles_write(self.ctx._h, self._h, path.encode()))
