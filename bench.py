@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the k-mer counting path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 21] [--ext-index] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--reads R] [--k 21] [--ext-index] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): distinct k-mers/sec, k=21, 150 bp synthetic reads.
 N=1 workload = BASELINE.json configs[1]: 10 M x 150 bp uniform reads (50x coverage of a
@@ -17,12 +17,17 @@ returns their exit code.  Every rank holds its own 10 M reads of a common genome
 ranks count locally, partition distinct canonical k-mers by owner hash, exchange them with ONE all_to_all_single (the
 only collective on the data path), merge-unique their shard and expand it to both strands.
 
-Extra objects on the JSON line (N=1): "roofline" for the dominant kernel, measured with HIP events on the engine's
-stream inside the timed region; "k55": the same step at k=55 (16-byte keys) with its own roofline; "gfa_build": wall
-seconds of extension index -> unitigs -> GFA on the same reads; "e2e": wall seconds of the two CLI binaries
-(spades-kmercount, spades-gbuilder --gfa) on the same reads written as FASTA to tmpfs, with their phases, next to the
-CPU oracle run end to end (parse included) on a bounded sample; "cpu_baseline": the CPU oracle -- a port of the
-reference's split/sort/unique/merge algorithm -- timed on a bounded sample on this box's host cores.
+A plain run sets up, warms up, times the K steps, dumps (--dump-outputs) and prints the JSON line, which carries
+"kernel_ms_per_step" and "roofline" for the dominant kernel, both measured with HIP events on the engine's stream inside
+the timed region.
+
+--full: after the timed region, also the side measurements that take runs of their own (--no-<name> leaves one out).
+N=1: "k55": the same step at k=55 (16-byte keys) with its own roofline; "metagenome": the step on a skewed community at
+k = 21, 33, 55; "gfa_build": wall seconds of extension index -> unitigs -> GFA on the same reads; "e2e": wall seconds
+of the two CLI binaries (spades-kmercount, spades-gbuilder --gfa) on the same reads written as FASTA to tmpfs, with
+their phases, next to the CPU oracle run end to end (parse included) on a bounded sample; "cpu_baseline": the CPU
+oracle -- a port of the reference's split/sort/unique/merge algorithm -- timed on a bounded sample on this box's host
+cores.  N>1: "gfa_build" of the sharded extension index, and "cpp_one_process_multi_gpu".
 
 --dump-outputs DIR: after the timed steps, the result of the last one (the k-mer set; with --ext-index also the
 extension index) is written to DIR/*.npy as float64, a fixed sample of at most 2^19 records per output, every rank its
@@ -69,13 +74,16 @@ def parse():
     ap.add_argument("--k", type=int, default=21)
     ap.add_argument("--ext-index", action="store_true",
                     help="a step also builds the extension index (BASELINE configs[2] with --reads 100000000 --k 55)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also the side measurements (k55, metagenome, gfa_build, e2e, "
+                         "cpu_baseline; at N>1 the sharded GFA build and the C++ multi-GPU run)")
     ap.add_argument("--cpu-sample-reads", type=int, default=4_000_000)
     ap.add_argument("--e2e-cpu-sample-reads", type=int, default=1_000_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-gfa", action="store_true", help="skip the (untimed-region) GFA-build wall-time measurement")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the CLI wall-time measurement on FASTA input")
-    ap.add_argument("--no-k55", action="store_true", help="skip the k=55 (16-byte keys) object")
-    ap.add_argument("--no-meta", action="store_true", help="skip the skewed-metagenome (configs[4] shape) object")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle object")
+    ap.add_argument("--no-gfa", action="store_true", help="with --full: skip the GFA-build wall-time measurement")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the CLI wall-time measurement on FASTA input")
+    ap.add_argument("--no-k55", action="store_true", help="with --full: skip the k=55 (16-byte keys) object")
+    ap.add_argument("--no-meta", action="store_true", help="with --full: skip the skewed-metagenome (configs[4] shape) object")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the last timed step computed to DIR/<name>.npy (float64; large outputs sampled)")
     args = ap.parse_args()
@@ -621,7 +629,7 @@ def main():
     # N>1: the second half of the metric over all ranks (configs[3] shape): sharded extension index -> gathered on
     # rank 0 -> unitigs + links -> GFA text on tmpfs; one un-timed-region measurement, every rank takes part
     gfa_sharded = None
-    if world > 1 and not args.no_gfa:
+    if args.full and world > 1 and not args.no_gfa:
         import tempfile
         d = "/dev/shm" if os.path.isdir("/dev/shm") else tempfile.gettempdir()
         path = os.path.join(d, "bbk_bench_sharded_%d.gfa" % os.getpid())
@@ -640,7 +648,7 @@ def main():
     # N > 1: the C++ one-process host over RCCL on the same GPUs, once, outside every timed region (rank 0 runs the
     # tools; all ranks hand their device memory back first and wait)
     cpp_multi = None
-    if world > 1 and not args.no_e2e and os.environ.get("BBK_BENCH_CPP_MULTI", "1") != "0":
+    if args.full and world > 1 and not args.no_e2e and os.environ.get("BBK_BENCH_CPP_MULTI", "1") != "0":
         try:
             ctx.trim()
             torch.cuda.empty_cache()
@@ -694,14 +702,15 @@ def main():
         if dump:
             line["dump_outputs"] = dump
         big = args.reads > 20_000_000
+        side = args.full and world == 1  # the side measurements of one GPU, after the timed region
         # the CLIs first: they are separate processes on the same GPU, and with the tens of GB that the k = 55 and
         # metagenome objects leave mapped in this process their device phase was intermittently 0.3-0.5 s instead of 0.03 s
-        if world == 1 and not args.no_e2e and not big:
+        if side and not args.no_e2e and not big:
             try:
                 line["e2e"] = e2e(ctx, reads, args)
             except Exception as ex:  # the headline must not die with a side measurement
                 line["e2e"] = {"error": repr(ex)[:300]}
-        if world == 1 and not args.no_k55 and not big and k != 55:
+        if side and not args.no_k55 and not big and k != 55:
             # the 16-byte-key path in front of the driver: the same step at k=55 on the same reads
             def step55():
                 s = ctx.count(reads, 55, B.BOTH_STRANDS | B.REFERENCE_ORDER)
@@ -712,15 +721,15 @@ def main():
                            "value": n55 / (dt55 / 2), "unit": "distinct k-mers/s", "dtype": "u128",
                            "kernel_ms_per_step": {f: v["ms"] / 2 for f, v in prof55.items()},
                            "roofline": roofline_of(prof55, 2, None, dt55 / 2 * 1e3)}
-        if world == 1 and not args.no_meta and not big:
+        if side and not args.no_meta and not big:
             line["metagenome"] = metagenome(ctx, args, B, fence)
-        if world == 1 and not args.no_gfa and not big:
+        if side and not args.no_gfa and not big:
             line["gfa_build"] = gfa_build(ctx, reads, k)
         if gfa_sharded:
             line["gfa_build"] = gfa_sharded
         if cpp_multi:
             line["cpp_one_process_multi_gpu"] = cpp_multi
-        if world == 1 and not args.no_cpu_baseline:
+        if side and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(ctx, args, B)
         print(json.dumps(line), flush=True)
     if sharded:

@@ -1,6 +1,6 @@
-"""GPU: `bench.py --steps K` times K steps, and `bench.py --dump-outputs DIR` writes what the last timed step computed:
-what the engine returns for the same seeded reads, the k-mer set (and with --ext-index the extension index) at the
-dumped record positions, within 64 MB for all ranks together."""
+"""GPU: `bench.py --steps K` times K steps, `--full` adds the side measurements, and `bench.py --dump-outputs DIR` writes
+what the last timed step computed: what the engine returns for the same seeded reads, the k-mer set (and with
+--ext-index the extension index) at the dumped record positions, within 64 MB for all ranks together."""
 import json
 import os
 import subprocess
@@ -26,13 +26,13 @@ def _u64(f):
 LEAN = ["--no-cpu-baseline", "--no-gfa", "--no-e2e", "--no-k55", "--no-meta"]
 
 
-def _bench(args, env=None):
+def _bench(args, env=None, lean=True):
     """bench.py in a process of its own -> its JSON result line"""
     e = dict(os.environ, **(env or {}))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + LEAN, capture_output=True, text=True,
-                       env=e, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + (LEAN if lean else []),
+                       capture_output=True, text=True, env=e, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -45,6 +45,22 @@ def test_bench_steps_sets_the_timed_steps():
     l3 = {e["kernel"]: e["launches"] for e in three["roofline"]["kernels"]}
     assert l1 and l3 == {f: 3 * n for f, n in l1.items()}
     assert three["steps"] == 3 and three["ms_per_step"] == three["roofline"]["step"]["ms"] > 0
+
+
+def test_bench_full_adds_the_side_measurements():
+    """A plain run prints the headline and what the timed region measured; the side measurements that take runs of
+    their own come with --full only, after the same timed steps."""
+    side = {"e2e", "k55", "metagenome", "gfa_build", "cpu_baseline"}
+    args = ["--gpus", "1", "--reads", str(READS), "--steps", "1", "--warmup", "1"]
+    plain, full = _bench(args, lean=False), _bench(args + ["--full"], lean=False)
+    assert not side & set(plain)
+    assert side <= set(full)
+    for key in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup", "distinct_kmers"):
+        assert plain[key] == full[key], key
+    assert plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["roofline"]["kernels"]
+    assert "error" not in full["e2e"] and all("error" not in full["e2e"][t] for t in ("kmercount", "gbuilder"))
+    assert full["k55"]["distinct_kmers"] > 0 and full["gfa_build"]["unitigs"] > 0
+    assert set(full["metagenome"]["per_k"]) == {"21", "33", "55"} and full["cpu_baseline"]["value"] > 0
 
 
 @pytest.mark.parametrize("ext_index", [False, True])

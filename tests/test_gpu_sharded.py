@@ -181,8 +181,8 @@ def test_nccl_one_rank_path():
 def test_bench_two_ranks_rehearsal():
     """`python bench.py --gpus 2` exactly as the driver calls it (no launcher: bench.py starts its own ranks), with
     the collective backend switched to gloo so that both ranks can share the one GPU of the test box: the whole N>1 code
-    path of the benchmark (owner exchange, merge, expansion, max-over-ranks timing, sharded GFA build) runs end to end
-    and the aggregate equals the single-rank count of the union of the two ranks' reads."""
+    path of the benchmark (owner exchange, merge, expansion, max-over-ranks timing; with --full the sharded GFA build)
+    runs end to end and the aggregate equals the single-rank count of the union of the two ranks' reads."""
     import json
     import subprocess
     import sys
@@ -191,7 +191,7 @@ def test_bench_two_ranks_rehearsal():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--reads", "200000", "--steps", "1",
-                        "--warmup", "1"], capture_output=True, text=True, env=env, timeout=900)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["value"] > 0
