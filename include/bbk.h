@@ -119,7 +119,11 @@ void bbk_reads_free(bbk_reads *r);
                                (projects/kmercount/main.cpp:64-82,106) */
 #define BBK_CANONICAL 2u    /* only IsMinimal k-mers (utils/ph_map/storing_traits.hpp:90-101), as the
                                gbuilder splitters use (kmer_splitters.hpp:25-41) */
-#define BBK_WITH_COUNTS 4u  /* keep multiplicities (occurrences over reads + rc(reads)) */
+#define BBK_WITH_COUNTS 4u  /* keep multiplicities (occurrences over reads + rc(reads)).  Multiplicities are u32 and
+                               wrap modulo 2^32 on every path, as the reference's uint32_t += does
+                               (common/stages/construction.cpp:29, coverage_hash_map_builder.hpp:34-35): counted
+                               instances and counts summed by a merge (bbk_kmerset_from_device*, pushed batches)
+                               alike, whichever sort path runs; bbk_unitigs_add_coverage_counts reads these values */
 #define BBK_UNSORTED 8u     /* distinct set only, internal (hash-bucket) order: enough for the owner partition,
                                bbk_kmerset_both_strands and a later bbk_kmerset_from_device; skips the sort */
 #define BBK_REFERENCE_ORDER 16u /* store the set in the final_kmers order (BBK_ORDER_REFERENCE_BUCKETS16) instead of

@@ -4139,7 +4139,12 @@ struct MsdRunner {
                         R.dmode, (unsigned long long)N, P.nb1, nbuckets, mx, R.bucket_cap(), big.size(),
                         (unsigned long long)novf, (unsigned long long)ovf_rec);
             }
-            if (!R.never_decline && (novf > 256 || ovf_rec > N / 4)) return Outcome::Declined;
+            if (!R.never_decline && (novf > 256 || ovf_rec > N / 4)) {
+                if (verbose)
+                    fprintf(stderr, "[bbk] msd declines: N=%llu, %llu records in %llu buckets above the bucket kernels\n",
+                            (unsigned long long)N, (unsigned long long)ovf_rec, (unsigned long long)novf);
+                return Outcome::Declined;
+            }
             if (novf == 0) return std::nullopt;
             const int op = R.op;
             const ReduceOp rop = op == MSD_OP_OR ? REDUCE_OR : (op == MSD_OP_SUM ? REDUCE_SUM : REDUCE_COUNT);

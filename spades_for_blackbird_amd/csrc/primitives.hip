@@ -721,7 +721,7 @@ __global__ __launch_bounds__(kRadix) void k_tile_offsets(uint32_t *__restrict__ 
     const uint64_t t0 = (uint64_t)blockIdx.x * kChunk;
     const uint64_t t1 = (t0 + kChunk < ntiles) ? t0 + kChunk : ntiles;
     // offsets RELATIVE to the chunk's base (a chunk of 256 tiles holds < 2^32 records): the scatter kernel adds the
-    // 64-bit base, so that an array of 2^32 records or more sorts like any other
+    // 64-bit base, so that an array of 2^32 records or more (up to the tile limit of sort_scratch) sorts like any other
     uint32_t run = 0;
     for (uint64_t t = t0; t < t1; ++t) {
         uint32_t v = hist[t * kRadix + threadIdx.x];
@@ -887,9 +887,12 @@ static void sort_pass(bbk_ctx *ctx, const Key<W> *src, Key<W> *dst, const uint32
 
 template <int W>
 static void sort_scratch(uint64_t n, bool with_vals, DevBuf &hist, DevBuf &chunk) {
-    BBK_REQUIRE(n < (1ull << 40), BBK_ERR_ARG, "sort_records: n=%llu", (unsigned long long)n);
     constexpr int TILE = SortCfg<W>::TILE;
     const uint64_t ntiles = (n + TILE - 1) / TILE;
+    // k_hist / k_scatter launch one workgroup per tile in x: 2^32 threads or more would be cut short without an error
+    // (bbk_internal.h, BBK_GID), i.e. n < 2^24 tiles = 2^36 records (8-byte keys) .. 2^34 (32-byte keys)
+    BBK_REQUIRE(ntiles * kThreads < (1ull << 32), BBK_ERR_ARG, "sort_records: n=%llu records exceed %llu tiles",
+                (unsigned long long)n, (unsigned long long)((1ull << 32) / kThreads));
     const uint64_t nchunks = (ntiles + kChunk - 1) / kChunk;
     hist.alloc(ntiles * kRadix * sizeof(uint32_t));
     chunk.alloc(nchunks * kRadix * sizeof(uint64_t));
@@ -1032,10 +1035,9 @@ __global__ __launch_bounds__(kThreads) void k_seg_reduce(const uint32_t *__restr
     uint32_t r;
     if (op == REDUCE_COUNT) {
         r = b - a;
-    } else if (op == REDUCE_SUM) {
-        uint64_t t = 0;
-        for (uint32_t i = a; i < b; ++i) t += vals[i];
-        r = t > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)t;
+    } else if (op == REDUCE_SUM) {  // modulo 2^32, like the MSD bucket kernels (bbk.h: BBK_WITH_COUNTS)
+        r = 0;
+        for (uint32_t i = a; i < b; ++i) r += vals[i];
     } else {
         r = 0;
         for (uint32_t i = a; i < b; ++i) r |= vals[i];
