@@ -205,6 +205,21 @@ inline void check_launch(const char *what) {
     }
 }
 
+// Every timed kernel launch: LDS limit, timer, launch, check
+template <class K, class... Args>
+void launch_timed(bbk_ctx *ctx, K fn, const char *name, double bytes, uint32_t grid, uint32_t threads, size_t lds,
+                  Args... args) {
+    if (lds)
+        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)lds));
+    KernelTimer t(ctx, name, bytes);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, ctx->stream, args...);
+    check_launch(name);
+}
+
+// a numeric BBK_* knob: `unset` when the variable is not set (an empty value reads as 0)
+inline uint64_t env_u64(const char *v, uint64_t unset) { return v ? strtoull(v, nullptr, 10) : unset; }
+
 inline unsigned words_of(unsigned k) { return (k + 31) >> 5; }
 
 // One thread per item over billions of items.  A launch whose x dimension holds 2^32 threads or more is neither refused

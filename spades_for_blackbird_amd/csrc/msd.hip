@@ -3044,7 +3044,6 @@ struct BktCfg {
 constexpr double kBucketFill = 0.70;
 
 static double wall() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static uint64_t env_u64(const char *v, uint64_t unset) { return v ? strtoull(v, nullptr, 10) : unset; }
 
 // Environment knobs of this file (tests, diagnostics and A/B switches); this is where all of them are read.
 struct MsdKnobs {
@@ -3130,15 +3129,9 @@ struct MsdRunner {
 
     int w0bits() const { return (W == 1) ? (int)(2 * k) : 64; }
 
-    // Every timed kernel launch: LDS limit, timer, launch, check
     template <class K, class... Args>
     void launch(K fn, const char *name, double bytes, uint32_t grid, uint32_t threads, size_t lds, Args... args) {
-        if (lds)
-            BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)lds));
-        KernelTimer t(ctx, name, bytes);
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, ctx->stream, args...);
-        check_launch(name);
+        launch_timed(ctx, fn, name, bytes, grid, threads, lds, args...);
     }
 
     // Partition pass over a key array at level 1 (LVL1; also the level-0 and planning passes) or 2: HIST only counts the

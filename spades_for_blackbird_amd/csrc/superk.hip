@@ -32,10 +32,7 @@
 // in passes over ranges of the minimizer hash; every pass re-reads the packed reads (0.4 GB per 10 M reads), never the
 // k-mers.
 // The output order is arbitrary (HASH semantics): stage B / the accumulator sort it.
-// Environment: BBK_NO_SUPERK (A/B switch), BBK_SUPERK_MIN (instances below which the k-mer path is used; tests set 0),
-// BBK_SUPERK_BUCKETS (tests: buckets per pass, forces several passes on small inputs), BBK_SUPERK_FILL (tests: planned
-// instances of a bucket / table slots), BBK_SUPERK_SLOT_SCALE (tests: level-1 slots below their load),
-// BBK_SUPERK_FALLBACK_MAX (share of a batch's instances the k-mer path may take over, default 0.25), BBK_VERBOSE.
+// Environment knobs: SuperkKnobs (host part, below).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -43,6 +40,8 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <optional>
+#include <type_traits>
 #include <vector>
 
 #include "bbk_internal.h"
@@ -907,105 +906,100 @@ __global__ void k_sk_sum_buckets(const uint32_t *__restrict__ ids, uint32_t n, c
     if (i < n) atomicAdd(total, boff[ids[i] + 1] - boff[ids[i]]);
 }
 
-struct SkDedupArgs {
-    const uint8_t *hot;
-    uint32_t *fail2_list;
-    const uint64_t *records;
-    const unsigned long long *boff;
-    void *out_keys;
-    uint32_t *out_vals;
-    unsigned long long *out_cursor;
-    uint64_t out_cap;
-    uint32_t *flags;
-    uint32_t *fail_list;
+// a knob that is unset (nothing) or parsed by `parse` (an empty value parses like "0")
+template <class T, class F>
+static std::optional<T> env_opt(const char *name, F parse) {
+    const char *v = getenv(name);
+    return v ? std::optional<T>((T)parse(v)) : std::nullopt;
+}
+
+// Environment knobs of this file (tests, diagnostics and A/B switches); this is where all of them are read.
+struct SuperkKnobs {
+    // Read once per process: the tests that change them start a fresh process.
+    struct PerProcess {
+        bool xcd_slots = env_u64(getenv("BBK_XCD_SLOTS"), 1) != 0;  // 0: one level-1 fill front per slot, not per XCD
+        bool xcd_tiles = env_u64(getenv("BBK_XCD_TILES"), 1) != 0;  // 0: level-2 workgroups in slot-major order
+    };
+    const PerProcess &once = *[] {
+        static const PerProcess p;
+        return &p;
+    }();
+    // Read on every call: tests change them inside one process.
+    bool no_superk = getenv("BBK_NO_SUPERK") != nullptr;                // A/B switch: every batch takes the k-mer path
+    bool verbose = getenv("BBK_VERBOSE") != nullptr;                    // "[bbk] superk ..." lines on stderr
+    uint64_t min_inst = env_u64(getenv("BBK_SUPERK_MIN"), 1ull << 22);  // instances below which the k-mer path is used
+    std::optional<int> m = env_opt<int>("BBK_SUPERK_M", atoi);          // experiments: minimizer length (11..31, >= k - 63)
+    std::optional<double> fill = env_opt<double>("BBK_SUPERK_FILL", atof);  // tests: planned instances per table slot
+    std::optional<uint64_t> buckets =  // tests: buckets per pass (several passes on small inputs)
+        env_opt<uint64_t>("BBK_SUPERK_BUCKETS", [](const char *v) { return strtoull(v, nullptr, 10); });
+    std::optional<double> slot_scale = env_opt<double>("BBK_SUPERK_SLOT_SCALE", atof);  // tests: level-1 slots below load
+    // share of the instances the k-mer path may take over (hot buckets, spilled records) before the batch is declined
+    double fallback_max = env_opt<double>("BBK_SUPERK_FALLBACK_MAX", atof).value_or(0.25);
 };
 
-template <int W, int OP, class G>
-void launch_dedup_g(bbk_ctx *ctx, const char *fam, uint32_t nblocks, const SkParams &P, const SkDedupArgs &A,
-                    const uint32_t *bucket_ids, uint32_t *fail_list, uint32_t fail_ctr, double bytes) {
-    if (nblocks == 0) return;
-    const size_t sm = sk_dedup_smem<W, OP, G>(P.C);
-    auto fn = k_sk_dedup<W, OP, G>;
-    BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm));
-    KernelTimer t(ctx, fam, bytes);
-    hipLaunchKernelGGL(fn, dim3(nblocks), dim3(G::NT), sm, ctx->stream, A.records, A.boff, P, (Key<W> *)A.out_keys, A.out_vals,
-                       A.out_cursor, (unsigned long long)A.out_cap, A.flags, bucket_ids, fail_list, fail_ctr, A.hot);
-    check_launch("k_sk_dedup");
-}
+// What a batch decides before level 1
+struct SkPlan {
+    SkParams P;                  // kernel parameters (P.pass is set by every pass)
+    uint64_t ntiles1;            // level-1 tiles
+    uint64_t nbuckets;           // P1 * P2
+    uint32_t grid2;              // level-2 workgroups
+    size_t sm1;                  // level-1 LDS
+    double est_total, est_pass;  // expected records of the batch, of one pass
+    double fill;                 // planned instances per slot of the first table
+    uint64_t out_cap;            // first output capacity (records)
+    double fallback_max;         // SuperkKnobs::fallback_max
+};
 
-// second == 0: all buckets, first geometry (failures are listed); else the `second` listed buckets, big geometry
+// k, m, w, C: the record holds nbase_max bases -> runs of up to n_cap k-mers; the minimizer is as long as it can be
+// without natural runs (<= k-m+1 k-mers) exceeding the record, within [15, 31]
 template <int W>
-void launch_dedup(bbk_ctx *ctx, int op, uint32_t nbuckets, uint32_t second, const SkParams &P, const SkDedupArgs &A, double bytes) {
-    const char *fam = second ? "k_sk_dedup_B" : "k_sk_dedup";
-#define BBK_SK_DEDUP(OPV)                                                                                    \
-    if (second) launch_dedup_g<W, OPV, SkdB>(ctx, fam, second, P, A, A.fail_list, A.fail2_list, (uint32_t)SKF_NFAIL2, bytes); \
-    else launch_dedup_g<W, OPV, SkdA>(ctx, fam, nbuckets, P, A, nullptr, A.fail_list, (uint32_t)SKF_NFAIL, bytes)
-    switch (op) {
-        case MSD_OP_NONE: BBK_SK_DEDUP(0); break;
-        case MSD_OP_COUNT: BBK_SK_DEDUP(1); break;
-        case MSD_OP_OR: BBK_SK_DEDUP(3); break;
-        default: BBK_REQUIRE(false, BBK_ERR_INTERNAL, "superk: bad reduce op %d", op);
-    }
-#undef BBK_SK_DEDUP
-}
-
-template <int W>
-bool superk_run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, DevBuf &out_keys, DevBuf &out_vals,
-                uint64_t &n_distinct, uint64_t &n_instances) {
+SkParams sk_geometry(unsigned k, const SuperkKnobs &kn) {
     constexpr int RW = W + 1;
-    const bool verbose = getenv("BBK_VERBOSE") != nullptr;
-    if (rd->n == 0 || rd->n >= (1ull << 32)) return false;
-    const auto t_start = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); };
-    double t_setup = 0, t_alloc = 0, t_passes = 0;
-    // geometry: the record holds nbase_max bases -> runs of up to n_cap k-mers; the minimizer is as long as it can be
-    // without natural runs (<= k-m+1 k-mers) exceeding the record, within [15, 31]
     const uint32_t nbase_max = (64u * RW - kSkHdrBits) / 2u;
     const uint32_t n_cap = std::min<uint32_t>(64u, nbase_max - k + 1u);
-    const char *em = getenv("BBK_SUPERK_M");  // experiments: minimizer length (11..31, at least k - 63)
-    const uint32_t m = em ? (uint32_t)std::min<int>(31, std::max<int>(std::max(11, (int)k - 63), atoi(em)))
-                          : (uint32_t)std::min<int>(31, std::max<int>(15, (int)k - (int)n_cap + 1));
-    const uint32_t w = k - m + 1u;
-    const uint32_t C = std::min(w, n_cap);
+    SkParams P{};
+    P.k = k;
+    P.m = kn.m ? (uint32_t)std::min<int>(31, std::max<int>(std::max(11, (int)k - 63), *kn.m))
+               : (uint32_t)std::min<int>(31, std::max<int>(15, (int)k - (int)n_cap + 1));
+    P.w = k - P.m + 1u;
+    P.C = std::min(P.w, n_cap);
+    return P;
+}
 
-    DevBuf nk((rd->n + 1) * sizeof(uint64_t)), coff((rd->n + 1) * sizeof(uint64_t));
-    hipLaunchKernelGGL(k_sk_segments, dim3((unsigned)((rd->n + 255) / 256)), dim3(256), 0, ctx->stream, rd->d_len, rd->n, k,
-                       C, nk.as<uint64_t>(), coff.as<uint64_t>());
-    check_launch("k_sk_segments");
-    const uint64_t N = exclusive_scan_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), rd->n);
-    const uint64_t n_segs = exclusive_scan_u64(ctx, coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n);
-    nk.release();
-    const char *smin = getenv("BBK_SUPERK_MIN");
-    const uint64_t min_inst = smin ? strtoull(smin, nullptr, 10) : (1ull << 22);
-    if (N < min_inst || N == 0) return false;
-    BBK_HIP(hipMemcpyAsync(coff.as<uint64_t>() + rd->n, &n_segs, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));  // n_segs is a stack variable
-    const uint64_t ntiles1 = (n_segs + kSk1NT - 1) / kSk1NT;
-    if (ntiles1 >= (1ull << 31)) return false;
+// Every decision taken before level 1, for N instances in n_segs segments of the geometry G (sk_geometry, which the
+// segment count needs first).  Nothing: the batch is not for this path.  No HIP calls.
+template <int W>
+std::optional<SkPlan> sk_plan(const bbk_ctx *ctx, const SuperkKnobs &kn, const SkParams &G, uint64_t N, uint64_t n_segs) {
+    constexpr int RW = W + 1;
+    if (N < kn.min_inst || N == 0) return std::nullopt;
+    SkPlan L{};
+    SkParams &P = L.P;
+    P = G;
+    const uint32_t C = P.C, w = P.w;
+    L.ntiles1 = (n_segs + kSk1NT - 1) / kSk1NT;
+    if (L.ntiles1 >= (1ull << 31)) return std::nullopt;
 
     // expected records: a segment of C k-mers starts one and the minimum changes with probability 2/(w+1) per step
     // (the last segment of a read is shorter, so this is an upper estimate); the level-1 slots carry 12 % slack.
     // Buckets are planned by INSTANCES: the dedup table holds distinct keys, at most the instances of its bucket
     const double per_seg = 1.0 + (double)(C - 1) * 2.0 / (double)(w + 1);
-    const double est_total = (double)n_segs * per_seg * 1.05 + 65536.0;
+    L.est_total = (double)n_segs * per_seg * 1.05 + 65536.0;
     // The table holds DISTINCT keys.  Planned for the multiplicity of the previous batch of this context (x 0.5; none
     // yet: 1, every instance its own key): a bucket costs ~15 us of dependent latencies whatever it holds, so buckets
     // a quarter full would spend most of the kernel's time on them.  A batch that turns out less repetitive sends
     // its fuller buckets to the second-chance table (4x the slots) and, past 65536 of those, back to the k-mer path.
-    const char *ef = getenv("BBK_SUPERK_FILL");  // tests: overfull buckets exercise the second-chance table
     // (x 0.5: measured at k = 55, multiplicity 3.7 -- planned instances per slot 0.55: 12.3 ms, 1.0: 10.1, 1.3: 10.4,
     // 1.63: 11.5, 2.0: 14.5, 2.4: 20.8; the table wants a load of ~0.3)
     const double dup_plan = std::min(4.0, std::max(1.0, 0.5 * ctx->superk_dup));
-    const double fill = ef ? atof(ef) : 0.55 * dup_plan;
+    const double fill = kn.fill ? *kn.fill : 0.55 * dup_plan;
     const double nb_total = std::max(1.0, std::ceil((double)N / (fill * SkdA::TS)));
-    const char *eb = getenv("BBK_SUPERK_BUCKETS");
-    const double per_pass_max = eb ? (double)strtoull(eb, nullptr, 10) : (double)(1u << kSkMaxP1Bits) * kSkMaxP2 * 0.9;
+    const double per_pass_max = kn.buckets ? (double)*kn.buckets : (double)(1u << kSkMaxP1Bits) * kSkMaxP2 * 0.9;
     uint32_t np = (uint32_t)std::max(1.0, std::ceil(nb_total / per_pass_max));
     // one pass fewer when somewhat fuller buckets allow it: a pass re-reads the reads and repeats the minimizer work (38 ms
     // per 100 M reads), fuller tables cost less than that up to ~1.8x the planned load (configs[2]: 2 passes at 1.03
     // instances per slot = 390 ms of stage A, 1 pass at 1.24 = 330 ms)
     double nb_plan = nb_total;
-    if (np > 1 && !ef) {
+    if (np > 1 && !kn.fill) {
         const double fill_max = 0.55 * std::min(4.0, std::max(1.0, 0.9 * ctx->superk_dup));
         const double need = (double)N / (SkdA::TS * per_pass_max * (np - 1));
         if (need <= fill_max) {
@@ -1019,21 +1013,15 @@ bool superk_run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, DevBuf &o
     while (b1bits < kSkMaxP1Bits && (double)(1u << b1bits) < want1 && (double)(1u << b1bits) < nbp) ++b1bits;
     const uint32_t P1 = 1u << b1bits;
     const uint32_t P2 = (uint32_t)std::min<double>(kSkMaxP2, std::max(1.0, std::ceil(nbp / P1)));
-    const double est_pass = est_total / np;
-    const char *es1 = getenv("BBK_SUPERK_SLOT_SCALE");  // tests: slots below the load, so that records spill
-    const uint64_t slot1_64 = (uint64_t)(est_pass / P1 * 1.12 * (es1 ? atof(es1) : 1.0)) + (es1 ? 16 : 4096);
-    if (slot1_64 >= (1ull << 31)) return false;
-    SkParams P{};
-    P.k = k;
-    P.m = m;
-    P.w = w;
-    P.C = C;
+    L.est_pass = L.est_total / np;
+    const bool es1 = kn.slot_scale.has_value();
+    const uint64_t slot1_64 = (uint64_t)(L.est_pass / P1 * 1.12 * kn.slot_scale.value_or(1.0)) + (es1 ? 16 : 4096);
+    if (slot1_64 >= (1ull << 31)) return std::nullopt;
     P.np = np;
     P.b1bits = b1bits;
     P.P1 = P1;
     P.P2 = P2;
-    static const bool xcd_slots = !(getenv("BBK_XCD_SLOTS") && atoi(getenv("BBK_XCD_SLOTS")) == 0);
-    if (xcd_slots && ctx->num_xcds == 8) {  // eight sub-slots, each with the slack of a slot of its size
+    if (kn.once.xcd_slots && ctx->num_xcds == 8) {  // eight sub-slots, each with the slack of a slot of its size
         P.sub1 = (uint32_t)((slot1_64 + 7) / 8) + (es1 ? 2u : 512u);
         P.slot1 = 8u * P.sub1;
         P.tps_sub = (P.sub1 + kSk2Tile - 1) / kSk2Tile;
@@ -1044,278 +1032,352 @@ bool superk_run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, DevBuf &o
         P.slot1 = (uint32_t)slot1_64;
         P.tps = (P.slot1 + kSk2Tile - 1) / kSk2Tile;
     }
-    P.spill_cap = (uint32_t)std::min<double>(2.0e9, es1 ? est_pass + 65536.0 : est_pass / 8 + 65536.0);
-    const uint64_t nbuckets = (uint64_t)P1 * P2;
-    if ((uint64_t)P1 * P.tps >= (1ull << 31)) return false;
-    const size_t sm1 = sk_part1_smem(C, P1, RW);
-    if (sm1 > 160 * 1024 || sk_dedup_smem<W, 3, SkdA>(C) > 160 * 1024 || sk_dedup_smem<W, 3, SkdB>(C) > 160 * 1024) return false;
-    if (verbose)
-        fprintf(stderr,
-                "[bbk] superk: k=%u m=%u w=%u C=%u segs=%llu est_records=%.0f passes=%u P1=%u P2=%u slot1=%u lds1=%zu fill=%.2f\n",
-                k, m, w, C, (unsigned long long)n_segs, est_total, np, P1, P2, P.slot1, sm1, (double)N / (nb_plan * SkdA::TS));
-
-    DevBuf tiles((size_t)(ntiles1 + 1) * sizeof(SkTile));
-    hipLaunchKernelGGL(k_sk_tiles, dim3((unsigned)((ntiles1 + 255) / 256)), dim3(256), 0, ctx->stream, coff.as<uint64_t>(),
-                       rd->n, ntiles1, (uint32_t)kSk1NT, n_segs, tiles.as<SkTile>());
-    check_launch("k_sk_tiles");
-    SkReads S{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tiles.as<SkTile>(), rd->n, n_segs};
-    if (verbose) {
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
-        t_setup = since();
-    }
-
-    const size_t rec_bytes = (size_t)RW * 8;
-    DevBuf buf1((size_t)P1 * P.slot1 * rec_bytes), buf2;
-    DevBuf cur1((size_t)P1 * 8 * 4 + 16), boff((size_t)(nbuckets + 1) * 8 + 16), cur2((size_t)nbuckets * 8 + 16), dflags(64),
-        dcursor(16), fail_list((size_t)kSkdFailCap * 4), fail2_list((size_t)kSkdFailCap * 4), hot, fb_total(16);
-    DevBuf spill((size_t)P.spill_cap * rec_bytes + 16);
-    // share of the instances the k-mer path may have to take over (hot buckets, spilled records) before the whole batch
-    // is handed to it instead
-    const char *efm = getenv("BBK_SUPERK_FALLBACK_MAX");
-    const double fallback_max = efm ? atof(efm) : 0.25;
-    BBK_HIP(hipMemsetAsync(dflags.p, 0, 64, ctx->stream));
-    BBK_HIP(hipMemsetAsync(dcursor.p, 0, 16, ctx->stream));
-
+    P.spill_cap = (uint32_t)std::min<double>(2.0e9, es1 ? L.est_pass + 65536.0 : L.est_pass / 8 + 65536.0);
+    P.xcd_tiles = kn.once.xcd_tiles ? 1u : 0u;
+    L.nbuckets = (uint64_t)P1 * P2;
+    if ((uint64_t)P1 * P.tps >= (1ull << 31)) return std::nullopt;
+    L.sm1 = sk_part1_smem(C, P1, RW);
+    if (L.sm1 > 160 * 1024 || sk_dedup_smem<W, 3, SkdA>(C) > 160 * 1024 || sk_dedup_smem<W, 3, SkdB>(C) > 160 * 1024)
+        return std::nullopt;
+    L.grid2 = P.xcd_tiles ? 8u * ((P1 + 7u) / 8u) * P.tps : P1 * P.tps;
+    L.fill = (double)N / (nb_plan * SkdA::TS);
     // output: distinct records are appended; sized from the multiplicity the caller is likely to see and regrown if
     // a pass runs over (its dedup kernel is then run again: the buckets are still there)
-    const size_t key_bytes = (size_t)W * 8;
-    uint64_t out_cap = std::min<uint64_t>(
+    L.out_cap = std::min<uint64_t>(
         N, (uint64_t)(ctx->superk_dup >= 1.0 ? (double)N / ctx->superk_dup * 1.15 : (double)N / 3.0) + (1u << 20));
-    DevBuf okeys(out_cap * key_bytes + 16), ovals;
-    if (op != MSD_OP_NONE) ovals.alloc(out_cap * 4 + 16);
+    L.fallback_max = kn.fallback_max;
+    return L;
+}
 
-    {
-        auto fn1 = k_sk_part1<RW>;
-        BBK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(fn1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm1));
-    }
-    if (verbose) {
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
-        t_alloc = since();
-    }
+// How a batch ended on this path
+enum class SkOutcome {
+    NotTaken,  // before any work of the path: nothing of the context touched
+    Declined,  // given up (a slot, a table or the k-mer path's share ran over): counted, and the multiplicity the next
+               // batch is planned for forgotten; the caller runs the batch on the k-mer path
+    Done,
+};
+
+// One batch: the buffers that cross its phases, and the host values that asynchronous copies read or write (they live
+// as long as the batch).
+template <int W>
+struct SuperkRun {
+    static constexpr int RW = W + 1;
+    static constexpr size_t rec_bytes = (size_t)RW * 8, key_bytes = (size_t)W * 8;
+    bbk_ctx *ctx;
+    const bbk_reads *rd;
+    const unsigned k;
+    const int op;
+    const bool has_vals;  // a reduced payload goes with every key (op != MSD_OP_NONE)
+    const SuperkKnobs &kn;
+    const std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    double t_setup = 0, t_alloc = 0, t_passes = 0;
+    SkPlan L{};
+    SkParams &P = L.P;
+    SkReads S{};
+    uint64_t N = 0, n_segs = 0, n_rec = 0;  // instances, segments; records of the pass
+    uint32_t n_spill = 0;                   // records of the pass in the spill list
+    DevBuf coff, tiles, buf1, buf2, cur1, boff, cur2, dflags, dcursor, fail_list, fail2_list, hot, fb_total, spill;
+    DevBuf okeys, ovals;  // the output: distinct records appended at dcursor
+    uint64_t out_cap = 0;
     uint32_t hflags[16];
-    unsigned long long done_before = 0;
-    auto declined = [&](uint32_t pass) {
-        // (after a level-1 overflow the slots have holes: level 2 may then have met anything)
-        BBK_REQUIRE(!hflags[SKF_SELECT] || hflags[SKF_SLOT1], BBK_ERR_INTERNAL,
-                    "superk: a record arrived in a bin its hash does not name");
-        if (verbose)
-            fprintf(stderr, "[bbk] superk declines (pass %u): level-1 overflow=%u, buckets to the second chance=%u, to the k-mer path=%u (list full=%u), spilled records=%u, largest bucket %u records\n",
-                    pass, hflags[SKF_SLOT1], hflags[SKF_NFAIL], hflags[SKF_NFAIL2], hflags[SKF_TABLE], hflags[SKF_NSPILL],
-                    hflags[SKF_MAXREC]);
-        ctx->add_stat("stat_superk_declined", 1);
-        ctx->superk_dup = 0;
-        return false;
-    };
-    static const bool xcd_tiles = !(getenv("BBK_XCD_TILES") && atoi(getenv("BBK_XCD_TILES")) == 0);
-    P.xcd_tiles = xcd_tiles ? 1u : 0u;
-    const uint32_t grid2 = xcd_tiles ? 8u * ((P1 + 7u) / 8u) * P.tps : P1 * P.tps;
-    for (uint32_t pass = 0; pass < np; ++pass) {
-        P.pass = pass;
+    unsigned long long cursor_now = 0, done_before = 0;  // output records: after the dedup of this pass, before this pass
+
+    SuperkRun(bbk_ctx *c, const bbk_reads *r, unsigned k_, int o, const SuperkKnobs &kn_)
+        : ctx(c), rd(r), k(k_), op(o), has_vals(o != MSD_OP_NONE), kn(kn_) {}
+
+    double since() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count(); }
+    void sync() { BBK_HIP(hipStreamSynchronize(ctx->stream)); }
+
+    SkOutcome run(DevBuf &out_keys, DevBuf &out_vals, uint64_t &n_distinct, uint64_t &n_instances) {
+        if (rd->n == 0 || rd->n >= (1ull << 32)) return SkOutcome::NotTaken;
+        const SkParams G = sk_geometry<W>(k, kn);
+        count_segments(G.C);
+        std::optional<SkPlan> plan = sk_plan<W>(ctx, kn, G, N, n_segs);
+        if (!plan) return SkOutcome::NotTaken;
+        L = *plan;
+        setup();
+        for (uint32_t pass = 0; pass < P.np; ++pass) {
+            P.pass = pass;
+            level1();
+            if (!level2()) return declined();
+            for (int attempt = 0;; ++attempt) {
+                if (!dedup() || !kmer_path()) return declined();
+                if (!hflags[SKF_OUT]) break;
+                regrow(attempt);
+            }
+            done_before = cursor_now;
+        }
+        finish(out_keys, out_vals);
+        n_instances = N;
+        n_distinct = done_before;
+        return SkOutcome::Done;
+    }
+
+    // ---- k-mers (N) and segments of C k-mers (n_segs) of the reads; coff: exclusive scan of the segments per read
+    void count_segments(uint32_t C) {
+        DevBuf nk((rd->n + 1) * sizeof(uint64_t));
+        coff.alloc((rd->n + 1) * sizeof(uint64_t));
+        hipLaunchKernelGGL(k_sk_segments, dim3((unsigned)((rd->n + 255) / 256)), dim3(256), 0, ctx->stream, rd->d_len, rd->n,
+                           k, C, nk.as<uint64_t>(), coff.as<uint64_t>());
+        check_launch("k_sk_segments");
+        N = exclusive_scan_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), rd->n);
+        n_segs = exclusive_scan_u64(ctx, coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n);
+    }
+
+    // ---- level-1 tiles and the buffers of the passes
+    void setup() {
+        BBK_HIP(hipMemcpyAsync(coff.as<uint64_t>() + rd->n, &n_segs, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+        sync();
+        if (kn.verbose)
+            fprintf(stderr,
+                    "[bbk] superk: k=%u m=%u w=%u C=%u segs=%llu est_records=%.0f passes=%u P1=%u P2=%u slot1=%u lds1=%zu fill=%.2f\n",
+                    k, P.m, P.w, P.C, (unsigned long long)n_segs, L.est_total, P.np, P.P1, P.P2, P.slot1, L.sm1, L.fill);
+        tiles.alloc((size_t)(L.ntiles1 + 1) * sizeof(SkTile));
+        hipLaunchKernelGGL(k_sk_tiles, dim3((unsigned)((L.ntiles1 + 255) / 256)), dim3(256), 0, ctx->stream,
+                           coff.as<uint64_t>(), rd->n, L.ntiles1, (uint32_t)kSk1NT, n_segs, tiles.as<SkTile>());
+        check_launch("k_sk_tiles");
+        S = SkReads{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tiles.as<SkTile>(), rd->n, n_segs};
+        if (kn.verbose) {
+            sync();
+            t_setup = since();
+        }
+        buf1.alloc((size_t)P.P1 * P.slot1 * rec_bytes);
+        cur1.alloc((size_t)P.P1 * 8 * 4 + 16);
+        boff.alloc((size_t)(L.nbuckets + 1) * 8 + 16);
+        cur2.alloc((size_t)L.nbuckets * 8 + 16);
+        dflags.alloc(64);
+        dcursor.alloc(16);
+        fail_list.alloc((size_t)kSkdFailCap * 4);
+        fail2_list.alloc((size_t)kSkdFailCap * 4);
+        fb_total.alloc(16);
+        spill.alloc((size_t)P.spill_cap * rec_bytes + 16);
         BBK_HIP(hipMemsetAsync(dflags.p, 0, 64, ctx->stream));
-        BBK_HIP(hipMemsetAsync(cur1.p, 0, (size_t)P1 * 8 * 4, ctx->stream));
-        BBK_HIP(hipMemsetAsync(boff.p, 0, (size_t)(nbuckets + 1) * 8, ctx->stream));
-        {
-            KernelTimer t(ctx, "k_sk_part1", (double)rd->n_words * 8 + est_pass * rec_bytes);
-            hipLaunchKernelGGL(k_sk_part1<RW>, dim3((unsigned)ntiles1), dim3(kSk1NT), sm1, ctx->stream, S, P, cur1.as<uint32_t>(),
-                               buf1.as<uint64_t>(), spill.as<uint64_t>(), dflags.as<uint32_t>());
-            check_launch("k_sk_part1");
+        BBK_HIP(hipMemsetAsync(dcursor.p, 0, 16, ctx->stream));
+        out_cap = L.out_cap;
+        okeys.alloc(out_cap * key_bytes + 16);
+        if (has_vals) ovals.alloc(out_cap * 4 + 16);
+        if (kn.verbose) {
+            sync();
+            t_alloc = since();
         }
-        {
-            KernelTimer t(ctx, "k_sk_part2_hist", est_pass * rec_bytes);
-            hipLaunchKernelGGL((k_sk_part2<RW, true>), dim3(grid2), dim3(kSk2NT), 0, ctx->stream, buf1.as<uint64_t>(), P,
-                               cur1.as<uint32_t>(), boff.as<unsigned long long>(), (uint64_t *)nullptr, dflags.as<uint32_t>());
-            check_launch("k_sk_hist2");
-        }
-        const uint64_t n_rec = exclusive_scan_u64(ctx, boff.as<uint64_t>(), boff.as<uint64_t>(), nbuckets);
-        BBK_HIP(hipMemcpyAsync(boff.as<uint64_t>() + nbuckets, &n_rec, 8, hipMemcpyHostToDevice, ctx->stream));
-        BBK_HIP(bbk::copy_async(cur2.p, boff.p, (size_t)nbuckets * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+
+    // ---- level 1: reads -> records in the level-1 slots of this pass (or the spill list)
+    void level1() {
+        BBK_HIP(hipMemsetAsync(dflags.p, 0, 64, ctx->stream));
+        BBK_HIP(hipMemsetAsync(cur1.p, 0, (size_t)P.P1 * 8 * 4, ctx->stream));
+        BBK_HIP(hipMemsetAsync(boff.p, 0, (size_t)(L.nbuckets + 1) * 8, ctx->stream));
+        launch_timed(ctx, k_sk_part1<RW>, "k_sk_part1", (double)rd->n_words * 8 + L.est_pass * rec_bytes,
+                     (uint32_t)L.ntiles1, kSk1NT, L.sm1, S, P, cur1.as<uint32_t>(), buf1.as<uint64_t>(),
+                     spill.as<uint64_t>(), dflags.as<uint32_t>());
+    }
+
+    // ---- level 2: histogram and scan (bucket offsets), level-1 flags, hot buckets, scatter into dense buckets.
+    // false: decline
+    bool level2() {
+        launch_timed(ctx, k_sk_part2<RW, true>, "k_sk_part2_hist", L.est_pass * rec_bytes, L.grid2, kSk2NT, 0,
+                     buf1.as<uint64_t>(), P, cur1.as<uint32_t>(), boff.as<unsigned long long>(), (uint64_t *)nullptr,
+                     dflags.as<uint32_t>());
+        n_rec = exclusive_scan_u64(ctx, boff.as<uint64_t>(), boff.as<uint64_t>(), L.nbuckets);
+        BBK_HIP(hipMemcpyAsync(boff.as<uint64_t>() + L.nbuckets, &n_rec, 8, hipMemcpyHostToDevice, ctx->stream));
+        BBK_HIP(bbk::copy_async(cur2.p, boff.p, (size_t)L.nbuckets * 8, hipMemcpyDeviceToDevice, ctx->stream));
         BBK_HIP(hipMemcpyAsync(hflags, dflags.p, 64, hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));  // n_rec is a stack variable; level-1 flags
-        if (hflags[SKF_SLOT1] || hflags[SKF_STAGE] || hflags[SKF_SELECT]) return declined(pass);
-        const uint32_t n_spill = hflags[SKF_NSPILL];
+        sync();  // level-1 flags
+        if (hflags[SKF_SLOT1] || hflags[SKF_STAGE] || hflags[SKF_SELECT]) return false;
+        n_spill = hflags[SKF_NSPILL];
         if (n_spill) {  // hot minimizers: the buckets of the spilled records go to the k-mer path as a whole
-            if (!hot.p) hot.alloc((size_t)nbuckets + 16);
-            BBK_HIP(hipMemsetAsync(hot.p, 0, (size_t)nbuckets, ctx->stream));
+            if (!hot.p) hot.alloc((size_t)L.nbuckets + 16);
+            BBK_HIP(hipMemsetAsync(hot.p, 0, (size_t)L.nbuckets, ctx->stream));
             hipLaunchKernelGGL(k_sk_mark_hot<RW>, dim3((n_spill + 255) / 256), dim3(256), 0, ctx->stream, spill.as<uint64_t>(),
                                n_spill, P, hot.as<uint8_t>(), dflags.as<uint32_t>());
             check_launch("k_sk_mark_hot");
-            if (verbose) fprintf(stderr, "[bbk] superk: %u records spilled from full level-1 slots\n", n_spill);
+            if (kn.verbose) fprintf(stderr, "[bbk] superk: %u records spilled from full level-1 slots\n", n_spill);
             ctx->add_stat("stat_superk_spilled", (double)n_spill);
         }
         if (buf2.bytes < (n_rec + 1) * rec_bytes) {
             buf2.release();
-            buf2.alloc((size_t)((double)(n_rec + 1) * (np > 1 ? 1.05 : 1.0)) * rec_bytes);
+            buf2.alloc((size_t)((double)(n_rec + 1) * (P.np > 1 ? 1.05 : 1.0)) * rec_bytes);
         }
-        {
-            KernelTimer t(ctx, "k_sk_part2", 2.0 * (double)n_rec * rec_bytes);
-            hipLaunchKernelGGL((k_sk_part2<RW, false>), dim3(grid2), dim3(kSk2NT), 0, ctx->stream, buf1.as<uint64_t>(), P,
-                               cur1.as<uint32_t>(), cur2.as<unsigned long long>(), buf2.as<uint64_t>(), dflags.as<uint32_t>());
-            check_launch("k_sk_part2");
-        }
+        launch_timed(ctx, k_sk_part2<RW, false>, "k_sk_part2", 2.0 * (double)n_rec * rec_bytes, L.grid2, kSk2NT, 0,
+                     buf1.as<uint64_t>(), P, cur1.as<uint32_t>(), cur2.as<unsigned long long>(), buf2.as<uint64_t>(),
+                     dflags.as<uint32_t>());
         ctx->add_stat("stat_superk_records", (double)n_rec);
-        for (int attempt = 0;; ++attempt) {
-            // algorithmic bytes: the records read + the distinct keys written; their number is known once the cursor has
-            // been read back (below) and is put into the timer's entry then
-            const double db = (double)n_rec * rec_bytes;
-            const size_t timer_entry = ctx->pending.size();
-            SkDedupArgs A{n_spill ? hot.as<uint8_t>() : nullptr, fail2_list.as<uint32_t>(), buf2.as<uint64_t>(),
-                          boff.as<unsigned long long>(), okeys.p, ovals.as<uint32_t>(), dcursor.as<unsigned long long>(), out_cap,
-                          dflags.as<uint32_t>(), fail_list.as<uint32_t>()};
-            BBK_HIP(hipMemsetAsync(dflags.as<uint32_t>() + SKF_NFAIL, 0, 4, ctx->stream));
-            BBK_HIP(hipMemsetAsync(dflags.as<uint32_t>() + SKF_NFAIL2, 0, 4, ctx->stream));
-            launch_dedup<W>(ctx, op, (uint32_t)nbuckets, 0, P, A, db);
-            unsigned long long cursor_now = 0;
-            BBK_HIP(hipMemcpyAsync(hflags, dflags.p, 64, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(&cursor_now, dcursor.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->profiling && ctx->pending.size() > timer_entry && cursor_now >= done_before)
-                ctx->pending[timer_entry].bytes += (double)(cursor_now - done_before) * (key_bytes + (op != MSD_OP_NONE ? 4 : 0));
-            if (hflags[SKF_NFAIL] && !hflags[SKF_OUT]) {  // second chance for the buckets the small table gave up
-                if (hflags[SKF_NFAIL] > kSkdFailCap) return declined(pass);
-                if (verbose)
-                    fprintf(stderr, "[bbk] superk: %u buckets to the second-chance table (largest %u records)\n", hflags[SKF_NFAIL],
-                            hflags[SKF_MAXREC]);
-                ctx->add_stat("stat_superk_second_chance", (double)hflags[SKF_NFAIL]);
-                launch_dedup<W>(ctx, op, (uint32_t)nbuckets, hflags[SKF_NFAIL], P, A, 0);
-                BBK_HIP(hipMemcpyAsync(hflags, dflags.p, 64, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipMemcpyAsync(&cursor_now, dcursor.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
-            }
-            if (hflags[SKF_TABLE] || hflags[SKF_SELECT]) return declined(pass);
-            const uint32_t n_fail2 = hflags[SKF_NFAIL2];
-            if (!hflags[SKF_OUT] && (n_fail2 || n_spill)) {
-                // What the tables could not take -- buckets with more distinct keys than the second-chance table holds
-                // (one low-complexity minimizer shared by thousands of k-mers) and the buckets of spilled records -- is
-                // expanded into one key per instance and deduplicated by the k-mer path; the keys of a bucket occur in
-                // no other bucket, so the distinct records are simply appended.
-                unsigned long long fb_rec = 0;
-                BBK_HIP(hipMemsetAsync(fb_total.p, 0, 16, ctx->stream));
-                if (n_fail2) {
-                    hipLaunchKernelGGL(k_sk_sum_buckets, dim3((n_fail2 + 255) / 256), dim3(256), 0, ctx->stream,
-                                       fail2_list.as<uint32_t>(), n_fail2, boff.as<unsigned long long>(),
-                                       fb_total.as<unsigned long long>());
-                    check_launch("k_sk_sum_buckets");
-                }
-                BBK_HIP(hipMemcpyAsync(&fb_rec, fb_total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
-                fb_rec += n_spill;
-                const uint64_t inst_ub = fb_rec * (uint64_t)C;
-                if (verbose)
-                    fprintf(stderr, "[bbk] superk: %u buckets (largest %u records) + %u spilled records = %llu records to the k-mer path\n",
-                            n_fail2, hflags[SKF_MAXREC], n_spill, fb_rec);
-                if ((double)inst_ub > fallback_max * (double)N / np + 65536.0) return declined(pass);
-                ctx->add_stat("stat_superk_kmer_path_records", (double)fb_rec);
-                DevBuf fk(inst_ub * key_bytes + 16), fv;
-                if (op == MSD_OP_OR) fv.alloc(inst_ub * 4 + 16);
-                BBK_HIP(hipMemsetAsync(fb_total.p, 0, 16, ctx->stream));
-                auto expand = [&](const uint64_t *recs, const uint32_t *ids, uint32_t nblocks, uint32_t n_flat) {
-                    if (nblocks == 0) return;
-                    KernelTimer t(ctx, "k_sk_expand", 0);
-                    if (op == MSD_OP_OR)
-                        hipLaunchKernelGGL((k_sk_expand<W, 3>), dim3(nblocks), dim3(256), 0, ctx->stream, recs, boff.as<unsigned long long>(),
-                                           ids, n_flat, P, fk.as<Key<W>>(), fv.as<uint32_t>(), fb_total.as<unsigned long long>(),
-                                           (unsigned long long)inst_ub, dflags.as<uint32_t>());
-                    else
-                        hipLaunchKernelGGL((k_sk_expand<W, 0>), dim3(nblocks), dim3(256), 0, ctx->stream, recs, boff.as<unsigned long long>(),
-                                           ids, n_flat, P, fk.as<Key<W>>(), (uint32_t *)nullptr, fb_total.as<unsigned long long>(),
-                                           (unsigned long long)inst_ub, dflags.as<uint32_t>());
-                    check_launch("k_sk_expand");
-                };
-                expand(buf2.as<uint64_t>(), fail2_list.as<uint32_t>(), n_fail2, 0);
-                expand(spill.as<uint64_t>(), nullptr, n_spill ? std::min<uint32_t>((n_spill + 255) / 256, 65536u) : 0u, n_spill);
-                unsigned long long fb_inst = 0;
-                BBK_HIP(hipMemcpyAsync(&fb_inst, fb_total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipMemcpyAsync(hflags, dflags.p, 64, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
-                BBK_REQUIRE(!hflags[SKF_OUT] && fb_inst <= inst_ub, BBK_ERR_INTERNAL, "superk: expansion ran over its bound");
-                MsdOutput mo;
-                if (!msd_sort_reduce(ctx, k, MSD_HASH, op, nullptr, fk.p, op == MSD_OP_OR ? fv.as<uint32_t>() : nullptr, fb_inst,
-                                     false, mo))
-                    return declined(pass);
-                fk.release();
-                fv.release();
-                if (cursor_now + mo.n > out_cap) {  // room for the appended records
-                    const uint64_t new_cap = cursor_now + mo.n + (N - std::min<uint64_t>(N, cursor_now + mo.n)) / 8;
-                    DevBuf nkeys(new_cap * key_bytes + 16), nvals;
-                    BBK_HIP(bbk::copy_async(nkeys.p, okeys.p, cursor_now * key_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-                    if (op != MSD_OP_NONE) {
-                        nvals.alloc(new_cap * 4 + 16);
-                        BBK_HIP(bbk::copy_async(nvals.p, ovals.p, cursor_now * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                    }
-                    BBK_HIP(hipStreamSynchronize(ctx->stream));
-                    okeys = std::move(nkeys);
-                    if (op != MSD_OP_NONE) ovals = std::move(nvals);
-                    out_cap = new_cap;
-                }
-                if (mo.n) {
-                    BBK_HIP(bbk::copy_async(okeys.as<char>() + cursor_now * key_bytes, mo.keys.p, mo.n * key_bytes,
-                                           hipMemcpyDeviceToDevice, ctx->stream));
-                    if (op != MSD_OP_NONE)
-                        BBK_HIP(bbk::copy_async(ovals.as<uint32_t>() + cursor_now, mo.vals.p, mo.n * 4, hipMemcpyDeviceToDevice,
-                                               ctx->stream));
-                }
-                cursor_now += mo.n;
-                BBK_HIP(hipMemcpyAsync(dcursor.p, &cursor_now, 8, hipMemcpyHostToDevice, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));  // cursor_now is a stack variable; mo's buffers are about to go
-            }
-            if (!hflags[SKF_OUT]) {
-                done_before = cursor_now;
-                break;
-            }
-            // the output ran over: keep what earlier passes wrote, grow, run this pass's dedup again
-            BBK_REQUIRE(attempt < 2, BBK_ERR_INTERNAL, "superk: output still too small after regrowing");
-            const uint64_t new_cap =
-                std::min<uint64_t>(N, attempt == 0 ? std::max<uint64_t>(2 * out_cap, done_before + N / np) : N);
-            if (verbose)
-                fprintf(stderr, "[bbk] superk: output regrown %llu -> %llu records (pass %u)\n", (unsigned long long)out_cap,
-                        (unsigned long long)new_cap, pass);
-            DevBuf nkeys(new_cap * key_bytes + 16), nvals;
-            BBK_HIP(bbk::copy_async(nkeys.p, okeys.p, done_before * key_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-            if (op != MSD_OP_NONE) {
-                nvals.alloc(new_cap * 4 + 16);
-                BBK_HIP(bbk::copy_async(nvals.p, ovals.p, done_before * 4, hipMemcpyDeviceToDevice, ctx->stream));
-            }
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            okeys = std::move(nkeys);
-            if (op != MSD_OP_NONE) ovals = std::move(nvals);
-            out_cap = new_cap;
-            BBK_HIP(hipMemcpyAsync(dcursor.p, &done_before, 8, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemsetAsync(reinterpret_cast<uint32_t *>(dflags.p) + SKF_OUT, 0, 4, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));  // done_before must stay put until the copy has run
+        return true;
+    }
+
+    // One workgroup per bucket.  First chance (second = false): every bucket through the first table geometry, the
+    // buckets it gives up listed in fail_list; second chance: the nblocks buckets of fail_list through the big geometry,
+    // the ones it gives up listed in fail2_list (the k-mer path)
+    void launch_dedup(bool second, uint32_t nblocks, double bytes) {
+        auto go = [&](auto opc) {
+            constexpr int OP = decltype(opc)::value;
+            auto on = [&](auto geo, const char *name, const uint32_t *ids, uint32_t *fails, uint32_t fail_ctr) {
+                using G = decltype(geo);
+                launch_timed(ctx, k_sk_dedup<W, OP, G>, name, bytes, nblocks, G::NT, sk_dedup_smem<W, OP, G>(P.C),
+                             buf2.as<uint64_t>(), boff.as<unsigned long long>(), P, okeys.as<Key<W>>(),
+                             ovals.as<uint32_t>(), dcursor.as<unsigned long long>(), (unsigned long long)out_cap,
+                             dflags.as<uint32_t>(), ids, fails, fail_ctr, n_spill ? hot.as<const uint8_t>() : nullptr);
+            };
+            if (second) on(SkdB(), "k_sk_dedup_B", fail_list.as<const uint32_t>(), fail2_list.as<uint32_t>(), (uint32_t)SKF_NFAIL2);
+            else on(SkdA(), "k_sk_dedup", nullptr, fail_list.as<uint32_t>(), (uint32_t)SKF_NFAIL);
+        };
+        switch (op) {  // (SUM has no kernel here)
+            case MSD_OP_NONE: go(std::integral_constant<int, 0>()); break;
+            case MSD_OP_COUNT: go(std::integral_constant<int, 1>()); break;
+            case MSD_OP_OR: go(std::integral_constant<int, 3>()); break;
+            default: BBK_REQUIRE(false, BBK_ERR_INTERNAL, "superk: bad reduce op %d", op);
         }
     }
-    buf1.release();
-    buf2.release();
-    if (verbose) t_passes = since();
-    const uint64_t D = done_before;
-    n_instances = N;
-    n_distinct = D;
-    ctx->add_stat("stat_superk_batches", 1);
-    if (N >= (1ull << 20)) ctx->superk_dup = D ? (double)N / (double)D : 0.0;  // a small batch says little about the next
-    auto report = [&]() {
-        if (verbose)
+
+    // flags and output cursor once the work issued so far has run
+    void read_back() {
+        BBK_HIP(hipMemcpyAsync(hflags, dflags.p, 64, hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipMemcpyAsync(&cursor_now, dcursor.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        sync();
+    }
+
+    // ---- first chance, then second chance for the buckets the small table gave up.  false: decline
+    bool dedup() {
+        // algorithmic bytes: the records read + the distinct keys written; their number is known once the cursor has
+        // been read back (below) and is put into the timer's entry then
+        const size_t timer_entry = ctx->pending.size();
+        BBK_HIP(hipMemsetAsync(dflags.as<uint32_t>() + SKF_NFAIL, 0, 4, ctx->stream));
+        BBK_HIP(hipMemsetAsync(dflags.as<uint32_t>() + SKF_NFAIL2, 0, 4, ctx->stream));
+        launch_dedup(false, (uint32_t)L.nbuckets, (double)n_rec * rec_bytes);
+        read_back();
+        if (ctx->profiling && ctx->pending.size() > timer_entry && cursor_now >= done_before)
+            ctx->pending[timer_entry].bytes += (double)(cursor_now - done_before) * (key_bytes + (has_vals ? 4 : 0));
+        if (hflags[SKF_NFAIL] && !hflags[SKF_OUT]) {
+            if (hflags[SKF_NFAIL] > kSkdFailCap) return false;
+            if (kn.verbose)
+                fprintf(stderr, "[bbk] superk: %u buckets to the second-chance table (largest %u records)\n", hflags[SKF_NFAIL],
+                        hflags[SKF_MAXREC]);
+            ctx->add_stat("stat_superk_second_chance", (double)hflags[SKF_NFAIL]);
+            launch_dedup(true, hflags[SKF_NFAIL], 0);
+            read_back();
+        }
+        return !hflags[SKF_TABLE] && !hflags[SKF_SELECT];
+    }
+
+    // ---- What the tables could not take -- buckets with more distinct keys than the second-chance table holds (one
+    // low-complexity minimizer shared by thousands of k-mers) and the buckets of spilled records -- is expanded into
+    // one key per instance and deduplicated by the k-mer path; the keys of a bucket occur in no other bucket, so the
+    // distinct records are simply appended.  false: decline
+    bool kmer_path() {
+        const uint32_t n_fail2 = hflags[SKF_NFAIL2];
+        if (hflags[SKF_OUT] || (!n_fail2 && !n_spill)) return true;
+        unsigned long long fb_rec = 0;
+        BBK_HIP(hipMemsetAsync(fb_total.p, 0, 16, ctx->stream));
+        if (n_fail2) {
+            hipLaunchKernelGGL(k_sk_sum_buckets, dim3((n_fail2 + 255) / 256), dim3(256), 0, ctx->stream,
+                               fail2_list.as<uint32_t>(), n_fail2, boff.as<unsigned long long>(),
+                               fb_total.as<unsigned long long>());
+            check_launch("k_sk_sum_buckets");
+        }
+        BBK_HIP(hipMemcpyAsync(&fb_rec, fb_total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        sync();
+        fb_rec += n_spill;
+        const uint64_t inst_ub = fb_rec * (uint64_t)P.C;
+        if (kn.verbose)
+            fprintf(stderr, "[bbk] superk: %u buckets (largest %u records) + %u spilled records = %llu records to the k-mer path\n",
+                    n_fail2, hflags[SKF_MAXREC], n_spill, fb_rec);
+        if ((double)inst_ub > L.fallback_max * (double)N / P.np + 65536.0) return false;
+        ctx->add_stat("stat_superk_kmer_path_records", (double)fb_rec);
+        DevBuf fk(inst_ub * key_bytes + 16), fv;
+        if (op == MSD_OP_OR) fv.alloc(inst_ub * 4 + 16);
+        BBK_HIP(hipMemsetAsync(fb_total.p, 0, 16, ctx->stream));
+        auto expand = [&](const uint64_t *recs, const uint32_t *ids, uint32_t nblocks, uint32_t n_flat) {
+            if (nblocks == 0) return;
+            launch_timed(ctx, op == MSD_OP_OR ? k_sk_expand<W, 3> : k_sk_expand<W, 0>, "k_sk_expand", 0, nblocks, 256, 0,
+                         recs, boff.as<unsigned long long>(), ids, n_flat, P, fk.as<Key<W>>(), fv.as<uint32_t>(),
+                         fb_total.as<unsigned long long>(), (unsigned long long)inst_ub, dflags.as<uint32_t>());
+        };
+        expand(buf2.as<uint64_t>(), fail2_list.as<uint32_t>(), n_fail2, 0);
+        expand(spill.as<uint64_t>(), nullptr, n_spill ? std::min<uint32_t>((n_spill + 255) / 256, 65536u) : 0u, n_spill);
+        unsigned long long fb_inst = 0;
+        BBK_HIP(hipMemcpyAsync(&fb_inst, fb_total.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipMemcpyAsync(hflags, dflags.p, 64, hipMemcpyDeviceToHost, ctx->stream));
+        sync();
+        BBK_REQUIRE(!hflags[SKF_OUT] && fb_inst <= inst_ub, BBK_ERR_INTERNAL, "superk: expansion ran over its bound");
+        MsdOutput mo;
+        if (!msd_sort_reduce(ctx, k, MSD_HASH, op, nullptr, fk.p, fv.as<uint32_t>(), fb_inst, false, mo)) return false;
+        fk.release();
+        fv.release();
+        if (cursor_now + mo.n > out_cap)  // room for the appended records
+            resize_output(cursor_now + mo.n + (N - std::min<uint64_t>(N, cursor_now + mo.n)) / 8, cursor_now);
+        if (mo.n) {
+            BBK_HIP(bbk::copy_async(okeys.as<char>() + cursor_now * key_bytes, mo.keys.p, mo.n * key_bytes,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+            if (has_vals)
+                BBK_HIP(bbk::copy_async(ovals.as<uint32_t>() + cursor_now, mo.vals.p, mo.n * 4, hipMemcpyDeviceToDevice,
+                                       ctx->stream));
+        }
+        cursor_now += mo.n;
+        BBK_HIP(hipMemcpyAsync(dcursor.p, &cursor_now, 8, hipMemcpyHostToDevice, ctx->stream));
+        sync();  // mo's buffers are about to go
+        return true;
+    }
+
+    // ---- the output ran over: keep what earlier passes wrote, grow, run this pass's dedup again (its buckets are
+    // still there)
+    void regrow(int attempt) {
+        BBK_REQUIRE(attempt < 2, BBK_ERR_INTERNAL, "superk: output still too small after regrowing");
+        const uint64_t new_cap =
+            std::min<uint64_t>(N, attempt == 0 ? std::max<uint64_t>(2 * out_cap, done_before + N / P.np) : N);
+        if (kn.verbose)
+            fprintf(stderr, "[bbk] superk: output regrown %llu -> %llu records (pass %u)\n", (unsigned long long)out_cap,
+                    (unsigned long long)new_cap, P.pass);
+        resize_output(new_cap, done_before);
+        BBK_HIP(hipMemcpyAsync(dcursor.p, &done_before, 8, hipMemcpyHostToDevice, ctx->stream));
+        BBK_HIP(hipMemsetAsync(dflags.as<uint32_t>() + SKF_OUT, 0, 4, ctx->stream));
+        sync();
+    }
+
+    // The output in new buffers of `cap` records that hold its first `keep`; the old ones go once the copy has run
+    void resize_output(uint64_t cap, uint64_t keep) {
+        DevBuf nkeys(cap * key_bytes + 16), nvals;
+        BBK_HIP(bbk::copy_async(nkeys.p, okeys.p, keep * key_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        if (has_vals) {
+            nvals.alloc(cap * 4 + 16);
+            BBK_HIP(bbk::copy_async(nvals.p, ovals.p, keep * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        sync();
+        okeys = std::move(nkeys);
+        if (has_vals) ovals = std::move(nvals);
+        out_cap = cap;
+    }
+
+    // ---- all passes done: done_before distinct records
+    void finish(DevBuf &out_keys, DevBuf &out_vals) {
+        buf1.release();
+        buf2.release();
+        if (kn.verbose) t_passes = since();
+        const uint64_t D = done_before;
+        ctx->add_stat("stat_superk_batches", 1);
+        if (N >= (1ull << 20)) ctx->superk_dup = D ? (double)N / (double)D : 0.0;  // a small batch says little about the next
+        // the caller keeps the result for the rest of the job: do not leave it in a buffer sized for the estimate
+        if (out_cap > D + D / 8 + (1u << 20)) resize_output(D, D);
+        out_keys = std::move(okeys);
+        if (has_vals) out_vals = std::move(ovals);
+        if (kn.verbose)
             fprintf(stderr, "[bbk] superk: %llu instances -> %llu distinct; wall %.3f s (setup %.3f, buffers %.3f, passes %.3f, result %.3f)\n",
                     (unsigned long long)N, (unsigned long long)D, since(), t_setup, t_alloc - t_setup, t_passes - t_alloc,
                     since() - t_passes);
-    };
-    // the caller keeps the result for the rest of the job: do not leave it in a buffer sized for the estimate
-    if (out_cap > D + D / 8 + (1u << 20)) {
-        DevBuf xk(D * key_bytes + 16), xv;
-        BBK_HIP(bbk::copy_async(xk.p, okeys.p, D * key_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        if (op != MSD_OP_NONE) {
-            xv.alloc(D * 4 + 16);
-            BBK_HIP(bbk::copy_async(xv.p, ovals.p, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
-        out_keys = std::move(xk);
-        if (op != MSD_OP_NONE) out_vals = std::move(xv);
-    } else {
-        out_keys = std::move(okeys);
-        if (op != MSD_OP_NONE) out_vals = std::move(ovals);
     }
-    report();
-    return true;
-}
+
+    SkOutcome declined() {
+        // (after a level-1 overflow the slots have holes: level 2 may then have met anything)
+        BBK_REQUIRE(!hflags[SKF_SELECT] || hflags[SKF_SLOT1], BBK_ERR_INTERNAL,
+                    "superk: a record arrived in a bin its hash does not name");
+        if (kn.verbose)
+            fprintf(stderr, "[bbk] superk declines (pass %u): level-1 overflow=%u, buckets to the second chance=%u, to the k-mer path=%u (list full=%u), spilled records=%u, largest bucket %u records\n",
+                    P.pass, hflags[SKF_SLOT1], hflags[SKF_NFAIL], hflags[SKF_NFAIL2], hflags[SKF_TABLE], hflags[SKF_NSPILL],
+                    hflags[SKF_MAXREC]);
+        ctx->add_stat("stat_superk_declined", 1);
+        ctx->superk_dup = 0;
+        return SkOutcome::Declined;
+    }
+};
 
 }  // namespace
 
@@ -1323,11 +1385,16 @@ bool superk_run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, DevBuf &o
 // false: not taken (key width, size, switch) or given up (a slot or table ran over): the caller uses the k-mer path.
 bool superk_dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, DevBuf &out_keys, DevBuf &out_vals,
                         uint64_t &n_distinct, uint64_t &n_instances) {
-    if (getenv("BBK_NO_SUPERK")) return false;
+    const SuperkKnobs kn;
+    if (kn.no_superk) return false;
+    auto run = [&](auto w) {
+        SuperkRun<decltype(w)::value> R(ctx, rd, k, op, kn);
+        return R.run(out_keys, out_vals, n_distinct, n_instances) == SkOutcome::Done;
+    };
     const unsigned W = words_of(k);
-    if (W == 2) return superk_run<2>(ctx, rd, k, op, out_keys, out_vals, n_distinct, n_instances);
-    if (W == 3) return superk_run<3>(ctx, rd, k, op, out_keys, out_vals, n_distinct, n_instances);
-    if (W == 4) return superk_run<4>(ctx, rd, k, op, out_keys, out_vals, n_distinct, n_instances);
+    if (W == 2) return run(std::integral_constant<int, 2>());
+    if (W == 3) return run(std::integral_constant<int, 3>());
+    if (W == 4) return run(std::integral_constant<int, 4>());
     return false;
 }
 

@@ -300,6 +300,33 @@ def test_superk_low_complexity_reads(monkeypatch, capfd):
     ctx.close()
 
 
+def test_superk_output_regrown(monkeypatch, capfd):
+    """The first output capacity of a batch comes from the multiplicity the context saw in its last batch of at least
+    2^20 instances.  A highly repetitive batch (20 k reads of a 5 kbp genome, 1.9 M instances), then one that is almost
+    all distinct (30 k reads of a 10 Mbp genome) on the same context: the second batch's output is planned near 1.06 M
+    records, far below its distinct count, so its dedup runs over, the output is regrown and the dedup runs again.
+    Neither batch is declined, and the counts equal the k-mer path's (BBK_NO_SUPERK=1)."""
+    import spades_for_blackbird_amd as B
+    k = 55
+    monkeypatch.setenv("BBK_SUPERK_MIN", "0")
+    monkeypatch.setenv("BBK_VERBOSE", "1")
+    ctx = B.Context(0)
+    rep = ctx.reads_synth(20_000, read_len=150, genome_len=5_000, sub_rate=0.0, seed_genome=3, seed_reads=4)
+    ctx.count(rep, k, B.CANONICAL | B.WITH_COUNTS).free()
+    err = capfd.readouterr().err
+    assert "distinct" in err and "declines" not in err and "output regrown" not in err, _superk_lines(err)[:5]
+    r = ctx.reads_synth(30_000, read_len=150, genome_len=10_000_000, sub_rate=0.0, seed_genome=5, seed_reads=6)
+    got, gc = ctx.count(r, k, B.CANONICAL | B.WITH_COUNTS).export(B.ORDER_SORTED, with_counts=True)
+    err = capfd.readouterr().err
+    assert "output regrown" in err and "declines" not in err, _superk_lines(err)[:5]
+    monkeypatch.setenv("BBK_NO_SUPERK", "1")
+    exp, ec = ctx.count(r, k, B.CANONICAL | B.WITH_COUNTS).export(B.ORDER_SORTED, with_counts=True)
+    assert "superk" not in capfd.readouterr().err
+    assert got.shape == exp.shape and (got == exp).all() and (gc == ec).all()
+    assert int(gc.sum()) == 30_000 * (150 - k + 1)
+    ctx.close()
+
+
 def test_one_call_is_cut_into_read_pieces():
     """8-byte keys: a call above one stage-A pass is cut into pieces of reads (each deduplicated on its own, merged
     once) instead of hash ranges that re-extract every k-mer per range; forced here with 60 k bases per piece"""
