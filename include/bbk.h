@@ -335,6 +335,40 @@ int bbk_profiles_export_raw(bbk_ctx *ctx, const bbk_profiles *p, uint64_t *h_raw
 int bbk_profiles_write(bbk_ctx *ctx, const bbk_profiles *p, const char *path);
 void bbk_profiles_free(bbk_profiles *p);
 
+/* ---- mapping paths: the mapper of spades-gmapper (projects/gmapper/main.cpp:156-247), the MappingPath of every read
+ *      (BasicSequenceMapper::MapSequence, modules/alignment/sequence_mapper.hpp:288-404) over the same index ---------- */
+typedef struct bbk_paths bbk_paths; /* the ranges of one batch of reads, in HBM */
+typedef struct {
+    uint64_t edge;                 /* 2 * segment, + 1 on the reverse strand of a segment that is not self-conjugate */
+    uint32_t read;                 /* read of the batch */
+    uint32_t init_start, init_end; /* (k+1)-mer positions on the read, [start, end) */
+    uint32_t map_start, map_end;   /* (k+1)-mer offsets on the oriented edge, [start, end) */
+    uint32_t reserved;
+} bbk_path_range;
+/* Maps every read of the batch as it stands, without its reverse complement; the ranges come in read order and in
+ * position order within a read.  The batch has gone through LongestValid, so a caller that cuts reads at N as MapRead
+ * does (sequence_mapper.hpp:68-98) passes the pieces as reads. */
+int bbk_edgeindex_map_paths(bbk_ctx *ctx, const bbk_edgeindex *ix, const bbk_reads *reads, bbk_paths **out);
+uint64_t bbk_paths_reads(const bbk_paths *p);
+uint64_t bbk_paths_ranges(const bbk_paths *p);
+/* h_read_offsets: reads + 1 entries, the ranges of read r are [off[r], off[r + 1]); h_ranges: one entry per range.
+ * Either may be NULL. */
+int bbk_paths_export(bbk_ctx *ctx, const bbk_paths *p, uint64_t *h_read_offsets, bbk_path_range *h_ranges);
+void bbk_paths_free(bbk_paths *p);
+/* bbk_edgeindex_from_gfa that also keeps the graph itself (bases, L lines, KC) for the calls below; the other
+ * constructors keep only the segment names */
+int bbk_edgeindex_from_gfa_with_graph(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out);
+/* the graph as the index holds it (parsed once from the GFA): L lines, bases (0 when not kept), segment names */
+uint64_t bbk_edgeindex_links(const bbk_edgeindex *ix);
+uint64_t bbk_edgeindex_total_bases(const bbk_edgeindex *ix);
+const char *bbk_edgeindex_name(const bbk_edgeindex *ix, uint64_t segment); /* NULL past the last segment */
+/* Any pointer may be NULL.  h_bases: the segments' bases back to back; h_offsets: segments + 1 entries; h_links: 4 x u32
+ * per L line in file order (segment a, 1 if a is '+', segment b, 1 if b is '+'); h_kc: the first KC:i: of every S line
+ * as GFAReader reads it (io/graph/gfa_reader.cpp:65-68: an int32), 0 without one.  BBK_ERR_ARG for an index that
+ * keeps no graph. */
+int bbk_edgeindex_export_graph(const bbk_edgeindex *ix, char *h_bases, uint64_t *h_offsets, uint32_t *h_links,
+                               uint32_t *h_kc);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

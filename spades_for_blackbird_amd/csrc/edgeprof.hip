@@ -20,6 +20,22 @@
 // A read and its reverse complement (EasyStream followed_by_rc) map to conjugate edges: contrib(rc r, X) =
 // contrib(r, conj X), so one pass over the forward read adds both strands to the segment; a self-conjugate segment gets
 // both terms from the same edge and takes every delta twice.
+//
+// Mapping paths (spades-gmapper, projects/gmapper/main.cpp:156-247): k_gm_paths emits the full MappingPath of every
+// read instead, one record per range (read, oriented edge, initial [start, end), mapped [start, end)).  By the same
+// argument a position starts a new range exactly where the delta rule does not merge it into its predecessor's:
+//   start_i = found_i && !(i-1 found on the same oriented edge && (off_i > off_{i-1} || off_i == off_{i-1} && !kEpLoop1))
+// (FindKmer merges on off_i + 1 >= mapped end = off_{i-1} + 1; TryThread extends by one inside an edge, the
+// off_i = off_{i-1} + 1 case, and opens a range at offset 0 of an outgoing edge, which differs from FindKmer only on a
+// one-(k+1)-mer edge looped to itself).  kEpLoop1 comes from the L lines (a link e+ -> e+); the literal mapper asks
+// whether e is among OutgoingEdges(EdgeEnd(e)) in the graph ConstructionHelper::LinkEdges builds, which can differ on a
+// GFA with partial junctions.  Where it differs, only the cut of a run on that edge into ranges changes (one range per
+// position, or one for the run): the edge sequence and the summed initial sizes that GappedPathExtractor reads
+// (DeleteSameEdges, CountMappedEdgeSize) stay the same, so spades-gmapper's output does not depend on it, and
+// host/gmapper_main.cpp reports such edges.  Records are written without a shared cursor: a count pass takes one
+// ballot per wave, an exclusive scan gives every wave its first record, and a write pass fills them.  A range is closed
+// by the position after its last one (or by its last one at the end of a read), which finds the record through the
+// range index (range starts up to the position, minus one).
 #include <hip/hip_runtime.h>
 
 #include <omp.h>
@@ -59,6 +75,11 @@ struct bbk_edgeindex {
     uint64_t n_seg = 0, n = 0;           // segments, indexed (k+1)-mers
     std::vector<std::string> names;      // segment names
     std::vector<uint64_t> len;           // (k+1)-mers per segment = |seq| - k (the reference's g.length(e))
+    std::string bases;                   // the segments' ACGT back to back
+    std::vector<uint64_t> off;           // n_seg + 1 offsets into bases
+    std::vector<uint32_t> links;         // 4 x u32 per L line in file order: a, a is '+', b, b is '+'
+    std::vector<uint32_t> kc;            // KC:i: of every segment (0 without one)
+    bool has_graph = false;              // bases / off / links / kc are kept (bbk_edgeindex_from_gfa_with_graph)
     bbk::DevBuf keys;                    // n * W u64, ascending canonical (k+1)-mers
     bbk::DevBuf pos;                     // n EdgePos
     bbk::DevBuf prefix;
@@ -71,6 +92,11 @@ struct bbk_profiles {
     const bbk_edgeindex *ix = nullptr;
     unsigned samples = 0;
     bbk::DevBuf raw;  // n_seg * samples u64, [segment][sample]
+};
+
+struct bbk_paths {
+    uint64_t n_reads = 0, n_ranges = 0;
+    bbk::DevBuf ranges;  // n_ranges bbk_path_range in read order
 };
 
 namespace bbk {
@@ -207,6 +233,94 @@ __global__ __launch_bounds__(256) void k_ep_map(const uint64_t *__restrict__ wor
     }
 }
 
+// ---- mapping paths ----------------------------------------------------------------------------------------------------
+
+// k_ep_map's waves and lookups, one record per range of MappingPath (header comment).  WRITE = false: the range starts
+// of every wave to wave_cnt[wave]; WRITE = true: wave_cnt holds their exclusive scan, a start writes (edge, read,
+// starts) of its record and the position that ends a range writes its ends.
+template <int W, bool WRITE>
+__global__ __launch_bounds__(256) void k_gm_paths(const uint64_t *__restrict__ words, const uint64_t *__restrict__ woff,
+                                                 const uint32_t *__restrict__ rlen, const uint64_t *__restrict__ pos_off,
+                                                 uint64_t n_reads, uint64_t total, int k1, const Key<W> *__restrict__ keys,
+                                                 const EdgePos *__restrict__ epos, PrefixTable P,
+                                                 uint64_t *__restrict__ wave_cnt, bbk_path_range *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t wave = (((uint64_t)blockIdx.y * gridDim.x) + blockIdx.x) * kMapWaves + (threadIdx.x >> 6);
+    const uint64_t g0 = wave * kMapStep;
+    if (g0 >= total) return;  // wave-uniform
+    const int64_t g = (int64_t)g0 + lane - 1;
+    const bool valid = g >= 0 && (uint64_t)g < total;
+
+    bool found = false;
+    uint32_t off = 0, flags = 0;
+    uint64_t oe = ~0ull;
+    uint32_t p = 0, last = 0, rd = 0;  // position inside the read, the read's last position, the read
+    if (valid) {
+        uint64_t lo = 0, hi = n_reads - 1;
+        while (lo < hi) {
+            const uint64_t mid = (lo + hi + 1) >> 1;
+            if (pos_off[mid] <= (uint64_t)g) lo = mid;
+            else hi = mid - 1;
+        }
+        rd = (uint32_t)lo;
+        p = (uint32_t)((uint64_t)g - pos_off[lo]);
+        last = (uint32_t)(pos_off[lo + 1] - pos_off[lo] - 1);
+        const uint64_t *rw = words + woff[lo];
+        Key<W> q;
+        bool minimal;
+        if constexpr (W == 1) {
+            q = kmer_extract_canon1(rw, p, k1, (rlen[lo] - 1u) >> 5, &minimal);
+        } else {
+            const Key<W> x = kmer_extract<W>(rw, p, k1);
+            const Key<W> r = kmer_rc<W>(x, k1);
+            minimal = !kmer_less_nucl<W>(r, x);
+            q = key_select<W>(minimal, x, r);
+        }
+        const uint64_t j = table_find<W>(keys, P, q);
+        if (j != kNotFound) {
+            const EdgePos e = epos[j];
+            found = true;
+            flags = e.flags;
+            const bool minus = minimal != ((e.flags & kEpCanonFw) != 0);
+            off = minus ? e.off_rc : e.off_fw;
+            oe = 2ull * e.seg + ((minus && !(e.flags & kEpSelfConj)) ? 1u : 0u);
+        }
+    }
+    const uint64_t pred_oe = __shfl_up(oe, 1);
+    const uint32_t pred_off = __shfl_up(off, 1);
+    const int pred_found = __shfl_up((int)found, 1);
+    const bool pred_here = lane > 0 && p > 0 && pred_found;  // the predecessor is on the graph, in the same read
+    const bool cont = found && pred_here && pred_oe == oe &&
+                      (off > pred_off || (off == pred_off && !(flags & kEpLoop1)));
+    const bool start = lane > 0 && found && !cont;
+    const uint64_t starts = __ballot(start);
+    if constexpr (!WRITE) {
+        if (lane == 0) wave_cnt[wave] = (uint64_t)__popcll(starts);
+    } else {
+        if (lane == 0) return;  // lane 0 is the previous wave's lane 63
+        // range starts at positions before g: earlier waves, then lanes 1 .. lane-1 of this one
+        const uint64_t before = wave_cnt[wave] + (uint64_t)__popcll(starts & ((1ull << lane) - 1));
+        if (start) {
+            bbk_path_range &r = out[before];
+            r.edge = oe;
+            r.read = rd;
+            r.init_start = p;
+            r.map_start = off;
+            r.reserved = 0;
+        }
+        if (pred_here && !cont) {  // the predecessor ends its range
+            bbk_path_range &r = out[before - 1];
+            r.init_end = p;
+            r.map_end = pred_off + 1;
+        }
+        if (found && p == last) {  // the read ends on the graph
+            bbk_path_range &r = out[before + (start ? 1 : 0) - 1];
+            r.init_end = p + 1;
+            r.map_end = off + 1;
+        }
+    }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------
 
 static inline char comp_base(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; }
@@ -223,6 +337,7 @@ struct HostGraph {
     std::string bases;
     std::vector<uint64_t> off{0};
     std::vector<HostLink> links;
+    std::vector<uint32_t> kc;  // KC:i: per segment (empty: none known)
 };
 
 template <int W>
@@ -243,7 +358,8 @@ static void run_gather(bbk_ctx *ctx, const DevBuf &keys, const DevBuf &idx, cons
 }
 
 // the index of a graph held on the host, checked as the position-local form needs
-static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g) {
+// keep_graph: the index also keeps the bases, offsets, links and KC of the graph (bbk_edgeindex_export_graph)
+static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g, bool keep_graph) {
     BBK_REQUIRE(k >= 1 && k < BBK_MAX_K && k % 2 == 1, BBK_ERR_ARG, "edge index: k = %u must be odd and < %d", k, BBK_MAX_K);
     const uint64_t ns = g.names.size();
     BBK_REQUIRE(ns > 0, BBK_ERR_ARG, "edge index: the graph has no segments");
@@ -317,7 +433,22 @@ static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g) {
     int rc = bbk_reads_from_ascii(ctx, g.bases.data(), g.off.data(), ns, &sr);
     if (rc != BBK_OK) throw Error{rc};
     std::unique_ptr<bbk_reads, void (*)(bbk_reads *)> sr_guard(sr, bbk_reads_free);
-    std::string().swap(g.bases);
+    if (keep_graph) {  // what spades-gmapper rebuilds the graph from; the profiles need none of it
+        ix->has_graph = true;
+        ix->bases = std::move(g.bases);
+        ix->off = std::move(g.off);
+        ix->kc = g.kc.empty() ? std::vector<uint32_t>(ns, 0) : std::move(g.kc);
+        ix->links.resize(4 * g.links.size());
+        for (size_t j = 0; j < g.links.size(); ++j) {
+            const HostLink &l = g.links[j];
+            ix->links[4 * j] = l.a;
+            ix->links[4 * j + 1] = l.oa ? 1u : 0u;
+            ix->links[4 * j + 2] = l.b;
+            ix->links[4 * j + 3] = l.ob ? 1u : 0u;
+        }
+    } else {
+        std::string().swap(g.bases);
+    }
 
     const unsigned W = ix->W;
     DevBuf d_emit((ns + 1) * 8), d_len(ns * 4), d_flags(ns * 4);
@@ -419,6 +550,13 @@ static void parse_gfa(const char *path, unsigned k, HostGraph &g) {
                 }
                 g.off.push_back(g.bases.size());
                 g.names.push_back(fld(1));
+                uint32_t kc = 0;  // the first KC:i: tag, read as the gfa library reads it (an int32; gfa_reader.cpp:65-68)
+                for (const char *t = fe[2]; t + 6 <= le; ++t)
+                    if (t[0] == '\t' && memcmp(t + 1, "KC:i:", 5) == 0) {
+                        kc = (uint32_t)(int32_t)strtol(t + 6, nullptr, 10);
+                        break;
+                    }
+                g.kc.push_back(kc);
             } else {
                 BBK_REQUIRE(nf >= 6 && fe[2] - fs[2] == 1 && fe[4] - fs[4] == 1 && (*fs[2] == '+' || *fs[2] == '-') &&
                                 (*fs[4] == '+' || *fs[4] == '-'),
@@ -490,6 +628,27 @@ static void run_map(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uin
     check_launch("k_ep_map");
 }
 
+// one pass of k_gm_paths: out == nullptr counts the range starts per wave, otherwise writes the ranges
+template <int W>
+static void run_paths(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix,
+                      uint64_t *wave_cnt, bbk_path_range *out) {
+    const int w0bits = (W == 1) ? (int)(2 * ix->k1) : 64;
+    const uint64_t waves = (total + kMapStep - 1) / kMapStep;
+    const PrefixTable P{ix->prefix.p, w0bits - (int)ix->prefix_bits, ix->prefix_wide ? 1 : 0};
+    const dim3 grid = grid_blocks((waves + kMapWaves - 1) / kMapWaves), block(64 * kMapWaves);
+    // the lookups' bytes as for k_ep_map; each pass runs them
+    KernelTimer t(ctx, out ? "gmap_write" : "gmap_count", (double)total * (8.0 * W + sizeof(EdgePos) + 4));
+    if (out)
+        hipLaunchKernelGGL((k_gm_paths<W, true>), grid, block, 0, ctx->stream, r->d_words, r->d_woff, r->d_len,
+                           pos_off.as<uint64_t>(), r->n, total, (int)ix->k1, ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(),
+                           P, wave_cnt, out);
+    else
+        hipLaunchKernelGGL((k_gm_paths<W, false>), grid, block, 0, ctx->stream, r->d_words, r->d_woff, r->d_len,
+                           pos_off.as<uint64_t>(), r->n, total, (int)ix->k1, ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(),
+                           P, wave_cnt, out);
+    check_launch("k_gm_paths");
+}
+
 static size_t fmt_line(char *dst, size_t cap, const std::string &name, const uint64_t *raw, unsigned S, uint64_t len) {
     size_t o = 0;
     o += (size_t)snprintf(dst + o, cap - o, "%s\t", name.c_str());
@@ -504,7 +663,7 @@ using namespace bbk;
 
 extern "C" {
 
-int bbk_edgeindex_from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out) {
+static int from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out, bool keep_graph) {
     return guarded([&] {
         BBK_REQUIRE(ctx && path && out, BBK_ERR_ARG, "bbk_edgeindex_from_gfa: NULL argument");
         BBK_REQUIRE(k >= 1 && k < BBK_MAX_K && k % 2 == 1, BBK_ERR_ARG, "bbk_edgeindex_from_gfa: k = %u must be odd and < %d",
@@ -512,8 +671,16 @@ int bbk_edgeindex_from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgei
         BBK_HIP(hipSetDevice(ctx->device));
         HostGraph g;
         parse_gfa(path, k, g);
-        *out = build_index(ctx, k, g);
+        *out = build_index(ctx, k, g, keep_graph);
     });
+}
+
+int bbk_edgeindex_from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out) {
+    return from_gfa(ctx, path, k, out, false);
+}
+
+int bbk_edgeindex_from_gfa_with_graph(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **out) {
+    return from_gfa(ctx, path, k, out, true);
 }
 
 int bbk_edgeindex_from_unitigs(bbk_ctx *ctx, const bbk_unitigs *u, bbk_edgeindex **out) {
@@ -532,7 +699,7 @@ int bbk_edgeindex_from_unitigs(bbk_ctx *ctx, const bbk_unitigs *u, bbk_edgeindex
         for (uint64_t i = 0; i < nu; ++i) g.names[i] = std::to_string(3 + 2 * i);  // as bbk_unitigs_write_gfa names them
         g.links.resize(nl);
         for (uint64_t l = 0; l < nl; ++l) g.links[l] = {hl[4 * l], hl[4 * l + 2], hl[4 * l + 1] == 1, hl[4 * l + 3] == 1};
-        *out = build_index(ctx, unitigs_k(u), g);
+        *out = build_index(ctx, unitigs_k(u), g, false);
     });
 }
 
@@ -632,5 +799,86 @@ int bbk_profiles_write(bbk_ctx *ctx, const bbk_profiles *p, const char *path) {
 }
 
 void bbk_profiles_free(bbk_profiles *p) { delete p; }
+
+int bbk_edgeindex_map_paths(bbk_ctx *ctx, const bbk_edgeindex *ix, const bbk_reads *reads, bbk_paths **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && ix && reads && out, BBK_ERR_ARG, "bbk_edgeindex_map_paths: NULL argument");
+        BBK_REQUIRE(reads->n < (1ull << 32), BBK_ERR_ARG, "bbk_edgeindex_map_paths: %llu reads, at most 2^32 - 1 per batch",
+                    (unsigned long long)reads->n);
+        BBK_HIP(hipSetDevice(ctx->device));
+        auto p = std::make_unique<bbk_paths>();
+        const uint64_t n = reads->n;
+        p->n_reads = n;
+        if (n > 0 && ix->n > 0) {
+            DevBuf pos_off((n + 1) * 8);
+            hipLaunchKernelGGL(k_ep_npos, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, reads->d_len, n, ix->k1,
+                               pos_off.as<uint64_t>());
+            check_launch("k_ep_npos");
+            const uint64_t total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
+            if (total > 0) {
+                BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
+                const uint64_t waves = (total + kMapStep - 1) / kMapStep;
+                DevBuf wave_cnt(waves * 8);
+                auto run = [&](bbk_path_range *o) {
+                    switch (ix->W) {
+                        case 1: run_paths<1>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
+                        case 2: run_paths<2>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
+                        case 3: run_paths<3>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
+                        default: run_paths<4>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
+                    }
+                };
+                run(nullptr);
+                p->n_ranges = exclusive_scan_u64(ctx, wave_cnt.as<uint64_t>(), wave_cnt.as<uint64_t>(), waves);
+                p->ranges.alloc(p->n_ranges * sizeof(bbk_path_range));
+                if (p->n_ranges) run(p->ranges.as<bbk_path_range>());
+                BBK_HIP(hipStreamSynchronize(ctx->stream));  // pos_off, wave_cnt and the staged total die here
+            }
+        }
+        *out = p.release();
+    });
+}
+
+uint64_t bbk_paths_reads(const bbk_paths *p) { return p ? p->n_reads : 0; }
+uint64_t bbk_paths_ranges(const bbk_paths *p) { return p ? p->n_ranges : 0; }
+
+int bbk_paths_export(bbk_ctx *ctx, const bbk_paths *p, uint64_t *h_read_offsets, bbk_path_range *h_ranges) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && p, BBK_ERR_ARG, "bbk_paths_export: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        std::vector<bbk_path_range> tmp;
+        bbk_path_range *r = h_ranges;
+        if (!r && h_read_offsets) {
+            tmp.resize(p->n_ranges);
+            r = tmp.data();
+        }
+        if (r && p->n_ranges) d2h_sync(ctx, r, p->ranges.p, p->n_ranges * sizeof(bbk_path_range));
+        if (h_read_offsets) {  // the ranges are in read order: count them per read
+            std::fill(h_read_offsets, h_read_offsets + p->n_reads + 1, 0ull);
+            for (uint64_t i = 0; i < p->n_ranges; ++i) ++h_read_offsets[r[i].read + 1];
+            for (uint64_t i = 0; i < p->n_reads; ++i) h_read_offsets[i + 1] += h_read_offsets[i];
+        }
+    });
+}
+
+void bbk_paths_free(bbk_paths *p) { delete p; }
+
+uint64_t bbk_edgeindex_links(const bbk_edgeindex *ix) { return ix ? ix->links.size() / 4 : 0; }
+uint64_t bbk_edgeindex_total_bases(const bbk_edgeindex *ix) { return ix ? ix->bases.size() : 0; }
+const char *bbk_edgeindex_name(const bbk_edgeindex *ix, uint64_t segment) {
+    return ix && segment < ix->n_seg ? ix->names[segment].c_str() : nullptr;
+}
+
+int bbk_edgeindex_export_graph(const bbk_edgeindex *ix, char *h_bases, uint64_t *h_offsets, uint32_t *h_links,
+                               uint32_t *h_kc) {
+    return guarded([&] {
+        BBK_REQUIRE(ix, BBK_ERR_ARG, "bbk_edgeindex_export_graph: NULL index");
+        BBK_REQUIRE(ix->has_graph, BBK_ERR_ARG,
+                    "bbk_edgeindex_export_graph: the index keeps no graph (load it with bbk_edgeindex_from_gfa_with_graph)");
+        if (h_bases) memcpy(h_bases, ix->bases.data(), ix->bases.size());
+        if (h_offsets) memcpy(h_offsets, ix->off.data(), ix->off.size() * 8);
+        if (h_links) memcpy(h_links, ix->links.data(), ix->links.size() * 4);
+        if (h_kc) memcpy(h_kc, ix->kc.data(), ix->kc.size() * 4);
+    });
+}
 
 }  // extern "C"

@@ -9,6 +9,9 @@ _LIB = None
 
 BOTH_STRANDS, CANONICAL, WITH_COUNTS, UNSORTED, REFERENCE_ORDER, WITH_MASKS = 1, 2, 4, 8, 16, 32
 ORDER_SORTED, ORDER_REFERENCE_BUCKETS16 = 0, 1
+# bbk_path_range of include/bbk.h
+PATH_RANGE = np.dtype([("edge", np.uint64), ("read", np.uint32), ("init_start", np.uint32), ("init_end", np.uint32),
+                       ("map_start", np.uint32), ("map_end", np.uint32), ("reserved", np.uint32)])
 
 # every symbol include/bbk.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -29,6 +32,8 @@ SYMBOLS = [
     "bbk_unitigs_write_gfa", "bbk_unitigs_write_fasta", "bbk_unitigs_write_fastg", "bbk_unitigs_write_spades", "bbk_unitigs_free",
     "bbk_edgeindex_from_gfa", "bbk_edgeindex_from_unitigs", "bbk_edgeindex_segments", "bbk_edgeindex_size", "bbk_edgeindex_free",
     "bbk_profiles_begin", "bbk_profiles_push_reads", "bbk_profiles_export_raw", "bbk_profiles_write", "bbk_profiles_free",
+    "bbk_edgeindex_map_paths", "bbk_edgeindex_from_gfa_with_graph", "bbk_paths_reads", "bbk_paths_ranges", "bbk_paths_export", "bbk_paths_free",
+    "bbk_edgeindex_links", "bbk_edgeindex_total_bases", "bbk_edgeindex_name", "bbk_edgeindex_export_graph",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -180,6 +185,20 @@ def load_library():
         L.bbk_profiles_export_raw.argtypes = [vp, vp, vp]
         L.bbk_profiles_write.argtypes = [vp, vp, C.c_char_p]
         L.bbk_profiles_free.argtypes = [vp]
+        L.bbk_edgeindex_map_paths.argtypes = [vp, vp, vp, C.POINTER(vp)]
+        L.bbk_edgeindex_from_gfa_with_graph.argtypes = [vp, C.c_char_p, C.c_uint, C.POINTER(vp)]
+        for f in ("reads", "ranges"):
+            getattr(L, "bbk_paths_" + f).restype = u64
+            getattr(L, "bbk_paths_" + f).argtypes = [vp]
+        L.bbk_paths_export.argtypes = [vp, vp, vp, vp]
+        L.bbk_paths_free.argtypes = [vp]
+        L.bbk_paths_free.restype = None
+        for f in ("links", "total_bases"):
+            getattr(L, "bbk_edgeindex_" + f).restype = u64
+            getattr(L, "bbk_edgeindex_" + f).argtypes = [vp]
+        L.bbk_edgeindex_name.restype = C.c_char_p
+        L.bbk_edgeindex_name.argtypes = [vp, u64]
+        L.bbk_edgeindex_export_graph.argtypes = [vp, vp, vp, vp, vp]
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -382,10 +401,12 @@ class Context:
         _check(self._L.bbk_unitigs_build_ex(self._h, ext._h, ref_threads, C.byref(h)))
         return Unitigs(self, h)
 
-    def edgeindex_from_gfa(self, path, k):
-        """(k+1)-mer index of a GFA graph for unitig-coverage: S lines are the segments, L lines must be kM overlaps."""
+    def edgeindex_from_gfa(self, path, k, keep_graph=False):
+        """(k+1)-mer index of a GFA graph for unitig-coverage: S lines are the segments, L lines must be kM overlaps.
+        keep_graph: the index also keeps the bases, links and KC (EdgeIndex.graph)."""
         h = C.c_void_p()
-        _check(self._L.bbk_edgeindex_from_gfa(self._h, path.encode(), k, C.byref(h)))
+        f = self._L.bbk_edgeindex_from_gfa_with_graph if keep_graph else self._L.bbk_edgeindex_from_gfa
+        _check(f(self._h, path.encode(), k, C.byref(h)))
         return EdgeIndex(self, h)
 
     def edgeindex_from_unitigs(self, unitigs):
@@ -719,6 +740,34 @@ class EdgeIndex(_Handle):
         h = C.c_void_p()
         _check(self._L.bbk_profiles_begin(self.ctx._h, self._h, n_samples, C.byref(h)))
         return Profiles(self, h, n_samples)
+
+    def map_paths(self, reads):
+        """MapSequence of every read as it stands (spades-gmapper's mapper): (offsets, ranges), offsets np.uint64
+        [reads + 1], ranges a PATH_RANGE array in read order (edge = 2 * segment + 1 on the reverse strand)"""
+        h = C.c_void_p()
+        _check(self._L.bbk_edgeindex_map_paths(self.ctx._h, self._h, reads._h, C.byref(h)))
+        try:
+            off = np.zeros(int(self._L.bbk_paths_reads(h)) + 1, dtype=np.uint64)
+            rec = np.zeros(int(self._L.bbk_paths_ranges(h)), dtype=PATH_RANGE)
+            _check(self._L.bbk_paths_export(self.ctx._h, h, _ptr(off), _ptr(rec)))
+        finally:
+            self._L.bbk_paths_free(h)
+        return off, rec
+
+    def graph(self):
+        """(names, sequences, links [(a, '+'|'-', b, '+'|'-')], kc np.uint32) as the index holds the graph"""
+        ns, nl = self.segments, int(self._L.bbk_edgeindex_links(self._h))
+        bases = C.create_string_buffer(int(self._L.bbk_edgeindex_total_bases(self._h)) + 1)
+        off = np.zeros(ns + 1, dtype=np.uint64)
+        lk = np.zeros(4 * nl + 1, dtype=np.uint32)
+        kc = np.zeros(ns, dtype=np.uint32)
+        _check(self._L.bbk_edgeindex_export_graph(self._h, bases, _ptr(off), _ptr(lk), _ptr(kc)))
+        raw = bases.raw
+        seqs = [raw[int(off[i]):int(off[i + 1])].decode() for i in range(ns)]
+        names = [self._L.bbk_edgeindex_name(self._h, i).decode() for i in range(ns)]
+        sign = lambda x: "+" if x else "-"  # noqa: E731
+        links = [(int(lk[4 * j]), sign(lk[4 * j + 1]), int(lk[4 * j + 2]), sign(lk[4 * j + 3])) for j in range(nl)]
+        return names, seqs, links, kc
 
 
 class Profiles(_Handle):
