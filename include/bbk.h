@@ -62,7 +62,8 @@ int bbk_ctx_profile_get(bbk_ctx *ctx, const char *family, double *ms_total, uint
                         double *bytes_total);
 /* Event counters are read the same way (launches = events, bytes_total = summed value): "stat_slot_records",
  * "stat_slot_spilled", "stat_slot_overflow_segments", "stat_slot_overflow_buckets", "stat_slot_reprocessed" -- what the
- * histogram-free slot mode of stage A placed, spilled and had to reprocess (skewed inputs). */
+ * histogram-free slot mode of stage A placed, spilled and had to reprocess (skewed inputs); "stat_host_waits": the times
+ * the counting path made the host wait for the stream (launches = waits). */
 
 /* ---- reads: replaces io::EasyStream(file, followed_by_rc=true, handle_Ns=true)
  *      (common/io/reads/io_helper.cpp:19-32) and the binary read cache

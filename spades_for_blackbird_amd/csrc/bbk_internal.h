@@ -169,6 +169,14 @@ struct bbk_ctx {
     // pinned staging for large device-to-host copies (pageable copies run at a fraction of PCIe)
     void *pinned[2] = {nullptr, nullptr};
     size_t pinned_bytes = 0;
+    // pinned staging of a pass's planning arrays (msd.hip: the level-2 layout goes to the device in one copy).  Written
+    // only right after a wait on the stream, so the copy queued from it before that wait has finished
+    void *plan_pinned = nullptr;
+    size_t plan_pinned_bytes = 0;
+    // free device memory as the driver last reported it, and the arena figures it was read at: asked again only after the
+    // arena has mapped or trimmed
+    size_t mem_free = 0;
+    uint64_t mem_free_mapped_now = ~0ull, mem_free_mapped_total = ~0ull;
     // super-k-mer stage A (superk.hip): instances / distinct keys of the last batch it finished (0: none yet).  The
     // buckets of the next batch are planned for that multiplicity instead of the worst case 1
     double superk_dup = 0;
@@ -215,6 +223,13 @@ void launch_timed(bbk_ctx *ctx, K fn, const char *name, double bytes, uint32_t g
     KernelTimer t(ctx, name, bytes);
     hipLaunchKernelGGL(fn, dim3(grid), dim3(threads), lds, ctx->stream, args...);
     check_launch(name);
+}
+
+// Every wait of the host for the context's stream in the counting path goes through here: "stat_host_waits" counts
+// them (the device idles ~20 us around each), so a test can hold the path to its number of decisions
+inline void stream_wait(bbk_ctx *ctx) {
+    ctx->add_stat("stat_host_waits", 1);
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
 }
 
 // a numeric BBK_* knob: `unset` when the variable is not set (an empty value reads as 0)
@@ -276,8 +291,32 @@ uint64_t unique_records(bbk_ctx *ctx, int W, const void *keys, const uint32_t *v
                         uint32_t *out_vals, ReduceOp op, bool drop_zero);
 // Exclusive scan of n u64 values (in place allowed); returns the total.
 uint64_t exclusive_scan_u64(bbk_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n);
+// Two arrays of n values in the same launches and ONE wait; out0[n] and out1[n] receive the totals as well (the
+// outputs hold n + 1 entries).
+void exclusive_scan2_u64(bbk_ctx *ctx, const uint64_t *in0, uint64_t *out0, const uint64_t *in1, uint64_t *out1,
+                         uint64_t n, uint64_t totals[2]);
+// What the first level of a scan reads: u64 values, u32 values (SCAN_U32_FLAGGED: 0xFFFFFFFF counts 0), or the fill of
+// slot i from its cursor, min(p[i] - i * stride, cap) (SCAN_SLOT_FILL)
+enum { SCAN_U64 = 0, SCAN_U32_FLAGGED = 1, SCAN_SLOT_FILL = 2 };
+struct ScanSrc {
+    const void *p;
+    uint32_t kind, stride, cap;
+};
+// The scan without its wait: narr (1 or 2) arrays are scanned into out[a] (u64), the totals are left in d_total[a] on
+// the device (tail: also in out[a][n]).  The scratch buffers go into `keep`, which must live until the caller has waited
+// for the stream.
+void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t *const *out, uint64_t n,
+                            uint64_t *d_total, bool tail, std::vector<DevBuf> &keep);
+// free device memory (see bbk_ctx::mem_free)
+size_t device_free_cached(bbk_ctx *ctx);
+// the context's pinned planning block, at least `bytes` long
+void *plan_staging(bbk_ctx *ctx, size_t bytes);
 
 }  // namespace bbk
+
+// Exported for the tests only (not declared in bbk.h): exclusive_scan2_u64 in place over two device arrays of n + 1 u64
+// each (entries 0..n-1 are the input, entry n receives the total); totals[2] on the host receives the two sums.
+extern "C" int bbk_scan2_u64(bbk_ctx *ctx, void *d_a, void *d_b, uint64_t n, uint64_t *totals);
 
 struct bbk_reads {
     bbk_ctx *ctx = nullptr;

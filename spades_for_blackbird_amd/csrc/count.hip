@@ -248,7 +248,7 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
         out_vals.alloc(D * 4 + 16);
         BBK_HIP(bbk::copy_async(out_vals.p, rv, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
     n_distinct = D;
 }
 
@@ -275,7 +275,7 @@ static uint64_t lsd_sort_unique(bbk_ctx *ctx, unsigned k, const void *d_keys, co
         out_vals.alloc(D * 4 + 16);
         BBK_HIP(bbk::copy_async(out_vals.p, cb.p, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
     return D;
 }
 
@@ -416,7 +416,7 @@ void Accum::merge() {
         if (has_vals())
             BBK_HIP(bbk::copy_async(cv.as<uint32_t>() + o, vb.p, cnt * 4, hipMemcpyDeviceToDevice, ctx->stream));
         o += cnt;
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         kb.release();
         vb.release();
     };
@@ -501,7 +501,7 @@ static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, cons
         s.counts.alloc(D2 * 4);
         BBK_HIP(bbk::copy_async(s.counts.p, ect.p, D2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
     }
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
 }
 
 static void check_k(unsigned k) {
@@ -738,7 +738,7 @@ int bbk_kmerset_from_device_ex(bbk_ctx *ctx, const void *d_keys, const void *d_c
             s->counts.alloc(D * 4);
             BBK_HIP(bbk::copy_async(s->counts.p, cb.p, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
         }
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         *out = s.release();
     });
 }
@@ -816,13 +816,13 @@ static void export_ordered(bbk_ctx *ctx, const bbk_kmerset *s, const PassDesc *p
                      key_passes(s->k));
         BBK_HIP(bbk::copy_async(dst_keys, a.p, s->n * rec, hipMemcpyDefault, ctx->stream));
         if (wc) BBK_HIP(bbk::copy_async(dst_counts, ca.p, s->n * 4, hipMemcpyDefault, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         return;
     }
     if (!pd || (s->ref_order && pd->kind == 1 && pd->nb == 16)) {  // stored in the requested order: plain copy
         BBK_HIP(bbk::copy_async(dst_keys, s->keys.p, s->n * rec, hipMemcpyDefault, ctx->stream));
         if (wc) BBK_HIP(bbk::copy_async(dst_counts, s->counts.p, s->n * 4, hipMemcpyDefault, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         return;
     }
     // One stable pass on the bucket digit keeps the ascending order inside each bucket.  It reads the set
@@ -840,7 +840,7 @@ static void export_ordered(bbk_ctx *ctx, const bbk_kmerset *s, const PassDesc *p
         for (unsigned i = 0; i < pd->nb; ++i) h_counts[i] = hc[i];
     if (!kdev) BBK_HIP(hipMemcpyAsync(dst_keys, tk.p, s->n * rec, hipMemcpyDeviceToHost, ctx->stream));
     if (wc && !cdev) BBK_HIP(hipMemcpyAsync(dst_counts, tc.p, s->n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
 }
 
 int bbk_kmerset_export(bbk_ctx *ctx, const bbk_kmerset *s, unsigned order, void *dst_keys, void *dst_counts) {
@@ -889,7 +889,7 @@ int bbk_kmerset_verify_order(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t *n_run
         check_launch("k_order_check");
         unsigned long long h[40];
         BBK_HIP(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         *n_runs = 1 + h[0];
         *n_equal = h[1];
         if (h_run_starts) {
@@ -915,7 +915,7 @@ int bbk_kmerset_bucket_offsets(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t *h_o
         check_launch("k_bucket_bounds");
         unsigned long long h[17];
         BBK_HIP(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         for (int b = 0; b <= 16; ++b) h_offsets[b] = h[b];
     });
 }
@@ -932,7 +932,7 @@ int bbk_kmerset_get(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t first, uint64_t
         if (h_counts && s->has_counts)
             BBK_HIP(hipMemcpyAsync(h_counts, s->counts.as<uint32_t>() + first, count * 4, hipMemcpyDeviceToHost,
                                    ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
     });
 }
 

@@ -211,13 +211,21 @@ __device__ inline uint64_t read_at(const uint64_t *__restrict__ off, uint64_t n_
     return lo;
 }
 
-// one thread per tile of `tile` chunks (a chunk = ch k-mer positions of one read)
+// one thread per tile of `tile` chunks (a chunk = ch k-mer positions of one read).  Two tilings of the same reads in
+// one launch: threads [0, n_tiles) describe the tiles of `tile` chunks into out, the next n_tiles_b threads those of
+// tile_b chunks into out_b (the scatter and the histogram kernels of level 1 have different workgroup sizes).
 __global__ void k_tile_reads(const uint64_t *__restrict__ coff, const uint64_t *__restrict__ woff,
                              const uint32_t *__restrict__ len, uint64_t n_reads, uint64_t n_tiles, uint32_t tile,
+                             RdTile *__restrict__ out, uint64_t n_tiles_b, uint32_t tile_b, RdTile *__restrict__ out_b,
                              uint32_t ch, uint32_t k, uint32_t max_reads, uint32_t max_words,
-                             const uint32_t *__restrict__ unordered, RdTile *__restrict__ out) {
-    const uint64_t t = BBK_GID();
-    if (t >= n_tiles) return;
+                             const uint32_t *__restrict__ unordered) {
+    uint64_t t = BBK_GID();
+    if (t >= n_tiles) {
+        t -= n_tiles;
+        if (t >= n_tiles_b) return;
+        tile = tile_b;
+        out = out_b;
+    }
     const uint64_t c0 = t * (uint64_t)tile;
     const uint64_t r0 = read_at(coff, n_reads, c0), r1 = read_at(coff, n_reads, c0 + tile);
     // staged word window: from the word of the first base this tile touches in r0 (one base before the chunk,
@@ -2090,19 +2098,22 @@ __global__ void k_flagged(const uint32_t *__restrict__ dcount, uint32_t n, uint3
     }
 }
 
-// records every bucket slot holds (cursor - slot start, at most the slot's capacity)
-__global__ void k_slot_counts(const uint32_t *__restrict__ cursor, uint32_t n, uint32_t stride, uint32_t cap,
-                              uint64_t *__restrict__ out) {
+// slot mode, one thread per bucket: its cursor starts at its slot; bucket_seg (narrow path, else null) gets the level-1
+// segment the bucket belongs to, the largest s in [0, nseg) with seg_bin[s] <= bucket
+__global__ void k_bucket_init(uint32_t *__restrict__ cursor, uint32_t n, uint32_t stride,
+                              const uint32_t *__restrict__ seg_bin, uint32_t nseg, uint16_t *__restrict__ bucket_seg) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const uint32_t c = cursor[i] - i * stride;
-        out[i] = c < cap ? c : cap;
+    if (i >= n) return;
+    cursor[i] = i * stride;
+    if (bucket_seg) {
+        uint32_t lo = 0, hi = nseg;
+        while (hi - lo > 1) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (seg_bin[mid] <= i) lo = mid;
+            else hi = mid;
+        }
+        bucket_seg[i] = (uint16_t)lo;
     }
-}
-
-__global__ void k_iota_mul(uint32_t *__restrict__ out, uint32_t n, uint32_t mul) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = i * mul;
 }
 
 __global__ void k_u32_to_u64(const uint32_t *__restrict__ in, uint64_t n, uint64_t *__restrict__ out, uint32_t clampv) {
@@ -2110,10 +2121,12 @@ __global__ void k_u32_to_u64(const uint32_t *__restrict__ in, uint64_t n, uint64
     if (i < n) out[i] = in[i] == 0xFFFFFFFFu ? (uint64_t)clampv : (uint64_t)in[i];
 }
 
-__global__ void k_scan_to_u32(const uint64_t *__restrict__ in, uint64_t n, uint64_t total, uint32_t *__restrict__ out) {
+// d_total (optional): the total is still on the device
+__global__ void k_scan_to_u32(const uint64_t *__restrict__ in, uint64_t n, uint64_t total,
+                              const uint64_t *__restrict__ d_total, uint32_t *__restrict__ out) {
     const uint64_t i = BBK_GID();
     if (i < n) out[i] = (uint32_t)in[i];
-    if (i == n) out[n] = (uint32_t)total;
+    if (i == n) out[n] = (uint32_t)(d_total ? *d_total : total);
 }
 
 // k-mers and chunks (of ch k-mer positions) of every read; *unordered is set when the packed words of the reads do not
@@ -3009,7 +3022,7 @@ void BucketView::materialise(bbk_ctx *ctx) {
     }
     if (n_extra)
         BBK_HIP(bbk::copy_async(keys.as<uint64_t>() + D, extra.p, n_extra * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
     release_slots();
 }
 
@@ -3358,11 +3371,25 @@ struct MsdRunner {
         const bool from_reads, has_val, ranged, has_dst, out_vals, need_vbuf, verbose;
         Plan P{};
         uint64_t N = 0, n_chunks = 0;  // records of the pass (a range: exact once level 1 has counted them); read chunks
-        DevBuf coff, tile_read, unordered, tiles_h;
+        DevBuf coff, tile_read, tiles_h;
+        // The pass's small device counters in one block, cleared by one fill when the pass starts and read back by one
+        // copy (fetch_flags).  u32 words: [0..3] spill counters ([0] spilled records [1] unused [2] buckets left to the
+        // caller), [4] reads not in word order, [8] duplicate seen by the direct pass, [12] flagged buckets (exact
+        // mode), [16..31] debug counters (BBK_VERBOSE), [32..35] two u64 scan totals
+        enum { kCtlSpill = 0, kCtlUnordered = 4, kCtlDup = 8, kCtlFlagN = 12, kCtlDbg = 16, kCtlTotal = 32, kCtlWords = 40 };
+        DevBuf ctl;
+        uint32_t h_ctl[kCtlWords] = {};
+        uint32_t *ctl_at(int w) const { return ctl.as<uint32_t>() + w; }
+        uint64_t *ctl_total() const { return reinterpret_cast<uint64_t *>(ctl_at(kCtlTotal)); }
+        uint64_t h_total() const {  // the scan total fetch_flags brought back
+            uint64_t t;
+            memcpy(&t, h_ctl + kCtlTotal, 8);
+            return t;
+        }
         ReadSrc S{}, Sh{};
         TileMap M1{}, M2{};
         PartLevel L1{}, L2{};
-        DevBuf spill_k, spill_v, spill_n;  // spill_n: u32 counters [0] spilled records [1] unused [2] buckets left to the caller
+        DevBuf spill_k, spill_v;
         // level 1 (off1 / tstart / hsub are per level-1 CURSOR: per segment, or per (segment, XCD) sub-slot on the
         // narrow path)
         DevBuf hist1, cur1, bufA, valA;
@@ -3372,11 +3399,21 @@ struct MsdRunner {
         // level 2
         uint32_t nbuckets = 0, ntiles2 = 0, nwg2 = 0;
         bool narrow_b = false;
-        DevBuf seg_tile, seg_off, seg_nb2, seg_bin, seg_size, xstart_d, desc2, desc2h, hist2, boff, bufB, valB;
+        // the layout arrays: one pinned host block (stage; its head is the source of the level-1 cursors), one copy, one
+        // device block
+        uint32_t *stage = nullptr;
+        DevBuf layout_d;
+        uint32_t *seg_tile = nullptr, *seg_off = nullptr, *seg_nb2 = nullptr, *seg_bin = nullptr, *seg_size = nullptr,
+                 *xstart_d = nullptr;
+        DevBuf desc2, desc2h, hist2, boff, bufB, valB;
         std::vector<uint32_t> xstart;
         // buckets
-        DevBuf dcount, dbg, dupf, slot_off, bseg, bbase, flag_ids, flag_n;  // bbase: narrow stage B, smallest key of a bucket
-        std::vector<uint16_t> h_bseg;
+        DevBuf dcount, slot_off, bseg, bbase, flag_ids;  // bbase: narrow stage B, smallest key of a bucket
+        // scans whose totals come back with the flags (fetch_flags): c64 = key slots, exclusive scan of the slot fills;
+        // d64 = hash slots, exclusive scan of the distinct counts.  scan_keep: their scratch, alive until the pass ends
+        DevBuf c64, d64;
+        bool d64_scanned = false;
+        std::vector<DevBuf> scan_keep;
         BucketArgs A{};
         bool direct = false;
         uint32_t ctr[4] = {0, 0, 0, 0};  // spilled, direct, flagged, duplicates seen by the direct pass
@@ -3396,6 +3433,8 @@ struct MsdRunner {
 
         // n_records: the whole input may be split into ranges; TooBig then gives its record count
         Outcome run(uint64_t *n_records = nullptr) {
+            ctl.alloc(kCtlWords * 4);
+            BBK_HIP(hipMemsetAsync(ctl.p, 0, kCtlWords * 4, ctx->stream));
             count_instances();
             out.instances = N;
             out.n = 0;
@@ -3442,19 +3481,18 @@ struct MsdRunner {
             BBK_REQUIRE(R.dmode == MSD_HASH, BBK_ERR_INTERNAL, "reads are partitioned by hash prefix only");
             DevBuf nk((rd->n + 1) * sizeof(uint64_t));
             coff.alloc((rd->n + 1) * sizeof(uint64_t));
-            unordered.alloc(16);
-            BBK_HIP(hipMemsetAsync(unordered.p, 0, 16, ctx->stream));
             if (rd->n) {
                 hipLaunchKernelGGL(k_kmers_per_read2, bbk::grid_blocks((rd->n + 255) / 256), dim3(256), 0, ctx->stream,
                                    rd->d_len, rd->d_woff, rd->n, R.k, (uint32_t)RdCfg<W>::CH, nk.as<uint64_t>(),
-                                   coff.as<uint64_t>(), unordered.as<uint32_t>());
+                                   coff.as<uint64_t>(), ctl_at(kCtlUnordered));
                 check_launch("k_kmers_per_read2");
             }
-            N = exclusive_scan_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), rd->n);
-            n_chunks = exclusive_scan_u64(ctx, coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n);
-            BBK_HIP(hipMemcpyAsync(coff.as<uint64_t>() + rd->n, &n_chunks, sizeof(uint64_t), hipMemcpyHostToDevice,
-                                   ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            // both scans in the same launches, both totals in one wait; coff[n] = n_chunks is written by the scan
+            uint64_t tot[2] = {0, 0};
+            exclusive_scan2_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n,
+                                tot);
+            N = tot[0];
+            n_chunks = tot[1];
         }
 
         // ---- level-1 tiles (reads) and the slot layout
@@ -3465,14 +3503,11 @@ struct MsdRunner {
                 tile_read.alloc(((size_t)P.ntiles1 + 1) * sizeof(RdTile));
                 tiles_h.alloc(((size_t)P.ntiles1h + 1) * sizeof(RdTile));
                 if (P.ntiles1) {
-                    hipLaunchKernelGGL(k_tile_reads, dim3((P.ntiles1 + 255) / 256), dim3(256), 0, ctx->stream,
-                                       coff.as<uint64_t>(), rd->d_woff, rd->d_len, rd->n, (uint64_t)P.ntiles1, P.rd_tile,
-                                       (uint32_t)RdCfg<W>::CH, R.k, (uint32_t)kRdSlots, (uint32_t)kRdWords,
-                                       unordered.as<uint32_t>(), tile_read.as<RdTile>());
-                    hipLaunchKernelGGL(k_tile_reads, dim3((P.ntiles1h + 255) / 256), dim3(256), 0, ctx->stream,
-                                       coff.as<uint64_t>(), rd->d_woff, rd->d_len, rd->n, (uint64_t)P.ntiles1h,
-                                       (uint32_t)kRdHistThreads, (uint32_t)RdCfg<W>::CH, R.k, (uint32_t)kRdSlots,
-                                       (uint32_t)kRdWords, unordered.as<uint32_t>(), tiles_h.as<RdTile>());
+                    hipLaunchKernelGGL(k_tile_reads, dim3(((uint64_t)P.ntiles1 + P.ntiles1h + 255) / 256), dim3(256), 0,
+                                       ctx->stream, coff.as<uint64_t>(), rd->d_woff, rd->d_len, rd->n, (uint64_t)P.ntiles1,
+                                       P.rd_tile, tile_read.as<RdTile>(), (uint64_t)P.ntiles1h, (uint32_t)kRdHistThreads,
+                                       tiles_h.as<RdTile>(), (uint32_t)RdCfg<W>::CH, R.k, (uint32_t)kRdSlots,
+                                       (uint32_t)kRdWords, ctl_at(kCtlUnordered));
                     check_launch("k_tile_reads");
                 }
                 S = ReadSrc{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tile_read.as<RdTile>(), rd->n,
@@ -3484,8 +3519,6 @@ struct MsdRunner {
             if (P.slots) {
                 spill_k.alloc((size_t)P.spill_cap * rec);
                 if (has_val) spill_v.alloc((size_t)P.spill_cap * 4);
-                spill_n.alloc(16);
-                BBK_HIP(hipMemsetAsync(spill_n.p, 0, 16, ctx->stream));
                 use_slots(L1, P.seg_cap, P.seg_cap);
                 L1.xcd_shift = P.xs;
                 L1.sub_cap = P.sub_cap;
@@ -3498,7 +3531,7 @@ struct MsdRunner {
             L.slot_stride = stride;
             L.spill_keys = spill_k.p;
             L.spill_vals = spill_v.as<uint32_t>();
-            L.spill_count = spill_n.as<uint32_t>();
+            L.spill_count = ctl_at(kCtlSpill);
             L.spill_cap = P.spill_cap;
             L.narrow_hb = P.narrow ? P.nw_hb : 0;
         }
@@ -3530,7 +3563,7 @@ struct MsdRunner {
                     BBK_HIP(hipMemcpyAsync(hist1.p, &n32, 4, hipMemcpyHostToDevice, ctx->stream));
                 }
                 BBK_HIP(hipMemcpyAsync(h1.data(), hist1.p, (size_t)nb1 * 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 off1[0] = 0;
                 for (uint32_t b = 0; b < nb1; ++b) off1[b + 1] = off1[b] + h1[b];
                 if (ranged) {
@@ -3546,7 +3579,11 @@ struct MsdRunner {
                 for (uint32_t s2 = 0; s2 <= nsub; ++s2)
                     off1[s2] = P.xs ? (s2 >> P.xs) * P.seg_cap + (s2 & ((1u << P.xs) - 1u)) * P.sub_cap : s2 * P.seg_cap;
             }
-            BBK_HIP(hipMemcpyAsync(cur1.p, off1.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
+            // (the pinned block: sized here for the cursors AND the level-2 layout, so that it is never replaced while the
+            // cursors' copy is in flight; both parts are written after a wait that followed the last copy out of them)
+            stage = (uint32_t *)plan_staging(ctx, (layout_words(nullptr) + pad4(nsub)) * 4);
+            memcpy(stage, off1.data(), (size_t)nsub * 4);
+            BBK_HIP(hipMemcpyAsync(cur1.p, stage, (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
 
             const uint64_t nA = P.slots ? (uint64_t)nb1 * P.seg_cap : N;  // records bufA holds (slot layout has gaps)
             bufA.alloc(nA * P.rec_ab);
@@ -3627,12 +3664,12 @@ struct MsdRunner {
                     DevBuf cnt(16);
                     BBK_HIP(hipMemsetAsync(cnt.p, 0, 16, ctx->stream));
                     hipLaunchKernelGGL(k_view_recanon, dim3(P.nsub), dim3(256), 0, ctx->stream, bufA.as<uint64_t>(),
-                                       seg_off.as<uint32_t>(), seg_size.as<uint32_t>(), (int)R.expand_k,
+                                       seg_off, seg_size, (int)R.expand_k,
                                        v.keys.as<uint64_t>(), n, cnt.as<uint32_t>());
                     check_launch("k_view_recanon");
                     uint32_t got = 0;
                     BBK_HIP(hipMemcpyAsync(&got, cnt.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-                    BBK_HIP(hipStreamSynchronize(ctx->stream));
+                    stream_wait(ctx);
                     BBK_REQUIRE(got == n, BBK_ERR_INTERNAL, "canonical keys rebuilt from level 1: %u of %llu", got,
                                 (unsigned long long)n);
                 }
@@ -3645,7 +3682,7 @@ struct MsdRunner {
             const uint32_t nsub = P.nsub, xs = P.xs;
             std::vector<uint32_t> c1(nsub);
             BBK_HIP(hipMemcpyAsync(c1.data(), cur1.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            stream_wait(ctx);
             uint64_t got = 0;
             const uint32_t cap1 = xs ? P.sub_cap : P.seg_cap;
             for (uint32_t b = 0; b < P.nb1; ++b) {
@@ -3666,7 +3703,7 @@ struct MsdRunner {
             if (got > P.Ntot) {  // cannot be: every instance reserves one place.  Say what was read before failing
                 std::vector<uint32_t> c2(nsub);
                 BBK_HIP(hipMemcpyAsync(c2.data(), cur1.p, (size_t)nsub * 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 uint32_t shown = 0, differ = 0;
                 for (uint32_t b = 0; b < nsub; ++b) differ += c1[b] != c2[b];
                 for (uint32_t b = 0; b < nsub && shown < 8; ++b)
@@ -3691,6 +3728,18 @@ struct MsdRunner {
                 return Outcome::KeySlotsGaveUp;
             }
             return std::nullopt;
+        }
+
+        static size_t pad4(size_t words) { return (words + 7) & ~(size_t)3; }  // 16-byte steps, 16 spare bytes at least
+        // words of the layout block; off_w (optional): where seg_tile, seg_off, seg_nb2, seg_bin, seg_size, xstart begin
+        size_t layout_words(uint32_t *off_w) const {
+            const size_t len[6] = {(size_t)P.nsub + 1, (size_t)P.nsub + 1, P.nb1, (size_t)P.nb1 + 1, P.nsub, P.nsub};
+            size_t at = 0;
+            for (int i = 0; i < 6; ++i) {
+                if (off_w) off_w[i] = (uint32_t)at;
+                at += pad4(len[i]);
+            }
+            return at;
         }
 
         // ---- level-2 layout: bins per segment, tile descriptors
@@ -3723,21 +3772,7 @@ struct MsdRunner {
                 fprintf(stderr, "[bbk] msd key slots: %s records from level 2 (widest bucket 2^%.1f keys)\n",
                         narrow_b ? "4-byte" : "8-byte", std::log2((double)std::max<uint64_t>(span_b, 1)));
 
-            seg_tile.alloc(((size_t)nsub + 1) * 4);
-            seg_off.alloc(((size_t)nsub + 1) * 4);
-            seg_nb2.alloc((size_t)nb1 * 4 + 16);
-            seg_bin.alloc(((size_t)nb1 + 1) * 4);
-            seg_size.alloc((size_t)nsub * 4 + 16);
-            BBK_HIP(hipMemcpyAsync(seg_tile.p, tstart.data(), ((size_t)nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(seg_off.p, off1.data(), ((size_t)nsub + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(seg_nb2.p, snb2.data(), (size_t)nb1 * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(seg_bin.p, sbin.data(), ((size_t)nb1 + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(seg_size.p, hsub.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
-            L2 = PartLevel{2, P.b1, nb1, R.dmode, w0bits, seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(),
-                           sel.lo, sel.span, sel.shl, sel.mul};
             ntiles2 = tstart[nsub];
-            M2 = TileMap{seg_tile.as<uint32_t>(), seg_off.as<uint32_t>(), seg_size.as<uint32_t>(), nsub, N, ntiles2, 1,
-                         nullptr, 0, 0};
             // narrow level 2: workgroups dealt to the XCDs by segment (k_tile_desc_narrow); BBK_XCD_TILES=0: A/B
             nwg2 = ntiles2;  // workgroups of the level-2 kernel
             if (R.knobs.once.xcd_tiles && ntiles2) {  // (exact mode too: its histogram pass keeps the plain order, see desc2h)
@@ -3749,24 +3784,41 @@ struct MsdRunner {
                     c += tstart[s2 + 1] - tstart[s2];
                 }
                 nwg2 = 8u * *std::max_element(per_xcd, per_xcd + 8);
-                xstart_d.alloc((size_t)nsub * 4);
-                BBK_HIP(hipMemcpyAsync(xstart_d.p, xstart.data(), (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
             }
+            // the six arrays into the pinned block behind the cursors' part, one copy, one device block
+            uint32_t off_w[6];
+            const size_t words = layout_words(off_w);
+            layout_d.alloc(words * 4);
+            uint32_t *h = stage + pad4(nsub), *d = layout_d.as<uint32_t>();
+            memcpy(h + off_w[0], tstart.data(), ((size_t)nsub + 1) * 4);
+            memcpy(h + off_w[1], off1.data(), ((size_t)nsub + 1) * 4);
+            memcpy(h + off_w[2], snb2.data(), (size_t)nb1 * 4);
+            memcpy(h + off_w[3], sbin.data(), ((size_t)nb1 + 1) * 4);
+            memcpy(h + off_w[4], hsub.data(), (size_t)nsub * 4);
+            if (!xstart.empty()) memcpy(h + off_w[5], xstart.data(), (size_t)nsub * 4);
+            BBK_HIP(hipMemcpyAsync(d, h, words * 4, hipMemcpyHostToDevice, ctx->stream));
+            seg_tile = d + off_w[0];
+            seg_off = d + off_w[1];
+            seg_nb2 = d + off_w[2];
+            seg_bin = d + off_w[3];
+            seg_size = d + off_w[4];
+            xstart_d = xstart.empty() ? nullptr : d + off_w[5];
+            L2 = PartLevel{2, P.b1, nb1, R.dmode, w0bits, seg_nb2, seg_bin, sel.lo, sel.span, sel.shl, sel.mul};
+            M2 = TileMap{seg_tile, seg_off, seg_size, nsub, N, ntiles2, 1, nullptr, 0, 0};
             desc2.alloc((size_t)nwg2 * sizeof(uint4) + 16);
             if (ntiles2) {
-                if (xstart_d.p) BBK_HIP(hipMemsetAsync(desc2.p, 0, (size_t)nwg2 * sizeof(uint4), ctx->stream));
+                if (xstart_d) BBK_HIP(hipMemsetAsync(desc2.p, 0, (size_t)nwg2 * sizeof(uint4), ctx->stream));
                 hipLaunchKernelGGL(P.narrow ? k_tile_desc_narrow : k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0,
-                                   ctx->stream, M2, seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), tile2, xs,
-                                   (const uint32_t *)xstart_d.p, desc2.as<uint4>());
+                                   ctx->stream, M2, seg_nb2, seg_bin, tile2, xs, (const uint32_t *)xstart_d,
+                                   desc2.as<uint4>());
                 check_launch("k_tile_desc");
             }
             M2.desc = desc2.as<uint4>();
             // exact mode: the histogram kernel walks 16 consecutive tiles per workgroup and wants them in plain order
-            if (!P.slots && xstart_d.p && !P.narrow) {
+            if (!P.slots && xstart_d && !P.narrow) {
                 desc2h.alloc((size_t)ntiles2 * sizeof(uint4) + 16);
-                hipLaunchKernelGGL(k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0, ctx->stream, M2,
-                                   seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), kPartTileK, xs, (const uint32_t *)nullptr,
-                                   desc2h.as<uint4>());
+                hipLaunchKernelGGL(k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0, ctx->stream, M2, seg_nb2, seg_bin,
+                                   kPartTileK, xs, (const uint32_t *)nullptr, desc2h.as<uint4>());
                 check_launch("k_tile_desc");
             }
         }
@@ -3792,15 +3844,18 @@ struct MsdRunner {
                 const uint64_t tot = exclusive_scan_u64(ctx, h64.as<uint64_t>(), h64.as<uint64_t>(), nbuckets);
                 BBK_REQUIRE(tot == N, BBK_ERR_INTERNAL, "level-2 histogram does not add up");
                 hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                                   h64.as<uint64_t>(), (uint64_t)nbuckets, tot, boff.as<uint32_t>());
+                                   h64.as<uint64_t>(), (uint64_t)nbuckets, tot, (const uint64_t *)nullptr,
+                                   boff.as<uint32_t>());
                 check_launch("k_scan_to_u32");
                 BBK_HIP(bbk::copy_async(hist2.p, boff.p, (size_t)nbuckets * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
             } else {
-                // cursor of bucket g starts at its slot
-                hipLaunchKernelGGL(k_iota_mul, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                                   hist2.as<uint32_t>(), nbuckets, P.stride2);
-                check_launch("k_iota_mul");
+                // cursor of bucket g starts at its slot; narrow path: the segment of every bucket, for the dedup kernel
+                if (P.narrow) bseg.alloc(((size_t)nbuckets + 1) * 2);
+                hipLaunchKernelGGL(k_bucket_init, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                   hist2.as<uint32_t>(), nbuckets, P.stride2, (const uint32_t *)seg_bin, P.nb1,
+                                   P.narrow ? bseg.as<uint16_t>() : (uint16_t *)nullptr);
+                check_launch("k_bucket_init");
                 use_slots(L2, P.cap2, P.stride2);
             }
             if (P.narrow) {
@@ -3823,14 +3878,12 @@ struct MsdRunner {
         // ---- buckets in LDS: the first pass; the direct output's result, give-up or in-place redo
         std::optional<Outcome> first_pass() {
             dcount.alloc((size_t)nbuckets * 4 + 16);
-            dbg.alloc(64);
-            BBK_HIP(hipMemsetAsync(dbg.p, 0, 64, ctx->stream));
             // (slot mode: the dedup kernels leave the distinct records at the head of every bucket slot, like the exact
             // mode in its dense buckets; the compaction makes the result.  BucketArgs::out_keys / out_total -- every
             // bucket reserving its place in the result with an atomicAdd on one counter -- is no longer used: the counter
             // served the 227 210 buckets of BASELINE configs[1] one after the other, 2.6 ms of 2.8.)
             A = BucketArgs{boff.as<uint32_t>(), dcount.as<uint32_t>(), nullptr, (int)R.k,
-                           verbose ? dbg.as<uint32_t>() : nullptr, P.slots ? P.cap2 : 0u, P.slots ? P.stride2 : 0u,
+                           verbose ? ctl_at(kCtlDbg) : nullptr, P.slots ? P.cap2 : 0u, P.slots ? P.stride2 : 0u,
                            hist2.as<uint32_t>(), nullptr, nullptr, nullptr, ~0ull, R.knobs.once.hash_max_probes, nullptr};
             // Sorted output of a key array that should hold no duplicates (both strands of a distinct canonical set, odd
             // k): the dense result has the offsets of the input, so the sorting kernels write it directly -- no
@@ -3839,22 +3892,18 @@ struct MsdRunner {
             direct = (!P.slots || P.kslots) && R.assume_distinct && (R.dmode == MSD_KEYS || R.dmode == MSD_REF) &&
                      !R.knobs.no_direct;
             if (P.kslots) {
-                // dense output offsets = exclusive scan of the slot fills; a total below N means a record missed its slot
-                DevBuf c64(((size_t)nbuckets + 1) * 8);
-                hipLaunchKernelGGL(k_slot_counts, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                                   hist2.as<uint32_t>(), nbuckets, P.stride2, P.cap2, c64.as<uint64_t>());
-                check_launch("k_slot_counts");
-                const uint64_t tot = exclusive_scan_u64(ctx, c64.as<uint64_t>(), c64.as<uint64_t>(), nbuckets);
-                if (tot != N) {
-                    if (verbose) fprintf(stderr, "[bbk] msd key slots: %llu of %llu records placed, exact mode\n",
-                                         (unsigned long long)tot, (unsigned long long)N);
-                    return give_up_key_slots();
-                }
+                // dense output offsets = exclusive scan of the slot fills (read from the cursors by the scan itself).  A
+                // total below N means a record missed its slot: the host learns it with the flags, after the buckets have
+                // run -- such a record also counts in ctr[0], and offsets from a total below N stay inside out.keys
+                c64.alloc(((size_t)nbuckets + 1) * 8);
+                const ScanSrc src{hist2.p, SCAN_SLOT_FILL, P.stride2, P.cap2};
+                uint64_t *const so = c64.as<uint64_t>();
+                exclusive_scan_enqueue(ctx, 1, &src, &so, nbuckets, ctl_total(), false, scan_keep);
                 slot_off.alloc(((size_t)nbuckets + 1) * 4 + 16);
                 hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                                   c64.as<uint64_t>(), (uint64_t)nbuckets, tot, slot_off.as<uint32_t>());
+                                   c64.as<uint64_t>(), (uint64_t)nbuckets, 0ull, (const uint64_t *)ctl_total(),
+                                   slot_off.as<uint32_t>());
                 check_launch("k_scan_to_u32");
-                BBK_HIP(hipStreamSynchronize(ctx->stream));  // c64 goes out of scope
                 A.out_off = slot_off.as<uint32_t>();
             }
             if (direct) {
@@ -3862,18 +3911,31 @@ struct MsdRunner {
                     out.keys.alloc(N * rec + 16);
                     if (out_vals) out.vals.alloc(N * 4 + 16);
                 }
-                dupf.alloc(16);
-                BBK_HIP(hipMemsetAsync(dupf.p, 0, 16, ctx->stream));
                 A.sorted_keys = has_dst ? dst.keys : out.keys.p;
                 A.sorted_vals = has_dst ? dst.vals : out.vals.as<uint32_t>();
-                A.dup_flag = dupf.as<uint32_t>();
+                A.dup_flag = ctl_at(kCtlDup);
                 A.strip_mask = R.strip_mask;
             }
             launch_buckets();
             // buckets the first pass left alone: listed on the device, only the (short) list comes to the host
             flag_ids.alloc((size_t)kFlagCap * 4);
-            if (!P.slots) flag_n.alloc(16);
+            // hash slots: the scan of the distinct counts (the dense offsets; D) rides on the same wait.  The buckets a
+            // flagged list excludes count 0 in it already, so it does not depend on the host's look at the flags
+            if (P.hslots && !direct) {
+                d64.alloc(((size_t)nbuckets + 1) * 8);
+                const ScanSrc src{dcount.p, SCAN_U32_FLAGGED, 0u, 0u};
+                uint64_t *const so = d64.as<uint64_t>();
+                exclusive_scan_enqueue(ctx, 1, &src, &so, nbuckets, ctl_total(), false, scan_keep);
+                d64_scanned = true;
+            }
             fetch_flags();
+            if (P.kslots && h_total() != N) {
+                if (verbose) fprintf(stderr, "[bbk] msd key slots: %llu of %llu records placed, exact mode\n",
+                                     (unsigned long long)h_total(), (unsigned long long)N);
+                out.keys.release();
+                out.vals.release();
+                return give_up_key_slots();
+            }
             if (!direct) return std::nullopt;
             if (ctr[2] == 0 && ctr[3] == 0 && (!P.kslots || ctr[0] == 0)) {  // every bucket sorted, nothing removed or
                 out.n = N;                                                    // spilled: the result is complete
@@ -3909,11 +3971,6 @@ struct MsdRunner {
         void launch_buckets() {
             if (P.narrow) {
                 if constexpr (W == 1) {
-                    h_bseg.resize((size_t)nbuckets + 1);
-                    for (uint32_t b = 0; b < P.nb1; ++b)
-                        for (uint32_t g = sbin[b]; g < sbin[b + 1]; ++g) h_bseg[g] = (uint16_t)b;
-                    bseg.alloc(((size_t)nbuckets + 1) * 2);
-                    BBK_HIP(hipMemcpyAsync(bseg.p, h_bseg.data(), (size_t)nbuckets * 2, hipMemcpyHostToDevice, ctx->stream));
                     if (nbuckets)
                         with_op(R.op, [&](auto o) {
                             constexpr int OP = decltype(o)::value;
@@ -3928,7 +3985,7 @@ struct MsdRunner {
                     bbase.alloc(((size_t)nbuckets + 1) * 8);
                     if (nbuckets) {
                         hipLaunchKernelGGL(k_bucket_base, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                                           seg_nb2.as<uint32_t>(), seg_bin.as<uint32_t>(), P.nb1, nbuckets, P.b1,
+                                           (const uint32_t *)seg_nb2, (const uint32_t *)seg_bin, P.nb1, nbuckets, P.b1,
                                            R.w0bits(), bbase.as<uint64_t>());
                         check_launch("k_bucket_base");
                         constexpr int NT = BktCfg<1>::NT, IT = BktCfg<1>::ITEMS;
@@ -3942,15 +3999,17 @@ struct MsdRunner {
         }
 
         void fetch_flags() {
-            uint32_t *d_flag_n = P.slots ? spill_n.as<uint32_t>() + 2 : flag_n.as<uint32_t>();
-            if (!P.slots) BBK_HIP(hipMemsetAsync(flag_n.p, 0, 16, ctx->stream));
+            uint32_t *d_flag_n = P.slots ? ctl_at(kCtlSpill) + 2 : ctl_at(kCtlFlagN);
+            if (!P.slots) BBK_HIP(hipMemsetAsync(d_flag_n, 0, 16, ctx->stream));  // (a withdrawn direct pass counts again)
             hipLaunchKernelGGL(k_flagged, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream, dcount.as<uint32_t>(),
                                nbuckets, flag_ids.as<uint32_t>(), kFlagCap, d_flag_n);
             check_launch("k_flagged");
-            if (P.slots) BBK_HIP(hipMemcpyAsync(ctr, spill_n.p, 12, hipMemcpyDeviceToHost, ctx->stream));
-            else BBK_HIP(hipMemcpyAsync(ctr + 2, flag_n.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            if (direct) BBK_HIP(hipMemcpyAsync(ctr + 3, dupf.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            // the whole control block in one copy: spill / flag / duplicate counters and the scan total that rode along
+            BBK_HIP(hipMemcpyAsync(h_ctl, ctl.p, kCtlWords * 4, hipMemcpyDeviceToHost, ctx->stream));
+            stream_wait(ctx);
+            if (P.slots) memcpy(ctr, h_ctl + kCtlSpill, 12);
+            else ctr[2] = h_ctl[kCtlFlagN];
+            if (direct) ctr[3] = h_ctl[kCtlDup];
         }
 
         // ---- what the first pass left: the slot mode's overflow, or the exact mode's oversized buckets
@@ -3963,7 +4022,7 @@ struct MsdRunner {
             flagged.resize(n_flag);
             if (n_flag) {
                 BBK_HIP(hipMemcpyAsync(flagged.data(), flag_ids.p, (size_t)n_flag * 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 std::sort(flagged.begin(), flagged.end());
             }
             const bool exact_check = !P.slots && (n_flag || verbose);
@@ -3972,7 +4031,7 @@ struct MsdRunner {
                 hb.resize((size_t)nbuckets + 1);
                 BBK_HIP(hipMemcpyAsync(hd.data(), dcount.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
                 BBK_HIP(hipMemcpyAsync(hb.data(), boff.p, ((size_t)nbuckets + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
             }
             if (P.slots)
                 if (auto r = slot_overflow()) return r;
@@ -4001,7 +4060,7 @@ struct MsdRunner {
             if (!over_bkt.empty()) {
                 std::vector<uint32_t> cur2(nbuckets);
                 BBK_HIP(hipMemcpyAsync(cur2.data(), hist2.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 for (size_t i = 0; i < over_bkt.size(); ++i) {
                     const uint32_t g = over_bkt[i];
                     bkt_fill[i] = std::min<uint32_t>(P.cap2, cur2[g] - g * P.stride2);
@@ -4054,7 +4113,7 @@ struct MsdRunner {
                     put(bufA.p, valA.as<uint32_t>(), (uint64_t)off1[s2], fill1[s2], P.narrow ? (int)b : -1);
             for (size_t i = 0; i < over_bkt.size(); ++i)
                 put(bufB.p, valB.as<uint32_t>(), (uint64_t)over_bkt[i] * P.stride2, bkt_fill[i],
-                    P.narrow ? (int)h_bseg[over_bkt[i]] : -1);
+                    P.narrow ? (int)(std::upper_bound(sbin.begin(), sbin.end(), over_bkt[i]) - sbin.begin()) - 1 : -1);
             if (tiny) {
                 // the usual case (one or two crowded buckets): ONE workgroup sorts + reduces all of it in LDS,
                 // instead of a whole partition pipeline for a few thousand records
@@ -4070,14 +4129,14 @@ struct MsdRunner {
                                                       /*allow_hash=*/false);
                 uint32_t d = 0;
                 BBK_HIP(hipMemcpyAsync(&d, tc.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 BBK_REQUIRE(d != 0xFFFFFFFFu && d <= n_extra, BBK_ERR_INTERNAL, "overflow pass: bad count");
                 extra.n = d;
                 extra.keys = std::move(ek);
                 if (out_vals) extra.vals = std::move(ev);
                 return std::nullopt;
             }
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            stream_wait(ctx);
             // The records were selected BY their hash bucket, so the same hash would pile them up again:
             // partition them by key instead (the order of the result does not matter), and never decline --
             // a k-mer with a million instances is finished by the per-bucket LSD fallback.
@@ -4114,7 +4173,7 @@ struct MsdRunner {
                 R.template bucket_dispatch<true>((uint32_t)big.size(), bufB.as<Key<W>>(), valB.as<uint32_t>(), A2,
                                                  rec_bytes(big_rec), /*allow_hash=*/false);
                 BBK_HIP(hipMemcpyAsync(hd.data(), dcount.p, (size_t)nbuckets * 4, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
             }
             for (uint32_t b = 0; b < nbuckets; ++b)
                 if (hd[b] == 0xFFFFFFFFu) {
@@ -4125,8 +4184,8 @@ struct MsdRunner {
                 uint32_t mx = 0;
                 for (uint32_t b = 0; b < nbuckets; ++b) mx = std::max(mx, hb[b + 1] - hb[b]);
                 uint32_t hdbg[2] = {0, 0};
-                BBK_HIP(hipMemcpyAsync(hdbg, dbg.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                BBK_HIP(hipMemcpyAsync(hdbg, ctl_at(kCtlDbg), 8, hipMemcpyDeviceToHost, ctx->stream));
+                stream_wait(ctx);
                 fprintf(stderr, "[bbk] msd all-words-fallback buckets=%u\n", hdbg[0]);
                 fprintf(stderr, "[bbk] msd mode=%d N=%llu nb1=%u buckets=%u max_bucket=%u cap=%u big=%zu lsd=%llu (%llu rec)\n",
                         R.dmode, (unsigned long long)N, P.nb1, nbuckets, mx, R.bucket_cap(), big.size(),
@@ -4153,7 +4212,7 @@ struct MsdRunner {
                                                   out_vals ? ov.as<uint32_t>() : nullptr, rop, false);
                 BBK_HIP(bbk::copy_async(kb, ok.p, d * rec, hipMemcpyDeviceToDevice, ctx->stream));
                 if (out_vals) BBK_HIP(bbk::copy_async(vb, ov.p, d * 4, hipMemcpyDeviceToDevice, ctx->stream));
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 hd[b] = (uint32_t)d;
             }
             BBK_HIP(hipMemcpyAsync(dcount.p, hd.data(), (size_t)nbuckets * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -4167,12 +4226,9 @@ struct MsdRunner {
             const char *why = nullptr;
             if (W != 1 || !P.narrow || out_vals || has_dst || ranged) why = "not a narrow pass";
             else if (R.knobs.once.no_bucket_handoff) why = "BBK_NO_BUCKET_HANDOFF";
-            size_t fr = 0, tot = 0;
             const size_t more = bufB.bytes > D * rec ? bufB.bytes - D * rec : 0;
-            if (!why) {
-                BBK_HIP(hipMemGetInfo(&fr, &tot));
-                if (more > fr) why = "device memory";
-            }
+            // (the driver is asked once per context and again only after the arena has mapped or trimmed)
+            if (!why && more > device_free_cached(ctx)) why = "device memory";
             if (verbose)
                 fprintf(stderr, "[bbk] msd hand-off to stage B: %s (%llu keys, buckets %.0f MB, dense %.0f MB)%s%s\n",
                         why ? "dense array" : "bucket view", (unsigned long long)out.n, bufB.bytes / 1e6, out.n * rec / 1e6,
@@ -4190,18 +4246,23 @@ struct MsdRunner {
             v.n_extra = extra.n;
             if (extra.n) v.extra = std::move(extra.keys);
             out.nbuckets = 0;
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            return true;
+            return true;  // no wait: everything the queued kernels use has moved into the view, which outlives the call
         }
 
         // ---- dense output: scan of the bucket counts + compaction.  (Slot mode: overflowing buckets wrote nothing and
         // count 0 here; their records are in `extra`, appended.)  Exact HASH mode also gets the bucket table.
         void compact() {
-            DevBuf d64(((size_t)nbuckets + 1) * 8);
-            hipLaunchKernelGGL(k_u32_to_u64, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                               dcount.as<uint32_t>(), (uint64_t)nbuckets, d64.as<uint64_t>(), 0u);
-            check_launch("k_u32_to_u64");
-            const uint64_t D = exclusive_scan_u64(ctx, d64.as<uint64_t>(), d64.as<uint64_t>(), nbuckets);
+            uint64_t D = 0;
+            if (d64_scanned) {  // scanned before fetch_flags' wait, the total came back with the flags
+                D = h_total();
+            } else {  // exact mode: the overflow passes have rewritten counts since the flags were read
+                d64.alloc(((size_t)nbuckets + 1) * 8);
+                const ScanSrc src{dcount.p, SCAN_U32_FLAGGED, 0u, 0u};
+                uint64_t *const so = d64.as<uint64_t>();
+                exclusive_scan_enqueue(ctx, 1, &src, &so, nbuckets, ctl_total(), false, scan_keep);
+                BBK_HIP(hipMemcpyAsync(&D, ctl_total(), 8, hipMemcpyDeviceToHost, ctx->stream));
+                stream_wait(ctx);
+            }
             if (P.slots) BBK_REQUIRE(D + extra.n <= N, BBK_ERR_INTERNAL, "more distinct records than records");
             out.n = D + (P.slots ? extra.n : 0);
             if (hand_off_view(D, d64)) return;
@@ -4236,10 +4297,11 @@ struct MsdRunner {
             if (!P.slots) {
                 out.bucket_off.alloc(((size_t)nbuckets + 1) * 4);
                 hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                                   d64.as<uint64_t>(), (uint64_t)nbuckets, D, out.bucket_off.as<uint32_t>());
+                                   d64.as<uint64_t>(), (uint64_t)nbuckets, D, (const uint64_t *)nullptr,
+                                   out.bucket_off.as<uint32_t>());
                 check_launch("k_scan_to_u32");
             }
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            stream_wait(ctx);
         }
     };
 
@@ -4277,7 +4339,7 @@ struct MsdRunner {
                                  (const Key<W> *)d_keys, nullptr, M, L, h.as<uint32_t>(), nullptr, nullptr, nullptr);
         std::vector<uint32_t> h32(nb);
         BBK_HIP(hipMemcpyAsync(h32.data(), h.p, (size_t)nb * 4, hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         std::vector<uint64_t> out(nb);
         uint64_t tot = 0;
         for (uint32_t i = 0; i < nb; ++i) tot += (out[i] = h32[i]);
@@ -4473,7 +4535,7 @@ struct MsdRunner {
                          buf0.as<Key<W>>(), val0.as<uint32_t>());
             std::vector<uint32_t> end(m);
             BBK_HIP(hipMemcpyAsync(end.data(), cur.p, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            stream_wait(ctx);
             for (size_t j = 0; j < m; ++j)
                 BBK_REQUIRE(end[j] == off[j + 1], BBK_ERR_INTERNAL, "level 0: range %zu received %u records, planned %u", c + j,
                             end[j] - off[j], off[j + 1] - off[j]);
@@ -4553,7 +4615,7 @@ struct MsdRunner {
                     ev.alloc(pt.n * 4 + 16);
                     BBK_HIP(bbk::copy_async(ev.p, pt.vals.p, pt.n * 4, hipMemcpyDeviceToDevice, ctx->stream));
                 }
-                BBK_HIP(hipStreamSynchronize(ctx->stream));
+                stream_wait(ctx);
                 pt.keys = std::move(ek);
                 if (out_vals) pt.vals = std::move(ev);
             }
@@ -4572,7 +4634,7 @@ struct MsdRunner {
                                            ctx->stream));
             }
             o += p.n;
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            stream_wait(ctx);
             p.keys.release();  // hand the part back before the next copy: peak = result + one part
             p.vals.release();
         }

@@ -426,7 +426,7 @@ void d2h_big(bbk_ctx *ctx, void *dst, const void *src, size_t bytes) {
     constexpr size_t kChunk = 32ull << 20;
     if (bytes < (4ull << 20)) {
         BBK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
         return;
     }
     if (!ctx->pinned[0]) {
@@ -559,93 +559,183 @@ __device__ inline uint32_t block_excl_scan(uint32_t v, uint32_t *smem_waves /*[k
 }
 
 // ------------------------------------------------------------------------------------------
-// exclusive scan of u64
+// exclusive scan of u64 (one array, or two arrays of the same length in the same launches)
 // ------------------------------------------------------------------------------------------
-constexpr int kScanItems = 8;
+// Reduce-then-apply over tiles of 4096 items: 16 M items take two levels (10 M reads: 2442 block sums, one block).
+// The top level is ONE workgroup that scans its (at most kScanTile) items in place and leaves the grand total in device
+// memory -- and behind the output array when the caller wants out[n] = total -- so no level needs a copy, a fill or
+// the host.
+constexpr int kScanItems = 16;
 constexpr int kScanTile = kThreads * kScanItems;
 
-__global__ __launch_bounds__(kThreads) void k_scan_reduce(const uint64_t *__restrict__ in, uint64_t n,
-                                                         uint64_t *__restrict__ bsum) {
-    __shared__ uint64_t sm[kWaves];
+struct ScanArrs {
+    ScanSrc src[2];
+    uint64_t *out[2];
+    uint64_t *bsum[2];   // block sums of this level (reduce: written; apply: read, already scanned)
+    uint64_t *total[2];  // top level: the grand total goes here ...
+    uint64_t *tail[2];   // ... and here when not null
+};
+
+__device__ inline uint64_t scan_load(const ScanSrc &s, uint64_t i) {
+    if (s.kind == SCAN_U64) return reinterpret_cast<const uint64_t *>(s.p)[i];
+    const uint32_t v = reinterpret_cast<const uint32_t *>(s.p)[i];
+    if (s.kind == SCAN_U32_FLAGGED) return v == 0xFFFFFFFFu ? 0ull : (uint64_t)v;
+    const uint32_t c = v - (uint32_t)i * s.stride;  // SCAN_SLOT_FILL
+    return c < s.cap ? c : s.cap;
+}
+
+template <int NA>
+__global__ __launch_bounds__(kThreads) void k_scan_reduce(ScanArrs A, uint64_t n) {
+    __shared__ uint64_t sm[NA][kWaves];
     const uint64_t base = (uint64_t)blockIdx.x * kScanTile;
-    uint64_t s = 0;
 #pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        uint64_t idx = base + (uint64_t)i * kThreads + threadIdx.x;
-        if (idx < n) s += in[idx];
+    for (int a = 0; a < NA; ++a) {
+        uint64_t s = 0;
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            const uint64_t idx = base + (uint64_t)i * kThreads + threadIdx.x;
+            if (idx < n) s += scan_load(A.src[a], idx);
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
+        if ((threadIdx.x & 63) == 0) sm[a][threadIdx.x >> 6] = s;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0) {
+    if (threadIdx.x < NA) {
         uint64_t t = 0;
-        for (int w = 0; w < kWaves; ++w) t += sm[w];
-        bsum[blockIdx.x] = t;
+        for (int w = 0; w < kWaves; ++w) t += sm[threadIdx.x][w];
+        A.bsum[threadIdx.x][blockIdx.x] = t;
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_scan_apply(const uint64_t *__restrict__ in, uint64_t *__restrict__ out,
-                                                        uint64_t n, const uint64_t *__restrict__ boff) {
-    __shared__ uint64_t sm[kWaves];
+// TOP: the only workgroup of the last level -- its offset is 0 and it publishes the total; otherwise the workgroup's
+// offset is its (scanned) block sum
+template <int NA, bool TOP>
+__global__ __launch_bounds__(kThreads) void k_scan_apply(ScanArrs A, uint64_t n) {
+    __shared__ uint64_t sm[NA][kWaves];
     const uint64_t base = (uint64_t)blockIdx.x * kScanTile + (uint64_t)threadIdx.x * kScanItems;
-    uint64_t v[kScanItems];
-    uint64_t s = 0;
-#pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        v[i] = (base + i < n) ? in[base + i] : 0;
-        s += v[i];
-    }
-    // block exclusive scan of s
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint64_t incl = s;
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        uint64_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) sm[wave] = incl;
-    __syncthreads();
-    uint64_t wbase = 0;
-    for (int w = 0; w < wave; ++w) wbase += sm[w];
-    uint64_t run = boff[blockIdx.x] + wbase + incl - s;
+    for (int a = 0; a < NA; ++a) {
+        uint64_t v[kScanItems];
+        uint64_t s = 0;
 #pragma unroll
-    for (int i = 0; i < kScanItems; ++i) {
-        if (base + i < n) out[base + i] = run;
-        run += v[i];
+        for (int i = 0; i < kScanItems; ++i) {
+            v[i] = (base + i < n) ? scan_load(A.src[a], base + i) : 0;
+            s += v[i];
+        }
+        uint64_t incl = s;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            uint64_t t = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += t;
+        }
+        if (lane == 63) sm[a][wave] = incl;
+        __syncthreads();
+        uint64_t wbase = 0;
+        for (int w = 0; w < wave; ++w) wbase += sm[a][w];
+        uint64_t run = (TOP ? 0ull : A.bsum[a][blockIdx.x]) + wbase + incl - s;
+#pragma unroll
+        for (int i = 0; i < kScanItems; ++i) {
+            if (base + i < n) A.out[a][base + i] = run;
+            run += v[i];
+        }
+        if (TOP && threadIdx.x == kThreads - 1) {  // run = the sum of everything
+            *A.total[a] = run;
+            if (A.tail[a]) *A.tail[a] = run;
+        }
     }
 }
 
 // One level of the scan: block sums, (recursively) their exclusive scan in place, then the blocks.  Nothing waits on the
-// host in between: the block-sum buffers of every level live in `keep` until the caller has synchronised once, and the
-// grand total is parked in *d_total on the way down.
-static void scan_level(bbk_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n, std::vector<DevBuf> &keep,
-                       uint64_t *d_total) {
+// host in between: the block-sum buffers of every level live in `keep` until the caller has synchronised.
+template <int NA>
+static void scan_level(bbk_ctx *ctx, ScanArrs A, uint64_t n, std::vector<DevBuf> &keep) {
     const uint64_t nb = (n + kScanTile - 1) / kScanTile;
-    keep.emplace_back((nb + 1) * sizeof(uint64_t));
-    uint64_t *bsum = keep.back().as<uint64_t>();
-    hipLaunchKernelGGL(k_scan_reduce, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, in, n, bsum);
-    check_launch("k_scan_reduce");
-    if (nb == 1) {
-        BBK_HIP(hipMemcpyAsync(d_total, bsum, sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-        BBK_HIP(hipMemsetAsync(bsum, 0, sizeof(uint64_t), ctx->stream));
-    } else {
-        scan_level(ctx, bsum, bsum, nb, keep, d_total);
+    if (nb <= 1) {  // (no items: the totals are 0)
+        hipLaunchKernelGGL((k_scan_apply<NA, true>), dim3(1), dim3(kThreads), 0, ctx->stream, A, n);
+        check_launch("k_scan_apply");
+        return;
     }
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, in, out, n, bsum);
+    BBK_REQUIRE(nb < (1ull << 31), BBK_ERR_ARG, "scan of %llu items", (unsigned long long)n);
+    keep.emplace_back((size_t)NA * (nb + 1) * sizeof(uint64_t));
+    uint64_t *bs = keep.back().as<uint64_t>();
+    ScanArrs B = A;  // the level above: the block sums, in place
+    for (int a = 0; a < NA; ++a) {
+        A.bsum[a] = bs + (size_t)a * (nb + 1);
+        B.src[a] = ScanSrc{A.bsum[a], SCAN_U64, 0u, 0u};
+        B.out[a] = A.bsum[a];  // (total and tail travel up unchanged: the top level writes them)
+    }
+    hipLaunchKernelGGL((k_scan_reduce<NA>), dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, A, n);
+    check_launch("k_scan_reduce");
+    scan_level<NA>(ctx, B, nb, keep);
+    hipLaunchKernelGGL((k_scan_apply<NA, false>), dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, A, n);
     check_launch("k_scan_apply");
+}
+
+void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t *const *out, uint64_t n,
+                            uint64_t *d_total, bool tail, std::vector<DevBuf> &keep) {
+    BBK_REQUIRE(narr == 1 || narr == 2, BBK_ERR_INTERNAL, "scan of %d arrays", narr);
+    ScanArrs A{};
+    for (int a = 0; a < narr; ++a) {
+        A.src[a] = src[a];
+        A.out[a] = out[a];
+        A.total[a] = d_total + a;
+        A.tail[a] = tail ? out[a] + n : nullptr;
+    }
+    if (narr == 1) scan_level<1>(ctx, A, n, keep);
+    else scan_level<2>(ctx, A, n, keep);
 }
 
 uint64_t exclusive_scan_u64(bbk_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n) {
     if (n == 0) return 0;
     std::vector<DevBuf> keep;
-    keep.reserve(8);  // levels: log_{tile}(n)
+    keep.reserve(4);  // levels: log_{tile}(n)
     DevBuf dt(16);
-    scan_level(ctx, in, out, n, keep, dt.as<uint64_t>());
+    const ScanSrc src{in, SCAN_U64, 0u, 0u};
+    exclusive_scan_enqueue(ctx, 1, &src, &out, n, dt.as<uint64_t>(), false, keep);
     uint64_t total = 0;
     BBK_HIP(hipMemcpyAsync(&total, dt.p, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));  // one wait per scan (it was one per level): the buffers go back now
+    stream_wait(ctx);  // one wait per scan: the buffers go back now
     return total;
+}
+
+void exclusive_scan2_u64(bbk_ctx *ctx, const uint64_t *in0, uint64_t *out0, const uint64_t *in1, uint64_t *out1,
+                         uint64_t n, uint64_t totals[2]) {
+    std::vector<DevBuf> keep;
+    keep.reserve(4);
+    DevBuf dt(16);
+    const ScanSrc src[2] = {{in0, SCAN_U64, 0u, 0u}, {in1, SCAN_U64, 0u, 0u}};
+    uint64_t *const out[2] = {out0, out1};
+    exclusive_scan_enqueue(ctx, 2, src, out, n, dt.as<uint64_t>(), true, keep);
+    BBK_HIP(hipMemcpyAsync(totals, dt.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    stream_wait(ctx);
+}
+
+size_t device_free_cached(bbk_ctx *ctx) {
+    uint64_t now = 0, total = 0;
+    pool_stats(ctx->device, &now, &total, nullptr);
+    if (now != ctx->mem_free_mapped_now || total != ctx->mem_free_mapped_total) {
+        size_t fr = 0, tot = 0;
+        BBK_HIP(hipMemGetInfo(&fr, &tot));
+        ctx->mem_free = fr;
+        ctx->mem_free_mapped_now = now;
+        ctx->mem_free_mapped_total = total;
+    }
+    return ctx->mem_free;
+}
+
+void *plan_staging(bbk_ctx *ctx, size_t bytes) {
+    if (bytes > ctx->plan_pinned_bytes) {
+        // (the block is replaced only here, by the caller's rule after a wait: no copy is reading the old one)
+        if (ctx->plan_pinned) BBK_HIP(hipHostFree(ctx->plan_pinned));
+        ctx->plan_pinned = nullptr;
+        ctx->plan_pinned_bytes = 0;
+        const size_t want = std::max<size_t>(2 * bytes, 256u << 10);
+        BBK_HIP(hipHostMalloc(&ctx->plan_pinned, want, hipHostMallocDefault));
+        ctx->plan_pinned_bytes = want;
+    }
+    return ctx->plan_pinned;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -923,7 +1013,7 @@ static void sort_impl(bbk_ctx *ctx, Key<W> *keys, Key<W> *tmp, uint32_t *vals, u
         BBK_HIP(bbk::copy_async(keys, src, n * sizeof(Key<W>), hipMemcpyDeviceToDevice, ctx->stream));
         if (vals) BBK_HIP(bbk::copy_async(vals, vsrc, n * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
     }
-    BBK_HIP(hipStreamSynchronize(ctx->stream));  // hist/chunk are freed on return
+    stream_wait(ctx);  // hist/chunk are freed on return
 }
 
 template <int W>
@@ -937,7 +1027,7 @@ static void partition_impl(bbk_ctx *ctx, const Key<W> *src, Key<W> *dst, const u
     sort_pass<W>(ctx, src, dst, vsrc, vdst, n, pd, hist, chunk, h_digit_totals ? tot.as<uint64_t>() : nullptr);
     if (h_digit_totals)
         BBK_HIP(hipMemcpyAsync(h_digit_totals, tot.p, kRadix * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
 }
 
 // one stable pass src -> dst (both on the device, not aliased): records ordered by the digit, input order kept inside
@@ -1147,9 +1237,9 @@ static uint64_t unique_impl(bbk_ctx *ctx, const Key<W> *keys, const uint32_t *va
         hipLaunchKernelGGL(k_nonzero_compact<W>, dim3((unsigned)nb2), dim3(kThreads), 0, ctx->stream, dk, dv, nd,
                            bc2.as<uint64_t>(), out_keys, out_vals);
         check_launch("k_nonzero_compact");
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        stream_wait(ctx);
     }
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
     return result;
 }
 
@@ -1169,7 +1259,7 @@ static uint64_t drop_zero_impl(bbk_ctx *ctx, const Key<W> *keys, const uint32_t 
     hipLaunchKernelGGL(k_nonzero_compact<W>, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, keys, vals, n,
                        bc.as<uint64_t>(), ok.as<Key<W>>(), ov.as<uint32_t>());
     check_launch("k_nonzero_compact");
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    stream_wait(ctx);
     return kept;
 }
 
@@ -1276,6 +1366,7 @@ int bbk_ctx_destroy(bbk_ctx *ctx) {
     if (getenv("BBK_VERBOSE")) bbk::pool_report();
     if (ctx->pinned[0]) (void)hipHostFree(ctx->pinned[0]);
     if (ctx->pinned[1]) (void)hipHostFree(ctx->pinned[1]);
+    if (ctx->plan_pinned) (void)hipHostFree(ctx->plan_pinned);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return BBK_OK;
@@ -1359,5 +1450,14 @@ int bbk_ctx_profile_get(bbk_ctx *ctx, const char *family, double *ms_total, uint
 }
 
 unsigned bbk_words(unsigned k) { return bbk::words_of(k); }
+
+int bbk_scan2_u64(bbk_ctx *ctx, void *d_a, void *d_b, uint64_t n, uint64_t *totals) {
+    return bbk::guarded([&] {
+        BBK_REQUIRE(ctx && d_a && d_b && totals, BBK_ERR_ARG, "bbk_scan2_u64: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        bbk::exclusive_scan2_u64(ctx, (const uint64_t *)d_a, (uint64_t *)d_a, (const uint64_t *)d_b, (uint64_t *)d_b, n,
+                                 totals);
+    });
+}
 
 }  // extern "C"
