@@ -3010,6 +3010,353 @@ __global__ void k_view_recanon(const uint64_t *__restrict__ in, const uint32_t *
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// stage B with the tag taken late (tagged sort of the both-strand set, fed from a BucketView, k <= 21)
+// ------------------------------------------------------------------------------------------
+// The tagged key is (tag: XXH3 bucket of 16) << 2k | k-mer, and the tag is a function of the k-mer.  Level 1 above
+// bins by the top bits of the TAGGED key, so its records keep 37 of the 46 bits: 8 bytes each.  Here level 1 bins by the
+// top ten bits of the k-mer alone (1024 segments, kMaxBins) and stores the remaining lobits = 2k - 10 <= 32 bits: 4-byte
+// records, as in narrow stage A.  Level 2 knows the whole k-mer (segment, lo), takes the tag there and sends the record
+// to bin tag * nsub + sub of its segment (sub: the next bits of lo, monotone, as bin_of).  Buckets then lie in memory
+// as (segment, tag, sub) while the result is ordered (tag, segment, sub): the dense offsets come from a scan of the
+// bucket fills gathered in that order (k_bucket_base_lt's perm).  A bucket holds lo in [q_j, q_(j+1)) of one segment
+// and one tag, q_j = ceil(j * 2^lobits / nsub): fewer than 2^32 keys by construction, so level 2 stores the k-mer's low
+// word and k_bucket_dist_nb sorts and widens it against base = tag << 2k | segment << lobits | q_j, unchanged.
+// Both kernels share one tail, the one of k_part_reads_narrow: the staged order is bin-major, a bit per position
+// marks where a non-empty bin starts, and what a store needs of its bin is one 8-byte LDS entry -- the bin of a
+// staged record (ten dropped bits at level 1, a hash at level 2) is never computed twice.
+constexpr int kLtThreads = 1024;  // == kMaxBins: one bin per thread in the scans
+// records per lane.  Level 1: 14 336 records = 56 KB staged, 73 KB of LDS with the tables: two workgroups per CU (16
+// records per lane would be 81.1 KB, one workgroup); a (tile, bin) run is 14 records = 56 bytes.  Level 2: as
+// k_part_narrow2.
+constexpr int kLt1Items = 14;
+constexpr int kLt2Items = 12;
+
+struct LtLds {
+    uint32_t *lhist;           // counts; later, with the 4 KB behind it:
+    uint2 *tab;                // r -> (global offset - staged start, first staged position past the slot)
+    uint32_t *lstart, *scan_tmp;
+    unsigned long long *mark;  // bit per staged position: a non-empty bin starts here
+    uint16_t *mbase, *nz;      // marks before every 64-position word; the r-th non-empty bin
+    uint32_t *stage;
+};
+template <int ITEMS>
+__device__ __forceinline__ LtLds lt_lds(unsigned char *smem) {
+    constexpr int MW = kLtThreads * ITEMS / 64;
+    LtLds S;
+    S.lhist = reinterpret_cast<uint32_t *>(smem);
+    S.tab = reinterpret_cast<uint2 *>(smem);
+    S.lstart = S.lhist + 2 * kMaxBins;
+    S.scan_tmp = S.lstart + kMaxBins;
+    S.mark = reinterpret_cast<unsigned long long *>(S.scan_tmp + 64);
+    S.mbase = reinterpret_cast<uint16_t *>(S.mark + MW);
+    S.nz = S.mbase + MW;
+    S.stage = reinterpret_cast<uint32_t *>(S.nz + kMaxBins);
+    return S;
+}
+static size_t lt_smem(int items, size_t more) {
+    const size_t tile = (size_t)kLtThreads * items;
+    return sizeof(uint32_t) * (3 * kMaxBins + 64) + (tile / 64) * (8 + 2) + (size_t)kMaxBins * 2 + tile * 4 + more;
+}
+
+// the tagged key of (segment, lo): what the spill list and the give-up path need
+__device__ inline uint64_t lt_tagged(uint32_t seg, uint32_t lo, int lobits, int k) {
+    Key<1> x;
+    x.w[0] = ((uint64_t)seg << lobits) | lo;
+    return x.w[0] | (__umul64hi(xxh3_64<1>(x), 16ull) << (2 * k));
+}
+
+// On entry lhist[b] = records of bin b in this tile (counted, not ranked), lo[i] / bin of item i (two bins per register,
+// 0xFFFF: no record).  cur / slot_end: cursor and end of the slot of bin `tid`.  The stored record is lo | rec_or.
+template <int ITEMS, class KeyOf>
+__device__ __forceinline__ void lt_tail(const LtLds &S, const uint32_t (&lo)[ITEMS], const uint32_t (&bins)[ITEMS / 2],
+                                        uint32_t nb, uint32_t *__restrict__ cur, uint64_t slot_end, uint32_t rec_or,
+                                        const PartLevel &L, uint32_t *__restrict__ out, KeyOf key_of) {
+    constexpr int NT = kLtThreads, MW = NT * ITEMS / 64;
+    static_assert(ITEMS % 2 == 0 && ITEMS <= 32 && NT * ITEMS < 65536, "packed bins, one bit per item, 16-bit positions");
+    const uint32_t tid = threadIdx.x;
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint32_t c = tid < nb ? S.lhist[tid] : 0u;
+    uint32_t incl = c;
+    incl = wave_scan_incl(incl);
+    const unsigned long long nzb = __ballot(c != 0);
+    if (lane == 63) S.scan_tmp[wave] = incl | ((uint32_t)__popcll(nzb) << 16);
+    __syncthreads();
+    uint32_t before, total;
+    wave_totals<NT / 64>(S.scan_tmp, lane, wave, before, total);
+    const uint32_t staged = total & 0xFFFFu;
+    const uint32_t ex = (before & 0xFFFFu) + incl - c;
+    const uint32_t myr = (before >> 16) + (uint32_t)__popcll(nzb & ((1ull << lane) - 1ull));
+    S.lstart[tid] = ex;
+    uint32_t greserve = 0;
+    if (c) {
+        greserve = atomicAdd(cur, c);  // issued now, consumed after the LDS reorder
+        S.nz[myr] = (uint16_t)tid;
+        atomicOr(&S.mark[ex >> 6], 1ull << (ex & 63u));
+    }
+    __syncthreads();  // (every thread has read its count: lhist may become the table)
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t bin = (bins[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+        if (bin != 0xFFFFu) {
+            const uint32_t pos = atomicAdd(&S.lstart[bin], 1u);  // (lstart ends as the bins' end offsets; nothing reads it again)
+            S.stage[pos] = lo[i];
+        }
+    }
+    asm volatile("" : "+v"(greserve));  // awaited by every lane here, not inside the store loop's conditional blocks
+    if (c) {
+        const int64_t room = (int64_t)slot_end - (int64_t)greserve;
+        S.tab[myr] = make_uint2(greserve - ex, (uint32_t)(int32_t)(room < -(int64_t)0x7FFF0000 ? -(int64_t)0x7FFF0000 : room) + ex);
+    }
+    if (wave == 0) {  // marks before every 64-position word: lane l owns words WPL*l .. WPL*l + WPL-1
+        constexpr int WPL = (MW + 63) / 64;
+        uint32_t pw[WPL], tot = 0;
+#pragma unroll
+        for (int j = 0; j < WPL; ++j) {
+            const int idx = lane * WPL + j;
+            pw[j] = tot;
+            tot += idx < MW ? (uint32_t)__popcll(S.mark[idx]) : 0u;
+        }
+        uint32_t inc2 = tot;
+        inc2 = wave_scan_incl(inc2);
+        const uint32_t lb = inc2 - tot;
+#pragma unroll
+        for (int j = 0; j < WPL; ++j) {
+            const int idx = lane * WPL + j;
+            if (idx < MW) S.mbase[idx] = (uint16_t)(lb + pw[j]);
+        }
+    }
+    __syncthreads();
+    const unsigned long long upto = (2ull << lane) - 1ull;  // this lane and the ones below
+    // pos = i * NT + tid: the 64 lanes of a wave cover mark word i * (NT / 64) + wave
+    const unsigned long long *wmark = S.mark + wave;
+    const uint16_t *wmbase = S.mbase + wave;
+    uint32_t full = 0;  // items whose slot is full (rare; handled after the stores so that no atomic sits between them)
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        const uint32_t pos = (uint32_t)i * NT + tid;
+        if (pos < staged) {
+            const uint32_t r = (uint32_t)wmbase[i * (NT / 64)] + (uint32_t)__popcll(wmark[i * (NT / 64)] & upto) - 1u;
+            unsigned long long e = reinterpret_cast<const unsigned long long *>(S.tab)[r];
+            const uint32_t rec = S.stage[pos];
+            asm volatile("" : "+v"(e));  // one 8-byte LDS read (otherwise: the limit, a branch, then the offset)
+            if ((int32_t)pos >= (int32_t)(uint32_t)(e >> 32)) full |= 1u << i;
+            else out[(uint32_t)e + pos] = rec | rec_or;
+        }
+    }
+    if (full) {
+#pragma unroll 1
+        for (int i = 0; i < ITEMS; ++i) {
+            if ((full >> i) & 1u) {
+                const uint32_t pos = (uint32_t)i * NT + tid;
+                const uint32_t r = (uint32_t)wmbase[i * (NT / 64)] + (uint32_t)__popcll(wmark[i * (NT / 64)] & upto) - 1u;
+                const uint32_t sp = atomicAdd(L.spill_count, 1u);
+                if (sp < L.spill_cap) reinterpret_cast<uint64_t *>(L.spill_keys)[sp] = key_of((uint32_t)S.nz[r], S.stage[pos]);
+            }
+        }
+    }
+}
+
+// Level 1.  Tile t covers the canonical keys [t * KPT, (t + 1) * KPT) of the view's dense order (DENSE: of a key array,
+// the view's overflow records); a lane loads a key once and emits it and its reverse complement.  No tag here.
+template <bool DENSE>
+__global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_part_view_lt(
+    const uint32_t *__restrict__ slots, const uint64_t *__restrict__ off, const uint16_t *__restrict__ seg,
+    const uint2 *__restrict__ vdesc, uint32_t stride, int hb, const uint64_t *__restrict__ dense, uint64_t nkeys_all, int k,
+    PartLevel L, uint32_t *__restrict__ cursor, uint32_t *__restrict__ out) {
+    constexpr int NT = kLtThreads, ITEMS = kLt1Items, KPT = NT * ITEMS / 2, MW = NT * ITEMS / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const LtLds S = lt_lds<ITEMS>(smem);
+    uint32_t *toff = S.stage + NT * ITEMS;
+    uint16_t *tseg = reinterpret_cast<uint16_t *>(toff + kViewSpan);
+    const uint32_t tid = threadIdx.x;
+    uint32_t xcc = 0;  // the XCD this workgroup runs on (placement is for speed only: any value gives a correct result)
+    if (L.xcd_shift) {
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        xcc &= (1u << L.xcd_shift) - 1u;
+    }
+    const int lobits = 2 * k - 10;
+    const uint32_t lomask = lobits >= 32 ? 0xFFFFFFFFu : (1u << lobits) - 1u;
+    const uint64_t c0 = (uint64_t)blockIdx.x * KPT;
+    const uint64_t left = nkeys_all - c0;
+    const uint32_t nkeys = left < (uint64_t)KPT ? (uint32_t)left : (uint32_t)KPT;
+    uint32_t b0 = 0, span = 0;
+    bool staged_tab = false;
+    if (!DENSE) {
+        const uint2 d = vdesc[blockIdx.x];
+        b0 = d.x;
+        span = d.y - d.x + 1u;
+        staged_tab = span <= (uint32_t)kViewSpan;  // uniform
+        if (staged_tab && tid < span) {
+            toff[tid] = (uint32_t)off[b0 + tid];  // key offsets < 2^32: one pass holds fewer records
+            tseg[tid] = seg[b0 + tid];
+        }
+    }
+    S.lhist[tid] = 0;  // NT == kMaxBins
+    if (tid < 2 * MW) reinterpret_cast<uint32_t *>(S.mark)[tid] = 0u;
+    __syncthreads();
+
+    // all loads first (index clamped into the tile)
+    uint64_t x[ITEMS / 2];
+    if (DENSE) {
+#pragma unroll
+        for (int j = 0; j < ITEMS / 2; ++j) {
+            const uint32_t cl = (uint32_t)(j * NT) + tid;
+            x[j] = dense[c0 + (cl < nkeys ? cl : nkeys - 1u)];
+        }
+    } else {
+        uint32_t w[ITEMS / 2], sg[ITEMS / 2];
+#pragma unroll
+        for (int j = 0; j < ITEMS / 2; ++j) {
+            const uint32_t cl = (uint32_t)(j * NT) + tid;
+            const uint32_t c = (uint32_t)c0 + (cl < nkeys ? cl : nkeys - 1u);
+            uint32_t b, base;
+            if (staged_tab) {
+                uint32_t i = 0, hi = span;
+                while (hi - i > 1) {
+                    const uint32_t mid = (i + hi) >> 1;
+                    if (toff[mid] <= c) i = mid;
+                    else hi = mid;
+                }
+                b = b0 + i;
+                base = toff[i];
+                sg[j] = tseg[i];
+            } else {
+                b = view_bucket(off, b0, b0 + span, c);
+                base = (uint32_t)off[b];
+                sg[j] = seg[b];
+            }
+            w[j] = slots[(size_t)b * stride + (c - base)];
+        }
+#pragma unroll
+        for (int j = 0; j < ITEMS / 2; ++j) x[j] = nw_key(sg[j], w[j], hb);
+    }
+    uint32_t lo[ITEMS], bins[ITEMS / 2];
+#pragma unroll
+    for (int j = 0; j < ITEMS / 2; ++j) {
+        Key<1> a;
+        a.w[0] = x[j];
+        const uint64_t r = kmer_rc<1>(a, k).w[0];
+        const uint32_t ba = (uint32_t)(x[j] >> lobits), br = (uint32_t)(r >> lobits);  // k-mers < 4^k: bins < 1024
+        lo[2 * j] = (uint32_t)x[j] & lomask;
+        lo[2 * j + 1] = (uint32_t)r & lomask;
+        bins[j] = 0xFFFFFFFFu;
+        if ((uint32_t)(j * NT) + tid < nkeys) {
+            bins[j] = ba | (br << 16);
+            atomicAdd(&S.lhist[ba], 1u);  // count only: the place inside the bin is taken after the scan
+            atomicAdd(&S.lhist[br], 1u);
+        }
+    }
+    __syncthreads();
+    const uint64_t slot_end = (uint64_t)tid * L.slot_stride + (L.xcd_shift ? (uint64_t)(xcc + 1u) * L.sub_cap : (uint64_t)L.slot_cap);
+    lt_tail<ITEMS>(S, lo, bins, (uint32_t)kMaxBins, &cursor[(tid << L.xcd_shift) + xcc], slot_end, 0u, L, out,
+                   [&](uint32_t bin, uint32_t rec) { return lt_tagged(bin, rec, lobits, k); });
+}
+
+// Level 2: one tile of one segment's sub-slot (k_tile_desc_narrow's descriptors) -> the buckets of that segment.  The
+// tag is taken here, once per record.
+__global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_part_lt2(
+    const uint32_t *__restrict__ in, const uint4 *__restrict__ desc, int k, PartLevel L, uint32_t *__restrict__ cursor,
+    uint32_t *__restrict__ out) {
+    constexpr int NT = kLtThreads, ITEMS = kLt2Items, MW = NT * ITEMS / 64;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const LtLds S = lt_lds<ITEMS>(smem);
+    const uint32_t tid = threadIdx.x;
+    const uint4 d = desc[blockIdx.x];  // first record, records, bins of the segment | segment << 16, flat index of bin 0
+    const uint32_t begin = d.x, count = d.y, nb = d.z & 0xFFFFu, sgm = d.z >> 16, gbin0 = d.w;
+    if (count == 0) return;  // an unused place of the XCD-wise order (k_tile_desc_narrow)
+    const int lobits = 2 * k - 10;
+    const uint32_t nsub = nb >> 4;
+    const uint64_t segbits = (uint64_t)sgm << lobits;
+    S.lhist[tid] = 0;  // NT == kMaxBins
+    if (tid < 2 * MW) reinterpret_cast<uint32_t *>(S.mark)[tid] = 0u;
+    __syncthreads();
+    uint32_t lo[ITEMS], bins[ITEMS / 2];
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {  // all loads first (index clamped into the tile)
+        const uint32_t local = (uint32_t)i * NT + tid;
+        lo[i] = in[begin + (local < count ? local : count - 1u)];
+    }
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) asm volatile("" : "+v"(lo[i]));
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        Key<1> x;
+        x.w[0] = segbits | lo[i];
+        const uint32_t tag = (uint32_t)__umul64hi(xxh3_64<1>(x), 16ull);
+        const uint32_t b = tag * nsub + __umulhi(lo[i] << (32 - lobits), nsub);
+        const bool valid = (uint32_t)i * NT + tid < count;
+        if (valid) atomicAdd(&S.lhist[b], 1u);
+        const uint32_t b16 = valid ? b : 0xFFFFu;
+        if (i & 1) bins[i >> 1] |= b16 << 16;
+        else bins[i >> 1] = b16;
+    }
+    __syncthreads();
+    const uint64_t slot_end = (uint64_t)(gbin0 + tid) * L.slot_stride + L.slot_cap;
+    lt_tail<ITEMS>(S, lo, bins, nb, &cursor[gbin0 + tid], slot_end, (uint32_t)segbits, L, out,
+                   [&](uint32_t, uint32_t rec) { return lt_tagged(sgm, rec, lobits, k); });
+}
+
+// one thread per bucket g = bin tag * nsub + j of segment s: its smallest tagged key, and its place in the order of the
+// result, (tag, segment, sub) -- the segments' bin counts are multiples of 16, so a tag owns nbuckets / 16 places
+__global__ void k_bucket_base_lt(const uint32_t *__restrict__ seg_nb2, const uint32_t *__restrict__ seg_bin, uint32_t nseg,
+                                 uint32_t nbuckets, int lobits, int k, uint64_t *__restrict__ base,
+                                 uint32_t *__restrict__ perm) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nbuckets) return;
+    uint32_t lo = 0, hi = nseg;  // largest s with seg_bin[s] <= g (every segment has at least one bin)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (seg_bin[mid] <= g) lo = mid;
+        else hi = mid;
+    }
+    const uint32_t nsub = seg_nb2[lo] >> 4, r = g - seg_bin[lo], tag = r / nsub, j = r - tag * nsub;
+    const uint64_t q = (((uint64_t)j << lobits) + nsub - 1u) / nsub;
+    base[g] = ((uint64_t)tag << (2 * k)) | ((uint64_t)lo << lobits) | q;
+    perm[g] = tag * (nbuckets >> 4) + (seg_bin[lo] >> 4) + j;
+}
+
+// the slot fills (as SCAN_SLOT_FILL reads them from the cursors) in the order of the result
+__global__ void k_lt_fill_perm(const uint32_t *__restrict__ cursor, const uint32_t *__restrict__ perm, uint32_t n,
+                               uint32_t stride, uint32_t cap, uint32_t *__restrict__ fill) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n) return;
+    const uint32_t c = cursor[g] - g * stride;
+    fill[perm[g]] = c < cap ? c : cap;
+}
+
+// ... and their exclusive scan back at the buckets
+__global__ void k_lt_unperm(const uint64_t *__restrict__ scanned, const uint32_t *__restrict__ perm, uint32_t n,
+                            uint32_t *__restrict__ out_off) {
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g < n) out_off[g] = (uint32_t)scanned[perm[g]];
+}
+
+// k_view_recanon over the 4-byte level-1 records: the segment comes from the sub-slot, lo from the record
+__global__ void k_view_recanon_lt(const uint32_t *__restrict__ in, const uint32_t *__restrict__ seg_off,
+                                  const uint32_t *__restrict__ seg_size, int sub_shift, int k, uint64_t *__restrict__ out,
+                                  uint64_t cap, uint32_t *__restrict__ count) {
+    const uint32_t o = seg_off[blockIdx.x], n = seg_size[blockIdx.x];
+    const uint64_t segbits = (uint64_t)(blockIdx.x >> sub_shift) << (2 * k - 10);
+    const int lane = threadIdx.x & 63;
+    for (uint32_t i0 = 0; i0 < n; i0 += blockDim.x) {  // uniform trip count: the ballot sees whole waves
+        const uint32_t i = i0 + threadIdx.x;
+        Key<1> x;
+        x.w[0] = 0;
+        bool keep = false;
+        if (i < n) {
+            x.w[0] = segbits | in[o + i];
+            keep = !kmer_less_nucl<1>(kmer_rc<1>(x, k), x);
+        }
+        const uint64_t bal = __ballot(keep);
+        uint32_t base = 0;
+        if (lane == 0 && bal) base = atomicAdd(count, (uint32_t)__popcll(bal));
+        base = __shfl(base, 0);
+        const uint64_t at = (uint64_t)base + __popcll(bal & ((1ull << lane) - 1ull));
+        if (keep && at < cap) out[at] = x.w[0];
+    }
+}
+
 void BucketView::materialise(bbk_ctx *ctx) {
     if (!live()) return;
     keys.alloc(n() * 8 + 16);
@@ -3071,6 +3418,7 @@ struct MsdKnobs {
         bool xcd_slots = env_u64(getenv("BBK_XCD_SLOTS"), 1) != 0;  // 0: one level-1 fill front per segment, not per XCD
         bool xcd_tiles = env_u64(getenv("BBK_XCD_TILES"), 1) != 0;  // 0: level-2 workgroups in plain tile order
         bool no_narrow_b = getenv("BBK_NO_NARROW_B") != nullptr;  // 8-byte records after level 1 of stage B
+        bool no_late_tag = getenv("BBK_NO_LATE_TAG") != nullptr;  // tagged stage B takes the tag at level 1 (8-byte records there)
         // stage A hands stage B the dense 8-byte array, not its buckets (BucketView)
         bool no_bucket_handoff = getenv("BBK_NO_BUCKET_HANDOFF") != nullptr;
         // k_part_reads_narrow as that many persistent workgroups per CU (0: one workgroup per tile)
@@ -3258,6 +3606,7 @@ struct MsdRunner {
         bool too_deep;  // would need a third level: declined
         int nw_hb;      // key bits above the low word (8-byte keys)
         bool narrow, hslots, kslots, slots;
+        bool late_tag = false;  // stage B from a BucketView, k <= 21: 4-byte records from level 1, tag taken at level 2
         uint32_t rd_tile, ntiles1, ntiles1h;  // chunks of a read tile; level-1 tiles (scatter, reads histogram)
         int xs;         // log2 of the level-1 sub-slots per segment (one per XCD)
         uint32_t nsub, sub_cap, seg_cap, cap2, stride2, spill_cap;
@@ -3265,7 +3614,8 @@ struct MsdRunner {
     };
 
     // The bin plan and the mode of a pass of N records (n_chunks read chunks).  No HIP calls.
-    Plan plan(uint64_t N, uint64_t n_chunks, bool from_reads, bool has_val, const Sel &sel, bool has_dst) const {
+    Plan plan(uint64_t N, uint64_t n_chunks, bool from_reads, bool has_val, const Sel &sel, bool has_dst,
+              bool from_view = false) const {
         Plan P;
         const bool ranged = sel.span != 0;
         P.Ntot = N;
@@ -3336,6 +3686,23 @@ struct MsdRunner {
                    !knobs.no_direct && u32_slots;
         P.slots = P.hslots || P.kslots;
         BBK_REQUIRE(!P.narrow || P.slots, BBK_ERR_INTERNAL, "narrow records need the slot mode");
+        // Late tag (see k_part_view_lt): everything narrow stage B asks for, a tagged expansion read from stage A's
+        // buckets, and 2k - 10 <= 32.  Narrow stage B's span check (no bucket of the 512-segment plan wider than 2^32
+        // keys) can only be taken on level 1's fills; here it is taken on the even fills the key slots are sized for, so
+        // that a call too small for 4-byte records keeps the 8-byte route as a whole.
+        P.late_tag = false;
+        if (W == 1 && from_view && P.kslots && expand_tag && !even_part && !ranged && !has_dst && !has_val &&
+            op == MSD_OP_NONE && dmode == MSD_KEYS && !knobs.once.no_narrow_b && !knobs.once.no_late_tag && expand_k >= 17 &&
+            2 * expand_k <= 42) {
+            const double nb2 = std::min<double>(kMaxBins, std::max(1.0, std::ceil((double)N / P.nb1 / P.target)));
+            const uint64_t Q = 1ull << (32 - P.b1), q = (Q + (uint64_t)nb2 - 1) / (uint64_t)nb2;
+            const int wb = w0bits();
+            P.late_tag = (wb > 32 ? q << (wb - 32) : q >> (32 - wb)) <= (1ull << 32);
+        }
+        if (P.late_tag) {
+            P.b1 = 10;
+            P.nb1 = kMaxBins;
+        }
         // narrow level 1: one sub-slot (and cursor) per XCD inside every segment slot (PartLevel::xcd_shift); the XCDs do
         // not take exactly equal shares of the tiles, so the sub-slots get 6 % + 2048 records of slack.
         // A 128-byte line of a segment that workgroups on DIFFERENT XCDs fill (their ~60-byte runs are adjacent) is
@@ -3352,7 +3719,7 @@ struct MsdRunner {
         P.cap2 = P.narrow ? (uint32_t)(kNwHashThreads * kNwHashItems) : bucket_cap();
         // bucket slots 256 B further apart than their capacity: with a power-of-two-ish stride every bucket's
         // fill front sits in the same HBM channel (level-2 scatter measured 10 % slower)
-        P.rec_ab = P.narrow ? 4 : rec;
+        P.rec_ab = (P.narrow || P.late_tag) ? 4 : rec;
         P.stride2 = P.cap2 + (uint32_t)(256 / P.rec_ab);
         P.spill_cap = P.slots ? (uint32_t)(N / 8 + 65536) : 0u;
         return P;
@@ -3409,6 +3776,7 @@ struct MsdRunner {
         std::vector<uint32_t> xstart;
         // buckets
         DevBuf dcount, slot_off, bseg, bbase, flag_ids;  // bbase: narrow stage B, smallest key of a bucket
+        DevBuf bperm, pfill;  // late tag: place of every bucket in the order of the result; the fills in that order
         // scans whose totals come back with the flags (fetch_flags): c64 = key slots, exclusive scan of the slot fills;
         // d64 = hash slots, exclusive scan of the distinct counts.  scan_keep: their scratch, alive until the pass ends
         DevBuf c64, d64;
@@ -3443,7 +3811,7 @@ struct MsdRunner {
                 *n_records = N;
                 return Outcome::TooBig;
             }
-            P = R.plan(N, n_chunks, from_reads, has_val, sel, has_dst);
+            P = R.plan(N, n_chunks, from_reads, has_val, sel, has_dst, in.view != nullptr);
             N = P.N;
             if (in.view && !view_level1()) return Outcome::NeedDense;
             if (P.too_deep) {  // leave to the LSD path
@@ -3628,6 +3996,10 @@ struct MsdRunner {
         void level1_from_view() {
             if constexpr (W == 1) {
                 BucketView &v = *in.view;
+                if (P.late_tag) {
+                    level1_late_tag(v);
+                    return;
+                }
                 const uint32_t half = kPartTileK / 2;
                 const uint32_t nt = (uint32_t)((v.D + half - 1) / half);
                 if (nt) {
@@ -3654,6 +4026,34 @@ struct MsdRunner {
             }
         }
 
+        // level 1 with the tag taken late: 4-byte records into 1024 key-prefix segments (k_part_view_lt), from the
+        // buckets and from the overflow path's dense keys
+        void level1_late_tag(BucketView &v) {
+            if constexpr (W == 1) {
+                constexpr uint32_t kpt = (uint32_t)kLtThreads * kLt1Items / 2;
+                const size_t lds = lt_smem(kLt1Items, (size_t)kViewSpan * (4 + 2));
+                const uint32_t nt = (uint32_t)((v.D + kpt - 1) / kpt);
+                ctx->add_stat("stat_late_tag", (double)N);
+                if (nt) {
+                    DevBuf vdesc((size_t)nt * sizeof(uint2) + 16);
+                    hipLaunchKernelGGL(k_view_tile_desc, dim3((nt + 255) / 256), dim3(256), 0, ctx->stream,
+                                       v.off.as<uint64_t>(), v.nbuckets, v.D, kpt, nt, vdesc.as<uint2>());
+                    check_launch("k_view_tile_desc");
+                    R.launch(k_part_view_lt<false>, "k_part_view", (double)v.D * 4 + 2.0 * (double)v.D * 4, nt, kLtThreads, lds,
+                             v.slots.as<uint32_t>(), v.off.as<uint64_t>(), v.seg.as<uint16_t>(), vdesc.as<uint2>(), v.stride,
+                             v.hb, (const uint64_t *)nullptr, v.D, (int)R.expand_k, L1, cur1.as<uint32_t>(),
+                             bufA.as<uint32_t>());
+                }
+                if (v.n_extra) {
+                    const uint32_t nte = (uint32_t)((v.n_extra + kpt - 1) / kpt);
+                    R.launch(k_part_view_lt<true>, "k_part_l1", (double)v.n_extra * 8 + 2.0 * (double)v.n_extra * 4, nte,
+                             kLtThreads, lds, (const uint32_t *)nullptr, (const uint64_t *)nullptr, (const uint16_t *)nullptr,
+                             (const uint2 *)nullptr, 0u, 0, v.extra.as<uint64_t>(), v.n_extra, (int)R.expand_k, L1,
+                             cur1.as<uint32_t>(), bufA.as<uint32_t>());
+                }
+            }
+        }
+
         // a key-slot give-up after level 1 released the view's buckets: the canonical keys again, from level 1's records
         Outcome give_up_key_slots() {
             if constexpr (W == 1) {
@@ -3663,9 +4063,16 @@ struct MsdRunner {
                     v.keys.alloc(n * rec + 16);
                     DevBuf cnt(16);
                     BBK_HIP(hipMemsetAsync(cnt.p, 0, 16, ctx->stream));
-                    hipLaunchKernelGGL(k_view_recanon, dim3(P.nsub), dim3(256), 0, ctx->stream, bufA.as<uint64_t>(),
-                                       seg_off, seg_size, (int)R.expand_k,
-                                       v.keys.as<uint64_t>(), n, cnt.as<uint32_t>());
+                    if (P.late_tag) {
+                        ctx->add_stat("stat_late_tag_recanon", (double)n);
+                        hipLaunchKernelGGL(k_view_recanon_lt, dim3(P.nsub), dim3(256), 0, ctx->stream, bufA.as<uint32_t>(),
+                                           seg_off, seg_size, P.xs, (int)R.expand_k, v.keys.as<uint64_t>(), n,
+                                           cnt.as<uint32_t>());
+                    } else {
+                        hipLaunchKernelGGL(k_view_recanon, dim3(P.nsub), dim3(256), 0, ctx->stream, bufA.as<uint64_t>(),
+                                           seg_off, seg_size, (int)R.expand_k, v.keys.as<uint64_t>(), n,
+                                           cnt.as<uint32_t>());
+                    }
                     check_launch("k_view_recanon");
                     uint32_t got = 0;
                     BBK_HIP(hipMemcpyAsync(&got, cnt.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -3749,10 +4156,14 @@ struct MsdRunner {
                 for (uint32_t b = 0; b < nb1; ++b) hsub[b] = h1[b];  // exact mode: one dense run per segment
             tstart[0] = 0;
             sbin[0] = 0;
-            const uint32_t tile2 = P.narrow ? (uint32_t)(has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE) : kPartTileK;
+            const uint32_t tile2 = P.late_tag ? (uint32_t)(kLtThreads * kLt2Items)
+                                   : P.narrow   ? (uint32_t)(has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE)
+                                                : kPartTileK;
             for (uint32_t s2 = 0; s2 < nsub; ++s2) tstart[s2 + 1] = tstart[s2] + (hsub[s2] + tile2 - 1) / tile2;
             for (uint32_t b = 0; b < nb1; ++b) {
-                snb2[b] = (uint32_t)std::min<double>(kMaxBins, std::max(1.0, std::ceil((double)h1[b] / P.target)));
+                // (late tag: 16 tags x nsub key ranges per segment)
+                snb2[b] = P.late_tag ? 16u * (uint32_t)std::min<double>(kMaxBins / 16, std::max(1.0, std::ceil((double)h1[b] / (16.0 * P.target))))
+                                     : (uint32_t)std::min<double>(kMaxBins, std::max(1.0, std::ceil((double)h1[b] / P.target)));
                 sbin[b + 1] = sbin[b] + snb2[b];
             }
             nbuckets = sbin[nb1];
@@ -3768,7 +4179,10 @@ struct MsdRunner {
                 }
             narrow_b = W == 1 && P.kslots && !R.even_part && !ranged && !has_dst && !has_val && R.op == MSD_OP_NONE &&
                        R.dmode == MSD_KEYS && span_b <= (1ull << 32) && !R.knobs.once.no_narrow_b;
-            if (P.kslots && verbose)
+            if (P.late_tag) narrow_b = true;  // a bucket is one tag and part of one segment: below 2^32 keys by construction
+            if (P.late_tag && verbose)
+                fprintf(stderr, "[bbk] msd key slots: 4-byte records from level 1, tag taken at level 2 (%u buckets)\n", nbuckets);
+            else if (P.kslots && verbose)
                 fprintf(stderr, "[bbk] msd key slots: %s records from level 2 (widest bucket 2^%.1f keys)\n",
                         narrow_b ? "4-byte" : "8-byte", std::log2((double)std::max<uint64_t>(span_b, 1)));
 
@@ -3808,7 +4222,7 @@ struct MsdRunner {
             desc2.alloc((size_t)nwg2 * sizeof(uint4) + 16);
             if (ntiles2) {
                 if (xstart_d) BBK_HIP(hipMemsetAsync(desc2.p, 0, (size_t)nwg2 * sizeof(uint4), ctx->stream));
-                hipLaunchKernelGGL(P.narrow ? k_tile_desc_narrow : k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0,
+                hipLaunchKernelGGL((P.narrow || P.late_tag) ? k_tile_desc_narrow : k_tile_desc, dim3((ntiles2 + 255) / 256), dim3(256), 0,
                                    ctx->stream, M2, seg_nb2, seg_bin, tile2, xs, (const uint32_t *)xstart_d,
                                    desc2.as<uint4>());
                 check_launch("k_tile_desc");
@@ -3864,6 +4278,12 @@ struct MsdRunner {
                              2.0 * (double)N * (4 + (has_val ? 4 : 0)), nwg2, kNw2Threads, part_narrow2_smem(has_val),
                              bufA.as<uint32_t>(), vals_or_null(valA), desc2.as<uint4>(), L2, hist2.as<uint32_t>(),
                              bufB.as<uint32_t>(), vals_or_null(valB));
+            } else if (P.late_tag) {
+                if constexpr (W == 1)
+                    if (ntiles2)
+                        R.launch(k_part_lt2, "k_part_l2", 2.0 * (double)N * 4, nwg2, kLtThreads, lt_smem(kLt2Items, 0),
+                                 bufA.as<uint32_t>(), desc2.as<uint4>(), (int)R.expand_k, L2, hist2.as<uint32_t>(),
+                                 bufB.as<uint32_t>());
             } else if (narrow_b) {
                 if constexpr (W == 1)
                     R.template launch_part<false, false, false, true>("k_part_l2", (double)N * (rec + 4), nwg2,
@@ -3896,14 +4316,35 @@ struct MsdRunner {
                 // total below N means a record missed its slot: the host learns it with the flags, after the buckets have
                 // run -- such a record also counts in ctr[0], and offsets from a total below N stay inside out.keys
                 c64.alloc(((size_t)nbuckets + 1) * 8);
-                const ScanSrc src{hist2.p, SCAN_SLOT_FILL, P.stride2, P.cap2};
                 uint64_t *const so = c64.as<uint64_t>();
-                exclusive_scan_enqueue(ctx, 1, &src, &so, nbuckets, ctl_total(), false, scan_keep);
                 slot_off.alloc(((size_t)nbuckets + 1) * 4 + 16);
-                hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
-                                   c64.as<uint64_t>(), (uint64_t)nbuckets, 0ull, (const uint64_t *)ctl_total(),
-                                   slot_off.as<uint32_t>());
-                check_launch("k_scan_to_u32");
+                if (P.late_tag) {
+                    // buckets lie as (segment, tag, sub), the result is ordered (tag, segment, sub): the fills are
+                    // gathered in that order, scanned, and the offsets brought back to the buckets
+                    const dim3 gb((nbuckets + 255) / 256);
+                    bbase.alloc(((size_t)nbuckets + 1) * 8);
+                    bperm.alloc(((size_t)nbuckets + 1) * 4);
+                    pfill.alloc(((size_t)nbuckets + 1) * 4);
+                    hipLaunchKernelGGL(k_bucket_base_lt, gb, dim3(256), 0, ctx->stream, (const uint32_t *)seg_nb2,
+                                       (const uint32_t *)seg_bin, P.nb1, nbuckets, 2 * (int)R.expand_k - 10, (int)R.expand_k,
+                                       bbase.as<uint64_t>(), bperm.as<uint32_t>());
+                    check_launch("k_bucket_base_lt");
+                    hipLaunchKernelGGL(k_lt_fill_perm, gb, dim3(256), 0, ctx->stream, hist2.as<uint32_t>(),
+                                       bperm.as<uint32_t>(), nbuckets, P.stride2, P.cap2, pfill.as<uint32_t>());
+                    check_launch("k_lt_fill_perm");
+                    const ScanSrc src{pfill.p, SCAN_U32_FLAGGED, 0u, 0u};
+                    exclusive_scan_enqueue(ctx, 1, &src, &so, nbuckets, ctl_total(), false, scan_keep);
+                    hipLaunchKernelGGL(k_lt_unperm, gb, dim3(256), 0, ctx->stream, c64.as<uint64_t>(), bperm.as<uint32_t>(),
+                                       nbuckets, slot_off.as<uint32_t>());
+                    check_launch("k_lt_unperm");
+                } else {
+                    const ScanSrc src{hist2.p, SCAN_SLOT_FILL, P.stride2, P.cap2};
+                    exclusive_scan_enqueue(ctx, 1, &src, &so, nbuckets, ctl_total(), false, scan_keep);
+                    hipLaunchKernelGGL(k_scan_to_u32, dim3((nbuckets + 1 + 255) / 256), dim3(256), 0, ctx->stream,
+                                       c64.as<uint64_t>(), (uint64_t)nbuckets, 0ull, (const uint64_t *)ctl_total(),
+                                       slot_off.as<uint32_t>());
+                    check_launch("k_scan_to_u32");
+                }
                 A.out_off = slot_off.as<uint32_t>();
             }
             if (direct) {
@@ -3982,12 +4423,14 @@ struct MsdRunner {
             } else if (narrow_b) {
                 if constexpr (W == 1) {
                     BBK_REQUIRE(direct, BBK_ERR_INTERNAL, "4-byte stage-B records need the direct output");
-                    bbase.alloc(((size_t)nbuckets + 1) * 8);
+                    if (!P.late_tag) bbase.alloc(((size_t)nbuckets + 1) * 8);  // (late tag: k_bucket_base_lt, with the offsets)
                     if (nbuckets) {
-                        hipLaunchKernelGGL(k_bucket_base, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
-                                           (const uint32_t *)seg_nb2, (const uint32_t *)seg_bin, P.nb1, nbuckets, P.b1,
-                                           R.w0bits(), bbase.as<uint64_t>());
-                        check_launch("k_bucket_base");
+                        if (!P.late_tag) {
+                            hipLaunchKernelGGL(k_bucket_base, dim3((nbuckets + 255) / 256), dim3(256), 0, ctx->stream,
+                                               (const uint32_t *)seg_nb2, (const uint32_t *)seg_bin, P.nb1, nbuckets, P.b1,
+                                               R.w0bits(), bbase.as<uint64_t>());
+                            check_launch("k_bucket_base");
+                        }
                         constexpr int NT = BktCfg<1>::NT, IT = BktCfg<1>::ITEMS;
                         R.launch(k_bucket_dist_nb<NT, IT>, "k_bucket_dist", (double)N * (4 + rec), nbuckets, NT,
                                  bucket_dist_nb_smem<NT, IT>(), bufB.as<uint32_t>(), bbase.as<uint64_t>(), A);
