@@ -370,6 +370,57 @@ const char *bbk_edgeindex_name(const bbk_edgeindex *ix, uint64_t segment); /* NU
 int bbk_edgeindex_export_graph(const bbk_edgeindex *ix, char *h_bases, uint64_t *h_offsets, uint32_t *h_links,
                                uint32_t *h_kc);
 
+/* ---- k-mer multiplicity profiles across samples: replaces KmerMultiplicityCounter::FilterCombinedKmers
+ *      (projects/mts/kmer_multiplicity_counter.cpp:72-139: one KMC database per sample, sorted and merged under
+ *      RtSeq::less3 = BBK_ORDER_SORTED) and, for the lookup, the BooPHF map of BuildKmerIndex (:141-181) -- and contig
+ *      abundances over them: ProfileCounter::operator() (projects/mts/contig_abundance.cpp:245-284) with the winsorised
+ *      mean of TrivialClusterAnalyzer (:46-78) ---------------------------------------------------------------------- */
+typedef struct bbk_kmerprofile_builder bbk_kmerprofile_builder; /* the filtered sets of the samples, in HBM          */
+typedef struct bbk_kmerprofile bbk_kmerprofile; /* kept k-mers ascending + one row of n_samples u16 each, in HBM     */
+/* ci / cs: KMC's per-sample filter (its defaults are 2 and 255): a k-mer counted fewer than ci times is absent from
+ * that sample, the remaining counts are saturated at cs.  BBK_ERR_ARG for ci < 1 and for cs outside 1..65535 (the
+ * reference would silently truncate a larger count to the 16 bits of a row, :92,127-129). */
+int bbk_kmerprofile_begin(bbk_ctx *ctx, unsigned k, unsigned n_samples, unsigned ci, unsigned cs,
+                          bbk_kmerprofile_builder **out);
+/* sample in [0, n_samples), each exactly once; the set must be the ascending canonical set with counts of the sample's
+ * reads (bbk_count*(k, BBK_CANONICAL | BBK_WITH_COUNTS)) and may be freed after the call: its filtered records (keys
+ * + u16 counts) stay in HBM until bbk_kmerprofile_finish.  An empty set is a valid sample. */
+int bbk_kmerprofile_add_sample(bbk_kmerprofile_builder *b, unsigned sample, const bbk_kmerset *canonical_counts);
+/* The join.  With present = samples holding the k-mer and total = the sum of its counts, a k-mer is kept iff
+ * present >= min_samples && (present > 1 || total > min_mult) (:115,125); an absent sample has 0 in the row.  An empty
+ * result is valid (min_samples > n_samples gives one).  Releases the builder, also on failure. */
+int bbk_kmerprofile_finish(bbk_kmerprofile_builder *b, uint64_t min_samples, uint64_t min_mult, bbk_kmerprofile **out);
+void bbk_kmerprofile_abort(bbk_kmerprofile_builder *b);
+uint64_t bbk_kmerprofile_size(const bbk_kmerprofile *p);
+unsigned bbk_kmerprofile_samples(const bbk_kmerprofile *p);
+unsigned bbk_kmerprofile_k(const bbk_kmerprofile *p);
+/* dst_keys: size * words u64 ascending; dst_rows: size * samples u16, sample-major inside a row (host or device;
+ * either may be NULL) */
+int bbk_kmerprofile_export(bbk_ctx *ctx, const bbk_kmerprofile *p, void *dst_keys, void *dst_rows);
+/* <prefix>.bpr: the rows as the reference writes them (:94,127-129); <prefix>.kmers: the kept k-mers as RtSeq::BinWrite
+ * records (the reference's temporary k-mer file, :126), ascending.  The latter stands in for <prefix>.kmm, the BooPHF
+ * serialisation of BuildKmerIndex: here the ascending table is the index. */
+int bbk_kmerprofile_write(bbk_ctx *ctx, const bbk_kmerprofile *p, const char *prefix);
+/* KmerProfileIndex's constructor (contig_abundance.cpp:189-206).  BBK_ERR_ARG when <prefix>.kmers is not a whole number
+ * of k-mer records, when <prefix>.bpr is not records x n_samples x 2 bytes, or when the k-mers do not ascend. */
+int bbk_kmerprofile_load(bbk_ctx *ctx, const char *prefix, unsigned k, unsigned n_samples, bbk_kmerprofile **out);
+/* Every read is one contig without a character other than ACGT (bbk_reads apply LongestValid).  For contig c:
+ * h_positions[c] = its k-mer positions; h_n[c] = those found in the profile, either strand (the "earmarks", :257-271);
+ * h_sum / h_sumsq[c * samples + s] = sum and sum of squares of the n values of column s after winsorising:
+ * o = ceil(float(n) * 0.05f), lo = sorted[o], hi = sorted[n - o - 1], v -> max(min(v, hi), lo); n = 1 stands as it is.
+ * That is WinsoredMeanImpl (:46-59) with its commented-out std::sort; the binary's std::nth_element leaves other
+ * elements at those two positions.  Integers only: mean = float(sum) / float(n), variance = float(sumsq) / float(n)
+ * - mean * mean and the share test n / (length - k + 1) >= 0.7 (math::ls, :274-281) are the caller's. */
+int bbk_kmerprofile_abundance(bbk_ctx *ctx, const bbk_kmerprofile *p, const bbk_reads *contigs, uint64_t *h_n,
+                              uint64_t *h_positions, uint64_t *h_sum, uint64_t *h_sumsq);
+/* The same for contigs that hold other characters: the caller cuts every contig into its maximal ACGT stretches
+ * (SplitOnNs, :172-185) and passes them as reads; contig c is the pieces [h_first_piece[c], h_first_piece[c + 1])
+ * (n_contigs + 1 entries, from 0 to the number of pieces; a contig may have none). */
+int bbk_kmerprofile_abundance_pieces(bbk_ctx *ctx, const bbk_kmerprofile *p, const bbk_reads *pieces,
+                                     const uint64_t *h_first_piece, uint64_t n_contigs, uint64_t *h_n,
+                                     uint64_t *h_positions, uint64_t *h_sum, uint64_t *h_sumsq);
+void bbk_kmerprofile_free(bbk_kmerprofile *p);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

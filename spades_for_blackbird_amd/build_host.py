@@ -9,7 +9,9 @@ BIN = os.path.join(HERE, "bin")
 PROGRAMS = {"spades-kmercount": "kmercount_main.cpp", "spades-gbuilder": "gbuilder_main.cpp",
             "spades-kmer-estimating": "kmer_estimating_main.cpp", "spades-read-filter": "read_filter_main.cpp",
             "bbk-fastx-dump": "fastx_dump_main.cpp",
-            "unitig-coverage": "unitig_coverage_main.cpp", "spades-gmapper": "gmapper_main.cpp"}
+            "unitig-coverage": "unitig_coverage_main.cpp", "spades-gmapper": "gmapper_main.cpp",
+            "kmer_multiplicity_counter": "kmer_multiplicity_counter_main.cpp",
+            "contig_abundance_counter": "contig_abundance_counter_main.cpp"}
 HEADERS = ["common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp"]
 
 

@@ -34,6 +34,10 @@ SYMBOLS = [
     "bbk_profiles_begin", "bbk_profiles_push_reads", "bbk_profiles_export_raw", "bbk_profiles_write", "bbk_profiles_free",
     "bbk_edgeindex_map_paths", "bbk_edgeindex_from_gfa_with_graph", "bbk_paths_reads", "bbk_paths_ranges", "bbk_paths_export", "bbk_paths_free",
     "bbk_edgeindex_links", "bbk_edgeindex_total_bases", "bbk_edgeindex_name", "bbk_edgeindex_export_graph",
+    "bbk_kmerprofile_begin", "bbk_kmerprofile_add_sample", "bbk_kmerprofile_finish", "bbk_kmerprofile_abort",
+    "bbk_kmerprofile_size", "bbk_kmerprofile_samples", "bbk_kmerprofile_k", "bbk_kmerprofile_export",
+    "bbk_kmerprofile_write", "bbk_kmerprofile_load", "bbk_kmerprofile_abundance", "bbk_kmerprofile_abundance_pieces",
+    "bbk_kmerprofile_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -199,6 +203,24 @@ def load_library():
         L.bbk_edgeindex_name.restype = C.c_char_p
         L.bbk_edgeindex_name.argtypes = [vp, u64]
         L.bbk_edgeindex_export_graph.argtypes = [vp, vp, vp, vp, vp]
+    L.bbk_kmerprofile_begin.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(vp)]
+    L.bbk_kmerprofile_add_sample.argtypes = [vp, C.c_uint, vp]
+    L.bbk_kmerprofile_finish.argtypes = [vp, u64, u64, C.POINTER(vp)]
+    L.bbk_kmerprofile_abort.argtypes = [vp]
+    L.bbk_kmerprofile_abort.restype = None
+    L.bbk_kmerprofile_size.restype = u64
+    L.bbk_kmerprofile_size.argtypes = [vp]
+    L.bbk_kmerprofile_samples.restype = C.c_uint
+    L.bbk_kmerprofile_samples.argtypes = [vp]
+    L.bbk_kmerprofile_k.restype = C.c_uint
+    L.bbk_kmerprofile_k.argtypes = [vp]
+    L.bbk_kmerprofile_export.argtypes = [vp, vp, vp, vp]
+    L.bbk_kmerprofile_write.argtypes = [vp, vp, C.c_char_p]
+    L.bbk_kmerprofile_load.argtypes = [vp, C.c_char_p, C.c_uint, C.c_uint, C.POINTER(vp)]
+    L.bbk_kmerprofile_abundance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.bbk_kmerprofile_abundance_pieces.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp]
+    L.bbk_kmerprofile_free.argtypes = [vp]
+    L.bbk_kmerprofile_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -414,6 +436,27 @@ class Context:
         h = C.c_void_p()
         _check(self._L.bbk_edgeindex_from_unitigs(self._h, unitigs._h, C.byref(h)))
         return EdgeIndex(self, h)
+
+    def kmerprofile(self, k, sets, min_samples, min_mult=5, ci=2, cs=255):
+        """KmerMultiplicityCounter::FilterCombinedKmers: the join of one ascending canonical KMerSet with counts per
+        sample (count(reads, k, CANONICAL | WITH_COUNTS)) into a KmerProfile.  ci / cs: KMC's per-sample filter."""
+        b = C.c_void_p()
+        _check(self._L.bbk_kmerprofile_begin(self._h, k, len(sets), ci, cs, C.byref(b)))
+        try:
+            for i, s in enumerate(sets):
+                _check(self._L.bbk_kmerprofile_add_sample(b, i, s._h))
+        except Exception:
+            self._L.bbk_kmerprofile_abort(b)
+            raise
+        h = C.c_void_p()
+        _check(self._L.bbk_kmerprofile_finish(b, min_samples, min_mult, C.byref(h)))
+        return KmerProfile(self, h)
+
+    def kmerprofile_load(self, prefix, k, n_samples):
+        """the <prefix>.kmers / <prefix>.bpr pair KmerProfile.write leaves"""
+        h = C.c_void_p()
+        _check(self._L.bbk_kmerprofile_load(self._h, str(prefix).encode(), k, n_samples, C.byref(h)))
+        return KmerProfile(self, h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -790,3 +833,57 @@ class Profiles(_Handle):
     def write(self, path):
         """the unitig-coverage output file (EdgeProfileStorage::Save)"""
         _check(self._L.bbk_profiles_write(self.ctx._h, self._h, path.encode()))
+
+
+class KmerProfile(_Handle):
+    """kept k-mers x samples table of u16 multiplicities (the reference's .bpr with its k-mer index)"""
+    _free = "bbk_kmerprofile_free"
+
+    def __len__(self):
+        return int(self._L.bbk_kmerprofile_size(self._h))
+
+    @property
+    def k(self):
+        return int(self._L.bbk_kmerprofile_k(self._h))
+
+    @property
+    def samples(self):
+        return int(self._L.bbk_kmerprofile_samples(self._h))
+
+    def keys(self):
+        """np.uint64 [size, words]: the kept canonical k-mers, ascending"""
+        a = np.zeros((len(self), words(self.k)), dtype=np.uint64)
+        _check(self._L.bbk_kmerprofile_export(self.ctx._h, self._h, _ptr(a), None))
+        return a
+
+    def rows(self):
+        """np.uint16 [size, samples]: the multiplicity of every kept k-mer in every sample (0: absent)"""
+        a = np.zeros((len(self), self.samples), dtype=np.uint16)
+        _check(self._L.bbk_kmerprofile_export(self.ctx._h, self._h, None, _ptr(a)))
+        return a
+
+    def write(self, prefix):
+        """<prefix>.bpr and <prefix>.kmers"""
+        _check(self._L.bbk_kmerprofile_write(self.ctx._h, self._h, str(prefix).encode()))
+
+    def abundance(self, reads, first_piece=None):
+        """(n, positions, sum, sumsq): per contig the k-mers found and the k-mer positions, per (contig, sample) the sum
+        and the sum of squares of the winsorised column; integers only (see bbk_kmerprofile_abundance).  Every read is
+        a contig, or with first_piece (contigs + 1 entries) contig c is the reads [first_piece[c], first_piece[c + 1]):
+        its maximal ACGT stretches."""
+        if first_piece is None:
+            nc = len(reads)
+        else:
+            first_piece = np.ascontiguousarray(first_piece, dtype=np.uint64)
+            nc = len(first_piece) - 1
+        n = np.zeros(nc, dtype=np.uint64)
+        pos = np.zeros(nc, dtype=np.uint64)
+        sm = np.zeros((nc, self.samples), dtype=np.uint64)
+        sq = np.zeros((nc, self.samples), dtype=np.uint64)
+        if first_piece is None:
+            _check(self._L.bbk_kmerprofile_abundance(self.ctx._h, self._h, reads._h, _ptr(n), _ptr(pos), _ptr(sm),
+                                                     _ptr(sq)))
+        else:
+            _check(self._L.bbk_kmerprofile_abundance_pieces(self.ctx._h, self._h, reads._h, _ptr(first_piece), nc, _ptr(n),
+                                                            _ptr(pos), _ptr(sm), _ptr(sq)))
+        return n, pos, sm, sq

@@ -1,0 +1,263 @@
+"""GPU: the k-mer multiplicity profile (join of per-sample counts) and the contig abundances over it, against the literal
+restatement of the reference's merge loop and winsorised mean (tests/kmerprofile_restated.py), through the Python
+binding and through the two command-line tools.  The per-sample counts themselves come from ctx.count, which other
+tests pin to the oracle."""
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import spades_for_blackbird_amd as B
+from spades_for_blackbird_amd import build, build_host
+from tests import kmerprofile_restated as R
+from tests.helpers import rc, read_fastq_gz
+
+pytestmark = pytest.mark.gpu
+
+FLAGS = B.CANONICAL | B.WITH_COUNTS
+
+
+@pytest.fixture(scope="module")
+def bins():
+    build.build()
+    return {os.path.basename(p): p for p in build_host.build()}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = B.Context(0)
+    yield c
+    c.close()
+
+
+def _genome(rng, n):
+    return "".join(rng.choice(list("ACGT"), n))
+
+
+def _reads(rng, genome, n, read_len=100, sub_rate=0.005):
+    out = []
+    for st in rng.integers(0, len(genome) - read_len + 1, n):
+        r = list(genome[st:st + read_len])
+        for j in np.nonzero(rng.random(read_len) < sub_rate)[0]:
+            r[j] = "ACGT"[("ACGT".index(r[j]) + int(rng.integers(1, 4))) & 3]
+        r = "".join(r)
+        out.append(rc(r) if rng.random() < 0.5 else r)
+    return out
+
+
+def _count(ctx, reads, k):
+    s = ctx.count(ctx.reads_from_ascii(reads), k, FLAGS)
+    return s, s.export(with_counts=True)
+
+
+def _check_join(ctx, tmp_path, k, sets, exported, min_samples, min_mult=5, ci=2, cs=255):
+    """profile == restatement: arrays, files, and the files loaded again"""
+    n_samples, nw = len(sets), R.words(k)
+    p = ctx.kmerprofile(k, sets, min_samples, min_mult=min_mult, ci=ci, cs=cs)
+    rk, rr = R.join([R.filter_sample(keys, cnt, ci, cs) for keys, cnt in exported], min_samples, min_mult)
+    exp_keys = np.array(rk, dtype=np.uint64).reshape(len(rk), nw)
+    exp_rows = np.array(rr, dtype=np.uint16).reshape(len(rr), n_samples)
+    assert len(p) == len(rk) and p.samples == n_samples and p.k == k
+    assert p.keys().tobytes() == exp_keys.tobytes()
+    assert p.rows().tobytes() == exp_rows.tobytes()
+    prefix = str(tmp_path / ("prof_%d_%d_%d_%d" % (min_samples, min_mult, ci, cs)))
+    p.write(prefix)
+    assert open(prefix + ".kmers", "rb").read() == R.kmers_bytes(rk)
+    assert open(prefix + ".bpr", "rb").read() == R.bpr_bytes(rr)
+    q = ctx.kmerprofile_load(prefix, k, n_samples)
+    assert len(q) == len(rk) and q.keys().tobytes() == exp_keys.tobytes() and q.rows().tobytes() == exp_rows.tobytes()
+    return p, rk, rr
+
+
+def _samples(n_samples, k, seed):
+    """reads of n_samples genomes with a shared and a private part; one sample has no k-mer at all (n_samples > 1); a
+    k-mer seen 6 times lives only in the last sample"""
+    rng = np.random.default_rng(seed)
+    shared = _genome(rng, 3000)
+    empty = {1: -1, 2: 0}.get(n_samples, 1)
+    out = []
+    for s in range(n_samples):
+        out.append(["ACGT"] if s == empty else _reads(rng, shared + _genome(rng, 1500), 2000))
+    lone = _genome(rng, k)
+    out[-1] += [lone] * 6
+    return out, R.encode(R.canonical(lone))
+
+
+@pytest.mark.parametrize("n_samples,k", [(1, 21), (2, 33), (3, 55), (5, 97)])
+def test_join_equals_restatement(ctx, tmp_path, n_samples, k):
+    reads, lone = _samples(n_samples, k, seed=k)
+    sets, exported = zip(*[_count(ctx, r, k) for r in reads])
+    if n_samples > 1:
+        assert sum(1 for s in sets if len(s) == 0) == 1
+    p, rk, rr = _check_join(ctx, tmp_path, k, sets, exported, min_samples=1)
+    assert 0 < len(rk) < len({tuple(int(x) for x in key) for keys, _ in exported for key in keys})
+    assert rr[rk.index(lone)] == [0] * (n_samples - 1) + [6]
+
+
+def test_join_settings(ctx, tmp_path):
+    """min_samples = N, counts above cs, ci above some counts, everything kept, nothing kept"""
+    k = 21
+    rng = np.random.default_rng(7)
+    shared = _genome(rng, 3000)
+    reads = [_reads(rng, shared + _genome(rng, 1500), 2000) for _ in range(3)]
+    sets, exported = zip(*[_count(ctx, r, k) for r in reads])
+    top = max(int(c.max()) for _, c in exported)
+    assert top > 40
+    _, rk, rr = _check_join(ctx, tmp_path, k, sets, exported, min_samples=3)
+    assert rk and all(all(v > 0 for v in row) for row in rr)
+    _, rk, rr = _check_join(ctx, tmp_path, k, sets, exported, min_samples=1, cs=20)
+    assert max(v for row in rr for v in row) == 20
+    _, rk2, rr = _check_join(ctx, tmp_path, k, sets, exported, min_samples=1, ci=40)
+    assert 0 < len(rk2) < len(rk) and min(v for row in rr for v in row if v) >= 40
+    _, rk3, _ = _check_join(ctx, tmp_path, k, sets, exported, min_samples=0, min_mult=0, ci=1, cs=65535)
+    assert len(rk3) == len({tuple(int(x) for x in key) for keys, _ in exported for key in keys})
+    p, rk4, _ = _check_join(ctx, tmp_path, k, sets, exported, min_samples=4)  # more samples than there are
+    assert rk4 == [] and len(p) == 0
+    prefix = str(tmp_path / "prof_4_5_2_255")
+    assert os.path.getsize(prefix + ".kmers") == 0 and os.path.getsize(prefix + ".bpr") == 0
+    n, pos, sm, sq = p.abundance(ctx.reads_from_ascii([shared[:300]]))
+    assert (int(n[0]), int(pos[0]), int(sm.sum()), int(sq.sum())) == (0, 280, 0, 0)
+
+
+def test_load_refuses_sizes_that_do_not_divide(ctx, tmp_path):
+    k = 33
+    keys = sorted(R.encode(_genome(np.random.default_rng(s), k)) for s in range(4))
+    prefix = str(tmp_path / "p")
+    open(prefix + ".kmers", "wb").write(R.kmers_bytes(keys))
+    open(prefix + ".bpr", "wb").write(R.bpr_bytes([[1, 2, 3]] * 4))
+    assert len(ctx.kmerprofile_load(prefix, k, 3)) == 4
+    with pytest.raises(B.BBKError, match="expected"):
+        ctx.kmerprofile_load(prefix, k, 2)
+    with pytest.raises(B.BBKError, match="whole number"):
+        ctx.kmerprofile_load(prefix, 65, 3)
+    open(prefix + ".kmers", "wb").write(R.kmers_bytes(keys[::-1]))
+    with pytest.raises(B.BBKError, match="ascend"):
+        ctx.kmerprofile_load(prefix, k, 3)
+    with pytest.raises(B.BBKError, match="cannot open"):
+        ctx.kmerprofile_load(str(tmp_path / "absent"), k, 3)
+
+
+def test_argument_errors(ctx):
+    k = 21
+    reads = ctx.reads_synth(500, read_len=100, genome_len=2000)
+    good = ctx.count(reads, k, FLAGS)
+    for flags in (FLAGS | B.UNSORTED, B.BOTH_STRANDS | B.WITH_COUNTS, B.CANONICAL):
+        with pytest.raises(B.BBKError, match="ascending canonical k-mer set with counts"):
+            ctx.kmerprofile(k, [good, ctx.count(reads, k, flags)], 1)
+    with pytest.raises(B.BBKError, match="16-bit"):
+        ctx.kmerprofile(k, [good], 1, cs=65536)
+    with pytest.raises(B.BBKError, match="ci"):
+        ctx.kmerprofile(k, [good], 1, ci=0)
+    with pytest.raises(B.BBKError, match="21-mers"):
+        ctx.kmerprofile(23, [good], 1)
+    assert len(ctx.kmerprofile(k, [good], 1)) > 0  # the context is still usable
+
+
+@pytest.fixture(scope="module")
+def community(ctx):
+    """three samples at k = 21; 500 bases of the shared part are covered ~600x in sample 0 (counts above 255)"""
+    k = 21
+    rng = np.random.default_rng(21)
+    shared = _genome(rng, 3000)
+    private = [_genome(rng, 1500) for _ in range(3)]
+    reads = [_reads(rng, shared + private[s], 2000) for s in range(3)]
+    reads[0] += _reads(rng, shared[1000:1500], 3000)
+    sets, exported = zip(*[_count(ctx, r, k) for r in reads])
+    assert max(int(c.max()) for _, c in exported) > 300
+    noise = _genome(rng, 300)
+    contigs = [("long shared", shared), ("hot", shared[1000:1500]),
+               ("with Ns", shared[0:200] + "N" + shared[201:210] + "NN" + shared[212:500])]
+    contigs += [("n%d" % n, shared[990:990 + k - 1 + n]) for n in (1, 2, 3, 20, 21)]
+    contigs += [("rc", rc(shared[500:900])), ("tiny", shared[:15]), ("k-1", shared[:k - 1]), ("random", noise),
+                ("half", shared[:100] + noise[:200]), ("private2", private[2][:400]), ("lower", shared[1500:1700].lower())]
+    return k, sets, exported, contigs
+
+
+@pytest.mark.parametrize("cs", [255, 1000])
+def test_abundance_equals_restatement(ctx, bins, community, tmp_path, cs):
+    """cs = 255: one selection pass; cs = 1000: values above 255, the high byte is selected first"""
+    k, sets, exported, contigs = community
+    p, rk, rr = _check_join(ctx, tmp_path, k, sets, exported, min_samples=1, cs=cs)
+    assert (max(v for row in rr for v in row) > 255) == (cs > 255)
+    table = {R.decode(key, k): row for key, row in zip(rk, rr)}
+    exp = [R.abundance_ints(seq, k, table, 3) for _, seq in contigs]
+    assert {1, 2, 3, 20, 21} <= {e[0] for e in exp} and max(e[0] for e in exp) > 2000
+    pieces, first = [], [0]
+    for _, seq in contigs:
+        pieces += R.split_on_ns(seq)
+        first.append(len(pieces))
+    n, pos, sm, sq = p.abundance(ctx.reads_from_ascii(pieces), first)
+    assert [int(x) for x in n] == [e[0] for e in exp]
+    assert [int(x) for x in pos] == [e[1] for e in exp]
+    assert sm.tolist() == [e[2] for e in exp] and sq.tolist() == [e[3] for e in exp]
+    # every read one contig
+    n1, pos1, sm1, sq1 = p.abundance(ctx.reads_from_ascii([contigs[0][1], contigs[1][1]]))
+    assert n1.tolist() == n[:2].tolist() and pos1.tolist() == pos[:2].tolist()
+    assert sm1.tolist() == sm[:2].tolist() and sq1.tolist() == sq[:2].tolist()
+    # the tool: all contigs, with the variance, and the run ended by the first contig shorter than -l
+    fa = tmp_path / "contigs.fasta"
+    fa.write_text("".join(">%s\n%s\n" % c for c in contigs))
+    prefix = str(tmp_path / ("prof_1_5_2_%d" % cs))
+    for extra, kw in (([], {}), (["-v"], {"var": True}), (["-l", "16", "-b", "2000"], {"min_len": 16})):
+        out = tmp_path / "ab.tsv"
+        r = subprocess.run([bins["contig_abundance_counter"], "-k", str(k), "-c", str(fa), "-n", "3", "-m", prefix, "-o",
+                            str(out)] + extra, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        text = R.run(contigs, k, table, 3, **kw)
+        assert out.read_text() == text
+        names = [line.split("\t")[0] for line in text.split("\n")[:-1]]
+        assert "long shared" in names and "with Ns" in names and "rc" in names
+        assert not {"tiny", "k-1", "random", "half"} & set(names)
+        assert ("private2" in names) == ("min_len" not in kw)
+
+
+def test_clis_end_to_end(ctx, bins, golden_dir, tmp_path):
+    """both tools on the two golden read files as two samples, contigs = the unitigs spades-gbuilder makes of the first"""
+    k = 21
+    d = tmp_path / "samples"
+    d.mkdir()
+    files = [os.path.join(golden_dir, "ecoli_1K_%d.fq.gz" % i) for i in (1, 2)]
+    for i, f in enumerate(files):
+        shutil.copy(f, d / ("sample%d.fq.gz" % (i + 1)))
+    prefix = str(tmp_path / "kmers")
+    exported = [_count(ctx, read_fastq_gz(f), k)[1] for f in files]
+    table = None
+    for extra, kw in ((["-s", "1"], {"min_samples": 1}),
+                      (["-s", "1", "-m", "0", "--ci", "1", "--cs", "3", "-t", "2", "-b", "20000"],
+                       {"min_samples": 1, "min_mult": 0, "ci": 1, "cs": 3})):
+        r = subprocess.run([bins["kmer_multiplicity_counter"], "-k", str(k), "-n", "2", "-o", prefix, "-f", str(d)] + extra,
+                           capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        ci, cs = kw.get("ci", 2), kw.get("cs", 255)
+        rk, rr = R.join([R.filter_sample(keys, cnt, ci, cs) for keys, cnt in exported], kw["min_samples"],
+                        kw.get("min_mult", 5))
+        assert open(prefix + ".kmers", "rb").read() == R.kmers_bytes(rk)
+        assert open(prefix + ".bpr", "rb").read() == R.bpr_bytes(rr)
+        table = {R.decode(key, k): row for key, row in zip(rk, rr)}
+    fa = tmp_path / "unitigs.fasta"
+    r = subprocess.run([bins["spades-gbuilder"], files[0], str(fa), "-k", str(k), "--unitigs"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    contigs = [(rec.split("\n", 1)[0], rec.split("\n", 1)[1].replace("\n", "")) for rec in fa.read_text().split(">")[1:]]
+    assert contigs
+    for extra, var in (([], False), (["-v"], True)):
+        out = tmp_path / "ab.tsv"
+        r = subprocess.run([bins["contig_abundance_counter"], "-k", str(k), "-c", str(fa), "-n", "2", "-m", prefix, "-o",
+                            str(out)] + extra, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
+        text = R.run(contigs, k, table, 2, var=var)
+        assert out.read_text() == text
+        assert text.count("\n") == len(contigs)  # every k-mer of the unitigs is in sample 1
+    # refusals: a sample without reads, a sample with two read files, a cs above 16 bits, a missing option
+    base = [bins["kmer_multiplicity_counter"], "-k", str(k), "-o", prefix, "-f", str(d), "-s", "1"]
+    for args, word in ((["-n", "3"], "none of"), (["-n", "2"], "several"), (["-n", "1", "--cs", "70000"], "16-bit")):
+        if word == "several":  # the samples are looked for in order: sample 3 is missed only while sample 2 has one file
+            shutil.copy(files[0], d / "sample2.fastq.gz")
+        r = subprocess.run(base + args, capture_output=True, text=True)
+        assert r.returncode > 0 and word in r.stderr, (args, r.returncode, r.stderr)
+    r = subprocess.run(base, capture_output=True, text=True)
+    assert r.returncode == 1 and "Usage" in r.stdout
+    r = subprocess.run([bins["contig_abundance_counter"], "-k", str(k), "-c", str(fa), "-n", "3", "-m", prefix, "-o",
+                        str(tmp_path / "x.tsv")], capture_output=True, text=True)
+    assert r.returncode > 0 and "expected" in r.stderr
