@@ -90,7 +90,7 @@ struct SkParams {
     uint32_t xcd_tiles;       // level 2: tiles dealt to the XCDs by slot (k_sk_part2)
     // level 1: a slot is cut into 8 sub-slots of sub1 records, one per XCD, each with a cursor (cursor1[8 b + xcd]): the
     // (tile, bin) runs are one to four 24-byte records, and a 128-byte line that workgroups on different XCDs fill is
-    // slow (msd.hip, level-1 call site).  0: one fill front per slot (slot1 = 8 * sub1 otherwise).
+    // slow (msd.hip, MsdRunner::plan: the sub-slots).  0: one fill front per slot (slot1 = 8 * sub1 otherwise).
     uint32_t sub1;
     uint32_t tps_sub;         // level-2 tiles of a sub-slot (tps = 8 * tps_sub)
 };
@@ -448,7 +448,7 @@ __global__ __launch_bounds__(kSk2NT) void k_sk_part2(const uint64_t *__restrict_
     __shared__ unsigned long long gbase[HIST ? 1 : kSkMaxP2];
     const uint32_t tid = threadIdx.x;
     // Workgroup w runs on XCD w % 8: the tiles of slot b1 all go to XCD b1 % 8, so that the buckets of a slot are filled
-    // through ONE L2 (a line that several XCDs fill is slow: see the level-1 call site in msd.hip).  Grid: 8 *
+    // through ONE L2 (a line that several XCDs fill is slow: see MsdRunner::plan in msd.hip).  Grid: 8 *
     // ceil(P1 / 8) * tps; BBK_XCD_TILES=0 (P.xcd_tiles = 0): slot-major order.
     uint32_t b1, t;
     if (P.xcd_tiles) {

@@ -1,4 +1,4 @@
-"""GPU: stage B's level 1 reading stage A's buckets in place (msd.h BucketView, msd.hip k_part_view).
+"""GPU: stage B's level 1 reading stage A's buckets in place (msd.h BucketView, msd_stage_b.h k_part_view).
 
 A single-batch both-strand count at odd k with 8-byte keys leaves stage A's distinct set in its level-2 slots; the key
 slots of stage B read it there, and nothing else ever sees it: every other consumer materialises the dense array

@@ -1,4 +1,4 @@
-"""GPU: tagged stage B with 4-byte records from level 1 and the tag taken at level 2 (msd.hip "late tag",
+"""GPU: tagged stage B with 4-byte records from level 1 and the tag taken at level 2 (msd_stage_b.h "late tag",
 k_part_view_lt / k_part_lt2 / k_bucket_base_lt).
 
 The route applies to the flagship shape (both strands, final_kmers order, stage A's buckets handed over in place) at

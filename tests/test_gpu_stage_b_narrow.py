@@ -1,4 +1,4 @@
-"""GPU: stage B with 4-byte records after level 1 (msd.hip "narrow stage B", k_bucket_base / k_bucket_dist_nb).
+"""GPU: stage B with 4-byte records after level 1 (msd_stage_b.h "narrow stage B", k_bucket_base / k_bucket_dist_nb).
 
 The ordering pass of the both-strand set takes the key slots; when no level-2 bucket spans more than 2^32 keys only the
 keys' low words travel from level 2 on and the sort kernel widens them with the bucket's smallest key.  Every case is
