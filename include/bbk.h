@@ -421,6 +421,34 @@ int bbk_kmerprofile_abundance_pieces(bbk_ctx *ctx, const bbk_kmerprofile *p, con
                                      uint64_t *h_positions, uint64_t *h_sum, uint64_t *h_sumsq);
 void bbk_kmerprofile_free(bbk_kmerprofile *p);
 
+/* ---- Hamming-graph clustering of a k-mer set: replaces TauOneKMerHamClusterer::cluster / ClusterChunk
+ *      (projects/hammer/hamcluster.cpp:228-289; BayesHammer's first step, projects/hammer/main.cpp:143-168) over a
+ *      dsu::ConcurrentDSU (common/adt/concurrent_dsu.hpp) and ConcurrentDSU::extract_to_file (concurrent_dsu.cpp:17-86) --- */
+typedef struct bbk_hamclusters bbk_hamclusters; /* label of every k-mer, members cluster by cluster, sizes: in HBM */
+/* set: ascending BBK_BOTH_STRANDS set, k <= 32, fewer than 2^32 - 2 k-mers (the union-find holds u32 parents).  An index
+ * is a position in that ascending set.  tau must be 1 (general_tau of configs/hammer/config.info).  K-mers at Hamming
+ * distance 1 are united; a cluster is a connected component of that graph unless the component has lock_size members
+ * or more: those are replayed on the host by the reference's rule (hamcluster.cpp:235-274: chunks of `chunk` indices
+ * in ascending order, the strand with key <= rc(key) of a pair is processed, no union with a locked set
+ * (canMerge2, :213-226), sets of >= lock_size members with a member in the chunk are locked after it; unite as
+ * concurrent_dsu.hpp:46-96).  lock_size / chunk: 0 = the reference's 2500 (:269) / 65536 (:281).
+ * BBK_ERR_ARG: tau != 1, k > 32, a BBK_UNSORTED or BBK_REFERENCE_ORDER set, 2^32 - 2 k-mers or more, a set that is not
+ * closed under reverse complement.  An empty set gives zero clusters. */
+int bbk_kmerset_hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *set, unsigned tau, uint64_t lock_size, uint64_t chunk,
+                                 bbk_hamclusters **out);
+uint64_t bbk_hamclusters_count(const bbk_hamclusters *h);    /* clusters (ConcurrentDSU::num_sets, concurrent_dsu.hpp:146-153) */
+uint64_t bbk_hamclusters_size(const bbk_hamclusters *h);     /* k-mers */
+uint64_t bbk_hamclusters_replayed(const bbk_hamclusters *h); /* k-mers that went through the host replay */
+/* h_labels: size entries, the smallest member index of the cluster of every k-mer; h_members: size entries, the member
+ * indices cluster by cluster, clusters by ascending label, ascending inside a cluster; h_sizes: count entries.  Any may
+ * be NULL.  (The reference lists clusters by DSU root, concurrent_dsu.cpp:54-69.) */
+int bbk_hamclusters_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_labels, uint64_t *h_members,
+                           uint64_t *h_sizes);
+/* <path>: h_members as u64; <path>.idx: h_sizes as u64 -- kmers.hamming / kmers.hamming.idx as
+ * ConcurrentDSU::extract_to_file writes them (concurrent_dsu.cpp:63-83) */
+int bbk_hamclusters_write(bbk_ctx *ctx, const bbk_hamclusters *h, const char *path);
+void bbk_hamclusters_free(bbk_hamclusters *h);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

@@ -11,7 +11,8 @@ PROGRAMS = {"spades-kmercount": "kmercount_main.cpp", "spades-gbuilder": "gbuild
             "bbk-fastx-dump": "fastx_dump_main.cpp",
             "unitig-coverage": "unitig_coverage_main.cpp", "spades-gmapper": "gmapper_main.cpp",
             "kmer_multiplicity_counter": "kmer_multiplicity_counter_main.cpp",
-            "contig_abundance_counter": "contig_abundance_counter_main.cpp"}
+            "contig_abundance_counter": "contig_abundance_counter_main.cpp",
+            "spades-hamcluster": "hamcluster_main.cpp"}
 HEADERS = ["common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp"]
 
 

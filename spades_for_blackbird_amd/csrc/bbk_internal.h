@@ -307,6 +307,9 @@ struct ScanSrc {
 // for the stream.
 void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t *const *out, uint64_t n,
                             uint64_t *d_total, bool tail, std::vector<DevBuf> &keep);
+// extindex.hip: the prefix table over an ascending key array that table_find (kmer_ops.h) reads; returns its bits
+unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
+                            bool *wide);
 // free device memory (see bbk_ctx::mem_free)
 size_t device_free_cached(bbk_ctx *ctx);
 // the context's pinned planning block, at least `bytes` long

@@ -1,0 +1,455 @@
+// hamclust.hip -- Hamming-graph clustering of a both-strand k-mer set, tau = 1.
+//
+// Replaces TauOneKMerHamClusterer::cluster / ClusterChunk (projects/hammer/hamcluster.cpp:228-289), the first thing
+// spades-hammer does with its counted 21-mers (projects/hammer/main.cpp:143-168): every k-mer is united in a
+// dsu::ConcurrentDSU (adt/concurrent_dsu.hpp) with each of its 3k single-base substitutions that is in the set, unless
+// one of the two sets has been locked (>= 2500 members at the end of a 64 Ki-index chunk).
+//
+// Here, for k <= 32 (one-word keys, base k-1 most significant in the ascending order):
+//   rc index (k_hc_rcidx): rcidx[i] = position of rc(key[i]), one table_find per record; a miss is the closure check.
+//   block scan (k_hc_scan): with m = k / 2, the records equal on their top m bases are contiguous (a block).  Two
+//     k-mers that differ at one base p < k - m share a block; for p >= k - m their reverse complements differ at
+//     k - 1 - p < m <= k - m and share one.  So every pair inside every block is compared, and a pair at distance exactly
+//     1 unites (a, b) and (rc a, rc b): every Hamming-1 edge of an rc-closed set is found, without a lookup.  A workgroup
+//     stages 256 consecutive records in LDS; every lane compares its record with the later records of its block, tile
+//     after tile until the block of the workgroup's last record ends.
+//   union-find: u32 parents, hooked inside the scan by compare-and-swap on the root with the larger index (a parent is
+//     always below its child, so the root of a tree is its smallest member), then pointer jumping in rounds until a
+//     round changes nothing (one flag read per round).
+//   sizes, the oversize subset, the listing: a histogram of the labels; the members of components of >= lock_size
+//     k-mers are compacted (index, key, rc index) through the scan of primitives.hip and replayed on the host by the
+//     reference's chunked rule -- below lock_size nothing is ever locked and a cluster is its component; the member
+//     indices are grouped by label with the LSD sort (stable: ascending inside a cluster).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "bbk_internal.h"
+#include "kmer_ops.h"
+
+struct bbk_hamclusters {
+    uint64_t n = 0, clusters = 0, replayed = 0;
+    bbk::DevBuf labels;   // n u32: smallest member index of the cluster of k-mer i
+    bbk::DevBuf members;  // n u32: the indices cluster by cluster
+    bbk::DevBuf sizes;    // clusters u64
+};
+
+namespace bbk {
+
+constexpr int kHcTile = 256;
+constexpr uint64_t kHcPairs = 0x5555555555555555ull;
+constexpr uint64_t kHcLockSize = 2500;    // hamcluster.cpp:269
+constexpr uint64_t kHcChunk = 64 * 1024;  // hamcluster.cpp:281
+
+__device__ inline uint32_t hc_load(const uint32_t *p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
+
+// root of x; on the way every visited node is moved to its grandparent (only ever to an ancestor: atomicMin)
+__device__ inline uint32_t hc_find(uint32_t *parent, uint32_t x) {
+    uint32_t p = hc_load(&parent[x]);
+    while (p != x) {
+        const uint32_t g = hc_load(&parent[p]);
+        if (g != p) atomicMin(&parent[x], g);
+        x = p;
+        p = g;
+    }
+    return x;
+}
+
+// the root with the larger index goes under the smaller; a lost race starts again from the two roots
+__device__ inline void hc_unite(uint32_t *parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = hc_find(parent, a);
+        b = hc_find(parent, b);
+        if (a == b) return;
+        const uint32_t hi = a > b ? a : b, lo = a > b ? b : a;
+        if (atomicCAS(&parent[hi], hi, lo) == hi) return;
+        a = hi;
+        b = lo;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hc_rcidx(const Key<1> *__restrict__ keys, uint64_t n, int k, PrefixTable P,
+                                                 uint32_t *__restrict__ rcidx, uint32_t *__restrict__ parent,
+                                                 uint32_t *__restrict__ status) {
+    const uint64_t i = BBK_GID();
+    if (i >= n) return;
+    uint64_t pos = table_find<1>(keys, P, kmer_rc<1>(key_load<1>(&keys[i]), k));
+    if (pos == kNotFound) {
+        atomicOr(&status[0], 1u);
+        pos = i;
+    }
+    rcidx[i] = (uint32_t)pos;
+    parent[i] = (uint32_t)i;
+}
+
+// status[1] receives the length of the longest block
+__global__ __launch_bounds__(kHcTile) void k_hc_scan(const uint64_t *__restrict__ keys, uint64_t n, int shift,
+                                                    const uint32_t *__restrict__ rcidx, uint32_t *__restrict__ parent,
+                                                    uint32_t *__restrict__ status) {
+    __shared__ uint64_t tile[kHcTile];
+    const uint64_t t0 = (((uint64_t)blockIdx.y * gridDim.x) + blockIdx.x) * kHcTile;
+    if (t0 >= n) return;
+    const int tid = threadIdx.x;
+    const uint64_t gi = t0 + (uint64_t)tid;
+    const bool valid = gi < n;
+    const uint64_t a = valid ? keys[gi] : 0ull;
+    const uint64_t ablk = valid ? a >> shift : ~0ull;
+    const uint64_t wmax = (uint64_t)__shfl((unsigned long long)ablk, 63, 64);  // block of the wave's last record
+    const uint64_t last = t0 + kHcTile - 1 < n ? t0 + kHcTile - 1 : n - 1;
+    const uint64_t lastblk = keys[last] >> shift;
+    uint32_t later = 0;  // later records of this lane's block
+    for (uint64_t ts = t0;;) {
+        const uint64_t gl = ts + (uint64_t)tid;
+        tile[tid] = gl < n ? keys[gl] : 0ull;
+        const int cnt = n - ts < (uint64_t)kHcTile ? (int)(n - ts) : kHcTile;
+        __syncthreads();
+        // a later tile holds records of this lane's block only if its first record is one
+        const bool mine = valid && (ts == t0 || (tile[0] >> shift) == ablk);
+        if (__ballot(mine)) {
+            for (int j = ts == t0 ? (tid & ~63) + 1 : 0; j < cnt; ++j) {  // every lane reads tile[j]: a broadcast
+                const uint64_t b = tile[j];
+                const uint64_t bblk = b >> shift;
+                if (bblk > wmax) break;  // ascending: nothing further belongs to a block of this wave
+                const uint64_t gj = ts + (uint64_t)j;
+                if (mine && gj > gi && bblk == ablk) {
+                    ++later;
+                    uint64_t x = a ^ b;
+                    x = (x | (x >> 1)) & kHcPairs;
+                    if (__popcll(x) == 1) {
+                        hc_unite(parent, (uint32_t)gi, (uint32_t)gj);
+                        hc_unite(parent, rcidx[gi], rcidx[gj]);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        ts += kHcTile;
+        if (ts >= n || (keys[ts] >> shift) != lastblk) break;
+    }
+    if (valid && (gi == 0 || (keys[gi - 1] >> shift) != ablk)) atomicMax(&status[1], later + 1u);
+}
+
+__global__ __launch_bounds__(256) void k_hc_jump(uint32_t *__restrict__ parent, uint64_t n, uint32_t *__restrict__ changed) {
+    const uint64_t i = BBK_GID();
+    if (i >= n) return;
+    const uint32_t p = hc_load(&parent[i]);
+    uint32_t r = p;
+    for (uint32_t q = hc_load(&parent[r]); q != r; q = hc_load(&parent[r])) r = q;
+    if (r != p) {
+        parent[i] = r;
+        atomicOr(changed, 1u);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_hc_count(const uint32_t *__restrict__ label, uint64_t n, uint32_t *__restrict__ cnt) {
+    const uint64_t i = BBK_GID();
+    if (i < n) atomicAdd(&cnt[label[i]], 1u);
+}
+
+__global__ __launch_bounds__(256) void k_hc_flag_over(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
+                                                     uint64_t n, uint64_t lock_size, uint64_t *__restrict__ flag) {
+    const uint64_t i = BBK_GID();
+    if (i < n) flag[i] = (uint64_t)cnt[label[i]] >= lock_size ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_hc_compact_over(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
+                                                        uint64_t n, uint64_t lock_size, const uint64_t *__restrict__ off,
+                                                        const uint64_t *__restrict__ keys, const uint32_t *__restrict__ rcidx,
+                                                        uint32_t *__restrict__ out_idx, uint64_t *__restrict__ out_key,
+                                                        uint32_t *__restrict__ out_rc) {
+    const uint64_t i = BBK_GID();
+    if (i >= n || (uint64_t)cnt[label[i]] < lock_size) return;
+    const uint64_t d = off[i];
+    out_idx[d] = (uint32_t)i;
+    out_key[d] = keys[i];
+    out_rc[d] = rcidx[i];
+}
+
+__global__ __launch_bounds__(256) void k_hc_relabel(const uint32_t *__restrict__ idx, const uint32_t *__restrict__ lab,
+                                                   uint64_t r, uint32_t *__restrict__ label) {
+    const uint64_t j = BBK_GID();
+    if (j < r) label[idx[j]] = lab[j];
+}
+
+__global__ __launch_bounds__(256) void k_hc_flag_roots(const uint32_t *__restrict__ label, uint64_t n,
+                                                      uint64_t *__restrict__ flag) {
+    const uint64_t i = BBK_GID();
+    if (i < n) flag[i] = label[i] == (uint32_t)i ? 1ull : 0ull;
+}
+
+__global__ __launch_bounds__(256) void k_hc_sizes(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
+                                                 const uint64_t *__restrict__ off, uint64_t n, uint64_t *__restrict__ sizes) {
+    const uint64_t i = BBK_GID();
+    if (i < n && label[i] == (uint32_t)i) sizes[off[i]] = cnt[i];
+}
+
+__global__ __launch_bounds__(256) void k_hc_pairs(const uint32_t *__restrict__ label, uint64_t n, uint64_t *__restrict__ key,
+                                                 uint32_t *__restrict__ val) {
+    const uint64_t i = BBK_GID();
+    if (i >= n) return;
+    key[i] = label[i];
+    val[i] = (uint32_t)i;
+}
+
+template <class... P, class... A>
+static void hc_launch(bbk_ctx *ctx, const char *family, void (*fn)(P...), uint64_t threads, A... args) {
+    KernelTimer t(ctx, family);
+    hipLaunchKernelGGL(fn, grid_blocks((threads + 255) / 256), dim3(256), 0, ctx->stream, args...);
+    check_launch(family);
+}
+
+// ---- the host replay of the oversize components (hamcluster.cpp:213-276 over adt/concurrent_dsu.hpp:46-133) ----------
+namespace {
+
+enum { HC_UNLOCKED = 0, HC_FULLY_LOCKED = 3 };  // hamcluster.cpp:207-211
+
+struct HostDsu {
+    std::vector<uint32_t> parent, size;
+    std::vector<uint8_t> aux;
+    explicit HostDsu(size_t n) : parent(n), size(n, 1), aux(n, HC_UNLOCKED) {
+        for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
+    }
+    uint32_t find(uint32_t x) {
+        uint32_t r = x;
+        while (parent[r] != r) r = parent[r];
+        while (parent[x] != r) {
+            const uint32_t nx = parent[x];
+            parent[x] = r;
+            x = nx;
+        }
+        return r;
+    }
+    // concurrent_dsu.hpp:46-96: the smaller set goes under the larger, of two equal ones the lower index goes under
+    // the higher; the merged root keeps the aux of the set that stays root
+    void unite(uint32_t x, uint32_t y) {
+        x = find(x);
+        y = find(y);
+        if (x == y) return;
+        if (size[x] > size[y] || (size[x] == size[y] && x > y)) std::swap(x, y);
+        parent[x] = y;
+        size[y] += size[x];
+    }
+};
+
+}  // namespace
+
+// idx ascending global indices of the members (so key ascends too), rcg the global index of each reverse complement;
+// lab[j] receives the smallest global index of the cluster of member j
+static void hc_replay(unsigned k, uint64_t lock_size, uint64_t chunk, const std::vector<uint32_t> &idx,
+                      const std::vector<uint64_t> &key, const std::vector<uint32_t> &rcg, std::vector<uint32_t> &lab) {
+    const size_t R = idx.size();
+    std::vector<uint32_t> lrc(R);
+    for (size_t j = 0; j < R; ++j) {
+        const auto it = std::lower_bound(idx.begin(), idx.end(), rcg[j]);
+        BBK_REQUIRE(it != idx.end() && *it == rcg[j], BBK_ERR_INTERNAL,
+                    "hamming clusters: the reverse complement of a replayed k-mer is not replayed");
+        lrc[j] = (uint32_t)(it - idx.begin());
+    }
+    HostDsu uf(R);
+    for (size_t j = 0; j < R;) {
+        const uint64_t c = idx[j] / chunk;
+        size_t e = j;
+        while (e < R && idx[e] / chunk == c) ++e;
+        for (size_t x = j; x < e; ++x) {
+            const uint64_t kmer = key[x];
+            if (kmer > key[lrc[x]]) continue;  // one strand of a pair is processed
+            for (unsigned p = 0; p < k; ++p) {
+                const uint64_t cur = (kmer >> (2 * p)) & 3ull;
+                for (uint64_t nc = 0; nc < 4; ++nc) {
+                    if (nc == cur) continue;
+                    const uint64_t cand = (kmer & ~(3ull << (2 * p))) | (nc << (2 * p));
+                    const auto it = std::lower_bound(key.begin(), key.end(), cand);
+                    if (it == key.end() || *it != cand) continue;
+                    const uint32_t y = (uint32_t)(it - key.begin());
+                    if (uf.aux[uf.find((uint32_t)x)] == HC_FULLY_LOCKED || uf.aux[uf.find(y)] == HC_FULLY_LOCKED) continue;
+                    uf.unite((uint32_t)x, y);
+                    uf.unite(lrc[x], lrc[y]);  // no lock check here (hamcluster.cpp:257-260)
+                }
+            }
+        }
+        for (size_t x = j; x < e; ++x) {
+            const uint32_t r = uf.find((uint32_t)x);
+            if (uf.size[r] >= lock_size) uf.aux[r] = HC_FULLY_LOCKED;
+        }
+        j = e;
+    }
+    std::vector<uint32_t> low(R, 0xFFFFFFFFu);
+    lab.resize(R);
+    for (size_t x = 0; x < R; ++x) {
+        const uint32_t r = uf.find((uint32_t)x);
+        if (low[r] == 0xFFFFFFFFu) low[r] = idx[x];
+        lab[x] = low[r];
+    }
+}
+
+static bbk_hamclusters *hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t lock_size, uint64_t chunk) {
+    BBK_HIP(hipSetDevice(ctx->device));
+    if (lock_size == 0) lock_size = kHcLockSize;
+    if (chunk == 0) chunk = kHcChunk;
+    auto h = std::make_unique<bbk_hamclusters>();
+    const uint64_t n = s->n;
+    h->n = n;
+    if (n == 0) {
+        h->labels.alloc(16);
+        h->members.alloc(16);
+        h->sizes.alloc(16);
+        return h.release();
+    }
+    const unsigned k = s->k;
+    const uint64_t *keys = s->keys.as<uint64_t>();
+    DevBuf prefix, rcidx(n * 4), status(16);
+    bool wide = false;
+    const unsigned pbits = build_prefix_index(ctx, keys, 1, k, n, prefix, &wide);
+    const PrefixTable P{prefix.p, (int)(2 * k) - (int)pbits, wide ? 1 : 0};
+    h->labels.alloc(n * 4);
+    uint32_t *label = h->labels.as<uint32_t>();
+    BBK_HIP(hipMemsetAsync(status.p, 0, 16, ctx->stream));
+    hc_launch(ctx, "hc_rcidx", k_hc_rcidx, n, (const Key<1> *)s->keys.as<Key<1>>(), n, (int)k, P, rcidx.as<uint32_t>(), label,
+              status.as<uint32_t>());
+    uint32_t h_status[2] = {0, 0};
+    BBK_HIP(hipMemcpyAsync(h_status, status.p, 4, hipMemcpyDeviceToHost, ctx->stream));
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    BBK_REQUIRE(h_status[0] == 0, BBK_ERR_ARG,
+                "bbk_kmerset_hamming_clusters: the set is not closed under reverse complement (it must be a "
+                "BBK_BOTH_STRANDS set)");
+    prefix.release();
+    {
+        const int shift = 2 * (int)(k - k / 2);
+        KernelTimer t(ctx, "hc_scan");
+        hipLaunchKernelGGL(k_hc_scan, grid_blocks((n + kHcTile - 1) / kHcTile), dim3(kHcTile), 0, ctx->stream, keys, n, shift,
+                           (const uint32_t *)rcidx.as<uint32_t>(), label, status.as<uint32_t>());
+        check_launch("hc_scan");
+    }
+    // pointer jumping: a round that changes nothing ends it; the device decides, the host reads the flag
+    uint64_t rounds = 0;
+    for (uint32_t changed = 1; changed;) {
+        BBK_HIP(hipMemsetAsync(status.as<uint32_t>() + 2, 0, 4, ctx->stream));
+        hc_launch(ctx, "hc_jump", k_hc_jump, n, label, n, status.as<uint32_t>() + 2);
+        BBK_HIP(hipMemcpyAsync(&changed, status.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        ++rounds;
+    }
+    DevBuf cnt(n * 4), off(n * 8 + 16);
+    BBK_HIP(hipMemsetAsync(cnt.p, 0, n * 4, ctx->stream));
+    hc_launch(ctx, "hc_list", k_hc_count, n, (const uint32_t *)label, n, cnt.as<uint32_t>());
+    hc_launch(ctx, "hc_list", k_hc_flag_over, n, (const uint32_t *)label, (const uint32_t *)cnt.as<uint32_t>(), n, lock_size,
+              off.as<uint64_t>());
+    BBK_HIP(hipMemcpyAsync(h_status, status.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+    const uint64_t R = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), n);
+    ctx->add_stat("stat_hc_largest_block", (double)h_status[1]);
+    ctx->add_stat("stat_hc_rounds", (double)rounds);
+    h->replayed = R;
+    if (R) {
+        DevBuf oi(R * 4), ok(R * 8), orc(R * 4);
+        hc_launch(ctx, "hc_list", k_hc_compact_over, n, (const uint32_t *)label, (const uint32_t *)cnt.as<uint32_t>(), n,
+                  lock_size, (const uint64_t *)off.as<uint64_t>(), keys, (const uint32_t *)rcidx.as<uint32_t>(),
+                  oi.as<uint32_t>(), ok.as<uint64_t>(), orc.as<uint32_t>());
+        std::vector<uint32_t> h_idx(R), h_rc(R), h_lab;
+        std::vector<uint64_t> h_key(R);
+        BBK_HIP(hipMemcpyAsync(h_idx.data(), oi.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipMemcpyAsync(h_key.data(), ok.p, R * 8, hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipMemcpyAsync(h_rc.data(), orc.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        hc_replay(k, lock_size, chunk, h_idx, h_key, h_rc, h_lab);
+        BBK_HIP(hipMemcpyAsync(orc.p, h_lab.data(), R * 4, hipMemcpyHostToDevice, ctx->stream));
+        hc_launch(ctx, "hc_list", k_hc_relabel, R, (const uint32_t *)oi.as<uint32_t>(), (const uint32_t *)orc.as<uint32_t>(), R,
+                  label);
+        BBK_HIP(hipMemsetAsync(cnt.p, 0, n * 4, ctx->stream));
+        hc_launch(ctx, "hc_list", k_hc_count, n, (const uint32_t *)label, n, cnt.as<uint32_t>());
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // h_lab is read by the copy above
+    }
+    rcidx.release();
+    hc_launch(ctx, "hc_list", k_hc_flag_roots, n, (const uint32_t *)label, n, off.as<uint64_t>());
+    h->clusters = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), n);
+    h->sizes.alloc(h->clusters * 8);
+    hc_launch(ctx, "hc_list", k_hc_sizes, n, (const uint32_t *)label, (const uint32_t *)cnt.as<uint32_t>(),
+              (const uint64_t *)off.as<uint64_t>(), n, h->sizes.as<uint64_t>());
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    cnt.release();
+    off.release();
+    // the listing: (label, index) records ordered by label; the sort is stable, so a cluster's members ascend
+    h->members.alloc(n * 4);
+    DevBuf ka(n * 8), kb(n * 8), vb(n * 4);
+    hc_launch(ctx, "hc_list", k_hc_pairs, n, (const uint32_t *)label, n, ka.as<uint64_t>(), h->members.as<uint32_t>());
+    unsigned bits = 1;
+    while (bits < 32 && ((n - 1) >> bits)) ++bits;
+    sort_records(ctx, 1, ka.p, kb.p, h->members.as<uint32_t>(), vb.as<uint32_t>(), n, key_passes((bits + 1) / 2));
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    return h.release();
+}
+
+static void hc_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_labels, uint64_t *h_members, uint64_t *h_sizes) {
+    BBK_HIP(hipSetDevice(ctx->device));
+    if (h->n == 0) return;
+    raw_vector<uint32_t> tmp(h->n);
+    for (int which = 0; which < 2; ++which) {
+        uint64_t *dst = which ? h_members : h_labels;
+        if (!dst) continue;
+        d2h_big(ctx, tmp.data(), which ? h->members.p : h->labels.p, h->n * 4);
+        for (uint64_t i = 0; i < h->n; ++i) dst[i] = tmp[i];
+    }
+    if (h_sizes) d2h_big(ctx, h_sizes, h->sizes.p, h->clusters * 8);
+}
+
+static void hc_write_file(const std::string &path, const uint64_t *p, uint64_t count) {
+    FILE *f = fopen(path.c_str(), "wb");
+    BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path.c_str());
+    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
+    const bool closed = fclose(f) == 0;
+    BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path.c_str());
+}
+
+}  // namespace bbk
+
+using namespace bbk;
+
+extern "C" {
+
+int bbk_kmerset_hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *set, unsigned tau, uint64_t lock_size, uint64_t chunk,
+                                 bbk_hamclusters **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && set && out, BBK_ERR_ARG, "bbk_kmerset_hamming_clusters: NULL argument");
+        BBK_REQUIRE(tau == 1, BBK_ERR_ARG, "bbk_kmerset_hamming_clusters: tau = %u: tau > 1 not built (and tau = 0 unites nothing)",
+                    tau);
+        BBK_REQUIRE(set->k <= 32, BBK_ERR_ARG, "bbk_kmerset_hamming_clusters: k = %u: one-word keys only (k <= 32)", set->k);
+        BBK_REQUIRE(set->sorted, BBK_ERR_ARG,
+                    "bbk_kmerset_hamming_clusters: the set was built with BBK_UNSORTED: an ascending set is needed");
+        BBK_REQUIRE(!set->ref_order, BBK_ERR_ARG,
+                    "bbk_kmerset_hamming_clusters: the set is in the final_kmers order (BBK_REFERENCE_ORDER): an ascending "
+                    "set is needed");
+        BBK_REQUIRE(set->n < (1ull << 32) - 2, BBK_ERR_ARG,
+                    "bbk_kmerset_hamming_clusters: %llu k-mers: the union-find holds 32-bit parents (fewer than 2^32 - 2)",
+                    (unsigned long long)set->n);
+        *out = hamming_clusters(ctx, set, lock_size, chunk);
+    });
+}
+
+uint64_t bbk_hamclusters_count(const bbk_hamclusters *h) { return h ? h->clusters : 0; }
+uint64_t bbk_hamclusters_size(const bbk_hamclusters *h) { return h ? h->n : 0; }
+uint64_t bbk_hamclusters_replayed(const bbk_hamclusters *h) { return h ? h->replayed : 0; }
+
+int bbk_hamclusters_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_labels, uint64_t *h_members,
+                           uint64_t *h_sizes) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && h, BBK_ERR_ARG, "bbk_hamclusters_export: NULL argument");
+        hc_export(ctx, h, h_labels, h_members, h_sizes);
+    });
+}
+
+int bbk_hamclusters_write(bbk_ctx *ctx, const bbk_hamclusters *h, const char *path) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && h && path, BBK_ERR_ARG, "bbk_hamclusters_write: NULL argument");
+        raw_vector<uint64_t> members(h->n), sizes(h->clusters);
+        hc_export(ctx, h, nullptr, members.data(), sizes.data());
+        hc_write_file(path, members.data(), h->n);
+        hc_write_file(std::string(path) + ".idx", sizes.data(), h->clusters);
+    });
+}
+
+void bbk_hamclusters_free(bbk_hamclusters *h) { delete h; }
+
+}  // extern "C"

@@ -38,6 +38,8 @@ SYMBOLS = [
     "bbk_kmerprofile_size", "bbk_kmerprofile_samples", "bbk_kmerprofile_k", "bbk_kmerprofile_export",
     "bbk_kmerprofile_write", "bbk_kmerprofile_load", "bbk_kmerprofile_abundance", "bbk_kmerprofile_abundance_pieces",
     "bbk_kmerprofile_free",
+    "bbk_kmerset_hamming_clusters", "bbk_hamclusters_count", "bbk_hamclusters_size", "bbk_hamclusters_replayed",
+    "bbk_hamclusters_export", "bbk_hamclusters_write", "bbk_hamclusters_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -221,6 +223,14 @@ def load_library():
     L.bbk_kmerprofile_abundance_pieces.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, vp]
     L.bbk_kmerprofile_free.argtypes = [vp]
     L.bbk_kmerprofile_free.restype = None
+    L.bbk_kmerset_hamming_clusters.argtypes = [vp, vp, C.c_uint, u64, u64, C.POINTER(vp)]
+    for f in ("count", "size", "replayed"):
+        getattr(L, "bbk_hamclusters_" + f).restype = u64
+        getattr(L, "bbk_hamclusters_" + f).argtypes = [vp]
+    L.bbk_hamclusters_export.argtypes = [vp, vp, vp, vp, vp]
+    L.bbk_hamclusters_write.argtypes = [vp, vp, C.c_char_p]
+    L.bbk_hamclusters_free.argtypes = [vp]
+    L.bbk_hamclusters_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -578,6 +588,59 @@ class KMerSet(_Handle):
 
     def write_final_kmers(self, path):
         _check(self._L.bbk_kmerset_write_final_kmers(self.ctx._h, self._h, path.encode()))
+
+    def hamming_clusters(self, lock_size=0, chunk=0, tau=1):
+        """TauOneKMerHamClusterer::cluster over this ascending both-strand set (k <= 32): HamClusters.  lock_size /
+        chunk: 0 = the reference's 2500 / 65536."""
+        h = C.c_void_p()
+        _check(self._L.bbk_kmerset_hamming_clusters(self.ctx._h, self._h, tau, lock_size, chunk, C.byref(h)))
+        return HamClusters(self.ctx, h)
+
+
+KmerSet = KMerSet
+
+
+class HamClusters(_Handle):
+    """clusters of k-mers at Hamming distance 1 (the reference's kmers.hamming); an index is a position in the
+    ascending set, a label the smallest index of a cluster"""
+    _free = "bbk_hamclusters_free"
+
+    def __len__(self):
+        return int(self._L.bbk_hamclusters_count(self._h))
+
+    @property
+    def size(self):
+        return int(self._L.bbk_hamclusters_size(self._h))
+
+    @property
+    def replayed(self):
+        """k-mers of components of lock_size members or more, which went through the host replay"""
+        return int(self._L.bbk_hamclusters_replayed(self._h))
+
+    def labels(self):
+        """np.uint64 [size]: the label of every k-mer"""
+        a = np.zeros(self.size, dtype=np.uint64)
+        _check(self._L.bbk_hamclusters_export(self.ctx._h, self._h, _ptr(a), None, None))
+        return a
+
+    def members(self):
+        """np.uint64 [size]: the indices cluster by cluster (by ascending label), ascending inside a cluster"""
+        a = np.zeros(self.size, dtype=np.uint64)
+        _check(self._L.bbk_hamclusters_export(self.ctx._h, self._h, None, _ptr(a), None))
+        return a
+
+    def sizes(self):
+        """np.uint64 [len]: members of every cluster, in the order of members()"""
+        a = np.zeros(len(self), dtype=np.uint64)
+        _check(self._L.bbk_hamclusters_export(self.ctx._h, self._h, None, None, _ptr(a)))
+        return a
+
+    def write(self, path):
+        """<path> (member indices, u64) and <path>.idx (cluster sizes, u64): ConcurrentDSU::extract_to_file"""
+        _check(self._L.bbk_hamclusters_write(self.ctx._h, self._h, str(path).encode()))
+
+    def close(self):
+        self.free()
 
 
 class Counter:
