@@ -212,12 +212,6 @@ __global__ __launch_bounds__(256) void k_at_tips_mark(TipTable T, uint32_t max_l
                            max_len, x, xm, a, c, g, tt, flag);
 }
 
-static TipTable tip_table(const bbk_extindex *x) {
-    const int w0bits = (x->W == 1) ? (int)(2 * x->k) : 64;
-    return TipTable{x->keys.p, x->masks.as<uint8_t>(),
-                    PrefixTable{x->prefix.p, w0bits - (int)x->prefix_bits, x->prefix_wide ? 1 : 0}, (int)x->k, x->n};
-}
-
 template <int W>
 static void at_edges_impl(bbk_ctx *ctx, bbk_extindex *x, double ratio, uint64_t *edges, uint64_t *links) {
     uint32_t lc_min = 0;
@@ -229,13 +223,10 @@ static void at_edges_impl(bbk_ctx *ctx, bbk_extindex *x, double ratio, uint64_t 
     const TipTable T = tip_table(x);
     {
         KernelTimer t(ctx, "at_edges_find", (double)x->n * (1 + 8 * W));  // one read of masks + keys
-        hipLaunchKernelGGL(k_at_edges_find<W>, bbk::grid_blocks((2 * x->n + 255) / 256), dim3(256), 0, ctx->stream, T,
-                           lc_min, clear.as<uint32_t>(), ctr.as<unsigned long long>());
-        check_launch("k_at_edges_find");
+        launch_items(ctx, "k_at_edges_find", k_at_edges_find<W>, 2 * x->n, T, lc_min, clear.as<uint32_t>(),
+                     ctr.as<unsigned long long>());
     }
-    hipLaunchKernelGGL(k_at_edges_apply, bbk::grid_blocks((x->n + 255) / 256), dim3(256), 0, ctx->stream,
-                       x->masks.as<uint8_t>(), clear.as<uint8_t>(), x->n);
-    check_launch("k_at_edges_apply");
+    launch_items(ctx, "k_at_edges_apply", k_at_edges_apply, x->n, x->masks.as<uint8_t>(), clear.as<uint8_t>(), x->n);
     unsigned long long h[2] = {0, 0};
     BBK_HIP(hipMemcpyAsync(h, ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipStreamSynchronize(ctx->stream));
@@ -254,21 +245,16 @@ static void at_tips_impl(bbk_ctx *ctx, bbk_extindex *x, double ratio, uint32_t m
     TipTable T = tip_table(x);
     {
         KernelTimer t(ctx, "at_tips_find", 0.0);  // both walks
-        hipLaunchKernelGGL(k_at_tips_find<W>, bbk::grid_blocks((2 * x->n + 255) / 256), dim3(256), 0, ctx->stream, T,
-                           ratio, min_len, max_len, start.as<uint8_t>(), tipped.as<uint8_t>(),
-                           ctr.as<unsigned long long>());
-        check_launch("k_at_tips_find");
-        hipLaunchKernelGGL(k_at_tips_mark<W>, bbk::grid_blocks((2 * x->n + 255) / 256), dim3(256), 0, ctx->stream, T,
-                           max_len, start.as<uint8_t>(), flag.as<uint8_t>());
-        check_launch("k_at_tips_mark");
+        launch_items(ctx, "k_at_tips_find", k_at_tips_find<W>, 2 * x->n, T, ratio, min_len, max_len,
+                     start.as<uint8_t>(), tipped.as<uint8_t>(), ctr.as<unsigned long long>());
+        launch_items(ctx, "k_at_tips_mark", k_at_tips_mark<W>, 2 * x->n, T, max_len, start.as<uint8_t>(),
+                     flag.as<uint8_t>());
     }
-    hipLaunchKernelGGL(k_tips_apply, bbk::grid_blocks((x->n + 255) / 256), dim3(256), 0, ctx->stream,
-                       x->masks.as<uint8_t>(), flag.as<uint8_t>(), x->n, m2.as<uint8_t>());
-    check_launch("k_tips_apply");
+    launch_items(ctx, "k_tips_apply", k_tips_apply, x->n, x->masks.as<uint8_t>(), flag.as<uint8_t>(), x->n,
+                 m2.as<uint8_t>());
     T.masks = m2.as<uint8_t>();
-    hipLaunchKernelGGL(k_tips_links<W>, bbk::grid_blocks((x->n + 255) / 256), dim3(256), 0, ctx->stream, T,
-                       tipped.as<uint8_t>(), m3.as<uint8_t>(), ctr.as<unsigned long long>() + 1);
-    check_launch("k_tips_links");
+    launch_items(ctx, "k_tips_links", k_tips_links<W>, x->n, T, tipped.as<uint8_t>(), m3.as<uint8_t>(),
+                 ctr.as<unsigned long long>() + 1);
     unsigned long long h[2] = {0, 0};
     BBK_HIP(hipMemcpyAsync(h, ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipStreamSynchronize(ctx->stream));
@@ -283,7 +269,6 @@ static void at_require(const char *fn, bbk_ctx *ctx, bbk_extindex *x, double rat
     BBK_REQUIRE(std::isfinite(ratio) && ratio > 0, BBK_ERR_ARG, "%s: ratio %g is not a finite positive number", fn, ratio);
     BBK_REQUIRE(x->k % 2 == 1, BBK_ERR_ARG, "%s: k = %u is even (a k-mer could be its own reverse complement)", fn, x->k);
     BBK_REQUIRE(x->n < (1ull << 37), BBK_ERR_ARG, "%s: %llu k-mers exceed the launch grid", fn, (unsigned long long)x->n);
-    BBK_REQUIRE(x->W >= 1 && x->W <= 4, BBK_ERR_ARG, "%s: unsupported key width %u", fn, x->W);
 }
 
 }  // namespace bbk
@@ -298,12 +283,9 @@ extern "C" int bbk_extindex_remove_at_edges(bbk_ctx *ctx, bbk_extindex *x, doubl
         *removed_edges = 0;
         *removed_links = 0;
         if (x->n == 0) return;
-        switch (x->W) {
-            case 1: at_edges_impl<1>(ctx, x, ratio, removed_edges, removed_links); break;
-            case 2: at_edges_impl<2>(ctx, x, ratio, removed_edges, removed_links); break;
-            case 3: at_edges_impl<3>(ctx, x, ratio, removed_edges, removed_links); break;
-            case 4: at_edges_impl<4>(ctx, x, ratio, removed_edges, removed_links); break;
-        }
+        dispatch_w(x->W, [&](auto w) {
+            at_edges_impl<decltype(w)::value>(ctx, x, ratio, removed_edges, removed_links);
+        });
     });
 }
 
@@ -318,11 +300,8 @@ extern "C" int bbk_extindex_remove_at_tips(bbk_ctx *ctx, bbk_extindex *x, double
         *removed_kmers = 0;
         *clipped_links = 0;
         if (x->n == 0) return;
-        switch (x->W) {
-            case 1: at_tips_impl<1>(ctx, x, ratio, min_len, max_len, removed_kmers, clipped_links); break;
-            case 2: at_tips_impl<2>(ctx, x, ratio, min_len, max_len, removed_kmers, clipped_links); break;
-            case 3: at_tips_impl<3>(ctx, x, ratio, min_len, max_len, removed_kmers, clipped_links); break;
-            case 4: at_tips_impl<4>(ctx, x, ratio, min_len, max_len, removed_kmers, clipped_links); break;
-        }
+        dispatch_w(x->W, [&](auto w) {
+            at_tips_impl<decltype(w)::value>(ctx, x, ratio, min_len, max_len, removed_kmers, clipped_links);
+        });
     });
 }

@@ -10,6 +10,7 @@
 #include <map>
 #include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -225,6 +226,19 @@ void launch_timed(bbk_ctx *ctx, K fn, const char *name, double bytes, uint32_t g
     check_launch(name);
 }
 
+// The one switch on the key width: f(std::integral_constant<int, W>) for W in 1..4, so the body names its templates
+// with `decltype(w)::value`.  words_of(k) of a legal k is always one of the four.
+template <class F>
+void dispatch_w(unsigned W, F &&f) {
+    switch (W) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", W);
+    }
+}
+
 // Every wait of the host for the context's stream in the counting path goes through here: "stat_host_waits" counts
 // them (the device idles ~20 us around each), so a test can hold the path to its number of decisions
 inline void stream_wait(bbk_ctx *ctx) {
@@ -247,6 +261,20 @@ inline dim3 grid_blocks(uint64_t blocks) {
     constexpr uint64_t kMaxX = 1ull << 21;  // x 1024 threads at most: 2^31 threads in x
     if (blocks <= kMaxX) return dim3((unsigned)(blocks ? blocks : 1));
     return dim3((unsigned)kMaxX, (unsigned)((blocks + kMaxX - 1) / kMaxX));
+}
+
+// One thread per item (or per fixed group of items): n_threads threads in blocks of 256 (grid_blocks), no LDS, the
+// context's stream, then the launch check.  Untimed: a caller that wants the launch in a family of its own uses
+// launch_items_timed, one that times several launches together opens a KernelTimer around them.
+template <class K, class... Args>
+void launch_items(bbk_ctx *ctx, const char *name, K fn, uint64_t n_threads, Args... args) {
+    hipLaunchKernelGGL(fn, grid_blocks((n_threads + 255) / 256), dim3(256), 0, ctx->stream, args...);
+    check_launch(name);
+}
+template <class K, class... Args>
+void launch_items_timed(bbk_ctx *ctx, const char *family, K fn, uint64_t n_threads, Args... args) {
+    KernelTimer t(ctx, family);
+    launch_items(ctx, family, fn, n_threads, args...);
 }
 
 // Large device -> host copy through the context's pinned staging buffers (chunked, two buffers:
@@ -307,9 +335,18 @@ struct ScanSrc {
 // for the stream.
 void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t *const *out, uint64_t n,
                             uint64_t *d_total, bool tail, std::vector<DevBuf> &keep);
-// extindex.hip: the prefix table over an ascending key array that table_find (kmer_ops.h) reads; returns its bits
-unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
-                            bool *wide);
+// extindex.hip: the prefix table over an ascending key array of n records (W words, k-mer size k) that table_find
+// (kmer_ops.h) reads: (1 << bits) + 1 entries, u32 (u64 when `wide`: 2^32 - 2 records or more).  It remembers the W and
+// k it was built for, so table() is the only place that derives the shift a lookup applies to word 0.
+struct PrefixTable;
+struct PrefixIndex {
+    DevBuf buf;
+    unsigned bits = 0;
+    bool wide = false;
+    unsigned W = 0, k = 0;
+    void build(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n);  // waits for the stream
+    PrefixTable table() const;
+};
 // free device memory (see bbk_ctx::mem_free)
 size_t device_free_cached(bbk_ctx *ctx);
 // the context's pinned planning block, at least `bytes` long
@@ -350,7 +387,5 @@ struct bbk_extindex {
     uint64_t instances = 0;
     bbk::DevBuf keys;   // n * W u64 ascending (canonical k-mers)
     bbk::DevBuf masks;  // n u8
-    bbk::DevBuf prefix; // lookup accelerator: (1<<prefix_bits)+1 entries, u32 (u64 when prefix_wide: 2^32-2 k-mers or more)
-    unsigned prefix_bits = 0;
-    bool prefix_wide = false;
+    bbk::PrefixIndex prefix;  // lookup accelerator over keys
 };

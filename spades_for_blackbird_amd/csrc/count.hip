@@ -158,23 +158,9 @@ static void launch_expand(bbk_ctx *ctx, const void *in, const uint32_t *cin, uin
                           uint32_t *cout, bool tag) {
     if (n == 0) return;
     KernelTimer t(ctx, "expand", 3.0 * (double)n * sizeof(Key<W>));
-    if (tag)
-        hipLaunchKernelGGL((k_expand_rc<W, true>), bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream,
-                           (const Key<W> *)in, cin, n, k, (Key<W> *)out, cout);
-    else
-        hipLaunchKernelGGL((k_expand_rc<W, false>), bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream,
-                           (const Key<W> *)in, cin, n, k, (Key<W> *)out, cout);
-    check_launch("k_expand_rc");
+    launch_items(ctx, "k_expand_rc", tag ? k_expand_rc<W, true> : k_expand_rc<W, false>, n, (const Key<W> *)in, cin, n,
+                 k, (Key<W> *)out, cout);
 }
-
-#define BBK_DISPATCH_W(W, ...)                                                   \
-    switch (W) {                                                                 \
-        case 1: { constexpr int W_ = 1; __VA_ARGS__; } break;                           \
-        case 2: { constexpr int W_ = 2; __VA_ARGS__; } break;                           \
-        case 3: { constexpr int W_ = 3; __VA_ARGS__; } break;                           \
-        case 4: { constexpr int W_ = 4; __VA_ARGS__; } break;                           \
-        default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %d", (int)(W)); \
-    }
 
 uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
                         DevBuf &out_vals);
@@ -206,11 +192,7 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
         }
     }
     DevBuf koff((rd->n + 1) * sizeof(uint64_t));
-    if (rd->n) {
-        hipLaunchKernelGGL(k_kmers_per_read, bbk::grid_blocks((rd->n + 255) / 256), dim3(256), 0, ctx->stream,
-                           rd->d_len, rd->n, k, koff.as<uint64_t>());
-        check_launch("k_kmers_per_read");
-    }
+    if (rd->n) launch_items(ctx, "k_kmers_per_read", k_kmers_per_read, rd->n, rd->d_len, rd->n, k, koff.as<uint64_t>());
     const uint64_t N = exclusive_scan_u64(ctx, koff.as<uint64_t>(), koff.as<uint64_t>(), rd->n);
     n_instances = N;
     if (N == 0) {
@@ -228,8 +210,10 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
         vals.alloc(N * 4);
         vtmp.alloc(N * 4);
     }
-    BBK_DISPATCH_W(W, launch_extract<W_>(ctx, rd, koff.as<uint64_t>(), (int)k, keys.p,
-                                         with_mask ? vals.as<uint32_t>() : nullptr, N));
+    dispatch_w(W, [&](auto w) {
+        launch_extract<decltype(w)::value>(ctx, rd, koff.as<uint64_t>(), (int)k, keys.p,
+                                           with_mask ? vals.as<uint32_t>() : nullptr, N);
+    });
     sort_records(ctx, W, keys.p, tmp.p, with_mask ? vals.as<uint32_t>() : nullptr,
                  with_mask ? vtmp.as<uint32_t>() : nullptr, N, key_passes(k));
     // distinct keys land in tmp (sized for the worst case), then are copied to an exact buffer
@@ -486,8 +470,10 @@ static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, cons
         ec.alloc(2 * D * 4);
         ect.alloc(2 * D * 4);
     }
-    BBK_DISPATCH_W(W, launch_expand<W_>(ctx, ckp, wc ? cv->as<uint32_t>() : nullptr, D, (int)k, e.p,
-                                        wc ? ec.as<uint32_t>() : nullptr, false));
+    dispatch_w(W, [&](auto w) {
+        launch_expand<decltype(w)::value>(ctx, ckp, wc ? cv->as<uint32_t>() : nullptr, D, (int)k, e.p,
+                                          wc ? ec.as<uint32_t>() : nullptr, false);
+    });
     sort_records(ctx, W, e.p, et.p, wc ? ec.as<uint32_t>() : nullptr, wc ? ect.as<uint32_t>() : nullptr, 2 * D,
                  key_passes(k));
     const uint64_t D2 = unique_records(ctx, W, e.p, wc ? ec.as<uint32_t>() : nullptr, 2 * D, et.p,
@@ -882,11 +868,11 @@ int bbk_kmerset_verify_order(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t *n_run
         if (s->n < 2) return;
         DevBuf d(8 * 40);
         BBK_HIP(hipMemsetAsync(d.p, 0, 8 * 40, ctx->stream));
-        const uint64_t nblk = (s->n + 255) / 256;
-        BBK_DISPATCH_W(s->W, hipLaunchKernelGGL((k_order_check<W_>), bbk::grid_blocks(nblk), dim3(256), 0, ctx->stream,
-                                                (const Key<W_> *)s->keys.p, s->n,
-                                                (unsigned long long *)d.p));
-        check_launch("k_order_check");
+        dispatch_w(s->W, [&](auto w) {
+            constexpr int W_ = decltype(w)::value;
+            launch_items(ctx, "k_order_check", k_order_check<W_>, s->n, (const Key<W_> *)s->keys.p, s->n,
+                         (unsigned long long *)d.p);
+        });
         unsigned long long h[40];
         BBK_HIP(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
         stream_wait(ctx);
@@ -910,8 +896,11 @@ int bbk_kmerset_bucket_offsets(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t *h_o
             return;
         }
         DevBuf d(17 * 8);
-        BBK_DISPATCH_W(s->W, hipLaunchKernelGGL((k_bucket_bounds<W_>), dim3(1), dim3(64), 0, ctx->stream,
-                                                (const Key<W_> *)s->keys.p, s->n, (unsigned long long *)d.p));
+        dispatch_w(s->W, [&](auto w) {
+            constexpr int W_ = decltype(w)::value;
+            hipLaunchKernelGGL(k_bucket_bounds<W_>, dim3(1), dim3(64), 0, ctx->stream, (const Key<W_> *)s->keys.p, s->n,
+                               (unsigned long long *)d.p);
+        });
         check_launch("k_bucket_bounds");
         unsigned long long h[17];
         BBK_HIP(hipMemcpyAsync(h, d.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));

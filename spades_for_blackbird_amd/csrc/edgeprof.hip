@@ -64,8 +64,6 @@ constexpr uint32_t kEpCanonFw = 1u;   // the canonical key is the forward window
 constexpr uint32_t kEpSelfConj = 2u;  // segment == its reverse complement
 constexpr uint32_t kEpLoop1 = 4u;     // segment is one homopolymer (k+1)-mer linked to itself
 
-unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
-                            bool *wide);
 unsigned unitigs_k(const bbk_unitigs *u);
 
 }  // namespace bbk
@@ -82,9 +80,7 @@ struct bbk_edgeindex {
     bool has_graph = false;              // bases / off / links / kc are kept (bbk_edgeindex_from_gfa_with_graph)
     bbk::DevBuf keys;                    // n * W u64, ascending canonical (k+1)-mers
     bbk::DevBuf pos;                     // n EdgePos
-    bbk::DevBuf prefix;
-    unsigned prefix_bits = 0;
-    bool prefix_wide = false;
+    bbk::PrefixIndex prefix;             // over keys, built for k1
 };
 
 struct bbk_profiles {
@@ -343,18 +339,16 @@ struct HostGraph {
 template <int W>
 static void run_emit(bbk_ctx *ctx, const bbk_reads *sr, const DevBuf &emit_off, const DevBuf &slen, const DevBuf &sflags,
                      uint64_t n_seg, uint64_t n, unsigned k1, DevBuf &keys, DevBuf &idx, DevBuf &pos) {
-    hipLaunchKernelGGL(k_ep_emit<W>, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, sr->d_words, sr->d_woff,
-                       emit_off.as<uint64_t>(), slen.as<uint32_t>(), sflags.as<uint32_t>(), n_seg, n, (int)k1,
-                       keys.as<Key<W>>(), idx.as<uint32_t>(), pos.as<EdgePos>());
-    check_launch("k_ep_emit");
+    launch_items(ctx, "k_ep_emit", k_ep_emit<W>, n, sr->d_words, sr->d_woff, emit_off.as<uint64_t>(),
+                 slen.as<uint32_t>(), sflags.as<uint32_t>(), n_seg, n, (int)k1, keys.as<Key<W>>(), idx.as<uint32_t>(),
+                 pos.as<EdgePos>());
 }
 
 template <int W>
 static void run_gather(bbk_ctx *ctx, const DevBuf &keys, const DevBuf &idx, const DevBuf &pos, uint64_t n, DevBuf &out,
                        DevBuf &dup) {
-    hipLaunchKernelGGL(k_ep_gather<W>, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, keys.as<Key<W>>(),
-                       idx.as<uint32_t>(), pos.as<EdgePos>(), n, out.as<EdgePos>(), dup.as<unsigned long long>());
-    check_launch("k_ep_gather");
+    launch_items(ctx, "k_ep_gather", k_ep_gather<W>, n, keys.as<Key<W>>(), idx.as<uint32_t>(), pos.as<EdgePos>(), n,
+                 out.as<EdgePos>(), dup.as<unsigned long long>());
 }
 
 // the index of a graph held on the host, checked as the position-local form needs
@@ -460,24 +454,15 @@ static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g, bool k
     ix->pos.alloc(n * sizeof(EdgePos));
     {
         KernelTimer t(ctx, "edgeindex", (double)n * (W * 8 + sizeof(EdgePos) + 4));
-        switch (W) {
-            case 1: run_emit<1>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
-            case 2: run_emit<2>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
-            case 3: run_emit<3>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
-            case 4: run_emit<4>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos); break;
-            default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", W);
-        }
+        dispatch_w(W, [&](auto w) {
+            run_emit<decltype(w)::value>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos);
+        });
     }
     sort_records(ctx, (int)W, ix->keys.p, tmp.p, idx.as<uint32_t>(), idx_tmp.as<uint32_t>(), n, key_passes(k1));
     BBK_HIP(hipMemsetAsync(dup.p, 0xFF, 8, ctx->stream));
     {
         KernelTimer t(ctx, "edgeindex", (double)n * (2 * W * 8 + 2 * sizeof(EdgePos) + 4));
-        switch (W) {
-            case 1: run_gather<1>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
-            case 2: run_gather<2>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
-            case 3: run_gather<3>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
-            default: run_gather<4>(ctx, ix->keys, idx, pos, n, ix->pos, dup); break;
-        }
+        dispatch_w(W, [&](auto w) { run_gather<decltype(w)::value>(ctx, ix->keys, idx, pos, n, ix->pos, dup); });
     }
     uint64_t first_dup = ~0ull;
     BBK_HIP(hipMemcpyAsync(&first_dup, dup.p, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -490,7 +475,7 @@ static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g, bool k
                     "reverse complement); the mapping needs every (k+1)-mer of the graph once",
                     ix->names[two[0].seg].c_str(), two[0].off_fw, ix->names[two[1].seg].c_str(), two[1].off_fw, k1);
     }
-    ix->prefix_bits = build_prefix_index(ctx, ix->keys.as<uint64_t>(), W, k1, n, ix->prefix, &ix->prefix_wide);
+    ix->prefix.build(ctx, ix->keys.as<uint64_t>(), W, k1, n);
     return ix.release();
 }
 
@@ -616,14 +601,12 @@ static void d2h_sync(bbk_ctx *ctx, void *dst, const void *src, size_t bytes) {
 template <int W>
 static void run_map(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix,
                     bbk_profiles *p, unsigned sample) {
-    const int w0bits = (W == 1) ? (int)(2 * ix->k1) : 64;
     const uint64_t waves = (total + kMapStep - 1) / kMapStep;
     // bytes the lookups need at the least: one prefix entry, the key and the record per position
     KernelTimer t(ctx, "edgeprof_map", (double)total * (8.0 * W + sizeof(EdgePos) + 4));
     hipLaunchKernelGGL(k_ep_map<W>, grid_blocks((waves + kMapWaves - 1) / kMapWaves), dim3(64 * kMapWaves), 0, ctx->stream,
                        r->d_words, r->d_woff, r->d_len, pos_off.as<uint64_t>(), r->n, total, (int)ix->k1,
-                       ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(),
-                       PrefixTable{ix->prefix.p, w0bits - (int)ix->prefix_bits, ix->prefix_wide ? 1 : 0},
+                       ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(), ix->prefix.table(),
                        p->raw.as<unsigned long long>(), p->samples, sample);
     check_launch("k_ep_map");
 }
@@ -632,9 +615,8 @@ static void run_map(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uin
 template <int W>
 static void run_paths(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix,
                       uint64_t *wave_cnt, bbk_path_range *out) {
-    const int w0bits = (W == 1) ? (int)(2 * ix->k1) : 64;
     const uint64_t waves = (total + kMapStep - 1) / kMapStep;
-    const PrefixTable P{ix->prefix.p, w0bits - (int)ix->prefix_bits, ix->prefix_wide ? 1 : 0};
+    const PrefixTable P = ix->prefix.table();
     const dim3 grid = grid_blocks((waves + kMapWaves - 1) / kMapWaves), block(64 * kMapWaves);
     // the lookups' bytes as for k_ep_map; each pass runs them
     KernelTimer t(ctx, out ? "gmap_write" : "gmap_count", (double)total * (8.0 * W + sizeof(EdgePos) + 4));
@@ -734,18 +716,11 @@ int bbk_profiles_push_reads(bbk_profiles *p, unsigned sample, const bbk_reads *r
         const uint64_t n = reads->n;
         if (n == 0 || ix->n == 0) return;
         DevBuf pos_off((n + 1) * 8);
-        hipLaunchKernelGGL(k_ep_npos, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, reads->d_len, n, ix->k1,
-                           pos_off.as<uint64_t>());
-        check_launch("k_ep_npos");
+        launch_items(ctx, "k_ep_npos", k_ep_npos, n, reads->d_len, n, ix->k1, pos_off.as<uint64_t>());
         const uint64_t total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
         if (total == 0) return;
         BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
-        switch (ix->W) {
-            case 1: run_map<1>(ctx, reads, pos_off, total, ix, p, sample); break;
-            case 2: run_map<2>(ctx, reads, pos_off, total, ix, p, sample); break;
-            case 3: run_map<3>(ctx, reads, pos_off, total, ix, p, sample); break;
-            default: run_map<4>(ctx, reads, pos_off, total, ix, p, sample); break;
-        }
+        dispatch_w(ix->W, [&](auto w) { run_map<decltype(w)::value>(ctx, reads, pos_off, total, ix, p, sample); });
         BBK_HIP(hipStreamSynchronize(ctx->stream));  // pos_off and the staged total are released on return
     });
 }
@@ -811,21 +786,16 @@ int bbk_edgeindex_map_paths(bbk_ctx *ctx, const bbk_edgeindex *ix, const bbk_rea
         p->n_reads = n;
         if (n > 0 && ix->n > 0) {
             DevBuf pos_off((n + 1) * 8);
-            hipLaunchKernelGGL(k_ep_npos, grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, reads->d_len, n, ix->k1,
-                               pos_off.as<uint64_t>());
-            check_launch("k_ep_npos");
+            launch_items(ctx, "k_ep_npos", k_ep_npos, n, reads->d_len, n, ix->k1, pos_off.as<uint64_t>());
             const uint64_t total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
             if (total > 0) {
                 BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
                 const uint64_t waves = (total + kMapStep - 1) / kMapStep;
                 DevBuf wave_cnt(waves * 8);
                 auto run = [&](bbk_path_range *o) {
-                    switch (ix->W) {
-                        case 1: run_paths<1>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
-                        case 2: run_paths<2>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
-                        case 3: run_paths<3>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
-                        default: run_paths<4>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o); break;
-                    }
+                    dispatch_w(ix->W, [&](auto w) {
+                        run_paths<decltype(w)::value>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o);
+                    });
                 };
                 run(nullptr);
                 p->n_ranges = exclusive_scan_u64(ctx, wave_cnt.as<uint64_t>(), wave_cnt.as<uint64_t>(), waves);

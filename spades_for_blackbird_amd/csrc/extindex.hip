@@ -52,38 +52,34 @@ bool index_is_wide(uint64_t n) {
     return n >= (1ull << 32) - 2 || getenv("BBK_WIDE_INDEX") != nullptr;  // read per call: tests switch it inside a process
 }
 
-// Prefix table over an ascending key array: ~8 keys per bin; word 0 holds min(2k, 64) populated bits.
-// Returns the number of prefix bits; lookups shift word 0 right by (w0bits - bits).  *wide: the entries are u64.
-unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
-                            bool *wide) {
-    const int w0bits = (W == 1) ? (int)(2 * k) : 64;
+// word 0 of a key holds min(2k, 64) populated bits
+static int w0bits(unsigned W, unsigned k) { return W == 1 ? (int)(2 * k) : 64; }
+
+// ~8 keys per bin; lookups shift word 0 right by (w0bits - bits)
+void PrefixIndex::build(bbk_ctx *ctx, const uint64_t *keys, unsigned W_, unsigned k_, uint64_t n) {
+    W = W_;
+    k = k_;
     const int max_bits = n > (1ull << 27) ? 30 : 24;
-    int bits = 4;
-    while (bits < max_bits && (1ull << (bits + 3)) < n) ++bits;
-    bits = std::min(bits, w0bits);
+    int b = 4;
+    while (b < max_bits && (1ull << (b + 3)) < n) ++b;
+    bits = (unsigned)std::min(b, w0bits(W, k));
     const uint64_t nbins = 1ull << bits;
-    *wide = index_is_wide(n);
-    const size_t esz = *wide ? sizeof(uint64_t) : sizeof(uint32_t);
-    prefix.alloc(((size_t)nbins + 1) * esz);
+    wide = index_is_wide(n);
+    const size_t esz = wide ? sizeof(uint64_t) : sizeof(uint32_t);
+    buf.alloc(((size_t)nbins + 1) * esz);
     if (n == 0) {
-        BBK_HIP(hipMemsetAsync(prefix.p, 0, ((size_t)nbins + 1) * esz, ctx->stream));
+        BBK_HIP(hipMemsetAsync(buf.p, 0, ((size_t)nbins + 1) * esz, ctx->stream));
+    } else if (wide) {
+        launch_items(ctx, "k_prefix_table", k_prefix_table<uint64_t>, n, keys, (int)W, n, w0bits(W, k) - (int)bits,
+                     nbins, buf.as<uint64_t>());
     } else {
-        const uint64_t nblk = (n + 255) / 256;
-        if (*wide)
-            hipLaunchKernelGGL(k_prefix_table<uint64_t>, bbk::grid_blocks(nblk), dim3(256), 0, ctx->stream, keys, (int)W, n,
-                               w0bits - bits, nbins, prefix.as<uint64_t>());
-        else
-            hipLaunchKernelGGL(k_prefix_table<uint32_t>, bbk::grid_blocks(nblk), dim3(256), 0, ctx->stream, keys, (int)W, n,
-                               w0bits - bits, nbins, prefix.as<uint32_t>());
-        check_launch("k_prefix_table");
+        launch_items(ctx, "k_prefix_table", k_prefix_table<uint32_t>, n, keys, (int)W, n, w0bits(W, k) - (int)bits,
+                     nbins, buf.as<uint32_t>());
     }
     BBK_HIP(hipStreamSynchronize(ctx->stream));
-    return (unsigned)bits;
 }
 
-void build_prefix_table(bbk_ctx *ctx, bbk_extindex *x) {
-    x->prefix_bits = build_prefix_index(ctx, x->keys.as<uint64_t>(), x->W, x->k, x->n, x->prefix, &x->prefix_wide);
-}
+PrefixTable PrefixIndex::table() const { return PrefixTable{buf.p, w0bits(W, k) - (int)bits, wide ? 1 : 0}; }
 
 // the accumulated (canonical k-mer, OR of mask bits) records -> the index: ascending keys, one InOutMask byte each
 static bbk_extindex *finish_extindex(Accum &acc) {
@@ -112,7 +108,7 @@ static bbk_extindex *finish_extindex(Accum &acc) {
                            x->masks.as<uint8_t>());
         check_launch("k_u32_to_u8");
     }
-    build_prefix_table(ctx, x.get());
+    x->prefix.build(ctx, x->keys.as<uint64_t>(), x->W, x->k, x->n);
     return x.release();
 }
 
@@ -173,9 +169,7 @@ int bbk_extindex_export_u32(bbk_ctx *ctx, const bbk_extindex *x, void *dst_keys,
         if (dst_keys) BBK_HIP(bbk::copy_async(dst_keys, x->keys.p, x->n * x->W * 8, hipMemcpyDefault, ctx->stream));
         if (dst_masks_u32) {
             DevBuf m(x->n * 4);
-            hipLaunchKernelGGL(k_u8_to_u32, bbk::grid_blocks((x->n + 255) / 256), dim3(256), 0, ctx->stream,
-                               x->masks.as<uint8_t>(), x->n, m.as<uint32_t>());
-            check_launch("k_u8_to_u32");
+            launch_items(ctx, "k_u8_to_u32", k_u8_to_u32, x->n, x->masks.as<uint8_t>(), x->n, m.as<uint32_t>());
             BBK_HIP(bbk::copy_async(dst_masks_u32, m.p, x->n * 4, hipMemcpyDefault, ctx->stream));
             BBK_HIP(hipStreamSynchronize(ctx->stream));
         }

@@ -26,6 +26,10 @@ struct TipTable {
     uint64_t n;
 };
 
+inline TipTable tip_table(const bbk_extindex *x) {
+    return TipTable{x->keys.p, x->masks.as<uint8_t>(), x->prefix.table(), (int)x->k, x->n};
+}
+
 template <int W>
 __device__ inline uint64_t tt_find(const TipTable &T, const Key<W> &q) {
     return table_find<W>(reinterpret_cast<const Key<W> *>(T.keys), T.P, q);

@@ -195,13 +195,6 @@ __global__ __launch_bounds__(256) void k_hc_pairs(const uint32_t *__restrict__ l
     val[i] = (uint32_t)i;
 }
 
-template <class... P, class... A>
-static void hc_launch(bbk_ctx *ctx, const char *family, void (*fn)(P...), uint64_t threads, A... args) {
-    KernelTimer t(ctx, family);
-    hipLaunchKernelGGL(fn, grid_blocks((threads + 255) / 256), dim3(256), 0, ctx->stream, args...);
-    check_launch(family);
-}
-
 // ---- the host replay of the oversize components (hamcluster.cpp:213-276 over adt/concurrent_dsu.hpp:46-133) ----------
 namespace {
 
@@ -301,43 +294,41 @@ static bbk_hamclusters *hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *s, uin
     }
     const unsigned k = s->k;
     const uint64_t *keys = s->keys.as<uint64_t>();
-    DevBuf prefix, rcidx(n * 4), status(16);
-    bool wide = false;
-    const unsigned pbits = build_prefix_index(ctx, keys, 1, k, n, prefix, &wide);
-    const PrefixTable P{prefix.p, (int)(2 * k) - (int)pbits, wide ? 1 : 0};
+    DevBuf rcidx(n * 4), status(16);
+    PrefixIndex prefix;
+    prefix.build(ctx, keys, 1, k, n);
     h->labels.alloc(n * 4);
     uint32_t *label = h->labels.as<uint32_t>();
     BBK_HIP(hipMemsetAsync(status.p, 0, 16, ctx->stream));
-    hc_launch(ctx, "hc_rcidx", k_hc_rcidx, n, (const Key<1> *)s->keys.as<Key<1>>(), n, (int)k, P, rcidx.as<uint32_t>(), label,
-              status.as<uint32_t>());
+    launch_items_timed(ctx, "hc_rcidx", k_hc_rcidx, n, s->keys.as<Key<1>>(), n, (int)k, prefix.table(),
+                       rcidx.as<uint32_t>(), label, status.as<uint32_t>());
     uint32_t h_status[2] = {0, 0};
     BBK_HIP(hipMemcpyAsync(h_status, status.p, 4, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipStreamSynchronize(ctx->stream));
     BBK_REQUIRE(h_status[0] == 0, BBK_ERR_ARG,
                 "bbk_kmerset_hamming_clusters: the set is not closed under reverse complement (it must be a "
                 "BBK_BOTH_STRANDS set)");
-    prefix.release();
+    prefix.buf.release();
     {
         const int shift = 2 * (int)(k - k / 2);
         KernelTimer t(ctx, "hc_scan");
         hipLaunchKernelGGL(k_hc_scan, grid_blocks((n + kHcTile - 1) / kHcTile), dim3(kHcTile), 0, ctx->stream, keys, n, shift,
-                           (const uint32_t *)rcidx.as<uint32_t>(), label, status.as<uint32_t>());
+                           rcidx.as<uint32_t>(), label, status.as<uint32_t>());
         check_launch("hc_scan");
     }
     // pointer jumping: a round that changes nothing ends it; the device decides, the host reads the flag
     uint64_t rounds = 0;
     for (uint32_t changed = 1; changed;) {
         BBK_HIP(hipMemsetAsync(status.as<uint32_t>() + 2, 0, 4, ctx->stream));
-        hc_launch(ctx, "hc_jump", k_hc_jump, n, label, n, status.as<uint32_t>() + 2);
+        launch_items_timed(ctx, "hc_jump", k_hc_jump, n, label, n, status.as<uint32_t>() + 2);
         BBK_HIP(hipMemcpyAsync(&changed, status.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
         BBK_HIP(hipStreamSynchronize(ctx->stream));
         ++rounds;
     }
     DevBuf cnt(n * 4), off(n * 8 + 16);
     BBK_HIP(hipMemsetAsync(cnt.p, 0, n * 4, ctx->stream));
-    hc_launch(ctx, "hc_list", k_hc_count, n, (const uint32_t *)label, n, cnt.as<uint32_t>());
-    hc_launch(ctx, "hc_list", k_hc_flag_over, n, (const uint32_t *)label, (const uint32_t *)cnt.as<uint32_t>(), n, lock_size,
-              off.as<uint64_t>());
+    launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, cnt.as<uint32_t>());
+    launch_items_timed(ctx, "hc_list", k_hc_flag_over, n, label, cnt.as<uint32_t>(), n, lock_size, off.as<uint64_t>());
     BBK_HIP(hipMemcpyAsync(h_status, status.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     const uint64_t R = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), n);
     ctx->add_stat("stat_hc_largest_block", (double)h_status[1]);
@@ -345,9 +336,9 @@ static bbk_hamclusters *hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *s, uin
     h->replayed = R;
     if (R) {
         DevBuf oi(R * 4), ok(R * 8), orc(R * 4);
-        hc_launch(ctx, "hc_list", k_hc_compact_over, n, (const uint32_t *)label, (const uint32_t *)cnt.as<uint32_t>(), n,
-                  lock_size, (const uint64_t *)off.as<uint64_t>(), keys, (const uint32_t *)rcidx.as<uint32_t>(),
-                  oi.as<uint32_t>(), ok.as<uint64_t>(), orc.as<uint32_t>());
+        launch_items_timed(ctx, "hc_list", k_hc_compact_over, n, label, cnt.as<uint32_t>(), n, lock_size,
+                           off.as<uint64_t>(), keys, rcidx.as<uint32_t>(), oi.as<uint32_t>(), ok.as<uint64_t>(),
+                           orc.as<uint32_t>());
         std::vector<uint32_t> h_idx(R), h_rc(R), h_lab;
         std::vector<uint64_t> h_key(R);
         BBK_HIP(hipMemcpyAsync(h_idx.data(), oi.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -356,25 +347,24 @@ static bbk_hamclusters *hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *s, uin
         BBK_HIP(hipStreamSynchronize(ctx->stream));
         hc_replay(k, lock_size, chunk, h_idx, h_key, h_rc, h_lab);
         BBK_HIP(hipMemcpyAsync(orc.p, h_lab.data(), R * 4, hipMemcpyHostToDevice, ctx->stream));
-        hc_launch(ctx, "hc_list", k_hc_relabel, R, (const uint32_t *)oi.as<uint32_t>(), (const uint32_t *)orc.as<uint32_t>(), R,
-                  label);
+        launch_items_timed(ctx, "hc_list", k_hc_relabel, R, oi.as<uint32_t>(), orc.as<uint32_t>(), R, label);
         BBK_HIP(hipMemsetAsync(cnt.p, 0, n * 4, ctx->stream));
-        hc_launch(ctx, "hc_list", k_hc_count, n, (const uint32_t *)label, n, cnt.as<uint32_t>());
+        launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, cnt.as<uint32_t>());
         BBK_HIP(hipStreamSynchronize(ctx->stream));  // h_lab is read by the copy above
     }
     rcidx.release();
-    hc_launch(ctx, "hc_list", k_hc_flag_roots, n, (const uint32_t *)label, n, off.as<uint64_t>());
+    launch_items_timed(ctx, "hc_list", k_hc_flag_roots, n, label, n, off.as<uint64_t>());
     h->clusters = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), n);
     h->sizes.alloc(h->clusters * 8);
-    hc_launch(ctx, "hc_list", k_hc_sizes, n, (const uint32_t *)label, (const uint32_t *)cnt.as<uint32_t>(),
-              (const uint64_t *)off.as<uint64_t>(), n, h->sizes.as<uint64_t>());
+    launch_items_timed(ctx, "hc_list", k_hc_sizes, n, label, cnt.as<uint32_t>(), off.as<uint64_t>(), n,
+                       h->sizes.as<uint64_t>());
     BBK_HIP(hipStreamSynchronize(ctx->stream));
     cnt.release();
     off.release();
     // the listing: (label, index) records ordered by label; the sort is stable, so a cluster's members ascend
     h->members.alloc(n * 4);
     DevBuf ka(n * 8), kb(n * 8), vb(n * 4);
-    hc_launch(ctx, "hc_list", k_hc_pairs, n, (const uint32_t *)label, n, ka.as<uint64_t>(), h->members.as<uint32_t>());
+    launch_items_timed(ctx, "hc_list", k_hc_pairs, n, label, n, ka.as<uint64_t>(), h->members.as<uint32_t>());
     unsigned bits = 1;
     while (bits < 32 && ((n - 1) >> bits)) ++bits;
     sort_records(ctx, 1, ka.p, kb.p, h->members.as<uint32_t>(), vb.as<uint32_t>(), n, key_passes((bits + 1) / 2));

@@ -34,20 +34,13 @@
 #include "bbk_internal.h"
 #include "kmer_ops.h"
 
-namespace bbk {
-unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
-                            bool *wide);
-}
-
 struct bbk_kmerprofile {
     unsigned k = 0, W = 0, N = 0;
     uint64_t n = 0;          // kept k-mers
     uint32_t max_value = 0;  // upper bound of every row value (cs, or the maximum of a loaded file)
     bbk::DevBuf keys;        // n * W u64, ascending canonical k-mers
     bbk::DevBuf rows;        // n * N u16, sample-major inside a row
-    bbk::DevBuf prefix;
-    unsigned prefix_bits = 0;
-    bool prefix_wide = false;
+    bbk::PrefixIndex prefix;  // over keys
 };
 
 struct bbk_kmerprofile_builder {
@@ -62,20 +55,6 @@ struct bbk_kmerprofile_builder {
 };
 
 namespace bbk {
-
-#define BBK_KP_DISPATCH_W(W, expr)                                                        \
-    switch (W) {                                                                          \
-        case 1: { constexpr int W_ = 1; expr; } break;                                    \
-        case 2: { constexpr int W_ = 2; expr; } break;                                    \
-        case 3: { constexpr int W_ = 3; expr; } break;                                    \
-        case 4: { constexpr int W_ = 4; expr; } break;                                    \
-        default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", (unsigned)(W)); \
-    }
-
-static PrefixTable prefix_of(const DevBuf &prefix, unsigned bits, bool wide, unsigned W, unsigned k) {
-    const int w0bits = (W == 1) ? (int)(2 * k) : 64;
-    return PrefixTable{prefix.p, w0bits - (int)bits, wide ? 1 : 0};
-}
 
 // ---- join ---------------------------------------------------------------------------------------------------------------
 
@@ -329,15 +308,8 @@ __global__ __launch_bounds__(256) void k_ab_reduce(const uint16_t *__restrict__ 
     }
 }
 
-template <class... P, class... A>
-static void launch(bbk_ctx *ctx, const char *family, void (*fn)(P...), uint64_t threads, A... args) {
-    KernelTimer t(ctx, family);
-    hipLaunchKernelGGL(fn, grid_blocks((threads + 255) / 256), dim3(256), 0, ctx->stream, args...);
-    check_launch(family);
-}
-
 static void build_profile_index(bbk_ctx *ctx, bbk_kmerprofile *p) {
-    p->prefix_bits = build_prefix_index(ctx, p->keys.as<uint64_t>(), p->W, p->k, p->n, p->prefix, &p->prefix_wide);
+    p->prefix.build(ctx, p->keys.as<uint64_t>(), p->W, p->k, p->n);
 }
 
 static void check_sample_set(const bbk_kmerset *s, const char *who) {
@@ -359,15 +331,18 @@ static void add_sample(bbk_kmerprofile_builder *b, unsigned sample, const bbk_km
     if (s->n == 0) return;
     const size_t rec = (size_t)b->W * 8;
     DevBuf off(s->n * 8 + 16);
-    launch(ctx, "kp_filter", k_kp_sample_flag, s->n, (const uint32_t *)s->counts.as<uint32_t>(), s->n, (uint32_t)b->ci,
-           off.as<uint64_t>());
+    launch_items_timed(ctx, "kp_filter", k_kp_sample_flag, s->n, s->counts.as<uint32_t>(), s->n, (uint32_t)b->ci,
+                       off.as<uint64_t>());
     const uint64_t kept = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), s->n);
     if (kept == 0) return;
     S.keys.alloc(kept * rec);
     S.vals.alloc(kept * 2);
-    BBK_KP_DISPATCH_W(b->W, launch(ctx, "kp_filter", k_kp_sample_compact<W_>, s->n, (const Key<W_> *)s->keys.as<Key<W_>>(),
-                                   (const uint32_t *)s->counts.as<uint32_t>(), s->n, (uint32_t)b->ci, (uint32_t)b->cs,
-                                   (const uint64_t *)off.as<uint64_t>(), S.keys.as<Key<W_>>(), S.vals.as<uint16_t>()));
+    dispatch_w(b->W, [&](auto w) {
+        constexpr int W_ = decltype(w)::value;
+        launch_items_timed(ctx, "kp_filter", k_kp_sample_compact<W_>, s->n, s->keys.as<Key<W_>>(),
+                           s->counts.as<uint32_t>(), s->n, (uint32_t)b->ci, (uint32_t)b->cs, off.as<uint64_t>(),
+                           S.keys.as<Key<W_>>(), S.vals.as<uint16_t>());
+    });
     BBK_HIP(hipStreamSynchronize(ctx->stream));
     S.n = kept;
 }
@@ -411,19 +386,20 @@ static bbk_kmerprofile *finish_profile(bbk_kmerprofile_builder *b, uint64_t min_
         build_profile_index(ctx, p.get());
         return p.release();
     }
-    DevBuf uprefix;
-    bool uwide = false;
-    const unsigned ubits = build_prefix_index(ctx, ukeys.as<uint64_t>(), W, b->k, U, uprefix, &uwide);
-    const PrefixTable UP = prefix_of(uprefix, ubits, uwide, W, b->k);
+    PrefixIndex uprefix;
+    uprefix.build(ctx, ukeys.as<uint64_t>(), W, b->k, U);
+    const PrefixTable UP = uprefix.table();
     DevBuf rows(U * (uint64_t)N * 2 + 16), err(16);
     BBK_HIP(hipMemsetAsync(rows.p, 0, U * (uint64_t)N * 2, ctx->stream));
     BBK_HIP(hipMemsetAsync(err.p, 0, 4, ctx->stream));
     for (unsigned s = 0; s < N; ++s) {
         auto &S = b->samples[s];
         if (!S.n) continue;
-        BBK_KP_DISPATCH_W(W, launch(ctx, "kp_scatter", k_kp_scatter<W_>, S.n, (const Key<W_> *)S.keys.as<Key<W_>>(),
-                                    (const uint16_t *)S.vals.as<uint16_t>(), S.n, (const Key<W_> *)ukeys.as<Key<W_>>(), UP,
-                                    N, s, rows.as<uint16_t>(), err.as<uint32_t>()));
+        dispatch_w(W, [&](auto w) {
+            constexpr int W_ = decltype(w)::value;
+            launch_items_timed(ctx, "kp_scatter", k_kp_scatter<W_>, S.n, S.keys.as<Key<W_>>(), S.vals.as<uint16_t>(),
+                               S.n, ukeys.as<Key<W_>>(), UP, N, s, rows.as<uint16_t>(), err.as<uint32_t>());
+        });
     }
     uint32_t h_err = 0;
     BBK_HIP(hipMemcpyAsync(&h_err, err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -434,16 +410,18 @@ static bbk_kmerprofile *finish_profile(bbk_kmerprofile_builder *b, uint64_t min_
         S.vals.release();
     }
     DevBuf keep(U + 16), off(U * 8 + 16);
-    launch(ctx, "kp_keep", k_kp_keep, U, (const uint16_t *)rows.as<uint16_t>(), U, N, min_samples, min_mult,
-           keep.as<uint8_t>(), off.as<uint64_t>());
+    launch_items_timed(ctx, "kp_keep", k_kp_keep, U, rows.as<uint16_t>(), U, N, min_samples, min_mult,
+                       keep.as<uint8_t>(), off.as<uint64_t>());
     const uint64_t kept = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), U);
     p->n = kept;
     p->keys.alloc(kept * rec);
     p->rows.alloc(kept * (uint64_t)N * 2);
     if (kept) {
-        BBK_KP_DISPATCH_W(W, launch(ctx, "kp_compact", k_kp_compact<W_>, U, (const Key<W_> *)ukeys.as<Key<W_>>(),
-                                    (const uint16_t *)rows.as<uint16_t>(), U, N, (const uint8_t *)keep.as<uint8_t>(),
-                                    (const uint64_t *)off.as<uint64_t>(), p->keys.as<Key<W_>>(), p->rows.as<uint16_t>()));
+        dispatch_w(W, [&](auto w) {
+            constexpr int W_ = decltype(w)::value;
+            launch_items_timed(ctx, "kp_compact", k_kp_compact<W_>, U, ukeys.as<Key<W_>>(), rows.as<uint16_t>(), U, N,
+                               keep.as<uint8_t>(), off.as<uint64_t>(), p->keys.as<Key<W_>>(), p->rows.as<uint16_t>());
+        });
         BBK_HIP(hipStreamSynchronize(ctx->stream));
     }
     build_profile_index(ctx, p.get());
@@ -468,8 +446,8 @@ static void abundance(bbk_ctx *ctx, const bbk_kmerprofile *p, const bbk_reads *p
     const uint64_t *d_first = h_first ? first.as<uint64_t>() : nullptr;
     DevBuf pos(nc * 8 + 16), off(nc * 8 + 16), err(16);
     BBK_HIP(hipMemsetAsync(err.p, 0, 4, ctx->stream));
-    launch(ctx, "ab_collect", k_ab_positions, nc, pieces->d_len, d_first, nc, (uint32_t)p->k, pos.as<uint64_t>(),
-           err.as<uint32_t>());
+    launch_items_timed(ctx, "ab_collect", k_ab_positions, nc, pieces->d_len, d_first, nc, (uint32_t)p->k,
+                       pos.as<uint64_t>(), err.as<uint32_t>());
     uint32_t h_err = 0;
     BBK_HIP(hipMemcpyAsync(h_positions, pos.p, nc * 8, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipMemcpyAsync(&h_err, err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -480,19 +458,16 @@ static void abundance(bbk_ctx *ctx, const bbk_kmerprofile *p, const bbk_reads *p
     memset(h_sumsq, 0, nc * (size_t)N * 8);
     if (p->n == 0 || total == 0) return;
     DevBuf found(total * 8 + 16), dn(nc * 8 + 16), dsum(nc * (uint64_t)N * 8 + 16), dsq(nc * (uint64_t)N * 8 + 16);
-    const PrefixTable P = prefix_of(p->prefix, p->prefix_bits, p->prefix_wide, p->W, p->k);
-    BBK_KP_DISPATCH_W(p->W, launch(ctx, "ab_collect", k_ab_collect<W_>, nc * 64, pieces->d_words, pieces->d_woff,
-                                   pieces->d_len, d_first, nc, (int)p->k, (const Key<W_> *)p->keys.as<Key<W_>>(), P,
-                                   (const uint64_t *)off.as<uint64_t>(), found.as<uint64_t>(), dn.as<uint64_t>()));
+    dispatch_w(p->W, [&](auto w) {
+        constexpr int W_ = decltype(w)::value;
+        launch_items_timed(ctx, "ab_collect", k_ab_collect<W_>, nc * 64, pieces->d_words, pieces->d_woff, pieces->d_len,
+                           d_first, nc, (int)p->k, p->keys.as<Key<W_>>(), p->prefix.table(), off.as<uint64_t>(),
+                           found.as<uint64_t>(), dn.as<uint64_t>());
+    });
     const uint64_t waves = nc * (uint64_t)N;
-    if (p->max_value > 255)
-        launch(ctx, "ab_reduce", k_ab_reduce<true>, waves * 64, (const uint16_t *)p->rows.as<uint16_t>(), N,
-               (const uint64_t *)found.as<uint64_t>(), (const uint64_t *)off.as<uint64_t>(),
-               (const uint64_t *)dn.as<uint64_t>(), nc, dsum.as<uint64_t>(), dsq.as<uint64_t>());
-    else
-        launch(ctx, "ab_reduce", k_ab_reduce<false>, waves * 64, (const uint16_t *)p->rows.as<uint16_t>(), N,
-               (const uint64_t *)found.as<uint64_t>(), (const uint64_t *)off.as<uint64_t>(),
-               (const uint64_t *)dn.as<uint64_t>(), nc, dsum.as<uint64_t>(), dsq.as<uint64_t>());
+    launch_items_timed(ctx, "ab_reduce", p->max_value > 255 ? k_ab_reduce<true> : k_ab_reduce<false>, waves * 64,
+                       p->rows.as<uint16_t>(), N, found.as<uint64_t>(), off.as<uint64_t>(), dn.as<uint64_t>(), nc,
+                       dsum.as<uint64_t>(), dsq.as<uint64_t>());
     BBK_HIP(hipMemcpyAsync(h_n, dn.p, nc * 8, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipMemcpyAsync(h_sum, dsum.p, waves * 8, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipMemcpyAsync(h_sumsq, dsq.p, waves * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -17,9 +17,6 @@
 
 namespace bbk {
 
-unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
-                            bool *wide);
-
 // one wavefront per read, lanes over its k-mer positions
 template <int W>
 __global__ __launch_bounds__(256) void k_median_filter(const uint64_t *__restrict__ words, const uint64_t *__restrict__ woff,
@@ -53,15 +50,10 @@ __global__ __launch_bounds__(256) void k_median_filter(const uint64_t *__restric
 
 template <int W>
 static void median_filter_impl(bbk_ctx *ctx, const bbk_reads *rd, const bbk_kmerset *s, uint32_t threshold, uint8_t *d_keep) {
-    DevBuf prefix;
-    bool wide = false;
-    const unsigned bits = build_prefix_index(ctx, s->keys.as<uint64_t>(), s->W, s->k, s->n, prefix, &wide);
-    const int w0bits = (W == 1) ? (int)(2 * s->k) : 64;
-    const uint64_t threads = rd->n * 64;
-    hipLaunchKernelGGL(k_median_filter<W>, bbk::grid_blocks((threads + 255) / 256), dim3(256), 0, ctx->stream, rd->d_words,
-                       rd->d_woff, rd->d_len, rd->n, (int)s->k, s->keys.as<Key<W>>(), s->counts.as<uint32_t>(),
-                       PrefixTable{prefix.p, w0bits - (int)bits, wide ? 1 : 0}, threshold, d_keep);
-    check_launch("k_median_filter");
+    PrefixIndex prefix;
+    prefix.build(ctx, s->keys.as<uint64_t>(), s->W, s->k, s->n);
+    launch_items(ctx, "k_median_filter", k_median_filter<W>, rd->n * 64, rd->d_words, rd->d_woff, rd->d_len, rd->n,
+                 (int)s->k, s->keys.as<Key<W>>(), s->counts.as<uint32_t>(), prefix.table(), threshold, d_keep);
     BBK_HIP(hipStreamSynchronize(ctx->stream));
 }
 
@@ -84,13 +76,9 @@ extern "C" int bbk_reads_median_filter(bbk_ctx *ctx, const bbk_reads *reads, con
         if (counts->n == 0) {
             BBK_HIP(hipMemsetAsync(keep.p, threshold == 0 ? 1 : 0, reads->n, ctx->stream));
         } else {
-            switch (counts->W) {
-                case 1: median_filter_impl<1>(ctx, reads, counts, threshold, keep.as<uint8_t>()); break;
-                case 2: median_filter_impl<2>(ctx, reads, counts, threshold, keep.as<uint8_t>()); break;
-                case 3: median_filter_impl<3>(ctx, reads, counts, threshold, keep.as<uint8_t>()); break;
-                case 4: median_filter_impl<4>(ctx, reads, counts, threshold, keep.as<uint8_t>()); break;
-                default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", counts->W);
-            }
+            dispatch_w(counts->W, [&](auto w) {
+                median_filter_impl<decltype(w)::value>(ctx, reads, counts, threshold, keep.as<uint8_t>());
+            });
         }
         BBK_HIP(hipMemcpyAsync(h_keep, keep.p, reads->n, hipMemcpyDeviceToHost, ctx->stream));
         BBK_HIP(hipStreamSynchronize(ctx->stream));

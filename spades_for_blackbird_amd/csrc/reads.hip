@@ -345,14 +345,12 @@ int bbk_reads_from_packed(bbk_ctx *ctx, const uint64_t *h_words, uint64_t n_word
         uint64_t total_words = 0, bases = 0;
         if (n_reads) {
             // word offsets and the base count come from the lengths, on the device (two scans)
-            hipLaunchKernelGGL(bbk::k_len_to_words, bbk::grid_blocks((n_reads + 255) / 256), dim3(256), 0, ctx->stream,
-                               rd->own_len.as<uint32_t>(), n_reads, rd->own_woff.as<uint64_t>());
-            bbk::check_launch("k_len_to_words");
+            bbk::launch_items(ctx, "k_len_to_words", bbk::k_len_to_words, n_reads, rd->own_len.as<uint32_t>(), n_reads,
+                              rd->own_woff.as<uint64_t>());
             total_words = bbk::exclusive_scan_u64(ctx, rd->own_woff.as<uint64_t>(), rd->own_woff.as<uint64_t>(), n_reads);
             bbk::DevBuf bl((n_reads + 1) * sizeof(uint64_t));
-            hipLaunchKernelGGL(bbk::k_len_to_u64, bbk::grid_blocks((n_reads + 255) / 256), dim3(256), 0, ctx->stream,
-                               rd->own_len.as<uint32_t>(), n_reads, bl.as<uint64_t>());
-            bbk::check_launch("k_len_to_u64");
+            bbk::launch_items(ctx, "k_len_to_u64", bbk::k_len_to_u64, n_reads, rd->own_len.as<uint32_t>(), n_reads,
+                              bl.as<uint64_t>());
             bases = bbk::exclusive_scan_u64(ctx, bl.as<uint64_t>(), bl.as<uint64_t>(), n_reads);
         }
         BBK_REQUIRE(total_words == n_words, BBK_ERR_ARG,
@@ -419,10 +417,9 @@ int bbk_reads_synth(bbk_ctx *ctx, uint64_t n_reads, uint32_t read_len, uint64_t 
         if (n_reads) {
             const uint64_t total = n_reads * wpr;
             const uint32_t thresh = (uint32_t)(sub_rate * 4294967296.0);
-            hipLaunchKernelGGL(bbk::k_synth_reads, bbk::grid_blocks((total + 255) / 256), dim3(256), 0, ctx->stream,
-                               n_reads, read_len, wpr, genome_len, thresh, seed_genome, seed_reads,
-                               rd->own_words.as<uint64_t>(), rd->own_woff.as<uint64_t>(), rd->own_len.as<uint32_t>());
-            bbk::check_launch("k_synth_reads");
+            bbk::launch_items(ctx, "k_synth_reads", bbk::k_synth_reads, total, n_reads, read_len, wpr, genome_len,
+                              thresh, seed_genome, seed_reads, rd->own_words.as<uint64_t>(),
+                              rd->own_woff.as<uint64_t>(), rd->own_len.as<uint32_t>());
         } else {
             BBK_HIP(hipMemsetAsync(rd->own_woff.p, 0, sizeof(uint64_t), ctx->stream));
         }
@@ -483,11 +480,9 @@ int bbk_reads_synth_meta(bbk_ctx *ctx, uint64_t n_reads, uint32_t read_len, uint
         if (n_reads) {
             const uint64_t total = n_reads * wpr;
             const uint32_t thresh = (uint32_t)(sub_rate * 4294967296.0);
-            hipLaunchKernelGGL(bbk::k_synth_meta, bbk::grid_blocks((total + 255) / 256), dim3(256), 0, ctx->stream, n_reads,
-                               read_len, wpr, n_genomes, d_cdf.as<uint64_t>(), d_glen.as<uint64_t>(), thresh, seed,
-                               seed ^ 0xA5A5A5A5A5A5A5A5ull, rd->own_words.as<uint64_t>(), rd->own_woff.as<uint64_t>(),
-                               rd->own_len.as<uint32_t>());
-            bbk::check_launch("k_synth_meta");
+            bbk::launch_items(ctx, "k_synth_meta", bbk::k_synth_meta, total, n_reads, read_len, wpr, n_genomes,
+                              d_cdf.as<uint64_t>(), d_glen.as<uint64_t>(), thresh, seed, seed ^ 0xA5A5A5A5A5A5A5A5ull,
+                              rd->own_words.as<uint64_t>(), rd->own_woff.as<uint64_t>(), rd->own_len.as<uint32_t>());
         } else {
             BBK_HIP(hipMemsetAsync(rd->own_woff.p, 0, sizeof(uint64_t), ctx->stream));
         }
@@ -530,9 +525,7 @@ int bbk_reads_export_ascii(bbk_ctx *ctx, const bbk_reads *r, char *h_bases, uint
         h_offsets[0] = 0;
         if (n == 0) return;
         bbk::DevBuf boff((n + 1) * sizeof(uint64_t));
-        hipLaunchKernelGGL(bbk::k_len_to_u64, bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream, r->d_len, n,
-                           boff.as<uint64_t>());
-        bbk::check_launch("k_len_to_u64");
+        bbk::launch_items(ctx, "k_len_to_u64", bbk::k_len_to_u64, n, r->d_len, n, boff.as<uint64_t>());
         const uint64_t total = bbk::exclusive_scan_u64(ctx, boff.as<uint64_t>(), boff.as<uint64_t>(), n);
         BBK_HIP(hipMemcpyAsync(h_offsets, boff.p, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
         h_offsets[n] = total;

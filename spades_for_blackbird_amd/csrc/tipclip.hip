@@ -84,26 +84,21 @@ __global__ __launch_bounds__(256) void k_tips_find(TipTable T, uint32_t length_b
 
 template <int W>
 static void clip_tips_impl(bbk_ctx *ctx, bbk_extindex *x, uint32_t length_bound, uint64_t *removed, uint64_t *links) {
-    const int w0bits = (W == 1) ? (int)(2 * x->k) : 64;
     DevBuf flag(x->n + 16), tipped(2 * x->n + 16), m2(x->n + 16), m3(x->n + 16), ctr(16);
     BBK_HIP(hipMemsetAsync(flag.p, 0, x->n + 16, ctx->stream));
     BBK_HIP(hipMemsetAsync(tipped.p, 0, 2 * x->n + 16, ctx->stream));
     BBK_HIP(hipMemsetAsync(ctr.p, 0, 16, ctx->stream));
-    TipTable T{x->keys.p, x->masks.as<uint8_t>(), PrefixTable{x->prefix.p, w0bits - (int)x->prefix_bits, x->prefix_wide ? 1 : 0},
-               (int)x->k, x->n};
+    TipTable T = tip_table(x);
     {
         KernelTimer t(ctx, "tip_find", 0.0);
-        hipLaunchKernelGGL(k_tips_find<W>, bbk::grid_blocks((2 * x->n + 255) / 256), dim3(256), 0, ctx->stream, T,
-                           length_bound, flag.as<uint8_t>(), tipped.as<uint8_t>(), ctr.as<unsigned long long>());
-        check_launch("k_tips_find");
+        launch_items(ctx, "k_tips_find", k_tips_find<W>, 2 * x->n, T, length_bound, flag.as<uint8_t>(),
+                     tipped.as<uint8_t>(), ctr.as<unsigned long long>());
     }
-    hipLaunchKernelGGL(k_tips_apply, bbk::grid_blocks((x->n + 255) / 256), dim3(256), 0, ctx->stream,
-                       x->masks.as<uint8_t>(), flag.as<uint8_t>(), x->n, m2.as<uint8_t>());
-    check_launch("k_tips_apply");
+    launch_items(ctx, "k_tips_apply", k_tips_apply, x->n, x->masks.as<uint8_t>(), flag.as<uint8_t>(), x->n,
+                 m2.as<uint8_t>());
     T.masks = m2.as<uint8_t>();
-    hipLaunchKernelGGL(k_tips_links<W>, bbk::grid_blocks((x->n + 255) / 256), dim3(256), 0, ctx->stream, T,
-                       tipped.as<uint8_t>(), m3.as<uint8_t>(), ctr.as<unsigned long long>() + 1);
-    check_launch("k_tips_links");
+    launch_items(ctx, "k_tips_links", k_tips_links<W>, x->n, T, tipped.as<uint8_t>(), m3.as<uint8_t>(),
+                 ctr.as<unsigned long long>() + 1);
     unsigned long long h[2] = {0, 0};
     BBK_HIP(hipMemcpyAsync(h, ctr.p, 16, hipMemcpyDeviceToHost, ctx->stream));
     BBK_HIP(hipStreamSynchronize(ctx->stream));
@@ -126,12 +121,8 @@ extern "C" int bbk_extindex_clip_tips(bbk_ctx *ctx, bbk_extindex *x, uint32_t le
         if (removed_kmers) *removed_kmers = 0;
         if (removed_links) *removed_links = 0;
         if (x->n == 0) return;
-        switch (x->W) {
-            case 1: clip_tips_impl<1>(ctx, x, length_bound, removed_kmers, removed_links); break;
-            case 2: clip_tips_impl<2>(ctx, x, length_bound, removed_kmers, removed_links); break;
-            case 3: clip_tips_impl<3>(ctx, x, length_bound, removed_kmers, removed_links); break;
-            case 4: clip_tips_impl<4>(ctx, x, length_bound, removed_kmers, removed_links); break;
-            default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", x->W);
-        }
+        dispatch_w(x->W, [&](auto w) {
+            clip_tips_impl<decltype(w)::value>(ctx, x, length_bound, removed_kmers, removed_links);
+        });
     });
 }

@@ -360,30 +360,18 @@ struct LoopTable {
 template <int W>
 static void run_walk(bbk_ctx *ctx, int pass, const bbk_extindex *x, const uint64_t *starts, uint64_t E, WalkOut o) {
     if (E == 0) return;
-    const int w0bits = (x->W == 1) ? (int)(2 * x->k) : 64;
-    const PrefixTable P{x->prefix.p, w0bits - (int)x->prefix_bits, x->prefix_wide ? 1 : 0};
+    const PrefixTable P = x->prefix.table();
     // bytes: every non-junction k-mer is stepped over once per orientation; a step is one lookup = 2 prefix-table
     // entries + ~3 key probes + 1 mask byte (latency-bound pointer chase: the figure is for reading the rate, not a
     // roofline claim); pass 1 also writes the bases
     KernelTimer t(ctx, pass == 0 ? "walk0" : "walk1", 2.0 * (double)x->n * (3.0 * x->W * 8 + 8 + 1));
-    if (pass == 0)
-        hipLaunchKernelGGL((k_walk<W, 0>), bbk::grid_blocks((E + 255) / 256), dim3(256), 0, ctx->stream,
-                           x->keys.as<Key<W>>(), x->masks.as<uint8_t>(), P, x->n, (int)x->k, starts, E, o);
-    else
-        hipLaunchKernelGGL((k_walk<W, 1>), bbk::grid_blocks((E + 255) / 256), dim3(256), 0, ctx->stream,
-                           x->keys.as<Key<W>>(), x->masks.as<uint8_t>(), P, x->n, (int)x->k, starts, E, o);
-    check_launch("k_walk");
+    launch_items(ctx, "k_walk", pass == 0 ? k_walk<W, 0> : k_walk<W, 1>, E, x->keys.as<Key<W>>(),
+                 x->masks.as<uint8_t>(), P, x->n, (int)x->k, starts, E, o);
 }
 
 static void dispatch_walk(bbk_ctx *ctx, int pass, const bbk_extindex *x, const uint64_t *starts, uint64_t E,
                           WalkOut o) {
-    switch (x->W) {
-        case 1: run_walk<1>(ctx, pass, x, starts, E, o); break;
-        case 2: run_walk<2>(ctx, pass, x, starts, E, o); break;
-        case 3: run_walk<3>(ctx, pass, x, starts, E, o); break;
-        case 4: run_walk<4>(ctx, pass, x, starts, E, o); break;
-        default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", x->W);
-    }
+    dispatch_w(x->W, [&](auto w) { run_walk<decltype(w)::value>(ctx, pass, x, starts, E, o); });
 }
 
 struct LinkRec {
@@ -503,16 +491,13 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
 
     // ---- start edges
     DevBuf cnt((n + 1) * 8);
-    hipLaunchKernelGGL(k_count_starts, bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream,
-                       x->masks.as<uint8_t>(), n, cnt.as<uint64_t>());
-    check_launch("k_count_starts");
+    launch_items(ctx, "k_count_starts", k_count_starts, n, x->masks.as<uint8_t>(), n, cnt.as<uint64_t>());
     const uint64_t E = exclusive_scan_u64(ctx, cnt.as<uint64_t>(), cnt.as<uint64_t>(), n);
     BBK_REQUIRE(E <= 8 * n, BBK_ERR_INTERNAL, "unitigs: %llu start edges counted for %llu k-mers", (unsigned long long)E,
                 (unsigned long long)n);
     DevBuf starts((E + 1) * 8);
-    hipLaunchKernelGGL(k_fill_starts, bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream,
-                       x->masks.as<uint8_t>(), n, cnt.as<uint64_t>(), starts.as<uint64_t>());
-    check_launch("k_fill_starts");
+    launch_items(ctx, "k_fill_starts", k_fill_starts, n, x->masks.as<uint8_t>(), n, cnt.as<uint64_t>(),
+                 starts.as<uint64_t>());
     cnt.release();
 
     // ---- pass 0: lengths + keep
@@ -559,9 +544,8 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
 
     // ---- loop candidates first: without perfect loops (the common case) links are made on the device
     DevBuf flag((n + 1) * 8);
-    hipLaunchKernelGGL(k_loop_candidates, bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream,
-                       x->masks.as<uint8_t>(), visited.as<uint8_t>(), n, flag.as<uint64_t>());
-    check_launch("k_loop_candidates");
+    launch_items(ctx, "k_loop_candidates", k_loop_candidates, n, x->masks.as<uint8_t>(), visited.as<uint8_t>(), n,
+                 flag.as<uint64_t>());
     const uint64_t NC = exclusive_scan_u64(ctx, flag.as<uint64_t>(), flag.as<uint64_t>(), n);
     if (NC != 0) {  // perfect loops are appended on the host: bring the paths over now
         U.bases.resize(NB);
@@ -575,9 +559,7 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
     std::vector<LinkRec> recs;
     if (NU) {
         DevBuf ids(2 * NU * 4 + 16), rtmp((2 * NU + 2) * 8), itmp(2 * NU * 4 + 16);
-        hipLaunchKernelGGL(k_edge_ids, bbk::grid_blocks((2 * NU + 255) / 256), dim3(256), 0, ctx->stream,
-                           ids.as<uint32_t>(), 2 * NU);
-        check_launch("k_edge_ids");
+        launch_items(ctx, "k_edge_ids", k_edge_ids, 2 * NU, ids.as<uint32_t>(), 2 * NU);
         int bits = 2;
         while ((1ull << (bits - 2)) < n + 1) ++bits;
         std::vector<PassDesc> passes;
@@ -590,16 +572,14 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
             KernelTimer t(ctx, "links", 0);
             DevBuf lcnt((2 * NU + 1) * 8), nv(16);
             BBK_HIP(hipMemsetAsync(nv.p, 0, 16, ctx->stream));
-            hipLaunchKernelGGL((k_links<false>), bbk::grid_blocks((2 * NU + 255) / 256), dim3(256), 0, ctx->stream,
-                               rec.as<uint64_t>(), ids.as<uint32_t>(), 2 * NU, selfc.as<uint8_t>(), lcnt.as<uint64_t>(),
-                               (const uint64_t *)nullptr, (uint64_t *)nullptr, nv.as<unsigned long long>());
-            check_launch("k_links<count>");
+            launch_items(ctx, "k_links<count>", k_links<false>, 2 * NU, rec.as<uint64_t>(), ids.as<uint32_t>(), 2 * NU,
+                         selfc.as<uint8_t>(), lcnt.as<uint64_t>(), (const uint64_t *)nullptr, (uint64_t *)nullptr,
+                         nv.as<unsigned long long>());
             const uint64_t NL = exclusive_scan_u64(ctx, lcnt.as<uint64_t>(), lcnt.as<uint64_t>(), 2 * NU);
             DevBuf dl(NL * 16 + 16);
-            hipLaunchKernelGGL((k_links<true>), bbk::grid_blocks((2 * NU + 255) / 256), dim3(256), 0, ctx->stream,
-                               rec.as<uint64_t>(), ids.as<uint32_t>(), 2 * NU, selfc.as<uint8_t>(), (uint64_t *)nullptr,
-                               lcnt.as<uint64_t>(), dl.as<uint64_t>(), (unsigned long long *)nullptr);
-            check_launch("k_links<write>");
+            launch_items(ctx, "k_links<write>", k_links<true>, 2 * NU, rec.as<uint64_t>(), ids.as<uint32_t>(), 2 * NU,
+                         selfc.as<uint8_t>(), (uint64_t *)nullptr, lcnt.as<uint64_t>(), dl.as<uint64_t>(),
+                         (unsigned long long *)nullptr);
             unsigned long long hv = 0;
             d2h(ctx, &hv, nv.p, 8);
             U.n = NU;
@@ -636,10 +616,8 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
         T.W = (int)x->W;
         T.idx.resize(NC);
         DevBuf cidx(NC * 8 + 16);
-        hipLaunchKernelGGL(k_compact_candidates, bbk::grid_blocks((n + 255) / 256), dim3(256), 0, ctx->stream,
-                           flag.as<uint64_t>(), x->masks.as<uint8_t>(), visited.as<uint8_t>(), n,
-                           cidx.as<uint64_t>());
-        check_launch("k_compact_candidates");
+        launch_items(ctx, "k_compact_candidates", k_compact_candidates, n, flag.as<uint64_t>(), x->masks.as<uint8_t>(),
+                     visited.as<uint8_t>(), n, cidx.as<uint64_t>());
         d2h_big(ctx, T.idx.data(), cidx.p, NC * 8);
         T.keys.resize(NC * T.W);
         T.masks.resize(NC);
@@ -648,10 +626,8 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
         // gather the candidate rows on the device (they may lie anywhere in a table of billions of k-mers)
         {
             DevBuf gk(NC * T.W * 8 + 16), gm(NC + 16);
-            hipLaunchKernelGGL(k_gather_candidates, bbk::grid_blocks((NC + 255) / 256), dim3(256), 0, ctx->stream,
-                               x->keys.as<uint64_t>(), x->masks.as<uint8_t>(), cidx.as<uint64_t>(), NC, T.W,
-                               gk.as<uint64_t>(), gm.as<uint8_t>());
-            check_launch("k_gather_candidates");
+            launch_items(ctx, "k_gather_candidates", k_gather_candidates, NC, x->keys.as<uint64_t>(),
+                         x->masks.as<uint8_t>(), cidx.as<uint64_t>(), NC, T.W, gk.as<uint64_t>(), gm.as<uint8_t>());
             d2h_big(ctx, T.keys.data(), gk.p, NC * T.W * 8);
             d2h_big(ctx, T.masks.data(), gm.p, NC);
             // CollectLoops (:308-344) takes the first unvisited k-mer in K-MER FILE ORDER, and the file is the
@@ -661,13 +637,10 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
             if (ref_threads) {
                 DevBuf gb(NC * 4 + 16);
                 const uint64_t nb = 10ull * ref_threads;
-                switch (T.W) {
-                    case 1: hipLaunchKernelGGL(k_candidate_buckets<1>, bbk::grid_blocks((NC + 255) / 256), dim3(256), 0, ctx->stream, gk.as<uint64_t>(), NC, nb, gb.as<uint32_t>()); break;
-                    case 2: hipLaunchKernelGGL(k_candidate_buckets<2>, bbk::grid_blocks((NC + 255) / 256), dim3(256), 0, ctx->stream, gk.as<uint64_t>(), NC, nb, gb.as<uint32_t>()); break;
-                    case 3: hipLaunchKernelGGL(k_candidate_buckets<3>, bbk::grid_blocks((NC + 255) / 256), dim3(256), 0, ctx->stream, gk.as<uint64_t>(), NC, nb, gb.as<uint32_t>()); break;
-                    default: hipLaunchKernelGGL(k_candidate_buckets<4>, bbk::grid_blocks((NC + 255) / 256), dim3(256), 0, ctx->stream, gk.as<uint64_t>(), NC, nb, gb.as<uint32_t>()); break;
-                }
-                check_launch("k_candidate_buckets");
+                dispatch_w(x->W, [&](auto w) {
+                    launch_items(ctx, "k_candidate_buckets", k_candidate_buckets<decltype(w)::value>, NC,
+                                 gk.as<uint64_t>(), NC, nb, gb.as<uint32_t>());
+                });
                 cand_bucket.resize(NC);
                 d2h_big(ctx, cand_bucket.data(), gb.p, NC * 4);
             }
@@ -791,9 +764,6 @@ static void build(bbk_ctx *ctx, bbk_extindex *x, bbk_unitigs &U, unsigned ref_th
     U.n_links = U.links.size() / 2;
 }
 
-unsigned build_prefix_index(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n, DevBuf &prefix,
-                            bool *wide);
-
 unsigned unitigs_k(const bbk_unitigs *u) { return u->k; }  // for the edge index (edgeprof.hip)
 
 // One thread per unitig: roll the (k+1)-mers of the sequence, look the canonical form up in the
@@ -828,17 +798,6 @@ __global__ __launch_bounds__(256) void k_unitig_kc(const char *__restrict__ base
     kc[u] = sum;
 }
 
-template <int W>
-static void run_kc(bbk_ctx *ctx, const char *d_bases, const uint64_t *d_off, uint64_t nu, unsigned k1,
-                   const bbk_kmerset *set, const DevBuf &pref, unsigned pbits, bool wide, uint64_t *d_kc, uint32_t *d_err) {
-    const int w0bits = (W == 1) ? (int)(2 * k1) : 64;
-    KernelTimer t(ctx, "coverage", 0);
-    hipLaunchKernelGGL(k_unitig_kc<W>, bbk::grid_blocks((nu + 255) / 256), dim3(256), 0, ctx->stream, d_bases, d_off, nu,
-                       (int)k1, set->keys.as<Key<W>>(), set->counts.as<uint32_t>(),
-                       PrefixTable{pref.p, w0bits - (int)pbits, wide ? 1 : 0}, d_kc, d_err);
-    check_launch("k_unitig_kc");
-}
-
 }  // namespace bbk
 
 using namespace bbk;
@@ -855,20 +814,19 @@ static void coverage_from_counts(bbk_ctx *ctx, bbk_unitigs *u, const bbk_kmerset
     u->kc.assign(u->n, 0);
     u->has_cov = true;
     if (u->n == 0) return;
-    DevBuf pref;
-    bool wide = false;
-    const unsigned pbits = build_prefix_index(ctx, set->keys.as<uint64_t>(), set->W, k1, set->n, pref, &wide);
+    PrefixIndex pref;
+    pref.build(ctx, set->keys.as<uint64_t>(), set->W, k1, set->n);
     DevBuf d_bases(u->bases.size() + 16), d_off((u->n + 1) * 8), d_kc(u->n * 8), d_err(16);
     BBK_HIP(hipMemcpyAsync(d_bases.p, u->bases.data(), u->bases.size(), hipMemcpyHostToDevice, ctx->stream));
     BBK_HIP(hipMemcpyAsync(d_off.p, u->offsets.data(), (u->n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     BBK_HIP(hipMemsetAsync(d_err.p, 0, 16, ctx->stream));
-    switch (set->W) {
-        case 1: run_kc<1>(ctx, d_bases.as<char>(), d_off.as<uint64_t>(), u->n, k1, set, pref, pbits, wide, d_kc.as<uint64_t>(), d_err.as<uint32_t>()); break;
-        case 2: run_kc<2>(ctx, d_bases.as<char>(), d_off.as<uint64_t>(), u->n, k1, set, pref, pbits, wide, d_kc.as<uint64_t>(), d_err.as<uint32_t>()); break;
-        case 3: run_kc<3>(ctx, d_bases.as<char>(), d_off.as<uint64_t>(), u->n, k1, set, pref, pbits, wide, d_kc.as<uint64_t>(), d_err.as<uint32_t>()); break;
-        case 4: run_kc<4>(ctx, d_bases.as<char>(), d_off.as<uint64_t>(), u->n, k1, set, pref, pbits, wide, d_kc.as<uint64_t>(), d_err.as<uint32_t>()); break;
-        default: BBK_REQUIRE(false, BBK_ERR_ARG, "unsupported key width %u", set->W);
-    }
+    dispatch_w(set->W, [&](auto w) {
+        constexpr int W_ = decltype(w)::value;
+        KernelTimer t(ctx, "coverage", 0);
+        launch_items(ctx, "k_unitig_kc", k_unitig_kc<W_>, u->n, d_bases.as<char>(), d_off.as<uint64_t>(), u->n, (int)k1,
+                     set->keys.as<Key<W_>>(), set->counts.as<uint32_t>(), pref.table(), d_kc.as<uint64_t>(),
+                     d_err.as<uint32_t>());
+    });
     uint32_t herr = 0;
     d2h(ctx, &herr, d_err.p, 4);
     BBK_REQUIRE(herr == 0, BBK_ERR_INTERNAL, "coverage: a (k+1)-mer of a unitig is missing from the count table");
@@ -933,9 +891,8 @@ int bbk_unitigs_to_reads(bbk_ctx *ctx, const bbk_unitigs *u, bbk_reads **out) {
         if (nu) {
             DevBuf err(16);
             BBK_HIP(hipMemsetAsync(err.p, 0, 16, ctx->stream));
-            hipLaunchKernelGGL(k_unitig_words, bbk::grid_blocks((nu + 255) / 256), dim3(256), 0, ctx->stream, d_uoff, nu,
-                               rd->own_woff.as<uint64_t>(), rd->own_len.as<uint32_t>(), err.as<uint32_t>());
-            check_launch("k_unitig_words");
+            launch_items(ctx, "k_unitig_words", k_unitig_words, nu, d_uoff, nu, rd->own_woff.as<uint64_t>(),
+                         rd->own_len.as<uint32_t>(), err.as<uint32_t>());
             nwords = exclusive_scan_u64(ctx, rd->own_woff.as<uint64_t>(), rd->own_woff.as<uint64_t>(), nu);
             uint32_t herr = 0;
             d2h(ctx, &herr, err.p, 4);
@@ -945,9 +902,8 @@ int bbk_unitigs_to_reads(bbk_ctx *ctx, const bbk_unitigs *u, bbk_reads **out) {
         rd->n_words = nwords;
         rd->own_words.alloc((nwords + 1) * sizeof(uint64_t));
         if (nu) {
-            hipLaunchKernelGGL(k_pack_unitigs, bbk::grid_blocks((nu * 64 + 255) / 256), dim3(256), 0, ctx->stream, d_bases,
-                               d_uoff, rd->own_woff.as<uint64_t>(), nu, rd->own_words.as<uint64_t>());
-            check_launch("k_pack_unitigs");
+            launch_items(ctx, "k_pack_unitigs", k_pack_unitigs, nu * 64, d_bases, d_uoff, rd->own_woff.as<uint64_t>(),
+                         nu, rd->own_words.as<uint64_t>());
         }
         BBK_HIP(hipStreamSynchronize(ctx->stream));
         rd->d_words = rd->own_words.as<uint64_t>();
@@ -1019,17 +975,13 @@ static void write_gfa_device(bbk_ctx *ctx, const bbk_unitigs *u, const char *pat
     DevBuf spos((nu + 1) * 8), lpos((nl + 1) * 8);
     uint64_t sbytes = 0, lbytes = 0;
     if (nu) {
-        hipLaunchKernelGGL(k_gfa_s_len, bbk::grid_blocks((nu + 255) / 256), dim3(256), 0, ctx->stream,
-                           u->d_uoff.as<uint64_t>(), nu, spos.as<uint64_t>());
-        check_launch("k_gfa_s_len");
+        launch_items(ctx, "k_gfa_s_len", k_gfa_s_len, nu, u->d_uoff.as<uint64_t>(), nu, spos.as<uint64_t>());
         sbytes = exclusive_scan_u64(ctx, spos.as<uint64_t>(), spos.as<uint64_t>(), nu);
     }
     uint32_t klen = 1;
     for (unsigned v = u->k; v >= 10; v /= 10) ++klen;
     if (nl) {
-        hipLaunchKernelGGL(k_gfa_l_len, bbk::grid_blocks((nl + 255) / 256), dim3(256), 0, ctx->stream,
-                           u->d_links.as<uint64_t>(), nl, klen, lpos.as<uint64_t>());
-        check_launch("k_gfa_l_len");
+        launch_items(ctx, "k_gfa_l_len", k_gfa_l_len, nl, u->d_links.as<uint64_t>(), nl, klen, lpos.as<uint64_t>());
         lbytes = exclusive_scan_u64(ctx, lpos.as<uint64_t>(), lpos.as<uint64_t>(), nl);
     }
     const uint64_t total = sbytes + lbytes;
@@ -1037,16 +989,12 @@ static void write_gfa_device(bbk_ctx *ctx, const bbk_unitigs *u, const char *pat
     {
         KernelTimer t(ctx, "gfa_text", (double)total + (double)u->total_bases);
         if (nu) {
-            hipLaunchKernelGGL(k_gfa_s_write, bbk::grid_blocks((nu * 64 + 255) / 256), dim3(256), 0, ctx->stream,
-                               u->d_bases.as<char>(), u->d_uoff.as<uint64_t>(), spos.as<uint64_t>(), nu,
-                               text.as<char>());
-            check_launch("k_gfa_s_write");
+            launch_items(ctx, "k_gfa_s_write", k_gfa_s_write, nu * 64, u->d_bases.as<char>(), u->d_uoff.as<uint64_t>(),
+                         spos.as<uint64_t>(), nu, text.as<char>());
         }
         if (nl) {
-            hipLaunchKernelGGL(k_gfa_l_write, bbk::grid_blocks((nl + 255) / 256), dim3(256), 0, ctx->stream,
-                               u->d_links.as<uint64_t>(), lpos.as<uint64_t>(), nl, (uint32_t)u->k, klen,
-                               text.as<char>() + sbytes);
-            check_launch("k_gfa_l_write");
+            launch_items(ctx, "k_gfa_l_write", k_gfa_l_write, nl, u->d_links.as<uint64_t>(), lpos.as<uint64_t>(), nl,
+                         (uint32_t)u->k, klen, text.as<char>() + sbytes);
         }
     }
     const int fd = open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644);

@@ -329,7 +329,7 @@ def test_heavy_hitters_at_default_thresholds(ctx):
     assert len(x) > 0
 
 
-@pytest.mark.parametrize("k", [21, 33, 77])
+@pytest.mark.parametrize("k", [21, 33, 77, 97])  # one per key width, 1 to 4 words
 def test_median_multiplicity_read_filter(ctx, k):
     """bbk_reads_median_filter (the device side of spades-read-filter: CoverageFilter::CheckMedianMlt,
     coverage_filtering_read_wrapper.hpp:22-76) against a direct evaluation: per read the upper median

@@ -1,5 +1,5 @@
 """GPU: spades-gmapper.  (a) the ranges of bbk_edgeindex_map_paths equal the restated MapSequence
-(tests/gmapper_restated.py) for k in {21, 33, 55, 127} on reads with substitutions and Ns, over gbuilder graphs and
+(tests/gmapper_restated.py) for k in {21, 33, 55, 77, 127} on reads with substitutions and Ns, over gbuilder graphs and
 over a homopolymer loop, a palindromic segment and a circular segment; (b) the CLI on a gbuilder GFA with contigs cut
 from the genome equals the restatement byte for byte, and its S/L part equals the input graph up to gfa_canon; (c) every
 segment as a contig is a one-edge path of weight 1; (d) consecutive edges of a P line are linked; (e) refusals, the last
@@ -57,27 +57,44 @@ def _check_ranges(ctx, ix, g, reads):
     return len(rec)
 
 
-@pytest.mark.parametrize("k", [21, 33, 55])
+def _cut_genome_gfa(rng, path, k):
+    """a random 3 kb genome as four segments that overlap by k, linked in a chain: the graph of a repeat-free genome.
+    gbuilder cannot make it at k = 127, where the (k+1)-mers its extension index is built from are no legal k-mers"""
+    genome = _rand(rng, 3000)
+    cuts = [0, 700, 1500, 2200, 3000]
+    segs = [genome[max(0, a - k):b] for a, b in zip(cuts, cuts[1:])]
+    path.write_text("".join("S\t%d\t%s\n" % (3 + 2 * i, q) for i, q in enumerate(segs)) +
+                    "".join("L\t%d\t+\t%d\t+\t%dM\n" % (3 + 2 * i, 5 + 2 * i, k) for i in range(len(segs) - 1)))
+    return genome
+
+
+@pytest.mark.parametrize("k", [21, 33, 55, 77, 127])
 def test_a_ranges_on_gbuilder_graphs(ctx, tmp_path, k):
-    r = ctx.reads_synth(3000, read_len=150, genome_len=20000, sub_rate=0.003, seed_genome=k, seed_reads=k + 1)
+    # The (k+1)-mers of k = 77 and 127 take three and four key words.  A 150-base read holds few of them and _mutate
+    # changes 1.4 % of its bases, so the floor on the number of ranges there comes from the reads left untouched: they
+    # map (the graph holds their (k+1)-mers), and 600 x 0.986^150 = 72 are expected; half of that is the floor.
+    min_ranges = 600 if k <= 55 else 36
+    rng = random.Random(k)
     gfa = tmp_path / "g.gfa"
-    ctx.unitigs(ctx.extindex(r, k)).write_gfa(str(gfa))
+    if k < 127:
+        r = ctx.reads_synth(3000, read_len=150, genome_len=20000, sub_rate=0.003, seed_genome=k, seed_reads=k + 1)
+        ctx.unitigs(ctx.extindex(r, k)).write_gfa(str(gfa))
+        reads = r.to_list()[:600]
+    else:  # no gbuilder graph at the largest k: the cut genome, 150-base reads of both strands
+        genome = _cut_genome_gfa(random.Random(k + 1), gfa, k)
+        starts = [rng.randint(0, len(genome) - 150) for _ in range(600)]
+        reads = [genome[st:st + 150] if i % 2 else rc(genome[st:st + 150]) for i, st in enumerate(starts)]
     g = G.Graph.from_gfa(gfa.read_text(), k)
     ix = ctx.edgeindex_from_gfa(str(gfa), k)
-    rng = random.Random(k)
-    reads = [_mutate(rng, s) for s in r.to_list()[:600]] + ["ACGT", "N" * 10, ""]
-    assert _check_ranges(ctx, ix, g, reads) > 600
+    reads = [_mutate(rng, s) for s in reads] + ["ACGT", "N" * 10, ""]
+    assert _check_ranges(ctx, ix, g, reads) > min_ranges
 
 
 def test_a_ranges_k127_and_adversarial_graphs(ctx, tmp_path):
     rng = random.Random(127)
     k = 127
-    genome = _rand(rng, 3000)
-    cuts = [0, 700, 1500, 2200, 3000]
-    segs = [genome[max(0, a - k):b] for a, b in zip(cuts, cuts[1:])]
     gfa = tmp_path / "g127.gfa"
-    gfa.write_text("".join("S\t%d\t%s\n" % (3 + 2 * i, q) for i, q in enumerate(segs)) +
-                   "".join("L\t%d\t+\t%d\t+\t%dM\n" % (3 + 2 * i, 5 + 2 * i, k) for i in range(len(segs) - 1)))
+    genome = _cut_genome_gfa(rng, gfa, k)
     reads = []
     for _ in range(300):
         st = rng.randint(0, len(genome) - 400)
