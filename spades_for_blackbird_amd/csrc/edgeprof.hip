@@ -50,6 +50,7 @@
 
 #include "bbk_internal.h"
 #include "kmer_ops.h"
+#include "unitigs.h"
 
 namespace bbk {
 
@@ -63,8 +64,6 @@ struct EdgePos {
 constexpr uint32_t kEpCanonFw = 1u;   // the canonical key is the forward window of the segment
 constexpr uint32_t kEpSelfConj = 2u;  // segment == its reverse complement
 constexpr uint32_t kEpLoop1 = 4u;     // segment is one homopolymer (k+1)-mer linked to itself
-
-unsigned unitigs_k(const bbk_unitigs *u);
 
 }  // namespace bbk
 
@@ -681,7 +680,7 @@ int bbk_edgeindex_from_unitigs(bbk_ctx *ctx, const bbk_unitigs *u, bbk_edgeindex
         for (uint64_t i = 0; i < nu; ++i) g.names[i] = std::to_string(3 + 2 * i);  // as bbk_unitigs_write_gfa names them
         g.links.resize(nl);
         for (uint64_t l = 0; l < nl; ++l) g.links[l] = {hl[4 * l], hl[4 * l + 2], hl[4 * l + 1] == 1, hl[4 * l + 3] == 1};
-        *out = build_index(ctx, unitigs_k(u), g, false);
+        *out = build_index(ctx, u->k, g, false);
     });
 }
 

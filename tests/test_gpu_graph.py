@@ -160,8 +160,7 @@ def test_gfa_vs_oracle_synthetic(ctx, k, seed, tmp_path):
         assert sorted(len(s[0]) for s in gs) == sorted(len(s[0]) for s in es)
 
 
-def test_circular_genomes_loops(ctx, tmp_path):
-    """Several perfect loops at once (plasmid-like circles without junctions)."""
+def six_circles():
     rng = np.random.default_rng(9)
     reads = []
     for c in range(6):
@@ -169,6 +168,12 @@ def test_circular_genomes_loops(ctx, tmp_path):
         dbl = circ + circ
         for s in range(0, len(circ), 7):
             reads.append(dbl[s:s + 60])
+    return reads
+
+
+def test_circular_genomes_loops(ctx, tmp_path):
+    """Several perfect loops at once (plasmid-like circles without junctions)."""
+    reads = six_circles()
     k = 21
     txt, u = gpu_gfa(ctx, reads, k, tmp_path)
     ou = O.ExtIndex(reads, k, 1).unitigs()
@@ -537,3 +542,111 @@ def test_unitigs_to_reads_and_graph_invariants(ctx, tmp_path):
     exp = O.ExtIndex(reads, k, 1).unitigs()
     _, nv, nl = exp.gfa()
     assert (len(u), u.n_vertices, u.n_links) == (exp.n, nv, nl)
+
+
+# ---- where a result lives ------------------------------------------------------------------------------------------
+# A unitig set is on the device after a build without perfect loops, on the host after a build with loops (or of an
+# empty index), and on both once a host export (sequences(), links(), a host-side writer) has run.  Every consumer
+# must give the same answer in each of these states.
+RES_K = 21
+
+
+def residency_reads(loops):
+    """600 reads of a 2.5 kb genome: >= 500 unitigs and no perfect loop at k = 9, 21 and 101 (the tests assert it);
+    with the six circles of test_circular_genomes_loops appended the result has loops and lives on the host."""
+    reads = synth_reads(600, read_len=150, genome_len=2500, sub_rate=0.01, seed=1)
+    return reads + six_circles() if loops else reads
+
+
+@pytest.fixture(scope="module")
+def residency_oracle():
+    """gfa(with_cov=True) of the oracle for the no-loop and the loop graph at RES_K, computed once"""
+    out = {}
+    for loops in (False, True):
+        ou = O.ExtIndex(residency_reads(loops), RES_K, 1).unitigs()
+        out[loops] = (ou.n, ou.n_loops, ou.gfa(with_cov=True)[0])
+    return out
+
+
+def build_unitigs(ctx, reads, k):
+    r = ctx.reads_from_ascii(reads)
+    return r, ctx.unitigs(ctx.extindex(r, k))
+
+
+def gfa_bytes(u, path):
+    u.write_gfa(str(path))
+    with open(str(path), "rb") as f:
+        return f.read()
+
+
+def expected_gfa(u, k):
+    """the GFA text of a result without coverage, from its exported sequences and links"""
+    lines = ["S\t%d\t%s\tDP:f:0\tKC:i:0\n" % (3 + 2 * i, s) for i, s in enumerate(u.sequences())]
+    lines += ["L\t%d\t%s\t%d\t%s\t%dM\n" % (3 + 2 * a, "+" if oa else "-", 3 + 2 * b, "+" if ob else "-", k)
+              for a, oa, b, ob in u.links().tolist()]
+    return "".join(lines).encode()
+
+
+@pytest.mark.parametrize("k", [9, 21, 101])
+def test_gfa_text_of_device_result(ctx, k, tmp_path):
+    """Written before any host export the text comes from the device formatter: byte for byte the S and L lines of the
+    exported sequences and links, with <k>M of 1, 2 and 3 digits and segment ids of 1 to 4 digits; written again after
+    the export (both copies present) the file is the same."""
+    _, u = build_unitigs(ctx, residency_reads(False), k)
+    first = gfa_bytes(u, tmp_path / "first.gfa")
+    assert u.n_loops == 0 and len(u) >= 500
+    assert first == expected_gfa(u, k)
+    assert gfa_bytes(u, tmp_path / "second.gfa") == first
+
+
+def test_gfa_text_of_host_result(ctx, tmp_path):
+    """a result with perfect loops lives on the host and goes through the host formatter: the same bytes"""
+    _, u = build_unitigs(ctx, residency_reads(True), RES_K)
+    got = gfa_bytes(u, tmp_path / "loops.gfa")
+    assert u.n_loops >= 1 and len(u) - u.n_loops >= 500
+    assert got == expected_gfa(u, RES_K)
+
+
+@pytest.mark.parametrize("loops", [True, False])
+def test_to_reads_of_host_and_two_copy_result(ctx, loops):
+    """to_reads of a host-only result (loops) and of one that is on the device and on the host (sequences() ran first);
+    test_unitigs_to_reads_and_graph_invariants covers the device-only state"""
+    _, u = build_unitigs(ctx, residency_reads(loops), RES_K)
+    assert (u.n_loops >= 1) == loops
+    seqs = u.sequences()
+    assert u.to_reads().to_list() == seqs
+
+
+@pytest.mark.parametrize("loops", [True, False])
+def test_coverage_of_host_and_two_copy_result(ctx, residency_oracle, loops, tmp_path):
+    """add_coverage on a host-only result (loops) and on one whose host copy was made before (sequences() ran first)"""
+    n, n_loops, exp = residency_oracle[loops]
+    r, u = build_unitigs(ctx, residency_reads(loops), RES_K)
+    assert (len(u), u.n_loops) == (n, n_loops) and (n_loops >= 1) == loops
+    if not loops:
+        u.sequences()
+    u.add_coverage(r)
+    got = gfa_bytes(u, tmp_path / "cov.gfa").decode()
+    assert gfa_canon.canon_md5(got, with_kc=True) == gfa_canon.canon_md5(exp, with_kc=True)
+
+
+def test_empty_graph(ctx, tmp_path):
+    """reads all shorter than k: an index of no k-mers gives an empty result that lives on the host; every export and
+    every writer works on it (empty files; the SPAdes binary keeps its three header words and its end mark)"""
+    r = ctx.reads_from_ascii(["ACGTACGTAC", "", "TTGACCA" * 2, "ACGTN" * 4])
+    x = ctx.extindex(r, RES_K)
+    assert len(x) == 0
+    u = ctx.unitigs(x)
+    assert (len(u), u.n_loops, u.n_vertices, u.n_links, u.total_bases) == (0, 0, 0, 0, 0)
+    assert u.sequences() == []
+    assert u.links().shape == (0, 4)
+    assert u.to_reads().to_list() == []
+    sizes = {}
+    for fmt in ("gfa", "fasta", "fastg"):
+        p = str(tmp_path / ("e." + fmt))
+        getattr(u, "write_" + fmt)(p)
+        sizes[fmt] = os.path.getsize(p)
+    u.write_spades(str(tmp_path / "e"))
+    sizes["grseq"] = os.path.getsize(str(tmp_path / "e.grseq"))
+    sizes["cvr"] = os.path.getsize(str(tmp_path / "e.cvr"))
+    assert sizes == {"gfa": 0, "fasta": 0, "fastg": 0, "grseq": 24, "cvr": 8}
