@@ -36,6 +36,11 @@ struct Accum {
     uint64_t instances = 0;  // k-mer positions seen
     uint64_t batches = 0, merges = 0;
 
+    // a count: the payload its BBK_* flags ask for (BBK_WITH_COUNTS / BBK_WITH_MASKS), the view where they allow it
+    Accum(bbk_ctx *ctx, unsigned k, unsigned count_flags);
+    // an extension index: canonical k-mers with the OR of their InOutMask bits
+    static Accum masks(bbk_ctx *ctx, unsigned k) { return Accum(ctx, k, BBK_CANONICAL | BBK_WITH_MASKS); }
+
     bool has_vals() const;
     int merge_op() const;
     void push(const bbk_reads *rd);
@@ -46,10 +51,9 @@ struct Accum {
     uint64_t finish_sorted(DevBuf &out_keys, DevBuf &out_vals);
 };
 
-// count.hip: canon U rc(canon) of the accumulated canonical records (payloads dropped); the accumulator keeps them
-bbk_kmerset *both_strands_of(Accum &acc, unsigned flags);
-
-uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
-                        DevBuf &out_vals);
+// count.hip: canon U rc(canon) of the accumulated canonical records as `flags` ask (BBK_BOTH_STRANDS [|
+// BBK_REFERENCE_ORDER]).  consume: the accumulator is left empty; otherwise it keeps its records (the extension index
+// is built from them afterwards).  carry_payload: the multiplicities travel with the keys.
+bbk_kmerset *finish_both_strands(Accum &acc, unsigned flags, bool consume, bool carry_payload);
 
 }  // namespace bbk

@@ -317,6 +317,10 @@ enum ReduceOp { REDUCE_COUNT = 0, REDUCE_SUM = 1, REDUCE_OR = 2 };
 // Returns the number of distinct keys.  drop_zero: omit keys whose reduced value is 0 (OR mode).
 uint64_t unique_records(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, void *out_keys,
                         uint32_t *out_vals, ReduceOp op, bool drop_zero);
+// The (key, val) pairs with val != 0, in their order, into out_* (allocated only when something is dropped); returns how
+// many were kept.
+uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
+                        DevBuf &out_vals);
 // Exclusive scan of n u64 values (in place allowed); returns the total.
 uint64_t exclusive_scan_u64(bbk_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n);
 // Two arrays of n values in the same launches and ONE wait; out0[n] and out1[n] receive the totals as well (the

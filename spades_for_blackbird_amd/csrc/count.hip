@@ -162,8 +162,55 @@ static void launch_expand(bbk_ctx *ctx, const void *in, const uint32_t *cin, uin
                  k, (Key<W> *)out, cout);
 }
 
-uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
-                        DevBuf &out_vals);
+// the result of a call that found no record: 16-byte buffers, so that a set's pointers are never null
+static void empty_result(DevBuf &keys, DevBuf *vals) {
+    keys.alloc(16);
+    if (vals) vals->alloc(16);
+}
+
+// ---- the general (LSD) path: what every MSD call that declines falls back to ------------------------------------
+// Owns the scratch of one radix sort of n records: a key pair and, with a payload, a payload pair.  The records come
+// in either from a producer kernel that writes keys.p / vals.p itself (extract, expand) or as a copy of a const
+// device array (load); sort() orders them in place, unique() reduces them into buffers of the caller.  n < 2^32: the
+// callers refuse larger inputs with a message of their own.
+struct LsdSort {
+    bbk_ctx *ctx;
+    unsigned k;
+    uint64_t n;
+    int W;
+    size_t rec;
+    DevBuf keys, tmp, vals, vtmp;
+    LsdSort(bbk_ctx *c, unsigned k_, uint64_t n_, bool payload)
+        : ctx(c), k(k_), n(n_), W((int)words_of(k_)), rec((size_t)W * 8), keys(n_ * rec), tmp(n_ * rec) {
+        if (payload) {
+            vals.alloc(n * 4);
+            vtmp.alloc(n * 4);
+        }
+    }
+    void load(const void *d_keys, const uint32_t *d_vals) {
+        BBK_HIP(bbk::copy_async(keys.p, d_keys, n * rec, hipMemcpyDeviceToDevice, ctx->stream));
+        if (vals.p) BBK_HIP(bbk::copy_async(vals.p, d_vals, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    void sort() { sort_records(ctx, W, keys.p, tmp.p, vals.as<uint32_t>(), vtmp.as<uint32_t>(), n, key_passes(k)); }
+    // The distinct records of the sorted array into out_keys and, when out_vals is given, their payloads reduced with
+    // `op` (REDUCE_COUNT without a payload: the run lengths) into *out_vals: exact size + 16 bytes of slack.  The
+    // distinct records land in the scratch's second half (sized for the worst case) first; one wait, at the end.
+    uint64_t unique(ReduceOp op, DevBuf &out_keys, DevBuf *out_vals) {
+        if (out_vals && !vtmp.p) vtmp.alloc(n * 4);
+        uint32_t *rv = out_vals ? vtmp.as<uint32_t>() : nullptr;
+        const uint64_t D = unique_records(ctx, W, keys.p, vals.as<uint32_t>(), n, tmp.p, rv, op, /*drop_zero=*/false);
+        keys.release();
+        vals.release();
+        out_keys.alloc(D * rec + 16);
+        BBK_HIP(bbk::copy_async(out_keys.p, tmp.p, D * rec, hipMemcpyDeviceToDevice, ctx->stream));
+        if (rv) {
+            out_vals->alloc(D * 4 + 16);
+            BBK_HIP(bbk::copy_async(out_vals->p, rv, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        stream_wait(ctx);
+        return D;
+    }
+};
 
 // ---- stage A: distinct canonical records (+ reduced payload) of one batch of reads, in ANY order ------------
 // payload: with_mask -> OR of the InOutMask bits of every occurrence; want_vals -> multiplicity.
@@ -172,7 +219,6 @@ uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *v
 // view: the caller takes the result as a BucketView where the narrow MSD pass leaves one (out_keys then stays empty)
 void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, bool want_vals, DevBuf &out_keys,
                  DevBuf &out_vals, uint64_t &n_distinct, uint64_t &n_instances, BucketView *view = nullptr) {
-    const int W = (int)words_of(k);
     n_distinct = 0;
     n_instances = 0;
     if (msd_enabled()) {
@@ -182,7 +228,7 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
         n_instances = 0;
         MsdOutput a;
         a.want_view = view != nullptr;
-        if (msd_sort_reduce(ctx, k, MSD_HASH, op1, rd, nullptr, nullptr, 0, with_mask, a)) {
+        if (msd_sort_reduce(ctx, k, MsdRequest::reads(MSD_HASH, op1, rd, with_mask), a)) {
             n_instances = a.instances;
             n_distinct = a.n;
             if (a.view.live()) *view = std::move(a.view);
@@ -195,113 +241,64 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
     if (rd->n) launch_items(ctx, "k_kmers_per_read", k_kmers_per_read, rd->n, rd->d_len, rd->n, k, koff.as<uint64_t>());
     const uint64_t N = exclusive_scan_u64(ctx, koff.as<uint64_t>(), koff.as<uint64_t>(), rd->n);
     n_instances = N;
-    if (N == 0) {
-        out_keys.alloc(16);
-        out_vals.alloc(16);
-        return;
-    }
+    if (N == 0) return empty_result(out_keys, &out_vals);
     BBK_REQUIRE(N < (1ull << 32), BBK_ERR_ARG,
                 "batch holds %llu k-mer instances; the LSD path is limited to 2^32-1 per batch (push the reads in "
                 "smaller batches)",
                 (unsigned long long)N);
-    const size_t rec = (size_t)W * 8;
-    DevBuf keys(N * rec), tmp(N * rec), vals, vtmp;
-    if (with_mask) {
-        vals.alloc(N * 4);
-        vtmp.alloc(N * 4);
-    }
-    dispatch_w(W, [&](auto w) {
-        launch_extract<decltype(w)::value>(ctx, rd, koff.as<uint64_t>(), (int)k, keys.p,
-                                           with_mask ? vals.as<uint32_t>() : nullptr, N);
+    LsdSort t(ctx, k, N, with_mask);  // the extraction writes straight into the scratch
+    dispatch_w(t.W, [&](auto w) {
+        launch_extract<decltype(w)::value>(ctx, rd, koff.as<uint64_t>(), (int)k, t.keys.p, t.vals.as<uint32_t>(), N);
     });
-    sort_records(ctx, W, keys.p, tmp.p, with_mask ? vals.as<uint32_t>() : nullptr,
-                 with_mask ? vtmp.as<uint32_t>() : nullptr, N, key_passes(k));
-    // distinct keys land in tmp (sized for the worst case), then are copied to an exact buffer
-    uint32_t *rv = nullptr;
-    if (with_mask || want_vals) {
-        if (!vtmp.p) vtmp.alloc(N * 4);
-        rv = vtmp.as<uint32_t>();
-    }
-    const uint64_t D = unique_records(ctx, W, keys.p, with_mask ? vals.as<uint32_t>() : nullptr, N, tmp.p, rv,
-                                      with_mask ? REDUCE_OR : REDUCE_COUNT, /*drop_zero=*/false);
-    keys.release();
-    vals.release();
-    out_keys.alloc(D * rec + 16);
-    BBK_HIP(bbk::copy_async(out_keys.p, tmp.p, D * rec, hipMemcpyDeviceToDevice, ctx->stream));
-    if (rv) {
-        out_vals.alloc(D * 4 + 16);
-        BBK_HIP(bbk::copy_async(out_vals.p, rv, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    stream_wait(ctx);
-    n_distinct = D;
+    t.sort();
+    n_distinct =
+        t.unique(with_mask ? REDUCE_OR : REDUCE_COUNT, out_keys, (with_mask || want_vals) ? &out_vals : nullptr);
 }
 
-// LSD sort + unique of a record array (the general path behind every MSD call that declines)
+// LSD sort + unique of a record array: the fallback of the three callers below
 static uint64_t lsd_sort_unique(bbk_ctx *ctx, unsigned k, const void *d_keys, const uint32_t *d_vals, uint64_t n,
                                 ReduceOp rop, DevBuf &out_keys, DevBuf &out_vals) {
-    const int W = (int)words_of(k);
-    const size_t rec = (size_t)W * 8;
-    BBK_REQUIRE(n < (1ull << 32), BBK_ERR_ARG, "%llu records exceed the LSD path's 2^32-1", (unsigned long long)n);
-    DevBuf a(n * rec), b(n * rec), ca, cb;
-    BBK_HIP(bbk::copy_async(a.p, d_keys, n * rec, hipMemcpyDeviceToDevice, ctx->stream));
-    if (d_vals) {
-        ca.alloc(n * 4);
-        cb.alloc(n * 4);
-        BBK_HIP(bbk::copy_async(ca.p, d_vals, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    LsdSort t(ctx, k, n, d_vals != nullptr);
+    t.load(d_keys, d_vals);
+    t.sort();
+    return t.unique(rop, out_keys, d_vals ? &out_vals : nullptr);
+}
+
+// Distinct records of a record array (payloads reduced with the MSD_OP_* `op`), hash-bucket order (prefix MSD_HASH) or
+// ascending (MSD_KEYS).  The general path orders either way.
+static uint64_t reduce_records(bbk_ctx *ctx, unsigned k, MsdRequest rq, DevBuf &out_keys, DevBuf &out_vals) {
+    if (rq.n == 0) {
+        empty_result(out_keys, rq.vals ? &out_vals : nullptr);
+        return 0;
     }
-    sort_records(ctx, W, a.p, b.p, d_vals ? ca.as<uint32_t>() : nullptr, d_vals ? cb.as<uint32_t>() : nullptr, n,
-                 key_passes(k));
-    const uint64_t D = unique_records(ctx, W, a.p, d_vals ? ca.as<uint32_t>() : nullptr, n, b.p,
-                                      d_vals ? cb.as<uint32_t>() : nullptr, rop, false);
-    out_keys.alloc(D * rec + 16);
-    BBK_HIP(bbk::copy_async(out_keys.p, b.p, D * rec, hipMemcpyDeviceToDevice, ctx->stream));
-    if (d_vals) {
-        out_vals.alloc(D * 4 + 16);
-        BBK_HIP(bbk::copy_async(out_vals.p, cb.p, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (msd_enabled()) {
+        MsdOutput m;
+        if (msd_sort_reduce(ctx, k, rq, m)) {
+            out_keys = std::move(m.keys);
+            if (rq.op != MSD_OP_NONE) out_vals = std::move(m.vals);
+            return m.n;
+        }
     }
-    stream_wait(ctx);
-    return D;
+    BBK_REQUIRE(rq.n < (1ull << 32), BBK_ERR_ARG, "%llu records exceed the LSD path's 2^32-1",
+                (unsigned long long)rq.n);
+    const ReduceOp rop = rq.op == MSD_OP_OR ? REDUCE_OR : REDUCE_SUM;
+    return lsd_sort_unique(ctx, k, rq.keys, rq.vals, rq.n, rop, out_keys, out_vals);
 }
 
 // Distinct records of a record array (payloads summed / OR-ed), in ANY order: the merge step of the streaming
 // count (MergeKMers analogue, kmer_index_builder.hpp:281-365) and of the multi-GPU exchange.
 static uint64_t dedup_keys(bbk_ctx *ctx, unsigned k, const void *d_keys, const uint32_t *d_vals, uint64_t n, int op,
                            DevBuf &out_keys, DevBuf &out_vals) {
-    if (n == 0) {
-        out_keys.alloc(16);
-        if (d_vals) out_vals.alloc(16);
-        return 0;
-    }
-    if (msd_enabled()) {
-        MsdOutput m;
-        if (msd_sort_reduce(ctx, k, MSD_HASH, op, nullptr, d_keys, d_vals, n, false, m)) {
-            out_keys = std::move(m.keys);
-            if (op != MSD_OP_NONE) out_vals = std::move(m.vals);
-            return m.n;
-        }
-    }
-    return lsd_sort_unique(ctx, k, d_keys, d_vals, n, op == MSD_OP_OR ? REDUCE_OR : REDUCE_SUM, out_keys, out_vals);
+    return reduce_records(ctx, k, MsdRequest::records(MSD_HASH, op, d_keys, d_vals, n), out_keys, out_vals);
 }
 
 // ---- stage B: a distinct set -> ascending (word 0 most significant, adt/array_vector.hpp:114-123) ---------------
 static uint64_t sort_distinct(bbk_ctx *ctx, unsigned k, const void *d_keys, const uint32_t *d_vals, uint64_t n, int op,
                               DevBuf &out_keys, DevBuf &out_vals) {
-    if (n == 0) {
-        out_keys.alloc(16);
-        if (d_vals) out_vals.alloc(16);
-        return 0;
-    }
-    if (msd_enabled()) {
-        MsdOutput b;
-        // the input is distinct: stage B only orders it (assume_distinct: the sorted result is written directly)
-        if (msd_sort_reduce(ctx, k, MSD_KEYS, d_vals ? op : MSD_OP_NONE, nullptr, d_keys, d_vals, n, false, b, 0u,
-                            /*assume_distinct=*/true)) {
-            out_keys = std::move(b.keys);
-            if (d_vals) out_vals = std::move(b.vals);
-            return b.n;
-        }
-    }
-    return lsd_sort_unique(ctx, k, d_keys, d_vals, n, op == MSD_OP_OR ? REDUCE_OR : REDUCE_SUM, out_keys, out_vals);
+    // the input is distinct: stage B only orders it (assume_distinct: the sorted result is written directly)
+    MsdRequest rq = MsdRequest::records(MSD_KEYS, d_vals ? op : MSD_OP_NONE, d_keys, d_vals, n);
+    rq.assume_distinct = true;
+    return reduce_records(ctx, k, rq, out_keys, out_vals);
 }
 
 // ---- accumulator of the streaming entry points -----------------------------------------------------------------
@@ -311,6 +308,20 @@ static uint64_t sort_distinct(bbk_ctx *ctx, unsigned k, const void *d_keys, cons
 // deduplicated on its own (stage A) and kept as a "run" of distinct canonical records; runs are merge-uniqued into
 // the accumulated set whenever they outweigh half of it (so the total merge work stays linear in the input), and
 // finish() orders the set once.
+
+// a count whose stage B may read stage A's buckets in place: both strands without payload, 8-byte keys, odd k (the
+// ordering pass takes the key slots only for a distinct expanded set)
+static bool view_wanted(unsigned k, unsigned flags) {
+    return (flags & BBK_BOTH_STRANDS) && !(flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS)) && words_of(k) == 1 && (k & 1);
+}
+
+Accum::Accum(bbk_ctx *c, unsigned k_, unsigned count_flags)
+    : ctx(c),
+      k(k_),
+      with_mask((count_flags & BBK_WITH_MASKS) != 0),
+      want_vals((count_flags & BBK_WITH_COUNTS) != 0),
+      want_view(view_wanted(k_, count_flags)) {}
+
 bool Accum::has_vals() const { return with_mask || want_vals; }
 int Accum::merge_op() const { return with_mask ? MSD_OP_OR : (want_vals ? MSD_OP_SUM : MSD_OP_NONE); }
 
@@ -408,7 +419,7 @@ void Accum::merge() {
     for (Run &r : runs) put(r.keys, r.vals, r.n);
     runs.clear();
     runs_n = 0;
-    n = dedup_keys(ctx, k, ck.p, has_vals() ? cv.as<uint32_t>() : nullptr, total, merge_op(), keys, vals);
+    n = dedup_keys(ctx, k, ck.p, cv.as<uint32_t>(), total, merge_op(), keys, vals);
     ++merges;
 }
 
@@ -427,36 +438,33 @@ uint64_t Accum::finish_sorted(DevBuf &out_keys, DevBuf &out_vals) {
 // canon U rc(canon): expand, sort, unique.  A k-mer equal to its own RC (even k) appears twice
 // and is merged by unique; its count doubles, as in the reference where both strands of such an
 // occurrence are counted.
-// want_ref: leave the set in the final_kmers order when that is free (tagged sort); s.ref_order tells.
+// want_ref: leave the set in the final_kmers order when that is free (tagged sort / REF prefix); s.ref_order tells.
 // view: the canonical set is still in stage A's buckets (ck empty, no payload); stage B's level 1 reads it there
 static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, const DevBuf *cv, uint64_t D,
                                 bbk_kmerset &s, bool want_ref = false, BucketView *view = nullptr) {
-    const bool wc = cv != nullptr;
+    const uint32_t *cvp = cv ? cv->as<uint32_t>() : nullptr;
     const int W = (int)words_of(k);
-    const size_t rec = (size_t)W * 8;
-    if (D == 0) {
-        s.n = 0;
-        s.keys.alloc(16);
-        if (wc) s.counts.alloc(16);
-        return;
-    }
+    if (D == 0) return empty_result(s.keys, cv ? &s.counts : nullptr);
     // (sets above one device pass -- 2^32 records and far less for wide keys -- are sorted in key-range passes inside
     // msd_sort_reduce; only the LSD fallback below keeps the 32-bit limit)
-    bool tag = want_ref && W == 1 && 2 * k + 4 <= 64 && msd_enabled();
     if (msd_enabled()) {
         // fused: the level-1 partition kernels generate key, reverse complement (and tag) from the canonical array
         // themselves -- the expanded array is never written
-        MsdOutput m;
-        // REF prefix (XXH3 bucket above the key bits: the final_kmers order straight from the sort) for every key
-        // width; BBK_NO_WIDE_REF=1: keys above 16 bytes are sorted ascending and take one more stable pass on the bucket
+        // TAG (8-byte keys with 4 spare bits) or REF prefix (every other key width): the XXH3 bucket above the key bits
+        // gives the final_kmers order straight from the sort; BBK_NO_WIDE_REF=1: keys above 16 bytes are sorted
+        // ascending and take one more stable pass on the bucket (to_reference_order)
+        const bool tag = want_ref && W == 1 && 2 * k + 4 <= 64;
         const bool ref_prefix = want_ref && !tag && (W <= 2 || getenv("BBK_NO_WIDE_REF") == nullptr);
-        if (msd_sort_reduce(ctx, k, ref_prefix ? MSD_REF : MSD_KEYS, wc ? MSD_OP_SUM : MSD_OP_NONE, nullptr,
-                            view ? nullptr : ck.p, wc ? cv->as<uint32_t>() : nullptr, D, false, m, tag ? 4u : 0u,
-                            /*assume_distinct: odd k has no self-reverse-complementary k-mers*/ (k & 1) != 0,
-                            /*expand_k=*/k, view)) {
+        const int prefix = ref_prefix ? MSD_REF : MSD_KEYS, op = cv ? MSD_OP_SUM : MSD_OP_NONE;
+        MsdRequest rq =
+            view ? MsdRequest::expand(prefix, op, k, *view) : MsdRequest::expand(prefix, op, k, ck.p, cvp, D);
+        rq.tag_bits = tag ? 4u : 0u;
+        rq.assume_distinct = (k & 1) != 0;  // odd k has no self-reverse-complementary k-mers
+        MsdOutput m;
+        if (msd_sort_reduce(ctx, k, rq, m)) {
             s.n = m.n;
             s.keys = std::move(m.keys);
-            if (wc) s.counts = std::move(m.vals);
+            if (cv) s.counts = std::move(m.vals);
             s.ref_order = tag || ref_prefix;
             return;
         }
@@ -465,29 +473,12 @@ static void expand_both_strands(bbk_ctx *ctx, unsigned k, const DevBuf &ck, cons
     BBK_REQUIRE(2 * D < (1ull << 32), BBK_ERR_ARG, "too many distinct k-mers for the LSD path (%llu)", (unsigned long long)D);
     if (view) view->materialise(ctx);
     const void *ckp = view ? view->keys.p : ck.p;
-    DevBuf e(2 * D * rec), et(2 * D * rec), ec, ect;
-    if (wc) {
-        ec.alloc(2 * D * 4);
-        ect.alloc(2 * D * 4);
-    }
+    LsdSort t(ctx, k, 2 * D, cv != nullptr);
     dispatch_w(W, [&](auto w) {
-        launch_expand<decltype(w)::value>(ctx, ckp, wc ? cv->as<uint32_t>() : nullptr, D, (int)k, e.p,
-                                          wc ? ec.as<uint32_t>() : nullptr, false);
+        launch_expand<decltype(w)::value>(ctx, ckp, cvp, D, (int)k, t.keys.p, t.vals.as<uint32_t>(), false);
     });
-    sort_records(ctx, W, e.p, et.p, wc ? ec.as<uint32_t>() : nullptr, wc ? ect.as<uint32_t>() : nullptr, 2 * D,
-                 key_passes(k));
-    const uint64_t D2 = unique_records(ctx, W, e.p, wc ? ec.as<uint32_t>() : nullptr, 2 * D, et.p,
-                                       wc ? ect.as<uint32_t>() : nullptr, wc ? REDUCE_SUM : REDUCE_COUNT, false);
-    e.release();
-    ec.release();
-    s.n = D2;
-    s.keys.alloc(D2 * rec);
-    BBK_HIP(bbk::copy_async(s.keys.p, et.p, D2 * rec, hipMemcpyDeviceToDevice, ctx->stream));
-    if (wc) {
-        s.counts.alloc(D2 * 4);
-        BBK_HIP(bbk::copy_async(s.counts.p, ect.p, D2 * 4, hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    stream_wait(ctx);
+    t.sort();
+    s.n = t.unique(cv ? REDUCE_SUM : REDUCE_COUNT, s.keys, cv ? &s.counts : nullptr);
 }
 
 static void check_k(unsigned k) {
@@ -495,82 +486,72 @@ static void check_k(unsigned k) {
     BBK_REQUIRE(k >= 1 && k < BBK_MAX_K, BBK_ERR_ARG, "k-mer size %u out of range [1,%d)", k, BBK_MAX_K);
 }
 
-// finish of a count: the accumulated distinct canonical set -> the bbk_kmerset the flags ask for
-static bbk_kmerset *finish_count(Accum &acc, unsigned flags) {
-    bbk_ctx *ctx = acc.ctx;
-    const unsigned k = acc.k;
-    const bool both = (flags & BBK_BOTH_STRANDS) != 0;
-    const bool wc = (flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS)) != 0;  // a u32 payload travels with the keys
-    const bool want_ref = (flags & BBK_REFERENCE_ORDER) != 0;
+static std::unique_ptr<bbk_kmerset> new_kmerset(unsigned k, unsigned flags, bool has_counts, uint64_t instances) {
     auto s = std::make_unique<bbk_kmerset>();
     s->k = k;
     s->W = words_of(k);
     s->flags = flags;
-    s->has_counts = wc;
-    s->instances = both ? 2 * acc.instances : acc.instances;
+    s->has_counts = has_counts;
+    s->instances = instances;
+    return s;
+}
+
+// CountAll(16, ...) (projects/kmercount/main.cpp:215): the XXH3 bucket of 16 as the digit of one stable pass.  Over an
+// ascending set it yields the final_kmers order (KMerDiskStorage::merge, kmer_index_builder.hpp:168-181).
+static PassDesc ref_bucket_pass() { return PassDesc{1, 0, 0, 8, 16}; }
+
+// An ascending set -> the final_kmers order, counts alongside (the key widths and paths whose sort did not leave it
+// there already).  No-op for a set in that order or without one (BBK_UNSORTED).
+static void to_reference_order(bbk_ctx *ctx, bbk_kmerset &s) {
+    if (s.ref_order || !s.sorted) return;
+    if (s.n) {
+        DevBuf nk(s.n * (size_t)s.W * 8), nc;
+        if (s.has_counts) nc.alloc(s.n * 4);
+        partition_records(ctx, (int)s.W, s.keys.p, nk.p, s.has_counts ? s.counts.as<uint32_t>() : nullptr,
+                          nc.as<uint32_t>(), s.n, ref_bucket_pass());
+        s.keys = std::move(nk);
+        if (s.has_counts) s.counts = std::move(nc);
+    }
+    s.ref_order = true;
+}
+
+// The both-strand set of spades-kmercount from the accumulated canonical set.  consume: the accumulator is left empty
+// (a bucket view is read in place); otherwise it keeps its records, dense (bbk_extindex_finish_with_set: the extension
+// index is built from them afterwards).  carry_payload: the multiplicities travel with the keys.
+bbk_kmerset *finish_both_strands(Accum &acc, unsigned flags, bool consume, bool carry_payload) {
+    auto s = new_kmerset(acc.k, flags, carry_payload, 2 * acc.instances);
     acc.merge();
-    if (both) {
-        expand_both_strands(ctx, k, acc.keys, wc ? &acc.vals : nullptr, acc.n, *s, want_ref,
-                            acc.view.live() ? &acc.view : nullptr);
+    if (!consume) acc.dense();
+    expand_both_strands(acc.ctx, acc.k, acc.keys, carry_payload ? &acc.vals : nullptr, acc.n, *s,
+                        (flags & BBK_REFERENCE_ORDER) != 0, acc.view.live() ? &acc.view : nullptr);
+    if (consume) {
         acc.keys.release();
         acc.vals.release();
         acc.view = BucketView();
-    } else if (flags & BBK_UNSORTED) {
+        acc.n = 0;
+    }
+    if (flags & BBK_REFERENCE_ORDER) to_reference_order(acc.ctx, *s);
+    return s.release();
+}
+
+// finish of a count: the accumulated distinct canonical set -> the bbk_kmerset the flags ask for
+static bbk_kmerset *finish_count(Accum &acc, unsigned flags) {
+    const bool wc = (flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS)) != 0;  // a u32 payload travels with the keys
+    if (flags & BBK_BOTH_STRANDS) return finish_both_strands(acc, flags, /*consume=*/true, wc);
+    auto s = new_kmerset(acc.k, flags, wc, acc.instances);
+    acc.merge();
+    if (flags & BBK_UNSORTED) {
         s->n = acc.n;
         s->sorted = false;
         s->keys = std::move(acc.keys);
         if (wc) s->counts = std::move(acc.vals);
-        if (!s->keys.p) s->keys.alloc(16);
+        if (!s->keys.p) empty_result(s->keys, nullptr);
+        acc.n = 0;
     } else {
         s->n = acc.finish_sorted(s->keys, s->counts);
     }
-    acc.n = 0;
-    if (want_ref && !s->ref_order && s->sorted) {  // an ascending set -> the final_kmers order: one stable pass on the
-        if (s->n) {                                // XXH3 bucket (key widths without room for the tag / REF prefix)
-            const PassDesc pd{1, 0, 0, 8, 16};
-            DevBuf nk(s->n * (size_t)s->W * 8), nc;
-            if (wc) nc.alloc(s->n * 4);
-            partition_records(ctx, (int)s->W, s->keys.p, nk.p, wc ? s->counts.as<uint32_t>() : nullptr,
-                              wc ? nc.as<uint32_t>() : nullptr, s->n, pd);
-            s->keys = std::move(nk);
-            if (wc) s->counts = std::move(nc);
-        }
-        s->ref_order = true;
-    }
+    if (flags & BBK_REFERENCE_ORDER) to_reference_order(acc.ctx, *s);
     return s.release();
-}
-
-// The both-strand set of spades-kmercount from an accumulator that is NOT consumed (bbk_extindex_finish_with_set: the
-// extension index is built from the same canonical records afterwards).  The payloads (mask bits) are not carried over.
-bbk_kmerset *both_strands_of(Accum &acc, unsigned flags) {
-    BBK_REQUIRE((flags & BBK_BOTH_STRANDS) && !(flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS | BBK_UNSORTED | BBK_CANONICAL)),
-                BBK_ERR_ARG, "the set built beside an extension index is BBK_BOTH_STRANDS [| BBK_REFERENCE_ORDER]");
-    auto s = std::make_unique<bbk_kmerset>();
-    s->k = acc.k;
-    s->W = words_of(acc.k);
-    s->flags = flags;
-    s->has_counts = false;
-    s->instances = 2 * acc.instances;
-    acc.merge();
-    acc.dense();
-    const bool want_ref = (flags & BBK_REFERENCE_ORDER) != 0;
-    expand_both_strands(acc.ctx, acc.k, acc.keys, nullptr, acc.n, *s, want_ref);
-    if (want_ref && !s->ref_order && s->sorted) {
-        if (s->n) {
-            const PassDesc pd{1, 0, 0, 8, 16};
-            DevBuf nk(s->n * (size_t)s->W * 8);
-            partition_records(acc.ctx, (int)s->W, s->keys.p, nk.p, nullptr, nullptr, s->n, pd);
-            s->keys = std::move(nk);
-        }
-        s->ref_order = true;
-    }
-    return s.release();
-}
-
-// a count whose stage B may read stage A's buckets in place: both strands without payload, 8-byte keys, odd k (the
-// ordering pass takes the key slots only for a distinct expanded set)
-static bool view_wanted(unsigned k, unsigned flags) {
-    return (flags & BBK_BOTH_STRANDS) && !(flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS)) && words_of(k) == 1 && (k & 1);
 }
 
 static void check_count_flags(unsigned flags) {
@@ -588,7 +569,8 @@ using namespace bbk;
 
 struct bbk_counter {
     bbk::Accum acc;
-    unsigned flags = 0;
+    unsigned flags;
+    bbk_counter(bbk_ctx *ctx, unsigned k, unsigned f) : acc(ctx, k, f), flags(f) {}
 };
 
 extern "C" {
@@ -598,14 +580,7 @@ int bbk_count_begin(bbk_ctx *ctx, unsigned k, unsigned flags, bbk_counter **out)
         BBK_REQUIRE(ctx && out, BBK_ERR_ARG, "bbk_count_begin: NULL argument");
         check_k(k);
         check_count_flags(flags);
-        auto c = std::make_unique<bbk_counter>();
-        c->acc.ctx = ctx;
-        c->acc.k = k;
-        c->acc.want_vals = (flags & BBK_WITH_COUNTS) != 0;
-        c->acc.with_mask = (flags & BBK_WITH_MASKS) != 0;
-        c->acc.want_view = view_wanted(k, flags);
-        c->flags = flags;
-        *out = c.release();
+        *out = new bbk_counter(ctx, k, flags);
     });
 }
 
@@ -652,12 +627,7 @@ int bbk_count(bbk_ctx *ctx, const bbk_reads *reads, unsigned k, unsigned flags, 
         BBK_HIP(hipSetDevice(ctx->device));
         // one batch through the streaming accumulator: hash-partitioned dedup of the canonical stream (stage A),
         // then expand + sort once (stage B)
-        Accum acc;
-        acc.ctx = ctx;
-        acc.k = k;
-        acc.want_vals = (flags & BBK_WITH_COUNTS) != 0;
-        acc.with_mask = (flags & BBK_WITH_MASKS) != 0;
-        acc.want_view = view_wanted(k, flags);
+        Accum acc(ctx, k, flags);
         acc.push(reads);
         *out = finish_count(acc, flags);
     });
@@ -680,51 +650,22 @@ int bbk_kmerset_from_device_ex(bbk_ctx *ctx, const void *d_keys, const void *d_c
         BBK_REQUIRE(ctx && out && (n == 0 || d_keys), BBK_ERR_ARG, "bbk_kmerset_from_device: NULL argument");
         check_k(k);
         BBK_HIP(hipSetDevice(ctx->device));
-        auto s = std::make_unique<bbk_kmerset>();
-        s->k = k;
-        s->W = words_of(k);
-        s->has_counts = d_counts != nullptr;
-        s->instances = n;
-        const size_t rec = (size_t)s->W * 8;
+        const uint32_t *d_vals = (const uint32_t *)d_counts;
+        auto s = new_kmerset(k, flags, d_vals != nullptr, n);
+        const bool unsorted = (flags & BBK_UNSORTED) != 0;
+        const MsdRequest rq =
+            MsdRequest::records(unsorted ? MSD_HASH : MSD_KEYS, d_vals ? MSD_OP_SUM : MSD_OP_NONE, d_keys, d_vals, n);
+        MsdOutput m;
         if (n == 0) {
-            s->keys.alloc(16);
-            if (d_counts) s->counts.alloc(16);
-            *out = s.release();
-            return;
+            empty_result(s->keys, d_vals ? &s->counts : nullptr);
+        } else if (msd_enabled() && msd_sort_reduce(ctx, k, rq, m)) {
+            s->n = m.n;
+            s->sorted = !unsorted;
+            s->keys = std::move(m.keys);
+            if (d_vals) s->counts = std::move(m.vals);
+        } else {  // the general path orders either way
+            s->n = lsd_sort_unique(ctx, k, d_keys, d_vals, n, d_vals ? REDUCE_SUM : REDUCE_COUNT, s->keys, s->counts);
         }
-        if (msd_enabled()) {
-            MsdOutput m;
-            const bool unsorted = (flags & BBK_UNSORTED) != 0;
-            if (msd_sort_reduce(ctx, k, unsorted ? MSD_HASH : MSD_KEYS, d_counts ? MSD_OP_SUM : MSD_OP_NONE, nullptr,
-                                d_keys, (const uint32_t *)d_counts, n, false, m)) {
-                s->n = m.n;
-                s->sorted = !unsorted;
-                s->keys = std::move(m.keys);
-                if (d_counts) s->counts = std::move(m.vals);
-                *out = s.release();
-                return;
-            }
-        }
-        DevBuf a(n * rec), b(n * rec), ca, cb;
-        BBK_HIP(bbk::copy_async(a.p, d_keys, n * rec, hipMemcpyDeviceToDevice, ctx->stream));
-        if (d_counts) {
-            ca.alloc(n * 4);
-            cb.alloc(n * 4);
-            BBK_HIP(bbk::copy_async(ca.p, d_counts, n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        sort_records(ctx, (int)s->W, a.p, b.p, d_counts ? ca.as<uint32_t>() : nullptr,
-                     d_counts ? cb.as<uint32_t>() : nullptr, n, key_passes(k));
-        const uint64_t D = unique_records(ctx, (int)s->W, a.p, d_counts ? ca.as<uint32_t>() : nullptr, n, b.p,
-                                          d_counts ? cb.as<uint32_t>() : nullptr,
-                                          d_counts ? REDUCE_SUM : REDUCE_COUNT, false);
-        s->n = D;
-        s->keys.alloc(D * rec);
-        BBK_HIP(bbk::copy_async(s->keys.p, b.p, D * rec, hipMemcpyDeviceToDevice, ctx->stream));
-        if (d_counts) {
-            s->counts.alloc(D * 4);
-            BBK_HIP(bbk::copy_async(s->counts.p, cb.p, D * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        stream_wait(ctx);
         *out = s.release();
     });
 }
@@ -739,32 +680,17 @@ int bbk_kmerset_both_strands_ex(bbk_ctx *ctx, const bbk_kmerset *canon, unsigned
         BBK_REQUIRE((flags & ~BBK_REFERENCE_ORDER) == 0, BBK_ERR_ARG,
                     "bbk_kmerset_both_strands_ex: only BBK_REFERENCE_ORDER is accepted");
         BBK_HIP(hipSetDevice(ctx->device));
+        auto s = new_kmerset(canon->k, (canon->flags & ~(BBK_CANONICAL | BBK_UNSORTED)) | BBK_BOTH_STRANDS | flags,
+                             canon->has_counts, 2 * canon->instances);
         const bool want_ref = (flags & BBK_REFERENCE_ORDER) != 0;
-        auto s = std::make_unique<bbk_kmerset>();
-        s->k = canon->k;
-        s->W = canon->W;
-        s->flags = (canon->flags & ~(BBK_CANONICAL | BBK_UNSORTED)) | BBK_BOTH_STRANDS | flags;
-        s->has_counts = canon->has_counts;
-        s->instances = 2 * canon->instances;
         expand_both_strands(ctx, canon->k, canon->keys, canon->has_counts ? &canon->counts : nullptr, canon->n, *s,
                             want_ref);
-        if (want_ref && !s->ref_order) {  // key widths without room for the tag: one stable pass on the bucket digit
-            if (s->n) {
-                const PassDesc pd{1, 0, 0, 8, 16};
-                const bool wc = s->has_counts;
-                DevBuf nk(s->n * (size_t)s->W * 8), nc;
-                if (wc) nc.alloc(s->n * 4);
-                partition_records(ctx, (int)s->W, s->keys.p, nk.p, wc ? s->counts.as<uint32_t>() : nullptr,
-                                  wc ? nc.as<uint32_t>() : nullptr, s->n, pd);
-                s->keys = std::move(nk);
-                if (wc) s->counts = std::move(nc);
-            }
-            s->ref_order = true;
-        }
+        if (want_ref) to_reference_order(ctx, *s);
         *out = s.release();
     });
 }
 
+// ---- bbk_kmerset: accessors, export, verification -----------------------------------------------------------------
 uint64_t bbk_kmerset_size(const bbk_kmerset *s) { return s ? s->n : 0; }
 unsigned bbk_kmerset_k(const bbk_kmerset *s) { return s ? s->k : 0; }
 uint64_t bbk_kmerset_instances(const bbk_kmerset *s) { return s ? s->instances : 0; }
@@ -791,17 +717,11 @@ static void export_ordered(bbk_ctx *ctx, const bbk_kmerset *s, const PassDesc *p
     const bool wc = s->has_counts && dst_counts;
     if (s->ref_order && !pd) {
         // ascending export of a set stored in the final_kmers order: sort a copy (not a hot path)
-        DevBuf a(s->n * rec), b(s->n * rec), ca, cb;
-        BBK_HIP(bbk::copy_async(a.p, s->keys.p, s->n * rec, hipMemcpyDeviceToDevice, ctx->stream));
-        if (wc) {
-            ca.alloc(s->n * 4);
-            cb.alloc(s->n * 4);
-            BBK_HIP(bbk::copy_async(ca.p, s->counts.p, s->n * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        sort_records(ctx, (int)s->W, a.p, b.p, wc ? ca.as<uint32_t>() : nullptr, wc ? cb.as<uint32_t>() : nullptr, s->n,
-                     key_passes(s->k));
-        BBK_HIP(bbk::copy_async(dst_keys, a.p, s->n * rec, hipMemcpyDefault, ctx->stream));
-        if (wc) BBK_HIP(bbk::copy_async(dst_counts, ca.p, s->n * 4, hipMemcpyDefault, ctx->stream));
+        LsdSort t(ctx, s->k, s->n, wc);
+        t.load(s->keys.p, s->counts.as<uint32_t>());
+        t.sort();
+        BBK_HIP(bbk::copy_async(dst_keys, t.keys.p, s->n * rec, hipMemcpyDefault, ctx->stream));
+        if (wc) BBK_HIP(bbk::copy_async(dst_counts, t.vals.p, s->n * 4, hipMemcpyDefault, ctx->stream));
         stream_wait(ctx);
         return;
     }
@@ -837,7 +757,7 @@ int bbk_kmerset_export(bbk_ctx *ctx, const bbk_kmerset *s, unsigned order, void 
         if (order == BBK_ORDER_SORTED) {
             export_ordered(ctx, s, nullptr, dst_keys, dst_counts, nullptr);
         } else {
-            const PassDesc pd{1, 0, 0, 8, 16};  // CountAll(16, ...) (projects/kmercount/main.cpp:215)
+            const PassDesc pd = ref_bucket_pass();
             export_ordered(ctx, s, &pd, dst_keys, dst_counts, nullptr);
         }
     });
@@ -936,7 +856,7 @@ int bbk_kmerset_write_final_kmers(bbk_ctx *ctx, const bbk_kmerset *s, const char
         const void *src = s->keys.p;
         if (!s->ref_order && s->n) {
             tmp.alloc(s->n * rec);
-            const PassDesc pd{1, 0, 0, 8, 16};
+            const PassDesc pd = ref_bucket_pass();
             export_ordered(ctx, s, &pd, tmp.p, nullptr, nullptr);
             src = tmp.p;
         }

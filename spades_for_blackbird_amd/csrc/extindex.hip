@@ -123,6 +123,7 @@ using namespace bbk;
 
 struct bbk_extbuilder {
     bbk::Accum acc;
+    bbk_extbuilder(bbk_ctx *ctx, unsigned k) : acc(bbk::Accum::masks(ctx, k)) {}
 };
 
 extern "C" {
@@ -132,10 +133,7 @@ int bbk_extindex_build(bbk_ctx *ctx, const bbk_reads *reads, unsigned k, bbk_ext
         BBK_REQUIRE(ctx && reads && out, BBK_ERR_ARG, "bbk_extindex_build: NULL argument");
         check_ext_k(k);
         BBK_HIP(hipSetDevice(ctx->device));
-        Accum acc;
-        acc.ctx = ctx;
-        acc.k = k;
-        acc.with_mask = true;
+        Accum acc = Accum::masks(ctx, k);
         acc.push(reads);
         *out = finish_extindex(acc);
     });
@@ -147,10 +145,7 @@ int bbk_extindex_from_device(bbk_ctx *ctx, const void *d_keys, const void *d_mas
         BBK_REQUIRE(ctx && out && (n == 0 || (d_keys && d_masks_u32)), BBK_ERR_ARG, "bbk_extindex_from_device: NULL argument");
         check_ext_k(k);
         BBK_HIP(hipSetDevice(ctx->device));
-        Accum acc;
-        acc.ctx = ctx;
-        acc.k = k;
-        acc.with_mask = true;
+        Accum acc = Accum::masks(ctx, k);
         acc.push_records(d_keys, (const uint32_t *)d_masks_u32, n);
         *out = finish_extindex(acc);
     });
@@ -171,7 +166,7 @@ int bbk_extindex_export_u32(bbk_ctx *ctx, const bbk_extindex *x, void *dst_keys,
             DevBuf m(x->n * 4);
             launch_items(ctx, "k_u8_to_u32", k_u8_to_u32, x->n, x->masks.as<uint8_t>(), x->n, m.as<uint32_t>());
             BBK_HIP(bbk::copy_async(dst_masks_u32, m.p, x->n * 4, hipMemcpyDefault, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            BBK_HIP(hipStreamSynchronize(ctx->stream));  // m is about to go
         }
         BBK_HIP(hipStreamSynchronize(ctx->stream));
     });
@@ -181,11 +176,7 @@ int bbk_extindex_begin(bbk_ctx *ctx, unsigned k, bbk_extbuilder **out) {
     return guarded([&] {
         BBK_REQUIRE(ctx && out, BBK_ERR_ARG, "bbk_extindex_begin: NULL argument");
         check_ext_k(k);
-        auto b = std::make_unique<bbk_extbuilder>();
-        b->acc.ctx = ctx;
-        b->acc.k = k;
-        b->acc.with_mask = true;
-        *out = b.release();
+        *out = new bbk_extbuilder(ctx, k);
     });
 }
 
@@ -215,7 +206,13 @@ int bbk_extindex_finish_with_set(bbk_extbuilder *b, unsigned set_flags, bbk_kmer
     const int rc = guarded([&] {
         BBK_REQUIRE(b && set && out, BBK_ERR_ARG, "bbk_extindex_finish_with_set: NULL argument");
         BBK_HIP(hipSetDevice(b->acc.ctx->device));
-        std::unique_ptr<bbk_kmerset, void (*)(bbk_kmerset *)> s(both_strands_of(b->acc, set_flags), bbk_kmerset_free);
+        BBK_REQUIRE((set_flags & BBK_BOTH_STRANDS) &&
+                        !(set_flags & (BBK_WITH_COUNTS | BBK_WITH_MASKS | BBK_UNSORTED | BBK_CANONICAL)),
+                    BBK_ERR_ARG, "the set built beside an extension index is BBK_BOTH_STRANDS [| BBK_REFERENCE_ORDER]");
+        // the accumulator is not consumed (the index is built from the same canonical records next) and its payloads,
+        // mask bits, are not carried over
+        std::unique_ptr<bbk_kmerset, void (*)(bbk_kmerset *)> s(
+            finish_both_strands(b->acc, set_flags, /*consume=*/false, /*carry_payload=*/false), bbk_kmerset_free);
         *out = finish_extindex(b->acc);
         *set = s.release();
     });

@@ -13,7 +13,7 @@ enum { MSD_OP_NONE = 0, MSD_OP_COUNT = 1, MSD_OP_SUM = 2, MSD_OP_OR = 3 };  // p
 // slots[b * stride .. + count), and their high bits come from the bucket's level-1 segment (nw_key).  off is the
 // exclusive scan of the counts, so key c of the dense order is in the bucket b with off[b] <= c < off[b + 1].  The
 // records of the overflow path (already 8-byte keys) follow as `extra`.  Stage B's level 1 reads it as it stands
-// (msd_sort_reduce with view); every other consumer calls materialise() first.
+// (MsdRequest::expand of the view); every other consumer calls materialise() first.
 struct BucketView {
     DevBuf slots;   // u32 [nbuckets * stride]
     DevBuf dcount;  // u32 [nbuckets]: distinct records per bucket (0xFFFFFFFF: none here, see extra)
@@ -50,25 +50,59 @@ struct MsdOutput {
     BucketView view;
 };
 
-// Sort + reduce records that come either from reads (rd != null: canonical k-mers are extracted on
-// the fly, with_mask adds the InOutMask bits of every occurrence as payload) or from a key array
-// (d_keys[, d_vals], n).  Returns false when this path declines (key width, size, too much
-// overflow): the caller then uses the LSD path.  MSD_KEYS output is globally ascending.
-// tag_bits > 0 (8-byte keys, key array input, MSD_KEYS): bits [2k, 2k + tag_bits) of every key hold a tag
-// that is more significant than the k-mer (the caller put it there); the records are ordered by
-// (tag, k-mer) and the tag is cleared in the output.
-bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, int dmode, int op, const bbk_reads *rd, const void *d_keys,
-                     const uint32_t *d_vals, uint64_t n, bool with_mask, MsdOutput &out, unsigned tag_bits = 0,
-                     bool assume_distinct = false, unsigned expand_k = 0, BucketView *view = nullptr);
-// expand_k = k (key array input): the array holds n CANONICAL k-mers and the records are generated on the fly -- 2n of
-// them: every key and its reverse complement, with the tag of tag_bits (the XXH3 bucket of 16) written by the
-// level-1 kernels themselves.
-// assume_distinct (key array, KEYS / REF prefix): the caller expects no duplicates, so the sorted result is written
-// directly at the offsets of the input (no compaction pass); verified on the fly, redone in place otherwise.
-// view (with expand_k, instead of d_keys; n = view->n()): the canonical array is a live BucketView.  The key-slot
-// level 1 reads it in place and releases its slots; a pass that needs the dense array materialises it, and a key-slot
-// give-up after the slots are gone rebuilds it from the level-1 records.  view->keys may hold the dense array after
-// the call.
+// What msd_sort_reduce is asked to sort + reduce: the partition prefix, the per-key reduction and ONE input, built by
+// the named constructor of that input (so a view never goes with anything but an expanded set); tag_bits and
+// assume_distinct are set on the result where they apply.
+struct MsdRequest {
+    int prefix = MSD_HASH;  // MSD_HASH / MSD_KEYS / MSD_REF; MSD_KEYS output is globally ascending
+    int op = MSD_OP_NONE;
+    const bbk_reads *rd = nullptr;  // reads: canonical k-mers are extracted on the fly ...
+    bool with_mask = false;         // ... with the InOutMask bits of every occurrence as payload
+    const void *keys = nullptr;     // a record array: keys[, vals], n
+    const uint32_t *vals = nullptr;
+    uint64_t n = 0;
+    // expand_k = k: the array holds n CANONICAL k-mers and the records are generated on the fly -- 2n of them: every key
+    // and its reverse complement, with the tag of tag_bits (the XXH3 bucket of 16) written by the level-1 kernels
+    // themselves
+    unsigned expand_k = 0;
+    // ... or the canonical array is a live BucketView (n = view->n(), no payload).  The key-slot level 1 reads it in
+    // place and releases its slots; a pass that needs the dense array materialises it, and a key-slot give-up after the
+    // slots are gone rebuilds it from the level-1 records.  view->keys may hold the dense array after the call.
+    BucketView *view = nullptr;
+    // > 0 (8-byte keys, key array input, MSD_KEYS): bits [2k, 2k + tag_bits) of every key hold a tag that is more
+    // significant than the k-mer (the caller put it there, or the expansion does); the records are ordered by
+    // (tag, k-mer) and the tag is cleared in the output
+    unsigned tag_bits = 0;
+    // key array, KEYS / REF prefix: the caller expects no duplicates, so the sorted result is written directly at the
+    // offsets of the input (no compaction pass); verified on the fly, redone in place otherwise
+    bool assume_distinct = false;
+
+    static MsdRequest reads(int prefix, int op, const bbk_reads *rd, bool with_mask) {
+        MsdRequest r;
+        r.prefix = prefix, r.op = op, r.rd = rd, r.with_mask = with_mask;
+        return r;
+    }
+    static MsdRequest records(int prefix, int op, const void *keys, const uint32_t *vals, uint64_t n) {
+        MsdRequest r;
+        r.prefix = prefix, r.op = op, r.keys = keys, r.vals = vals, r.n = n;
+        return r;
+    }
+    static MsdRequest expand(int prefix, int op, unsigned k, const void *canon, const uint32_t *vals,
+                             uint64_t n) {
+        MsdRequest r = records(prefix, op, canon, vals, n);
+        r.expand_k = k;
+        return r;
+    }
+    static MsdRequest expand(int prefix, int op, unsigned k, BucketView &view) {
+        MsdRequest r = expand(prefix, op, k, nullptr, nullptr, view.n());
+        r.view = &view;
+        return r;
+    }
+};
+
+// Sort + reduce the records of `rq` (k-mer size k).  Returns false when this path declines (key width, size, too much
+// overflow): the caller then uses the LSD path.
+bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, const MsdRequest &rq, MsdOutput &out);
 
 // superk.hip: stage A of a batch of reads for 16- and 24-byte keys through super-k-mer records (distinct canonical
 // k-mers + count / OR of edge masks, in any order).  false: not taken or given up -- use msd_sort_reduce.

@@ -109,7 +109,7 @@ enum class Outcome {
     NeedDense,       // the input is a BucketView and the pass cannot read it in place: materialise it, run again
 };
 
-// Records of a call: reads (rd, see msd_sort_reduce) or a key array (keys[, vals], n)
+// Records of a call: reads (rd, see MsdRequest) or a key array (keys[, vals], n)
 struct MsdInput {
     const bbk_reads *rd;
     const void *keys;
@@ -1773,35 +1773,32 @@ static bool msd_run(bbk_ctx *ctx, unsigned k, int dmode, int op, const MsdInput 
     return MsdRunner<W>{ctx, k, dmode, op, strip_mask, assume_distinct, expand_k, expand_tag}.run_all(in, out);
 }
 
-bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, int dmode, int op, const bbk_reads *rd, const void *d_keys,
-                     const uint32_t *d_vals, uint64_t n, bool with_mask, MsdOutput &out, unsigned tag_bits,
-                     bool assume_distinct, unsigned expand_k, BucketView *view) {
-    BBK_REQUIRE(!view || (!d_keys && !d_vals && !rd && expand_k && n == view->n() && (view->live() || view->keys.p)),
+bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, const MsdRequest &rq, MsdOutput &out) {
+    BucketView *view = rq.view;
+    BBK_REQUIRE(!view || (!rq.keys && !rq.vals && !rq.rd && rq.expand_k && rq.n == view->n() && (view->live() || view->keys.p)),
                 BBK_ERR_INTERNAL, "bucket view input: expanded canonical keys only");
-    MsdInput in{rd, d_keys, d_vals, n, with_mask};
+    MsdInput in{rq.rd, rq.keys, rq.vals, rq.n, rq.with_mask};
     if (view && !view->live()) in.keys = view->keys.p;  // already dense
     else in.view = view;
-    if (tag_bits) {
+    if (rq.tag_bits) {
         // the tag sits right above the k-mer (bits [2k, 2k + tag_bits)): sort as a (k + tag_bits/2)-mer, clear the
         // tag on the way out
-        BBK_REQUIRE(words_of(k) == 1 && rd == nullptr && dmode == MSD_KEYS && tag_bits % 2 == 0 && 2 * k + tag_bits <= 64 &&
-                        (expand_k == 0 || expand_k == k),
-                    BBK_ERR_INTERNAL, "tagged sort needs 8-byte keys with %u spare bits", tag_bits);
-        return msd_run<1>(ctx, k + tag_bits / 2, dmode, op, in, out, assume_distinct, expand_k, expand_k != 0,
-                          (2 * k >= 64) ? ~0ull : ((1ull << (2 * k)) - 1ull));
+        BBK_REQUIRE(words_of(k) == 1 && rq.rd == nullptr && rq.prefix == MSD_KEYS && rq.tag_bits % 2 == 0 &&
+                        2 * k + rq.tag_bits <= 64 && (rq.expand_k == 0 || rq.expand_k == k),
+                    BBK_ERR_INTERNAL, "tagged sort needs 8-byte keys with %u spare bits", rq.tag_bits);
+        return msd_run<1>(ctx, k + rq.tag_bits / 2, rq.prefix, rq.op, in, out, rq.assume_distinct, rq.expand_k,
+                          rq.expand_k != 0, (2 * k >= 64) ? ~0ull : ((1ull << (2 * k)) - 1ull));
     }
 #ifdef BBK_PHASE_PROF
     struct Dump {
         ~Dump() { dump_phases(); }
     } dump_on_exit;
 #endif
-    switch (words_of(k)) {
-        case 1: return msd_run<1>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
-        case 2: return msd_run<2>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
-        case 3: return msd_run<3>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
-        case 4: return msd_run<4>(ctx, k, dmode, op, in, out, assume_distinct, expand_k);
-    }
-    return false;
+    bool done = false;
+    dispatch_w(words_of(k), [&](auto w) {
+        done = msd_run<decltype(w)::value>(ctx, k, rq.prefix, rq.op, in, out, rq.assume_distinct, rq.expand_k);
+    });
+    return done;
 }
 
 }  // namespace bbk

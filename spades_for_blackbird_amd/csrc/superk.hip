@@ -1300,7 +1300,7 @@ struct SuperkRun {
         sync();
         BBK_REQUIRE(!hflags[SKF_OUT] && fb_inst <= inst_ub, BBK_ERR_INTERNAL, "superk: expansion ran over its bound");
         MsdOutput mo;
-        if (!msd_sort_reduce(ctx, k, MSD_HASH, op, nullptr, fk.p, fv.as<uint32_t>(), fb_inst, false, mo)) return false;
+        if (!msd_sort_reduce(ctx, k, MsdRequest::records(MSD_HASH, op, fk.p, fv.as<uint32_t>(), fb_inst), mo)) return false;
         fk.release();
         fv.release();
         if (cursor_now + mo.n > out_cap)  // room for the appended records

@@ -1,5 +1,6 @@
 """GPU parity tests of the k-mer counting path (through the C ABI) against the CPU oracle and
 the reference's golden vectors.  Bit-exact: integer/byte work."""
+import functools
 import hashlib
 import os
 
@@ -457,3 +458,104 @@ def test_device_info_and_xcd_switches(monkeypatch):
     want = "%s %s %s" % (hashlib.md5(a[0].tobytes()).hexdigest(), hashlib.md5(a[1].tobytes()).hexdigest(),
                          hashlib.md5(b55.tobytes()).hexdigest())
     assert out.stdout.strip().splitlines()[-1] == want
+
+
+# ---- the shared seams of count.hip: the reference-order step, the ordered export, the empty result --------------------
+
+@functools.lru_cache(maxsize=None)
+def ref_case(k):
+    """reads of test_reference_order_flag's shape (tens of thousands of distinct records: several partition tiles at
+    every key width, all 16 buckets populated) and their final_kmers records with counts; computed once per k, read-only"""
+    reads = synth_reads(600, read_len=150, genome_len=5000, sub_rate=0.01, seed=100 + k, n_rate=0.001)
+    reads += ["", "ACGT" * 40, "T" * 150]
+    exp, expc = O.kmercount(reads, k, 16, 2, with_counts=True)
+    exp.setflags(write=False)
+    expc.setflags(write=False)
+    return tuple(reads), exp, expc
+
+
+def assert_final_kmers(s, exp, expc=None):
+    """the set is stored in the final_kmers order and equals the oracle's records (and counts)"""
+    assert s.device_keys()[1] == B.ORDER_REFERENCE_BUCKETS16
+    if expc is None:
+        assert np.array_equal(s.export(B.ORDER_REFERENCE_BUCKETS16), exp)
+    else:
+        got, gotc = s.export(B.ORDER_REFERENCE_BUCKETS16, with_counts=True)
+        assert np.array_equal(got, exp) and np.array_equal(gotc, expc)
+
+
+def check_ref_order_by_extra_pass(ctx, k):
+    """the three entry points that bring an ascending both-strand set into the final_kmers order with one stable pass on
+    the XXH3 bucket (to_reference_order): a count and both_strands() carry the counts through it, the set beside an
+    extension index has none.  The extension index takes k + 1 < BBK_MAX_K, so its half runs at k = 126 (still 32-byte
+    keys) where the others run at 127."""
+    reads, exp, expc = ref_case(k)
+    r = ctx.reads_from_ascii(list(reads))
+    assert_final_kmers(ctx.count(r, k, B.BOTH_STRANDS | B.REFERENCE_ORDER | B.WITH_COUNTS), exp, expc)
+    assert_final_kmers(ctx.count(r, k, B.CANONICAL | B.WITH_COUNTS).both_strands(B.REFERENCE_ORDER), exp, expc)
+    kx = min(k, 126)  # BBK_MAX_K - 2
+    if kx != k:
+        with pytest.raises(B.BBKError, match="out of range"):
+            ctx.count_extindex(r, k, B.BOTH_STRANDS | B.REFERENCE_ORDER)
+        reads, exp, _ = ref_case(kx)
+        r = ctx.reads_from_ascii(list(reads))
+    s, x = ctx.count_extindex(r, kx, B.BOTH_STRANDS | B.REFERENCE_ORDER)
+    assert_final_kmers(s, exp)
+    assert len(x) > 0
+
+
+@pytest.mark.parametrize("k", [33, 77, 127])
+def test_wide_ref_order_by_extra_pass_with_payload(ctx, monkeypatch, k):
+    """BBK_NO_WIDE_REF=1 (read per call): keys above 16 bytes are sorted ascending and take the extra pass; k = 33 keeps
+    the REF prefix.  Either way the stored set is the oracle's final_kmers, counts included."""
+    monkeypatch.setenv("BBK_NO_WIDE_REF", "1")
+    check_ref_order_by_extra_pass(ctx, k)
+
+
+@pytest.mark.parametrize("k", [21, 55])
+def test_ascending_export_of_reference_order_set_with_counts(ctx, k):
+    """export(ORDER_SORTED) of a set stored in the final_kmers order sorts a copy, payload alongside: keys and counts equal
+    those of a set that was counted ascending"""
+    reads, _, _ = ref_case(k)
+    r = ctx.reads_from_ascii(list(reads))
+    s = ctx.count(r, k, B.BOTH_STRANDS | B.REFERENCE_ORDER | B.WITH_COUNTS)
+    assert s.device_keys()[1] == B.ORDER_REFERENCE_BUCKETS16
+    a = ctx.count(r, k, B.BOTH_STRANDS | B.WITH_COUNTS)
+    assert a.device_keys()[1] == B.ORDER_SORTED
+    gk, gc = s.export(B.ORDER_SORTED, with_counts=True)
+    ak, ac = a.export(B.ORDER_SORTED, with_counts=True)
+    assert len(gk) > 10_000
+    assert np.array_equal(gk, ak) and np.array_equal(gc, ac)
+
+
+def bucket_offsets(ctx, s):
+    off = np.full(17, 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+    B.engine._check(B.load_library().bbk_kmerset_bucket_offsets(ctx._h, s._h, B.engine._ptr(off)))
+    return off
+
+
+def test_empty_sets_through_every_constructor(ctx):
+    """size 0, the order the flags asked for, empty exports, seventeen zero bucket offsets for the final_kmers order"""
+    import torch
+    k = 21
+    dk = torch.zeros(1, dtype=torch.int64, device="cuda")
+    dc = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    for counts in (None, dc):
+        s = ctx.kmerset_from_device(dk, 0, k, d_counts=counts)
+        assert len(s) == 0 and s.device_keys()[1] == B.ORDER_SORTED
+        keys, cnt = s.export(B.ORDER_SORTED, with_counts=True)
+        assert keys.shape == (0, 1) and cnt.shape == (0,)
+        assert s.export(B.ORDER_REFERENCE_BUCKETS16).shape == (0, 1)
+        assert s.verify_order()[:2] == (0, 0)
+    short = ctx.reads_from_ascii(["", "ACGT", "ACGTACGTAC", "N" * 40])
+    for wc in (0, B.WITH_COUNTS):
+        canon = ctx.count(short, k, B.CANONICAL | wc)
+        assert len(canon) == 0 and canon.device_keys()[1] == B.ORDER_SORTED
+        for s in (canon.both_strands(B.REFERENCE_ORDER), ctx.count(short, k, B.BOTH_STRANDS | B.REFERENCE_ORDER | wc)):
+            assert len(s) == 0 and s.device_keys()[1] == B.ORDER_REFERENCE_BUCKETS16
+            assert not bucket_offsets(ctx, s).any()
+            keys, cnt = s.export(B.ORDER_REFERENCE_BUCKETS16, with_counts=True)
+            assert keys.shape == (0, 1) and cnt.shape == (0,)
+            assert s.export(B.ORDER_SORTED).shape == (0, 1)
+        assert len(canon.both_strands()) == 0 and canon.both_strands().device_keys()[1] == B.ORDER_SORTED

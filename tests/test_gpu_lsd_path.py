@@ -1,6 +1,7 @@
 """GPU: the general (LSD) path of counting, merging and the extension index, and the sort / unique / scan primitives it
-is built on (count.hip: dedup_reads' extract + sort + unique, lsd_sort_unique, expand_both_strands' expand + sort,
-bbk_kmerset_from_device_ex's inline copy; primitives.hip: sort_records, unique_records, exclusive_scan_u64).
+is built on (count.hip: LsdSort behind dedup_reads' extract + sort + unique, lsd_sort_unique, expand_both_strands'
+expand + sort and the ascending export of a final_kmers set; primitives.hip: sort_records, unique_records,
+exclusive_scan_u64).
 
 The engine takes this path whenever an MSD pass declines (one k-mer making up more than a quarter of a batch: poly-A
 or amplicon libraries), and finishes oversized MSD buckets with the same primitives.  BBK_DISABLE_MSD=1 forces it (read
@@ -22,6 +23,7 @@ import spades_for_blackbird_amd as B
 from oracle import oracle as O
 from spades_for_blackbird_amd.tools import gfa_canon
 from tests.helpers import rc, synth_reads
+from tests.test_gpu_count import check_ref_order_by_extra_pass
 
 pytestmark = pytest.mark.gpu
 
@@ -245,6 +247,14 @@ def test_forced_count_vs_oracle(lsd, monkeypatch, k):
             assert_lsd(ctx, "extract", "expand", "hist", "scatter", "unique")
             got, gotc = fs.export(B.ORDER_REFERENCE_BUCKETS16, with_counts=True)
             assert np.array_equal(got, exp) and np.array_equal(gotc, expc)
+
+
+def test_forced_wide_ref_order_by_extra_pass_with_payload(lsd, monkeypatch):
+    """test_gpu_count's wide-key case on the forced general path: the ascending result of expand + sort + unique takes
+    the one stable pass on the XXH3 bucket, counts alongside"""
+    monkeypatch.setenv("BBK_NO_WIDE_REF", "1")
+    check_ref_order_by_extra_pass(lsd, 77)
+    assert_lsd(lsd, "extract", "expand", "hist", "scatter", "unique")
 
 
 def oracle_ext(reads, k):
