@@ -23,6 +23,31 @@ def read_fastq_gz(path):
     return out
 
 
+def gpu_gfa(ctx, reads, k, tmp_path, name="g.gfa"):
+    """(GFA text, Unitigs) of the engine for a list of reads"""
+    r = ctx.reads_from_ascii(reads)
+    x = ctx.extindex(r, k)
+    u = ctx.unitigs(x)
+    p = str(tmp_path / name)
+    u.write_gfa(p)
+    with open(p) as f:
+        return f.read(), u
+
+
+def gfa_bytes(u, path):
+    u.write_gfa(str(path))
+    with open(str(path), "rb") as f:
+        return f.read()
+
+
+def expected_gfa(u, k):
+    """the GFA text of a result without coverage, from its exported sequences and links"""
+    lines = ["S\t%d\t%s\tDP:f:0\tKC:i:0\n" % (3 + 2 * i, s) for i, s in enumerate(u.sequences())]
+    lines += ["L\t%d\t%s\t%d\t%s\t%dM\n" % (3 + 2 * a, "+" if oa else "-", 3 + 2 * b, "+" if ob else "-", k)
+              for a, oa, b, ob in u.links().tolist()]
+    return "".join(lines).encode()
+
+
 def synth_reads(n_reads, read_len=150, genome_len=None, sub_rate=0.005, seed=42, n_rate=0.0):
     """Synthetic reads in the shape of SURVEY 8(d): uniform genome, uniform starts,
     random strand, substitutions; optional N injection for the LongestValid rule."""
@@ -42,3 +67,33 @@ def synth_reads(n_reads, read_len=150, genome_len=None, sub_rate=0.005, seed=42,
     if n_rate > 0:
         asc = np.where(rng.random(asc.shape) < n_rate, np.uint8(ord("N")), asc)
     return [bytes(row).decode() for row in asc]
+
+
+def polya_reads(seed=5, n_tx=8, read_len=150, n_reads=1500, n_tail=400, sub_rate=0.01):
+    """RNA-seq-shaped reads: random transcripts of 300-3000 bp with poly-A tails of 10-60 bp, reads on random strands
+    with 1 % substitutions (errors inside the tails make low-complexity tips), a share of them ending inside the tail;
+    plus a few poly-C reads (complex flanks: the C run becomes a junction) and a few (AT)n reads (never clipped)."""
+    rng = np.random.default_rng(seed)
+    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
+    txs = [np.concatenate([rng.integers(0, 4, size=int(rng.integers(300, 3001)), dtype=np.uint8),
+                           np.zeros(int(rng.integers(10, 61)), dtype=np.uint8)]) for _ in range(n_tx)]
+    reads = []
+
+    def emit(t, start):
+        r = t[start:start + read_len].copy()
+        err = rng.random(len(r)) < sub_rate
+        r[err] = (r[err] + rng.integers(1, 4, size=int(err.sum()), dtype=np.uint8)) & 3
+        if rng.random() < 0.5:
+            r = (3 - r)[::-1]
+        reads.append(bytes(lut[r]).decode())
+    for _ in range(n_reads):
+        t = txs[int(rng.integers(0, n_tx))]
+        emit(t, int(rng.integers(0, len(t) - read_len + 1)))
+    for _ in range(n_tail):
+        t = txs[int(rng.integers(0, n_tx))]
+        emit(t, len(t) - int(rng.integers(0, 10)) - read_len)
+    for _ in range(4):
+        flank = [bytes(lut[rng.integers(0, 4, size=10, dtype=np.uint8)]).decode() for _ in range(2)]
+        reads.append(flank[0] + "C" * 130 + flank[1])
+        reads.append("AT" * 75)
+    return reads

@@ -12,39 +12,9 @@ import spades_for_blackbird_amd as B
 from oracle import oracle as O
 from spades_for_blackbird_amd.tools import gfa_canon
 from tests import atclip_restated as R
-from tests.helpers import synth_reads
+from tests.helpers import polya_reads, synth_reads
 
 pytestmark = pytest.mark.gpu
-
-
-def polya_reads(seed=5, n_tx=8, read_len=150, n_reads=1500, n_tail=400, sub_rate=0.01):
-    """RNA-seq-shaped reads: random transcripts of 300-3000 bp with poly-A tails of 10-60 bp, reads on random strands
-    with 1 % substitutions (errors inside the tails make low-complexity tips), a share of them ending inside the tail;
-    plus a few poly-C reads (complex flanks: the C run becomes a junction) and a few (AT)n reads (never clipped)."""
-    rng = np.random.default_rng(seed)
-    lut = np.frombuffer(b"ACGT", dtype=np.uint8)
-    txs = [np.concatenate([rng.integers(0, 4, size=int(rng.integers(300, 3001)), dtype=np.uint8),
-                           np.zeros(int(rng.integers(10, 61)), dtype=np.uint8)]) for _ in range(n_tx)]
-    reads = []
-
-    def emit(t, start):
-        r = t[start:start + read_len].copy()
-        err = rng.random(len(r)) < sub_rate
-        r[err] = (r[err] + rng.integers(1, 4, size=int(err.sum()), dtype=np.uint8)) & 3
-        if rng.random() < 0.5:
-            r = (3 - r)[::-1]
-        reads.append(bytes(lut[r]).decode())
-    for _ in range(n_reads):
-        t = txs[int(rng.integers(0, n_tx))]
-        emit(t, int(rng.integers(0, len(t) - read_len + 1)))
-    for _ in range(n_tail):
-        t = txs[int(rng.integers(0, n_tx))]
-        emit(t, len(t) - int(rng.integers(0, 10)) - read_len)
-    for _ in range(4):
-        flank = [bytes(lut[rng.integers(0, 4, size=10, dtype=np.uint8)]).decode() for _ in range(2)]
-        reads.append(flank[0] + "C" * 130 + flank[1])
-        reads.append("AT" * 75)
-    return reads
 
 
 READS = polya_reads()

@@ -9,7 +9,7 @@ import pytest
 import spades_for_blackbird_amd as B
 from oracle import oracle as O
 from spades_for_blackbird_amd.tools import gfa_canon
-from tests.helpers import rc, read_fastq_gz, synth_reads
+from tests.helpers import expected_gfa, gfa_bytes, gpu_gfa, rc, read_fastq_gz, synth_reads
 
 pytestmark = pytest.mark.gpu
 
@@ -26,16 +26,6 @@ def oracle_table(reads, k):
     keys, masks = x.kmers, x.masks
     order = np.lexsort([keys[:, j] for j in range(keys.shape[1] - 1, -1, -1)])
     return keys[order], masks[order]
-
-
-def gpu_gfa(ctx, reads, k, tmp_path, name="g.gfa"):
-    r = ctx.reads_from_ascii(reads)
-    x = ctx.extindex(r, k)
-    u = ctx.unitigs(x)
-    p = str(tmp_path / name)
-    u.write_gfa(p)
-    with open(p) as f:
-        return f.read(), u
 
 
 @pytest.mark.parametrize("k", [3, 5, 9, 21, 31, 33, 55, 63, 65, 99])
@@ -571,20 +561,6 @@ def residency_oracle():
 def build_unitigs(ctx, reads, k):
     r = ctx.reads_from_ascii(reads)
     return r, ctx.unitigs(ctx.extindex(r, k))
-
-
-def gfa_bytes(u, path):
-    u.write_gfa(str(path))
-    with open(str(path), "rb") as f:
-        return f.read()
-
-
-def expected_gfa(u, k):
-    """the GFA text of a result without coverage, from its exported sequences and links"""
-    lines = ["S\t%d\t%s\tDP:f:0\tKC:i:0\n" % (3 + 2 * i, s) for i, s in enumerate(u.sequences())]
-    lines += ["L\t%d\t%s\t%d\t%s\t%dM\n" % (3 + 2 * a, "+" if oa else "-", 3 + 2 * b, "+" if ob else "-", k)
-              for a, oa, b, ob in u.links().tolist()]
-    return "".join(lines).encode()
 
 
 @pytest.mark.parametrize("k", [9, 21, 101])
