@@ -449,6 +449,46 @@ int bbk_hamclusters_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_l
 int bbk_hamclusters_write(bbk_ctx *ctx, const bbk_hamclusters *h, const char *path);
 void bbk_hamclusters_free(bbk_hamclusters *h);
 
+/* ---- quality-aware k-mer statistics: replaces KMerDataCounter::FillKMerData / KMerDataFiller over a KMerData
+ *      (projects/hammer/kmer_data.cpp:119-187,369-399): one KMerStat per k-mer (projects/hammer/kmer_stat.hpp:120-149)
+ *      -- the occurrence count, total_qual and the saturating 6-bit per-position quality sums (QualBitSet,
+ *      kmer_stat.hpp:49-118) that everything BayesHammer does after the clustering reads ------------------------------- */
+typedef struct bbk_quals bbk_quals;         /* one quality byte per base of a bbk_reads, in HBM                   */
+typedef struct bbk_kmerstats bbk_kmerstats; /* the statistics of every k-mer of a set, in HBM                     */
+/* h_qual: the quality of every base with the offset already subtracted (Read's qual_, io/reads/read.hpp), read i at
+ * [h_offsets[i], h_offsets[i + 1]) (n_reads + 1 entries).  BBK_ERR_ARG unless n_reads and every length equal those of
+ * `reads` -- a read that LongestValid shortened no longer matches -- and for a quality above 93 (33 + 93 is the last
+ * printable character; the bound keeps the statistics' sums from overflowing).  `reads` must outlive the result. */
+int bbk_quals_from_host(bbk_ctx *ctx, const bbk_reads *reads, const uint8_t *h_qual, const uint64_t *h_offsets,
+                        uint64_t n_reads, bbk_quals **out);
+void bbk_quals_free(bbk_quals *q);
+/* set: ascending BBK_BOTH_STRANDS set, k <= 32, fewer than 2^32 - 2 k-mers; it must outlive the statistics, and an
+ * index is a position in it.  BBK_ERR_ARG for a BBK_CANONICAL, BBK_UNSORTED or BBK_REFERENCE_ORDER set and for k > 32.
+ * All statistics start as KMerStat() does: count 0, total_qual 1, sums 0. */
+int bbk_kmerstats_begin(bbk_ctx *ctx, const bbk_kmerset *set, bbk_kmerstats **out);
+/* Every k-mer position p of every read is one occurrence (the reads are free of N; which positions
+ * ValidKMerGenerator<K>(read, 2) yields after Read::trimNsAndBadQuality, valid_kmer_generator.hpp:147-199 and
+ * io/reads/read.hpp:87-122, is the caller's business: spades-kmerdata cuts the reads accordingly).  With
+ * cp = the product over the window of Prob(q) = 1 - (q < 3 ? 0.75 : 10^(-q / 10)) in double (main.cpp:103-105), the
+ * k-mer is merged with the qualities q[p .. p + k) and its reverse complement with the same qualities reversed
+ * (PushKMer / PushKMerRC, kmer_data.cpp:125-154), each only if it is in the set; Merge (:119-123) is count += 1,
+ * total_qual *= (float)(1 - cp), sum[i] = min(63, sum[i] + (q[i] & 63)).  A k-mer that is its own reverse complement
+ * is merged twice.  Counts and sums are exact; total_qual is carried as a fixed-point sum of log2 of the factors, so
+ * the result is the same bytes for any order and batching of the reads (the reference's float product depends on its
+ * thread timing; the difference stays inside that spread).  `quals` must have been made for `reads`. */
+int bbk_kmerstats_push(bbk_kmerstats *ks, const bbk_reads *reads, const bbk_quals *quals);
+/* after the last push and before an export or a write; pushing again afterwards is allowed and needs another finish */
+int bbk_kmerstats_finish(bbk_kmerstats *ks);
+uint64_t bbk_kmerstats_size(const bbk_kmerstats *ks);
+/* h_count: size u32; h_total_qual: size floats; h_qual_words: size x ceil(6k / 64) u64, the QualBitSet of every k-mer
+ * (sum i in bits [6i, 6i + 6) of the 6k-bit little-endian string).  Any pointer may be NULL. */
+int bbk_kmerstats_export(bbk_ctx *ctx, const bbk_kmerstats *ks, uint32_t *h_count, float *h_total_qual,
+                         uint64_t *h_qual_words);
+/* one binary_write(KMerStat) record per k-mer (kmer_stat.hpp:170-175): u32 count << 1 (the good bit is 0, mark_bad), float
+ * total_qual, the QualBitSet words: 24 bytes at k = 21.  BBK_ERR_ARG when a count is 2^31 or more. */
+int bbk_kmerstats_write(bbk_ctx *ctx, const bbk_kmerstats *ks, const char *path);
+void bbk_kmerstats_free(bbk_kmerstats *ks);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

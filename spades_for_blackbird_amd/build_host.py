@@ -12,8 +12,9 @@ PROGRAMS = {"spades-kmercount": "kmercount_main.cpp", "spades-gbuilder": "gbuild
             "unitig-coverage": "unitig_coverage_main.cpp", "spades-gmapper": "gmapper_main.cpp",
             "kmer_multiplicity_counter": "kmer_multiplicity_counter_main.cpp",
             "contig_abundance_counter": "contig_abundance_counter_main.cpp",
-            "spades-hamcluster": "hamcluster_main.cpp"}
-HEADERS = ["common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp"]
+            "spades-hamcluster": "hamcluster_main.cpp", "spades-kmerdata": "kmerdata_main.cpp",
+            "bbk-hammer-reads-dump": "hammer_reads_dump_main.cpp"}
+HEADERS = ["common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp", "hammer_reads.hpp"]
 
 
 def build(force=False, verbose=False):
@@ -36,13 +37,14 @@ def build(force=False, verbose=False):
     return out
 
 
-def build_sanitized(force=False):
-    """Host sanitizer build (the reference's SPADES_ENABLE_ASAN option, cmake/options.cmake:18-23): the host-only
-    parser tool compiled with AddressSanitizer + UndefinedBehaviorSanitizer (CPU only: GPU ASAN is not available on
-    this pool).  tests/test_ingest.py runs the parser corner cases through it."""
+def build_sanitized(force=False, program="bbk-fastx-dump"):
+    """Host sanitizer build (the reference's SPADES_ENABLE_ASAN option, cmake/options.cmake:18-23): a host-only
+    tool (bbk-fastx-dump or bbk-hammer-reads-dump) compiled with AddressSanitizer + UndefinedBehaviorSanitizer (CPU
+    only: GPU ASAN is not available on this pool).  tests/test_ingest.py runs the parser corner cases through the
+    first, tests/test_kmerdata_host.py the trimming and generator corner cases through the second."""
     os.makedirs(BIN, exist_ok=True)
-    exe = os.path.join(BIN, "bbk-fastx-dump-asan")
-    srcp = os.path.join(HOST, "fastx_dump_main.cpp")
+    exe = os.path.join(BIN, program + "-asan")
+    srcp = os.path.join(HOST, PROGRAMS[program])
     deps = [os.path.join(HOST, h) for h in HEADERS] + [srcp]
     stale = not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps if os.path.exists(d))
     if force or stale:

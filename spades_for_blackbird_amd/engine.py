@@ -40,6 +40,8 @@ SYMBOLS = [
     "bbk_kmerprofile_free",
     "bbk_kmerset_hamming_clusters", "bbk_hamclusters_count", "bbk_hamclusters_size", "bbk_hamclusters_replayed",
     "bbk_hamclusters_export", "bbk_hamclusters_write", "bbk_hamclusters_free",
+    "bbk_quals_from_host", "bbk_quals_free", "bbk_kmerstats_begin", "bbk_kmerstats_push", "bbk_kmerstats_finish",
+    "bbk_kmerstats_size", "bbk_kmerstats_export", "bbk_kmerstats_write", "bbk_kmerstats_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -231,6 +233,18 @@ def load_library():
     L.bbk_hamclusters_write.argtypes = [vp, vp, C.c_char_p]
     L.bbk_hamclusters_free.argtypes = [vp]
     L.bbk_hamclusters_free.restype = None
+    L.bbk_quals_from_host.argtypes = [vp, vp, vp, vp, u64, C.POINTER(vp)]
+    L.bbk_quals_free.argtypes = [vp]
+    L.bbk_quals_free.restype = None
+    L.bbk_kmerstats_begin.argtypes = [vp, vp, C.POINTER(vp)]
+    L.bbk_kmerstats_push.argtypes = [vp, vp, vp]
+    L.bbk_kmerstats_finish.argtypes = [vp]
+    L.bbk_kmerstats_size.restype = u64
+    L.bbk_kmerstats_size.argtypes = [vp]
+    L.bbk_kmerstats_export.argtypes = [vp, vp, vp, vp, vp]
+    L.bbk_kmerstats_write.argtypes = [vp, vp, C.c_char_p]
+    L.bbk_kmerstats_free.argtypes = [vp]
+    L.bbk_kmerstats_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -407,6 +421,18 @@ class Context:
         _check(self._L.bbk_reads_median_filter(self._h, reads._h, counts._h, threshold, _ptr(keep), C.byref(kept)))
         assert int(kept.value) == int(keep.sum())
         return keep
+
+    def quals(self, reads, qual_bytes, offsets):
+        """Qualities of `reads` (offset already subtracted): qual_bytes uint8, read i at [offsets[i], offsets[i + 1]);
+        every length must equal the read's.  The reads must outlive the result."""
+        q = np.ascontiguousarray(np.frombuffer(qual_bytes, dtype=np.uint8) if isinstance(qual_bytes, (bytes, bytearray))
+                                 else qual_bytes, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        h = C.c_void_p()
+        _check(self._L.bbk_quals_from_host(self._h, reads._h, _ptr(q), _ptr(offsets), len(offsets) - 1, C.byref(h)))
+        r = Quals(self, h)
+        r._reads = reads
+        return r
 
     def extindex(self, reads, k):
         """DeBruijnExtensionIndexBuilder::BuildExtensionIndexFromStream analogue."""
@@ -596,8 +622,59 @@ class KMerSet(_Handle):
         _check(self._L.bbk_kmerset_hamming_clusters(self.ctx._h, self._h, tau, lock_size, chunk, C.byref(h)))
         return HamClusters(self.ctx, h)
 
+    def kmer_stats(self):
+        """KMerData over this ascending both-strand set (k <= 32): KmerStats, all empty; the set must outlive it."""
+        h = C.c_void_p()
+        _check(self._L.bbk_kmerstats_begin(self.ctx._h, self._h, C.byref(h)))
+        ks = KmerStats(self.ctx, h)
+        ks._set, ks.k = self, self.k
+        return ks
+
 
 KmerSet = KMerSet
+
+
+class Quals(_Handle):
+    """one quality byte per base of a Reads (offset already subtracted)"""
+    _free = "bbk_quals_free"
+
+
+class KmerStats(_Handle):
+    """BayesHammer's KMerStat of every k-mer of a set: count, total_qual and the saturating 6-bit quality sums; an index
+    is a position in the ascending set"""
+    _free = "bbk_kmerstats_free"
+
+    def __len__(self):
+        return int(self._L.bbk_kmerstats_size(self._h))
+
+    def push(self, reads, quals):
+        """every k-mer position of every read is an occurrence, of the k-mer and of its reverse complement"""
+        _check(self._L.bbk_kmerstats_push(self._h, reads._h, quals._h))
+
+    def finish(self):
+        _check(self._L.bbk_kmerstats_finish(self._h))
+
+    def export(self):
+        """(count np.uint32[n], total_qual np.float32[n], qual_words np.uint64[n, ceil(6k / 64)])"""
+        n, nw = len(self), (6 * self.k + 63) // 64
+        cnt = np.zeros(n, dtype=np.uint32)
+        tq = np.zeros(n, dtype=np.float32)
+        qw = np.zeros((n, nw), dtype=np.uint64)
+        _check(self._L.bbk_kmerstats_export(self.ctx._h, self._h, _ptr(cnt), _ptr(tq), _ptr(qw)))
+        return cnt, tq, qw
+
+    def qual_matrix(self):
+        """np.uint8[n, k]: the quality sums unpacked (sum i of a k-mer is bits [6i, 6i + 6) of its words)"""
+        qw = self.export()[2]
+        bits = np.unpackbits(np.ascontiguousarray(qw).view(np.uint8), axis=1, bitorder="little")[:, :6 * self.k]
+        return (bits.reshape(len(self), self.k, 6) << np.arange(6, dtype=np.uint8)).sum(axis=2).astype(np.uint8)
+
+    def write(self, path):
+        """one binary_write(KMerStat) record per k-mer: u32 count << 1, float total_qual, the QualBitSet words"""
+        _check(self._L.bbk_kmerstats_write(self.ctx._h, self._h, str(path).encode()))
+
+    def close(self):
+        self.free()
 
 
 class HamClusters(_Handle):

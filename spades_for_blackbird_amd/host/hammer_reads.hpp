@@ -1,0 +1,118 @@
+// hammer_reads.hpp -- which k-mer positions of a read BayesHammer's KMerDataFiller pushes (host side of
+// spades-kmerdata; no GPU needed).  The two rules are restated literally, quirks included, without the probabilities
+// (those are the device's):
+//   Read::trimNsAndBadQuality / trimLeftRight   common/io/reads/read.hpp:87-122
+//   ValidKMerGenerator<K>(read, 2)              projects/hammer/valid_kmer_generator.hpp:147-199
+//   KMerDataFiller::operator()                  projects/hammer/kmer_data.cpp:163-186
+// Consecutive valid starts a..b are handed out as one stretch [a, b + k) of the read: a stretch holds no character other
+// than ACGT (every window the generator yields is checked base by base), and its k-mer positions are exactly the valid
+// starts a..b -- so one stretch is one read of the engine, for bbk_count_push_* and bbk_kmerstats_push alike.
+#pragma once
+
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace bbkhost {
+namespace hammer {
+
+inline bool is_nucl(char c) {  // common/sequence/nucl.hpp:45-62
+    switch (c) {
+        case 'A': case 'C': case 'G': case 'T':
+        case 'a': case 'c': case 'g': case 't':
+            return true;
+        default:
+            return false;
+    }
+}
+
+struct Stretch {
+    uint32_t start, length;  // in the read as parsed
+};
+
+// seq / qual: the read as parsed, qualities with the offset already subtracted (Read's qual_ is a string of char).
+// Appends the stretches of the read to out; returns how many.
+inline size_t valid_stretches(const std::string &seq_in, const std::string &qual_in, unsigned k, int trim_quality,
+                              std::vector<Stretch> &out) {
+    // ---- Read::trimNsAndBadQuality(trim_quality) on a copy (kmer_data.cpp:167-171) ----
+    std::string seq_ = seq_in, qual_ = qual_in;
+    int start = 0;
+    for (; start < (int)seq_.size(); ++start) {
+        if (seq_[start] != 'N' && (int)qual_[start] > trim_quality) break;
+    }
+    int end = 0;
+    for (end = (int)seq_.size() - 1; end > -1; --end) {
+        if (seq_[end] != 'N' && (int)qual_[end] > trim_quality) break;
+    }
+    {  // trimLeftRight(ltrim = start, rtrim = end)
+        const int ltrim = start, rtrim = end;
+        if (ltrim >= (int)seq_.size() || rtrim < 0 || rtrim < ltrim) return 0;  // nothing left
+        if (ltrim > 0) {
+            seq_.erase(0, ltrim);
+            qual_.erase(0, ltrim);
+        }
+        // seq_.size() is the size AFTER the left erase: with ltrim > 0 the second test can fail for an rtrim that is
+        // before the end, and the bad tail stays
+        if (rtrim - ltrim + 1 < (int)seq_.size() && rtrim < (int)seq_.size() - ltrim - 1) {
+            seq_.erase(rtrim - ltrim + 1, std::string::npos);
+            qual_.erase(rtrim - ltrim + 1, std::string::npos);
+        }
+    }
+    if (seq_.size() < k) return 0;  // sz < hammer::K
+
+    // ---- ValidKMerGenerator<k>(cr, 2): Reset = TrimBadQuality + Next ----
+    const size_t len_ = seq_.size();
+    const uint8_t bad_quality_threshold_ = 2;
+    auto GetQual = [&](uint32_t pos) -> uint8_t { return pos >= len_ ? 2 : (uint8_t)qual_[pos]; };
+    size_t pos_ = 0, end_ = 0;
+    for (; pos_ < len_; ++pos_) {
+        if (GetQual((uint32_t)pos_) >= bad_quality_threshold_) break;
+    }
+    end_ = len_;
+    for (; end_ > pos_; --end_) {
+        if (GetQual((uint32_t)(end_ - 1)) >= bad_quality_threshold_) break;
+    }
+    bool has_more_ = true, first = true;
+    size_t kmer_start = 0;  // start of the current k-mer: pos() - 1
+    auto Next = [&] {
+        if (pos_ + k > end_) {
+            has_more_ = false;
+        } else if (first || !is_nucl(seq_[pos_ + k - 1])) {
+            // looks for a new k-mer up to len_ (not end_) and does not check the window it finds against end_
+            uint32_t start_hypothesis = (uint32_t)pos_;
+            uint32_t i = (uint32_t)pos_;
+            for (; i < len_; ++i) {
+                if (i == k + start_hypothesis) break;
+                if (!is_nucl(seq_[i])) start_hypothesis = i + 1;
+            }
+            if (i == k + start_hypothesis) {
+                kmer_start = start_hypothesis;
+                pos_ = start_hypothesis + 1;
+            } else {
+                has_more_ = false;
+            }
+        } else {
+            kmer_start = pos_;
+            ++pos_;
+        }
+        first = false;
+    };
+    Next();
+    size_t added = 0;
+    bool open = false;
+    while (has_more_) {
+        const uint32_t s = (uint32_t)(start + kmer_start);  // back in the read as parsed
+        if (open && out.back().start + out.back().length - k + 1 == s) {
+            ++out.back().length;
+        } else {
+            out.push_back({s, k});
+            open = true;
+            ++added;
+        }
+        Next();
+    }
+    return added;
+}
+
+}  // namespace hammer
+}  // namespace bbkhost

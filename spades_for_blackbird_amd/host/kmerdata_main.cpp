@@ -1,0 +1,223 @@
+// spades-kmerdata: BayesHammer's counting phase -- the k-mer set and one KMerStat per k-mer -- on the MI355X engine behind
+// the C ABI (include/bbk.h).  Not a drop-in: the reference has this only inside spades-hammer
+// (projects/hammer/main.cpp:122-171: KMerDataCounter::BuildKMerIndex, the Hamming clustering, then
+// KMerDataCounter::FillKMerData, "Collecting K-mer information, this takes a while"); this tool is that sequence alone.
+//   -k/--kmer <int=21>  -t/--threads <int>  -b/--bufsize <bytes>  -o/--output <prefix>  -d/--dataset <yaml>  [input files...]
+//   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster)
+// Every FASTQ record is cut into the stretches of its valid k-mer starts (hammer_reads.hpp: input_trim_quality 4 of
+// configs/hammer/config.info, then ValidKMerGenerator); a stretch is one read of the engine.
+//   pass 1  the stretches, in blocks of -b bytes, through bbk_count_begin / push / finish(BBK_BOTH_STRANDS)
+//   pass 2  the same files again: the same stretches with their qualities through bbk_kmerstats_push
+// Output:
+//   <prefix>.kmers        the ascending both-strand k-mers (final_kmers records), as spades-hamcluster writes them: index
+//                         i of the other files is record i
+//   <prefix>.kmstat       one binary_write(KMerStat) record per k-mer (projects/hammer/kmer_stat.hpp:170-175)
+//   <prefix>.hamming, <prefix>.hamming.idx   with --cluster: the Hamming clusters of that set, as spades-hamcluster
+// The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
+// common interface.
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+#include "hammer_reads.hpp"
+
+using namespace bbkhost;
+
+static void usage(const char *argv0) {
+    printf("SYNOPSIS\n        %s [-k <value>] [-d <file>] [-t <value>] [-b <value>] -o <prefix> [-h] [<input files>]...\n\n"
+           "OPTIONS\n"
+           "        -k, --kmer <value>      K-mer length (at most 32, default 21)\n"
+           "        -d, --dataset <file>    Dataset description (in YAML), input files ignored\n"
+           "        -t, --threads <value>   # of threads to use\n"
+           "        -b, --bufsize <value>   Bytes of input per block\n"
+           "        -o, --output <prefix>   Output prefix\n"
+           "        -h, --help              Show help\n"
+           "        --device <value>        GPU to use (default 0)\n"
+           "        --qvoffset <value>      Quality offset of the input (default 33)\n"
+           "        --trim-quality <value>  Ns and bases of at most this quality are trimmed from the ends (default 4)\n"
+           "        --cluster               Also cluster the Hamming graph of the k-mers (tau = 1)\n\n"
+           "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
+           "        Output: <prefix>.kmers - the k-mers in ascending order, in the final_kmers record format;\n"
+           "        <prefix>.kmstat - per k-mer: 32-bit count << 1, float total_qual, the 6-bit quality sums packed into 64-bit words;\n"
+           "        with --cluster <prefix>.hamming and <prefix>.hamming.idx as spades-hamcluster writes them.\n",
+           argv0);
+}
+
+// one block of stretches: bases and qualities (offset subtracted) back to back, offsets for both
+struct Block {
+    std::string bases, quals;
+    std::vector<uint64_t> offsets{0};
+    void clear() {
+        bases.clear();
+        quals.clear();
+        offsets.assign(1, 0);
+    }
+    uint64_t size() const { return offsets.size() - 1; }
+};
+
+// Calls push(block) for every block of at most block_bytes bases of the stretches of all records, in file order; returns
+// the number of records.  Both passes go through here, so they see the same stretches in the same blocks.
+template <class Push>
+static uint64_t for_each_block(const std::vector<std::string> &files, unsigned k, int qvoffset, int trim_quality,
+                               size_t block_bytes, bool announce, Push push) {
+    Block b;
+    std::string name, seq, qual;
+    std::vector<hammer::Stretch> st;
+    uint64_t records = 0;
+    for (const std::string &f : files) {
+        if (announce) info("Processing %s", f.c_str());
+        FastxReader rd(f);
+        if (!rd.is_open()) fatal("cannot open %s", f.c_str());
+        while (rd.next_record(name, seq, qual)) {
+            if (qual.size() != seq.size())
+                fatal("%s: record %llu (%s) has no quality string: the statistics need FASTQ input", f.c_str(),
+                      (unsigned long long)records, name.c_str());
+            for (char &c : qual) {
+                const int q = (unsigned char)c - qvoffset;
+                if (q < 0 || q > 93)
+                    fatal("%s: record %llu (%s): quality character '%c' is outside [0, 93] at offset %d", f.c_str(),
+                          (unsigned long long)records, name.c_str(), c, qvoffset);
+                c = (char)q;
+            }
+            ++records;
+            st.clear();
+            hammer::valid_stretches(seq, qual, k, trim_quality, st);
+            for (const hammer::Stretch &s : st) {
+                b.bases.append(seq, s.start, s.length);
+                b.quals.append(qual, s.start, s.length);
+                b.offsets.push_back(b.bases.size());
+            }
+            if (b.bases.size() >= block_bytes) {
+                push(b);
+                b.clear();
+            }
+        }
+    }
+    if (b.size()) push(b);
+    return records;
+}
+
+static void write_u64(const std::string &path, const uint64_t *p, size_t count) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) fatal("cannot open %s for writing", path.c_str());
+    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
+    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
+}
+
+int main(int argc, char **argv) {
+    unsigned K = 21, device = 0;
+    unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4;
+    std::string prefix, dataset;
+    std::vector<std::string> input;
+    bool help = false, bad = false, cluster = false;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        auto need = [&](unsigned long long *v) { return i + 1 < argc && parse_uint(argv[++i], v); };
+        unsigned long long v = 0;
+        if (a == "-k" || a == "--kmer") { if (need(&v)) K = (unsigned)v; else bad = true; }
+        else if (a == "-t" || a == "--threads") { if (need(&v)) threads = v; else bad = true; }
+        else if (a == "-b" || a == "--bufsize") { if (need(&v)) bufsize = v; else bad = true; }
+        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
+        else if (a == "--qvoffset") { if (need(&v)) qvoffset = v; else bad = true; }
+        else if (a == "--trim-quality") { if (need(&v)) trim_quality = v; else bad = true; }
+        else if (a == "--cluster") cluster = true;
+        else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
+        else if (a == "-o" || a == "--output") { if (i + 1 < argc) prefix = argv[++i]; else bad = true; }
+        else if (a == "-h" || a == "--help") help = true;
+        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
+        else input.push_back(a);
+    }
+    (void)threads;
+    if (bad || help || (prefix.empty() && !(input.empty() && dataset.empty()))) {
+        usage(argv[0]);
+        return help ? 0 : 1;
+    }
+    if (input.empty() && dataset.empty()) {
+        fprintf(stderr, "ERROR: No input files were specified\n\n");
+        usage(argv[0]);
+        return 255;
+    }
+    if (K < 1 || K > 32) fatal("k-mer size %u is out of range [1, 32]", K);
+    if (qvoffset > 255 || trim_quality > 93) fatal("--qvoffset / --trim-quality out of range");
+
+    info("Starting k-mer statistics (MI355X, %s)", bbk_version());
+    info("K-mer length set to %u", K);
+    std::vector<std::string> files = input;
+    if (!dataset.empty()) {
+        files.clear();
+        std::string err;
+        if (!load_dataset_yaml(dataset, files, err)) fatal("%s", err.c_str());
+    }
+    Phases ph;
+    const double t_start = now_s();
+    bbk_ctx *ctx = nullptr;
+    double t0 = now_s();
+    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
+    ph.ctx = now_s() - t0;
+
+    // pass 1: the set
+    bbk_counter *counter = nullptr;
+    check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
+    uint64_t stretches = 0;
+    t0 = now_s();
+    const uint64_t records = for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, true, [&](const Block &b) {
+        check(bbk_count_push_ascii(counter, b.bases.data(), b.offsets.data(), b.size()), "bbk_count_push_ascii");
+        stretches += b.size();
+        ++ph.blocks;
+    });
+    info("Total %llu reads processed, %llu stretches of valid k-mers", (unsigned long long)records,
+         (unsigned long long)stretches);
+    bbk_kmerset *set = nullptr;
+    check(bbk_count_finish(counter, &set), "bbk_count_finish");
+    const uint64_t n = bbk_kmerset_size(set);
+    info("K-mer counting done. There are %llu kmers in total.", (unsigned long long)n);
+
+    bbk_hamclusters *hc = nullptr;
+    if (cluster) check(bbk_kmerset_hamming_clusters(ctx, set, 1, 0, 0, &hc), "bbk_kmerset_hamming_clusters");
+
+    // pass 2: the statistics
+    info("Collecting K-mer information");
+    bbk_kmerstats *ks = nullptr;
+    check(bbk_kmerstats_begin(ctx, set, &ks), "bbk_kmerstats_begin");
+    for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, false, [&](const Block &b) {
+        bbk_reads *r = nullptr;
+        bbk_quals *q = nullptr;
+        check(bbk_reads_from_ascii(ctx, b.bases.data(), b.offsets.data(), b.size(), &r), "bbk_reads_from_ascii");
+        check(bbk_quals_from_host(ctx, r, reinterpret_cast<const uint8_t *>(b.quals.data()), b.offsets.data(), b.size(), &q),
+              "bbk_quals_from_host");
+        check(bbk_kmerstats_push(ks, r, q), "bbk_kmerstats_push");
+        bbk_quals_free(q);
+        bbk_reads_free(r);
+    });
+    check(bbk_kmerstats_finish(ks), "bbk_kmerstats_finish");
+    ph.device = now_s() - t0;
+
+    t0 = now_s();
+    {
+        std::vector<uint64_t> buf((size_t)n);  // one word per k-mer (k <= 32)
+        check(bbk_kmerset_export(ctx, set, BBK_ORDER_SORTED, buf.data(), nullptr), "bbk_kmerset_export");
+        write_u64(prefix + ".kmers", buf.data(), buf.size());
+    }
+    check(bbk_kmerstats_write(ctx, ks, (prefix + ".kmstat").c_str()), "bbk_kmerstats_write");
+    if (hc) {
+        check(bbk_hamclusters_write(ctx, hc, (prefix + ".hamming").c_str()), "bbk_hamclusters_write");
+        info("Clustering done. Total clusters: %llu", (unsigned long long)bbk_hamclusters_count(hc));
+        bbk_hamclusters_free(hc);
+    }
+    {
+        std::vector<uint32_t> cnt((size_t)n);
+        check(bbk_kmerstats_export(ctx, ks, cnt.data(), nullptr, nullptr), "bbk_kmerstats_export");
+        uint64_t singletons = 0;
+        for (uint32_t c : cnt) singletons += c == 1;
+        info("There are %llu kmers in total. Among them %llu (%g%%) are singletons.", (unsigned long long)n,
+             (unsigned long long)singletons, n ? 100.0 * (double)singletons / (double)n : 0.0);
+    }
+    bbk_kmerstats_free(ks);
+    bbk_kmerset_free(set);
+    ph.write = now_s() - t0;
+    ph.total = now_s() - t_start;
+    ph.memory(ctx);
+    ph.report("spades-kmerdata");
+    finish_process(ctx, 0);
+}
