@@ -4,6 +4,8 @@
 // first_pass, launch_buckets and give_up_key_slots (msd.hip); 8-byte keys only.
 #pragma once
 
+#include "msd_bucket_tail.h"
+
 namespace bbk {
 
 // ---- narrow stage B (8-byte keys, key slots, no payload): 4-byte records from level 2 on
@@ -25,11 +27,11 @@ __global__ void k_bucket_base(const uint32_t *__restrict__ seg_nb2, const uint32
 }
 
 // k_bucket_dist (OP 0, sorted result written directly) on those 4-byte records: the same distribution sort and in-bin
-// ranking over 32-bit offsets, with half the LDS (38 KB against 61 KB) and at most 80 registers (76: four records per
-// ranking round instead of six), so that three workgroups fit a CU instead of two.  A bucket it turns down, a duplicate or a spill
+// ranking over 32-bit offsets, with half the LDS (38 KB against 61 KB) and at most 64 registers (62: two records per
+// ranking round instead of six), so that four workgroups fit a CU instead of two.  A bucket it turns down, a duplicate or a spill
 // sends the call back to the exact mode, as on the 8-byte key slots, so no second-chance kernel needs this form.
 template <int NT, int ITEMS>
-__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_bucket_dist_nb(const uint32_t *__restrict__ buf, const uint64_t *__restrict__ base,
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bucket_dist_nb(const uint32_t *__restrict__ buf, const uint64_t *__restrict__ base,
                                                        BucketArgs A) {
     constexpr int CAP = NT * ITEMS;
     constexpr int NWAVES = NT / 64;
@@ -59,19 +61,27 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     unsigned long long t_prev = clock64();
 #endif
 
+    // Rows: record p = i * NT + tid lies in row i of the lane.  A bucket is planned ~70 % full, so the last rows of
+    // nearly every bucket hold no record in any wave: every per-row phase below runs for i < rows only, behind a
+    // branch that is uniform across the workgroup and skips the whole body.  Only the last row in use is partial.
+    const uint32_t rows = bucket_rows(n, NT);
     const uint64_t kbase = base[b];
     uint32_t keys[ITEMS];  // offsets from the base: the key order
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t p = (uint32_t)(i * NT + tid);
-        keys[i] = buf[start + (p < n ? p : n - 1u)];
+    for (int i = 0; i < ITEMS; ++i) {  // the loads of the rows in use are issued up front, the last one clamped
+        if ((uint32_t)i < rows) {
+            const uint32_t p = (uint32_t)(i * NT + tid);
+            keys[i] = buf[start + (p < n ? p : n - 1u)];
+        }
     }
     uint32_t mn = ~0u, mx = 0;
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {  // clamped duplicates do not change min / max
-        keys[i] -= (uint32_t)kbase;
-        mn = keys[i] < mn ? keys[i] : mn;
-        mx = keys[i] > mx ? keys[i] : mx;
+        if ((uint32_t)i < rows) {
+            keys[i] -= (uint32_t)kbase;
+            mn = keys[i] < mn ? keys[i] : mn;
+            mx = keys[i] > mx ? keys[i] : mx;
+        }
     }
 #pragma unroll
     for (int dd = 32; dd >= 1; dd >>= 1) {
@@ -98,8 +108,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void
 
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t p = (uint32_t)(i * NT + tid);
-        if (p < n) atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
+        if ((uint32_t)i < rows) {
+            const uint32_t p = (uint32_t)(i * NT + tid);
+            if (p < n) atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
+        }
     }
     __syncthreads();
     BBK_PH(3, 1, t_prev);  // count
@@ -134,61 +146,68 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     uint32_t at[ITEMS];  // where the scatter put the record (breaks ties between equal offsets), then its final place
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t p = (uint32_t)(i * NT + tid);
-        at[i] = 0xFFFFFFFFu;
-        if (p < n) {
-            const uint32_t pos = atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
-            skeys[pos] = keys[i];
-            at[i] = pos;
+        if ((uint32_t)i < rows) {
+            const uint32_t p = (uint32_t)(i * NT + tid);
+            if (p < n) {
+                const uint32_t pos = atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
+                skeys[pos] = keys[i];
+                at[i] = pos;
+            }
         }
     }
     __syncthreads();
     BBK_PH(3, 3, t_prev);  // scatter
     // in-bin ranking as in k_bucket_dist: bin d = [bins[d-1], bins[d]) after the scatter, RB records per round with the
-    // first four candidates of every bin read unconditionally (one array for both places saves eleven registers)
-    constexpr int RB = 4;  // (6 as in k_bucket_dist: 93 registers, two workgroups per CU)
+    // first four candidates of every bin read unconditionally (one array for both places saves eleven registers).  A
+    // round whose first row is not in use is skipped as a whole; inside a round there is no branch per row, so that
+    // its LDS reads stay batched.
+    // (RB = 6 as in k_bucket_dist: 93 registers, two workgroups per CU; 4: 80, three; 3 needs scratch at 64; 2: 62
+    // registers, four workgroups per CU -- 1.42 -> 1.29 ms at the flagship size against RB = 4)
+    constexpr int RB = 2;
 #pragma unroll
     for (int i0 = 0; i0 < ITEMS; i0 += RB) {
-        uint32_t sb[RB], e[RB];
+        if ((uint32_t)i0 < rows) {
+            uint32_t sb[RB], e[RB];
 #pragma unroll
-        for (int u = 0; u < RB; ++u) {
-            const int i = i0 + u;
-            sb[u] = e[u] = 0;
-            if (i < ITEMS) {
-                const uint32_t p = (uint32_t)(i * NT + tid);
-                if (p < n) {
-                    const uint32_t d = (keys[i] - kmin) >> sh;
-                    sb[u] = d ? bins[d - 1] : 0u;
-                    e[u] = bins[d];
+            for (int u = 0; u < RB; ++u) {
+                const int i = i0 + u;
+                sb[u] = e[u] = 0;
+                if (i < ITEMS) {
+                    const uint32_t p = (uint32_t)(i * NT + tid);
+                    if (p < n) {
+                        const uint32_t d = (keys[i] - kmin) >> sh;
+                        sb[u] = d ? bins[d - 1] : 0u;
+                        e[u] = bins[d];
+                    }
                 }
             }
-        }
-        uint32_t o[RB][4];
+            uint32_t o[RB][4];
 #pragma unroll
-        for (int u = 0; u < RB; ++u) {
+            for (int u = 0; u < RB; ++u) {
 #pragma unroll
-            for (int c4 = 0; c4 < 4; ++c4) {
-                const uint32_t y = sb[u] + c4;
-                o[u][c4] = skeys[y < e[u] ? y : (e[u] ? e[u] - 1u : 0u)];
+                for (int c4 = 0; c4 < 4; ++c4) {
+                    const uint32_t y = sb[u] + c4;
+                    o[u][c4] = skeys[y < e[u] ? y : (e[u] ? e[u] - 1u : 0u)];
+                }
             }
-        }
 #pragma unroll
-        for (int u = 0; u < RB; ++u) {
-            const int i = i0 + u;
-            if (i < ITEMS) {
-                const uint32_t p = (uint32_t)(i * NT + tid);
-                if (p < n) {
-                    uint32_t before = 0;
+            for (int u = 0; u < RB; ++u) {
+                const int i = i0 + u;
+                if (i < ITEMS) {
+                    const uint32_t p = (uint32_t)(i * NT + tid);
+                    if (p < n) {
+                        uint32_t before = 0;
 #pragma unroll
-                    for (int c4 = 0; c4 < 4; ++c4) {
-                        const uint32_t y = sb[u] + c4;
-                        if (y < e[u]) before += (o[u][c4] < keys[i] || (o[u][c4] == keys[i] && y < at[i])) ? 1u : 0u;
+                        for (int c4 = 0; c4 < 4; ++c4) {
+                            const uint32_t y = sb[u] + c4;
+                            if (y < e[u]) before += (o[u][c4] < keys[i] || (o[u][c4] == keys[i] && y < at[i])) ? 1u : 0u;
+                        }
+                        for (uint32_t y = sb[u] + 4; y < e[u]; ++y) {  // bins above four records
+                            const uint32_t ok = skeys[y];
+                            before += (ok < keys[i] || (ok == keys[i] && y < at[i])) ? 1u : 0u;
+                        }
+                        at[i] = sb[u] + before;
                     }
-                    for (uint32_t y = sb[u] + 4; y < e[u]; ++y) {  // bins above four records
-                        const uint32_t ok = skeys[y];
-                        before += (ok < keys[i] || (ok == keys[i] && y < at[i])) ? 1u : 0u;
-                    }
-                    at[i] = sb[u] + before;
                 }
             }
         }
@@ -196,53 +215,35 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(6, 6))) void
     __syncthreads();  // every rank is computed from the scattered order: only now overwrite it
     BBK_PH(3, 4, t_prev);  // rank
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i)
-        if (at[i] != 0xFFFFFFFFu) skeys[at[i]] = keys[i];
-    __syncthreads();
-    BBK_PH(3, 5, t_prev);  // write
-
-    // heads (blocked ownership: thread t owns [t*ITEMS, (t+1)*ITEMS)), the distinct offsets compacted in LDS, then
-    // widened and stored coalesced at the bucket's place in the result.  Every offset is a possible value: the first
-    // record of the bucket is a head by position, not by comparison with a sentinel.
-    uint32_t ostart = A.out_off ? A.out_off[b] : start;
-    const uint32_t p0 = (uint32_t)tid * ITEMS;
-    const uint32_t prev = (p0 > 0 && p0 - 1 < n) ? skeys[p0 - 1] : 0u;
-    uint32_t mine[ITEMS];
-    uint32_t nheads = 0, headbits = 0;
-#pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        mine[i] = 0;
-        if (p0 + i < n) {
-            mine[i] = skeys[p0 + i];
-            const bool h = (i == 0) ? (p0 == 0 || mine[0] != prev) : mine[i] != mine[i - 1];
-            if (h) {
-                headbits |= 1u << i;
-                ++nheads;
-            }
+        if ((uint32_t)i < rows) {
+            const uint32_t p = (uint32_t)(i * NT + tid);
+            if (p < n) skeys[at[i]] = keys[i];
         }
     }
-    uint32_t excl, total;
-    {
-        uint32_t hincl = wave_scan_incl(nheads);
-        __syncthreads();  // everyone has its offsets in registers: skeys may be reused below
-        if (lane == 63) scan_tmp[wave] = hincl;
-        __syncthreads();
-        uint32_t wbase, tot;
-        wave_totals<NWAVES>(scan_tmp, lane, wave, wbase, tot);
-        excl = wbase + hincl - nheads;
-        total = tot;
-        asm volatile("" : "+v"(ostart));  // awaited here, not inside the store loop (see bucket_reduce)
-    }
-    int seg = (int)excl - 1;
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i)
-        if (p0 + i < n && (headbits & (1u << i))) skeys[++seg] = mine[i];
+    uint32_t ostart = A.out_off ? A.out_off[b] : start;
     __syncthreads();
+    BBK_PH(3, 5, t_prev);  // write
+    asm volatile("" : "+v"(ostart));  // awaited here, not inside the store loop (see bucket_reduce)
+
+    // The input is distinct by construction (the caller requires the direct output, assume_distinct), and all the host
+    // takes from a bucket is whether that held: the sorted offsets leave as they lie, widened, position s to dst[s]
+    // (coalesced), and equal neighbours raise the duplicate flag -- no heads, no scan, no compaction.  Any duplicate
+    // sends the whole call to give_up_key_slots() and the result is released, so what a bucket that holds one stores
+    // inside its own [ostart, ostart + n) does not matter.  dcount is n: the bucket was sorted here.
     uint64_t *dst = reinterpret_cast<uint64_t *>(A.sorted_keys) + ostart;
-    for (uint32_t s = tid; s < total; s += NT) dst[s] = (kbase + skeys[s]) & A.strip_mask;
-    if (tid == 0 && total != n) atomicOr(A.dup_flag, 1u);
-    if (tid == 0) A.dcount[b] = total;
-    BBK_PH(3, 6, t_prev);  // heads + output
+    bool dup = false;
+#pragma unroll
+    for (int i = 0; i < ITEMS; ++i) {
+        if ((uint32_t)i < rows) {
+            const uint32_t s = (uint32_t)(i * NT + tid);
+            if (s < n) dup = dist_tail_at(skeys, s, kbase, A.strip_mask, dst) || dup;
+        }
+    }
+    // (one lane of a wave that saw a pair: rare, and a workgroup-wide verdict would cost one more barrier)
+    if (__any(dup) && lane == 0) atomicOr(A.dup_flag, 1u);
+    if (tid == 0) A.dcount[b] = n;
+    BBK_PH(3, 6, t_prev);  // copy-out
 #ifdef BBK_PHASE_PROF
     if (threadIdx.x == 0) atomicAdd(&g_phase[3][7], 1ull);
 #endif
