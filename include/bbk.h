@@ -447,6 +447,11 @@ int bbk_hamclusters_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_l
 /* <path>: h_members as u64; <path>.idx: h_sizes as u64 -- kmers.hamming / kmers.hamming.idx as
  * ConcurrentDSU::extract_to_file writes them (concurrent_dsu.cpp:63-83) */
 int bbk_hamclusters_write(bbk_ctx *ctx, const bbk_hamclusters *h, const char *path);
+/* The inverse of bbk_hamclusters_write (a restart with hamming_do 0, projects/hammer/main.cpp:143-168): <path> and
+ * <path>.idx for a set of n k-mers.  Clusters may come in any order and members in any order inside a cluster (the
+ * reference lists by DSU root); the result is in the documented order.  BBK_ERR_ARG unless <path> holds n members that are
+ * a permutation of 0 .. n-1 and the sizes are positive and sum to n. */
+int bbk_hamclusters_load(bbk_ctx *ctx, uint64_t n, const char *path, bbk_hamclusters **out);
 void bbk_hamclusters_free(bbk_hamclusters *h);
 
 /* ---- quality-aware k-mer statistics: replaces KMerDataCounter::FillKMerData / KMerDataFiller over a KMerData
@@ -487,7 +492,62 @@ int bbk_kmerstats_export(bbk_ctx *ctx, const bbk_kmerstats *ks, uint32_t *h_coun
 /* one binary_write(KMerStat) record per k-mer (kmer_stat.hpp:170-175): u32 count << 1 (the good bit is 0, mark_bad), float
  * total_qual, the QualBitSet words: 24 bytes at k = 21.  BBK_ERR_ARG when a count is 2^31 or more. */
 int bbk_kmerstats_write(bbk_ctx *ctx, const bbk_kmerstats *ks, const char *path);
+/* The inverse of bbk_kmerstats_write: the statistics of every k-mer of `set` from a file of binary_write(KMerStat)
+ * records (the good bit is ignored), so that a run can restart after the statistics as the reference does with
+ * count_do 0 (projects/hammer/main.cpp:122-141).  The result is finished; bbk_kmerstats_push refuses it.  BBK_ERR_ARG
+ * unless the file holds exactly one record of 8 + 8 * ceil(6k / 64) bytes per k-mer of the set. */
+int bbk_kmerstats_load(bbk_ctx *ctx, const bbk_kmerset *set, const char *path, bbk_kmerstats **out);
 void bbk_kmerstats_free(bbk_kmerstats *ks);
+
+/* ---- Bayesian subclustering of the Hamming clusters: replaces KMerClustering::process / ProcessCluster /
+ *      SubClusterSingle / lMeansClustering / ClusterBIC / Consensus / ConsensusWithMask
+ *      (projects/hammer/kmer_cluster.cpp:49-633) over ExpandedKMer (projects/hammer/kmer_stat.hpp:205-279) and the
+ *      tables of projects/hammer/main.cpp:103-108 -- the step that gives every k-mer its good bit (KMerStat::good(),
+ *      kmer_stat.hpp:140-148), the one thing Expander and ReadCorrector read ----------------------------------------- */
+typedef struct bbk_subclusters bbk_subclusters; /* the subclusters, the good bits and the new k-mers: in HBM */
+typedef struct bbk_subcluster_params {
+    double singleton_threshold;    /* bayes_singleton_threshold, 0.995 in configs/hammer/config.info */
+    double nonsingleton_threshold; /* bayes_nonsingleton_threshold, 0.9 */
+    double correct_threshold;      /* correct_threshold, 0.98 */
+    int correct_use_threshold;     /* correct_use_threshold, 1 */
+} bbk_subcluster_params;
+/* set, hamclusters and kmerstats belong together (k <= 32, the ascending both-strand set, fewer than 2^32 - 2 k-mers, one
+ * GPU).  The configuration is config.info's bayes_initial_refine 1, bayes_use_hamming_dist 0, bayes_hammer_mode 0; the
+ * other settings of the three are not offered.  p = NULL: the four thresholds of config.info.
+ * Every Hamming cluster is processed as ProcessCluster does (:455-577): a singleton by :463-491; any other is ordered
+ * by count, split by SubClusterSingle (:261-446: l-means for l = 1, 2, ... scored by ClusterBIC, the merge of duplicate
+ * centers, the listing, a consensus that is no member looked up in the set or appended as a new k-mer with count 0 and
+ * total_qual 1), and the center of every subcluster is marked good or bad (:503-556).  Exact parity with the literal
+ * restatement tests/subcluster_restated.py, the bits of the BIC included (DESIGN.md 4.3e says what that takes).
+ * Divergences from the reference: an index is a position in the ascending set; the members of a cluster are ordered by
+ * (count descending, index ascending) where the reference's std::sort (:625) is unstable; new k-mers get the indices n,
+ * n + 1, ... in the order (cluster by ascending label, subcluster by ascending center number), not deduplicated (the
+ * reference appends them in thread-timing order and does not deduplicate either, :429-438); where several subclusters
+ * name the same k-mer as their center, the last in that order decides its bit (the reference: the last in time);
+ * total_qual is the engine's reproducible value (bbk_kmerstats_push).
+ * Clusters of more than 256 k-mers are processed on the host (OpenMP); BBK_SUBCLUSTER_HOST=1 sends all of them there.
+ * BBK_ERR_ARG: handles of different sizes or sets, statistics without bbk_kmerstats_finish, a threshold outside [0, 1]. */
+int bbk_hamclusters_subcluster(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_hamclusters *hamclusters,
+                               const bbk_kmerstats *kmerstats, const bbk_subcluster_params *p, bbk_subclusters **out);
+uint64_t bbk_subclusters_count(const bbk_subclusters *s);      /* subclusters (empty lists are dropped, :505) */
+uint64_t bbk_subclusters_size(const bbk_subclusters *s);       /* entries of all lists together */
+uint64_t bbk_subclusters_new_kmers(const bbk_subclusters *s);  /* "non-read kmers" (:650) */
+uint64_t bbk_subclusters_host_kmers(const bbk_subclusters *s); /* k-mers of the clusters that went through the host path */
+/* Every pointer may be NULL.  h_good: n + new bytes, KMerStat::good() of every k-mer, the new ones last; h_members: size
+ * entries, the k-mers subcluster by subcluster (clusters in their order), the center first (blocksInPlace, :493-510), a
+ * new k-mer as n + j; h_sizes: count entries; h_per_cluster: the subclusters of every Hamming cluster (1 for a
+ * singleton); h_new_keys: new entries; h_bic: the best BIC (bestLikelihood, :305-328) of every Hamming cluster, -inf
+ * for a singleton; h_errs[16]: UpdateErrors (:448-453,564), errs[4 * center[i] + kmer[i]] over all positions of every
+ * non-center entry; h_stats[9]: gsingl, tsingl, tcsingl, gcsingl, tcls, gcls, tkmers, tncls, newkmers (:592,650-657). */
+int bbk_subclusters_export(bbk_ctx *ctx, const bbk_subclusters *s, uint8_t *h_good, uint64_t *h_members, uint64_t *h_sizes,
+                           uint64_t *h_per_cluster, uint64_t *h_new_keys, double *h_bic, uint64_t *h_errs,
+                           uint64_t *h_stats);
+/* <prefix>.kmstat as bbk_kmerstats_write, with the good bit in bit 0 of the count word and the records of the new k-mers
+ * (count 0, total_qual 1, no qualities) after the others (KMerData::push_back, kmer_data.hpp); <prefix>.subclusters /
+ * .subclusters.idx: h_members / h_sizes as u64, like <path> / <path>.idx of bbk_hamclusters_write; <prefix>.newkmers:
+ * the new k-mers, one u64 record each like <prefix>.kmers of spades-kmerdata. */
+int bbk_subclusters_write(bbk_ctx *ctx, const bbk_subclusters *s, const bbk_kmerstats *ks, const char *prefix);
+void bbk_subclusters_free(bbk_subclusters *s);
 
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------

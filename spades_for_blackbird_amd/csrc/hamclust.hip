@@ -31,13 +31,6 @@
 #include "bbk_internal.h"
 #include "kmer_ops.h"
 
-struct bbk_hamclusters {
-    uint64_t n = 0, clusters = 0, replayed = 0;
-    bbk::DevBuf labels;   // n u32: smallest member index of the cluster of k-mer i
-    bbk::DevBuf members;  // n u32: the indices cluster by cluster
-    bbk::DevBuf sizes;    // clusters u64
-};
-
 namespace bbk {
 
 constexpr int kHcTile = 256;
@@ -437,6 +430,85 @@ int bbk_hamclusters_write(bbk_ctx *ctx, const bbk_hamclusters *h, const char *pa
         hc_export(ctx, h, nullptr, members.data(), sizes.data());
         hc_write_file(path, members.data(), h->n);
         hc_write_file(std::string(path) + ".idx", sizes.data(), h->clusters);
+    });
+}
+
+int bbk_hamclusters_load(bbk_ctx *ctx, uint64_t n, const char *path, bbk_hamclusters **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && path && out, BBK_ERR_ARG, "bbk_hamclusters_load: NULL argument");
+        BBK_REQUIRE(n < (1ull << 32) - 2, BBK_ERR_ARG, "bbk_hamclusters_load: %llu k-mers: fewer than 2^32 - 2 are needed",
+                    (unsigned long long)n);
+        BBK_HIP(hipSetDevice(ctx->device));
+        auto read_all = [](const std::string &p, raw_vector<uint64_t> &v) {
+            FILE *f = fopen(p.c_str(), "rb");
+            BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s", p.c_str());
+            fseek(f, 0, SEEK_END);
+            const long long bytes = ftell(f);
+            fseek(f, 0, SEEK_SET);
+            BBK_REQUIRE(bytes >= 0 && bytes % 8 == 0, BBK_ERR_ARG, "bbk_hamclusters_load: %s is not a file of 64-bit values",
+                        p.c_str());
+            v.resize((size_t)bytes / 8);
+            const bool ok = v.empty() || fread(v.data(), 8, v.size(), f) == v.size();
+            fclose(f);
+            BBK_REQUIRE(ok, BBK_ERR_IO, "reading %s failed", p.c_str());
+        };
+        raw_vector<uint64_t> mem, sz;
+        read_all(path, mem);
+        read_all(std::string(path) + ".idx", sz);
+        BBK_REQUIRE(mem.size() == n, BBK_ERR_ARG, "bbk_hamclusters_load: %s lists %zu members, the set has %llu k-mers", path,
+                    mem.size(), (unsigned long long)n);
+        uint64_t sum = 0;
+        for (uint64_t s : sz) {
+            BBK_REQUIRE(s >= 1 && s <= n - sum, BBK_ERR_ARG,
+                        "bbk_hamclusters_load: %s.idx: the cluster sizes are not positive numbers that sum to %llu", path,
+                        (unsigned long long)n);
+            sum += s;
+        }
+        BBK_REQUIRE(sum == n, BBK_ERR_ARG, "bbk_hamclusters_load: %s.idx: the cluster sizes sum to %llu, not to %llu", path,
+                    (unsigned long long)sum, (unsigned long long)n);
+        std::vector<uint8_t> seen(n, 0);
+        for (uint64_t m : mem) {
+            BBK_REQUIRE(m < n && !seen[m], BBK_ERR_ARG,
+                        "bbk_hamclusters_load: %s: the members are not a permutation of 0 .. %llu (index %llu is %s)", path,
+                        (unsigned long long)n, (unsigned long long)m, m < n ? "listed twice" : "out of range");
+            seen[m] = 1;
+        }
+        // into the documented order: ascending inside a cluster, clusters by ascending label (the reference lists
+        // clusters by DSU root, concurrent_dsu.cpp:54-69)
+        const size_t C = sz.size();
+        std::vector<uint64_t> start(C + 1, 0);
+        for (size_t c = 0; c < C; ++c) {
+            start[c + 1] = start[c] + sz[c];
+            std::sort(mem.begin() + start[c], mem.begin() + start[c + 1]);
+        }
+        std::vector<size_t> order(C);
+        for (size_t c = 0; c < C; ++c) order[c] = c;
+        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return mem[start[a]] < mem[start[b]]; });
+        raw_vector<uint32_t> members(n), labels(n);
+        raw_vector<uint64_t> sizes(C);
+        uint64_t o = 0;
+        for (size_t c = 0; c < C; ++c) {
+            const size_t src = order[c];
+            sizes[c] = sz[src];
+            for (uint64_t j = 0; j < sz[src]; ++j) {
+                const uint32_t m = (uint32_t)mem[start[src] + j];
+                members[o++] = m;
+                labels[m] = (uint32_t)mem[start[src]];
+            }
+        }
+        auto h = std::make_unique<bbk_hamclusters>();
+        h->n = n;
+        h->clusters = C;
+        h->labels.alloc(n * 4);
+        h->members.alloc(n * 4);
+        h->sizes.alloc(C * 8);
+        if (n) {
+            BBK_HIP(hipMemcpyAsync(h->labels.p, labels.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(h->members.p, members.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(h->sizes.p, sizes.data(), C * 8, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        *out = h.release();
     });
 }
 

@@ -37,20 +37,6 @@ struct bbk_quals {
     bbk::DevBuf off;  // n + 1 u64
 };
 
-struct bbk_kmerstats {
-    bbk_ctx *ctx = nullptr;
-    const bbk_kmerset *set = nullptr;  // must outlive the statistics
-    unsigned k = 0, acc_words = 0, qual_words = 0;
-    uint64_t n = 0;
-    bool finished = false, count_overflow = false;
-    bbk::PrefixIndex prefix;
-    bbk::DevBuf probs;       // 256 doubles: Globals::quality_probs
-    bbk::DevBuf rec;         // n * (2 + acc_words) u64
-    bbk::DevBuf count;       // n u32            \.
-    bbk::DevBuf total_qual;  // n f32             > written by finish
-    bbk::DevBuf qual;        // n * qual_words u64 /
-};
-
 namespace bbk {
 
 // Fixed-point fraction bits of the log sum.  A quality is at most 93 (bbk_quals_from_host refuses more: '~', the last
@@ -291,6 +277,8 @@ int bbk_kmerstats_push(bbk_kmerstats *ks, const bbk_reads *reads, const bbk_qual
         BBK_REQUIRE(ks && reads && quals, BBK_ERR_ARG, "bbk_kmerstats_push: NULL argument");
         BBK_REQUIRE(quals->reads == reads && quals->n == reads->n, BBK_ERR_ARG,
                     "bbk_kmerstats_push: the qualities were not made for these reads (bbk_quals_from_host)");
+        BBK_REQUIRE(!ks->loaded, BBK_ERR_ARG,
+                    "bbk_kmerstats_push: these statistics were read from a file (bbk_kmerstats_load): nothing can be added");
         bbk_ctx *ctx = ks->ctx;
         BBK_HIP(hipSetDevice(ctx->device));
         ks->finished = false;
@@ -363,6 +351,57 @@ int bbk_kmerstats_write(bbk_ctx *ctx, const bbk_kmerstats *ks, const char *path)
         }
         const bool closed = fclose(f) == 0;
         BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path);
+    });
+}
+
+int bbk_kmerstats_load(bbk_ctx *ctx, const bbk_kmerset *set, const char *path, bbk_kmerstats **out) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && set && path && out, BBK_ERR_ARG, "bbk_kmerstats_load: NULL argument");
+        BBK_REQUIRE(set->k <= 32 && !(set->flags & BBK_CANONICAL) && set->sorted && !set->ref_order &&
+                        set->n < (1ull << 32) - 2,
+                    BBK_ERR_ARG, "bbk_kmerstats_load: needs what bbk_kmerstats_begin needs: an ascending both-strand set, k <= 32, "
+                                 "fewer than 2^32 - 2 k-mers");
+        BBK_HIP(hipSetDevice(ctx->device));
+        auto ks = std::make_unique<bbk_kmerstats>();
+        ks->ctx = ctx;
+        ks->set = set;
+        ks->k = set->k;
+        ks->n = set->n;
+        ks->acc_words = (set->k + 9) / 10;
+        ks->qual_words = (6 * set->k + 63) / 64;
+        const unsigned qw = ks->qual_words;
+        const size_t rsz = 8 + 8 * (size_t)qw;
+        FILE *f = fopen(path, "rb");
+        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s", path);
+        raw_vector<char> buf(ks->n * rsz + 1);
+        const size_t got = fread(buf.data(), 1, buf.size(), f);
+        fclose(f);
+        BBK_REQUIRE(got == ks->n * rsz, BBK_ERR_ARG,
+                    "bbk_kmerstats_load: %s does not hold %llu records of %zu bytes (k = %u), one per k-mer of the set", path,
+                    (unsigned long long)ks->n, rsz, ks->k);
+        raw_vector<uint32_t> cnt(ks->n);
+        raw_vector<float> tq(ks->n);
+        raw_vector<uint64_t> qv(ks->n * qw);
+        for (uint64_t i = 0; i < ks->n; ++i) {
+            const char *r = buf.data() + i * rsz;
+            uint32_t c2;
+            memcpy(&c2, r, 4);
+            cnt[i] = c2 >> 1;  // the good bit is not part of the statistics
+            memcpy(&tq[i], r + 4, 4);
+            memcpy(&qv[i * qw], r + 8, 8 * (size_t)qw);
+        }
+        ks->count.alloc(ks->n * 4);
+        ks->total_qual.alloc(ks->n * 4);
+        ks->qual.alloc(ks->n * qw * 8);
+        if (ks->n) {
+            BBK_HIP(hipMemcpyAsync(ks->count.p, cnt.data(), ks->n * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(ks->total_qual.p, tq.data(), ks->n * 4, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(ks->qual.p, qv.data(), ks->n * qw * 8, hipMemcpyHostToDevice, ctx->stream));
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            ks->prefix.build(ctx, set->keys.as<uint64_t>(), 1, set->k, set->n);
+        }
+        ks->finished = ks->loaded = true;
+        *out = ks.release();
     });
 }
 

@@ -42,6 +42,9 @@ SYMBOLS = [
     "bbk_hamclusters_export", "bbk_hamclusters_write", "bbk_hamclusters_free",
     "bbk_quals_from_host", "bbk_quals_free", "bbk_kmerstats_begin", "bbk_kmerstats_push", "bbk_kmerstats_finish",
     "bbk_kmerstats_size", "bbk_kmerstats_export", "bbk_kmerstats_write", "bbk_kmerstats_free",
+    "bbk_kmerstats_load", "bbk_hamclusters_load", "bbk_hamclusters_subcluster", "bbk_subclusters_count",
+    "bbk_subclusters_size", "bbk_subclusters_new_kmers", "bbk_subclusters_host_kmers", "bbk_subclusters_export",
+    "bbk_subclusters_write", "bbk_subclusters_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -245,6 +248,16 @@ def load_library():
     L.bbk_kmerstats_write.argtypes = [vp, vp, C.c_char_p]
     L.bbk_kmerstats_free.argtypes = [vp]
     L.bbk_kmerstats_free.restype = None
+    L.bbk_kmerstats_load.argtypes = [vp, vp, C.c_char_p, C.POINTER(vp)]
+    L.bbk_hamclusters_load.argtypes = [vp, u64, C.c_char_p, C.POINTER(vp)]
+    L.bbk_hamclusters_subcluster.argtypes = [vp, vp, vp, vp, vp, C.POINTER(vp)]
+    for f in ("count", "size", "new_kmers", "host_kmers"):
+        getattr(L, "bbk_subclusters_" + f).restype = u64
+        getattr(L, "bbk_subclusters_" + f).argtypes = [vp]
+    L.bbk_subclusters_export.argtypes = [vp] * 10
+    L.bbk_subclusters_write.argtypes = [vp, vp, vp, C.c_char_p]
+    L.bbk_subclusters_free.argtypes = [vp]
+    L.bbk_subclusters_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -494,6 +507,20 @@ class Context:
         _check(self._L.bbk_kmerprofile_load(self._h, str(prefix).encode(), k, n_samples, C.byref(h)))
         return KmerProfile(self, h)
 
+    def kmerstats_load(self, kmer_set, path):
+        """the inverse of KmerStats.write: the statistics of every k-mer of kmer_set from a .kmstat file"""
+        h = C.c_void_p()
+        _check(self._L.bbk_kmerstats_load(self._h, kmer_set._h, str(path).encode(), C.byref(h)))
+        ks = KmerStats(self, h)
+        ks._set, ks.k = kmer_set, kmer_set.k
+        return ks
+
+    def hamclusters_load(self, n, path):
+        """the inverse of HamClusters.write: <path> and <path>.idx for a set of n k-mers, clusters in any order"""
+        h = C.c_void_p()
+        _check(self._L.bbk_hamclusters_load(self._h, n, str(path).encode(), C.byref(h)))
+        return HamClusters(self, h)
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.bbk_ctx_destroy(self._h)
@@ -715,6 +742,73 @@ class HamClusters(_Handle):
     def write(self, path):
         """<path> (member indices, u64) and <path>.idx (cluster sizes, u64): ConcurrentDSU::extract_to_file"""
         _check(self._L.bbk_hamclusters_write(self.ctx._h, self._h, str(path).encode()))
+
+    def subcluster(self, kmer_stats, singleton_threshold=0.995, nonsingleton_threshold=0.9, correct_threshold=0.98,
+                   correct_use_threshold=True):
+        """KMerClustering::process over these clusters and the finished statistics of the same set: SubClusters.  The
+        defaults are the thresholds of configs/hammer/config.info."""
+        p = SubclusterParams(singleton_threshold, nonsingleton_threshold, correct_threshold, int(bool(correct_use_threshold)))
+        h = C.c_void_p()
+        _check(self._L.bbk_hamclusters_subcluster(self.ctx._h, kmer_stats._set._h, self._h, kmer_stats._h, C.byref(p),
+                                                  C.byref(h)))
+        sc = SubClusters(self.ctx, h)
+        sc._n, sc._clusters, sc._stats_of = self.size, len(self), kmer_stats
+        return sc
+
+    def close(self):
+        self.free()
+
+
+class SubclusterParams(C.Structure):
+    """bbk_subcluster_params of include/bbk.h"""
+    _fields_ = [("singleton_threshold", C.c_double), ("nonsingleton_threshold", C.c_double),
+                ("correct_threshold", C.c_double), ("correct_use_threshold", C.c_int)]
+
+
+class SubClusters(_Handle):
+    """BayesHammer's subclusters of the Hamming clusters, the good bit of every k-mer and the new k-mers"""
+    _free = "bbk_subclusters_free"
+    STATS = ("gsingl", "tsingl", "tcsingl", "gcsingl", "tcls", "gcls", "tkmers", "tncls", "newkmers")
+
+    def __len__(self):
+        return int(self._L.bbk_subclusters_count(self._h))
+
+    @property
+    def size(self):
+        """entries of all lists together"""
+        return int(self._L.bbk_subclusters_size(self._h))
+
+    @property
+    def new_kmers(self):
+        return int(self._L.bbk_subclusters_new_kmers(self._h))
+
+    @property
+    def host_kmers(self):
+        """k-mers of the clusters that went through the host path (more than 256 members, or BBK_SUBCLUSTER_HOST=1)"""
+        return int(self._L.bbk_subclusters_host_kmers(self._h))
+
+    def export(self):
+        """dict: good u8[n + new], members u64[size] (the center first, a new k-mer as n + j), sizes u64[len],
+        per_cluster u64[clusters], new_keys u64[new], bic f64[clusters] (-inf for a singleton), errs u64[16]
+        (4 * center base + k-mer base), stats u64[9] (SubClusters.STATS)"""
+        r = dict(good=np.zeros(self._n + self.new_kmers, dtype=np.uint8), members=np.zeros(self.size, dtype=np.uint64),
+                 sizes=np.zeros(len(self), dtype=np.uint64), per_cluster=np.zeros(self._clusters, dtype=np.uint64),
+                 new_keys=np.zeros(self.new_kmers, dtype=np.uint64), bic=np.zeros(self._clusters, dtype=np.float64),
+                 errs=np.zeros(16, dtype=np.uint64), stats=np.zeros(9, dtype=np.uint64))
+        _check(self._L.bbk_subclusters_export(self.ctx._h, self._h, *[_ptr(r[x]) for x in (
+            "good", "members", "sizes", "per_cluster", "new_keys", "bic", "errs", "stats")]))
+        return r
+
+    @property
+    def stats(self):
+        """the counters of the reference's "Subclustering statistics" lines, by name"""
+        a = np.zeros(9, dtype=np.uint64)
+        _check(self._L.bbk_subclusters_export(self.ctx._h, self._h, None, None, None, None, None, None, None, _ptr(a)))
+        return dict(zip(self.STATS, (int(x) for x in a)))
+
+    def write(self, prefix):
+        """<prefix>.kmstat (good bits set, new k-mers appended), .subclusters, .subclusters.idx, .newkmers"""
+        _check(self._L.bbk_subclusters_write(self.ctx._h, self._h, self._stats_of._h, str(prefix).encode()))
 
     def close(self):
         self.free()

@@ -3,7 +3,8 @@
 // (projects/hammer/main.cpp:122-171: KMerDataCounter::BuildKMerIndex, the Hamming clustering, then
 // KMerDataCounter::FillKMerData, "Collecting K-mer information, this takes a while"); this tool is that sequence alone.
 //   -k/--kmer <int=21>  -t/--threads <int>  -b/--bufsize <bytes>  -o/--output <prefix>  -d/--dataset <yaml>  [input files...]
-//   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster)
+//   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster, --subcluster with --singleton-threshold,
+//      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold)
 // Every FASTQ record is cut into the stretches of its valid k-mer starts (hammer_reads.hpp: input_trim_quality 4 of
 // configs/hammer/config.info, then ValidKMerGenerator); a stretch is one read of the engine.
 //   pass 1  the stretches, in blocks of -b bytes, through bbk_count_begin / push / finish(BBK_BOTH_STRANDS)
@@ -13,6 +14,9 @@
 //                         i of the other files is record i
 //   <prefix>.kmstat       one binary_write(KMerStat) record per k-mer (projects/hammer/kmer_stat.hpp:170-175)
 //   <prefix>.hamming, <prefix>.hamming.idx   with --cluster: the Hamming clusters of that set, as spades-hamcluster
+//   with --subcluster (KMerClustering::process, projects/hammer/kmer_cluster.cpp:590-659; implies --cluster):
+//   <prefix>.kmstat then carries the good bit and the records of the new k-mers, and <prefix>.subclusters,
+//   <prefix>.subclusters.idx and <prefix>.newkmers are written (bbk_subclusters_write)
 // The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
 // common interface.
 #include <cstring>
@@ -36,11 +40,18 @@ static void usage(const char *argv0) {
            "        --device <value>        GPU to use (default 0)\n"
            "        --qvoffset <value>      Quality offset of the input (default 33)\n"
            "        --trim-quality <value>  Ns and bases of at most this quality are trimmed from the ends (default 4)\n"
-           "        --cluster               Also cluster the Hamming graph of the k-mers (tau = 1)\n\n"
+           "        --cluster               Also cluster the Hamming graph of the k-mers (tau = 1)\n"
+           "        --subcluster            Also subcluster the Hamming clusters and mark the solid k-mers (implies --cluster)\n"
+           "        --singleton-threshold <value>     bayes_singleton_threshold (default 0.995)\n"
+           "        --nonsingleton-threshold <value>  bayes_nonsingleton_threshold (default 0.9)\n"
+           "        --correct-threshold <value>       correct_threshold (default 0.98)\n"
+           "        --no-correct-threshold            correct_use_threshold 0\n\n"
            "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
            "        Output: <prefix>.kmers - the k-mers in ascending order, in the final_kmers record format;\n"
            "        <prefix>.kmstat - per k-mer: 32-bit count << 1, float total_qual, the 6-bit quality sums packed into 64-bit words;\n"
-           "        with --cluster <prefix>.hamming and <prefix>.hamming.idx as spades-hamcluster writes them.\n",
+           "        with --cluster <prefix>.hamming and <prefix>.hamming.idx as spades-hamcluster writes them;\n"
+           "        with --subcluster the good bit in <prefix>.kmstat, the new k-mers' records after the others, and\n"
+           "        <prefix>.subclusters, <prefix>.subclusters.idx, <prefix>.newkmers.\n",
            argv0);
 }
 
@@ -110,7 +121,8 @@ int main(int argc, char **argv) {
     unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4;
     std::string prefix, dataset;
     std::vector<std::string> input;
-    bool help = false, bad = false, cluster = false;
+    bool help = false, bad = false, cluster = false, subcluster = false;
+    bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         auto need = [&](unsigned long long *v) { return i + 1 < argc && parse_uint(argv[++i], v); };
@@ -122,6 +134,15 @@ int main(int argc, char **argv) {
         else if (a == "--qvoffset") { if (need(&v)) qvoffset = v; else bad = true; }
         else if (a == "--trim-quality") { if (need(&v)) trim_quality = v; else bad = true; }
         else if (a == "--cluster") cluster = true;
+        else if (a == "--subcluster") cluster = subcluster = true;
+        else if (a == "--no-correct-threshold") sp.correct_use_threshold = 0;
+        else if (a == "--singleton-threshold" || a == "--nonsingleton-threshold" || a == "--correct-threshold") {
+            char *end = nullptr;
+            const double d = i + 1 < argc ? strtod(argv[++i], &end) : 0.0;
+            if (!end || end == argv[i] || *end) bad = true;
+            else (a == "--singleton-threshold" ? sp.singleton_threshold
+                  : a == "--nonsingleton-threshold" ? sp.nonsingleton_threshold : sp.correct_threshold) = d;
+        }
         else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
         else if (a == "-o" || a == "--output") { if (i + 1 < argc) prefix = argv[++i]; else bad = true; }
         else if (a == "-h" || a == "--help") help = true;
@@ -199,12 +220,49 @@ int main(int argc, char **argv) {
         check(bbk_kmerset_export(ctx, set, BBK_ORDER_SORTED, buf.data(), nullptr), "bbk_kmerset_export");
         write_u64(prefix + ".kmers", buf.data(), buf.size());
     }
-    check(bbk_kmerstats_write(ctx, ks, (prefix + ".kmstat").c_str()), "bbk_kmerstats_write");
+    if (!subcluster) check(bbk_kmerstats_write(ctx, ks, (prefix + ".kmstat").c_str()), "bbk_kmerstats_write");
     if (hc) {
         check(bbk_hamclusters_write(ctx, hc, (prefix + ".hamming").c_str()), "bbk_hamclusters_write");
         info("Clustering done. Total clusters: %llu", (unsigned long long)bbk_hamclusters_count(hc));
-        bbk_hamclusters_free(hc);
     }
+    if (subcluster) {
+        bbk_subclusters *sc = nullptr;
+        check(bbk_hamclusters_subcluster(ctx, set, hc, ks, &sp, &sc), "bbk_hamclusters_subcluster");
+        check(bbk_subclusters_write(ctx, sc, ks, prefix.c_str()), "bbk_subclusters_write");
+        uint64_t st[9], errs[16];
+        check(bbk_subclusters_export(ctx, sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, st),
+              "bbk_subclusters_export");
+        const uint64_t gsingl = st[0], tsingl = st[1], tcsingl = st[2], gcsingl = st[3], tcls = st[4], gcls = st[5],
+                       tkmers = st[6], tncls = st[7], newkmers = st[8];
+        // kmer_cluster.cpp:650-658
+        info("Subclustering done. Total %llu non-read kmers were generated.", (unsigned long long)newkmers);
+        info("Subclustering statistics:");
+        info("  Total singleton hamming clusters: %llu. Among them %llu (%g%%) are good", (unsigned long long)tsingl,
+             (unsigned long long)gsingl, 100.0 * (double)gsingl / (double)tsingl);
+        info("  Total singleton subclusters: %llu. Among them %llu (%g%%) are good", (unsigned long long)tcsingl,
+             (unsigned long long)gcsingl, 100.0 * (double)gcsingl / (double)tcsingl);
+        info("  Total non-singleton subcluster centers: %llu. Among them %llu (%g%%) are good", (unsigned long long)tcls,
+             (unsigned long long)gcls, 100.0 * (double)gcls / (double)tcls);
+        info("  Average size of non-trivial subcluster: %g kmers", 1.0 * (double)tkmers / (double)tcls);
+        info("  Average number of sub-clusters per non-singleton cluster: %g", 1.0 * (double)(tcsingl + tcls) / (double)tncls);
+        info("  Total solid k-mers: %llu", (unsigned long long)(gsingl + gcsingl + gcls));
+        std::string m;
+        for (int r = 0; r < 4; ++r) {
+            uint64_t row = 0;
+            for (int c = 0; c < 4; ++c) row += errs[4 * r + c];
+            for (int c = 0; c < 4; ++c) {
+                char b[64];
+                snprintf(b, sizeof(b), "%s%g", c ? "," : "", (double)errs[4 * r + c] / (double)row);
+                m += b;
+            }
+            m += r < 3 ? ")," : ")";
+            if (r < 3) m += "(";
+        }
+        info("  Substitution probabilities: [4,4]((%s)", m.c_str());
+        info("  K-mers subclustered on the host: %llu", (unsigned long long)bbk_subclusters_host_kmers(sc));
+        bbk_subclusters_free(sc);
+    }
+    if (hc) bbk_hamclusters_free(hc);
     {
         std::vector<uint32_t> cnt((size_t)n);
         check(bbk_kmerstats_export(ctx, ks, cnt.data(), nullptr, nullptr), "bbk_kmerstats_export");
