@@ -14,7 +14,7 @@ PROGRAMS = {"spades-kmercount": "kmercount_main.cpp", "spades-gbuilder": "gbuild
             "contig_abundance_counter": "contig_abundance_counter_main.cpp",
             "spades-hamcluster": "hamcluster_main.cpp", "spades-kmerdata": "kmerdata_main.cpp",
             "bbk-hammer-reads-dump": "hammer_reads_dump_main.cpp"}
-HEADERS = ["common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp", "hammer_reads.hpp"]
+HEADERS = ["cli.hpp", "common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp", "hammer_reads.hpp"]
 
 
 def build(force=False, verbose=False):

@@ -1,5 +1,6 @@
-// common.hpp -- shared host plumbing of the two CLIs: logging in the reference's style
-// (common/utils/logger: elapsed time prefix), C-ABI error handling, batched upload of reads.
+// common.hpp -- shared host plumbing of the CLIs: logging in the reference's style (common/utils/logger: elapsed time
+// prefix), C-ABI error handling, the frame of a run (Run), batched upload of reads, and the steps several tools share.
+// A new tool is an option table (cli.hpp), its usage text and a body between Run::create_ctx and Run::done.
 #pragma once
 
 #include <unistd.h>
@@ -18,6 +19,7 @@
 #include <omp.h>
 
 #include "../../include/bbk.h"
+#include "cli.hpp"
 #include "dataset.hpp"
 #include "fastx.hpp"
 #include "ingest.hpp"
@@ -196,11 +198,104 @@ inline uint64_t stream_reads(bbk_ctx *&ctx, const std::vector<std::string> &file
     return total;
 }
 
-inline bool parse_uint(const char *s, unsigned long long *v) {
-    if (!s || !*s) return false;
-    char *end = nullptr;
-    *v = strtoull(s, &end, 10);
-    return end && *end == 0;
+// Streams `files` into a counter of k-mers (bbk_count_begin with `flags`) and returns the finished set; the time of
+// bbk_count_finish is added to ph.finish.  `before` (optional) runs first inside stream_reads' init hook: a tool that
+// creates its context under the parse of the first block passes Run::create_ctx there.
+inline bbk_kmerset *count_files(bbk_ctx *&ctx, Phases &ph, const std::vector<std::string> &files, unsigned k, unsigned flags,
+                                size_t block_bytes, int threads, const std::function<void()> &before = nullptr) {
+    bbk_counter *counter = nullptr;
+    stream_reads(
+        ctx, files, block_bytes, threads, ph,
+        [&](bbk_reads *r) { check(bbk_count_push_reads(counter, r), "bbk_count_push_reads"); },
+        [&] {
+            if (before) before();
+            check(bbk_count_begin(ctx, k, flags, &counter), "bbk_count_begin");
+        });
+    const double t0 = now_s();
+    bbk_kmerset *set = nullptr;
+    check(bbk_count_finish(counter, &set), "bbk_count_finish");
+    ph.finish += now_s() - t0;
+    return set;
 }
+
+// One run of a tool: its phases, its start and its context.  The clock starts where the Run is declared.
+struct Run {
+    Phases ph;
+    const double t_start = now_s();
+    bbk_ctx *ctx = nullptr;
+    void create_ctx(unsigned device) {
+        const double t0 = now_s();
+        check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
+        ph.ctx = now_s() - t0;
+    }
+    void report(const char *tool) {  // the BBK_PHASES line
+        ph.total = now_s() - t_start;
+        ph.memory(ctx);
+        ph.report(tool);
+    }
+    [[noreturn]] void leave() { finish_process(ctx, 0); }
+    [[noreturn]] void done(const char *tool) {
+        report(tool);
+        leave();
+    }
+};
+
+// The read files of a tool that takes them as words or from a -d dataset (which wins); neither: the reference's error
+// (projects/kmercount/main.cpp:178-182), the tool's usage and exit(-1).
+inline std::vector<std::string> input_files(const std::vector<std::string> &input, const std::string &dataset) {
+    if (dataset.empty()) return input;
+    std::vector<std::string> files;
+    std::string err;
+    if (!load_dataset_yaml(dataset, files, err)) fatal("%s", err.c_str());
+    return files;
+}
+inline void require_input(const std::vector<std::string> &input, const std::string &dataset, void (*usage)(const char *),
+                          const char *argv0) {
+    if (!input.empty() || !dataset.empty()) return;
+    fprintf(stderr, "ERROR: No input files were specified\n\n");
+    usage(argv0);
+    exit(255);
+}
+
+// the k of a tool that works on a de Bruijn graph (projects/gbuilder/main.cpp:121-126)
+inline void check_graph_k(unsigned k) {
+    if (k < 1) fatal("k-mer size %u is too low", k);
+    if (k >= BBK_MAX_K) fatal("k-mer size %u is too high, recompile with larger SPADES_MAX_K option", k);
+    if (k % 2 == 0) fatal("k-mer size must be odd");
+}
+
+inline void require_gfa(const std::string &graph) {
+    if (!ends_with(graph, ".gfa"))
+        fatal("graph %s: only a GFA graph (*.gfa) is read; the SPAdes binary graph pack is not supported", graph.c_str());
+}
+
+inline void write_u64(const std::string &path, const uint64_t *p, size_t count) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) fatal("cannot open %s for writing", path.c_str());
+    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
+    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
+}
+
+// Sequences cut into pieces at the characters `cut` names: the pieces back to back, and the first piece of every sequence
+struct PieceBlock {
+    std::string bases;
+    std::vector<uint64_t> off{0};
+    std::vector<uint64_t> first_piece{0};
+    uint64_t sequences() const { return first_piece.size() - 1; }
+    uint64_t pieces() const { return off.size() - 1; }
+    template <class Cut>
+    void add(const std::string &seq, Cut cut) {
+        size_t l = 0;
+        for (size_t j = 0; j <= seq.size(); ++j) {
+            if (j < seq.size() && !cut(seq[j])) continue;
+            if (j > l) {
+                bases.append(seq, l, j - l);
+                off.push_back(bases.size());
+            }
+            l = j + 1;
+        }
+        first_piece.push_back(pieces());
+    }
+};
 
 }  // namespace bbkhost

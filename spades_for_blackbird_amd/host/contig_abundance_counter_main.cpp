@@ -32,16 +32,6 @@ bool ls(double a, double b) {
     return a < b;
 }
 
-struct Block {
-    std::string bases;  // the pieces back to back
-    std::vector<uint64_t> off{0};
-    std::vector<uint64_t> first_piece{0};
-    std::vector<std::string> names;
-    std::vector<uint64_t> length;  // of the whole contig, other characters included
-    uint64_t contigs() const { return names.size(); }
-    uint64_t pieces() const { return off.size() - 1; }
-};
-
 void usage() {
     printf("Usage: contig_abundance_counter -k <K> -c <contigs path> -n <sample cnt> -m <kmer multiplicities path> "
            "-o <contigs abundance path> [-v] [-l <contig length bound> (default: 0)]\n"
@@ -51,40 +41,27 @@ void usage() {
 }  // namespace
 
 int main(int argc, char **argv) {
-    unsigned long long k = 0, n = 0, min_len = 0, device = 0, bufsize = 268435456ull;
-    bool have_k = false, have_n = false, var = false, bad = false;
+    unsigned long long k = 0, n = 0, min_len = 0, bufsize = 268435456ull;
+    unsigned device = 0;
+    bool var = false;
     std::string contigs, prefix, outfile;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        auto need = [&](unsigned long long *x) { return i + 1 < argc && parse_uint(argv[++i], x); };
-        auto str = [&](std::string *x) { return i + 1 < argc ? (*x = argv[++i], true) : false; };
-        if (a == "-k") { if (need(&k)) have_k = true; else bad = true; }
-        else if (a == "-n") { if (need(&n)) have_n = true; else bad = true; }
-        else if (a == "-l") { if (!need(&min_len)) bad = true; }
-        else if (a == "-b") { if (!need(&bufsize) || bufsize == 0) bad = true; }
-        else if (a == "--device") { if (!need(&device)) bad = true; }
-        else if (a == "-c") { if (!str(&contigs)) bad = true; }
-        else if (a == "-m") { if (!str(&prefix)) bad = true; }
-        else if (a == "-o") { if (!str(&outfile)) bad = true; }
-        else if (a == "-v") var = true;
-        else bad = true;
-    }
-    if (bad || !have_k || !have_n || contigs.empty() || prefix.empty() || outfile.empty()) {  // GetOptEx (:67-72)
-        usage();
+    Options opt;
+    opt.num("-k", "", &k).num("-n", "", &n).num("-l", "", &min_len).num("-b", "", &bufsize, 1ull).num("", "--device", &device)
+        .str("-c", "", &contigs).str("-m", "", &prefix).str("-o", "", &outfile).flag("-v", "", &var);
+    if (!opt.parse(argc, argv) || !opt.seen("-k") || !opt.seen("-n") || contigs.empty() || prefix.empty() || outfile.empty()) {
+        usage();  // GetOptEx (:67-72)
         return 1;
     }
     info("Starting contig abundance counter (MI355X, %s)", bbk_version());
     if (k < 1 || k >= BBK_MAX_K) fatal("k-mer size %llu is out of range [1,%d)", k, BBK_MAX_K);
     if (n < 1 || n > 65535) fatal("sample count %llu is out of range [1,65535]", n);
 
-    Phases ph;
-    const double t_start = now_s();
-    bbk_ctx *ctx = nullptr;
-    double t0 = now_s();
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-    ph.ctx = now_s() - t0;
+    Run run;
+    Phases &ph = run.ph;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
     info("Loading kmer index from %s.kmers and profiles from %s.bpr", prefix.c_str(), prefix.c_str());
-    t0 = now_s();
+    const double t0 = now_s();
     bbk_kmerprofile *p = nullptr;
     check(bbk_kmerprofile_load(ctx, prefix.c_str(), (unsigned)k, (unsigned)n, &p), "bbk_kmerprofile_load");
     ph.finish = now_s() - t0;
@@ -96,10 +73,12 @@ int main(int argc, char **argv) {
     if (!out) fatal("cannot open %s for writing", outfile.c_str());
     const unsigned N = (unsigned)n;
     uint64_t n_contigs = 0, n_lines = 0;
-    Block blk;
+    PieceBlock blk;                  // the ACGT stretches of the contigs
+    std::vector<std::string> names;  // of the block's contigs
+    std::vector<uint64_t> length;    // of the whole contig, other characters included
     std::string text;
     auto flush = [&] {
-        const uint64_t nc = blk.contigs(), np = blk.pieces();
+        const uint64_t nc = blk.sequences(), np = blk.pieces();
         if (nc == 0) return;
         std::vector<uint64_t> hn(nc, 0), hpos(nc, 0), hsum(nc * N, 0), hsq(nc * N, 0);
         if (np > 0) {
@@ -120,9 +99,9 @@ int main(int argc, char **argv) {
         char buf[64];
         for (uint64_t c = 0; c < nc; ++c) {
             if (hn[c] == 0) continue;  // a share of 0 (or the reference's 0 / 0)
-            const uint64_t denom = blk.length[c] - k + 1;  // size_t arithmetic, as s.size() - k_ + 1
+            const uint64_t denom = length[c] - k + 1;  // size_t arithmetic, as s.size() - k_ + 1
             if (ls((double)hn[c] / (double)denom, 0.7)) continue;
-            text += blk.names[c];
+            text += names[c];
             text += '\t';
             for (unsigned s = 0; s < N; ++s) {
                 // float, one rounded operation per statement (no contraction into a fused multiply-add)
@@ -145,25 +124,17 @@ int main(int argc, char **argv) {
         if (!text.empty() && fwrite(text.data(), 1, text.size(), out) != text.size())
             fatal("writing %s failed", outfile.c_str());
         ph.write += now_s() - t1;
-        blk = Block();
+        blk = PieceBlock();
+        names.clear();
+        length.clear();
     };
     const double tl = now_s();
     std::string name, seq, qual;
     while (rd.next_record(name, seq, qual)) {  // upper-cased by the reader; is_nucl takes either case
         if (seq.size() < min_len) break;
-        uint64_t l = 0;
-        for (uint64_t j = 0; j <= seq.size(); ++j) {
-            const char ch = j < seq.size() ? seq[j] : 'N';
-            if (ch == 'A' || ch == 'C' || ch == 'G' || ch == 'T') continue;
-            if (j > l) {
-                blk.bases.append(seq, l, j - l);
-                blk.off.push_back(blk.bases.size());
-            }
-            l = j + 1;
-        }
-        blk.first_piece.push_back(blk.pieces());
-        blk.names.push_back(name);
-        blk.length.push_back(seq.size());
+        blk.add(seq, [](char ch) { return ch != 'A' && ch != 'C' && ch != 'G' && ch != 'T'; });
+        names.push_back(name);
+        length.push_back(seq.size());
         ++n_contigs;
         if (blk.bases.size() >= bufsize) flush();
     }
@@ -173,8 +144,5 @@ int main(int argc, char **argv) {
     info("%llu contigs analysed, %llu abundance lines written to %s", (unsigned long long)n_contigs,
          (unsigned long long)n_lines, outfile.c_str());
     bbk_kmerprofile_free(p);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("contig_abundance_counter");
-    finish_process(ctx, 0);
+    run.done("contig_abundance_counter");
 }

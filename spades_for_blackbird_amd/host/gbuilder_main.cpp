@@ -43,43 +43,27 @@ int main(int argc, char **argv) {
     unsigned k = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull;  // projects/gbuilder/main.cpp:47-52
     unsigned long long tip_bound = 0;
-    bool coverage = false, bad = false, at_clip = false, tip_clip = false;
+    bool coverage = false, at_clip = false;
     enum { UNITIGS, FASTG, GFA, SPADES } mode = UNITIGS;
     int modes_given = 0;
     std::vector<std::string> pos;
-    std::string devices_arg, exchange_arg = "rccl";
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        unsigned long long v = 0;
-        auto need = [&](unsigned long long *x) { return i + 1 < argc && parse_uint(argv[++i], x); };
-        if (a == "-k") { if (need(&v)) k = (unsigned)v; else bad = true; }
-        else if (a == "-c") coverage = true;
-        else if (a == "-t") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "-b") { if (need(&v)) bufsize = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "--devices") { if (i + 1 < argc) devices_arg = argv[++i]; else bad = true; }
-        else if (a == "--exchange") { if (i + 1 < argc) exchange_arg = argv[++i]; else bad = true; }
-        else if (a == "-tmp-dir") { if (i + 1 < argc) ++i; else bad = true; }
-        else if (a == "--early-at-clip") at_clip = true;
-        else if (a == "--early-tip-clip") { if (need(&tip_bound) && tip_bound <= 0xFFFFFFFFull) tip_clip = true; else bad = true; }
-        else if (a == "--unitigs") { mode = UNITIGS; ++modes_given; }
-        else if (a == "--fastg") { mode = FASTG; ++modes_given; }
-        else if (a == "--gfa") { mode = GFA; ++modes_given; }
-        else if (a == "--spades") { mode = SPADES; ++modes_given; }
-        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
-        else pos.push_back(a);
-    }
-    if (bad || pos.size() != 2 || modes_given > 1) {  // projects/gbuilder/main.cpp:82-86
+    DeviceArgs dev;
+    Options opt;
+    opt.num("-k", "", &k).flag("-c", "", &coverage).num("-t", "", &threads).num("-b", "", &bufsize).num("", "--device", &device)
+        .ignored("-tmp-dir", "").flag("", "--early-at-clip", &at_clip).num("", "--early-tip-clip", &tip_bound, 0ull, 0xFFFFFFFFull)
+        .flag("", "--unitigs", [&] { mode = UNITIGS, ++modes_given; }).flag("", "--fastg", [&] { mode = FASTG, ++modes_given; })
+        .flag("", "--gfa", [&] { mode = GFA, ++modes_given; }).flag("", "--spades", [&] { mode = SPADES, ++modes_given; })
+        .positional(&pos);
+    dev.add_to(opt);
+    if (!opt.parse(argc, argv) || pos.size() != 2 || modes_given > 1) {  // projects/gbuilder/main.cpp:82-86
         usage(argv[0]);
         return 1;
     }
+    const bool tip_clip = opt.seen("--early-tip-clip");
     const std::string file = pos[0], outfile = pos[1];
 
     info("Starting SPAdes standalone graph builder (MI355X, %s)", bbk_version());
-    // projects/gbuilder/main.cpp:121-126
-    if (k < 1) fatal("k-mer size %u is too low", k);
-    if (k >= BBK_MAX_K) fatal("k-mer size %u is too high, recompile with larger SPADES_MAX_K option", k);
-    if (k % 2 == 0) fatal("k-mer size must be odd");
+    check_graph_k(k);  // projects/gbuilder/main.cpp:121-126
     info("K-mer length set to %u", k);
     switch (mode) {
         case UNITIGS: info("Producing unitigs only"); break;
@@ -101,12 +85,11 @@ int main(int argc, char **argv) {
         files.push_back(file);
     }
 
-    std::vector<int> devices;
-    if (!devices_arg.empty() && !parse_devices(devices_arg, devices)) fatal("--devices: expected a comma-separated list of GPU indices");
-    if (exchange_arg != "rccl" && exchange_arg != "copy") fatal("--exchange: rccl or copy");
-    Phases ph;
-    const double t_start = now_s();
-    bbk_ctx *ctx = nullptr;
+    dev.validate();
+    const std::vector<int> &devices = dev.devices;
+    Run run;
+    Phases &ph = run.ph;
+    bbk_ctx *&ctx = run.ctx;
     const bool want_cov = coverage && mode != UNITIGS;
     bbk_extindex *ext = nullptr;
     bbk_kmerset *kp1 = nullptr;  // -c: ascending canonical (k+1)-mers with multiplicities
@@ -114,9 +97,9 @@ int main(int argc, char **argv) {
     if (!devices.empty()) {
         // ---- several devices: every rank reduces its blocks to (canonical k-mer, OR of mask bits) records, the records go
         //      to the k-mer's owner in one all-to-all, the owners' shards are gathered on rank 0 for the walk
-        auto gf = create_group_async(devices, exchange_arg == "rccl" ? BBK_EXCHANGE_RCCL : BBK_EXCHANGE_COPY);
+        auto gf = create_group_async(devices, dev.exchange());
         const int n = (int)devices.size();
-        info("Using %d device(s), %s exchange", n, exchange_arg.c_str());
+        info("Using %d device(s), %s exchange", n, dev.exchange_arg.c_str());
         std::vector<bbk_counter *> xc((size_t)n, nullptr), cc((size_t)n, nullptr);
         std::vector<bbk_ctx *> ctxs;
         RankHooks hooks;
@@ -158,9 +141,7 @@ int main(int argc, char **argv) {
     bbk_extbuilder *xb = nullptr;
     bbk_counter *covc = nullptr;
     auto init = [&] {
-        const double t0c = now_s();
-        check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-        ph.ctx = now_s() - t0c;
+        run.create_ctx(device);
         check(bbk_extindex_begin(ctx, k, &xb), "bbk_extindex_begin");
         if (want_cov) check(bbk_count_begin(ctx, k + 1, BBK_CANONICAL | BBK_WITH_COUNTS, &covc), "bbk_count_begin");
     };
@@ -232,9 +213,7 @@ int main(int argc, char **argv) {
     }
     bbk_unitigs_free(u);
     bbk_extindex_free(ext);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("spades-gbuilder");
+    run.report("spades-gbuilder");
     info("SPAdes standalone graph builder finished");
-    finish_process(ctx, 0);
+    run.leave();
 }

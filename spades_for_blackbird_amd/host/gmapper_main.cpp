@@ -365,15 +365,6 @@ void write_output(const Graph &g, const std::map<std::vector<Edge>, uint64_t> &p
     if (fclose(f) != 0 || fail) fatal("writing %s failed", path.c_str());
 }
 
-// contigs cut at N: the pieces back to back, and the first piece of every contig
-struct Block {
-    std::string bases;
-    std::vector<uint64_t> off{0};
-    std::vector<uint64_t> first_piece{0};
-    uint64_t contigs() const { return first_piece.size() - 1; }
-    uint64_t pieces() const { return off.size() - 1; }
-};
-
 void usage(const char *argv0) {
     printf("SYNOPSIS\n        %s <dataset description (in YAML)> <graph (in GFA)> <output filename> [-k <value>]\n"
            "           [-t <value>] [--tmp-dir <dir>]\n\n"
@@ -391,32 +382,19 @@ void usage(const char *argv0) {
 int main(int argc, char **argv) {
     unsigned k = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull;
-    bool bad = false;
     std::vector<std::string> pos;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        unsigned long long v = 0;
-        auto need = [&](unsigned long long *x) { return i + 1 < argc && parse_uint(argv[++i], x); };
-        if (a == "-k") { if (need(&v) && v < 1000) k = (unsigned)v; else bad = true; }
-        else if (a == "-t") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "-b") { if (need(&v) && v > 0) bufsize = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "--tmp-dir") { if (i + 1 < argc) ++i; else bad = true; }
-        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
-        else pos.push_back(a);
-    }
-    if (bad || pos.size() != 3) {  // clipp's man page and exit(1) (:77-81)
+    Options opt;
+    opt.num("-k", "", &k, 0u, 999u).num("-t", "", &threads).num("-b", "", &bufsize, 1ull).num("", "--device", &device)
+        .ignored("", "--tmp-dir").positional(&pos);
+    if (!opt.parse(argc, argv) || pos.size() != 3) {  // clipp's man page and exit(1) (:77-81)
         usage(argv[0]);
         return 1;
     }
     const std::string dataset = pos[0], graph = pos[1], outfile = pos[2];
 
     info("Starting SPAdes sequence-to-graph mapper (MI355X, %s)", bbk_version());
-    if (k < 1) fatal("k-mer size %u is too low", k);
-    if (k >= BBK_MAX_K) fatal("k-mer size %u is too high, recompile with larger SPADES_MAX_K option", k);
-    if (k % 2 == 0) fatal("k-mer size must be odd");
-    if (!ends_with(graph, ".gfa"))
-        fatal("graph %s: only a GFA graph (*.gfa) is read; the SPAdes binary graph pack is not supported", graph.c_str());
+    check_graph_k(k);
+    require_gfa(graph);
     std::vector<DatasetLib> libs;
     std::string err;
     if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
@@ -434,15 +412,13 @@ int main(int argc, char **argv) {
                   i, t.c_str());
     }
 
-    Phases ph;
-    const double t_start = now_s();
+    Run run;
+    Phases &ph = run.ph;
     const int nthreads = threads ? (int)std::min<unsigned long long>(threads, 1024) : default_threads();
-    bbk_ctx *ctx = nullptr;
-    double t0 = now_s();
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-    ph.ctx = now_s() - t0;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
     info("Loading de Bruijn graph from %s", graph.c_str());
-    t0 = now_s();
+    double t0 = now_s();
     bbk_edgeindex *ix = nullptr;
     check(bbk_edgeindex_from_gfa_with_graph(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa_with_graph");
     Graph g;
@@ -463,11 +439,11 @@ int main(int argc, char **argv) {
         }
         info("Mapping contigs library #%zu", li);
         std::map<std::vector<Edge>, uint64_t> storage;  // PathStorage: by first edge, then by path; AddPath(path, 1)
-        Block blk;
+        PieceBlock blk;  // the contigs cut at N
         double t_flush = 0;
         auto flush = [&] {
             const double tf = now_s();
-            const uint64_t np = blk.pieces(), nc = blk.contigs();
+            const uint64_t np = blk.pieces(), nc = blk.sequences();
             std::vector<uint64_t> roff(np + 1, 0);
             std::vector<bbk_path_range> ranges;
             if (np > 0) {
@@ -503,7 +479,7 @@ int main(int argc, char **argv) {
             for (auto &v : found)
                 for (auto &p : v) storage[std::move(p)] += 1;
             t_extract += now_s() - t1;
-            blk = Block();
+            blk = PieceBlock();
             t_flush += now_s() - tf;
         };
         const double tl = now_s();
@@ -512,22 +488,12 @@ int main(int argc, char **argv) {
             if (!rd.is_open()) fatal("cannot open %s", file.c_str());
             std::string name, seq, qual;
             while (rd.next_record(name, seq, qual)) {  // upper-cased by the reader, as kseq does
-                uint64_t l = 0;
-                for (uint64_t j = 0; j <= seq.size(); ++j) {
-                    const char c = j < seq.size() ? seq[j] : 'N';
-                    if (c == 'N') {
-                        if (j > l) {
-                            blk.bases.append(seq, l, j - l);
-                            blk.off.push_back(blk.bases.size());
-                        }
-                        l = j + 1;
-                    } else if (c != 'A' && c != 'C' && c != 'G' && c != 'T') {
-                        fatal("contig %s of %s holds '%c' at position %llu: only A, C, G, T and N are accepted (the "
-                              "reference aborts on it)",
-                              name.substr(0, name.find_first_of(" \t")).c_str(), file.c_str(), c, (unsigned long long)j);
-                    }
-                }
-                blk.first_piece.push_back(blk.pieces());
+                const size_t j = seq.find_first_not_of("ACGTN");
+                if (j != std::string::npos)
+                    fatal("contig %s of %s holds '%c' at position %llu: only A, C, G, T and N are accepted (the "
+                          "reference aborts on it)",
+                          name.substr(0, name.find_first_of(" \t")).c_str(), file.c_str(), seq[j], (unsigned long long)j);
+                blk.add(seq, [](char c) { return c == 'N'; });
                 ++n_contigs;
                 if (blk.bases.size() >= bufsize) flush();
             }
@@ -541,8 +507,5 @@ int main(int argc, char **argv) {
     }
     info("%llu contigs mapped; path extraction %.3f s", (unsigned long long)n_contigs, t_extract);
     bbk_edgeindex_free(ix);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("spades-gmapper");
-    finish_process(ctx, 0);
+    run.done("spades-gmapper");
 }

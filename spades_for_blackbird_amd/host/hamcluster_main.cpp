@@ -35,75 +35,38 @@ static void usage(const char *argv0) {
            argv0);
 }
 
-static void write_u64(const std::string &path, const uint64_t *p, size_t count) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) fatal("cannot open %s for writing", path.c_str());
-    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
-    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
-}
-
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull, lock_size = 0, chunk = 0;
     std::string prefix, dataset;
     std::vector<std::string> input;
-    bool help = false, bad = false;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        auto need = [&](unsigned long long *v) { return i + 1 < argc && parse_uint(argv[++i], v); };
-        unsigned long long v = 0;
-        if (a == "-k" || a == "--kmer") { if (need(&v)) K = (unsigned)v; else bad = true; }
-        else if (a == "-t" || a == "--threads") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "-b" || a == "--bufsize") { if (need(&v)) bufsize = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "--lock-size") { if (need(&v)) lock_size = v; else bad = true; }
-        else if (a == "--chunk") { if (need(&v)) chunk = v; else bad = true; }
-        else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
-        else if (a == "-o" || a == "--output") { if (i + 1 < argc) prefix = argv[++i]; else bad = true; }
-        else if (a == "-h" || a == "--help") help = true;
-        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
-        else input.push_back(a);
-    }
-    if (bad || help || (prefix.empty() && !(input.empty() && dataset.empty()))) {
+    bool help = false;
+    Options opt;
+    opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
+        .num("", "--lock-size", &lock_size).num("", "--chunk", &chunk).str("-d", "--dataset", &dataset)
+        .str("-o", "--output", &prefix).flag("-h", "--help", &help).positional(&input);
+    if (!opt.parse(argc, argv) || help || (prefix.empty() && !(input.empty() && dataset.empty()))) {
         usage(argv[0]);
         return help ? 0 : 1;
     }
-    if (input.empty() && dataset.empty()) {
-        fprintf(stderr, "ERROR: No input files were specified\n\n");
-        usage(argv[0]);
-        return 255;
-    }
+    require_input(input, dataset, usage, argv[0]);
     if (K < 1 || K > 32) fatal("k-mer size %u is out of range [1, 32]", K);
 
     info("Starting Hamming-graph clustering (MI355X, %s)", bbk_version());
     info("K-mer length set to %u", K);
-    std::vector<std::string> files = input;
-    if (!dataset.empty()) {
-        files.clear();
-        std::string err;
-        if (!load_dataset_yaml(dataset, files, err)) fatal("%s", err.c_str());
-    }
-    Phases ph;
-    const double t_start = now_s();
-    bbk_ctx *ctx = nullptr;
-    bbk_counter *counter = nullptr;
-    auto init = [&] {
-        const double t0c = now_s();
-        check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-        ph.ctx = now_s() - t0c;
-        check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
-    };
-    stream_reads(ctx, files, (size_t)bufsize, threads ? (int)threads : default_threads(), ph, [&](bbk_reads *r) {
-        check(bbk_count_push_reads(counter, r), "bbk_count_push_reads");
-    }, init);
-    double t0 = now_s();
-    bbk_kmerset *set = nullptr;
-    check(bbk_count_finish(counter, &set), "bbk_count_finish");
+    const std::vector<std::string> files = input_files(input, dataset);
+    Run run;
+    Phases &ph = run.ph;
+    // the context is created while the first block is being parsed
+    bbk_kmerset *set = count_files(run.ctx, ph, files, K, BBK_BOTH_STRANDS, (size_t)bufsize,
+                                   threads ? (int)threads : default_threads(), [&] { run.create_ctx(device); });
+    bbk_ctx *ctx = run.ctx;
     const uint64_t n = bbk_kmerset_size(set);
     info("K-mer counting done. There are %llu kmers in total.", (unsigned long long)n);
+    double t0 = now_s();
     bbk_hamclusters *hc = nullptr;
     check(bbk_kmerset_hamming_clusters(ctx, set, 1, lock_size, chunk, &hc), "bbk_kmerset_hamming_clusters");
-    ph.finish = now_s() - t0;
+    ph.finish += now_s() - t0;
 
     t0 = now_s();
     std::vector<uint64_t> buf((size_t)n);  // one word per k-mer (k <= 32), then reused for the member indices
@@ -122,8 +85,5 @@ int main(int argc, char **argv) {
          (unsigned long long)n, (unsigned long long)clusters, (unsigned long long)largest,
          (unsigned long long)bbk_hamclusters_replayed(hc));
     bbk_hamclusters_free(hc);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("spades-hamcluster");
-    finish_process(ctx, 0);
+    run.done("spades-hamcluster");
 }

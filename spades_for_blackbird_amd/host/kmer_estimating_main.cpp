@@ -26,20 +26,13 @@ static void usage(const char *argv0) {
 
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
+    unsigned long long threads = 0;  // accepted; the parser takes its default
     std::string dataset;
-    bool help = false, bad = false;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        auto need = [&](unsigned long long *v) { return i + 1 < argc && parse_uint(argv[++i], v); };
-        unsigned long long v = 0;
-        if (a == "-k" || a == "--kmer") { if (need(&v)) K = (unsigned)v; else bad = true; }
-        else if (a == "-t" || a == "--threads") { if (!need(&v)) bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
-        else if (a == "-h" || a == "--help") help = true;
-        else bad = true;
-    }
-    if (bad || help || dataset.empty()) {  // kmer_estimating.cpp:50-57: -d is required
+    bool help = false;
+    Options opt;
+    opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("", "--device", &device).str("-d", "--dataset", &dataset)
+        .flag("-h", "--help", &help);
+    if (!opt.parse(argc, argv) || help || dataset.empty()) {  // kmer_estimating.cpp:50-57: -d is required
         usage(argv[0]);
         return help ? 0 : 1;
     }
@@ -47,21 +40,13 @@ int main(int argc, char **argv) {
 
     info("Starting kmer spectra cardinality (MI355X, %s)", bbk_version());
     info("K-mer length set to %u", K);
-    std::vector<std::string> files;
-    std::string err;
-    if (!load_dataset_yaml(dataset, files, err)) fatal("%s", err.c_str());
-    bbk_ctx *ctx = nullptr;
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
+    const std::vector<std::string> files = input_files({}, dataset);
+    Run run;
+    run.create_ctx(device);
     info("Estimating kmer cardinality");
     // strand-independent distinct k-mers: the canonical set; hash-bucket order is enough (no sort); streamed block by block
-    bbk_counter *counter = nullptr;
-    check(bbk_count_begin(ctx, K, BBK_CANONICAL | BBK_UNSORTED, &counter), "bbk_count_begin");
-    Phases ph;
-    stream_reads(ctx, files, 512u << 20, default_threads(), ph,
-                 [&](bbk_reads *r) { check(bbk_count_push_reads(counter, r), "bbk_count_push_reads"); });
-    bbk_kmerset *set = nullptr;
-    check(bbk_count_finish(counter, &set), "bbk_count_finish");
+    bbk_kmerset *set = count_files(run.ctx, run.ph, files, K, BBK_CANONICAL | BBK_UNSORTED, 512u << 20, default_threads());
     info("Kmer number estimation: %llu", (unsigned long long)bbk_kmerset_size(set));  // :99, exact here
     bbk_kmerset_free(set);
-    finish_process(ctx, 0);
+    run.leave();
 }

@@ -40,27 +40,15 @@ static bool exists(const std::string &p) {
 }
 
 int main(int argc, char **argv) {
-    unsigned long long k = 0, n = 0, s = 0, m = 5, threads = 1, ci = 2, cs = 255, device = 0, bufsize = 536870912ull;
-    bool have_k = false, have_n = false, have_s = false, bad = false;
+    unsigned long long k = 0, n = 0, s = 0, m = 5, threads = 1, ci = 2, cs = 255, bufsize = 536870912ull;
+    unsigned device = 0;
     std::string out, dir;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        auto need = [&](unsigned long long *x) { return i + 1 < argc && parse_uint(argv[++i], x); };
-        if (a == "-k") { if (need(&k)) have_k = true; else bad = true; }
-        else if (a == "-n") { if (need(&n)) have_n = true; else bad = true; }
-        else if (a == "-s") { if (need(&s)) have_s = true; else bad = true; }
-        else if (a == "-m" || a == "--min-mult") { if (!need(&m)) bad = true; }
-        else if (a == "-t" || a == "--threads") { if (!need(&threads)) bad = true; }
-        else if (a == "--ci") { if (!need(&ci)) bad = true; }
-        else if (a == "--cs") { if (!need(&cs)) bad = true; }
-        else if (a == "-b") { if (!need(&bufsize) || bufsize == 0) bad = true; }
-        else if (a == "--device") { if (!need(&device)) bad = true; }
-        else if (a == "-o") { if (i + 1 < argc) out = argv[++i]; else bad = true; }
-        else if (a == "-f") { if (i + 1 < argc) dir = argv[++i]; else bad = true; }
-        else bad = true;
-    }
-    if (bad || !have_k || !have_n || !have_s || out.empty() || dir.empty()) {  // GetOptEx (:228-231)
-        usage();
+    Options opt;
+    opt.num("-k", "", &k).num("-n", "", &n).num("-s", "", &s).num("-m", "--min-mult", &m).num("-t", "--threads", &threads)
+        .num("", "--ci", &ci).num("", "--cs", &cs).num("-b", "", &bufsize, 1ull).num("", "--device", &device).str("-o", "", &out)
+        .str("-f", "", &dir);
+    if (!opt.parse(argc, argv) || !opt.seen("-k") || !opt.seen("-n") || !opt.seen("-s") || out.empty() || dir.empty()) {
+        usage();  // GetOptEx (:228-231)
         return 1;
     }
     info("Starting k-mer multiplicity counter (MI355X, %s)", bbk_version());
@@ -85,36 +73,29 @@ int main(int argc, char **argv) {
         files.push_back(found[0]);
     }
 
-    Phases ph;
-    const double t_start = now_s();
-    bbk_ctx *ctx = nullptr;
-    double t0 = now_s();
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-    ph.ctx = now_s() - t0;
+    Run run;
+    Phases &ph = run.ph;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
     bbk_kmerprofile_builder *b = nullptr;
     check(bbk_kmerprofile_begin(ctx, (unsigned)k, (unsigned)n, (unsigned)ci, (unsigned)cs, &b), "bbk_kmerprofile_begin");
     const int nthreads = (int)std::min<unsigned long long>(std::max<unsigned long long>(threads, 1), 1024);
     for (unsigned i = 0; i < (unsigned)n; ++i) {
-        bbk_counter *c = nullptr;
-        check(bbk_count_begin(ctx, (unsigned)k, BBK_CANONICAL | BBK_WITH_COUNTS, &c), "bbk_count_begin");
-        Phases one;
-        stream_reads(ctx, {files[i]}, (size_t)bufsize, nthreads, one,
-                     [&](bbk_reads *r) { check(bbk_count_push_reads(c, r), "bbk_count_push_reads"); });
+        Phases one;  // of this sample: stream_reads sets some fields, the samples add up
+        bbk_kmerset *set = count_files(ctx, one, {files[i]}, (unsigned)k, BBK_CANONICAL | BBK_WITH_COUNTS, (size_t)bufsize, nthreads);
         ph.parse += one.parse;
         ph.parse_wait += one.parse_wait;
         ph.upload += one.upload;
-        ph.device += one.device;
+        ph.device += one.device + one.finish;
         ph.blocks += one.blocks;
         ph.fallback_blocks += one.fallback_blocks;
-        t0 = now_s();
-        bbk_kmerset *set = nullptr;
-        check(bbk_count_finish(c, &set), "bbk_count_finish");
+        const double t0 = now_s();
         info("Sample %u: %llu distinct canonical %llu-mers", i + 1, (unsigned long long)bbk_kmerset_size(set), k);
         check(bbk_kmerprofile_add_sample(b, i, set), "bbk_kmerprofile_add_sample");
         bbk_kmerset_free(set);
         ph.device += now_s() - t0;
     }
-    t0 = now_s();
+    double t0 = now_s();
     bbk_kmerprofile *p = nullptr;
     check(bbk_kmerprofile_finish(b, s, m, &p), "bbk_kmerprofile_finish");
     ph.finish = now_s() - t0;
@@ -124,8 +105,5 @@ int main(int argc, char **argv) {
     ph.write = now_s() - t0;
     info("Saved kmer profiles to %s.bpr, k-mers to %s.kmers", out.c_str(), out.c_str());
     bbk_kmerprofile_free(p);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("kmer_multiplicity_counter");
-    finish_process(ctx, 0);
+    run.done("kmer_multiplicity_counter");
 }

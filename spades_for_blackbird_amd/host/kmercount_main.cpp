@@ -43,55 +43,34 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull;  // projects/kmercount/main.cpp:124-130
-    std::string workdir, dataset, devices_arg, exchange_arg = "rccl";
+    std::string workdir, dataset;
     std::vector<std::string> input;
-    bool help = false, bad = false;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        auto need = [&](unsigned long long *v) { return i + 1 < argc && parse_uint(argv[++i], v); };
-        unsigned long long v = 0;
-        if (a == "-k" || a == "--kmer") { if (need(&v)) K = (unsigned)v; else bad = true; }
-        else if (a == "-t" || a == "--threads") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "-b" || a == "--bufsize") { if (need(&v)) bufsize = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "--devices") { if (i + 1 < argc) devices_arg = argv[++i]; else bad = true; }
-        else if (a == "--exchange") { if (i + 1 < argc) exchange_arg = argv[++i]; else bad = true; }
-        else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
-        else if (a == "-w" || a == "--workdir") { if (i + 1 < argc) workdir = argv[++i]; else bad = true; }
-        else if (a == "-h" || a == "--help") help = true;
-        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
-        else input.push_back(a);
-    }
-    if (bad || help) {  // projects/kmercount/main.cpp:169-176
+    bool help = false;
+    DeviceArgs dev;
+    Options opt;
+    opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
+        .str("-d", "--dataset", &dataset).str("-w", "--workdir", &workdir).flag("-h", "--help", &help).positional(&input);
+    dev.add_to(opt);
+    if (!opt.parse(argc, argv) || help) {  // projects/kmercount/main.cpp:169-176
         usage(argv[0]);
         return help ? 0 : 1;
     }
-    if (input.empty() && dataset.empty()) {  // :178-182
-        fprintf(stderr, "ERROR: No input files were specified\n\n");
-        usage(argv[0]);
-        return 255;  // exit(-1)
-    }
+    require_input(input, dataset, usage, argv[0]);  // :178-182
     if (K < 1 || K >= BBK_MAX_K) fatal("k-mer size %u is out of range [1, %d)", K, BBK_MAX_K);
 
     info("Starting SPAdes k-mer counting engine (MI355X, %s)", bbk_version());
     info("K-mer length set to %u", K);
-    std::vector<std::string> files = input;
-    if (!dataset.empty()) {
-        files.clear();
-        std::string err;
-        if (!load_dataset_yaml(dataset, files, err)) fatal("%s", err.c_str());
-    }
-    std::vector<int> devices;
-    if (!devices_arg.empty() && !parse_devices(devices_arg, devices)) fatal("--devices: expected a comma-separated list of GPU indices");
-    if (exchange_arg != "rccl" && exchange_arg != "copy") fatal("--exchange: rccl or copy");
-    Phases ph;
-    const double t_start = now_s();
+    const std::vector<std::string> files = input_files(input, dataset);
+    dev.validate();
+    const std::vector<int> &devices = dev.devices;
+    Run run;
+    Phases &ph = run.ph;
     if (!devices.empty()) {
         // ---- several devices (or one, through the same code): local count -> owner exchange -> per-rank final_kmers order
         //      -> one file.  The group (RCCL communicators) is set up while the parser reads the first block.
-        auto gf = create_group_async(devices, exchange_arg == "rccl" ? BBK_EXCHANGE_RCCL : BBK_EXCHANGE_COPY);
+        auto gf = create_group_async(devices, dev.exchange());
         const int n = (int)devices.size();
-        info("Using %d device(s), %s exchange", n, exchange_arg.c_str());
+        info("Using %d device(s), %s exchange", n, dev.exchange_arg.c_str());
         const unsigned W = bbk_words(K);
         std::vector<bbk_counter *> counters((size_t)n, nullptr);
         std::vector<ShardOnHost> shards((size_t)n);
@@ -124,38 +103,21 @@ int main(int argc, char **argv) {
         ph.write = now_s() - t0w;
         info("K-mer counting done. There are %llu kmers in total.", (unsigned long long)total);
         info("K-mer counting done, kmers saved to %s", out.c_str());
-        ph.total = now_s() - t_start;
-        ph.report("spades-kmercount");
+        run.report("spades-kmercount");  // run.ctx stays unset: the ranks' memory is not summed
         finish_process(ctxs.empty() ? nullptr : ctxs[0], 0);
     }
-    bbk_ctx *ctx = nullptr;
-    bbk_counter *counter = nullptr;
     // the context (HIP initialisation: 0.1-0.2 s) and the counter are created while the first block is being parsed;
     // the set is built in the final_kmers order (what CountAll(16, ..., merge=true) leaves on disk, :214-219)
-    auto init = [&] {
-        const double t0c = now_s();
-        check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-        ph.ctx = now_s() - t0c;
-        check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS | BBK_REFERENCE_ORDER, &counter), "bbk_count_begin");
-    };
-    stream_reads(ctx, files, (size_t)bufsize, threads ? (int)threads : default_threads(), ph, [&](bbk_reads *r) {
-        check(bbk_count_push_reads(counter, r), "bbk_count_push_reads");
-    }, init);
-    double t0 = now_s();
-    bbk_kmerset *set = nullptr;
-    check(bbk_count_finish(counter, &set), "bbk_count_finish");
-    ph.finish = now_s() - t0;
+    bbk_kmerset *set = count_files(run.ctx, ph, files, K, BBK_BOTH_STRANDS | BBK_REFERENCE_ORDER, (size_t)bufsize,
+                                   threads ? (int)threads : default_threads(), [&] { run.create_ctx(device); });
     // same line as KMerDiskCounter::Count (common/utils/kmer_mph/kmer_index_builder.hpp:260)
     info("K-mer counting done. There are %llu kmers in total.", (unsigned long long)bbk_kmerset_size(set));
     if (!workdir.empty()) mkdir(workdir.c_str(), 0755);
     const std::string out = (workdir.empty() ? std::string("") : workdir + "/") + "final_kmers";
-    t0 = now_s();
-    check(bbk_kmerset_write_final_kmers(ctx, set, out.c_str()), "bbk_kmerset_write_final_kmers");
+    const double t0 = now_s();
+    check(bbk_kmerset_write_final_kmers(run.ctx, set, out.c_str()), "bbk_kmerset_write_final_kmers");
     ph.write = now_s() - t0;
     info("K-mer counting done, kmers saved to %s", out.c_str());
     bbk_kmerset_free(set);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("spades-kmercount");
-    finish_process(ctx, 0);
+    run.done("spades-kmercount");
 }

@@ -109,79 +109,42 @@ static uint64_t for_each_block(const std::vector<std::string> &files, unsigned k
     return records;
 }
 
-static void write_u64(const std::string &path, const uint64_t *p, size_t count) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) fatal("cannot open %s for writing", path.c_str());
-    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
-    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
-}
-
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4;
     std::string prefix, dataset;
     std::vector<std::string> input;
-    bool help = false, bad = false, cluster = false, subcluster = false;
+    bool help = false, cluster = false, subcluster = false;
     bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        auto need = [&](unsigned long long *v) { return i + 1 < argc && parse_uint(argv[++i], v); };
-        unsigned long long v = 0;
-        if (a == "-k" || a == "--kmer") { if (need(&v)) K = (unsigned)v; else bad = true; }
-        else if (a == "-t" || a == "--threads") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "-b" || a == "--bufsize") { if (need(&v)) bufsize = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "--qvoffset") { if (need(&v)) qvoffset = v; else bad = true; }
-        else if (a == "--trim-quality") { if (need(&v)) trim_quality = v; else bad = true; }
-        else if (a == "--cluster") cluster = true;
-        else if (a == "--subcluster") cluster = subcluster = true;
-        else if (a == "--no-correct-threshold") sp.correct_use_threshold = 0;
-        else if (a == "--singleton-threshold" || a == "--nonsingleton-threshold" || a == "--correct-threshold") {
-            char *end = nullptr;
-            const double d = i + 1 < argc ? strtod(argv[++i], &end) : 0.0;
-            if (!end || end == argv[i] || *end) bad = true;
-            else (a == "--singleton-threshold" ? sp.singleton_threshold
-                  : a == "--nonsingleton-threshold" ? sp.nonsingleton_threshold : sp.correct_threshold) = d;
-        }
-        else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
-        else if (a == "-o" || a == "--output") { if (i + 1 < argc) prefix = argv[++i]; else bad = true; }
-        else if (a == "-h" || a == "--help") help = true;
-        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
-        else input.push_back(a);
-    }
-    (void)threads;
-    if (bad || help || (prefix.empty() && !(input.empty() && dataset.empty()))) {
+    Options opt;
+    opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
+        .num("", "--qvoffset", &qvoffset).num("", "--trim-quality", &trim_quality).flag("", "--cluster", &cluster)
+        .flag("", "--subcluster", [&] { cluster = subcluster = true; })
+        .flag("", "--no-correct-threshold", [&] { sp.correct_use_threshold = 0; })
+        .real("", "--singleton-threshold", &sp.singleton_threshold)
+        .real("", "--nonsingleton-threshold", &sp.nonsingleton_threshold).real("", "--correct-threshold", &sp.correct_threshold)
+        .str("-d", "--dataset", &dataset).str("-o", "--output", &prefix).flag("-h", "--help", &help).positional(&input);
+    if (!opt.parse(argc, argv) || help || (prefix.empty() && !(input.empty() && dataset.empty()))) {
         usage(argv[0]);
         return help ? 0 : 1;
     }
-    if (input.empty() && dataset.empty()) {
-        fprintf(stderr, "ERROR: No input files were specified\n\n");
-        usage(argv[0]);
-        return 255;
-    }
+    require_input(input, dataset, usage, argv[0]);
     if (K < 1 || K > 32) fatal("k-mer size %u is out of range [1, 32]", K);
     if (qvoffset > 255 || trim_quality > 93) fatal("--qvoffset / --trim-quality out of range");
 
     info("Starting k-mer statistics (MI355X, %s)", bbk_version());
     info("K-mer length set to %u", K);
-    std::vector<std::string> files = input;
-    if (!dataset.empty()) {
-        files.clear();
-        std::string err;
-        if (!load_dataset_yaml(dataset, files, err)) fatal("%s", err.c_str());
-    }
-    Phases ph;
-    const double t_start = now_s();
-    bbk_ctx *ctx = nullptr;
-    double t0 = now_s();
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-    ph.ctx = now_s() - t0;
+    const std::vector<std::string> files = input_files(input, dataset);
+    Run run;
+    Phases &ph = run.ph;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
 
     // pass 1: the set
     bbk_counter *counter = nullptr;
     check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
     uint64_t stretches = 0;
-    t0 = now_s();
+    double t0 = now_s();
     const uint64_t records = for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, true, [&](const Block &b) {
         check(bbk_count_push_ascii(counter, b.bases.data(), b.offsets.data(), b.size()), "bbk_count_push_ascii");
         stretches += b.size();
@@ -274,8 +237,5 @@ int main(int argc, char **argv) {
     bbk_kmerstats_free(ks);
     bbk_kmerset_free(set);
     ph.write = now_s() - t0;
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("spades-kmerdata");
-    finish_process(ctx, 0);
+    run.done("spades-kmerdata");
 }

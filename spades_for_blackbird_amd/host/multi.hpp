@@ -22,13 +22,25 @@ inline bool parse_devices(const std::string &arg, std::vector<int> &out) {
     while (i < arg.size()) {
         size_t j = arg.find(',', i);
         if (j == std::string::npos) j = arg.size();
-        unsigned long long v = 0;
-        if (j == i || !parse_uint(arg.substr(i, j - i).c_str(), &v) || v > 1023) return false;
+        unsigned v = 0;
+        if (!parse_num(arg.substr(i, j - i).c_str(), &v, 0u, 1023u)) return false;
         out.push_back((int)v);
         i = j + 1;
     }
     return !out.empty();
 }
+
+// `--devices a,b,..` and `--exchange rccl|copy` of the tools that run on several GPUs
+struct DeviceArgs {
+    std::string devices_arg, exchange_arg = "rccl";
+    std::vector<int> devices;  // empty: the single-device path
+    void add_to(Options &o) { o.str("", "--devices", &devices_arg).str("", "--exchange", &exchange_arg); }
+    void validate() {
+        if (!devices_arg.empty() && !parse_devices(devices_arg, devices)) fatal("--devices: expected a comma-separated list of GPU indices");
+        if (exchange_arg != "rccl" && exchange_arg != "copy") fatal("--exchange: rccl or copy");
+    }
+    unsigned exchange() const { return exchange_arg == "rccl" ? BBK_EXCHANGE_RCCL : BBK_EXCHANGE_COPY; }
+};
 
 // The group (RCCL: loading librccl and ncclCommInitAll take seconds) is set up on a thread of its own while the ranks
 // parse and count; the first collective call waits for it.

@@ -161,23 +161,12 @@ int main(int argc, char **argv) {
     unsigned k = 21, thr = 2, device = 0;
     unsigned long long threads = 0;
     std::string dataset, outdir = ".";
-    bool drop_names = false, drop_quality = false, help = false, bad = false;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        unsigned long long v = 0;
-        auto need = [&](unsigned long long *x) { return i + 1 < argc && parse_uint(argv[++i], x); };
-        if (a == "-k" || a == "--kmer") { if (need(&v)) k = (unsigned)v; else bad = true; }
-        else if (a == "-c" || a == "--cov") { if (need(&v)) thr = (unsigned)v; else bad = true; }
-        else if (a == "-t" || a == "--threads") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "-d" || a == "--dataset") { if (i + 1 < argc) dataset = argv[++i]; else bad = true; }
-        else if (a == "-o" || a == "--outdir") { if (i + 1 < argc) outdir = argv[++i]; else bad = true; }
-        else if (a == "--drop-names") drop_names = true;
-        else if (a == "--drop-quality") drop_quality = true;
-        else if (a == "-h" || a == "--help") help = true;
-        else bad = true;
-    }
-    if (bad || help || dataset.empty()) {  // read_filter.cpp:62-70: -d is required
+    bool drop_names = false, drop_quality = false, help = false;
+    Options opt;
+    opt.num("-k", "--kmer", &k).num("-c", "--cov", &thr).num("-t", "--threads", &threads).num("", "--device", &device)
+        .str("-d", "--dataset", &dataset).str("-o", "--outdir", &outdir).flag("", "--drop-names", &drop_names)
+        .flag("", "--drop-quality", &drop_quality).flag("-h", "--help", &help);
+    if (!opt.parse(argc, argv) || help || dataset.empty()) {  // read_filter.cpp:62-70: -d is required
         usage(argv[0]);
         return help ? 0 : 1;
     }
@@ -192,8 +181,9 @@ int main(int argc, char **argv) {
     if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
     mkdir(outdir.c_str(), 0755);
 
-    bbk_ctx *ctx = nullptr;
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
+    Run run;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
 
     // exact multiplicities of the canonical k-mers of every read of every library (the reference: cardinality estimate
     // + CQF fill over single_binary_readers_for_libs(..., followed_by_rc=false, including_paired=true), :139-152)
@@ -202,14 +192,8 @@ int main(int argc, char **argv) {
     for (const DatasetLib &l : libs)
         for (int j = 0; j < 5; ++j)
             for (const std::string &f : l.v[j]) all.push_back(f);
-    bbk_counter *counter = nullptr;
-    check(bbk_count_begin(ctx, k, BBK_CANONICAL | BBK_WITH_COUNTS, &counter), "bbk_count_begin");
     info("Filling kmer coverage");
-    Phases ph;
-    stream_reads(ctx, all, 512u << 20, nthreads, ph,
-                 [&](bbk_reads *r) { check(bbk_count_push_reads(counter, r), "bbk_count_push_reads"); });
-    bbk_kmerset *counts = nullptr;
-    check(bbk_count_finish(counter, &counts), "bbk_count_finish");
+    bbk_kmerset *counts = count_files(run.ctx, run.ph, all, k, BBK_CANONICAL | BBK_WITH_COUNTS, 512u << 20, nthreads);
     info("Kmer coverage filled");
 
     const bool fasta = drop_names || drop_quality;  // read_filter.cpp:181,205,224
@@ -249,5 +233,5 @@ int main(int argc, char **argv) {
     info("Saving filtered dataset description to %s", fname.c_str());
     if (!save_dataset_yaml(fname, outlibs)) fatal("Cannot write %s", fname.c_str());
     bbk_kmerset_free(counts);
-    finish_process(ctx, 0);
+    run.leave();
 }

@@ -29,47 +29,32 @@ static void usage(const char *argv0) {
 int main(int argc, char **argv) {
     unsigned k = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull;
-    bool bad = false;
     std::vector<std::string> pos;
-    for (int i = 1; i < argc; ++i) {
-        const std::string a = argv[i];
-        unsigned long long v = 0;
-        auto need = [&](unsigned long long *x) { return i + 1 < argc && parse_uint(argv[++i], x); };
-        if (a == "-k") { if (need(&v) && v < 1000) k = (unsigned)v; else bad = true; }
-        else if (a == "-t" || a == "--threads") { if (need(&v)) threads = v; else bad = true; }
-        else if (a == "-b") { if (need(&v) && v > 0) bufsize = v; else bad = true; }
-        else if (a == "--device") { if (need(&v)) device = (unsigned)v; else bad = true; }
-        else if (a == "--tmpdir") { if (i + 1 < argc) ++i; else bad = true; }
-        else if (!a.empty() && a[0] == '-' && a.size() > 1) bad = true;
-        else pos.push_back(a);
-    }
-    if (bad || pos.size() != 3) {  // clipp's man page and exit(1) (:100-104)
+    Options opt;
+    opt.num("-k", "", &k, 0u, 999u).num("-t", "--threads", &threads).num("-b", "", &bufsize, 1ull).num("", "--device", &device)
+        .ignored("", "--tmpdir").positional(&pos);
+    if (!opt.parse(argc, argv) || pos.size() != 3) {  // clipp's man page and exit(1) (:100-104)
         usage(argv[0]);
         return 1;
     }
     const std::string dataset = pos[0], graph = pos[1], outfile = pos[2];
 
     info("Starting computing unitig coverage profiles across a list of samples (MI355X, %s)", bbk_version());
-    if (k < 1) fatal("k-mer size %u is too low", k);
-    if (k >= BBK_MAX_K) fatal("k-mer size %u is too high, recompile with larger SPADES_MAX_K option", k);
-    if (k % 2 == 0) fatal("k-mer size must be odd");
+    check_graph_k(k);
     info("K-mer length set to %u", k);
-    if (!ends_with(graph, ".gfa"))
-        fatal("graph %s: only a GFA graph (*.gfa) is read; the SPAdes binary graph pack is not supported", graph.c_str());
+    require_gfa(graph);
 
     std::vector<DatasetLib> libs;
     std::string err;
     if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
     const unsigned S = (unsigned)libs.size();
 
-    Phases ph;
-    const double t_start = now_s();
-    bbk_ctx *ctx = nullptr;
-    double t0 = now_s();
-    check(bbk_ctx_create((int)device, &ctx), "bbk_ctx_create");
-    ph.ctx = now_s() - t0;
+    Run run;
+    Phases &ph = run.ph;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
     info("Loading de Bruijn graph from %s", graph.c_str());
-    t0 = now_s();
+    double t0 = now_s();
     bbk_edgeindex *ix = nullptr;
     check(bbk_edgeindex_from_gfa(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa");
     info("Graph: %llu edges, %llu %u-mers indexed", (unsigned long long)bbk_edgeindex_segments(ix),
@@ -97,9 +82,7 @@ int main(int argc, char **argv) {
     ph.write = now_s() - t0;
     bbk_profiles_free(prof);
     bbk_edgeindex_free(ix);
-    ph.total = now_s() - t_start;
-    ph.memory(ctx);
-    ph.report("unitig-coverage");
+    run.report("unitig-coverage");
     info("Computing unitig coverage profiles finished");
-    finish_process(ctx, 0);
+    run.leave();
 }

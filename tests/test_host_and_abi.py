@@ -48,30 +48,105 @@ def test_no_cpu_fallback():
     assert "import oracle" not in src and "from oracle" not in src and "liboracle" not in src
 
 
-def test_kmercount_argv_contract(bins):
-    exe = bins["spades-kmercount"]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 255 and "No input files were specified" in r.stderr
-    r = subprocess.run([exe, "-h"], capture_output=True, text=True)
-    assert r.returncode == 0 and "--kmer" in r.stdout and "final_kmers" in r.stdout
-    r = subprocess.run([exe, "--bogus", "x.fa"], capture_output=True, text=True)
-    assert r.returncode == 1
-    r = subprocess.run([exe, "-k", "notanumber", "x.fa"], capture_output=True, text=True)
-    assert r.returncode == 1
+Y = "/nonexistent/d.yaml"
+USAGE = (1, "stdout", "SYNOPSIS")  # the usage text and exit(1)
+REQ = ["-k", "21", "-n", "2", "-s", "1", "-o", "p", "-f", "/nonexistent"]  # kmer_multiplicity_counter's required options
+ABU = ["-k", "21", "-n", "2", "-c", "c", "-m", "m", "-o", "o"]             # contig_abundance_counter's
+
+# (tool, argv, exit code, stream, words that must appear there); every row ends before the first HIP call
+ARGV_ROWS = [
+    ("spades-kmercount", [], 255, "stderr", "No input files were specified"),
+    ("spades-kmercount", ["-h"], 0, "stdout", ("--kmer", "final_kmers")),
+    ("spades-kmercount", ["--bogus", "x.fa"], *USAGE),
+    ("spades-kmercount", ["-k"], *USAGE),
+    ("spades-kmercount", ["-k", "x", "a.fa"], *USAGE),
+    ("spades-kmercount", ["-k", "notanumber", "x.fa"], *USAGE),
+    ("spades-kmercount", ["-k", "128", "a.fa"], 255, "stderr", "out of range"),
+    ("spades-kmercount", ["-k", "0", "a.fa"], 255, "stderr", "out of range"),
+    ("spades-kmercount", ["--devices", "a,b", "a.fa"], 255, "stderr", "comma-separated"),
+    ("spades-kmercount", ["--exchange", "x", "a.fa"], 255, "stderr", "rccl or copy"),
+    ("spades-kmercount", ["-d", Y], 255, "stderr", "cannot open dataset"),
+]
+for _tool in ("spades-hamcluster", "spades-kmerdata"):
+    ARGV_ROWS += [
+        (_tool, [], 255, "stderr", "No input files were specified"),
+        (_tool, ["-h"], 0, "stdout", "SYNOPSIS"),
+        (_tool, ["a.fq"], *USAGE),
+        (_tool, ["-k", "33", "-o", "p", "a.fq"], 255, "stderr", "out of range [1, 32]"),
+        (_tool, ["-o", "p", "-d", Y], 255, "stderr", "cannot open dataset"),
+    ]
+ARGV_ROWS += [
+    ("spades-hamcluster", ["--chunk", "-o", "p", "a.fq"], *USAGE),
+    ("spades-kmerdata", ["--singleton-threshold", "abc", "-o", "p", "a.fq"], *USAGE),
+    ("spades-kmerdata", ["--singleton-threshold"], *USAGE),
+    ("spades-kmerdata", ["--qvoffset", "256", "-o", "p", "a.fq"], 255, "stderr", "out of range"),
+    ("spades-kmerdata", ["--trim-quality", "94", "-o", "p", "a.fq"], 255, "stderr", "out of range"),
+    ("spades-gbuilder", [], 1, "stdout", ("SYNOPSIS", "--gfa")),
+    ("spades-gbuilder", ["a", "b", "-k", "22"], 255, "stderr", "must be odd"),
+    ("spades-gbuilder", ["in.fa", "out.gfa", "-k", "22", "--gfa"], 255, "stderr", "k-mer size must be odd"),
+    ("spades-gbuilder", ["a", "b", "-k", "129"], 255, "stderr", "too high"),
+    ("spades-gbuilder", ["a", "b", "-k", "0"], 255, "stderr", "too low"),
+    ("spades-gbuilder", ["a", "b", "--gfa", "--fastg"], *USAGE),
+    ("spades-gbuilder", ["a", "b", "c"], *USAGE),
+    ("spades-gbuilder", ["a", "b", "--early-tip-clip"], *USAGE),
+    ("spades-gbuilder", ["a", "b", "--early-tip-clip", "4294967296"], *USAGE),
+    ("spades-gbuilder", ["/nonexistent/a", "b", "--gfa", "-tmp-dir", "t"], 255, "stderr", "does not exist"),
+    ("spades-gbuilder", ["/nonexistent/in.fa", "out.gfa", "--gfa"], 255, "stderr", "does not exist"),
+    ("spades-gbuilder", ["/nonexistent/a.yaml", "b"], 255, "stderr", "cannot open dataset"),
+]
+for _tool in ("spades-kmer-estimating", "spades-read-filter"):
+    ARGV_ROWS += [
+        (_tool, [], *USAGE),
+        (_tool, ["-h"], 0, "stdout", "SYNOPSIS"),
+        (_tool, ["-d", Y, "extra"], *USAGE),
+        (_tool, ["-d", Y], 255, "stderr", "cannot open dataset"),
+    ]
+ARGV_ROWS += [
+    ("spades-kmer-estimating", ["-k", "0", "-d", Y], 255, "stderr", "out of range"),
+    ("spades-kmer-estimating", ["-t", "x", "-d", Y], *USAGE),
+    ("spades-read-filter", ["-k", "128", "-d", Y], 255, "stderr", "out of range"),
+]
+for _tool, _tmp in (("unitig-coverage", "--tmpdir"), ("spades-gmapper", "--tmp-dir")):
+    ARGV_ROWS += [
+        (_tool, [], *USAGE),
+        (_tool, ["a", "b"], *USAGE),
+        (_tool, [Y, "g.gfa", "o", "-k", "22"], 255, "stderr", "must be odd"),
+        (_tool, [Y, "g.gfa", "o", "-k", "1000"], *USAGE),
+        (_tool, [Y, "g.gfa", "o", "-k", "999"], 255, "stderr", "too high"),
+        (_tool, [Y, "g.gfa", "o", "-b", "0"], *USAGE),
+        (_tool, [Y, "g.txt", "o"], 255, "stderr", "only a GFA graph"),
+        (_tool, [Y, "g.gfa", "o", _tmp, "t"], 255, "stderr", "cannot open dataset"),
+    ]
+ARGV_ROWS += [
+    ("kmer_multiplicity_counter", [], 1, "stdout", "Usage"),
+    ("kmer_multiplicity_counter", [a for a in REQ if a not in ("-s", "1")], 1, "stdout", "Usage"),
+    ("kmer_multiplicity_counter", ["-k", "200"] + REQ[2:], 255, "stderr", "out of range"),
+    ("kmer_multiplicity_counter", REQ[:2] + ["-n", "0"] + REQ[4:], 255, "stderr", "sample count"),
+    ("kmer_multiplicity_counter", REQ + ["-b", "0"], 1, "stdout", "Usage"),
+    ("kmer_multiplicity_counter", REQ + ["--cs", "70000"], 255, "stderr", "16-bit"),
+    ("kmer_multiplicity_counter", REQ + ["--ci", "0"], 255, "stderr", "at least 1"),
+    ("kmer_multiplicity_counter", REQ, 255, "stderr", "sample 1: none of"),
+    ("kmer_multiplicity_counter", REQ + ["word"], 1, "stdout", "Usage"),
+    ("contig_abundance_counter", [], 1, "stdout", "Usage"),
+    ("contig_abundance_counter", ["-k", "200"] + ABU[2:], 255, "stderr", "out of range"),
+    ("contig_abundance_counter", ABU[:2] + ["-n", "0"] + ABU[4:], 255, "stderr", "sample count"),
+    ("contig_abundance_counter", ABU + ["-b", "0"], 1, "stdout", "Usage"),
+    ("contig_abundance_counter", ABU[:-2], 1, "stdout", "Usage"),
+    # a value that does not fit its destination, or carries a sign, is a usage error (it used to be truncated / wrapped)
+    ("spades-kmercount", ["-k", "4294967317", "-d", Y], *USAGE),
+    ("spades-hamcluster", ["-k", "4294967317", "-o", "p", "-d", Y], *USAGE),
+    ("spades-kmercount", ["-k", "-5", "a.fa"], *USAGE),
+]
 
 
-def test_gbuilder_argv_contract(bins):
-    exe = bins["spades-gbuilder"]
-    r = subprocess.run([exe], capture_output=True, text=True)
-    assert r.returncode == 1 and "--gfa" in r.stdout
-    r = subprocess.run([exe, "in.fa", "out.gfa", "-k", "22", "--gfa"], capture_output=True, text=True)
-    assert r.returncode == 255 and "k-mer size must be odd" in r.stderr
-    r = subprocess.run([exe, "in.fa", "out.gfa", "-k", "129"], capture_output=True, text=True)
-    assert r.returncode == 255 and "too high" in r.stderr
-    r = subprocess.run([exe, "in.fa", "out.gfa", "--gfa", "--fastg"], capture_output=True, text=True)
-    assert r.returncode == 1
-    r = subprocess.run([exe, "/nonexistent/in.fa", "out.gfa", "--gfa"], capture_output=True, text=True)
-    assert r.returncode == 255 and "does not exist" in r.stderr
+def test_argv_contracts(bins, tmp_path):
+    """The argv contract of the ten GPU tools: exit code, and the stream a given word appears on."""
+    for tool, argv, code, stream, words in ARGV_ROWS:
+        r = subprocess.run([bins[tool]] + argv, capture_output=True, text=True, cwd=str(tmp_path))
+        row = (tool, argv, r.returncode, r.stdout[-300:], r.stderr[-300:])
+        assert r.returncode == code, row
+        for w in (words,) if isinstance(words, str) else words:
+            assert w in getattr(r, stream), row
 
 
 def _dump(bins, path):
