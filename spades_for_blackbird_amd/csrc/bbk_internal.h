@@ -393,26 +393,3 @@ struct bbk_extindex {
     bbk::DevBuf masks;  // n u8
     bbk::PrefixIndex prefix;  // lookup accelerator over keys
 };
-
-// shared by hamclust.hip / kmerstat.hip (which fill them) and subclust.hip (which reads both)
-struct bbk_hamclusters {
-    uint64_t n = 0, clusters = 0, replayed = 0;
-    bbk::DevBuf labels;   // n u32: smallest member index of the cluster of k-mer i
-    bbk::DevBuf members;  // n u32: the indices cluster by cluster
-    bbk::DevBuf sizes;    // clusters u64
-};
-
-struct bbk_kmerstats {
-    bbk_ctx *ctx = nullptr;
-    const bbk_kmerset *set = nullptr;  // must outlive the statistics
-    unsigned k = 0, acc_words = 0, qual_words = 0;
-    uint64_t n = 0;
-    bool finished = false, count_overflow = false;
-    bool loaded = false;  // read from a file (bbk_kmerstats_load): finished for good, there are no accumulators
-    bbk::PrefixIndex prefix;
-    bbk::DevBuf probs;       // 256 doubles: Globals::quality_probs
-    bbk::DevBuf rec;         // n * (2 + acc_words) u64
-    bbk::DevBuf count;       // n u32            \.
-    bbk::DevBuf total_qual;  // n f32             > written by finish
-    bbk::DevBuf qual;        // n * qual_words u64 /
-};

@@ -16,25 +16,22 @@
 //   union-find: u32 parents, hooked inside the scan by compare-and-swap on the root with the larger index (a parent is
 //     always below its child, so the root of a tree is its smallest member), then pointer jumping in rounds until a
 //     round changes nothing (one flag read per round).
-//   sizes, the oversize subset, the listing: a histogram of the labels; the members of components of >= lock_size
-//     k-mers are compacted (index, key, rc index) through the scan of primitives.hip and replayed on the host by the
-//     reference's chunked rule -- below lock_size nothing is ever locked and a cluster is its component; the member
-//     indices are grouped by label with the LSD sort (stable: ascending inside a cluster).
+//   sizes, the oversize subset, the listing: a histogram of the labels; the members of components of >= lock_size k-mers
+//     are compacted (index, key, rc index) and replayed on the host by the reference's chunked rule -- below lock_size nothing
+//     is ever locked and a cluster is its component; the LSD sort groups the indices by label (stable: ascending in a cluster).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "bbk_internal.h"
+#include "hammer.h"
 #include "kmer_ops.h"
 
 namespace bbk {
 
 constexpr int kHcTile = 256;
-constexpr uint64_t kHcPairs = 0x5555555555555555ull;
 constexpr uint64_t kHcLockSize = 2500;    // hamcluster.cpp:269
 constexpr uint64_t kHcChunk = 64 * 1024;  // hamcluster.cpp:281
 
@@ -110,9 +107,7 @@ __global__ __launch_bounds__(kHcTile) void k_hc_scan(const uint64_t *__restrict_
                 const uint64_t gj = ts + (uint64_t)j;
                 if (mine && gj > gi && bblk == ablk) {
                     ++later;
-                    uint64_t x = a ^ b;
-                    x = (x | (x >> 1)) & kHcPairs;
-                    if (__popcll(x) == 1) {
+                    if (kmer_hamdist(a, b) == 1) {
                         hc_unite(parent, (uint32_t)gi, (uint32_t)gj);
                         hc_unite(parent, rcidx[gi], rcidx[gj]);
                     }
@@ -272,98 +267,104 @@ static void hc_replay(unsigned k, uint64_t lock_size, uint64_t chunk, const std:
     }
 }
 
-static bbk_hamclusters *hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *s, uint64_t lock_size, uint64_t chunk) {
-    BBK_HIP(hipSetDevice(ctx->device));
-    if (lock_size == 0) lock_size = kHcLockSize;
-    if (chunk == 0) chunk = kHcChunk;
-    auto h = std::make_unique<bbk_hamclusters>();
-    const uint64_t n = s->n;
-    h->n = n;
-    if (n == 0) {
-        h->labels.alloc(16);
-        h->members.alloc(16);
-        h->sizes.alloc(16);
-        return h.release();
-    }
-    const unsigned k = s->k;
-    const uint64_t *keys = s->keys.as<uint64_t>();
-    DevBuf rcidx(n * 4), status(16);
-    PrefixIndex prefix;
-    prefix.build(ctx, keys, 1, k, n);
-    h->labels.alloc(n * 4);
-    uint32_t *label = h->labels.as<uint32_t>();
-    BBK_HIP(hipMemsetAsync(status.p, 0, 16, ctx->stream));
-    launch_items_timed(ctx, "hc_rcidx", k_hc_rcidx, n, s->keys.as<Key<1>>(), n, (int)k, prefix.table(),
-                       rcidx.as<uint32_t>(), label, status.as<uint32_t>());
-    uint32_t h_status[2] = {0, 0};
-    BBK_HIP(hipMemcpyAsync(h_status, status.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
-    BBK_REQUIRE(h_status[0] == 0, BBK_ERR_ARG,
-                "bbk_kmerset_hamming_clusters: the set is not closed under reverse complement (it must be a "
-                "BBK_BOTH_STRANDS set)");
-    prefix.buf.release();
-    {
-        const int shift = 2 * (int)(k - k / 2);
-        KernelTimer t(ctx, "hc_scan");
-        hipLaunchKernelGGL(k_hc_scan, grid_blocks((n + kHcTile - 1) / kHcTile), dim3(kHcTile), 0, ctx->stream, keys, n, shift,
-                           rcidx.as<uint32_t>(), label, status.as<uint32_t>());
-        check_launch("hc_scan");
-    }
-    // pointer jumping: a round that changes nothing ends it; the device decides, the host reads the flag
-    uint64_t rounds = 0;
-    for (uint32_t changed = 1; changed;) {
-        BBK_HIP(hipMemsetAsync(status.as<uint32_t>() + 2, 0, 4, ctx->stream));
-        launch_items_timed(ctx, "hc_jump", k_hc_jump, n, label, n, status.as<uint32_t>() + 2);
-        BBK_HIP(hipMemcpyAsync(&changed, status.as<uint32_t>() + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+// ---- the driver: three phases over one state -----------------------------------------------------------------------------
+struct HcRun {
+    bbk_ctx *ctx;
+    const bbk_kmerset *s;
+    bbk_hamclusters *h;
+    uint64_t n, lock_size, chunk;
+    uint32_t *label = nullptr;  // h->labels: the parents of the union-find, in the end the labels
+    DevBuf rcidx, status;       // n u32; status: [0] an rc is missing, [1] the longest block, [2] a jump round changed something
+    DevBuf cnt, off;            // k-mers per label; flags and their scan
+
+    // the rc index with the closure refusal, the block scan, pointer jumping until a round changes nothing
+    void unite() {
+        const unsigned k = s->k;
+        const uint64_t *keys = s->keys.as<uint64_t>();
+        rcidx.alloc(n * 4);
+        status.alloc(16);
+        uint32_t *st = status.as<uint32_t>(), missing = 0;
+        PrefixIndex prefix;
+        prefix.build(ctx, keys, 1, k, n);
+        h->labels.alloc(n * 4);
+        label = h->labels.as<uint32_t>();
+        BBK_HIP(hipMemsetAsync(st, 0, 16, ctx->stream));
+        launch_items_timed(ctx, "hc_rcidx", k_hc_rcidx, n, s->keys.as<Key<1>>(), n, (int)k, prefix.table(), rcidx.as<uint32_t>(),
+                           label, st);
+        BBK_HIP(hipMemcpyAsync(&missing, st, 4, hipMemcpyDeviceToHost, ctx->stream));
         BBK_HIP(hipStreamSynchronize(ctx->stream));
-        ++rounds;
+        BBK_REQUIRE(missing == 0, BBK_ERR_ARG,
+                    "bbk_kmerset_hamming_clusters: the set is not closed under reverse complement (it must be a BBK_BOTH_STRANDS set)");
+        prefix.buf.release();
+        {
+            const int shift = 2 * (int)(k - k / 2);
+            KernelTimer t(ctx, "hc_scan");
+            hipLaunchKernelGGL(k_hc_scan, grid_blocks((n + kHcTile - 1) / kHcTile), dim3(kHcTile), 0, ctx->stream, keys, n, shift,
+                               rcidx.as<uint32_t>(), label, st);
+            check_launch("hc_scan");
+        }
+        uint64_t rounds = 0;  // the device decides, the host reads the flag
+        for (uint32_t changed = 1; changed; ++rounds) {
+            BBK_HIP(hipMemsetAsync(st + 2, 0, 4, ctx->stream));
+            launch_items_timed(ctx, "hc_jump", k_hc_jump, n, label, n, st + 2);
+            BBK_HIP(hipMemcpyAsync(&changed, st + 2, 4, hipMemcpyDeviceToHost, ctx->stream));
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+        }
+        ctx->add_stat("stat_hc_rounds", (double)rounds);
     }
-    DevBuf cnt(n * 4), off(n * 8 + 16);
-    BBK_HIP(hipMemsetAsync(cnt.p, 0, n * 4, ctx->stream));
-    launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, cnt.as<uint32_t>());
-    launch_items_timed(ctx, "hc_list", k_hc_flag_over, n, label, cnt.as<uint32_t>(), n, lock_size, off.as<uint64_t>());
-    BBK_HIP(hipMemcpyAsync(h_status, status.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    const uint64_t R = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), n);
-    ctx->add_stat("stat_hc_largest_block", (double)h_status[1]);
-    ctx->add_stat("stat_hc_rounds", (double)rounds);
-    h->replayed = R;
-    if (R) {
-        DevBuf oi(R * 4), ok(R * 8), orc(R * 4);
-        launch_items_timed(ctx, "hc_list", k_hc_compact_over, n, label, cnt.as<uint32_t>(), n, lock_size,
-                           off.as<uint64_t>(), keys, rcidx.as<uint32_t>(), oi.as<uint32_t>(), ok.as<uint64_t>(),
-                           orc.as<uint32_t>());
-        std::vector<uint32_t> h_idx(R), h_rc(R), h_lab;
-        std::vector<uint64_t> h_key(R);
-        BBK_HIP(hipMemcpyAsync(h_idx.data(), oi.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(h_key.data(), ok.p, R * 8, hipMemcpyDeviceToHost, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(h_rc.data(), orc.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
+
+    // the sizes of the components; the members of those of >= lock_size k-mers go through hc_replay; returns how many did
+    uint64_t replay_oversize() {
+        cnt.alloc(n * 4);
+        off.alloc(n * 8 + 16);
+        uint32_t *c = cnt.as<uint32_t>(), h_status[2] = {0, 0};
+        uint64_t *o = off.as<uint64_t>();
+        BBK_HIP(hipMemsetAsync(c, 0, n * 4, ctx->stream));
+        launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, c);
+        launch_items_timed(ctx, "hc_list", k_hc_flag_over, n, label, c, n, lock_size, o);
+        BBK_HIP(hipMemcpyAsync(h_status, status.p, 8, hipMemcpyDeviceToHost, ctx->stream));
+        const uint64_t R = exclusive_scan_u64(ctx, o, o, n);  // waits: h_status has arrived
+        ctx->add_stat("stat_hc_largest_block", (double)h_status[1]);
+        if (R) {
+            DevBuf oi(R * 4), ok(R * 8), orc(R * 4);
+            launch_items_timed(ctx, "hc_list", k_hc_compact_over, n, label, c, n, lock_size, o, s->keys.as<uint64_t>(),
+                               rcidx.as<uint32_t>(), oi.as<uint32_t>(), ok.as<uint64_t>(), orc.as<uint32_t>());
+            std::vector<uint32_t> h_idx(R), h_rc(R), h_lab;
+            std::vector<uint64_t> h_key(R);
+            BBK_HIP(hipMemcpyAsync(h_idx.data(), oi.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(h_key.data(), ok.p, R * 8, hipMemcpyDeviceToHost, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(h_rc.data(), orc.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
+            BBK_HIP(hipStreamSynchronize(ctx->stream));
+            hc_replay(s->k, lock_size, chunk, h_idx, h_key, h_rc, h_lab);
+            BBK_HIP(hipMemcpyAsync(orc.p, h_lab.data(), R * 4, hipMemcpyHostToDevice, ctx->stream));
+            launch_items_timed(ctx, "hc_list", k_hc_relabel, R, oi.as<uint32_t>(), orc.as<uint32_t>(), R, label);
+            BBK_HIP(hipMemsetAsync(c, 0, n * 4, ctx->stream));
+            launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, c);
+            BBK_HIP(hipStreamSynchronize(ctx->stream));  // h_lab is read by the copy above
+        }
+        rcidx.release();
+        return R;
+    }
+
+    // the roots and their sizes; the listing: (label, index) records sorted by label, stably, so a cluster's members ascend
+    void list() {
+        uint64_t *o = off.as<uint64_t>();
+        launch_items_timed(ctx, "hc_list", k_hc_flag_roots, n, label, n, o);
+        h->clusters = exclusive_scan_u64(ctx, o, o, n);
+        h->sizes.alloc(h->clusters * 8);
+        launch_items_timed(ctx, "hc_list", k_hc_sizes, n, label, cnt.as<uint32_t>(), o, n, h->sizes.as<uint64_t>());
         BBK_HIP(hipStreamSynchronize(ctx->stream));
-        hc_replay(k, lock_size, chunk, h_idx, h_key, h_rc, h_lab);
-        BBK_HIP(hipMemcpyAsync(orc.p, h_lab.data(), R * 4, hipMemcpyHostToDevice, ctx->stream));
-        launch_items_timed(ctx, "hc_list", k_hc_relabel, R, oi.as<uint32_t>(), orc.as<uint32_t>(), R, label);
-        BBK_HIP(hipMemsetAsync(cnt.p, 0, n * 4, ctx->stream));
-        launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, cnt.as<uint32_t>());
-        BBK_HIP(hipStreamSynchronize(ctx->stream));  // h_lab is read by the copy above
+        cnt.release();
+        off.release();
+        h->members.alloc(n * 4);
+        DevBuf ka(n * 8), kb(n * 8), vb(n * 4);
+        launch_items_timed(ctx, "hc_list", k_hc_pairs, n, label, n, ka.as<uint64_t>(), h->members.as<uint32_t>());
+        unsigned bits = 1;
+        while (bits < 32 && ((n - 1) >> bits)) ++bits;
+        sort_records(ctx, 1, ka.p, kb.p, h->members.as<uint32_t>(), vb.as<uint32_t>(), n, key_passes((bits + 1) / 2));
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
     }
-    rcidx.release();
-    launch_items_timed(ctx, "hc_list", k_hc_flag_roots, n, label, n, off.as<uint64_t>());
-    h->clusters = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), n);
-    h->sizes.alloc(h->clusters * 8);
-    launch_items_timed(ctx, "hc_list", k_hc_sizes, n, label, cnt.as<uint32_t>(), off.as<uint64_t>(), n,
-                       h->sizes.as<uint64_t>());
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
-    cnt.release();
-    off.release();
-    // the listing: (label, index) records ordered by label; the sort is stable, so a cluster's members ascend
-    h->members.alloc(n * 4);
-    DevBuf ka(n * 8), kb(n * 8), vb(n * 4);
-    launch_items_timed(ctx, "hc_list", k_hc_pairs, n, label, n, ka.as<uint64_t>(), h->members.as<uint32_t>());
-    unsigned bits = 1;
-    while (bits < 32 && ((n - 1) >> bits)) ++bits;
-    sort_records(ctx, 1, ka.p, kb.p, h->members.as<uint32_t>(), vb.as<uint32_t>(), n, key_passes((bits + 1) / 2));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
-    return h.release();
-}
+};
 
 static void hc_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_labels, uint64_t *h_members, uint64_t *h_sizes) {
     BBK_HIP(hipSetDevice(ctx->device));
@@ -378,14 +379,6 @@ static void hc_export(bbk_ctx *ctx, const bbk_hamclusters *h, uint64_t *h_labels
     if (h_sizes) d2h_big(ctx, h_sizes, h->sizes.p, h->clusters * 8);
 }
 
-static void hc_write_file(const std::string &path, const uint64_t *p, uint64_t count) {
-    FILE *f = fopen(path.c_str(), "wb");
-    BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path.c_str());
-    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
-    const bool closed = fclose(f) == 0;
-    BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path.c_str());
-}
-
 }  // namespace bbk
 
 using namespace bbk;
@@ -398,16 +391,18 @@ int bbk_kmerset_hamming_clusters(bbk_ctx *ctx, const bbk_kmerset *set, unsigned 
         BBK_REQUIRE(ctx && set && out, BBK_ERR_ARG, "bbk_kmerset_hamming_clusters: NULL argument");
         BBK_REQUIRE(tau == 1, BBK_ERR_ARG, "bbk_kmerset_hamming_clusters: tau = %u: tau > 1 not built (and tau = 0 unites nothing)",
                     tau);
-        BBK_REQUIRE(set->k <= 32, BBK_ERR_ARG, "bbk_kmerset_hamming_clusters: k = %u: one-word keys only (k <= 32)", set->k);
-        BBK_REQUIRE(set->sorted, BBK_ERR_ARG,
-                    "bbk_kmerset_hamming_clusters: the set was built with BBK_UNSORTED: an ascending set is needed");
-        BBK_REQUIRE(!set->ref_order, BBK_ERR_ARG,
-                    "bbk_kmerset_hamming_clusters: the set is in the final_kmers order (BBK_REFERENCE_ORDER): an ascending "
-                    "set is needed");
-        BBK_REQUIRE(set->n < (1ull << 32) - 2, BBK_ERR_ARG,
-                    "bbk_kmerset_hamming_clusters: %llu k-mers: the union-find holds 32-bit parents (fewer than 2^32 - 2)",
-                    (unsigned long long)set->n);
-        *out = hamming_clusters(ctx, set, lock_size, chunk);
+        require_hammer_set("bbk_kmerset_hamming_clusters", set);
+        BBK_HIP(hipSetDevice(ctx->device));
+        auto h = std::make_unique<bbk_hamclusters>();
+        h->n = set->n;
+        for (DevBuf *b : {&h->labels, &h->members, &h->sizes}) b->alloc(16);  // what an empty set keeps
+        if (set->n) {
+            HcRun r{ctx, set, h.get(), set->n, lock_size ? lock_size : kHcLockSize, chunk ? chunk : kHcChunk};
+            r.unite();
+            h->replayed = r.replay_oversize();
+            r.list();
+        }
+        *out = h.release();
     });
 }
 
@@ -428,86 +423,30 @@ int bbk_hamclusters_write(bbk_ctx *ctx, const bbk_hamclusters *h, const char *pa
         BBK_REQUIRE(ctx && h && path, BBK_ERR_ARG, "bbk_hamclusters_write: NULL argument");
         raw_vector<uint64_t> members(h->n), sizes(h->clusters);
         hc_export(ctx, h, nullptr, members.data(), sizes.data());
-        hc_write_file(path, members.data(), h->n);
-        hc_write_file(std::string(path) + ".idx", sizes.data(), h->clusters);
+        write_u64_file(path, members.data(), h->n);
+        write_u64_file(std::string(path) + ".idx", sizes.data(), h->clusters);
     });
 }
 
 int bbk_hamclusters_load(bbk_ctx *ctx, uint64_t n, const char *path, bbk_hamclusters **out) {
     return guarded([&] {
         BBK_REQUIRE(ctx && path && out, BBK_ERR_ARG, "bbk_hamclusters_load: NULL argument");
-        BBK_REQUIRE(n < (1ull << 32) - 2, BBK_ERR_ARG, "bbk_hamclusters_load: %llu k-mers: fewer than 2^32 - 2 are needed",
-                    (unsigned long long)n);
+        require_hammer_count("bbk_hamclusters_load", n);
         BBK_HIP(hipSetDevice(ctx->device));
-        auto read_all = [](const std::string &p, raw_vector<uint64_t> &v) {
-            FILE *f = fopen(p.c_str(), "rb");
-            BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s", p.c_str());
-            fseek(f, 0, SEEK_END);
-            const long long bytes = ftell(f);
-            fseek(f, 0, SEEK_SET);
-            BBK_REQUIRE(bytes >= 0 && bytes % 8 == 0, BBK_ERR_ARG, "bbk_hamclusters_load: %s is not a file of 64-bit values",
-                        p.c_str());
-            v.resize((size_t)bytes / 8);
-            const bool ok = v.empty() || fread(v.data(), 8, v.size(), f) == v.size();
-            fclose(f);
-            BBK_REQUIRE(ok, BBK_ERR_IO, "reading %s failed", p.c_str());
-        };
         raw_vector<uint64_t> mem, sz;
-        read_all(path, mem);
-        read_all(std::string(path) + ".idx", sz);
-        BBK_REQUIRE(mem.size() == n, BBK_ERR_ARG, "bbk_hamclusters_load: %s lists %zu members, the set has %llu k-mers", path,
-                    mem.size(), (unsigned long long)n);
-        uint64_t sum = 0;
-        for (uint64_t s : sz) {
-            BBK_REQUIRE(s >= 1 && s <= n - sum, BBK_ERR_ARG,
-                        "bbk_hamclusters_load: %s.idx: the cluster sizes are not positive numbers that sum to %llu", path,
-                        (unsigned long long)n);
-            sum += s;
-        }
-        BBK_REQUIRE(sum == n, BBK_ERR_ARG, "bbk_hamclusters_load: %s.idx: the cluster sizes sum to %llu, not to %llu", path,
-                    (unsigned long long)sum, (unsigned long long)n);
-        std::vector<uint8_t> seen(n, 0);
-        for (uint64_t m : mem) {
-            BBK_REQUIRE(m < n && !seen[m], BBK_ERR_ARG,
-                        "bbk_hamclusters_load: %s: the members are not a permutation of 0 .. %llu (index %llu is %s)", path,
-                        (unsigned long long)n, (unsigned long long)m, m < n ? "listed twice" : "out of range");
-            seen[m] = 1;
-        }
-        // into the documented order: ascending inside a cluster, clusters by ascending label (the reference lists
-        // clusters by DSU root, concurrent_dsu.cpp:54-69)
-        const size_t C = sz.size();
-        std::vector<uint64_t> start(C + 1, 0);
-        for (size_t c = 0; c < C; ++c) {
-            start[c + 1] = start[c] + sz[c];
-            std::sort(mem.begin() + start[c], mem.begin() + start[c + 1]);
-        }
-        std::vector<size_t> order(C);
-        for (size_t c = 0; c < C; ++c) order[c] = c;
-        std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return mem[start[a]] < mem[start[b]]; });
-        raw_vector<uint32_t> members(n), labels(n);
-        raw_vector<uint64_t> sizes(C);
-        uint64_t o = 0;
-        for (size_t c = 0; c < C; ++c) {
-            const size_t src = order[c];
-            sizes[c] = sz[src];
-            for (uint64_t j = 0; j < sz[src]; ++j) {
-                const uint32_t m = (uint32_t)mem[start[src] + j];
-                members[o++] = m;
-                labels[m] = (uint32_t)mem[start[src]];
-            }
-        }
+        std::vector<uint64_t> sizes;
+        std::vector<uint32_t> members, labels;
+        read_u64_file(path, "bbk_hamclusters_load", mem);
+        read_u64_file(std::string(path) + ".idx", "bbk_hamclusters_load", sz);
+        const std::string err = hamclusters_normalise(path, mem.data(), mem.size(), sz.data(), sz.size(), n, members, labels, sizes);
+        BBK_REQUIRE(err.empty(), BBK_ERR_ARG, "bbk_hamclusters_load: %s", err.c_str());
         auto h = std::make_unique<bbk_hamclusters>();
         h->n = n;
-        h->clusters = C;
-        h->labels.alloc(n * 4);
-        h->members.alloc(n * 4);
-        h->sizes.alloc(C * 8);
-        if (n) {
-            BBK_HIP(hipMemcpyAsync(h->labels.p, labels.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(h->members.p, members.data(), n * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(h->sizes.p, sizes.data(), C * 8, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-        }
+        h->clusters = sizes.size();
+        upload(ctx, h->labels, labels.data(), n);
+        upload(ctx, h->members, members.data(), n);
+        upload(ctx, h->sizes, sizes.data(), sizes.size());
+        if (n) BBK_HIP(hipStreamSynchronize(ctx->stream));  // the three arrays are on this frame
         *out = h.release();
     });
 }

@@ -1,0 +1,114 @@
+// hammer.h -- what hamclust.hip, kmerstat.hip and subclust.hip (the BayesHammer stage) share.  Host code
+// only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit through it.
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+#include "bbk_internal.h"
+#include "hammer_files.h"
+
+struct bbk_hamclusters {
+    uint64_t n = 0, clusters = 0, replayed = 0;
+    bbk::DevBuf labels;   // n u32: smallest member index of the cluster of k-mer i
+    bbk::DevBuf members;  // n u32: the indices cluster by cluster
+    bbk::DevBuf sizes;    // clusters u64
+};
+
+struct bbk_kmerstats {
+    bbk_ctx *ctx = nullptr;
+    const bbk_kmerset *set = nullptr;  // must outlive the statistics
+    unsigned k = 0, acc_words = 0, qual_words = 0;
+    uint64_t n = 0;
+    bool finished = false, count_overflow = false;
+    bool loaded = false;  // read from a file (bbk_kmerstats_load): finished for good, there are no accumulators
+    bbk::PrefixIndex prefix;
+    bbk::DevBuf probs;       // 256 doubles: Globals::quality_probs
+    bbk::DevBuf rec;         // n * (2 + acc_words) u64
+    bbk::DevBuf count;       // n u32            \.
+    bbk::DevBuf total_qual;  // n f32             > written by finish
+    bbk::DevBuf qual;        // n * qual_words u64 /
+};
+
+namespace bbk {
+
+// The k-mer sets of the stage: one-word keys, ascending, k-mer indices in 32 bits with two values to spare.  BBK_CANONICAL
+// is not judged here: the statistics refuse a canonical set by its flag, the clustering by its closure check.
+inline void require_hammer_count(const char *fn, uint64_t n) {
+    BBK_REQUIRE(n < (1ull << 32) - 2, BBK_ERR_ARG, "%s: %llu k-mers: fewer than 2^32 - 2 are needed", fn, (unsigned long long)n);
+}
+inline void require_hammer_set(const char *fn, const bbk_kmerset *set) {
+    BBK_REQUIRE(set->k <= 32, BBK_ERR_ARG, "%s: k = %u: one-word keys only (k <= 32)", fn, set->k);
+    BBK_REQUIRE(set->sorted, BBK_ERR_ARG, "%s: the set was built with BBK_UNSORTED: an ascending set is needed", fn);
+    BBK_REQUIRE(!set->ref_order, BBK_ERR_ARG, "%s: the set is in the final_kmers order (BBK_REFERENCE_ORDER), not ascending", fn);
+    require_hammer_count(fn, set->n);
+}
+
+// Globals::quality_probs / quality_rprobs (projects/hammer/main.cpp:103-108): the error probability of a base of quality q.
+// Host only; 1 - r (kmerstat.hip), log(1 - r) and log(r) - log(3) (subclust.hip) feed results that are pinned bit for bit.
+inline double hammer_error_prob(unsigned q) { return q < 3 ? 0.75 : pow(10.0, -(int)q / 10.0); }
+
+// A host array into a fresh device buffer, asynchronously: the caller waits for the stream before the host memory dies.
+template <class T>
+void upload(bbk_ctx *ctx, DevBuf &dst, const T *src, uint64_t count) {
+    dst.alloc(count * sizeof(T));
+    if (count) BBK_HIP(hipMemcpyAsync(dst.p, src, count * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+}
+
+inline FILE *open_file(const std::string &path, bool writing) {
+    FILE *f = fopen(path.c_str(), writing ? "wb" : "rb");
+    BBK_REQUIRE(f, BBK_ERR_IO, writing ? "cannot open %s for writing" : "cannot open %s", path.c_str());
+    return f;
+}
+inline void write_u64_file(const std::string &path, const uint64_t *p, uint64_t count) {
+    FILE *f = open_file(path, true);
+    const bool ok = count == 0 || fwrite(p, 8, count, f) == count, closed = fclose(f) == 0;
+    BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path.c_str());
+}
+inline void read_u64_file(const std::string &path, const char *fn, raw_vector<uint64_t> &v) {
+    FILE *f = open_file(path, false);
+    fseek(f, 0, SEEK_END);
+    const long long bytes = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    v.resize(bytes > 0 && bytes % 8 == 0 ? (size_t)bytes / 8 : 0);
+    const bool ok = v.empty() || fread(v.data(), 8, v.size(), f) == v.size();
+    fclose(f);
+    BBK_REQUIRE(bytes >= 0 && bytes % 8 == 0, BBK_ERR_ARG, "%s: %s is not a file of 64-bit values", fn, path.c_str());
+    BBK_REQUIRE(ok, BBK_ERR_IO, "reading %s failed", path.c_str());  // both after fclose: a refusal leaves no file open
+}
+
+// The KMerStat records of ks, then new_kmers records of new k-mers, into `path`, 2^20 records at a time; good (device,
+// n + new_kmers u8, or null) supplies bit 0 of every record.  Refuses a count of 2^31 or more.
+inline void write_kmstat(bbk_ctx *ctx, const char *fn, const std::string &path, const bbk_kmerstats *ks, const uint8_t *good,
+                         uint64_t new_kmers) {
+    BBK_REQUIRE(!ks->count_overflow, BBK_ERR_ARG,
+                "%s: a k-mer has 2^31 occurrences or more: the record holds twice the count in 32 bits (kmer_stat.hpp:138-139)", fn);
+    BBK_HIP(hipSetDevice(ctx->device));
+    const uint64_t block = 1ull << 20, n = ks->n, total = n + new_kmers;
+    const unsigned qw = ks->qual_words;
+    const size_t rsz = kmstat_record_bytes(qw);
+    raw_vector<uint32_t> cnt(std::min(n, block));
+    raw_vector<float> tq(cnt.size());
+    raw_vector<uint64_t> qv(cnt.size() * qw);
+    raw_vector<uint8_t> gd(good ? std::min(total, block) : 0);
+    raw_vector<char> buf(std::min(total, block) * rsz);
+    FILE *f = open_file(path, true);
+    bool ok = true;
+    for (uint64_t b = 0; b < total && ok; b += block) {
+        const uint64_t m = std::min(total - b, block);              // records of the block
+        const uint64_t old = b < n ? std::min(n - b, m) : 0;  // those of them that are k-mers of the set
+        if (old) {
+            d2h_big(ctx, cnt.data(), ks->count.as<uint32_t>() + b, old * 4);
+            d2h_big(ctx, tq.data(), ks->total_qual.as<float>() + b, old * 4);
+            d2h_big(ctx, qv.data(), ks->qual.as<uint64_t>() + b * qw, old * qw * 8);
+        }
+        if (good) d2h_big(ctx, gd.data(), good + b, m);
+        kmstat_pack_block(buf.data(), qw, b, m, n, cnt.data(), tq.data(), qv.data(), good ? gd.data() : nullptr);
+        ok = fwrite(buf.data(), rsz, m, f) == m;
+    }
+    const bool closed = fclose(f) == 0;
+    BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path.c_str());
+}
+
+}  // namespace bbk

@@ -65,6 +65,17 @@ __device__ inline uint64_t rev2(uint64_t v) {  // reverse the order of the 32 2-
     return ((v & 0xAAAAAAAAAAAAAAAAull) >> 1) | ((v & 0x5555555555555555ull) << 1);
 }
 
+// Hamming distance of two one-word k-mers: the number of bases (bit pairs) in which they differ
+__host__ __device__ inline uint32_t kmer_hamdist(uint64_t a, uint64_t b) {
+    uint64_t x = a ^ b;
+    x = (x | (x >> 1)) & 0x5555555555555555ull;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__popcll(x);
+#else
+    return (uint32_t)__builtin_popcountll(x);
+#endif
+}
+
 // k-mer starting at base p of a read whose packed words start at rw.
 template <int W>
 __device__ inline Key<W> kmer_extract(const uint64_t *__restrict__ rw, uint32_t p, int k) {

@@ -6,7 +6,7 @@
 // KMerStat(1, (float)(1 - cp), q) is merged into the entry under a spin lock (Merge, :119-123): count += 1, total_qual *=
 // factor (float), qual[i] = min(63, qual[i] + (q[i] & 63)) (NibbleString::operator+=, kmer_stat.hpp:95-101, whose
 // constructor masks and does not saturate, :60-69).  cp is the product of Globals::quality_probs over the window
-// (valid_kmer_generator.hpp:164-199, projects/hammer/main.cpp:103-108).  Which positions are valid -- the trimming of
+// (valid_kmer_generator.hpp:164-199; the table is hammer_error_prob, hammer.h).  Which positions are valid -- the trimming of
 // Read::trimNsAndBadQuality and the generator's own rule -- is the host's business (host/hammer_reads.hpp): every k-mer
 // position of a pushed read is an occurrence.
 //
@@ -27,7 +27,7 @@
 #include <string>
 #include <vector>
 
-#include "bbk_internal.h"
+#include "hammer.h"
 #include "kmer_ops.h"
 
 struct bbk_quals {
@@ -185,6 +185,23 @@ static void ks_finish(bbk_kmerstats *ks) {
     ks->finished = true;
 }
 
+// the handle of bbk_kmerstats_begin / _load over a set the stage accepts, with its lookup index
+static std::unique_ptr<bbk_kmerstats> ks_new(const char *fn, bbk_ctx *ctx, const bbk_kmerset *set) {
+    BBK_REQUIRE(!(set->flags & BBK_CANONICAL), BBK_ERR_ARG,
+                "%s: needs a both-strand k-mer set (bbk_count(BBK_BOTH_STRANDS)): this one is canonical only (BBK_CANONICAL)", fn);
+    require_hammer_set(fn, set);
+    BBK_HIP(hipSetDevice(ctx->device));
+    auto ks = std::make_unique<bbk_kmerstats>();
+    ks->ctx = ctx;
+    ks->set = set;
+    ks->k = set->k;
+    ks->n = set->n;
+    ks->acc_words = (set->k + 9) / 10;
+    ks->qual_words = (6 * set->k + 63) / 64;
+    if (ks->n) ks->prefix.build(ctx, set->keys.as<uint64_t>(), 1, set->k, set->n);
+    return ks;
+}
+
 }  // namespace bbk
 
 using namespace bbk;
@@ -224,9 +241,8 @@ int bbk_quals_from_host(bbk_ctx *ctx, const bbk_reads *reads, const uint8_t *h_q
         q->n = n_reads;
         q->bytes = bytes;
         q->q.alloc(bytes + 16);
-        q->off.alloc((n_reads + 1) * 8);
         if (bytes) BBK_HIP(hipMemcpyAsync(q->q.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        BBK_HIP(hipMemcpyAsync(q->off.p, off.data(), (n_reads + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        upload(ctx, q->off, off.data(), n_reads + 1);
         BBK_HIP(hipStreamSynchronize(ctx->stream));
         *out = q.release();
     });
@@ -237,37 +253,17 @@ void bbk_quals_free(bbk_quals *q) { delete q; }
 int bbk_kmerstats_begin(bbk_ctx *ctx, const bbk_kmerset *set, bbk_kmerstats **out) {
     return guarded([&] {
         BBK_REQUIRE(ctx && set && out, BBK_ERR_ARG, "bbk_kmerstats_begin: NULL argument");
-        BBK_REQUIRE(set->k <= 32, BBK_ERR_ARG, "bbk_kmerstats_begin: k = %u: one-word keys only (k <= 32)", set->k);
-        BBK_REQUIRE(!(set->flags & BBK_CANONICAL) && set->sorted && !set->ref_order, BBK_ERR_ARG,
-                    "bbk_kmerstats_begin: needs an ascending both-strand k-mer set (bbk_count(BBK_BOTH_STRANDS)): this one is "
-                    "%s",
-                    (set->flags & BBK_CANONICAL) ? "canonical only (BBK_CANONICAL)"
-                    : !set->sorted               ? "unsorted (BBK_UNSORTED)"
-                                                 : "in the final_kmers order (BBK_REFERENCE_ORDER)");
-        BBK_REQUIRE(set->n < (1ull << 32) - 2, BBK_ERR_ARG, "bbk_kmerstats_begin: %llu k-mers: fewer than 2^32 - 2 are needed",
-                    (unsigned long long)set->n);
-        BBK_HIP(hipSetDevice(ctx->device));
-        auto ks = std::make_unique<bbk_kmerstats>();
-        ks->ctx = ctx;
-        ks->set = set;
-        ks->k = set->k;
-        ks->n = set->n;
-        ks->acc_words = (set->k + 9) / 10;
-        ks->qual_words = (6 * set->k + 63) / 64;
-        double probs[256];  // projects/hammer/main.cpp:103-105
-        for (unsigned q = 0; q < 256; ++q) probs[q] = 1 - (q < 3 ? 0.75 : pow(10.0, -(int)q / 10.0));
-        ks->probs.alloc(sizeof(probs));
-        BBK_HIP(hipMemcpyAsync(ks->probs.p, probs, sizeof(probs), hipMemcpyHostToDevice, ctx->stream));
+        auto ks = ks_new("bbk_kmerstats_begin", ctx, set);
+        double probs[256];  // Globals::quality_probs
+        for (unsigned q = 0; q < 256; ++q) probs[q] = 1 - hammer_error_prob(q);
+        upload(ctx, ks->probs, probs, 256);
         BBK_HIP(hipStreamSynchronize(ctx->stream));  // probs is on this frame
         const size_t rec_bytes = ks->n * (2 + ks->acc_words) * 8;
         ks->rec.alloc(rec_bytes);
         ks->count.alloc(ks->n * 4);
         ks->total_qual.alloc(ks->n * 4);
         ks->qual.alloc(ks->n * ks->qual_words * 8);
-        if (ks->n) {
-            BBK_HIP(hipMemsetAsync(ks->rec.p, 0, rec_bytes, ctx->stream));
-            ks->prefix.build(ctx, set->keys.as<uint64_t>(), 1, set->k, set->n);
-        }
+        if (ks->n) BBK_HIP(hipMemsetAsync(ks->rec.p, 0, rec_bytes, ctx->stream));
         *out = ks.release();
     });
 }
@@ -319,87 +315,29 @@ int bbk_kmerstats_write(bbk_ctx *ctx, const bbk_kmerstats *ks, const char *path)
     return guarded([&] {
         BBK_REQUIRE(ctx && ks && path, BBK_ERR_ARG, "bbk_kmerstats_write: NULL argument");
         BBK_REQUIRE(ks->finished, BBK_ERR_ARG, "bbk_kmerstats_write: call bbk_kmerstats_finish after the last push");
-        BBK_REQUIRE(!ks->count_overflow, BBK_ERR_ARG,
-                    "bbk_kmerstats_write: a k-mer has 2^31 occurrences or more: the record holds count << 1 in 32 bits "
-                    "(kmer_stat.hpp:138-139)");
-        BBK_HIP(hipSetDevice(ctx->device));
-        FILE *f = fopen(path, "wb");
-        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path);
-        // binary_write(KMerStat), kmer_stat.hpp:170-175: count_with_lock (count << 1, the good bit 0 after mark_bad),
-        // total_qual, the QualBitSet words -- a block of k-mers at a time
-        const uint64_t block = 1ull << 20;
-        const unsigned qw = ks->qual_words;
-        const size_t rsz = 8 + 8 * (size_t)qw;
-        raw_vector<uint32_t> cnt(ks->n < block ? ks->n : block);
-        raw_vector<float> tq(cnt.size());
-        raw_vector<uint64_t> qv(cnt.size() * qw);
-        raw_vector<char> buf(cnt.size() * rsz);
-        bool ok = true;
-        for (uint64_t b = 0; b < ks->n && ok; b += block) {
-            const uint64_t m = ks->n - b < block ? ks->n - b : block;
-            d2h_big(ctx, cnt.data(), ks->count.as<uint32_t>() + b, m * 4);
-            d2h_big(ctx, tq.data(), ks->total_qual.as<float>() + b, m * 4);
-            d2h_big(ctx, qv.data(), ks->qual.as<uint64_t>() + b * qw, m * qw * 8);
-            for (uint64_t i = 0; i < m; ++i) {
-                char *o = buf.data() + i * rsz;
-                const uint32_t c2 = cnt[i] << 1;
-                memcpy(o, &c2, 4);
-                memcpy(o + 4, &tq[i], 4);
-                memcpy(o + 8, &qv[i * qw], 8 * (size_t)qw);
-            }
-            ok = fwrite(buf.data(), rsz, m, f) == m;
-        }
-        const bool closed = fclose(f) == 0;
-        BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path);
+        write_kmstat(ctx, "bbk_kmerstats_write", path, ks, nullptr, 0);
     });
 }
 
 int bbk_kmerstats_load(bbk_ctx *ctx, const bbk_kmerset *set, const char *path, bbk_kmerstats **out) {
     return guarded([&] {
         BBK_REQUIRE(ctx && set && path && out, BBK_ERR_ARG, "bbk_kmerstats_load: NULL argument");
-        BBK_REQUIRE(set->k <= 32 && !(set->flags & BBK_CANONICAL) && set->sorted && !set->ref_order &&
-                        set->n < (1ull << 32) - 2,
-                    BBK_ERR_ARG, "bbk_kmerstats_load: needs what bbk_kmerstats_begin needs: an ascending both-strand set, k <= 32, "
-                                 "fewer than 2^32 - 2 k-mers");
-        BBK_HIP(hipSetDevice(ctx->device));
-        auto ks = std::make_unique<bbk_kmerstats>();
-        ks->ctx = ctx;
-        ks->set = set;
-        ks->k = set->k;
-        ks->n = set->n;
-        ks->acc_words = (set->k + 9) / 10;
-        ks->qual_words = (6 * set->k + 63) / 64;
+        auto ks = ks_new("bbk_kmerstats_load", ctx, set);
         const unsigned qw = ks->qual_words;
-        const size_t rsz = 8 + 8 * (size_t)qw;
-        FILE *f = fopen(path, "rb");
-        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s", path);
-        raw_vector<char> buf(ks->n * rsz + 1);
-        const size_t got = fread(buf.data(), 1, buf.size(), f);
-        fclose(f);
-        BBK_REQUIRE(got == ks->n * rsz, BBK_ERR_ARG,
+        const size_t rsz = kmstat_record_bytes(qw);
+        raw_vector<uint64_t> buf;  // a record is a whole number of 64-bit words
+        read_u64_file(path, "bbk_kmerstats_load", buf);
+        BBK_REQUIRE(buf.size() * 8 == ks->n * rsz, BBK_ERR_ARG,
                     "bbk_kmerstats_load: %s does not hold %llu records of %zu bytes (k = %u), one per k-mer of the set", path,
                     (unsigned long long)ks->n, rsz, ks->k);
         raw_vector<uint32_t> cnt(ks->n);
         raw_vector<float> tq(ks->n);
         raw_vector<uint64_t> qv(ks->n * qw);
-        for (uint64_t i = 0; i < ks->n; ++i) {
-            const char *r = buf.data() + i * rsz;
-            uint32_t c2;
-            memcpy(&c2, r, 4);
-            cnt[i] = c2 >> 1;  // the good bit is not part of the statistics
-            memcpy(&tq[i], r + 4, 4);
-            memcpy(&qv[i * qw], r + 8, 8 * (size_t)qw);
-        }
-        ks->count.alloc(ks->n * 4);
-        ks->total_qual.alloc(ks->n * 4);
-        ks->qual.alloc(ks->n * qw * 8);
-        if (ks->n) {
-            BBK_HIP(hipMemcpyAsync(ks->count.p, cnt.data(), ks->n * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(ks->total_qual.p, tq.data(), ks->n * 4, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(ks->qual.p, qv.data(), ks->n * qw * 8, hipMemcpyHostToDevice, ctx->stream));
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            ks->prefix.build(ctx, set->keys.as<uint64_t>(), 1, set->k, set->n);
-        }
+        kmstat_unpack(reinterpret_cast<const char *>(buf.data()), qw, ks->n, cnt.data(), tq.data(), qv.data());
+        upload(ctx, ks->count, cnt.data(), ks->n);
+        upload(ctx, ks->total_qual, tq.data(), ks->n);
+        upload(ctx, ks->qual, qv.data(), ks->n * qw);
+        if (ks->n) BBK_HIP(hipStreamSynchronize(ctx->stream));  // cnt, tq and qv are on this frame
         ks->finished = ks->loaded = true;
         *out = ks.release();
     });

@@ -2,12 +2,11 @@
 // f10, section 4.3e).
 //
 // Replaces KMerClustering::process / ProcessCluster / SubClusterSingle / lMeansClustering / ClusterBIC / Consensus /
-// ConsensusWithMask (projects/hammer/kmer_cluster.cpp:49-633) over ExpandedKMer (kmer_stat.hpp:205-279) with the tables of
-// projects/hammer/main.cpp:103-108, in the configuration of configs/hammer/config.info: bayes_initial_refine 1,
-// bayes_use_hamming_dist 0, bayes_hammer_mode 0.  Inputs are the clusters of hamclust.hip and the statistics of
-// kmerstat.hip.  Parity with tests/subcluster_restated.py is exact, the bits of every BIC included:
-//   tables: logL(center) = sum over i = 0 .. k-1, from 0.0, of (center[i] == s[i] ? LP[q_i] : LR3[q_i]); LP[q] =
-//     log(1 - r(q)), LR3[q] = log(r(q)) - log(3), 64 entries each, computed on the host (std::pow / std::log) and uploaded.
+// ConsensusWithMask (projects/hammer/kmer_cluster.cpp:49-633) over ExpandedKMer (kmer_stat.hpp:205-279), in the
+// configuration of configs/hammer/config.info: bayes_initial_refine 1, bayes_use_hamming_dist 0, bayes_hammer_mode 0.  Inputs
+// are the clusters of hamclust.hip and the statistics of kmerstat.hip.  Parity with tests/subcluster_restated.py is exact:
+//   tables: logL(center) = sum over i = 0 .. k-1, from 0.0, of (center[i] == s[i] ? LP[q_i] : LR3[q_i]); LP[q] = log(1 - r(q)),
+//     LR3[q] = log(r(q)) - log(3), r = hammer_error_prob (hammer.h), 64 entries each, computed on the host and uploaded.
 //   log(total) of ClusterBIC: the totals of the non-singleton clusters are gathered (k_sc_totals), std::log is taken on
 //     the host and the logs go back up.  The device's log is never called.
 //   no contraction: `#pragma clang fp contract(off)` for the whole file; `loglik += count * logL` is a multiply and an add.
@@ -31,7 +30,7 @@
 #include <string>
 #include <vector>
 
-#include "bbk_internal.h"
+#include "hammer.h"
 #include "kmer_ops.h"
 
 #pragma clang fp contract(off)
@@ -83,16 +82,6 @@ struct ScSlab {
 __host__ __device__ inline bool sc_good_quality(float tq, const ScParams &p) {
     const float q = 1.0f - tq;
     return (double)q > p.singleton || (p.use_correct && (double)q > p.correct);
-}
-
-__host__ __device__ inline uint32_t sc_hamdist(uint64_t a, uint64_t b) {
-    uint64_t x = a ^ b;
-    x = (x | (x >> 1)) & 0x5555555555555555ull;
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__popcll(x);
-#else
-    return (uint32_t)__builtin_popcountll(x);
-#endif
 }
 
 // ExpandedKMer::logL: tab[2 q + (center[i] != s[i])]; q0..q2 are the QualBitSet words of the k-mer
@@ -357,8 +346,8 @@ __global__ __launch_bounds__(NT) void k_sc_cluster(ScIn in, PrefixTable P, const
             if (lane == 0) s_cen[l - 1] = s_key[l - 1];
             __syncthreads();
             if (active) {
-                const uint32_t cdist = sc_hamdist(key, s_cen[ind]);
-                const uint32_t mdist = sc_hamdist(key, s_cen[l - 1]);  // cut off at cdist there: only `<` is read
+                const uint32_t cdist = kmer_hamdist(key, s_cen[ind]);
+                const uint32_t mdist = kmer_hamdist(key, s_cen[l - 1]);  // cut off at cdist there: only `<` is read
                 if (mdist < cdist) ind = l - 1;
                 s_lik[lane] = sc_logl(key, s_cen[ind], q0, q1, q2, k, s_tab);
             }
@@ -457,28 +446,12 @@ __global__ __launch_bounds__(NT) void k_sc_cluster(ScIn in, PrefixTable P, const
 namespace {
 
 struct ScHost {
+    int k, qw;
+    ScParams p;
+    const double *tab;
     std::vector<uint64_t> keys, qual, sizes, off;
     std::vector<uint32_t> count, members;
     std::vector<float> tq;
-    uint64_t n = 0;
-    int k = 0, qw = 0;
-    ScParams p;
-    double tab[128];
-};
-
-struct ScFindHost {
-    const std::vector<uint64_t> *keys;
-    uint64_t operator()(uint64_t key) const {
-        const auto it = std::lower_bound(keys->begin(), keys->end(), key);
-        return it != keys->end() && *it == key ? (uint64_t)(it - keys->begin()) : ~0ull;
-    }
-};
-
-struct ScHostOut {
-    std::vector<uint32_t> mem, size;
-    std::vector<uint64_t> nkey;
-    uint64_t nsub = 0, nmem = 0, nnew = 0;
-    double bic = 0;
 };
 
 struct HostKMer {  // ExpandedKMer
@@ -531,8 +504,8 @@ double sc_host_lmeans(unsigned l, const std::vector<HostKMer> &kmers, std::vecto
     centers[l - 1] = kmers[l - 1].key;
     for (size_t i = 0; i < kmers.size(); ++i) {
         uint32_t cidx = indices[i];
-        const uint32_t cdist = sc_hamdist(kmers[i].key, centers[cidx]);
-        const uint32_t mdist = sc_hamdist(kmers[i].key, centers[l - 1]);
+        const uint32_t cdist = kmer_hamdist(kmers[i].key, centers[cidx]);
+        const uint32_t mdist = kmer_hamdist(kmers[i].key, centers[l - 1]);
         if (mdist < cdist) {
             indices[i] = l - 1;
             cidx = l - 1;
@@ -568,7 +541,8 @@ double sc_host_lmeans(unsigned l, const std::vector<HostKMer> &kmers, std::vecto
     return sc_host_bic(centers, indices, kmers, h);
 }
 
-void sc_host_cluster(const ScHost &h, uint32_t c, ScHostOut &o) {
+// the lists of cluster c into its staging slots (2 m, m and m of them, zero so far), counts = {subclusters, members, new}
+void sc_host_cluster(const ScHost &h, uint32_t c, uint32_t *mem, uint32_t *size, uint64_t *nkey, uint64_t *counts, double *bic) {
     const uint32_t m = (uint32_t)h.sizes[c];
     std::vector<uint32_t> g(h.members.begin() + h.off[c], h.members.begin() + h.off[c] + m);
     std::sort(g.begin(), g.end(), [&](uint32_t a, uint32_t b) {
@@ -605,12 +579,13 @@ void sc_host_cluster(const ScHost &h, uint32_t c, ScHostOut &o) {
     std::vector<int> cic(bestL, -1);
     for (uint32_t i = 0; i < m; ++i)
         if (kmers[i].key == bestCenters[bestIndices[i]]) cic[bestIndices[i]] = (int)i;
-    o.mem.assign(2 * (size_t)m, 0);
-    o.size.assign(m, 0);
-    o.nkey.assign(m, 0);
+    auto find = [&](uint64_t key) {
+        const auto it = std::lower_bound(h.keys.begin(), h.keys.end(), key);
+        return it != h.keys.end() && *it == key ? (uint64_t)(it - h.keys.begin()) : ~0ull;
+    };
     sc_list(m, bestL, bestCenters.data(), bestCount.data(), indices.data(), bestIndices.data(), cic.data(), g.data(),
-            ScFindHost{&h.keys}, o.mem.data(), o.size.data(), o.nkey.data(), &o.nsub, &o.nmem, &o.nnew);
-    o.bic = bestLikelihood;
+            find, mem, size, nkey, &counts[0], &counts[1], &counts[2]);
+    *bic = bestLikelihood;
 }
 
 }  // namespace
@@ -734,223 +709,172 @@ __global__ __launch_bounds__(256) void k_sc_good(uint64_t subs, const uint64_t *
     if (last[cidx] == s + 1) good[cidx] = sval[s];
 }
 
-// ---- the driver -------------------------------------------------------------------------------------------------------
-static void sc_tables(double *tab) {  // main.cpp:103-108, kmer_stat.hpp:211-213
-    for (unsigned q = 0; q < 64; ++q) {
-        const double r = q < 3 ? 0.75 : pow(10.0, -(int)q / 10.0);
-        tab[2 * q] = log(1 - r);
-        tab[2 * q + 1] = log(r) - log(3);
-    }
-}
-
-static uint64_t sc_class(bbk_ctx *ctx, const uint64_t *sizes, uint64_t C, uint64_t lo, uint64_t hi, DevBuf &scratch,
-                         DevBuf &list) {
-    launch_items(ctx, "sc_classes", k_sc_class_flag, C, sizes, C, lo, hi, scratch.as<uint64_t>());
-    const uint64_t cnt = exclusive_scan_u64(ctx, scratch.as<uint64_t>(), scratch.as<uint64_t>(), C);
-    list.alloc(cnt * 4);
-    if (cnt) launch_items(ctx, "sc_classes", k_sc_class_list, C, sizes, C, lo, hi, scratch.as<uint64_t>(), list.as<uint32_t>());
-    return cnt;
-}
-
-static void sc_run_host(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_hamclusters *hc, const bbk_kmerstats *ks,
-                        const ScIn &in, const DevBuf &list, uint64_t nlist, const double *tab, ScSlab slab) {
-    ScHost h;
-    const uint64_t n = in.n, C = in.clusters;
-    h.n = n;
-    h.k = in.k;
-    h.qw = in.qw;
-    h.p = in.p;
-    memcpy(h.tab, tab, sizeof(h.tab));
-    h.keys.resize(n);
-    h.count.resize(n);
-    h.tq.resize(n);
-    h.qual.resize(n * in.qw);
-    h.members.resize(n);
-    h.sizes.resize(C);
-    h.off.resize(C);
-    std::vector<uint32_t> cl(nlist);
-    d2h_big(ctx, h.keys.data(), set->keys.p, n * 8);
-    d2h_big(ctx, h.count.data(), ks->count.p, n * 4);
-    d2h_big(ctx, h.tq.data(), ks->total_qual.p, n * 4);
-    d2h_big(ctx, h.qual.data(), ks->qual.p, n * in.qw * 8);
-    d2h_big(ctx, h.members.data(), hc->members.p, n * 4);
-    d2h_big(ctx, h.sizes.data(), hc->sizes.p, C * 8);
-    d2h_big(ctx, h.off.data(), in.off, C * 8);
-    d2h_big(ctx, cl.data(), list.p, nlist * 4);
-    const auto t0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> hoff(nlist + 1, 0);
-    for (uint64_t j = 0; j < nlist; ++j) hoff[j + 1] = hoff[j] + h.sizes[cl[j]];
-    const uint64_t slots = hoff[nlist];
-    std::vector<uint32_t> hmem(2 * slots), hsize(slots);
-    std::vector<uint64_t> hkey(slots), hcounts(3 * nlist);
-    std::vector<double> hbic(nlist);
-#pragma omp parallel for schedule(dynamic, 16)
-    for (long long j = 0; j < (long long)nlist; ++j) {
-        ScHostOut o;
-        sc_host_cluster(h, cl[j], o);
-        std::copy(o.mem.begin(), o.mem.begin() + o.nmem, hmem.begin() + 2 * hoff[j]);
-        std::copy(o.size.begin(), o.size.begin() + o.nsub, hsize.begin() + hoff[j]);
-        std::copy(o.nkey.begin(), o.nkey.begin() + o.nnew, hkey.begin() + hoff[j]);
-        hcounts[3 * j] = o.nsub;
-        hcounts[3 * j + 1] = o.nmem;
-        hcounts[3 * j + 2] = o.nnew;
-        hbic[j] = o.bic;
-    }
-    ctx->add_stat("stat_sc_host_us",
-                  std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
-    DevBuf d_hoff((nlist + 1) * 8), d_hmem(2 * slots * 4), d_hsize(slots * 4), d_hkey(slots * 8), d_hcounts(3 * nlist * 8),
-        d_hbic(nlist * 8);
-    BBK_HIP(hipMemcpyAsync(d_hoff.p, hoff.data(), (nlist + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_hmem.p, hmem.data(), 2 * slots * 4, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_hsize.p, hsize.data(), slots * 4, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_hkey.p, hkey.data(), slots * 8, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_hcounts.p, hcounts.data(), 3 * nlist * 8, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_hbic.p, hbic.data(), nlist * 8, hipMemcpyHostToDevice, ctx->stream));
-    launch_items_timed(ctx, "sc_host_scatter", k_sc_host_scatter, nlist, in, list.as<uint32_t>(), nlist, d_hoff.as<uint64_t>(),
-                       d_hmem.as<uint32_t>(), d_hsize.as<uint32_t>(), d_hkey.as<uint64_t>(), d_hcounts.as<uint64_t>(),
-                       d_hbic.as<double>(), slab);
-    BBK_HIP(hipStreamSynchronize(ctx->stream));  // the staging vectors are on this frame
-}
-
-template <int NT>
-static void sc_run_device(bbk_ctx *ctx, const char *family, const ScIn &in, PrefixTable P, const DevBuf &list, uint64_t nlist,
-                          const double *d_tab, ScSlab slab) {
-    // log((double)total) of every cluster of the class, from the host's libm
-    DevBuf d_total(nlist * 4), d_log(nlist * 8);
-    launch_items(ctx, "sc_totals", k_sc_totals, nlist, in, list.as<uint32_t>(), nlist, d_total.as<uint32_t>());
-    raw_vector<uint32_t> total(nlist);
-    d2h_big(ctx, total.data(), d_total.p, nlist * 4);
-    raw_vector<double> lg(nlist);
-    for (uint64_t j = 0; j < nlist; ++j) lg[j] = std::log((double)total[j]);
-    BBK_HIP(hipMemcpyAsync(d_log.p, lg.data(), nlist * 8, hipMemcpyHostToDevice, ctx->stream));
-    {
-        KernelTimer t(ctx, family);
-        hipLaunchKernelGGL(k_sc_cluster<NT>, grid_blocks(nlist), dim3(NT), 0, ctx->stream, in, P, list.as<uint32_t>(), nlist,
-                           d_log.as<double>(), d_tab, slab);
-        check_launch(family);
-    }
-    BBK_HIP(hipStreamSynchronize(ctx->stream));  // lg is on this frame
-}
-
-static bbk_subclusters *subcluster(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_hamclusters *hc, const bbk_kmerstats *ks,
-                                   const ScParams &p) {
-    BBK_HIP(hipSetDevice(ctx->device));
-    auto sc = std::make_unique<bbk_subclusters>();
-    const uint64_t n = set->n, C = hc->clusters;
-    sc->k = set->k;
-    sc->n = n;
-    sc->clusters = C;
-    if (n == 0) {
-        for (DevBuf *b : {&sc->good, &sc->members, &sc->sizes, &sc->per_cluster, &sc->new_keys, &sc->bic}) b->alloc(16);
-        return sc.release();
-    }
-    const char *env = getenv("BBK_SUBCLUSTER_HOST");
-    const bool all_host = env && atoi(env) != 0;
-    double tab[128];
-    sc_tables(tab);
-    DevBuf d_tab(sizeof(tab)), off((C + 1) * 8), soff((C + 1) * 8), scratch((C + 1) * 8);
-    BBK_HIP(hipMemcpyAsync(d_tab.p, tab, sizeof(tab), hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t *sizes = hc->sizes.as<uint64_t>();
-    exclusive_scan_u64(ctx, sizes, off.as<uint64_t>(), C);
-    launch_items(ctx, "sc_classes", k_sc_slab_sizes, C, sizes, C, soff.as<uint64_t>());
-    const uint64_t slots = exclusive_scan_u64(ctx, soff.as<uint64_t>(), soff.as<uint64_t>(), C);
-
+// ---- the driver: layout, solve, finish over one state ------------------------------------------------------------------
+struct ScRun {
+    bbk_ctx *ctx;
+    bbk_subclusters *sc;
+    PrefixTable P;  // over the keys of the set: is a center one of them?
     ScIn in;
-    in.keys = set->keys.as<uint64_t>();
-    in.count = ks->count.as<uint32_t>();
-    in.tq = ks->total_qual.as<float>();
-    in.qual = ks->qual.as<uint64_t>();
-    in.members = hc->members.as<uint32_t>();
-    in.sizes = sizes;
-    in.off = off.as<uint64_t>();
-    in.soff = soff.as<uint64_t>();
-    in.n = n;
-    in.clusters = C;
-    in.k = (int)set->k;
-    in.qw = (int)ks->qual_words;
-    in.p = p;
+    ScSlab slab;
+    double tab[128];  // LP[q], LR3[q] interleaved (kmer_stat.hpp:211-213)
+    DevBuf d_tab, off, soff, scratch, s_mem, s_size, s_nkey, nsub, nmem, nnew, cval, d_stats;  // d_stats: 16 counters, 16 error counts
 
-    DevBuf s_mem(2 * slots * 4), s_size(slots * 4), s_nkey(slots * 8), nsub((C + 1) * 8), nmem((C + 1) * 8), nnew((C + 1) * 8),
-        cval(C), d_stats(32 * 8);
-    sc->bic.alloc(C * 8);
-    ScSlab slab{s_mem.as<uint32_t>(), s_size.as<uint32_t>(), s_nkey.as<uint64_t>(), nsub.as<uint64_t>(), nmem.as<uint64_t>(),
-                nnew.as<uint64_t>(), sc->bic.as<double>()};
-    BBK_HIP(hipMemsetAsync(d_stats.p, 0, 32 * 8, ctx->stream));
-    unsigned long long *stats = d_stats.as<unsigned long long>(), *errs = stats + 16;
-
-    launch_items_timed(ctx, "sc_single", k_sc_single, C, in, slab, cval.as<uint8_t>(), stats);
-    DevBuf list;
-    uint64_t non_singletons = 0;
-    if (all_host) {
-        const uint64_t cnt = sc_class(ctx, sizes, C, 2, ~0ull, scratch, list);
-        non_singletons = cnt;
-        sc->host_kmers = slots;
-        if (cnt) sc_run_host(ctx, set, hc, ks, in, list, cnt, tab, slab);
-    } else {
-        uint64_t cnt = sc_class(ctx, sizes, C, 2, kScWave, scratch, list);
-        non_singletons += cnt;
-        ctx->add_stat("stat_sc_wave_clusters", (double)cnt);
-        if (cnt) sc_run_device<kScWave>(ctx, "sc_wave", in, ks->prefix.table(), list, cnt, d_tab.as<double>(), slab);
-        cnt = sc_class(ctx, sizes, C, kScWave + 1, kScGroup, scratch, list);
-        non_singletons += cnt;
-        ctx->add_stat("stat_sc_group_clusters", (double)cnt);
-        if (cnt) sc_run_device<kScGroup>(ctx, "sc_group", in, ks->prefix.table(), list, cnt, d_tab.as<double>(), slab);
-        cnt = sc_class(ctx, sizes, C, kScGroup + 1, ~0ull, scratch, list);
-        non_singletons += cnt;
-        if (cnt) {
-            // the k-mers of the class: its slab slots
-            std::vector<uint32_t> cl(cnt);
-            std::vector<uint64_t> hs(C);
-            d2h_big(ctx, cl.data(), list.p, cnt * 4);
-            d2h_big(ctx, hs.data(), hc->sizes.p, C * 8);
-            for (uint32_t c : cl) sc->host_kmers += hs[c];
-            sc_run_host(ctx, set, hc, ks, in, list, cnt, tab, slab);
+    // offsets of the clusters in the member list and in the slabs, the kernels' view of the inputs, the slab buffers
+    void layout(const bbk_kmerset *set, const bbk_hamclusters *hc, const bbk_kmerstats *ks, const ScParams &p) {
+        const uint64_t C = hc->clusters, *sizes = hc->sizes.as<uint64_t>();
+        P = ks->prefix.table();
+        for (unsigned q = 0; q < 64; ++q) {
+            const double r = hammer_error_prob(q);
+            tab[2 * q] = log(1 - r);
+            tab[2 * q + 1] = log(r) - log(3);
         }
+        upload(ctx, d_tab, tab, 128);  // this outlives the waits below
+        for (DevBuf *b : {&off, &soff, &scratch}) b->alloc((C + 1) * 8);
+        exclusive_scan_u64(ctx, sizes, off.as<uint64_t>(), C);
+        launch_items(ctx, "sc_classes", k_sc_slab_sizes, C, sizes, C, soff.as<uint64_t>());
+        const uint64_t slots = exclusive_scan_u64(ctx, soff.as<uint64_t>(), soff.as<uint64_t>(), C);
+        in = ScIn{set->keys.as<uint64_t>(), ks->count.as<uint32_t>(), ks->total_qual.as<float>(), ks->qual.as<uint64_t>(),
+                  hc->members.as<uint32_t>(), sizes, off.as<uint64_t>(), soff.as<uint64_t>(), set->n, C, (int)set->k,
+                  (int)ks->qual_words, p};
+        s_mem.alloc(2 * slots * 4);
+        s_size.alloc(slots * 4);
+        s_nkey.alloc(slots * 8);
+        for (DevBuf *b : {&nsub, &nmem, &nnew}) b->alloc((C + 1) * 8);
+        cval.alloc(C);
+        d_stats.alloc(32 * 8);
+        sc->bic.alloc(C * 8);
+        slab = ScSlab{s_mem.as<uint32_t>(), s_size.as<uint32_t>(), s_nkey.as<uint64_t>(), nsub.as<uint64_t>(), nmem.as<uint64_t>(),
+                      nnew.as<uint64_t>(), sc->bic.as<double>()};
+        BBK_HIP(hipMemsetAsync(d_stats.p, 0, 32 * 8, ctx->stream));
     }
-    list.release();
 
-    // the lists in cluster order
-    uint64_t *sub_off = nsub.as<uint64_t>(), *mem_off = nmem.as<uint64_t>(), *new_off = nnew.as<uint64_t>();
-    sc->per_cluster.alloc(C * 8);
-    BBK_HIP(copy_async(sc->per_cluster.p, nsub.p, C * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    sc->subs = exclusive_scan_u64(ctx, sub_off, sub_off, C);
-    sc->listed = exclusive_scan_u64(ctx, mem_off, mem_off, C);
-    sc->new_kmers = exclusive_scan_u64(ctx, new_off, new_off, C);
-    const uint64_t S = sc->subs, total = n + sc->new_kmers;
-    sc->members.alloc(sc->listed * 8);
-    sc->sizes.alloc(S * 8);
-    sc->new_keys.alloc(sc->new_kmers * 8);
-    sc->good.alloc(total);
-    DevBuf first(S * 8), cluster(S * 4), sval(S), last(total * 8);
-    BBK_HIP(hipMemsetAsync(sc->good.p, 0, total, ctx->stream));
-    BBK_HIP(hipMemsetAsync(last.p, 0, total * 8, ctx->stream));
-    {
-        KernelTimer t(ctx, "sc_finish");
-        launch_items(ctx, "sc_gather", k_sc_gather, C, in, slab, sc->per_cluster.as<uint64_t>(), sub_off, mem_off, new_off, sc->members.as<uint64_t>(),
-                     sc->sizes.as<uint64_t>(), first.as<uint64_t>(), cluster.as<uint32_t>(), sc->new_keys.as<uint64_t>());
-        launch_items(ctx, "sc_mark", k_sc_mark, S, in, S, sc->members.as<uint64_t>(), sc->sizes.as<uint64_t>(),
-                     first.as<uint64_t>(), cluster.as<uint32_t>(), sc->new_keys.as<uint64_t>(), cval.as<uint8_t>(),
-                     sval.as<uint8_t>(), last.as<unsigned long long>(), stats, errs);
-        launch_items(ctx, "sc_good", k_sc_good, S, S, sc->members.as<uint64_t>(), first.as<uint64_t>(), sval.as<uint8_t>(),
-                     last.as<unsigned long long>(), sc->good.as<uint8_t>());
+    // The clusters of `list` on the host; returns the k-mers they hold.
+    uint64_t run_host(const DevBuf &list, uint64_t nlist) {
+        ScHost h{in.k, in.qw, in.p, tab};
+        std::vector<uint32_t> cl;
+        auto fetch = [&](auto &v, const void *src, uint64_t cnt) { v.resize(cnt), d2h_big(ctx, v.data(), src, cnt * sizeof(v[0])); };
+        fetch(h.keys, in.keys, in.n);
+        fetch(h.count, in.count, in.n);
+        fetch(h.tq, in.tq, in.n);
+        fetch(h.qual, in.qual, in.n * in.qw);
+        fetch(h.members, in.members, in.n);
+        fetch(h.sizes, in.sizes, in.clusters);
+        fetch(h.off, in.off, in.clusters);
+        fetch(cl, list.p, nlist);
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<uint64_t> hoff(nlist + 1, 0);
+        for (uint64_t j = 0; j < nlist; ++j) hoff[j + 1] = hoff[j] + h.sizes[cl[j]];
+        const uint64_t slots = hoff[nlist];
+        std::vector<uint32_t> hmem(2 * slots), hsize(slots);
+        std::vector<uint64_t> hkey(slots), hcounts(3 * nlist);
+        std::vector<double> hbic(nlist);
+#pragma omp parallel for schedule(dynamic, 16)
+        for (long long j = 0; j < (long long)nlist; ++j)
+            sc_host_cluster(h, cl[j], &hmem[2 * hoff[j]], &hsize[hoff[j]], &hkey[hoff[j]], &hcounts[3 * j], &hbic[j]);
+        ctx->add_stat("stat_sc_host_us", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+        DevBuf d_hoff, d_hmem, d_hsize, d_hkey, d_hcounts, d_hbic;
+        upload(ctx, d_hoff, hoff.data(), nlist + 1);
+        upload(ctx, d_hmem, hmem.data(), 2 * slots);
+        upload(ctx, d_hsize, hsize.data(), slots);
+        upload(ctx, d_hkey, hkey.data(), slots);
+        upload(ctx, d_hcounts, hcounts.data(), 3 * nlist);
+        upload(ctx, d_hbic, hbic.data(), nlist);
+        launch_items_timed(ctx, "sc_host_scatter", k_sc_host_scatter, nlist, in, list.as<uint32_t>(), nlist, d_hoff.as<uint64_t>(),
+                           d_hmem.as<uint32_t>(), d_hsize.as<uint32_t>(), d_hkey.as<uint64_t>(), d_hcounts.as<uint64_t>(),
+                           d_hbic.as<double>(), slab);
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // the staging vectors are on this frame
+        return slots;
     }
-    uint64_t h_stats[32];
-    BBK_HIP(hipMemcpyAsync(h_stats, d_stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
-    memcpy(sc->stats, h_stats, sizeof(sc->stats));
-    memcpy(sc->errs, h_stats + 16, sizeof(sc->errs));
-    sc->stats[SC_TNCLS] = non_singletons;
-    sc->stats[SC_NEWKMERS] = sc->new_kmers;
-    return sc.release();
-}
 
-static void sc_write_u64(const std::string &path, const uint64_t *p, uint64_t count) {
-    FILE *f = fopen(path.c_str(), "wb");
-    BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path.c_str());
-    const bool ok = count == 0 || fwrite(p, 8, count, f) == count;
-    const bool closed = fclose(f) == 0;
-    BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path.c_str());
-}
+    // The clusters of `list` by k_sc_cluster<NT>; none of their k-mers is the host's.
+    template <int NT>
+    uint64_t run_device(const DevBuf &list, uint64_t nlist) {
+        const char *family = NT == kScWave ? "sc_wave" : "sc_group";
+        // log((double)total) of every cluster of the class, from the host's libm
+        DevBuf d_total(nlist * 4), d_log(nlist * 8);
+        launch_items(ctx, "sc_totals", k_sc_totals, nlist, in, list.as<uint32_t>(), nlist, d_total.as<uint32_t>());
+        raw_vector<uint32_t> total(nlist);
+        d2h_big(ctx, total.data(), d_total.p, nlist * 4);
+        raw_vector<double> lg(nlist);
+        for (uint64_t j = 0; j < nlist; ++j) lg[j] = std::log((double)total[j]);
+        BBK_HIP(hipMemcpyAsync(d_log.p, lg.data(), nlist * 8, hipMemcpyHostToDevice, ctx->stream));
+        {
+            KernelTimer t(ctx, family);
+            hipLaunchKernelGGL(k_sc_cluster<NT>, grid_blocks(nlist), dim3(NT), 0, ctx->stream, in, P, list.as<uint32_t>(), nlist,
+                               d_log.as<double>(), d_tab.as<double>(), slab);
+            check_launch(family);
+        }
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // lg is on this frame
+        return 0;
+    }
+
+    // the singletons, then class after class: who solves the clusters of lo .. hi members, and the stat (may be null) that
+    // receives how many there are.  Returns the number of non-singleton clusters.
+    uint64_t solve() {
+        struct Class {
+            uint64_t lo, hi;
+            uint64_t (ScRun::*run)(const DevBuf &list, uint64_t nlist);
+            const char *stat;
+        };
+        const char *env = getenv("BBK_SUBCLUSTER_HOST");
+        const bool host = env && atoi(env) != 0;  // then the last row takes every class
+        const Class by_size[] = {{2, kScWave, &ScRun::run_device<kScWave>, "stat_sc_wave_clusters"},
+                                 {kScWave + 1, kScGroup, &ScRun::run_device<kScGroup>, "stat_sc_group_clusters"},
+                                 {host ? 2ull : kScGroup + 1ull, ~0ull, &ScRun::run_host, nullptr}};
+        const uint64_t C = in.clusters;
+        launch_items_timed(ctx, "sc_single", k_sc_single, C, in, slab, cval.as<uint8_t>(), d_stats.as<unsigned long long>());
+        uint64_t *flag = scratch.as<uint64_t>(), non_singletons = 0;
+        DevBuf list;
+        for (const Class *c = by_size + (host ? 2 : 0); c < by_size + 3; ++c) {
+            launch_items(ctx, "sc_classes", k_sc_class_flag, C, in.sizes, C, c->lo, c->hi, flag);
+            const uint64_t cnt = exclusive_scan_u64(ctx, flag, flag, C);
+            list.alloc(cnt * 4);
+            if (cnt) launch_items(ctx, "sc_classes", k_sc_class_list, C, in.sizes, C, c->lo, c->hi, flag, list.as<uint32_t>());
+            non_singletons += cnt;
+            if (c->stat) ctx->add_stat(c->stat, (double)cnt);
+            if (cnt) sc->host_kmers += (this->*c->run)(list, cnt);
+        }
+        return non_singletons;
+    }
+
+    // the lists in cluster order, the decision per subcluster, the good bits, the counters
+    void finish(uint64_t non_singletons) {
+        const uint64_t C = in.clusters;
+        unsigned long long *stats = d_stats.as<unsigned long long>(), *errs = stats + 16;
+        uint64_t *sub_off = nsub.as<uint64_t>(), *mem_off = nmem.as<uint64_t>(), *new_off = nnew.as<uint64_t>();
+        sc->per_cluster.alloc(C * 8);
+        BBK_HIP(copy_async(sc->per_cluster.p, nsub.p, C * 8, hipMemcpyDeviceToDevice, ctx->stream));
+        sc->subs = exclusive_scan_u64(ctx, sub_off, sub_off, C);
+        sc->listed = exclusive_scan_u64(ctx, mem_off, mem_off, C);
+        sc->new_kmers = exclusive_scan_u64(ctx, new_off, new_off, C);
+        const uint64_t S = sc->subs, total = in.n + sc->new_kmers;
+        sc->members.alloc(sc->listed * 8);
+        sc->sizes.alloc(S * 8);
+        sc->new_keys.alloc(sc->new_kmers * 8);
+        sc->good.alloc(total);
+        DevBuf first(S * 8), cluster(S * 4), sval(S), last(total * 8);
+        BBK_HIP(hipMemsetAsync(sc->good.p, 0, total, ctx->stream));
+        BBK_HIP(hipMemsetAsync(last.p, 0, total * 8, ctx->stream));
+        {
+            KernelTimer t(ctx, "sc_finish");
+            launch_items(ctx, "sc_gather", k_sc_gather, C, in, slab, sc->per_cluster.as<uint64_t>(), sub_off, mem_off, new_off,
+                         sc->members.as<uint64_t>(), sc->sizes.as<uint64_t>(), first.as<uint64_t>(), cluster.as<uint32_t>(),
+                         sc->new_keys.as<uint64_t>());
+            launch_items(ctx, "sc_mark", k_sc_mark, S, in, S, sc->members.as<uint64_t>(), sc->sizes.as<uint64_t>(),
+                         first.as<uint64_t>(), cluster.as<uint32_t>(), sc->new_keys.as<uint64_t>(), cval.as<uint8_t>(),
+                         sval.as<uint8_t>(), last.as<unsigned long long>(), stats, errs);
+            launch_items(ctx, "sc_good", k_sc_good, S, S, sc->members.as<uint64_t>(), first.as<uint64_t>(), sval.as<uint8_t>(),
+                         last.as<unsigned long long>(), sc->good.as<uint8_t>());
+        }
+        uint64_t h_stats[32];
+        BBK_HIP(hipMemcpyAsync(h_stats, d_stats.p, sizeof(h_stats), hipMemcpyDeviceToHost, ctx->stream));
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        memcpy(sc->stats, h_stats, sizeof(sc->stats));
+        memcpy(sc->errs, h_stats + 16, sizeof(sc->errs));
+        sc->stats[SC_TNCLS] = non_singletons;
+        sc->stats[SC_NEWKMERS] = sc->new_kmers;
+    }
+};
 
 }  // namespace bbk
 
@@ -974,7 +898,18 @@ int bbk_hamclusters_subcluster(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_h
         for (double t : {d.singleton_threshold, d.nonsingleton_threshold, d.correct_threshold})
             BBK_REQUIRE(t >= 0.0 && t <= 1.0, BBK_ERR_ARG, "bbk_hamclusters_subcluster: threshold %g is outside [0, 1]", t);
         const ScParams sp{d.singleton_threshold, d.nonsingleton_threshold, d.correct_threshold, d.correct_use_threshold ? 1 : 0};
-        *out = subcluster(ctx, set, hamclusters, kmerstats, sp);
+        BBK_HIP(hipSetDevice(ctx->device));
+        auto sc = std::make_unique<bbk_subclusters>();
+        sc->k = set->k;
+        sc->n = set->n;
+        sc->clusters = hamclusters->clusters;
+        for (DevBuf *b : {&sc->good, &sc->members, &sc->sizes, &sc->per_cluster, &sc->new_keys, &sc->bic}) b->alloc(16);
+        if (sc->n) {
+            ScRun r{ctx, sc.get()};
+            r.layout(set, hamclusters, kmerstats, sp);
+            r.finish(r.solve());
+        }
+        *out = sc.release();
     });
 }
 
@@ -1006,44 +941,16 @@ int bbk_subclusters_write(bbk_ctx *ctx, const bbk_subclusters *s, const bbk_kmer
         BBK_REQUIRE(ctx && s && ks && prefix, BBK_ERR_ARG, "bbk_subclusters_write: NULL argument");
         BBK_REQUIRE(ks->finished && ks->n == s->n && ks->k == s->k, BBK_ERR_ARG,
                     "bbk_subclusters_write: these are not the statistics the subclusters were made from");
-        BBK_REQUIRE(!ks->count_overflow, BBK_ERR_ARG,
-                    "bbk_subclusters_write: a k-mer has 2^31 occurrences or more: the record holds count << 1 in 32 bits");
-        BBK_HIP(hipSetDevice(ctx->device));
         const std::string pre(prefix);
-        const uint64_t n = s->n, total = n + s->new_kmers;
-        const unsigned qw = ks->qual_words;
-        const size_t rsz = 8 + 8 * (size_t)qw;
-        raw_vector<uint8_t> good(total);
-        raw_vector<uint32_t> cnt(n);
-        raw_vector<float> tq(n);
-        raw_vector<uint64_t> qv(n * qw), members(s->listed), sizes(s->subs), nk(s->new_kmers);
-        if (n) {
-            d2h_big(ctx, good.data(), s->good.p, total);
-            d2h_big(ctx, cnt.data(), ks->count.p, n * 4);
-            d2h_big(ctx, tq.data(), ks->total_qual.p, n * 4);
-            d2h_big(ctx, qv.data(), ks->qual.p, n * qw * 8);
-            d2h_big(ctx, members.data(), s->members.p, s->listed * 8);
-            d2h_big(ctx, sizes.data(), s->sizes.p, s->subs * 8);
-            if (s->new_kmers) d2h_big(ctx, nk.data(), s->new_keys.p, s->new_kmers * 8);
-        }
-        // binary_write(KMerStat), kmer_stat.hpp:170-175, the good bit in bit 0; a new k-mer is KMerStat(0, 1.0, NULL)
-        std::vector<char> buf(total * rsz, 0);
-        for (uint64_t i = 0; i < total; ++i) {
-            char *o = buf.data() + i * rsz;
-            const uint32_t c2 = (i < n ? cnt[i] << 1 : 0u) | good[i];
-            const float t = i < n ? tq[i] : 1.0f;
-            memcpy(o, &c2, 4);
-            memcpy(o + 4, &t, 4);
-            if (i < n) memcpy(o + 8, &qv[i * qw], 8 * (size_t)qw);
-        }
-        FILE *f = fopen((pre + ".kmstat").c_str(), "wb");
-        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s.kmstat for writing", prefix);
-        const bool ok = total == 0 || fwrite(buf.data(), rsz, total, f) == total;
-        const bool closed = fclose(f) == 0;
-        BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s.kmstat failed", prefix);
-        sc_write_u64(pre + ".subclusters", members.data(), s->listed);
-        sc_write_u64(pre + ".subclusters.idx", sizes.data(), s->subs);
-        sc_write_u64(pre + ".newkmers", nk.data(), s->new_kmers);
+        write_kmstat(ctx, "bbk_subclusters_write", pre + ".kmstat", ks, s->good.as<uint8_t>(), s->new_kmers);
+        auto put = [&](const char *ext, const DevBuf &d, uint64_t count) {
+            raw_vector<uint64_t> v(count);
+            if (count) d2h_big(ctx, v.data(), d.p, count * 8);
+            write_u64_file(pre + ext, v.data(), count);
+        };
+        put(".subclusters", s->members, s->listed);
+        put(".subclusters.idx", s->sizes, s->subs);
+        put(".newkmers", s->new_keys, s->new_kmers);
     });
 }
 

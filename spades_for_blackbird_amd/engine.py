@@ -544,6 +544,9 @@ class _Handle:
             getattr(self._L, self._free)(self._h)
             self._h = None
 
+    def close(self):
+        self.free()
+
     def __del__(self):
         try:
             self.free()
@@ -700,9 +703,6 @@ class KmerStats(_Handle):
         """one binary_write(KMerStat) record per k-mer: u32 count << 1, float total_qual, the QualBitSet words"""
         _check(self._L.bbk_kmerstats_write(self.ctx._h, self._h, str(path).encode()))
 
-    def close(self):
-        self.free()
-
 
 class HamClusters(_Handle):
     """clusters of k-mers at Hamming distance 1 (the reference's kmers.hamming); an index is a position in the
@@ -755,9 +755,6 @@ class HamClusters(_Handle):
         sc._n, sc._clusters, sc._stats_of = self.size, len(self), kmer_stats
         return sc
 
-    def close(self):
-        self.free()
-
 
 class SubclusterParams(C.Structure):
     """bbk_subcluster_params of include/bbk.h"""
@@ -809,9 +806,6 @@ class SubClusters(_Handle):
     def write(self, prefix):
         """<prefix>.kmstat (good bits set, new k-mers appended), .subclusters, .subclusters.idx, .newkmers"""
         _check(self._L.bbk_subclusters_write(self.ctx._h, self._h, self._stats_of._h, str(prefix).encode()))
-
-    def close(self):
-        self.free()
 
 
 class Counter:

@@ -295,6 +295,54 @@ def test_refusals(ctx, tmp_path):
     assert b"1.5" in L.bbk_last_error()
 
 
+def test_kmstat_writer_across_a_block_boundary(ctx, tmp_path):
+    """KmerStats.write and SubClusters.write share one writer that goes 2^20 records at a time: 2^20 + 3 k-mers, all of
+    them singleton clusters, so the good bit of a record is the decision on its own total_qual"""
+    import torch
+    k, block = 21, 1 << 20
+    n = block + 3
+    keys = np.arange(n, dtype=np.uint64) * np.uint64(3) + np.uint64(1)  # distinct, ascending, below 4^21
+    rec = np.zeros(n, dtype=np.dtype([("c", "<u4"), ("tq", "<f4"), ("w", "<u8", (2,))]))
+    count = (np.arange(1, n + 1, dtype=np.uint64) % 1000 + 1).astype(np.uint32)
+    rec["c"] = count << 1
+    rec["tq"] = np.where(np.arange(n) % 2 == 0, np.float32(0.015), np.float32(0.025))  # 1 - tq either side of 0.98
+    rec["w"][:, 0] = keys * np.uint64(0x9E3779B97F4A7C15)
+    rec["w"][:, 1] = (keys * np.uint64(0xBF58476D1CE4E5B9)) >> np.uint64(2)  # 6 * 21 = 126 bits: the top two stay clear
+    prefix = str(tmp_path / "big")
+    rec.tofile(prefix + ".kmstat")
+    np.arange(n, dtype=np.uint64).tofile(prefix + ".hamming")
+    np.ones(n, dtype=np.uint64).tofile(prefix + ".hamming.idx")
+    d = torch.from_numpy(keys.view(np.int64).copy()).cuda()
+    torch.cuda.synchronize()
+    s = ctx.kmerset_from_device(d, n, k)
+    ks, hc = ctx.kmerstats_load(s, prefix + ".kmstat"), ctx.hamclusters_load(n, prefix + ".hamming")
+    sc = hc.subcluster(ks)
+    assert len(sc) == n and sc.new_kmers == 0 and sc.host_kmers == 0
+    ks.write(prefix + ".again.kmstat")
+    sc.write(prefix + ".sc")
+    for h in (sc, hc, ks, s):
+        h.free()
+    edge = range(block - 2, block + 3)  # the records either side of the boundary by name, then everything
+    again = np.fromfile(prefix + ".again.kmstat", dtype=rec.dtype)
+    assert len(again) == n
+    for i in edge:
+        assert again[i].tobytes() == rec[i].tobytes(), i
+    assert open(prefix + ".again.kmstat", "rb").read() == rec.tobytes()
+    good = (np.float32(1) - rec["tq"]).astype(np.float64) > 0.98  # sc_good_quality: a float subtraction, then widened
+    assert good[0] and not good[1]
+    exp = rec.copy()
+    exp["c"] |= good.astype(np.uint32)
+    got = np.fromfile(prefix + ".sc.kmstat", dtype=rec.dtype)
+    assert len(got) == n
+    for i in edge:
+        assert got[i].tobytes() == exp[i].tobytes(), i
+    assert open(prefix + ".sc.kmstat", "rb").read() == exp.tobytes()
+    m = 1000
+    restated = R.process(keys[:m], k, count[:m], rec["tq"][:m], rec["w"][:m], np.arange(m), np.ones(m, dtype=np.uint64))
+    assert (got["c"][:m] & 1).astype(np.uint8).tolist() == restated["good"].tolist()
+    assert open(prefix + ".sc.subclusters", "rb").read() == np.arange(n, dtype=np.uint64).tobytes()
+
+
 # md5 of the files `spades-kmerdata -k 21 -o out --cluster -b 60000 tests/golden/ecoli_1K_1.fq.gz` writes, from the binary
 # and library of the commit before --subcluster existed
 PARENT_MD5 = {
