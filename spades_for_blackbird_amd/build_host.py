@@ -21,6 +21,7 @@ def build(force=False, verbose=False):
     os.makedirs(BIN, exist_ok=True)
     out = []
     deps = [os.path.join(HOST, h) for h in HEADERS] + [os.path.join(HERE, "..", "include", "bbk.h"),
+                                                      os.path.join(HERE, "csrc", "gfa_graph.h"),  # gmapper_main.cpp
                                                       os.path.join(HERE, "libbbk.so")]
     for name, src in PROGRAMS.items():
         exe = os.path.join(BIN, name)

@@ -246,6 +246,12 @@ inline void stream_wait(bbk_ctx *ctx) {
     BBK_HIP(hipStreamSynchronize(ctx->stream));
 }
 
+// a device -> host copy on the context's stream that the host waits for (outside the counting path: not a counted wait)
+inline void d2h_sync(bbk_ctx *ctx, void *dst, const void *src, size_t bytes) {
+    BBK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+}
+
 // a numeric BBK_* knob: `unset` when the variable is not set (an empty value reads as 0)
 inline uint64_t env_u64(const char *v, uint64_t unset) { return v ? strtoull(v, nullptr, 10) : unset; }
 

@@ -45,10 +45,10 @@
 #include <cstring>
 #include <memory>
 #include <string>
-#include <unordered_map>
 #include <vector>
 
 #include "bbk_internal.h"
+#include "gfa_graph.h"
 #include "kmer_ops.h"
 #include "unitigs.h"
 
@@ -59,11 +59,8 @@ struct EdgePos {
     uint32_t seg;     // segment (S-line order)
     uint32_t off_fw;  // offset of the (k+1)-mer on the forward strand of the segment
     uint32_t off_rc;  // offset of its reverse complement on the reverse strand (len - 1 - off_fw)
-    uint32_t flags;   // kEpCanonFw | kEpSelfConj | kEpLoop1
+    uint32_t flags;   // kEpCanonFw | kEpSelfConj | kEpLoop1 (gfa_graph.h)
 };
-constexpr uint32_t kEpCanonFw = 1u;   // the canonical key is the forward window of the segment
-constexpr uint32_t kEpSelfConj = 2u;  // segment == its reverse complement
-constexpr uint32_t kEpLoop1 = 4u;     // segment is one homopolymer (k+1)-mer linked to itself
 
 }  // namespace bbk
 
@@ -108,23 +105,18 @@ __global__ __launch_bounds__(256) void k_ep_emit(const uint64_t *__restrict__ wo
                                                 EdgePos *__restrict__ pos) {
     const uint64_t j = BBK_GID();
     if (j >= n) return;
-    uint64_t lo = 0, hi = n_seg - 1;  // last segment with emit_off[s] <= j (segments emit at least one record)
-    while (lo < hi) {
-        const uint64_t mid = (lo + hi + 1) >> 1;
-        if (emit_off[mid] <= j) lo = mid;
-        else hi = mid - 1;
-    }
-    const uint32_t p = (uint32_t)(j - emit_off[lo]);
-    const Key<W> x = kmer_extract<W>(words + woff[lo], p, k1);
+    const uint64_t s = last_le(emit_off, n_seg, j);  // the segment that emits record j (segments emit at least one)
+    const uint32_t p = (uint32_t)(j - emit_off[s]);
+    const Key<W> x = kmer_extract<W>(words + woff[s], p, k1);
     const Key<W> r = kmer_rc<W>(x, k1);
     const bool fw = !kmer_less_nucl<W>(r, x);
     key_store<W>(&keys[j], key_select<W>(fw, x, r));
     idx[j] = (uint32_t)j;
     EdgePos e;
-    e.seg = (uint32_t)lo;
+    e.seg = (uint32_t)s;
     e.off_fw = p;
-    e.off_rc = seg_len[lo] - 1u - p;
-    e.flags = seg_flags[lo] | (fw ? kEpCanonFw : 0u);
+    e.off_rc = seg_len[s] - 1u - p;
+    e.flags = seg_flags[s] | (fw ? kEpCanonFw : 0u);
     pos[j] = e;
 }
 
@@ -173,24 +165,11 @@ __global__ __launch_bounds__(256) void k_ep_map(const uint64_t *__restrict__ wor
     uint64_t oe = ~0ull;  // oriented edge: 2 * seg + (minus strand of a segment that is not self-conjugate)
     uint32_t p = 0;       // position inside the read
     if (valid) {
-        uint64_t lo = 0, hi = n_reads - 1;  // last read with pos_off[r] <= g: the read that holds position g
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (pos_off[mid] <= (uint64_t)g) lo = mid;
-            else hi = mid - 1;
-        }
+        const uint64_t lo = last_le(pos_off, n_reads, (uint64_t)g);  // the read that holds position g
         p = (uint32_t)((uint64_t)g - pos_off[lo]);
         const uint64_t *rw = words + woff[lo];
-        Key<W> q;
         bool minimal;
-        if constexpr (W == 1) {
-            q = kmer_extract_canon1(rw, p, k1, (rlen[lo] - 1u) >> 5, &minimal);
-        } else {
-            const Key<W> x = kmer_extract<W>(rw, p, k1);
-            const Key<W> r = kmer_rc<W>(x, k1);
-            minimal = !kmer_less_nucl<W>(r, x);
-            q = key_select<W>(minimal, x, r);
-        }
+        const Key<W> q = kmer_canon<W>(rw, p, k1, (rlen[lo] - 1u) >> 5, &minimal);
         const uint64_t j = table_find<W>(keys, P, q);
         if (j != kNotFound) {
             const EdgePos e = epos[j];
@@ -251,26 +230,13 @@ __global__ __launch_bounds__(256) void k_gm_paths(const uint64_t *__restrict__ w
     uint64_t oe = ~0ull;
     uint32_t p = 0, last = 0, rd = 0;  // position inside the read, the read's last position, the read
     if (valid) {
-        uint64_t lo = 0, hi = n_reads - 1;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi + 1) >> 1;
-            if (pos_off[mid] <= (uint64_t)g) lo = mid;
-            else hi = mid - 1;
-        }
+        const uint64_t lo = last_le(pos_off, n_reads, (uint64_t)g);
         rd = (uint32_t)lo;
         p = (uint32_t)((uint64_t)g - pos_off[lo]);
         last = (uint32_t)(pos_off[lo + 1] - pos_off[lo] - 1);
         const uint64_t *rw = words + woff[lo];
-        Key<W> q;
         bool minimal;
-        if constexpr (W == 1) {
-            q = kmer_extract_canon1(rw, p, k1, (rlen[lo] - 1u) >> 5, &minimal);
-        } else {
-            const Key<W> x = kmer_extract<W>(rw, p, k1);
-            const Key<W> r = kmer_rc<W>(x, k1);
-            minimal = !kmer_less_nucl<W>(r, x);
-            q = key_select<W>(minimal, x, r);
-        }
+        const Key<W> q = kmer_canon<W>(rw, p, k1, (rlen[lo] - 1u) >> 5, &minimal);
         const uint64_t j = table_find<W>(keys, P, q);
         if (j != kNotFound) {
             const EdgePos e = epos[j];
@@ -318,324 +284,120 @@ __global__ __launch_bounds__(256) void k_gm_paths(const uint64_t *__restrict__ w
 
 // ---- host side --------------------------------------------------------------------------------------------------------
 
-static inline char comp_base(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; }
+static void require_graph(const GraphError &e) { BBK_REQUIRE(!e, e.io ? BBK_ERR_IO : BBK_ERR_ARG, "%s", e.msg.c_str()); }
 
-// link: segment a in orientation oa (true = '+') followed by segment b in orientation ob
-struct HostLink {
-    uint32_t a, b;
-    bool oa, ob;
-};
-
-// the graph on the host: segment names, their ACGT sequences back to back (off: n + 1 entries), links
-struct HostGraph {
-    std::vector<std::string> names;
-    std::string bases;
-    std::vector<uint64_t> off{0};
-    std::vector<HostLink> links;
-    std::vector<uint32_t> kc;  // KC:i: per segment (empty: none known)
-};
-
-template <int W>
-static void run_emit(bbk_ctx *ctx, const bbk_reads *sr, const DevBuf &emit_off, const DevBuf &slen, const DevBuf &sflags,
-                     uint64_t n_seg, uint64_t n, unsigned k1, DevBuf &keys, DevBuf &idx, DevBuf &pos) {
-    launch_items(ctx, "k_ep_emit", k_ep_emit<W>, n, sr->d_words, sr->d_woff, emit_off.as<uint64_t>(),
-                 slen.as<uint32_t>(), sflags.as<uint32_t>(), n_seg, n, (int)k1, keys.as<Key<W>>(), idx.as<uint32_t>(),
-                 pos.as<EdgePos>());
+// keep: the index also keeps bases, offsets, links and KC (what spades-gmapper rebuilds the graph from); profiles need none
+static void keep_or_drop_graph(bbk_edgeindex *ix, HostGraph &g, bool keep) {
+    if (!keep) return std::string().swap(g.bases);
+    ix->has_graph = true;
+    ix->bases = std::move(g.bases);
+    ix->off = std::move(g.off);
+    ix->kc = g.kc.empty() ? std::vector<uint32_t>(ix->n_seg, 0) : std::move(g.kc);
+    ix->links.reserve(4 * g.links.size());
+    for (const HostLink &l : g.links) ix->links.insert(ix->links.end(), {l.a, l.oa ? 1u : 0u, l.b, l.ob ? 1u : 0u});
 }
 
-template <int W>
-static void run_gather(bbk_ctx *ctx, const DevBuf &keys, const DevBuf &idx, const DevBuf &pos, uint64_t n, DevBuf &out,
-                       DevBuf &dup) {
-    launch_items(ctx, "k_ep_gather", k_ep_gather<W>, n, keys.as<Key<W>>(), idx.as<uint32_t>(), pos.as<EdgePos>(), n,
-                 out.as<EdgePos>(), dup.as<unsigned long long>());
-}
-
-// the index of a graph held on the host, checked as the position-local form needs
-// keep_graph: the index also keeps the bases, offsets, links and KC of the graph (bbk_edgeindex_export_graph)
-static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g, bool keep_graph) {
-    BBK_REQUIRE(k >= 1 && k < BBK_MAX_K && k % 2 == 1, BBK_ERR_ARG, "edge index: k = %u must be odd and < %d", k, BBK_MAX_K);
-    const uint64_t ns = g.names.size();
-    BBK_REQUIRE(ns > 0, BBK_ERR_ARG, "edge index: the graph has no segments");
-    BBK_REQUIRE(ns < (1ull << 32) - 1, BBK_ERR_ARG, "edge index: too many segments (%llu)", (unsigned long long)ns);
-    const unsigned k1 = k + 1;
-    auto ix = std::make_unique<bbk_edgeindex>();
-    ix->k = k;
-    ix->k1 = k1;
-    ix->W = words_of(k1);
-    ix->n_seg = ns;
-    ix->len.resize(ns);
-    std::vector<uint32_t> hflags(ns, 0), hlen(ns);
-    std::vector<uint64_t> hemit(ns + 1, 0);
-    int64_t bad = -1;
-#pragma omp parallel for schedule(static) num_threads(16)
-    for (int64_t s = 0; s < (int64_t)ns; ++s) {
-        const char *q = g.bases.data() + g.off[s];
-        const uint64_t n = g.off[s + 1] - g.off[s];
-        if (n < k1 || n - k >= (1ull << 32) - 1) {
-#pragma omp critical
-            bad = bad < 0 || s < bad ? s : bad;
-            continue;
-        }
-        const uint64_t L = n - k;
-        ix->len[s] = L;
-        hlen[s] = (uint32_t)L;
-        bool selfc = true;  // q == rc(q)
-        for (uint64_t i = 0; i < (n + 1) / 2 && selfc; ++i) selfc = q[i] == comp_base(q[n - 1 - i]);
-        if (selfc) hflags[s] |= kEpSelfConj;
-        hemit[s + 1] = selfc ? (L + 1) / 2 : L;
-    }
-    BBK_REQUIRE(bad < 0, BBK_ERR_ARG, "segment %s is %llu bp: shorter than k + 1 = %u or too long", g.names[bad].c_str(),
-                (unsigned long long)(g.off[bad + 1] - g.off[bad]), k1);
-    for (uint64_t s = 0; s < ns; ++s) hemit[s + 1] += hemit[s];
-    // a link is a true k-overlap: the last k bases of a (as oriented) are the first k bases of b
-    const int64_t nl = (int64_t)g.links.size();
-    int64_t bad_link = -1;
-#pragma omp parallel for schedule(static) num_threads(16)
-    for (int64_t j = 0; j < nl; ++j) {
-        const HostLink &l = g.links[j];
-        const char *A = g.bases.data() + g.off[l.a], *B = g.bases.data() + g.off[l.b];
-        const uint64_t la = g.off[l.a + 1] - g.off[l.a], lb = g.off[l.b + 1] - g.off[l.b];
-        bool ok = true;
-        for (unsigned i = 0; i < k && ok; ++i)
-            ok = (l.oa ? A[la - k + i] : comp_base(A[k - 1 - i])) == (l.ob ? B[i] : comp_base(B[lb - 1 - i]));
-        if (!ok) {
-#pragma omp critical
-            bad_link = bad_link < 0 || j < bad_link ? j : bad_link;
-        }
-    }
-    if (bad_link >= 0) {
-        const HostLink &l = g.links[bad_link];
-        BBK_REQUIRE(false, BBK_ERR_ARG, "link %s%c -> %s%c: the %uM overlap does not match the sequences",
-                    g.names[l.a].c_str(), l.oa ? '+' : '-', g.names[l.b].c_str(), l.ob ? '+' : '-', k);
-    }
-    for (const HostLink &l : g.links) {
-        if (l.a != l.b || l.oa != l.ob || ix->len[l.a] != 1) continue;
-        const char *q = g.bases.data() + g.off[l.a];
-        bool homo = true;
-        for (unsigned i = 1; i < k1; ++i) homo = homo && q[i] == q[0];
-        if (homo) hflags[l.a] |= kEpLoop1;
-    }
-    const uint64_t n = hemit[ns];
-    BBK_REQUIRE(n < (1ull << 32), BBK_ERR_ARG, "edge index: %llu (k+1)-mers, at most 2^32 - 1 supported",
-                (unsigned long long)n);
-    ix->n = n;
-    ix->names = std::move(g.names);
-
-    // the segments as a packed read set (one segment per read)
-    bbk_reads *sr = nullptr;
-    int rc = bbk_reads_from_ascii(ctx, g.bases.data(), g.off.data(), ns, &sr);
-    if (rc != BBK_OK) throw Error{rc};
-    std::unique_ptr<bbk_reads, void (*)(bbk_reads *)> sr_guard(sr, bbk_reads_free);
-    if (keep_graph) {  // what spades-gmapper rebuilds the graph from; the profiles need none of it
-        ix->has_graph = true;
-        ix->bases = std::move(g.bases);
-        ix->off = std::move(g.off);
-        ix->kc = g.kc.empty() ? std::vector<uint32_t>(ns, 0) : std::move(g.kc);
-        ix->links.resize(4 * g.links.size());
-        for (size_t j = 0; j < g.links.size(); ++j) {
-            const HostLink &l = g.links[j];
-            ix->links[4 * j] = l.a;
-            ix->links[4 * j + 1] = l.oa ? 1u : 0u;
-            ix->links[4 * j + 2] = l.b;
-            ix->links[4 * j + 3] = l.ob ? 1u : 0u;
-        }
-    } else {
-        std::string().swap(g.bases);
-    }
-
-    const unsigned W = ix->W;
+// emit, sort, gather over the segments as a packed read set (one segment per read): keys and records of the index in
+// key order.  Returns the smallest index whose key equals its predecessor's (~0: every (k+1)-mer is there once).
+static uint64_t build_device_index(bbk_ctx *ctx, bbk_edgeindex *ix, const bbk_reads *sr, const SegmentTable &t) {
+    const uint64_t ns = ix->n_seg, n = ix->n;
+    const unsigned W = ix->W, k1 = ix->k1;
     DevBuf d_emit((ns + 1) * 8), d_len(ns * 4), d_flags(ns * 4);
-    BBK_HIP(hipMemcpyAsync(d_emit.p, hemit.data(), (ns + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_len.p, hlen.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
-    BBK_HIP(hipMemcpyAsync(d_flags.p, hflags.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    BBK_HIP(hipMemcpyAsync(d_emit.p, t.emit.data(), (ns + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    BBK_HIP(hipMemcpyAsync(d_len.p, t.len32.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    BBK_HIP(hipMemcpyAsync(d_flags.p, t.flags.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
     DevBuf tmp(n * W * 8), idx(n * 4), idx_tmp(n * 4), pos(n * sizeof(EdgePos)), dup(8);
     ix->keys.alloc(n * W * 8);
     ix->pos.alloc(n * sizeof(EdgePos));
     {
-        KernelTimer t(ctx, "edgeindex", (double)n * (W * 8 + sizeof(EdgePos) + 4));
+        KernelTimer timer(ctx, "edgeindex", (double)n * (W * 8 + sizeof(EdgePos) + 4));
         dispatch_w(W, [&](auto w) {
-            run_emit<decltype(w)::value>(ctx, sr, d_emit, d_len, d_flags, ns, n, k1, ix->keys, idx, pos);
+            constexpr int W_ = decltype(w)::value;
+            launch_items(ctx, "k_ep_emit", k_ep_emit<W_>, n, sr->d_words, sr->d_woff, d_emit.as<uint64_t>(),
+                         d_len.as<uint32_t>(), d_flags.as<uint32_t>(), ns, n, (int)k1, ix->keys.as<Key<W_>>(),
+                         idx.as<uint32_t>(), pos.as<EdgePos>());
         });
     }
     sort_records(ctx, (int)W, ix->keys.p, tmp.p, idx.as<uint32_t>(), idx_tmp.as<uint32_t>(), n, key_passes(k1));
     BBK_HIP(hipMemsetAsync(dup.p, 0xFF, 8, ctx->stream));
     {
-        KernelTimer t(ctx, "edgeindex", (double)n * (2 * W * 8 + 2 * sizeof(EdgePos) + 4));
-        dispatch_w(W, [&](auto w) { run_gather<decltype(w)::value>(ctx, ix->keys, idx, pos, n, ix->pos, dup); });
+        KernelTimer timer(ctx, "edgeindex", (double)n * (2 * W * 8 + 2 * sizeof(EdgePos) + 4));
+        dispatch_w(W, [&](auto w) {
+            constexpr int W_ = decltype(w)::value;
+            launch_items(ctx, "k_ep_gather", k_ep_gather<W_>, n, ix->keys.as<Key<W_>>(), idx.as<uint32_t>(),
+                         pos.as<EdgePos>(), n, ix->pos.as<EdgePos>(), dup.as<unsigned long long>());
+        });
     }
     uint64_t first_dup = ~0ull;
-    BBK_HIP(hipMemcpyAsync(&first_dup, dup.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
-    if (first_dup != ~0ull) {
-        EdgePos two[2];
-        BBK_HIP(hipMemcpy(two, ix->pos.as<EdgePos>() + first_dup - 1, sizeof(two), hipMemcpyDeviceToHost));
-        BBK_REQUIRE(false, BBK_ERR_ARG,
-                    "duplicated (k+1)-mer: segment %s offset %u and segment %s offset %u hold the same %u-mer (up to "
-                    "reverse complement); the mapping needs every (k+1)-mer of the graph once",
-                    ix->names[two[0].seg].c_str(), two[0].off_fw, ix->names[two[1].seg].c_str(), two[1].off_fw, k1);
-    }
-    ix->prefix.build(ctx, ix->keys.as<uint64_t>(), W, k1, n);
+    d2h_sync(ctx, &first_dup, dup.p, 8);
+    return first_dup;
+}
+
+static void report_duplicate(const bbk_edgeindex *ix, uint64_t first_dup) {
+    EdgePos two[2];
+    BBK_HIP(hipMemcpy(two, ix->pos.as<EdgePos>() + first_dup - 1, sizeof(two), hipMemcpyDeviceToHost));
+    BBK_REQUIRE(false, BBK_ERR_ARG,
+                "duplicated (k+1)-mer: segment %s offset %u and segment %s offset %u hold the same %u-mer (up to "
+                "reverse complement); the mapping needs every (k+1)-mer of the graph once",
+                ix->names[two[0].seg].c_str(), two[0].off_fw, ix->names[two[1].seg].c_str(), two[1].off_fw, ix->k1);
+}
+
+// the index of a graph held on the host, checked as the position-local form needs (gfa_graph.h): classify, check the
+// links, flag the loops, keep or drop the graph, build on the device, report a duplicate, prefix table
+static bbk_edgeindex *build_index(bbk_ctx *ctx, unsigned k, HostGraph &g, bool keep_graph) {
+    BBK_REQUIRE(k >= 1 && k < BBK_MAX_K && k % 2 == 1, BBK_ERR_ARG, "edge index: k = %u must be odd and < %d", k, BBK_MAX_K);
+    const uint64_t ns = g.names.size();
+    BBK_REQUIRE(ns > 0, BBK_ERR_ARG, "edge index: the graph has no segments");
+    BBK_REQUIRE(ns < (1ull << 32) - 1, BBK_ERR_ARG, "edge index: too many segments (%llu)", (unsigned long long)ns);
+    auto ix = std::make_unique<bbk_edgeindex>();
+    ix->k = k;
+    ix->k1 = k + 1;
+    ix->W = words_of(k + 1);
+    ix->n_seg = ns;
+    SegmentTable t(ns);
+    require_graph(classify_segments(g, k, t));
+    require_graph(check_links(g, k));
+    flag_loops(g, k, t);
+    ix->n = t.emit[ns];
+    BBK_REQUIRE(ix->n < (1ull << 32), BBK_ERR_ARG, "edge index: %llu (k+1)-mers, at most 2^32 - 1 supported",
+                (unsigned long long)ix->n);
+    ix->len = std::move(t.len);
+    ix->names = std::move(g.names);
+    bbk_reads *sr = nullptr;
+    int rc = bbk_reads_from_ascii(ctx, g.bases.data(), g.off.data(), ns, &sr);
+    if (rc != BBK_OK) throw Error{rc};
+    std::unique_ptr<bbk_reads, void (*)(bbk_reads *)> sr_guard(sr, bbk_reads_free);
+    keep_or_drop_graph(ix.get(), g, keep_graph);
+    const uint64_t first_dup = build_device_index(ctx, ix.get(), sr, t);
+    if (first_dup != ~0ull) report_duplicate(ix.get(), first_dup);
+    ix->prefix.build(ctx, ix->keys.as<uint64_t>(), ix->W, ix->k1, ix->n);
     return ix.release();
 }
 
-// GFA1 S and L lines (io/graph/gfa_reader.cpp): segment names and sequences in file order, links with a kM overlap
-static void parse_gfa(const char *path, unsigned k, HostGraph &g) {
-    std::string text;
-    {
-        FILE *f = fopen(path, "rb");
-        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open graph %s", path);
-        std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
-        char buf[1 << 20];
-        size_t got;
-        while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got);
-        BBK_REQUIRE(!ferror(f), BBK_ERR_IO, "reading graph %s failed", path);
-    }
-    static const auto code = [] {
-        std::vector<char> t(256, 0);
-        t['A'] = t['a'] = 'A';
-        t['C'] = t['c'] = 'C';
-        t['G'] = t['g'] = 'G';
-        t['T'] = t['t'] = 'T';
-        return t;
-    }();
-    struct RawLink {
-        const char *a, *b;
-        size_t na, nb;
-        bool oa, ob;
-        uint64_t line;
-    };
-    std::vector<RawLink> raw;
-    const std::string kM = std::to_string(k) + "M";
-    g.bases.reserve(text.size());
-    const char *p = text.data(), *end = p + text.size();
-    const char *fs[7], *fe[7];
-    for (uint64_t lineno = 1; p < end; ++lineno) {
-        const char *nl = static_cast<const char *>(memchr(p, '\n', (size_t)(end - p)));
-        const char *le = nl ? nl : end;
-        const char *next = nl ? nl + 1 : end;
-        while (le > p && le[-1] == '\r') --le;
-        if (le - p >= 2 && p[1] == '\t' && (p[0] == 'S' || p[0] == 'L')) {
-            int nf = 0;
-            for (const char *f = p; nf < 7;) {
-                const char *t = static_cast<const char *>(memchr(f, '\t', (size_t)(le - f)));
-                fs[nf] = f;
-                fe[nf++] = t ? t : le;
-                if (!t) break;
-                f = t + 1;
-            }
-            auto fld = [&](int i) { return std::string(fs[i], (size_t)(fe[i] - fs[i])); };
-            if (p[0] == 'S') {
-                BBK_REQUIRE(nf >= 3, BBK_ERR_ARG, "%s:%llu: S line without a sequence", path, (unsigned long long)lineno);
-                for (const char *c = fs[2]; c < fe[2]; ++c) {
-                    const char u = code[(unsigned char)*c];
-                    BBK_REQUIRE(u, BBK_ERR_ARG, "%s:%llu: segment %s holds a base other than ACGT ('%c')", path,
-                                (unsigned long long)lineno, fld(1).c_str(), *c);
-                    g.bases.push_back(u);
-                }
-                g.off.push_back(g.bases.size());
-                g.names.push_back(fld(1));
-                uint32_t kc = 0;  // the first KC:i: tag, read as the gfa library reads it (an int32; gfa_reader.cpp:65-68)
-                for (const char *t = fe[2]; t + 6 <= le; ++t)
-                    if (t[0] == '\t' && memcmp(t + 1, "KC:i:", 5) == 0) {
-                        kc = (uint32_t)(int32_t)strtol(t + 6, nullptr, 10);
-                        break;
-                    }
-                g.kc.push_back(kc);
-            } else {
-                BBK_REQUIRE(nf >= 6 && fe[2] - fs[2] == 1 && fe[4] - fs[4] == 1 && (*fs[2] == '+' || *fs[2] == '-') &&
-                                (*fs[4] == '+' || *fs[4] == '-'),
-                            BBK_ERR_ARG, "%s:%llu: malformed L line", path, (unsigned long long)lineno);
-                BBK_REQUIRE(fld(5) == kM, BBK_ERR_ARG,
-                            "%s:%llu: link overlap %s, only %s (a k-overlap at k = %u) is supported", path,
-                            (unsigned long long)lineno, fld(5).c_str(), kM.c_str(), k);
-                raw.push_back({fs[1], fs[3], (size_t)(fe[1] - fs[1]), (size_t)(fe[3] - fs[3]), *fs[2] == '+', *fs[4] == '+',
-                               lineno});
-            }
-        }
-        p = next;
-    }
-    // names: spades-gbuilder's are 3 + 2i in S-line order (graph_core.hpp:228,610-624), taken by value; others by map
-    const uint64_t ns = g.names.size();
-    std::unordered_map<std::string, uint32_t> id;
-    bool by_value = true;
-    for (uint64_t i = 0; i < ns && by_value; ++i) by_value = g.names[i] == std::to_string(3 + 2 * i);
-    if (!by_value) {
-        id.reserve(ns);
-        for (uint64_t i = 0; i < ns; ++i)
-            BBK_REQUIRE(id.emplace(g.names[i], (uint32_t)i).second, BBK_ERR_ARG, "%s: segment %s defined twice", path,
-                        g.names[i].c_str());
-    }
-    auto resolve = [&](const char *s, size_t n, uint32_t *out) {
-        if (by_value) {
-            uint64_t v = 0;
-            for (size_t i = 0; i < n; ++i) {
-                if (s[i] < '0' || s[i] > '9' || v > (1ull << 60)) return false;
-                v = v * 10 + (uint64_t)(s[i] - '0');
-            }
-            if (n == 0 || (n > 1 && s[0] == '0') || v < 3 || (v & 1) == 0 || (v - 3) / 2 >= ns) return false;
-            *out = (uint32_t)((v - 3) / 2);
-            return true;
-        }
-        auto it = id.find(std::string(s, n));
-        if (it == id.end()) return false;
-        *out = it->second;
-        return true;
-    };
-    g.links.resize(raw.size());
-    for (size_t j = 0; j < raw.size(); ++j) {
-        const RawLink &l = raw[j];
-        HostLink &h = g.links[j];
-        BBK_REQUIRE(resolve(l.a, l.na, &h.a) && resolve(l.b, l.nb, &h.b), BBK_ERR_ARG, "%s:%llu: link to an undefined segment",
-                    path, (unsigned long long)l.line);
-        h.oa = l.oa;
-        h.ob = l.ob;
-    }
+// pos_off[r] = (k+1)-mer positions before read r, pos_off[n] = total: npos kernel, scan (one wait), total staged from the
+// caller's variable, which lives until the stream is waited for.  Returns total: 0 when there is nothing to map
+static uint64_t read_positions(bbk_ctx *ctx, const bbk_edgeindex *ix, const bbk_reads *reads, DevBuf &pos_off,
+                               uint64_t &total) {
+    const uint64_t n = reads->n;
+    if (n == 0 || ix->n == 0) return total = 0;
+    pos_off.alloc((n + 1) * 8);
+    launch_items(ctx, "k_ep_npos", k_ep_npos, n, reads->d_len, n, ix->k1, pos_off.as<uint64_t>());
+    total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
+    if (total) BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
+    return total;
 }
 
-static void d2h_sync(bbk_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    BBK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
-}
-
-template <int W>
-static void run_map(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix,
-                    bbk_profiles *p, unsigned sample) {
+// One launch over waves of 63 positions (k_ep_map, k_gm_paths), timed as `family`; extra are the kernel's own arguments
+template <int W, class K, class... Args>
+static void launch_map(bbk_ctx *ctx, const char *family, const char *name, K fn, const bbk_reads *r,
+                       const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix, Args... extra) {
     const uint64_t waves = (total + kMapStep - 1) / kMapStep;
-    // bytes the lookups need at the least: one prefix entry, the key and the record per position
-    KernelTimer t(ctx, "edgeprof_map", (double)total * (8.0 * W + sizeof(EdgePos) + 4));
-    hipLaunchKernelGGL(k_ep_map<W>, grid_blocks((waves + kMapWaves - 1) / kMapWaves), dim3(64 * kMapWaves), 0, ctx->stream,
-                       r->d_words, r->d_woff, r->d_len, pos_off.as<uint64_t>(), r->n, total, (int)ix->k1,
-                       ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(), ix->prefix.table(),
-                       p->raw.as<unsigned long long>(), p->samples, sample);
-    check_launch("k_ep_map");
-}
-
-// one pass of k_gm_paths: out == nullptr counts the range starts per wave, otherwise writes the ranges
-template <int W>
-static void run_paths(bbk_ctx *ctx, const bbk_reads *r, const DevBuf &pos_off, uint64_t total, const bbk_edgeindex *ix,
-                      uint64_t *wave_cnt, bbk_path_range *out) {
-    const uint64_t waves = (total + kMapStep - 1) / kMapStep;
-    const PrefixTable P = ix->prefix.table();
-    const dim3 grid = grid_blocks((waves + kMapWaves - 1) / kMapWaves), block(64 * kMapWaves);
-    // the lookups' bytes as for k_ep_map; each pass runs them
-    KernelTimer t(ctx, out ? "gmap_write" : "gmap_count", (double)total * (8.0 * W + sizeof(EdgePos) + 4));
-    if (out)
-        hipLaunchKernelGGL((k_gm_paths<W, true>), grid, block, 0, ctx->stream, r->d_words, r->d_woff, r->d_len,
-                           pos_off.as<uint64_t>(), r->n, total, (int)ix->k1, ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(),
-                           P, wave_cnt, out);
-    else
-        hipLaunchKernelGGL((k_gm_paths<W, false>), grid, block, 0, ctx->stream, r->d_words, r->d_woff, r->d_len,
-                           pos_off.as<uint64_t>(), r->n, total, (int)ix->k1, ix->keys.as<Key<W>>(), ix->pos.as<EdgePos>(),
-                           P, wave_cnt, out);
-    check_launch("k_gm_paths");
-}
-
-static size_t fmt_line(char *dst, size_t cap, const std::string &name, const uint64_t *raw, unsigned S, uint64_t len) {
-    size_t o = 0;
-    o += (size_t)snprintf(dst + o, cap - o, "%s\t", name.c_str());
-    for (unsigned s = 0; s < S; ++s) o += (size_t)snprintf(dst + o, cap - o, "%g\t", (double)raw[s] / (double)len);
-    dst[o++] = '\n';
-    return o;
+    // bytes the lookups need at the least: one prefix entry, the key and the record per position (each pass runs them)
+    KernelTimer t(ctx, family, (double)total * (8.0 * W + sizeof(EdgePos) + 4));
+    hipLaunchKernelGGL(fn, grid_blocks((waves + kMapWaves - 1) / kMapWaves), dim3(64 * kMapWaves), 0, ctx->stream, r->d_words,
+                       r->d_woff, r->d_len, pos_off.as<uint64_t>(), r->n, total, (int)ix->k1, ix->keys.as<Key<W>>(),
+                       ix->pos.as<EdgePos>(), ix->prefix.table(), extra...);
+    check_launch(name);
 }
 
 }  // namespace bbk
@@ -651,7 +413,11 @@ static int from_gfa(bbk_ctx *ctx, const char *path, unsigned k, bbk_edgeindex **
                     k, BBK_MAX_K);
         BBK_HIP(hipSetDevice(ctx->device));
         HostGraph g;
-        parse_gfa(path, k, g);
+        {
+            std::string text;
+            require_graph(read_whole_file(path, "cannot open graph %s", "reading graph %s failed", text));
+            require_graph(parse_gfa_text(text.data(), text.data() + text.size(), k, path, g));
+        }
         *out = build_index(ctx, k, g, keep_graph);
     });
 }
@@ -710,16 +476,15 @@ int bbk_profiles_push_reads(bbk_profiles *p, unsigned sample, const bbk_reads *r
         BBK_REQUIRE(p && reads, BBK_ERR_ARG, "bbk_profiles_push_reads: NULL argument");
         BBK_REQUIRE(sample < p->samples, BBK_ERR_ARG, "bbk_profiles_push_reads: sample %u of %u", sample, p->samples);
         bbk_ctx *ctx = p->ctx;
-        const bbk_edgeindex *ix = p->ix;
         BBK_HIP(hipSetDevice(ctx->device));
-        const uint64_t n = reads->n;
-        if (n == 0 || ix->n == 0) return;
-        DevBuf pos_off((n + 1) * 8);
-        launch_items(ctx, "k_ep_npos", k_ep_npos, n, reads->d_len, n, ix->k1, pos_off.as<uint64_t>());
-        const uint64_t total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
-        if (total == 0) return;
-        BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
-        dispatch_w(ix->W, [&](auto w) { run_map<decltype(w)::value>(ctx, reads, pos_off, total, ix, p, sample); });
+        DevBuf pos_off;
+        uint64_t total;
+        if (read_positions(ctx, p->ix, reads, pos_off, total) == 0) return;
+        dispatch_w(p->ix->W, [&](auto w) {
+            constexpr int W_ = decltype(w)::value;
+            launch_map<W_>(ctx, "edgeprof_map", "k_ep_map", k_ep_map<W_>, reads, pos_off, total, p->ix,
+                           p->raw.as<unsigned long long>(), (uint32_t)p->samples, (uint32_t)sample);
+        });
         BBK_HIP(hipStreamSynchronize(ctx->stream));  // pos_off and the staged total are released on return
     });
 }
@@ -739,34 +504,24 @@ int bbk_profiles_write(bbk_ctx *ctx, const bbk_profiles *p, const char *path) {
         BBK_REQUIRE(ctx && p && path, BBK_ERR_ARG, "bbk_profiles_write: NULL argument");
         BBK_HIP(hipSetDevice(ctx->device));
         const bbk_edgeindex *ix = p->ix;
-        const uint64_t ns = ix->n_seg;
         const unsigned S = p->samples;
-        std::vector<uint64_t> raw((size_t)ns * S);
+        std::vector<uint64_t> raw((size_t)ix->n_seg * S);
         d2h_sync(ctx, raw.data(), p->raw.p, raw.size() * 8);
         FILE *f = fopen(path, "wb");
         BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path);
         std::unique_ptr<FILE, int (*)(FILE *)> guard(f, fclose);
-        constexpr uint64_t kBlock = 1 << 14;  // segments formatted per task
-        const uint64_t nblocks = (ns + kBlock - 1) / kBlock;
         const int nt = std::max(1, std::min(omp_get_max_threads(), 16));
-        for (uint64_t b0 = 0; b0 < nblocks; b0 += (uint64_t)nt) {
-            const uint64_t b1 = std::min(nblocks, b0 + (uint64_t)nt);
-            std::vector<std::string> text(b1 - b0);
-            bool fail = false;
-#pragma omp parallel for num_threads(nt) schedule(dynamic, 1)
-            for (int64_t b = (int64_t)b0; b < (int64_t)b1; ++b) {
-                std::string &t = text[(size_t)(b - (int64_t)b0)];
-                std::vector<char> line;
-                for (uint64_t s = (uint64_t)b * kBlock; s < std::min(ns, (uint64_t)(b + 1) * kBlock); ++s) {
-                    const size_t cap = ix->names[s].size() + 2 + (size_t)S * 32;
-                    if (line.size() < cap) line.resize(cap);
-                    t.append(line.data(), fmt_line(line.data(), cap, ix->names[s], &raw[s * S], S, ix->len[s]));
-                }
-            }
-            for (const std::string &t : text)
-                if (!t.empty() && fwrite(t.data(), 1, t.size(), f) != t.size()) fail = true;
-            BBK_REQUIRE(!fail, BBK_ERR_IO, "short write to %s", path);
-        }
+        const bool ok = format_blocks(
+            ix->n_seg, nt, (uint64_t)nt, [&](const std::string &t) { return fwrite(t.data(), 1, t.size(), f) == t.size(); },
+            [&](uint64_t s, std::string &o) {
+                char num[32];
+                o += ix->names[s];
+                o += '\t';
+                for (unsigned i = 0; i < S; ++i)
+                    o.append(num, (size_t)snprintf(num, sizeof(num), "%g\t", (double)raw[s * S + i] / (double)ix->len[s]));
+                o += '\n';
+            });
+        BBK_REQUIRE(ok, BBK_ERR_IO, "short write to %s", path);
         FILE *fo = guard.release();
         BBK_REQUIRE(fclose(fo) == 0, BBK_ERR_IO, "closing %s failed", path);
     });
@@ -781,27 +536,25 @@ int bbk_edgeindex_map_paths(bbk_ctx *ctx, const bbk_edgeindex *ix, const bbk_rea
                     (unsigned long long)reads->n);
         BBK_HIP(hipSetDevice(ctx->device));
         auto p = std::make_unique<bbk_paths>();
-        const uint64_t n = reads->n;
-        p->n_reads = n;
-        if (n > 0 && ix->n > 0) {
-            DevBuf pos_off((n + 1) * 8);
-            launch_items(ctx, "k_ep_npos", k_ep_npos, n, reads->d_len, n, ix->k1, pos_off.as<uint64_t>());
-            const uint64_t total = exclusive_scan_u64(ctx, pos_off.as<uint64_t>(), pos_off.as<uint64_t>(), n);
-            if (total > 0) {
-                BBK_HIP(hipMemcpyAsync(pos_off.as<uint64_t>() + n, &total, 8, hipMemcpyHostToDevice, ctx->stream));
-                const uint64_t waves = (total + kMapStep - 1) / kMapStep;
-                DevBuf wave_cnt(waves * 8);
-                auto run = [&](bbk_path_range *o) {
-                    dispatch_w(ix->W, [&](auto w) {
-                        run_paths<decltype(w)::value>(ctx, reads, pos_off, total, ix, wave_cnt.as<uint64_t>(), o);
-                    });
-                };
-                run(nullptr);
-                p->n_ranges = exclusive_scan_u64(ctx, wave_cnt.as<uint64_t>(), wave_cnt.as<uint64_t>(), waves);
-                p->ranges.alloc(p->n_ranges * sizeof(bbk_path_range));
-                if (p->n_ranges) run(p->ranges.as<bbk_path_range>());
-                BBK_HIP(hipStreamSynchronize(ctx->stream));  // pos_off, wave_cnt and the staged total die here
-            }
+        p->n_reads = reads->n;
+        DevBuf pos_off;
+        uint64_t total;
+        if (read_positions(ctx, ix, reads, pos_off, total) > 0) {
+            const uint64_t waves = (total + kMapStep - 1) / kMapStep;
+            DevBuf wave_cnt(waves * 8);
+            auto run = [&](auto write) {  // one pass of k_gm_paths: count the range starts per wave, or write the ranges
+                dispatch_w(ix->W, [&](auto w) {
+                    constexpr int W_ = decltype(w)::value;
+                    constexpr bool WRITE = decltype(write)::value;
+                    launch_map<W_>(ctx, WRITE ? "gmap_write" : "gmap_count", "k_gm_paths", k_gm_paths<W_, WRITE>, reads,
+                                   pos_off, total, ix, wave_cnt.as<uint64_t>(), p->ranges.as<bbk_path_range>());
+                });
+            };
+            run(std::false_type{});
+            p->n_ranges = exclusive_scan_u64(ctx, wave_cnt.as<uint64_t>(), wave_cnt.as<uint64_t>(), waves);
+            p->ranges.alloc(p->n_ranges * sizeof(bbk_path_range));
+            if (p->n_ranges) run(std::true_type{});
+            BBK_HIP(hipStreamSynchronize(ctx->stream));  // pos_off, wave_cnt and the staged total die here
         }
         *out = p.release();
     });

@@ -165,6 +165,31 @@ __device__ inline bool kmer_less_nucl(const Key<W> &a, const Key<W> &b) {
     return false;
 }
 
+// canonical k-mer at base p of a read: the one-word fast path where it exists (last_word: index of the read's last packed
+// word, read by that path only), otherwise extract / reverse complement / select.  *minimal: the read's own strand won
+template <int W>
+__device__ inline Key<W> kmer_canon(const uint64_t *__restrict__ rw, uint32_t p, int k, uint32_t last_word, bool *minimal) {
+    if constexpr (W == 1) {
+        return kmer_extract_canon1(rw, p, k, last_word, minimal);
+    } else {
+        const Key<W> x = kmer_extract<W>(rw, p, k);
+        const Key<W> r = kmer_rc<W>(x, k);
+        *minimal = !kmer_less_nucl<W>(r, x);
+        return key_select<W>(*minimal, x, r);
+    }
+}
+
+// last index i < n with off[i] <= x, for ascending off with off[0] <= x: the slice of a prefix sum that holds item x
+__device__ inline uint64_t last_le(const uint64_t *__restrict__ off, uint64_t n, uint64_t x) {
+    uint64_t lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
 // drop base 0, append c as base k-1 (RtSeq::operator<<=, rtseq.hpp:450-467)
 template <int W>
 __device__ inline Key<W> kmer_shl(const Key<W> &x, int k, uint32_t c) {

@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 
 #include <fcntl.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cstring>
@@ -32,6 +31,7 @@
 #include <vector>
 
 #include "bbk_internal.h"
+#include "gfa_graph.h"
 #include "kmer_ops.h"
 
 struct bbk_kmerprofile {
@@ -402,8 +402,7 @@ static bbk_kmerprofile *finish_profile(bbk_kmerprofile_builder *b, uint64_t min_
         });
     }
     uint32_t h_err = 0;
-    BBK_HIP(hipMemcpyAsync(&h_err, err.p, 4, hipMemcpyDeviceToHost, ctx->stream));
-    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    d2h_sync(ctx, &h_err, err.p, 4);
     BBK_REQUIRE(h_err == 0, BBK_ERR_INTERNAL, "bbk_kmerprofile_finish: a sample k-mer is missing from the union");
     for (auto &S : b->samples) {
         S.keys.release();
@@ -482,18 +481,9 @@ static void write_device(bbk_ctx *ctx, const std::string &path, const void *src,
     BBK_REQUIRE(ok && closed, BBK_ERR_IO, "writing %s failed", path.c_str());
 }
 
-static void read_file(const std::string &path, raw_vector<char> &out) {
-    FILE *f = fopen(path.c_str(), "rb");
-    BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s", path.c_str());
-    struct stat st;
-    if (fstat(fileno(f), &st) != 0) {
-        fclose(f);
-        BBK_REQUIRE(false, BBK_ERR_IO, "cannot stat %s", path.c_str());
-    }
-    out.resize((size_t)st.st_size);
-    const size_t got = out.empty() ? 0 : fread(out.data(), 1, out.size(), f);
-    fclose(f);
-    BBK_REQUIRE(got == out.size(), BBK_ERR_IO, "short read of %s", path.c_str());
+static void read_file(const std::string &path, std::string &out) {
+    const GraphError e = read_whole_file(path.c_str(), "cannot open %s", "short read of %s", out);
+    BBK_REQUIRE(!e, BBK_ERR_IO, "%s", e.msg.c_str());
 }
 
 }  // namespace bbk
@@ -575,7 +565,7 @@ int bbk_kmerprofile_load(bbk_ctx *ctx, const char *prefix, unsigned k, unsigned 
                     "bbk_kmerprofile_load: %u samples, 1..65535 are supported", n_samples);
         BBK_HIP(hipSetDevice(ctx->device));
         const std::string kp = std::string(prefix) + ".kmers", rp = std::string(prefix) + ".bpr";
-        raw_vector<char> kb, rb;
+        std::string kb, rb;
         read_file(kp, kb);
         read_file(rp, rb);
         const unsigned W = words_of(k);

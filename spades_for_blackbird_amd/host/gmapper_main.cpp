@@ -23,7 +23,6 @@
 // Sequence).  Other library types are skipped with the reference's warning.  --tmp-dir is accepted and unused.
 #include <algorithm>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <queue>
 #include <string>
@@ -31,6 +30,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "../csrc/gfa_graph.h"
 #include "common.hpp"
 
 using namespace bbkhost;
@@ -93,8 +93,6 @@ struct Graph {
     }
 };
 
-char comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A'; }
-
 // GFAReader::to_graph over the graph the index has parsed.  Returns the number of one-(k+1)-mer homopolymer edges whose
 // loop flag in the index (an L line from the segment to itself) differs from "e is among OutgoingEdges(EdgeEnd(e))"
 // here: csrc/edgeprof.hip explains why that changes the cut of ranges only, not this tool's output.
@@ -114,13 +112,8 @@ uint64_t build_graph(const bbk_edgeindex *ix, unsigned k, int threads, Graph &g)
           "bbk_edgeindex_export_graph");
     g.selfc.assign(ns, 0);
 #pragma omp parallel for schedule(static) num_threads(threads)
-    for (int64_t s = 0; s < (int64_t)ns; ++s) {
-        const char *q = g.bases.data() + g.off[s];
-        const uint64_t n = g.off[s + 1] - g.off[s];
-        bool sc = true;
-        for (uint64_t i = 0; i < (n + 1) / 2 && sc; ++i) sc = q[i] == comp(q[n - 1 - i]);
-        g.selfc[s] = sc;
-    }
+    for (int64_t s = 0; s < (int64_t)ns; ++s)
+        g.selfc[s] = bbk::segment_is_self_conjugate(g.bases.data() + g.off[s], g.off[s + 1] - g.off[s]);
     g.end.assign(nx, 0);
     for (uint64_t s = 0; s < ns; ++s) {  // LinkIncomingEdge: edge 2s ends at vertex 4s, edge 2s + 1 at 4s + 2
         g.end[2 * s] = (Vertex)(4 * s);
@@ -180,11 +173,8 @@ uint64_t build_graph(const bbk_edgeindex *ix, unsigned k, int threads, Graph &g)
     for (uint64_t s = 0; s < ns; ++s) {
         const Edge e = (Edge)(2 * s);
         if (g.length(e) != 1) continue;
-        const char *q = g.bases.data() + g.off[s];
-        bool homo = true;
-        for (unsigned i = 1; i <= k; ++i) homo = homo && q[i] == q[0];
-        if (homo && (std::find(g.out_begin(g.end[e]), g.out_end(g.end[e]), e) != g.out_end(g.end[e])) != (bool)self_linked[s])
-            ++differ;
+        const bool looped = std::find(g.out_begin(g.end[e]), g.out_end(g.end[e]), e) != g.out_end(g.end[e]);
+        if (bbk::is_homopolymer_k1(g.bases.data() + g.off[s], k + 1) && looped != (bool)self_linked[s]) ++differ;
     }
     return differ;
 }
@@ -304,22 +294,10 @@ void write_output(const Graph &g, const std::map<std::vector<Edge>, uint64_t> &p
     bool fail = false;
     auto put = [&](const std::string &t) {
         if (!t.empty() && fwrite(t.data(), 1, t.size(), f) != t.size()) fail = true;
+        return true;  // the failure is reported after the last write
     };
-    // items formatted in blocks, 64 blocks at a time
-    auto emit = [&](uint64_t n, const std::function<void(uint64_t, std::string &)> &fmt) {
-        constexpr uint64_t kBlock = 1 << 14;
-        const uint64_t nb = (n + kBlock - 1) / kBlock;
-        for (uint64_t b0 = 0; b0 < nb; b0 += 64) {
-            const uint64_t b1 = std::min(nb, b0 + 64);
-            std::vector<std::string> text(b1 - b0);
-#pragma omp parallel for num_threads(threads) schedule(dynamic, 1)
-            for (int64_t b = (int64_t)b0; b < (int64_t)b1; ++b)
-                for (uint64_t i = (uint64_t)b * kBlock; i < std::min(n, (uint64_t)(b + 1) * kBlock); ++i)
-                    fmt(i, text[(size_t)(b - (int64_t)b0)]);
-            for (const std::string &t : text) put(t);
-        }
-    };
-    emit(g.ns, [&](uint64_t s, std::string &o) {  // S lines of the canonical edges: DP = float(raw / length), KC = raw
+    // items formatted in blocks, 64 blocks at a time.  S lines of the canonical edges: DP = float(raw / length), KC = raw
+    bbk::format_blocks(g.ns, threads, 64, put, [&](uint64_t s, std::string &o) {
         char tail[96];
         snprintf(tail, sizeof(tail), "\tDP:f:%g\tKC:i:%u\n", (double)(float)g.coverage((Edge)(2 * s)), g.kc[s]);
         o += "S\t";
@@ -329,7 +307,8 @@ void write_output(const Graph &g, const std::map<std::vector<Edge>, uint64_t> &p
         o += tail;
     });
     const std::string ovl = "\t" + std::to_string(g.k) + "M\n";
-    emit(2 * g.ns, [&](uint64_t h, std::string &o) {  // L lines at canonical vertex 2h: incoming x outgoing
+    // L lines at canonical vertex 2h: incoming x outgoing
+    bbk::format_blocks(2 * g.ns, threads, 64, put, [&](uint64_t h, std::string &o) {
         const Vertex v = (Vertex)(2 * h);
         for (const Edge *a = g.out_begin(v ^ 1u); a != g.out_end(v ^ 1u); ++a)
             for (const Edge *b = g.out_begin(v); b != g.out_end(v); ++b) {

@@ -1,19 +1,22 @@
 """GPU: spades-gmapper.  (a) the ranges of bbk_edgeindex_map_paths equal the restated MapSequence
 (tests/gmapper_restated.py) for k in {21, 33, 55, 77, 127} on reads with substitutions and Ns, over gbuilder graphs and
-over a homopolymer loop, a palindromic segment and a circular segment; (b) the CLI on a gbuilder GFA with contigs cut
-from the genome equals the restatement byte for byte, and its S/L part equals the input graph up to gfa_canon; (c) every
-segment as a contig is a one-edge path of weight 1; (d) consecutive edges of a P line are linked; (e) refusals, the last
-contig library wins, and no file without one."""
+over a homopolymer loop, a palindromic segment and a circular segment, and at the wave and block edges of the position
+lookup of the two mapping kernels; (b) the CLI on a gbuilder GFA with contigs cut from the genome equals the
+restatement byte for byte, and its S/L part equals the input graph up to gfa_canon; (c) every segment as a contig is a
+one-edge path of weight 1; (d) consecutive edges of a P line are linked; (e) refusals, the last contig library wins, and
+no file without one."""
 import os
 import random
 import subprocess
 
+import numpy as np
 import pytest
 
 import spades_for_blackbird_amd as B
 from spades_for_blackbird_amd import build, build_host
 from spades_for_blackbird_amd.tools import gfa_canon
 from tests import gmapper_restated as G
+from tests import unitig_profile_restated as R
 from tests.helpers import rc
 
 pytestmark = pytest.mark.gpu
@@ -114,6 +117,36 @@ def test_a_ranges_k127_and_adversarial_graphs(ctx, tmp_path):
     reads = ["G" + "A" * n + "C" for n in (21, 22, 25, 40)] + ["A" * 30, "T" * 30, x + rc(x), rc(x)[4:] + x[:9]]
     reads += [(y * 5)[i:i + 140] for i in range(0, 50, 7)] + [rc(y * 3)[3:120], _mutate(rng, y * 4, 0.02, 0.01)]
     _check_ranges(ctx, ctx.edgeindex_from_gfa(str(gfa), k), g, reads)
+
+
+@pytest.mark.parametrize("k", [21, 33])
+def test_a_ranges_at_wave_and_block_edges(ctx, tmp_path, k):
+    """The position lookup of k_gm_paths and k_ep_map: a wave takes 63 positions of the concatenated reads in lanes
+    1..63 and its lane 0 looks up the position before them; a block takes 4 waves, 252 positions.  One segment with 300
+    (k+1)-mers, one and two key words; every batch of reads is its own call and its own sample of the profile."""
+    rng = random.Random(k)
+    seg = _rand(rng, 300 + k)
+    gfa = tmp_path / "one.gfa"
+    gfa.write_text("S\t3\t%s\n" % seg)
+    g = G.Graph.from_gfa(gfa.read_text(), k)
+    ix = ctx.edgeindex_from_gfa(str(gfa), k)
+    sub = lambda start, positions: seg[start:start + positions + k]  # a read with that many (k+1)-mer positions
+    # one read whose single range ends before, at and after the end of a wave, of two waves, and of the block
+    batches = [[sub(5, n)] for n in (62, 63, 64, 126, 127, 252, 253)]
+    # the first read fills one wave (two waves): position 0 of the second read is lane 1 of the next wave, and lane 0
+    # there holds the first read's last position, on the same edge at a smaller offset.  A new read opens a new range
+    batches += [[sub(3, n), sub(3 + n + 20, 40)] for n in (63, 126)]
+    # a read shorter than k + 1 has no position: its neighbours follow each other in the concatenation
+    batches += [[sub(0, 80), seg[10:10 + k], sub(100, 70)]]
+    for reads in batches:
+        assert _check_ranges(ctx, ix, g, reads) == sum(len(r) > k for r in reads)  # one range per mapped read
+    p = ix.profiles(len(batches))
+    for i, reads in enumerate(batches):
+        p.push(i, ctx.reads_from_ascii(reads))
+    gr = R.Graph.from_gfa(gfa.read_text(), k)
+    exp = np.array(R.segment_raw(gr, R.fill_literal(gr, batches)), dtype=np.uint64)
+    assert list(exp[0]) == [62, 63, 64, 126, 127, 252, 253, 63 + 40, 126 + 40, 80 + 70]  # every position once
+    assert np.array_equal(p.raw(), exp)
 
 
 def _genome_graph(bins, tmp_path, seed=11, k=21):
