@@ -97,3 +97,23 @@ def polya_reads(seed=5, n_tx=8, read_len=150, n_reads=1500, n_tail=400, sub_rate
         reads.append(flank[0] + "C" * 130 + flank[1])
         reads.append("AT" * 75)
     return reads
+
+
+def check_profile_join(ctx, tmp_path, k, sets, exported, min_samples, min_mult=5, ci=2, cs=255):
+    """profile == restatement: arrays, files, and the files loaded again"""
+    from tests import kmerprofile_restated as R
+    n_samples, nw = len(sets), R.words(k)
+    p = ctx.kmerprofile(k, sets, min_samples, min_mult=min_mult, ci=ci, cs=cs)
+    rk, rr = R.join([R.filter_sample(keys, cnt, ci, cs) for keys, cnt in exported], min_samples, min_mult)
+    exp_keys = np.array(rk, dtype=np.uint64).reshape(len(rk), nw)
+    exp_rows = np.array(rr, dtype=np.uint16).reshape(len(rr), n_samples)
+    assert len(p) == len(rk) and p.samples == n_samples and p.k == k
+    assert p.keys().tobytes() == exp_keys.tobytes()
+    assert p.rows().tobytes() == exp_rows.tobytes()
+    prefix = str(tmp_path / ("prof_%d_%d_%d_%d" % (min_samples, min_mult, ci, cs)))
+    p.write(prefix)
+    assert open(prefix + ".kmers", "rb").read() == R.kmers_bytes(rk)
+    assert open(prefix + ".bpr", "rb").read() == R.bpr_bytes(rr)
+    q = ctx.kmerprofile_load(prefix, k, n_samples)
+    assert len(q) == len(rk) and q.keys().tobytes() == exp_keys.tobytes() and q.rows().tobytes() == exp_rows.tobytes()
+    return p, rk, rr

@@ -12,6 +12,7 @@ import pytest
 import spades_for_blackbird_amd as B
 from spades_for_blackbird_amd import build, build_host
 from tests import kmerprofile_restated as R
+from tests.helpers import check_profile_join as _check_join
 from tests.helpers import rc, read_fastq_gz
 
 pytestmark = pytest.mark.gpu
@@ -50,25 +51,6 @@ def _reads(rng, genome, n, read_len=100, sub_rate=0.005):
 def _count(ctx, reads, k):
     s = ctx.count(ctx.reads_from_ascii(reads), k, FLAGS)
     return s, s.export(with_counts=True)
-
-
-def _check_join(ctx, tmp_path, k, sets, exported, min_samples, min_mult=5, ci=2, cs=255):
-    """profile == restatement: arrays, files, and the files loaded again"""
-    n_samples, nw = len(sets), R.words(k)
-    p = ctx.kmerprofile(k, sets, min_samples, min_mult=min_mult, ci=ci, cs=cs)
-    rk, rr = R.join([R.filter_sample(keys, cnt, ci, cs) for keys, cnt in exported], min_samples, min_mult)
-    exp_keys = np.array(rk, dtype=np.uint64).reshape(len(rk), nw)
-    exp_rows = np.array(rr, dtype=np.uint16).reshape(len(rr), n_samples)
-    assert len(p) == len(rk) and p.samples == n_samples and p.k == k
-    assert p.keys().tobytes() == exp_keys.tobytes()
-    assert p.rows().tobytes() == exp_rows.tobytes()
-    prefix = str(tmp_path / ("prof_%d_%d_%d_%d" % (min_samples, min_mult, ci, cs)))
-    p.write(prefix)
-    assert open(prefix + ".kmers", "rb").read() == R.kmers_bytes(rk)
-    assert open(prefix + ".bpr", "rb").read() == R.bpr_bytes(rr)
-    q = ctx.kmerprofile_load(prefix, k, n_samples)
-    assert len(q) == len(rk) and q.keys().tobytes() == exp_keys.tobytes() and q.rows().tobytes() == exp_rows.tobytes()
-    return p, rk, rr
 
 
 def _samples(n_samples, k, seed):
