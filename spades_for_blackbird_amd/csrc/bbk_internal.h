@@ -333,16 +333,23 @@ uint64_t exclusive_scan_u64(bbk_ctx *ctx, const uint64_t *in, uint64_t *out, uin
 // outputs hold n + 1 entries).
 void exclusive_scan2_u64(bbk_ctx *ctx, const uint64_t *in0, uint64_t *out0, const uint64_t *in1, uint64_t *out1,
                          uint64_t n, uint64_t totals[2]);
-// What the first level of a scan reads: u64 values, u32 values (SCAN_U32_FLAGGED: 0xFFFFFFFF counts 0), or the fill of
-// slot i from its cursor, min(p[i] - i * stride, cap) (SCAN_SLOT_FILL)
-enum { SCAN_U64 = 0, SCAN_U32_FLAGGED = 1, SCAN_SLOT_FILL = 2 };
+// What the first level of a scan reads: u64 values, u32 values (SCAN_U32_FLAGGED: 0xFFFFFFFF counts 0), the fill of
+// slot i from its cursor, min(p[i] - i * stride, cap) (SCAN_SLOT_FILL), or the units of read i computed from its length
+// p[i] (SCAN_READ_UNITS: ceil(max(0, len - k + 1) / C) with k = stride and C = cap -- C = 1: k-mers, C = CH: chunks,
+// C = the segment length: super-k-mer segments).  A SCAN_READ_UNITS source with `woff` also checks the order of the
+// packed words in its reduce pass (in the one-workgroup scan when n fits a single tile and there is none): *unordered
+// is set when woff[i + 1] < woff[i] + ceil(len[i] / 32) for some read
+enum { SCAN_U64 = 0, SCAN_U32_FLAGGED = 1, SCAN_SLOT_FILL = 2, SCAN_READ_UNITS = 3 };
 struct ScanSrc {
     const void *p;
     uint32_t kind, stride, cap;
+    const uint64_t *woff = nullptr;
+    uint32_t *unordered = nullptr;
 };
 // The scan without its wait: narr (1 or 2) arrays are scanned into out[a] (u64), the totals are left in d_total[a] on
-// the device (tail: also in out[a][n]).  The scratch buffers go into `keep`, which must live until the caller has waited
-// for the stream.
+// the device (tail: also in out[a][n]).  out[a] == nullptr makes array a TOTAL-ONLY: its reduce pass still sums it, its
+// apply pass neither loads nor stores below the top level.  The scratch buffers go into `keep`, which must live until
+// the caller has waited for the stream.
 void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t *const *out, uint64_t n,
                             uint64_t *d_total, bool tail, std::vector<DevBuf> &keep);
 // extindex.hip: the prefix table over an ascending key array of n records (W words, k-mer size k) that table_find
@@ -367,6 +374,13 @@ void *plan_staging(bbk_ctx *ctx, size_t bytes);
 // Exported for the tests only (not declared in bbk.h): exclusive_scan2_u64 in place over two device arrays of n + 1 u64
 // each (entries 0..n-1 are the input, entry n receives the total); totals[2] on the host receives the two sums.
 extern "C" int bbk_scan2_u64(bbk_ctx *ctx, void *d_a, void *d_b, uint64_t n, uint64_t *totals);
+// ... and the read plan (msd.hip): the tile geometry of the counting paths at k, and the plan of a read set with the
+// descriptors of its tiles, copied to the host
+struct bbk_reads;
+extern "C" int bbk_read_plan_geometry(unsigned k, uint32_t *out);
+extern "C" int bbk_read_plan(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, unsigned tile, int superk,
+                             uint64_t *coff, uint64_t *totals, uint32_t *unordered, void *tiles, uint64_t tile_cap,
+                             uint64_t *n_tiles);
 
 struct bbk_reads {
     bbk_ctx *ctx = nullptr;
@@ -378,6 +392,23 @@ struct bbk_reads {
     const uint32_t *d_len = nullptr;   // n
     bbk::DevBuf own_words, own_woff, own_len;
 };
+
+namespace bbk {
+
+// What a pass over a read set needs before its first tile: the k-mers of the reads, their units of C k-mer positions
+// (chunks of the level-1 kernels, super-k-mer segments; C = 1: the k-mers themselves) and the exclusive scan of the
+// units per read.  One fused scan straight from the read lengths (SCAN_READ_UNITS: no per-read array is materialised,
+// the k-mers are a total-only array of the same launches) and ONE wait for both totals; coff[n] is written on the
+// device.  The tile descriptors of a caller are one launch of its tile kernel over coff once `units` has given the
+// tile count (kmer_ops.h: read_of_unit).
+struct ReadPlan {
+    DevBuf coff;                    // n + 1 entries: units before read i; coff[n] = units
+    uint64_t kmers = 0, units = 0;  // totals over the reads
+    // d_unordered: a zeroed device word, set when the packed words of the reads are not in read order (null: not asked)
+    void run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, uint32_t *d_unordered);
+};
+
+}  // namespace bbk
 
 struct bbk_kmerset {
     unsigned k = 0, W = 0;

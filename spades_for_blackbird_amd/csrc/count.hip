@@ -34,15 +34,6 @@ static bool msd_enabled() {
     return !(e && e[0] == '1');
 }
 
-__global__ void k_kmers_per_read(const uint32_t *__restrict__ len, uint64_t n, uint32_t k,
-                                 uint64_t *__restrict__ nk) {
-    const uint64_t i = BBK_GID();
-    if (i < n) {
-        const uint32_t L = len[i];
-        nk[i] = L >= k ? (uint64_t)(L - k + 1) : 0ull;
-    }
-}
-
 // One wavefront per read, lanes over k-mer positions: stores of one wave are 64 consecutive
 // records.  MODE 0: canonical key.  MODE 1: canonical key + InOutMask bits of this occurrence
 // (kmer_extension_index.hpp:67-69,92-106: a non-minimal k-mer stores position 7-pos).
@@ -237,9 +228,10 @@ void dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, bool with_mask, 
             return;
         }
     }
-    DevBuf koff((rd->n + 1) * sizeof(uint64_t));
-    if (rd->n) launch_items(ctx, "k_kmers_per_read", k_kmers_per_read, rd->n, rd->d_len, rd->n, k, koff.as<uint64_t>());
-    const uint64_t N = exclusive_scan_u64(ctx, koff.as<uint64_t>(), koff.as<uint64_t>(), rd->n);
+    ReadPlan rp;  // units of one k-mer: the scan of the k-mers per read, straight from the lengths
+    rp.run(ctx, rd, k, 1u, nullptr);
+    const DevBuf &koff = rp.coff;
+    const uint64_t N = rp.kmers;
     n_instances = N;
     if (N == 0) return empty_result(out_keys, &out_vals);
     BBK_REQUIRE(N < (1ull << 32), BBK_ERR_ARG,

@@ -190,6 +190,47 @@ __device__ inline uint64_t last_le(const uint64_t *__restrict__ off, uint64_t n,
     return lo;
 }
 
+// last_le(coff, n, c) over the scan of units per read (ReadPlan: coff[n] = units), without the search over all reads:
+// the read an even spread of the units would put unit c in, then a gallop of at most kReadGallop doublings to either
+// side until [lo, hi) brackets the answer (coff[lo] <= c, and hi == n or coff[hi] > c), then the bisection of that
+// bracket.  Where the gallop runs out the bracket is the rest of the array: the full search is the fallback.  Reads of
+// one length resolve in two loads.  The answer is last_le's by construction -- the LAST of equal entries, so a unit
+// belongs to the read behind any run of reads that have none -- and n - 1 for c >= units.
+constexpr int kReadGallop = 8;
+__device__ inline uint64_t read_of_unit(const uint64_t *__restrict__ coff, uint64_t n, uint64_t units, uint64_t c) {
+    if (c >= units) return n - 1;
+    uint64_t g = (uint64_t)((double)c * (double)n / (double)units);
+    if (g > n - 1) g = n - 1;
+    uint64_t lo = 0, hi = n;
+    if (coff[g] <= c) {
+        lo = g;
+        uint64_t d = 1;
+        for (int s = 0; s < kReadGallop && lo + d < n; ++s, d <<= 1) {
+            if (coff[lo + d] > c) {
+                hi = lo + d;
+                break;
+            }
+            lo += d;
+        }
+    } else {
+        hi = g;
+        uint64_t d = 1;
+        for (int s = 0; s < kReadGallop && hi > d; ++s, d <<= 1) {
+            if (coff[hi - d] <= c) {
+                lo = hi - d;
+                break;
+            }
+            hi -= d;
+        }
+    }
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (coff[mid] <= c) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // drop base 0, append c as base k-1 (RtSeq::operator<<=, rtseq.hpp:450-467)
 template <int W>
 __device__ inline Key<W> kmer_shl(const Key<W> &x, int k, uint32_t c) {

@@ -109,4 +109,12 @@ bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, const MsdRequest &rq, MsdOutput &
 bool superk_dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, DevBuf &out_keys, DevBuf &out_vals,
                         uint64_t &n_distinct, uint64_t &n_instances);
 
+// superk.hip, for the test export of the read plan (bbk_read_plan): the segment length the path uses at k (0: k is not
+// for it) and the segments of a level-1 tile; superk_plan_tiles is the path's own launch of its tile kernel (SkTile:
+// r0, nr, for the n_tiles tiles of `tile` segments over the ReadPlan's coff / n_segs, into `tiles`)
+uint32_t superk_segment_len(unsigned k);
+uint32_t superk_tile_segments();
+void superk_plan_tiles(bbk_ctx *ctx, const uint64_t *coff, uint64_t n_reads, uint64_t n_segs, uint32_t tile,
+                       uint64_t n_tiles, DevBuf &tiles);
+
 }  // namespace bbk

@@ -131,6 +131,16 @@ static void with_op(int op, F &&f) {
     }
 }
 
+// The one launch of k_tile_reads (level1_tiles, and the test export of the read plan): the n_a tiles of tile_a chunks
+// into out_a and, where n_b is not 0, the n_b tiles of tile_b chunks into out_b, over the ReadPlan's coff / n_chunks
+static void launch_tile_reads(bbk_ctx *ctx, const bbk_reads *rd, const uint64_t *coff, uint64_t n_chunks, uint64_t n_a,
+                              uint32_t tile_a, RdTile *out_a, uint64_t n_b, uint32_t tile_b, RdTile *out_b, uint32_t ch,
+                              uint32_t k, const uint32_t *unordered) {
+    if (n_a + n_b == 0) return;
+    launch_items(ctx, "k_tile_reads", k_tile_reads, n_a + n_b, coff, rd->d_woff, rd->d_len, rd->n, n_chunks, n_a, tile_a,
+                 out_a, n_b, tile_b, out_b, ch, k, (uint32_t)kRdSlots, (uint32_t)kRdWords, unordered);
+}
+
 template <int W>
 struct MsdRunner {
     static constexpr size_t rec = (size_t)W * 8;
@@ -514,17 +524,12 @@ struct MsdRunner {
             if (!from_reads) return;
             const bbk_reads *rd = in.rd;
             BBK_REQUIRE(R.dmode == MSD_HASH, BBK_ERR_INTERNAL, "reads are partitioned by hash prefix only");
-            DevBuf nk((rd->n + 1) * sizeof(uint64_t));
-            coff.alloc((rd->n + 1) * sizeof(uint64_t));
-            if (rd->n)
-                R.launch_plan(k_kmers_per_read2, "k_kmers_per_read2", rd->n, rd->d_len, rd->d_woff, rd->n, R.k,
-                              (uint32_t)RdCfg<W>::CH, nk.as<uint64_t>(), coff.as<uint64_t>(), ctl_at(kCtlUnordered));
-            // both scans in the same launches, both totals in one wait; coff[n] = n_chunks is written by the scan
-            uint64_t tot[2] = {0, 0};
-            exclusive_scan2_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n,
-                                tot);
-            N = tot[0];
-            n_chunks = tot[1];
+            // one fused scan over the read lengths, both totals in one wait; coff[n] = n_chunks is written by the scan
+            ReadPlan rp;
+            rp.run(ctx, rd, R.k, (unsigned)RdCfg<W>::CH, ctl_at(kCtlUnordered));
+            coff = std::move(rp.coff);
+            N = rp.kmers;
+            n_chunks = rp.units;
         }
 
         // ---- level-1 tiles (reads) and the slot layout
@@ -532,14 +537,14 @@ struct MsdRunner {
             L1 = PartLevel{1, P.b1, P.nb1, R.dmode, R.w0bits(), nullptr, nullptr, sel.lo, sel.span, sel.shl, sel.mul};
             if (from_reads) {
                 const bbk_reads *rd = in.rd;
+                // (the histogram tiling is read by the exact mode alone: slot mode has no histogram pass)
+                const uint64_t nth = P.slots ? 0 : P.ntiles1h;
                 tile_read.alloc(((size_t)P.ntiles1 + 1) * sizeof(RdTile));
-                tiles_h.alloc(((size_t)P.ntiles1h + 1) * sizeof(RdTile));
+                tiles_h.alloc(((size_t)nth + 1) * sizeof(RdTile));
                 if (P.ntiles1)
-                    R.launch_plan(k_tile_reads, "k_tile_reads", (uint64_t)P.ntiles1 + P.ntiles1h, coff.as<uint64_t>(),
-                                  rd->d_woff, rd->d_len, rd->n, (uint64_t)P.ntiles1, P.rd_tile, tile_read.as<RdTile>(),
-                                  (uint64_t)P.ntiles1h, (uint32_t)kRdHistThreads, tiles_h.as<RdTile>(),
-                                  (uint32_t)RdCfg<W>::CH, R.k, (uint32_t)kRdSlots, (uint32_t)kRdWords,
-                                  ctl_at(kCtlUnordered));
+                    launch_tile_reads(ctx, rd, coff.as<uint64_t>(), n_chunks, P.ntiles1, P.rd_tile, tile_read.as<RdTile>(),
+                                      nth, (uint32_t)kRdHistThreads, tiles_h.as<RdTile>(), (uint32_t)RdCfg<W>::CH, R.k,
+                                      ctl_at(kCtlUnordered));
                 S = ReadSrc{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tile_read.as<RdTile>(), rd->n,
                             n_chunks, (int)R.k};
                 Sh = S;
@@ -1802,3 +1807,55 @@ bool msd_sort_reduce(bbk_ctx *ctx, unsigned k, const MsdRequest &rq, MsdOutput &
 }
 
 }  // namespace bbk
+
+// Exported for the tests only (not declared in bbk.h).  out[10]: chunk length CH of the level-1 kernels at k, chunks of
+// a scatter tile, of a histogram tile, of a narrow tile without / with payload, the super-k-mer segment length at k
+// (0: not for that path), segments of a super-k-mer tile, reads and packed words a tile may stage in LDS, 0
+extern "C" int bbk_read_plan_geometry(unsigned k, uint32_t *out) {
+    return bbk::guarded([&] {
+        BBK_REQUIRE(out && k >= 1, BBK_ERR_ARG, "bbk_read_plan_geometry: bad argument");
+        uint32_t ch = 0;
+        bbk::dispatch_w(bbk::words_of(k), [&](auto w) { ch = (uint32_t)bbk::RdCfg<decltype(w)::value>::CH; });
+        const uint32_t g[10] = {ch, (uint32_t)bbk::kRdThreads, (uint32_t)bbk::kRdHistThreads,
+                                (uint32_t)bbk::NwCfg<false>::CHUNKS, (uint32_t)bbk::NwCfg<true>::CHUNKS,
+                                bbk::superk_segment_len(k), bbk::superk_tile_segments(), (uint32_t)bbk::kRdSlots,
+                                (uint32_t)bbk::kRdWords, 0u};
+        for (int i = 0; i < 10; ++i) out[i] = g[i];
+    });
+}
+
+// The ReadPlan of `rd` for k-mers of k in units of C, and its tiles of `tile` units: coff (n + 1 values), totals[2] =
+// {k-mers, units}, the unordered flag and the descriptors of the ceil(units / tile) tiles (superk = 0: RdTile of the
+// level-1 kernels, 24 bytes each; 1: SkTile, 8 bytes) go to the host; tile_cap: tiles the caller's buffer holds
+extern "C" int bbk_read_plan(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, unsigned tile, int superk,
+                             uint64_t *coff, uint64_t *totals, uint32_t *unordered, void *tiles, uint64_t tile_cap,
+                             uint64_t *n_tiles) {
+    using namespace bbk;
+    return guarded([&] {
+        BBK_REQUIRE(ctx && rd && coff && totals && unordered && tiles && n_tiles && k >= 1 && C >= 1 && tile >= 1, BBK_ERR_ARG,
+                    "bbk_read_plan: bad argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        DevBuf flag(16), td;
+        BBK_HIP(hipMemsetAsync(flag.p, 0, 16, ctx->stream));
+        ReadPlan rp;
+        rp.run(ctx, rd, k, C, flag.as<uint32_t>());
+        const uint64_t nt = (rp.units + tile - 1) / tile;
+        BBK_REQUIRE(nt <= tile_cap, BBK_ERR_ARG, "bbk_read_plan: %llu tiles, room for %llu", (unsigned long long)nt,
+                    (unsigned long long)tile_cap);
+        size_t tile_bytes = sizeof(RdTile);
+        if (superk) {
+            superk_plan_tiles(ctx, rp.coff.as<uint64_t>(), rd->n, rp.units, tile, nt, td);
+            tile_bytes = 8;
+        } else {
+            td.alloc((size_t)(nt + 1) * sizeof(RdTile));
+            launch_tile_reads(ctx, rd, rp.coff.as<uint64_t>(), rp.units, nt, (uint32_t)tile, td.as<RdTile>(), 0, (uint32_t)tile,
+                              td.as<RdTile>(), (uint32_t)C, (uint32_t)k, flag.as<uint32_t>());
+        }
+        totals[0] = rp.kmers;
+        totals[1] = rp.units;
+        *n_tiles = nt;
+        d2h_sync(ctx, coff, rp.coff.p, (size_t)(rd->n + 1) * sizeof(uint64_t));
+        d2h_sync(ctx, unordered, flag.p, sizeof(uint32_t));
+        if (nt) d2h_sync(ctx, tiles, td.p, (size_t)nt * tile_bytes);
+    });
+}

@@ -134,10 +134,12 @@ struct RdTile {
 // one thread per tile of `tile` chunks (a chunk = ch k-mer positions of one read).  Two tilings of the same reads in
 // one launch: threads [0, n_tiles) describe the tiles of `tile` chunks into out, the next n_tiles_b threads those of
 // tile_b chunks into out_b (the scatter and the histogram kernels of level 1 have different workgroup sizes).
+// coff is the ReadPlan's scan (n_chunks = coff[n_reads]); *unordered is its flag: set when the packed words of the reads
+// do not lie one after the other in read order (then no tile stages its window of words in LDS).
 __global__ void k_tile_reads(const uint64_t *__restrict__ coff, const uint64_t *__restrict__ woff,
-                             const uint32_t *__restrict__ len, uint64_t n_reads, uint64_t n_tiles, uint32_t tile,
-                             RdTile *__restrict__ out, uint64_t n_tiles_b, uint32_t tile_b, RdTile *__restrict__ out_b,
-                             uint32_t ch, uint32_t k, uint32_t max_reads, uint32_t max_words,
+                             const uint32_t *__restrict__ len, uint64_t n_reads, uint64_t n_chunks, uint64_t n_tiles,
+                             uint32_t tile, RdTile *__restrict__ out, uint64_t n_tiles_b, uint32_t tile_b,
+                             RdTile *__restrict__ out_b, uint32_t ch, uint32_t k, uint32_t max_reads, uint32_t max_words,
                              const uint32_t *__restrict__ unordered) {
     uint64_t t = BBK_GID();
     if (t >= n_tiles) {
@@ -147,7 +149,7 @@ __global__ void k_tile_reads(const uint64_t *__restrict__ coff, const uint64_t *
         out = out_b;
     }
     const uint64_t c0 = t * (uint64_t)tile;
-    const uint64_t r0 = last_le(coff, n_reads, c0), r1 = last_le(coff, n_reads, c0 + tile);
+    const uint64_t r0 = read_of_unit(coff, n_reads, n_chunks, c0), r1 = read_of_unit(coff, n_reads, n_chunks, c0 + tile);
     // staged word window: from the word of the first base this tile touches in r0 (one base before the chunk,
     // for the incoming-edge bit) to the last word it can touch in r1
     const uint32_t p0 = (uint32_t)(c0 - coff[r0]) * ch;
@@ -166,21 +168,6 @@ __global__ void k_tile_reads(const uint64_t *__restrict__ coff, const uint64_t *
     T.wspan = fast ? (uint32_t)(wend - wbase) : 0xFFFFFFFFu;
     T.pad = 0;
     out[t] = T;
-}
-
-// k-mers and chunks (of ch k-mer positions) of every read; *unordered is set when the packed words of the reads do not
-// lie one after the other in read order (then no tile stages its window of words in LDS: k_tile_reads)
-__global__ void k_kmers_per_read2(const uint32_t *__restrict__ len, const uint64_t *__restrict__ woff, uint64_t n,
-                                  uint32_t k, uint32_t ch, uint64_t *__restrict__ nk, uint64_t *__restrict__ nch,
-                                  uint32_t *__restrict__ unordered) {
-    const uint64_t i = BBK_GID();
-    if (i < n) {
-        const uint32_t L = len[i];
-        const uint64_t c = L >= k ? (uint64_t)(L - k + 1) : 0ull;
-        nk[i] = c;
-        nch[i] = (c + ch - 1) / ch;
-        if (i + 1 < n && woff[i + 1] < woff[i] + ((L + 31u) >> 5)) *unordered = 1u;
-    }
 }
 
 // Tile -> (segment, range).  Level 1: tile t covers records [t*TILE, ...).  Level 2: tiles never

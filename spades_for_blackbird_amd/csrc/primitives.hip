@@ -580,8 +580,23 @@ __device__ inline uint64_t scan_load(const ScanSrc &s, uint64_t i) {
     if (s.kind == SCAN_U64) return reinterpret_cast<const uint64_t *>(s.p)[i];
     const uint32_t v = reinterpret_cast<const uint32_t *>(s.p)[i];
     if (s.kind == SCAN_U32_FLAGGED) return v == 0xFFFFFFFFu ? 0ull : (uint64_t)v;
+    if (s.kind == SCAN_READ_UNITS) {  // v = len: k-mers, in units of cap
+        const uint32_t c = v >= s.stride ? v - s.stride + 1u : 0u;
+        if (c == 0u) return 0ull;
+        // (a uniform choice: the unit lengths in use are powers of two)
+        const uint32_t q = (s.cap & (s.cap - 1u)) ? (c - 1u) / s.cap : (c - 1u) >> (__ffs(s.cap) - 1);
+        return (uint64_t)q + 1ull;
+    }
     const uint32_t c = v - (uint32_t)i * s.stride;  // SCAN_SLOT_FILL
     return c < s.cap ? c : s.cap;
+}
+
+// SCAN_READ_UNITS with woff: do the words of read i + 1 start before those of read i end?
+// (the callers store the flag once, behind their loop: a store between the loads of two items would make every item
+// wait for its own loads)
+__device__ inline bool scan_out_of_order(const ScanSrc &s, uint64_t i, uint64_t n) {
+    const uint32_t L = reinterpret_cast<const uint32_t *>(s.p)[i];
+    return i + 1 < n && s.woff[i + 1] < s.woff[i] + ((L + 31u) >> 5);
 }
 
 template <int NA>
@@ -591,11 +606,17 @@ __global__ __launch_bounds__(kThreads) void k_scan_reduce(ScanArrs A, uint64_t n
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
         uint64_t s = 0;
+        const bool check = A.src[a].kind == SCAN_READ_UNITS && A.src[a].woff;
+        bool bad = false;
 #pragma unroll
         for (int i = 0; i < kScanItems; ++i) {
             const uint64_t idx = base + (uint64_t)i * kThreads + threadIdx.x;
-            if (idx < n) s += scan_load(A.src[a], idx);
+            if (idx < n) {
+                s += scan_load(A.src[a], idx);
+                if (check) bad |= scan_out_of_order(A.src[a], idx, n);
+            }
         }
+        if (bad) *A.src[a].unordered = 1u;
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) s += __shfl_down(s, d, 64);
         if ((threadIdx.x & 63) == 0) sm[a][threadIdx.x >> 6] = s;
@@ -617,13 +638,20 @@ __global__ __launch_bounds__(kThreads) void k_scan_apply(ScanArrs A, uint64_t n)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int a = 0; a < NA; ++a) {
+        const bool store = A.out[a] != nullptr;  // (uniform) total-only arrays matter at the top level alone
+        if (!TOP && !store) continue;
         uint64_t v[kScanItems];
         uint64_t s = 0;
+        // (a read source at the top level: n fits one tile and no reduce pass has looked at the word order)
+        const bool check = TOP && A.src[a].kind == SCAN_READ_UNITS && A.src[a].woff;
+        bool bad = false;
 #pragma unroll
         for (int i = 0; i < kScanItems; ++i) {
             v[i] = (base + i < n) ? scan_load(A.src[a], base + i) : 0;
             s += v[i];
+            if (check && base + i < n) bad |= scan_out_of_order(A.src[a], base + i, n);
         }
+        if (bad) *A.src[a].unordered = 1u;
         uint64_t incl = s;
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {
@@ -637,7 +665,7 @@ __global__ __launch_bounds__(kThreads) void k_scan_apply(ScanArrs A, uint64_t n)
         uint64_t run = (TOP ? 0ull : A.bsum[a][blockIdx.x]) + wbase + incl - s;
 #pragma unroll
         for (int i = 0; i < kScanItems; ++i) {
-            if (base + i < n) A.out[a][base + i] = run;
+            if (store && base + i < n) A.out[a][base + i] = run;
             run += v[i];
         }
         if (TOP && threadIdx.x == kThreads - 1) {  // run = the sum of everything
@@ -681,7 +709,7 @@ void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t
         A.src[a] = src[a];
         A.out[a] = out[a];
         A.total[a] = d_total + a;
-        A.tail[a] = tail ? out[a] + n : nullptr;
+        A.tail[a] = (tail && out[a]) ? out[a] + n : nullptr;
     }
     if (narr == 1) scan_level<1>(ctx, A, n, keep);
     else scan_level<2>(ctx, A, n, keep);
@@ -710,6 +738,26 @@ void exclusive_scan2_u64(bbk_ctx *ctx, const uint64_t *in0, uint64_t *out0, cons
     exclusive_scan_enqueue(ctx, 2, src, out, n, dt.as<uint64_t>(), true, keep);
     BBK_HIP(hipMemcpyAsync(totals, dt.p, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     stream_wait(ctx);
+}
+
+void ReadPlan::run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, uint32_t *d_unordered) {
+    BBK_REQUIRE(k >= 1 && C >= 1, BBK_ERR_INTERNAL, "read plan: k = %u, C = %u", k, C);
+    const uint64_t n = rd->n;
+    coff.alloc((n + 1) * sizeof(uint64_t));
+    std::vector<DevBuf> keep;
+    keep.reserve(4);
+    DevBuf dt(16);
+    // [0] the k-mers (total only), [1] the units; at C = 1 they are the same array
+    const ScanSrc src[2] = {{rd->d_len, SCAN_READ_UNITS, k, 1u},
+                            {rd->d_len, SCAN_READ_UNITS, k, C, d_unordered ? rd->d_woff : nullptr, d_unordered}};
+    uint64_t *const out[2] = {nullptr, coff.as<uint64_t>()};
+    const int first = C == 1 ? 1 : 0;
+    exclusive_scan_enqueue(ctx, 2 - first, src + first, out + first, n, dt.as<uint64_t>(), true, keep);
+    uint64_t tot[2] = {0, 0};
+    BBK_HIP(hipMemcpyAsync(tot, dt.p, (2 - first) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    stream_wait(ctx);
+    kmers = tot[0];
+    units = tot[1 - first];
 }
 
 size_t device_free_cached(bbk_ctx *ctx) {

@@ -193,24 +193,15 @@ __device__ inline uint64_t sk_read_at(const uint64_t *__restrict__ off, uint64_t
     return lo;
 }
 
-__global__ void k_sk_segments(const uint32_t *__restrict__ len, uint64_t n, uint32_t k, uint32_t C,
-                              uint64_t *__restrict__ nk, uint64_t *__restrict__ nseg) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const uint32_t L = len[i];
-        const uint64_t c = L >= k ? (uint64_t)(L - k + 1) : 0ull;
-        nk[i] = c;
-        nseg[i] = (c + C - 1) / C;
-    }
-}
-
+// one thread per level-1 tile of `tile` segments: the reads that own them (coff: the ReadPlan's scan of segments per
+// read)
 __global__ void k_sk_tiles(const uint64_t *__restrict__ coff, uint64_t n_reads, uint64_t n_tiles, uint32_t tile,
                            uint64_t n_segs, SkTile *__restrict__ out) {
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const uint64_t t = BBK_GID();
     if (t >= n_tiles) return;
     const uint64_t c0 = t * (uint64_t)tile;
     const uint64_t c1 = (c0 + tile < n_segs ? c0 + tile : n_segs) - 1;
-    const uint64_t r0 = sk_read_at(coff, 0, n_reads, c0), r1 = sk_read_at(coff, 0, n_reads, c1);
+    const uint64_t r0 = read_of_unit(coff, n_reads, n_segs, c0), r1 = read_of_unit(coff, n_reads, n_segs, c1);
     out[t] = SkTile{(uint32_t)r0, (uint32_t)(r1 - r0 + 1)};
 }
 
@@ -1115,27 +1106,20 @@ struct SuperkRun {
 
     // ---- k-mers (N) and segments of C k-mers (n_segs) of the reads; coff: exclusive scan of the segments per read
     void count_segments(uint32_t C) {
-        DevBuf nk((rd->n + 1) * sizeof(uint64_t));
-        coff.alloc((rd->n + 1) * sizeof(uint64_t));
-        hipLaunchKernelGGL(k_sk_segments, dim3((unsigned)((rd->n + 255) / 256)), dim3(256), 0, ctx->stream, rd->d_len, rd->n,
-                           k, C, nk.as<uint64_t>(), coff.as<uint64_t>());
-        check_launch("k_sk_segments");
-        N = exclusive_scan_u64(ctx, nk.as<uint64_t>(), nk.as<uint64_t>(), rd->n);
-        n_segs = exclusive_scan_u64(ctx, coff.as<uint64_t>(), coff.as<uint64_t>(), rd->n);
+        ReadPlan rp;
+        rp.run(ctx, rd, k, C, nullptr);  // one wait; coff[n] = n_segs stays on the device
+        coff = std::move(rp.coff);
+        N = rp.kmers;
+        n_segs = rp.units;
     }
 
     // ---- level-1 tiles and the buffers of the passes
     void setup() {
-        BBK_HIP(hipMemcpyAsync(coff.as<uint64_t>() + rd->n, &n_segs, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-        sync();
         if (kn.verbose)
             fprintf(stderr,
                     "[bbk] superk: k=%u m=%u w=%u C=%u segs=%llu est_records=%.0f passes=%u P1=%u P2=%u slot1=%u lds1=%zu fill=%.2f\n",
                     k, P.m, P.w, P.C, (unsigned long long)n_segs, L.est_total, P.np, P.P1, P.P2, P.slot1, L.sm1, L.fill);
-        tiles.alloc((size_t)(L.ntiles1 + 1) * sizeof(SkTile));
-        hipLaunchKernelGGL(k_sk_tiles, dim3((unsigned)((L.ntiles1 + 255) / 256)), dim3(256), 0, ctx->stream,
-                           coff.as<uint64_t>(), rd->n, L.ntiles1, (uint32_t)kSk1NT, n_segs, tiles.as<SkTile>());
-        check_launch("k_sk_tiles");
+        superk_plan_tiles(ctx, coff.as<uint64_t>(), rd->n, n_segs, (uint32_t)kSk1NT, L.ntiles1, tiles);
         S = SkReads{rd->d_words, rd->d_woff, rd->d_len, coff.as<uint64_t>(), tiles.as<SkTile>(), rd->n, n_segs};
         if (kn.verbose) {
             sync();
@@ -1396,6 +1380,24 @@ bool superk_dedup_reads(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, int op, D
     if (W == 3) return run(std::integral_constant<int, 3>());
     if (W == 4) return run(std::integral_constant<int, 4>());
     return false;
+}
+
+uint32_t superk_segment_len(unsigned k) {
+    const SuperkKnobs kn;
+    switch (words_of(k)) {
+        case 2: return sk_geometry<2>(k, kn).C;
+        case 3: return sk_geometry<3>(k, kn).C;
+        case 4: return sk_geometry<4>(k, kn).C;
+        default: return 0;
+    }
+}
+
+uint32_t superk_tile_segments() { return (uint32_t)kSk1NT; }
+
+void superk_plan_tiles(bbk_ctx *ctx, const uint64_t *coff, uint64_t n_reads, uint64_t n_segs, uint32_t tile,
+                       uint64_t n_tiles, DevBuf &tiles) {
+    tiles.alloc((size_t)(n_tiles + 1) * sizeof(SkTile));
+    if (n_tiles) launch_items(ctx, "k_sk_tiles", k_sk_tiles, n_tiles, coff, n_reads, n_tiles, tile, n_segs, tiles.as<SkTile>());
 }
 
 }  // namespace bbk
