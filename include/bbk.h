@@ -549,6 +549,46 @@ int bbk_subclusters_export(bbk_ctx *ctx, const bbk_subclusters *s, uint8_t *h_go
 int bbk_subclusters_write(bbk_ctx *ctx, const bbk_subclusters *s, const bbk_kmerstats *ks, const char *prefix);
 void bbk_subclusters_free(bbk_subclusters *s);
 
+/* ---- expansion of the solid k-mers: replaces Expander::operator() (projects/hammer/expander.cpp:20-70) and the loop
+ *      around it (projects/hammer/main.cpp:194-222) -- every read that is covered end to end by good k-mers makes all of
+ *      its k-mers good, again and again until little changes; what is left is the kmer.index3 ReadCorrector reads -------- */
+typedef struct bbk_expander bbk_expander; /* good bits of a set, two generations, in HBM */
+/* set: as for bbk_kmerstats_begin (ascending BBK_BOTH_STRANDS, k <= 32, fewer than 2^32 - 2 k-mers); it must outlive the
+ * expander, and the lookup index over it is built here, once.  The bits of the first n k-mers of `sc` (the new k-mers
+ * are never found from a read: KMerData::checking_seq_idx, kmer_data.hpp), or h_good: n bytes, 0 or 1.
+ * BBK_ERR_ARG: a set the stage refuses, subclusters of another n or k, a byte other than 0 or 1. */
+int bbk_expander_from_subclusters(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_subclusters *sc, bbk_expander **out);
+int bbk_expander_from_host(bbk_ctx *ctx, const bbk_kmerset *set, const uint8_t *h_good, bbk_expander **out);
+/* One iteration of main.cpp:198-221 as a SNAPSHOT ROUND: every read pushed between round_begin and
+ * round_end is judged against the bits G_r the round began with, and the marks go to the next generation.  A read of sz
+ * bases (one run of ACGT: the caller pushes the reads that can ever be solid, trimmed -- host/hammer_reads.hpp
+ * expander_candidate; sz < k: ignored, expander.cpp:27-28) has the starts 0 .. nk - 1, nk = sz - k + 1.  It is solid when
+ * start 0 and start nk - 1 are in the set and good in G_r and no two consecutive good starts are more than k apart
+ * (covered_by_solid all true, :30-51); only the forward k-mer is looked up (:36), and a start whose k-mer is not in the
+ * set neither covers nor is marked (:37,54-55).  G_{r+1} = G_r with every k-mer, present in the set, of every solid read
+ * (:53-67); *changed = |G_{r+1} \ G_r|, distinct k-mers (changed_ of one thread, :59-61).  Unlike the reference, where a
+ * mark is seen by the reads after it in thread-timing order, the result is the same bytes for any order and batching
+ * of the reads; the reference's state after t passes of one thread lies between G_t and the closure, which both reach.
+ * h_status (n_reads bytes, or NULL): 0 not solid, 1 solid, 2 every start already good.  push does not wait for the
+ * device unless h_status is given, so the reads must stay alive until round_end, which waits once, or a
+ * bbk_ctx_synchronize.
+ * BBK_ERR_ARG: push or round_end outside a round, round_begin inside one. */
+int bbk_expander_round_begin(bbk_expander *e);
+int bbk_expander_push(bbk_expander *e, const bbk_reads *reads, uint8_t *h_status /* n_reads bytes or NULL */);
+int bbk_expander_round_end(bbk_expander *e, uint64_t *changed);
+/* reads resident: rounds until changed < min_changed or max_rounds (expand_max_iterations 25 and the 10 of
+ * main.cpp:219); *rounds: how many ran; h_changed: max_rounds entries or NULL, the first *rounds are written.  One host
+ * wait per round.  BBK_ERR_ARG: max_rounds 0, a round is open. */
+int bbk_expander_run(bbk_expander *e, const bbk_reads *reads, unsigned max_rounds, uint64_t min_changed,
+                     unsigned *rounds, uint64_t *h_changed);
+uint64_t bbk_expander_good(const bbk_expander *e); /* good k-mers now (at the start of the open round) */
+int bbk_expander_export(bbk_ctx *ctx, const bbk_expander *e, uint8_t *h_good); /* n bytes */
+/* the n bits back into sc (KMerData is one object: Expander marks the KMerStat the subclustering wrote): afterwards
+ * bbk_subclusters_export / _write give the expanded bits for the first n k-mers; the bits of the new k-mers and every
+ * other field are untouched.  BBK_ERR_ARG: subclusters of another n or k, a round is open. */
+int bbk_expander_store(bbk_expander *e, bbk_subclusters *sc);
+void bbk_expander_free(bbk_expander *e);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

@@ -1,5 +1,6 @@
-// hammer.h -- what hamclust.hip, kmerstat.hip and subclust.hip (the BayesHammer stage) share.  Host code
-// only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit through it.
+// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip and expand.hip (the BayesHammer stage)
+// share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation
+// unit through it.
 #pragma once
 
 #include <algorithm>
@@ -29,6 +30,18 @@ struct bbk_kmerstats {
     bbk::DevBuf count;       // n u32            \.
     bbk::DevBuf total_qual;  // n f32             > written by finish
     bbk::DevBuf qual;        // n * qual_words u64 /
+};
+
+struct bbk_subclusters {
+    unsigned k = 0;
+    uint64_t n = 0, clusters = 0, subs = 0, listed = 0, new_kmers = 0, host_kmers = 0;
+    bbk::DevBuf good;         // n + new_kmers u8
+    bbk::DevBuf members;      // listed u64: subcluster by subcluster, the center first; a new k-mer is n + j
+    bbk::DevBuf sizes;        // subs u64
+    bbk::DevBuf per_cluster;  // clusters u64
+    bbk::DevBuf new_keys;     // new_kmers u64
+    bbk::DevBuf bic;          // clusters double
+    uint64_t errs[16] = {0}, stats[9] = {0};
 };
 
 namespace bbk {

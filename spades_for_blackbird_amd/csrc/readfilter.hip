@@ -52,8 +52,8 @@ template <int W>
 static void median_filter_impl(bbk_ctx *ctx, const bbk_reads *rd, const bbk_kmerset *s, uint32_t threshold, uint8_t *d_keep) {
     PrefixIndex prefix;
     prefix.build(ctx, s->keys.as<uint64_t>(), s->W, s->k, s->n);
-    launch_items(ctx, "k_median_filter", k_median_filter<W>, rd->n * 64, rd->d_words, rd->d_woff, rd->d_len, rd->n,
-                 (int)s->k, s->keys.as<Key<W>>(), s->counts.as<uint32_t>(), prefix.table(), threshold, d_keep);
+    launch_items_timed(ctx, "k_median_filter", k_median_filter<W>, rd->n * 64, rd->d_words, rd->d_woff, rd->d_len, rd->n,
+                       (int)s->k, s->keys.as<Key<W>>(), s->counts.as<uint32_t>(), prefix.table(), threshold, d_keep);
     BBK_HIP(hipStreamSynchronize(ctx->stream));
 }
 

@@ -35,18 +35,6 @@
 
 #pragma clang fp contract(off)
 
-struct bbk_subclusters {
-    unsigned k = 0;
-    uint64_t n = 0, clusters = 0, subs = 0, listed = 0, new_kmers = 0, host_kmers = 0;
-    bbk::DevBuf good;         // n + new_kmers u8
-    bbk::DevBuf members;      // listed u64: subcluster by subcluster, the center first; a new k-mer is n + j
-    bbk::DevBuf sizes;        // subs u64
-    bbk::DevBuf per_cluster;  // clusters u64
-    bbk::DevBuf new_keys;     // new_kmers u64
-    bbk::DevBuf bic;          // clusters double
-    uint64_t errs[16] = {0}, stats[9] = {0};
-};
-
 namespace bbk {
 
 constexpr uint32_t kScNew = 0xFFFFFFFFu;  // a new k-mer in a slab (indices stay below 2^32 - 2)

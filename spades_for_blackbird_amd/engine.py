@@ -45,6 +45,9 @@ SYMBOLS = [
     "bbk_kmerstats_load", "bbk_hamclusters_load", "bbk_hamclusters_subcluster", "bbk_subclusters_count",
     "bbk_subclusters_size", "bbk_subclusters_new_kmers", "bbk_subclusters_host_kmers", "bbk_subclusters_export",
     "bbk_subclusters_write", "bbk_subclusters_free",
+    "bbk_expander_from_subclusters", "bbk_expander_from_host", "bbk_expander_round_begin", "bbk_expander_push",
+    "bbk_expander_round_end", "bbk_expander_run", "bbk_expander_good", "bbk_expander_export", "bbk_expander_store",
+    "bbk_expander_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -258,6 +261,18 @@ def load_library():
     L.bbk_subclusters_write.argtypes = [vp, vp, vp, C.c_char_p]
     L.bbk_subclusters_free.argtypes = [vp]
     L.bbk_subclusters_free.restype = None
+    L.bbk_expander_from_subclusters.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.bbk_expander_from_host.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.bbk_expander_round_begin.argtypes = [vp]
+    L.bbk_expander_push.argtypes = [vp, vp, vp]
+    L.bbk_expander_round_end.argtypes = [vp, C.POINTER(u64)]
+    L.bbk_expander_run.argtypes = [vp, vp, C.c_uint, u64, C.POINTER(C.c_uint), vp]
+    L.bbk_expander_good.restype = u64
+    L.bbk_expander_good.argtypes = [vp]
+    L.bbk_expander_export.argtypes = [vp, vp, vp]
+    L.bbk_expander_store.argtypes = [vp, vp]
+    L.bbk_expander_free.argtypes = [vp]
+    L.bbk_expander_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -660,6 +675,18 @@ class KMerSet(_Handle):
         ks._set, ks.k = self, self.k
         return ks
 
+    def expander(self, good):
+        """Expander over this ascending both-strand set (k <= 32) from the good bit of every k-mer: `good` is one byte
+        per k-mer, 0 or 1.  The set must outlive it."""
+        good = np.ascontiguousarray(good, dtype=np.uint8)
+        if good.shape != (len(self),):
+            raise ValueError("one good byte per k-mer of the set: %d, not %r" % (len(self), good.shape))
+        h = C.c_void_p()
+        _check(self._L.bbk_expander_from_host(self.ctx._h, self._h, _ptr(good), C.byref(h)))
+        e = Expander(self.ctx, h)
+        e._set = self
+        return e
+
 
 KmerSet = KMerSet
 
@@ -806,6 +833,60 @@ class SubClusters(_Handle):
     def write(self, prefix):
         """<prefix>.kmstat (good bits set, new k-mers appended), .subclusters, .subclusters.idx, .newkmers"""
         _check(self._L.bbk_subclusters_write(self.ctx._h, self._h, self._stats_of._h, str(prefix).encode()))
+
+    def expander(self):
+        """Expander over the set these subclusters were made for, from their good bits"""
+        kmer_set = self._stats_of._set
+        h = C.c_void_p()
+        _check(self._L.bbk_expander_from_subclusters(self.ctx._h, kmer_set._h, self._h, C.byref(h)))
+        e = Expander(self.ctx, h)
+        e._set = kmer_set
+        return e
+
+
+class Expander(_Handle):
+    """BayesHammer's expansion of the solid k-mers in snapshot rounds (bbk_expander_*): a read that good k-mers cover end to
+    end makes all of its k-mers good.  The reads are the candidates of host/hammer_reads.hpp, one trimmed read each."""
+    _free = "bbk_expander_free"
+
+    def begin_round(self):
+        _check(self._L.bbk_expander_round_begin(self._h))
+
+    def push(self, reads, status=False):
+        """the reads of a round, in any order and batching; status=True: np.uint8[len(reads)], 0 not solid, 1 solid,
+        2 every start already good (and the call waits for the device).  Keep the reads until end_round."""
+        st = np.zeros(len(reads), dtype=np.uint8) if status else None
+        _check(self._L.bbk_expander_push(self._h, reads._h, _ptr(st)))
+        return st
+
+    def end_round(self):
+        """the k-mers the round made good"""
+        c = C.c_uint64()
+        _check(self._L.bbk_expander_round_end(self._h, C.byref(c)))
+        return int(c.value)
+
+    def run(self, reads, max_rounds=25, min_changed=10):
+        """rounds over resident reads until one adds fewer than min_changed k-mers or max_rounds have run (the
+        reference's expand_max_iterations 25 and 10): the list of the rounds' counts"""
+        n = C.c_uint(0)
+        counts = np.zeros(max(int(max_rounds), 1), dtype=np.uint64)
+        _check(self._L.bbk_expander_run(self._h, reads._h, max_rounds, min_changed, C.byref(n), _ptr(counts)))
+        return [int(x) for x in counts[:n.value]]
+
+    @property
+    def good(self):
+        """good k-mers now"""
+        return int(self._L.bbk_expander_good(self._h))
+
+    def export(self):
+        """np.uint8[n]: the good bit of every k-mer of the set"""
+        a = np.zeros(len(self._set), dtype=np.uint8)
+        _check(self._L.bbk_expander_export(self.ctx._h, self._h, _ptr(a)))
+        return a
+
+    def store(self, subclusters):
+        """the bits back into the subclusters (their first n k-mers): SubClusters.export() / write() then carry them"""
+        _check(self._L.bbk_expander_store(self._h, subclusters._h))
 
 
 class Counter:

@@ -7,6 +7,10 @@
 // Consecutive valid starts a..b are handed out as one stretch [a, b + k) of the read: a stretch holds no character other
 // than ACGT (every window the generator yields is checked base by base), and its k-mer positions are exactly the valid
 // starts a..b -- so one stretch is one read of the engine, for bbk_count_push_* and bbk_kmerstats_push alike.
+//   Expander::operator()                        projects/hammer/expander.cpp:20-51
+// A read can pass the Expander's coverage test only when the windows the generator yields cover the whole trimmed read
+// [0, sz): every window is free of non-ACGT, and a start is skipped only in the search branch, which a non-nucleotide
+// enters -- so the read is ONE stretch that is the trimmed read itself (expander_candidate).
 #pragma once
 
 #include <cstdint>
@@ -31,9 +35,10 @@ struct Stretch {
 };
 
 // seq / qual: the read as parsed, qualities with the offset already subtracted (Read's qual_ is a string of char).
-// Appends the stretches of the read to out; returns how many.
-inline size_t valid_stretches(const std::string &seq_in, const std::string &qual_in, unsigned k, int trim_quality,
-                              std::vector<Stretch> &out) {
+// Appends the stretches of the read to out; returns how many.  *trimmed (may be null): the read trimNsAndBadQuality
+// leaves, as a range of the read as parsed -- written only when it has k bases or more (the generator ran).
+inline size_t trimmed_stretches(const std::string &seq_in, const std::string &qual_in, unsigned k, int trim_quality,
+                                std::vector<Stretch> &out, Stretch *trimmed) {
     // ---- Read::trimNsAndBadQuality(trim_quality) on a copy (kmer_data.cpp:167-171) ----
     std::string seq_ = seq_in, qual_ = qual_in;
     int start = 0;
@@ -59,6 +64,7 @@ inline size_t valid_stretches(const std::string &seq_in, const std::string &qual
         }
     }
     if (seq_.size() < k) return 0;  // sz < hammer::K
+    if (trimmed) *trimmed = {(uint32_t)start, (uint32_t)seq_.size()};
 
     // ---- ValidKMerGenerator<k>(cr, 2): Reset = TrimBadQuality + Next ----
     const size_t len_ = seq_.size();
@@ -112,6 +118,25 @@ inline size_t valid_stretches(const std::string &seq_in, const std::string &qual
         Next();
     }
     return added;
+}
+
+inline size_t valid_stretches(const std::string &seq, const std::string &qual, unsigned k, int trim_quality,
+                              std::vector<Stretch> &out) {
+    return trimmed_stretches(seq, qual, k, trim_quality, out, nullptr);
+}
+
+// Whether Expander::operator() can ever find the read solid: its valid k-mer starts are consecutive from the first base
+// of the trimmed read to its last k-mer.  *stretch is then the trimmed read, one read of the engine for
+// bbk_expander_push.  Every other read returns before it marks anything, whatever the good bits are: one with an interior
+// N, one whose q < 2 tail survived the trimming (end_ stops before sz), one with fewer than k bases left.
+inline bool expander_candidate(const std::string &seq, const std::string &qual, unsigned k, int trim_quality,
+                               Stretch *stretch) {
+    std::vector<Stretch> st;
+    Stretch trimmed = {0, 0};
+    if (trimmed_stretches(seq, qual, k, trim_quality, st, &trimmed) != 1) return false;
+    if (st[0].start != trimmed.start || st[0].length != trimmed.length) return false;
+    *stretch = trimmed;
+    return true;
 }
 
 }  // namespace hammer

@@ -1,7 +1,8 @@
-// bbk-hammer-reads-dump [-k <int=21>] [--qvoffset <int=33>] [--trim-quality <int=4>] <file>...: test helper for
-// hammer_reads.hpp (no GPU needed).  For every FASTQ record, in file order, one line per stretch of valid k-mer starts:
+// bbk-hammer-reads-dump [-k <int=21>] [--qvoffset <int=33>] [--trim-quality <int=4>] [--expander] <file>...: test helper
+// for hammer_reads.hpp (no GPU needed).  For every FASTQ record, in file order, one line per stretch of valid k-mer starts:
 //   <read index> <start> <length>
-// (read index counts the records of all files from 0; a record without a stretch prints nothing).
+// (read index counts the records of all files from 0; a record without a stretch prints nothing).  With --expander: one
+// such line for every record the Expander can ever find solid (expander_candidate), the trimmed read, and nothing else.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -13,7 +14,14 @@ int main(int argc, char **argv) {
     unsigned k = 21;
     int qvoffset = 33, trim_quality = 4;
     int first = 1;
-    while (first + 1 < argc && argv[first][0] == '-') {
+    bool expander = false;
+    while (first < argc && argv[first][0] == '-') {
+        if (!strcmp(argv[first], "--expander")) {
+            expander = true;
+            first += 1;
+            continue;
+        }
+        if (first + 1 >= argc) return 2;
         if (!strcmp(argv[first], "-k")) k = (unsigned)atoi(argv[first + 1]);
         else if (!strcmp(argv[first], "--qvoffset")) qvoffset = atoi(argv[first + 1]);
         else if (!strcmp(argv[first], "--trim-quality")) trim_quality = atoi(argv[first + 1]);
@@ -37,7 +45,9 @@ int main(int argc, char **argv) {
             }
             for (char &c : qual) c = (char)(c - qvoffset);
             st.clear();
-            bbkhost::hammer::valid_stretches(seq, qual, k, trim_quality, st);
+            bbkhost::hammer::Stretch whole;
+            if (!expander) bbkhost::hammer::valid_stretches(seq, qual, k, trim_quality, st);
+            else if (bbkhost::hammer::expander_candidate(seq, qual, k, trim_quality, &whole)) st.push_back(whole);
             for (const auto &s : st) printf("%llu %u %u\n", index, s.start, s.length);
             ++index;
         }

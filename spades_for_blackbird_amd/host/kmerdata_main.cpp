@@ -4,7 +4,8 @@
 // KMerDataCounter::FillKMerData, "Collecting K-mer information, this takes a while"); this tool is that sequence alone.
 //   -k/--kmer <int=21>  -t/--threads <int>  -b/--bufsize <bytes>  -o/--output <prefix>  -d/--dataset <yaml>  [input files...]
 //   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster, --subcluster with --singleton-threshold,
-//      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold)
+//      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold, --expand with --expand-max-iterations <int=25>,
+//      --expand-min-changed <int=10>)
 // Every FASTQ record is cut into the stretches of its valid k-mer starts (hammer_reads.hpp: input_trim_quality 4 of
 // configs/hammer/config.info, then ValidKMerGenerator); a stretch is one read of the engine.
 //   pass 1  the stretches, in blocks of -b bytes, through bbk_count_begin / push / finish(BBK_BOTH_STRANDS)
@@ -17,6 +18,11 @@
 //   with --subcluster (KMerClustering::process, projects/hammer/kmer_cluster.cpp:590-659; implies --cluster):
 //   <prefix>.kmstat then carries the good bit and the records of the new k-mers, and <prefix>.subclusters,
 //   <prefix>.subclusters.idx and <prefix>.newkmers are written (bbk_subclusters_write)
+//   with --expand (the solid k-mer expansion, projects/hammer/main.cpp:194-222 and expander.cpp:20-70; implies
+//   --subcluster): after the subclustering every round reads the files again and pushes the records the Expander can ever
+//   find solid (hammer_reads.hpp: expander_candidate), trimmed, in blocks of -b bytes through bbk_expander_push, until a
+//   round adds fewer than --expand-min-changed k-mers or --expand-max-iterations rounds have run; <prefix>.kmstat then
+//   carries the expanded good bits (bbk_expander_store) and every other file is as without --expand
 // The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
 // common interface.
 #include <cstring>
@@ -45,13 +51,17 @@ static void usage(const char *argv0) {
            "        --singleton-threshold <value>     bayes_singleton_threshold (default 0.995)\n"
            "        --nonsingleton-threshold <value>  bayes_nonsingleton_threshold (default 0.9)\n"
            "        --correct-threshold <value>       correct_threshold (default 0.98)\n"
-           "        --no-correct-threshold            correct_use_threshold 0\n\n"
+           "        --no-correct-threshold            correct_use_threshold 0\n"
+           "        --expand                Also expand the solid k-mers over the reads they cover (implies --subcluster)\n"
+           "        --expand-max-iterations <value>   expand_max_iterations (default 25)\n"
+           "        --expand-min-changed <value>      Stop after an iteration that adds fewer k-mers than this (default 10)\n\n"
            "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
            "        Output: <prefix>.kmers - the k-mers in ascending order, in the final_kmers record format;\n"
            "        <prefix>.kmstat - per k-mer: 32-bit count << 1, float total_qual, the 6-bit quality sums packed into 64-bit words;\n"
            "        with --cluster <prefix>.hamming and <prefix>.hamming.idx as spades-hamcluster writes them;\n"
            "        with --subcluster the good bit in <prefix>.kmstat, the new k-mers' records after the others, and\n"
-           "        <prefix>.subclusters, <prefix>.subclusters.idx, <prefix>.newkmers.\n",
+           "        <prefix>.subclusters, <prefix>.subclusters.idx, <prefix>.newkmers;\n"
+           "        with --expand the good bits in <prefix>.kmstat are those after the expansion.\n",
            argv0);
 }
 
@@ -68,10 +78,11 @@ struct Block {
 };
 
 // Calls push(block) for every block of at most block_bytes bases of the stretches of all records, in file order; returns
-// the number of records.  Both passes go through here, so they see the same stretches in the same blocks.
+// the number of records.  Both passes go through here, so they see the same stretches in the same blocks.  candidates:
+// the rounds of the expansion, which take the trimmed read of every record the Expander can ever find solid instead.
 template <class Push>
 static uint64_t for_each_block(const std::vector<std::string> &files, unsigned k, int qvoffset, int trim_quality,
-                               size_t block_bytes, bool announce, Push push) {
+                               size_t block_bytes, bool announce, bool candidates, Push push) {
     Block b;
     std::string name, seq, qual;
     std::vector<hammer::Stretch> st;
@@ -93,7 +104,9 @@ static uint64_t for_each_block(const std::vector<std::string> &files, unsigned k
             }
             ++records;
             st.clear();
-            hammer::valid_stretches(seq, qual, k, trim_quality, st);
+            hammer::Stretch whole;
+            if (!candidates) hammer::valid_stretches(seq, qual, k, trim_quality, st);
+            else if (hammer::expander_candidate(seq, qual, k, trim_quality, &whole)) st.push_back(whole);
             for (const hammer::Stretch &s : st) {
                 b.bases.append(seq, s.start, s.length);
                 b.quals.append(qual, s.start, s.length);
@@ -114,12 +127,16 @@ int main(int argc, char **argv) {
     unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4;
     std::string prefix, dataset;
     std::vector<std::string> input;
-    bool help = false, cluster = false, subcluster = false;
+    unsigned expand_max_iterations = 25;  // configs/hammer/config.info
+    unsigned long long expand_min_changed = 10;  // main.cpp:219
+    bool help = false, cluster = false, subcluster = false, expand = false;
     bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
     Options opt;
     opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
         .num("", "--qvoffset", &qvoffset).num("", "--trim-quality", &trim_quality).flag("", "--cluster", &cluster)
         .flag("", "--subcluster", [&] { cluster = subcluster = true; })
+        .flag("", "--expand", [&] { cluster = subcluster = expand = true; })
+        .num("", "--expand-max-iterations", &expand_max_iterations, 1u).num("", "--expand-min-changed", &expand_min_changed)
         .flag("", "--no-correct-threshold", [&] { sp.correct_use_threshold = 0; })
         .real("", "--singleton-threshold", &sp.singleton_threshold)
         .real("", "--nonsingleton-threshold", &sp.nonsingleton_threshold).real("", "--correct-threshold", &sp.correct_threshold)
@@ -145,7 +162,7 @@ int main(int argc, char **argv) {
     check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
     uint64_t stretches = 0;
     double t0 = now_s();
-    const uint64_t records = for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, true, [&](const Block &b) {
+    const uint64_t records = for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, true, false, [&](const Block &b) {
         check(bbk_count_push_ascii(counter, b.bases.data(), b.offsets.data(), b.size()), "bbk_count_push_ascii");
         stretches += b.size();
         ++ph.blocks;
@@ -164,7 +181,7 @@ int main(int argc, char **argv) {
     info("Collecting K-mer information");
     bbk_kmerstats *ks = nullptr;
     check(bbk_kmerstats_begin(ctx, set, &ks), "bbk_kmerstats_begin");
-    for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, false, [&](const Block &b) {
+    for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, false, false, [&](const Block &b) {
         bbk_reads *r = nullptr;
         bbk_quals *q = nullptr;
         check(bbk_reads_from_ascii(ctx, b.bases.data(), b.offsets.data(), b.size(), &r), "bbk_reads_from_ascii");
@@ -191,6 +208,28 @@ int main(int argc, char **argv) {
     if (subcluster) {
         bbk_subclusters *sc = nullptr;
         check(bbk_hamclusters_subcluster(ctx, set, hc, ks, &sp, &sc), "bbk_hamclusters_subcluster");
+        if (expand) {  // main.cpp:194-222
+            bbk_expander *ex = nullptr;
+            check(bbk_expander_from_subclusters(ctx, set, sc, &ex), "bbk_expander_from_subclusters");
+            info("Starting solid k-mers expansion in snapshot rounds.");
+            for (unsigned iter = 0; iter < expand_max_iterations; ++iter) {
+                check(bbk_expander_round_begin(ex), "bbk_expander_round_begin");
+                for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, false, true, [&](const Block &b) {
+                    bbk_reads *r = nullptr;
+                    check(bbk_reads_from_ascii(ctx, b.bases.data(), b.offsets.data(), b.size(), &r), "bbk_reads_from_ascii");
+                    check(bbk_expander_push(ex, r, nullptr), "bbk_expander_push");
+                    check(bbk_ctx_synchronize(ctx), "bbk_ctx_synchronize");  // push does not wait, and the reads go now
+                    bbk_reads_free(r);
+                });
+                uint64_t changed = 0;
+                check(bbk_expander_round_end(ex, &changed), "bbk_expander_round_end");
+                info("Solid k-mers iteration %u produced %llu new k-mers.", iter, (unsigned long long)changed);
+                if (changed < expand_min_changed) break;
+            }
+            info("Solid k-mers finalized");
+            check(bbk_expander_store(ex, sc), "bbk_expander_store");
+            bbk_expander_free(ex);
+        }
         check(bbk_subclusters_write(ctx, sc, ks, prefix.c_str()), "bbk_subclusters_write");
         uint64_t st[9], errs[16];
         check(bbk_subclusters_export(ctx, sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, st),
