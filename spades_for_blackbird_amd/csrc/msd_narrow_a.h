@@ -26,6 +26,15 @@ __device__ inline uint32_t nw_slot(uint32_t t) { return (t * 0x27D4EB2Fu) >> 19;
 __device__ inline uint32_t nw_bin1(uint32_t hi, uint32_t t, int hb) { return (t >> 22) ^ (hi << (10 - hb)); }
 // prefix for level 2: the bits of the mix that level 1 has not used (top-aligned)
 __device__ inline uint32_t nw_p2(uint32_t t) { return t << 10; }
+// level-2 bin of a record among the nb <= 1024 bins of its segment: __umulhi(nw_p2(t), nb) = ((t & 0x3FFFFF) * nb) >> 22
+// exactly, and both factors lie below 2^24 (the product below 2^32): one full-rate 24-bit multiply
+__device__ inline uint32_t nw_bin2(uint32_t t, uint32_t nb) {
+#ifdef BBK_AB_NW_BIN2_MULHI  // (A/B: the 32 x 32 -> high-word multiply, as before round 11)
+    return __umulhi(nw_p2(t), nb);
+#else
+    return __umul24(t & 0x3FFFFFu, nb) >> 22;
+#endif
+}
 __device__ inline uint64_t nw_key(uint32_t bin1, uint32_t lo, int hb) {
     const uint32_t hi = (bin1 ^ (nw_mix(lo) >> 22)) >> (10 - hb);
     return ((uint64_t)hi << 32) | lo;
@@ -467,7 +476,7 @@ __global__ __launch_bounds__(kNw2Threads) void k_part_narrow2(const uint32_t *__
         const uint32_t local = (uint32_t)i * NT + tid;
         binrank[i] = 0xFFFFFFFFu;
         if (local < count) {
-            const uint32_t b = __umulhi(nw_p2(nw_mix(lo[i])), nb);
+            const uint32_t b = nw_bin2(nw_mix(lo[i]), nb);
             const uint32_t rank = atomicAdd(&lhist[b], 1u);
             binrank[i] = (b << 16) | rank;
         }
@@ -510,7 +519,7 @@ __global__ __launch_bounds__(kNw2Threads) void k_part_narrow2(const uint32_t *__
         const uint32_t pos = (uint32_t)i * NT + tid;
         if (pos < staged) {
             const uint32_t rec = stage[pos];
-            const uint32_t b = __umulhi(nw_p2(nw_mix(rec)), nb);
+            const uint32_t b = nw_bin2(nw_mix(rec), nb);
             if ((int32_t)pos >= (int32_t)lhist[b]) {
                 full |= 1u << i;
             } else {
@@ -545,40 +554,191 @@ static size_t part_narrow2_smem(bool has_val) {
 constexpr int kNwHashThreads = 512;
 constexpr int kNwHashItems = 16;  // 8192 records per bucket
 constexpr uint32_t kNwHashSlots = 8192;
+constexpr uint32_t kNwEmpty = 0xFFFFFFFFu;
+
+// Table slot of a record: the top 13 bits of the FIRST product of nw_mix.  Segment and level-2 bin fix about 18 bits of
+// nw_mix(lo) inside a bucket; the top bits of lo * 0x9E3779B1 are not among them, and linear probing on them needs
+// the same number of extra probes as on a third multiply of the mix (tests/test_hash32_slot.py) -- one multiply per
+// record instead of three.
+__device__ inline uint32_t nw_hslot(uint32_t lo) {
+#ifdef BBK_AB_HASH32_OLD  // (A/B: the third multiply of the mix, as before round 11)
+    return nw_slot(nw_mix(lo)) & (kNwHashSlots - 1);
+#else
+    return (lo * 0x9E3779B1u) >> 19;
+#endif
+}
 
 template <int OP>
-__global__ __launch_bounds__(kNwHashThreads) void k_bucket_hash32(uint32_t *__restrict__ buf,
-                                                                 uint32_t *__restrict__ vals, BucketArgs A,
-                                                                 const uint16_t *__restrict__ bucket_seg, int hb) {
+__device__ __forceinline__ void nw_pay(uint32_t *at, uint32_t v) {
+    if (OP == 1) atomicAdd(at, 1u);
+    else if (OP == 2) atomicAdd(at, v);
+    else if (OP == 3) atomicOr(at, v);
+}
+
+// Linear probing behind a slot that held another key: walks on from slot + 1 until the key is in the table (`first`:
+// this call put it there) or more than max_probes slots were tried, which raises the give-up flag.  `probes` counts
+// the slots tried before (0xFFFFFFFF with slot - 1: the walk starts at the slot itself).  Returns the slot it ended on.
+__device__ __forceinline__ uint32_t nw_walk(uint32_t *tab, uint32_t *scan_tmp, uint32_t key, uint32_t slot, uint32_t probes,
+                                            uint32_t max_probes, bool &first) {
+    for (;;) {
+        slot = (slot + 1) & (kNwHashSlots - 1);
+        if (++probes > max_probes) {
+            scan_tmp[14] = 1;
+            break;
+        }
+        const uint32_t old = atomicCAS(&tab[slot], kNwEmpty, key);
+        if (old == kNwEmpty) first = true;
+        if (old == kNwEmpty || old == key) break;
+    }
+    return slot;
+}
+
+// One row of a bucket: NR records per lane (k[j] is record p0 + j), `full` (uniform): every record of the row lies
+// below n.  The first probes of the row are straight-line -- NR ds_cmpst in flight, one wait, no per-record branch, and
+// in a full row no per-record predicate; the lanes that met another key walk on behind ONE wave-uniform test.  A row
+// that holds the all-ones record (or, past n, whatever the slot held before) goes record by record: at k <= 21 a
+// canonical record is never all ones.  Returns bit j = record j was the first of its key in the table.
+template <int OP, int NR>
+__device__ __forceinline__ uint32_t nw_insert_row(uint32_t *tab, uint32_t *pay, uint32_t *scan_tmp, const uint32_t *k,
+                                                  const uint32_t *v, uint32_t p0, bool full, uint32_t n,
+                                                  uint32_t max_probes) {
+    constexpr uint32_t ALL = (1u << NR) - 1u;
+    const uint32_t left = p0 < n ? n - p0 : 0u;
+    const uint32_t valid = full || left >= (uint32_t)NR ? ALL : (1u << left) - 1u;
+    uint32_t mx = k[0], first = 0;
+#pragma unroll
+    for (int j = 1; j < NR; ++j) mx = k[j] > mx ? k[j] : mx;
+    if (__any(mx == kNwEmpty)) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            if (!((valid >> j) & 1u)) continue;
+            if (k[j] == kNwEmpty) {
+                scan_tmp[13] = 1;
+                nw_pay<OP>(&scan_tmp[12], v[j]);
+                continue;
+            }
+            bool f = false;
+            const uint32_t slot = nw_walk(tab, scan_tmp, k[j], nw_hslot(k[j]) - 1u, 0xFFFFFFFFu, max_probes, f);
+            first |= (f ? 1u : 0u) << j;
+            if (OP != 0) nw_pay<OP>(&pay[slot], v[j]);
+        }
+        return first;
+    }
+    uint32_t slot[NR], old[NR];
+#pragma unroll
+    for (int j = 0; j < NR; ++j) slot[j] = nw_hslot(k[j]);
+    if (full) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) old[j] = atomicCAS(&tab[slot[j]], kNwEmpty, k[j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) old[j] = (valid >> j) & 1u ? atomicCAS(&tab[slot[j]], kNwEmpty, k[j]) : k[j];
+    }
+    uint32_t miss = 0;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+        first |= (old[j] == kNwEmpty ? 1u : 0u) << j;
+        miss |= (old[j] != kNwEmpty && old[j] != k[j] ? 1u : 0u) << j;
+    }
+    if (__any(miss != 0)) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j) {
+            if ((miss >> j) & 1u) {
+                bool f = false;
+                slot[j] = nw_walk(tab, scan_tmp, k[j], slot[j], 0u, max_probes, f);
+                first |= (f ? 1u : 0u) << j;
+            }
+        }
+    }
+    if (OP != 0) {
+#pragma unroll
+        for (int j = 0; j < NR; ++j)
+            if ((valid >> j) & 1u) nw_pay<OP>(&pay[slot[j]], v[j]);
+    }
+    return first;
+}
+
+// Front half of k_bucket_hash32 (every OP): the bucket's records into registers, the table cleared, the records
+// inserted row by row.  A row is NR records per lane: 4 in slot mode, where every bucket starts on a 256-byte boundary
+// (Plan::stride2) and a lane loads four uint4 -- records 4 * (r * 512 + tid) .. + 3 of row r; 1 with the dense layout,
+// whose buckets start anywhere (dword loads, record r * 512 + tid).  n is uniform: a row past n costs one scalar
+// branch, a row below n runs unpredicated, only the last one tests its records.  Leaves kk[i] and returns bit i =
+// record i was the first of its key.
+template <int OP, int NR>
+__device__ __forceinline__ uint32_t nw_hash32_rows(const uint32_t *__restrict__ buf, const uint32_t *__restrict__ vals,
+                                                   uint32_t *tab, uint32_t *pay, uint32_t *scan_tmp, uint32_t start,
+                                                   uint32_t n, uint32_t max_probes, uint32_t (&kk)[kNwHashItems],
+                                                   unsigned long long &t_prev) {
     constexpr bool IN_VAL = OP >= 2;
-    constexpr uint32_t EMPTY = 0xFFFFFFFFu;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *pay = tab + kNwHashSlots;
-    uint32_t *scan_tmp = pay + (OP != 0 ? kNwHashSlots : 0);  // [0..7] wave totals, [12] payload of the all-ones record,
-                                                              // [13] its presence, [14] give-up flag, [15] output base
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t b = blockIdx.x;
+    constexpr int ROWS = kNwHashItems / NR;
+    constexpr uint32_t ROW = (uint32_t)kNwHashThreads * NR;
+    const uint32_t tid = threadIdx.x;
+    uint32_t vv[kNwHashItems];
+    if constexpr (NR == 4) {
+        // (a lane past the bucket's last group of four re-reads that group: one address for all of them, and the loads
+        // stay unconditional -- with a branch around a load every insertion waits for ALL loads, profiles/r09)
+        const uint32_t last = (n - 1u) & ~3u;
+#pragma unroll
+        for (int r = 0; r < ROWS; ++r) {
+            const uint32_t p = (uint32_t)r * ROW + tid * 4u;
+            const uint32_t at = start + (p < last ? p : last);
+            const uint4 q = *reinterpret_cast<const uint4 *>(buf + at);
+            kk[4 * r] = q.x, kk[4 * r + 1] = q.y, kk[4 * r + 2] = q.z, kk[4 * r + 3] = q.w;
+            if (IN_VAL) {
+                const uint4 w = *reinterpret_cast<const uint4 *>(vals + at);
+                vv[4 * r] = w.x, vv[4 * r + 1] = w.y, vv[4 * r + 2] = w.z, vv[4 * r + 3] = w.w;
+            } else {
+                vv[4 * r] = vv[4 * r + 1] = vv[4 * r + 2] = vv[4 * r + 3] = 0u;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < kNwHashItems; ++i) {
+            const uint32_t p = (uint32_t)i * ROW + tid;
+            const uint32_t at = start + (p < n ? p : n - 1u);
+            kk[i] = buf[at];
+            vv[i] = IN_VAL ? vals[at] : 0u;
+        }
+    }
+    // (the loads are in flight while the table is cleared; four ds_write_b128 per thread instead of this loop were
+    // measured and did not move the kernel: profiles/r11)
+    for (uint32_t s = tid; s < kNwHashSlots; s += kNwHashThreads) {
+        tab[s] = kNwEmpty;
+        if (OP != 0) pay[s] = 0;
+    }
+    if (tid < 4) scan_tmp[12 + tid] = 0;
+    __syncthreads();
+    BBK_PH(4, 0, t_prev);  // table cleared
 #ifdef BBK_PHASE_PROF
-    unsigned long long t_prev = clock64();
-#else
-    const unsigned long long t_prev = 0;
-    (void)t_prev;
+#pragma unroll
+    for (int i = 0; i < kNwHashItems; ++i) asm volatile("" : "+v"(kk[i]));
+    BBK_PH(4, 1, t_prev);  // records loaded
 #endif
-    uint32_t start, n;
-    bucket_range(A, b, &start, &n);
-    if (n == 0) {
-        if (tid == 0) A.dcount[b] = 0;
-        return;
+    uint32_t firsts = 0;
+#pragma unroll
+    for (int r = 0; r < ROWS; ++r) {
+        if ((uint32_t)r * ROW < n)
+            firsts |= nw_insert_row<OP, NR>(tab, pay, scan_tmp, kk + r * NR, vv + r * NR, (uint32_t)r * ROW + tid * NR,
+                                            (uint32_t)(r + 1) * ROW <= n, n, max_probes)
+                      << (r * NR);
     }
-    if (n > (uint32_t)(kNwHashThreads * kNwHashItems)) {
-        if (tid == 0) A.dcount[b] = 0xFFFFFFFFu;
-        return;
-    }
-    uint32_t kk[kNwHashItems], vv[kNwHashItems];
+    return firsts;
+}
+
+#ifdef BBK_AB_HASH32_OLD  // (A/B: the front half as before round 11 -- sixteen clamped dword loads, a cleared-slot loop,
+                          // every record inserted under its own predicates and probe loop, nw_slot(nw_mix(lo)))
+template <int OP>
+__device__ __forceinline__ uint32_t nw_hash32_records(const uint32_t *__restrict__ buf, const uint32_t *__restrict__ vals,
+                                                      uint32_t *tab, uint32_t *pay, uint32_t *scan_tmp, uint32_t start,
+                                                      uint32_t n, uint32_t max_probes, uint32_t (&kk)[kNwHashItems],
+                                                      unsigned long long &t_prev) {
+    constexpr bool IN_VAL = OP >= 2;
+    constexpr uint32_t EMPTY = kNwEmpty;
+    const uint32_t tid = threadIdx.x;
+    uint32_t vv[kNwHashItems];
 #pragma unroll
     for (int i = 0; i < kNwHashItems; ++i) {  // (the loads are in flight while the table is cleared)
-        const uint32_t p = (uint32_t)(i * kNwHashThreads + tid);
+        const uint32_t p = (uint32_t)(i * kNwHashThreads) + tid;
         const uint32_t at = start + (p < n ? p : n - 1u);
         kk[i] = buf[at];
         vv[i] = IN_VAL ? vals[at] : 0u;
@@ -598,32 +758,68 @@ __global__ __launch_bounds__(kNwHashThreads) void k_bucket_hash32(uint32_t *__re
     uint32_t firsts = 0;  // bit i: record i of this lane was the first of its key in the table
 #pragma unroll
     for (int i = 0; i < kNwHashItems; ++i) {
-        const uint32_t p = (uint32_t)(i * kNwHashThreads + tid);
+        const uint32_t p = (uint32_t)(i * kNwHashThreads) + tid;
         if (p < n) {
             if (kk[i] == EMPTY) {
                 scan_tmp[13] = 1;
-                if (OP == 1) atomicAdd(&scan_tmp[12], 1u);
-                else if (OP == 2) atomicAdd(&scan_tmp[12], vv[i]);
-                else if (OP == 3) atomicOr(&scan_tmp[12], vv[i]);
+                nw_pay<OP>(&scan_tmp[12], vv[i]);
                 continue;
             }
-            uint32_t slot = nw_slot(nw_mix(kk[i])) & (kNwHashSlots - 1);
+            uint32_t slot = nw_hslot(kk[i]);
             uint32_t probes = 0;
             for (;;) {
                 const uint32_t old = atomicCAS(&tab[slot], EMPTY, kk[i]);
                 if (old == EMPTY) firsts |= 1u << i;
                 if (old == EMPTY || old == kk[i]) break;
                 slot = (slot + 1) & (kNwHashSlots - 1);
-                if (++probes > A.max_probes) {
+                if (++probes > max_probes) {
                     scan_tmp[14] = 1;
                     break;
                 }
             }
-            if (OP == 1) atomicAdd(&pay[slot], 1u);
-            else if (OP == 2) atomicAdd(&pay[slot], vv[i]);
-            else if (OP == 3) atomicOr(&pay[slot], vv[i]);
+            if (OP != 0) nw_pay<OP>(&pay[slot], vv[i]);
         }
     }
+    return firsts;
+}
+#endif
+
+template <int OP>
+__global__ __launch_bounds__(kNwHashThreads) void k_bucket_hash32(uint32_t *__restrict__ buf,
+                                                                 uint32_t *__restrict__ vals, BucketArgs A,
+                                                                 const uint16_t *__restrict__ bucket_seg, int hb) {
+    constexpr uint32_t EMPTY = kNwEmpty;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    uint32_t *tab = reinterpret_cast<uint32_t *>(smem);
+    uint32_t *pay = tab + kNwHashSlots;
+    uint32_t *scan_tmp = pay + (OP != 0 ? kNwHashSlots : 0);  // [0..7] wave totals, [12] payload of the all-ones record,
+                                                              // [13] its presence, [14] give-up flag, [15] output base
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t b = blockIdx.x;
+#ifdef BBK_PHASE_PROF
+    unsigned long long t_prev = clock64();
+#else
+    unsigned long long t_prev = 0;
+    (void)t_prev;
+#endif
+    uint32_t start, n;
+    bucket_range(A, b, &start, &n);
+    if (n == 0) {
+        if (tid == 0) A.dcount[b] = 0;
+        return;
+    }
+    if (n > (uint32_t)(kNwHashThreads * kNwHashItems)) {
+        if (tid == 0) A.dcount[b] = 0xFFFFFFFFu;
+        return;
+    }
+    uint32_t kk[kNwHashItems];
+    uint32_t firsts;  // bit i: record kk[i] of this lane was the first of its key in the table
+#ifdef BBK_AB_HASH32_OLD
+    firsts = nw_hash32_records<OP>(buf, vals, tab, pay, scan_tmp, start, n, A.max_probes, kk, t_prev);
+#else
+    if (A.slot_cap) firsts = nw_hash32_rows<OP, 4>(buf, vals, tab, pay, scan_tmp, start, n, A.max_probes, kk, t_prev);
+    else firsts = nw_hash32_rows<OP, 1>(buf, vals, tab, pay, scan_tmp, start, n, A.max_probes, kk, t_prev);
+#endif
     __syncthreads();
     BBK_PH(4, 2, t_prev);  // inserted
     if (scan_tmp[14]) {  // the table is (nearly) full: nothing has been written, the caller takes over
