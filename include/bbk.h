@@ -589,6 +589,43 @@ int bbk_expander_export(bbk_ctx *ctx, const bbk_expander *e, uint8_t *h_good); /
 int bbk_expander_store(bbk_expander *e, bbk_subclusters *sc);
 void bbk_expander_free(bbk_expander *e);
 
+/* ---- read correction: replaces ReadCorrector::CorrectOneRead / CorrectReadRight (projects/hammer/read_corrector.cpp:49-245)
+ *      and CorrectReadsBatch (projects/hammer/hammer_tools.cpp:79-105) -- the consumer of the good bits: every read is
+ *      corrected outwards from its longest run of solid k-mers ----------------------------------------------------------- */
+typedef struct bbk_corrector bbk_corrector; /* a set's lookup index and a copy of its good bits, in HBM */
+/* set: as for bbk_expander_* (ascending BBK_BOTH_STRANDS, k <= 32, fewer than 2^32 - 2 k-mers); it must outlive the
+ * corrector.  The bits are those of the expander now (copied: the expander may go on or be freed), or h_good: n bytes.
+ * BBK_ERR_ARG: a set the stage refuses, a byte other than 0 or 1, an expander with an open round or of another n or k. */
+int bbk_corrector_from_expander(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_expander *e, bbk_corrector **out);
+int bbk_corrector_from_host(bbk_ctx *ctx, const bbk_kmerset *set, const uint8_t *h_good, bbk_corrector **out);
+/* The fixed capacities of a search on the device: a search whose queue would hold more than *heap_cap
+ * states after a flush, or that pops more than *pop_cap states, is done by the host rule instead -- with the same result. */
+void bbk_corrector_limits(unsigned *heap_cap, unsigned *pop_cap);
+/* CorrectReadsBatch over n_reads TRIMMED reads (what Read::trimNsAndBadQuality left; the generator's own q < 2 trimming
+ * is applied here): read i is h_bases[h_offsets[i] .. h_offsets[i + 1]), ASCII, any byte other than A, C, G, T is a
+ * non-nucleotide; h_qual holds one quality per base with the offset already subtracted.  h_out (same layout) receives the
+ * corrected reads, h_result[i] the flag of CorrectOneRead.  A read shorter than k is copied, gets 0 and is not counted
+ * (hammer_tools.cpp:90-95).  Per read (:160-245): the longest run of consecutive valid starts (ValidKMerGenerator, bad
+ * quality 2) whose k-mer is in the set and good is the solid island [lleft, lright] -- the earliest of equal runs (:185);
+ * with 0 < solid_len < size the read is corrected to the right of lright, then its reverse complement to the right of
+ * size - 1 - lleft (:206-208), and the flag is 1; otherwise the flag is solid_len == size.  A search (:66-158) is
+ * best-first over std::priority_queue ordered by (penalty, pos): keeping the read's base costs 0 / 1 / 2 / 2 / 3 (good;
+ * present with q >= 20 / q < 20; absent with q >= 20 / q < 20) and forgets the positions of earlier corrections (the
+ * outer cpos, :70,98,104); no correction is tried after a good base of q >= 20, below a penalty of -15 % of the bases to
+ * go, or fewer than 8 bases after the fourth-last correction; a correction must give a good k-mer and costs 5 (q >= 20),
+ * 1 (q < 20) or 0 (the read has no nucleotide there); the first state that reaches the last base wins; an empty queue
+ * leaves the side as it was and counts its bases as uncorrected.  States of equal (penalty, pos) leave the queue in the
+ * order of libstdc++'s push_heap / pop_heap, which the device's heap follows step for step.
+ * h_where (n_reads bytes, or NULL): 0 no search, 1 searched on the device, 2 a search of the read went through the host
+ * rule (capacities above, or BBK_CORRECTOR_HOST=1 in the environment, which sends every search there).  The call waits.
+ * BBK_ERR_ARG: descending offsets, a read of more than 65535 bases (positions are 16 bits, :20), a quality above 93. */
+int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *h_qual, const uint64_t *h_offsets,
+                          uint64_t n_reads, char *h_out, uint8_t *h_result, uint8_t *h_where);
+/* summed over the calls so far: changed reads, changed nucleotides, uncorrected nucleotides, total nucleotides
+ * (CorrectionStats, hammer_tools.cpp:98-104), and the searches that went through the host rule */
+int bbk_corrector_stats(const bbk_corrector *c, uint64_t stats[5]);
+void bbk_corrector_free(bbk_corrector *c);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

@@ -25,17 +25,6 @@
 #include "hammer.h"
 #include "kmer_ops.h"
 
-struct bbk_expander {
-    bbk_ctx *ctx = nullptr;
-    const bbk_kmerset *set = nullptr;  // must outlive the expander
-    unsigned k = 0;
-    uint64_t n = 0, good = 0;
-    bool in_round = false;
-    bbk::PrefixIndex prefix;
-    bbk::DevBuf cur, next;  // n u8 each, zero-padded to a multiple of 16: G_r and G_{r+1}; equal outside a round
-    bbk::DevBuf changed;    // one u64
-};
-
 namespace bbk {
 
 constexpr uint32_t kExNone = 0xFFFFFFFFu;  // nothing to mark at this start (indices stay below 2^32 - 2)

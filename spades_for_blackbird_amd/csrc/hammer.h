@@ -1,6 +1,7 @@
-// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip and expand.hip (the BayesHammer stage)
-// share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation
-// unit through it.
+// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip and readcorrect.hip (the BayesHammer stage, DESIGN.md
+// 4.3c-g)
+// share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
+// through it.
 #pragma once
 
 #include <algorithm>
@@ -42,6 +43,17 @@ struct bbk_subclusters {
     bbk::DevBuf new_keys;     // new_kmers u64
     bbk::DevBuf bic;          // clusters double
     uint64_t errs[16] = {0}, stats[9] = {0};
+};
+
+struct bbk_expander {
+    bbk_ctx *ctx = nullptr;
+    const bbk_kmerset *set = nullptr;  // must outlive the expander
+    unsigned k = 0;
+    uint64_t n = 0, good = 0;
+    bool in_round = false;
+    bbk::PrefixIndex prefix;
+    bbk::DevBuf cur, next;  // n u8 each, zero-padded to a multiple of 16: G_r and G_{r+1}; equal outside a round
+    bbk::DevBuf changed;    // one u64
 };
 
 namespace bbk {

@@ -48,6 +48,8 @@ SYMBOLS = [
     "bbk_expander_from_subclusters", "bbk_expander_from_host", "bbk_expander_round_begin", "bbk_expander_push",
     "bbk_expander_round_end", "bbk_expander_run", "bbk_expander_good", "bbk_expander_export", "bbk_expander_store",
     "bbk_expander_free",
+    "bbk_corrector_from_expander", "bbk_corrector_from_host", "bbk_corrector_limits", "bbk_corrector_correct",
+    "bbk_corrector_stats", "bbk_corrector_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -273,6 +275,14 @@ def load_library():
     L.bbk_expander_store.argtypes = [vp, vp]
     L.bbk_expander_free.argtypes = [vp]
     L.bbk_expander_free.restype = None
+    L.bbk_corrector_from_expander.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.bbk_corrector_from_host.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.bbk_corrector_limits.argtypes = [C.POINTER(C.c_uint), C.POINTER(C.c_uint)]
+    L.bbk_corrector_limits.restype = None
+    L.bbk_corrector_correct.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp]
+    L.bbk_corrector_stats.argtypes = [vp, vp]
+    L.bbk_corrector_free.argtypes = [vp]
+    L.bbk_corrector_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -687,6 +697,18 @@ class KMerSet(_Handle):
         e._set = self
         return e
 
+    def corrector(self, good):
+        """Corrector over this ascending both-strand set (k <= 32) from the good bit of every k-mer (one byte each, 0 or
+        1).  The set must outlive it."""
+        good = np.ascontiguousarray(good, dtype=np.uint8)
+        if good.shape != (len(self),):
+            raise ValueError("one good byte per k-mer of the set: %d, not %r" % (len(self), good.shape))
+        h = C.c_void_p()
+        _check(self._L.bbk_corrector_from_host(self.ctx._h, self._h, _ptr(good), C.byref(h)))
+        c = Corrector(self.ctx, h)
+        c._set = self
+        return c
+
 
 KmerSet = KMerSet
 
@@ -887,6 +909,62 @@ class Expander(_Handle):
     def store(self, subclusters):
         """the bits back into the subclusters (their first n k-mers): SubClusters.export() / write() then carry them"""
         _check(self._L.bbk_expander_store(self._h, subclusters._h))
+
+    def corrector(self):
+        """Corrector over the expander's set from its bits as they are now (copied)"""
+        h = C.c_void_p()
+        _check(self._L.bbk_corrector_from_expander(self.ctx._h, self._set._h, self._h, C.byref(h)))
+        c = Corrector(self.ctx, h)
+        c._set = self._set
+        return c
+
+
+class Corrector(_Handle):
+    """BayesHammer's ReadCorrector (bbk_corrector_*): trimmed reads corrected outwards from their longest solid island,
+    equal to the reference base for base"""
+    _free = "bbk_corrector_free"
+    STATS = ("changed_reads", "changed_nucleotides", "uncorrected_nucleotides", "total_nucleotides", "host_searches")
+
+    def limits(self):
+        """(heap_cap, pop_cap) of a search on the device; a search beyond them runs through the host rule"""
+        a, b = C.c_uint(), C.c_uint()
+        self._L.bbk_corrector_limits(C.byref(a), C.byref(b))
+        return int(a.value), int(b.value)
+
+    def correct(self, reads):
+        """reads: [(seq, quals)], trimmed, quals with the offset subtracted -> (corrected sequences, result np.uint8[n],
+        where np.uint8[n]: 0 no search, 1 device, 2 host rule)"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s, _ in reads]
+        off = np.zeros(len(reads) + 1, dtype=np.uint64)
+        if reads:
+            off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        bases = np.frombuffer(b"".join(seqs), dtype=np.uint8)
+        qual = np.zeros(len(bases), dtype=np.uint8)
+        for i, (_, q) in enumerate(reads):
+            if len(q) != len(seqs[i]):
+                raise ValueError("read %d: %d bases, %d qualities" % (i, len(seqs[i]), len(q)))
+            qual[int(off[i]):int(off[i + 1])] = np.asarray(q, dtype=np.int64).clip(0, 255)
+        out, res, where = self.correct_arrays(bases, qual, off)
+        raw = out.tobytes()
+        return [raw[int(off[i]):int(off[i + 1])].decode() for i in range(len(reads))], res, where
+
+    def correct_arrays(self, bases, qual, offsets):
+        """the same over the arrays of the C call: bases and qual np.uint8 back to back, offsets np.uint64[n + 1] ->
+        (corrected bases np.uint8, result np.uint8[n], where np.uint8[n])"""
+        n = len(offsets) - 1
+        out = np.zeros(len(bases), dtype=np.uint8)
+        res = np.zeros(n, dtype=np.uint8)
+        where = np.zeros(n, dtype=np.uint8)
+        _check(self._L.bbk_corrector_correct(self._h, _ptr(bases), _ptr(qual), _ptr(offsets), n, _ptr(out), _ptr(res),
+                                             _ptr(where)))
+        return out, res, where
+
+    @property
+    def stats(self):
+        """the counters summed over the calls so far, by name (Corrector.STATS)"""
+        a = np.zeros(5, dtype=np.uint64)
+        _check(self._L.bbk_corrector_stats(self._h, _ptr(a)))
+        return dict(zip(self.STATS, (int(x) for x in a)))
 
 
 class Counter:

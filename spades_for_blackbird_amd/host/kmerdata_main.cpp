@@ -5,7 +5,7 @@
 //   -k/--kmer <int=21>  -t/--threads <int>  -b/--bufsize <bytes>  -o/--output <prefix>  -d/--dataset <yaml>  [input files...]
 //   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster, --subcluster with --singleton-threshold,
 //      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold, --expand with --expand-max-iterations <int=25>,
-//      --expand-min-changed <int=10>)
+//      --expand-min-changed <int=10>, --correct)
 // Every FASTQ record is cut into the stretches of its valid k-mer starts (hammer_reads.hpp: input_trim_quality 4 of
 // configs/hammer/config.info, then ValidKMerGenerator); a stretch is one read of the engine.
 //   pass 1  the stretches, in blocks of -b bytes, through bbk_count_begin / push / finish(BBK_BOTH_STRANDS)
@@ -23,6 +23,10 @@
 //   find solid (hammer_reads.hpp: expander_candidate), trimmed, in blocks of -b bytes through bbk_expander_push, until a
 //   round adds fewer than --expand-min-changed k-mers or --expand-max-iterations rounds have run; <prefix>.kmstat then
 //   carries the expanded good bits (bbk_expander_store) and every other file is as without --expand
+//   with --correct (ReadCorrector, projects/hammer/read_corrector.cpp and hammer_tools.cpp:79-142 CorrectReadFile; implies
+//   --expand): after the expansion every input file i is read once more as a single-read file: every record is trimmed
+//   (Read::trimNsAndBadQuality(--trim-quality)), corrected in blocks of -b bytes (bbk_corrector_correct) and printed in
+//   the format of Read::print to <prefix>.<i>.cor.fastq (result true) or <prefix>.<i>.bad.fastq
 // The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
 // common interface.
 #include <cstring>
@@ -54,14 +58,16 @@ static void usage(const char *argv0) {
            "        --no-correct-threshold            correct_use_threshold 0\n"
            "        --expand                Also expand the solid k-mers over the reads they cover (implies --subcluster)\n"
            "        --expand-max-iterations <value>   expand_max_iterations (default 25)\n"
-           "        --expand-min-changed <value>      Stop after an iteration that adds fewer k-mers than this (default 10)\n\n"
+           "        --expand-min-changed <value>      Stop after an iteration that adds fewer k-mers than this (default 10)\n"
+           "        --correct               Also correct the reads with the expanded solid k-mers (implies --expand)\n\n"
            "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
            "        Output: <prefix>.kmers - the k-mers in ascending order, in the final_kmers record format;\n"
            "        <prefix>.kmstat - per k-mer: 32-bit count << 1, float total_qual, the 6-bit quality sums packed into 64-bit words;\n"
            "        with --cluster <prefix>.hamming and <prefix>.hamming.idx as spades-hamcluster writes them;\n"
            "        with --subcluster the good bit in <prefix>.kmstat, the new k-mers' records after the others, and\n"
            "        <prefix>.subclusters, <prefix>.subclusters.idx, <prefix>.newkmers;\n"
-           "        with --expand the good bits in <prefix>.kmstat are those after the expansion.\n",
+           "        with --expand the good bits in <prefix>.kmstat are those after the expansion;\n"
+           "        with --correct <prefix>.<i>.cor.fastq and <prefix>.<i>.bad.fastq: the corrected reads of input file i.\n",
            argv0);
 }
 
@@ -122,6 +128,66 @@ static uint64_t for_each_block(const std::vector<std::string> &files, unsigned k
     return records;
 }
 
+// CorrectReadFile (hammer_tools.cpp:107-142) over one input file: trimmed records in blocks of block_bytes bases through the
+// corrector, printed as Read::print does (read.hpp:221-236)
+static void correct_read_file(bbk_corrector *cor, const std::string &file, int qvoffset, int trim_quality, size_t block_bytes,
+                              const std::string &cor_path, const std::string &bad_path) {
+    FastxReader rd(file);
+    if (!rd.is_open()) fatal("cannot open %s", file.c_str());
+    FILE *good = fopen(cor_path.c_str(), "wb"), *bad = fopen(bad_path.c_str(), "wb");
+    if (!good || !bad) fatal("cannot open %s for writing", (good ? bad_path : cor_path).c_str());
+    Block b;
+    std::vector<std::string> names;
+    std::vector<hammer::Trim> trims;
+    std::string out;
+    std::vector<uint8_t> res;
+    unsigned buffer_no = 0;
+    auto flush = [&] {
+        info("Prepared batch %u of %llu reads.", buffer_no, (unsigned long long)b.size());
+        out.resize(b.bases.size());
+        res.resize(b.size());
+        check(bbk_corrector_correct(cor, b.bases.data(), reinterpret_cast<const uint8_t *>(b.quals.data()), b.offsets.data(),
+                                    b.size(), &out[0], res.data(), nullptr),
+              "bbk_corrector_correct");
+        info("Processed batch %u", buffer_no);
+        std::string line;
+        for (uint64_t i = 0; i < b.size(); ++i) {
+            const hammer::Trim &t = trims[i];
+            const size_t o = b.offsets[i], len = b.offsets[i + 1] - o;
+            const int tail = t.initial_size_ - t.rtrim_;
+            line.assign("@").append(names[i]).append("\n").append((size_t)t.ltrim_, 'N').append(out, o, len).append((size_t)tail, 'N');
+            line.append("\n+").append(names[i]);
+            if (t.ltrim_ > 0) line.append(" ltrim=").append(std::to_string(t.ltrim_));
+            if (t.rtrim_ < t.initial_size_) line.append(" rtrim=").append(std::to_string(tail));
+            line.append("\n").append((size_t)t.ltrim_, (char)(qvoffset + 2));
+            for (size_t j = 0; j < len; ++j) line.push_back((char)(b.quals[o + j] + qvoffset));
+            line.append((size_t)tail, (char)(qvoffset + 2)).append("\n");
+            if (fwrite(line.data(), 1, line.size(), res[i] ? good : bad) != line.size()) fatal("writing the corrected reads failed");
+        }
+        info("Written batch %u", buffer_no);
+        ++buffer_no;
+        b.clear();
+        names.clear();
+        trims.clear();
+    };
+    std::string name, seq, qual;
+    uint64_t records = 0;
+    while (rd.next_record(name, seq, qual)) {
+        if (qual.size() != seq.size()) fatal("%s: record %llu (%s) has no quality string", file.c_str(), (unsigned long long)records, name.c_str());
+        for (char &c : qual) c = (char)((unsigned char)c - qvoffset);  // checked in the first pass
+        ++records;
+        const hammer::Trim t = hammer::trim_ns_and_bad_quality(seq, qual, trim_quality);
+        b.bases.append(seq, t.start, t.length);
+        b.quals.append(qual, t.start, t.length);
+        b.offsets.push_back(b.bases.size());
+        names.push_back(name);
+        trims.push_back(t);
+        if (b.bases.size() >= block_bytes) flush();
+    }
+    if (b.size()) flush();
+    if (fclose(good) != 0 || fclose(bad) != 0) fatal("writing the corrected reads failed");
+}
+
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4;
@@ -129,13 +195,14 @@ int main(int argc, char **argv) {
     std::vector<std::string> input;
     unsigned expand_max_iterations = 25;  // configs/hammer/config.info
     unsigned long long expand_min_changed = 10;  // main.cpp:219
-    bool help = false, cluster = false, subcluster = false, expand = false;
+    bool help = false, cluster = false, subcluster = false, expand = false, correct = false;
     bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
     Options opt;
     opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
         .num("", "--qvoffset", &qvoffset).num("", "--trim-quality", &trim_quality).flag("", "--cluster", &cluster)
         .flag("", "--subcluster", [&] { cluster = subcluster = true; })
         .flag("", "--expand", [&] { cluster = subcluster = expand = true; })
+        .flag("", "--correct", [&] { cluster = subcluster = expand = correct = true; })
         .num("", "--expand-max-iterations", &expand_max_iterations, 1u).num("", "--expand-min-changed", &expand_min_changed)
         .flag("", "--no-correct-threshold", [&] { sp.correct_use_threshold = 0; })
         .real("", "--singleton-threshold", &sp.singleton_threshold)
@@ -228,6 +295,23 @@ int main(int argc, char **argv) {
             }
             info("Solid k-mers finalized");
             check(bbk_expander_store(ex, sc), "bbk_expander_store");
+            if (correct) {  // hammer_tools.cpp:218-277, every file as a single-read file
+                bbk_corrector *cor = nullptr;
+                check(bbk_corrector_from_expander(ctx, set, ex, &cor), "bbk_corrector_from_expander");
+                info("Starting read correction.");
+                for (size_t i = 0; i < files.size(); ++i) {
+                    info("Correcting single reads: %s", files[i].c_str());
+                    const std::string base = prefix + "." + std::to_string(i);
+                    correct_read_file(cor, files[i], (int)qvoffset, (int)trim_quality, (size_t)bufsize, base + ".cor.fastq",
+                                      base + ".bad.fastq");
+                }
+                uint64_t cs[5];
+                check(bbk_corrector_stats(cor, cs), "bbk_corrector_stats");
+                info("Correction done. Changed %llu bases in %llu reads.", (unsigned long long)cs[1], (unsigned long long)cs[0]);
+                info("Failed to correct %llu bases out of %llu.", (unsigned long long)cs[2], (unsigned long long)cs[3]);
+                info("  Searches corrected on the host: %llu", (unsigned long long)cs[4]);
+                bbk_corrector_free(cor);
+            }
             bbk_expander_free(ex);
         }
         check(bbk_subclusters_write(ctx, sc, ks, prefix.c_str()), "bbk_subclusters_write");
