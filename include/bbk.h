@@ -473,7 +473,7 @@ void bbk_quals_free(bbk_quals *q);
 int bbk_kmerstats_begin(bbk_ctx *ctx, const bbk_kmerset *set, bbk_kmerstats **out);
 /* Every k-mer position p of every read is one occurrence (the reads are free of N; which positions
  * ValidKMerGenerator<K>(read, 2) yields after Read::trimNsAndBadQuality, valid_kmer_generator.hpp:147-199 and
- * io/reads/read.hpp:87-122, is the caller's business: spades-kmerdata cuts the reads accordingly).  With
+ * io/reads/read.hpp:87-122, is the caller's business: bbk_hreads_stretch_view gives exactly those reads from records as parsed).  With
  * cp = the product over the window of Prob(q) = 1 - (q < 3 ? 0.75 : 10^(-q / 10)) in double (main.cpp:103-105), the
  * k-mer is merged with the qualities q[p .. p + k) and its reverse complement with the same qualities reversed
  * (PushKMer / PushKMerRC, kmer_data.cpp:125-154), each only if it is in the set; Merge (:119-123) is count += 1,
@@ -561,8 +561,8 @@ int bbk_expander_from_subclusters(bbk_ctx *ctx, const bbk_kmerset *set, const bb
 int bbk_expander_from_host(bbk_ctx *ctx, const bbk_kmerset *set, const uint8_t *h_good, bbk_expander **out);
 /* One iteration of main.cpp:198-221 as a SNAPSHOT ROUND: every read pushed between round_begin and
  * round_end is judged against the bits G_r the round began with, and the marks go to the next generation.  A read of sz
- * bases (one run of ACGT: the caller pushes the reads that can ever be solid, trimmed -- host/hammer_reads.hpp
- * expander_candidate; sz < k: ignored, expander.cpp:27-28) has the starts 0 .. nk - 1, nk = sz - k + 1.  It is solid when
+ * bases (one run of ACGT: the caller pushes the reads that can ever be solid, trimmed -- bbk_hreads_candidate_view,
+ * or host/hammer_reads.hpp expander_candidate; sz < k: ignored, expander.cpp:27-28) has the starts 0 .. nk - 1, nk = sz - k + 1.  It is solid when
  * start 0 and start nk - 1 are in the set and good in G_r and no two consecutive good starts are more than k apart
  * (covered_by_solid all true, :30-51); only the forward k-mer is looked up (:36), and a start whose k-mer is not in the
  * set neither covers nor is marked (:37,54-55).  G_{r+1} = G_r with every k-mer, present in the set, of every solid read
@@ -625,6 +625,52 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
  * (CorrectionStats, hammer_tools.cpp:98-104), and the searches that went through the host rule */
 int bbk_corrector_stats(const bbk_corrector *c, uint64_t stats[5]);
 void bbk_corrector_free(bbk_corrector *c);
+
+/* ---- prepared reads: replaces Read::trimNsAndBadQuality / trimLeftRight (common/io/reads/read.hpp:87-122) followed by
+ *      ValidKMerGenerator<K>(read, 2) (projects/hammer/valid_kmer_generator.hpp:147-199), the step KMerDataFiller
+ *      (projects/hammer/kmer_data.cpp:163-186), Expander (projects/hammer/expander.cpp:20-29) and ReadCorrector
+ *      (projects/hammer/read_corrector.cpp:160-176) all begin with -- FASTQ records as parsed go in, and what the count,
+ *      the statistics, the expansion and the correction consume comes out, resident in HBM --------------------------- */
+typedef struct bbk_hreads bbk_hreads; /* a batch of records as parsed, their trims, stretches and candidate flags */
+/* Record i is h_bases[h_offsets[i] .. h_offsets[i + 1]) (n + 1 offsets), any byte values; h_qual holds one quality per
+ * base with the offset already subtracted (Read's qual_).  Per record the batch keeps, on the device:
+ *   the trim    (start, length) of what trimNsAndBadQuality(trim_quality) leaves, in the record as parsed (read.hpp:87-122;
+ *               a left trim suppresses the right trim, :114); (0, 0): nothing is left.  Read::print's ltrim_ / rtrim_
+ *               (:221-236) are start and start + length, or 0 and the record's size when nothing is left;
+ *   two tables  the valid starts of ValidKMerGenerator<k>(trimmed read, 2), consecutive starts a..b as one stretch
+ *               (a, b - a + k).  The k-mer table takes ACGTacgt for nucleotides (common/sequence/nucl.hpp:45-62), its
+ *               starts are in the record as parsed, and it is empty for a trimmed read of fewer than k bases
+ *               (kmer_data.cpp:171): what KMerDataFiller and Expander see.  The corrector table takes ACGT only and its
+ *               starts are in the trimmed read: what bbk_corrector_correct computes for the same trimmed reads;
+ *   the flag    1 when the k-mer table holds exactly one stretch and that is the whole trimmed read: the records
+ *               Expander::operator() can ever find solid (expander.cpp:30-51).
+ * BBK_ERR_ARG: k outside 1..32, descending offsets, a quality above 93, a record of 2^31 bases or more. */
+int bbk_hreads_from_host(bbk_ctx *ctx, const char *h_bases, const uint8_t *h_qual, const uint64_t *h_offsets, uint64_t n,
+                         unsigned k, int trim_quality, bbk_hreads **out);
+uint64_t bbk_hreads_size(const bbk_hreads *hr);               /* records */
+uint64_t bbk_hreads_kmer_stretches(const bbk_hreads *hr);      /* S_k: stretches of the k-mer table */
+uint64_t bbk_hreads_corrector_stretches(const bbk_hreads *hr); /* S_c: stretches of the corrector table */
+uint64_t bbk_hreads_candidates(const bbk_hreads *hr);
+/* Any pointer may be NULL.  h_trim: 2n u32 (start, length); h_candidate: n bytes; h_koff / h_coff: n + 1 entries, the
+ * stretches of record i are [off[i], off[i + 1]); h_kst / h_cst: (start, length) u32 pairs, 2 S_k / 2 S_c values. */
+int bbk_hreads_export(bbk_ctx *ctx, const bbk_hreads *hr, uint32_t *h_trim, uint8_t *h_candidate, uint64_t *h_koff,
+                      uint32_t *h_kst, uint64_t *h_coff, uint32_t *h_cst);
+/* One engine read per stretch of the k-mer table with its qualities (what KMerDataFiller pushes, kmer_data.cpp:172-183):
+ * for bbk_count_push_reads and bbk_kmerstats_push.  Packed on the device from the resident bytes on the first call,
+ * then cached; the batch owns both, they die with it and must not be freed.  quals may be NULL. */
+int bbk_hreads_stretch_view(const bbk_hreads *hr, const bbk_reads **reads, const bbk_quals **quals);
+/* The trimmed read of every candidate (expander.cpp:20-29), for bbk_expander_push / bbk_expander_run; owned and cached
+ * like the stretch view. */
+int bbk_hreads_candidate_view(const bbk_hreads *hr, const bbk_reads **reads);
+/* CorrectReadsBatch (hammer_tools.cpp:79-105) over the trimmed reads of the batch: bbk_corrector_correct without its
+ * host preparation -- the bases, the qualities and the corrector table are the resident ones.  h_out receives the
+ * corrected trimmed reads back to back, read i at [h_out_offsets[i], h_out_offsets[i + 1]) (n + 1 entries, from 0; the
+ * caller sizes h_out for the bases of the batch, which no trim exceeds); h_result, h_where and the counters are those
+ * of bbk_corrector_correct on the same trimmed reads.  h_where may be NULL.
+ * BBK_ERR_ARG: a batch made for another k than the corrector's, a record of more than 65535 bases. */
+int bbk_corrector_correct_prepared(bbk_corrector *c, const bbk_hreads *hr, char *h_out, uint64_t *h_out_offsets,
+                                   uint8_t *h_result, uint8_t *h_where);
+void bbk_hreads_free(bbk_hreads *hr);
 
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------

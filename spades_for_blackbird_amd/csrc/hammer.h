@@ -1,6 +1,5 @@
-// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip and readcorrect.hip (the BayesHammer stage, DESIGN.md
-// 4.3c-g)
-// share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
+// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip, readcorrect.hip and hreads.hip (the BayesHammer stage,
+// DESIGN.md 4.3c-h) share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
 // through it.
 #pragma once
 
@@ -56,7 +55,48 @@ struct bbk_expander {
     bbk::DevBuf changed;    // one u64
 };
 
+struct bbk_quals {
+    const bbk_reads *reads = nullptr;  // the reads these belong to (lengths checked against them)
+    uint64_t n = 0, bytes = 0;
+    bbk::DevBuf q;    // bytes u8, offset already subtracted
+    bbk::DevBuf off;  // n + 1 u64
+};
+
+// hreads.hip: the records of a batch as parsed, and what Read::trimNsAndBadQuality and ValidKMerGenerator<K>(read, 2)
+// make of them
+struct bbk_hreads {
+    bbk_ctx *ctx = nullptr;
+    unsigned k = 0;
+    int trim_quality = 0;
+    uint64_t n = 0, bytes = 0;  // records; bases (= qualities) of all of them
+    uint64_t longest = 0;       // bases of the longest record
+    uint64_t n_kst = 0, n_cst = 0, n_cand = 0;
+    bbk::DevBuf bases, quals;  // bytes u8 each, as parsed (quals: offset already subtracted)
+    bbk::DevBuf off;           // n + 1 u64
+    bbk::DevBuf trim;          // n x (start, length) u32, in the record as parsed; (0, 0): nothing is left
+    bbk::DevBuf cand;          // n u8: expander_candidate
+    bbk::DevBuf koff, kst;     // n + 1 u64; n_kst x (start, length) u32: the k-mer table, starts in the record as parsed
+    bbk::DevBuf coff, cst;     // n + 1 u64; n_cst x (start, length) u32: the corrector table, starts in the trimmed read
+    bbk::DevBuf cpos;          // n + 1 u64: candidates before record i
+    // made on first request, freed with the batch (mutable: a cache behind a const handle, one host thread per context)
+    struct View {
+        bool made = false;
+        bbk_reads reads;
+        bbk_quals quals;
+    };
+    mutable View stretch_view, candidate_view;
+    struct Trimmed {  // the trimmed reads back to back, what the corrector's kernels read
+        bool made = false;
+        bbk::DevBuf bases, quals, off;  // total u8 each; n + 1 u64
+        uint64_t total = 0;
+    };
+    mutable Trimmed trimmed;
+};
+
 namespace bbk {
+
+// hreads.hip: fills hr->trimmed on first use (two launches, one scan, one wait)
+const bbk_hreads::Trimmed &hreads_trimmed(const bbk_hreads *hr);
 
 // The k-mer sets of the stage: one-word keys, ascending, k-mer indices in 32 bits with two values to spare.  BBK_CANONICAL
 // is not judged here: the statistics refuse a canonical set by its flag, the clustering by its closure check.

@@ -30,13 +30,6 @@
 #include "hammer.h"
 #include "kmer_ops.h"
 
-struct bbk_quals {
-    const bbk_reads *reads = nullptr;  // the reads these belong to (lengths checked against them)
-    uint64_t n = 0, bytes = 0;
-    bbk::DevBuf q;    // bytes u8, offset already subtracted
-    bbk::DevBuf off;  // n + 1 u64
-};
-
 namespace bbk {
 
 // Fixed-point fraction bits of the log sum.  A quality is at most 93 (bbk_quals_from_host refuses more: '~', the last

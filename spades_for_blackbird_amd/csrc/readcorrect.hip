@@ -20,10 +20,13 @@
 // exactly when `corrections` would hold more than kRcHeapCap states after a flush, when it pops more than kRcPopCap times,
 // or when its edit log fills (kRcEditCap = 3 * kRcPopCap nodes: a pop makes three at most, so the pop cap always comes
 // first).  Both paths give the same bytes.
+// Two doors lead to the same code (rc_run): bbk_corrector_correct cuts the generator's stretches on the host and uploads
+// bases, qualities and table; bbk_corrector_correct_prepared takes all three from a bbk_hreads (hreads.hip), resident.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <memory>
 
 #include "hammer.h"
@@ -361,6 +364,125 @@ static void rc_fetch_set(bbk_corrector *c) {
 using namespace bbk;
 namespace rch = bbkhost::readcorrect;
 
+// A batch of trimmed reads with the generator's stretches, as the device pass and the host tail see it: the bases, the
+// qualities, the offsets (n_reads + 1, from 0) and the stretch table on the device (the caller's uploads, or the resident
+// ones of a bbk_hreads), the bases and the offsets on the host as well.  h_qual is asked for only when a search goes
+// through the host rule.
+struct RcBatch {
+    uint64_t n_reads = 0, bytes = 0;
+    uint32_t longest = 0;
+    const uint8_t *d_bases = nullptr, *d_qual = nullptr;
+    const uint64_t *d_off = nullptr, *d_stoff = nullptr;
+    const uint32_t *d_st = nullptr;
+    const char *h_bases = nullptr;
+    const uint64_t *h_offsets = nullptr;
+    std::function<const uint8_t *()> h_qual;
+};
+
+// CorrectReadsBatch behind the stretch table: k_rc_island, k_rc_search, the searches beyond the capacities by the host
+// rule, the counters.  h_out (from 0, like the batch) is written here, all of it: the device's output when a search
+// ran there, a copy of the bases otherwise; h_result / h_where are zeroed.
+static void rc_run(bbk_corrector *c, const RcBatch &b, char *h_out, uint8_t *h_result, uint8_t *h_where) {
+    bbk_ctx *ctx = c->ctx;
+    const unsigned k = c->k;
+    const uint64_t n_reads = b.n_reads, bytes = b.bytes;
+    const uint64_t *h_offsets = b.h_offsets;
+    const char *h_bases = b.h_bases;
+    raw_vector<uint32_t> thr(b.longest + 1);
+    thr[0] = 0;
+    for (uint32_t n = 1; n <= b.longest; ++n) thr[n] = (uint32_t)rch::size_threshold(n);  // the same log2 as the host rule
+
+    // ---- device pass ----
+    DevBuf d_thr, d_out(bytes), d_isl(n_reads * 8), d_res(n_reads), d_items(n_reads * 16), d_count(8), d_sstat(n_reads * 2);
+    upload(ctx, d_thr, thr.data(), (uint64_t)thr.size());
+    BBK_HIP(copy_async(d_out.p, b.d_bases, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    BBK_HIP(hipMemsetAsync(d_count.p, 0, 8, ctx->stream));
+    BBK_HIP(hipMemsetAsync(d_sstat.p, 0, n_reads * 2, ctx->stream));
+    launch_items_timed(ctx, "k_rc_island", k_rc_island, n_reads * 64, b.d_bases, b.d_off, n_reads, (int)k, b.d_st, b.d_stoff,
+                       c->set->keys.as<Key<1>>(), c->prefix.table(), c->good.as<uint8_t>(), d_isl.as<uint32_t>(),
+                       d_res.as<uint8_t>(), d_count.as<unsigned long long>(), d_items.as<uint64_t>());
+    uint64_t n_items = 0;
+    d2h_sync(ctx, &n_items, d_count.p, 8);
+    BBK_REQUIRE(n_items <= 2 * n_reads, BBK_ERR_INTERNAL, "bbk_corrector_correct: %llu work items for %llu reads",
+                (unsigned long long)n_items, (unsigned long long)n_reads);
+    const char *env = getenv("BBK_CORRECTOR_HOST");
+    const bool host_only = env && atoi(env) != 0;
+    if (n_items && !host_only) {
+        KernelTimer t(ctx, "k_rc_search");
+        hipLaunchKernelGGL(k_rc_search, grid_blocks(n_items), dim3(64), 0, ctx->stream, b.d_bases, b.d_qual, b.d_off, (int)k, c->set->keys.as<Key<1>>(), c->prefix.table(),
+                           c->good.as<uint8_t>(), d_isl.as<uint32_t>(), d_items.as<uint64_t>(), n_items,
+                           d_thr.as<uint32_t>(), d_out.as<uint8_t>(), d_sstat.as<uint8_t>());
+        check_launch("k_rc_search");
+    }
+    raw_vector<uint32_t> isl(n_reads * 2);
+    raw_vector<uint8_t> sstat(n_reads * 2);
+    d2h_big(ctx, isl.data(), d_isl.p, n_reads * 8);
+    d2h_big(ctx, h_result, d_res.p, n_reads);
+    d2h_big(ctx, sstat.data(), d_sstat.p, n_reads * 2);
+    if (n_items && !host_only) d2h_big(ctx, h_out, d_out.p, bytes);
+    else if (bytes) memcpy(h_out, h_bases, bytes);
+
+    // ---- the searches the device did not finish, by the host rule; then the counters ----
+    raw_vector<uint64_t> todo;  // read << 1 | direction
+    for (uint64_t r = 0; r < n_reads && n_items; ++r) {
+        const uint64_t len = h_offsets[r + 1] - h_offsets[r];
+        const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
+        if (!solid || solid == len) continue;
+        const uint32_t lleft = isl[2 * r], lright = lleft + solid - 1;
+        const size_t before = todo.size();
+        if (lright + 1 < len && (host_only || sstat[2 * r] == kRcOverflow)) todo.push_back(r << 1);
+        if (lleft > 0 && (host_only || sstat[2 * r + 1] == kRcOverflow)) todo.push_back((r << 1) | 1);
+        if (h_where && todo.size() != before) h_where[r] = 2;
+    }
+    if (!todo.empty()) rc_fetch_set(c);
+    const uint8_t *h_qual = todo.empty() ? nullptr : b.h_qual();
+    const uint64_t *hk = c->h_keys.data();
+    const uint8_t *hg = c->h_good.data();
+    const uint64_t hn = c->n;
+    auto lookup = [hk, hn](uint64_t key) -> uint64_t {
+        const uint64_t *it = std::lower_bound(hk, hk + hn, key);
+        return it != hk + hn && *it == key ? (uint64_t)(it - hk) : rch::kNone;
+    };
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t j = 0; j < (int64_t)todo.size(); ++j) {
+        const uint64_t r = todo[j] >> 1, o = h_offsets[r], len = h_offsets[r + 1] - o;
+        const bool left = todo[j] & 1;
+        const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
+        const std::string seq(h_bases + o, len), qual((const char *)h_qual + o, len);
+        rch::SearchFigures fig;
+        if (!left) {
+            const std::string s = rch::CorrectReadRight(seq, qual, lright, k, lookup, hg, &fig);
+            memcpy(h_out + o + lright + 1, s.data() + lright + 1, len - lright - 1);  // it touches nothing else
+        } else {
+            const std::string s = rch::ReverseComplement(
+                rch::CorrectReadRight(rch::ReverseComplement(seq), rch::Reverse(qual), len - 1 - lleft, k, lookup, hg, &fig));
+            memcpy(h_out + o, s.data(), lleft);
+        }
+        sstat[2 * r + left] = fig.failed ? kRcFailed : kRcDone;
+    }
+    uint64_t changed_reads = 0, changed_nucl = 0, uncorrected = 0;
+#pragma omp parallel for reduction(+ : changed_reads, changed_nucl, uncorrected)
+    for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
+        const uint64_t o = h_offsets[r], len = h_offsets[r + 1] - o;
+        const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
+        if (!solid || solid == len) continue;
+        if (h_where && h_where[r] == 0) h_where[r] = 1;
+        const uint32_t lleft = isl[2 * r], lright = lleft + solid - 1;
+        if (sstat[2 * r] == kRcFailed) uncorrected += len - lright;
+        if (sstat[2 * r + 1] == kRcFailed) uncorrected += lleft + 1;  // read_size - (read_size - 1 - lleft)
+        uint64_t diff = 0;
+        for (uint64_t i = 0; i < len; ++i) diff += h_out[o + i] != h_bases[o + i];
+        if (diff) {
+            ++changed_reads;
+            changed_nucl += diff;
+        }
+    }
+    c->stats[0] += changed_reads;
+    c->stats[1] += changed_nucl;
+    c->stats[2] += uncorrected;
+    c->stats[4] += todo.size();
+}
+
 extern "C" {
 
 int bbk_corrector_from_expander(bbk_ctx *ctx, const bbk_kmerset *set, const bbk_expander *e, bbk_corrector **out) {
@@ -420,7 +542,6 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
             BBK_REQUIRE(h_qual[i] <= 93, BBK_ERR_ARG,
                         "bbk_corrector_correct: the quality at byte %llu is %u: 93 at most (the offset is already subtracted)",
                         (unsigned long long)i, (unsigned)h_qual[i]);
-        if (total > first) memcpy(h_out + first, h_bases + first, total - first);
         memset(h_result, 0, n_reads);
         if (h_where) memset(h_where, 0, n_reads);
         const unsigned k = c->k;
@@ -428,7 +549,10 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
         for (uint64_t r = 0; r < n_reads; ++r)
             if (h_offsets[r + 1] - h_offsets[r] >= k) nucleotides += h_offsets[r + 1] - h_offsets[r];  // hammer_tools.cpp:90-95
         c->stats[3] += nucleotides;
-        if (c->n == 0 || nucleotides == 0) return;  // no k-mer is good, or no read has k bases: every result is false
+        if (c->n == 0 || nucleotides == 0) {  // no k-mer is good, or no read has k bases: every result is false
+            if (total > first) memcpy(h_out + first, h_bases + first, total - first);
+            return;
+        }
 
         bbk_ctx *ctx = c->ctx;
         BBK_HIP(hipSetDevice(ctx->device));
@@ -463,14 +587,9 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
                     stretches[at++] = s.length;
                 }
         }
-        raw_vector<uint32_t> thr(longest + 1);
-        thr[0] = 0;
-        for (uint32_t n = 1; n <= longest; ++n) thr[n] = (uint32_t)rch::size_threshold(n);  // the same log2 as the host rule
-
-        // ---- device pass ----
+        // ---- the uploads, then everything behind the table ----
         const uint64_t bytes = total - first;
-        DevBuf d_bases, d_qual, d_off, d_st, d_stoff, d_thr, d_out(bytes), d_isl(n_reads * 8), d_res(n_reads), d_items(n_reads * 16),
-            d_count(8), d_sstat(n_reads * 2);
+        DevBuf d_bases, d_qual, d_off, d_st, d_stoff;
         raw_vector<uint64_t> rel(n_reads + 1);
         for (uint64_t r = 0; r <= n_reads; ++r) rel[r] = h_offsets[r] - first;
         upload(ctx, d_bases, (const uint8_t *)h_bases + first, bytes);
@@ -478,93 +597,73 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
         upload(ctx, d_off, rel.data(), n_reads + 1);
         upload(ctx, d_st, stretches.data(), (uint64_t)stretches.size());
         upload(ctx, d_stoff, st_off.data(), n_reads + 1);
-        upload(ctx, d_thr, thr.data(), (uint64_t)thr.size());
-        BBK_HIP(copy_async(d_out.p, d_bases.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-        BBK_HIP(hipMemsetAsync(d_count.p, 0, 8, ctx->stream));
-        BBK_HIP(hipMemsetAsync(d_sstat.p, 0, n_reads * 2, ctx->stream));
-        launch_items_timed(ctx, "k_rc_island", k_rc_island, n_reads * 64, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), n_reads,
-                           (int)k, d_st.as<uint32_t>(), d_stoff.as<uint64_t>(), c->set->keys.as<Key<1>>(), c->prefix.table(),
-                           c->good.as<uint8_t>(), d_isl.as<uint32_t>(), d_res.as<uint8_t>(), d_count.as<unsigned long long>(),
-                           d_items.as<uint64_t>());
-        uint64_t n_items = 0;
-        d2h_sync(ctx, &n_items, d_count.p, 8);
-        BBK_REQUIRE(n_items <= 2 * n_reads, BBK_ERR_INTERNAL, "bbk_corrector_correct: %llu work items for %llu reads",
-                    (unsigned long long)n_items, (unsigned long long)n_reads);
-        const char *env = getenv("BBK_CORRECTOR_HOST");
-        const bool host_only = env && atoi(env) != 0;
-        if (n_items && !host_only) {
-            KernelTimer t(ctx, "k_rc_search");
-            hipLaunchKernelGGL(k_rc_search, grid_blocks(n_items), dim3(64), 0, ctx->stream, d_bases.as<uint8_t>(),
-                               d_qual.as<uint8_t>(), d_off.as<uint64_t>(), (int)k, c->set->keys.as<Key<1>>(), c->prefix.table(),
-                               c->good.as<uint8_t>(), d_isl.as<uint32_t>(), d_items.as<uint64_t>(), n_items,
-                               d_thr.as<uint32_t>(), d_out.as<uint8_t>(), d_sstat.as<uint8_t>());
-            check_launch("k_rc_search");
-        }
-        raw_vector<uint32_t> isl(n_reads * 2);
-        raw_vector<uint8_t> sstat(n_reads * 2);
-        d2h_big(ctx, isl.data(), d_isl.p, n_reads * 8);
-        d2h_big(ctx, h_result, d_res.p, n_reads);
-        d2h_big(ctx, sstat.data(), d_sstat.p, n_reads * 2);
-        if (n_items && !host_only) d2h_big(ctx, h_out + first, d_out.p, bytes);
+        RcBatch b;
+        b.n_reads = n_reads;
+        b.bytes = bytes;
+        b.longest = longest;
+        b.d_bases = d_bases.as<uint8_t>();
+        b.d_qual = d_qual.as<uint8_t>();
+        b.d_off = d_off.as<uint64_t>();
+        b.d_st = d_st.as<uint32_t>();
+        b.d_stoff = d_stoff.as<uint64_t>();
+        b.h_bases = h_bases + first;
+        b.h_offsets = rel.data();
+        b.h_qual = [&] { return h_qual + first; };
+        rc_run(c, b, h_out + first, h_result, h_where);
+    });
+}
 
-        // ---- the searches the device did not finish, by the host rule; then the counters ----
-        raw_vector<uint64_t> todo;  // read << 1 | direction
-        for (uint64_t r = 0; r < n_reads && n_items; ++r) {
-            const uint64_t len = h_offsets[r + 1] - h_offsets[r];
-            const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
-            if (!solid || solid == len) continue;
-            const uint32_t lleft = isl[2 * r], lright = lleft + solid - 1;
-            const size_t before = todo.size();
-            if (lright + 1 < len && (host_only || sstat[2 * r] == kRcOverflow)) todo.push_back(r << 1);
-            if (lleft > 0 && (host_only || sstat[2 * r + 1] == kRcOverflow)) todo.push_back((r << 1) | 1);
-            if (h_where && todo.size() != before) h_where[r] = 2;
+int bbk_corrector_correct_prepared(bbk_corrector *c, const bbk_hreads *hr, char *h_out, uint64_t *h_out_offsets,
+                                   uint8_t *h_result, uint8_t *h_where) {
+    return guarded([&] {
+        BBK_REQUIRE(c && hr && h_out_offsets && h_result, BBK_ERR_ARG, "bbk_corrector_correct_prepared: NULL argument");
+        BBK_REQUIRE(hr->k == c->k, BBK_ERR_ARG,
+                    "bbk_corrector_correct_prepared: the batch was prepared for k = %u, the corrector's set has k = %u", hr->k, c->k);
+        BBK_REQUIRE(hr->ctx == c->ctx, BBK_ERR_ARG, "bbk_corrector_correct_prepared: the batch belongs to another context");
+        BBK_REQUIRE(hr->longest <= kRcMaxRead, BBK_ERR_ARG,
+                    "bbk_corrector_correct_prepared: a record has %llu bases: a position is 16 bits (read_corrector.cpp:20), %u at most",
+                    (unsigned long long)hr->longest, kRcMaxRead);
+        bbk_ctx *ctx = c->ctx;
+        BBK_HIP(hipSetDevice(ctx->device));
+        const uint64_t n_reads = hr->n;
+        const bbk_hreads::Trimmed &t = hreads_trimmed(hr);  // the trimmed reads back to back, made once per batch
+        BBK_REQUIRE(t.total == 0 || h_out, BBK_ERR_ARG, "bbk_corrector_correct_prepared: NULL argument");
+        d2h_big(ctx, h_out_offsets, t.off.p, (n_reads + 1) * 8);
+        memset(h_result, 0, n_reads);
+        if (h_where) memset(h_where, 0, n_reads);
+        const unsigned k = c->k;
+        uint64_t nucleotides = 0;
+        uint32_t longest = 0;
+        for (uint64_t r = 0; r < n_reads; ++r) {
+            const uint64_t len = h_out_offsets[r + 1] - h_out_offsets[r];
+            if (len >= k) nucleotides += len;  // hammer_tools.cpp:90-95
+            longest = std::max(longest, (uint32_t)len);
         }
-        if (!todo.empty()) rc_fetch_set(c);
-        const uint64_t *hk = c->h_keys.data();
-        const uint8_t *hg = c->h_good.data();
-        const uint64_t hn = c->n;
-        auto lookup = [hk, hn](uint64_t key) -> uint64_t {
-            const uint64_t *it = std::lower_bound(hk, hk + hn, key);
-            return it != hk + hn && *it == key ? (uint64_t)(it - hk) : rch::kNone;
+        c->stats[3] += nucleotides;
+        if (c->n == 0 || nucleotides == 0) {
+            if (t.total) d2h_big(ctx, h_out, t.bases.p, t.total);
+            return;
+        }
+        raw_vector<char> orig(t.total);  // the reads as they were: the counters compare with them
+        if (t.total) d2h_big(ctx, orig.data(), t.bases.p, t.total);
+        raw_vector<uint8_t> qual;
+        RcBatch b;
+        b.n_reads = n_reads;
+        b.bytes = t.total;
+        b.longest = longest;
+        b.d_bases = t.bases.as<uint8_t>();
+        b.d_qual = t.quals.as<uint8_t>();
+        b.d_off = t.off.as<uint64_t>();
+        b.d_st = hr->cst.as<uint32_t>();
+        b.d_stoff = hr->coff.as<uint64_t>();
+        b.h_bases = orig.data();
+        b.h_offsets = h_out_offsets;
+        b.h_qual = [&] {
+            qual.resize(t.total);
+            d2h_big(ctx, qual.data(), t.quals.p, t.total);
+            return (const uint8_t *)qual.data();
         };
-#pragma omp parallel for schedule(dynamic, 16)
-        for (int64_t j = 0; j < (int64_t)todo.size(); ++j) {
-            const uint64_t r = todo[j] >> 1, o = h_offsets[r], len = h_offsets[r + 1] - o;
-            const bool left = todo[j] & 1;
-            const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
-            const std::string seq(h_bases + o, len), qual((const char *)h_qual + o, len);
-            rch::SearchFigures fig;
-            if (!left) {
-                const std::string s = rch::CorrectReadRight(seq, qual, lright, k, lookup, hg, &fig);
-                memcpy(h_out + o + lright + 1, s.data() + lright + 1, len - lright - 1);  // it touches nothing else
-            } else {
-                const std::string s = rch::ReverseComplement(
-                    rch::CorrectReadRight(rch::ReverseComplement(seq), rch::Reverse(qual), len - 1 - lleft, k, lookup, hg, &fig));
-                memcpy(h_out + o, s.data(), lleft);
-            }
-            sstat[2 * r + left] = fig.failed ? kRcFailed : kRcDone;
-        }
-        uint64_t changed_reads = 0, changed_nucl = 0, uncorrected = 0;
-#pragma omp parallel for reduction(+ : changed_reads, changed_nucl, uncorrected)
-        for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
-            const uint64_t o = h_offsets[r], len = h_offsets[r + 1] - o;
-            const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
-            if (!solid || solid == len) continue;
-            if (h_where && h_where[r] == 0) h_where[r] = 1;
-            const uint32_t lleft = isl[2 * r], lright = lleft + solid - 1;
-            if (sstat[2 * r] == kRcFailed) uncorrected += len - lright;
-            if (sstat[2 * r + 1] == kRcFailed) uncorrected += lleft + 1;  // read_size - (read_size - 1 - lleft)
-            uint64_t diff = 0;
-            for (uint64_t i = 0; i < len; ++i) diff += h_out[o + i] != h_bases[o + i];
-            if (diff) {
-                ++changed_reads;
-                changed_nucl += diff;
-            }
-        }
-        c->stats[0] += changed_reads;
-        c->stats[1] += changed_nucl;
-        c->stats[2] += uncorrected;
-        c->stats[4] += todo.size();
+        rc_run(c, b, h_out, h_result, h_where);
     });
 }
 

@@ -50,6 +50,8 @@ SYMBOLS = [
     "bbk_expander_free",
     "bbk_corrector_from_expander", "bbk_corrector_from_host", "bbk_corrector_limits", "bbk_corrector_correct",
     "bbk_corrector_stats", "bbk_corrector_free",
+    "bbk_hreads_from_host", "bbk_hreads_size", "bbk_hreads_kmer_stretches", "bbk_hreads_corrector_stretches", "bbk_hreads_candidates",
+    "bbk_hreads_export", "bbk_hreads_stretch_view", "bbk_hreads_candidate_view", "bbk_corrector_correct_prepared", "bbk_hreads_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -283,6 +285,16 @@ def load_library():
     L.bbk_corrector_stats.argtypes = [vp, vp]
     L.bbk_corrector_free.argtypes = [vp]
     L.bbk_corrector_free.restype = None
+    L.bbk_hreads_from_host.argtypes = [vp, vp, vp, vp, u64, C.c_uint, C.c_int, C.POINTER(vp)]
+    for f in ("size", "kmer_stretches", "corrector_stretches", "candidates"):
+        getattr(L, "bbk_hreads_" + f).restype = u64
+        getattr(L, "bbk_hreads_" + f).argtypes = [vp]
+    L.bbk_hreads_export.argtypes = [vp] * 8
+    L.bbk_hreads_stretch_view.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    L.bbk_hreads_candidate_view.argtypes = [vp, C.POINTER(vp)]
+    L.bbk_corrector_correct_prepared.argtypes = [vp] * 6
+    L.bbk_hreads_free.argtypes = [vp]
+    L.bbk_hreads_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -472,6 +484,24 @@ class Context:
         r._reads = reads
         return r
 
+    def hammer_reads(self, bases, quals, offsets, k, trim_quality=4):
+        """FASTQ records as parsed -> HammerReads: bases and quals uint8 back to back (any byte values; qualities with the
+        offset already subtracted, at most 93), record i at [offsets[i], offsets[i + 1])."""
+        b = np.ascontiguousarray(np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else bases,
+                                 dtype=np.uint8)
+        q = np.ascontiguousarray(np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals,
+                                 dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if len(offsets) < 1 or len(b) != len(q) or (len(offsets) > 1 and int(offsets.max()) > len(b)):
+            raise ValueError("hammer_reads: %d bases, %d qualities, offsets up to %d"
+                             % (len(b), len(q), int(offsets.max()) if len(offsets) else -1))
+        h = C.c_void_p()
+        _check(self._L.bbk_hreads_from_host(self._h, _ptr(b), _ptr(q), _ptr(offsets), len(offsets) - 1, k, trim_quality,
+                                            C.byref(h)))
+        r = HammerReads(self, h)
+        r.k, r.bases = k, len(b)
+        return r
+
     def extindex(self, reads, k):
         """DeBruijnExtensionIndexBuilder::BuildExtensionIndexFromStream analogue."""
         h = C.c_void_p()
@@ -566,8 +596,16 @@ class _Handle:
 
     def free(self):
         if getattr(self, "_h", None):
-            getattr(self._L, self._free)(self._h)
+            if not getattr(self, "_borrowed", False):
+                getattr(self._L, self._free)(self._h)
             self._h = None
+
+    @classmethod
+    def borrowed(cls, ctx, h, owner):
+        """a handle the library object `owner` owns: never freed from here, and `owner` is kept alive with it"""
+        x = cls(ctx, h)
+        x._borrowed, x._owner = True, owner
+        return x
 
     def close(self):
         self.free()
@@ -716,6 +754,53 @@ KmerSet = KMerSet
 class Quals(_Handle):
     """one quality byte per base of a Reads (offset already subtracted)"""
     _free = "bbk_quals_free"
+
+
+class HammerReads(_Handle):
+    """A batch of FASTQ records prepared on the device (bbk_hreads_*): what Read::trimNsAndBadQuality leaves of every
+    record, the valid k-mer starts of ValidKMerGenerator as stretches, and the records the Expander can find solid."""
+    _free = "bbk_hreads_free"
+
+    def __len__(self):
+        return int(self._L.bbk_hreads_size(self._h))
+
+    def trims(self):
+        """np.uint32[n, 2]: (start, length) of the trimmed read in the record as parsed; (0, 0): nothing is left"""
+        t = np.zeros((len(self), 2), dtype=np.uint32)
+        _check(self._L.bbk_hreads_export(self.ctx._h, self._h, _ptr(t), None, None, None, None, None))
+        return t
+
+    def candidates(self):
+        """np.uint8[n]: 1 where the valid starts cover the whole trimmed read (host/hammer_reads.hpp: expander_candidate)"""
+        c = np.zeros(len(self), dtype=np.uint8)
+        _check(self._L.bbk_hreads_export(self.ctx._h, self._h, None, _ptr(c), None, None, None, None))
+        return c
+
+    def stretches(self, table="kmer"):
+        """(offsets np.uint64[n + 1], stretches np.uint32[S, 2]): the (start, length) stretches of record i are rows
+        offsets[i] .. offsets[i + 1].  table "kmer": ACGTacgt are nucleotides, starts in the record as parsed, nothing
+        for a trimmed read shorter than k; "corrector": ACGT only, starts in the trimmed read."""
+        if table not in ("kmer", "corrector"):
+            raise ValueError("table is 'kmer' or 'corrector', not %r" % (table,))
+        kmer = table == "kmer"
+        s = int((self._L.bbk_hreads_kmer_stretches if kmer else self._L.bbk_hreads_corrector_stretches)(self._h))
+        off = np.zeros(len(self) + 1, dtype=np.uint64)
+        st = np.zeros((s, 2), dtype=np.uint32)
+        a = (_ptr(off), _ptr(st), None, None) if kmer else (None, None, _ptr(off), _ptr(st))
+        _check(self._L.bbk_hreads_export(self.ctx._h, self._h, None, None, *a))
+        return off, st
+
+    def stretch_view(self):
+        """(Reads, Quals) the batch owns: one engine read per k-mer stretch, for Counter.push and KmerStats.push"""
+        r, q = C.c_void_p(), C.c_void_p()
+        _check(self._L.bbk_hreads_stretch_view(self._h, C.byref(r), C.byref(q)))
+        return Reads.borrowed(self.ctx, r, self), Quals.borrowed(self.ctx, q, self)
+
+    def candidate_view(self):
+        """Reads the batch owns: the trimmed read of every candidate, for Expander.push / Expander.run"""
+        r = C.c_void_p()
+        _check(self._L.bbk_hreads_candidate_view(self._h, C.byref(r)))
+        return Reads.borrowed(self.ctx, r, self)
 
 
 class KmerStats(_Handle):
@@ -958,6 +1043,17 @@ class Corrector(_Handle):
         _check(self._L.bbk_corrector_correct(self._h, _ptr(bases), _ptr(qual), _ptr(offsets), n, _ptr(out), _ptr(res),
                                              _ptr(where)))
         return out, res, where
+
+    def correct_prepared(self, hr):
+        """the same over the trimmed reads of a HammerReads, from its resident bytes and corrector table ->
+        (corrected bases np.uint8, offsets np.uint64[n + 1], result np.uint8[n], where np.uint8[n])"""
+        n = len(hr)
+        out = np.zeros(hr.bases, dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        res = np.zeros(n, dtype=np.uint8)
+        where = np.zeros(n, dtype=np.uint8)
+        _check(self._L.bbk_corrector_correct_prepared(self._h, hr._h, _ptr(out), _ptr(off), _ptr(res), _ptr(where)))
+        return out[:int(off[n])], off, res, where
 
     @property
     def stats(self):

@@ -5,11 +5,15 @@
 //   -k/--kmer <int=21>  -t/--threads <int>  -b/--bufsize <bytes>  -o/--output <prefix>  -d/--dataset <yaml>  [input files...]
 //   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster, --subcluster with --singleton-threshold,
 //      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold, --expand with --expand-max-iterations <int=25>,
-//      --expand-min-changed <int=10>, --correct)
-// Every FASTQ record is cut into the stretches of its valid k-mer starts (hammer_reads.hpp: input_trim_quality 4 of
-// configs/hammer/config.info, then ValidKMerGenerator); a stretch is one read of the engine.
-//   pass 1  the stretches, in blocks of -b bytes, through bbk_count_begin / push / finish(BBK_BOTH_STRANDS)
-//   pass 2  the same files again: the same stretches with their qualities through bbk_kmerstats_push
+//      --expand-min-changed <int=10>, --correct, --resident-bytes <bytes=0>)
+// The records of every file go to the device as parsed, in blocks of -b bases, and are prepared there (bbk_hreads: the trim
+// of input_trim_quality 4 of configs/hammer/config.info, then ValidKMerGenerator's valid starts as stretches); a stretch is
+// one read of the engine.  Every pass takes a view of the prepared blocks:
+//   pass 1  the stretches through bbk_count_begin / push / finish(BBK_BOTH_STRANDS)
+//   pass 2  the same stretches with their qualities through bbk_kmerstats_push
+// With --resident-bytes 0 every pass parses the files again; otherwise the blocks of pass 1 stay on the device while their
+// bases and qualities total at most that many bytes, and the later passes parse only the blocks behind them.  The output
+// files are the same bytes either way.
 // Output:
 //   <prefix>.kmers        the ascending both-strand k-mers (final_kmers records), as spades-hamcluster writes them: index
 //                         i of the other files is record i
@@ -19,22 +23,23 @@
 //   <prefix>.kmstat then carries the good bit and the records of the new k-mers, and <prefix>.subclusters,
 //   <prefix>.subclusters.idx and <prefix>.newkmers are written (bbk_subclusters_write)
 //   with --expand (the solid k-mer expansion, projects/hammer/main.cpp:194-222 and expander.cpp:20-70; implies
-//   --subcluster): after the subclustering every round reads the files again and pushes the records the Expander can ever
-//   find solid (hammer_reads.hpp: expander_candidate), trimmed, in blocks of -b bytes through bbk_expander_push, until a
+//   --subcluster): after the subclustering every round pushes the records the Expander can ever find solid
+//   (bbk_hreads_candidate_view), trimmed, block by block through bbk_expander_push, until a
 //   round adds fewer than --expand-min-changed k-mers or --expand-max-iterations rounds have run; <prefix>.kmstat then
 //   carries the expanded good bits (bbk_expander_store) and every other file is as without --expand
 //   with --correct (ReadCorrector, projects/hammer/read_corrector.cpp and hammer_tools.cpp:79-142 CorrectReadFile; implies
-//   --expand): after the expansion every input file i is read once more as a single-read file: every record is trimmed
-//   (Read::trimNsAndBadQuality(--trim-quality)), corrected in blocks of -b bytes (bbk_corrector_correct) and printed in
+//   --expand): after the expansion every input file i is taken once more as a single-read file: every record is trimmed
+//   (Read::trimNsAndBadQuality(--trim-quality)), corrected block by block (bbk_corrector_correct_prepared) and printed in
 //   the format of Read::print to <prefix>.<i>.cor.fastq (result true) or <prefix>.<i>.bad.fastq
 // The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
 // common interface.
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "common.hpp"
-#include "hammer_reads.hpp"
 
 using namespace bbkhost;
 
@@ -59,7 +64,9 @@ static void usage(const char *argv0) {
            "        --expand                Also expand the solid k-mers over the reads they cover (implies --subcluster)\n"
            "        --expand-max-iterations <value>   expand_max_iterations (default 25)\n"
            "        --expand-min-changed <value>      Stop after an iteration that adds fewer k-mers than this (default 10)\n"
-           "        --correct               Also correct the reads with the expanded solid k-mers (implies --expand)\n\n"
+           "        --correct               Also correct the reads with the expanded solid k-mers (implies --expand)\n"
+           "        --resident-bytes <value>  Keep the first blocks on the GPU for the later passes while their bases and\n"
+           "                                qualities total at most this many bytes (default 0: every pass parses the input)\n\n"
            "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
            "        Output: <prefix>.kmers - the k-mers in ascending order, in the final_kmers record format;\n"
            "        <prefix>.kmstat - per k-mer: 32-bit count << 1, float total_qual, the 6-bit quality sums packed into 64-bit words;\n"
@@ -71,126 +78,189 @@ static void usage(const char *argv0) {
            argv0);
 }
 
-// one block of stretches: bases and qualities (offset subtracted) back to back, offsets for both
+// One block of records of one input file, as parsed, and its prepared batch on the device (bbk_hreads: the trims, the
+// stretches and the candidates of every record).  A resident block keeps the batch, the names, the qualities and the
+// offsets for the later passes -- what Read::print needs besides the corrected bases -- and lets the bases go.
 struct Block {
-    std::string bases, quals;
+    size_t file = 0;
+    std::string bases, quals;  // quals: the offset subtracted
     std::vector<uint64_t> offsets{0};
-    void clear() {
-        bases.clear();
-        quals.clear();
-        offsets.assign(1, 0);
-    }
+    std::vector<std::string> names;
+    bbk_hreads *hr = nullptr;
+    bool resident = false;
     uint64_t size() const { return offsets.size() - 1; }
+    uint64_t total() const { return offsets.back(); }
+    ~Block() { bbk_hreads_free(hr); }
 };
 
-// Calls push(block) for every block of at most block_bytes bases of the stretches of all records, in file order; returns
-// the number of records.  Both passes go through here, so they see the same stretches in the same blocks.  candidates:
-// the rounds of the expansion, which take the trimmed read of every record the Expander can ever find solid instead.
-template <class Push>
-static uint64_t for_each_block(const std::vector<std::string> &files, unsigned k, int qvoffset, int trim_quality,
-                               size_t block_bytes, bool announce, bool candidates, Push push) {
-    Block b;
-    std::string name, seq, qual;
-    std::vector<hammer::Stretch> st;
-    uint64_t records = 0;
-    for (const std::string &f : files) {
-        if (announce) info("Processing %s", f.c_str());
-        FastxReader rd(f);
-        if (!rd.is_open()) fatal("cannot open %s", f.c_str());
+// The records of all files as prepared blocks, in file order, once per pass.  A block holds the records of one file up to
+// -b bases, so every pass and every --resident-bytes sees the same blocks.  The blocks of the first pass stay on the
+// device while their bases and qualities fit --resident-bytes; the later passes take those as they are and parse the
+// files again only for the blocks behind them.
+class ReadSource {
+public:
+    ReadSource(bbk_ctx *ctx, const std::vector<std::string> &files, unsigned k, int qvoffset, int trim_quality, size_t block_bytes,
+               uint64_t resident_bytes)
+        : ctx_(ctx), files_(files), k_(k), qvoffset_(qvoffset), trim_quality_(trim_quality), block_bytes_(block_bytes),
+          budget_(resident_bytes), keeping_(resident_bytes != 0), kept_in_file_(files.size(), 0), whole_file_(files.size(), false) {}
+
+    // fn(block) for every block; returns the number of records
+    template <class F>
+    uint64_t each(bool announce, F fn) {
+        uint64_t records = 0;
+        for (const auto &b : resident_) {
+            fn(*b);
+            records += b->size();
+        }
+        for (size_t f = 0; f < files_.size(); ++f) {
+            if (whole_file_[f]) continue;
+            if (announce) info("Processing %s", files_[f].c_str());
+            records += parse(f, fn);
+        }
+        keeping_ = false;
+        return records;
+    }
+
+    void clear() { resident_.clear(); }  // the resident blocks leave the device
+
+private:
+    template <class F>
+    uint64_t parse(size_t f, F &fn) {
+        FastxReader rd(files_[f]);
+        if (!rd.is_open()) fatal("cannot open %s", files_[f].c_str());
+        std::unique_ptr<Block> b(new Block);
+        std::string name, seq, qual;
+        uint64_t records = 0, block_no = 0;
+        auto flush = [&] {
+            if (block_no++ >= kept_in_file_[f]) {  // the blocks before are resident and have been handed out
+                b->file = f;
+                check(bbk_hreads_from_host(ctx_, b->bases.data(), reinterpret_cast<const uint8_t *>(b->quals.data()), b->offsets.data(),
+                                           b->size(), k_, trim_quality_, &b->hr),
+                      "bbk_hreads_from_host");
+                fn(*b);
+                records += b->size();
+                if (keeping_ && held_ + 2 * b->total() <= budget_) {
+                    held_ += 2 * b->total();
+                    b->resident = true;
+                    std::string().swap(b->bases);
+                    ++kept_in_file_[f];
+                    resident_.push_back(std::move(b));
+                } else {
+                    keeping_ = false;  // the resident blocks are a prefix of all blocks
+                }
+            }
+            b.reset(new Block);
+        };
         while (rd.next_record(name, seq, qual)) {
             if (qual.size() != seq.size())
-                fatal("%s: record %llu (%s) has no quality string: the statistics need FASTQ input", f.c_str(),
+                fatal("%s: record %llu (%s) has no quality string: the statistics need FASTQ input", files_[f].c_str(),
                       (unsigned long long)records, name.c_str());
             for (char &c : qual) {
-                const int q = (unsigned char)c - qvoffset;
+                const int q = (unsigned char)c - qvoffset_;
                 if (q < 0 || q > 93)
-                    fatal("%s: record %llu (%s): quality character '%c' is outside [0, 93] at offset %d", f.c_str(),
-                          (unsigned long long)records, name.c_str(), c, qvoffset);
+                    fatal("%s: record %llu (%s): quality character '%c' is outside [0, 93] at offset %d", files_[f].c_str(),
+                          (unsigned long long)records, name.c_str(), c, qvoffset_);
                 c = (char)q;
             }
-            ++records;
-            st.clear();
-            hammer::Stretch whole;
-            if (!candidates) hammer::valid_stretches(seq, qual, k, trim_quality, st);
-            else if (hammer::expander_candidate(seq, qual, k, trim_quality, &whole)) st.push_back(whole);
-            for (const hammer::Stretch &s : st) {
-                b.bases.append(seq, s.start, s.length);
-                b.quals.append(qual, s.start, s.length);
-                b.offsets.push_back(b.bases.size());
+            b->bases += seq;
+            b->quals += qual;
+            b->offsets.push_back(b->bases.size());
+            b->names.push_back(name);
+            if (b->bases.size() >= block_bytes_) flush();
+        }
+        if (b->size()) flush();
+        if (keeping_) whole_file_[f] = true;
+        return records;
+    }
+
+    bbk_ctx *ctx_;
+    const std::vector<std::string> &files_;
+    unsigned k_;
+    int qvoffset_, trim_quality_;
+    size_t block_bytes_;
+    uint64_t budget_, held_ = 0;
+    bool keeping_;
+    std::vector<std::unique_ptr<Block>> resident_;
+    std::vector<uint64_t> kept_in_file_;  // resident blocks of every file: its first ones
+    std::vector<bool> whole_file_;        // every block of the file is resident
+};
+
+// CorrectReadFile (hammer_tools.cpp:107-142) over the blocks of all files: the trimmed reads of a block through the
+// corrector, printed as Read::print does (read.hpp:221-236) into the pair of files of the block's input file
+struct CorrectedWriter {
+    const std::vector<std::string> &files;
+    const std::string &prefix;
+    bbk_ctx *ctx;
+    bbk_corrector *cor;
+    int qvoffset;
+    size_t open_file = 0;
+    bool is_open = false;
+    FILE *good = nullptr, *bad = nullptr;
+    unsigned buffer_no = 0;
+    std::string out, line;
+    std::vector<uint64_t> offs;
+    std::vector<uint8_t> res;
+    std::vector<uint32_t> trims;
+
+    void close() {
+        if (is_open && (fclose(good) != 0 || fclose(bad) != 0)) fatal("writing the corrected reads failed");
+        is_open = false;
+    }
+    // the files of input file i, and of every file before it that had no block
+    void open_until(size_t i) {
+        while (!is_open || open_file < i) {
+            if (is_open) {
+                close();
+                ++open_file;
             }
-            if (b.bases.size() >= block_bytes) {
-                push(b);
-                b.clear();
-            }
+            if (open_file >= files.size()) return;
+            info("Correcting single reads: %s", files[open_file].c_str());
+            const std::string base = prefix + "." + std::to_string(open_file);
+            const std::string cor_path = base + ".cor.fastq", bad_path = base + ".bad.fastq";
+            good = fopen(cor_path.c_str(), "wb");
+            bad = fopen(bad_path.c_str(), "wb");
+            if (!good || !bad) fatal("cannot open %s for writing", (good ? bad_path : cor_path).c_str());
+            is_open = true;
+            buffer_no = 0;
         }
     }
-    if (b.size()) push(b);
-    return records;
-}
-
-// CorrectReadFile (hammer_tools.cpp:107-142) over one input file: trimmed records in blocks of block_bytes bases through the
-// corrector, printed as Read::print does (read.hpp:221-236)
-static void correct_read_file(bbk_corrector *cor, const std::string &file, int qvoffset, int trim_quality, size_t block_bytes,
-                              const std::string &cor_path, const std::string &bad_path) {
-    FastxReader rd(file);
-    if (!rd.is_open()) fatal("cannot open %s", file.c_str());
-    FILE *good = fopen(cor_path.c_str(), "wb"), *bad = fopen(bad_path.c_str(), "wb");
-    if (!good || !bad) fatal("cannot open %s for writing", (good ? bad_path : cor_path).c_str());
-    Block b;
-    std::vector<std::string> names;
-    std::vector<hammer::Trim> trims;
-    std::string out;
-    std::vector<uint8_t> res;
-    unsigned buffer_no = 0;
-    auto flush = [&] {
+    void finish() {
+        open_until(files.empty() ? 0 : files.size() - 1);
+        close();
+    }
+    void operator()(const Block &b) {
+        open_until(b.file);
         info("Prepared batch %u of %llu reads.", buffer_no, (unsigned long long)b.size());
-        out.resize(b.bases.size());
+        out.resize(b.total());
+        offs.resize(b.size() + 1);
         res.resize(b.size());
-        check(bbk_corrector_correct(cor, b.bases.data(), reinterpret_cast<const uint8_t *>(b.quals.data()), b.offsets.data(),
-                                    b.size(), &out[0], res.data(), nullptr),
-              "bbk_corrector_correct");
+        trims.resize(2 * b.size());
+        check(bbk_corrector_correct_prepared(cor, b.hr, &out[0], offs.data(), res.data(), nullptr), "bbk_corrector_correct_prepared");
+        check(bbk_hreads_export(ctx, b.hr, trims.data(), nullptr, nullptr, nullptr, nullptr, nullptr), "bbk_hreads_export");
         info("Processed batch %u", buffer_no);
-        std::string line;
         for (uint64_t i = 0; i < b.size(); ++i) {
-            const hammer::Trim &t = trims[i];
-            const size_t o = b.offsets[i], len = b.offsets[i + 1] - o;
-            const int tail = t.initial_size_ - t.rtrim_;
-            line.assign("@").append(names[i]).append("\n").append((size_t)t.ltrim_, 'N').append(out, o, len).append((size_t)tail, 'N');
-            line.append("\n+").append(names[i]);
-            if (t.ltrim_ > 0) line.append(" ltrim=").append(std::to_string(t.ltrim_));
-            if (t.rtrim_ < t.initial_size_) line.append(" rtrim=").append(std::to_string(tail));
-            line.append("\n").append((size_t)t.ltrim_, (char)(qvoffset + 2));
-            for (size_t j = 0; j < len; ++j) line.push_back((char)(b.quals[o + j] + qvoffset));
-            line.append((size_t)tail, (char)(qvoffset + 2)).append("\n");
+            // Read::trimLeftRight's bookkeeping (read.hpp:99-122): ltrim_ / rtrim_ are the ends of what is left, or 0 and
+            // the size when nothing is
+            const size_t initial = b.offsets[i + 1] - b.offsets[i], start = trims[2 * i], len = trims[2 * i + 1];
+            const size_t ltrim = len ? start : 0, rtrim = len ? start + len : initial, tail = initial - rtrim;
+            const size_t o = offs[i], q0 = b.offsets[i] + start;
+            line.assign("@").append(b.names[i]).append("\n").append(ltrim, 'N').append(out, o, len).append(tail, 'N');
+            line.append("\n+").append(b.names[i]);
+            if (ltrim > 0) line.append(" ltrim=").append(std::to_string(ltrim));
+            if (rtrim < initial) line.append(" rtrim=").append(std::to_string(tail));
+            line.append("\n").append(ltrim, (char)(qvoffset + 2));
+            for (size_t j = 0; j < len; ++j) line.push_back((char)(b.quals[q0 + j] + qvoffset));
+            line.append(tail, (char)(qvoffset + 2)).append("\n");
             if (fwrite(line.data(), 1, line.size(), res[i] ? good : bad) != line.size()) fatal("writing the corrected reads failed");
         }
         info("Written batch %u", buffer_no);
         ++buffer_no;
-        b.clear();
-        names.clear();
-        trims.clear();
-    };
-    std::string name, seq, qual;
-    uint64_t records = 0;
-    while (rd.next_record(name, seq, qual)) {
-        if (qual.size() != seq.size()) fatal("%s: record %llu (%s) has no quality string", file.c_str(), (unsigned long long)records, name.c_str());
-        for (char &c : qual) c = (char)((unsigned char)c - qvoffset);  // checked in the first pass
-        ++records;
-        const hammer::Trim t = hammer::trim_ns_and_bad_quality(seq, qual, trim_quality);
-        b.bases.append(seq, t.start, t.length);
-        b.quals.append(qual, t.start, t.length);
-        b.offsets.push_back(b.bases.size());
-        names.push_back(name);
-        trims.push_back(t);
-        if (b.bases.size() >= block_bytes) flush();
     }
-    if (b.size()) flush();
-    if (fclose(good) != 0 || fclose(bad) != 0) fatal("writing the corrected reads failed");
-}
+};
 
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
-    unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4;
+    unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4, resident_bytes = 0;
     std::string prefix, dataset;
     std::vector<std::string> input;
     unsigned expand_max_iterations = 25;  // configs/hammer/config.info
@@ -199,7 +269,7 @@ int main(int argc, char **argv) {
     bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
     Options opt;
     opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
-        .num("", "--qvoffset", &qvoffset).num("", "--trim-quality", &trim_quality).flag("", "--cluster", &cluster)
+        .num("", "--resident-bytes", &resident_bytes).num("", "--qvoffset", &qvoffset).num("", "--trim-quality", &trim_quality).flag("", "--cluster", &cluster)
         .flag("", "--subcluster", [&] { cluster = subcluster = true; })
         .flag("", "--expand", [&] { cluster = subcluster = expand = true; })
         .flag("", "--correct", [&] { cluster = subcluster = expand = correct = true; })
@@ -229,9 +299,12 @@ int main(int argc, char **argv) {
     check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
     uint64_t stretches = 0;
     double t0 = now_s();
-    const uint64_t records = for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, true, false, [&](const Block &b) {
-        check(bbk_count_push_ascii(counter, b.bases.data(), b.offsets.data(), b.size()), "bbk_count_push_ascii");
-        stretches += b.size();
+    ReadSource src(ctx, files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, resident_bytes);
+    const uint64_t records = src.each(true, [&](const Block &b) {
+        const bbk_reads *r = nullptr;
+        check(bbk_hreads_stretch_view(b.hr, &r, nullptr), "bbk_hreads_stretch_view");
+        check(bbk_count_push_reads(counter, r), "bbk_count_push_reads");
+        stretches += bbk_hreads_kmer_stretches(b.hr);
         ++ph.blocks;
     });
     info("Total %llu reads processed, %llu stretches of valid k-mers", (unsigned long long)records,
@@ -248,15 +321,11 @@ int main(int argc, char **argv) {
     info("Collecting K-mer information");
     bbk_kmerstats *ks = nullptr;
     check(bbk_kmerstats_begin(ctx, set, &ks), "bbk_kmerstats_begin");
-    for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, false, false, [&](const Block &b) {
-        bbk_reads *r = nullptr;
-        bbk_quals *q = nullptr;
-        check(bbk_reads_from_ascii(ctx, b.bases.data(), b.offsets.data(), b.size(), &r), "bbk_reads_from_ascii");
-        check(bbk_quals_from_host(ctx, r, reinterpret_cast<const uint8_t *>(b.quals.data()), b.offsets.data(), b.size(), &q),
-              "bbk_quals_from_host");
+    src.each(false, [&](const Block &b) {
+        const bbk_reads *r = nullptr;
+        const bbk_quals *q = nullptr;
+        check(bbk_hreads_stretch_view(b.hr, &r, &q), "bbk_hreads_stretch_view");
         check(bbk_kmerstats_push(ks, r, q), "bbk_kmerstats_push");
-        bbk_quals_free(q);
-        bbk_reads_free(r);
     });
     check(bbk_kmerstats_finish(ks), "bbk_kmerstats_finish");
     ph.device = now_s() - t0;
@@ -281,12 +350,12 @@ int main(int argc, char **argv) {
             info("Starting solid k-mers expansion in snapshot rounds.");
             for (unsigned iter = 0; iter < expand_max_iterations; ++iter) {
                 check(bbk_expander_round_begin(ex), "bbk_expander_round_begin");
-                for_each_block(files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, false, true, [&](const Block &b) {
-                    bbk_reads *r = nullptr;
-                    check(bbk_reads_from_ascii(ctx, b.bases.data(), b.offsets.data(), b.size(), &r), "bbk_reads_from_ascii");
+                src.each(false, [&](const Block &b) {
+                    const bbk_reads *r = nullptr;
+                    check(bbk_hreads_candidate_view(b.hr, &r), "bbk_hreads_candidate_view");
                     check(bbk_expander_push(ex, r, nullptr), "bbk_expander_push");
-                    check(bbk_ctx_synchronize(ctx), "bbk_ctx_synchronize");  // push does not wait, and the reads go now
-                    bbk_reads_free(r);
+                    // push does not wait, and a block that is not resident goes now
+                    if (!b.resident) check(bbk_ctx_synchronize(ctx), "bbk_ctx_synchronize");
                 });
                 uint64_t changed = 0;
                 check(bbk_expander_round_end(ex, &changed), "bbk_expander_round_end");
@@ -299,12 +368,9 @@ int main(int argc, char **argv) {
                 bbk_corrector *cor = nullptr;
                 check(bbk_corrector_from_expander(ctx, set, ex, &cor), "bbk_corrector_from_expander");
                 info("Starting read correction.");
-                for (size_t i = 0; i < files.size(); ++i) {
-                    info("Correcting single reads: %s", files[i].c_str());
-                    const std::string base = prefix + "." + std::to_string(i);
-                    correct_read_file(cor, files[i], (int)qvoffset, (int)trim_quality, (size_t)bufsize, base + ".cor.fastq",
-                                      base + ".bad.fastq");
-                }
+                CorrectedWriter w{files, prefix, ctx, cor, (int)qvoffset};
+                src.each(false, std::ref(w));
+                w.finish();
                 uint64_t cs[5];
                 check(bbk_corrector_stats(cor, cs), "bbk_corrector_stats");
                 info("Correction done. Changed %llu bases in %llu reads.", (unsigned long long)cs[1], (unsigned long long)cs[0]);
@@ -357,6 +423,7 @@ int main(int argc, char **argv) {
         info("There are %llu kmers in total. Among them %llu (%g%%) are singletons.", (unsigned long long)n,
              (unsigned long long)singletons, n ? 100.0 * (double)singletons / (double)n : 0.0);
     }
+    src.clear();
     bbk_kmerstats_free(ks);
     bbk_kmerset_free(set);
     ph.write = now_s() - t0;
