@@ -50,7 +50,7 @@ int bbk_ctx_set_stream(bbk_ctx *ctx, void *hip_stream);
 int bbk_ctx_synchronize(bbk_ctx *ctx);
 /* Returns device memory the allocator holds but does not use to the driver -- where that is safe: the block-cache
  * allocator (BBK_NO_VMM=1) frees its cached blocks; the default arena allocator keeps its mapped high-water mark for the
- * life of the process (unmapping and re-mapping chunks faults on this platform, see primitives.hip). */
+ * life of the process (unmapping and re-mapping chunks faults on this platform, see pool.hip). */
 int bbk_ctx_trim(bbk_ctx *ctx);
 /* Accumulated HIP-event time (ms) and launch count of one named kernel family since the last
  * reset ("extract", "hist", "scan", "scatter", "unique", "expand", "mask", "walk", ...).
@@ -707,9 +707,10 @@ int bbk_group_gather_extindex(bbk_group *g, int rank, bbk_ctx *ctx, const bbk_ex
 /* the same for a sharded set with multiplicities -> one ascending set on rank dst (gbuilder -c: the (k+1)-mer counts) */
 int bbk_group_gather_kmers(bbk_group *g, int rank, bbk_ctx *ctx, const bbk_kmerset *shard, int dst, bbk_kmerset **full);
 
-/* Device memory of the calling thread's allocator on the context's device: bytes mapped now, bytes mapped since the
- * process started (growth is what a first call pays: ~30 ms/GiB when the driver has to clear the memory first), seconds
- * spent mapping, and the device's free / total bytes as the driver reports them.  Any pointer may be NULL. */
+/* Device memory of the allocator: *mapped_now = bytes the calling thread's arenas on the context's device hold mapped;
+ * *mapped_total / *map_seconds = bytes mapped, and seconds spent mapping, since the process started, by every thread on
+ * every device (growth is what a first call pays: ~30 ms/GiB when the driver has to clear the memory first); and the
+ * device's free / total bytes as the driver reports them.  Any pointer may be NULL. */
 int bbk_ctx_memory_stats(bbk_ctx *ctx, uint64_t *mapped_now, uint64_t *mapped_total, double *map_seconds,
                          uint64_t *device_free, uint64_t *device_total);
 /* What the engine found on the device at bbk_ctx_create: compute units, and the XCDs a probe launch's workgroups were seen

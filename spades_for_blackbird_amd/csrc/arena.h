@@ -1,4 +1,4 @@
-// arena.h -- bookkeeping of the device allocator's arena (primitives.hip): physical chunks are mapped one after the
+// arena.h -- bookkeeping of the device allocator's arena (pool.hip): physical chunks are mapped one after the
 // other into a reserved virtual range; inside the backed part a best-fit free list with coalescing.  Pure host data
 // structure (no HIP calls: mapping and unmapping are the caller's), so that it can be exercised by a host-only
 // randomized test (tests/test_arena.py).

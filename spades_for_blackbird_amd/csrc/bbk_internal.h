@@ -1,5 +1,6 @@
-// bbk_internal.h -- host-side plumbing shared by the HIP translation units (context, errors,
-// device buffers, per-kernel-family HIP-event timing).  Not part of the C ABI.
+// bbk_internal.h -- the one internal include of the HIP translation units: errors, device buffers, the context with its
+// timers, launch helpers and waits, copies, the handle structs, and the scan / sort / unique primitives.  Each section is
+// headed by the file that defines what it declares.  Not part of the C ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,9 +17,11 @@
 
 #include "../../include/bbk.h"
 
+// ---- errors (context.hip) -------------------------------------------------------------------------------------------
 namespace bbk {
 
 void set_error(const char *fmt, ...);
+const char *get_error();
 
 struct Error {
     int code;
@@ -59,12 +62,16 @@ int guarded(F &&f) {
     }
 }
 
+// ---- device allocator (pool.hip) ------------------------------------------------------------------------------------
 void *pool_alloc(size_t bytes, size_t *granted, int *device);  // on the current device
 void pool_free(void *p, size_t bytes, int device);
 void pool_trim(int device);  // gives the free memory this (device, host thread) holds back to the driver
 void pool_report();          // allocator statistics to stderr
-size_t pool_mapped_bytes(int device);
-void pool_stats(int device, uint64_t *mapped_now, uint64_t *mapped_total, double *map_seconds);  // calling thread's arenas  // device memory the arenas of all host threads hold mapped on `device`
+size_t pool_mapped_bytes(int device);  // device memory the arenas of all host threads hold mapped on `device`
+// *mapped_now: what the calling thread's arenas on `device` hold mapped; *mapped_total, *map_seconds: bytes mapped and
+// seconds spent mapping since the process started, by every thread on every device
+void pool_stats(int device, uint64_t *mapped_now, uint64_t *mapped_total, double *map_seconds);
+bool pool_owns(const void *p);  // the address lies in an arena of the allocator
 
 // Owning device buffer.
 struct DevBuf {
@@ -91,7 +98,7 @@ struct DevBuf {
         return *this;
     }
     ~DevBuf() { release(); }
-    // Device memory comes from a caching pool (primitives.hip) keyed by (device, host thread): hipMalloc/hipFree of
+    // Device memory comes from a caching pool (pool.hip) keyed by (device, host thread): hipMalloc/hipFree of
     // multi-GB buffers cost far more than the kernels that use them, and every step of the path
     // asks for the same sizes again.  All work of a context is issued on one stream, so handing a
     // released block to the next request of the same context is stream-ordered and needs no synchronisation.
@@ -113,27 +120,7 @@ struct DevBuf {
     }
 };
 
-// Device-to-device / default-kind copies of the library: one place to change how they are done.
-hipError_t copy_async(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t stream);
-bool pool_owns(const void *p);  // the address lies in an arena of the allocator
-
-// std::vector whose resize() does not zero-fill (multi-hundred-MB host buffers that are about to
-// be overwritten by a device-to-host copy)
-template <class T>
-struct default_init_alloc : std::allocator<T> {
-    template <class U>
-    struct rebind {
-        using other = default_init_alloc<U>;
-    };
-    template <class U, class... A>
-    void construct(U *p, A &&...a) {
-        if constexpr (sizeof...(A) == 0) ::new ((void *)p) U;
-        else ::new ((void *)p) U(std::forward<A>(a)...);
-    }
-};
-template <class T>
-using raw_vector = std::vector<T, default_init_alloc<T>>;
-
+// ---- context, timers, launches, waits (context.hip) -----------------------------------------------------------------
 struct FamilyStat {
     double ms = 0;
     uint64_t launches = 0;
@@ -283,50 +270,68 @@ void launch_items_timed(bbk_ctx *ctx, const char *family, K fn, uint64_t n_threa
     launch_items(ctx, family, fn, n_threads, args...);
 }
 
+// free device memory (see bbk_ctx::mem_free)
+size_t device_free_cached(bbk_ctx *ctx);
+// the context's pinned planning block, at least `bytes` long
+void *plan_staging(bbk_ctx *ctx, size_t bytes);
+
+// ---- copies (context.hip) -------------------------------------------------------------------------------------------
+// Device-to-device / default-kind copies of the library: one place to change how they are done.
+hipError_t copy_async(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t stream);
+
+// std::vector whose resize() does not zero-fill (multi-hundred-MB host buffers that are about to
+// be overwritten by a device-to-host copy)
+template <class T>
+struct default_init_alloc : std::allocator<T> {
+    template <class U>
+    struct rebind {
+        using other = default_init_alloc<U>;
+    };
+    template <class U, class... A>
+    void construct(U *p, A &&...a) {
+        if constexpr (sizeof...(A) == 0) ::new ((void *)p) U;
+        else ::new ((void *)p) U(std::forward<A>(a)...);
+    }
+};
+template <class T>
+using raw_vector = std::vector<T, default_init_alloc<T>>;
+
 // Large device -> host copy through the context's pinned staging buffers (chunked, two buffers:
 // the copy of chunk i+1 overlaps the host memcpy of chunk i).
 void d2h_big(bbk_ctx *ctx, void *dst, const void *src, size_t bytes);
-
-// Device -> file: chunks through the pinned staging buffers (copy of chunk i+1 overlaps the positional writes of
-// chunk i, several writers per chunk).  Returns false on a short write.
+// Device -> file through the same pump (the copy of chunk i+1 overlaps the positional writes of chunk i, several writers
+// per chunk).  Returns false on a short write.
 bool d2f_big(bbk_ctx *ctx, int fd, uint64_t file_off, const void *src, size_t bytes);
 
-// ---- primitives.hip -------------------------------------------------------------------------
-// One LSD pass selector: kind 0 = bits [shift, shift+bits) of key word `word`;
-// kind 1 = XXH3 bucket (kmer_buckets.hpp:28-33) with nb <= 256 buckets;
-// kind 2 = owner(mix(key), nb) for the multi-GPU partition.
-struct PassDesc {
-    int kind;
-    int word;
-    int shift;
-    int bits;
-    unsigned nb;
+}  // namespace bbk
+
+// ---- handles (bbk_extindex: below, behind its PrefixIndex) ----------------------------------------------------------
+struct bbk_reads {
+    bbk_ctx *ctx = nullptr;
+    uint64_t n = 0;        // reads
+    uint64_t n_words = 0;  // packed words
+    uint64_t bases = 0;    // total bases (sum of len)
+    const uint64_t *d_words = nullptr;
+    const uint64_t *d_woff = nullptr;  // n+1
+    const uint32_t *d_len = nullptr;   // n
+    bbk::DevBuf own_words, own_woff, own_len;
 };
 
-// Key-bit passes that sort records of W words into the reference order (word 0 most
-// significant, adt/array_vector.hpp:114-123) given that only the low 2k bits are populated.
-std::vector<PassDesc> key_passes(unsigned k);
+struct bbk_kmerset {
+    unsigned k = 0, W = 0;
+    unsigned flags = 0;
+    uint64_t n = 0;          // distinct records
+    uint64_t instances = 0;  // k-mer instances that entered the sort
+    bbk::DevBuf keys;        // n * W u64, ascending
+    bbk::DevBuf counts;      // n u32 (optional)
+    bool has_counts = false;
+    bool sorted = true;      // false: distinct but in hash-bucket order (BBK_UNSORTED)
+    bool ref_order = false;  // true: final_kmers order (16 XXH3 buckets, ascending inside) instead of ascending
+};
 
-// Stable LSD radix sort of n records (W u64 words each, optional u32 payload). keys/vals are
-// sorted in place; tmp buffers must hold n records.  n < 2^32.
-void sort_records(bbk_ctx *ctx, int W, void *keys, void *keys_tmp, uint32_t *vals, uint32_t *vals_tmp, uint64_t n,
-                  const std::vector<PassDesc> &passes);
-// Per-bin record counts of one pass (256 bins, written to h_counts), e.g. bucket sizes.
-// one stable counting pass src -> dst (device buffers, not aliased) on the digit `pd`; h_digit_totals (256 entries,
-// optional) receives the number of records of every digit value
-void partition_records(bbk_ctx *ctx, int W, const void *src, void *dst, const uint32_t *vsrc, uint32_t *vdst, uint64_t n,
-                       const PassDesc &pd, uint64_t *h_digit_totals = nullptr);
+namespace bbk {
 
-enum ReduceOp { REDUCE_COUNT = 0, REDUCE_SUM = 1, REDUCE_OR = 2 };
-// Unique of a sorted record array: distinct keys to out_keys (may alias nothing), per-key reduction of
-// vals (COUNT: run length, SUM: sum of vals, OR: or of vals) to out_vals (may be null for COUNT-less).
-// Returns the number of distinct keys.  drop_zero: omit keys whose reduced value is 0 (OR mode).
-uint64_t unique_records(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, void *out_keys,
-                        uint32_t *out_vals, ReduceOp op, bool drop_zero);
-// The (key, val) pairs with val != 0, in their order, into out_* (allocated only when something is dropped); returns how
-// many were kept.
-uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
-                        DevBuf &out_vals);
+// ---- scan (scan.hip) ------------------------------------------------------------------------------------------------
 // Exclusive scan of n u64 values (in place allowed); returns the total.
 uint64_t exclusive_scan_u64(bbk_ctx *ctx, const uint64_t *in, uint64_t *out, uint64_t n);
 // Two arrays of n values in the same launches and ONE wait; out0[n] and out1[n] receive the totals as well (the
@@ -352,48 +357,6 @@ struct ScanSrc {
 // the caller has waited for the stream.
 void exclusive_scan_enqueue(bbk_ctx *ctx, int narr, const ScanSrc *src, uint64_t *const *out, uint64_t n,
                             uint64_t *d_total, bool tail, std::vector<DevBuf> &keep);
-// extindex.hip: the prefix table over an ascending key array of n records (W words, k-mer size k) that table_find
-// (kmer_ops.h) reads: (1 << bits) + 1 entries, u32 (u64 when `wide`: 2^32 - 2 records or more).  It remembers the W and
-// k it was built for, so table() is the only place that derives the shift a lookup applies to word 0.
-struct PrefixTable;
-struct PrefixIndex {
-    DevBuf buf;
-    unsigned bits = 0;
-    bool wide = false;
-    unsigned W = 0, k = 0;
-    void build(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n);  // waits for the stream
-    PrefixTable table() const;
-};
-// free device memory (see bbk_ctx::mem_free)
-size_t device_free_cached(bbk_ctx *ctx);
-// the context's pinned planning block, at least `bytes` long
-void *plan_staging(bbk_ctx *ctx, size_t bytes);
-
-}  // namespace bbk
-
-// Exported for the tests only (not declared in bbk.h): exclusive_scan2_u64 in place over two device arrays of n + 1 u64
-// each (entries 0..n-1 are the input, entry n receives the total); totals[2] on the host receives the two sums.
-extern "C" int bbk_scan2_u64(bbk_ctx *ctx, void *d_a, void *d_b, uint64_t n, uint64_t *totals);
-// ... and the read plan (msd.hip): the tile geometry of the counting paths at k, and the plan of a read set with the
-// descriptors of its tiles, copied to the host
-struct bbk_reads;
-extern "C" int bbk_read_plan_geometry(unsigned k, uint32_t *out);
-extern "C" int bbk_read_plan(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, unsigned tile, int superk,
-                             uint64_t *coff, uint64_t *totals, uint32_t *unordered, void *tiles, uint64_t tile_cap,
-                             uint64_t *n_tiles);
-
-struct bbk_reads {
-    bbk_ctx *ctx = nullptr;
-    uint64_t n = 0;        // reads
-    uint64_t n_words = 0;  // packed words
-    uint64_t bases = 0;    // total bases (sum of len)
-    const uint64_t *d_words = nullptr;
-    const uint64_t *d_woff = nullptr;  // n+1
-    const uint32_t *d_len = nullptr;   // n
-    bbk::DevBuf own_words, own_woff, own_len;
-};
-
-namespace bbk {
 
 // What a pass over a read set needs before its first tile: the k-mers of the reads, their units of C k-mer positions
 // (chunks of the level-1 kernels, super-k-mer segments; C = 1: the k-mers themselves) and the exclusive scan of the
@@ -408,20 +371,60 @@ struct ReadPlan {
     void run(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, uint32_t *d_unordered);
 };
 
-}  // namespace bbk
-
-struct bbk_kmerset {
-    unsigned k = 0, W = 0;
-    unsigned flags = 0;
-    uint64_t n = 0;          // distinct records
-    uint64_t instances = 0;  // k-mer instances that entered the sort
-    bbk::DevBuf keys;        // n * W u64, ascending
-    bbk::DevBuf counts;      // n u32 (optional)
-    bool has_counts = false;
-    bool sorted = true;      // false: distinct but in hash-bucket order (BBK_UNSORTED)
-    bool ref_order = false;  // true: final_kmers order (16 XXH3 buckets, ascending inside) instead of ascending
+// ---- sort (sort.hip) ------------------------------------------------------------------------------------------------
+// One LSD pass selector: kind 0 = bits [shift, shift+bits) of key word `word`;
+// kind 1 = XXH3 bucket (kmer_buckets.hpp:28-33) with nb <= 256 buckets;
+// kind 2 = owner(mix(key), nb) for the multi-GPU partition.
+struct PassDesc {
+    int kind;
+    int word;
+    int shift;
+    int bits;
+    unsigned nb;
 };
 
+// Key-bit passes that sort records of W words into the reference order (word 0 most
+// significant, adt/array_vector.hpp:114-123) given that only the low 2k bits are populated.
+std::vector<PassDesc> key_passes(unsigned k);
+
+// Stable LSD radix sort of n records (W u64 words each, optional u32 payload). keys/vals are
+// sorted in place; tmp buffers must hold n records.  n < 2^32.
+void sort_records(bbk_ctx *ctx, int W, void *keys, void *keys_tmp, uint32_t *vals, uint32_t *vals_tmp, uint64_t n,
+                  const std::vector<PassDesc> &passes);
+// one stable counting pass src -> dst (device buffers, not aliased) on the digit `pd`; h_digit_totals (256 entries,
+// optional) receives the number of records of every digit value
+void partition_records(bbk_ctx *ctx, int W, const void *src, void *dst, const uint32_t *vsrc, uint32_t *vdst, uint64_t n,
+                       const PassDesc &pd, uint64_t *h_digit_totals = nullptr);
+
+// ---- unique (unique.hip) --------------------------------------------------------------------------------------------
+enum ReduceOp { REDUCE_COUNT = 0, REDUCE_SUM = 1, REDUCE_OR = 2 };
+// Unique of a sorted record array: distinct keys to out_keys (may alias nothing), per-key reduction of
+// vals (COUNT: run length, SUM: sum of vals, OR: or of vals) to out_vals (may be null for COUNT-less).
+// Returns the number of distinct keys.  drop_zero: omit keys whose reduced value is 0 (OR mode).
+uint64_t unique_records(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, void *out_keys,
+                        uint32_t *out_vals, ReduceOp op, bool drop_zero);
+// The (key, val) pairs with val != 0, in their order, into out_* (allocated only when something is dropped); returns how
+// many were kept.
+uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
+                        DevBuf &out_vals);
+
+// ---- prefix table (extindex.hip) ------------------------------------------------------------------------------------
+// The prefix table over an ascending key array of n records (W words, k-mer size k) that table_find
+// (kmer_ops.h) reads: (1 << bits) + 1 entries, u32 (u64 when `wide`: 2^32 - 2 records or more).  It remembers the W and
+// k it was built for, so table() is the only place that derives the shift a lookup applies to word 0.
+struct PrefixTable;
+struct PrefixIndex {
+    DevBuf buf;
+    unsigned bits = 0;
+    bool wide = false;
+    unsigned W = 0, k = 0;
+    void build(bbk_ctx *ctx, const uint64_t *keys, unsigned W, unsigned k, uint64_t n);  // waits for the stream
+    PrefixTable table() const;
+};
+
+}  // namespace bbk
+
+// (the one handle down here: it holds a PrefixIndex by value)
 struct bbk_extindex {
     unsigned k = 0, W = 0;
     uint64_t n = 0;
@@ -430,3 +433,17 @@ struct bbk_extindex {
     bbk::DevBuf masks;  // n u8
     bbk::PrefixIndex prefix;  // lookup accelerator over keys
 };
+
+// ---- exported for the tests only (not declared in bbk.h) ------------------------------------------------------------
+// scan.hip: exclusive_scan2_u64 in place over two device arrays of n + 1 u64 each (entries 0..n-1 are the input, entry n
+// receives the total); totals[2] on the host receives the two sums.
+extern "C" int bbk_scan2_u64(bbk_ctx *ctx, void *d_a, void *d_b, uint64_t n, uint64_t *totals);
+// context.hip: `bytes` of device memory through d2h_big into h_dst (when not NULL) and through d2f_big to offset 0 of fd
+// (when fd >= 0)
+extern "C" int bbk_staged_copy(bbk_ctx *ctx, const void *d_src, uint64_t bytes, void *h_dst, int fd);
+// msd.hip: the tile geometry of the counting paths at k, and the plan of a read set with the descriptors of its tiles,
+// copied to the host
+extern "C" int bbk_read_plan_geometry(unsigned k, uint32_t *out);
+extern "C" int bbk_read_plan(bbk_ctx *ctx, const bbk_reads *rd, unsigned k, unsigned C, unsigned tile, int superk,
+                             uint64_t *coff, uint64_t *totals, uint32_t *unordered, void *tiles, uint64_t tile_cap,
+                             uint64_t *n_tiles);

@@ -184,7 +184,7 @@ void exchange_segments(bbk_group *g, int rank, bbk_ctx *ctx, size_t rec, const D
             uint64_t pstart = 0;
             for (int j = 0; j < rank; ++j) pstart += g->counts[p][j];
             const uint64_t cap = std::max<uint64_t>(1, g->max_msg / rec);
-            for (uint64_t q = 0; q < c; q += cap) {  // pieces: see bbk::copy_async
+            for (uint64_t q = 0; q < c; q += cap) {  // pieces of at most max_msg bytes, as in the message rounds
                 const uint64_t m = std::min(cap, c - q);
                 BBK_HIP(hipMemcpyPeerAsync(recv_k.as<char>() + (rstart[p] + q) * rec, g->devices[rank],
                                            (const char *)g->send_keys[p] + (pstart + q) * rec, g->devices[p], m * rec, ctx->stream));
@@ -298,7 +298,7 @@ void gather_arrays(bbk_group *g, int rank, bbk_ctx *ctx, size_t rec, const DevBu
             for (int p = 0; p < g->n; ++p) {
                 const uint64_t c = g->gather_n[p];
                 if (c && (p == dst || g->exchange == BBK_EXCHANGE_COPY)) {
-                    for (uint64_t q = 0; q < c; q += cap) {  // pieces: see bbk::copy_async
+                    for (uint64_t q = 0; q < c; q += cap) {  // pieces of at most max_msg bytes, as in the message rounds
                         const uint64_t m = std::min(cap, c - q);
                         BBK_HIP(hipMemcpyPeerAsync(rk.as<char>() + (o + q) * rec, g->devices[rank],
                                                    (const char *)g->gather_keys[p] + q * rec, g->devices[p], m * rec, ctx->stream));

@@ -7,7 +7,7 @@
 // filtered (count >= ci, saturated at cs) and kept on the device as keys + u16 counts; finish() concatenates the key
 // arrays, merge-uniques them with the engine's own sort (bbk_kmerset_from_device_ex), scatters every sample's counts
 // into rows[union position * N + sample] through the prefix table + binary search, applies the keep rule per union
-// k-mer and compacts keys and rows through the scan of primitives.hip.
+// k-mer and compacts keys and rows through the scan of scan.hip.
 //
 // Abundance: replaces ProfileCounter::operator() (projects/mts/contig_abundance.cpp:245-284) with the winsorised mean
 // of TrivialClusterAnalyzer (:46-78).  A contig is the run of pieces (maximal ACGT stretches) the caller cut it into.

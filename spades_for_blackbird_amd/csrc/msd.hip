@@ -1,7 +1,7 @@
 // msd.hip -- the fast sort-and-count path: two MSD radix-partition levels in HBM, then one
 // workgroup per bucket deduplicates / sorts + reduces its keys entirely in LDS.
 //
-// Why: the LSD path (primitives.hip) moves every record 3x per 8-bit pass (k=21: 6 passes, ~19 N*W
+// Why: the LSD path (sort.hip) moves every record 3x per 8-bit pass (k=21: 6 passes, ~19 N*W
 // bytes).  Here a record is written by the (fused) extraction+partition, read and written once
 // more by the second partition level and read once by the bucket kernel, independent of the key
 // length, and the duplicate-heavy k-mer stream (50x coverage) collapses inside LDS.

@@ -1,6 +1,6 @@
 """GPU: the general (LSD) path of counting, merging and the extension index, and the sort / unique / scan primitives it
 is built on (count.hip: LsdSort behind dedup_reads' extract + sort + unique, lsd_sort_unique, expand_both_strands'
-expand + sort and the ascending export of a final_kmers set; primitives.hip: sort_records, unique_records,
+expand + sort and the ascending export of a final_kmers set; sort.hip / unique.hip / scan.hip: sort_records, unique_records,
 exclusive_scan_u64).
 
 The engine takes this path whenever an MSD pass declines (one k-mer making up more than a quarter of a batch: poly-A
@@ -33,7 +33,7 @@ LSD_FAMILIES = ("extract", "expand", "hist", "scatter", "unique")
 MSD_FAMILIES = ("k_part_reads_narrow", "k_part_reads", "k_bucket_hash", "k_bucket_hashidx", "k_bucket_dist", "k_bucket",
                 "k_sk_dedup", "k_sk_dedup_B", "k_sk_part1")
 BUCKET_FAMILIES = ("k_bucket_hash", "k_bucket_hashidx", "k_bucket_dist", "k_bucket")
-TILE = {1: 4096, 2: 2048, 3: 2048, 4: 1024}  # SortCfg<W>::TILE (primitives.hip)
+TILE = {1: 4096, 2: 2048, 3: 2048, 4: 1024}  # SortCfg<W>::TILE (sort.hip)
 K_CHUNK = 256                                # tiles per chunk of k_colsum / k_tile_offsets
 UNIQ_TILE = 2048                             # kUniqTile of k_head_count / k_head_compact
 SCAN_TILE = 2048                             # kScanTile of exclusive_scan_u64
