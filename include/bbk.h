@@ -672,6 +672,50 @@ int bbk_corrector_correct_prepared(bbk_corrector *c, const bbk_hreads *hr, char 
                                    uint8_t *h_result, uint8_t *h_where);
 void bbk_hreads_free(bbk_hreads *hr);
 
+/* ---- corrected reads as FASTQ text: replaces the last step of CorrectAllReads (projects/hammer/hammer_tools.cpp:107-193:
+ *      CorrectReadFile, CorrectPairedReadFiles), the BH: tags of ReadCorrector::CorrectOneRead
+ *      (projects/hammer/read_corrector.cpp:214-242) and Read::print (common/io/reads/read.hpp:221-236) -- the outcome of a
+ *      batch stays in HBM, and the text of every output file is formatted there ------------------------------------------ */
+typedef struct bbk_corrected bbk_corrected;   /* what CorrectReadsBatch made of a prepared batch, resident */
+typedef struct bbk_fastq_text bbk_fastq_text; /* the FASTQ text of one or two corrected batches, stream by stream */
+/* bbk_corrector_correct_prepared with the result kept on the device (hammer_tools.cpp:79-105): the corrected trimmed
+ * reads in the batch's trimmed layout, the flag of CorrectOneRead and the `where` byte of every read; the counters of
+ * the corrector advance as they do there.  A search that goes through the host rule (bbk_corrector_limits, or
+ * BBK_CORRECTOR_HOST=1) is copied back into the device's reads before the call returns, the bases it may touch and no
+ * others.  The result borrows hr, which must outlive it.  BBK_ERR_ARG: as bbk_corrector_correct_prepared. */
+int bbk_corrector_correct_resident(bbk_corrector *c, const bbk_hreads *hr, bbk_corrected **out);
+uint64_t bbk_corrected_size(const bbk_corrected *cr); /* records */
+/* Any pointer may be NULL.  h_out, h_out_offsets (n + 1), h_result, h_where: as bbk_corrector_correct_prepared gives
+ * them; h_changed: n u32, the positions where the corrected read differs from the trimmed read (read_corrector.cpp:210-212);
+ * h_tag: n bytes, the tag correct_stats 1 puts behind the read's name (:214-242): 0 none (fewer than k bases are left, or
+ * no search ran and the flag is 0), 1 " BH:ok" (no search, flag 1), 2 " BH:failed" (searched, nothing changed),
+ * 3 " BH:changed:<h_changed>". */
+int bbk_corrected_export(bbk_ctx *ctx, const bbk_corrected *cr, char *h_out, uint64_t *h_out_offsets, uint8_t *h_result,
+                         uint8_t *h_where, uint32_t *h_changed, uint8_t *h_tag);
+void bbk_corrected_free(bbk_corrected *cr);
+/* Read::print (read.hpp:221-236) of every record of `left` -- and of `right`, its mates, when that is not NULL -- routed as
+ * CorrectReadFile (hammer_tools.cpp:135-137) or CorrectPairedReadFiles (:178-186) route them.  Record i is
+ *   @<name><tag>\n N^ltrim <corrected trimmed read> N^tail \n +<name><tag>[ ltrim=<ltrim>][ rtrim=<tail>]\n
+ *   (qvoffset + 2)^ltrim <qualities + qvoffset> (qvoffset + 2)^tail \n
+ * with ltrim / tail from the batch's trim table (nothing left: no padding, two empty lines) and the tag only when `tags`
+ * is not 0.  Names: h_names_* is a byte blob, name i of a side is [h_name_off[i], h_name_off[i + 1]) (n + 1 offsets);
+ * both are copied by the call.  Streams: one batch gives 0 good (flag 1) and 1 bad; a pair gives 0 cor-left and 1 cor-right
+ * (both flags 1), 2 unpaired (the mate with flag 1 of any other pair), 3 bad-left, 4 bad-right.  Inside a stream the
+ * records keep the order (index, left before right); positions come from a scan, so the bytes are the same on every run.
+ * BBK_ERR_ARG: a NULL argument, left and right of different sizes or contexts, descending name offsets, a name of 2^30
+ * bytes or more, a line feed inside a name, qvoffset outside 0..162 (93 + qvoffset must fit a byte). */
+int bbk_corrected_print(const bbk_corrected *left, const bbk_corrected *right, const char *h_names_l,
+                        const uint64_t *h_name_off_l, const char *h_names_r, const uint64_t *h_name_off_r, int qvoffset,
+                        int tags, bbk_fastq_text **out);
+int bbk_fastq_text_streams(const bbk_fastq_text *t); /* 2 or 5 */
+uint64_t bbk_fastq_text_size(const bbk_fastq_text *t, int stream); /* bytes; 0 for a stream the text does not have */
+/* stream `stream` into h_dst (bbk_fastq_text_size bytes) / into the file `path` through the context's staged copy: the
+ * file is replaced, or with append != 0 the bytes go behind what it holds (std::ofstream of hammer_tools.cpp:206-258,
+ * one batch after the other).  BBK_ERR_ARG: a stream index out of range. */
+int bbk_fastq_text_export(bbk_ctx *ctx, const bbk_fastq_text *t, int stream, char *h_dst);
+int bbk_fastq_text_write(bbk_ctx *ctx, const bbk_fastq_text *t, int stream, const char *path, int append);
+void bbk_fastq_text_free(bbk_fastq_text *t);
+
 
 /* ---- several GPUs of one node in one process (bbk_ctx_create(devices, ndev); 8e: the exchange) --------
  * The reference tools are one process for the whole job with hash buckets owned by worker threads

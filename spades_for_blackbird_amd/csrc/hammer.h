@@ -1,5 +1,5 @@
-// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip, readcorrect.hip and hreads.hip (the BayesHammer stage,
-// DESIGN.md 4.3c-h) share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
+// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip, readcorrect.hip, hreads.hip and readprint.hip (the
+// BayesHammer stage) share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
 // through it.
 #pragma once
 
@@ -93,10 +93,32 @@ struct bbk_hreads {
     mutable Trimmed trimmed;
 };
 
+// readcorrect.hip: what CorrectReadsBatch made of a prepared batch, resident
+struct bbk_corrected {
+    bbk_ctx *ctx = nullptr;
+    const bbk_hreads *hr = nullptr;  // borrowed: the trimmed layout, the qualities and the trims are the batch's
+    unsigned k = 0;
+    uint64_t n = 0, total = 0;  // records; bases of the trimmed reads
+    bbk::DevBuf out;            // total u8: the corrected trimmed reads, at the offsets of hr's trimmed layout
+    bbk::DevBuf res, where;     // n u8 each: CorrectOneRead's flag; 0 no search, 1 device, 2 host rule
+    bbk::DevBuf changed, tag;   // n u32, n u8: readprint.hip's k_rp_outcome
+    uint64_t stats[5] = {0, 0, 0, 0, 0};  // what the batch added to the corrector's counters
+};
+
+// readprint.hip: the FASTQ text of one or two corrected batches, stream after stream in one buffer
+struct bbk_fastq_text {
+    bbk_ctx *ctx = nullptr;
+    int streams = 0;        // 2 or 5
+    uint64_t start[6] = {0, 0, 0, 0, 0, 0};  // stream s is text[start[s], start[s + 1])
+    bbk::DevBuf text;
+};
+
 namespace bbk {
 
 // hreads.hip: fills hr->trimmed on first use (two launches, one scan, one wait)
 const bbk_hreads::Trimmed &hreads_trimmed(const bbk_hreads *hr);
+// readprint.hip: fills cr->changed and cr->tag from cr->out, res and where (one launch, no wait)
+void corrected_outcome(bbk_corrected *cr);
 
 // The k-mer sets of the stage: one-word keys, ascending, k-mer indices in 32 bits with two values to spare.  BBK_CANONICAL
 // is not judged here: the statistics refuse a canonical set by its flag, the clustering by its closure check.

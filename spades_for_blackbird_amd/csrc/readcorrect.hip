@@ -21,7 +21,9 @@
 // or when its edit log fills (kRcEditCap = 3 * kRcPopCap nodes: a pop makes three at most, so the pop cap always comes
 // first).  Both paths give the same bytes.
 // Two doors lead to the same code (rc_run): bbk_corrector_correct cuts the generator's stretches on the host and uploads
-// bases, qualities and table; bbk_corrector_correct_prepared takes all three from a bbk_hreads (hreads.hip), resident.
+// bases, qualities and table; bbk_corrector_correct_resident takes all three from a bbk_hreads (hreads.hip), resident, and
+// keeps the outcome there as well (bbk_corrected: what readprint.hip prints); bbk_corrector_correct_prepared is that call
+// followed by bbk_corrected_export.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -366,41 +368,50 @@ namespace rch = bbkhost::readcorrect;
 
 // A batch of trimmed reads with the generator's stretches, as the device pass and the host tail see it: the bases, the
 // qualities, the offsets (n_reads + 1, from 0) and the stretch table on the device (the caller's uploads, or the resident
-// ones of a bbk_hreads), the bases and the offsets on the host as well.  h_qual is asked for only when a search goes
-// through the host rule.
+// ones of a bbk_hreads), the offsets on the host as well.  h_bases / h_qual are asked for only when a search goes through
+// the host rule.
 struct RcBatch {
     uint64_t n_reads = 0, bytes = 0;
     uint32_t longest = 0;
     const uint8_t *d_bases = nullptr, *d_qual = nullptr;
     const uint64_t *d_off = nullptr, *d_stoff = nullptr;
     const uint32_t *d_st = nullptr;
-    const char *h_bases = nullptr;
     const uint64_t *h_offsets = nullptr;
+    std::function<const char *()> h_bases;
     std::function<const uint8_t *()> h_qual;
 };
 
+// What rc_run leaves: the corrected reads and the flags on the device, where every read's searches ran on the host
+struct RcResult {
+    DevBuf out, res;            // bytes u8 (the batch's layout); n_reads u8
+    raw_vector<uint8_t> where;  // n_reads: 0 no search, 1 device, 2 host rule
+    bool searched = false;      // a search ran at all: otherwise `out` is a copy of the bases
+};
+
 // CorrectReadsBatch behind the stretch table: k_rc_island, k_rc_search, the searches beyond the capacities by the host
-// rule, the counters.  h_out (from 0, like the batch) is written here, all of it: the device's output when a search
-// ran there, a copy of the bases otherwise; h_result / h_where are zeroed.
-static void rc_run(bbk_corrector *c, const RcBatch &b, char *h_out, uint8_t *h_result, uint8_t *h_where) {
+// rule -- their spans are copied back into `out`, and only those -- and the counters but the two that compare the reads
+// (changed reads, changed nucleotides: the caller's, which knows where the reads are).
+static void rc_run(bbk_corrector *c, const RcBatch &b, RcResult &R) {
     bbk_ctx *ctx = c->ctx;
     const unsigned k = c->k;
     const uint64_t n_reads = b.n_reads, bytes = b.bytes;
     const uint64_t *h_offsets = b.h_offsets;
-    const char *h_bases = b.h_bases;
     raw_vector<uint32_t> thr(b.longest + 1);
     thr[0] = 0;
     for (uint32_t n = 1; n <= b.longest; ++n) thr[n] = (uint32_t)rch::size_threshold(n);  // the same log2 as the host rule
 
     // ---- device pass ----
-    DevBuf d_thr, d_out(bytes), d_isl(n_reads * 8), d_res(n_reads), d_items(n_reads * 16), d_count(8), d_sstat(n_reads * 2);
+    DevBuf d_thr, d_isl(n_reads * 8), d_items(n_reads * 16), d_count(8), d_sstat(n_reads * 2);
+    R.out.alloc(bytes);
+    R.res.alloc(n_reads);
+    R.where.assign(n_reads, 0);
     upload(ctx, d_thr, thr.data(), (uint64_t)thr.size());
-    BBK_HIP(copy_async(d_out.p, b.d_bases, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    BBK_HIP(copy_async(R.out.p, b.d_bases, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     BBK_HIP(hipMemsetAsync(d_count.p, 0, 8, ctx->stream));
     BBK_HIP(hipMemsetAsync(d_sstat.p, 0, n_reads * 2, ctx->stream));
     launch_items_timed(ctx, "k_rc_island", k_rc_island, n_reads * 64, b.d_bases, b.d_off, n_reads, (int)k, b.d_st, b.d_stoff,
                        c->set->keys.as<Key<1>>(), c->prefix.table(), c->good.as<uint8_t>(), d_isl.as<uint32_t>(),
-                       d_res.as<uint8_t>(), d_count.as<unsigned long long>(), d_items.as<uint64_t>());
+                       R.res.as<uint8_t>(), d_count.as<unsigned long long>(), d_items.as<uint64_t>());
     uint64_t n_items = 0;
     d2h_sync(ctx, &n_items, d_count.p, 8);
     BBK_REQUIRE(n_items <= 2 * n_reads, BBK_ERR_INTERNAL, "bbk_corrector_correct: %llu work items for %llu reads",
@@ -411,20 +422,22 @@ static void rc_run(bbk_corrector *c, const RcBatch &b, char *h_out, uint8_t *h_r
         KernelTimer t(ctx, "k_rc_search");
         hipLaunchKernelGGL(k_rc_search, grid_blocks(n_items), dim3(64), 0, ctx->stream, b.d_bases, b.d_qual, b.d_off, (int)k, c->set->keys.as<Key<1>>(), c->prefix.table(),
                            c->good.as<uint8_t>(), d_isl.as<uint32_t>(), d_items.as<uint64_t>(), n_items,
-                           d_thr.as<uint32_t>(), d_out.as<uint8_t>(), d_sstat.as<uint8_t>());
+                           d_thr.as<uint32_t>(), R.out.as<uint8_t>(), d_sstat.as<uint8_t>());
         check_launch("k_rc_search");
+    }
+    R.searched = n_items != 0;
+    if (!n_items) {
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // thr goes now
+        return;
     }
     raw_vector<uint32_t> isl(n_reads * 2);
     raw_vector<uint8_t> sstat(n_reads * 2);
     d2h_big(ctx, isl.data(), d_isl.p, n_reads * 8);
-    d2h_big(ctx, h_result, d_res.p, n_reads);
     d2h_big(ctx, sstat.data(), d_sstat.p, n_reads * 2);
-    if (n_items && !host_only) d2h_big(ctx, h_out, d_out.p, bytes);
-    else if (bytes) memcpy(h_out, h_bases, bytes);
 
     // ---- the searches the device did not finish, by the host rule; then the counters ----
     raw_vector<uint64_t> todo;  // read << 1 | direction
-    for (uint64_t r = 0; r < n_reads && n_items; ++r) {
+    for (uint64_t r = 0; r < n_reads; ++r) {
         const uint64_t len = h_offsets[r + 1] - h_offsets[r];
         const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
         if (!solid || solid == len) continue;
@@ -432,55 +445,157 @@ static void rc_run(bbk_corrector *c, const RcBatch &b, char *h_out, uint8_t *h_r
         const size_t before = todo.size();
         if (lright + 1 < len && (host_only || sstat[2 * r] == kRcOverflow)) todo.push_back(r << 1);
         if (lleft > 0 && (host_only || sstat[2 * r + 1] == kRcOverflow)) todo.push_back((r << 1) | 1);
-        if (h_where && todo.size() != before) h_where[r] = 2;
+        R.where[r] = todo.size() != before ? 2 : 1;
     }
-    if (!todo.empty()) rc_fetch_set(c);
-    const uint8_t *h_qual = todo.empty() ? nullptr : b.h_qual();
-    const uint64_t *hk = c->h_keys.data();
-    const uint8_t *hg = c->h_good.data();
-    const uint64_t hn = c->n;
-    auto lookup = [hk, hn](uint64_t key) -> uint64_t {
-        const uint64_t *it = std::lower_bound(hk, hk + hn, key);
-        return it != hk + hn && *it == key ? (uint64_t)(it - hk) : rch::kNone;
-    };
+    if (!todo.empty()) {
+        rc_fetch_set(c);
+        const char *h_bases = b.h_bases();
+        const uint8_t *h_qual = b.h_qual();
+        const uint64_t *hk = c->h_keys.data();
+        const uint8_t *hg = c->h_good.data();
+        const uint64_t hn = c->n;
+        auto lookup = [hk, hn](uint64_t key) -> uint64_t {
+            const uint64_t *it = std::lower_bound(hk, hk + hn, key);
+            return it != hk + hn && *it == key ? (uint64_t)(it - hk) : rch::kNone;
+        };
+        std::vector<std::string> span(todo.size());  // what a search made of the bases it may touch
 #pragma omp parallel for schedule(dynamic, 16)
-    for (int64_t j = 0; j < (int64_t)todo.size(); ++j) {
-        const uint64_t r = todo[j] >> 1, o = h_offsets[r], len = h_offsets[r + 1] - o;
-        const bool left = todo[j] & 1;
-        const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
-        const std::string seq(h_bases + o, len), qual((const char *)h_qual + o, len);
-        rch::SearchFigures fig;
-        if (!left) {
-            const std::string s = rch::CorrectReadRight(seq, qual, lright, k, lookup, hg, &fig);
-            memcpy(h_out + o + lright + 1, s.data() + lright + 1, len - lright - 1);  // it touches nothing else
-        } else {
-            const std::string s = rch::ReverseComplement(
-                rch::CorrectReadRight(rch::ReverseComplement(seq), rch::Reverse(qual), len - 1 - lleft, k, lookup, hg, &fig));
-            memcpy(h_out + o, s.data(), lleft);
+        for (int64_t j = 0; j < (int64_t)todo.size(); ++j) {
+            const uint64_t r = todo[j] >> 1, o = h_offsets[r], len = h_offsets[r + 1] - o;
+            const bool left = todo[j] & 1;
+            const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
+            const std::string seq(h_bases + o, len), qual((const char *)h_qual + o, len);
+            rch::SearchFigures fig;
+            if (!left) {
+                const std::string s = rch::CorrectReadRight(seq, qual, lright, k, lookup, hg, &fig);
+                span[j] = s.substr(lright + 1);  // it touches nothing else
+            } else {
+                const std::string s = rch::ReverseComplement(
+                    rch::CorrectReadRight(rch::ReverseComplement(seq), rch::Reverse(qual), len - 1 - lleft, k, lookup, hg, &fig));
+                span[j] = s.substr(0, lleft);
+            }
+            sstat[2 * r + left] = fig.failed ? kRcFailed : kRcDone;
         }
-        sstat[2 * r + left] = fig.failed ? kRcFailed : kRcDone;
+        for (size_t j = 0; j < todo.size(); ++j) {  // back into the device's reads: only the spans those searches own
+            const uint64_t r = todo[j] >> 1, o = h_offsets[r];
+            const uint64_t at = (todo[j] & 1) ? o : o + isl[2 * r] + isl[2 * r + 1] + k - 1;
+            if (!span[j].empty())
+                BBK_HIP(hipMemcpyAsync(R.out.as<uint8_t>() + at, span[j].data(), span[j].size(), hipMemcpyHostToDevice, ctx->stream));
+        }
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // the spans go now
     }
-    uint64_t changed_reads = 0, changed_nucl = 0, uncorrected = 0;
-#pragma omp parallel for reduction(+ : changed_reads, changed_nucl, uncorrected)
+    uint64_t uncorrected = 0;
+#pragma omp parallel for reduction(+ : uncorrected)
     for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
-        const uint64_t o = h_offsets[r], len = h_offsets[r + 1] - o;
-        const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
-        if (!solid || solid == len) continue;
-        if (h_where && h_where[r] == 0) h_where[r] = 1;
-        const uint32_t lleft = isl[2 * r], lright = lleft + solid - 1;
+        if (!R.where[r]) continue;
+        const uint64_t len = h_offsets[r + 1] - h_offsets[r];
+        const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
         if (sstat[2 * r] == kRcFailed) uncorrected += len - lright;
         if (sstat[2 * r + 1] == kRcFailed) uncorrected += lleft + 1;  // read_size - (read_size - 1 - lleft)
-        uint64_t diff = 0;
-        for (uint64_t i = 0; i < len; ++i) diff += h_out[o + i] != h_bases[o + i];
-        if (diff) {
-            ++changed_reads;
-            changed_nucl += diff;
-        }
+    }
+    c->stats[2] += uncorrected;
+    c->stats[4] += todo.size();
+}
+
+static void rc_check(const char *fn, const bbk_corrector *c, const bbk_hreads *hr) {
+    BBK_REQUIRE(hr->k == c->k, BBK_ERR_ARG, "%s: the batch was prepared for k = %u, the corrector's set has k = %u", fn, hr->k, c->k);
+    BBK_REQUIRE(hr->ctx == c->ctx, BBK_ERR_ARG, "%s: the batch belongs to another context", fn);
+    BBK_REQUIRE(hr->longest <= kRcMaxRead, BBK_ERR_ARG,
+                "%s: a record has %llu bases: a position is 16 bits (read_corrector.cpp:20), %u at most", fn,
+                (unsigned long long)hr->longest, kRcMaxRead);
+}
+
+// CorrectReadsBatch over the trimmed reads of a prepared batch, the outcome resident: what bbk_corrector_correct_resident
+// and bbk_corrector_correct_prepared (fn) share.  h_off receives the offsets of the trimmed layout.
+static std::unique_ptr<bbk_corrected> rc_resident(const char *fn, bbk_corrector *c, const bbk_hreads *hr, raw_vector<uint64_t> &h_off) {
+    rc_check(fn, c, hr);
+    bbk_ctx *ctx = c->ctx;
+    BBK_HIP(hipSetDevice(ctx->device));
+    const uint64_t n_reads = hr->n;
+    const bbk_hreads::Trimmed &t = hreads_trimmed(hr);  // the trimmed reads back to back, made once per batch
+    h_off.resize(n_reads + 1);
+    d2h_big(ctx, h_off.data(), t.off.p, (n_reads + 1) * 8);
+    const unsigned k = c->k;
+    uint64_t nucleotides = 0;
+    uint32_t longest = 0;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        const uint64_t len = h_off[r + 1] - h_off[r];
+        if (len >= k) nucleotides += len;  // hammer_tools.cpp:90-95
+        longest = std::max(longest, (uint32_t)len);
+    }
+    auto cr = std::make_unique<bbk_corrected>();
+    cr->ctx = ctx;
+    cr->hr = hr;
+    cr->k = k;
+    cr->n = n_reads;
+    cr->total = t.total;
+    cr->where.alloc(n_reads);
+    cr->changed.alloc(n_reads * 4);
+    cr->tag.alloc(n_reads);
+    uint64_t before[5];
+    memcpy(before, c->stats, sizeof(before));
+    c->stats[3] += nucleotides;
+    RcResult R;
+    raw_vector<char> orig;
+    raw_vector<uint8_t> qual;
+    if (c->n == 0 || nucleotides == 0) {  // no k-mer is good, or no read has k bases: every result is false
+        cr->out.alloc(t.total);
+        cr->res.alloc(n_reads);
+        if (t.total) BBK_HIP(copy_async(cr->out.p, t.bases.p, t.total, hipMemcpyDeviceToDevice, ctx->stream));
+        BBK_HIP(hipMemsetAsync(cr->res.p, 0, n_reads, ctx->stream));
+        BBK_HIP(hipMemsetAsync(cr->where.p, 0, n_reads, ctx->stream));
+    } else {
+        RcBatch b;
+        b.n_reads = n_reads;
+        b.bytes = t.total;
+        b.longest = longest;
+        b.d_bases = t.bases.as<uint8_t>();
+        b.d_qual = t.quals.as<uint8_t>();
+        b.d_off = t.off.as<uint64_t>();
+        b.d_st = hr->cst.as<uint32_t>();
+        b.d_stoff = hr->coff.as<uint64_t>();
+        b.h_offsets = h_off.data();
+        b.h_bases = [&] {
+            orig.resize(t.total);
+            d2h_big(ctx, orig.data(), t.bases.p, t.total);
+            return (const char *)orig.data();
+        };
+        b.h_qual = [&] {
+            qual.resize(t.total);
+            d2h_big(ctx, qual.data(), t.quals.p, t.total);
+            return (const uint8_t *)qual.data();
+        };
+        rc_run(c, b, R);
+        cr->out = std::move(R.out);
+        cr->res = std::move(R.res);
+        if (n_reads) BBK_HIP(hipMemcpyAsync(cr->where.p, R.where.data(), n_reads, hipMemcpyHostToDevice, ctx->stream));
+    }
+    corrected_outcome(cr.get());
+    // changed reads, changed nucleotides (read_corrector.cpp:210-219): four bytes per read come back, not the reads
+    raw_vector<uint32_t> changed(n_reads);
+    if (n_reads) d2h_big(ctx, changed.data(), cr->changed.p, n_reads * 4);  // waits: R.where goes after it
+    else BBK_HIP(hipStreamSynchronize(ctx->stream));
+    uint64_t changed_reads = 0, changed_nucl = 0;
+    for (uint64_t r = 0; r < n_reads; ++r) {
+        changed_reads += changed[r] != 0;
+        changed_nucl += changed[r];
     }
     c->stats[0] += changed_reads;
     c->stats[1] += changed_nucl;
-    c->stats[2] += uncorrected;
-    c->stats[4] += todo.size();
+    for (int i = 0; i < 5; ++i) cr->stats[i] = c->stats[i] - before[i];
+    return cr;
+}
+
+static void rc_export(bbk_ctx *ctx, const bbk_corrected *cr, char *h_out, uint64_t *h_out_offsets, uint8_t *h_result,
+                      uint8_t *h_where, uint32_t *h_changed, uint8_t *h_tag) {
+    BBK_HIP(hipSetDevice(ctx->device));
+    const uint64_t n = cr->n;
+    if (h_out && cr->total) d2h_big(ctx, h_out, cr->out.p, cr->total);
+    if (h_out_offsets) d2h_big(ctx, h_out_offsets, hreads_trimmed(cr->hr).off.p, (n + 1) * 8);
+    if (h_result && n) d2h_big(ctx, h_result, cr->res.p, n);
+    if (h_where && n) d2h_big(ctx, h_where, cr->where.p, n);
+    if (h_changed && n) d2h_big(ctx, h_changed, cr->changed.p, n * 4);
+    if (h_tag && n) d2h_big(ctx, h_tag, cr->tag.p, n);
 }
 
 extern "C" {
@@ -606,64 +721,62 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
         b.d_off = d_off.as<uint64_t>();
         b.d_st = d_st.as<uint32_t>();
         b.d_stoff = d_stoff.as<uint64_t>();
-        b.h_bases = h_bases + first;
+        b.h_bases = [&] { return h_bases + first; };
         b.h_offsets = rel.data();
         b.h_qual = [&] { return h_qual + first; };
-        rc_run(c, b, h_out + first, h_result, h_where);
+        RcResult R;
+        rc_run(c, b, R);
+        d2h_big(ctx, h_result, R.res.p, n_reads);
+        if (h_where) memcpy(h_where, R.where.data(), n_reads);
+        if (R.searched) d2h_big(ctx, h_out + first, R.out.p, bytes);
+        else memcpy(h_out + first, h_bases + first, bytes);
+        uint64_t changed_reads = 0, changed_nucl = 0;  // read_corrector.cpp:210-219
+#pragma omp parallel for reduction(+ : changed_reads, changed_nucl)
+        for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
+            if (!R.where[r]) continue;
+            uint64_t diff = 0;
+            for (uint64_t i = h_offsets[r]; i < h_offsets[r + 1]; ++i) diff += h_out[i] != h_bases[i];
+            if (diff) {
+                ++changed_reads;
+                changed_nucl += diff;
+            }
+        }
+        c->stats[0] += changed_reads;
+        c->stats[1] += changed_nucl;
     });
 }
+
+int bbk_corrector_correct_resident(bbk_corrector *c, const bbk_hreads *hr, bbk_corrected **out) {
+    return guarded([&] {
+        BBK_REQUIRE(c && hr && out, BBK_ERR_ARG, "bbk_corrector_correct_resident: NULL argument");
+        raw_vector<uint64_t> h_off;
+        *out = rc_resident("bbk_corrector_correct_resident", c, hr, h_off).release();
+    });
+}
+
+uint64_t bbk_corrected_size(const bbk_corrected *cr) { return cr ? cr->n : 0; }
+
+int bbk_corrected_export(bbk_ctx *ctx, const bbk_corrected *cr, char *h_out, uint64_t *h_out_offsets, uint8_t *h_result,
+                         uint8_t *h_where, uint32_t *h_changed, uint8_t *h_tag) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && cr, BBK_ERR_ARG, "bbk_corrected_export: NULL argument");
+        rc_export(ctx, cr, h_out, h_out_offsets, h_result, h_where, h_changed, h_tag);
+    });
+}
+
+void bbk_corrected_free(bbk_corrected *cr) { delete cr; }
 
 int bbk_corrector_correct_prepared(bbk_corrector *c, const bbk_hreads *hr, char *h_out, uint64_t *h_out_offsets,
                                    uint8_t *h_result, uint8_t *h_where) {
     return guarded([&] {
         BBK_REQUIRE(c && hr && h_out_offsets && h_result, BBK_ERR_ARG, "bbk_corrector_correct_prepared: NULL argument");
-        BBK_REQUIRE(hr->k == c->k, BBK_ERR_ARG,
-                    "bbk_corrector_correct_prepared: the batch was prepared for k = %u, the corrector's set has k = %u", hr->k, c->k);
-        BBK_REQUIRE(hr->ctx == c->ctx, BBK_ERR_ARG, "bbk_corrector_correct_prepared: the batch belongs to another context");
-        BBK_REQUIRE(hr->longest <= kRcMaxRead, BBK_ERR_ARG,
-                    "bbk_corrector_correct_prepared: a record has %llu bases: a position is 16 bits (read_corrector.cpp:20), %u at most",
-                    (unsigned long long)hr->longest, kRcMaxRead);
-        bbk_ctx *ctx = c->ctx;
-        BBK_HIP(hipSetDevice(ctx->device));
-        const uint64_t n_reads = hr->n;
-        const bbk_hreads::Trimmed &t = hreads_trimmed(hr);  // the trimmed reads back to back, made once per batch
-        BBK_REQUIRE(t.total == 0 || h_out, BBK_ERR_ARG, "bbk_corrector_correct_prepared: NULL argument");
-        d2h_big(ctx, h_out_offsets, t.off.p, (n_reads + 1) * 8);
-        memset(h_result, 0, n_reads);
-        if (h_where) memset(h_where, 0, n_reads);
-        const unsigned k = c->k;
-        uint64_t nucleotides = 0;
-        uint32_t longest = 0;
-        for (uint64_t r = 0; r < n_reads; ++r) {
-            const uint64_t len = h_out_offsets[r + 1] - h_out_offsets[r];
-            if (len >= k) nucleotides += len;  // hammer_tools.cpp:90-95
-            longest = std::max(longest, (uint32_t)len);
-        }
-        c->stats[3] += nucleotides;
-        if (c->n == 0 || nucleotides == 0) {
-            if (t.total) d2h_big(ctx, h_out, t.bases.p, t.total);
-            return;
-        }
-        raw_vector<char> orig(t.total);  // the reads as they were: the counters compare with them
-        if (t.total) d2h_big(ctx, orig.data(), t.bases.p, t.total);
-        raw_vector<uint8_t> qual;
-        RcBatch b;
-        b.n_reads = n_reads;
-        b.bytes = t.total;
-        b.longest = longest;
-        b.d_bases = t.bases.as<uint8_t>();
-        b.d_qual = t.quals.as<uint8_t>();
-        b.d_off = t.off.as<uint64_t>();
-        b.d_st = hr->cst.as<uint32_t>();
-        b.d_stoff = hr->coff.as<uint64_t>();
-        b.h_bases = orig.data();
-        b.h_offsets = h_out_offsets;
-        b.h_qual = [&] {
-            qual.resize(t.total);
-            d2h_big(ctx, qual.data(), t.quals.p, t.total);
-            return (const uint8_t *)qual.data();
-        };
-        rc_run(c, b, h_out, h_result, h_where);
+        rc_check("bbk_corrector_correct_prepared", c, hr);
+        BBK_HIP(hipSetDevice(c->ctx->device));
+        BBK_REQUIRE(hreads_trimmed(hr).total == 0 || h_out, BBK_ERR_ARG, "bbk_corrector_correct_prepared: NULL argument");
+        raw_vector<uint64_t> h_off;
+        const auto cr = rc_resident("bbk_corrector_correct_prepared", c, hr, h_off);
+        memcpy(h_out_offsets, h_off.data(), (hr->n + 1) * 8);
+        rc_export(c->ctx, cr.get(), h_out, nullptr, h_result, h_where, nullptr, nullptr);
     });
 }
 

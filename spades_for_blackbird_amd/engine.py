@@ -52,6 +52,8 @@ SYMBOLS = [
     "bbk_corrector_stats", "bbk_corrector_free",
     "bbk_hreads_from_host", "bbk_hreads_size", "bbk_hreads_kmer_stretches", "bbk_hreads_corrector_stretches", "bbk_hreads_candidates",
     "bbk_hreads_export", "bbk_hreads_stretch_view", "bbk_hreads_candidate_view", "bbk_corrector_correct_prepared", "bbk_hreads_free",
+    "bbk_corrector_correct_resident", "bbk_corrected_size", "bbk_corrected_export", "bbk_corrected_free", "bbk_corrected_print",
+    "bbk_fastq_text_streams", "bbk_fastq_text_size", "bbk_fastq_text_export", "bbk_fastq_text_write", "bbk_fastq_text_free",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -295,6 +297,20 @@ def load_library():
     L.bbk_corrector_correct_prepared.argtypes = [vp] * 6
     L.bbk_hreads_free.argtypes = [vp]
     L.bbk_hreads_free.restype = None
+    L.bbk_corrector_correct_resident.argtypes = [vp, vp, C.POINTER(vp)]
+    L.bbk_corrected_size.restype = u64
+    L.bbk_corrected_size.argtypes = [vp]
+    L.bbk_corrected_export.argtypes = [vp] * 8
+    L.bbk_corrected_free.argtypes = [vp]
+    L.bbk_corrected_free.restype = None
+    L.bbk_corrected_print.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.bbk_fastq_text_streams.argtypes = [vp]
+    L.bbk_fastq_text_size.restype = u64
+    L.bbk_fastq_text_size.argtypes = [vp, C.c_int]
+    L.bbk_fastq_text_export.argtypes = [vp, vp, C.c_int, vp]
+    L.bbk_fastq_text_write.argtypes = [vp, vp, C.c_int, C.c_char_p, C.c_int]
+    L.bbk_fastq_text_free.argtypes = [vp]
+    L.bbk_fastq_text_free.restype = None
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -1055,12 +1071,86 @@ class Corrector(_Handle):
         _check(self._L.bbk_corrector_correct_prepared(self._h, hr._h, _ptr(out), _ptr(off), _ptr(res), _ptr(where)))
         return out[:int(off[n])], off, res, where
 
+    def correct_resident(self, hr):
+        """correct_prepared with the outcome kept on the device -> Corrected (it borrows hr)"""
+        h = C.c_void_p()
+        _check(self._L.bbk_corrector_correct_resident(self._h, hr._h, C.byref(h)))
+        cr = Corrected(self.ctx, h)
+        cr._hr, cr._corrector = hr, self
+        return cr
+
     @property
     def stats(self):
         """the counters summed over the calls so far, by name (Corrector.STATS)"""
         a = np.zeros(5, dtype=np.uint64)
         _check(self._L.bbk_corrector_stats(self._h, _ptr(a)))
         return dict(zip(self.STATS, (int(x) for x in a)))
+
+
+def _name_blob(names, n, what):
+    """names: n str / bytes -> (blob np.uint8, offsets np.uint64[n + 1])"""
+    raw = [x.encode() if isinstance(x, str) else bytes(x) for x in names]
+    if len(raw) != n:
+        raise ValueError("%d %s names for %d records" % (len(raw), what, n))
+    off = np.zeros(n + 1, dtype=np.uint64)
+    if raw:
+        off[1:] = np.cumsum([len(x) for x in raw], dtype=np.uint64)
+    return np.frombuffer(b"".join(raw), dtype=np.uint8), off
+
+
+class Corrected(_Handle):
+    """What the corrector made of a HammerReads, resident (bbk_corrected_*): the corrected trimmed reads, the result
+    flags, where the searches ran, and per read the changed positions and the kind of its BH: tag"""
+    _free = "bbk_corrected_free"
+    TAGS = ("", " BH:ok", " BH:failed", " BH:changed:")
+
+    def __len__(self):
+        return int(self._L.bbk_corrected_size(self._h))
+
+    def export(self, outcome=False):
+        """(corrected bases np.uint8, offsets np.uint64[n + 1], result np.uint8[n], where np.uint8[n]) as
+        Corrector.correct_prepared gives them; with outcome also (changed np.uint32[n], tag np.uint8[n])"""
+        n = len(self)
+        out = np.zeros(self._hr.bases, dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        res = np.zeros(n, dtype=np.uint8)
+        where = np.zeros(n, dtype=np.uint8)
+        changed = np.zeros(n, dtype=np.uint32)
+        tag = np.zeros(n, dtype=np.uint8)
+        _check(self._L.bbk_corrected_export(self.ctx._h, self._h, _ptr(out), _ptr(off), _ptr(res), _ptr(where),
+                                            _ptr(changed) if outcome else None, _ptr(tag) if outcome else None))
+        r = (out[:int(off[n])], off, res, where)
+        return r + (changed, tag) if outcome else r
+
+    def print(self, names, qvoffset=33, tags=False, mate=None, mate_names=None):
+        """Read::print of every record, named names[i], routed like CorrectReadFile -> FastqText with streams (good, bad);
+        with mate (the Corrected of the right reads) and mate_names like CorrectPairedReadFiles -> streams (cor-left,
+        cor-right, unpaired, bad-left, bad-right).  tags: the BH: tags of correct_stats 1."""
+        bl, ol = _name_blob(names, len(self), "left" if mate is not None else "read")
+        br, orr = _name_blob(mate_names or [], len(mate), "right") if mate is not None else (None, None)
+        h = C.c_void_p()
+        _check(self._L.bbk_corrected_print(self._h, mate._h if mate is not None else None, _ptr(bl), _ptr(ol),
+                                           _ptr(br) if mate is not None else None, _ptr(orr) if mate is not None else None,
+                                           int(qvoffset), 1 if tags else 0, C.byref(h)))
+        return FastqText(self.ctx, h)
+
+
+class FastqText(_Handle):
+    """FASTQ text on the device, one stream per output file (bbk_fastq_text_*)"""
+    _free = "bbk_fastq_text_free"
+
+    @property
+    def sizes(self):
+        return [int(self._L.bbk_fastq_text_size(self._h, i)) for i in range(int(self._L.bbk_fastq_text_streams(self._h)))]
+
+    def stream(self, i):
+        """the bytes of stream i"""
+        buf = np.zeros(int(self._L.bbk_fastq_text_size(self._h, i)), dtype=np.uint8)
+        _check(self._L.bbk_fastq_text_export(self.ctx._h, self._h, i, _ptr(buf)))
+        return buf.tobytes()
+
+    def write(self, i, path, append=False):
+        _check(self._L.bbk_fastq_text_write(self.ctx._h, self._h, i, os.fsencode(path), 1 if append else 0))
 
 
 class Counter:

@@ -5,7 +5,8 @@
 //   -k/--kmer <int=21>  -t/--threads <int>  -b/--bufsize <bytes>  -o/--output <prefix>  -d/--dataset <yaml>  [input files...]
 //   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster, --subcluster with --singleton-threshold,
 //      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold, --expand with --expand-max-iterations <int=25>,
-//      --expand-min-changed <int=10>, --correct, --resident-bytes <bytes=0>)
+//      --expand-min-changed <int=10>, --correct with --correct-stats, --paired and --output-dir <dir>,
+//      --resident-bytes <bytes=0>)
 // The records of every file go to the device as parsed, in blocks of -b bases, and are prepared there (bbk_hreads: the trim
 // of input_trim_quality 4 of configs/hammer/config.info, then ValidKMerGenerator's valid starts as stretches); a stretch is
 // one read of the engine.  Every pass takes a view of the prepared blocks:
@@ -27,12 +28,27 @@
 //   (bbk_hreads_candidate_view), trimmed, block by block through bbk_expander_push, until a
 //   round adds fewer than --expand-min-changed k-mers or --expand-max-iterations rounds have run; <prefix>.kmstat then
 //   carries the expanded good bits (bbk_expander_store) and every other file is as without --expand
-//   with --correct (ReadCorrector, projects/hammer/read_corrector.cpp and hammer_tools.cpp:79-142 CorrectReadFile; implies
-//   --expand): after the expansion every input file i is taken once more as a single-read file: every record is trimmed
-//   (Read::trimNsAndBadQuality(--trim-quality)), corrected block by block (bbk_corrector_correct_prepared) and printed in
-//   the format of Read::print to <prefix>.<i>.cor.fastq (result true) or <prefix>.<i>.bad.fastq
+//   with --correct (CorrectAllReads, projects/hammer/hammer_tools.cpp:79-277, and read_corrector.cpp; implies --expand):
+//   after the expansion every block is taken once more: its records are trimmed (Read::trimNsAndBadQuality(--trim-quality)),
+//   corrected (bbk_corrector_correct_resident), printed in the format of Read::print on the device (bbk_corrected_print)
+//   and every stream of the text goes behind its file (bbk_fastq_text_write).  Input file i is a single-read file
+//   (CorrectReadFile): <prefix>.<i>.cor.fastq (result true) and <prefix>.<i>.bad.fastq.
+//   --correct-stats: correct_stats 1 of configs/hammer/config.info: the name of a read carries BH:ok, BH:failed or
+//   BH:changed:<n> (read_corrector.cpp:214-242).
+//   --paired: the positional files two at a time, or with -d every library's left reads[i] and right reads[i], are a
+//   pair (CorrectPairedReadFiles, hammer_tools.cpp:144-193): both mates good -> the two .cor.fastq, otherwise a good mate ->
+//   <prefix>.<i_left>.unpaired.fastq and a bad one -> its own .bad.fastq.  Both files of a pair are cut into blocks at the
+//   same record indices, in every pass; a block ends when either side reaches -b.
+//   --output-dir <dir>: the corrected reads under the reference's names instead (hammer_tools.cpp:53-59,206-258:
+//   <dir>/<basename>.00.<ilib>_<iread>.cor.fastq, <dir>/<basename>.00.bad.fastq, the unpaired reads under the basename of
+//   <largest common prefix>_unpaired.fastq), and <dir>/corrected.yaml, the corrected libraries (main.cpp:254-256).
 // The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
 // common interface.
+#include <sys/stat.h>
+
+#include <cerrno>
+#include <climits>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <memory>
@@ -65,6 +81,11 @@ static void usage(const char *argv0) {
            "        --expand-max-iterations <value>   expand_max_iterations (default 25)\n"
            "        --expand-min-changed <value>      Stop after an iteration that adds fewer k-mers than this (default 10)\n"
            "        --correct               Also correct the reads with the expanded solid k-mers (implies --expand)\n"
+           "        --correct-stats         Tag the names of the corrected reads: BH:ok, BH:failed, BH:changed:<n>\n"
+           "        --paired                Input files two at a time (with -d: left reads[i] and right reads[i]) are pairs:\n"
+           "                                a pair is kept only when both mates are good, a single good mate is unpaired\n"
+           "        --output-dir <value>    Write the corrected reads under the names BayesHammer gives them in this\n"
+           "                                directory, and corrected.yaml, the dataset description of the corrected reads\n"
            "        --resident-bytes <value>  Keep the first blocks on the GPU for the later passes while their bases and\n"
            "                                qualities total at most this many bytes (default 0: every pass parses the input)\n\n"
            "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
@@ -74,198 +95,331 @@ static void usage(const char *argv0) {
            "        with --subcluster the good bit in <prefix>.kmstat, the new k-mers' records after the others, and\n"
            "        <prefix>.subclusters, <prefix>.subclusters.idx, <prefix>.newkmers;\n"
            "        with --expand the good bits in <prefix>.kmstat are those after the expansion;\n"
-           "        with --correct <prefix>.<i>.cor.fastq and <prefix>.<i>.bad.fastq: the corrected reads of input file i.\n",
+           "        with --correct <prefix>.<i>.cor.fastq and <prefix>.<i>.bad.fastq: the corrected reads of input file i;\n"
+           "        with --paired also <prefix>.<i>.unpaired.fastq for the left file i of every pair.\n",
            argv0);
 }
 
+// An input file as CorrectAllReads sees it: its library, its number in the library (pairs first, then merged, then single
+// files: hammer_tools.cpp:233-268) and the list of the corrected library its output joins
+struct InFile {
+    std::string path;
+    size_t ilib = 0, iread = 0;
+    int kind = LIB_SINGLE;  // LIB_LEFT / LIB_RIGHT: a mate file of a pair; LIB_MERGED; anything else counts as single
+};
+// What is read together: one single-read file, or the two files of a pair in step
+struct Group {
+    size_t f0 = 0;
+    long f1 = -1;  // the right file of a pair, or -1
+};
+
 // One block of records of one input file, as parsed, and its prepared batch on the device (bbk_hreads: the trims, the
 // stretches and the candidates of every record).  A resident block keeps the batch, the names, the qualities and the
-// offsets for the later passes -- what Read::print needs besides the corrected bases -- and lets the bases go.
+// offsets for the later passes and lets the bases go.  The block of a left file owns the block of the same records of the
+// right file.
 struct Block {
-    size_t file = 0;
+    size_t group = 0, file = 0;
     std::string bases, quals;  // quals: the offset subtracted
     std::vector<uint64_t> offsets{0};
-    std::vector<std::string> names;
+    std::string names;  // back to back
+    std::vector<uint64_t> name_off{0};
     bbk_hreads *hr = nullptr;
     bool resident = false;
+    std::unique_ptr<Block> mate;
     uint64_t size() const { return offsets.size() - 1; }
     uint64_t total() const { return offsets.back(); }
     ~Block() { bbk_hreads_free(hr); }
 };
 
-// The records of all files as prepared blocks, in file order, once per pass.  A block holds the records of one file up to
-// -b bases, so every pass and every --resident-bytes sees the same blocks.  The blocks of the first pass stay on the
-// device while their bases and qualities fit --resident-bytes; the later passes take those as they are and parse the
-// files again only for the blocks behind them.
+// The records of all groups as prepared blocks, in group order, once per pass.  A block holds the records of one file up
+// to -b bases -- of a pair: up to the record at which either file reaches -b, the same records of both -- so every pass
+// and every --resident-bytes sees the same blocks.  The blocks of the first pass stay on the device while their bases and
+// qualities fit --resident-bytes; the later passes take those as they are and parse the files again only for the blocks
+// behind them.
 class ReadSource {
 public:
-    ReadSource(bbk_ctx *ctx, const std::vector<std::string> &files, unsigned k, int qvoffset, int trim_quality, size_t block_bytes,
-               uint64_t resident_bytes)
-        : ctx_(ctx), files_(files), k_(k), qvoffset_(qvoffset), trim_quality_(trim_quality), block_bytes_(block_bytes),
-          budget_(resident_bytes), keeping_(resident_bytes != 0), kept_in_file_(files.size(), 0), whole_file_(files.size(), false) {}
+    ReadSource(bbk_ctx *ctx, const std::vector<InFile> &files, const std::vector<Group> &groups, unsigned k, int qvoffset,
+               int trim_quality, size_t block_bytes, uint64_t resident_bytes)
+        : ctx_(ctx), files_(files), groups_(groups), k_(k), qvoffset_(qvoffset), trim_quality_(trim_quality),
+          block_bytes_(block_bytes), budget_(resident_bytes), keeping_(resident_bytes != 0), kept_in_group_(groups.size(), 0),
+          whole_group_(groups.size(), false) {}
 
-    // fn(block) for every block; returns the number of records
+    // fn(block) for the block of every group's first file (its mate, if any, hangs on it); returns the number of records
     template <class F>
-    uint64_t each(bool announce, F fn) {
+    uint64_t each_group(bool announce, F fn) {
         uint64_t records = 0;
         for (const auto &b : resident_) {
             fn(*b);
-            records += b->size();
+            records += b->size() + (b->mate ? b->mate->size() : 0);
         }
-        for (size_t f = 0; f < files_.size(); ++f) {
-            if (whole_file_[f]) continue;
-            if (announce) info("Processing %s", files_[f].c_str());
-            records += parse(f, fn);
+        for (size_t g = 0; g < groups_.size(); ++g) {
+            if (whole_group_[g]) continue;
+            if (announce) {
+                info("Processing %s", files_[groups_[g].f0].path.c_str());
+                if (groups_[g].f1 >= 0) info("Processing %s", files_[(size_t)groups_[g].f1].path.c_str());
+            }
+            records += parse(g, fn);
         }
         keeping_ = false;
         return records;
+    }
+    // fn(block) for every block, a left block before its mate
+    template <class F>
+    uint64_t each(bool announce, F fn) {
+        return each_group(announce, [&](const Block &b) {
+            fn(b);
+            if (b.mate) fn(*b.mate);
+        });
     }
 
     void clear() { resident_.clear(); }  // the resident blocks leave the device
 
 private:
+    void take(Block &b, size_t f, uint64_t record, const std::string &name, const std::string &seq, std::string &qual) {
+        if (qual.size() != seq.size())
+            fatal("%s: record %llu (%s) has no quality string: the statistics need FASTQ input", files_[f].path.c_str(),
+                  (unsigned long long)record, name.c_str());
+        for (char &c : qual) {
+            const int q = (unsigned char)c - qvoffset_;
+            if (q < 0 || q > 93)
+                fatal("%s: record %llu (%s): quality character '%c' is outside [0, 93] at offset %d", files_[f].path.c_str(),
+                      (unsigned long long)record, name.c_str(), c, qvoffset_);
+            c = (char)q;
+        }
+        b.bases += seq;
+        b.quals += qual;
+        b.offsets.push_back(b.bases.size());
+        b.names += name;
+        b.name_off.push_back(b.names.size());
+    }
+    void prepare(Block &b, size_t g, size_t f) {
+        b.group = g;
+        b.file = f;
+        check(bbk_hreads_from_host(ctx_, b.bases.data(), reinterpret_cast<const uint8_t *>(b.quals.data()), b.offsets.data(), b.size(),
+                                   k_, trim_quality_, &b.hr),
+              "bbk_hreads_from_host");
+    }
+
     template <class F>
-    uint64_t parse(size_t f, F &fn) {
-        FastxReader rd(files_[f]);
-        if (!rd.is_open()) fatal("cannot open %s", files_[f].c_str());
-        std::unique_ptr<Block> b(new Block);
-        std::string name, seq, qual;
-        uint64_t records = 0, block_no = 0;
+    uint64_t parse(size_t g, F &fn) {
+        const size_t f0 = groups_[g].f0;
+        const bool paired = groups_[g].f1 >= 0;
+        const size_t f1 = paired ? (size_t)groups_[g].f1 : f0;
+        FastxReader rl(files_[f0].path);
+        if (!rl.is_open()) fatal("cannot open %s", files_[f0].path.c_str());
+        std::unique_ptr<FastxReader> rr;
+        if (paired) {
+            rr.reset(new FastxReader(files_[f1].path));
+            if (!rr->is_open()) fatal("cannot open %s", files_[f1].path.c_str());
+        }
+        auto fresh = [&] {
+            std::unique_ptr<Block> b(new Block);
+            if (paired) b->mate.reset(new Block);
+            return b;
+        };
+        std::unique_ptr<Block> b = fresh();
+        std::string name, seq, qual, name2, seq2, qual2;
+        uint64_t records = 0, in_file = 0, block_no = 0;
         auto flush = [&] {
-            if (block_no++ >= kept_in_file_[f]) {  // the blocks before are resident and have been handed out
-                b->file = f;
-                check(bbk_hreads_from_host(ctx_, b->bases.data(), reinterpret_cast<const uint8_t *>(b->quals.data()), b->offsets.data(),
-                                           b->size(), k_, trim_quality_, &b->hr),
-                      "bbk_hreads_from_host");
+            if (block_no++ >= kept_in_group_[g]) {  // the blocks before are resident and have been handed out
+                prepare(*b, g, f0);
+                if (paired) prepare(*b->mate, g, f1);
                 fn(*b);
-                records += b->size();
-                if (keeping_ && held_ + 2 * b->total() <= budget_) {
-                    held_ += 2 * b->total();
+                const uint64_t held = 2 * (b->total() + (paired ? b->mate->total() : 0));
+                records += b->size() + (paired ? b->mate->size() : 0);
+                if (keeping_ && held_ + held <= budget_) {
+                    held_ += held;
                     b->resident = true;
                     std::string().swap(b->bases);
-                    ++kept_in_file_[f];
+                    if (paired) {
+                        b->mate->resident = true;
+                        std::string().swap(b->mate->bases);
+                    }
+                    ++kept_in_group_[g];
                     resident_.push_back(std::move(b));
                 } else {
                     keeping_ = false;  // the resident blocks are a prefix of all blocks
                 }
             }
-            b.reset(new Block);
+            b = fresh();
         };
-        while (rd.next_record(name, seq, qual)) {
-            if (qual.size() != seq.size())
-                fatal("%s: record %llu (%s) has no quality string: the statistics need FASTQ input", files_[f].c_str(),
-                      (unsigned long long)records, name.c_str());
-            for (char &c : qual) {
-                const int q = (unsigned char)c - qvoffset_;
-                if (q < 0 || q > 93)
-                    fatal("%s: record %llu (%s): quality character '%c' is outside [0, 93] at offset %d", files_[f].c_str(),
-                          (unsigned long long)records, name.c_str(), c, qvoffset_);
-                c = (char)q;
-            }
-            b->bases += seq;
-            b->quals += qual;
-            b->offsets.push_back(b->bases.size());
-            b->names.push_back(name);
-            if (b->bases.size() >= block_bytes_) flush();
+        for (;;) {
+            const bool more = rl.next_record(name, seq, qual);
+            if (paired && rr->next_record(name2, seq2, qual2) != more)  // hammer_tools.cpp:190-191
+                fatal("Pair of read files %s and %s contain unequal amount of reads", files_[f0].path.c_str(), files_[f1].path.c_str());
+            if (!more) break;
+            take(*b, f0, in_file, name, seq, qual);
+            if (paired) take(*b->mate, f1, in_file, name2, seq2, qual2);
+            ++in_file;
+            if (b->bases.size() >= block_bytes_ || (paired && b->mate->bases.size() >= block_bytes_)) flush();
         }
         if (b->size()) flush();
-        if (keeping_) whole_file_[f] = true;
+        if (keeping_) whole_group_[g] = true;
         return records;
     }
 
     bbk_ctx *ctx_;
-    const std::vector<std::string> &files_;
+    const std::vector<InFile> &files_;
+    const std::vector<Group> &groups_;
     unsigned k_;
     int qvoffset_, trim_quality_;
     size_t block_bytes_;
     uint64_t budget_, held_ = 0;
     bool keeping_;
     std::vector<std::unique_ptr<Block>> resident_;
-    std::vector<uint64_t> kept_in_file_;  // resident blocks of every file: its first ones
-    std::vector<bool> whole_file_;        // every block of the file is resident
+    std::vector<uint64_t> kept_in_group_;  // resident blocks of every group: its first ones
+    std::vector<bool> whole_group_;        // every block of the group is resident
 };
 
-// CorrectReadFile (hammer_tools.cpp:107-142) over the blocks of all files: the trimmed reads of a block through the
-// corrector, printed as Read::print does (read.hpp:221-236) into the pair of files of the block's input file
+// fs::basename (common/utils/filesystem/path_helper.cpp:104-113): no directory, no last extension
+static std::string ref_basename(const std::string &path) {
+    const size_t slash = path.find_last_of('/'), after = slash == std::string::npos ? 0 : slash + 1;
+    size_t dot = path.find_last_of('.');
+    if (dot != std::string::npos && dot < after) dot = std::string::npos;
+    return path.substr(after, dot == std::string::npos ? std::string::npos : dot - after);
+}
+// getReadsFilename (hammer_tools.cpp:53-59) of iteration 0
+static std::string ref_reads_filename(const std::string &dir, const std::string &fname, const std::string &suffix) {
+    return dir + "/" + ref_basename(fname) + ".00." + suffix;
+}
+static std::string largest_prefix(const std::string &a, const std::string &b) {  // hammer_tools.cpp:195-204
+    size_t i = 0;
+    while (i < a.size() && i < b.size() && a[i] == b[i]) ++i;
+    return a.substr(0, i);
+}
+
+// CorrectAllReads' loop over the read files (hammer_tools.cpp:218-277) as a thin loop over the blocks: a block -- with its
+// mate, CorrectPairedReadFiles (:144-193), without, CorrectReadFile (:107-142) -- is corrected, printed on the device and
+// every stream of the text appended to the file of that stream
 struct CorrectedWriter {
-    const std::vector<std::string> &files;
-    const std::string &prefix;
+    const std::vector<InFile> &files;
+    const std::vector<Group> &groups;
+    const std::string &prefix, &out_dir;  // out_dir empty: <prefix>.<i>.* names
     bbk_ctx *ctx;
     bbk_corrector *cor;
     int qvoffset;
-    size_t open_file = 0;
+    bool tags;
+    std::vector<DatasetLib> &outlibs;
+    size_t open_group = 0;
     bool is_open = false;
-    FILE *good = nullptr, *bad = nullptr;
+    std::string path[5];
     unsigned buffer_no = 0;
-    std::string out, line;
-    std::vector<uint64_t> offs;
-    std::vector<uint8_t> res;
-    std::vector<uint32_t> trims;
 
-    void close() {
-        if (is_open && (fclose(good) != 0 || fclose(bad) != 0)) fatal("writing the corrected reads failed");
-        is_open = false;
-    }
-    // the files of input file i, and of every file before it that had no block
-    void open_until(size_t i) {
-        while (!is_open || open_file < i) {
-            if (is_open) {
-                close();
-                ++open_file;
+    // the files of group g, and of every group before it that had no block: created empty, appended to block by block
+    void open_until(size_t g) {
+        while (!is_open || open_group < g) {
+            if (is_open) ++open_group;
+            if (open_group >= groups.size()) return;
+            const Group &G = groups[open_group];
+            const InFile &l = files[G.f0];
+            int n = 2;
+            auto names = [&](const InFile &f, size_t index, std::string &cor_path, std::string &bad_path) {
+                const std::string usuffix = std::to_string(f.ilib) + "_" + std::to_string(f.iread) + ".cor.fastq";
+                cor_path = out_dir.empty() ? prefix + "." + std::to_string(index) + ".cor.fastq" : ref_reads_filename(out_dir, f.path, usuffix);
+                bad_path = out_dir.empty() ? prefix + "." + std::to_string(index) + ".bad.fastq" : ref_reads_filename(out_dir, f.path, "bad.fastq");
+            };
+            if (G.f1 < 0) {
+                info(l.kind == LIB_MERGED ? "Correcting merged reads: %s" : "Correcting single reads: %s", l.path.c_str());
+                names(l, G.f0, path[0], path[1]);
+                outlibs[l.ilib].v[l.kind == LIB_MERGED ? LIB_MERGED : LIB_SINGLE].push_back(path[0]);
+            } else {
+                const InFile &r = files[(size_t)G.f1];
+                info("Correcting pair of reads: %s and %s", l.path.c_str(), r.path.c_str());
+                names(l, G.f0, path[0], path[3]);
+                names(r, (size_t)G.f1, path[1], path[4]);
+                const std::string usuffix = std::to_string(l.ilib) + "_" + std::to_string(l.iread) + ".cor.fastq";
+                path[2] = out_dir.empty() ? prefix + "." + std::to_string(G.f0) + ".unpaired.fastq"
+                                          : ref_reads_filename(out_dir, largest_prefix(l.path, r.path) + "_unpaired.fastq", usuffix);
+                outlibs[l.ilib].v[LIB_LEFT].push_back(path[0]);
+                outlibs[l.ilib].v[LIB_RIGHT].push_back(path[1]);
+                outlibs[l.ilib].v[LIB_SINGLE].push_back(path[2]);
+                n = 5;
             }
-            if (open_file >= files.size()) return;
-            info("Correcting single reads: %s", files[open_file].c_str());
-            const std::string base = prefix + "." + std::to_string(open_file);
-            const std::string cor_path = base + ".cor.fastq", bad_path = base + ".bad.fastq";
-            good = fopen(cor_path.c_str(), "wb");
-            bad = fopen(bad_path.c_str(), "wb");
-            if (!good || !bad) fatal("cannot open %s for writing", (good ? bad_path : cor_path).c_str());
+            for (int s = 0; s < n; ++s) {
+                FILE *f = fopen(path[s].c_str(), "wb");
+                if (!f || fclose(f) != 0) fatal("cannot open %s for writing", path[s].c_str());
+            }
             is_open = true;
             buffer_no = 0;
         }
     }
-    void finish() {
-        open_until(files.empty() ? 0 : files.size() - 1);
-        close();
-    }
+    void finish() { open_until(groups.empty() ? 0 : groups.size() - 1); }
     void operator()(const Block &b) {
-        open_until(b.file);
+        open_until(b.group);
+        const Block *m = b.mate.get();
         info("Prepared batch %u of %llu reads.", buffer_no, (unsigned long long)b.size());
-        out.resize(b.total());
-        offs.resize(b.size() + 1);
-        res.resize(b.size());
-        trims.resize(2 * b.size());
-        check(bbk_corrector_correct_prepared(cor, b.hr, &out[0], offs.data(), res.data(), nullptr), "bbk_corrector_correct_prepared");
-        check(bbk_hreads_export(ctx, b.hr, trims.data(), nullptr, nullptr, nullptr, nullptr, nullptr), "bbk_hreads_export");
+        bbk_corrected *left = nullptr, *right = nullptr;
+        check(bbk_corrector_correct_resident(cor, b.hr, &left), "bbk_corrector_correct_resident");
+        if (m) check(bbk_corrector_correct_resident(cor, m->hr, &right), "bbk_corrector_correct_resident");
         info("Processed batch %u", buffer_no);
-        for (uint64_t i = 0; i < b.size(); ++i) {
-            // Read::trimLeftRight's bookkeeping (read.hpp:99-122): ltrim_ / rtrim_ are the ends of what is left, or 0 and
-            // the size when nothing is
-            const size_t initial = b.offsets[i + 1] - b.offsets[i], start = trims[2 * i], len = trims[2 * i + 1];
-            const size_t ltrim = len ? start : 0, rtrim = len ? start + len : initial, tail = initial - rtrim;
-            const size_t o = offs[i], q0 = b.offsets[i] + start;
-            line.assign("@").append(b.names[i]).append("\n").append(ltrim, 'N').append(out, o, len).append(tail, 'N');
-            line.append("\n+").append(b.names[i]);
-            if (ltrim > 0) line.append(" ltrim=").append(std::to_string(ltrim));
-            if (rtrim < initial) line.append(" rtrim=").append(std::to_string(tail));
-            line.append("\n").append(ltrim, (char)(qvoffset + 2));
-            for (size_t j = 0; j < len; ++j) line.push_back((char)(b.quals[q0 + j] + qvoffset));
-            line.append(tail, (char)(qvoffset + 2)).append("\n");
-            if (fwrite(line.data(), 1, line.size(), res[i] ? good : bad) != line.size()) fatal("writing the corrected reads failed");
-        }
+        bbk_fastq_text *text = nullptr;
+        check(bbk_corrected_print(left, right, b.names.data(), b.name_off.data(), m ? m->names.data() : nullptr,
+                                  m ? m->name_off.data() : nullptr, qvoffset, tags ? 1 : 0, &text),
+              "bbk_corrected_print");
+        for (int s = 0; s < bbk_fastq_text_streams(text); ++s)
+            if (bbk_fastq_text_size(text, s)) check(bbk_fastq_text_write(ctx, text, s, path[s].c_str(), 1), "bbk_fastq_text_write");
+        bbk_fastq_text_free(text);
+        bbk_corrected_free(right);
+        bbk_corrected_free(left);
         info("Written batch %u", buffer_no);
         ++buffer_no;
     }
 };
 
+// The input files in the order the passes take them, what is read together, and the corrected libraries to be filled
+static void plan_input(const std::vector<std::string> &input, const std::string &dataset, bool paired, std::vector<InFile> &files,
+                       std::vector<Group> &groups, std::vector<DatasetLib> &outlibs) {
+    std::vector<DatasetLib> libs;
+    if (dataset.empty()) {
+        libs.emplace_back();
+        if (paired) {
+            if (input.size() % 2) fatal("--paired: %zu input files: a pair is a left and a right file", input.size());
+            for (size_t i = 0; i < input.size(); ++i) libs[0].v[i % 2 ? LIB_RIGHT : LIB_LEFT].push_back(input[i]);
+        } else {
+            libs[0].v[LIB_SINGLE] = input;
+        }
+    } else {
+        std::string err;
+        if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
+    }
+    for (size_t ilib = 0; ilib < libs.size(); ++ilib) {
+        const DatasetLib &lib = libs[ilib];
+        outlibs.emplace_back();
+        outlibs.back().type = lib.type;
+        outlibs.back().orientation = lib.orientation;
+        size_t iread = 0;
+        auto single = [&](const std::string &p, int kind) {
+            files.push_back({p, ilib, iread++, kind});
+            groups.push_back({files.size() - 1, -1});
+        };
+        if (paired) {
+            if (!lib.v[LIB_INTERLACED].empty())
+                fatal("--paired: library %zu has interlaced reads (%s): interlaced libraries are not supported", ilib,
+                      lib.v[LIB_INTERLACED][0].c_str());
+            if (lib.v[LIB_LEFT].size() != lib.v[LIB_RIGHT].size())
+                fatal("--paired: library %zu has %zu left and %zu right read files", ilib, lib.v[LIB_LEFT].size(), lib.v[LIB_RIGHT].size());
+            for (size_t i = 0; i < lib.v[LIB_LEFT].size(); ++i, ++iread) {
+                files.push_back({lib.v[LIB_LEFT][i], ilib, iread, LIB_LEFT});
+                files.push_back({lib.v[LIB_RIGHT][i], ilib, iread, LIB_RIGHT});
+                groups.push_back({files.size() - 2, (long)files.size() - 1});
+            }
+        } else {  // every file a single-read file, in the order of the dataset's keys
+            for (int kind : {LIB_LEFT, LIB_RIGHT, LIB_INTERLACED})
+                for (const std::string &p : lib.v[kind]) single(p, LIB_SINGLE);
+        }
+        for (const std::string &p : lib.v[LIB_MERGED]) single(p, LIB_MERGED);
+        for (const std::string &p : lib.v[LIB_SINGLE]) single(p, LIB_SINGLE);
+    }
+}
+
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4, resident_bytes = 0;
-    std::string prefix, dataset;
+    std::string prefix, dataset, out_dir;
     std::vector<std::string> input;
     unsigned expand_max_iterations = 25;  // configs/hammer/config.info
     unsigned long long expand_min_changed = 10;  // main.cpp:219
-    bool help = false, cluster = false, subcluster = false, expand = false, correct = false;
+    bool help = false, cluster = false, subcluster = false, expand = false, correct = false, correct_stats = false, paired = false;
     bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
     Options opt;
     opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
@@ -273,6 +427,7 @@ int main(int argc, char **argv) {
         .flag("", "--subcluster", [&] { cluster = subcluster = true; })
         .flag("", "--expand", [&] { cluster = subcluster = expand = true; })
         .flag("", "--correct", [&] { cluster = subcluster = expand = correct = true; })
+        .flag("", "--correct-stats", &correct_stats).flag("", "--paired", &paired).str("", "--output-dir", &out_dir)
         .num("", "--expand-max-iterations", &expand_max_iterations, 1u).num("", "--expand-min-changed", &expand_min_changed)
         .flag("", "--no-correct-threshold", [&] { sp.correct_use_threshold = 0; })
         .real("", "--singleton-threshold", &sp.singleton_threshold)
@@ -288,7 +443,16 @@ int main(int argc, char **argv) {
 
     info("Starting k-mer statistics (MI355X, %s)", bbk_version());
     info("K-mer length set to %u", K);
-    const std::vector<std::string> files = input_files(input, dataset);
+    std::vector<InFile> files;
+    std::vector<Group> groups;
+    std::vector<DatasetLib> outlibs;
+    plan_input(input, dataset, paired, files, groups, outlibs);
+    if (correct && !out_dir.empty()) {  // the names in corrected.yaml are absolute: a reader resolves relative ones against it
+        if (mkdir(out_dir.c_str(), 0755) != 0 && errno != EEXIST) fatal("cannot create %s", out_dir.c_str());
+        char real[PATH_MAX];
+        if (!realpath(out_dir.c_str(), real)) fatal("cannot resolve %s", out_dir.c_str());
+        out_dir = real;
+    }
     Run run;
     Phases &ph = run.ph;
     run.create_ctx(device);
@@ -299,7 +463,7 @@ int main(int argc, char **argv) {
     check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
     uint64_t stretches = 0;
     double t0 = now_s();
-    ReadSource src(ctx, files, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, resident_bytes);
+    ReadSource src(ctx, files, groups, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, resident_bytes);
     const uint64_t records = src.each(true, [&](const Block &b) {
         const bbk_reads *r = nullptr;
         check(bbk_hreads_stretch_view(b.hr, &r, nullptr), "bbk_hreads_stretch_view");
@@ -364,18 +528,23 @@ int main(int argc, char **argv) {
             }
             info("Solid k-mers finalized");
             check(bbk_expander_store(ex, sc), "bbk_expander_store");
-            if (correct) {  // hammer_tools.cpp:218-277, every file as a single-read file
+            if (correct) {  // hammer_tools.cpp:218-277
                 bbk_corrector *cor = nullptr;
                 check(bbk_corrector_from_expander(ctx, set, ex, &cor), "bbk_corrector_from_expander");
                 info("Starting read correction.");
-                CorrectedWriter w{files, prefix, ctx, cor, (int)qvoffset};
-                src.each(false, std::ref(w));
+                CorrectedWriter w{files, groups, prefix, out_dir, ctx, cor, (int)qvoffset, correct_stats, outlibs};
+                src.each_group(false, std::ref(w));
                 w.finish();
                 uint64_t cs[5];
                 check(bbk_corrector_stats(cor, cs), "bbk_corrector_stats");
                 info("Correction done. Changed %llu bases in %llu reads.", (unsigned long long)cs[1], (unsigned long long)cs[0]);
                 info("Failed to correct %llu bases out of %llu.", (unsigned long long)cs[2], (unsigned long long)cs[3]);
                 info("  Searches corrected on the host: %llu", (unsigned long long)cs[4]);
+                if (!out_dir.empty()) {  // main.cpp:254-256
+                    const std::string yaml = out_dir + "/corrected.yaml";
+                    info("Saving corrected dataset description to %s", yaml.c_str());
+                    if (!save_dataset_yaml(yaml, outlibs)) fatal("cannot write %s", yaml.c_str());
+                }
                 bbk_corrector_free(cor);
             }
             bbk_expander_free(ex);
