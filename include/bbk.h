@@ -618,7 +618,9 @@ void bbk_corrector_limits(unsigned *heap_cap, unsigned *pop_cap);
  * order of libstdc++'s push_heap / pop_heap, which the device's heap follows step for step.
  * h_where (n_reads bytes, or NULL): 0 no search, 1 searched on the device, 2 a search of the read went through the host
  * rule (capacities above, or BBK_CORRECTOR_HOST=1 in the environment, which sends every search there).  The call waits.
- * BBK_ERR_ARG: descending offsets, a read of more than 65535 bases (positions are 16 bits, :20), a quality above 93. */
+ * The reads are prepared with BBK_NO_TRIM (below: uploaded, the generator's stretches cut on the device), then the call is
+ * bbk_corrector_correct_prepared; its output offsets are h_offsets less h_offsets[0].
+ * BBK_ERR_ARG: descending offsets, a quality above 93, a read of more than 65535 bases (positions are 16 bits, :20). */
 int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *h_qual, const uint64_t *h_offsets,
                           uint64_t n_reads, char *h_out, uint8_t *h_result, uint8_t *h_where);
 /* summed over the calls so far: changed reads, changed nucleotides, uncorrected nucleotides, total nucleotides
@@ -644,7 +646,11 @@ typedef struct bbk_hreads bbk_hreads; /* a batch of records as parsed, their tri
  *               starts are in the trimmed read: what bbk_corrector_correct computes for the same trimmed reads;
  *   the flag    1 when the k-mer table holds exactly one stretch and that is the whole trimmed read: the records
  *               Expander::operator() can ever find solid (expander.cpp:30-51).
+ * trim_quality BBK_NO_TRIM: the records are trimmed already and are taken whole -- every trim is (0, size) -- and the
+ * tables and the flag are those of a trimmed read of these bases; the trimmed layout of such a batch is the batch itself,
+ * so nothing is gathered for the corrector or the printer.  It is the one value of trim_quality that is not a quality.
  * BBK_ERR_ARG: k outside 1..32, descending offsets, a quality above 93, a record of 2^31 bases or more. */
+#define BBK_NO_TRIM (-2147483647 - 1) /* INT_MIN */
 int bbk_hreads_from_host(bbk_ctx *ctx, const char *h_bases, const uint8_t *h_qual, const uint64_t *h_offsets, uint64_t n,
                          unsigned k, int trim_quality, bbk_hreads **out);
 uint64_t bbk_hreads_size(const bbk_hreads *hr);               /* records */
@@ -662,8 +668,8 @@ int bbk_hreads_stretch_view(const bbk_hreads *hr, const bbk_reads **reads, const
 /* The trimmed read of every candidate (expander.cpp:20-29), for bbk_expander_push / bbk_expander_run; owned and cached
  * like the stretch view. */
 int bbk_hreads_candidate_view(const bbk_hreads *hr, const bbk_reads **reads);
-/* CorrectReadsBatch (hammer_tools.cpp:79-105) over the trimmed reads of the batch: bbk_corrector_correct without its
- * host preparation -- the bases, the qualities and the corrector table are the resident ones.  h_out receives the
+/* CorrectReadsBatch (hammer_tools.cpp:79-105) over the trimmed reads of the batch: the bases, the qualities and the
+ * corrector table are the resident ones (bbk_corrector_correct is this call on a BBK_NO_TRIM batch).  h_out receives the
  * corrected trimmed reads back to back, read i at [h_out_offsets[i], h_out_offsets[i + 1]) (n + 1 entries, from 0; the
  * caller sizes h_out for the bases of the batch, which no trim exceeds); h_result, h_where and the counters are those
  * of bbk_corrector_correct on the same trimmed reads.  h_where may be NULL.

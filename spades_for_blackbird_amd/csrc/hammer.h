@@ -85,10 +85,12 @@ struct bbk_hreads {
         bbk_quals quals;
     };
     mutable View stretch_view, candidate_view;
-    struct Trimmed {  // the trimmed reads back to back, what the corrector's kernels read
+    struct Trimmed {  // the trimmed reads back to back, what the corrector's kernels and the printer read
         bool made = false;
-        bbk::DevBuf bases, quals, off;  // total u8 each; n + 1 u64
+        const uint8_t *bases = nullptr, *quals = nullptr;  // total u8 each
+        const uint64_t *off = nullptr;                     // n + 1
         uint64_t total = 0;
+        bbk::DevBuf own_bases, own_quals, own_off;  // the gather; empty for a BBK_NO_TRIM batch, whose own arrays are the layout
     };
     mutable Trimmed trimmed;
 };
@@ -115,8 +117,12 @@ struct bbk_fastq_text {
 
 namespace bbk {
 
-// hreads.hip: fills hr->trimmed on first use (two launches, one scan, one wait)
+// hreads.hip: fills hr->trimmed on first use (two launches, one scan, one wait; nothing for a BBK_NO_TRIM batch)
 const bbk_hreads::Trimmed &hreads_trimmed(const bbk_hreads *hr);
+// hreads.hip: bbk_hreads_from_host behind its NULL checks, for the entry `fn`, which calls a record a `unit` in its refusals
+std::unique_ptr<bbk_hreads> hreads_from_host(const char *fn, const char *unit, bbk_ctx *ctx, const char *h_bases,
+                                             const uint8_t *h_qual, const uint64_t *h_offsets, uint64_t n, unsigned k,
+                                             int trim_quality);
 // readprint.hip: fills cr->changed and cr->tag from cr->out, res and where (one launch, no wait)
 void corrected_outcome(bbk_corrected *cr);
 

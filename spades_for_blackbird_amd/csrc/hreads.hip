@@ -6,7 +6,9 @@
 // ReadCorrector apply them (kmer_data.cpp:163-186, expander.cpp:20-29, read_corrector.cpp:160-176), restated for the host in
 // host/hammer_reads.hpp.  A batch keeps the records as parsed in HBM, and for every record its trim, the generator's valid
 // starts as stretches under both nucleotide predicates (ACGTacgt: the k-mer table; ACGT: the corrector table) and the
-// expander-candidate flag.
+// expander-candidate flag.  trim_quality BBK_NO_TRIM (INT_MIN, which until then meant "trim only Ns" and which nobody
+// passed: the one addition to the accepted inputs) takes the records as trimmed already: every trim is (0, n), the rest
+// follows from it, and the trimmed layout is the batch's own arrays (hreads_trimmed gathers nothing).
 //
 // The two rules are sequential walks in the reference; here they are a closed form over first / last positions and run
 // lengths (tests/hreads_restated.py states it, tests/test_hreads_restated.py holds it against the literal rules):
@@ -120,7 +122,8 @@ __global__ __launch_bounds__(256) void k_hr_prepare(const uint8_t *__restrict__ 
     const uint32_t n = (uint32_t)(off[r + 1] - base);
     // ---- Read::trimNsAndBadQuality ----
     uint32_t first = kHrNone, last = 0;
-    for (uint32_t cb = 0; cb < n; cb += 64u) {
+    const bool whole = trim_quality == BBK_NO_TRIM;  // trimmed already: (0, n)
+    for (uint32_t cb = 0; cb < n && !whole; cb += 64u) {
         const uint32_t p = cb + lane;
         bool g = false;
         if (p < n) g = bases[base + p] != 'N' && (int)quals[base + p] > trim_quality;
@@ -130,7 +133,7 @@ __global__ __launch_bounds__(256) void k_hr_prepare(const uint8_t *__restrict__ 
             last = cb + hr_top_bit(m);
         }
     }
-    uint32_t tstart = 0, len = 0;
+    uint32_t tstart = 0, len = whole ? n : 0;
     if (first != kHrNone) {
         tstart = first;
         len = n - first;
@@ -333,23 +336,114 @@ static void hr_make_view(const bbk_hreads *hr, int mode, bool with_quals, bbk_hr
 const bbk_hreads::Trimmed &hreads_trimmed(const bbk_hreads *hr) {
     bbk_hreads::Trimmed &t = hr->trimmed;
     if (t.made) return t;
+    if (hr->trim_quality == BBK_NO_TRIM) {  // every trim is (0, n): the records as parsed are the layout
+        t.bases = hr->bases.as<uint8_t>();
+        t.quals = hr->quals.as<uint8_t>();
+        t.off = hr->off.as<uint64_t>();
+        t.total = hr->bytes;
+        t.made = true;
+        return t;
+    }
     bbk_ctx *ctx = hr->ctx;
     HrRanges g;
     hr_ranges(hr, 0, g);
-    t.bases.alloc(g.n_bytes);
-    t.quals.alloc(g.n_bytes);
+    t.own_bases.alloc(g.n_bytes);
+    t.own_quals.alloc(g.n_bytes);
     if (g.m) {
         KernelTimer timer(ctx, "k_hr_copy");
         launch_items(ctx, "k_hr_copy", k_hr_copy, g.m * 64, hr->bases.as<uint8_t>(), g.first.as<uint64_t>(), g.len.as<uint32_t>(),
-                     g.boff.as<uint64_t>(), g.m, t.bases.as<uint8_t>());
+                     g.boff.as<uint64_t>(), g.m, t.own_bases.as<uint8_t>());
         launch_items(ctx, "k_hr_copy", k_hr_copy, g.m * 64, hr->quals.as<uint8_t>(), g.first.as<uint64_t>(), g.len.as<uint32_t>(),
-                     g.boff.as<uint64_t>(), g.m, t.quals.as<uint8_t>());
+                     g.boff.as<uint64_t>(), g.m, t.own_quals.as<uint8_t>());
     }
     BBK_HIP(hipStreamSynchronize(ctx->stream));
-    t.off = std::move(g.boff);
+    t.own_off = std::move(g.boff);
+    t.bases = t.own_bases.as<uint8_t>();
+    t.quals = t.own_quals.as<uint8_t>();
+    t.off = t.own_off.as<uint64_t>();
     t.total = g.n_bytes;
     t.made = true;
     return t;
+}
+
+// The offsets, then the qualities, are checked here for every entry that takes records from the host; a record is a `unit`
+// in what `fn` refuses
+std::unique_ptr<bbk_hreads> hreads_from_host(const char *fn, const char *unit, bbk_ctx *ctx, const char *h_bases,
+                                             const uint8_t *h_qual, const uint64_t *h_offsets, uint64_t n, unsigned k,
+                                             int trim_quality) {
+    BBK_REQUIRE(k >= 1 && k <= 32, BBK_ERR_ARG, "%s: k = %u: one-word k-mers only (1 <= k <= 32)", fn, k);
+    const uint64_t first = h_offsets[0];
+    uint64_t longest = 0;
+    for (uint64_t r = 0; r < n; ++r) {
+        BBK_REQUIRE(h_offsets[r] <= h_offsets[r + 1], BBK_ERR_ARG, "%s: the offsets of %s %llu descend", fn, unit,
+                    (unsigned long long)r);
+        longest = std::max(longest, h_offsets[r + 1] - h_offsets[r]);
+    }
+    BBK_REQUIRE(longest < (1ull << 31), BBK_ERR_ARG, "%s: a %s of %llu bases: fewer than 2^31 are needed", fn, unit,
+                (unsigned long long)longest);
+    const uint64_t bytes = h_offsets[n] - first;
+    BBK_REQUIRE(bytes == 0 || (h_bases && h_qual), BBK_ERR_ARG, "%s: NULL argument", fn);
+    BBK_REQUIRE(bytes <= kHrCountMask && n <= kHrCountMask, BBK_ERR_ARG,
+                "%s: %llu bases in %llu %ss: at most 2^%u of either in one batch", fn, (unsigned long long)bytes,
+                (unsigned long long)n, unit, kHrCandShift);
+    uint8_t worst = 0;
+#pragma omp parallel for reduction(max : worst) schedule(static)
+    for (int64_t i = 0; i < (int64_t)bytes; ++i) worst = std::max(worst, h_qual[first + i]);
+    if (worst > kHrMaxQual)  // say where, like the other entries do
+        for (uint64_t i = first; i < first + bytes; ++i)
+            BBK_REQUIRE(h_qual[i] <= kHrMaxQual, BBK_ERR_ARG,
+                        "%s: the quality at byte %llu is %u: %u at most (the offset is already subtracted)", fn,
+                        (unsigned long long)i, (unsigned)h_qual[i], kHrMaxQual);
+    BBK_HIP(hipSetDevice(ctx->device));
+    auto hr = std::make_unique<bbk_hreads>();
+    hr->ctx = ctx;
+    hr->k = k;
+    hr->trim_quality = trim_quality;
+    hr->n = n;
+    hr->bytes = bytes;
+    hr->longest = longest;
+    raw_vector<uint64_t> rel(n + 1);
+    for (uint64_t r = 0; r <= n; ++r) rel[r] = h_offsets[r] - first;
+    upload(ctx, hr->bases, (const uint8_t *)h_bases + first, bytes);
+    upload(ctx, hr->quals, h_qual + first, bytes);
+    upload(ctx, hr->off, rel.data(), n + 1);
+    hr->trim.alloc(n * 8);
+    hr->cand.alloc(n);
+    hr->koff.alloc((n + 1) * 8);
+    hr->coff.alloc((n + 1) * 8);
+    hr->cpos.alloc((n + 1) * 8);
+    if (n == 0) {
+        BBK_HIP(hipMemsetAsync(hr->koff.p, 0, 8, ctx->stream));
+        BBK_HIP(hipMemsetAsync(hr->coff.p, 0, 8, ctx->stream));
+        BBK_HIP(hipMemsetAsync(hr->cpos.p, 0, 8, ctx->stream));
+        hr->kst.alloc(0);
+        hr->cst.alloc(0);
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        return hr;
+    }
+    DevBuf packed((n + 1) * 8);
+    launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<false>, n * 64, hr->bases.as<uint8_t>(), hr->quals.as<uint8_t>(),
+                       hr->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, hr->trim.as<uint32_t>(), hr->cand.as<uint8_t>(),
+                       packed.as<uint64_t>(), hr->coff.as<uint64_t>(), (uint64_t *)nullptr, (uint64_t *)nullptr,
+                       (uint32_t *)nullptr, (uint32_t *)nullptr);
+    uint64_t totals[2] = {0, 0};  // the one wait: the uploads are done with it as well
+    exclusive_scan2_u64(ctx, packed.as<uint64_t>(), packed.as<uint64_t>(), hr->coff.as<uint64_t>(), hr->coff.as<uint64_t>(), n,
+                        totals);
+    hr->n_kst = totals[0] & kHrCountMask;
+    hr->n_cand = totals[0] >> kHrCandShift;
+    hr->n_cst = totals[1];
+    BBK_REQUIRE(hr->n_kst <= bytes && hr->n_cst <= bytes && hr->n_cand <= n, BBK_ERR_INTERNAL,
+                "%s: %llu + %llu stretches, %llu candidates for %llu bases in %llu %ss", fn,
+                (unsigned long long)hr->n_kst, (unsigned long long)hr->n_cst, (unsigned long long)hr->n_cand,
+                (unsigned long long)bytes, (unsigned long long)n, unit);
+    hr->kst.alloc(hr->n_kst * 8);
+    hr->cst.alloc(hr->n_cst * 8);
+    launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<true>, n * 64, hr->bases.as<uint8_t>(), hr->quals.as<uint8_t>(),
+                       hr->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, (uint32_t *)nullptr, (uint8_t *)nullptr,
+                       packed.as<uint64_t>(), hr->coff.as<uint64_t>(), hr->koff.as<uint64_t>(), hr->cpos.as<uint64_t>(),
+                       hr->kst.as<uint32_t>(), hr->cst.as<uint32_t>());
+    BBK_HIP(hipStreamSynchronize(ctx->stream));  // `packed` goes now
+    return hr;
 }
 
 }  // namespace bbk
@@ -362,80 +456,7 @@ int bbk_hreads_from_host(bbk_ctx *ctx, const char *h_bases, const uint8_t *h_qua
                          unsigned k, int trim_quality, bbk_hreads **out) {
     return guarded([&] {
         BBK_REQUIRE(ctx && out && h_offsets, BBK_ERR_ARG, "bbk_hreads_from_host: NULL argument");
-        BBK_REQUIRE(k >= 1 && k <= 32, BBK_ERR_ARG, "bbk_hreads_from_host: k = %u: one-word k-mers only (1 <= k <= 32)", k);
-        const uint64_t first = h_offsets[0];
-        uint64_t longest = 0;
-        for (uint64_t r = 0; r < n; ++r) {
-            BBK_REQUIRE(h_offsets[r] <= h_offsets[r + 1], BBK_ERR_ARG, "bbk_hreads_from_host: the offsets of record %llu descend",
-                        (unsigned long long)r);
-            longest = std::max(longest, h_offsets[r + 1] - h_offsets[r]);
-        }
-        BBK_REQUIRE(longest < (1ull << 31), BBK_ERR_ARG, "bbk_hreads_from_host: a record of %llu bases: fewer than 2^31 are needed",
-                    (unsigned long long)longest);
-        const uint64_t bytes = h_offsets[n] - first;
-        BBK_REQUIRE(bytes == 0 || (h_bases && h_qual), BBK_ERR_ARG, "bbk_hreads_from_host: NULL argument");
-        BBK_REQUIRE(bytes <= kHrCountMask && n <= kHrCountMask, BBK_ERR_ARG,
-                    "bbk_hreads_from_host: %llu bases in %llu records: at most 2^%u of either in one batch", (unsigned long long)bytes,
-                    (unsigned long long)n, kHrCandShift);
-        uint8_t worst = 0;
-#pragma omp parallel for reduction(max : worst) schedule(static)
-        for (int64_t i = 0; i < (int64_t)bytes; ++i) worst = std::max(worst, h_qual[first + i]);
-        if (worst > kHrMaxQual)  // say where, like the other entries do
-            for (uint64_t i = first; i < first + bytes; ++i)
-                BBK_REQUIRE(h_qual[i] <= kHrMaxQual, BBK_ERR_ARG,
-                            "bbk_hreads_from_host: the quality at byte %llu is %u: %u at most (the offset is already subtracted)",
-                            (unsigned long long)i, (unsigned)h_qual[i], kHrMaxQual);
-        BBK_HIP(hipSetDevice(ctx->device));
-        auto hr = std::make_unique<bbk_hreads>();
-        hr->ctx = ctx;
-        hr->k = k;
-        hr->trim_quality = trim_quality;
-        hr->n = n;
-        hr->bytes = bytes;
-        hr->longest = longest;
-        raw_vector<uint64_t> rel(n + 1);
-        for (uint64_t r = 0; r <= n; ++r) rel[r] = h_offsets[r] - first;
-        upload(ctx, hr->bases, (const uint8_t *)h_bases + first, bytes);
-        upload(ctx, hr->quals, h_qual + first, bytes);
-        upload(ctx, hr->off, rel.data(), n + 1);
-        hr->trim.alloc(n * 8);
-        hr->cand.alloc(n);
-        hr->koff.alloc((n + 1) * 8);
-        hr->coff.alloc((n + 1) * 8);
-        hr->cpos.alloc((n + 1) * 8);
-        if (n == 0) {
-            BBK_HIP(hipMemsetAsync(hr->koff.p, 0, 8, ctx->stream));
-            BBK_HIP(hipMemsetAsync(hr->coff.p, 0, 8, ctx->stream));
-            BBK_HIP(hipMemsetAsync(hr->cpos.p, 0, 8, ctx->stream));
-            hr->kst.alloc(0);
-            hr->cst.alloc(0);
-            BBK_HIP(hipStreamSynchronize(ctx->stream));
-            *out = hr.release();
-            return;
-        }
-        DevBuf packed((n + 1) * 8);
-        launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<false>, n * 64, hr->bases.as<uint8_t>(), hr->quals.as<uint8_t>(),
-                           hr->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, hr->trim.as<uint32_t>(), hr->cand.as<uint8_t>(),
-                           packed.as<uint64_t>(), hr->coff.as<uint64_t>(), (uint64_t *)nullptr, (uint64_t *)nullptr,
-                           (uint32_t *)nullptr, (uint32_t *)nullptr);
-        uint64_t totals[2] = {0, 0};  // the one wait: the uploads are done with it as well
-        exclusive_scan2_u64(ctx, packed.as<uint64_t>(), packed.as<uint64_t>(), hr->coff.as<uint64_t>(), hr->coff.as<uint64_t>(), n,
-                            totals);
-        hr->n_kst = totals[0] & kHrCountMask;
-        hr->n_cand = totals[0] >> kHrCandShift;
-        hr->n_cst = totals[1];
-        BBK_REQUIRE(hr->n_kst <= bytes && hr->n_cst <= bytes && hr->n_cand <= n, BBK_ERR_INTERNAL,
-                    "bbk_hreads_from_host: %llu + %llu stretches, %llu candidates for %llu bases in %llu records",
-                    (unsigned long long)hr->n_kst, (unsigned long long)hr->n_cst, (unsigned long long)hr->n_cand,
-                    (unsigned long long)bytes, (unsigned long long)n);
-        hr->kst.alloc(hr->n_kst * 8);
-        hr->cst.alloc(hr->n_cst * 8);
-        launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<true>, n * 64, hr->bases.as<uint8_t>(), hr->quals.as<uint8_t>(),
-                           hr->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, (uint32_t *)nullptr, (uint8_t *)nullptr,
-                           packed.as<uint64_t>(), hr->coff.as<uint64_t>(), hr->koff.as<uint64_t>(), hr->cpos.as<uint64_t>(),
-                           hr->kst.as<uint32_t>(), hr->cst.as<uint32_t>());
-        BBK_HIP(hipStreamSynchronize(ctx->stream));  // `packed` goes now
-        *out = hr.release();
+        *out = hreads_from_host("bbk_hreads_from_host", "record", ctx, h_bases, h_qual, h_offsets, n, k, trim_quality).release();
     });
 }
 

@@ -5,8 +5,8 @@
 // EQUAL to it: every corrected base, every result flag, every counter -- and that includes the order in which
 // std::priority_queue pops states of equal (penalty, pos), which is libstdc++'s __push_heap / __adjust_heap.
 // Kernels:
-//   k_rc_island   one wavefront per read, lanes over the generator's valid starts (host/hammer_reads.hpp:
-//                 generator_stretches) in chunks of 64: one table_find<1> and one good byte per start, the good starts of a
+//   k_rc_island   one wavefront per read, lanes over the generator's valid starts (the corrector table of the prepared
+//                 batch, hreads.hip) in chunks of 64: one table_find<1> and one good byte per start, the good starts of a
 //                 chunk as one 64-bit ballot, the longest run of consecutive good starts over those masks with the run
 //                 carried from chunk to chunk (the earliest run wins a tie: strict >, :185).  Writes the island and the
 //                 result flag of the reads that need no search, and appends (read, direction) work items for the others.
@@ -20,15 +20,17 @@
 // exactly when `corrections` would hold more than kRcHeapCap states after a flush, when it pops more than kRcPopCap times,
 // or when its edit log fills (kRcEditCap = 3 * kRcPopCap nodes: a pop makes three at most, so the pop cap always comes
 // first).  Both paths give the same bytes.
-// Two doors lead to the same code (rc_run): bbk_corrector_correct cuts the generator's stretches on the host and uploads
-// bases, qualities and table; bbk_corrector_correct_resident takes all three from a bbk_hreads (hreads.hip), resident, and
-// keeps the outcome there as well (bbk_corrected: what readprint.hip prints); bbk_corrector_correct_prepared is that call
-// followed by bbk_corrected_export.
+// One path (rc_correct) serves every entry, and it runs on a prepared batch (bbk_hreads, hreads.hip): the bases, the
+// qualities and the generator's stretches are the resident ones, and the outcome stays resident as well (bbk_corrected: what
+// readprint.hip prints).  bbk_corrector_correct_resident is that path; bbk_corrector_correct_prepared is it followed by
+// bbk_corrected_export; bbk_corrector_correct, which takes host arrays that are trimmed already, prepares them with
+// BBK_NO_TRIM first -- an upload and two k_hr_prepare launches where it used to cut the stretches on the host -- and exports
+// into the caller's layout.  The steps: rc_device_pass (island, search), rc_host_tail (the searches beyond the capacities,
+// their spans copied back), rc_uncorrected; changed reads and bases are k_rp_outcome's per-read counts.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <memory>
 
 #include "hammer.h"
@@ -366,137 +368,6 @@ static void rc_fetch_set(bbk_corrector *c) {
 using namespace bbk;
 namespace rch = bbkhost::readcorrect;
 
-// A batch of trimmed reads with the generator's stretches, as the device pass and the host tail see it: the bases, the
-// qualities, the offsets (n_reads + 1, from 0) and the stretch table on the device (the caller's uploads, or the resident
-// ones of a bbk_hreads), the offsets on the host as well.  h_bases / h_qual are asked for only when a search goes through
-// the host rule.
-struct RcBatch {
-    uint64_t n_reads = 0, bytes = 0;
-    uint32_t longest = 0;
-    const uint8_t *d_bases = nullptr, *d_qual = nullptr;
-    const uint64_t *d_off = nullptr, *d_stoff = nullptr;
-    const uint32_t *d_st = nullptr;
-    const uint64_t *h_offsets = nullptr;
-    std::function<const char *()> h_bases;
-    std::function<const uint8_t *()> h_qual;
-};
-
-// What rc_run leaves: the corrected reads and the flags on the device, where every read's searches ran on the host
-struct RcResult {
-    DevBuf out, res;            // bytes u8 (the batch's layout); n_reads u8
-    raw_vector<uint8_t> where;  // n_reads: 0 no search, 1 device, 2 host rule
-    bool searched = false;      // a search ran at all: otherwise `out` is a copy of the bases
-};
-
-// CorrectReadsBatch behind the stretch table: k_rc_island, k_rc_search, the searches beyond the capacities by the host
-// rule -- their spans are copied back into `out`, and only those -- and the counters but the two that compare the reads
-// (changed reads, changed nucleotides: the caller's, which knows where the reads are).
-static void rc_run(bbk_corrector *c, const RcBatch &b, RcResult &R) {
-    bbk_ctx *ctx = c->ctx;
-    const unsigned k = c->k;
-    const uint64_t n_reads = b.n_reads, bytes = b.bytes;
-    const uint64_t *h_offsets = b.h_offsets;
-    raw_vector<uint32_t> thr(b.longest + 1);
-    thr[0] = 0;
-    for (uint32_t n = 1; n <= b.longest; ++n) thr[n] = (uint32_t)rch::size_threshold(n);  // the same log2 as the host rule
-
-    // ---- device pass ----
-    DevBuf d_thr, d_isl(n_reads * 8), d_items(n_reads * 16), d_count(8), d_sstat(n_reads * 2);
-    R.out.alloc(bytes);
-    R.res.alloc(n_reads);
-    R.where.assign(n_reads, 0);
-    upload(ctx, d_thr, thr.data(), (uint64_t)thr.size());
-    BBK_HIP(copy_async(R.out.p, b.d_bases, bytes, hipMemcpyDeviceToDevice, ctx->stream));
-    BBK_HIP(hipMemsetAsync(d_count.p, 0, 8, ctx->stream));
-    BBK_HIP(hipMemsetAsync(d_sstat.p, 0, n_reads * 2, ctx->stream));
-    launch_items_timed(ctx, "k_rc_island", k_rc_island, n_reads * 64, b.d_bases, b.d_off, n_reads, (int)k, b.d_st, b.d_stoff,
-                       c->set->keys.as<Key<1>>(), c->prefix.table(), c->good.as<uint8_t>(), d_isl.as<uint32_t>(),
-                       R.res.as<uint8_t>(), d_count.as<unsigned long long>(), d_items.as<uint64_t>());
-    uint64_t n_items = 0;
-    d2h_sync(ctx, &n_items, d_count.p, 8);
-    BBK_REQUIRE(n_items <= 2 * n_reads, BBK_ERR_INTERNAL, "bbk_corrector_correct: %llu work items for %llu reads",
-                (unsigned long long)n_items, (unsigned long long)n_reads);
-    const char *env = getenv("BBK_CORRECTOR_HOST");
-    const bool host_only = env && atoi(env) != 0;
-    if (n_items && !host_only) {
-        KernelTimer t(ctx, "k_rc_search");
-        hipLaunchKernelGGL(k_rc_search, grid_blocks(n_items), dim3(64), 0, ctx->stream, b.d_bases, b.d_qual, b.d_off, (int)k, c->set->keys.as<Key<1>>(), c->prefix.table(),
-                           c->good.as<uint8_t>(), d_isl.as<uint32_t>(), d_items.as<uint64_t>(), n_items,
-                           d_thr.as<uint32_t>(), R.out.as<uint8_t>(), d_sstat.as<uint8_t>());
-        check_launch("k_rc_search");
-    }
-    R.searched = n_items != 0;
-    if (!n_items) {
-        BBK_HIP(hipStreamSynchronize(ctx->stream));  // thr goes now
-        return;
-    }
-    raw_vector<uint32_t> isl(n_reads * 2);
-    raw_vector<uint8_t> sstat(n_reads * 2);
-    d2h_big(ctx, isl.data(), d_isl.p, n_reads * 8);
-    d2h_big(ctx, sstat.data(), d_sstat.p, n_reads * 2);
-
-    // ---- the searches the device did not finish, by the host rule; then the counters ----
-    raw_vector<uint64_t> todo;  // read << 1 | direction
-    for (uint64_t r = 0; r < n_reads; ++r) {
-        const uint64_t len = h_offsets[r + 1] - h_offsets[r];
-        const uint32_t run = isl[2 * r + 1], solid = run ? run + k - 1 : 0;
-        if (!solid || solid == len) continue;
-        const uint32_t lleft = isl[2 * r], lright = lleft + solid - 1;
-        const size_t before = todo.size();
-        if (lright + 1 < len && (host_only || sstat[2 * r] == kRcOverflow)) todo.push_back(r << 1);
-        if (lleft > 0 && (host_only || sstat[2 * r + 1] == kRcOverflow)) todo.push_back((r << 1) | 1);
-        R.where[r] = todo.size() != before ? 2 : 1;
-    }
-    if (!todo.empty()) {
-        rc_fetch_set(c);
-        const char *h_bases = b.h_bases();
-        const uint8_t *h_qual = b.h_qual();
-        const uint64_t *hk = c->h_keys.data();
-        const uint8_t *hg = c->h_good.data();
-        const uint64_t hn = c->n;
-        auto lookup = [hk, hn](uint64_t key) -> uint64_t {
-            const uint64_t *it = std::lower_bound(hk, hk + hn, key);
-            return it != hk + hn && *it == key ? (uint64_t)(it - hk) : rch::kNone;
-        };
-        std::vector<std::string> span(todo.size());  // what a search made of the bases it may touch
-#pragma omp parallel for schedule(dynamic, 16)
-        for (int64_t j = 0; j < (int64_t)todo.size(); ++j) {
-            const uint64_t r = todo[j] >> 1, o = h_offsets[r], len = h_offsets[r + 1] - o;
-            const bool left = todo[j] & 1;
-            const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
-            const std::string seq(h_bases + o, len), qual((const char *)h_qual + o, len);
-            rch::SearchFigures fig;
-            if (!left) {
-                const std::string s = rch::CorrectReadRight(seq, qual, lright, k, lookup, hg, &fig);
-                span[j] = s.substr(lright + 1);  // it touches nothing else
-            } else {
-                const std::string s = rch::ReverseComplement(
-                    rch::CorrectReadRight(rch::ReverseComplement(seq), rch::Reverse(qual), len - 1 - lleft, k, lookup, hg, &fig));
-                span[j] = s.substr(0, lleft);
-            }
-            sstat[2 * r + left] = fig.failed ? kRcFailed : kRcDone;
-        }
-        for (size_t j = 0; j < todo.size(); ++j) {  // back into the device's reads: only the spans those searches own
-            const uint64_t r = todo[j] >> 1, o = h_offsets[r];
-            const uint64_t at = (todo[j] & 1) ? o : o + isl[2 * r] + isl[2 * r + 1] + k - 1;
-            if (!span[j].empty())
-                BBK_HIP(hipMemcpyAsync(R.out.as<uint8_t>() + at, span[j].data(), span[j].size(), hipMemcpyHostToDevice, ctx->stream));
-        }
-        BBK_HIP(hipStreamSynchronize(ctx->stream));  // the spans go now
-    }
-    uint64_t uncorrected = 0;
-#pragma omp parallel for reduction(+ : uncorrected)
-    for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
-        if (!R.where[r]) continue;
-        const uint64_t len = h_offsets[r + 1] - h_offsets[r];
-        const uint32_t lleft = isl[2 * r], lright = lleft + isl[2 * r + 1] + k - 2;
-        if (sstat[2 * r] == kRcFailed) uncorrected += len - lright;
-        if (sstat[2 * r + 1] == kRcFailed) uncorrected += lleft + 1;  // read_size - (read_size - 1 - lleft)
-    }
-    c->stats[2] += uncorrected;
-    c->stats[4] += todo.size();
-}
-
 static void rc_check(const char *fn, const bbk_corrector *c, const bbk_hreads *hr) {
     BBK_REQUIRE(hr->k == c->k, BBK_ERR_ARG, "%s: the batch was prepared for k = %u, the corrector's set has k = %u", fn, hr->k, c->k);
     BBK_REQUIRE(hr->ctx == c->ctx, BBK_ERR_ARG, "%s: the batch belongs to another context", fn);
@@ -505,17 +376,133 @@ static void rc_check(const char *fn, const bbk_corrector *c, const bbk_hreads *h
                 (unsigned long long)hr->longest, kRcMaxRead);
 }
 
-// CorrectReadsBatch over the trimmed reads of a prepared batch, the outcome resident: what bbk_corrector_correct_resident
-// and bbk_corrector_correct_prepared (fn) share.  h_off receives the offsets of the trimmed layout.
-static std::unique_ptr<bbk_corrected> rc_resident(const char *fn, bbk_corrector *c, const bbk_hreads *hr, raw_vector<uint64_t> &h_off) {
+// What the device pass leaves on the host for the tail and the counter
+struct RcPass {
+    uint64_t n_items = 0;       // searches: none -> the reads stay as they are, and nothing below is filled
+    bool host_only = false;     // BBK_CORRECTOR_HOST: no search ran on the device
+    raw_vector<uint32_t> isl;   // n_reads x (first start, starts) of the longest run
+    raw_vector<uint8_t> sstat;  // n_reads x (right, left): what the search came to
+};
+
+// k_rc_island over the batch's corrector table, then k_rc_search for every work item: cr->res, and the searched spans of
+// cr->out (a copy of the trimmed reads so far)
+static void rc_device_pass(bbk_corrector *c, const bbk_hreads *hr, uint32_t longest, bbk_corrected *cr, RcPass &P) {
+    bbk_ctx *ctx = c->ctx;
+    const unsigned k = c->k;
+    const uint64_t n_reads = hr->n;
+    const bbk_hreads::Trimmed &t = hreads_trimmed(hr);
+    raw_vector<uint32_t> thr(longest + 1);
+    thr[0] = 0;
+    for (uint32_t n = 1; n <= longest; ++n) thr[n] = (uint32_t)rch::size_threshold(n);  // the same log2 as the host rule
+    DevBuf d_thr, d_isl(n_reads * 8), d_items(n_reads * 16), d_count(8), d_sstat(n_reads * 2);
+    upload(ctx, d_thr, thr.data(), (uint64_t)thr.size());
+    BBK_HIP(hipMemsetAsync(d_count.p, 0, 8, ctx->stream));
+    BBK_HIP(hipMemsetAsync(d_sstat.p, 0, n_reads * 2, ctx->stream));
+    launch_items_timed(ctx, "k_rc_island", k_rc_island, n_reads * 64, t.bases, t.off, n_reads, (int)k, hr->cst.as<uint32_t>(),
+                       hr->coff.as<uint64_t>(), c->set->keys.as<Key<1>>(), c->prefix.table(), c->good.as<uint8_t>(),
+                       d_isl.as<uint32_t>(), cr->res.as<uint8_t>(), d_count.as<unsigned long long>(), d_items.as<uint64_t>());
+    d2h_sync(ctx, &P.n_items, d_count.p, 8);
+    BBK_REQUIRE(P.n_items <= 2 * n_reads, BBK_ERR_INTERNAL, "bbk_corrector_correct: %llu work items for %llu reads",
+                (unsigned long long)P.n_items, (unsigned long long)n_reads);
+    const char *env = getenv("BBK_CORRECTOR_HOST");
+    P.host_only = env && atoi(env) != 0;
+    if (!P.n_items) return;
+    if (!P.host_only) {
+        KernelTimer timer(ctx, "k_rc_search");
+        hipLaunchKernelGGL(k_rc_search, grid_blocks(P.n_items), dim3(64), 0, ctx->stream, t.bases, t.quals, t.off, (int)k,
+                           c->set->keys.as<Key<1>>(), c->prefix.table(), c->good.as<uint8_t>(), d_isl.as<uint32_t>(),
+                           d_items.as<uint64_t>(), P.n_items, d_thr.as<uint32_t>(), cr->out.as<uint8_t>(), d_sstat.as<uint8_t>());
+        check_launch("k_rc_search");
+    }
+    P.isl.resize(n_reads * 2);
+    P.sstat.resize(n_reads * 2);
+    d2h_big(ctx, P.isl.data(), d_isl.p, n_reads * 8);
+    d2h_big(ctx, P.sstat.data(), d_sstat.p, n_reads * 2);
+}
+
+// The searches the device did not finish, by the host rule (readcorrect_host.hpp, OpenMP): their spans are copied back
+// into cr->out, and only those; the trimmed bases and qualities come to the host only when there is such a search.  Fills
+// `where` (n_reads, zeroed) and returns the number of those searches.
+static uint64_t rc_host_tail(bbk_corrector *c, const bbk_hreads *hr, const uint64_t *h_off, RcPass &P, bbk_corrected *cr,
+                             uint8_t *where) {
+    bbk_ctx *ctx = c->ctx;
+    const unsigned k = c->k;
+    raw_vector<uint64_t> todo;  // read << 1 | direction
+    for (uint64_t r = 0; r < hr->n; ++r) {
+        const uint64_t len = h_off[r + 1] - h_off[r];
+        const uint32_t run = P.isl[2 * r + 1], solid = run ? run + k - 1 : 0;
+        if (!solid || solid == len) continue;
+        const uint32_t lleft = P.isl[2 * r], lright = lleft + solid - 1;
+        const size_t before = todo.size();
+        if (lright + 1 < len && (P.host_only || P.sstat[2 * r] == kRcOverflow)) todo.push_back(r << 1);
+        if (lleft > 0 && (P.host_only || P.sstat[2 * r + 1] == kRcOverflow)) todo.push_back((r << 1) | 1);
+        where[r] = todo.size() != before ? 2 : 1;
+    }
+    if (todo.empty()) return 0;
+    rc_fetch_set(c);
+    const bbk_hreads::Trimmed &t = hreads_trimmed(hr);
+    raw_vector<char> h_bases(t.total), h_qual(t.total);
+    d2h_big(ctx, h_bases.data(), t.bases, t.total);
+    d2h_big(ctx, h_qual.data(), t.quals, t.total);
+    const uint64_t *hk = c->h_keys.data();
+    const uint8_t *hg = c->h_good.data();
+    const uint64_t hn = c->n;
+    auto lookup = [hk, hn](uint64_t key) -> uint64_t {
+        const uint64_t *it = std::lower_bound(hk, hk + hn, key);
+        return it != hk + hn && *it == key ? (uint64_t)(it - hk) : rch::kNone;
+    };
+    std::vector<std::string> span(todo.size());  // what a search made of the bases it may touch
+#pragma omp parallel for schedule(dynamic, 16)
+    for (int64_t j = 0; j < (int64_t)todo.size(); ++j) {
+        const uint64_t r = todo[j] >> 1, o = h_off[r], len = h_off[r + 1] - o;
+        const bool left = todo[j] & 1;
+        const uint32_t lleft = P.isl[2 * r], lright = lleft + P.isl[2 * r + 1] + k - 2;
+        const std::string seq(h_bases.data() + o, len), qual(h_qual.data() + o, len);
+        rch::SearchFigures fig;
+        if (!left) {
+            const std::string s = rch::CorrectReadRight(seq, qual, lright, k, lookup, hg, &fig);
+            span[j] = s.substr(lright + 1);  // it touches nothing else
+        } else {
+            const std::string s = rch::ReverseComplement(
+                rch::CorrectReadRight(rch::ReverseComplement(seq), rch::Reverse(qual), len - 1 - lleft, k, lookup, hg, &fig));
+            span[j] = s.substr(0, lleft);
+        }
+        P.sstat[2 * r + left] = fig.failed ? kRcFailed : kRcDone;
+    }
+    for (size_t j = 0; j < todo.size(); ++j) {  // back into the device's reads: only the spans those searches own
+        const uint64_t r = todo[j] >> 1, o = h_off[r];
+        const uint64_t at = (todo[j] & 1) ? o : o + P.isl[2 * r] + P.isl[2 * r + 1] + k - 1;
+        if (!span[j].empty())
+            BBK_HIP(hipMemcpyAsync(cr->out.as<uint8_t>() + at, span[j].data(), span[j].size(), hipMemcpyHostToDevice, ctx->stream));
+    }
+    BBK_HIP(hipStreamSynchronize(ctx->stream));  // the spans go now
+    return todo.size();
+}
+
+// the bases of the searches that failed (read_corrector.cpp:206-208)
+static uint64_t rc_uncorrected(unsigned k, uint64_t n_reads, const uint64_t *h_off, const RcPass &P, const uint8_t *where) {
+    uint64_t uncorrected = 0;
+#pragma omp parallel for reduction(+ : uncorrected)
+    for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
+        if (!where[r]) continue;
+        const uint64_t len = h_off[r + 1] - h_off[r];
+        const uint32_t lleft = P.isl[2 * r], lright = lleft + P.isl[2 * r + 1] + k - 2;
+        if (P.sstat[2 * r] == kRcFailed) uncorrected += len - lright;
+        if (P.sstat[2 * r + 1] == kRcFailed) uncorrected += lleft + 1;  // read_size - (read_size - 1 - lleft)
+    }
+    return uncorrected;
+}
+
+// CorrectReadsBatch over the trimmed reads of a prepared batch, the outcome resident: the one path of every entry (fn)
+static std::unique_ptr<bbk_corrected> rc_correct(const char *fn, bbk_corrector *c, const bbk_hreads *hr) {
     rc_check(fn, c, hr);
     bbk_ctx *ctx = c->ctx;
     BBK_HIP(hipSetDevice(ctx->device));
     const uint64_t n_reads = hr->n;
-    const bbk_hreads::Trimmed &t = hreads_trimmed(hr);  // the trimmed reads back to back, made once per batch
-    h_off.resize(n_reads + 1);
-    d2h_big(ctx, h_off.data(), t.off.p, (n_reads + 1) * 8);
     const unsigned k = c->k;
+    const bbk_hreads::Trimmed &t = hreads_trimmed(hr);  // the trimmed reads back to back, made once per batch
+    raw_vector<uint64_t> h_off(n_reads + 1);
+    d2h_big(ctx, h_off.data(), t.off, (n_reads + 1) * 8);
     uint64_t nucleotides = 0;
     uint32_t longest = 0;
     for (uint64_t r = 0; r < n_reads; ++r) {
@@ -529,59 +516,37 @@ static std::unique_ptr<bbk_corrected> rc_resident(const char *fn, bbk_corrector 
     cr->k = k;
     cr->n = n_reads;
     cr->total = t.total;
+    cr->out.alloc(t.total);
+    cr->res.alloc(n_reads);
     cr->where.alloc(n_reads);
     cr->changed.alloc(n_reads * 4);
     cr->tag.alloc(n_reads);
     uint64_t before[5];
     memcpy(before, c->stats, sizeof(before));
     c->stats[3] += nucleotides;
-    RcResult R;
-    raw_vector<char> orig;
-    raw_vector<uint8_t> qual;
-    if (c->n == 0 || nucleotides == 0) {  // no k-mer is good, or no read has k bases: every result is false
-        cr->out.alloc(t.total);
-        cr->res.alloc(n_reads);
-        if (t.total) BBK_HIP(copy_async(cr->out.p, t.bases.p, t.total, hipMemcpyDeviceToDevice, ctx->stream));
-        BBK_HIP(hipMemsetAsync(cr->res.p, 0, n_reads, ctx->stream));
-        BBK_HIP(hipMemsetAsync(cr->where.p, 0, n_reads, ctx->stream));
+    BBK_HIP(copy_async(cr->out.p, t.bases, t.total, hipMemcpyDeviceToDevice, ctx->stream));
+    RcPass P;
+    if (c->n != 0 && nucleotides != 0) rc_device_pass(c, hr, longest, cr.get(), P);
+    else BBK_HIP(hipMemsetAsync(cr->res.p, 0, n_reads, ctx->stream));  // no k-mer is good, or no read has k bases: all false
+    raw_vector<uint8_t> where;  // 0 no search, 1 device, 2 host rule
+    if (P.n_items) {
+        where.assign(n_reads, 0);
+        c->stats[4] += rc_host_tail(c, hr, h_off.data(), P, cr.get(), where.data());
+        c->stats[2] += rc_uncorrected(k, n_reads, h_off.data(), P, where.data());
+        BBK_HIP(hipMemcpyAsync(cr->where.p, where.data(), n_reads, hipMemcpyHostToDevice, ctx->stream));
     } else {
-        RcBatch b;
-        b.n_reads = n_reads;
-        b.bytes = t.total;
-        b.longest = longest;
-        b.d_bases = t.bases.as<uint8_t>();
-        b.d_qual = t.quals.as<uint8_t>();
-        b.d_off = t.off.as<uint64_t>();
-        b.d_st = hr->cst.as<uint32_t>();
-        b.d_stoff = hr->coff.as<uint64_t>();
-        b.h_offsets = h_off.data();
-        b.h_bases = [&] {
-            orig.resize(t.total);
-            d2h_big(ctx, orig.data(), t.bases.p, t.total);
-            return (const char *)orig.data();
-        };
-        b.h_qual = [&] {
-            qual.resize(t.total);
-            d2h_big(ctx, qual.data(), t.quals.p, t.total);
-            return (const uint8_t *)qual.data();
-        };
-        rc_run(c, b, R);
-        cr->out = std::move(R.out);
-        cr->res = std::move(R.res);
-        if (n_reads) BBK_HIP(hipMemcpyAsync(cr->where.p, R.where.data(), n_reads, hipMemcpyHostToDevice, ctx->stream));
+        BBK_HIP(hipMemsetAsync(cr->where.p, 0, n_reads, ctx->stream));
     }
     corrected_outcome(cr.get());
-    // changed reads, changed nucleotides (read_corrector.cpp:210-219): four bytes per read come back, not the reads
+    // changed reads, changed nucleotides (read_corrector.cpp:210-219): four bytes per read come back, not the reads; an
+    // unsearched read is a copy and counts 0
     raw_vector<uint32_t> changed(n_reads);
-    if (n_reads) d2h_big(ctx, changed.data(), cr->changed.p, n_reads * 4);  // waits: R.where goes after it
+    if (n_reads) d2h_big(ctx, changed.data(), cr->changed.p, n_reads * 4);  // waits: `where` goes after it
     else BBK_HIP(hipStreamSynchronize(ctx->stream));
-    uint64_t changed_reads = 0, changed_nucl = 0;
     for (uint64_t r = 0; r < n_reads; ++r) {
-        changed_reads += changed[r] != 0;
-        changed_nucl += changed[r];
+        c->stats[0] += changed[r] != 0;
+        c->stats[1] += changed[r];
     }
-    c->stats[0] += changed_reads;
-    c->stats[1] += changed_nucl;
     for (int i = 0; i < 5; ++i) cr->stats[i] = c->stats[i] - before[i];
     return cr;
 }
@@ -591,7 +556,7 @@ static void rc_export(bbk_ctx *ctx, const bbk_corrected *cr, char *h_out, uint64
     BBK_HIP(hipSetDevice(ctx->device));
     const uint64_t n = cr->n;
     if (h_out && cr->total) d2h_big(ctx, h_out, cr->out.p, cr->total);
-    if (h_out_offsets) d2h_big(ctx, h_out_offsets, hreads_trimmed(cr->hr).off.p, (n + 1) * 8);
+    if (h_out_offsets) d2h_big(ctx, h_out_offsets, hreads_trimmed(cr->hr).off, (n + 1) * 8);
     if (h_result && n) d2h_big(ctx, h_result, cr->res.p, n);
     if (h_where && n) d2h_big(ctx, h_where, cr->where.p, n);
     if (h_changed && n) d2h_big(ctx, h_changed, cr->changed.p, n * 4);
@@ -643,114 +608,17 @@ int bbk_corrector_correct(bbk_corrector *c, const char *h_bases, const uint8_t *
         const uint64_t first = h_offsets[0], total = h_offsets[n_reads];
         BBK_REQUIRE(first <= total && (total == first || (h_bases && h_qual && h_out)), BBK_ERR_ARG,
                     "bbk_corrector_correct: NULL argument");
-        uint32_t longest = 0;
-        for (uint64_t r = 0; r < n_reads; ++r) {
-            BBK_REQUIRE(h_offsets[r] <= h_offsets[r + 1], BBK_ERR_ARG, "bbk_corrector_correct: the offsets of read %llu descend",
-                        (unsigned long long)r);
-            const uint64_t len = h_offsets[r + 1] - h_offsets[r];
-            BBK_REQUIRE(len <= kRcMaxRead, BBK_ERR_ARG,
-                        "bbk_corrector_correct: read %llu has %llu bases: a position is 16 bits (read_corrector.cpp:20), %u at most",
-                        (unsigned long long)r, (unsigned long long)len, kRcMaxRead);
-            longest = std::max(longest, (uint32_t)len);
-        }
-        for (uint64_t i = first; i < total; ++i)
-            BBK_REQUIRE(h_qual[i] <= 93, BBK_ERR_ARG,
-                        "bbk_corrector_correct: the quality at byte %llu is %u: 93 at most (the offset is already subtracted)",
-                        (unsigned long long)i, (unsigned)h_qual[i]);
-        memset(h_result, 0, n_reads);
-        if (h_where) memset(h_where, 0, n_reads);
-        const unsigned k = c->k;
-        uint64_t nucleotides = 0;
-        for (uint64_t r = 0; r < n_reads; ++r)
-            if (h_offsets[r + 1] - h_offsets[r] >= k) nucleotides += h_offsets[r + 1] - h_offsets[r];  // hammer_tools.cpp:90-95
-        c->stats[3] += nucleotides;
-        if (c->n == 0 || nucleotides == 0) {  // no k-mer is good, or no read has k bases: every result is false
-            if (total > first) memcpy(h_out + first, h_bases + first, total - first);
-            return;
-        }
-
-        bbk_ctx *ctx = c->ctx;
-        BBK_HIP(hipSetDevice(ctx->device));
-        // ---- the generator's valid starts of every read, as stretches: blocks of reads, one per thread ----
-        const int nblk = (int)std::min<uint64_t>(64, (n_reads + 4095) / 4096);
-        std::vector<std::vector<bbkhost::hammer::Stretch>> part(nblk);
-        raw_vector<uint64_t> st_off(n_reads + 1);
-#pragma omp parallel for schedule(dynamic, 1)
-        for (int b = 0; b < nblk; ++b) {
-            const uint64_t r0 = n_reads * b / nblk, r1 = n_reads * (b + 1) / nblk;
-            for (uint64_t r = r0; r < r1; ++r) {
-                const uint64_t o = h_offsets[r], len = h_offsets[r + 1] - o;
-                st_off[r] = len >= k ? bbkhost::hammer::generator_stretches(h_bases + o, (const char *)h_qual + o, len, k, 0, part[b],
-                                                                           rch::is_nucl)
-                                     : 0;
-            }
-        }
-        raw_vector<uint32_t> stretches;
-        {
-            uint64_t sum = 0;
-            for (uint64_t r = 0; r < n_reads; ++r) {
-                const uint64_t x = st_off[r];
-                st_off[r] = sum;
-                sum += x;
-            }
-            st_off[n_reads] = sum;
-            stretches.resize(2 * sum);
-            uint64_t at = 0;
-            for (int b = 0; b < nblk; ++b)
-                for (const auto &s : part[b]) {
-                    stretches[at++] = s.start;
-                    stretches[at++] = s.length;
-                }
-        }
-        // ---- the uploads, then everything behind the table ----
-        const uint64_t bytes = total - first;
-        DevBuf d_bases, d_qual, d_off, d_st, d_stoff;
-        raw_vector<uint64_t> rel(n_reads + 1);
-        for (uint64_t r = 0; r <= n_reads; ++r) rel[r] = h_offsets[r] - first;
-        upload(ctx, d_bases, (const uint8_t *)h_bases + first, bytes);
-        upload(ctx, d_qual, h_qual + first, bytes);
-        upload(ctx, d_off, rel.data(), n_reads + 1);
-        upload(ctx, d_st, stretches.data(), (uint64_t)stretches.size());
-        upload(ctx, d_stoff, st_off.data(), n_reads + 1);
-        RcBatch b;
-        b.n_reads = n_reads;
-        b.bytes = bytes;
-        b.longest = longest;
-        b.d_bases = d_bases.as<uint8_t>();
-        b.d_qual = d_qual.as<uint8_t>();
-        b.d_off = d_off.as<uint64_t>();
-        b.d_st = d_st.as<uint32_t>();
-        b.d_stoff = d_stoff.as<uint64_t>();
-        b.h_bases = [&] { return h_bases + first; };
-        b.h_offsets = rel.data();
-        b.h_qual = [&] { return h_qual + first; };
-        RcResult R;
-        rc_run(c, b, R);
-        d2h_big(ctx, h_result, R.res.p, n_reads);
-        if (h_where) memcpy(h_where, R.where.data(), n_reads);
-        if (R.searched) d2h_big(ctx, h_out + first, R.out.p, bytes);
-        else memcpy(h_out + first, h_bases + first, bytes);
-        uint64_t changed_reads = 0, changed_nucl = 0;  // read_corrector.cpp:210-219
-#pragma omp parallel for reduction(+ : changed_reads, changed_nucl)
-        for (int64_t r = 0; r < (int64_t)n_reads; ++r) {
-            if (!R.where[r]) continue;
-            uint64_t diff = 0;
-            for (uint64_t i = h_offsets[r]; i < h_offsets[r + 1]; ++i) diff += h_out[i] != h_bases[i];
-            if (diff) {
-                ++changed_reads;
-                changed_nucl += diff;
-            }
-        }
-        c->stats[0] += changed_reads;
-        c->stats[1] += changed_nucl;
+        const char *fn = "bbk_corrector_correct";
+        const auto hr = hreads_from_host(fn, "read", c->ctx, h_bases, h_qual, h_offsets, n_reads, c->k, BBK_NO_TRIM);
+        const auto cr = rc_correct(fn, c, hr.get());
+        rc_export(c->ctx, cr.get(), h_out ? h_out + first : nullptr, nullptr, h_result, h_where, nullptr, nullptr);
     });
 }
 
 int bbk_corrector_correct_resident(bbk_corrector *c, const bbk_hreads *hr, bbk_corrected **out) {
     return guarded([&] {
         BBK_REQUIRE(c && hr && out, BBK_ERR_ARG, "bbk_corrector_correct_resident: NULL argument");
-        raw_vector<uint64_t> h_off;
-        *out = rc_resident("bbk_corrector_correct_resident", c, hr, h_off).release();
+        *out = rc_correct("bbk_corrector_correct_resident", c, hr).release();
     });
 }
 
@@ -773,10 +641,8 @@ int bbk_corrector_correct_prepared(bbk_corrector *c, const bbk_hreads *hr, char 
         rc_check("bbk_corrector_correct_prepared", c, hr);
         BBK_HIP(hipSetDevice(c->ctx->device));
         BBK_REQUIRE(hreads_trimmed(hr).total == 0 || h_out, BBK_ERR_ARG, "bbk_corrector_correct_prepared: NULL argument");
-        raw_vector<uint64_t> h_off;
-        const auto cr = rc_resident("bbk_corrector_correct_prepared", c, hr, h_off);
-        memcpy(h_out_offsets, h_off.data(), (hr->n + 1) * 8);
-        rc_export(c->ctx, cr.get(), h_out, nullptr, h_result, h_where, nullptr, nullptr);
+        const auto cr = rc_correct("bbk_corrector_correct_prepared", c, hr);
+        rc_export(c->ctx, cr.get(), h_out, h_out_offsets, h_result, h_where, nullptr, nullptr);
     });
 }
 

@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256) void k_rp_write(RpSide a, RpSide b, int paired
 void corrected_outcome(bbk_corrected *cr) {
     if (!cr->n) return;
     const bbk_hreads::Trimmed &t = hreads_trimmed(cr->hr);
-    launch_items_timed(cr->ctx, "k_rp_outcome", k_rp_outcome, cr->n * 64, cr->out.as<uint8_t>(), t.bases.as<uint8_t>(),
-                       t.off.as<uint64_t>(), cr->res.as<uint8_t>(), cr->where.as<uint8_t>(), cr->n, (uint32_t)cr->k,
+    launch_items_timed(cr->ctx, "k_rp_outcome", k_rp_outcome, cr->n * 64, cr->out.as<uint8_t>(), t.bases, t.off,
+                       cr->res.as<uint8_t>(), cr->where.as<uint8_t>(), cr->n, (uint32_t)cr->k,
                        cr->changed.as<uint32_t>(), cr->tag.as<uint8_t>());
 }
 
@@ -259,8 +259,8 @@ static RpSide rp_side(const bbk_corrected *cr, const RpNames &names) {
     const bbk_hreads::Trimmed &t = hreads_trimmed(hr);
     RpSide s;
     s.bases = cr->out.as<uint8_t>();
-    s.quals = t.quals.as<uint8_t>();
-    s.toff = t.off.as<uint64_t>();
+    s.quals = t.quals;
+    s.toff = t.off;
     s.off = hr->off.as<uint64_t>();
     s.trim = hr->trim.as<uint32_t>();
     s.res = cr->res.as<uint8_t>();

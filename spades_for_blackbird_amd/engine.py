@@ -9,6 +9,7 @@ _LIB = None
 
 BOTH_STRANDS, CANONICAL, WITH_COUNTS, UNSORTED, REFERENCE_ORDER, WITH_MASKS = 1, 2, 4, 8, 16, 32
 ORDER_SORTED, ORDER_REFERENCE_BUCKETS16 = 0, 1
+NO_TRIM = -2 ** 31  # BBK_NO_TRIM: the trim_quality of records that are trimmed already
 # bbk_path_range of include/bbk.h
 PATH_RANGE = np.dtype([("edge", np.uint64), ("read", np.uint32), ("init_start", np.uint32), ("init_end", np.uint32),
                        ("map_start", np.uint32), ("map_end", np.uint32), ("reserved", np.uint32)])
@@ -502,7 +503,8 @@ class Context:
 
     def hammer_reads(self, bases, quals, offsets, k, trim_quality=4):
         """FASTQ records as parsed -> HammerReads: bases and quals uint8 back to back (any byte values; qualities with the
-        offset already subtracted, at most 93), record i at [offsets[i], offsets[i + 1])."""
+        offset already subtracted, at most 93), record i at [offsets[i], offsets[i + 1]).  trim_quality=NO_TRIM: the records
+        are trimmed already and are taken whole."""
         b = np.ascontiguousarray(np.frombuffer(bases, dtype=np.uint8) if isinstance(bases, (bytes, bytearray)) else bases,
                                  dtype=np.uint8)
         q = np.ascontiguousarray(np.frombuffer(quals, dtype=np.uint8) if isinstance(quals, (bytes, bytearray)) else quals,

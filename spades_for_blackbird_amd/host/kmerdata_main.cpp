@@ -412,6 +412,84 @@ static void plan_input(const std::vector<std::string> &input, const std::string 
     }
 }
 
+// The solid k-mer expansion in snapshot rounds (main.cpp:194-222): the expander with the expanded good bits, stored in sc
+static bbk_expander *expand_solid(bbk_ctx *ctx, const bbk_kmerset *set, bbk_subclusters *sc, ReadSource &src,
+                                  unsigned max_iterations, unsigned long long min_changed) {
+    bbk_expander *ex = nullptr;
+    check(bbk_expander_from_subclusters(ctx, set, sc, &ex), "bbk_expander_from_subclusters");
+    info("Starting solid k-mers expansion in snapshot rounds.");
+    for (unsigned iter = 0; iter < max_iterations; ++iter) {
+        check(bbk_expander_round_begin(ex), "bbk_expander_round_begin");
+        src.each(false, [&](const Block &b) {
+            const bbk_reads *r = nullptr;
+            check(bbk_hreads_candidate_view(b.hr, &r), "bbk_hreads_candidate_view");
+            check(bbk_expander_push(ex, r, nullptr), "bbk_expander_push");
+            // push does not wait, and a block that is not resident goes now
+            if (!b.resident) check(bbk_ctx_synchronize(ctx), "bbk_ctx_synchronize");
+        });
+        uint64_t changed = 0;
+        check(bbk_expander_round_end(ex, &changed), "bbk_expander_round_end");
+        info("Solid k-mers iteration %u produced %llu new k-mers.", iter, (unsigned long long)changed);
+        if (changed < min_changed) break;
+    }
+    info("Solid k-mers finalized");
+    check(bbk_expander_store(ex, sc), "bbk_expander_store");
+    return ex;
+}
+
+// CorrectAllReads (hammer_tools.cpp:218-277): every block through w, which gets its corrector here; then the counters and,
+// with --output-dir, corrected.yaml (main.cpp:254-256)
+static void correct_reads(const bbk_kmerset *set, const bbk_expander *ex, ReadSource &src, CorrectedWriter &w) {
+    check(bbk_corrector_from_expander(w.ctx, set, ex, &w.cor), "bbk_corrector_from_expander");
+    info("Starting read correction.");
+    src.each_group(false, std::ref(w));
+    w.finish();
+    uint64_t cs[5];
+    check(bbk_corrector_stats(w.cor, cs), "bbk_corrector_stats");
+    info("Correction done. Changed %llu bases in %llu reads.", (unsigned long long)cs[1], (unsigned long long)cs[0]);
+    info("Failed to correct %llu bases out of %llu.", (unsigned long long)cs[2], (unsigned long long)cs[3]);
+    info("  Searches corrected on the host: %llu", (unsigned long long)cs[4]);
+    if (!w.out_dir.empty()) {
+        const std::string yaml = w.out_dir + "/corrected.yaml";
+        info("Saving corrected dataset description to %s", yaml.c_str());
+        if (!save_dataset_yaml(yaml, w.outlibs)) fatal("cannot write %s", yaml.c_str());
+    }
+    bbk_corrector_free(w.cor);
+}
+
+// The report of KMerClustering::process (kmer_cluster.cpp:650-658)
+static void report_subclusters(bbk_ctx *ctx, const bbk_subclusters *sc) {
+    uint64_t st[9], errs[16];
+    check(bbk_subclusters_export(ctx, sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, st), "bbk_subclusters_export");
+    const uint64_t gsingl = st[0], tsingl = st[1], tcsingl = st[2], gcsingl = st[3], tcls = st[4], gcls = st[5],
+                   tkmers = st[6], tncls = st[7], newkmers = st[8];
+    info("Subclustering done. Total %llu non-read kmers were generated.", (unsigned long long)newkmers);
+    info("Subclustering statistics:");
+    info("  Total singleton hamming clusters: %llu. Among them %llu (%g%%) are good", (unsigned long long)tsingl,
+         (unsigned long long)gsingl, 100.0 * (double)gsingl / (double)tsingl);
+    info("  Total singleton subclusters: %llu. Among them %llu (%g%%) are good", (unsigned long long)tcsingl,
+         (unsigned long long)gcsingl, 100.0 * (double)gcsingl / (double)tcsingl);
+    info("  Total non-singleton subcluster centers: %llu. Among them %llu (%g%%) are good", (unsigned long long)tcls,
+         (unsigned long long)gcls, 100.0 * (double)gcls / (double)tcls);
+    info("  Average size of non-trivial subcluster: %g kmers", 1.0 * (double)tkmers / (double)tcls);
+    info("  Average number of sub-clusters per non-singleton cluster: %g", 1.0 * (double)(tcsingl + tcls) / (double)tncls);
+    info("  Total solid k-mers: %llu", (unsigned long long)(gsingl + gcsingl + gcls));
+    std::string m;
+    for (int r = 0; r < 4; ++r) {
+        uint64_t row = 0;
+        for (int c = 0; c < 4; ++c) row += errs[4 * r + c];
+        for (int c = 0; c < 4; ++c) {
+            char b[64];
+            snprintf(b, sizeof(b), "%s%g", c ? "," : "", (double)errs[4 * r + c] / (double)row);
+            m += b;
+        }
+        m += r < 3 ? ")," : ")";
+        if (r < 3) m += "(";
+    }
+    info("  Substitution probabilities: [4,4]((%s)", m.c_str());
+    info("  K-mers subclustered on the host: %llu", (unsigned long long)bbk_subclusters_host_kmers(sc));
+}
+
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
     unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4, resident_bytes = 0;
@@ -508,79 +586,16 @@ int main(int argc, char **argv) {
     if (subcluster) {
         bbk_subclusters *sc = nullptr;
         check(bbk_hamclusters_subcluster(ctx, set, hc, ks, &sp, &sc), "bbk_hamclusters_subcluster");
-        if (expand) {  // main.cpp:194-222
-            bbk_expander *ex = nullptr;
-            check(bbk_expander_from_subclusters(ctx, set, sc, &ex), "bbk_expander_from_subclusters");
-            info("Starting solid k-mers expansion in snapshot rounds.");
-            for (unsigned iter = 0; iter < expand_max_iterations; ++iter) {
-                check(bbk_expander_round_begin(ex), "bbk_expander_round_begin");
-                src.each(false, [&](const Block &b) {
-                    const bbk_reads *r = nullptr;
-                    check(bbk_hreads_candidate_view(b.hr, &r), "bbk_hreads_candidate_view");
-                    check(bbk_expander_push(ex, r, nullptr), "bbk_expander_push");
-                    // push does not wait, and a block that is not resident goes now
-                    if (!b.resident) check(bbk_ctx_synchronize(ctx), "bbk_ctx_synchronize");
-                });
-                uint64_t changed = 0;
-                check(bbk_expander_round_end(ex, &changed), "bbk_expander_round_end");
-                info("Solid k-mers iteration %u produced %llu new k-mers.", iter, (unsigned long long)changed);
-                if (changed < expand_min_changed) break;
-            }
-            info("Solid k-mers finalized");
-            check(bbk_expander_store(ex, sc), "bbk_expander_store");
-            if (correct) {  // hammer_tools.cpp:218-277
-                bbk_corrector *cor = nullptr;
-                check(bbk_corrector_from_expander(ctx, set, ex, &cor), "bbk_corrector_from_expander");
-                info("Starting read correction.");
-                CorrectedWriter w{files, groups, prefix, out_dir, ctx, cor, (int)qvoffset, correct_stats, outlibs};
-                src.each_group(false, std::ref(w));
-                w.finish();
-                uint64_t cs[5];
-                check(bbk_corrector_stats(cor, cs), "bbk_corrector_stats");
-                info("Correction done. Changed %llu bases in %llu reads.", (unsigned long long)cs[1], (unsigned long long)cs[0]);
-                info("Failed to correct %llu bases out of %llu.", (unsigned long long)cs[2], (unsigned long long)cs[3]);
-                info("  Searches corrected on the host: %llu", (unsigned long long)cs[4]);
-                if (!out_dir.empty()) {  // main.cpp:254-256
-                    const std::string yaml = out_dir + "/corrected.yaml";
-                    info("Saving corrected dataset description to %s", yaml.c_str());
-                    if (!save_dataset_yaml(yaml, outlibs)) fatal("cannot write %s", yaml.c_str());
-                }
-                bbk_corrector_free(cor);
+        if (expand) {
+            bbk_expander *ex = expand_solid(ctx, set, sc, src, expand_max_iterations, expand_min_changed);
+            if (correct) {
+                CorrectedWriter w{files, groups, prefix, out_dir, ctx, nullptr, (int)qvoffset, correct_stats, outlibs};
+                correct_reads(set, ex, src, w);
             }
             bbk_expander_free(ex);
         }
         check(bbk_subclusters_write(ctx, sc, ks, prefix.c_str()), "bbk_subclusters_write");
-        uint64_t st[9], errs[16];
-        check(bbk_subclusters_export(ctx, sc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, errs, st),
-              "bbk_subclusters_export");
-        const uint64_t gsingl = st[0], tsingl = st[1], tcsingl = st[2], gcsingl = st[3], tcls = st[4], gcls = st[5],
-                       tkmers = st[6], tncls = st[7], newkmers = st[8];
-        // kmer_cluster.cpp:650-658
-        info("Subclustering done. Total %llu non-read kmers were generated.", (unsigned long long)newkmers);
-        info("Subclustering statistics:");
-        info("  Total singleton hamming clusters: %llu. Among them %llu (%g%%) are good", (unsigned long long)tsingl,
-             (unsigned long long)gsingl, 100.0 * (double)gsingl / (double)tsingl);
-        info("  Total singleton subclusters: %llu. Among them %llu (%g%%) are good", (unsigned long long)tcsingl,
-             (unsigned long long)gcsingl, 100.0 * (double)gcsingl / (double)tcsingl);
-        info("  Total non-singleton subcluster centers: %llu. Among them %llu (%g%%) are good", (unsigned long long)tcls,
-             (unsigned long long)gcls, 100.0 * (double)gcls / (double)tcls);
-        info("  Average size of non-trivial subcluster: %g kmers", 1.0 * (double)tkmers / (double)tcls);
-        info("  Average number of sub-clusters per non-singleton cluster: %g", 1.0 * (double)(tcsingl + tcls) / (double)tncls);
-        info("  Total solid k-mers: %llu", (unsigned long long)(gsingl + gcsingl + gcls));
-        std::string m;
-        for (int r = 0; r < 4; ++r) {
-            uint64_t row = 0;
-            for (int c = 0; c < 4; ++c) row += errs[4 * r + c];
-            for (int c = 0; c < 4; ++c) {
-                char b[64];
-                snprintf(b, sizeof(b), "%s%g", c ? "," : "", (double)errs[4 * r + c] / (double)row);
-                m += b;
-            }
-            m += r < 3 ? ")," : ")";
-            if (r < 3) m += "(";
-        }
-        info("  Substitution probabilities: [4,4]((%s)", m.c_str());
-        info("  K-mers subclustered on the host: %llu", (unsigned long long)bbk_subclusters_host_kmers(sc));
+        report_subclusters(ctx, sc);
         bbk_subclusters_free(sc);
     }
     if (hc) bbk_hamclusters_free(hc);

@@ -76,6 +76,11 @@ def literal_starts(seq, qual, k, is_nucleotide):
     return out
 
 
+def identity_trim(seq, qual, threshold=None):
+    """the trim of a record that is trimmed already (BBK_NO_TRIM): all of it"""
+    return 0, len(seq)
+
+
 # ---- closed form -----------------------------------------------------------------------------------------------------
 def closed_trim(seq, qual, threshold):
     n = len(seq)
@@ -159,4 +164,26 @@ def random_records(rng, n, k=None, max_len=None, odd=0.15):
                 for j in range(min(m, ln)):
                     q[j if side == 0 else ln - 1 - j] = int(rng.choice(quals))
         out.append((seq, q))
+    return out
+
+
+def boundary_records(rng):
+    """every event of the two rules at a chunk boundary: positions 62..65 and 126..129 in records of 63..200 bases"""
+    out = []
+    for n in (63, 64, 65, 127, 128, 129, 200):
+        seq = "".join(rng.choice(list("ACGT"), n))
+        for p in (62, 63, 64, 65, 126, 127, 128, 129):
+            if p >= n:
+                continue
+            out.append((seq, [3] * p + [30] * (n - p)))                        # the first good base
+            out.append((seq, [30] * (p + 1) + [3] * (n - p - 1)))              # the last good base (right trim)
+            out.append((seq, [3] + [30] * p + [1] * (n - p - 1)))              # ... after a left trim: the tail stays,
+            out.append((seq, [0] + [30] * p + [1] * (n - p - 1)))              #     and end_ is at the boundary
+            out.append((seq, [1] * p + [30] * (n - p)))                        # the first q >= 2 (at trim quality 0)
+            out.append((seq, [1] * p + [30] + [1] * (n - p - 1)))              # both at the same base
+            for c in "Nn.a":
+                out.append((seq[:p] + c + seq[p + 1:], [30] * n))              # an N, a lower-case base, a '.'
+                out.append((seq[:p] + c + seq[p + 1:], [0] + [30] * (n - 3) + [1] * 2))
+            out.append((seq[:p] + "N" * (n - p), [30] * n))                    # nothing but N from there on
+            out.append(("N" * p + seq[p:], [30] * n))
     return out

@@ -37,11 +37,13 @@ def tag_text(kind, changed):
 
 
 def corrected_records(rc, records, trim_quality, tags, offset):
-    """[(result, text)] of the records of one file: trimNsAndBadQuality, CorrectReadsBatch, Read::print"""
+    """[(result, text)] of the records of one file: trimNsAndBadQuality, CorrectReadsBatch, Read::print.  trim_quality
+    None: the records are trimmed already (BBK_NO_TRIM) and are taken whole."""
     out = []
     for i, (name, seq, qual) in enumerate(records):
         rc._read = i
-        s, q, ltrim, rtrim, initial = R.trim_read(seq, list(qual), trim_quality)
+        s, q, ltrim, rtrim, initial = R.trim_read(seq, list(qual), trim_quality) if trim_quality is not None else \
+            (seq, list(qual), 0, len(seq), len(seq))
         res, newseq, kind, changed = tag_of(rc, s, q)
         shown = name + (tag_text(kind, changed) if tags else "")
         out.append((bool(res), R.read_print(shown, newseq, q, ltrim, rtrim, initial, offset), kind, changed))

@@ -40,8 +40,9 @@ def tables_of(hr):
     return trims, out[0], out[1], hr.candidates().tolist()
 
 
-def check_batch(ctx, records, k, tq):
-    want = HR.prepare(records, k, tq)
+def check_batch(ctx, records, k, tq, trim=HR.literal_trim):
+    """trim: the rule the batch's trims must follow (HR.identity_trim for tq = B.NO_TRIM)"""
+    want = HR.prepare(records, k, tq, trim=trim)
     hr = ctx.hammer_reads(*arrays(records), k, trim_quality=tq)
     got = tables_of(hr)
     L = hr._L
@@ -59,44 +60,42 @@ def with_empties(records):
     return [("", [])] + records[:m] + [("", []), ("", [])] + records[m:] + [("", [])]
 
 
-@pytest.mark.parametrize("k", [5, 21, 32])
-def test_crafted_reads(ctx, k):
+def crafted(k):
     rng = np.random.default_rng(200 + k)
     recs = [(s, q) for _, s, q in KR.crafted_reads(k, rng)]
     recs += [(s.lower(), q) for s, q in recs[:8]] + [(s.replace("N", "."), q) for s, q in recs[4:8]]
     recs += [(s[:3] + s[3:9].lower() + s[9:], q) for s, q in recs[:8]]
     rb = "".join(rng.choice(list("ACGT"), k + 1))
-    recs += [(rb[:n], [30] * n) for n in (k - 1, k, k + 1)]
+    return recs + [(rb[:n], [30] * n) for n in (k - 1, k, k + 1)]
+
+
+@pytest.mark.parametrize("k", [5, 21, 32])
+def test_crafted_reads(ctx, k):
+    recs = crafted(k)
     want = check_batch(ctx, with_empties(recs), k, 4)
     assert any(len(x) > 1 for x in want[1]) and any(a != b for a, b in zip(want[1], want[2]))  # the tables do differ
     check_batch(ctx, with_empties(recs), k, 0)
 
 
-def boundary_records(rng):
-    """every event of the two rules at a chunk boundary: positions 62..65 and 126..129 in records of 63..200 bases"""
-    out = []
-    for n in (63, 64, 65, 127, 128, 129, 200):
-        seq = "".join(rng.choice(list("ACGT"), n))
-        for p in (62, 63, 64, 65, 126, 127, 128, 129):
-            if p >= n:
-                continue
-            out.append((seq, [3] * p + [30] * (n - p)))                        # the first good base
-            out.append((seq, [30] * (p + 1) + [3] * (n - p - 1)))              # the last good base (right trim)
-            out.append((seq, [3] + [30] * p + [1] * (n - p - 1)))              # ... after a left trim: the tail stays,
-            out.append((seq, [0] + [30] * p + [1] * (n - p - 1)))              #     and end_ is at the boundary
-            out.append((seq, [1] * p + [30] * (n - p)))                        # the first q >= 2 (at trim quality 0)
-            out.append((seq, [1] * p + [30] + [1] * (n - p - 1)))              # both at the same base
-            for c in "Nn.a":
-                out.append((seq[:p] + c + seq[p + 1:], [30] * n))              # an N, a lower-case base, a '.'
-                out.append((seq[:p] + c + seq[p + 1:], [0] + [30] * (n - 3) + [1] * 2))
-            out.append((seq[:p] + "N" * (n - p), [30] * n))                    # nothing but N from there on
-            out.append(("N" * p + seq[p:], [30] * n))
-    return out
+@pytest.mark.parametrize("k", [5, 21, 32])
+def test_records_taken_as_trimmed(ctx, k):
+    """trim_quality = B.NO_TRIM: every trim is (0, n) -- (0, 0) for an empty record -- and the tables and the flag are
+    those of a trimmed read of these bases.  The restatement alone says that the boundary records tell this from a trim
+    at quality 4: in the trims, in the corrector table (in record coordinates) and in the candidate flag."""
+    recs = HR.boundary_records(np.random.default_rng(9))
+    assert len(recs) == 512
+    at4, whole = HR.prepare(recs, k, 4), HR.prepare(recs, k, None, trim=HR.identity_trim)
+    assert sum(t != (0, len(s)) for t, (s, _) in zip(at4[0], recs)) >= 300
+    assert sum([(a + t[0], n) for a, n in x] != y for t, x, y in zip(at4[0], at4[2], whole[2])) >= 50
+    assert sum(a != b for a, b in zip(at4[3], whole[3])) >= 100
+    want = check_batch(ctx, with_empties(recs), k, B.NO_TRIM, trim=HR.identity_trim)
+    assert want[0][0] == (0, 0) and want[0][1] == (0, len(recs[0][0]))  # an empty record; the first boundary record
+    check_batch(ctx, with_empties(crafted(k)), k, B.NO_TRIM, trim=HR.identity_trim)
 
 
 @pytest.mark.parametrize("k,tq", [(21, 4), (21, 0), (5, 4), (5, 0), (32, 1)])
 def test_events_at_chunk_boundaries(ctx, k, tq):
-    recs = boundary_records(np.random.default_rng(9))
+    recs = HR.boundary_records(np.random.default_rng(9))
     want = check_batch(ctx, with_empties(recs), k, tq)
     assert sum(want[3]) > 20 and sum(len(x) == 2 for x in want[1]) > 20
 
@@ -186,6 +185,37 @@ def test_same_bytes_from_the_views(ctx, golden_dir):
 def test_correct_prepared(ctx, golden):
     st, wh = compare_corrections(ctx, golden)
     assert st["changed_reads"] > 1000 and st["host_searches"] == 0 and wh == [0, 1]
+    # the host-array entry is the prepared one over a batch that is taken as trimmed already
+    k, keys, good, trimmed, _ = golden
+    s = device_set(ctx, keys, k)
+    c1, c2 = s.corrector(good), s.corrector(good)
+    bases, quals, off = arrays(trimmed)
+    out1, res1, where1 = c1.correct_arrays(bases, quals, off)
+    hr = ctx.hammer_reads(bases, quals, off, k, trim_quality=B.NO_TRIM)
+    out2, off2, res2, where2 = c2.correct_prepared(hr)
+    assert np.array_equal(off, off2) and np.array_equal(out1, out2)
+    assert np.array_equal(res1, res2) and np.array_equal(where1, where2) and c1.stats == c2.stats == st
+    for x in (hr, c1, c2, s):
+        x.free()
+
+
+def test_print_of_records_taken_as_trimmed(ctx):
+    """a B.NO_TRIM batch through correct_resident and Corrected.print: no ltrim= / rtrim=, no padding, the bad ends and
+    the Ns of the records stay where they are -- the text of tests/readprint_restated.py with the identity trim"""
+    from tests import readcorrect_restated as R
+    from tests import readprint_restated as P
+    from tests.readprint_child import run_batch
+    from tests.test_gpu_readprint import shape_cases
+    k = 21
+    index, keys, good, recs = shape_cases(k)
+    rows = P.corrected_records(R.ReadCorrector(index, good, k), recs, None, True, 33)
+    want = [x.encode("latin-1") for x in P.route_single(rows)]
+    got = run_batch(ctx, k, keys, good, recs, trim_quality=B.NO_TRIM)
+    assert got["streams"] == want and all(len(w) > 0 for w in want)
+    assert b"trim=" not in want[0] + want[1] and {x[2] for x in rows} >= {P.NONE, P.OK, P.CHANGED}
+    assert got["sides"][0][4] == [x[3] for x in rows] and got["sides"][0][5] == [x[2] for x in rows]
+    at4 = P.corrected_records(R.ReadCorrector(index, good, k), recs, 4, True, 33)
+    assert sum(a[1] != b[1] for a, b in zip(rows, at4)) >= 10  # the same records do print differently when trimmed at 4
 
 
 def test_correct_prepared_by_the_host_rule(golden_dir):

@@ -15,6 +15,10 @@ def test_library_exports_the_entries():
     missing = [e for e in ENTRIES if not hasattr(L, e)]
     assert not missing, missing
     assert "HammerReads" in B.__all__ and hasattr(B.Corrector, "correct_prepared") and hasattr(B.Context, "hammer_reads")
+    assert "NO_TRIM" in B.__all__ and B.NO_TRIM == -2 ** 31  # BBK_NO_TRIM of include/bbk.h: INT_MIN
+    import os
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "bbk.h")).read()
+    assert "#define BBK_NO_TRIM (-2147483647 - 1)" in header
 
 
 def test_kernels_use_no_scratch():

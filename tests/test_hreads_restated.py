@@ -56,3 +56,15 @@ def test_candidates_are_the_expander_restatement():
     want = ER.candidate_reads(recs, 5)
     assert 10 < len(want) < len(recs)
     assert [recs[i][0][t[0]:t[0] + t[1]].upper() for i, t in enumerate(trims) if cand[i]] == want
+
+
+@pytest.mark.parametrize("k", [5, 21, 32])
+def test_identity_trim_closed_form(k):
+    """a batch that is trimmed already (BBK_NO_TRIM): the closed-form starts over whole records equal the literal ones,
+    bad ends, Ns and all"""
+    rng = np.random.default_rng(40 + k)
+    recs = [("", [])] + HR.random_records(rng, 600, k=k) + HR.boundary_records(np.random.default_rng(9))
+    got = HR.prepare(recs, k, None, trim=HR.identity_trim, starts=HR.closed_starts)
+    assert got == HR.prepare(recs, k, None, trim=HR.identity_trim)
+    assert got[0] == [(0, len(s)) for s, _ in recs]
+    assert any(got[3]) and not all(got[3]) and any(len(x) > 1 for x in got[2])
