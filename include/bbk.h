@@ -677,6 +677,54 @@ int bbk_hreads_candidate_view(const bbk_hreads *hr, const bbk_reads **reads);
 int bbk_corrector_correct_prepared(bbk_corrector *c, const bbk_hreads *hr, char *h_out, uint64_t *h_out_offsets,
                                    uint8_t *h_result, uint8_t *h_where);
 void bbk_hreads_free(bbk_hreads *hr);
+/* The records of a batch as it holds them.  Any pointer may be NULL.  h_bases / h_quals: bbk_hreads_bases bytes each (the
+ * qualities with the offset subtracted); h_offsets: n + 1 entries from 0; h_names: bbk_hreads_name_bytes bytes, name i at
+ * [h_name_off[i], h_name_off[i + 1]) (n + 1 entries from 0).  A batch made from host arrays holds no names: 0 bytes, every
+ * offset 0. */
+uint64_t bbk_hreads_bases(const bbk_hreads *hr);
+uint64_t bbk_hreads_name_bytes(const bbk_hreads *hr);
+int bbk_hreads_export_records(bbk_ctx *ctx, const bbk_hreads *hr, char *h_bases, uint8_t *h_quals, uint64_t *h_offsets,
+                              char *h_names, uint64_t *h_name_off);
+
+/* ---- FASTQ text parsed on the device: replaces FastaFastqGzParser over kseq (common/io/reads/
+ *      fasta_fastq_gz_parser.hpp:64-80,113-136; ext/include/kseq/kseq.h:170-212) for input in the four-line form, and says
+ *      where the input stops being in that form so that the serial reader can take over there -- text blocks go in (plain
+ *      bytes, after any gunzip), prepared batches with their names come out, resident in HBM ------------ */
+typedef struct bbk_fastq_input bbk_fastq_input; /* one chunk of FASTQ text on the device, with its index */
+#define BBK_FASTQ_FORM 1    /* verdict kind: the record is not in the strict four-line form */
+#define BBK_FASTQ_QUALITY 2 /* verdict kind: a quality byte outside [qvoffset, qvoffset + 93] */
+/* Uploads h_text[0 .. n_bytes) and indexes it.  Lines end at '\n'; with final == 0 only terminated lines count (the
+ * caller carries the rest into its next chunk), with final != 0 a non-empty unterminated tail is the last line.  Record r
+ * is lines 4r .. 4r + 3, and there are lines / 4 records.  A record is in the strict form -- exactly then kseq
+ * (kseq.h:170-212) reads the four lines as name, sequence and quality -- when line 4r begins with '@', line 4r + 1 is empty or
+ * begins with none of '@', '+', '>', line 4r + 2 begins with '+', and the sequence and the quality line are equally long
+ * after one trailing '\r' has been dropped from a field of more than one byte (ks_getuntil2; the name, the header line
+ * without its first byte, loses it the same way).  The verdict is the smallest record index that is not in the strict
+ * form (kind BBK_FASTQ_FORM) or, being in it, holds a quality byte outside [qvoffset, qvoffset + 93] (BBK_FASTQ_QUALITY);
+ * with final != 0 leftover lines (lines % 4 != 0) make the record after the last one a BBK_FASTQ_FORM verdict.
+ * BBK_ERR_ARG: a NULL argument, qvoffset outside 0..162, a chunk of 2^40 bytes or more. */
+int bbk_fastq_input_from_host(bbk_ctx *ctx, const char *h_text, uint64_t n_bytes, int final, int qvoffset,
+                              bbk_fastq_input **out);
+uint64_t bbk_fastq_input_records(const bbk_fastq_input *in); /* complete records: lines / 4 */
+/* Returns 1 and fills *record, *kind and *byte (the first offending quality character of a BBK_FASTQ_QUALITY verdict,
+ * otherwise -1) when there is a verdict, 0 when every record is usable; any pointer may be NULL. */
+int bbk_fastq_input_verdict(const bbk_fastq_input *in, uint64_t *record, int *kind, int *byte);
+/* The byte just past record n - 1 (0 for n == 0; n_bytes for a last record without its line feed): where the caller's next
+ * chunk starts, or where the serial reader resumes, between records.  ~0 for n above the record count. */
+uint64_t bbk_fastq_input_text_end(const bbk_fastq_input *in, uint64_t n);
+/* The block rule of a reader that closes a block with the record at which its bases reach max_bases: the number of
+ * records from `first` up to and including that one, or all the usable records behind `first` when they do not get there.
+ * Usable records are those before the verdict. */
+uint64_t bbk_fastq_input_records_within(const bbk_fastq_input *in, uint64_t first, uint64_t max_bases);
+void bbk_fastq_input_free(bbk_fastq_input *in);
+/* bbk_hreads_from_host for the records [first, first + n) of the index, gathered on the device: the bases with a..z
+ * upper-cased (kseq.h:193-194), the qualities with qvoffset subtracted, and the names, which the batch keeps
+ * (bbk_hreads_export_records, bbk_corrected_print_resident).  Every position comes from a scan, so the bytes are the same on
+ * every run.  The batch does not borrow the index.
+ * BBK_ERR_ARG: k outside 1..32, a range that reaches the verdict or the end of the records, a record of 2^31 bases or a
+ * name of 2^30 bytes or more. */
+int bbk_hreads_from_fastq_input(const bbk_fastq_input *in, uint64_t first, uint64_t n, unsigned k, int trim_quality,
+                                bbk_hreads **out);
 
 /* ---- corrected reads as FASTQ text: replaces the last step of CorrectAllReads (projects/hammer/hammer_tools.cpp:107-193:
  *      CorrectReadFile, CorrectPairedReadFiles), the BH: tags of ReadCorrector::CorrectOneRead
@@ -713,6 +761,10 @@ void bbk_corrected_free(bbk_corrected *cr);
 int bbk_corrected_print(const bbk_corrected *left, const bbk_corrected *right, const char *h_names_l,
                         const uint64_t *h_name_off_l, const char *h_names_r, const uint64_t *h_name_off_r, int qvoffset,
                         int tags, bbk_fastq_text **out);
+/* bbk_corrected_print with the names taken from the batches' own blobs (batches made by bbk_hreads_from_fastq_input): nothing
+ * is uploaded.  BBK_ERR_ARG also for a batch that holds no names. */
+int bbk_corrected_print_resident(const bbk_corrected *left, const bbk_corrected *right, int qvoffset, int tags,
+                                 bbk_fastq_text **out);
 int bbk_fastq_text_streams(const bbk_fastq_text *t); /* 2 or 5 */
 uint64_t bbk_fastq_text_size(const bbk_fastq_text *t, int stream); /* bytes; 0 for a stream the text does not have */
 /* stream `stream` into h_dst (bbk_fastq_text_size bytes) / into the file `path` through the context's staged copy: the

@@ -1,5 +1,5 @@
-// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip, readcorrect.hip, hreads.hip and readprint.hip (the
-// BayesHammer stage) share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
+// hammer.h -- what hamclust.hip, kmerstat.hip, subclust.hip, expand.hip, readcorrect.hip, hreads.hip, readprint.hip and
+// fastqparse.hip (the BayesHammer stage) share.  Host code only: no device arithmetic, so subclust.hip's `fp contract(off)` scope reaches no other translation unit
 // through it.
 #pragma once
 
@@ -78,6 +78,10 @@ struct bbk_hreads {
     bbk::DevBuf koff, kst;     // n + 1 u64; n_kst x (start, length) u32: the k-mer table, starts in the record as parsed
     bbk::DevBuf coff, cst;     // n + 1 u64; n_cst x (start, length) u32: the corrector table, starts in the trimmed read
     bbk::DevBuf cpos;          // n + 1 u64: candidates before record i
+    // a batch gathered from FASTQ text (fastqparse.hip) also keeps the names; a batch made from host arrays has none
+    bool has_names = false;
+    uint64_t name_bytes = 0;
+    bbk::DevBuf names, name_off;  // name_bytes u8 back to back; n + 1 u64
     // made on first request, freed with the batch (mutable: a cache behind a const handle, one host thread per context)
     struct View {
         bool made = false;
@@ -115,8 +119,28 @@ struct bbk_fastq_text {
     bbk::DevBuf text;
 };
 
+// fastqparse.hip: one chunk of FASTQ text on the device with its index.  Line i is
+// text[ls[i], ls[i + 1] - 1): ls[i + 1] is one past the line feed, or n_bytes + 1 behind an unterminated last line.
+struct bbk_fastq_input {
+    bbk_ctx *ctx = nullptr;
+    uint64_t n_bytes = 0, lines = 0, records = 0;
+    int qvoffset = 0;
+    uint64_t usable = 0;             // records before the verdict (all of them without one)
+    uint64_t verdict = ~0ull;        // record << 2 | kind, ~0: none
+    int verdict_byte = -1;           // the first offending quality character of a quality verdict
+    uint64_t oversize = ~0ull;       // the first record of 2^31 bases or with a name of 2^30 bytes or more
+    bbk::DevBuf text;                // n_bytes u8
+    bbk::DevBuf ls;                  // lines + 1 u64
+    bbk::DevBuf seq0, qual0, name0;  // records u64: the first byte of the three fields in text
+    bbk::DevBuf boff, noff;          // records + 1 u64: bases / name bytes before record i
+    bbk::raw_vector<uint64_t> h_boff;  // boff on the host: the block rule and the limits read it
+};
+
 namespace bbk {
 
+// hreads.hip: the prepare tail of a batch whose bases, quals and off are on the device (queued on the context's stream is
+// enough): trims, flags and both stretch tables; waits for the stream.  `fn` / `unit` as below
+void hreads_prepare(const char *fn, const char *unit, bbk_hreads *hr);
 // hreads.hip: fills hr->trimmed on first use (two launches, one scan, one wait; nothing for a BBK_NO_TRIM batch)
 const bbk_hreads::Trimmed &hreads_trimmed(const bbk_hreads *hr);
 // hreads.hip: bbk_hreads_from_host behind its NULL checks, for the entry `fn`, which calls a record a `unit` in its refusals

@@ -366,6 +366,51 @@ const bbk_hreads::Trimmed &hreads_trimmed(const bbk_hreads *hr) {
     return t;
 }
 
+// The prepare tail both doors share: the count pass, one scan (the one wait: what was queued before it is done with it as
+// well), the write pass
+void hreads_prepare(const char *fn, const char *unit, bbk_hreads *H) {
+    bbk_ctx *ctx = H->ctx;
+    const uint64_t n = H->n, bytes = H->bytes;
+    const unsigned k = H->k;
+    const int trim_quality = H->trim_quality;
+    H->trim.alloc(n * 8);
+    H->cand.alloc(n);
+    H->koff.alloc((n + 1) * 8);
+    H->coff.alloc((n + 1) * 8);
+    H->cpos.alloc((n + 1) * 8);
+    if (n == 0) {
+        BBK_HIP(hipMemsetAsync(H->koff.p, 0, 8, ctx->stream));
+        BBK_HIP(hipMemsetAsync(H->coff.p, 0, 8, ctx->stream));
+        BBK_HIP(hipMemsetAsync(H->cpos.p, 0, 8, ctx->stream));
+        H->kst.alloc(0);
+        H->cst.alloc(0);
+        BBK_HIP(hipStreamSynchronize(ctx->stream));
+        return;
+    }
+    DevBuf packed((n + 1) * 8);
+    launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<false>, n * 64, H->bases.as<uint8_t>(), H->quals.as<uint8_t>(),
+                       H->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, H->trim.as<uint32_t>(), H->cand.as<uint8_t>(),
+                       packed.as<uint64_t>(), H->coff.as<uint64_t>(), (uint64_t *)nullptr, (uint64_t *)nullptr,
+                       (uint32_t *)nullptr, (uint32_t *)nullptr);
+    uint64_t totals[2] = {0, 0};  // the one wait: the uploads are done with it as well
+    exclusive_scan2_u64(ctx, packed.as<uint64_t>(), packed.as<uint64_t>(), H->coff.as<uint64_t>(), H->coff.as<uint64_t>(), n,
+                        totals);
+    H->n_kst = totals[0] & kHrCountMask;
+    H->n_cand = totals[0] >> kHrCandShift;
+    H->n_cst = totals[1];
+    BBK_REQUIRE(H->n_kst <= bytes && H->n_cst <= bytes && H->n_cand <= n, BBK_ERR_INTERNAL,
+                "%s: %llu + %llu stretches, %llu candidates for %llu bases in %llu %ss", fn,
+                (unsigned long long)H->n_kst, (unsigned long long)H->n_cst, (unsigned long long)H->n_cand,
+                (unsigned long long)bytes, (unsigned long long)n, unit);
+    H->kst.alloc(H->n_kst * 8);
+    H->cst.alloc(H->n_cst * 8);
+    launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<true>, n * 64, H->bases.as<uint8_t>(), H->quals.as<uint8_t>(),
+                       H->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, (uint32_t *)nullptr, (uint8_t *)nullptr,
+                       packed.as<uint64_t>(), H->coff.as<uint64_t>(), H->koff.as<uint64_t>(), H->cpos.as<uint64_t>(),
+                       H->kst.as<uint32_t>(), H->cst.as<uint32_t>());
+    BBK_HIP(hipStreamSynchronize(ctx->stream));  // `packed` goes now
+}
+
 // The offsets, then the qualities, are checked here for every entry that takes records from the host; a record is a `unit`
 // in what `fn` refuses
 std::unique_ptr<bbk_hreads> hreads_from_host(const char *fn, const char *unit, bbk_ctx *ctx, const char *h_bases,
@@ -407,42 +452,7 @@ std::unique_ptr<bbk_hreads> hreads_from_host(const char *fn, const char *unit, b
     upload(ctx, hr->bases, (const uint8_t *)h_bases + first, bytes);
     upload(ctx, hr->quals, h_qual + first, bytes);
     upload(ctx, hr->off, rel.data(), n + 1);
-    hr->trim.alloc(n * 8);
-    hr->cand.alloc(n);
-    hr->koff.alloc((n + 1) * 8);
-    hr->coff.alloc((n + 1) * 8);
-    hr->cpos.alloc((n + 1) * 8);
-    if (n == 0) {
-        BBK_HIP(hipMemsetAsync(hr->koff.p, 0, 8, ctx->stream));
-        BBK_HIP(hipMemsetAsync(hr->coff.p, 0, 8, ctx->stream));
-        BBK_HIP(hipMemsetAsync(hr->cpos.p, 0, 8, ctx->stream));
-        hr->kst.alloc(0);
-        hr->cst.alloc(0);
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
-        return hr;
-    }
-    DevBuf packed((n + 1) * 8);
-    launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<false>, n * 64, hr->bases.as<uint8_t>(), hr->quals.as<uint8_t>(),
-                       hr->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, hr->trim.as<uint32_t>(), hr->cand.as<uint8_t>(),
-                       packed.as<uint64_t>(), hr->coff.as<uint64_t>(), (uint64_t *)nullptr, (uint64_t *)nullptr,
-                       (uint32_t *)nullptr, (uint32_t *)nullptr);
-    uint64_t totals[2] = {0, 0};  // the one wait: the uploads are done with it as well
-    exclusive_scan2_u64(ctx, packed.as<uint64_t>(), packed.as<uint64_t>(), hr->coff.as<uint64_t>(), hr->coff.as<uint64_t>(), n,
-                        totals);
-    hr->n_kst = totals[0] & kHrCountMask;
-    hr->n_cand = totals[0] >> kHrCandShift;
-    hr->n_cst = totals[1];
-    BBK_REQUIRE(hr->n_kst <= bytes && hr->n_cst <= bytes && hr->n_cand <= n, BBK_ERR_INTERNAL,
-                "%s: %llu + %llu stretches, %llu candidates for %llu bases in %llu %ss", fn,
-                (unsigned long long)hr->n_kst, (unsigned long long)hr->n_cst, (unsigned long long)hr->n_cand,
-                (unsigned long long)bytes, (unsigned long long)n, unit);
-    hr->kst.alloc(hr->n_kst * 8);
-    hr->cst.alloc(hr->n_cst * 8);
-    launch_items_timed(ctx, "k_hr_prepare", k_hr_prepare<true>, n * 64, hr->bases.as<uint8_t>(), hr->quals.as<uint8_t>(),
-                       hr->off.as<uint64_t>(), n, (uint32_t)k, trim_quality, (uint32_t *)nullptr, (uint8_t *)nullptr,
-                       packed.as<uint64_t>(), hr->coff.as<uint64_t>(), hr->koff.as<uint64_t>(), hr->cpos.as<uint64_t>(),
-                       hr->kst.as<uint32_t>(), hr->cst.as<uint32_t>());
-    BBK_HIP(hipStreamSynchronize(ctx->stream));  // `packed` goes now
+    hreads_prepare(fn, unit, hr.get());
     return hr;
 }
 
@@ -476,6 +486,25 @@ int bbk_hreads_export(bbk_ctx *ctx, const bbk_hreads *hr, uint32_t *h_trim, uint
         if (h_kst && hr->n_kst) d2h_big(ctx, h_kst, hr->kst.p, hr->n_kst * 8);
         if (h_coff) d2h_big(ctx, h_coff, hr->coff.p, (hr->n + 1) * 8);
         if (h_cst && hr->n_cst) d2h_big(ctx, h_cst, hr->cst.p, hr->n_cst * 8);
+    });
+}
+
+uint64_t bbk_hreads_bases(const bbk_hreads *hr) { return hr ? hr->bytes : 0; }
+uint64_t bbk_hreads_name_bytes(const bbk_hreads *hr) { return hr ? hr->name_bytes : 0; }
+
+int bbk_hreads_export_records(bbk_ctx *ctx, const bbk_hreads *hr, char *h_bases, uint8_t *h_quals, uint64_t *h_offsets,
+                              char *h_names, uint64_t *h_name_off) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && hr, BBK_ERR_ARG, "bbk_hreads_export_records: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        if (h_bases && hr->bytes) d2h_big(ctx, h_bases, hr->bases.p, hr->bytes);
+        if (h_quals && hr->bytes) d2h_big(ctx, h_quals, hr->quals.p, hr->bytes);
+        if (h_offsets) d2h_big(ctx, h_offsets, hr->off.p, (hr->n + 1) * 8);
+        if (h_names && hr->name_bytes) d2h_big(ctx, h_names, hr->names.p, hr->name_bytes);
+        if (h_name_off) {
+            if (hr->has_names) d2h_big(ctx, h_name_off, hr->name_off.p, (hr->n + 1) * 8);
+            else memset(h_name_off, 0, (hr->n + 1) * 8);  // a batch made from host arrays: every name is empty
+        }
     });
 }
 

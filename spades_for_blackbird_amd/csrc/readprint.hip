@@ -254,7 +254,7 @@ static void rp_upload_names(bbk_ctx *ctx, const char *what, const char *h_names,
     upload(ctx, d.off, rel.data(), n + 1);
 }
 
-static RpSide rp_side(const bbk_corrected *cr, const RpNames &names) {
+static RpSide rp_side(const bbk_corrected *cr, const uint8_t *names, const uint64_t *name_off) {
     const bbk_hreads *hr = cr->hr;
     const bbk_hreads::Trimmed &t = hreads_trimmed(hr);
     RpSide s;
@@ -266,9 +266,55 @@ static RpSide rp_side(const bbk_corrected *cr, const RpNames &names) {
     s.res = cr->res.as<uint8_t>();
     s.tag = cr->tag.as<uint8_t>();
     s.changed = cr->changed.as<uint32_t>();
-    s.names = names.blob.as<uint8_t>();
-    s.name_off = names.off.as<uint64_t>();
+    s.names = names;
+    s.name_off = name_off;
     return s;
+}
+
+// What both print entries check before they look at their names
+static void rp_check(const char *fn, const bbk_corrected *left, const bbk_corrected *right, int qvoffset) {
+    BBK_REQUIRE(qvoffset >= 0 && qvoffset <= kRpMaxQvOffset, BBK_ERR_ARG,
+                "%s: qvoffset %d is outside [0, %d]: a quality of 93 plus the offset must fit a byte", fn, qvoffset, kRpMaxQvOffset);
+    if (right) {
+        BBK_REQUIRE(right->ctx == left->ctx, BBK_ERR_ARG, "%s: the two batches belong to different contexts", fn);
+        BBK_REQUIRE(right->n == left->n, BBK_ERR_ARG, "%s: %llu left and %llu right reads: a pair is one of each", fn,
+                    (unsigned long long)left->n, (unsigned long long)right->n);
+    }
+}
+
+// The text of one or two corrected batches whose names (blob, n + 1 offsets per side) are on the device; waits for the stream
+static bbk_fastq_text *rp_text(const char *fn, const bbk_corrected *left, const bbk_corrected *right, const uint8_t *names_l,
+                               const uint64_t *name_off_l, const uint8_t *names_r, const uint64_t *name_off_r, int qvoffset,
+                               int tags) {
+    bbk_ctx *ctx = left->ctx;
+    const uint64_t n = left->n, n_items = right ? 2 * n : n;
+    const int streams = right ? 5 : 2;
+    auto t = std::make_unique<bbk_fastq_text>();
+    t->ctx = ctx;
+    t->streams = streams;
+    if (n_items == 0) {
+        t->text.alloc(0);
+        BBK_HIP(hipStreamSynchronize(ctx->stream));  // the (empty) uploads
+        return t.release();
+    }
+    const RpSide a = rp_side(left, names_l, name_off_l), b = right ? rp_side(right, names_r, name_off_r) : a;
+    const uint64_t cells = (uint64_t)streams * n_items;
+    DevBuf stream(n_items), pos((cells + 1) * 8);
+    BBK_HIP(hipMemsetAsync(pos.p, 0, cells * 8, ctx->stream));
+    launch_items_timed(ctx, "k_rp_size", k_rp_size, n_items, a, b, right ? 1 : 0, tags ? 1 : 0, n_items, stream.as<uint8_t>(),
+                       pos.as<uint64_t>());
+    const uint64_t total = exclusive_scan_u64(ctx, pos.as<uint64_t>(), pos.as<uint64_t>(), cells);  // waits: uploaded names are in
+    for (int s = 1; s < streams; ++s)
+        BBK_HIP(hipMemcpyAsync(&t->start[s], pos.as<uint64_t>() + (uint64_t)s * n_items, 8, hipMemcpyDeviceToHost, ctx->stream));
+    t->start[streams] = total;
+    t->text.alloc(total + 16);
+    launch_items_timed(ctx, "k_rp_write", k_rp_write, n_items * 64, a, b, right ? 1 : 0, tags ? 1 : 0, (uint32_t)qvoffset, n_items,
+                       stream.as<uint8_t>(), pos.as<uint64_t>(), t->text.as<uint8_t>());
+    BBK_HIP(hipStreamSynchronize(ctx->stream));  // the stream starts are in; the names and the table go now
+    for (int s = 0; s < streams; ++s)
+        BBK_REQUIRE(t->start[s] <= t->start[s + 1], BBK_ERR_INTERNAL, "%s: stream %d starts at %llu, the next at %llu", fn, s,
+                    (unsigned long long)t->start[s], (unsigned long long)t->start[s + 1]);
+    return t.release();
 }
 
 }  // namespace bbk
@@ -282,49 +328,31 @@ int bbk_corrected_print(const bbk_corrected *left, const bbk_corrected *right, c
                         int tags, bbk_fastq_text **out) {
     return guarded([&] {
         BBK_REQUIRE(left && out && h_name_off_l && (!right || h_name_off_r), BBK_ERR_ARG, "bbk_corrected_print: NULL argument");
-        BBK_REQUIRE(qvoffset >= 0 && qvoffset <= kRpMaxQvOffset, BBK_ERR_ARG,
-                    "bbk_corrected_print: qvoffset %d is outside [0, %d]: a quality of 93 plus the offset must fit a byte", qvoffset,
-                    kRpMaxQvOffset);
-        if (right) {
-            BBK_REQUIRE(right->ctx == left->ctx, BBK_ERR_ARG, "bbk_corrected_print: the two batches belong to different contexts");
-            BBK_REQUIRE(right->n == left->n, BBK_ERR_ARG, "bbk_corrected_print: %llu left and %llu right reads: a pair is one of each",
-                        (unsigned long long)left->n, (unsigned long long)right->n);
-        }
+        rp_check("bbk_corrected_print", left, right, qvoffset);
         bbk_ctx *ctx = left->ctx;
         BBK_HIP(hipSetDevice(ctx->device));
-        const uint64_t n = left->n, n_items = right ? 2 * n : n;
-        const int streams = right ? 5 : 2;
+        const uint64_t n = left->n;
         RpNames nl, nr;
-        raw_vector<uint64_t> rel_l, rel_r;
+        raw_vector<uint64_t> rel_l, rel_r;  // rp_text waits before they go
         rp_upload_names(ctx, "left", h_names_l, h_name_off_l, n, nl, rel_l);
         if (right) rp_upload_names(ctx, "right", h_names_r, h_name_off_r, n, nr, rel_r);
-        auto t = std::make_unique<bbk_fastq_text>();
-        t->ctx = ctx;
-        t->streams = streams;
-        if (n_items == 0) {
-            t->text.alloc(0);
-            BBK_HIP(hipStreamSynchronize(ctx->stream));  // the (empty) uploads
-            *out = t.release();
-            return;
-        }
-        const RpSide a = rp_side(left, nl), b = right ? rp_side(right, nr) : a;
-        const uint64_t cells = (uint64_t)streams * n_items;
-        DevBuf stream(n_items), pos((cells + 1) * 8);
-        BBK_HIP(hipMemsetAsync(pos.p, 0, cells * 8, ctx->stream));
-        launch_items_timed(ctx, "k_rp_size", k_rp_size, n_items, a, b, right ? 1 : 0, tags ? 1 : 0, n_items, stream.as<uint8_t>(),
-                           pos.as<uint64_t>());
-        const uint64_t total = exclusive_scan_u64(ctx, pos.as<uint64_t>(), pos.as<uint64_t>(), cells);  // waits: rel_l / rel_r may go
-        for (int s = 1; s < streams; ++s)
-            BBK_HIP(hipMemcpyAsync(&t->start[s], pos.as<uint64_t>() + (uint64_t)s * n_items, 8, hipMemcpyDeviceToHost, ctx->stream));
-        t->start[streams] = total;
-        t->text.alloc(total + 16);
-        launch_items_timed(ctx, "k_rp_write", k_rp_write, n_items * 64, a, b, right ? 1 : 0, tags ? 1 : 0, (uint32_t)qvoffset, n_items,
-                           stream.as<uint8_t>(), pos.as<uint64_t>(), t->text.as<uint8_t>());
-        BBK_HIP(hipStreamSynchronize(ctx->stream));  // the stream starts are in; the names and the table go now
-        for (int s = 0; s < streams; ++s)
-            BBK_REQUIRE(t->start[s] <= t->start[s + 1], BBK_ERR_INTERNAL, "bbk_corrected_print: stream %d starts at %llu, the next at %llu", s,
-                        (unsigned long long)t->start[s], (unsigned long long)t->start[s + 1]);
-        *out = t.release();
+        *out = rp_text("bbk_corrected_print", left, right, nl.blob.as<uint8_t>(), nl.off.as<uint64_t>(), nr.blob.as<uint8_t>(),
+                       nr.off.as<uint64_t>(), qvoffset, tags);
+    });
+}
+
+int bbk_corrected_print_resident(const bbk_corrected *left, const bbk_corrected *right, int qvoffset, int tags,
+                                 bbk_fastq_text **out) {
+    return guarded([&] {
+        BBK_REQUIRE(left && out, BBK_ERR_ARG, "bbk_corrected_print_resident: NULL argument");
+        rp_check("bbk_corrected_print_resident", left, right, qvoffset);
+        BBK_REQUIRE(left->hr->has_names && (!right || right->hr->has_names), BBK_ERR_ARG,
+                    "bbk_corrected_print_resident: the batch was made from host arrays and holds no names: "
+                    "bbk_corrected_print takes them from the host");
+        BBK_HIP(hipSetDevice(left->ctx->device));
+        *out = rp_text("bbk_corrected_print_resident", left, right, left->hr->names.as<uint8_t>(), left->hr->name_off.as<uint64_t>(),
+                       right ? right->hr->names.as<uint8_t>() : nullptr, right ? right->hr->name_off.as<uint64_t>() : nullptr,
+                       qvoffset, tags);
     });
 }
 

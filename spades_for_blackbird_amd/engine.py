@@ -55,6 +55,9 @@ SYMBOLS = [
     "bbk_hreads_export", "bbk_hreads_stretch_view", "bbk_hreads_candidate_view", "bbk_corrector_correct_prepared", "bbk_hreads_free",
     "bbk_corrector_correct_resident", "bbk_corrected_size", "bbk_corrected_export", "bbk_corrected_free", "bbk_corrected_print",
     "bbk_fastq_text_streams", "bbk_fastq_text_size", "bbk_fastq_text_export", "bbk_fastq_text_write", "bbk_fastq_text_free",
+    "bbk_hreads_bases", "bbk_hreads_name_bytes", "bbk_hreads_export_records", "bbk_corrected_print_resident",
+    "bbk_fastq_input_from_host", "bbk_fastq_input_records", "bbk_fastq_input_verdict", "bbk_fastq_input_text_end",
+    "bbk_fastq_input_records_within", "bbk_fastq_input_free", "bbk_hreads_from_fastq_input",
     "bbk_group_create", "bbk_group_size", "bbk_group_device", "bbk_group_destroy", "bbk_group_abort", "bbk_group_exchange_kmers",
     "bbk_group_exchange_extindex", "bbk_group_gather_extindex", "bbk_group_gather_kmers", "bbk_ctx_memory_stats", "bbk_ctx_device_info", "bbk_kmerset_bucket_offsets",
 ]
@@ -312,6 +315,22 @@ def load_library():
     L.bbk_fastq_text_write.argtypes = [vp, vp, C.c_int, C.c_char_p, C.c_int]
     L.bbk_fastq_text_free.argtypes = [vp]
     L.bbk_fastq_text_free.restype = None
+    for f in ("bases", "name_bytes"):
+        getattr(L, "bbk_hreads_" + f).restype = u64
+        getattr(L, "bbk_hreads_" + f).argtypes = [vp]
+    L.bbk_hreads_export_records.argtypes = [vp] * 7
+    L.bbk_corrected_print_resident.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
+    L.bbk_fastq_input_from_host.argtypes = [vp, vp, u64, C.c_int, C.c_int, C.POINTER(vp)]
+    L.bbk_fastq_input_records.restype = u64
+    L.bbk_fastq_input_records.argtypes = [vp]
+    L.bbk_fastq_input_verdict.argtypes = [vp, C.POINTER(u64), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.bbk_fastq_input_text_end.restype = u64
+    L.bbk_fastq_input_text_end.argtypes = [vp, u64]
+    L.bbk_fastq_input_records_within.restype = u64
+    L.bbk_fastq_input_records_within.argtypes = [vp, u64, u64]
+    L.bbk_fastq_input_free.argtypes = [vp]
+    L.bbk_fastq_input_free.restype = None
+    L.bbk_hreads_from_fastq_input.argtypes = [vp, u64, u64, C.c_uint, C.c_int, C.POINTER(vp)]
     L.bbk_group_create.argtypes = [C.POINTER(C.c_int), C.c_int, C.c_uint, C.POINTER(vp)]
     L.bbk_group_size.argtypes = [vp]
     L.bbk_group_device.argtypes = [vp, C.c_int]
@@ -519,6 +538,15 @@ class Context:
         r = HammerReads(self, h)
         r.k, r.bases = k, len(b)
         return r
+
+    def fastq_input(self, text, final=True, qvoffset=33):
+        """One chunk of FASTQ text (bytes, after any gunzip) -> FastqInput: the text on the device with the index of its
+        records.  final=False: the text goes on in a later chunk, and only terminated lines count."""
+        t = np.ascontiguousarray(np.frombuffer(text, dtype=np.uint8) if isinstance(text, (bytes, bytearray, memoryview))
+                                 else text, dtype=np.uint8)
+        h = C.c_void_p()
+        _check(self._L.bbk_fastq_input_from_host(self._h, _ptr(t), len(t), 1 if final else 0, int(qvoffset), C.byref(h)))
+        return FastqInput(self, h)
 
     def extindex(self, reads, k):
         """DeBruijnExtensionIndexBuilder::BuildExtensionIndexFromStream analogue."""
@@ -808,6 +836,18 @@ class HammerReads(_Handle):
         _check(self._L.bbk_hreads_export(self.ctx._h, self._h, None, None, *a))
         return off, st
 
+    def records(self):
+        """(bases np.uint8, quals np.uint8, offsets np.uint64[n + 1], names np.uint8, name offsets np.uint64[n + 1]): the
+        records as the batch holds them, qualities with the offset subtracted; a batch made from host arrays has no names"""
+        n = len(self)
+        b = np.zeros(int(self._L.bbk_hreads_bases(self._h)), dtype=np.uint8)
+        q = np.zeros(len(b), dtype=np.uint8)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        names = np.zeros(int(self._L.bbk_hreads_name_bytes(self._h)), dtype=np.uint8)
+        noff = np.zeros(n + 1, dtype=np.uint64)
+        _check(self._L.bbk_hreads_export_records(self.ctx._h, self._h, _ptr(b), _ptr(q), _ptr(off), _ptr(names), _ptr(noff)))
+        return b, q, off, names, noff
+
     def stretch_view(self):
         """(Reads, Quals) the batch owns: one engine read per k-mer stretch, for Counter.push and KmerStats.push"""
         r, q = C.c_void_p(), C.c_void_p()
@@ -819,6 +859,47 @@ class HammerReads(_Handle):
         r = C.c_void_p()
         _check(self._L.bbk_hreads_candidate_view(self._h, C.byref(r)))
         return Reads.borrowed(self.ctx, r, self)
+
+
+class FastqInput(_Handle):
+    """One chunk of FASTQ text on the device with the index of its records (bbk_fastq_input_*): record r is lines
+    4r .. 4r + 3, judged against the strict four-line form; the verdict is the first record the device does not take."""
+    _free = "bbk_fastq_input_free"
+    FORM, QUALITY = 1, 2  # BBK_FASTQ_FORM, BBK_FASTQ_QUALITY
+
+    @property
+    def records(self):
+        """complete records of the chunk: lines // 4"""
+        return int(self._L.bbk_fastq_input_records(self._h))
+
+    def verdict(self):
+        """None, or (record, kind, byte): the first record that is not in the strict form (FORM) or holds a quality
+        character outside [qvoffset, qvoffset + 93] (QUALITY: byte is that character, otherwise -1)"""
+        r, k, b = C.c_uint64(), C.c_int(), C.c_int()
+        if not self._L.bbk_fastq_input_verdict(self._h, C.byref(r), C.byref(k), C.byref(b)):
+            return None
+        return int(r.value), int(k.value), int(b.value)
+
+    def text_end(self, n):
+        """the byte just past record n - 1: where the next chunk starts, or where a serial reader resumes"""
+        e = int(self._L.bbk_fastq_input_text_end(self._h, n))
+        if e == 2 ** 64 - 1:
+            raise ValueError("text_end(%d): the chunk has %d records" % (n, self.records))
+        return e
+
+    def records_within(self, first, max_bases):
+        """records from `first` up to and including the one at which their bases reach max_bases (all the records
+        before the verdict when they do not)"""
+        return int(self._L.bbk_fastq_input_records_within(self._h, first, max_bases))
+
+    def hammer_reads(self, first, n, k, trim_quality=4):
+        """records [first, first + n), which lie before the verdict, gathered and prepared on the device -> HammerReads
+        with names"""
+        h = C.c_void_p()
+        _check(self._L.bbk_hreads_from_fastq_input(self._h, first, n, k, trim_quality, C.byref(h)))
+        r = HammerReads(self.ctx, h)
+        r.k, r.bases = k, int(self._L.bbk_hreads_bases(h))
+        return r
 
 
 class KmerStats(_Handle):
@@ -1134,6 +1215,14 @@ class Corrected(_Handle):
         _check(self._L.bbk_corrected_print(self._h, mate._h if mate is not None else None, _ptr(bl), _ptr(ol),
                                            _ptr(br) if mate is not None else None, _ptr(orr) if mate is not None else None,
                                            int(qvoffset), 1 if tags else 0, C.byref(h)))
+        return FastqText(self.ctx, h)
+
+
+    def print_resident(self, mate=None, qvoffset=33, tags=False):
+        """print with the names the batches hold themselves (HammerReads made by FastqInput.hammer_reads)"""
+        h = C.c_void_p()
+        _check(self._L.bbk_corrected_print_resident(self._h, mate._h if mate is not None else None, int(qvoffset),
+                                                    1 if tags else 0, C.byref(h)))
         return FastqText(self.ctx, h)
 
 

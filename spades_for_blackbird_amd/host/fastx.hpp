@@ -65,6 +65,16 @@ class FastxReader {
         return true;
     }
 
+    // Continues at byte `offset` of the (uncompressed) stream, which must lie between records: right behind the last line
+    // of one.  false when the file cannot be positioned there.
+    bool seek(uint64_t offset) {
+        if (gzseek(fp_, (z_off_t)offset, SEEK_SET) < 0) return false;
+        pos_ = len_ = 0;
+        eof_in_ = eof_ = hit_nl_ = false;
+        last_char_ = 0;
+        return true;
+    }
+
   private:
     int getc_() {
         if (pos_ >= len_) {

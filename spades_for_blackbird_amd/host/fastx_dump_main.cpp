@@ -1,19 +1,25 @@
-// bbk-fastx-dump [--fast <threads> <block_bytes> | --serial-lv] <file>...: test helper for the host-side
+// bbk-fastx-dump [--fast <threads> <block_bytes> | --serial-lv | --records | --time-records] <file>...: test helper for the host-side
 // FASTA/FASTQ(.gz) readers (no GPU needed).
 //   default      every parsed read sequence of the serial reader (fastx.hpp) on its own line
 //   --serial-lv  the same reads after the LongestValid rule (longest run of ACGTacgt, upper-cased)
 //   --fast       the parallel block parser (ingest.hpp): its packed reads decoded back to ACGT -- must print
 //                exactly what --serial-lv prints, for any thread count and block size
+//   --records    every record of the serial reader's next_record as three fields -- name, upper-cased sequence, quality
+//                ("" for FASTA) -- each written as <decimal length> <bytes>\n, so that any byte may stand in a field
+//   --time-records  the serial parse loop of spades-kmerdata alone (next_record, then the record appended to a block with
+//                33 subtracted from every quality), timed: prints "<records> <bases> <seconds>" per file
+//                (tools/fastqparse_perf.py)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <chrono>
 
 #include "fastx.hpp"
 #include "ingest.hpp"
 
 int main(int argc, char **argv) {
     int first = 1;
-    bool fast = false, lv = false;
+    bool fast = false, lv = false, records = false, timed = false;
     int threads = 1;
     size_t block = 1u << 20;
     if (argc > 1 && !strcmp(argv[1], "--fast")) {
@@ -24,6 +30,10 @@ int main(int argc, char **argv) {
         first = 4;
     } else if (argc > 1 && !strcmp(argv[1], "--serial-lv")) {
         lv = true;
+        first = 2;
+    } else if (argc > 1 && (!strcmp(argv[1], "--records") || !strcmp(argv[1], "--time-records"))) {
+        records = true;
+        timed = argv[1][2] == 't';
         first = 2;
     }
     if (fast) {
@@ -57,6 +67,32 @@ int main(int argc, char **argv) {
         if (!rd.is_open()) {
             fprintf(stderr, "cannot open %s\n", argv[i]);
             return 2;
+        }
+        if (timed) {
+            std::string name, seq, qual, bases, quals, names;
+            std::vector<uint64_t> offsets{0}, name_off{0};
+            const auto t0 = std::chrono::steady_clock::now();
+            while (rd.next_record(name, seq, qual)) {
+                for (char &c : qual) c = (char)((unsigned char)c - 33);
+                bases += seq;
+                quals += qual;
+                offsets.push_back(bases.size());
+                names += name;
+                name_off.push_back(names.size());
+            }
+            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            printf("%zu %zu %.6f\n", offsets.size() - 1, bases.size(), dt);
+            continue;
+        }
+        if (records) {
+            std::string name, seq, qual;
+            while (rd.next_record(name, seq, qual))
+                for (const std::string *f : {&name, &seq, &qual}) {
+                    printf("%zu ", f->size());
+                    fwrite(f->data(), 1, f->size(), stdout);
+                    fputc('\n', stdout);
+                }
+            continue;
         }
         bbkhost::ReadBatch b;
         while (rd.read(b, 1000, ~0ull) > 0) {

@@ -6,7 +6,7 @@
 //   (+ --device <int>, --qvoffset <int=33>, --trim-quality <int=4>, --cluster, --subcluster with --singleton-threshold,
 //      --nonsingleton-threshold, --correct-threshold, --no-correct-threshold, --expand with --expand-max-iterations <int=25>,
 //      --expand-min-changed <int=10>, --correct with --correct-stats, --paired and --output-dir <dir>,
-//      --resident-bytes <bytes=0>)
+//      --resident-bytes <bytes=0>, --device-parse with --parse-chunk <bytes=67108864>)
 // The records of every file go to the device as parsed, in blocks of -b bases, and are prepared there (bbk_hreads: the trim
 // of input_trim_quality 4 of configs/hammer/config.info, then ValidKMerGenerator's valid starts as stretches); a stretch is
 // one read of the engine.  Every pass takes a view of the prepared blocks:
@@ -44,6 +44,16 @@
 //   <largest common prefix>_unpaired.fastq), and <dir>/corrected.yaml, the corrected libraries (main.cpp:254-256).
 // The records are parsed by one thread (fastx.hpp's next_record, which keeps the quality line); -t is accepted for the
 // common interface.
+//   --device-parse: the text of every file (gzread: plain files pass through, decompression stays on the host) goes to the
+//   device in chunks of --parse-chunk bytes and is parsed there (bbk_fastq_input_*): the blocks hold the
+//   same records (bbk_fastq_input_records_within is the rule above; of a pair, the side that closes its block first), the
+//   text behind the last block of a chunk is carried into the next one, and a block keeps nothing on the host -- the
+//   corrected reads are printed with the names the batch holds (bbk_corrected_print_resident).  Where the index has a
+//   verdict -- a record that is not four lines, or a quality character outside the offset's range -- the group goes on
+//   with fastx.hpp's reader from the first record of the block that did not get complete (of a pair: both files), so
+//   multi-line records, blank lines, FASTA records, truncated files and every refusal are exactly those of the serial
+//   reader; the place is remembered, and the later passes go there without indexing that text again.  Every output file
+//   is the same bytes with and without the option.
 #include <sys/stat.h>
 
 #include <cerrno>
@@ -87,7 +97,10 @@ static void usage(const char *argv0) {
            "        --output-dir <value>    Write the corrected reads under the names BayesHammer gives them in this\n"
            "                                directory, and corrected.yaml, the dataset description of the corrected reads\n"
            "        --resident-bytes <value>  Keep the first blocks on the GPU for the later passes while their bases and\n"
-           "                                qualities total at most this many bytes (default 0: every pass parses the input)\n\n"
+           "                                qualities total at most this many bytes (default 0: every pass parses the input)\n"
+           "        --device-parse          Parse the FASTQ text on the GPU; input that is not in the four-line form goes\n"
+           "                                through the serial reader from the first such record on (same output files)\n"
+           "        --parse-chunk <value>   Bytes of text per chunk of --device-parse (default 67108864)\n\n"
            "DESCRIPTION\n        K-mers of FASTQ reads and their reverse complements with BayesHammer's per-k-mer statistics (MI355X)\n\n"
            "        Output: <prefix>.kmers - the k-mers in ascending order, in the final_kmers record format;\n"
            "        <prefix>.kmstat - per k-mer: 32-bit count << 1, float total_qual, the 6-bit quality sums packed into 64-bit words;\n"
@@ -125,10 +138,67 @@ struct Block {
     std::vector<uint64_t> name_off{0};
     bbk_hreads *hr = nullptr;
     bool resident = false;
+    bool device = false;  // parsed on the device (--device-parse): the batch holds the records and their names, the host nothing
     std::unique_ptr<Block> mate;
-    uint64_t size() const { return offsets.size() - 1; }
-    uint64_t total() const { return offsets.back(); }
+    uint64_t size() const { return device ? bbk_hreads_size(hr) : offsets.size() - 1; }
+    uint64_t total() const { return device ? bbk_hreads_bases(hr) : offsets.back(); }
     ~Block() { bbk_hreads_free(hr); }
+};
+
+// The text of one file on its way to the device (--device-parse): a reused buffer that holds the text behind the last
+// record taken, and the index of that text.
+struct TextFeed {
+    std::string path;
+    gzFile fp = nullptr;
+    std::vector<char> buf;
+    size_t have = 0, want = 0;  // bytes in buf; bytes a chunk is read up to
+    uint64_t file_off = 0;      // where buf[0] is in the (uncompressed) file
+    bool eof = false;
+    bbk_fastq_input *in = nullptr;
+    uint64_t next = 0, usable = 0;  // the first record of the index not taken yet; its records before the verdict
+    bool verdict = false;
+
+    TextFeed() = default;
+    TextFeed(const TextFeed &) = delete;
+    TextFeed &operator=(const TextFeed &) = delete;
+    ~TextFeed() {
+        bbk_fastq_input_free(in);
+        if (fp) gzclose(fp);
+    }
+    void open(const std::string &p, size_t chunk) {
+        path = p;
+        fp = gzopen(p.c_str(), "r");
+        if (!fp) fatal("cannot open %s", p.c_str());
+        gzbuffer(fp, 1 << 20);
+        want = chunk;
+    }
+    uint64_t avail() const { return usable - next; }
+    bool can_extend() const { return !eof && !verdict; }  // more text would give more usable records
+    uint64_t offset_of_next() const { return file_off + bbk_fastq_input_text_end(in, next); }
+    // Drops the text of the records taken, reads on (a chunk that did not hold a block grows) and indexes what is there
+    void advance(bbk_ctx *ctx, int qvoffset) {
+        if (in) {
+            const size_t consumed = (size_t)bbk_fastq_input_text_end(in, next);
+            memmove(buf.data(), buf.data() + consumed, have - consumed);
+            have -= consumed;
+            file_off += consumed;
+            bbk_fastq_input_free(in);
+            in = nullptr;
+            if (have >= want / 2) want *= 2;
+        }
+        if (buf.size() < want) buf.resize(want);
+        while (have < want && !eof) {
+            const int n = gzread(fp, buf.data() + have, (unsigned)std::min<size_t>(want - have, 1u << 30));
+            if (n < 0) fatal("cannot read %s", path.c_str());
+            if (n == 0) eof = true;
+            have += (size_t)n;
+        }
+        check(bbk_fastq_input_from_host(ctx, buf.data(), have, eof ? 1 : 0, qvoffset, &in), "bbk_fastq_input_from_host");
+        uint64_t record = 0;
+        verdict = bbk_fastq_input_verdict(in, &record, nullptr, nullptr) != 0;
+        usable = verdict ? record : bbk_fastq_input_records(in);
+        next = 0;
+    }
 };
 
 // The records of all groups as prepared blocks, in group order, once per pass.  A block holds the records of one file up
@@ -139,10 +209,10 @@ struct Block {
 class ReadSource {
 public:
     ReadSource(bbk_ctx *ctx, const std::vector<InFile> &files, const std::vector<Group> &groups, unsigned k, int qvoffset,
-               int trim_quality, size_t block_bytes, uint64_t resident_bytes)
+               int trim_quality, size_t block_bytes, uint64_t resident_bytes, bool device_parse, size_t parse_chunk)
         : ctx_(ctx), files_(files), groups_(groups), k_(k), qvoffset_(qvoffset), trim_quality_(trim_quality),
           block_bytes_(block_bytes), budget_(resident_bytes), keeping_(resident_bytes != 0), kept_in_group_(groups.size(), 0),
-          whole_group_(groups.size(), false) {}
+          whole_group_(groups.size(), false), device_parse_(device_parse), parse_chunk_(parse_chunk), resume_(groups.size()) {}
 
     // fn(block) for the block of every group's first file (its mate, if any, hangs on it); returns the number of records
     template <class F>
@@ -200,8 +270,54 @@ private:
               "bbk_hreads_from_host");
     }
 
+    // Where the serial reader takes a group over from the device parser
+    struct Resume {
+        bool known = false;
+        uint64_t off[2] = {0, 0}, in_file = 0, block_no = 0;
+    };
+
+    std::unique_ptr<Block> fresh(bool paired) const {
+        std::unique_ptr<Block> b(new Block);
+        if (paired) b->mate.reset(new Block);
+        return b;
+    }
+    // Block number block_no of group g is complete: handed to fn unless it is resident and has been handed out already,
+    // then kept while the budget lasts
+    template <class F>
+    void hand_out(size_t g, std::unique_ptr<Block> &b, uint64_t &block_no, uint64_t &records, F &fn) {
+        const bool paired = groups_[g].f1 >= 0;
+        if (block_no++ < kept_in_group_[g]) return;  // the blocks before are resident and have been handed out
+        const size_t f0 = groups_[g].f0, f1 = paired ? (size_t)groups_[g].f1 : f0;
+        if (!b->device) {
+            prepare(*b, g, f0);
+            if (paired) prepare(*b->mate, g, f1);
+        }
+        fn(*b);
+        const uint64_t held = 2 * (b->total() + (paired ? b->mate->total() : 0));
+        records += b->size() + (paired ? b->mate->size() : 0);
+        if (keeping_ && held_ + held <= budget_) {
+            held_ += held;
+            b->resident = true;
+            std::string().swap(b->bases);
+            if (paired) {
+                b->mate->resident = true;
+                std::string().swap(b->mate->bases);
+            }
+            ++kept_in_group_[g];
+            resident_.push_back(std::move(b));
+        } else {
+            keeping_ = false;  // the resident blocks are a prefix of all blocks
+        }
+    }
+
     template <class F>
     uint64_t parse(size_t g, F &fn) {
+        return device_parse_ ? parse_device(g, fn) : parse_host(g, fn, Resume());
+    }
+
+    // The serial reader over the group, from the start or from where the device parser left it
+    template <class F>
+    uint64_t parse_host(size_t g, F &fn, const Resume &from) {
         const size_t f0 = groups_[g].f0;
         const bool paired = groups_[g].f1 >= 0;
         const size_t f1 = paired ? (size_t)groups_[g].f1 : f0;
@@ -212,37 +328,11 @@ private:
             rr.reset(new FastxReader(files_[f1].path));
             if (!rr->is_open()) fatal("cannot open %s", files_[f1].path.c_str());
         }
-        auto fresh = [&] {
-            std::unique_ptr<Block> b(new Block);
-            if (paired) b->mate.reset(new Block);
-            return b;
-        };
-        std::unique_ptr<Block> b = fresh();
+        if (from.known && (!rl.seek(from.off[0]) || (paired && !rr->seek(from.off[1]))))
+            fatal("cannot position %s at the record the serial reader takes over from", files_[f0].path.c_str());
+        std::unique_ptr<Block> b = fresh(paired);
         std::string name, seq, qual, name2, seq2, qual2;
-        uint64_t records = 0, in_file = 0, block_no = 0;
-        auto flush = [&] {
-            if (block_no++ >= kept_in_group_[g]) {  // the blocks before are resident and have been handed out
-                prepare(*b, g, f0);
-                if (paired) prepare(*b->mate, g, f1);
-                fn(*b);
-                const uint64_t held = 2 * (b->total() + (paired ? b->mate->total() : 0));
-                records += b->size() + (paired ? b->mate->size() : 0);
-                if (keeping_ && held_ + held <= budget_) {
-                    held_ += held;
-                    b->resident = true;
-                    std::string().swap(b->bases);
-                    if (paired) {
-                        b->mate->resident = true;
-                        std::string().swap(b->mate->bases);
-                    }
-                    ++kept_in_group_[g];
-                    resident_.push_back(std::move(b));
-                } else {
-                    keeping_ = false;  // the resident blocks are a prefix of all blocks
-                }
-            }
-            b = fresh();
-        };
+        uint64_t records = 0, in_file = from.in_file, block_no = from.block_no;
         for (;;) {
             const bool more = rl.next_record(name, seq, qual);
             if (paired && rr->next_record(name2, seq2, qual2) != more)  // hammer_tools.cpp:190-191
@@ -251,9 +341,87 @@ private:
             take(*b, f0, in_file, name, seq, qual);
             if (paired) take(*b->mate, f1, in_file, name2, seq2, qual2);
             ++in_file;
-            if (b->bases.size() >= block_bytes_ || (paired && b->mate->bases.size() >= block_bytes_)) flush();
+            if (b->bases.size() >= block_bytes_ || (paired && b->mate->bases.size() >= block_bytes_)) {
+                hand_out(g, b, block_no, records, fn);
+                b = fresh(paired);
+            }
         }
-        if (b->size()) flush();
+        if (b->size()) hand_out(g, b, block_no, records, fn);
+        if (keeping_) whole_group_[g] = true;
+        return records;
+    }
+
+    // The same blocks cut from text that is indexed on the device.  A block is complete when a side has a record at which
+    // its bases reach -b BEFORE its last usable record (the block rule stops there: more text cannot change it); a side
+    // whose usable records run out first reads on, and where it cannot -- a verdict, or the end of the file -- the
+    // serial reader takes over at the block's first record, or the group ends.
+    template <class F>
+    uint64_t parse_device(size_t g, F &fn) {
+        const bool paired = groups_[g].f1 >= 0;
+        const int ns = paired ? 2 : 1;
+        const size_t f[2] = {groups_[g].f0, paired ? (size_t)groups_[g].f1 : groups_[g].f0};
+        Resume &rs = resume_[g];
+        TextFeed fd[2];
+        uint64_t records = 0, in_file = 0, block_no = 0;
+        for (int s = 0; s < ns; ++s) fd[s].open(files_[f[s]].path, parse_chunk_);
+        auto unequal = [&] {
+            fatal("Pair of read files %s and %s contain unequal amount of reads", files_[f[0]].path.c_str(), files_[f[1]].path.c_str());
+        };
+        for (;;) {
+            if (rs.known && block_no == rs.block_no) return records + parse_host(g, fn, rs);
+            for (int s = 0; s < ns; ++s)
+                if (!fd[s].in) fd[s].advance(ctx_, qvoffset_);
+            uint64_t c = ~0ull;  // the records of the block, when a side closes it
+            for (int s = 0; s < ns; ++s) {
+                const uint64_t cs = bbk_fastq_input_records_within(fd[s].in, fd[s].next, block_bytes_);
+                if (cs < fd[s].avail()) c = std::min(c, cs);
+            }
+            bool last = false, again = false, give_up = false;
+            if (c != ~0ull) {
+                for (int s = 0; s < ns; ++s) {
+                    if (fd[s].avail() >= c) continue;
+                    if (fd[s].can_extend()) again = true, fd[s].advance(ctx_, qvoffset_);
+                    else if (fd[s].verdict) give_up = true;
+                    else unequal();  // the file ends inside a block the other file completes
+                }
+            } else {
+                for (int s = 0; s < ns; ++s) give_up = give_up || fd[s].verdict;
+                for (int s = 0; s < ns && !give_up; ++s)
+                    if (fd[s].can_extend()) again = true, fd[s].advance(ctx_, qvoffset_);
+                if (!give_up && !again) {  // every file is at its end: what is left is the last block
+                    if (paired && fd[0].avail() != fd[1].avail()) unequal();
+                    c = fd[0].avail();
+                    last = true;
+                }
+            }
+            if (give_up) {
+                rs.known = true;
+                for (int s = 0; s < ns; ++s) rs.off[s] = fd[s].offset_of_next();
+                rs.in_file = in_file;
+                rs.block_no = block_no;
+                info("%s: not in the four-line form behind record %llu: the serial reader goes on from there",
+                     files_[f[0]].path.c_str(), (unsigned long long)in_file);
+                continue;
+            }
+            if (again) continue;
+            if (c) {
+                std::unique_ptr<Block> b = fresh(paired);
+                if (block_no >= kept_in_group_[g]) {
+                    Block *side[2] = {b.get(), b->mate.get()};
+                    for (int s = 0; s < ns; ++s) {
+                        side[s]->device = true;
+                        side[s]->group = g;
+                        side[s]->file = f[s];
+                        check(bbk_hreads_from_fastq_input(fd[s].in, fd[s].next, c, k_, trim_quality_, &side[s]->hr),
+                              "bbk_hreads_from_fastq_input");
+                    }
+                }
+                hand_out(g, b, block_no, records, fn);
+                for (int s = 0; s < ns; ++s) fd[s].next += c;
+                in_file += c;
+            }
+            if (last) break;
+        }
         if (keeping_) whole_group_[g] = true;
         return records;
     }
@@ -269,6 +437,9 @@ private:
     std::vector<std::unique_ptr<Block>> resident_;
     std::vector<uint64_t> kept_in_group_;  // resident blocks of every group: its first ones
     std::vector<bool> whole_group_;        // every block of the group is resident
+    bool device_parse_;
+    size_t parse_chunk_;
+    std::vector<Resume> resume_;  // per group: found in the first pass that gets there, used by every later one
 };
 
 // fs::basename (common/utils/filesystem/path_helper.cpp:104-113): no directory, no last extension
@@ -353,9 +524,12 @@ struct CorrectedWriter {
         if (m) check(bbk_corrector_correct_resident(cor, m->hr, &right), "bbk_corrector_correct_resident");
         info("Processed batch %u", buffer_no);
         bbk_fastq_text *text = nullptr;
-        check(bbk_corrected_print(left, right, b.names.data(), b.name_off.data(), m ? m->names.data() : nullptr,
-                                  m ? m->name_off.data() : nullptr, qvoffset, tags ? 1 : 0, &text),
-              "bbk_corrected_print");
+        if (b.device)  // the names are the batch's own
+            check(bbk_corrected_print_resident(left, right, qvoffset, tags ? 1 : 0, &text), "bbk_corrected_print_resident");
+        else
+            check(bbk_corrected_print(left, right, b.names.data(), b.name_off.data(), m ? m->names.data() : nullptr,
+                                      m ? m->name_off.data() : nullptr, qvoffset, tags ? 1 : 0, &text),
+                  "bbk_corrected_print");
         for (int s = 0; s < bbk_fastq_text_streams(text); ++s)
             if (bbk_fastq_text_size(text, s)) check(bbk_fastq_text_write(ctx, text, s, path[s].c_str(), 1), "bbk_fastq_text_write");
         bbk_fastq_text_free(text);
@@ -492,12 +666,13 @@ static void report_subclusters(bbk_ctx *ctx, const bbk_subclusters *sc) {
 
 int main(int argc, char **argv) {
     unsigned K = 21, device = 0;
-    unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4, resident_bytes = 0;
+    unsigned long long threads = 0, bufsize = 536870912ull, qvoffset = 33, trim_quality = 4, resident_bytes = 0, parse_chunk = 67108864ull;
     std::string prefix, dataset, out_dir;
     std::vector<std::string> input;
     unsigned expand_max_iterations = 25;  // configs/hammer/config.info
     unsigned long long expand_min_changed = 10;  // main.cpp:219
-    bool help = false, cluster = false, subcluster = false, expand = false, correct = false, correct_stats = false, paired = false;
+    bool help = false, cluster = false, subcluster = false, expand = false, correct = false, correct_stats = false, paired = false,
+         device_parse = false;
     bbk_subcluster_params sp = {0.995, 0.9, 0.98, 1};  // configs/hammer/config.info
     Options opt;
     opt.num("-k", "--kmer", &K).num("-t", "--threads", &threads).num("-b", "--bufsize", &bufsize).num("", "--device", &device)
@@ -505,7 +680,8 @@ int main(int argc, char **argv) {
         .flag("", "--subcluster", [&] { cluster = subcluster = true; })
         .flag("", "--expand", [&] { cluster = subcluster = expand = true; })
         .flag("", "--correct", [&] { cluster = subcluster = expand = correct = true; })
-        .flag("", "--correct-stats", &correct_stats).flag("", "--paired", &paired).str("", "--output-dir", &out_dir)
+        .flag("", "--correct-stats", &correct_stats).flag("", "--paired", &paired).flag("", "--device-parse", &device_parse)
+        .num("", "--parse-chunk", &parse_chunk, 1ull).str("", "--output-dir", &out_dir)
         .num("", "--expand-max-iterations", &expand_max_iterations, 1u).num("", "--expand-min-changed", &expand_min_changed)
         .flag("", "--no-correct-threshold", [&] { sp.correct_use_threshold = 0; })
         .real("", "--singleton-threshold", &sp.singleton_threshold)
@@ -541,7 +717,8 @@ int main(int argc, char **argv) {
     check(bbk_count_begin(ctx, K, BBK_BOTH_STRANDS, &counter), "bbk_count_begin");
     uint64_t stretches = 0;
     double t0 = now_s();
-    ReadSource src(ctx, files, groups, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, resident_bytes);
+    ReadSource src(ctx, files, groups, K, (int)qvoffset, (int)trim_quality, (size_t)bufsize, resident_bytes, device_parse,
+                   (size_t)parse_chunk);
     const uint64_t records = src.each(true, [&](const Block &b) {
         const bbk_reads *r = nullptr;
         check(bbk_hreads_stretch_view(b.hr, &r, nullptr), "bbk_hreads_stretch_view");
