@@ -151,6 +151,17 @@ int bbk_count_push_reads(bbk_counter *c, const bbk_reads *reads);
 /* ASCII batch (same arguments and LongestValid rule as bbk_reads_from_ascii) */
 int bbk_count_push_ascii(bbk_counter *c, const char *h_bases, const uint64_t *h_offsets, uint64_t n_reads);
 int bbk_count_finish(bbk_counter *c, bbk_kmerset **out);
+/* bbk_count_finish with a minimum multiplicity: the exact form of BayesHammer's count_filter_singletons
+ * (KMerDataCounter::BuildKMerIndex, projects/hammer/kmer_data.cpp:280-335, which keeps the k-mers a counting quotient
+ * filter has seen more than once; that filter may over-count and let a singleton through, this one may not).  The
+ * counter must have been begun with BBK_WITH_COUNTS (BBK_ERR_ARG otherwise).  The result is record for record what
+ * bbk_count_finish of the same counter would give, minus every record whose exported multiplicity is < min_count: order
+ * and counts of the others are unchanged, min_count <= 1 is the identity, and *n_dropped receives the number of records
+ * of the unfiltered result that are absent.  The rule is on the EXPORTED multiplicity: in a BBK_BOTH_STRANDS set at even
+ * k a k-mer equal to its own reverse complement counts twice per occurrence, so a single occurrence of it survives
+ * min_count = 2.  The filter runs on the distinct canonical records before they are expanded and ordered: the unfiltered
+ * set never exists.  Releases the counter, also on failure. */
+int bbk_count_finish_min_count(bbk_counter *c, uint32_t min_count, bbk_kmerset **out, uint64_t *n_dropped);
 void bbk_count_abort(bbk_counter *c);
 uint64_t bbk_count_pushed_instances(const bbk_counter *c); /* k-mer positions seen so far */
 /* Device pointer to the records of the set (size * words u64) in the order it is stored in; valid until

@@ -56,4 +56,11 @@ struct Accum {
 // is built from them afterwards).  carry_payload: the multiplicities travel with the keys.
 bbk_kmerset *finish_both_strands(Accum &acc, unsigned flags, bool consume, bool carry_payload);
 
+// kmerfilter.hip: the distinct records (keys, u32 multiplicities in vals; n of them, any order) whose multiplicity is at
+// least min_count, in their order, back into keys / vals; returns how many stay.  self_rc_doubles: a k-mer equal to its
+// own reverse complement counts twice its payload (what a both-strand set reports for it at even k);
+// *dropped_self_rc receives the dropped records of that kind (0 without self_rc_doubles).  Waits for the stream.
+uint64_t filter_min_count(bbk_ctx *ctx, unsigned k, bool self_rc_doubles, uint32_t min_count, DevBuf &keys, DevBuf &vals,
+                          uint64_t n, uint64_t *dropped_self_rc);
+
 }  // namespace bbk

@@ -546,6 +546,23 @@ static bbk_kmerset *finish_count(Accum &acc, unsigned flags) {
     return s.release();
 }
 
+// finish of a count that keeps only the records whose exported multiplicity reaches min_count (the exact form of
+// KMerDataCounter::BuildKMerIndex with count_filter_singletons, projects/hammer/kmer_data.cpp:280-335).  The filter runs on
+// the accumulated canonical records, before the expansion and the ordering: a canonical record's count is the
+// multiplicity both of its strands will report, and the full both-strand set never exists.  With BBK_WITH_COUNTS the
+// accumulator carries payloads, so no bucket view is live here (view_wanted) and the records are dense after merge().
+static bbk_kmerset *finish_count_min(Accum &acc, unsigned flags, uint32_t min_count, uint64_t *n_dropped) {
+    *n_dropped = 0;
+    if (min_count <= 1) return finish_count(acc, flags);
+    acc.merge();
+    const bool both = (flags & BBK_BOTH_STRANDS) != 0;
+    const uint64_t before = acc.n;
+    uint64_t self_rc = 0;  // dropped records that are their own reverse complement: one record of the expanded set each
+    acc.n = filter_min_count(acc.ctx, acc.k, both && !(acc.k & 1), min_count, acc.keys, acc.vals, acc.n, &self_rc);
+    *n_dropped = both ? 2 * (before - acc.n) - self_rc : before - acc.n;
+    return finish_count(acc, flags);
+}
+
 static void check_count_flags(unsigned flags) {
     const bool both = (flags & BBK_BOTH_STRANDS) != 0, canon = (flags & BBK_CANONICAL) != 0;
     BBK_REQUIRE(both != canon, BBK_ERR_ARG, "bbk_count: pass exactly one of BBK_BOTH_STRANDS / BBK_CANONICAL");
@@ -604,6 +621,18 @@ int bbk_count_finish(bbk_counter *c, bbk_kmerset **out) {
         *out = finish_count(c->acc, c->flags);
     });
     delete c;  // finished or failed: the counter is gone either way
+    return rc;
+}
+
+int bbk_count_finish_min_count(bbk_counter *c, uint32_t min_count, bbk_kmerset **out, uint64_t *n_dropped) {
+    const int rc = guarded([&] {
+        BBK_REQUIRE(c && out && n_dropped, BBK_ERR_ARG, "bbk_count_finish_min_count: NULL argument");
+        BBK_REQUIRE(c->flags & BBK_WITH_COUNTS, BBK_ERR_ARG,
+                    "bbk_count_finish_min_count: the counter was begun without BBK_WITH_COUNTS");
+        BBK_HIP(hipSetDevice(c->acc.ctx->device));
+        *out = finish_count_min(c->acc, c->flags, min_count, n_dropped);
+    });
+    delete c;
     return rc;
 }
 

@@ -21,7 +21,7 @@ SYMBOLS = [
     "bbk_reads_from_ascii", "bbk_reads_from_packed", "bbk_host_alloc", "bbk_host_free", "bbk_reads_from_device", "bbk_reads_synth", "bbk_reads_synth_meta", "bbk_reads_from_spades_binary",
     "bbk_reads_write_spades_binary", "bbk_reads_count", "bbk_reads_bases",
     "bbk_reads_get_ascii", "bbk_reads_export_ascii", "bbk_reads_free",
-    "bbk_count", "bbk_count_begin", "bbk_count_push_reads", "bbk_count_push_ascii", "bbk_count_finish", "bbk_count_abort",
+    "bbk_count", "bbk_count_begin", "bbk_count_push_reads", "bbk_count_push_ascii", "bbk_count_finish", "bbk_count_finish_min_count", "bbk_count_abort",
     "bbk_count_pushed_instances", "bbk_extindex_from_device", "bbk_extindex_export_u32", "bbk_extindex_begin", "bbk_extindex_push_reads", "bbk_extindex_finish",
     "bbk_extindex_abort", "bbk_extindex_finish_with_set", "bbk_count_extindex", "bbk_kmerset_from_device", "bbk_kmerset_from_device_ex", "bbk_kmerset_both_strands", "bbk_kmerset_both_strands_ex", "bbk_words", "bbk_kmerset_size", "bbk_kmerset_k", "bbk_kmerset_keys", "bbk_reads_median_filter",
     "bbk_kmerset_instances", "bbk_kmerset_export", "bbk_kmerset_export_by_owner", "bbk_kmerset_free",
@@ -139,6 +139,7 @@ def load_library():
     L.bbk_count_push_reads.argtypes = [vp, vp]
     L.bbk_count_push_ascii.argtypes = [vp, C.c_char_p, vp, u64]
     L.bbk_count_finish.argtypes = [vp, C.POINTER(vp)]
+    L.bbk_count_finish_min_count.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u64)]
     L.bbk_count_abort.argtypes = [vp]
     L.bbk_count_pushed_instances.restype = u64
     L.bbk_count_pushed_instances.argtypes = [vp]
@@ -1267,11 +1268,19 @@ class Counter:
     def instances(self):
         return int(self._L.bbk_count_pushed_instances(self._h))
 
-    def finish(self):
+    def finish(self, min_count=None):
+        """the KMerSet; with min_count only the records whose multiplicity reaches it (bbk_count_finish_min_count: the
+        counter needs WITH_COUNTS), and the set's n_dropped tells how many records of the unfiltered set are absent"""
         h = C.c_void_p()
         c, self._h = self._h, None
-        _check(self._L.bbk_count_finish(c, C.byref(h)))
-        return KMerSet(self.ctx, h)
+        if min_count is None:
+            _check(self._L.bbk_count_finish(c, C.byref(h)))
+            return KMerSet(self.ctx, h)
+        dropped = C.c_uint64(0)
+        _check(self._L.bbk_count_finish_min_count(c, int(min_count), C.byref(h), C.byref(dropped)))
+        s = KMerSet(self.ctx, h)
+        s.n_dropped = int(dropped.value)
+        return s
 
     def abort(self):
         if getattr(self, "_h", None):

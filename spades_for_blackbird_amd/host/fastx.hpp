@@ -172,4 +172,20 @@ class FastxReader {
     int last_char_ = 0;
 };
 
+// determine_offset (common/io/reads/ireadstream.hpp:154-170): the PHRED offset of a FASTQ file from its first 10 000
+// records in stream order -- the first quality byte below ';' says 33, the first above 'K' says 64 (the bytes are
+// compared as the signed chars they are there) -- or -1 when neither occurs; -2: the file cannot be opened
+inline int determine_offset(const std::string &path) {
+    FastxReader rd(path);
+    if (!rd.is_open()) return -2;
+    std::string name, seq, qual;
+    for (size_t count = 0; count < 10000 && rd.next_record(name, seq, qual); ++count)
+        for (const char c : qual) {
+            const int q = (signed char)c;
+            if (q < ';') return 33;
+            if (q > 'K') return 64;
+        }
+    return -1;
+}
+
 }  // namespace bbkhost

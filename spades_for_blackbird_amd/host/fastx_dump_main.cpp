@@ -1,4 +1,4 @@
-// bbk-fastx-dump [--fast <threads> <block_bytes> | --serial-lv | --records | --time-records] <file>...: test helper for the host-side
+// bbk-fastx-dump [--fast <threads> <block_bytes> | --serial-lv | --records | --time-records | --offset] <file>...: test helper for the host-side
 // FASTA/FASTQ(.gz) readers (no GPU needed).
 //   default      every parsed read sequence of the serial reader (fastx.hpp) on its own line
 //   --serial-lv  the same reads after the LongestValid rule (longest run of ACGTacgt, upper-cased)
@@ -9,6 +9,8 @@
 //   --time-records  the serial parse loop of spades-kmerdata alone (next_record, then the record appended to a block with
 //                33 subtracted from every quality), timed: prints "<records> <bases> <seconds>" per file
 //                (tools/fastqparse_perf.py)
+//   --offset     determine_offset of every file (fastx.hpp: what spades-hammer does when input_qvoffset is absent): prints
+//                33, 64 or "failed" on a line of its own
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +37,18 @@ int main(int argc, char **argv) {
         records = true;
         timed = argv[1][2] == 't';
         first = 2;
+    }
+    if (argc > 1 && !strcmp(argv[1], "--offset")) {
+        for (int i = 2; i < argc; ++i) {
+            const int off = bbkhost::determine_offset(argv[i]);
+            if (off == -2) {
+                fprintf(stderr, "cannot open %s\n", argv[i]);
+                return 2;
+            }
+            if (off < 0) printf("failed\n");
+            else printf("%d\n", off);
+        }
+        return 0;
     }
     if (fast) {
         std::vector<std::string> files(argv + first, argv + argc);
