@@ -400,9 +400,9 @@ void partition_records(bbk_ctx *ctx, int W, const void *src, void *dst, const ui
 enum ReduceOp { REDUCE_COUNT = 0, REDUCE_SUM = 1, REDUCE_OR = 2 };
 // Unique of a sorted record array: distinct keys to out_keys (may alias nothing), per-key reduction of
 // vals (COUNT: run length, SUM: sum of vals, OR: or of vals) to out_vals (may be null for COUNT-less).
-// Returns the number of distinct keys.  drop_zero: omit keys whose reduced value is 0 (OR mode).
+// Returns the number of distinct keys.
 uint64_t unique_records(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, void *out_keys,
-                        uint32_t *out_vals, ReduceOp op, bool drop_zero);
+                        uint32_t *out_vals, ReduceOp op);
 // The (key, val) pairs with val != 0, in their order, into out_* (allocated only when something is dropped); returns how
 // many were kept.
 uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
@@ -441,6 +441,10 @@ extern "C" int bbk_scan2_u64(bbk_ctx *ctx, void *d_a, void *d_b, uint64_t n, uin
 // context.hip: `bytes` of device memory through d2h_big into h_dst (when not NULL) and through d2f_big to offset 0 of fd
 // (when fd >= 0)
 extern "C" int bbk_staged_copy(bbk_ctx *ctx, const void *d_src, uint64_t bytes, void *h_dst, int fd);
+// unique.hip: the ordered selection of select.h with per_item(vals[i] >= min) over n u32 values: the index (u64) and the
+// value of every kept item at its rank, *kept their number; waits for the stream
+extern "C" int bbk_select_u32(bbk_ctx *ctx, const void *d_vals, uint64_t n, uint32_t min, void *d_idx_out, void *d_val_out,
+                              uint64_t *kept);
 // msd.hip: the tile geometry of the counting paths at k, and the plan of a read set with the descriptors of its tiles,
 // copied to the host
 extern "C" int bbk_read_plan_geometry(unsigned k, uint32_t *out);

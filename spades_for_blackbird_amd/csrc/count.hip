@@ -189,7 +189,7 @@ struct LsdSort {
     uint64_t unique(ReduceOp op, DevBuf &out_keys, DevBuf *out_vals) {
         if (out_vals && !vtmp.p) vtmp.alloc(n * 4);
         uint32_t *rv = out_vals ? vtmp.as<uint32_t>() : nullptr;
-        const uint64_t D = unique_records(ctx, W, keys.p, vals.as<uint32_t>(), n, tmp.p, rv, op, /*drop_zero=*/false);
+        const uint64_t D = unique_records(ctx, W, keys.p, vals.as<uint32_t>(), n, tmp.p, rv, op);
         keys.release();
         vals.release();
         out_keys.alloc(D * rec + 16);

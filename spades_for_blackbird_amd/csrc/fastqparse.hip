@@ -31,6 +31,7 @@
 #include <memory>
 
 #include "hammer.h"
+#include "select.h"
 
 namespace bbk {
 
@@ -52,20 +53,6 @@ __device__ inline uint32_t fq_lf_mask(const uint8_t *__restrict__ text, uint64_t
     return left >= 16 ? m : m & ((1u << left) - 1u);
 }
 
-// The counts c (0..16) of the lanes of a wavefront: their sum over the lanes below this one, and over all lanes
-__device__ inline void fq_wave_sums(uint32_t c, uint32_t lane, uint32_t *below, uint32_t *all) {
-    const uint64_t lt = (1ull << lane) - 1ull;
-    uint32_t b = 0, a = 0;
-#pragma unroll
-    for (uint32_t bit = 0; bit < 5; ++bit) {
-        const uint64_t m = __ballot((c >> bit) & 1u);
-        b += (uint32_t)__popcll(m & lt) << bit;
-        a += (uint32_t)__popcll(m) << bit;
-    }
-    *below = b;
-    *all = a;
-}
-
 __global__ __launch_bounds__(256) void k_fq_count(const uint8_t *__restrict__ text, uint64_t n_bytes, uint64_t n_tiles,
                                                  uint64_t *__restrict__ counts) {
     const uint64_t tile = (BBK_GID()) >> 6;
@@ -74,7 +61,7 @@ __global__ __launch_bounds__(256) void k_fq_count(const uint8_t *__restrict__ te
     const uint64_t p = tile * kFqTile + (uint64_t)lane * kFqLane;
     const uint32_t c = p < n_bytes ? (uint32_t)__popc(fq_lf_mask(text, n_bytes, p)) : 0u;
     uint32_t below, all;
-    fq_wave_sums(c, lane, &below, &all);
+    wave_sums<5>(c, lane, &below, &all);  // (the lanes' counts run 0..16)
     if (lane == 0) counts[tile] = all;
 }
 
@@ -94,7 +81,7 @@ __global__ __launch_bounds__(256) void k_fq_lines(const uint8_t *__restrict__ te
     const uint64_t p = tile * kFqTile + (uint64_t)lane * kFqLane;
     uint32_t m = p < n_bytes ? fq_lf_mask(text, n_bytes, p) : 0u;
     uint32_t below, all;
-    fq_wave_sums((uint32_t)__popc(m), lane, &below, &all);
+    wave_sums<5>((uint32_t)__popc(m), lane, &below, &all);
     uint64_t j = base[tile] + below + 1;
     while (m) {
         const uint32_t b = (uint32_t)__builtin_ctz(m);

@@ -28,6 +28,7 @@
 
 #include "hammer.h"
 #include "kmer_ops.h"
+#include "select.h"
 
 namespace bbk {
 
@@ -138,24 +139,25 @@ __global__ __launch_bounds__(256) void k_hc_count(const uint32_t *__restrict__ l
     if (i < n) atomicAdd(&cnt[label[i]], 1u);
 }
 
-__global__ __launch_bounds__(256) void k_hc_flag_over(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
-                                                     uint64_t n, uint64_t lock_size, uint64_t *__restrict__ flag) {
-    const uint64_t i = BBK_GID();
-    if (i < n) flag[i] = (uint64_t)cnt[label[i]] >= lock_size ? 1ull : 0ull;
-}
+// the members of the components of >= lock_size k-mers (an ordered selection, select.h), with their keys and rc indices
+struct HcOversize {
+    const uint32_t *__restrict__ label, *__restrict__ cnt;
+    uint64_t lock_size;
+    __device__ bool operator()(uint64_t i) const { return (uint64_t)cnt[label[i]] >= lock_size; }
+};
 
-__global__ __launch_bounds__(256) void k_hc_compact_over(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
-                                                        uint64_t n, uint64_t lock_size, const uint64_t *__restrict__ off,
-                                                        const uint64_t *__restrict__ keys, const uint32_t *__restrict__ rcidx,
-                                                        uint32_t *__restrict__ out_idx, uint64_t *__restrict__ out_key,
-                                                        uint32_t *__restrict__ out_rc) {
-    const uint64_t i = BBK_GID();
-    if (i >= n || (uint64_t)cnt[label[i]] < lock_size) return;
-    const uint64_t d = off[i];
-    out_idx[d] = (uint32_t)i;
-    out_key[d] = keys[i];
-    out_rc[d] = rcidx[i];
-}
+struct HcStoreMember {
+    const uint64_t *__restrict__ keys;
+    const uint32_t *__restrict__ rcidx;
+    uint32_t *__restrict__ out_idx;
+    uint64_t *__restrict__ out_key;
+    uint32_t *__restrict__ out_rc;
+    __device__ void operator()(uint64_t i, uint64_t rank) const {
+        out_idx[rank] = (uint32_t)i;
+        out_key[rank] = keys[i];
+        out_rc[rank] = rcidx[i];
+    }
+};
 
 __global__ __launch_bounds__(256) void k_hc_relabel(const uint32_t *__restrict__ idx, const uint32_t *__restrict__ lab,
                                                    uint64_t r, uint32_t *__restrict__ label) {
@@ -163,17 +165,17 @@ __global__ __launch_bounds__(256) void k_hc_relabel(const uint32_t *__restrict__
     if (j < r) label[idx[j]] = lab[j];
 }
 
-__global__ __launch_bounds__(256) void k_hc_flag_roots(const uint32_t *__restrict__ label, uint64_t n,
-                                                      uint64_t *__restrict__ flag) {
-    const uint64_t i = BBK_GID();
-    if (i < n) flag[i] = label[i] == (uint32_t)i ? 1ull : 0ull;
-}
+// the roots, and the size of each in their order
+struct HcRoot {
+    const uint32_t *__restrict__ label;
+    __device__ bool operator()(uint64_t i) const { return label[i] == (uint32_t)i; }
+};
 
-__global__ __launch_bounds__(256) void k_hc_sizes(const uint32_t *__restrict__ label, const uint32_t *__restrict__ cnt,
-                                                 const uint64_t *__restrict__ off, uint64_t n, uint64_t *__restrict__ sizes) {
-    const uint64_t i = BBK_GID();
-    if (i < n && label[i] == (uint32_t)i) sizes[off[i]] = cnt[i];
-}
+struct HcStoreSize {
+    const uint32_t *__restrict__ cnt;
+    uint64_t *__restrict__ sizes;
+    __device__ void operator()(uint64_t i, uint64_t rank) const { sizes[rank] = cnt[i]; }
+};
 
 __global__ __launch_bounds__(256) void k_hc_pairs(const uint32_t *__restrict__ label, uint64_t n, uint64_t *__restrict__ key,
                                                  uint32_t *__restrict__ val) {
@@ -275,7 +277,7 @@ struct HcRun {
     uint64_t n, lock_size, chunk;
     uint32_t *label = nullptr;  // h->labels: the parents of the union-find, in the end the labels
     DevBuf rcidx, status;       // n u32; status: [0] an rc is missing, [1] the longest block, [2] a jump round changed something
-    DevBuf cnt, off;            // k-mers per label; flags and their scan
+    DevBuf cnt;                 // k-mers per label
 
     // the rc index with the closure refusal, the block scan, pointer jumping until a round changes nothing
     void unite() {
@@ -316,19 +318,19 @@ struct HcRun {
     // the sizes of the components; the members of those of >= lock_size k-mers go through hc_replay; returns how many did
     uint64_t replay_oversize() {
         cnt.alloc(n * 4);
-        off.alloc(n * 8 + 16);
         uint32_t *c = cnt.as<uint32_t>(), h_status[2] = {0, 0};
-        uint64_t *o = off.as<uint64_t>();
         BBK_HIP(hipMemsetAsync(c, 0, n * 4, ctx->stream));
         launch_items_timed(ctx, "hc_list", k_hc_count, n, label, n, c);
-        launch_items_timed(ctx, "hc_list", k_hc_flag_over, n, label, c, n, lock_size, o);
         BBK_HIP(hipMemcpyAsync(h_status, status.p, 8, hipMemcpyDeviceToHost, ctx->stream));
-        const uint64_t R = exclusive_scan_u64(ctx, o, o, n);  // waits: h_status has arrived
+        const auto oversize = per_item(HcOversize{label, c, lock_size});
+        const Selection sel = select_count(ctx, "hc_list", n, oversize);  // waits: h_status has arrived
+        const uint64_t R = sel.kept;
         ctx->add_stat("stat_hc_largest_block", (double)h_status[1]);
         if (R) {
             DevBuf oi(R * 4), ok(R * 8), orc(R * 4);
-            launch_items_timed(ctx, "hc_list", k_hc_compact_over, n, label, c, n, lock_size, o, s->keys.as<uint64_t>(),
-                               rcidx.as<uint32_t>(), oi.as<uint32_t>(), ok.as<uint64_t>(), orc.as<uint32_t>());
+            select_write(ctx, "hc_list", sel, oversize,
+                         HcStoreMember{s->keys.as<uint64_t>(), rcidx.as<uint32_t>(), oi.as<uint32_t>(), ok.as<uint64_t>(),
+                                       orc.as<uint32_t>()});
             std::vector<uint32_t> h_idx(R), h_rc(R), h_lab;
             std::vector<uint64_t> h_key(R);
             BBK_HIP(hipMemcpyAsync(h_idx.data(), oi.p, R * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -348,14 +350,13 @@ struct HcRun {
 
     // the roots and their sizes; the listing: (label, index) records sorted by label, stably, so a cluster's members ascend
     void list() {
-        uint64_t *o = off.as<uint64_t>();
-        launch_items_timed(ctx, "hc_list", k_hc_flag_roots, n, label, n, o);
-        h->clusters = exclusive_scan_u64(ctx, o, o, n);
+        const auto root = per_item(HcRoot{label});
+        const Selection sel = select_count(ctx, "hc_list", n, root);
+        h->clusters = sel.kept;
         h->sizes.alloc(h->clusters * 8);
-        launch_items_timed(ctx, "hc_list", k_hc_sizes, n, label, cnt.as<uint32_t>(), o, n, h->sizes.as<uint64_t>());
+        select_write(ctx, "hc_list", sel, root, HcStoreSize{cnt.as<uint32_t>(), h->sizes.as<uint64_t>()});
         BBK_HIP(hipStreamSynchronize(ctx->stream));
         cnt.release();
-        off.release();
         h->members.alloc(n * 4);
         DevBuf ka(n * 8), kb(n * 8), vb(n * 4);
         launch_items_timed(ctx, "hc_list", k_hc_pairs, n, label, n, ka.as<uint64_t>(), h->members.as<uint32_t>());

@@ -12,46 +12,33 @@
 // k-mer equal to its own reverse complement (even k) in a both-strand set: both strands of every occurrence are the same
 // k-mer, the expansion merges them and its count doubles (count.hip: expand_both_strands), wrapping modulo 2^32 like
 // every multiplicity.  `self_rc_doubles` asks for that reading.
-// Kernels (an order-preserving compaction, no atomics: the same input gives the same bytes):
-//   k_mc_count   one wavefront per tile of 256 records, four per lane: the four counts in one 16-byte load, the kept
-//                records of a lane as a 4-bit mask, of the tile as three ballots (the bits of the lanes' totals); with
-//                self_rc_doubles also the keys, and the dropped self-complementary records of the tile
-//   k_mc_write   the same tiles behind one scan of their totals: the rank of a lane's first kept record from the same
-//                ballots below the lane, keys (16-byte loads) and counts stored at their ranks
+// An ordered selection (select.h: no atomics, the same input gives the same bytes) with the rule, McRule, stated once:
+//   the count            select_count over McKept, in mask form: the four counts of a lane in one 16-byte load; with
+//                        self_rc_doubles also its keys (timing family "k_mc_count")
+//   the dropped self-complementary records   a second, count-only selection under self_rc_doubles ("k_mc_self_rc")
+//   k_mc_write           the site's own write kernel over the selection's tile bases: counts AND keys of a lane loaded up
+//                        front (16-byte loads), the same McRule, the kept records stored at their ranks.  Through
+//                        select_write, whose emitter loads the key of a kept record only once the mask is known, the
+//                        write measured 21 % slower (profiles/select/README.md), so the kernel stays
 #include <hip/hip_runtime.h>
 
 #include "accum.h"
 #include "bbk_internal.h"
 #include "kmer_ops.h"
+#include "select.h"
 
 namespace bbk {
 
-constexpr uint32_t kMcLane = 4, kMcTile = 64 * kMcLane;  // records of a lane, of a wavefront's tile
-
-// The counts of records [p, p + 4): one load where all four exist (p is a multiple of 4: 16-byte aligned), 0 beyond n
-__device__ inline void mc_load_counts(const uint32_t *__restrict__ counts, uint64_t n, uint64_t p, uint32_t c[kMcLane]) {
-    if (p + kMcLane <= n) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(counts + p);
-        c[0] = v.x;
-        c[1] = v.y;
-        c[2] = v.z;
-        c[3] = v.w;
-    } else {
-#pragma unroll
-        for (uint32_t b = 0; b < kMcLane; ++b) c[b] = p + b < n ? counts[p + b] : 0u;
-    }
-}
-
 // The keys of records [p, p + 4): 2 W loads of 16 bytes where all four exist (4 W words, 32 W bytes from an aligned p)
 template <int W>
-__device__ inline void mc_load_keys(const Key<W> *__restrict__ keys, uint64_t n, uint64_t p, Key<W> x[kMcLane]) {
-    if (p + kMcLane <= n) {
+__device__ inline void mc_load_keys(const Key<W> *__restrict__ keys, uint64_t n, uint64_t p, Key<W> x[kSelLane]) {
+    if (p + kSelLane <= n) {
         const uint4 *q = reinterpret_cast<const uint4 *>(keys + p);
         uint4 v[2 * W];
 #pragma unroll
         for (int i = 0; i < 2 * W; ++i) v[i] = q[i];
 #pragma unroll
-        for (uint32_t b = 0; b < kMcLane; ++b)
+        for (uint32_t b = 0; b < kSelLane; ++b)
 #pragma unroll
             for (int i = 0; i < W; ++i) {
                 const int j = (int)b * W + i;
@@ -60,7 +47,7 @@ __device__ inline void mc_load_keys(const Key<W> *__restrict__ keys, uint64_t n,
             }
     } else {
 #pragma unroll
-        for (uint32_t b = 0; b < kMcLane; ++b) {
+        for (uint32_t b = 0; b < kSelLane; ++b) {
 #pragma unroll
             for (int i = 0; i < W; ++i) x[b].w[i] = 0;
             if (p + b < n) x[b] = key_load<W>(&keys[p + b]);
@@ -68,87 +55,78 @@ __device__ inline void mc_load_keys(const Key<W> *__restrict__ keys, uint64_t n,
     }
 }
 
-// The kept records among [p, p + 4) as a mask; *self_rc: the dropped ones that are their own reverse complement
+// The rule, stated once
 template <int W>
-__device__ inline uint32_t mc_kept(const uint32_t c[kMcLane], const Key<W> x[kMcLane], uint64_t n, uint64_t p,
-                                   uint32_t min_count, bool self_rc_doubles, int k, uint32_t *self_rc) {
-    uint32_t m = 0, s = 0;
+struct McRule {
+    const Key<W> *__restrict__ keys;
+    const uint32_t *__restrict__ counts;
+    uint32_t min_count;
+    int self_rc_doubles, k;
+    // The kept records among [p, p + 4) as a mask, from their counts c and (read only with self_rc_doubles) their keys x;
+    // *own_rc: those that are their own reverse complement (none without self_rc_doubles)
+    __device__ uint32_t decide(const uint32_t c[kSelLane], const Key<W> x[kSelLane], uint64_t p, uint64_t n,
+                               uint32_t *own_rc) const {
+        uint32_t m = 0, o = 0;
 #pragma unroll
-    for (uint32_t b = 0; b < kMcLane; ++b) {
-        const bool own = self_rc_doubles && key_eq<W>(kmer_rc<W>(x[b], k), x[b]);
-        const uint32_t mult = own ? c[b] + c[b] : c[b];  // (u32: wraps as the merged count does)
-        const bool keep = p + b < n && mult >= min_count;
-        m |= (keep ? 1u : 0u) << b;
-        s |= (p + b < n && own && !keep ? 1u : 0u) << b;
+        for (uint32_t b = 0; b < kSelLane; ++b) {
+            const bool own = self_rc_doubles && key_eq<W>(kmer_rc<W>(x[b], k), x[b]);
+            const uint32_t mult = own ? c[b] + c[b] : c[b];  // (u32: wraps as the merged count does)
+            m |= (p + b < n && mult >= min_count ? 1u : 0u) << b;
+            o |= (p + b < n && own ? 1u : 0u) << b;
+        }
+        *own_rc = o;
+        return m;
     }
-    *self_rc = s;
-    return m;
-}
-
-// The totals t (0..4) of the lanes of a wavefront: their sum over the lanes below this one, and over all lanes
-__device__ inline void mc_wave_sums(uint32_t t, uint32_t lane, uint32_t *below, uint32_t *all) {
-    const uint64_t lt = (1ull << lane) - 1ull;
-    uint32_t b = 0, a = 0;
-#pragma unroll
-    for (uint32_t bit = 0; bit < 3; ++bit) {
-        const uint64_t m = __ballot((t >> bit) & 1u);
-        b += (uint32_t)__popcll(m & lt) << bit;
-        a += (uint32_t)__popcll(m) << bit;
+    // ... loading what the rule reads: the plain rule reads no key
+    __device__ uint32_t kept(uint64_t p, uint64_t n, uint32_t *own_rc) const {
+        uint32_t c[kSelLane];
+        Key<W> x[kSelLane];
+        load4_u32(counts, n, p, c);
+        if (self_rc_doubles) mc_load_keys<W>(keys, n, p, x);  // (uniform)
+        return decide(c, x, p, n, own_rc);
     }
-    *below = b;
-    *all = a;
-}
+};
 
-// kept[tile]: the records of the tile that stay; self_rc[tile] (with self_rc_doubles): its dropped self-complementary ones
 template <int W>
-__global__ __launch_bounds__(256) void k_mc_count(const Key<W> *__restrict__ keys, const uint32_t *__restrict__ counts,
-                                                 uint64_t n, uint64_t n_tiles, uint32_t min_count, int self_rc_doubles,
-                                                 int k, uint64_t *__restrict__ kept, uint64_t *__restrict__ self_rc) {
-    const uint64_t tile = (BBK_GID()) >> 6;
-    if (tile >= n_tiles) return;
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t p = tile * kMcTile + (uint64_t)lane * kMcLane;
-    uint32_t c[kMcLane];
-    Key<W> x[kMcLane];
-    mc_load_counts(counts, n, p, c);
-    if (self_rc_doubles) mc_load_keys<W>(keys, n, p, x);  // (uniform) the plain rule reads no key
-    else
-#pragma unroll
-        for (uint32_t b = 0; b < kMcLane; ++b)
-#pragma unroll
-            for (int i = 0; i < W; ++i) x[b].w[i] = 0;
-    uint32_t s;
-    const uint32_t m = mc_kept<W>(c, x, n, p, min_count, self_rc_doubles != 0, k, &s);
-    uint32_t below, all;
-    mc_wave_sums((uint32_t)__popc(m), lane, &below, &all);
-    if (lane == 0) kept[tile] = all;
-    if (self_rc_doubles) {
-        mc_wave_sums((uint32_t)__popc(s), lane, &below, &all);
-        if (lane == 0) self_rc[tile] = all;
+struct McKept {
+    McRule<W> rule;
+    __device__ uint32_t operator()(uint64_t p, uint64_t n) const {
+        uint32_t own;
+        return rule.kept(p, n, &own);
     }
-}
+};
 
-// base: the scanned totals of k_mc_count.  n_kept: their sum, the records the outputs hold
+// own reverse complement and not kept
 template <int W>
-__global__ __launch_bounds__(256) void k_mc_write(const Key<W> *__restrict__ keys, const uint32_t *__restrict__ counts,
-                                                 uint64_t n, uint64_t n_tiles, uint32_t min_count, int self_rc_doubles,
-                                                 int k, const uint64_t *__restrict__ base, uint64_t n_kept,
+struct McDroppedSelfRc {
+    McRule<W> rule;
+    __device__ uint32_t operator()(uint64_t p, uint64_t n) const {
+        uint32_t own;
+        const uint32_t kept = rule.kept(p, n, &own);
+        return own & ~kept;
+    }
+};
+
+// base: the tile bases of the selection on McKept{rule}.  n_kept: its total, the records the outputs hold
+template <int W>
+__global__ __launch_bounds__(256) void k_mc_write(McRule<W> rule, uint64_t n, uint64_t n_tiles,
+                                                 const uint64_t *__restrict__ base, uint64_t n_kept,
                                                  Key<W> *__restrict__ out_keys, uint32_t *__restrict__ out_counts) {
     const uint64_t tile = (BBK_GID()) >> 6;
     if (tile >= n_tiles) return;
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t p = tile * kMcTile + (uint64_t)lane * kMcLane;
-    uint32_t c[kMcLane];
-    Key<W> x[kMcLane];
-    mc_load_counts(counts, n, p, c);
-    mc_load_keys<W>(keys, n, p, x);
-    uint32_t s;
-    const uint32_t m = mc_kept<W>(c, x, n, p, min_count, self_rc_doubles != 0, k, &s);
+    const uint64_t p = tile * kSelTile + (uint64_t)lane * kSelLane;
+    uint32_t c[kSelLane];
+    Key<W> x[kSelLane];
+    load4_u32(rule.counts, n, p, c);
+    mc_load_keys<W>(rule.keys, n, p, x);
+    uint32_t own;
+    const uint32_t m = rule.decide(c, x, p, n, &own);
     uint32_t below, all;
-    mc_wave_sums((uint32_t)__popc(m), lane, &below, &all);
+    wave_sums<3>((uint32_t)__popc(m), lane, &below, &all);
     uint64_t j = base[tile] + below;
 #pragma unroll
-    for (uint32_t b = 0; b < kMcLane; ++b) {
+    for (uint32_t b = 0; b < kSelLane; ++b) {
         if (((m >> b) & 1u) && j < n_kept) {
             key_store<W>(&out_keys[j], x[b]);
             out_counts[j] = c[b];
@@ -163,39 +141,23 @@ uint64_t filter_min_count(bbk_ctx *ctx, unsigned k, bool self_rc_doubles, uint32
     if (n == 0) return 0;
     const int W = (int)words_of(k);
     const size_t rec = (size_t)W * 8;
-    const uint64_t n_tiles = (n + kMcTile - 1) / kMcTile;
-    DevBuf d_kept((n_tiles + 1) * 8), d_self((n_tiles + 1) * 8);
-    const int own = self_rc_doubles ? 1 : 0;
+    uint64_t n_kept = n;
     dispatch_w((unsigned)W, [&](auto w) {
         constexpr int W_ = decltype(w)::value;
-        launch_items_timed(ctx, "k_mc_count", k_mc_count<W_>, n_tiles * 64, (const Key<W_> *)keys.p, vals.as<uint32_t>(), n,
-                           n_tiles, min_count, own, (int)k, d_kept.as<uint64_t>(), d_self.as<uint64_t>());
+        const McRule<W_> rule{(const Key<W_> *)keys.p, vals.as<uint32_t>(), min_count, self_rc_doubles ? 1 : 0, (int)k};
+        const Selection sel = select_count(ctx, "k_mc_count", n, McKept<W_>{rule});
+        n_kept = sel.kept;
+        if (self_rc_doubles) *dropped_self_rc = select_count(ctx, "k_mc_self_rc", n, McDroppedSelfRc<W_>{rule}).kept;
+        if (n_kept == n) return;  // nothing to drop: the records stay where they are
+        DevBuf ok(n_kept * rec + 16), ov(n_kept * 4 + 16);
+        if (n_kept) {
+            launch_items_timed(ctx, "k_mc_write", k_mc_write<W_>, sel.n_tiles * 64, rule, n, sel.n_tiles,
+                               sel.base.as<uint64_t>(), n_kept, (Key<W_> *)ok.p, ov.as<uint32_t>());
+            stream_wait(ctx);  // the tile bases go back to the pool with this frame
+        }
+        keys = std::move(ok);
+        vals = std::move(ov);
     });
-    uint64_t n_kept = 0;
-    if (self_rc_doubles) {
-        uint64_t totals[2] = {0, 0};
-        exclusive_scan2_u64(ctx, d_kept.as<uint64_t>(), d_kept.as<uint64_t>(), d_self.as<uint64_t>(), d_self.as<uint64_t>(),
-                            n_tiles, totals);
-        n_kept = totals[0];
-        *dropped_self_rc = totals[1];
-    } else {
-        n_kept = exclusive_scan_u64(ctx, d_kept.as<uint64_t>(), d_kept.as<uint64_t>(), n_tiles);
-    }
-    BBK_REQUIRE(n_kept <= n, BBK_ERR_INTERNAL, "minimum-count filter: %llu of %llu records kept",
-                (unsigned long long)n_kept, (unsigned long long)n);
-    if (n_kept == n) return n;  // nothing to drop: the records stay where they are
-    DevBuf ok(n_kept * rec + 16), ov(n_kept * 4 + 16);
-    if (n_kept) {
-        dispatch_w((unsigned)W, [&](auto w) {
-            constexpr int W_ = decltype(w)::value;
-            launch_items_timed(ctx, "k_mc_write", k_mc_write<W_>, n_tiles * 64, (const Key<W_> *)keys.p, vals.as<uint32_t>(),
-                               n, n_tiles, min_count, own, (int)k, d_kept.as<uint64_t>(), n_kept, (Key<W_> *)ok.p,
-                               ov.as<uint32_t>());
-        });
-        stream_wait(ctx);  // the tile bases go back to the pool with this frame
-    }
-    keys = std::move(ok);
-    vals = std::move(ov);
     return n_kept;
 }
 

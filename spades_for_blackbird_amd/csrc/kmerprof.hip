@@ -7,7 +7,7 @@
 // filtered (count >= ci, saturated at cs) and kept on the device as keys + u16 counts; finish() concatenates the key
 // arrays, merge-uniques them with the engine's own sort (bbk_kmerset_from_device_ex), scatters every sample's counts
 // into rows[union position * N + sample] through the prefix table + binary search, applies the keep rule per union
-// k-mer and compacts keys and rows through the scan of scan.hip.
+// k-mer and moves the kept keys and rows with the ordered selection of select.h.
 //
 // Abundance: replaces ProfileCounter::operator() (projects/mts/contig_abundance.cpp:245-284) with the winsorised mean
 // of TrivialClusterAnalyzer (:46-78).  A contig is the run of pieces (maximal ACGT stretches) the caller cut it into.
@@ -33,6 +33,7 @@
 #include "bbk_internal.h"
 #include "gfa_graph.h"
 #include "kmer_ops.h"
+#include "select.h"
 
 struct bbk_kmerprofile {
     unsigned k = 0, W = 0, N = 0;
@@ -58,28 +59,21 @@ namespace bbk {
 
 // ---- join ---------------------------------------------------------------------------------------------------------------
 
-// per-sample filter: a k-mer counted fewer than ci times is absent from the sample
-__global__ __launch_bounds__(256) void k_kp_sample_flag(const uint32_t *__restrict__ counts, uint64_t n, uint32_t ci,
-                                                       uint64_t *__restrict__ flag) {
-    const uint64_t i = BBK_GID();
-    if (i >= n) return;
-    flag[i] = counts[i] >= ci ? 1ull : 0ull;
-}
-
-// ... and the remaining counts are saturated at cs (<= 65535) and narrowed to u16
+// per-sample filter (an ordered selection on U32AtLeast{counts, ci}, select.h): a k-mer counted fewer than ci times is
+// absent from the sample, and the remaining counts are saturated at cs (<= 65535) and narrowed to u16
 template <int W>
-__global__ __launch_bounds__(256) void k_kp_sample_compact(const Key<W> *__restrict__ keys,
-                                                          const uint32_t *__restrict__ counts, uint64_t n, uint32_t ci,
-                                                          uint32_t cs, const uint64_t *__restrict__ off,
-                                                          Key<W> *__restrict__ out_keys, uint16_t *__restrict__ out_vals) {
-    const uint64_t i = BBK_GID();
-    if (i >= n) return;
-    const uint32_t c = counts[i];
-    if (c < ci) return;
-    const uint64_t d = off[i];
-    key_store<W>(&out_keys[d], key_load<W>(&keys[i]));
-    out_vals[d] = (uint16_t)(c < cs ? c : cs);
-}
+struct KpStoreSample {
+    const Key<W> *__restrict__ keys;
+    const uint32_t *__restrict__ counts;
+    uint32_t cs;
+    Key<W> *__restrict__ out_keys;
+    uint16_t *__restrict__ out_vals;
+    __device__ void operator()(uint64_t i, uint64_t rank) const {
+        const uint32_t c = counts[i];
+        key_store<W>(&out_keys[rank], key_load<W>(&keys[i]));
+        out_vals[rank] = (uint16_t)(c < cs ? c : cs);
+    }
+};
 
 // one lane per record of sample s: its place in the union, its count into the row
 template <int W>
@@ -96,10 +90,10 @@ __global__ __launch_bounds__(256) void k_kp_scatter(const Key<W> *__restrict__ s
     rows[pos * (uint64_t)N + s] = svals[i];
 }
 
-// one lane per union k-mer: present = samples holding it, total = sum of its counts (:115-125)
+// one lane per union k-mer: present = samples holding it, total = sum of its counts (:115-125); the rule over a row is
+// stated here only: the selection reads the keep byte
 __global__ __launch_bounds__(256) void k_kp_keep(const uint16_t *__restrict__ rows, uint64_t n, unsigned N,
-                                                uint64_t min_samples, uint64_t min_mult, uint8_t *__restrict__ keep,
-                                                uint64_t *__restrict__ flag) {
+                                                uint64_t min_samples, uint64_t min_mult, uint8_t *__restrict__ keep) {
     const uint64_t i = BBK_GID();
     if (i >= n) return;
     const uint16_t *row = rows + i * (uint64_t)N;
@@ -109,24 +103,35 @@ __global__ __launch_bounds__(256) void k_kp_keep(const uint16_t *__restrict__ ro
         present += v != 0 ? 1u : 0u;
         total += v;
     }
-    const bool k = present >= min_samples && (present > 1 || total > min_mult);
-    keep[i] = k ? 1 : 0;
-    flag[i] = k ? 1ull : 0ull;
+    keep[i] = present >= min_samples && (present > 1 || total > min_mult) ? 1 : 0;
 }
 
+// (mask form: the four keep bytes of a lane in one load; p is a multiple of 4 and keep holds 16 bytes beyond n)
+struct KpKeepByte {
+    const uint8_t *__restrict__ keep;
+    __device__ uint32_t operator()(uint64_t p, uint64_t n) const {
+        const uint32_t v = *reinterpret_cast<const uint32_t *>(keep + p);
+        uint32_t m = 0;
+#pragma unroll
+        for (uint32_t b = 0; b < kSelLane; ++b) m |= (p + b < n && ((v >> (8 * b)) & 0xFFu) ? 1u : 0u) << b;
+        return m;
+    }
+};
+
 template <int W>
-__global__ __launch_bounds__(256) void k_kp_compact(const Key<W> *__restrict__ keys, const uint16_t *__restrict__ rows,
-                                                   uint64_t n, unsigned N, const uint8_t *__restrict__ keep,
-                                                   const uint64_t *__restrict__ off, Key<W> *__restrict__ out_keys,
-                                                   uint16_t *__restrict__ out_rows) {
-    const uint64_t i = BBK_GID();
-    if (i >= n || !keep[i]) return;
-    const uint64_t d = off[i];
-    key_store<W>(&out_keys[d], key_load<W>(&keys[i]));
-    const uint16_t *src = rows + i * (uint64_t)N;
-    uint16_t *dst = out_rows + d * (uint64_t)N;
-    for (unsigned s = 0; s < N; ++s) dst[s] = src[s];
-}
+struct KpMoveRow {
+    const Key<W> *__restrict__ keys;
+    const uint16_t *__restrict__ rows;
+    unsigned N;
+    Key<W> *__restrict__ out_keys;
+    uint16_t *__restrict__ out_rows;
+    __device__ void operator()(uint64_t i, uint64_t rank) const {
+        key_store<W>(&out_keys[rank], key_load<W>(&keys[i]));
+        const uint16_t *src = rows + i * (uint64_t)N;
+        uint16_t *dst = out_rows + rank * (uint64_t)N;
+        for (unsigned s = 0; s < N; ++s) dst[s] = src[s];
+    }
+};
 
 // ---- abundance ----------------------------------------------------------------------------------------------------------
 
@@ -330,18 +335,17 @@ static void add_sample(bbk_kmerprofile_builder *b, unsigned sample, const bbk_km
     S.n = 0;
     if (s->n == 0) return;
     const size_t rec = (size_t)b->W * 8;
-    DevBuf off(s->n * 8 + 16);
-    launch_items_timed(ctx, "kp_filter", k_kp_sample_flag, s->n, s->counts.as<uint32_t>(), s->n, (uint32_t)b->ci,
-                       off.as<uint64_t>());
-    const uint64_t kept = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), s->n);
+    const U32AtLeast counted{s->counts.as<uint32_t>(), (uint32_t)b->ci};
+    const Selection sel = select_count(ctx, "kp_filter", s->n, counted);
+    const uint64_t kept = sel.kept;
     if (kept == 0) return;
     S.keys.alloc(kept * rec);
     S.vals.alloc(kept * 2);
     dispatch_w(b->W, [&](auto w) {
         constexpr int W_ = decltype(w)::value;
-        launch_items_timed(ctx, "kp_filter", k_kp_sample_compact<W_>, s->n, s->keys.as<Key<W_>>(),
-                           s->counts.as<uint32_t>(), s->n, (uint32_t)b->ci, (uint32_t)b->cs, off.as<uint64_t>(),
-                           S.keys.as<Key<W_>>(), S.vals.as<uint16_t>());
+        select_write(ctx, "kp_filter", sel, counted,
+                     KpStoreSample<W_>{s->keys.as<Key<W_>>(), s->counts.as<uint32_t>(), (uint32_t)b->cs, S.keys.as<Key<W_>>(),
+                                       S.vals.as<uint16_t>()});
     });
     BBK_HIP(hipStreamSynchronize(ctx->stream));
     S.n = kept;
@@ -408,18 +412,19 @@ static bbk_kmerprofile *finish_profile(bbk_kmerprofile_builder *b, uint64_t min_
         S.keys.release();
         S.vals.release();
     }
-    DevBuf keep(U + 16), off(U * 8 + 16);
-    launch_items_timed(ctx, "kp_keep", k_kp_keep, U, rows.as<uint16_t>(), U, N, min_samples, min_mult,
-                       keep.as<uint8_t>(), off.as<uint64_t>());
-    const uint64_t kept = exclusive_scan_u64(ctx, off.as<uint64_t>(), off.as<uint64_t>(), U);
+    DevBuf keep(U + 16);
+    launch_items_timed(ctx, "kp_keep", k_kp_keep, U, rows.as<uint16_t>(), U, N, min_samples, min_mult, keep.as<uint8_t>());
+    const KpKeepByte kept_byte{keep.as<uint8_t>()};
+    const Selection sel = select_count(ctx, "kp_keep", U, kept_byte);
+    const uint64_t kept = sel.kept;
     p->n = kept;
     p->keys.alloc(kept * rec);
     p->rows.alloc(kept * (uint64_t)N * 2);
     if (kept) {
         dispatch_w(W, [&](auto w) {
             constexpr int W_ = decltype(w)::value;
-            launch_items_timed(ctx, "kp_compact", k_kp_compact<W_>, U, ukeys.as<Key<W_>>(), rows.as<uint16_t>(), U, N,
-                               keep.as<uint8_t>(), off.as<uint64_t>(), p->keys.as<Key<W_>>(), p->rows.as<uint16_t>());
+            select_write(ctx, "kp_compact", sel, kept_byte,
+                         KpMoveRow<W_>{ukeys.as<Key<W_>>(), rows.as<uint16_t>(), N, p->keys.as<Key<W_>>(), p->rows.as<uint16_t>()});
         });
         BBK_HIP(hipStreamSynchronize(ctx->stream));
     }

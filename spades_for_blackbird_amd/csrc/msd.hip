@@ -1300,7 +1300,7 @@ struct MsdRunner {
                 sort_records(ctx, W, kb, tk.p, has_val ? vb : nullptr, has_val ? tv.as<uint32_t>() : nullptr, cnt,
                              key_passes(R.k));
                 const uint64_t d = unique_records(ctx, W, kb, has_val ? vb : nullptr, cnt, ok.p,
-                                                  out_vals ? ov.as<uint32_t>() : nullptr, rop, false);
+                                                  out_vals ? ov.as<uint32_t>() : nullptr, rop);
                 BBK_HIP(bbk::copy_async(kb, ok.p, d * rec, hipMemcpyDeviceToDevice, ctx->stream));
                 if (out_vals) BBK_HIP(bbk::copy_async(vb, ov.p, d * 4, hipMemcpyDeviceToDevice, ctx->stream));
                 stream_wait(ctx);

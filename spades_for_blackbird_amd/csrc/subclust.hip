@@ -32,6 +32,7 @@
 
 #include "hammer.h"
 #include "kmer_ops.h"
+#include "select.h"
 
 #pragma clang fp contract(off)
 
@@ -178,18 +179,17 @@ __global__ __launch_bounds__(256) void k_sc_slab_sizes(const uint64_t *__restric
     if (c < C) out[c] = sizes[c] == 1 ? 0ull : sizes[c];
 }
 
-__global__ __launch_bounds__(256) void k_sc_class_flag(const uint64_t *__restrict__ sizes, uint64_t C, uint64_t lo,
-                                                      uint64_t hi, uint64_t *__restrict__ flag) {
-    const uint64_t c = BBK_GID();
-    if (c < C) flag[c] = sizes[c] >= lo && sizes[c] <= hi ? 1ull : 0ull;
-}
+// the clusters of a size class, in their order (an ordered selection, select.h)
+struct ScSizeIn {
+    const uint64_t *__restrict__ sizes;
+    uint64_t lo, hi;
+    __device__ bool operator()(uint64_t c) const { return sizes[c] >= lo && sizes[c] <= hi; }
+};
 
-__global__ __launch_bounds__(256) void k_sc_class_list(const uint64_t *__restrict__ sizes, uint64_t C, uint64_t lo,
-                                                      uint64_t hi, const uint64_t *__restrict__ pos,
-                                                      uint32_t *__restrict__ list) {
-    const uint64_t c = BBK_GID();
-    if (c < C && sizes[c] >= lo && sizes[c] <= hi) list[pos[c]] = (uint32_t)c;
-}
+struct ScListCluster {
+    uint32_t *__restrict__ list;
+    __device__ void operator()(uint64_t c, uint64_t rank) const { list[rank] = (uint32_t)c; }
+};
 
 // `unsigned total` of ClusterBIC:106-110: the sum of the counts, modulo 2^32
 __global__ __launch_bounds__(256) void k_sc_totals(ScIn in, const uint32_t *__restrict__ list, uint64_t nlist,
@@ -705,7 +705,7 @@ struct ScRun {
     ScIn in;
     ScSlab slab;
     double tab[128];  // LP[q], LR3[q] interleaved (kmer_stat.hpp:211-213)
-    DevBuf d_tab, off, soff, scratch, s_mem, s_size, s_nkey, nsub, nmem, nnew, cval, d_stats;  // d_stats: 16 counters, 16 error counts
+    DevBuf d_tab, off, soff, s_mem, s_size, s_nkey, nsub, nmem, nnew, cval, d_stats;  // d_stats: 16 counters, 16 error counts
 
     // offsets of the clusters in the member list and in the slabs, the kernels' view of the inputs, the slab buffers
     void layout(const bbk_kmerset *set, const bbk_hamclusters *hc, const bbk_kmerstats *ks, const ScParams &p) {
@@ -717,7 +717,7 @@ struct ScRun {
             tab[2 * q + 1] = log(r) - log(3);
         }
         upload(ctx, d_tab, tab, 128);  // this outlives the waits below
-        for (DevBuf *b : {&off, &soff, &scratch}) b->alloc((C + 1) * 8);
+        for (DevBuf *b : {&off, &soff}) b->alloc((C + 1) * 8);
         exclusive_scan_u64(ctx, sizes, off.as<uint64_t>(), C);
         launch_items(ctx, "sc_classes", k_sc_slab_sizes, C, sizes, C, soff.as<uint64_t>());
         const uint64_t slots = exclusive_scan_u64(ctx, soff.as<uint64_t>(), soff.as<uint64_t>(), C);
@@ -811,13 +811,14 @@ struct ScRun {
                                  {host ? 2ull : kScGroup + 1ull, ~0ull, &ScRun::run_host, nullptr}};
         const uint64_t C = in.clusters;
         launch_items_timed(ctx, "sc_single", k_sc_single, C, in, slab, cval.as<uint8_t>(), d_stats.as<unsigned long long>());
-        uint64_t *flag = scratch.as<uint64_t>(), non_singletons = 0;
+        uint64_t non_singletons = 0;
         DevBuf list;
         for (const Class *c = by_size + (host ? 2 : 0); c < by_size + 3; ++c) {
-            launch_items(ctx, "sc_classes", k_sc_class_flag, C, in.sizes, C, c->lo, c->hi, flag);
-            const uint64_t cnt = exclusive_scan_u64(ctx, flag, flag, C);
+            const auto in_class = per_item(ScSizeIn{in.sizes, c->lo, c->hi});
+            const Selection sel = select_count(ctx, "sc_classes", C, in_class);
+            const uint64_t cnt = sel.kept;
             list.alloc(cnt * 4);
-            if (cnt) launch_items(ctx, "sc_classes", k_sc_class_list, C, in.sizes, C, c->lo, c->hi, flag, list.as<uint32_t>());
+            select_write(ctx, "sc_classes", sel, in_class, ScListCluster{list.as<uint32_t>()});
             non_singletons += cnt;
             if (c->stat) ctx->add_stat(c->stat, (double)cnt);
             if (cnt) sc->host_kmers += (this->*c->run)(list, cnt);

@@ -6,6 +6,7 @@
 #include "bbk_internal.h"
 #include "block_scan.h"
 #include "kmer_ops.h"
+#include "select.h"
 
 namespace bbk {
 
@@ -88,60 +89,9 @@ __global__ __launch_bounds__(kThreads) void k_seg_reduce(const uint32_t *__restr
     out_vals[s] = r;
 }
 
-// compaction of (key, val) pairs with val != 0
-template <int W>
-__global__ __launch_bounds__(kThreads) void k_nonzero_count(const uint32_t *__restrict__ vals, uint64_t n,
-                                                           uint64_t *__restrict__ bcount) {
-    __shared__ uint32_t sm[kWaves];
-    const uint64_t base = (uint64_t)blockIdx.x * kUniqTile;
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < kUniqItems; ++i) {
-        uint64_t idx = base + (uint64_t)i * kThreads + threadIdx.x;
-        if (idx < n && vals[idx] != 0) ++c;
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_down(c, d, 64);
-    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < kWaves; ++w) t += sm[w];
-        bcount[blockIdx.x] = t;
-    }
-}
-
-template <int W>
-__global__ __launch_bounds__(kThreads) void k_nonzero_compact(const Key<W> *__restrict__ keys,
-                                                             const uint32_t *__restrict__ vals, uint64_t n,
-                                                             const uint64_t *__restrict__ boff,
-                                                             Key<W> *__restrict__ out_keys,
-                                                             uint32_t *__restrict__ out_vals) {
-    __shared__ uint32_t scan_tmp[kWaves + 1];
-    const uint64_t base = (uint64_t)blockIdx.x * kUniqTile + (uint64_t)threadIdx.x * kUniqItems;
-    bool h[kUniqItems];
-    uint32_t c = 0;
-#pragma unroll
-    for (int i = 0; i < kUniqItems; ++i) {
-        h[i] = (base + i < n) && vals[base + i] != 0;
-        c += h[i] ? 1u : 0u;
-    }
-    uint32_t tot;
-    uint32_t pre = block_excl_scan(c, scan_tmp, &tot);
-    uint64_t pos = boff[blockIdx.x] + pre;
-#pragma unroll
-    for (int i = 0; i < kUniqItems; ++i) {
-        if (h[i]) {
-            out_keys[pos] = keys[base + i];
-            out_vals[pos] = vals[base + i];
-            ++pos;
-        }
-    }
-}
-
 template <int W>
 static uint64_t unique_impl(bbk_ctx *ctx, const Key<W> *keys, const uint32_t *vals, uint64_t n, Key<W> *out_keys,
-                            uint32_t *out_vals, ReduceOp op, bool drop_zero) {
+                            uint32_t *out_vals, ReduceOp op) {
     if (n == 0) return 0;
     BBK_REQUIRE(n < (1ull << 32), BBK_ERR_ARG, "unique_records: n=%llu does not fit 32-bit offsets",
                 (unsigned long long)n);
@@ -151,80 +101,94 @@ static uint64_t unique_impl(bbk_ctx *ctx, const Key<W> *keys, const uint32_t *va
                  bcount.as<uint64_t>());
     const uint64_t nd = exclusive_scan_u64(ctx, bcount.as<uint64_t>(), bcount.as<uint64_t>(), nb);
     DevBuf head((nd + 1) * sizeof(uint32_t));
-    const bool need_tmp = drop_zero && op == REDUCE_OR;
-    DevBuf tkeys, tvals;
-    Key<W> *dk = out_keys;
-    uint32_t *dv = out_vals;
-    if (need_tmp) {
-        tkeys.alloc(nd * sizeof(Key<W>));
-        tvals.alloc(nd * sizeof(uint32_t));
-        dk = tkeys.as<Key<W>>();
-        dv = tvals.as<uint32_t>();
-    }
     launch_timed(ctx, k_head_compact<W>, "unique", (double)n * sizeof(Key<W>) + (double)nd * sizeof(Key<W>), (uint32_t)nb,
-                 kThreads, 0, keys, n, bcount.as<uint64_t>(), dk, head.as<uint32_t>());
+                 kThreads, 0, keys, n, bcount.as<uint64_t>(), out_keys, head.as<uint32_t>());
     const uint32_t n32 = (uint32_t)n;
     BBK_HIP(hipMemcpyAsync(head.as<uint32_t>() + nd, &n32, sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (dv) {
+    if (out_vals) {
         KernelTimer t(ctx, "reduce", (double)nd * 8 + (vals ? (double)n * 4 : 0));
-        launch_items(ctx, "k_seg_reduce", k_seg_reduce, nd, head.as<uint32_t>(), nd, vals, (int)op, dv);
-    }
-    uint64_t result = nd;
-    if (need_tmp) {
-        const uint64_t nb2 = (nd + kUniqTile - 1) / kUniqTile;
-        DevBuf bc2(nb2 * sizeof(uint64_t));
-        hipLaunchKernelGGL(k_nonzero_count<W>, dim3((unsigned)nb2), dim3(kThreads), 0, ctx->stream, dv, nd,
-                           bc2.as<uint64_t>());
-        check_launch("k_nonzero_count");
-        result = exclusive_scan_u64(ctx, bc2.as<uint64_t>(), bc2.as<uint64_t>(), nb2);
-        hipLaunchKernelGGL(k_nonzero_compact<W>, dim3((unsigned)nb2), dim3(kThreads), 0, ctx->stream, dk, dv, nd,
-                           bc2.as<uint64_t>(), out_keys, out_vals);
-        check_launch("k_nonzero_compact");
-        stream_wait(ctx);
+        launch_items(ctx, "k_seg_reduce", k_seg_reduce, nd, head.as<uint32_t>(), nd, vals, (int)op, out_vals);
     }
     stream_wait(ctx);
-    return result;
+    return nd;
 }
+
+// ---- ordered selections on a u32 value (select.h) ----------------------------------------------------------------------
+struct ValAtLeast {
+    const uint32_t *__restrict__ vals;
+    uint32_t min;
+    __device__ bool operator()(uint64_t i) const { return vals[i] >= min; }
+};
 
 template <int W>
-static uint64_t drop_zero_impl(bbk_ctx *ctx, const Key<W> *keys, const uint32_t *vals, uint64_t n, DevBuf &ok,
-                               DevBuf &ov) {
-    if (n == 0) return 0;
-    const uint64_t nb = (n + kUniqTile - 1) / kUniqTile;
-    DevBuf bc(nb * sizeof(uint64_t));
-    hipLaunchKernelGGL(k_nonzero_count<W>, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, vals, n,
-                       bc.as<uint64_t>());
-    check_launch("k_nonzero_count");
-    const uint64_t kept = exclusive_scan_u64(ctx, bc.as<uint64_t>(), bc.as<uint64_t>(), nb);
-    if (kept == n) return n;  // nothing to drop: caller keeps its buffers (the usual case: nothing is allocated)
-    ok.alloc(kept * sizeof(Key<W>) + 16);
-    ov.alloc(kept * 4 + 16);
-    hipLaunchKernelGGL(k_nonzero_compact<W>, dim3((unsigned)nb), dim3(kThreads), 0, ctx->stream, keys, vals, n,
-                       bc.as<uint64_t>(), ok.as<Key<W>>(), ov.as<uint32_t>());
-    check_launch("k_nonzero_compact");
-    stream_wait(ctx);
-    return kept;
-}
+struct MovePair {
+    const Key<W> *__restrict__ keys;
+    const uint32_t *__restrict__ vals;
+    Key<W> *__restrict__ out_keys;
+    uint32_t *__restrict__ out_vals;
+    __device__ void operator()(uint64_t i, uint64_t rank) const {
+        out_keys[rank] = keys[i];
+        out_vals[rank] = vals[i];
+    }
+};
+
+struct StoreIndexAndVal {
+    const uint32_t *__restrict__ vals;
+    uint64_t *__restrict__ out_idx;
+    uint32_t *__restrict__ out_vals;
+    __device__ void operator()(uint64_t i, uint64_t rank) const {
+        out_idx[rank] = i;
+        out_vals[rank] = vals[i];
+    }
+};
 
 // Compacts the (key, val) pairs with val != 0 into out_* (allocated here, only when something is dropped); returns
-// how many were kept (if all are kept nothing is allocated or written).
+// how many were kept (if all are kept nothing is allocated or written: the usual case).
 uint64_t drop_zero_vals(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, DevBuf &out_keys,
                         DevBuf &out_vals) {
-    uint64_t kept = 0;
+    const U32AtLeast nonzero{vals, 1u};  // (vals is the start of the caller's buffer)
+    const Selection sel = select_count(ctx, "drop_zero", n, nonzero);
+    if (sel.kept == n) return n;
+    out_keys.alloc(sel.kept * (size_t)W * 8 + 16);
+    out_vals.alloc(sel.kept * 4 + 16);
     dispatch_w((unsigned)W, [&](auto w) {
-        kept = drop_zero_impl(ctx, (const Key<decltype(w)::value> *)keys, vals, n, out_keys, out_vals);
+        constexpr int W_ = decltype(w)::value;
+        select_write(ctx, "drop_zero", sel, nonzero,
+                     MovePair<W_>{(const Key<W_> *)keys, vals, out_keys.as<Key<W_>>(), out_vals.as<uint32_t>()});
     });
-    return kept;
+    stream_wait(ctx);
+    return sel.kept;
 }
 
 uint64_t unique_records(bbk_ctx *ctx, int W, const void *keys, const uint32_t *vals, uint64_t n, void *out_keys,
-                        uint32_t *out_vals, ReduceOp op, bool drop_zero) {
+                        uint32_t *out_vals, ReduceOp op) {
     uint64_t distinct = 0;
     dispatch_w((unsigned)W, [&](auto w) {
         using K = Key<decltype(w)::value>;
-        distinct = unique_impl(ctx, (const K *)keys, vals, n, (K *)out_keys, out_vals, op, drop_zero);
+        distinct = unique_impl(ctx, (const K *)keys, vals, n, (K *)out_keys, out_vals, op);
     });
     return distinct;
 }
 
 }  // namespace bbk
+
+using namespace bbk;
+
+extern "C" {
+
+int bbk_select_u32(bbk_ctx *ctx, const void *d_vals, uint64_t n, uint32_t min, void *d_idx_out, void *d_val_out,
+                   uint64_t *kept) {
+    return guarded([&] {
+        BBK_REQUIRE(ctx && kept && (n == 0 || (d_vals && d_idx_out && d_val_out)), BBK_ERR_ARG,
+                    "bbk_select_u32: NULL argument");
+        BBK_HIP(hipSetDevice(ctx->device));
+        const uint32_t *vals = (const uint32_t *)d_vals;
+        const auto pred = per_item(ValAtLeast{vals, min});
+        const Selection sel = select_count(ctx, "select_u32", n, pred);
+        select_write(ctx, "select_u32", sel, pred, StoreIndexAndVal{vals, (uint64_t *)d_idx_out, (uint32_t *)d_val_out});
+        stream_wait(ctx);
+        *kept = sel.kept;
+    });
+}
+
+}  // extern "C"

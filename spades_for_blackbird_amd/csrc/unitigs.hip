@@ -22,6 +22,7 @@
 
 #include "bbk_internal.h"
 #include "kmer_ops.h"
+#include "select.h"
 #include "unitigs.h"
 
 namespace bbk {
@@ -163,19 +164,16 @@ __global__ __launch_bounds__(256) void k_walk(const Key<W> *__restrict__ keys, c
     }
 }
 
-__global__ void k_loop_candidates(const uint8_t *__restrict__ masks, const uint8_t *__restrict__ visited, uint64_t n,
-                                  uint64_t *__restrict__ flag) {
-    const uint64_t i = BBK_GID();
-    if (i >= n) return;
-    flag[i] = (!mask_is_junction(masks[i]) && !visited[i]) ? 1ull : 0ull;
-}
+// the candidates of perfect loops (an ordered selection, select.h): non-junction k-mers no path went through
+struct LoopCandidate {
+    const uint8_t *__restrict__ masks, *__restrict__ visited;
+    __device__ bool operator()(uint64_t i) const { return !mask_is_junction(masks[i]) && !visited[i]; }
+};
 
-__global__ void k_compact_candidates(const uint64_t *__restrict__ flag_scan, const uint8_t *__restrict__ masks,
-                                     const uint8_t *__restrict__ visited, uint64_t n, uint64_t *__restrict__ idx) {
-    const uint64_t i = BBK_GID();
-    if (i >= n) return;
-    if (!mask_is_junction(masks[i]) && !visited[i]) idx[flag_scan[i]] = i;
-}
+struct StoreIndex {
+    uint64_t *__restrict__ idx;
+    __device__ void operator()(uint64_t i, uint64_t rank) const { idx[rank] = i; }
+};
 
 // unitigs -> packed reads (bbk_unitigs_to_reads): words per unitig, then one wavefront per unitig packs 32 bases per lane
 __global__ void k_unitig_words(const uint64_t *__restrict__ uoff, uint64_t nu, uint64_t *__restrict__ nw,
@@ -449,18 +447,14 @@ static Paths walk_paths(bbk_ctx *ctx, const bbk_extindex *x, StartEdges S) {
 }
 
 struct LoopCandidates {
-    DevBuf flag;      // [n] exclusive scan of "non-junction k-mer no path went through"
-    uint64_t NC = 0;  // how many: 0 = no perfect loops
+    PerItem<LoopCandidate> is;  // the test, over masks and Paths::visited
+    Selection sel;              // sel.kept: how many; 0 = no perfect loops.  sel.base: n / 256 tile bases
 };
 
-// live: the paths, flag
+// live: the paths, sel
 static LoopCandidates loop_candidates(bbk_ctx *ctx, const bbk_extindex *x, const Paths &P) {
-    const uint64_t n = x->n;
-    LoopCandidates C;
-    C.flag.alloc((n + 1) * 8);
-    launch_items(ctx, "k_loop_candidates", k_loop_candidates, n, x->masks.as<uint8_t>(), P.visited.as<uint8_t>(), n,
-                 C.flag.as<uint64_t>());
-    C.NC = exclusive_scan_u64(ctx, C.flag.as<uint64_t>(), C.flag.as<uint64_t>(), n);
+    LoopCandidates C{per_item(LoopCandidate{x->masks.as<uint8_t>(), P.visited.as<uint8_t>()}), {}};
+    C.sel = select_count(ctx, "loop_candidates", x->n, C.is);
     return C;
 }
 
@@ -469,7 +463,7 @@ struct SortedRecs {
     DevBuf rtmp, itmp;  // the sort's other halves: they stay as long as ids does, as they always have
 };
 
-// live: the paths, flag, ids, rtmp, itmp
+// live: the paths, sel, ids, rtmp, itmp
 static SortedRecs sort_link_records(bbk_ctx *ctx, uint64_t n, Paths &P) {
     const uint64_t NU = P.NU;
     SortedRecs S;
@@ -489,7 +483,7 @@ static SortedRecs sort_link_records(bbk_ctx *ctx, uint64_t n, Paths &P) {
 }
 
 // No perfect loops: vertices and links from the sorted records, and the result stays on the device (host copies are
-// made on demand, ensure_host).  live: the paths, flag, the sorted records, lcnt, nv, dl
+// made on demand, ensure_host).  live: the paths, sel, the sorted records, lcnt, nv, dl
 static void links_on_device(bbk_ctx *ctx, Paths &P, const SortedRecs &S, bbk_unitigs &U) {
     const uint64_t NU = P.NU;
     KernelTimer t(ctx, "links", 0);
@@ -515,7 +509,7 @@ static void links_on_device(bbk_ctx *ctx, Paths &P, const SortedRecs &S, bbk_uni
     U.d_links = std::move(dl);
 }
 
-// Perfect loops are appended on the host: the paths come over first.  live: the paths, flag
+// Perfect loops are appended on the host: the paths come over first.  live: the paths, sel
 static void paths_to_host(bbk_ctx *ctx, const Paths &P, bbk_unitigs &U) {
     U.bases.resize(P.NB);
     U.offsets.resize(P.NU + 1);
@@ -523,7 +517,7 @@ static void paths_to_host(bbk_ctx *ctx, const Paths &P, bbk_unitigs &U) {
     d2h_big(ctx, U.offsets.data(), P.uoff.p, (P.NU + 1) * 8);
 }
 
-// the sorted link records without the "no record" entries at their end.  live: the paths, flag, the sorted records
+// the sorted link records without the "no record" entries at their end.  live: the paths, sel, the sorted records
 static std::vector<LinkRec> link_records_to_host(bbk_ctx *ctx, uint64_t n, Paths &P) {
     const uint64_t NU = P.NU;
     const SortedRecs S = sort_link_records(ctx, n, P);
@@ -541,17 +535,15 @@ static std::vector<LinkRec> link_records_to_host(bbk_ctx *ctx, uint64_t n, Paths
 }
 
 // The leftover non-junction k-mers with their masks, and the order CollectLoops visits them in.
-// live: visited, flag, cidx, and for a moment gk, gm, gb (rec, uoff and bases are gone by now)
-static LoopTable load_loop_table(bbk_ctx *ctx, const bbk_extindex *x, const LoopCandidates &C, const Paths &P,
-                                 unsigned ref_threads) {
-    const uint64_t n = x->n, NC = C.NC;
+// live: visited, sel, cidx, and for a moment gk, gm, gb (rec, uoff and bases are gone by now)
+static LoopTable load_loop_table(bbk_ctx *ctx, const bbk_extindex *x, const LoopCandidates &C, unsigned ref_threads) {
+    const uint64_t NC = C.sel.kept;
     LoopTable T;
     T.k = (int)x->k;
     T.W = (int)x->W;
     T.idx.resize(NC);
     DevBuf cidx(NC * 8 + 16);
-    launch_items(ctx, "k_compact_candidates", k_compact_candidates, n, C.flag.as<uint64_t>(), x->masks.as<uint8_t>(),
-                 P.visited.as<uint8_t>(), n, cidx.as<uint64_t>());
+    select_write(ctx, "loop_candidates", C.sel, C.is, StoreIndex{cidx.as<uint64_t>()});
     d2h_big(ctx, T.idx.data(), cidx.p, NC * 8);
     T.keys.resize(NC * T.W);
     T.masks.resize(NC);
@@ -719,18 +711,18 @@ static void build(bbk_ctx *ctx, const bbk_extindex *x, bbk_unitigs &U, unsigned 
     }
     Paths P = walk_paths(ctx, x, start_edges(ctx, x));
     const LoopCandidates C = loop_candidates(ctx, x, P);
-    if (C.NC == 0 && P.NU != 0) {  // the common case: no perfect loops, links are made on the device
+    if (C.sel.kept == 0 && P.NU != 0) {  // the common case: no perfect loops, links are made on the device
         const SortedRecs S = sort_link_records(ctx, n, P);
         links_on_device(ctx, P, S, U);
     } else {
-        if (C.NC) paths_to_host(ctx, P, U);
+        if (C.sel.kept) paths_to_host(ctx, P, U);
         std::vector<LinkRec> recs;
         if (P.NU) recs = link_records_to_host(ctx, n, P);
-        P.rec.release();  // the device is done with the paths; the loop walk keeps visited and flag
+        P.rec.release();  // the device is done with the paths; the loop walk keeps visited and sel
         P.uoff.release();
         P.bases.release();
-        if (C.NC) {
-            LoopTable T = load_loop_table(ctx, x, C, P, ref_threads);
+        if (C.sel.kept) {
+            LoopTable T = load_loop_table(ctx, x, C, ref_threads);
             collect_loops_on_host(T, U, recs);
         }
         U.n = P.NU + U.n_loops;

@@ -3,8 +3,8 @@ CPU that the cases hold the classes they claim and tell wrong selections apart).
 
 Abundance (k_ab_collect<W>, k_ab_reduce<TWO>): profiles the test writes itself and loads with kmerprofile_load, in all
 four key widths and at both sides of every word boundary; every integer equals the restatement.  Join
-(k_kp_sample_flag/compact, k_kp_scatter, k_kp_keep, k_kp_compact): samples made with kmerset_from_device from counts at
-ci, cs and the 16- and 32-bit limits.  Both look keys up through table_find over a PrefixIndex: tables of 1, 2 and 129
+(the per-sample selection on counts >= ci, k_kp_scatter, k_kp_keep and the selection on its keep byte): samples made
+with kmerset_from_device from counts at ci, cs and the 16- and 32-bit limits.  Both look keys up through table_find over a PrefixIndex: tables of 1, 2 and 129
 keys, one whose keys share a single bin, and 64-bit table entries (BBK_WIDE_INDEX)."""
 import os
 import subprocess

@@ -1,5 +1,5 @@
 """GPU: Counter.finish(min_count) (bbk_count_finish_min_count) against numpy on the unfiltered result of
-the same reads and flags -- keys, counts, stored order and n_dropped -- at set sizes around the tile of k_mc_count, with
+the same reads and flags -- keys, counts, stored order and n_dropped -- at set sizes around the tile of the selection, with
 kept and dropped records alternating, for every key width and every order flag.  Bit-exact: integer work."""
 import numpy as np
 import pytest
@@ -9,7 +9,7 @@ from tests.helpers import rc
 
 pytestmark = pytest.mark.gpu
 
-T = 256  # the tile of k_mc_count (kmerfilter.hip: kMcTile): distinct canonical records, the filter's input
+T = 256  # the tile of the ordered selection (select.h: kSelTile): distinct canonical records, the filter's input
 SIZES = (0, 1, T - 1, T, T + 1, 3 * T + 5)
 MIN_COUNTS = (0, 1, 2, 3, 2 ** 32 - 1)
 FLAGS = {"both": B.BOTH_STRANDS, "canonical": B.CANONICAL, "both_ref": B.BOTH_STRANDS | B.REFERENCE_ORDER}

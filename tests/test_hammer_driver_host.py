@@ -12,7 +12,17 @@ from spades_for_blackbird_amd import build, build_host, engine
 from tests import fastq_restated as FR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-KERNELS = ("k_mc_count", "k_mc_write")
+# kmerfilter.o's kernels: its instantiations of the ordered selection (select.h), as kernel<first template argument: the
+# predicate> -- the count of the filter and the count-only selection of the dropped self-complementary records -- and the
+# filter's own write kernel
+KERNELS = ("k_select_count<McKept>", "k_select_count<McDroppedSelfRc>", "k_mc_write")
+
+
+def is_kernel(kname, mangled):
+    """the mangled name is an instantiation of `kname` (kernel<Predicate> or kernel) for some key width"""
+    kernel, _, pred = kname.rstrip(">").partition("<")
+    head = "%d%sI" % (len(kernel), kernel)
+    return (head + "NS_%d%sILi" % (len(pred), pred) if pred else head + "Li") in mangled
 
 
 @pytest.fixture(scope="module")
@@ -139,7 +149,7 @@ def test_kernels_use_no_scratch():
         return
     mine = [r for r in res if r[0] == "kmerfilter.o"]
     for kname in KERNELS:  # one instantiation per key width
-        rows = [r for r in mine if kname in r[1]]
+        rows = [r for r in mine if is_kernel(kname, r[1])]
         assert len(rows) == 4, (kname, [r[1] for r in mine])
         assert all(r[2:] == (0, 0, 0) for r in rows), rows  # scratch bytes, SGPR spills, VGPR spills
     assert len(mine) == 4 * len(KERNELS), [r[1] for r in mine]

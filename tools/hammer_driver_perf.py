@@ -9,8 +9,9 @@ of 150 bases with 1 % substitutions written as one FASTQ file, k = 21.
             the same single-read library, both once more with the singleton filter (count_filter_singletons 1 /
             --filter-singletons): the four alternate run by run, one warm-up each and then --repeats runs, every run under
             its own time limit; spades-hammer and spades-kmerdata must write the same bytes.
-  registers VGPRs and SGPRs of the k_mc_* kernels from the code-object metadata of kmerfilter.o where the object is at
-            hand (--registers-only prints them and stops: no GPU needed).
+  registers VGPRs and SGPRs of the filter's kernels (k_select_count of select.h over kmerfilter.hip's predicates, and
+            k_mc_write) from the code-object metadata of kmerfilter.o where the object is at hand
+            (--registers-only prints them and stops: no GPU needed).
 Prints one JSON line and, with --out-dir, writes hammer_driver_perf_<reads>k_k21.json there.
 
     python tools/hammer_driver_perf.py [--reads 200000] [--repeats 5] [--out-dir profiles/hammer_driver]
@@ -33,7 +34,7 @@ from spades_for_blackbird_amd import build  # noqa: E402
 from tools.hreads_perf import make_input, med  # noqa: E402
 from tools.readprint_perf import write_fastq  # noqa: E402
 
-KERNELS = ("k_mc_count", "k_mc_write")
+KERNELS = ("k_mc_count", "k_mc_write")  # the timing families of the filter's count and write
 
 
 def registers():
@@ -52,7 +53,7 @@ def registers():
                 continue
             notes = subprocess.run([readelf, "--notes", os.path.join(d, f)], capture_output=True, text=True, check=True).stdout
             for block in notes.split("- .agpr_count:")[1:]:
-                name = re.search(r"\.name:\s+(\S*k_mc_\S+)", block)
+                name = re.search(r"\.name:\s+(\S*k_(?:select|mc)_\S+)", block)
                 v, s = re.search(r"\.vgpr_count:\s+(\d+)", block), re.search(r"\.sgpr_count:\s+(\d+)", block)
                 if name and v and s:
                     out[name.group(1)] = {"vgpr": int(v.group(1)), "sgpr": int(s.group(1))}
