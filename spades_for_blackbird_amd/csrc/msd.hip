@@ -704,7 +704,7 @@ struct MsdRunner {
         // buckets and from the overflow path's dense keys
         void level1_late_tag(BucketView &v) {
             constexpr uint32_t kpt = (uint32_t)kLtThreads * kLt1Items / 2;
-            const size_t lds = lt_smem(kLt1Items, (size_t)kViewSpan * (4 + 2));
+            const size_t lds = lt_smem(kLt1Items, lt_view_tables());
             ctx->add_stat("stat_late_tag", (double)N);
             const auto [vdesc, nt] = view_tiles(v, kpt);
             if (nt)

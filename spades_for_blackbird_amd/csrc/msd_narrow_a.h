@@ -3,6 +3,8 @@
 // and compact (msd.hip) when Plan::narrow is set.
 #pragma once
 
+#include "msd_mark_tail.h"
+
 namespace bbk {
 
 // ---- narrow records (stage A, 17 <= k <= 21) ---------------------------------------------------------------
@@ -51,7 +53,7 @@ constexpr int kNwThreads = 1024;
 #endif
 constexpr int kNwRounds = BBK_NW_ROUNDS;  // consecutive chunks of 8 k-mer positions per lane (the last 64 lanes of a full tile idle)
 constexpr int kNwChunks = BBK_NW_CHUNKS;  // chunks of a level-1 tile: 15360 records = 60 KB staged, runs of ~15 per bin;
-                                  // (x 8 records) with the tables 77 KB of LDS: two workgroups per CU
+                                  // (x 8 records) with the tables 78 KB of LDS: two workgroups per CU
 // with a payload (one mask byte per record: the extension index) the same tile would take 94 KB = ONE workgroup per CU
 // (measured 8.4 ms against 3.8 ms without payload); 1536 chunks = 12 288 records x 5 bytes + tables = 78 KB
 template <bool HAS_VAL>
@@ -198,8 +200,8 @@ __device__ __forceinline__ void nw_extract(const ReadSrc &S, const PartLevel &L,
 // Level 1: fused extraction + partition into 1024 segments.  The bin of a staged record cannot be recomputed from lo
 // alone, and a per-record side array would cost as much LDS as the stage itself: the staged order is bin-major, so
 // one bit per position marks where a non-empty bin starts and the r-th non-empty bin owns position pos when
-// r = #marks at or before pos - 1 (a 64-position word of marks is exactly what a wave handles per step).  What a
-// store needs of its bin -- global offset and room left in the slot -- sits in one 8-byte entry indexed by r.
+// r = #marks below pos (a 64-position word of marks is exactly what a wave handles per step).  What a store needs
+// of its bin sits in one 8-byte entry indexed by r.  The tail is msd_mark_tail.h's, shared with stage B's late tag.
 template <bool HAS_VAL>
 __global__ __launch_bounds__(kNwThreads) __attribute__((amdgpu_waves_per_eu(BBK_NW_WAVES, BBK_NW_WAVES))) void k_part_reads_narrow(ReadSrc S, PartLevel L, uint32_t ntiles,
                                                                  const RdTile *__restrict__ tiles_arg,  // = S.tiles: as an
@@ -207,22 +209,14 @@ __global__ __launch_bounds__(kNwThreads) __attribute__((amdgpu_waves_per_eu(BBK_
                                                                  uint32_t *__restrict__ cursor,
                                                                  uint32_t *__restrict__ out, uint32_t *__restrict__ vout) {
     constexpr int NT = kNwThreads, CH = 8, MAXB = kNwBins1, ITEMS = CH * NwCfg<HAS_VAL>::ROUNDS;
-    constexpr int MW = NwCfg<HAS_VAL>::TILE / 64;  // 64-bit mark words
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);                   // counts; later, with the next array:
-    uint2 *tab = reinterpret_cast<uint2 *>(smem);                           // r -> (global offset - staged start, limit)
-    uint32_t *lstart = lhist + 2 * MAXB;
-    uint32_t *scan_tmp = lstart + MAXB;                                     // 64 entries
-    unsigned long long *mark = reinterpret_cast<unsigned long long *>(scan_tmp + 64);  // MW words
-    uint16_t *mbase = reinterpret_cast<uint16_t *>(mark + MW);              // marks before every word
-    uint16_t *nz = mbase + MW;                                              // r-th non-empty bin
-    unsigned char *U = reinterpret_cast<unsigned char *>(nz + MAXB);
+    const MarkLds ML = mark_lds<NwCfg<HAS_VAL>::TILE>(smem);  // counts, table, marks | then the read tables, later the stage
+    uint32_t *lhist = ML.lhist;
+    unsigned char *U = reinterpret_cast<unsigned char *>(ML.stage);
     int32_t *s_rel = reinterpret_cast<int32_t *>(U);
     int32_t *s_wrel = s_rel + (kRdSlots + 2);
     uint32_t *s_len = reinterpret_cast<uint32_t *>(s_wrel + (kRdSlots + 2));
     uint64_t *s_words = reinterpret_cast<uint64_t *>(s_len + (kRdSlots + 2));
-    uint32_t *stage = reinterpret_cast<uint32_t *>(U);
-    uint8_t *vstage = reinterpret_cast<uint8_t *>(stage + NwCfg<HAS_VAL>::TILE);  // payloads of this path are 8 mask bits
 
     uint32_t tid = threadIdx.x;
     const uint32_t k_ = (uint32_t)S.k;
@@ -277,7 +271,6 @@ __global__ __launch_bounds__(kNwThreads) __attribute__((amdgpu_waves_per_eu(BBK_
         // it -- 16 stage positions, table slots ... -- once before the loop and keeps ~45 registers alive through it,
         // which is one workgroup per CU instead of two)
         asm volatile("" : "+v"(tid));
-        const int lane = tid & 63, wave = tid >> 6;
         const uint32_t tile_next = tile + gridDim.x;
         const bool more = tile_next < ntiles;  // uniform: every wave of the workgroup leaves the loop together
         RdTile Tn = T;
@@ -289,8 +282,7 @@ __global__ __launch_bounds__(kNwThreads) __attribute__((amdgpu_waves_per_eu(BBK_
         const uint32_t r0 = T.r0, nr = T.nr;
         const uint64_t wbase = T.wbase;
         const bool fast = staged_ok(T);
-        lhist[tid] = 0;  // NT == MAXB
-        if (tid < 2 * MW) reinterpret_cast<uint32_t *>(mark)[tid] = 0u;
+        mark_clear<NwCfg<HAS_VAL>::TILE>(ML, tid);  // NT == MAXB
         if (fast) {  // (a staged tile's reads lie inside its window of words: k_tile_reads)
             if (tid <= nr) s_rel[tid] = (int32_t)(int64_t)(Q.coff - c0);
             if (tid < nr) {
@@ -311,104 +303,22 @@ __global__ __launch_bounds__(kNwThreads) __attribute__((amdgpu_waves_per_eu(BBK_
         __syncthreads();  // histogram complete; the read tables may be overwritten by the stage
         BBK_PH(5, 1, t_prev);  // extraction + LDS ranking
 
-        // scan of the 1024 bin counts (one bin per thread) and of the non-empty flags; reservation of the tile's run
-        const uint32_t c = lhist[tid];
-        uint32_t incl = c;
-        incl = wave_scan_incl(incl);
-        const unsigned long long nzb = __ballot(c != 0);
-        if (lane == 63) scan_tmp[wave] = incl | ((uint32_t)__popcll(nzb) << 16);  // records < 2^16, non-empty bins <= 1024
-        __syncthreads();
-        uint32_t before, total;
-        wave_totals<NT / 64>(scan_tmp, lane, wave, before, total);
-        const uint32_t staged = total & 0xFFFFu;
-        const uint32_t ex = (before & 0xFFFFu) + incl - c;
-        const uint32_t myr = (before >> 16) + (uint32_t)__popcll(nzb & ((1ull << lane) - 1ull));
-        lstart[tid] = ex;
-        uint32_t greserve = 0;
-        if (c) {
-            greserve = atomicAdd(&cursor[(tid << L.xcd_shift) + xcc], c);
-            nz[myr] = (uint16_t)tid;
-            atomicOr(&mark[ex >> 6], 1ull << (ex & 63u));
-        }
-        __syncthreads();  // (every thread has read its count: lhist may become the table)
-        BBK_PH(5, 2, t_prev);  // scans + reservation issue + marks
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            const int r = i / CH, j = i % CH;
-            if ((uint32_t)j < ((cnts >> (4 * r)) & 15u)) {
-                const uint32_t bin = (bins[r * 3 + j / 3] >> (10 * (j % 3))) & 1023u;
-                const uint32_t pos = atomicAdd(&lstart[bin], 1u);  // (lstart ends as the bins' end offsets; nothing reads it again)
-                stage[pos] = lo[i];
-                if (HAS_VAL) vstage[pos] = (uint8_t)(masks[r * 2 + (j >> 2)] >> (8 * (j & 3)));
-            }
-        }
-        asm volatile("" : "+v"(greserve));  // awaited by every lane here, not inside the store loop's conditional blocks
-        if (c) {
-            // first staged position of this bin that no longer fits its slot
-            const uint64_t slot_end = L.xcd_shift ? (uint64_t)tid * L.slot_stride + (uint64_t)(xcc + 1u) * L.sub_cap
-                                                  : (uint64_t)tid * L.slot_stride + L.slot_cap;
-            const int64_t room = (int64_t)slot_end - (int64_t)greserve;
-            tab[myr] = make_uint2(greserve - ex,
-                                  (uint32_t)(int32_t)(room < -(int64_t)0x7FFF0000 ? -(int64_t)0x7FFF0000 : room) + ex);
-        }
-        if (wave == 0) {  // marks before every 64-position word: lane l owns words WPL*l .. WPL*l + WPL-1
-            constexpr int WPL = (MW + 63) / 64;
-            uint32_t pw[WPL], tot = 0;
-#pragma unroll
-            for (int j = 0; j < WPL; ++j) {
-                const int idx = lane * WPL + j;
-                pw[j] = tot;
-                tot += idx < MW ? (uint32_t)__popcll(mark[idx]) : 0u;
-            }
-            uint32_t inc2 = tot;
-            inc2 = wave_scan_incl(inc2);
-            const uint32_t lb = inc2 - tot;
-#pragma unroll
-            for (int j = 0; j < WPL; ++j) {
-                const int idx = lane * WPL + j;
-                if (idx < MW) mbase[idx] = (uint16_t)(lb + pw[j]);
-            }
-        }
-        __syncthreads();
-        BBK_PH(5, 3, t_prev);  // reorder into LDS + mark prefix
-        if (more) prefetch(Tn, Q);  // in flight during the stores below
-        else Q = Pre{0, 0, 0, 0, 0};   // (the old values end here either way: they must not stay alive through the loop)
-        const unsigned long long upto = (2ull << lane) - 1ull;  // this lane and the ones below
-        // pos = i * NT + tid: the 64 lanes of a wave cover mark word i * (NT / 64) + wave
-        const unsigned long long *wmark = mark + wave;
-        const uint16_t *wmbase = mbase + wave;
-        uint32_t full = 0;  // items whose slot is full (rare; handled after the stores so that no atomic sits between them)
-#pragma unroll
-        for (int i = 0; i < ITEMS; ++i) {
-            const uint32_t pos = (uint32_t)i * NT + tid;
-            if (pos < staged) {
-                const uint32_t r = (uint32_t)wmbase[i * (NT / 64)] + (uint32_t)__popcll(wmark[i * (NT / 64)] & upto) - 1u;
-                unsigned long long e = reinterpret_cast<const unsigned long long *>(tab)[r];
-                const uint32_t rec = stage[pos];
-                asm volatile("" : "+v"(e));  // one 8-byte LDS read (otherwise: the limit, a branch, then the offset)
-                if ((int32_t)pos >= (int32_t)(uint32_t)(e >> 32)) {
-                    full |= 1u << i;
-                } else {
-                    const uint32_t g = (uint32_t)e + pos;
-                    out[g] = rec;
-                    if (HAS_VAL) vout[g] = vstage[pos];
-                }
-            }
-        }
-        if (full) {
-#pragma unroll 1
-            for (int i = 0; i < ITEMS; ++i) {
-                if ((full >> i) & 1u) {
-                    const uint32_t pos = (uint32_t)i * NT + tid;
-                    const uint32_t r = (uint32_t)wmbase[i * (NT / 64)] + (uint32_t)__popcll(wmark[i * (NT / 64)] & upto) - 1u;
-                    const uint32_t sp = atomicAdd(L.spill_count, 1u);
-                    if (sp < L.spill_cap) {
-                        reinterpret_cast<uint64_t *>(L.spill_keys)[sp] = nw_key(nz[r], stage[pos], hb);
-                        if (HAS_VAL) L.spill_vals[sp] = vstage[pos];
-                    }
-                }
-            }
-        }
+        // scan, reservation, reorder, mark prefix, stores and spills: the shared tail (msd_mark_tail.h)
+        const uint64_t slot_end = L.xcd_shift ? (uint64_t)tid * L.slot_stride + (uint64_t)(xcc + 1u) * L.sub_cap
+                                              : (uint64_t)tid * L.slot_stride + L.slot_cap;
+        mark_tail<NwCfg<HAS_VAL>::TILE, ITEMS, HAS_VAL>(
+            ML, lo, tid, (uint32_t)MAXB, &cursor[(tid << L.xcd_shift) + xcc], slot_end, 0u, L, out, vout,
+            [&](int i) {
+                const int r = i / CH, j = i % CH;
+                return (uint32_t)j < ((cnts >> (4 * r)) & 15u) ? (bins[r * 3 + j / 3] >> (10 * (j % 3))) & 1023u : 0xFFFFFFFFu;
+            },
+            [&](int i) { return masks[(i / CH) * 2 + ((i % CH) >> 2)] >> (8 * (i & 3)); },
+            [&](uint32_t bin, uint32_t rec) { return nw_key(bin, rec, hb); },
+            [&]() {
+                BBK_PH(5, 3, t_prev);  // scans + reservation + reorder into LDS + mark prefix
+                if (more) prefetch(Tn, Q);  // in flight during the stores
+                else Q = Pre{0, 0, 0, 0, 0};   // (the old values end here either way: they must not stay alive through the loop)
+            });
         BBK_PH(5, 4, t_prev);  // store issue
 #ifdef BBK_PHASE_PROF
         if (threadIdx.x == 0) atomicAdd(&g_phase[5][7], 1ull);
@@ -424,8 +334,7 @@ static size_t part_reads_narrow_smem(bool has_val) {
     const size_t tables = sizeof(uint32_t) * 3 * (kRdSlots + 2) + sizeof(uint64_t) * (kRdWords + 1 + 2);
     const size_t tile = has_val ? NwCfg<true>::TILE : NwCfg<false>::TILE;
     const size_t stage = tile * (has_val ? 5 : 4);
-    const size_t fixed = sizeof(uint32_t) * (3 * kNwBins1 + 64) + (tile / 64) * (8 + 2) + (size_t)kNwBins1 * 2;
-    return fixed + std::max(tables, stage);
+    return mark_smem(tile) + std::max(tables, stage);
 }
 
 // Level 2: one tile (<= 16384 records) of one segment -> the bucket slots of that segment.  Everything derives from lo.

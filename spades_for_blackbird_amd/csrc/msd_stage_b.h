@@ -428,37 +428,19 @@ __global__ void k_view_recanon(const uint64_t *__restrict__ in, const uint32_t *
 // marks where a non-empty bin starts, and what a store needs of its bin is one 8-byte LDS entry -- the bin of a
 // staged record (ten dropped bits at level 1, a hash at level 2) is never computed twice.
 constexpr int kLtThreads = 1024;  // == kMaxBins: one bin per thread in the scans
-// records per lane.  Level 1: 14 336 records = 56 KB staged, 73 KB of LDS with the tables: two workgroups per CU (16
-// records per lane would be 81.1 KB, one workgroup); a (tile, bin) run is 14 records = 56 bytes.  Level 2: as
+// records per lane.  Level 1: 14 336 records = 56 KB staged, 76 KB of LDS with the tables: two workgroups per CU (16
+// records per lane would be 84 KB, one workgroup); a (tile, bin) run is 14 records = 56 bytes.  Level 2: as
 // k_part_narrow2.
 constexpr int kLt1Items = 14;
 constexpr int kLt2Items = 12;
 
-struct LtLds {
-    uint32_t *lhist;           // counts; later, with the 4 KB behind it:
-    uint2 *tab;                // r -> (global offset - staged start, first staged position past the slot)
-    uint32_t *lstart, *scan_tmp;
-    unsigned long long *mark;  // bit per staged position: a non-empty bin starts here
-    uint16_t *mbase, *nz;      // marks before every 64-position word; the r-th non-empty bin
-    uint32_t *stage;
-};
-template <int ITEMS>
-__device__ __forceinline__ LtLds lt_lds(unsigned char *smem) {
-    constexpr int MW = kLtThreads * ITEMS / 64;
-    LtLds S;
-    S.lhist = reinterpret_cast<uint32_t *>(smem);
-    S.tab = reinterpret_cast<uint2 *>(smem);
-    S.lstart = S.lhist + 2 * kMaxBins;
-    S.scan_tmp = S.lstart + kMaxBins;
-    S.mark = reinterpret_cast<unsigned long long *>(S.scan_tmp + 64);
-    S.mbase = reinterpret_cast<uint16_t *>(S.mark + MW);
-    S.nz = S.mbase + MW;
-    S.stage = reinterpret_cast<uint32_t *>(S.nz + kMaxBins);
-    return S;
-}
 static size_t lt_smem(int items, size_t more) {
     const size_t tile = (size_t)kLtThreads * items;
-    return sizeof(uint32_t) * (3 * kMaxBins + 64) + (tile / 64) * (8 + 2) + (size_t)kMaxBins * 2 + tile * 4 + more;
+    return mark_smem(tile) + tile * 4 + more;
+}
+// what k_part_view_lt keeps of its tile's buckets behind the stage: a word of marks per 64 keys, an entry per bucket
+static size_t lt_view_tables() {
+    return ((size_t)kLtThreads * kLt1Items / 2 / 64) * sizeof(MarkWord) + (size_t)kViewSpan * sizeof(uint2);
 }
 
 // the tagged key of (segment, lo): what the spill list and the give-up path need
@@ -468,95 +450,11 @@ __device__ inline uint64_t lt_tagged(uint32_t seg, uint32_t lo, int lobits, int 
     return x.w[0] | (__umul64hi(xxh3_64<1>(x), 16ull) << (2 * k));
 }
 
-// On entry lhist[b] = records of bin b in this tile (counted, not ranked), lo[i] / bin of item i (two bins per register,
-// 0xFFFF: no record).  cur / slot_end: cursor and end of the slot of bin `tid`.  The stored record is lo | rec_or.
-template <int ITEMS, class KeyOf>
-__device__ __forceinline__ void lt_tail(const LtLds &S, const uint32_t (&lo)[ITEMS], const uint32_t (&bins)[ITEMS / 2],
-                                        uint32_t nb, uint32_t *__restrict__ cur, uint64_t slot_end, uint32_t rec_or,
-                                        const PartLevel &L, uint32_t *__restrict__ out, KeyOf key_of) {
-    constexpr int NT = kLtThreads, MW = NT * ITEMS / 64;
-    static_assert(ITEMS % 2 == 0 && ITEMS <= 32 && NT * ITEMS < 65536, "packed bins, one bit per item, 16-bit positions");
-    const uint32_t tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint32_t c = tid < nb ? S.lhist[tid] : 0u;
-    uint32_t incl = c;
-    incl = wave_scan_incl(incl);
-    const unsigned long long nzb = __ballot(c != 0);
-    if (lane == 63) S.scan_tmp[wave] = incl | ((uint32_t)__popcll(nzb) << 16);
-    __syncthreads();
-    uint32_t before, total;
-    wave_totals<NT / 64>(S.scan_tmp, lane, wave, before, total);
-    const uint32_t staged = total & 0xFFFFu;
-    const uint32_t ex = (before & 0xFFFFu) + incl - c;
-    const uint32_t myr = (before >> 16) + (uint32_t)__popcll(nzb & ((1ull << lane) - 1ull));
-    S.lstart[tid] = ex;
-    uint32_t greserve = 0;
-    if (c) {
-        greserve = atomicAdd(cur, c);  // issued now, consumed after the LDS reorder
-        S.nz[myr] = (uint16_t)tid;
-        atomicOr(&S.mark[ex >> 6], 1ull << (ex & 63u));
-    }
-    __syncthreads();  // (every thread has read its count: lhist may become the table)
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t bin = (bins[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-        if (bin != 0xFFFFu) {
-            const uint32_t pos = atomicAdd(&S.lstart[bin], 1u);  // (lstart ends as the bins' end offsets; nothing reads it again)
-            S.stage[pos] = lo[i];
-        }
-    }
-    asm volatile("" : "+v"(greserve));  // awaited by every lane here, not inside the store loop's conditional blocks
-    if (c) {
-        const int64_t room = (int64_t)slot_end - (int64_t)greserve;
-        S.tab[myr] = make_uint2(greserve - ex, (uint32_t)(int32_t)(room < -(int64_t)0x7FFF0000 ? -(int64_t)0x7FFF0000 : room) + ex);
-    }
-    if (wave == 0) {  // marks before every 64-position word: lane l owns words WPL*l .. WPL*l + WPL-1
-        constexpr int WPL = (MW + 63) / 64;
-        uint32_t pw[WPL], tot = 0;
-#pragma unroll
-        for (int j = 0; j < WPL; ++j) {
-            const int idx = lane * WPL + j;
-            pw[j] = tot;
-            tot += idx < MW ? (uint32_t)__popcll(S.mark[idx]) : 0u;
-        }
-        uint32_t inc2 = tot;
-        inc2 = wave_scan_incl(inc2);
-        const uint32_t lb = inc2 - tot;
-#pragma unroll
-        for (int j = 0; j < WPL; ++j) {
-            const int idx = lane * WPL + j;
-            if (idx < MW) S.mbase[idx] = (uint16_t)(lb + pw[j]);
-        }
-    }
-    __syncthreads();
-    const unsigned long long upto = (2ull << lane) - 1ull;  // this lane and the ones below
-    // pos = i * NT + tid: the 64 lanes of a wave cover mark word i * (NT / 64) + wave
-    const unsigned long long *wmark = S.mark + wave;
-    const uint16_t *wmbase = S.mbase + wave;
-    uint32_t full = 0;  // items whose slot is full (rare; handled after the stores so that no atomic sits between them)
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t pos = (uint32_t)i * NT + tid;
-        if (pos < staged) {
-            const uint32_t r = (uint32_t)wmbase[i * (NT / 64)] + (uint32_t)__popcll(wmark[i * (NT / 64)] & upto) - 1u;
-            unsigned long long e = reinterpret_cast<const unsigned long long *>(S.tab)[r];
-            const uint32_t rec = S.stage[pos];
-            asm volatile("" : "+v"(e));  // one 8-byte LDS read (otherwise: the limit, a branch, then the offset)
-            if ((int32_t)pos >= (int32_t)(uint32_t)(e >> 32)) full |= 1u << i;
-            else out[(uint32_t)e + pos] = rec | rec_or;
-        }
-    }
-    if (full) {
-#pragma unroll 1
-        for (int i = 0; i < ITEMS; ++i) {
-            if ((full >> i) & 1u) {
-                const uint32_t pos = (uint32_t)i * NT + tid;
-                const uint32_t r = (uint32_t)wmbase[i * (NT / 64)] + (uint32_t)__popcll(wmark[i * (NT / 64)] & upto) - 1u;
-                const uint32_t sp = atomicAdd(L.spill_count, 1u);
-                if (sp < L.spill_cap) reinterpret_cast<uint64_t *>(L.spill_keys)[sp] = key_of((uint32_t)S.nz[r], S.stage[pos]);
-            }
-        }
-    }
+// bin of item i of a lane: two 16-bit bins per register, 0xFFFF = no record
+template <int ITEMS>
+__device__ __forceinline__ uint32_t lt_bin(const uint32_t (&bins)[ITEMS / 2], int i) {
+    const uint32_t bin = (bins[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+    return bin != 0xFFFFu ? bin : 0xFFFFFFFFu;
 }
 
 // Level 1.  Tile t covers the canonical keys [t * KPT, (t + 1) * KPT) of the view's dense order (DENSE: of a key array,
@@ -566,11 +464,14 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     const uint32_t *__restrict__ slots, const uint64_t *__restrict__ off, const uint16_t *__restrict__ seg,
     const uint2 *__restrict__ vdesc, uint32_t stride, int hb, const uint64_t *__restrict__ dense, uint64_t nkeys_all, int k,
     PartLevel L, uint32_t *__restrict__ cursor, uint32_t *__restrict__ out) {
-    constexpr int NT = kLtThreads, ITEMS = kLt1Items, KPT = NT * ITEMS / 2, MW = NT * ITEMS / 64;
+    constexpr int NT = kLtThreads, ITEMS = kLt1Items, KPT = NT * ITEMS / 2, VW = KPT / 64;
+    static_assert(KPT % 64 == 0 && VW <= 128, "whole words of marks, two per lane of one wave");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LtLds S = lt_lds<ITEMS>(smem);
-    uint32_t *toff = S.stage + NT * ITEMS;
-    uint16_t *tseg = reinterpret_cast<uint16_t *>(toff + kViewSpan);
+    const MarkLds S = mark_lds<NT * ITEMS>(smem);
+    // the buckets of the tile: a mark where a non-empty one starts among the tile's KPT positions, and the r-th of them
+    // as (first key offset, index in the span | segment << 16) -- what bucket a key lies in is its run's rank
+    MarkWord *vmw = reinterpret_cast<MarkWord *>(S.stage + NT * ITEMS);
+    uint2 *vent = reinterpret_cast<uint2 *>(vmw + VW);
     const uint32_t tid = threadIdx.x;
     uint32_t xcc = 0;  // the XCD this workgroup runs on (placement is for speed only: any value gives a correct result)
     if (L.xcd_shift) {
@@ -589,13 +490,40 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
         b0 = d.x;
         span = d.y - d.x + 1u;
         staged_tab = span <= (uint32_t)kViewSpan;  // uniform
-        if (staged_tab && tid < span) {
-            toff[tid] = (uint32_t)off[b0 + tid];  // key offsets < 2^32: one pass holds fewer records
-            tseg[tid] = seg[b0 + tid];
+        if (staged_tab && tid < 64u) {
+            // Wave 0 alone, ahead of the barrier below: zero, marks, prefixes.  One wave's LDS operations execute in
+            // order, and the fences keep the compiler from moving them across each other.
+            uint64_t o = 0, on = 0;
+            uint32_t sg = 0;
+            if (tid < span) {
+                o = off[b0 + tid];  // key offsets < 2^32: one pass holds fewer records
+                if (tid + 1u < span) on = off[b0 + tid + 1u];
+                sg = seg[b0 + tid];
+            }
+#ifdef BBK_AB_VIEW_SEARCH  // (A/B: every bucket of the span listed, the lanes search the list)
+            (void)on;
+            if (tid < span) vent[tid] = make_uint2((uint32_t)o, tid | (sg << 16));
+#else
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const uint32_t idx = tid * 2u + (uint32_t)j;
+                if (idx < (uint32_t)VW) *reinterpret_cast<uint4 *>(&vmw[idx]) = make_uint4(0u, 0u, 0u, 0u);
+            }
+            __threadfence_block();
+            // (the span's first bucket holds the tile's first key: it is live, starts at 0 and needs no mark)
+            const bool live = tid < span && view_bucket_live(tid, span, o, on);
+            const unsigned long long lv = __ballot(live);
+            if (live) {
+                vent[__popcll(lv & ((1ull << tid) - 1ull))] = make_uint2((uint32_t)o, tid | (sg << 16));
+                const uint32_t start = view_run_start(o, c0);
+                if (start) atomicOr(&reinterpret_cast<uint32_t *>(vmw)[mark_slot32(start)], mark_bit32(start));
+            }
+            __threadfence_block();
+            mark_prefix<VW>(vmw, (int)tid);
+#endif
         }
     }
-    S.lhist[tid] = 0;  // NT == kMaxBins
-    if (tid < 2 * MW) reinterpret_cast<uint32_t *>(S.mark)[tid] = 0u;
+    mark_clear<NT * ITEMS>(S, tid);  // NT == kMaxBins
     __syncthreads();
 
     // all loads first (index clamped into the tile)
@@ -614,15 +542,24 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
             const uint32_t c = (uint32_t)c0 + (cl < nkeys ? cl : nkeys - 1u);
             uint32_t b, base;
             if (staged_tab) {
+#ifdef BBK_AB_VIEW_SEARCH
                 uint32_t i = 0, hi = span;
                 while (hi - i > 1) {
                     const uint32_t mid = (i + hi) >> 1;
-                    if (toff[mid] <= c) i = mid;
+                    if (vent[mid].x <= c) i = mid;
                     else hi = mid;
                 }
-                b = b0 + i;
-                base = toff[i];
-                sg[j] = tseg[i];
+                const uint2 e = vent[i];
+#else
+                // the bucket of key position cl: the rank of its run (cl is NOT clamped here -- the wave's word is
+                // j * 16 + wave for all its lanes; past the tile's last key there is no mark, so such a lane gets the
+                // last bucket, which holds the key it is clamped to)
+                const uint4 m = *reinterpret_cast<const uint4 *>(&vmw[j * (NT / 64) + (int)(tid >> 6)]);
+                const uint2 e = vent[mark_rank(m.x, m.y, m.z, tid & 63u)];
+#endif
+                b = b0 + (e.y & 0xFFFFu);
+                base = e.x;
+                sg[j] = e.y >> 16;
             } else {
                 b = view_bucket(off, b0, b0 + span, c);
                 base = (uint32_t)off[b];
@@ -651,8 +588,10 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     }
     __syncthreads();
     const uint64_t slot_end = (uint64_t)tid * L.slot_stride + (L.xcd_shift ? (uint64_t)(xcc + 1u) * L.sub_cap : (uint64_t)L.slot_cap);
-    lt_tail<ITEMS>(S, lo, bins, (uint32_t)kMaxBins, &cursor[(tid << L.xcd_shift) + xcc], slot_end, 0u, L, out,
-                   [&](uint32_t bin, uint32_t rec) { return lt_tagged(bin, rec, lobits, k); });
+    mark_tail<NT * ITEMS, ITEMS, false>(
+        S, lo, tid, (uint32_t)kMaxBins, &cursor[(tid << L.xcd_shift) + xcc], slot_end, 0u, L, out, nullptr,
+        [&](int i) { return lt_bin<ITEMS>(bins, i); }, [](int) { return 0u; },
+        [&](uint32_t bin, uint32_t rec) { return lt_tagged(bin, rec, lobits, k); }, []() {});
 }
 
 // Level 2: one tile of one segment's sub-slot (k_tile_desc<true>'s descriptors) -> the buckets of that segment.  The
@@ -660,9 +599,9 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
 __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_part_lt2(
     const uint32_t *__restrict__ in, const uint4 *__restrict__ desc, int k, PartLevel L, uint32_t *__restrict__ cursor,
     uint32_t *__restrict__ out) {
-    constexpr int NT = kLtThreads, ITEMS = kLt2Items, MW = NT * ITEMS / 64;
+    constexpr int NT = kLtThreads, ITEMS = kLt2Items;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const LtLds S = lt_lds<ITEMS>(smem);
+    const MarkLds S = mark_lds<NT * ITEMS>(smem);
     const uint32_t tid = threadIdx.x;
     const uint4 d = desc[blockIdx.x];  // first record, records, bins of the segment | segment << 16, flat index of bin 0
     const uint32_t begin = d.x, count = d.y, nb = d.z & 0xFFFFu, sgm = d.z >> 16, gbin0 = d.w;
@@ -670,8 +609,7 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     const int lobits = 2 * k - 10;
     const uint32_t nsub = nb >> 4;
     const uint64_t segbits = (uint64_t)sgm << lobits;
-    S.lhist[tid] = 0;  // NT == kMaxBins
-    if (tid < 2 * MW) reinterpret_cast<uint32_t *>(S.mark)[tid] = 0u;
+    mark_clear<NT * ITEMS>(S, tid);  // NT == kMaxBins
     __syncthreads();
     uint32_t lo[ITEMS], bins[ITEMS / 2];
 #pragma unroll
@@ -695,8 +633,10 @@ __global__ __launch_bounds__(kLtThreads) __attribute__((amdgpu_waves_per_eu(8, 8
     }
     __syncthreads();
     const uint64_t slot_end = (uint64_t)(gbin0 + tid) * L.slot_stride + L.slot_cap;
-    lt_tail<ITEMS>(S, lo, bins, nb, &cursor[gbin0 + tid], slot_end, (uint32_t)segbits, L, out,
-                   [&](uint32_t, uint32_t rec) { return lt_tagged(sgm, rec, lobits, k); });
+    mark_tail<NT * ITEMS, ITEMS, false>(
+        S, lo, tid, nb, &cursor[gbin0 + tid], slot_end, (uint32_t)segbits, L, out, nullptr,
+        [&](int i) { return lt_bin<ITEMS>(bins, i); }, [](int) { return 0u; },
+        [&](uint32_t, uint32_t rec) { return lt_tagged(sgm, rec, lobits, k); }, []() {});
 }
 
 // one thread per bucket g = bin tag * nsub + j of segment s: its smallest tagged key, and its place in the order of the
