@@ -621,8 +621,8 @@ struct MsdRunner {
             BBK_HIP(hipMemcpyAsync(cur1.p, stage, (size_t)nsub * 4, hipMemcpyHostToDevice, ctx->stream));
 
             const uint64_t nA = P.slots ? (uint64_t)nb1 * P.seg_cap : N;  // records bufA holds (slot layout has gaps)
-            bufA.alloc(nA * P.rec_ab);
-            if (has_val) valA.alloc(nA * 4);
+            bufA.alloc(nA * P.rec_ab + 16);  // (+ 16: k_part_narrow2 loads a tile's records four at a time, tile_rows4)
+            if (has_val) valA.alloc(nA * 4 + 16);
             if (P.narrow) {
                 if constexpr (W == 1) {
                     const double pbn = (double)in.rd->n_words * 8 + (double)N * (4 + (has_val ? 4 : 0));
@@ -708,7 +708,7 @@ struct MsdRunner {
             ctx->add_stat("stat_late_tag", (double)N);
             const auto [vdesc, nt] = view_tiles(v, kpt);
             if (nt)
-                R.launch(k_part_view_lt<false>, "k_part_view", (double)v.D * 4 + 2.0 * (double)v.D * 4, nt, kLtThreads, lds,
+                R.launch(k_part_view_lt<false>, "k_part_l1", (double)v.D * 4 + 2.0 * (double)v.D * 4, nt, kLtThreads, lds,
                          v.slots.as<uint32_t>(), v.off.as<uint64_t>(), v.seg.as<uint16_t>(), vdesc.template as<uint2>(),
                          v.stride, v.hb, (const uint64_t *)nullptr, v.D, (int)R.expand_k, L1, cur1.as<uint32_t>(),
                          bufA.as<uint32_t>());
@@ -827,6 +827,18 @@ struct MsdRunner {
                                    : P.narrow   ? (uint32_t)(has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE)
                                                 : kPartTileK;
             for (uint32_t s2 = 0; s2 < nsub; ++s2) tstart[s2 + 1] = tstart[s2] + (hsub[s2] + tile2 - 1) / tile2;
+            if (P.narrow && verbose) {  // the tiles by size: whole ones, and the last one of a sub-slot by the groups of
+                                        // four records per lane (4096 records) it reaches -- what tile_rows4 walks
+                uint32_t whole = 0, part[3] = {0, 0, 0}, largest = 0;
+                for (uint32_t s2 = 0; s2 < nsub; ++s2) {
+                    const uint32_t rest = hsub[s2] % tile2;
+                    whole += hsub[s2] / tile2;
+                    if (rest) ++part[(rest - 1) / (4u * kNw2Threads)];
+                    largest = std::max(largest, hsub[s2]);
+                }
+                fprintf(stderr, "[bbk] msd level-2 tiles (narrow records): whole=%u groups1=%u groups2=%u groups3=%u largest_sub_slot=%u\n",
+                        whole, part[0], part[1], part[2], largest);
+            }
             for (uint32_t b = 0; b < nb1; ++b) {
                 // (late tag: 16 tags x nsub key ranges per segment)
                 snb2[b] = P.late_tag ? 16u * (uint32_t)std::min<double>(kMaxBins / 16, std::max(1.0, std::ceil((double)h1[b] / (16.0 * P.target))))
@@ -1083,8 +1095,11 @@ struct MsdRunner {
                             R.launch_plan(k_bucket_base, "k_bucket_base", nbuckets, (const uint32_t *)seg_nb2,
                                           (const uint32_t *)seg_bin, P.nb1, nbuckets, P.b1, R.w0bits(), bbase.as<uint64_t>());
                         constexpr int NT = BktCfg<1>::NT, IT = BktCfg<1>::ITEMS;
-                        R.launch(k_bucket_dist_nb<NT, IT>, "k_bucket_dist", (double)N * (4 + rec), nbuckets, NT,
-                                 bucket_dist_nb_smem<NT, IT>(), bufB.as<uint32_t>(), bbase.as<uint64_t>(), A);
+                        // (16-byte loads of a bucket's rows where every bucket starts on a 16-byte boundary: its slots)
+                        const bool wide = A.slot_cap != 0 && A.slot_stride % 4 == 0;
+                        R.launch(wide ? k_bucket_dist_nb<NT, IT, true> : k_bucket_dist_nb<NT, IT, false>, "k_bucket_dist",
+                                 (double)N * (4 + rec), nbuckets, NT, bucket_dist_nb_smem<NT, IT>(), bufB.as<uint32_t>(),
+                                 bbase.as<uint64_t>(), A);
                     }
                 }
             } else {

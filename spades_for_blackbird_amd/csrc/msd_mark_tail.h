@@ -1,5 +1,5 @@
-// msd_mark_tail.h -- the mark-bit scatter tail of k_part_reads_narrow (msd_narrow_a.h), k_part_view_lt and k_part_lt2
-// (msd_stage_b.h), and the rank-of-a-position helper that k_part_view_lt also uses to find the bucket of a key.
+// msd_mark_tail.h -- the mark-bit scatter tail of k_part_reads_narrow, k_part_narrow2 (msd_narrow_a.h), k_part_view_lt
+// and k_part_lt2 (msd_stage_b.h), and the rank-of-a-position helper that k_part_view_lt also uses to find the bucket of a key.
 // The layout and the index arithmetic are plain functions, so that the host can run them too
 // (tests/mark_tail_check.cpp); the tail itself is device code and needs msd_part.h in front of it.
 #pragma once
@@ -130,8 +130,10 @@ __device__ __forceinline__ uint32_t mark_rank_at(const MarkWord *wmw, int i, int
     return mark_rank(m.x, m.y, m.z, (uint32_t)lane);
 }
 
-// On entry lhist[b] = records of bin b in this tile (counted, not ranked) and bin_of_item(i) = the bin of item i
-// (0xFFFFFFFF: no record); lo[i] is its record, val_of(i) its payload byte (HAS_VAL).  cur / slot_end: cursor and end of
+// On entry lhist[b] = records of bin b in this tile and bin_of_item(i) = the bin of item i (0xFFFFFFFF: no record);
+// the place inside the bin is taken here, with a second atomic after the scan.  RANKED: the caller's counting atomic
+// has returned that place already and bin_of_item(i) = bin << 16 | place (k_part_narrow2, whose bins and places fit
+// sixteen bits each).  lo[i] is the item's record, val_of(i) its payload byte (HAS_VAL).  cur / slot_end: cursor and end of
 // the slot of bin `tid`.  The stored record is lo | rec_or.  before_stores() runs between the last barrier and the
 // stores (k_part_reads_narrow starts the next tile's loads there).
 //
@@ -140,7 +142,7 @@ __device__ __forceinline__ uint32_t mark_rank_at(const MarkWord *wmw, int i, int
 // entry is the byte address out + 4 * (reservation - staged start) and a store is that plus 4 * position: no limit, no
 // second exec region.  Otherwise the bin threads rewrite their entries as (offset, limit) and the tile takes the loop
 // with the limit test and the spill loop behind it.  Both loops store the same records to the same places.
-template <int TILE, int ITEMS, bool HAS_VAL, class BinOf, class ValOf, class KeyOf, class Hook>
+template <int TILE, int ITEMS, bool HAS_VAL, bool RANKED = false, class BinOf, class ValOf, class KeyOf, class Hook>
 __device__ __forceinline__ void mark_tail(const MarkLds &S, const uint32_t (&lo)[ITEMS], uint32_t tid, uint32_t nb,
                                           uint32_t *__restrict__ cur, uint64_t slot_end, uint32_t rec_or, const PartLevel &L,
                                           uint32_t *__restrict__ out, uint32_t *__restrict__ vout, BinOf bin_of_item,
@@ -172,7 +174,8 @@ __device__ __forceinline__ void mark_tail(const MarkLds &S, const uint32_t (&lo)
     for (int i = 0; i < ITEMS; ++i) {
         const uint32_t bin = bin_of_item(i);
         if (bin != 0xFFFFFFFFu) {
-            const uint32_t pos = atomicAdd(&S.lstart[bin], 1u);  // (lstart ends as the bins' end offsets; nothing reads it again)
+            // (lstart ends as the bins' end offsets; nothing reads it again.  RANKED: it stays, bin << 16 | place)
+            const uint32_t pos = RANKED ? S.lstart[bin >> 16] + (bin & 0xFFFFu) : atomicAdd(&S.lstart[bin], 1u);
             S.stage[pos] = lo[i];
             if (HAS_VAL) S.vstage[pos] = (uint8_t)val_of(i);
         }

@@ -337,124 +337,87 @@ static size_t part_reads_narrow_smem(bool has_val) {
     return mark_smem(tile) + std::max(tables, stage);
 }
 
-// Level 2: one tile (<= 16384 records) of one segment -> the bucket slots of that segment.  Everything derives from lo.
-constexpr int kNw2Threads = 1024;
-// records per lane: 12 without payload (60 VGPRs: two workgroups of 1024 per CU; with 16 the kernel needed 72 and ran
-// one: 3.2 -> 2.6 ms at BASELINE configs[1]), 8 with a payload (the mask array costs the registers of four records)
+// Level 2: one tile (<= 12288 records) of one segment -> the bucket slots of that segment.  Everything derives from lo.
+constexpr int kNw2Threads = 1024;  // == kMaxBins: one bin per thread in the scans
+// records per lane: 12 without payload (two workgroups of 1024 per CU; with 16 the kernel needed 72 registers and ran
+// one: 3.2 -> 2.6 ms at BASELINE configs[1]), 8 with a payload (the mask byte of level 1: the extension index)
 template <bool HAS_VAL>
 struct Nw2Cfg {
     static constexpr int ITEMS = HAS_VAL ? 8 : 12;
     static constexpr int TILE = kNw2Threads * ITEMS;
 };
 
+// The contiguous records of a tile, four per load.  Item i of a lane is record tile_item4(i, tid) of the tile: group
+// i / 4 of the lane is records 4 * ((i / 4) * NT + tid) .. + 3, one 16-byte load.  Which lane holds which record is
+// free -- the staged order is by bin.  The loads stay unconditional: a lane past the tile's last group re-reads that
+// group (one address for all of them), so up to three words behind the tile's last record are read and never used;
+// the level-1 buffer has that slack behind its last slot.  Tile starts are 4-byte aligned only (an odd
+// Plan::sub_cap), hence the vector type of alignment 4.  (k_part_lt2 was measured with these loads and did not move:
+// profiles/level2_tail.)
+typedef uint32_t TileRow4 __attribute__((ext_vector_type(4), aligned(4)));
+template <int NT>
+__device__ __forceinline__ uint32_t tile_item4(int i, uint32_t tid) {
+    return 4u * ((uint32_t)(i >> 2) * NT + tid) + (uint32_t)(i & 3);
+}
+template <int NT, int ITEMS>
+__device__ __forceinline__ void tile_rows4(const uint32_t *__restrict__ in, uint32_t begin, uint32_t count, uint32_t tid,
+                                           uint32_t (&rec)[ITEMS]) {
+    static_assert(ITEMS % 4 == 0, "whole groups of four");
+    const uint32_t last = (count - 1u) & ~3u;
+#pragma unroll
+    for (int r = 0; r < ITEMS / 4; ++r) {
+        const uint32_t p = 4u * ((uint32_t)r * NT + tid);
+        const TileRow4 q = *reinterpret_cast<const TileRow4 *>(in + begin + (p < last ? p : last));
+        rec[4 * r] = q.x, rec[4 * r + 1] = q.y, rec[4 * r + 2] = q.z, rec[4 * r + 3] = q.w;
+    }
+}
+
+// The histogram's atomic returns a record's place inside its bin, kept beside the bin (sixteen bits each); the scan,
+// reservation, reorder, stores and spills are the shared tail's (msd_mark_tail.h) in its RANKED form: the reorder adds
+// the place to the bin's start, and the bin of a staged record is not computed a second time.  (Counting first and
+// taking the place with a second returning atomic after the scan, as the tail's other users do, was measured slower
+// than the kernel's former own tail: profiles/level2_tail.)  The payload of every caller is level 1's mask byte.
 template <bool HAS_VAL>
-__global__ __launch_bounds__(kNw2Threads) void k_part_narrow2(const uint32_t *__restrict__ in, const uint32_t *__restrict__ vin,
-                                                             const uint4 *__restrict__ desc, PartLevel L,
-                                                             uint32_t *__restrict__ cursor, uint32_t *__restrict__ out,
-                                                             uint32_t *__restrict__ vout) {
-    constexpr int NT = kNw2Threads, ITEMS = Nw2Cfg<HAS_VAL>::ITEMS, MAXB = kMaxBins;
+__global__ __launch_bounds__(kNw2Threads) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_part_narrow2(
+    const uint32_t *__restrict__ in, const uint32_t *__restrict__ vin, const uint4 *__restrict__ desc, PartLevel L,
+    uint32_t *__restrict__ cursor, uint32_t *__restrict__ out, uint32_t *__restrict__ vout) {
+    constexpr int NT = kNw2Threads, ITEMS = Nw2Cfg<HAS_VAL>::ITEMS, TILE = Nw2Cfg<HAS_VAL>::TILE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint32_t *lhist = reinterpret_cast<uint32_t *>(smem);
-    uint32_t *lstart = lhist + MAXB;
-    uint32_t *goff = lstart + MAXB;
-    uint32_t *scan_tmp = goff + MAXB;
-    uint32_t *stage = scan_tmp + 32;
-    uint32_t *vstage = stage + Nw2Cfg<HAS_VAL>::TILE;
+    const MarkLds S = mark_lds<TILE>(smem);
     const uint32_t tid = threadIdx.x;
     const int hb = L.narrow_hb;
     const uint4 d = desc[blockIdx.x];  // first record, records, bins of the segment | segment << 16, flat index of bin 0
     const uint32_t begin = d.x, count = d.y, nb = d.z & 0xFFFFu, seg = d.z >> 16, gbin0 = d.w;
     if (count == 0) return;  // an unused place of the XCD-wise order (k_tile_desc)
-    lhist[tid] = 0;  // NT == MAXB
+    mark_clear<TILE>(S, tid);  // NT == kMaxBins
     __syncthreads();
-    uint32_t lo[ITEMS], vals[ITEMS], binrank[ITEMS];
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {  // all loads first (index clamped into the tile)
-        const uint32_t local = (uint32_t)i * NT + tid;
-        const uint32_t at = begin + (local < count ? local : count - 1u);
-        lo[i] = in[at];
-        vals[i] = HAS_VAL ? vin[at] : 0u;
-    }
+    uint32_t lo[ITEMS], vals[ITEMS];
+    tile_rows4<NT, ITEMS>(in, begin, count, tid, lo);  // all loads first
+    if (HAS_VAL) tile_rows4<NT, ITEMS>(vin, begin, count, tid, vals);
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
         asm volatile("" : "+v"(lo[i]));
         if (HAS_VAL) asm volatile("" : "+v"(vals[i]));
     }
+    uint32_t binrank[ITEMS];
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t local = (uint32_t)i * NT + tid;
         binrank[i] = 0xFFFFFFFFu;
-        if (local < count) {
+        if (tile_item4<NT>(i, tid) < count) {
             const uint32_t b = nw_bin2(nw_mix(lo[i]), nb);
-            const uint32_t rank = atomicAdd(&lhist[b], 1u);
-            binrank[i] = (b << 16) | rank;
+            binrank[i] = (b << 16) | atomicAdd(&S.lhist[b], 1u);
         }
     }
     __syncthreads();
-    const int lane = tid & 63, wave = tid >> 6;
-    const uint32_t c = tid < nb ? lhist[tid] : 0u;
-    uint32_t incl = c;
-    incl = wave_scan_incl(incl);
-    if (lane == 63) scan_tmp[wave] = incl;
-    __syncthreads();
-    uint32_t wb, staged;
-    wave_totals<NT / 64>(scan_tmp, lane, wave, wb, staged);
-    const uint32_t ex = wb + incl - c;
-    if (tid < nb) lstart[tid] = ex;
-    uint32_t greserve = c ? atomicAdd(&cursor[gbin0 + tid], c) : 0u;
-    __syncthreads();
-    // the reservation's result is awaited HERE, by every lane: the compiler otherwise puts the wait for it (vmcnt 0) into
-    // the conditional blocks of the store loop below, where it makes every store wait for the one before
-    asm volatile("" : "+v"(greserve));
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        if (binrank[i] != 0xFFFFFFFFu) {
-            const uint32_t pos = lstart[binrank[i] >> 16] + (binrank[i] & 0xFFFFu);
-            stage[pos] = lo[i];
-            if (HAS_VAL) vstage[pos] = vals[i];
-        }
-    }
-    if (tid < nb) {
-        goff[tid] = greserve - ex;
-        const int64_t room = (int64_t)((uint64_t)(gbin0 + tid) * L.slot_stride + L.slot_cap) - (int64_t)greserve;
-        lhist[tid] = (uint32_t)(int32_t)(room < -(int64_t)0x7FFF0000 ? -(int64_t)0x7FFF0000 : room) + ex;
-    }
-    __syncthreads();
-    // (records whose slot is full are rare and handled after the stores: the spill counter's atomic returns a value, and
-    // a wait for it between the stores would make every store wait for the one before)
-    uint32_t full = 0;
-#pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {
-        const uint32_t pos = (uint32_t)i * NT + tid;
-        if (pos < staged) {
-            const uint32_t rec = stage[pos];
-            const uint32_t b = nw_bin2(nw_mix(rec), nb);
-            if ((int32_t)pos >= (int32_t)lhist[b]) {
-                full |= 1u << i;
-            } else {
-                const uint32_t g = goff[b] + pos;
-                out[g] = rec;
-                if (HAS_VAL) vout[g] = vstage[pos];
-            }
-        }
-    }
-    if (full) {
-#pragma unroll 1
-        for (int i = 0; i < ITEMS; ++i) {
-            if ((full >> i) & 1u) {
-                const uint32_t pos = (uint32_t)i * NT + tid;
-                const uint32_t sp = atomicAdd(L.spill_count, 1u);
-                if (sp < L.spill_cap) {
-                    reinterpret_cast<uint64_t *>(L.spill_keys)[sp] = nw_key(seg, stage[pos], hb);
-                    if (HAS_VAL) L.spill_vals[sp] = vstage[pos];
-                }
-            }
-        }
-    }
+    const uint64_t slot_end = (uint64_t)(gbin0 + tid) * L.slot_stride + L.slot_cap;
+    mark_tail<TILE, ITEMS, HAS_VAL, true>(
+        S, lo, tid, nb, &cursor[gbin0 + tid], slot_end, 0u, L, out, vout, [&](int i) { return binrank[i]; },
+        [&](int i) { return vals[i]; }, [&](uint32_t, uint32_t rec) { return nw_key(seg, rec, hb); }, []() {});
 }
 
 static size_t part_narrow2_smem(bool has_val) {
-    return sizeof(uint32_t) * (3 * kMaxBins + 32) + (size_t)(has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE) * 4 * (has_val ? 2 : 1);
+    const size_t tile = has_val ? Nw2Cfg<true>::TILE : Nw2Cfg<false>::TILE;
+    return mark_smem(tile) + tile * (has_val ? 5 : 4);
 }
 
 // Dedup of one bucket of 4-byte records in an LDS table (32-bit ds_cmpst); the distinct records leave as 8-byte keys

@@ -30,7 +30,8 @@ __global__ void k_bucket_base(const uint32_t *__restrict__ seg_nb2, const uint32
 // ranking over 32-bit offsets, with half the LDS (38 KB against 61 KB) and at most 64 registers (62: two records per
 // ranking round instead of six), so that four workgroups fit a CU instead of two.  A bucket it turns down, a duplicate or a spill
 // sends the call back to the exact mode, as on the 8-byte key slots, so no second-chance kernel needs this form.
-template <int NT, int ITEMS>
+// WIDE: 16-byte loads of the first eight records of a lane (below; 57 registers), for buckets in slots.
+template <int NT, int ITEMS, bool WIDE>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_bucket_dist_nb(const uint32_t *__restrict__ buf, const uint64_t *__restrict__ base,
                                                        BucketArgs A) {
     constexpr int CAP = NT * ITEMS;
@@ -67,20 +68,43 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     const uint32_t rows = bucket_rows(n, NT);
     const uint64_t kbase = base[b];
     uint32_t keys[ITEMS];  // offsets from the base: the key order
+    // WIDE (bucket slots, which start on 16-byte boundaries): the first eight records of a lane arrive as two 16-byte
+    // loads, item i < 8 being record (i / 4) * 4 NT + 4 tid + i % 4, and a "row" of those items is in use when its
+    // group of 4 NT records is; items 8 .. ITEMS - 1 keep their rows (8 NT = 2 * 4 NT: no record twice).  The loads
+    // stay unconditional, a lane past the last group of four re-reads it: up to three words behind record n - 1,
+    // inside the slot's own slack, which pos(i) < n keeps out of everything below.
+    static_assert(!WIDE || (ITEMS >= 8 && ITEMS <= 12), "two groups of four, then single rows");
+    auto pos = [&](int i) -> uint32_t {
+        return WIDE && i < 8 ? (uint32_t)(i >> 2) * (4u * NT) + 4u * (uint32_t)tid + (uint32_t)(i & 3) : (uint32_t)(i * NT + tid);
+    };
+    auto used = [&](int i) -> bool { return WIDE && i < 8 ? (uint32_t)(i >> 2) * (4u * NT) < n : (uint32_t)i < rows; };
+    if (WIDE) {
+        const uint32_t last = (n - 1u) & ~3u;
 #pragma unroll
-    for (int i = 0; i < ITEMS; ++i) {  // the loads of the rows in use are issued up front, the last one clamped
-        if ((uint32_t)i < rows) {
-            const uint32_t p = (uint32_t)(i * NT + tid);
+        for (int g = 0; g < 2; ++g) {
+            if (used(4 * g)) {
+                const uint32_t p = (uint32_t)g * (4u * NT) + 4u * (uint32_t)tid;
+                const uint4 q = *reinterpret_cast<const uint4 *>(buf + start + (p < last ? p : last));
+                keys[4 * g] = q.x, keys[4 * g + 1] = q.y, keys[4 * g + 2] = q.z, keys[4 * g + 3] = q.w;
+            }
+        }
+    }
+#pragma unroll
+    for (int i = WIDE ? 8 : 0; i < ITEMS; ++i) {  // the loads of the rows in use are issued up front, the last one clamped
+        if (used(i)) {
+            const uint32_t p = pos(i);
             keys[i] = buf[start + (p < n ? p : n - 1u)];
         }
     }
     uint32_t mn = ~0u, mx = 0;
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {  // clamped duplicates do not change min / max
-        if ((uint32_t)i < rows) {
+        if (used(i)) {
             keys[i] -= (uint32_t)kbase;
-            mn = keys[i] < mn ? keys[i] : mn;
-            mx = keys[i] > mx ? keys[i] : mx;
+            if (!WIDE || pos(i) < n) {  // (a re-read last group of four may reach past n)
+                mn = keys[i] < mn ? keys[i] : mn;
+                mx = keys[i] > mx ? keys[i] : mx;
+            }
         }
     }
 #pragma unroll
@@ -108,8 +132,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        if ((uint32_t)i < rows) {
-            const uint32_t p = (uint32_t)(i * NT + tid);
+        if (used(i)) {
+            const uint32_t p = pos(i);
             if (p < n) atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
         }
     }
@@ -146,8 +170,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     uint32_t at[ITEMS];  // where the scatter put the record (breaks ties between equal offsets), then its final place
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        if ((uint32_t)i < rows) {
-            const uint32_t p = (uint32_t)(i * NT + tid);
+        if (used(i)) {
+            const uint32_t p = pos(i);
             if (p < n) {
                 const uint32_t pos = atomicAdd(&bins[(keys[i] - kmin) >> sh], 1u);
                 skeys[pos] = keys[i];
@@ -166,14 +190,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     constexpr int RB = 2;
 #pragma unroll
     for (int i0 = 0; i0 < ITEMS; i0 += RB) {
-        if ((uint32_t)i0 < rows) {
+        if (used(i0)) {
             uint32_t sb[RB], e[RB];
 #pragma unroll
             for (int u = 0; u < RB; ++u) {
                 const int i = i0 + u;
                 sb[u] = e[u] = 0;
                 if (i < ITEMS) {
-                    const uint32_t p = (uint32_t)(i * NT + tid);
+                    const uint32_t p = pos(i);
                     if (p < n) {
                         const uint32_t d = (keys[i] - kmin) >> sh;
                         sb[u] = d ? bins[d - 1] : 0u;
@@ -194,7 +218,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
             for (int u = 0; u < RB; ++u) {
                 const int i = i0 + u;
                 if (i < ITEMS) {
-                    const uint32_t p = (uint32_t)(i * NT + tid);
+                    const uint32_t p = pos(i);
                     if (p < n) {
                         uint32_t before = 0;
 #pragma unroll
@@ -216,8 +240,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     BBK_PH(3, 4, t_prev);  // rank
 #pragma unroll
     for (int i = 0; i < ITEMS; ++i) {
-        if ((uint32_t)i < rows) {
-            const uint32_t p = (uint32_t)(i * NT + tid);
+        if (used(i)) {
+            const uint32_t p = pos(i);
             if (p < n) skeys[at[i]] = keys[i];
         }
     }
@@ -231,6 +255,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     // (coalesced), and equal neighbours raise the duplicate flag -- no heads, no scan, no compaction.  Any duplicate
     // sends the whole call to give_up_key_slots() and the result is released, so what a bucket that holds one stores
     // inside its own [ostart, ostart + n) does not matter.  dcount is n: the bucket was sorted here.
+    // (Two positions per lane and one 16-byte store for both -- half as many stores -- were measured: the kernel's
+    // average fell by 2-3 %, inside its own launch range, and the form was not kept: profiles/level2_tail.)
     uint64_t *dst = reinterpret_cast<uint64_t *>(A.sorted_keys) + ostart;
     bool dup = false;
 #pragma unroll

@@ -26,8 +26,8 @@ FAMILY = [  # rocprof kernel symbol -> the name bbk_ctx_profile_get / bench.py u
     (r"k_part_reads_narrow", "k_part_reads_narrow"),
     (r"k_part_narrow2", "k_part_narrow2"),
     (r"k_bucket_hash32", "k_bucket_hash32"),
-    (r"k_part_view_lt<true>", "k_part_l1"),  # late tag: the view's overflow keys (dense)
-    (r"k_part_view", "k_part_view"),  # stage B's level 1 over stage A's buckets (BucketView); k_part_view_lt: late tag
+    (r"k_part_view_lt", "k_part_l1"),  # late tag: level 1 from the view's buckets and from its overflow keys (dense)
+    (r"k_part_view", "k_part_view"),  # stage B's level 1 over stage A's buckets (BucketView), tag taken early
     (r"k_part_lt2", "k_part_l2"),  # late tag: 4-byte level 2, tag taken there
     (r"k_bucket_base_lt", "k_bucket_base_lt"),
     (r"k_lt_fill_perm", "k_lt_fill_perm"),
