@@ -381,6 +381,75 @@ const char *bbk_edgeindex_name(const bbk_edgeindex *ix, uint64_t segment); /* NU
 int bbk_edgeindex_export_graph(const bbk_edgeindex *ix, char *h_bases, uint64_t *h_offsets, uint32_t *h_links,
                                uint32_t *h_kc);
 
+/* h_len: the (k+1)-mers of every segment, |seq| - k, the reference's g.length(e) of its edge and of the conjugate;
+ * h_self_conjugate: 1 for a segment that is its own reverse complement (one edge), 0 otherwise (two).  Either may be
+ * NULL; segments entries each. */
+int bbk_edgeindex_export_segments(const bbk_edgeindex *ix, uint64_t *h_len, uint8_t *h_self_conjugate);
+
+/* ---- paired-read info: the paired-end side of PairInfoCount (projects/spades/pair_info_count.cpp:199-243, 285-324,
+ *      328-417) over the mapping paths of the two mates: InsertSizeCounter (common/paired_info/is_counter.hpp:85-115) with
+ *      the statistics of insert_size_refiner.hpp:23-166, EdgePairCounterFiller / DEFilter (pair_info_count.cpp:70-137)
+ *      and LatePairedIndexFiller (common/paired_info/pair_info_filler.hpp:63-93) into the raw, unclustered paired index
+ *      (common/paired_info/paired_info_buffer.hpp:54-57, 103-147).  The reference has the stage only inside spades-core;
+ *      parity is with a restatement (tests/pairinfo_restated.py) ------------------------------------------------------ */
+typedef struct bbk_pairinfo bbk_pairinfo; /* the reduced runs of the passes in HBM, their results on the host */
+/* OrientationChanger (common/io/reads/orientation.hpp:15-41): which mate is reverse-complemented before it is mapped */
+#define BBK_ORIENT_FF 0 /* neither */
+#define BBK_ORIENT_FR 1 /* the second */
+#define BBK_ORIENT_RF 2 /* the first */
+#define BBK_ORIENT_RR 3 /* both */
+typedef struct bbk_pairinfo_stats {
+    uint64_t total, mapped, negative; /* pairs seen; with a positive insert size on one long edge; with one <= 0 there */
+    uint64_t edge_pairs;              /* distinct ordered (e1, e2) over path1 x path2: exact, where the reference
+                                         estimates it with a HyperLogLog */
+    double mean, deviation;           /* find_mean */
+    double median, mad;               /* find_median */
+    double left_quantile, right_quantile; /* GetISInterval(0.8) of the cropped histogram */
+    uint64_t percentiles[19];         /* 5 % ... 95 % of find_mean; 0 where the reference sets none */
+    int ok;                           /* CollectLibInformation's verdict: 0 when mapped == 0 (no statistic is computed),
+                                         when median < k + 2 (no quantile is), or when the cropped histogram is empty */
+} bbk_pairinfo_stats;
+/* ix must outlive the result.  min_edge_length: edge_length_threshold of InsertSizeCounter. */
+int bbk_pairinfo_begin(bbk_ctx *ctx, const bbk_edgeindex *ix, uint64_t min_edge_length, bbk_pairinfo **out);
+/* One batch of pairs: pair p is read p of `first` and read p of `second`, in file orientation; both have gone through
+ * LongestValid (bbk_reads).  h_cut: 4 x u32 per pair, the bases LongestValid cut before and after each mate in file
+ * orientation (left1, right1, left2, right2: SingleRead's offsets, io/reads/single_read.hpp:247-258); NULL = zeros.  The
+ * engine swaps a mate's two values when the orientation reverse-complements it (single_read.hpp:143-147).  Every pair
+ * counts in total; its insert size and its edge pairs are reduced on the device.  The result of the pass is the same
+ * bytes for any batching of the pairs.  BBK_ERR_ARG: unequal read counts, an orientation out of range, 2^32 pairs or
+ * 2^32 edge-pair records in one pass (the device counts are 32 bits wide: nothing wraps silently). */
+int bbk_pairinfo_push_estimate(bbk_pairinfo *pi, const bbk_reads *first, const bbk_reads *second, int orientation,
+                               const uint32_t *h_cut);
+/* Ends (or refreshes, after further pushes) the estimate pass: the statistics in doubles on the host, line by line as
+ * the reference computes them. */
+int bbk_pairinfo_estimate(bbk_pairinfo *pi, bbk_pairinfo_stats *stats);
+/* the insert-size histogram of the estimate pass, ascending; either pointer may be NULL */
+uint64_t bbk_pairinfo_hist_size(const bbk_pairinfo *pi);
+int bbk_pairinfo_hist_export(const bbk_pairinfo *pi, int32_t *h_is, uint64_t *h_count);
+/* The fill pass.  insert_size: the reference passes (size_t) mean_insert_size.  round_distance > 1 rounds every distance
+ * to a multiple of it, half away from zero.  filter_threshold t > 0 keeps a pair of edges iff min(c, 3) > t with
+ * c = occurrences(e1, e2) + occurrences(conj e2, conj e1) over the estimate pass (the reference's counting Bloom filter
+ * has 2-bit cells and may over-count; these counts are exact); t = 0 keeps every pair.  BBK_ERR_ARG: t > 0 without an
+ * estimate pass over the same handle; bbk_pairinfo_push_fill before bbk_pairinfo_estimate or before
+ * bbk_pairinfo_fill_begin; the errors of bbk_pairinfo_push_estimate. */
+int bbk_pairinfo_fill_begin(bbk_pairinfo *pi, uint64_t insert_size, unsigned round_distance, unsigned filter_threshold);
+int bbk_pairinfo_push_fill(bbk_pairinfo *pi, const bbk_reads *first, const bbk_reads *second, int orientation,
+                           const uint32_t *h_cut);
+int bbk_pairinfo_fill_finish(bbk_pairinfo *pi);
+/* The index: points (e1, e2, gap, weight) ascending, edges numbered as bbk_path_range.edge, gap = distance - length(e1),
+ * stored under the smaller of (e1, e2) and (conj e2, conj e1); a pair with e1 == conj e2 has every weight doubled.
+ * Integers, exact.  Any pointer may be NULL. */
+uint64_t bbk_pairinfo_points(const bbk_pairinfo *pi);
+int bbk_pairinfo_export(const bbk_pairinfo *pi, uint64_t *h_e1, uint64_t *h_e2, int32_t *h_gap, uint64_t *h_weight);
+/* <path> in the layout of PairedBuffer::BinWrite (paired_info_buffer.hpp:197-210): the number of first edges; per first
+ * edge, ascending, its id, then per stored second edge its id and its histogram as io::binary::BinWrite writes one (the
+ * number of points, then per point float gap, float weight: RawPointT::BinWrite, index_point.hpp:195-197), then a 0.
+ * Unsigned integers are ULEB128, as io::binary::BinWrite encodes them (io/binary/binary.hpp:109-122).  The reference's
+ * edge ids are not reproducible here, so an id is edge + 1 (0 is the terminator).  The file's floats are exact below
+ * 2^24; bbk_pairinfo_export is exact always. */
+int bbk_pairinfo_write(const bbk_pairinfo *pi, const char *path);
+void bbk_pairinfo_free(bbk_pairinfo *pi);
+
 /* ---- k-mer multiplicity profiles across samples: replaces KmerMultiplicityCounter::FilterCombinedKmers
  *      (projects/mts/kmer_multiplicity_counter.cpp:72-139: one KMC database per sample, sorted and merged under
  *      RtSeq::less3 = BBK_ORDER_SORTED) and, for the lookup, the BooPHF map of BuildKmerIndex (:141-181) -- and contig

@@ -13,7 +13,8 @@ PROGRAMS = {"spades-kmercount": "kmercount_main.cpp", "spades-gbuilder": "gbuild
             "kmer_multiplicity_counter": "kmer_multiplicity_counter_main.cpp",
             "contig_abundance_counter": "contig_abundance_counter_main.cpp",
             "spades-hamcluster": "hamcluster_main.cpp", "spades-kmerdata": "kmerdata_main.cpp",
-            "bbk-hammer-reads-dump": "hammer_reads_dump_main.cpp", "spades-hammer": "hammer_main.cpp"}
+            "bbk-hammer-reads-dump": "hammer_reads_dump_main.cpp", "spades-hammer": "hammer_main.cpp",
+            "spades-pairinfo": "pairinfo_main.cpp"}
 HEADERS = ["cli.hpp", "common.hpp", "dataset.hpp", "fastx.hpp", "ingest.hpp", "multi.hpp", "hammer_reads.hpp", "hammer_run.hpp",
            "hammer_config.hpp"]
 

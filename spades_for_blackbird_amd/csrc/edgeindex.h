@@ -1,0 +1,55 @@
+// edgeindex.h -- the handles of the graph-mapping stage that more than one translation unit reads: the edge index
+// (edgeprof.hip builds it; pairinfo.hip joins the paths of two mates over its segment table) and the mapping paths of a
+// batch.  Not part of the C ABI.
+#pragma once
+
+#include <string>
+#include <vector>
+
+#include "bbk_internal.h"
+
+namespace bbk {
+
+// one record of the edge index, 16 bytes: one dwordx4 load per found position
+struct EdgePos {
+    uint32_t seg;     // segment (S-line order)
+    uint32_t off_fw;  // offset of the (k+1)-mer on the forward strand of the segment
+    uint32_t off_rc;  // offset of its reverse complement on the reverse strand (len - 1 - off_fw)
+    uint32_t flags;   // kEpCanonFw | kEpSelfConj | kEpLoop1 (gfa_graph.h)
+};
+
+}  // namespace bbk
+
+struct bbk_edgeindex {
+    unsigned k = 0, k1 = 0, W = 0;
+    uint64_t n_seg = 0, n = 0;           // segments, indexed (k+1)-mers
+    std::vector<std::string> names;      // segment names
+    std::vector<uint64_t> len;           // (k+1)-mers per segment = |seq| - k (the reference's g.length(e))
+    std::string bases;                   // the segments' ACGT back to back
+    std::vector<uint64_t> off;           // n_seg + 1 offsets into bases
+    std::vector<uint32_t> links;         // 4 x u32 per L line in file order: a, a is '+', b, b is '+'
+    std::vector<uint32_t> kc;            // KC:i: of every segment (0 without one)
+    bool has_graph = false;              // bases / off / links / kc are kept (bbk_edgeindex_from_gfa_with_graph)
+    bbk::DevBuf keys;                    // n * W u64, ascending canonical (k+1)-mers
+    bbk::DevBuf pos;                     // n EdgePos
+    bbk::PrefixIndex prefix;             // over keys, built for k1
+    bbk::DevBuf seg;                     // n_seg u32: len[s] | kSegSelfConj when the segment is its own conjugate
+    std::vector<uint32_t> seg_h;         // the same on the host
+};
+
+namespace bbk {
+constexpr uint32_t kSegSelfConj = 1u << 31;  // (a segment holds fewer than 2^31 (k+1)-mers: the index has < 2^32 in all)
+}
+
+struct bbk_profiles {
+    bbk_ctx *ctx = nullptr;
+    const bbk_edgeindex *ix = nullptr;
+    unsigned samples = 0;
+    bbk::DevBuf raw;  // n_seg * samples u64, [segment][sample]
+};
+
+struct bbk_paths {
+    uint64_t n_reads = 0, n_ranges = 0;
+    bbk::DevBuf ranges;  // n_ranges bbk_path_range in read order
+};
+

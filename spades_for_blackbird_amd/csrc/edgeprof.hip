@@ -48,48 +48,10 @@
 #include <vector>
 
 #include "bbk_internal.h"
+#include "edgeindex.h"
 #include "gfa_graph.h"
 #include "kmer_ops.h"
 #include "unitigs.h"
-
-namespace bbk {
-
-// one record of the edge index, 16 bytes: one dwordx4 load per found position
-struct EdgePos {
-    uint32_t seg;     // segment (S-line order)
-    uint32_t off_fw;  // offset of the (k+1)-mer on the forward strand of the segment
-    uint32_t off_rc;  // offset of its reverse complement on the reverse strand (len - 1 - off_fw)
-    uint32_t flags;   // kEpCanonFw | kEpSelfConj | kEpLoop1 (gfa_graph.h)
-};
-
-}  // namespace bbk
-
-struct bbk_edgeindex {
-    unsigned k = 0, k1 = 0, W = 0;
-    uint64_t n_seg = 0, n = 0;           // segments, indexed (k+1)-mers
-    std::vector<std::string> names;      // segment names
-    std::vector<uint64_t> len;           // (k+1)-mers per segment = |seq| - k (the reference's g.length(e))
-    std::string bases;                   // the segments' ACGT back to back
-    std::vector<uint64_t> off;           // n_seg + 1 offsets into bases
-    std::vector<uint32_t> links;         // 4 x u32 per L line in file order: a, a is '+', b, b is '+'
-    std::vector<uint32_t> kc;            // KC:i: of every segment (0 without one)
-    bool has_graph = false;              // bases / off / links / kc are kept (bbk_edgeindex_from_gfa_with_graph)
-    bbk::DevBuf keys;                    // n * W u64, ascending canonical (k+1)-mers
-    bbk::DevBuf pos;                     // n EdgePos
-    bbk::PrefixIndex prefix;             // over keys, built for k1
-};
-
-struct bbk_profiles {
-    bbk_ctx *ctx = nullptr;
-    const bbk_edgeindex *ix = nullptr;
-    unsigned samples = 0;
-    bbk::DevBuf raw;  // n_seg * samples u64, [segment][sample]
-};
-
-struct bbk_paths {
-    uint64_t n_reads = 0, n_ranges = 0;
-    bbk::DevBuf ranges;  // n_ranges bbk_path_range in read order
-};
 
 namespace bbk {
 
@@ -306,6 +268,12 @@ static uint64_t build_device_index(bbk_ctx *ctx, bbk_edgeindex *ix, const bbk_re
     BBK_HIP(hipMemcpyAsync(d_emit.p, t.emit.data(), (ns + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
     BBK_HIP(hipMemcpyAsync(d_len.p, t.len32.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
     BBK_HIP(hipMemcpyAsync(d_flags.p, t.flags.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
+    // (length, self-conjugate) of every segment stays on the device: what the paired-info join reads per range
+    std::vector<uint32_t> &seg = ix->seg_h;
+    seg.resize(ns);
+    for (uint64_t s = 0; s < ns; ++s) seg[s] = t.len32[s] | ((t.flags[s] & kEpSelfConj) ? kSegSelfConj : 0u);
+    ix->seg.alloc(ns * 4);
+    BBK_HIP(hipMemcpyAsync(ix->seg.p, seg.data(), ns * 4, hipMemcpyHostToDevice, ctx->stream));
     DevBuf tmp(n * W * 8), idx(n * 4), idx_tmp(n * 4), pos(n * sizeof(EdgePos)), dup(8);
     ix->keys.alloc(n * W * 8);
     ix->pos.alloc(n * sizeof(EdgePos));
@@ -588,6 +556,15 @@ uint64_t bbk_edgeindex_links(const bbk_edgeindex *ix) { return ix ? ix->links.si
 uint64_t bbk_edgeindex_total_bases(const bbk_edgeindex *ix) { return ix ? ix->bases.size() : 0; }
 const char *bbk_edgeindex_name(const bbk_edgeindex *ix, uint64_t segment) {
     return ix && segment < ix->n_seg ? ix->names[segment].c_str() : nullptr;
+}
+
+int bbk_edgeindex_export_segments(const bbk_edgeindex *ix, uint64_t *h_len, uint8_t *h_self_conjugate) {
+    return guarded([&] {
+        BBK_REQUIRE(ix, BBK_ERR_ARG, "bbk_edgeindex_export_segments: NULL index");
+        if (h_len) std::copy(ix->len.begin(), ix->len.end(), h_len);
+        if (h_self_conjugate)
+            for (uint64_t s = 0; s < ix->n_seg; ++s) h_self_conjugate[s] = (ix->seg_h[s] & kSegSelfConj) ? 1 : 0;
+    });
 }
 
 int bbk_edgeindex_export_graph(const bbk_edgeindex *ix, char *h_bases, uint64_t *h_offsets, uint32_t *h_links,

@@ -14,6 +14,17 @@ NO_TRIM = -2 ** 31  # BBK_NO_TRIM: the trim_quality of records that are trimmed 
 PATH_RANGE = np.dtype([("edge", np.uint64), ("read", np.uint32), ("init_start", np.uint32), ("init_end", np.uint32),
                        ("map_start", np.uint32), ("map_end", np.uint32), ("reserved", np.uint32)])
 
+ORIENT_FF, ORIENT_FR, ORIENT_RF, ORIENT_RR = 0, 1, 2, 3  # BBK_ORIENT_*: which mate is reverse-complemented
+
+
+class PairInfoStats(C.Structure):
+    """bbk_pairinfo_stats of include/bbk.h"""
+    _fields_ = [("total", C.c_uint64), ("mapped", C.c_uint64), ("negative", C.c_uint64), ("edge_pairs", C.c_uint64),
+                ("mean", C.c_double), ("deviation", C.c_double), ("median", C.c_double), ("mad", C.c_double),
+                ("left_quantile", C.c_double), ("right_quantile", C.c_double), ("percentiles", C.c_uint64 * 19),
+                ("ok", C.c_int)]
+
+
 # every symbol include/bbk.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "bbk_last_error", "bbk_version", "bbk_ctx_create", "bbk_ctx_destroy", "bbk_ctx_set_stream",
@@ -35,6 +46,9 @@ SYMBOLS = [
     "bbk_profiles_begin", "bbk_profiles_push_reads", "bbk_profiles_export_raw", "bbk_profiles_write", "bbk_profiles_free",
     "bbk_edgeindex_map_paths", "bbk_edgeindex_from_gfa_with_graph", "bbk_paths_reads", "bbk_paths_ranges", "bbk_paths_export", "bbk_paths_free",
     "bbk_edgeindex_links", "bbk_edgeindex_total_bases", "bbk_edgeindex_name", "bbk_edgeindex_export_graph",
+    "bbk_edgeindex_export_segments", "bbk_pairinfo_begin", "bbk_pairinfo_push_estimate", "bbk_pairinfo_estimate", "bbk_pairinfo_hist_size", "bbk_pairinfo_hist_export",
+    "bbk_pairinfo_fill_begin", "bbk_pairinfo_push_fill", "bbk_pairinfo_fill_finish", "bbk_pairinfo_points", "bbk_pairinfo_export",
+    "bbk_pairinfo_write", "bbk_pairinfo_free",
     "bbk_kmerprofile_begin", "bbk_kmerprofile_add_sample", "bbk_kmerprofile_finish", "bbk_kmerprofile_abort",
     "bbk_kmerprofile_size", "bbk_kmerprofile_samples", "bbk_kmerprofile_k", "bbk_kmerprofile_export",
     "bbk_kmerprofile_write", "bbk_kmerprofile_load", "bbk_kmerprofile_abundance", "bbk_kmerprofile_abundance_pieces",
@@ -224,6 +238,20 @@ def load_library():
         L.bbk_edgeindex_name.restype = C.c_char_p
         L.bbk_edgeindex_name.argtypes = [vp, u64]
         L.bbk_edgeindex_export_graph.argtypes = [vp, vp, vp, vp, vp]
+        L.bbk_edgeindex_export_segments.argtypes = [vp, vp, vp]
+        L.bbk_pairinfo_begin.argtypes = [vp, vp, u64, C.POINTER(vp)]
+        L.bbk_pairinfo_push_estimate.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.bbk_pairinfo_estimate.argtypes = [vp, C.POINTER(PairInfoStats)]
+        for f in ("hist_size", "points"):
+            getattr(L, "bbk_pairinfo_" + f).restype = u64
+            getattr(L, "bbk_pairinfo_" + f).argtypes = [vp]
+        L.bbk_pairinfo_hist_export.argtypes = [vp, vp, vp]
+        L.bbk_pairinfo_fill_begin.argtypes = [vp, u64, C.c_uint, C.c_uint]
+        L.bbk_pairinfo_push_fill.argtypes = [vp, vp, vp, C.c_int, vp]
+        L.bbk_pairinfo_fill_finish.argtypes = [vp]
+        L.bbk_pairinfo_export.argtypes = [vp, vp, vp, vp, vp]
+        L.bbk_pairinfo_write.argtypes = [vp, C.c_char_p]
+        L.bbk_pairinfo_free.argtypes = [vp]
     L.bbk_kmerprofile_begin.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(vp)]
     L.bbk_kmerprofile_add_sample.argtypes = [vp, C.c_uint, vp]
     L.bbk_kmerprofile_finish.argtypes = [vp, u64, u64, C.POINTER(vp)]
@@ -1470,6 +1498,19 @@ class EdgeIndex(_Handle):
             self._L.bbk_paths_free(h)
         return off, rec
 
+    def segment_lengths(self):
+        """(lengths np.uint64 in (k+1)-mers, self-conjugate np.uint8) of the segments"""
+        n = self.segments
+        a, c = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint8)
+        _check(self._L.bbk_edgeindex_export_segments(self._h, _ptr(a), _ptr(c)))
+        return a, c
+
+    def pairinfo(self, min_edge_length=0):
+        """paired-read info over this index (PairInfoCount for a paired-end library): a PairInfo"""
+        h = C.c_void_p()
+        _check(self._L.bbk_pairinfo_begin(self.ctx._h, self._h, min_edge_length, C.byref(h)))
+        return PairInfo(self, h)
+
     def graph(self):
         """(names, sequences, links [(a, '+'|'-', b, '+'|'-')], kc np.uint32) as the index holds the graph"""
         ns, nl = self.segments, int(self._L.bbk_edgeindex_links(self._h))
@@ -1484,6 +1525,67 @@ class EdgeIndex(_Handle):
         sign = lambda x: "+" if x else "-"  # noqa: E731
         links = [(int(lk[4 * j]), sign(lk[4 * j + 1]), int(lk[4 * j + 2]), sign(lk[4 * j + 3])) for j in range(nl)]
         return names, seqs, links, kc
+
+
+class PairInfo(_Handle):
+    """insert sizes, edge pairs and the raw paired index of one paired-end library: push_estimate the batches, estimate(),
+    fill_begin(), push_fill the same batches, fill_finish(), then points() or write()"""
+    _free = "bbk_pairinfo_free"
+
+    def __init__(self, index, h):
+        super().__init__(index.ctx, h)
+        self.index = index  # the index must outlive the handle
+
+    @staticmethod
+    def _cut(cut, n):
+        if cut is None:
+            return None
+        cut = np.ascontiguousarray(cut, dtype=np.uint32)
+        if cut.shape != (n, 4):
+            raise ValueError("cut must hold (left1, right1, left2, right2) for each of the %d pairs" % n)
+        return cut
+
+    def push_estimate(self, first, second, orientation=ORIENT_FR, cut=None):
+        cut = self._cut(cut, len(first))
+        _check(self._L.bbk_pairinfo_push_estimate(self._h, first._h, second._h, orientation, _ptr(cut) if cut is not None else None))
+
+    def estimate(self):
+        """the statistics of CollectLibInformation as a dict (percentiles: 19 values, 5 % ... 95 %)"""
+        st = PairInfoStats()
+        _check(self._L.bbk_pairinfo_estimate(self._h, C.byref(st)))
+        d = {f: getattr(st, f) for f, _ in PairInfoStats._fields_ if f != "percentiles"}
+        d["percentiles"] = [int(x) for x in st.percentiles]
+        d["ok"] = bool(st.ok)
+        return d
+
+    def hist(self):
+        """(insert sizes np.int32, counts np.uint64), ascending"""
+        n = int(self._L.bbk_pairinfo_hist_size(self._h))
+        a, c = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint64)
+        _check(self._L.bbk_pairinfo_hist_export(self._h, _ptr(a), _ptr(c)))
+        return a, c
+
+    def fill_begin(self, insert_size, round_distance=0, filter_threshold=0):
+        _check(self._L.bbk_pairinfo_fill_begin(self._h, int(insert_size), round_distance, filter_threshold))
+
+    def push_fill(self, first, second, orientation=ORIENT_FR, cut=None):
+        cut = self._cut(cut, len(first))
+        _check(self._L.bbk_pairinfo_push_fill(self._h, first._h, second._h, orientation, _ptr(cut) if cut is not None else None))
+
+    def fill_finish(self):
+        _check(self._L.bbk_pairinfo_fill_finish(self._h))
+
+    def points(self):
+        """(e1 np.uint64, e2 np.uint64, gap np.int32, weight np.uint64) of the index, ascending"""
+        n = int(self._L.bbk_pairinfo_points(self._h))
+        e1, e2 = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
+        gap, w = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.uint64)
+        _check(self._L.bbk_pairinfo_export(self._h, _ptr(e1), _ptr(e2), _ptr(gap), _ptr(w)))
+        return e1, e2, gap, w
+
+    def write(self, path):
+        """the index in the layout of PairedBuffer::BinWrite (.prd), ids = edge + 1"""
+        _check(self._L.bbk_pairinfo_write(self._h, str(path).encode()))
 
 
 class Profiles(_Handle):

@@ -1,0 +1,310 @@
+// spades-pairinfo: the paired-end side of spades-core's PairInfoCount stage as a tool of its own (the reference has the
+// stage only inside spades-core, projects/spades/pair_info_count.cpp:328-417, so this is a new tool and not a drop-in):
+//   <graph (in GFA)> <dataset description (in YAML)> <output prefix> -k <value>
+//   [-b <bytes>] [-t <value>] [--device <value>] [--min-edge-length <n>] [--meta] [--filter-threshold <t>]
+//   [--max-distance-coeff <x>] [--rounding-coeff <x>] [--rounding-threshold <n>]
+// Every paired-end library (left reads / right reads in lock step, with its orientation) is read twice: the estimate pass
+// (CollectLibInformation, :199-243: insert sizes and edge pairs) and the fill pass (the DEFilter counts of :379-400 come
+// from the estimate pass here; ProcessPairedReads, :285-324).  Per library i, counted from 0 over the dataset:
+//   <prefix>.<i>.is.hist   "<insert size>\t<count>\n", ascending
+//   <prefix>.<i>.lib       "key value" lines: the counters and the statistics, doubles as std::ostream prints them
+//   <prefix>.<i>.prd       the raw paired index (bbk_pairinfo_write); absent when the insert size cannot be estimated
+// The bound on the edge length is --min-edge-length, or with it the N50 of the graph unless --meta is given (:335-337).
+// The defaults are the shipped configuration: raw_filter_threshold 2 (1 in meta_mode.info), max_distance_coeff 2.0,
+// rounding_coeff 0.5, rounding_threshold 0 (configs/debruijn/distance_estimation.info), which makes the round bound 0.
+// Refused, naming the library: mate-pair libraries and libraries whose reads are shorter than k (the reference maps both
+// with BWA), and interlaced libraries.  Long-read, contig and single-read libraries are skipped.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "common.hpp"
+
+using namespace bbkhost;
+
+static void usage(const char *argv0) {
+    printf("SYNOPSIS\n        %s <graph (in GFA)> <dataset description (in YAML)> <output prefix> -k <value>\n"
+           "           [-b <value>] [-t <value>] [--device <value>] [--min-edge-length <value>] [--meta]\n"
+           "           [--filter-threshold <value>] [--max-distance-coeff <value>] [--rounding-coeff <value>]\n"
+           "           [--rounding-threshold <value>]\n\n"
+           "OPTIONS\n"
+           "        -k <value>  k-mer length of the graph\n"
+           "        -b <value>  bytes of read sequence per batch\n"
+           "        -t, --threads <value>\n                    # of threads to use\n"
+           "        --device <value>  GPU to use (default 0)\n"
+           "        --min-edge-length <value>\n                    shortest edge an insert size is taken from (default 0)\n"
+           "        --meta      metagenomic mode: the bound is not raised to the N50 of the graph, filter threshold 1\n"
+           "        --filter-threshold <value>\n                    edge pairs seen at most this often are dropped (default 2; 0: none)\n"
+           "        --max-distance-coeff <value>, --rounding-coeff <value>, --rounding-threshold <value>\n"
+           "                    distances are rounded to min(max-distance-coeff * deviation * rounding-coeff,\n"
+           "                    rounding-threshold) (defaults 2.0, 0.5, 0: no rounding)\n",
+           argv0);
+}
+
+// Nx (assembly_graph/core/basic_graph_stats.hpp:97-113) over every edge of the graph: a segment is an edge and its
+// conjugate, a self-conjugate segment one edge
+static uint64_t graph_nx(const std::vector<uint64_t> &seg_len, const std::vector<uint8_t> &self_conj, double percent) {
+    uint64_t sum = 0;
+    std::vector<uint64_t> lengths;
+    for (size_t s = 0; s < seg_len.size(); ++s)
+        for (int c = self_conj[s] ? 1 : 2; c > 0; --c) {
+            lengths.push_back(seg_len[s]);
+            sum += seg_len[s];
+        }
+    std::sort(lengths.begin(), lengths.end());
+    double len_perc = (1.0 - percent * 0.01) * (double)sum;
+    for (size_t i = 0; i < lengths.size(); ++i) {
+        if ((double)lengths[i] >= len_perc) return lengths[i];
+        len_perc -= (double)lengths[i];
+    }
+    return 0;
+}
+
+static bool is_nucl(char c) { return memchr("ACGTacgt", c, 8) != nullptr; }  // common/sequence/nucl.hpp:45-62
+
+// LongestValidCoords (io/reads/longest_valid_wrapper.hpp:15-42): [from, to) of the first longest run of nucleotides
+static void longest_valid(const std::string &seq, size_t &from, size_t &to) {
+    size_t best_len = 0, best_pos = 0, pos = std::string::npos;
+    for (size_t i = 0; i <= seq.size(); ++i) {
+        if (i < seq.size() && is_nucl(seq[i])) {
+            if (pos == std::string::npos) pos = i;
+        } else {
+            if (pos != std::string::npos && i - pos > best_len) {
+                best_len = i - pos;
+                best_pos = pos;
+            }
+            pos = std::string::npos;
+        }
+    }
+    from = best_len ? best_pos : 0;
+    to = from + best_len;
+}
+
+// the mates of a batch, cut to their LongestValid stretches, and what was cut (left1, right1, left2, right2 per pair)
+struct PairBatch {
+    std::string bases[2];
+    std::vector<uint64_t> off[2];
+    std::vector<uint32_t> cut;
+    PairBatch() { clear(); }
+    void clear() {
+        for (int m = 0; m < 2; ++m) {
+            bases[m].clear();
+            off[m].assign(1, 0);
+        }
+        cut.clear();
+    }
+    uint64_t pairs() const { return off[0].size() - 1; }
+    size_t bytes() const { return bases[0].size() + bases[1].size(); }
+    void add(int m, const std::string &seq) {
+        size_t from, to;
+        longest_valid(seq, from, to);
+        bases[m].append(seq, from, to - from);
+        off[m].push_back(bases[m].size());
+        cut.push_back((uint32_t)(to > from ? from : 0));
+        cut.push_back((uint32_t)(to > from ? seq.size() - to : 0));
+    }
+};
+
+// one pass over a library: every batch of pairs goes to push(first, second, h_cut); returns the longest read seen
+template <class Push>
+static size_t for_each_batch(bbk_ctx *ctx, const DatasetLib &L, size_t batch_bytes, uint64_t &n_pairs, Push push) {
+    PairBatch b;
+    size_t max_len = 0;
+    n_pairs = 0;
+    auto flush = [&] {
+        if (b.pairs() == 0) return;
+        bbk_reads *r[2] = {nullptr, nullptr};
+        for (int m = 0; m < 2; ++m)
+            check(bbk_reads_from_ascii(ctx, b.bases[m].data(), b.off[m].data(), b.pairs(), &r[m]), "bbk_reads_from_ascii");
+        push(r[0], r[1], b.cut.data());
+        bbk_reads_free(r[0]);
+        bbk_reads_free(r[1]);
+        n_pairs += b.pairs();
+        b.clear();
+    };
+    for (size_t i = 0; i < L.v[LIB_LEFT].size(); ++i) {
+        FastxReader r1(L.v[LIB_LEFT][i]), r2(L.v[LIB_RIGHT][i]);
+        if (!r1.is_open()) fatal("Cannot open %s", L.v[LIB_LEFT][i].c_str());
+        if (!r2.is_open()) fatal("Cannot open %s", L.v[LIB_RIGHT][i].c_str());
+        info("Processing %s and %s", L.v[LIB_LEFT][i].c_str(), L.v[LIB_RIGHT][i].c_str());
+        std::string n1, s1, q1, n2, s2, q2;
+        // a pair needs both mates: the stream ends with the shorter file
+        while (r1.next_record(n1, s1, q1) && r2.next_record(n2, s2, q2)) {
+            max_len = std::max(max_len, std::max(s1.size(), s2.size()));
+            b.add(0, s1);
+            b.add(1, s2);
+            if (b.bytes() >= batch_bytes) flush();
+        }
+    }
+    flush();
+    return max_len;
+}
+
+static void write_text(const std::string &path, const std::string &text) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) fatal("cannot open %s for writing", path.c_str());
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
+}
+
+static std::string lib_text(const bbk_pairinfo_stats &st) {
+    char buf[128];
+    std::string o;
+    auto u = [&](const char *key, unsigned long long v) { o.append(buf, (size_t)snprintf(buf, sizeof(buf), "%s %llu\n", key, v)); };
+    auto d = [&](const char *key, double v) { o.append(buf, (size_t)snprintf(buf, sizeof(buf), "%s %g\n", key, v)); };
+    u("total", st.total);
+    u("mapped", st.mapped);
+    u("negative", st.negative);
+    u("edge_pairs", st.edge_pairs);
+    d("mean", st.mean);
+    d("deviation", st.deviation);
+    d("median", st.median);
+    d("mad", st.mad);
+    d("left_quantile", st.left_quantile);
+    d("right_quantile", st.right_quantile);
+    for (int i = 0; i < 19; ++i)
+        o.append(buf, (size_t)snprintf(buf, sizeof(buf), "percentile_%d %llu\n", 5 * (i + 1), (unsigned long long)st.percentiles[i]));
+    u("ok", st.ok ? 1 : 0);
+    return o;
+}
+
+static int orientation_of(const std::string &o, size_t lib) {
+    if (o.empty() || o == "fr") return BBK_ORIENT_FR;  // (the default of a paired-end library, pipeline/library.cpp)
+    if (o == "ff") return BBK_ORIENT_FF;
+    if (o == "rf") return BBK_ORIENT_RF;
+    if (o == "rr") return BBK_ORIENT_RR;
+    fatal("library #%zu: unknown orientation \"%s\"", lib, o.c_str());
+}
+
+int main(int argc, char **argv) {
+    unsigned k = 0, device = 0, filter_threshold = 2, rounding_thr = 0;
+    unsigned long long threads = 0, bufsize = 268435456ull, min_edge_length = 0;
+    double max_distance_coeff = 2.0, rounding_coeff = 0.5;
+    bool meta = false;
+    std::vector<std::string> pos;
+    Options opt;
+    opt.num("-k", "", &k, 0u, 999u).num("-t", "--threads", &threads).num("-b", "", &bufsize, 1ull).num("", "--device", &device)
+        .num("", "--min-edge-length", &min_edge_length).flag("", "--meta", &meta)
+        .num("", "--filter-threshold", &filter_threshold).real("", "--max-distance-coeff", &max_distance_coeff)
+        .real("", "--rounding-coeff", &rounding_coeff).num("", "--rounding-threshold", &rounding_thr).positional(&pos);
+    if (!opt.parse(argc, argv) || pos.size() != 3 || !opt.seen("-k")) {
+        usage(argv[0]);
+        return 1;
+    }
+    if (meta && !opt.seen("--filter-threshold")) filter_threshold = 1;  // raw_filter_threshold of meta_mode.info
+    const std::string graph = pos[0], dataset = pos[1], prefix = pos[2];
+    info("Starting paired info counting (MI355X, %s)", bbk_version());
+    check_graph_k(k);
+    info("K-mer length set to %u", k);
+    require_gfa(graph);
+
+    std::vector<DatasetLib> libs;
+    std::string err;
+    if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
+    // what cannot be done is refused before anything is written
+    std::vector<int> paired(libs.size(), 0);
+    for (size_t i = 0; i < libs.size(); ++i) {
+        const DatasetLib &L = libs[i];
+        const std::string &t = L.type;
+        if (t == "mate-pairs" || t == "hq-mate-pairs" || t == "nxmate")
+            fatal("library #%zu: mate-pair libraries (%s) are not supported: the reference maps them with BWA", i, t.c_str());
+        if (!t.empty() && t != "paired-end") {
+            info("Library #%zu (%s) is not a paired-end library, skipping", i, t.c_str());
+            continue;
+        }
+        if (!L.v[LIB_INTERLACED].empty())
+            fatal("library #%zu: interlaced reads are not supported: give the mates as left reads / right reads", i);
+        if (L.v[LIB_LEFT].empty() && L.v[LIB_RIGHT].empty()) {
+            info("Library #%zu has no paired reads, skipping", i);
+            continue;
+        }
+        if (L.v[LIB_LEFT].size() != L.v[LIB_RIGHT].size())
+            fatal("library #%zu: %zu left but %zu right read files", i, L.v[LIB_LEFT].size(), L.v[LIB_RIGHT].size());
+        orientation_of(L.orientation, i);
+        paired[i] = 1;
+    }
+
+    Run run;
+    run.create_ctx(device);
+    bbk_ctx *ctx = run.ctx;
+    info("Loading de Bruijn graph from %s", graph.c_str());
+    bbk_edgeindex *ix = nullptr;
+    check(bbk_edgeindex_from_gfa(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa");
+    const uint64_t ns = bbk_edgeindex_segments(ix);
+    info("Graph: %llu edges, %llu %u-mers indexed", (unsigned long long)ns, (unsigned long long)bbk_edgeindex_size(ix), k + 1);
+    uint64_t edge_length_threshold = min_edge_length;
+    if (!meta) {
+        std::vector<uint64_t> seg_len(ns);
+        std::vector<uint8_t> self_conj(ns);
+        check(bbk_edgeindex_export_segments(ix, seg_len.data(), self_conj.data()), "bbk_edgeindex_export_segments");
+        edge_length_threshold = std::max<uint64_t>(edge_length_threshold, graph_nx(seg_len, self_conj, 50));
+    }
+    info("Min edge length for estimation: %llu", (unsigned long long)edge_length_threshold);
+    (void)threads;  // the mates are read in lock step by this thread; the option is accepted as every tool accepts it
+
+    for (size_t i = 0; i < libs.size(); ++i) {
+        if (!paired[i]) continue;
+        const DatasetLib &L = libs[i];
+        const int orientation = orientation_of(L.orientation, i);
+        const std::string base = prefix + "." + std::to_string(i);
+        info("Estimating insert size for library #%zu", i);
+        bbk_pairinfo *pi = nullptr;
+        check(bbk_pairinfo_begin(ctx, ix, edge_length_threshold, &pi), "bbk_pairinfo_begin");
+        uint64_t n_pairs = 0;
+        const size_t rl = for_each_batch(ctx, L, (size_t)bufsize, n_pairs, [&](bbk_reads *a, bbk_reads *b, const uint32_t *cut) {
+            check(bbk_pairinfo_push_estimate(pi, a, b, orientation, cut), "bbk_pairinfo_push_estimate");
+        });
+        if (n_pairs > 0 && rl < k)
+            fatal("library #%zu: its reads (at most %zu bases) are shorter than K (%u): the reference maps such a library "
+                  "with BWA, which is not supported", i, rl, k);
+        bbk_pairinfo_stats st;
+        check(bbk_pairinfo_estimate(pi, &st), "bbk_pairinfo_estimate");
+        info("Edge pairs: %llu", (unsigned long long)st.edge_pairs);
+        info("%llu paired reads (%g%% of all) aligned to long edges", (unsigned long long)st.mapped,
+             (double)st.mapped * 100.0 / (double)st.total);
+        if (st.negative > 3 * st.mapped)
+            info("WARN Too much reads aligned with negative insert size. Is the library orientation set properly?");
+        {
+            const uint64_t nh = bbk_pairinfo_hist_size(pi);
+            std::vector<int32_t> is(nh);
+            std::vector<uint64_t> cnt(nh);
+            check(bbk_pairinfo_hist_export(pi, is.data(), cnt.data()), "bbk_pairinfo_hist_export");
+            std::string text;
+            char buf[64];
+            for (uint64_t j = 0; j < nh; ++j)
+                text.append(buf, (size_t)snprintf(buf, sizeof(buf), "%d\t%llu\n", is[j], (unsigned long long)cnt[j]));
+            write_text(base + ".is.hist", text);
+            write_text(base + ".lib", lib_text(st));
+        }
+        if (!st.ok) {  // pair_info_count.cpp:356-367
+            info("WARN Unable to estimate insert size for paired library #%zu", i);
+            if (rl > 0 && rl <= k) info("WARN Maximum read length (%zu) should be greater than K (%u)", rl, k);
+            else if (rl <= (size_t)k * 11 / 10) info("WARN Maximum read length (%zu) is probably too close to K (%u)", rl, k);
+            else info("WARN None of paired reads aligned properly. Please, check orientation of your read pairs.");
+            bbk_pairinfo_free(pi);
+            continue;
+        }
+        info("  Insert size = %g, deviation = %g, left quantile = %g, right quantile = %g, read length = %zu", st.mean,
+             st.deviation, st.left_quantile, st.right_quantile, rl);
+        if (st.mean < 1.1 * (double)rl)
+            info("WARN Estimated mean insert size %g is very small compared to read length %zu", st.mean, rl);
+        unsigned round_thr = 0;  // pair_info_count.cpp:292-296: no rounding when the filter is off
+        if (filter_threshold)
+            round_thr = (unsigned)std::min(max_distance_coeff * st.deviation * rounding_coeff, (double)rounding_thr);
+        info("Left insert size quantile %g, right insert size quantile %g, filtering threshold %u, rounding threshold %u",
+             st.left_quantile, st.right_quantile, filter_threshold, round_thr);
+        info("Mapping library #%zu", i);
+        check(bbk_pairinfo_fill_begin(pi, (uint64_t)st.mean, round_thr, filter_threshold), "bbk_pairinfo_fill_begin");
+        for_each_batch(ctx, L, (size_t)bufsize, n_pairs, [&](bbk_reads *a, bbk_reads *b, const uint32_t *cut) {
+            check(bbk_pairinfo_push_fill(pi, a, b, orientation, cut), "bbk_pairinfo_push_fill");
+        });
+        check(bbk_pairinfo_fill_finish(pi), "bbk_pairinfo_fill_finish");
+        info("Paired index: %llu points; saving to %s.prd", (unsigned long long)bbk_pairinfo_points(pi), base.c_str());
+        check(bbk_pairinfo_write(pi, (base + ".prd").c_str()), "bbk_pairinfo_write");
+        bbk_pairinfo_free(pi);
+    }
+    bbk_edgeindex_free(ix);
+    info("Paired info counting finished");
+    run.done("spades-pairinfo");
+}
