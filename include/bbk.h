@@ -450,6 +450,45 @@ int bbk_pairinfo_export(const bbk_pairinfo *pi, uint64_t *h_e1, uint64_t *h_e2, 
 int bbk_pairinfo_write(const bbk_pairinfo *pi, const char *path);
 void bbk_pairinfo_free(bbk_pairinfo *pi);
 
+/* ---- distance estimation: the raw paired index clustered on the graph distances between the two edges of every stored
+ *      pair (projects/spades/distance_estimation.cpp:137-154: DistanceEstimator, common/paired_info/distance_estimation.cpp,
+ *      and PairInfoWeightChecker; csrc/distest.hip).  Left out: RefinePairedInfo (it cannot fire on this output),
+ *      PairInfoImprover, the scaffolding index and amb_de.  Parity is with a restatement (tests/distest_restated.py) --- */
+typedef struct bbk_clustered bbk_clustered; /* the clustered index on the host */
+/* A raw index from host points instead of reads: every point goes under the smaller of (e1, e2) and (conj e2, conj e1)
+ * with its gap (the gap is the same under both), the points are sorted, and equal (e1, e2, gap) have their weights
+ * added: what bbk_pairinfo_fill_finish leaves.  Weights are stored weights (bbk_pairinfo_export's): nothing is doubled,
+ * so an exported index comes back as it was.  BBK_ERR_ARG: an edge the graph does not have. */
+int bbk_pairinfo_import(bbk_ctx *ctx, const bbk_edgeindex *ix, uint64_t n, const uint64_t *h_e1, const uint64_t *h_e2,
+                        const int32_t *h_gap, const uint64_t *h_weight, bbk_pairinfo **out);
+typedef struct bbk_cluster_params { /* estimate_distance (distance_estimation.cpp:137-154) */
+    uint64_t insert_size;      /* (size_t) math::round(mean_insert_size) */
+    uint64_t read_length;      /* the library's read length */
+    uint64_t delta;            /* size_t(deviation) */
+    uint64_t linkage_distance; /* size_t(linkage_distance_coeff * deviation); shipped coefficient 0.0 */
+    uint64_t max_distance;     /* size_t(max_distance_coeff * deviation); shipped coefficient 2.0 */
+    double filter_threshold;   /* clustered_filter_threshold; shipped 2.0 */
+} bbk_cluster_params;
+/* Clusters the points of a filled (or imported) index.  The index must keep its graph
+ * (bbk_edgeindex_from_gfa_with_graph); its vertices and their CSR go to the device with the first call.  A pair whose
+ * search would make 500 calls or more, whose ball holds more than 512 vertices, or any pair when insert_size + delta -
+ * k - 2 > 2047, is searched on the host by the literal backtracking search (ties by ascending edge number); so is every
+ * pair when BBK_NO_DISTEST_DEVICE is set.  BBK_ERR_ARG: before bbk_pairinfo_fill_finish, an index without a graph,
+ * insert_size + delta - k - 2 <= 0 (the reference's VERIFY), a distance parameter of 2^24 or more. */
+int bbk_pairinfo_cluster(bbk_pairinfo *pi, const bbk_cluster_params *params, bbk_clustered **out);
+/* Clusters ascending (e1, e2, centre) under the canonical pair only: centre = the distance (not the gap) and var = the
+ * half-span as the reference's floats, weight in half-units (twice the weight; a pair with e1 == conj e2 carries four
+ * times its clusters' weight, as the reference's buffer and merge leave it).  Any pointer may be NULL. */
+uint64_t bbk_clustered_points(const bbk_clustered *c);
+uint64_t bbk_clustered_pairs(const bbk_clustered *c);      /* edge pairs the raw index held */
+uint64_t bbk_clustered_host_pairs(const bbk_clustered *c); /* of these, searched on the host */
+int bbk_clustered_export(const bbk_clustered *c, uint64_t *h_e1, uint64_t *h_e2, float *h_centre, float *h_var,
+                         uint64_t *h_weight);
+/* <path> in the layout of bbk_pairinfo_write: a point is float gap = centre - length(e1), float weight (PointT inherits
+ * RawPointT::BinWrite, index_point.hpp:195-197, 218-259: 8 bytes, no variance).  Ids are edge + 1. */
+int bbk_clustered_write(const bbk_clustered *c, const char *path);
+void bbk_clustered_free(bbk_clustered *c);
+
 /* ---- k-mer multiplicity profiles across samples: replaces KmerMultiplicityCounter::FilterCombinedKmers
  *      (projects/mts/kmer_multiplicity_counter.cpp:72-139: one KMC database per sample, sorted and merged under
  *      RtSeq::less3 = BBK_ORDER_SORTED) and, for the lookup, the BooPHF map of BuildKmerIndex (:141-181) -- and contig

@@ -6,8 +6,8 @@ csrc/).  This package is the thin Python binding used by tests and bench.py; the
 fallback: importing works anywhere, but creating a Context without the library or without a
 GPU raises.
 """
-from .engine import (Context, Reads, KMerSet, ExtIndex, Unitigs, EdgeIndex, Profiles, PairInfo, KmerProfile, HamClusters, SubClusters, Expander, Corrector, HammerReads, Corrected, FastqText, FastqInput, BBKError, lib_path, load_library,  # noqa: F401
+from .engine import (Context, Reads, KMerSet, ExtIndex, Unitigs, EdgeIndex, Profiles, PairInfo, Clustered, KmerProfile, HamClusters, SubClusters, Expander, Corrector, HammerReads, Corrected, FastqText, FastqInput, BBKError, lib_path, load_library,  # noqa: F401
                      BOTH_STRANDS, CANONICAL, WITH_COUNTS, UNSORTED, REFERENCE_ORDER, WITH_MASKS, ORDER_SORTED, ORDER_REFERENCE_BUCKETS16, NO_TRIM, ORIENT_FF, ORIENT_FR, ORIENT_RF, ORIENT_RR)
 
-__all__ = ["Context", "Reads", "KMerSet", "ExtIndex", "Unitigs", "EdgeIndex", "Profiles", "PairInfo", "KmerProfile", "HamClusters", "SubClusters", "Expander", "Corrector", "HammerReads", "Corrected", "FastqText", "FastqInput", "BBKError", "lib_path", "load_library",
+__all__ = ["Context", "Reads", "KMerSet", "ExtIndex", "Unitigs", "EdgeIndex", "Profiles", "PairInfo", "Clustered", "KmerProfile", "HamClusters", "SubClusters", "Expander", "Corrector", "HammerReads", "Corrected", "FastqText", "FastqInput", "BBKError", "lib_path", "load_library",
            "BOTH_STRANDS", "CANONICAL", "WITH_COUNTS", "UNSORTED", "REFERENCE_ORDER", "WITH_MASKS", "ORDER_SORTED", "ORDER_REFERENCE_BUCKETS16", "NO_TRIM", "ORIENT_FF", "ORIENT_FR", "ORIENT_RF", "ORIENT_RR"]

@@ -3,12 +3,16 @@
 // batch.  Not part of the C ABI.
 #pragma once
 
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "bbk_internal.h"
 
 namespace bbk {
+
+struct DeDeviceGraph;  // distest.hip: the graph as a CSR on the device
 
 // one record of the edge index, 16 bytes: one dwordx4 load per found position
 struct EdgePos {
@@ -35,6 +39,9 @@ struct bbk_edgeindex {
     bbk::PrefixIndex prefix;             // over keys, built for k1
     bbk::DevBuf seg;                     // n_seg u32: len[s] | kSegSelfConj when the segment is its own conjugate
     std::vector<uint32_t> seg_h;         // the same on the host
+    // the vertices and the CSR of the distance-estimation stage, built by the first bbk_pairinfo_cluster over the index
+    mutable std::shared_ptr<bbk::DeDeviceGraph> de_graph;
+    mutable std::mutex de_mutex;
 };
 
 namespace bbk {
@@ -53,3 +60,27 @@ struct bbk_paths {
     bbk::DevBuf ranges;  // n_ranges bbk_path_range in read order
 };
 
+// the paired-read info of one library (pairinfo.hip fills it, distest.hip clusters its points)
+struct bbk_pairinfo {
+    struct Run {  // reduced records: ascending distinct keys with their counts
+        bbk::DevBuf keys, vals;
+        uint64_t n = 0;
+    };
+    bbk_ctx *ctx = nullptr;
+    const bbk_edgeindex *ix = nullptr;
+    uint64_t min_edge_length = 0;
+    int edge_bits = 1;
+    // estimate pass
+    uint64_t total = 0, mapped = 0, negative = 0, est_records = 0;
+    std::vector<Run> is_runs, pair_runs;  // after bbk_pairinfo_estimate: one run each, the histogram and the pair table
+    bool estimated = false;
+    std::vector<int32_t> hist_is;
+    std::vector<uint64_t> hist_count;
+    // fill pass
+    bool filling = false, filled = false;
+    uint64_t insert_size = 0, fill_records = 0;
+    uint32_t round_distance = 0, threshold = 0;
+    std::vector<Run> point_runs;
+    std::vector<uint64_t> pt_e1, pt_e2, pt_weight;
+    std::vector<int32_t> pt_gap;
+};

@@ -48,30 +48,6 @@
 #include "edgeindex.h"
 #include "kmer_ops.h"
 
-struct bbk_pairinfo {
-    struct Run {  // reduced records: ascending distinct keys with their counts
-        bbk::DevBuf keys, vals;
-        uint64_t n = 0;
-    };
-    bbk_ctx *ctx = nullptr;
-    const bbk_edgeindex *ix = nullptr;
-    uint64_t min_edge_length = 0;
-    int edge_bits = 1;
-    // estimate pass
-    uint64_t total = 0, mapped = 0, negative = 0, est_records = 0;
-    std::vector<Run> is_runs, pair_runs;  // after bbk_pairinfo_estimate: one run each, the histogram and the pair table
-    bool estimated = false;
-    std::vector<int32_t> hist_is;
-    std::vector<uint64_t> hist_count;
-    // fill pass
-    bool filling = false, filled = false;
-    uint64_t insert_size = 0, fill_records = 0;
-    uint32_t round_distance = 0, threshold = 0;
-    std::vector<Run> point_runs;
-    std::vector<uint64_t> pt_e1, pt_e2, pt_weight;
-    std::vector<int32_t> pt_gap;
-};
-
 namespace bbk {
 
 constexpr uint64_t kIsNone = 0xFFFFFFFFull;  // the insert-size key of a pair that does not count (is is a positive int)

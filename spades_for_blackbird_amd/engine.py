@@ -17,6 +17,12 @@ PATH_RANGE = np.dtype([("edge", np.uint64), ("read", np.uint32), ("init_start", 
 ORIENT_FF, ORIENT_FR, ORIENT_RF, ORIENT_RR = 0, 1, 2, 3  # BBK_ORIENT_*: which mate is reverse-complemented
 
 
+class ClusterParams(C.Structure):
+    """bbk_cluster_params of include/bbk.h"""
+    _fields_ = [("insert_size", C.c_uint64), ("read_length", C.c_uint64), ("delta", C.c_uint64),
+                ("linkage_distance", C.c_uint64), ("max_distance", C.c_uint64), ("filter_threshold", C.c_double)]
+
+
 class PairInfoStats(C.Structure):
     """bbk_pairinfo_stats of include/bbk.h"""
     _fields_ = [("total", C.c_uint64), ("mapped", C.c_uint64), ("negative", C.c_uint64), ("edge_pairs", C.c_uint64),
@@ -49,6 +55,8 @@ SYMBOLS = [
     "bbk_edgeindex_export_segments", "bbk_pairinfo_begin", "bbk_pairinfo_push_estimate", "bbk_pairinfo_estimate", "bbk_pairinfo_hist_size", "bbk_pairinfo_hist_export",
     "bbk_pairinfo_fill_begin", "bbk_pairinfo_push_fill", "bbk_pairinfo_fill_finish", "bbk_pairinfo_points", "bbk_pairinfo_export",
     "bbk_pairinfo_write", "bbk_pairinfo_free",
+    "bbk_pairinfo_import", "bbk_pairinfo_cluster", "bbk_clustered_points", "bbk_clustered_pairs", "bbk_clustered_host_pairs",
+    "bbk_clustered_export", "bbk_clustered_write", "bbk_clustered_free",
     "bbk_kmerprofile_begin", "bbk_kmerprofile_add_sample", "bbk_kmerprofile_finish", "bbk_kmerprofile_abort",
     "bbk_kmerprofile_size", "bbk_kmerprofile_samples", "bbk_kmerprofile_k", "bbk_kmerprofile_export",
     "bbk_kmerprofile_write", "bbk_kmerprofile_load", "bbk_kmerprofile_abundance", "bbk_kmerprofile_abundance_pieces",
@@ -252,6 +260,14 @@ def load_library():
         L.bbk_pairinfo_export.argtypes = [vp, vp, vp, vp, vp]
         L.bbk_pairinfo_write.argtypes = [vp, C.c_char_p]
         L.bbk_pairinfo_free.argtypes = [vp]
+        L.bbk_pairinfo_import.argtypes = [vp, vp, u64, vp, vp, vp, vp, C.POINTER(vp)]
+        L.bbk_pairinfo_cluster.argtypes = [vp, C.POINTER(ClusterParams), C.POINTER(vp)]
+        for f in ("points", "pairs", "host_pairs"):
+            getattr(L, "bbk_clustered_" + f).restype = u64
+            getattr(L, "bbk_clustered_" + f).argtypes = [vp]
+        L.bbk_clustered_export.argtypes = [vp, vp, vp, vp, vp, vp]
+        L.bbk_clustered_write.argtypes = [vp, C.c_char_p]
+        L.bbk_clustered_free.argtypes = [vp]
     L.bbk_kmerprofile_begin.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(vp)]
     L.bbk_kmerprofile_add_sample.argtypes = [vp, C.c_uint, vp]
     L.bbk_kmerprofile_finish.argtypes = [vp, u64, u64, C.POINTER(vp)]
@@ -1511,6 +1527,17 @@ class EdgeIndex(_Handle):
         _check(self._L.bbk_pairinfo_begin(self.ctx._h, self._h, min_edge_length, C.byref(h)))
         return PairInfo(self, h)
 
+    def pairinfo_from_points(self, e1, e2, gap, weight):
+        """a filled PairInfo from host points (bbk_pairinfo_import): canonicalised, sorted, equal points added"""
+        e1, e2 = np.ascontiguousarray(e1, dtype=np.uint64), np.ascontiguousarray(e2, dtype=np.uint64)
+        gap, weight = np.ascontiguousarray(gap, dtype=np.int32), np.ascontiguousarray(weight, dtype=np.uint64)
+        if not (e1.shape == e2.shape == gap.shape == weight.shape and e1.ndim == 1):
+            raise ValueError("e1, e2, gap and weight must be one-dimensional and equally long")
+        h = C.c_void_p()
+        _check(self._L.bbk_pairinfo_import(self.ctx._h, self._h, len(e1), _ptr(e1), _ptr(e2), _ptr(gap), _ptr(weight),
+                                           C.byref(h)))
+        return PairInfo(self, h)
+
     def graph(self):
         """(names, sequences, links [(a, '+'|'-', b, '+'|'-')], kc np.uint32) as the index holds the graph"""
         ns, nl = self.segments, int(self._L.bbk_edgeindex_links(self._h))
@@ -1586,6 +1613,50 @@ class PairInfo(_Handle):
     def write(self, path):
         """the index in the layout of PairedBuffer::BinWrite (.prd), ids = edge + 1"""
         _check(self._L.bbk_pairinfo_write(self._h, str(path).encode()))
+
+    def cluster(self, insert_size, read_length, delta, linkage_distance=0, max_distance=0, filter_threshold=2.0):
+        """DistanceEstimator and the weight filter over the points (bbk_pairinfo_cluster): a Clustered.  The index must
+        keep its graph (edgeindex_from_gfa(..., keep_graph=True))"""
+        prm = ClusterParams(int(insert_size), int(read_length), int(delta), int(linkage_distance), int(max_distance),
+                            float(filter_threshold))
+        h = C.c_void_p()
+        _check(self._L.bbk_pairinfo_cluster(self._h, C.byref(prm), C.byref(h)))
+        return Clustered(self, h)
+
+
+class Clustered(_Handle):
+    """the clustered paired index of one library: export() or write()"""
+    _free = "bbk_clustered_free"
+
+    def __init__(self, pairinfo, h):
+        super().__init__(pairinfo.ctx, h)
+        self.pairinfo = pairinfo  # the raw index (and with it the edge index) must outlive the handle
+
+    def __len__(self):
+        return int(self._L.bbk_clustered_points(self._h))
+
+    @property
+    def pairs(self):
+        """edge pairs of the raw index"""
+        return int(self._L.bbk_clustered_pairs(self._h))
+
+    @property
+    def host_pairs(self):
+        """of these, the pairs the host searched"""
+        return int(self._L.bbk_clustered_host_pairs(self._h))
+
+    def export(self):
+        """(e1 np.uint64, e2 np.uint64, centre np.float32, half-span np.float32, weight in half-units np.uint64),
+        ascending (e1, e2, centre)"""
+        n = len(self)
+        e1, e2, w = (np.zeros(n, dtype=np.uint64) for _ in range(3))
+        c, v = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.float32)
+        _check(self._L.bbk_clustered_export(self._h, _ptr(e1), _ptr(e2), _ptr(c), _ptr(v), _ptr(w)))
+        return e1, e2, c, v, w
+
+    def write(self, path):
+        """the index in the layout of PairedBuffer::BinWrite (.clustered.prd), ids = edge + 1"""
+        _check(self._L.bbk_clustered_write(self._h, str(path).encode()))
 
 
 class Profiles(_Handle):

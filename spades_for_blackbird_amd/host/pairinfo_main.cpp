@@ -3,18 +3,25 @@
 //   <graph (in GFA)> <dataset description (in YAML)> <output prefix> -k <value>
 //   [-b <bytes>] [-t <value>] [--device <value>] [--min-edge-length <n>] [--meta] [--filter-threshold <t>]
 //   [--max-distance-coeff <x>] [--rounding-coeff <x>] [--rounding-threshold <n>]
+//   [--cluster] [--read-length <n>] [--linkage-distance-coeff <x>] [--clustered-filter-threshold <x>]
 // Every paired-end library (left reads / right reads in lock step, with its orientation) is read twice: the estimate pass
 // (CollectLibInformation, :199-243: insert sizes and edge pairs) and the fill pass (the DEFilter counts of :379-400 come
 // from the estimate pass here; ProcessPairedReads, :285-324).  Per library i, counted from 0 over the dataset:
 //   <prefix>.<i>.is.hist   "<insert size>\t<count>\n", ascending
 //   <prefix>.<i>.lib       "key value" lines: the counters and the statistics, doubles as std::ostream prints them
 //   <prefix>.<i>.prd       the raw paired index (bbk_pairinfo_write); absent when the insert size cannot be estimated
+//   <prefix>.<i>.clustered.prd   with --cluster: the clustered index of the next stage, DistanceEstimation
+//                          (projects/spades/distance_estimation.cpp:137-154; bbk_pairinfo_cluster, bbk_clustered_write),
+//                          with the parameters of estimate_distance from the statistics above: insert size
+//                          math::round(mean), delta size_t(deviation), linkage and maximal distance their coefficient
+//                          times the deviation, read length the longest mate seen or --read-length
 // The bound on the edge length is --min-edge-length, or with it the N50 of the graph unless --meta is given (:335-337).
 // The defaults are the shipped configuration: raw_filter_threshold 2 (1 in meta_mode.info), max_distance_coeff 2.0,
 // rounding_coeff 0.5, rounding_threshold 0 (configs/debruijn/distance_estimation.info), which makes the round bound 0.
 // Refused, naming the library: mate-pair libraries and libraries whose reads are shorter than k (the reference maps both
 // with BWA), and interlaced libraries.  Long-read, contig and single-read libraries are skipped.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -27,7 +34,8 @@ static void usage(const char *argv0) {
     printf("SYNOPSIS\n        %s <graph (in GFA)> <dataset description (in YAML)> <output prefix> -k <value>\n"
            "           [-b <value>] [-t <value>] [--device <value>] [--min-edge-length <value>] [--meta]\n"
            "           [--filter-threshold <value>] [--max-distance-coeff <value>] [--rounding-coeff <value>]\n"
-           "           [--rounding-threshold <value>]\n\n"
+           "           [--rounding-threshold <value>] [--cluster] [--read-length <value>]\n"
+           "           [--linkage-distance-coeff <value>] [--clustered-filter-threshold <value>]\n\n"
            "OPTIONS\n"
            "        -k <value>  k-mer length of the graph\n"
            "        -b <value>  bytes of read sequence per batch\n"
@@ -38,7 +46,12 @@ static void usage(const char *argv0) {
            "        --filter-threshold <value>\n                    edge pairs seen at most this often are dropped (default 2; 0: none)\n"
            "        --max-distance-coeff <value>, --rounding-coeff <value>, --rounding-threshold <value>\n"
            "                    distances are rounded to min(max-distance-coeff * deviation * rounding-coeff,\n"
-           "                    rounding-threshold) (defaults 2.0, 0.5, 0: no rounding)\n",
+           "                    rounding-threshold) (defaults 2.0, 0.5, 0: no rounding)\n"
+           "        --cluster   also estimate distances: write <prefix>.<i>.clustered.prd (the maximal distance is\n"
+           "                    max-distance-coeff * deviation)\n"
+           "        --read-length <value>\n                    read length of the library (default: the longest mate seen)\n"
+           "        --linkage-distance-coeff <value>\n                    graph distances this close (times the deviation) form one cluster (default 0.0)\n"
+           "        --clustered-filter-threshold <value>\n                    clusters lighter than this are dropped (default 2.0)\n",
            argv0);
 }
 
@@ -180,14 +193,17 @@ static int orientation_of(const std::string &o, size_t lib) {
 int main(int argc, char **argv) {
     unsigned k = 0, device = 0, filter_threshold = 2, rounding_thr = 0;
     unsigned long long threads = 0, bufsize = 268435456ull, min_edge_length = 0;
-    double max_distance_coeff = 2.0, rounding_coeff = 0.5;
-    bool meta = false;
+    unsigned long long read_length = 0;
+    double max_distance_coeff = 2.0, rounding_coeff = 0.5, linkage_coeff = 0.0, clustered_threshold = 2.0;
+    bool meta = false, cluster = false;
     std::vector<std::string> pos;
     Options opt;
     opt.num("-k", "", &k, 0u, 999u).num("-t", "--threads", &threads).num("-b", "", &bufsize, 1ull).num("", "--device", &device)
         .num("", "--min-edge-length", &min_edge_length).flag("", "--meta", &meta)
         .num("", "--filter-threshold", &filter_threshold).real("", "--max-distance-coeff", &max_distance_coeff)
-        .real("", "--rounding-coeff", &rounding_coeff).num("", "--rounding-threshold", &rounding_thr).positional(&pos);
+        .real("", "--rounding-coeff", &rounding_coeff).num("", "--rounding-threshold", &rounding_thr).flag("", "--cluster", &cluster)
+        .num("", "--read-length", &read_length).real("", "--linkage-distance-coeff", &linkage_coeff)
+        .real("", "--clustered-filter-threshold", &clustered_threshold).positional(&pos);
     if (!opt.parse(argc, argv) || pos.size() != 3 || !opt.seen("-k")) {
         usage(argv[0]);
         return 1;
@@ -230,7 +246,8 @@ int main(int argc, char **argv) {
     bbk_ctx *ctx = run.ctx;
     info("Loading de Bruijn graph from %s", graph.c_str());
     bbk_edgeindex *ix = nullptr;
-    check(bbk_edgeindex_from_gfa(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa");
+    if (cluster) check(bbk_edgeindex_from_gfa_with_graph(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa_with_graph");
+    else check(bbk_edgeindex_from_gfa(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa");
     const uint64_t ns = bbk_edgeindex_segments(ix);
     info("Graph: %llu edges, %llu %u-mers indexed", (unsigned long long)ns, (unsigned long long)bbk_edgeindex_size(ix), k + 1);
     uint64_t edge_length_threshold = min_edge_length;
@@ -302,6 +319,25 @@ int main(int argc, char **argv) {
         check(bbk_pairinfo_fill_finish(pi), "bbk_pairinfo_fill_finish");
         info("Paired index: %llu points; saving to %s.prd", (unsigned long long)bbk_pairinfo_points(pi), base.c_str());
         check(bbk_pairinfo_write(pi, (base + ".prd").c_str()), "bbk_pairinfo_write");
+        if (cluster) {  // estimate_distance (distance_estimation.cpp:137-154)
+            bbk_cluster_params prm;
+            prm.insert_size = (uint64_t)std::floor(st.mean + 0.5 + 1e-10);  // math::round (math/xmath.h:324-330)
+            prm.read_length = opt.seen("--read-length") ? read_length : rl;
+            prm.delta = (uint64_t)st.deviation;
+            prm.linkage_distance = (uint64_t)(linkage_coeff * st.deviation);
+            prm.max_distance = (uint64_t)(max_distance_coeff * st.deviation);
+            prm.filter_threshold = clustered_threshold;
+            info("Estimating distances: insert size %llu, read length %llu, delta %llu, linkage distance %llu, max distance %llu",
+                 (unsigned long long)prm.insert_size, (unsigned long long)prm.read_length, (unsigned long long)prm.delta,
+                 (unsigned long long)prm.linkage_distance, (unsigned long long)prm.max_distance);
+            bbk_clustered *cl = nullptr;
+            check(bbk_pairinfo_cluster(pi, &prm, &cl), "bbk_pairinfo_cluster");
+            info("Clustered index: %llu points of %llu edge pairs (%llu searched on the host); saving to %s.clustered.prd",
+                 (unsigned long long)bbk_clustered_points(cl), (unsigned long long)bbk_clustered_pairs(cl),
+                 (unsigned long long)bbk_clustered_host_pairs(cl), base.c_str());
+            check(bbk_clustered_write(cl, (base + ".clustered.prd").c_str()), "bbk_clustered_write");
+            bbk_clustered_free(cl);
+        }
         bbk_pairinfo_free(pi);
     }
     bbk_edgeindex_free(ix);

@@ -1,0 +1,342 @@
+"""GPU: the distance-estimation stage (csrc/distest.hip, spades-pairinfo --cluster) against its restatement
+(tests/distest_restated.py).  Every comparison is exact: the same pairs, the same float bits of centre and half-span, the
+same half-unit weights, the same file bytes, and host_pairs equal to the pairs the restatement finds at 500 calls or
+more, at 2999 ball vertices or more, or beyond the device's capacities (stated in tests/distest_cases.py, not read from
+the engine).  Every graph is also run with BBK_NO_DISTEST_DEVICE, which sends every pair through the host's literal
+search: the same bytes.
+
+(a) the hand-derived cases of tests/test_distest_restated.py through pairinfo_from_points.  (b) the grouping: 0, 1, 63,
+64, 65 and 257 first edges; one first edge with 1, 64 and 65 second edges (a vertex of these graphs has at most four
+edges a side, as in any de Bruijn graph: the second edges hang in a tree below the first).  (c) each capacity at capacity - 1, capacity
+and capacity + 1: a ball of 511, 512, 513 vertices, U = 2046, 2047, 2048.  (d) the order-free boundary: a chain of bubbles
+at 499 and at 500 calls, and 3000 one-(k+1)-mer edges in a row, where the Dijkstra meets its vertex limit.  (e) random
+junction-rich graphs with cycles, conjugate links and palindromes, where some searches run into their limits and the
+order of the incoming edges decides.  (f) the tool on the two synthetic graphs of tests/test_gpu_pairinfo.py (on the junction-rich one the insert size
+cannot be estimated and the tool writes no index; the library clusters its raw points with the nominal geometry).
+(g) argument errors."""
+import os
+import random
+import subprocess
+
+import numpy as np
+import pytest
+
+import spades_for_blackbird_amd as B
+from spades_for_blackbird_amd import build, build_host
+from tests import distest_cases as Cs
+from tests import distest_restated as D
+from tests import gmapper_restated as G
+from tests import pairinfo_cases as PCs
+from tests import pairinfo_restated as P
+
+pytestmark = pytest.mark.gpu
+
+SWITCH = "BBK_NO_DISTEST_DEVICE"
+
+
+@pytest.fixture(scope="module")
+def bins():
+    build.build()
+    return {os.path.basename(p): p for p in build_host.build()}
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = B.Context(0)
+    yield c
+    c.close()
+
+
+def _export(cl):
+    """the clusters with every float as its bit pattern"""
+    e1, e2, c, v, w = cl.export()
+    return list(zip(e1.tolist(), e2.tolist(), c.view(np.uint32).tolist(), v.view(np.uint32).tolist(), w.tolist()))
+
+
+def _bits(records):
+    f = lambda x: int(np.float32(x).view(np.uint32))  # noqa: E731
+    return [(e1, e2, f(c), f(v), w) for e1, e2, c, v, w in records]
+
+
+def _cluster(pi, p):
+    return pi.cluster(p.insert_size, p.read_length, p.delta, p.linkage_distance, p.max_distance, p.filter_threshold)
+
+
+def _check(ctx, tmp_path, monkeypatch, gfa, points, p, hard=None):
+    """engine == restatement for one graph and one set of host points, on the device path and on the host path;
+    hard: the pairs expected on the host (None: what the restatement finds).  Returns the restatement's Clustering"""
+    g = G.Graph.from_gfa(gfa, Cs.K)
+    path = tmp_path / "g.gfa"
+    path.write_text(gfa)
+    ix = ctx.edgeindex_from_gfa(str(path), Cs.K, keep_graph=True)
+    canon = D.canonical_points(g, points)
+    want = D.Clustering(g, canon, p)
+    cols = [np.array([pt[i] for pt in points], dtype=t) for i, t in enumerate((np.uint64, np.uint64, np.int32, np.uint64))]
+    pi = ix.pairinfo_from_points(*cols)
+    e1, e2, gap, w = pi.points()
+    assert list(zip(e1.tolist(), e2.tolist(), gap.tolist(), w.tolist())) == canon
+    if hard is None:
+        hard = want.hard_pairs(Cs.BALL_CAP, Cs.U_CAP)
+    monkeypatch.delenv(SWITCH, raising=False)
+    cl = _cluster(pi, p)
+    assert _export(cl) == _bits(want.records)
+    assert (cl.pairs, cl.host_pairs) == (len(want.calls), len(hard))
+    out = tmp_path / "x.clustered.prd"
+    cl.write(out)
+    assert out.read_bytes() == want.file_bytes()
+    monkeypatch.setenv(SWITCH, "1")
+    on_host = _cluster(pi, p)
+    monkeypatch.delenv(SWITCH)
+    assert _export(on_host) == _bits(want.records) and on_host.host_pairs == len(want.calls)
+    for h in (cl, on_host, pi, ix):
+        h.close()
+    return want
+
+
+# ---- (a) the hand-derived cases ----------------------------------------------------------------------------------------
+
+def test_a_single_path_and_filter(ctx, tmp_path, monkeypatch):
+    b, (A, M, Bq) = Cs.single_path()
+    g = b.graph()
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), [(g.conj[Bq], g.conj[A], 48, 3), (A, Bq, 55, 2), (A, Bq, 55, 0)],
+                  Cs.params())
+    assert want.records == [(A, Bq, 150.0, 0.0, 10)]
+    assert _check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 48, 1)], Cs.params()).records == []
+    assert len(_check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 48, 1)], Cs.params(threshold=0.5)).records) == 1
+    assert len(_check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 48, 1)], Cs.params(threshold=0.0)).records) == 1
+
+
+@pytest.mark.parametrize("linkage,threshold", [(0, 2.0), (0, 0.0), (30, 0.0), (170, 2.0)])
+def test_a_bubble_ties_drops_and_linkage(ctx, tmp_path, monkeypatch, linkage, threshold):
+    b, (A, arms, Bq) = Cs.bubble()
+    pts = [(A, Bq, 30, 4), (A, Bq, 45, 2), (A, Bq, 58, 3), (A, Bq, 145, 7), (A, Bq, 320, 1), (A, Bq, -101, 9)]
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), pts, Cs.params(linkage=linkage, threshold=threshold))
+    expected = {(0, 2.0): [(130.0, 0.0, 10), (160.0, 0.0, 8)], (0, 0.0): [(130.0, 0.0, 10), (160.0, 0.0, 8), (330.0, 0.0, 0)],
+                (30, 0.0): [(145.0, 15.0, 18), (330.0, 0.0, 0)], (170, 2.0): [(230.0, 100.0, 18)]}
+    assert [r[2:] for r in want.records] == expected[(linkage, threshold)]
+
+
+def test_a_cycles_same_edge_no_path(ctx, tmp_path, monkeypatch):
+    b, (A, C, Bq) = Cs.cycle_between()
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 0, 3), (A, Bq, 215, 4)],
+                  Cs.params(max_distance=1000, threshold=0.0))
+    assert [r[2] for r in want.records] == [100.0 + 40 * j for j in range(11)]
+    b, (A, R) = Cs.cycle_through()
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, A, -100, 3), (A, A, 71, 2), (A, A + 1, 0, 1)],
+                  Cs.params(threshold=0.0))
+    assert [r[:3] for r in want.records] == [(A, A, 0.0), (A, A, 170.0)] and want.lengths[(A, A)] == [0, 170, 340, 510]
+    b, (A, Bq) = Cs.no_path()
+    assert _check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 30, 5)], Cs.params(threshold=0.0)).records == []
+
+
+def test_a_self_conjugate_pairs_and_palindrome(ctx, tmp_path, monkeypatch):
+    b, (A, Pl, Q) = Cs.hairpin()
+    pts = [(A, A + 1, 41, 3), (Pl, Pl, -41, 2), (A, Q, 0, 2), (Pl, A + 1, 0, 5), (A, Pl, 0, 5), (Q + 1, Pl, 41, 2)]
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), pts, Cs.params())
+    assert want.records[0] == (A, A + 1, 141.0, 0.0, 24) and (Pl, Pl, 0.0, 0.0, 16) in want.records
+
+
+# ---- (b) the grouping ----------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("n_first", [0, 1, 63, 64, 65, 257])
+def test_b_first_edges(ctx, tmp_path, monkeypatch, n_first):
+    b, (firsts, seconds) = Cs.paths(max(n_first, 1))
+    pairs = list(zip(firsts, seconds))[:n_first]
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), Cs.pair_points(pairs, [130] * n_first), Cs.params(threshold=1.0))
+    assert len(want.calls) == len(want.ball) == n_first and len(want.records) == n_first
+    assert all(r[2] == 130.0 for r in want.records)
+
+
+@pytest.mark.parametrize("n_second", [1, 64, 65])
+def test_b_second_edges_of_one_first_edge(ctx, tmp_path, monkeypatch, n_second):
+    b, (A, edges, depths) = Cs.tree(n_second)
+    pts = Cs.pair_points([(A, e) for e in edges], [100 + 23 * d for d in depths])
+    # insert size 300: min_len = 100 + 23 - 100 - 23 - 40 < 0, so the empty walk to the root's edges counts
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), pts, Cs.params(insert_size=300, threshold=1.0))
+    assert len(want.calls) == n_second and len(want.ball) == 1
+    assert [r[2] for r in want.records] == [100.0 + 23 * d for d in depths]
+
+
+# ---- (c) the capacities --------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("vertices", [Cs.BALL_CAP - 1, Cs.BALL_CAP, Cs.BALL_CAP + 1])
+def test_c_ball_capacity(ctx, tmp_path, monkeypatch, vertices):
+    b, (A, edges, depths) = Cs.tree(vertices - 1)
+    # U = 150 + 40 - 23 = 167 reaches all five levels of the tree (5 * 23 = 115): the root and a vertex per edge
+    pts = [(A, edges[0], 3, 3), (A, edges[0], -2, 1), (A, edges[-1], 23 * depths[-1], 2)]
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), pts, Cs.params(insert_size=150),
+                  hard=[(A, edges[0]), (A, edges[-1])] if vertices > Cs.BALL_CAP else [])
+    assert want.ball[A] == vertices and depths[-1] == 4
+    assert want.records == [(A, edges[0], 100.0, 0.0, 8), (A, edges[-1], 192.0, 0.0, 4)]
+
+
+@pytest.mark.parametrize("U", [Cs.U_CAP - 1, Cs.U_CAP, Cs.U_CAP + 1])
+def test_c_u_capacity(ctx, tmp_path, monkeypatch, U):
+    b, (A, C, Bq) = Cs.cycle_between()
+    p = Cs.params(insert_size=U - 40 + Cs.K + 2, threshold=0.0)
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 0, 3), (A, Bq, 1960, 4), (A, Bq, 1985, 2)], p,
+                  hard=[(A, Bq)] if U > Cs.U_CAP else [])
+    # walks 0, 40, ..., 2040 <= U; min_len = (U - 217) + 23 - 200 - 40 is 1612 +- 1, so the distances are 1740 ... 2140.
+    # d = 100 is further than 80 from all of them, d = 2060 falls on one, d = 2085 is nearest to 2100
+    assert want.U == U and [r[2] for r in want.records] == [1740.0 + 40 * j for j in range(11)]
+    assert [r[4] for r in want.records] == [0] * 8 + [8, 4, 0]
+
+
+# ---- (d) the order-free boundary and the vertex limit -------------------------------------------------------------------
+
+@pytest.mark.parametrize("calls", [499, 500])
+def test_d_bubble_chain_at_the_boundary(ctx, tmp_path, monkeypatch, calls):
+    b, (A, Bq) = Cs.bubble_chain(*Cs.BOUNDARY[calls])
+    # a second pair of the same first edge, ending one edge earlier, stays on the device either way
+    mid = 2 * (len(b.segs) - 2)
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), [(A, Bq, 990, 3), (A, Bq, 1013, 2), (A, mid, 970, 2)],
+                  Cs.boundary_params(), hard=[(A, Bq)] if calls >= 500 else [])
+    assert want.calls[(A, Bq)] == calls and want.calls[(A, mid)] < calls
+    assert len(want.lengths[(A, Bq)]) == 6 and want.records
+
+
+def test_d_vertex_limit_goes_to_the_host(ctx, tmp_path, monkeypatch):
+    gfa, (A, Bq) = Cs.one_mer_chain(3000)
+    want = _check(ctx, tmp_path, monkeypatch, gfa, [(A, Bq, 3000, 3)], Cs.params(insert_size=3100), hard=[(A, Bq)])
+    assert want.ball[A] == 3000 and want.records == []
+    gfa, (A, Bq) = Cs.one_mer_chain(600)  # 601 vertices within U: beyond the ball capacity, below the vertex limit
+    want = _check(ctx, tmp_path, monkeypatch, gfa, [(A, Bq, 600, 3)], Cs.params(insert_size=700), hard=[(A, Bq)])
+    assert want.records == [(A, Bq, 700.0, 0.0, 6)]
+    gfa, (A, Bq) = Cs.one_mer_chain(400)  # a ball of 402 vertices found in 401 relaxation rounds
+    want = _check(ctx, tmp_path, monkeypatch, gfa, [(A, Bq, 400, 3)], Cs.params(insert_size=500), hard=[])
+    assert want.records == [(A, Bq, 500.0, 0.0, 6)]
+
+
+# ---- (e) random graphs ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("seed", [0, 1, 2])
+def test_e_random_graphs(ctx, tmp_path, monkeypatch, seed):
+    b = Cs.random_graph(seed)
+    g = b.graph()
+    pts = Cs.random_points(g, seed)
+    rng = random.Random(seed)
+    rng.shuffle(pts)
+    want = _check(ctx, tmp_path, monkeypatch, b.gfa(), pts + pts[:7], Cs.params(linkage=(0, 5, 0)[seed]))
+    assert want.records and (seed == 1 or want.hard_pairs(Cs.BALL_CAP, Cs.U_CAP))
+
+
+# ---- (f) the tool --------------------------------------------------------------------------------------------------------
+
+def _fastq(path, seqs):
+    path.write_text("".join("@r%d/x\n%s\n+\n%s\n" % (i, s, "I" * len(s)) for i, s in enumerate(seqs)))
+    return path.name
+
+
+def _synth(ctx, tmp_path, sub, n_pairs, k=21):
+    """the graph of test_gpu_pairinfo.synth_graphs and pairs cut from its genome: (gfa path, Graph, pairs)"""
+    r = ctx.reads_synth(3000, read_len=150, genome_len=20000, sub_rate=sub, seed_genome=k, seed_reads=k + 1)
+    gfa = tmp_path / "g.gfa"
+    ctx.unitigs(ctx.extindex(r, k)).write_gfa(str(gfa))
+    return gfa, G.Graph.from_gfa(gfa.read_text(), k), PCs.cut_pairs(random.Random(k), PCs.synth_genome(k, 20000), n_pairs)
+
+
+def _tool(bins, tmp_path, gfa, pairs, extra):
+    y = tmp_path / "d.yaml"
+    y.write_text('- orientation: "fr"\n  type: "paired-end"\n  left reads:\n    - "%s"\n  right reads:\n    - "%s"\n' %
+                 (_fastq(tmp_path / "a_1.fastq", [a for a, _ in pairs]), _fastq(tmp_path / "a_2.fastq", [b for _, b in pairs])))
+    prefix = tmp_path / "out"
+    run = subprocess.run([bins["spades-pairinfo"], str(gfa), str(y), str(prefix), "-k", "21", "--meta", "--cluster"] + extra,
+                         capture_output=True, text=True)
+    assert run.returncode == 0, run.stderr
+    return prefix, run.stdout
+
+
+def test_f_tool_on_the_plain_graph(ctx, bins, tmp_path):
+    gfa, g, pairs = _synth(ctx, tmp_path, 0.0, 300)
+    prefix, stdout = _tool(bins, tmp_path, gfa, pairs, ["--read-length", "140", "--clustered-filter-threshold", "1.5"])
+    lib = P.Library(g, 0)
+    lib.push_estimate(pairs, P.FR)
+    st = lib.estimate()
+    assert st["ok"]
+    lib.push_fill(pairs, P.FR, int(st["mean"]), P.round_bound(st["deviation"], 1), 1)  # --meta: raw filter threshold 1
+    assert open("%s.0.prd" % prefix, "rb").read() == P.prd_bytes(lib.points())
+    want = D.Clustering(g, lib.points(), D.library_params(st["mean"], st["deviation"], 140, 0.0, 2.0, 1.5))
+    # one segment: the pair (0, 0) keeps its distance 0; (0, 1) and (1, 0) have no path
+    assert [r[:3] for r in want.records] == [(0, 0, 0.0)] and len(want.calls) == 3
+    assert open("%s.0.clustered.prd" % prefix, "rb").read() == want.file_bytes()
+    assert "Clustered index: 1 points of 3 edge pairs (0 searched on the host)" in stdout
+    # the longest mate seen is the default read length
+    prefix, stdout = _tool(bins, tmp_path, gfa, pairs, ["--linkage-distance-coeff", "0.5", "--max-distance-coeff", "3"])
+    p = D.library_params(st["mean"], st["deviation"], 150, 0.5, 3.0, 2.0)
+    assert "read length 150, delta %d, linkage distance %d, max distance %d" % (p.delta, p.linkage_distance, p.max_distance) in stdout
+    assert open("%s.0.clustered.prd" % prefix, "rb").read() == D.Clustering(g, lib.points(), p).file_bytes()
+
+
+def test_f_junction_rich_graph(ctx, bins, tmp_path, monkeypatch):
+    """gbuilder does not simplify: the substitutions leave a bubble or a tip each, no mate lies on one edge and the insert
+    size cannot be estimated, so the tool writes neither index, as the restatement has none.  The library takes the
+    nominal geometry of the pairs instead; about half of the searches make 500 calls or more between the bubbles."""
+    gfa, g, pairs = _synth(ctx, tmp_path, 0.003, 3)
+    prefix, stdout = _tool(bins, tmp_path, gfa, pairs, [])
+    lib = P.Library(g, 0)
+    lib.push_estimate(pairs, P.FR)
+    assert not lib.estimate()["ok"] and "Unable to estimate insert size for paired library #0" in stdout
+    assert not os.path.exists("%s.0.prd" % prefix) and not os.path.exists("%s.0.clustered.prd" % prefix)
+    lib.push_fill(pairs, P.FR, 400, 0, 0)
+    p = D.library_params(400.0, 30.0, 150, threshold=0.5)
+    want = D.Clustering(g, lib.points(), p)
+    hard = want.hard_pairs(Cs.BALL_CAP, Cs.U_CAP)
+    assert len(g.names) > 1000 and len(want.calls) > 400 and len(want.records) > 100 and 100 < len(hard) < len(want.calls)
+    ix = ctx.edgeindex_from_gfa(str(gfa), 21, keep_graph=True)
+    got_st, _, got_points = PCs.engine(ctx, ix, pairs, P.FR, insert_size=400)
+    assert got_points == lib.points()
+    pi = ix.pairinfo_from_points(*[np.array([pt[i] for pt in got_points], dtype=t)
+                                   for i, t in enumerate((np.uint64, np.uint64, np.int32, np.uint64))])
+    for on_host in (False, True):
+        if on_host:
+            monkeypatch.setenv(SWITCH, "1")
+        cl = _cluster(pi, p)
+        assert _export(cl) == _bits(want.records)
+        assert cl.host_pairs == (len(want.calls) if on_host else len(hard))
+    monkeypatch.delenv(SWITCH)
+
+
+def test_f_filled_index_clusters_like_imported(ctx, tmp_path):
+    """PairInfo.cluster straight after fill_finish, with no import in between"""
+    gfa, g, pairs = _synth(ctx, tmp_path, 0.0, 120)
+    ix = ctx.edgeindex_from_gfa(str(gfa), 21, keep_graph=True)
+    first, second = ctx.reads_from_ascii([a for a, _ in pairs]), ctx.reads_from_ascii([b for _, b in pairs])
+    pi = ix.pairinfo(0)
+    pi.push_estimate(first, second, P.FR, PCs.cuts(pairs))
+    st = pi.estimate()
+    pi.fill_begin(int(st["mean"]), 0, 0)
+    pi.push_fill(first, second, P.FR, PCs.cuts(pairs))
+    pi.fill_finish()
+    e1, e2, gap, w = pi.points()
+    p = D.library_params(st["mean"], st["deviation"], 150, threshold=1.0)
+    want = D.Clustering(g, list(zip(e1.tolist(), e2.tolist(), gap.tolist(), w.tolist())), p)
+    assert want.records and _export(_cluster(pi, p)) == _bits(want.records)
+
+
+# ---- (g) argument errors ---------------------------------------------------------------------------------------------------
+
+def test_g_argument_errors(ctx, tmp_path):
+    b, (A, M, Bq) = Cs.single_path()
+    path = tmp_path / "g.gfa"
+    path.write_text(b.gfa())
+    u64, i32 = (lambda *x: np.array(x, dtype=np.uint64)), (lambda *x: np.array(x, dtype=np.int32))
+    bare = ctx.edgeindex_from_gfa(str(path), Cs.K)
+    pi = bare.pairinfo_from_points(u64(A), u64(Bq), i32(48), u64(3))
+    with pytest.raises(B.BBKError, match="keeps no graph"):
+        pi.cluster(400, 100, 40)
+    ix = ctx.edgeindex_from_gfa(str(path), Cs.K, keep_graph=True)
+    pi = ix.pairinfo_from_points(u64(A), u64(Bq), i32(48), u64(3))
+    with pytest.raises(B.BBKError, match="is not positive"):
+        pi.cluster(20, 100, 3)  # 20 + 3 - 21 - 2 = 0
+    assert len(pi.cluster(21, 100, 3)) == 0  # U = 1
+    with pytest.raises(B.BBKError, match="2\\^24"):
+        pi.cluster(1 << 24, 100, 3)
+    with pytest.raises(B.BBKError, match="before bbk_pairinfo_fill_finish"):
+        ix.pairinfo().cluster(400, 100, 40)
+    with pytest.raises(B.BBKError, match="names edge 6"):
+        ix.pairinfo_from_points(u64(A), u64(6), i32(48), u64(3))
+    with pytest.raises(ValueError):
+        ix.pairinfo_from_points(u64(A, A), u64(Bq), i32(48), u64(3))
+    empty = ix.pairinfo_from_points(u64(), u64(), i32(), u64())
+    cl = empty.cluster(400, 100, 40)
+    assert len(cl) == 0 and cl.pairs == 0 and cl.host_pairs == 0
