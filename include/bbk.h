@@ -476,8 +476,9 @@ typedef struct bbk_cluster_params { /* estimate_distance (distance_estimation.cp
  * pair when BBK_NO_DISTEST_DEVICE is set.  BBK_ERR_ARG: before bbk_pairinfo_fill_finish, an index without a graph,
  * insert_size + delta - k - 2 <= 0 (the reference's VERIFY), a distance parameter of 2^24 or more. */
 int bbk_pairinfo_cluster(bbk_pairinfo *pi, const bbk_cluster_params *params, bbk_clustered **out);
-/* Clusters ascending (e1, e2, centre) under the canonical pair only: centre = the distance (not the gap) and var = the
- * half-span as the reference's floats, weight in half-units (twice the weight; a pair with e1 == conj e2 carries four
+/* Clusters ascending (e1, e2, centre) under the canonical pair only: centre = the distance (not the gap) as the
+ * reference's float, var = 0 (the reference's AddToResult drops ClusterResult's half-span: its buffer holds raw points),
+ * weight in half-units (twice the weight; a pair with e1 == conj e2 carries four
  * times its clusters' weight, as the reference's buffer and merge leave it).  Any pointer may be NULL. */
 uint64_t bbk_clustered_points(const bbk_clustered *c);
 uint64_t bbk_clustered_pairs(const bbk_clustered *c);      /* edge pairs the raw index held */

@@ -23,7 +23,7 @@ def build(force=False):
     stale = not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in src)
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
-    built = all(os.path.exists(os.path.join(_HERE, "_ref", f)) for f in ("libxxh3_ref.so", "hammer_ref"))
+    built = all(os.path.exists(os.path.join(_HERE, "_ref", f)) for f in ("libxxh3_ref.so", "hammer_ref", "graph_ref"))
     if os.path.isdir("/root/reference") and (force or not built):
         subprocess.check_call(["make", "-C", _HERE, "-j8", "ref"], stdout=subprocess.DEVNULL)
     return so

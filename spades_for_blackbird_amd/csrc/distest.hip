@@ -269,7 +269,10 @@ struct DeClusters {
                 r.e1 = e1;
                 r.e2 = e2;
                 r.centre = (float)((double)(left + last) * 0.5);
-                r.var = (float)((double)(last - left) * 0.5);
+                // ClusterResult computes (last - left) / 2, and AddToResult loses it: the thread's buffer holds raw points
+                // (PairedInfoBuffer has RawPointTraits, paired_info.hpp:711-712), so AddMany slices the variance off and
+                // Merge restores it as 0 (index_point.hpp:228-229).  Every cluster of the reference has variance 0
+                r.var = 0.0f;
                 r.weight = w;
                 out[n] = r;
             }

@@ -1646,7 +1646,7 @@ class Clustered(_Handle):
         return int(self._L.bbk_clustered_host_pairs(self._h))
 
     def export(self):
-        """(e1 np.uint64, e2 np.uint64, centre np.float32, half-span np.float32, weight in half-units np.uint64),
+        """(e1 np.uint64, e2 np.uint64, centre np.float32, half-span np.float32 (0, as the reference leaves it), weight in half-units np.uint64),
         ascending (e1, e2, centre)"""
         n = len(self)
         e1, e2, w = (np.zeros(n, dtype=np.uint64) for _ in range(3))

@@ -17,7 +17,10 @@ gmapper_restated.Graph and the raw points of pairinfo_restated (ascending (e1, e
   - DistanceEstimator::EstimateEdgePairDistances (:97-150), AbstractDistanceEstimator::ClusterResult (:51-67).
   - AddToResult / PairedIndex::Merge (paired_info_buffer.hpp:63-68, 103-133; paired_info.hpp:282-299): a pair that is its
     own conjugate (e1 == conj e2) has its clusters inserted twice into the thread's buffer and that buffer's histogram
-    merged twice into the result: four times the weight.
+    merged twice into the result: four times the weight.  The thread's buffer is a PairedInfoBuffer, whose points are raw
+    (RawPointTraits, paired_info.hpp:711-712): AddMany slices the half-span that ClusterResult computed off every cluster
+    and Merge restores it as 0 (index_point.hpp:228-229), so every cluster of the result has half-span 0
+    (tests/golden/graph_ref/ records it so; the earlier reading kept ClusterResult's value).
   - PairInfoFilter with PairInfoWeightChecker (pair_info_filters.hpp:42-56, 241-261): a point stays iff
     math::ge(weight, threshold).
   - PairedBuffer::BinWrite of the clustered index (paired_info_buffer.hpp:197-210): PointT (index_point.hpp:218-259) does
@@ -184,7 +187,7 @@ def cluster_result(estimated, linkage_distance):
 
 
 class Clustering:
-    """the clustered index of one library: records [(e1, e2, centre, half-span, weight in half-units)] ascending, and
+    """the clustered index of one library: records [(e1, e2, centre, half-span = 0, weight in half-units)] ascending, and
     per pair what its search met: calls[(e1, e2)] (the literal search's, or the recurrence's sum) and ball[e1]"""
 
     def __init__(self, g, points, p, lengths="search", keep_unfiltered=False):
@@ -211,9 +214,9 @@ class Clustering:
                 hist = [(gap + g.length(e1), 2 * w) for gap, w in sorted(by_pair[e1][e2])]
                 est = estimate_edge_pair(g, e1, e2, hist, raw, p.max_distance)
                 times = 4 if e1 == g.conj[e2] else 1
-                for centre, weight, var in cluster_result(est, p.linkage_distance):
+                for centre, weight, _ in cluster_result(est, p.linkage_distance):
                     if keep_unfiltered or ge(weight * times / 2.0, p.filter_threshold):
-                        self.records.append((e1, e2, centre, var, weight * times))
+                        self.records.append((e1, e2, centre, f32(0.0), weight * times))  # AddToResult drops the half-span
 
     def order_free(self, e1, e2):
         return self.calls[(e1, e2)] < VERTEX_USAGE_ENABLE_THRESHOLD and self.ball[e1] < MAX_DIJKSTRA_VERTICES - 1

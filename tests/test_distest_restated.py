@@ -55,9 +55,11 @@ def test_bubble_ties_drops_and_linkage():
     assert c.lengths == {(A, B): [130, 160, 330]}
     assert c.records == [(A, B, 130.0, 0.0, 10), (A, B, 160.0, 0.0, 8), (A, B, 330.0, 0.0, 0)]
     assert _records(g, pts, Cs.params()) == [(A, B, 130.0, 0.0, 10), (A, B, 160.0, 0.0, 8)]
-    # linkage_distance 30 joins 130 and 160: centre 145, half-span 15
-    assert _records(g, pts, Cs.params(linkage=30), keep_unfiltered=True) == [(A, B, 145.0, 15.0, 18), (A, B, 330.0, 0.0, 0)]
-    assert _records(g, pts, Cs.params(linkage=170)) == [(A, B, 230.0, 100.0, 18)]
+    # linkage_distance 30 joins 130 and 160: centre 145; ClusterResult's half-span 15 does not survive AddToResult (the
+    # reference's recorded clusters, tests/golden/graph_ref/bubble.json.gz, all have 0)
+    assert D.cluster_result([(130, 10), (160, 8), (330, 0)], 30) == [(145.0, 18, 15.0), (330.0, 0, 0.0)]
+    assert _records(g, pts, Cs.params(linkage=30), keep_unfiltered=True) == [(A, B, 145.0, 0.0, 18), (A, B, 330.0, 0.0, 0)]
+    assert _records(g, pts, Cs.params(linkage=170)) == [(A, B, 230.0, 0.0, 18)]
     # without the far point 330 is outside [130 - 80, 245 + 80] and is not kept at all
     assert [r[2] for r in _records(g, pts[:4], Cs.params(), keep_unfiltered=True)] == [130.0, 160.0]
     # a point with 2 d + len2 < len1 is skipped: d = -1 (gap -101), which alone would have kept nothing anyway
