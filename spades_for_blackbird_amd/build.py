@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbbk.so")
 SOURCES = ["pool.hip", "context.hip", "scan.hip", "sort.hip", "unique.hip", "msd.hip", "superk.hip", "reads.hip", "count.hip", "extindex.hip", "tipclip.hip", "atclip.hip", "readfilter.hip", "unitigs.hip", "unitigs_write.hip", "edgeprof.hip", "pairinfo.hip", "distest.hip", "kmerprof.hip", "hamclust.hip", "kmerstat.hip", "subclust.hip", "expand.hip", "readcorrect.hip", "hreads.hip", "readprint.hip", "group.hip", "fastqparse.hip", "kmerfilter.hip"]
-HEADERS = ["bbk_internal.h", "block_scan.h", "kmer_ops.h", "extwalk.h", "msd.h", "msd_part.h", "msd_bucket.h", "msd_narrow_a.h", "msd_stage_b.h", "msd_bucket_tail.h", "msd_mark_tail.h", "accum.h", "arena.h", "select.h", "unitigs.h", "hammer.h", "hammer_files.h", "readcorrect_host.hpp", "distest_host.hpp", os.path.join("..", "host", "hammer_reads.hpp"), "gfa_graph.h", "edgeindex.h", os.path.join("..", "..", "include", "bbk.h")]
+HEADERS = ["bbk_internal.h", "block_scan.h", "kmer_ops.h", "extwalk.h", "msd.h", "msd_part.h", "msd_bucket.h", "msd_narrow_a.h", "msd_stage_b.h", "msd_bucket_tail.h", "host_device.h", "edge_ops.h", "pairinfo_host.hpp", "msd_mark_tail.h", "accum.h", "arena.h", "select.h", "unitigs.h", "hammer.h", "hammer_files.h", "readcorrect_host.hpp", "distest_host.hpp", os.path.join("..", "host", "hammer_reads.hpp"), "gfa_graph.h", "edgeindex.h", os.path.join("..", "..", "include", "bbk.h")]
 ARCH = "gfx950"
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-fopenmp", "-Wall", "-Wno-unused-function"]
 

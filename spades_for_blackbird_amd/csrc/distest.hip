@@ -34,6 +34,11 @@
 // Weights are integer half-units in u64 (an exact tie gives half of a point's weight to each neighbour), so the result
 // is exact and independent of order; the reference sums floats, equal while a sum stays below 2^23.  Distances are
 // integers; the reference holds them as floats and compares within 4 ULPs, the same below 2^21.
+//
+// Where the rest lives.  The rules of an edge and the lower bound of a path length: edge_ops.h.  The point table, its
+// grouping into pairs and first edges, the weight threshold in half-units, the import's canonicalise-sort-merge and the
+// writer of the file: pairinfo_host.hpp.  bbk_pairinfo_cluster is a sequence of phases, each a function below:
+// cluster_params, group_pairs + upload_pairs, walk_on_device, search_on_host, estimate_clusters.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -41,7 +46,6 @@
 #include <cstdio>
 #include <cstring>
 #include <memory>
-#include <numeric>
 #include <string>
 #include <vector>
 
@@ -131,7 +135,7 @@ __global__ __launch_bounds__(64) void k_de_walk(uint64_t ng, const uint32_t *__r
     const uint64_t g = (uint64_t)blockIdx.y * gridDim.x + blockIdx.x;
     if (g >= ng) return;
     const uint32_t lane = threadIdx.x, p0 = grp[g], p1 = grp[g + 1];
-    const uint32_t e1 = pair_e1[p0], s0 = G.e_end[e1], len1 = G.seg[e1 >> 1] & ~kSegSelfConj;
+    const uint32_t e1 = pair_e1[p0], s0 = G.e_end[e1], len1 = edge_length(G.seg[e1 >> 1]);
     for (uint32_t s = lane; s < kDeSlots; s += 64) {
         key[s] = kDeEmpty;
         dist[s] = kDeNone;
@@ -156,7 +160,7 @@ __global__ __launch_bounds__(64) void k_de_walk(uint64_t ng, const uint32_t *__r
             const uint32_t v = key[s], d = __hip_atomic_load(&dist[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             for (uint32_t i = G.out_off[v]; i < G.out_off[v + 1]; ++i) {
                 const uint32_t e = G.out_e[i];
-                const uint64_t nd = (uint64_t)d + (G.seg[e >> 1] & ~kSegSelfConj);
+                const uint64_t nd = (uint64_t)d + edge_length(G.seg[e >> 1]);
                 if (nd <= P.U) de_relax(key, dist, mark[cur ^ 1], &count, &overflow, G.e_end[e], (uint32_t)nd);
             }
         }
@@ -165,9 +169,10 @@ __global__ __launch_bounds__(64) void k_de_walk(uint64_t ng, const uint32_t *__r
     const bool too_big = overflow != 0 || count > kDeBallCap;
 
     for (uint32_t p = p0; p < p1; ++p) {
-        const uint32_t e2 = pair_e2[p], t = G.e_start[e2], len2 = G.seg[e2 >> 1] & ~kSegSelfConj;
-        const int64_t lb = P.gap + (int64_t)P.k + 2 - (int64_t)len1 - (int64_t)len2 - (int64_t)P.delta;
-        const uint32_t min_len = lb <= 0 ? 0u : lb > (int64_t)P.U ? P.U + 1 : (uint32_t)lb;
+        const uint32_t e2 = pair_e2[p], t = G.e_start[e2], len2 = edge_length(G.seg[e2 >> 1]);
+        // no walk is longer than U: a bound beyond it is as good as U + 1, which fits the worklist's 32-bit lengths
+        const uint64_t lb = path_length_lower_bound(P.k, len1, len2, P.gap, P.delta);
+        const uint32_t min_len = lb > P.U ? P.U + 1 : (uint32_t)lb;
         bits[lane] = 0;
         bool is_hard = too_big;
         const bool reached = !too_big && de_lookup(key, dist, t) != kDeNone;
@@ -192,7 +197,7 @@ __global__ __launch_bounds__(64) void k_de_walk(uint64_t ng, const uint32_t *__r
                 // IncomingEdges(v): the conjugates of the edges that start at conj v
                 for (uint32_t i = G.out_off[v ^ 1u]; i < G.out_off[(v ^ 1u) + 1]; ++i) {
                     const uint32_t ec = G.out_e[i], sv = G.e_end[ec] ^ 1u;
-                    const uint64_t ln = G.seg[ec >> 1] & ~kSegSelfConj;
+                    const uint64_t ln = edge_length(G.seg[ec >> 1]);
                     const uint32_t d = de_lookup(key, dist, sv);
                     if (d == kDeNone || (uint64_t)d + ln + l > P.U) continue;
                     const uint32_t at = atomicAdd(&tail, 1u);
@@ -306,11 +311,10 @@ __global__ __launch_bounds__(256) void k_de_estimate(uint64_t np, const uint32_t
     if (p >= np) return;
     const uint32_t e1 = pair_e1[p], e2 = pair_e2[p], a = pair_pt[p], b = pair_pt[p + 1];
     const uint32_t s1 = seg[e1 >> 1], s2 = seg[e2 >> 1];
-    const int64_t len1 = s1 & ~kSegSelfConj, len2 = s2 & ~kSegSelfConj, md = (int64_t)P.max_distance;
-    const uint32_t conj2 = (s2 & kSegSelfConj) ? e2 : e2 ^ 1u;
+    const int64_t len1 = edge_length(s1), len2 = edge_length(s2), md = (int64_t)P.max_distance;
     DeClusters<WRITE> cl;
     cl.linkage = (int64_t)P.linkage;
-    cl.times = e1 == conj2 ? 4 : 1;
+    cl.times = pair_is_self_conj(e1, e2, seg) ? 4 : 1;
     cl.min_weight = P.min_weight;
     cl.e1 = e1;
     cl.e2 = e2;
@@ -362,6 +366,13 @@ __global__ __launch_bounds__(256) void k_de_estimate(uint64_t np, const uint32_t
 
 // ---- host ---------------------------------------------------------------------------------------------------------------
 
+// a host array to the device on the stream; the array stays until the stream has been waited for
+template <class T>
+static void upload(bbk_ctx *ctx, DevBuf &d, const std::vector<T> &v) {
+    d.alloc(v.size() * sizeof(T));
+    if (!v.empty()) BBK_HIP(hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+}
+
 static std::shared_ptr<DeDeviceGraph> device_graph(bbk_ctx *ctx, const bbk_edgeindex *ix) {
     std::lock_guard<std::mutex> lock(ix->de_mutex);
     if (ix->de_graph) return ix->de_graph;
@@ -369,29 +380,146 @@ static std::shared_ptr<DeDeviceGraph> device_graph(bbk_ctx *ctx, const bbk_edgei
                 (unsigned long long)ix->n_seg);
     auto g = std::make_shared<DeDeviceGraph>();
     de_build_graph(ix->k, ix->n_seg, ix->seg_h.data(), ix->links.data(), ix->links.size() / 4, ix->kc.data(), g->h);
-    auto up = [&](DevBuf &d, const std::vector<uint32_t> &v) {
-        d.alloc(v.size() * 4);
-        if (!v.empty()) BBK_HIP(hipMemcpyAsync(d.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    };
-    up(g->out_off, g->h.out_off);
-    up(g->out_e, g->h.out_e);
-    up(g->e_end, g->h.end);
-    up(g->e_start, g->h.start);
+    upload(ctx, g->out_off, g->h.out_off);
+    upload(ctx, g->out_e, g->h.out_e);
+    upload(ctx, g->e_end, g->h.end);
+    upload(ctx, g->e_start, g->h.start);
     BBK_HIP(hipStreamSynchronize(ctx->stream));
     ix->de_graph = g;
     return g;
 }
 
-// math::ge(weight, threshold) on doubles (math/xmath.h:210-322): not (weight < threshold and more than 4 ULPs apart)
-static bool math_ge(double a, double b) {
-    auto biased = [](double x) {
-        uint64_t u;
-        memcpy(&u, &x, 8);
-        return (u >> 63) ? ~u + 1 : u | (1ull << 63);
+// ---- the phases of bbk_pairinfo_cluster ---------------------------------------------------------------------------------
+
+// the checks on the parameters of a call and the integers every phase reads
+static DeParams cluster_params(const bbk_edgeindex *ix, const bbk_cluster_params *prm) {
+    BBK_REQUIRE(ix->has_graph, BBK_ERR_ARG,
+                "bbk_pairinfo_cluster: the index keeps no graph (load it with bbk_edgeindex_from_gfa_with_graph)");
+    // PairInfoPathLengthUpperBound's VERIFY (pair_info_bounds.hpp:16-21)
+    BBK_REQUIRE(prm->insert_size + prm->delta > (uint64_t)ix->k + 2, BBK_ERR_ARG,
+                "bbk_pairinfo_cluster: insert_size %llu + delta %llu - k %u - 2 is not positive",
+                (unsigned long long)prm->insert_size, (unsigned long long)prm->delta, ix->k);
+    const uint64_t U = prm->insert_size + prm->delta - ix->k - 2;
+    BBK_REQUIRE(U < (1ull << 24) && prm->insert_size < (1ull << 24) && prm->read_length < (1ull << 24) &&
+                    prm->max_distance < (1ull << 24) && prm->linkage_distance < (1ull << 24),
+                BBK_ERR_ARG, "bbk_pairinfo_cluster: a distance parameter of 2^24 or more");
+    BBK_REQUIRE(!std::isnan(prm->filter_threshold), BBK_ERR_ARG, "bbk_pairinfo_cluster: filter_threshold is not a number");
+    DeParams P{};
+    P.k = ix->k;
+    P.U = (uint32_t)U;
+    P.words = (uint32_t)(U >> 5) + 1;
+    P.gap = (int64_t)prm->insert_size - 2 * (int64_t)prm->read_length;
+    P.delta = prm->delta;
+    P.linkage = prm->linkage_distance;
+    P.max_distance = prm->max_distance;
+    P.min_weight = least_half_units(prm->filter_threshold);
+    return P;
+}
+
+// the pairs and the first edges of the ascending points (pair_groups, pairinfo_host.hpp) and what the kernels read of
+// them; the host arrays live as long as their copies may be in flight
+struct DePairs {
+    PairGroups h;
+    uint64_t n = 0, np = 0, ng = 0;  // points, pairs, first edges
+    DevBuf pe1, pe2, ppt, grp, gap, w;
+};
+
+static DePairs group_pairs(const PairPoints &pt) {
+    DePairs d;
+    d.n = pt.size();
+    BBK_REQUIRE(d.n < (1ull << 32) - 1, BBK_ERR_ARG, "bbk_pairinfo_cluster: 2^32 - 1 points or more");
+    d.h = pair_groups(pt);
+    d.np = d.h.pairs();
+    d.ng = d.h.firsts();
+    return d;
+}
+
+static void upload_pairs(bbk_ctx *ctx, const PairPoints &pt, DePairs &d) {
+    upload(ctx, d.pe1, d.h.pe1);
+    upload(ctx, d.pe2, d.h.pe2);
+    upload(ctx, d.ppt, d.h.ppt);
+    upload(ctx, d.grp, d.h.grp);
+    upload(ctx, d.gap, pt.gap);
+    upload(ctx, d.w, pt.weight);
+}
+
+// k_de_walk over every first edge: the rows of the pairs it finished; returns hard[p] = 1 for those it left to the host,
+// which is every pair under the A/B switch BBK_NO_DISTEST_DEVICE or with U beyond the bitmap
+static std::vector<uint32_t> walk_on_device(bbk_ctx *ctx, const bbk_edgeindex *ix, const DeDeviceGraph &G, const DePairs &d,
+                                            const DeParams &P, DevBuf &rows) {
+    std::vector<uint32_t> hard(d.np, 1);
+    if (getenv("BBK_NO_DISTEST_DEVICE") != nullptr || P.U > kDeUCap) return hard;
+    DevBuf d_hard(d.np * 4);
+    const DeGraphView V{G.out_off.as<uint32_t>(), G.out_e.as<uint32_t>(), G.e_end.as<uint32_t>(), G.e_start.as<uint32_t>(),
+                        ix->seg.as<uint32_t>()};
+    {
+        KernelTimer t(ctx, "distest_walk", (double)d.np * P.words * 4);
+        hipLaunchKernelGGL(k_de_walk, grid_blocks(d.ng), dim3(64), 0, ctx->stream, d.ng, d.grp.as<uint32_t>(),
+                           d.pe1.as<uint32_t>(), d.pe2.as<uint32_t>(), V, P, rows.as<uint32_t>(), d_hard.as<uint32_t>());
+        check_launch("k_de_walk");
+    }
+    d2h_sync(ctx, hard.data(), d_hard.p, d.np * 4);
+    return hard;
+}
+
+// the host's pairs: one Dijkstra per first edge that has any, the literal search per pair (distest_host.hpp), and their
+// rows scattered into their places; returns how many there were
+static uint64_t search_on_host(bbk_ctx *ctx, const DeGraph &g, const DePairs &d, const DeParams &P,
+                               const std::vector<uint32_t> &hard, DevBuf &rows) {
+    const std::vector<uint32_t> &pe1 = d.h.pe1, &pe2 = d.h.pe2;
+    std::vector<uint32_t> hidx;
+    for (uint64_t p = 0; p < d.np; ++p)
+        if (hard[p]) hidx.push_back((uint32_t)p);
+    const uint64_t nh = hidx.size();
+    if (nh == 0) return 0;
+    std::vector<uint32_t> hrows(nh * P.words, 0);
+    std::vector<uint64_t> first;  // where the pairs of a first edge begin in hidx
+    for (uint64_t i = 0; i < nh; ++i)
+        if (!i || pe1[hidx[i]] != pe1[hidx[i - 1]]) first.push_back(i);
+    first.push_back(nh);
+#pragma omp parallel num_threads(16)
+    {
+        DeSearch s(g);
+#pragma omp for schedule(dynamic, 1)
+        for (int64_t f = 0; f < (int64_t)first.size() - 1; ++f) {
+            const uint32_t e1 = pe1[hidx[first[f]]];
+            s.dijkstra(g.end[e1], P.U);
+            for (uint64_t i = first[f]; i < first[f + 1]; ++i) {
+                const uint32_t e2 = pe2[hidx[i]];
+                s.lengths(g.end[e1], g.start[e2], path_length_lower_bound(P.k, g.length(e1), g.length(e2), P.gap, P.delta),
+                          &hrows[i * P.words]);
+            }
+        }
+    }
+    DevBuf d_hidx, d_hrows;
+    upload(ctx, d_hidx, hidx);
+    upload(ctx, d_hrows, hrows);
+    launch_items(ctx, "k_de_scatter", k_de_scatter, nh * P.words, nh * P.words, P.words, d_hidx.as<uint32_t>(),
+                 d_hrows.as<uint32_t>(), rows.as<uint32_t>());
+    BBK_HIP(hipStreamSynchronize(ctx->stream));  // the host vectors leave scope
+    return nh;
+}
+
+// count, scan and write of k_de_estimate, then the clusters on the host
+static std::vector<DeRec> estimate_clusters(bbk_ctx *ctx, const bbk_edgeindex *ix, const DePairs &d, const DeParams &P,
+                                            const DevBuf &rows) {
+    DevBuf cnt(d.np * 8), rec;
+    auto estimate = [&](auto write, DeRec *o) {
+        KernelTimer t(ctx, "distest_estimate", (double)d.n * 12 + (double)d.np * P.words * 4);
+        launch_items(ctx, "k_de_estimate", k_de_estimate<decltype(write)::value>, d.np, d.np, d.pe1.as<uint32_t>(),
+                     d.pe2.as<uint32_t>(), d.ppt.as<uint32_t>(), d.gap.as<int32_t>(), d.w.as<uint64_t>(),
+                     ix->seg.as<uint32_t>(), P, rows.as<uint32_t>(), cnt.as<uint64_t>(), o);
     };
-    const uint64_t x = biased(a), y = biased(b);
-    const bool eq = !std::isnan(a) && !std::isnan(b) && (x >= y ? x - y : y - x) <= 4;
-    return eq || !(a < b);
+    estimate(std::false_type{}, nullptr);
+    const uint64_t total = exclusive_scan_u64(ctx, cnt.as<uint64_t>(), cnt.as<uint64_t>(), d.np);
+    std::vector<DeRec> recs(total);
+    if (total) {
+        rec.alloc(total * sizeof(DeRec));
+        estimate(std::true_type{}, rec.as<DeRec>());
+        d2h_big(ctx, recs.data(), rec.p, total * sizeof(DeRec));
+    }
+    BBK_HIP(hipStreamSynchronize(ctx->stream));
+    return recs;
 }
 
 }  // namespace bbk
@@ -400,8 +528,7 @@ using namespace bbk;
 
 struct bbk_clustered {
     const bbk_edgeindex *ix = nullptr;
-    std::vector<uint64_t> e1, e2, weight;
-    std::vector<float> centre, var;
+    std::vector<DeRec> recs;  // as k_de_estimate wrote them: ascending (e1, e2, centre)
     uint64_t pairs = 0, host_pairs = 0;
 };
 
@@ -416,35 +543,12 @@ int bbk_pairinfo_import(bbk_ctx *ctx, const bbk_edgeindex *ix, uint64_t n, const
         const int rc = bbk_pairinfo_begin(ctx, ix, 0, &made);
         if (rc != BBK_OK) throw Error{rc};
         std::unique_ptr<bbk_pairinfo> pi(made);
-        auto conj = [&](uint64_t e) { return (ix->seg_h[e >> 1] & kSegSelfConj) ? e : e ^ 1ull; };
-        struct Pt {
-            uint64_t e1, e2;
-            int32_t gap;
-            uint64_t w;
-        };
-        std::vector<Pt> pts(n);
-        for (uint64_t i = 0; i < n; ++i) {
+        for (uint64_t i = 0; i < n; ++i)
             for (const uint64_t e : {h_e1[i], h_e2[i]})
-                BBK_REQUIRE(e < 2 * ix->n_seg && (!(e & 1) || !(ix->seg_h[e >> 1] & kSegSelfConj)), BBK_ERR_ARG,
+                BBK_REQUIRE(e < 2 * ix->n_seg && edge_exists(e, ix->seg_h[e >> 1]), BBK_ERR_ARG,
                             "bbk_pairinfo_import: point %llu names edge %llu, which the graph does not have",
                             (unsigned long long)i, (unsigned long long)e);
-            const uint64_t c1 = conj(h_e2[i]), c2 = conj(h_e1[i]);
-            const bool smaller = c1 < h_e1[i] || (c1 == h_e1[i] && c2 < h_e2[i]);
-            pts[i] = {smaller ? c1 : h_e1[i], smaller ? c2 : h_e2[i], h_gap[i], h_weight[i]};
-        }
-        std::sort(pts.begin(), pts.end(), [](const Pt &a, const Pt &b) {
-            return std::tie(a.e1, a.e2, a.gap) < std::tie(b.e1, b.e2, b.gap);
-        });
-        for (const Pt &p : pts) {
-            if (!pi->pt_e1.empty() && pi->pt_e1.back() == p.e1 && pi->pt_e2.back() == p.e2 && pi->pt_gap.back() == p.gap) {
-                pi->pt_weight.back() += p.w;
-                continue;
-            }
-            pi->pt_e1.push_back(p.e1);
-            pi->pt_e2.push_back(p.e2);
-            pi->pt_gap.push_back(p.gap);
-            pi->pt_weight.push_back(p.w);
-        }
+        pi->points = canonical_points(n, h_e1, h_e2, h_gap, h_weight, ix->seg_h.data());
         pi->filled = true;
         *out = pi.release();
     });
@@ -455,155 +559,32 @@ int bbk_pairinfo_cluster(bbk_pairinfo *pi, const bbk_cluster_params *prm, bbk_cl
         BBK_REQUIRE(pi && prm && out, BBK_ERR_ARG, "bbk_pairinfo_cluster: NULL argument");
         BBK_REQUIRE(pi->filled, BBK_ERR_ARG, "bbk_pairinfo_cluster: before bbk_pairinfo_fill_finish");
         const bbk_edgeindex *ix = pi->ix;
-        BBK_REQUIRE(ix->has_graph, BBK_ERR_ARG,
-                    "bbk_pairinfo_cluster: the index keeps no graph (load it with bbk_edgeindex_from_gfa_with_graph)");
-        // PairInfoPathLengthUpperBound's VERIFY (pair_info_bounds.hpp:16-21)
-        BBK_REQUIRE(prm->insert_size + prm->delta > (uint64_t)ix->k + 2, BBK_ERR_ARG,
-                    "bbk_pairinfo_cluster: insert_size %llu + delta %llu - k %u - 2 is not positive",
-                    (unsigned long long)prm->insert_size, (unsigned long long)prm->delta, ix->k);
-        const uint64_t U = prm->insert_size + prm->delta - ix->k - 2;
-        BBK_REQUIRE(U < (1ull << 24) && prm->insert_size < (1ull << 24) && prm->read_length < (1ull << 24) &&
-                        prm->max_distance < (1ull << 24) && prm->linkage_distance < (1ull << 24),
-                    BBK_ERR_ARG, "bbk_pairinfo_cluster: a distance parameter of 2^24 or more");
-        BBK_REQUIRE(!std::isnan(prm->filter_threshold), BBK_ERR_ARG, "bbk_pairinfo_cluster: filter_threshold is not a number");
+        const DeParams P = cluster_params(ix, prm);
         bbk_ctx *ctx = pi->ctx;
         BBK_HIP(hipSetDevice(ctx->device));
         const std::shared_ptr<DeDeviceGraph> G = device_graph(ctx, ix);
-        const DeGraph &g = G->h;
 
-        DeParams P{};
-        P.k = ix->k;
-        P.U = (uint32_t)U;
-        P.words = (uint32_t)(U >> 5) + 1;
-        P.gap = (int64_t)prm->insert_size - 2 * (int64_t)prm->read_length;
-        P.delta = prm->delta;
-        P.linkage = prm->linkage_distance;
-        P.max_distance = prm->max_distance;
-        if (prm->filter_threshold > 0) {  // the least weight in half-units with math::ge(weight, threshold)
-            const double twice = std::min(2 * prm->filter_threshold, 1.8e19);
-            uint64_t w = (uint64_t)std::floor(twice);
-            w = w > 2 ? w - 2 : 0;
-            while (!math_ge((double)w / 2.0, prm->filter_threshold)) ++w;
-            P.min_weight = w;
-        }
-
-        // the pairs and the first edges of the ascending points
-        const uint64_t n = pi->pt_e1.size();
-        BBK_REQUIRE(n < (1ull << 32) - 1, BBK_ERR_ARG, "bbk_pairinfo_cluster: 2^32 - 1 points or more");
-        std::vector<uint32_t> pe1, pe2, ppt, grp;
-        for (uint64_t i = 0; i < n; ++i) {
-            if (i && pi->pt_e1[i] == pi->pt_e1[i - 1] && pi->pt_e2[i] == pi->pt_e2[i - 1]) continue;
-            if (!i || pi->pt_e1[i] != pi->pt_e1[i - 1]) grp.push_back((uint32_t)pe1.size());
-            pe1.push_back((uint32_t)pi->pt_e1[i]);
-            pe2.push_back((uint32_t)pi->pt_e2[i]);
-            ppt.push_back((uint32_t)i);
-        }
-        const uint64_t np = pe1.size(), ng = grp.size();
-        ppt.push_back((uint32_t)n);
-        grp.push_back((uint32_t)np);
+        DePairs d = group_pairs(pi->points);
         auto res = std::make_unique<bbk_clustered>();
         res->ix = ix;
-        res->pairs = np;
-        if (np == 0) {
+        res->pairs = d.np;
+        if (d.np == 0) {
             *out = res.release();
             return;
         }
-        BBK_REQUIRE(np * (uint64_t)P.words < (1ull << 32), BBK_ERR_ARG,
-                    "bbk_pairinfo_cluster: %llu pairs at %u length words each: 2^32 words or more", (unsigned long long)np,
+        BBK_REQUIRE(d.np * (uint64_t)P.words < (1ull << 32), BBK_ERR_ARG,
+                    "bbk_pairinfo_cluster: %llu pairs at %u length words each: 2^32 words or more", (unsigned long long)d.np,
                     P.words);
-        DevBuf d_pe1(np * 4), d_pe2(np * 4), d_ppt((np + 1) * 4), d_grp((ng + 1) * 4), d_gap(n * 4), d_w(n * 8);
-        DevBuf d_rows(np * P.words * 4), d_hard(np * 4);
-        auto up = [&](DevBuf &d, const void *h, size_t bytes) {
-            BBK_HIP(hipMemcpyAsync(d.p, h, bytes, hipMemcpyHostToDevice, ctx->stream));
-        };
-        up(d_pe1, pe1.data(), np * 4);
-        up(d_pe2, pe2.data(), np * 4);
-        up(d_ppt, ppt.data(), (np + 1) * 4);
-        up(d_grp, grp.data(), (ng + 1) * 4);
-        up(d_gap, pi->pt_gap.data(), n * 4);
-        up(d_w, pi->pt_weight.data(), n * 8);
-
-        // A/B switch: every pair takes the host's literal search
-        const bool all_host = getenv("BBK_NO_DISTEST_DEVICE") != nullptr || U > kDeUCap;
-        std::vector<uint32_t> hard(np, 1);
-        if (!all_host) {
-            const DeGraphView V{G->out_off.as<uint32_t>(), G->out_e.as<uint32_t>(), G->e_end.as<uint32_t>(),
-                                G->e_start.as<uint32_t>(), ix->seg.as<uint32_t>()};
-            {
-                KernelTimer t(ctx, "distest_walk", (double)np * P.words * 4);
-                hipLaunchKernelGGL(k_de_walk, grid_blocks(ng), dim3(64), 0, ctx->stream, ng, d_grp.as<uint32_t>(),
-                                   d_pe1.as<uint32_t>(), d_pe2.as<uint32_t>(), V, P, d_rows.as<uint32_t>(),
-                                   d_hard.as<uint32_t>());
-                check_launch("k_de_walk");
-            }
-            d2h_sync(ctx, hard.data(), d_hard.p, np * 4);
-        }
-        // the host's pairs: one Dijkstra per first edge that has any, the literal search per pair
-        std::vector<uint32_t> hidx;
-        for (uint64_t p = 0; p < np; ++p)
-            if (hard[p]) hidx.push_back((uint32_t)p);
-        const uint64_t nh = res->host_pairs = hidx.size();
-        if (nh) {
-            std::vector<uint32_t> hrows(nh * P.words, 0);
-            std::vector<uint64_t> first;  // where the pairs of a first edge begin in hidx
-            for (uint64_t i = 0; i < nh; ++i)
-                if (!i || pe1[hidx[i]] != pe1[hidx[i - 1]]) first.push_back(i);
-            first.push_back(nh);
-#pragma omp parallel num_threads(16)
-            {
-                DeSearch s(g);
-#pragma omp for schedule(dynamic, 1)
-                for (int64_t f = 0; f < (int64_t)first.size() - 1; ++f) {
-                    const uint32_t e1 = pe1[hidx[first[f]]];
-                    s.dijkstra(g.end[e1], U);
-                    for (uint64_t i = first[f]; i < first[f + 1]; ++i) {
-                        const uint32_t e2 = pe2[hidx[i]];
-                        s.lengths(g.end[e1], g.start[e2], de_lower_bound(P.k, g.length(e1), g.length(e2), P.gap, P.delta),
-                                  &hrows[i * P.words]);
-                    }
-                }
-            }
-            DevBuf d_hidx(nh * 4), d_hrows(nh * P.words * 4);
-            up(d_hidx, hidx.data(), nh * 4);
-            up(d_hrows, hrows.data(), nh * P.words * 4);
-            launch_items(ctx, "k_de_scatter", k_de_scatter, nh * P.words, nh * P.words, P.words, d_hidx.as<uint32_t>(),
-                         d_hrows.as<uint32_t>(), d_rows.as<uint32_t>());
-            BBK_HIP(hipStreamSynchronize(ctx->stream));  // the host vectors leave scope
-        }
-
-        DevBuf cnt(np * 8), rec;
-        auto estimate = [&](auto write, DeRec *o) {
-            KernelTimer t(ctx, "distest_estimate", (double)n * 12 + (double)np * P.words * 4);
-            launch_items(ctx, "k_de_estimate", k_de_estimate<decltype(write)::value>, np, np, d_pe1.as<uint32_t>(),
-                         d_pe2.as<uint32_t>(), d_ppt.as<uint32_t>(), d_gap.as<int32_t>(), d_w.as<uint64_t>(),
-                         ix->seg.as<uint32_t>(), P, d_rows.as<uint32_t>(), cnt.as<uint64_t>(), o);
-        };
-        estimate(std::false_type{}, nullptr);
-        const uint64_t total = exclusive_scan_u64(ctx, cnt.as<uint64_t>(), cnt.as<uint64_t>(), np);
-        std::vector<DeRec> recs(total);
-        if (total) {
-            rec.alloc(total * sizeof(DeRec));
-            estimate(std::true_type{}, rec.as<DeRec>());
-            d2h_big(ctx, recs.data(), rec.p, total * sizeof(DeRec));
-        }
-        BBK_HIP(hipStreamSynchronize(ctx->stream));
-        res->e1.resize(total);
-        res->e2.resize(total);
-        res->weight.resize(total);
-        res->centre.resize(total);
-        res->var.resize(total);
-        for (uint64_t i = 0; i < total; ++i) {
-            res->e1[i] = recs[i].e1;
-            res->e2[i] = recs[i].e2;
-            res->centre[i] = recs[i].centre;
-            res->var[i] = recs[i].var;
-            res->weight[i] = recs[i].weight;
-        }
+        upload_pairs(ctx, pi->points, d);
+        DevBuf rows(d.np * P.words * 4);  // per pair the bitmap of its walk lengths
+        const std::vector<uint32_t> hard = walk_on_device(ctx, ix, *G, d, P, rows);
+        res->host_pairs = search_on_host(ctx, G->h, d, P, hard, rows);
+        res->recs = estimate_clusters(ctx, ix, d, P, rows);
         *out = res.release();
     });
 }
 
-uint64_t bbk_clustered_points(const bbk_clustered *c) { return c ? c->e1.size() : 0; }
+uint64_t bbk_clustered_points(const bbk_clustered *c) { return c ? c->recs.size() : 0; }
 uint64_t bbk_clustered_pairs(const bbk_clustered *c) { return c ? c->pairs : 0; }
 uint64_t bbk_clustered_host_pairs(const bbk_clustered *c) { return c ? c->host_pairs : 0; }
 
@@ -611,55 +592,28 @@ int bbk_clustered_export(const bbk_clustered *c, uint64_t *h_e1, uint64_t *h_e2,
                          uint64_t *h_weight) {
     return guarded([&] {
         BBK_REQUIRE(c, BBK_ERR_ARG, "bbk_clustered_export: NULL argument");
-        if (h_e1) std::copy(c->e1.begin(), c->e1.end(), h_e1);
-        if (h_e2) std::copy(c->e2.begin(), c->e2.end(), h_e2);
-        if (h_centre) std::copy(c->centre.begin(), c->centre.end(), h_centre);
-        if (h_var) std::copy(c->var.begin(), c->var.end(), h_var);
-        if (h_weight) std::copy(c->weight.begin(), c->weight.end(), h_weight);
+        for (size_t i = 0; i < c->recs.size(); ++i) {
+            const DeRec &r = c->recs[i];
+            if (h_e1) h_e1[i] = r.e1;
+            if (h_e2) h_e2[i] = r.e2;
+            if (h_centre) h_centre[i] = r.centre;
+            if (h_var) h_var[i] = r.var;  // the stored 0 (DeClusters::flush)
+            if (h_weight) h_weight[i] = r.weight;
+        }
     });
 }
 
-// PairedBuffer::BinWrite of the clustered index (paired_info_buffer.hpp:197-210), the layout of bbk_pairinfo_write: PointT
-// inherits RawPointT::BinWrite (index_point.hpp:195-197, 218-259), which writes sizeof(RawPointT) = 8 bytes, so a point is
-// the float gap = d - length(e1) (PointTraits::Shrink, :296-299, a float subtraction) and the float weight; the variance
-// is not in the file.  Ids are edge + 1.
+// the clustered index in the layout of write_paired_index; what a cluster is in the file: clustered_index_point
+// (pairinfo_host.hpp)
 int bbk_clustered_write(const bbk_clustered *c, const char *path) {
     return guarded([&] {
         BBK_REQUIRE(c && path, BBK_ERR_ARG, "bbk_clustered_write: NULL argument");
-        auto uleb = [](std::string &o, uint64_t v) {
-            do {
-                uint8_t b = v & 0x7f;
-                v >>= 7;
-                if (v) b |= 0x80;
-                o.push_back((char)b);
-            } while (v);
-        };
-        const uint64_t n = c->e1.size();
-        uint64_t firsts = 0;
-        for (uint64_t i = 0; i < n; ++i) firsts += i == 0 || c->e1[i] != c->e1[i - 1];
         std::string o;
-        uleb(o, firsts);
-        for (uint64_t i = 0; i < n;) {
-            const uint64_t e1 = c->e1[i];
-            const float len1 = (float)c->ix->len[e1 >> 1];
-            uleb(o, e1 + 1);
-            while (i < n && c->e1[i] == e1) {
-                const uint64_t e2 = c->e2[i];
-                uint64_t j = i;
-                while (j < n && c->e1[j] == e1 && c->e2[j] == e2) ++j;
-                uleb(o, e2 + 1);
-                uleb(o, j - i);
-                for (; i < j; ++i) {
-                    const float pt[2] = {c->centre[i] - len1, (float)((double)c->weight[i] / 2.0)};
-                    o.append(reinterpret_cast<const char *>(pt), 8);
-                }
-            }
-            uleb(o, 0);
-        }
-        FILE *f = fopen(path, "wb");
-        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path);
-        const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
-        BBK_REQUIRE((fclose(f) == 0) && ok, BBK_ERR_IO, "short write to %s", path);
+        write_paired_index(o, c->recs.size(), [&](uint64_t i) {
+            const DeRec &r = c->recs[i];
+            return clustered_index_point(r.e1, r.e2, r.centre, r.weight, c->ix->len[r.e1 >> 1]);
+        });
+        write_index_file(path, o);
     });
 }
 

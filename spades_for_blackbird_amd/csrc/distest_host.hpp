@@ -1,7 +1,8 @@
 // distest_host.hpp -- the host side of the distance-estimation stage (csrc/distest.hip) as plain C++: the graph as the
 // reference's reader links it, and the literal search of GraphDistanceFinder for the pairs the device leaves to the host.
 // Standard headers only (no HIP, no bbk_internal.h), as readcorrect_host.hpp is for the corrector, so a stand-alone
-// program can build it with g++ alone.
+// program can build it with g++ alone.  The rules of an edge (conjugate, length, existence) and the lower bound of a path
+// length are edge_ops.h's; the weight threshold and the grouping of the points are pairinfo_host.hpp's.
 //
 //   DeGraph / de_build_graph   GFAReader::to_graph (io/graph/gfa_reader.cpp:54-148) over the kept L lines: segment i is
 //                              edge 2i and its conjugate 2i + 1 (a self-conjugate segment is the one edge 2i), the numbering
@@ -23,23 +24,24 @@
 #include <unordered_map>
 #include <vector>
 
+#include "edge_ops.h"
+
 namespace bbk {
 
-constexpr uint32_t kDeSelfConj = 1u << 31;  // kSegSelfConj of edgeindex.h: the flag in a segment's length word
 constexpr uint64_t kDeMaxCalls = 3000, kDeMaxVertices = 3000, kDeUsageThreshold = 500, kDeMaxUsage = 5;
 
 struct DeGraph {
     unsigned k = 0;
     uint64_t ns = 0;
-    std::vector<uint32_t> seg;             // (k+1)-mers of the segment | kDeSelfConj
+    std::vector<uint32_t> seg;             // (k+1)-mers of the segment | kSegSelfConj (edge_ops.h)
     std::vector<uint32_t> kc;              // KC:i: of the segment
     std::vector<uint32_t> end, start;      // per oriented edge (2 * ns; an edge that does not exist holds 0)
     std::vector<uint32_t> out_off, out_e;  // per vertex (4 * ns + 1): the edges that start there, ascending
 
-    bool selfc(uint32_t e) const { return (seg[e >> 1] & kDeSelfConj) != 0; }
-    bool exists(uint32_t e) const { return !(e & 1u) || !selfc(e); }
-    uint32_t conj(uint32_t e) const { return selfc(e) ? e : e ^ 1u; }
-    uint64_t length(uint32_t e) const { return seg[e >> 1] & ~kDeSelfConj; }
+    bool selfc(uint32_t e) const { return edge_self_conj(seg[e >> 1]); }
+    bool exists(uint32_t e) const { return edge_exists(e, seg[e >> 1]); }
+    uint32_t conj(uint32_t e) const { return edge_conj(e, seg[e >> 1]); }
+    uint64_t length(uint32_t e) const { return edge_length(seg[e >> 1]); }
     double coverage(uint32_t e) const { return (double)kc[e >> 1] / (double)length(e); }
 };
 
@@ -106,12 +108,6 @@ inline void de_build_graph(unsigned k, uint64_t ns, const uint32_t *seg, const u
     std::vector<uint32_t> fill(g.out_off.begin(), g.out_off.end() - 1);
     for (uint32_t e = 0; e < nx; ++e)
         if (g.exists(e)) g.out_e[fill[g.start[e]]++] = e;
-}
-
-// PairInfoPathLengthLowerBound (pair_info_bounds.hpp:23-27) in integers
-inline uint64_t de_lower_bound(unsigned k, uint64_t l1, uint64_t l2, int64_t gap, uint64_t delta) {
-    const int64_t a = gap + (int64_t)k + 2 - (int64_t)l1 - (int64_t)l2 - (int64_t)delta;
-    return a > 0 ? (uint64_t)a : 0;
 }
 
 struct DeSearch {

@@ -1,6 +1,7 @@
 // edgeindex.h -- the handles of the graph-mapping stage that more than one translation unit reads: the edge index
-// (edgeprof.hip builds it; pairinfo.hip joins the paths of two mates over its segment table) and the mapping paths of a
-// batch.  Not part of the C ABI.
+// (edgeprof.hip builds it; pairinfo.hip joins the paths of two mates over its segment table), the mapping paths of a
+// batch and the paired-read info of a library.  The rules of an oriented edge over the segment table are edge_ops.h's,
+// the point table of a library is pairinfo_host.hpp's.  Not part of the C ABI.
 #pragma once
 
 #include <memory>
@@ -9,6 +10,8 @@
 #include <vector>
 
 #include "bbk_internal.h"
+#include "edge_ops.h"
+#include "pairinfo_host.hpp"
 
 namespace bbk {
 
@@ -44,10 +47,6 @@ struct bbk_edgeindex {
     mutable std::mutex de_mutex;
 };
 
-namespace bbk {
-constexpr uint32_t kSegSelfConj = 1u << 31;  // (a segment holds fewer than 2^31 (k+1)-mers: the index has < 2^32 in all)
-}
-
 struct bbk_profiles {
     bbk_ctx *ctx = nullptr;
     const bbk_edgeindex *ix = nullptr;
@@ -60,27 +59,35 @@ struct bbk_paths {
     bbk::DevBuf ranges;  // n_ranges bbk_path_range in read order
 };
 
-// the paired-read info of one library (pairinfo.hip fills it, distest.hip clusters its points)
+// the paired-read info of one library (pairinfo.hip fills it, distest.hip clusters its points).  The calls are not a
+// linear state machine: push_estimate after estimate clears `estimated`, fill_begin may be called again.
 struct bbk_pairinfo {
     struct Run {  // reduced records: ascending distinct keys with their counts
         bbk::DevBuf keys, vals;
         uint64_t n = 0;
     };
+    struct EstimatePass {
+        uint64_t total = 0, mapped = 0, negative = 0, records = 0;
+        std::vector<Run> is_runs, pair_runs;  // after bbk_pairinfo_estimate: one run each, the histogram and the pair table
+        std::vector<int32_t> hist_is;
+        std::vector<uint64_t> hist_count;
+    };
+    struct FillPass {
+        uint64_t insert_size = 0, records = 0;
+        uint32_t round_distance = 0, threshold = 0;
+        std::vector<Run> point_runs;
+    };
     bbk_ctx *ctx = nullptr;
     const bbk_edgeindex *ix = nullptr;
     uint64_t min_edge_length = 0;
     int edge_bits = 1;
-    // estimate pass
-    uint64_t total = 0, mapped = 0, negative = 0, est_records = 0;
-    std::vector<Run> is_runs, pair_runs;  // after bbk_pairinfo_estimate: one run each, the histogram and the pair table
-    bool estimated = false;
-    std::vector<int32_t> hist_is;
-    std::vector<uint64_t> hist_count;
-    // fill pass
-    bool filling = false, filled = false;
-    uint64_t insert_size = 0, fill_records = 0;
-    uint32_t round_distance = 0, threshold = 0;
-    std::vector<Run> point_runs;
-    std::vector<uint64_t> pt_e1, pt_e2, pt_weight;
-    std::vector<int32_t> pt_gap;
+    EstimatePass est;
+    FillPass fill;
+    bbk::PairPoints points;  // what bbk_pairinfo_fill_finish or bbk_pairinfo_import left
+    bool estimated = false, filling = false, filled = false;
 };
+
+namespace bbk {
+// `bytes` to the file `path` (pairinfo.hip): the end of bbk_pairinfo_write and bbk_clustered_write
+void write_index_file(const char *path, const std::string &bytes);
+}

@@ -563,7 +563,7 @@ int bbk_edgeindex_export_segments(const bbk_edgeindex *ix, uint64_t *h_len, uint
         BBK_REQUIRE(ix, BBK_ERR_ARG, "bbk_edgeindex_export_segments: NULL index");
         if (h_len) std::copy(ix->len.begin(), ix->len.end(), h_len);
         if (h_self_conjugate)
-            for (uint64_t s = 0; s < ix->n_seg; ++s) h_self_conjugate[s] = (ix->seg_h[s] & kSegSelfConj) ? 1 : 0;
+            for (uint64_t s = 0; s < ix->n_seg; ++s) h_self_conjugate[s] = edge_self_conj(ix->seg_h[s]) ? 1 : 0;
     });
 }
 

@@ -4,11 +4,7 @@
 
 #include <cstdint>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
-#define BBK_HOST_DEVICE __host__ __device__
-#else
-#define BBK_HOST_DEVICE
-#endif
+#include "host_device.h"
 
 namespace bbk {
 

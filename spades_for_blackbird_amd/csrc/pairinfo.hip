@@ -7,9 +7,9 @@
 //   LatePairedIndexFiller::ProcessPairedRead (common/paired_info/pair_info_filler.hpp:63-93) with
 //   PairedBufferBase::Add / InsertWithConj (common/paired_info/paired_info_buffer.hpp:54-57, 103-147)
 //                                                                                          -> k_pi_pairs<*, true>
-// and, on the host in doubles, find_mean / find_median / GetISInterval (common/paired_info/insert_size_refiner.hpp:23-166)
-// in the order CollectLibInformation calls them (pair_info_count.cpp:231-242), and PairedBuffer::BinWrite
-// (paired_info_buffer.hpp:197-210).
+// The host arithmetic of the stage is pairinfo_host.hpp's: the insert-size statistics in doubles (lib_statistics), the
+// rounding of a distance (pi_round), the point table (PairPoints) and PairedBuffer::BinWrite (write_paired_index).  The
+// conjugate of an edge and the canonical form of a pair are edge_ops.h's.
 //
 // A pair as presented.  OrientationChanger (common/io/reads/orientation.hpp:15-41) reverse-complements a mate before it
 // is mapped.  The paths of the file-orientation mates are what the batch holds; the path of a reverse complement is
@@ -36,10 +36,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -65,10 +63,6 @@ struct PiRange {
     uint32_t is, ie, ms, me;  // initial [start, end), mapped [start, end)
 };
 
-__device__ inline uint64_t pi_conj(uint64_t e, const uint32_t *__restrict__ seg) {
-    return (seg[e >> 1] & kSegSelfConj) ? e : e ^ 1ull;
-}
-
 // range i of `cnt` of the presented mate (header comment); npos = (k+1)-mer positions of the mate
 __device__ inline PiRange pi_range(const PiSide &s, uint32_t first, uint32_t cnt, uint32_t i, uint32_t npos,
                                    const uint32_t *__restrict__ seg) {
@@ -81,8 +75,8 @@ __device__ inline PiRange pi_range(const PiSide &s, uint32_t first, uint32_t cnt
         o.ms = x.map_start;
         o.me = x.map_end;
     } else {
-        const uint32_t sg = seg[x.edge >> 1], L = sg & ~kSegSelfConj;
-        o.edge = (sg & kSegSelfConj) ? x.edge : x.edge ^ 1ull;
+        const uint32_t sg = seg[x.edge >> 1], L = edge_length(sg);
+        o.edge = edge_conj(x.edge, sg);
         o.is = npos - x.init_end;
         o.ie = npos - x.init_start;
         o.ms = L - x.map_end;
@@ -128,7 +122,7 @@ __global__ __launch_bounds__(256) void k_pi_is(uint64_t n, PiSide a, PiSide b, c
         uint64_t key = kIsNone;
         if (c1 == 1 && c2 == 1) {
             const PiRange x = pi_range(a, f1, 1, 0, a.len[p] - k, seg), y = pi_range(b, f2, 1, 0, b.len[p] - k, seg);
-            if (x.edge == y.edge && (uint64_t)(seg[x.edge >> 1] & ~kSegSelfConj) >= min_len) {
+            if (x.edge == y.edge && (uint64_t)edge_length(seg[x.edge >> 1]) >= min_len) {
                 const int read1_start = (int)x.ms - (int)x.is, read2_start = (int)y.ms - (int)y.is;
                 const int is = read2_start - read1_start + (int)b.len[p] + (int)pi_trim(cut, p, a.rc, b.rc);
                 counted = is > 0;
@@ -170,12 +164,18 @@ struct PiFill {
     uint64_t tab_n;
 };
 
-// int(std::round(d / double(r))) * r (pair_info_filler.hpp:84-85) in integers: half away from zero
-__host__ __device__ inline int32_t pi_round(int32_t d, uint32_t r) {
-    const uint64_t ad = d < 0 ? (uint64_t)(-(int64_t)d) : (uint64_t)d;
-    const uint32_t q = (uint32_t)((2 * ad + r) / (2 * (uint64_t)r));
-    const uint32_t m = q * r;
-    return (int32_t)(d < 0 ? 0u - m : m);
+// the parameters of the fill pass and the pair table of the estimate pass, as the handle holds them
+static PiFill fill_params(const bbk_pairinfo *pi) {
+    PiFill f{};
+    f.insert_size = (uint32_t)pi->fill.insert_size;
+    f.round_distance = pi->fill.round_distance;
+    f.threshold = pi->fill.threshold;
+    if (!pi->est.pair_runs.empty()) {
+        f.tab = pi->est.pair_runs[0].keys.as<Key<2>>();
+        f.tab_cnt = pi->est.pair_runs[0].vals.as<uint32_t>();
+        f.tab_n = pi->est.pair_runs[0].n;
+    }
+    return f;
 }
 
 // One lane per pair over path1 x path2.  FILL = false (estimate pass): a record is the ordered edge pair.  FILL = true:
@@ -215,7 +215,7 @@ __global__ __launch_bounds__(256) void k_pi_pairs(uint64_t n, PiSide a, PiSide b
                 r.w[1] = y.edge;
                 out[at + w++] = r;
             } else {
-                const uint64_t cy = pi_conj(y.edge, seg), cx = pi_conj(x.edge, seg);
+                const uint64_t cy = edge_conj(y.edge, seg[y.edge >> 1]), cx = edge_conj(x.edge, seg[x.edge >> 1]);
                 if (f.threshold > 0) {
                     const uint32_t c = pi_pair_count(f.tab, f.tab_cnt, f.tab_n, x.edge, y.edge) +
                                        pi_pair_count(f.tab, f.tab_cnt, f.tab_n, cy, cx);
@@ -225,9 +225,9 @@ __global__ __launch_bounds__(256) void k_pi_pairs(uint64_t n, PiSide a, PiSide b
                     const uint32_t kmer_distance = read_distance + y.ie - x.is;
                     int32_t d = (int32_t)(kmer_distance + x.ms - y.me);
                     if (f.round_distance > 1) d = pi_round(d, f.round_distance);
-                    const uint32_t gap = (uint32_t)d - (seg[x.edge >> 1] & ~kSegSelfConj);
-                    const bool conj_smaller = cy < x.edge || (cy == x.edge && cx < y.edge);
-                    const uint64_t e1 = conj_smaller ? cy : x.edge, e2 = conj_smaller ? cx : y.edge;
+                    const uint32_t gap = (uint32_t)d - edge_length(seg[x.edge >> 1]);
+                    uint64_t e1, e2;
+                    canonical_pair(x.edge, y.edge, seg, &e1, &e2);
                     Key<2> r;
                     r.w[0] = (e1 << 31) | (e2 >> 2);
                     r.w[1] = ((e2 & 3ull) << 32) | (uint64_t)(gap ^ 0x80000000u);
@@ -394,106 +394,11 @@ static Run pair_records(bbk_pairinfo *pi, const Batch &bt, const PiFill &f, uint
     return reduce_records(ctx, 2, rec, total, FILL ? point_passes(pi->edge_bits) : pair_passes(pi->edge_bits));
 }
 
-// ---- statistics (host, doubles; insert_size_refiner.hpp line by line) -------------------------------------------------
-
-typedef std::map<int, uint64_t> HistType;
-
-static double get_median(const HistType &hist) {
-    double S = 0;
-    for (auto it = hist.begin(); it != hist.end(); ++it) S += (double)it->second;
-    double sum = S;
-    for (auto it = hist.begin(); it != hist.end(); ++it) {
-        sum -= (double)it->second;
-        if (sum <= S / 2) return it->first;
-    }
-    return -1;
-}
-
-// math::round_to_zero (math/xmath.h:330-340); the medians it is given are histogram keys
-static int round_to_zero(double t) {
-    const int res = (int)std::floor(std::fabs(t) + 0.5);
-    return t < 0 ? -res : res;
-}
-
-static double get_mad(const HistType &hist, double median) {
-    HistType hist2;
-    for (auto it = hist.begin(); it != hist.end(); ++it) hist2[std::abs(it->first - round_to_zero(median))] = it->second;
-    return get_median(hist2);
-}
-
-static void hist_crop(const HistType &hist, double low, double high, HistType &res) {
-    for (auto it = hist.begin(); it != hist.end(); ++it)
-        if (it->first >= low && it->first <= high) res.insert(*it);
-}
-
-static std::pair<double, double> get_is_interval(double quantile, const HistType &is_hist) {
-    double S = 0;
-    for (const auto &kv : is_hist) S += (double)kv.second;
-    const double lval = S * (1 - quantile) / 2, rval = S * (1 + quantile) / 2;
-    double is_min = is_hist.begin()->first, is_max = is_hist.rbegin()->first;
-    double cS = 0;
-    for (const auto &kv : is_hist) {
-        if (cS <= lval) is_min = kv.first;
-        else if (cS <= rval) is_max = kv.first;
-        cS += (double)kv.second;
-    }
-    return {is_min, is_max};
-}
-
-static void find_median(const HistType &hist, double &median, double &mad, HistType &cropped) {
-    median = get_median(hist);
-    mad = get_mad(hist, median);
-    const double low = median - 5. * 1.4826 * mad;
-    const double high = median + 5. * 1.4826 * mad;
-    hist_crop(hist, low, high, cropped);
-    median = get_median(cropped);
-    mad = get_mad(cropped, median);
-}
-
-static void moments(const HistType &hist, double low, double high, uint64_t &n, double &mean, double &delta) {
-#pragma STDC FP_CONTRACT OFF
-    n = 0;
-    double sum = 0., sum2 = 0.;
-    for (auto it = hist.begin(); it != hist.end(); ++it) {
-        if (it->first < low || it->first > high) continue;
-        n += it->second;
-        sum += (double)it->second * 1. * (double)it->first;
-        sum2 += (double)it->second * 1. * (double)it->first * (double)it->first;
-    }
-    mean = sum / (double)n;
-    delta = sqrt(sum2 / (double)n - mean * mean);
-}
-
-static void find_mean(const HistType &hist, double &mean, double &delta, uint64_t percentiles[19]) {
-#pragma STDC FP_CONTRACT OFF
-    const double median = get_median(hist);
-    const double mad = get_mad(hist, median);
-    double low = median - 5. * 1.4826 * mad;
-    double high = median + 5. * 1.4826 * mad;
-    uint64_t n;
-    moments(hist, low, high, n, mean, delta);
-    low = mean - 5 * delta;
-    high = mean + 5 * delta;
-    moments(hist, low, high, n, mean, delta);
-    uint64_t m = 0;
-    for (auto it = hist.begin(); it != hist.end(); ++it) {
-        if (it->first < low || it->first > high) continue;
-        const uint64_t mm = m + it->second;
-        for (unsigned i = 0; i < 19; ++i) {
-            const uint64_t scaled = (uint64_t)((double)(5 * (i + 1)) / 100. * (double)n);
-            if (m < scaled && mm >= scaled) percentiles[i] = (uint64_t)it->first;
-        }
-        m = mm;
-    }
-}
-
-static void uleb128(std::string &o, uint64_t v) {  // io::binary::BinWrite of an unsigned integer (binary.hpp:109-122)
-    do {
-        uint8_t b = v & 0x7f;
-        v >>= 7;
-        if (v) b |= 0x80;
-        o.push_back((char)b);
-    } while (v);
+void write_index_file(const char *path, const std::string &bytes) {
+    FILE *f = fopen(path, "wb");
+    BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path);
+    const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+    BBK_REQUIRE((fclose(f) == 0) && ok, BBK_ERR_IO, "short write to %s", path);
 }
 
 }  // namespace bbk
@@ -525,10 +430,11 @@ int bbk_pairinfo_push_estimate(bbk_pairinfo *pi, const bbk_reads *first, const b
         Batch bt;
         map_batch(pi, "bbk_pairinfo_push_estimate", first, second, orientation, h_cut, bt);
         const uint64_t n = bt.n;
-        BBK_REQUIRE(pi->total + n < (1ull << 32), BBK_ERR_ARG,
+        bbk_pairinfo::EstimatePass &est = pi->est;
+        BBK_REQUIRE(est.total + n < (1ull << 32), BBK_ERR_ARG,
                     "bbk_pairinfo_push_estimate: 2^32 pairs or more in one estimate pass (the counts are 32 bits wide)");
         pi->estimated = false;
-        pi->total += n;
+        est.total += n;
         if (n == 0) return;
         bbk_ctx *ctx = pi->ctx;
         DevBuf is_key(n * 8), ctr(16);
@@ -540,13 +446,13 @@ int bbk_pairinfo_push_estimate(bbk_pairinfo *pi, const bbk_reads *first, const b
         }
         uint64_t c[2];
         d2h_sync(ctx, c, ctr.p, 16);
-        pi->mapped += c[0];
-        pi->negative += c[1];
+        est.mapped += c[0];
+        est.negative += c[1];
         Run r = reduce_records(ctx, 1, is_key, n, is_passes());
         if (c[0] < n) --r.n;  // the last key is kIsNone
-        keep_run(ctx, 1, pi->is_runs, std::move(r), is_passes());
-        Run pr = pair_records<false>(pi, bt, PiFill{}, pi->est_records);
-        keep_run(ctx, 2, pi->pair_runs, std::move(pr), pair_passes(pi->edge_bits));
+        keep_run(ctx, 1, est.is_runs, std::move(r), is_passes());
+        Run pr = pair_records<false>(pi, bt, PiFill{}, est.records);
+        keep_run(ctx, 2, est.pair_runs, std::move(pr), pair_passes(pi->edge_bits));
     });
 }
 
@@ -555,54 +461,50 @@ int bbk_pairinfo_estimate(bbk_pairinfo *pi, bbk_pairinfo_stats *st) {
         BBK_REQUIRE(pi && st, BBK_ERR_ARG, "bbk_pairinfo_estimate: NULL argument");
         bbk_ctx *ctx = pi->ctx;
         BBK_HIP(hipSetDevice(ctx->device));
+        bbk_pairinfo::EstimatePass &est = pi->est;
         if (!pi->estimated) {
-            merge_runs(ctx, 1, pi->is_runs, is_passes());
-            merge_runs(ctx, 2, pi->pair_runs, pair_passes(pi->edge_bits));
-            if (!pi->pair_runs.empty()) {  // what the filter reads: min(c, 3) = min(min(a, 3) + min(b, 3), 3)
-                Run &t = pi->pair_runs[0];
+            merge_runs(ctx, 1, est.is_runs, is_passes());
+            merge_runs(ctx, 2, est.pair_runs, pair_passes(pi->edge_bits));
+            if (!est.pair_runs.empty()) {  // what the filter reads: min(c, 3) = min(min(a, 3) + min(b, 3), 3)
+                Run &t = est.pair_runs[0];
                 launch_items(ctx, "k_pi_clamp", k_pi_clamp, t.n, t.vals.as<uint32_t>(), t.n, 3u);
             }
-            const uint64_t nh = pi->is_runs.empty() ? 0 : pi->is_runs[0].n;
+            const uint64_t nh = est.is_runs.empty() ? 0 : est.is_runs[0].n;
             std::vector<uint64_t> keys(nh);
             std::vector<uint32_t> cnt(nh);
             if (nh) {
-                BBK_HIP(hipMemcpyAsync(keys.data(), pi->is_runs[0].keys.p, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
-                BBK_HIP(hipMemcpyAsync(cnt.data(), pi->is_runs[0].vals.p, nh * 4, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipMemcpyAsync(keys.data(), est.is_runs[0].keys.p, nh * 8, hipMemcpyDeviceToHost, ctx->stream));
+                BBK_HIP(hipMemcpyAsync(cnt.data(), est.is_runs[0].vals.p, nh * 4, hipMemcpyDeviceToHost, ctx->stream));
             }
             BBK_HIP(hipStreamSynchronize(ctx->stream));
-            pi->hist_is.resize(nh);
-            pi->hist_count.resize(nh);
+            est.hist_is.resize(nh);
+            est.hist_count.resize(nh);
             for (uint64_t i = 0; i < nh; ++i) {
-                pi->hist_is[i] = (int32_t)(uint32_t)keys[i];
-                pi->hist_count[i] = cnt[i];
+                est.hist_is[i] = (int32_t)(uint32_t)keys[i];
+                est.hist_count[i] = cnt[i];
             }
             pi->estimated = true;
         }
         memset(st, 0, sizeof(*st));
-        st->total = pi->total;
-        st->mapped = pi->mapped;
-        st->negative = pi->negative;
-        st->edge_pairs = pi->pair_runs.empty() ? 0 : pi->pair_runs[0].n;
-        // CollectLibInformation (pair_info_count.cpp:227-242)
-        if (pi->mapped == 0) return;
-        HistType hist, cropped;
-        for (size_t i = 0; i < pi->hist_is.size(); ++i) hist[pi->hist_is[i]] = pi->hist_count[i];
-        find_mean(hist, st->mean, st->deviation, st->percentiles);
-        find_median(hist, st->median, st->mad, cropped);
-        if (st->median < (double)(pi->ix->k + 2)) return;
-        std::tie(st->left_quantile, st->right_quantile) = get_is_interval(0.8, cropped);
-        st->ok = !cropped.empty();
+        st->total = est.total;
+        st->mapped = est.mapped;
+        st->negative = est.negative;
+        st->edge_pairs = est.pair_runs.empty() ? 0 : est.pair_runs[0].n;
+        if (est.mapped == 0) return;  // CollectLibInformation (pair_info_count.cpp:227-230)
+        HistType hist;
+        for (size_t i = 0; i < est.hist_is.size(); ++i) hist[est.hist_is[i]] = est.hist_count[i];
+        lib_statistics(hist, pi->ix->k, st);
     });
 }
 
-uint64_t bbk_pairinfo_hist_size(const bbk_pairinfo *pi) { return pi && pi->estimated ? pi->hist_is.size() : 0; }
+uint64_t bbk_pairinfo_hist_size(const bbk_pairinfo *pi) { return pi && pi->estimated ? pi->est.hist_is.size() : 0; }
 
 int bbk_pairinfo_hist_export(const bbk_pairinfo *pi, int32_t *h_is, uint64_t *h_count) {
     return guarded([&] {
         BBK_REQUIRE(pi, BBK_ERR_ARG, "bbk_pairinfo_hist_export: NULL argument");
         BBK_REQUIRE(pi->estimated, BBK_ERR_ARG, "bbk_pairinfo_hist_export: before bbk_pairinfo_estimate");
-        if (h_is) std::copy(pi->hist_is.begin(), pi->hist_is.end(), h_is);
-        if (h_count) std::copy(pi->hist_count.begin(), pi->hist_count.end(), h_count);
+        if (h_is) std::copy(pi->est.hist_is.begin(), pi->est.hist_is.end(), h_is);
+        if (h_count) std::copy(pi->est.hist_count.begin(), pi->est.hist_count.end(), h_count);
     });
 }
 
@@ -614,11 +516,10 @@ int bbk_pairinfo_fill_begin(bbk_pairinfo *pi, uint64_t insert_size, unsigned rou
                     "(bbk_pairinfo_push_estimate, bbk_pairinfo_estimate) over the same handle", filter_threshold);
         pi->filling = true;
         pi->filled = false;
-        pi->insert_size = insert_size;
-        pi->round_distance = round_distance;
-        pi->threshold = filter_threshold;
-        pi->fill_records = 0;
-        pi->point_runs.clear();
+        pi->fill = {};  // the runs of an earlier fill pass go
+        pi->fill.insert_size = insert_size;
+        pi->fill.round_distance = round_distance;
+        pi->fill.threshold = filter_threshold;
     });
 }
 
@@ -631,18 +532,9 @@ int bbk_pairinfo_push_fill(bbk_pairinfo *pi, const bbk_reads *first, const bbk_r
         Batch bt;
         map_batch(pi, "bbk_pairinfo_push_fill", first, second, orientation, h_cut, bt);
         if (bt.n == 0) return;
-        PiFill f{};
-        f.insert_size = (uint32_t)pi->insert_size;
-        f.round_distance = pi->round_distance;
-        f.threshold = pi->threshold;
-        if (!pi->pair_runs.empty()) {
-            f.tab = pi->pair_runs[0].keys.as<Key<2>>();
-            f.tab_cnt = pi->pair_runs[0].vals.as<uint32_t>();
-            f.tab_n = pi->pair_runs[0].n;
-        }
         pi->filled = false;
-        Run r = pair_records<true>(pi, bt, f, pi->fill_records);
-        keep_run(pi->ctx, 2, pi->point_runs, std::move(r), point_passes(pi->edge_bits));
+        Run r = pair_records<true>(pi, bt, fill_params(pi), pi->fill.records);
+        keep_run(pi->ctx, 2, pi->fill.point_runs, std::move(r), point_passes(pi->edge_bits));
     });
 }
 
@@ -652,82 +544,54 @@ int bbk_pairinfo_fill_finish(bbk_pairinfo *pi) {
         BBK_REQUIRE(pi->filling, BBK_ERR_ARG, "bbk_pairinfo_fill_finish: before bbk_pairinfo_fill_begin");
         bbk_ctx *ctx = pi->ctx;
         BBK_HIP(hipSetDevice(ctx->device));
-        merge_runs(ctx, 2, pi->point_runs, point_passes(pi->edge_bits));
-        const uint64_t n = pi->point_runs.empty() ? 0 : pi->point_runs[0].n;
+        std::vector<Run> &runs = pi->fill.point_runs;
+        merge_runs(ctx, 2, runs, point_passes(pi->edge_bits));
+        const uint64_t n = runs.empty() ? 0 : runs[0].n;
         std::vector<uint64_t> keys(2 * n);
         std::vector<uint32_t> cnt(n);
         if (n) {
-            BBK_HIP(hipMemcpyAsync(keys.data(), pi->point_runs[0].keys.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
-            BBK_HIP(hipMemcpyAsync(cnt.data(), pi->point_runs[0].vals.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(keys.data(), runs[0].keys.p, n * 16, hipMemcpyDeviceToHost, ctx->stream));
+            BBK_HIP(hipMemcpyAsync(cnt.data(), runs[0].vals.p, n * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
         BBK_HIP(hipStreamSynchronize(ctx->stream));
-        pi->pt_e1.resize(n);
-        pi->pt_e2.resize(n);
-        pi->pt_gap.resize(n);
-        pi->pt_weight.resize(n);
-        const bbk_edgeindex *ix = pi->ix;
+        PairPoints &pt = pi->points;
+        pt.resize(n);
         for (uint64_t i = 0; i < n; ++i) {
             const uint64_t w0 = keys[2 * i], w1 = keys[2 * i + 1];
             const uint64_t e1 = w0 >> 31, e2 = ((w0 & 0x7FFFFFFFull) << 2) | (w1 >> 32);
-            pi->pt_e1[i] = e1;
-            pi->pt_e2[i] = e2;
-            pi->pt_gap[i] = (int32_t)((uint32_t)w1 ^ 0x80000000u);
-            // a pair that is its own conjugate gets every point twice (paired_info_buffer.hpp:106-115); conj of an edge
-            // of a segment that is not self-conjugate is e ^ 1, and two edges of one self-conjugate segment are equal
-            const bool same_seg = (e1 >> 1) == (e2 >> 1);
-            const bool selfconj = same_seg && (e1 != e2 || (ix->seg_h[e1 >> 1] & kSegSelfConj));
-            pi->pt_weight[i] = (uint64_t)cnt[i] * (selfconj ? 2 : 1);
+            pt.e1[i] = e1;
+            pt.e2[i] = e2;
+            pt.gap[i] = (int32_t)((uint32_t)w1 ^ 0x80000000u);
+            // a pair that is its own conjugate gets every point twice (paired_info_buffer.hpp:106-115)
+            pt.weight[i] = (uint64_t)cnt[i] * (pair_is_self_conj(e1, e2, pi->ix->seg_h.data()) ? 2 : 1);
         }
         pi->filled = true;
     });
 }
 
-uint64_t bbk_pairinfo_points(const bbk_pairinfo *pi) { return pi && pi->filled ? pi->pt_e1.size() : 0; }
+uint64_t bbk_pairinfo_points(const bbk_pairinfo *pi) { return pi && pi->filled ? pi->points.size() : 0; }
 
 int bbk_pairinfo_export(const bbk_pairinfo *pi, uint64_t *h_e1, uint64_t *h_e2, int32_t *h_gap, uint64_t *h_weight) {
     return guarded([&] {
         BBK_REQUIRE(pi, BBK_ERR_ARG, "bbk_pairinfo_export: NULL argument");
         BBK_REQUIRE(pi->filled, BBK_ERR_ARG, "bbk_pairinfo_export: before bbk_pairinfo_fill_finish");
-        if (h_e1) std::copy(pi->pt_e1.begin(), pi->pt_e1.end(), h_e1);
-        if (h_e2) std::copy(pi->pt_e2.begin(), pi->pt_e2.end(), h_e2);
-        if (h_gap) std::copy(pi->pt_gap.begin(), pi->pt_gap.end(), h_gap);
-        if (h_weight) std::copy(pi->pt_weight.begin(), pi->pt_weight.end(), h_weight);
+        const PairPoints &pt = pi->points;
+        if (h_e1) std::copy(pt.e1.begin(), pt.e1.end(), h_e1);
+        if (h_e2) std::copy(pt.e2.begin(), pt.e2.end(), h_e2);
+        if (h_gap) std::copy(pt.gap.begin(), pt.gap.end(), h_gap);
+        if (h_weight) std::copy(pt.weight.begin(), pt.weight.end(), h_weight);
     });
 }
 
-// PairedBuffer::BinWrite (paired_info_buffer.hpp:197-210): the number of first edges; per first edge its id, per stored
-// second edge its id and the histogram (the number of points, then RawPointT::BinWrite of each, index_point.hpp:195-197:
-// float gap, float weight), and a 0.  io::binary::BinWrite writes an unsigned integer as ULEB128 (binary.hpp:109-122,
-// 136-139) and a float raw.  Ids are edge + 1 (bbk.h).
+// the raw index in the layout of write_paired_index (pairinfo_host.hpp): a point is the float gap and the float weight
 int bbk_pairinfo_write(const bbk_pairinfo *pi, const char *path) {
     return guarded([&] {
         BBK_REQUIRE(pi && path, BBK_ERR_ARG, "bbk_pairinfo_write: NULL argument");
         BBK_REQUIRE(pi->filled, BBK_ERR_ARG, "bbk_pairinfo_write: before bbk_pairinfo_fill_finish");
-        const uint64_t n = pi->pt_e1.size();
-        uint64_t firsts = 0;
-        for (uint64_t i = 0; i < n; ++i) firsts += i == 0 || pi->pt_e1[i] != pi->pt_e1[i - 1];
+        const PairPoints &pt = pi->points;
         std::string o;
-        uleb128(o, firsts);
-        for (uint64_t i = 0; i < n;) {
-            const uint64_t e1 = pi->pt_e1[i];
-            uleb128(o, e1 + 1);
-            while (i < n && pi->pt_e1[i] == e1) {
-                const uint64_t e2 = pi->pt_e2[i];
-                uint64_t j = i;
-                while (j < n && pi->pt_e1[j] == e1 && pi->pt_e2[j] == e2) ++j;
-                uleb128(o, e2 + 1);
-                uleb128(o, j - i);
-                for (; i < j; ++i) {
-                    const float pt[2] = {(float)pi->pt_gap[i], (float)pi->pt_weight[i]};
-                    o.append(reinterpret_cast<const char *>(pt), 8);
-                }
-            }
-            uleb128(o, 0);
-        }
-        FILE *f = fopen(path, "wb");
-        BBK_REQUIRE(f, BBK_ERR_IO, "cannot open %s for writing", path);
-        const bool ok = fwrite(o.data(), 1, o.size(), f) == o.size();
-        BBK_REQUIRE((fclose(f) == 0) && ok, BBK_ERR_IO, "short write to %s", path);
+        write_paired_index(o, pt.size(), [&](uint64_t i) { return raw_index_point(pt, i); });
+        write_index_file(path, o);
     });
 }
 

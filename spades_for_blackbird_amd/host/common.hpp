@@ -276,6 +276,13 @@ inline void write_u64(const std::string &path, const uint64_t *p, size_t count) 
     if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
 }
 
+inline void write_text(const std::string &path, const std::string &text) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) fatal("cannot open %s for writing", path.c_str());
+    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
+    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
+}
+
 // Sequences cut into pieces at the characters `cut` names: the pieces back to back, and the first piece of every sequence
 struct PieceBlock {
     std::string bases;

@@ -22,7 +22,6 @@
 // with BWA), and interlaced libraries.  Long-read, contig and single-read libraries are skipped.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
 #include <string>
 #include <vector>
 
@@ -74,26 +73,6 @@ static uint64_t graph_nx(const std::vector<uint64_t> &seg_len, const std::vector
     return 0;
 }
 
-static bool is_nucl(char c) { return memchr("ACGTacgt", c, 8) != nullptr; }  // common/sequence/nucl.hpp:45-62
-
-// LongestValidCoords (io/reads/longest_valid_wrapper.hpp:15-42): [from, to) of the first longest run of nucleotides
-static void longest_valid(const std::string &seq, size_t &from, size_t &to) {
-    size_t best_len = 0, best_pos = 0, pos = std::string::npos;
-    for (size_t i = 0; i <= seq.size(); ++i) {
-        if (i < seq.size() && is_nucl(seq[i])) {
-            if (pos == std::string::npos) pos = i;
-        } else {
-            if (pos != std::string::npos && i - pos > best_len) {
-                best_len = i - pos;
-                best_pos = pos;
-            }
-            pos = std::string::npos;
-        }
-    }
-    from = best_len ? best_pos : 0;
-    to = from + best_len;
-}
-
 // the mates of a batch, cut to their LongestValid stretches, and what was cut (left1, right1, left2, right2 per pair)
 struct PairBatch {
     std::string bases[2];
@@ -111,7 +90,7 @@ struct PairBatch {
     size_t bytes() const { return bases[0].size() + bases[1].size(); }
     void add(int m, const std::string &seq) {
         size_t from, to;
-        longest_valid(seq, from, to);
+        detail::longest_valid(seq.data(), seq.size(), &from, &to);  // LongestValidCoords (ingest.hpp)
         bases[m].append(seq, from, to - from);
         off[m].push_back(bases[m].size());
         cut.push_back((uint32_t)(to > from ? from : 0));
@@ -154,13 +133,6 @@ static size_t for_each_batch(bbk_ctx *ctx, const DatasetLib &L, size_t batch_byt
     return max_len;
 }
 
-static void write_text(const std::string &path, const std::string &text) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f) fatal("cannot open %s for writing", path.c_str());
-    const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size();
-    if (fclose(f) != 0 || !ok) fatal("cannot write %s", path.c_str());
-}
-
 static std::string lib_text(const bbk_pairinfo_stats &st) {
     char buf[128];
     std::string o;
@@ -190,35 +162,107 @@ static int orientation_of(const std::string &o, size_t lib) {
     fatal("library #%zu: unknown orientation \"%s\"", lib, o.c_str());
 }
 
-int main(int argc, char **argv) {
+struct Settings {  // (threads: the mates are read in lock step by one thread; accepted as every tool accepts it)
     unsigned k = 0, device = 0, filter_threshold = 2, rounding_thr = 0;
-    unsigned long long threads = 0, bufsize = 268435456ull, min_edge_length = 0;
-    unsigned long long read_length = 0;
+    unsigned long long threads = 0, bufsize = 268435456ull, min_edge_length = 0, read_length = 0;
     double max_distance_coeff = 2.0, rounding_coeff = 0.5, linkage_coeff = 0.0, clustered_threshold = 2.0;
-    bool meta = false, cluster = false;
-    std::vector<std::string> pos;
-    Options opt;
-    opt.num("-k", "", &k, 0u, 999u).num("-t", "--threads", &threads).num("-b", "", &bufsize, 1ull).num("", "--device", &device)
-        .num("", "--min-edge-length", &min_edge_length).flag("", "--meta", &meta)
-        .num("", "--filter-threshold", &filter_threshold).real("", "--max-distance-coeff", &max_distance_coeff)
-        .real("", "--rounding-coeff", &rounding_coeff).num("", "--rounding-threshold", &rounding_thr).flag("", "--cluster", &cluster)
-        .num("", "--read-length", &read_length).real("", "--linkage-distance-coeff", &linkage_coeff)
-        .real("", "--clustered-filter-threshold", &clustered_threshold).positional(&pos);
-    if (!opt.parse(argc, argv) || pos.size() != 3 || !opt.seen("-k")) {
-        usage(argv[0]);
-        return 1;
-    }
-    if (meta && !opt.seen("--filter-threshold")) filter_threshold = 1;  // raw_filter_threshold of meta_mode.info
-    const std::string graph = pos[0], dataset = pos[1], prefix = pos[2];
-    info("Starting paired info counting (MI355X, %s)", bbk_version());
-    check_graph_k(k);
-    info("K-mer length set to %u", k);
-    require_gfa(graph);
+    bool meta = false, cluster = false, read_length_given = false;
+};
 
-    std::vector<DatasetLib> libs;
-    std::string err;
-    if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
-    // what cannot be done is refused before anything is written
+struct Library {  // one paired-end library on its way through estimate_library, fill_library and cluster_library
+    const DatasetLib &L;
+    size_t i;  // its number in the dataset
+    int orientation;
+    std::string base;  // <prefix>.<i>
+    bbk_pairinfo *pi = nullptr;
+    bbk_pairinfo_stats st{};
+    size_t rl = 0;  // the longest read seen
+};
+
+// the estimate pass, <base>.is.hist and <base>.lib; false: the insert size cannot be estimated, the library ends here
+static bool estimate_library(bbk_ctx *ctx, const bbk_edgeindex *ix, const Settings &s, Library &lib) {
+    info("Estimating insert size for library #%zu", lib.i);
+    bbk_pairinfo *&pi = lib.pi;
+    check(bbk_pairinfo_begin(ctx, ix, s.min_edge_length, &pi), "bbk_pairinfo_begin");
+    uint64_t n_pairs = 0;
+    const size_t rl = lib.rl = for_each_batch(ctx, lib.L, (size_t)s.bufsize, n_pairs, [&](bbk_reads *a, bbk_reads *b, const uint32_t *cut) {
+        check(bbk_pairinfo_push_estimate(pi, a, b, lib.orientation, cut), "bbk_pairinfo_push_estimate");
+    });
+    if (n_pairs > 0 && rl < s.k)
+        fatal("library #%zu: its reads (at most %zu bases) are shorter than K (%u): the reference maps such a library "
+              "with BWA, which is not supported", lib.i, rl, s.k);
+    bbk_pairinfo_stats &st = lib.st;
+    check(bbk_pairinfo_estimate(pi, &st), "bbk_pairinfo_estimate");
+    info("Edge pairs: %llu", (unsigned long long)st.edge_pairs);
+    info("%llu paired reads (%g%% of all) aligned to long edges", (unsigned long long)st.mapped,
+         (double)st.mapped * 100.0 / (double)st.total);
+    if (st.negative > 3 * st.mapped)
+        info("WARN Too much reads aligned with negative insert size. Is the library orientation set properly?");
+    const uint64_t nh = bbk_pairinfo_hist_size(pi);
+    std::vector<int32_t> is(nh);
+    std::vector<uint64_t> cnt(nh);
+    check(bbk_pairinfo_hist_export(pi, is.data(), cnt.data()), "bbk_pairinfo_hist_export");
+    std::string text;
+    char buf[64];
+    for (uint64_t j = 0; j < nh; ++j)
+        text.append(buf, (size_t)snprintf(buf, sizeof(buf), "%d\t%llu\n", is[j], (unsigned long long)cnt[j]));
+    write_text(lib.base + ".is.hist", text);
+    write_text(lib.base + ".lib", lib_text(st));
+    if (!st.ok) {  // pair_info_count.cpp:356-367
+        info("WARN Unable to estimate insert size for paired library #%zu", lib.i);
+        if (rl > 0 && rl <= s.k) info("WARN Maximum read length (%zu) should be greater than K (%u)", rl, s.k);
+        else if (rl <= (size_t)s.k * 11 / 10) info("WARN Maximum read length (%zu) is probably too close to K (%u)", rl, s.k);
+        else info("WARN None of paired reads aligned properly. Please, check orientation of your read pairs.");
+        return false;
+    }
+    info("  Insert size = %g, deviation = %g, left quantile = %g, right quantile = %g, read length = %zu", st.mean,
+         st.deviation, st.left_quantile, st.right_quantile, rl);
+    if (st.mean < 1.1 * (double)rl)
+        info("WARN Estimated mean insert size %g is very small compared to read length %zu", st.mean, rl);
+    return true;
+}
+
+// the fill pass and <base>.prd
+static void fill_library(bbk_ctx *ctx, const Settings &s, Library &lib) {
+    unsigned round_thr = 0;  // pair_info_count.cpp:292-296: no rounding when the filter is off
+    if (s.filter_threshold)
+        round_thr = (unsigned)std::min(s.max_distance_coeff * lib.st.deviation * s.rounding_coeff, (double)s.rounding_thr);
+    info("Left insert size quantile %g, right insert size quantile %g, filtering threshold %u, rounding threshold %u",
+         lib.st.left_quantile, lib.st.right_quantile, s.filter_threshold, round_thr);
+    info("Mapping library #%zu", lib.i);
+    check(bbk_pairinfo_fill_begin(lib.pi, (uint64_t)lib.st.mean, round_thr, s.filter_threshold), "bbk_pairinfo_fill_begin");
+    uint64_t n_pairs = 0;
+    for_each_batch(ctx, lib.L, (size_t)s.bufsize, n_pairs, [&](bbk_reads *a, bbk_reads *b, const uint32_t *cut) {
+        check(bbk_pairinfo_push_fill(lib.pi, a, b, lib.orientation, cut), "bbk_pairinfo_push_fill");
+    });
+    check(bbk_pairinfo_fill_finish(lib.pi), "bbk_pairinfo_fill_finish");
+    info("Paired index: %llu points; saving to %s.prd", (unsigned long long)bbk_pairinfo_points(lib.pi), lib.base.c_str());
+    check(bbk_pairinfo_write(lib.pi, (lib.base + ".prd").c_str()), "bbk_pairinfo_write");
+}
+
+// estimate_distance (distance_estimation.cpp:137-154) and <base>.clustered.prd
+static void cluster_library(const Settings &s, Library &lib) {
+    bbk_cluster_params prm;
+    prm.insert_size = (uint64_t)std::floor(lib.st.mean + 0.5 + 1e-10);  // math::round (math/xmath.h:324-330)
+    prm.read_length = s.read_length_given ? s.read_length : lib.rl;
+    prm.delta = (uint64_t)lib.st.deviation;
+    prm.linkage_distance = (uint64_t)(s.linkage_coeff * lib.st.deviation);
+    prm.max_distance = (uint64_t)(s.max_distance_coeff * lib.st.deviation);
+    prm.filter_threshold = s.clustered_threshold;
+    info("Estimating distances: insert size %llu, read length %llu, delta %llu, linkage distance %llu, max distance %llu",
+         (unsigned long long)prm.insert_size, (unsigned long long)prm.read_length, (unsigned long long)prm.delta,
+         (unsigned long long)prm.linkage_distance, (unsigned long long)prm.max_distance);
+    bbk_clustered *cl = nullptr;
+    check(bbk_pairinfo_cluster(lib.pi, &prm, &cl), "bbk_pairinfo_cluster");
+    info("Clustered index: %llu points of %llu edge pairs (%llu searched on the host); saving to %s.clustered.prd",
+         (unsigned long long)bbk_clustered_points(cl), (unsigned long long)bbk_clustered_pairs(cl),
+         (unsigned long long)bbk_clustered_host_pairs(cl), lib.base.c_str());
+    check(bbk_clustered_write(cl, (lib.base + ".clustered.prd").c_str()), "bbk_clustered_write");
+    bbk_clustered_free(cl);
+}
+
+// what cannot be done is refused before anything is written; paired[i]: library i is a paired-end library to process
+static std::vector<int> check_libraries(const std::vector<DatasetLib> &libs) {
     std::vector<int> paired(libs.size(), 0);
     for (size_t i = 0; i < libs.size(); ++i) {
         const DatasetLib &L = libs[i];
@@ -240,105 +284,60 @@ int main(int argc, char **argv) {
         orientation_of(L.orientation, i);
         paired[i] = 1;
     }
+    return paired;
+}
 
+int main(int argc, char **argv) {
+    Settings s;
+    std::vector<std::string> pos;
+    Options opt;
+    opt.num("-k", "", &s.k, 0u, 999u).num("-t", "--threads", &s.threads).num("-b", "", &s.bufsize, 1ull)
+        .num("", "--device", &s.device).num("", "--min-edge-length", &s.min_edge_length).flag("", "--meta", &s.meta)
+        .num("", "--filter-threshold", &s.filter_threshold).real("", "--max-distance-coeff", &s.max_distance_coeff)
+        .real("", "--rounding-coeff", &s.rounding_coeff).num("", "--rounding-threshold", &s.rounding_thr).flag("", "--cluster", &s.cluster)
+        .num("", "--read-length", &s.read_length).real("", "--linkage-distance-coeff", &s.linkage_coeff)
+        .real("", "--clustered-filter-threshold", &s.clustered_threshold).positional(&pos);
+    if (!opt.parse(argc, argv) || pos.size() != 3 || !opt.seen("-k")) {
+        usage(argv[0]);
+        return 1;
+    }
+    if (s.meta && !opt.seen("--filter-threshold")) s.filter_threshold = 1;  // raw_filter_threshold of meta_mode.info
+    s.read_length_given = opt.seen("--read-length");
+    const std::string graph = pos[0], dataset = pos[1], prefix = pos[2];
+    const unsigned k = s.k;
+    info("Starting paired info counting (MI355X, %s)", bbk_version());
+    check_graph_k(k);
+    info("K-mer length set to %u", k);
+    require_gfa(graph);
+    std::vector<DatasetLib> libs;
+    std::string err;
+    if (!load_dataset_libs(dataset, libs, err)) fatal("%s", err.c_str());
+    const std::vector<int> paired = check_libraries(libs);
     Run run;
-    run.create_ctx(device);
+    run.create_ctx(s.device);
     bbk_ctx *ctx = run.ctx;
     info("Loading de Bruijn graph from %s", graph.c_str());
     bbk_edgeindex *ix = nullptr;
-    if (cluster) check(bbk_edgeindex_from_gfa_with_graph(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa_with_graph");
+    if (s.cluster) check(bbk_edgeindex_from_gfa_with_graph(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa_with_graph");
     else check(bbk_edgeindex_from_gfa(ctx, graph.c_str(), k, &ix), "bbk_edgeindex_from_gfa");
     const uint64_t ns = bbk_edgeindex_segments(ix);
     info("Graph: %llu edges, %llu %u-mers indexed", (unsigned long long)ns, (unsigned long long)bbk_edgeindex_size(ix), k + 1);
-    uint64_t edge_length_threshold = min_edge_length;
-    if (!meta) {
+    if (!s.meta) {  // the bound is raised to the N50 of the graph
         std::vector<uint64_t> seg_len(ns);
         std::vector<uint8_t> self_conj(ns);
         check(bbk_edgeindex_export_segments(ix, seg_len.data(), self_conj.data()), "bbk_edgeindex_export_segments");
-        edge_length_threshold = std::max<uint64_t>(edge_length_threshold, graph_nx(seg_len, self_conj, 50));
+        s.min_edge_length = std::max<unsigned long long>(s.min_edge_length, graph_nx(seg_len, self_conj, 50));
     }
-    info("Min edge length for estimation: %llu", (unsigned long long)edge_length_threshold);
-    (void)threads;  // the mates are read in lock step by this thread; the option is accepted as every tool accepts it
+    info("Min edge length for estimation: %llu", s.min_edge_length);
 
     for (size_t i = 0; i < libs.size(); ++i) {
         if (!paired[i]) continue;
-        const DatasetLib &L = libs[i];
-        const int orientation = orientation_of(L.orientation, i);
-        const std::string base = prefix + "." + std::to_string(i);
-        info("Estimating insert size for library #%zu", i);
-        bbk_pairinfo *pi = nullptr;
-        check(bbk_pairinfo_begin(ctx, ix, edge_length_threshold, &pi), "bbk_pairinfo_begin");
-        uint64_t n_pairs = 0;
-        const size_t rl = for_each_batch(ctx, L, (size_t)bufsize, n_pairs, [&](bbk_reads *a, bbk_reads *b, const uint32_t *cut) {
-            check(bbk_pairinfo_push_estimate(pi, a, b, orientation, cut), "bbk_pairinfo_push_estimate");
-        });
-        if (n_pairs > 0 && rl < k)
-            fatal("library #%zu: its reads (at most %zu bases) are shorter than K (%u): the reference maps such a library "
-                  "with BWA, which is not supported", i, rl, k);
-        bbk_pairinfo_stats st;
-        check(bbk_pairinfo_estimate(pi, &st), "bbk_pairinfo_estimate");
-        info("Edge pairs: %llu", (unsigned long long)st.edge_pairs);
-        info("%llu paired reads (%g%% of all) aligned to long edges", (unsigned long long)st.mapped,
-             (double)st.mapped * 100.0 / (double)st.total);
-        if (st.negative > 3 * st.mapped)
-            info("WARN Too much reads aligned with negative insert size. Is the library orientation set properly?");
-        {
-            const uint64_t nh = bbk_pairinfo_hist_size(pi);
-            std::vector<int32_t> is(nh);
-            std::vector<uint64_t> cnt(nh);
-            check(bbk_pairinfo_hist_export(pi, is.data(), cnt.data()), "bbk_pairinfo_hist_export");
-            std::string text;
-            char buf[64];
-            for (uint64_t j = 0; j < nh; ++j)
-                text.append(buf, (size_t)snprintf(buf, sizeof(buf), "%d\t%llu\n", is[j], (unsigned long long)cnt[j]));
-            write_text(base + ".is.hist", text);
-            write_text(base + ".lib", lib_text(st));
+        Library lib{libs[i], i, orientation_of(libs[i].orientation, i), prefix + "." + std::to_string(i)};
+        if (estimate_library(ctx, ix, s, lib)) {
+            fill_library(ctx, s, lib);
+            if (s.cluster) cluster_library(s, lib);
         }
-        if (!st.ok) {  // pair_info_count.cpp:356-367
-            info("WARN Unable to estimate insert size for paired library #%zu", i);
-            if (rl > 0 && rl <= k) info("WARN Maximum read length (%zu) should be greater than K (%u)", rl, k);
-            else if (rl <= (size_t)k * 11 / 10) info("WARN Maximum read length (%zu) is probably too close to K (%u)", rl, k);
-            else info("WARN None of paired reads aligned properly. Please, check orientation of your read pairs.");
-            bbk_pairinfo_free(pi);
-            continue;
-        }
-        info("  Insert size = %g, deviation = %g, left quantile = %g, right quantile = %g, read length = %zu", st.mean,
-             st.deviation, st.left_quantile, st.right_quantile, rl);
-        if (st.mean < 1.1 * (double)rl)
-            info("WARN Estimated mean insert size %g is very small compared to read length %zu", st.mean, rl);
-        unsigned round_thr = 0;  // pair_info_count.cpp:292-296: no rounding when the filter is off
-        if (filter_threshold)
-            round_thr = (unsigned)std::min(max_distance_coeff * st.deviation * rounding_coeff, (double)rounding_thr);
-        info("Left insert size quantile %g, right insert size quantile %g, filtering threshold %u, rounding threshold %u",
-             st.left_quantile, st.right_quantile, filter_threshold, round_thr);
-        info("Mapping library #%zu", i);
-        check(bbk_pairinfo_fill_begin(pi, (uint64_t)st.mean, round_thr, filter_threshold), "bbk_pairinfo_fill_begin");
-        for_each_batch(ctx, L, (size_t)bufsize, n_pairs, [&](bbk_reads *a, bbk_reads *b, const uint32_t *cut) {
-            check(bbk_pairinfo_push_fill(pi, a, b, orientation, cut), "bbk_pairinfo_push_fill");
-        });
-        check(bbk_pairinfo_fill_finish(pi), "bbk_pairinfo_fill_finish");
-        info("Paired index: %llu points; saving to %s.prd", (unsigned long long)bbk_pairinfo_points(pi), base.c_str());
-        check(bbk_pairinfo_write(pi, (base + ".prd").c_str()), "bbk_pairinfo_write");
-        if (cluster) {  // estimate_distance (distance_estimation.cpp:137-154)
-            bbk_cluster_params prm;
-            prm.insert_size = (uint64_t)std::floor(st.mean + 0.5 + 1e-10);  // math::round (math/xmath.h:324-330)
-            prm.read_length = opt.seen("--read-length") ? read_length : rl;
-            prm.delta = (uint64_t)st.deviation;
-            prm.linkage_distance = (uint64_t)(linkage_coeff * st.deviation);
-            prm.max_distance = (uint64_t)(max_distance_coeff * st.deviation);
-            prm.filter_threshold = clustered_threshold;
-            info("Estimating distances: insert size %llu, read length %llu, delta %llu, linkage distance %llu, max distance %llu",
-                 (unsigned long long)prm.insert_size, (unsigned long long)prm.read_length, (unsigned long long)prm.delta,
-                 (unsigned long long)prm.linkage_distance, (unsigned long long)prm.max_distance);
-            bbk_clustered *cl = nullptr;
-            check(bbk_pairinfo_cluster(pi, &prm, &cl), "bbk_pairinfo_cluster");
-            info("Clustered index: %llu points of %llu edge pairs (%llu searched on the host); saving to %s.clustered.prd",
-                 (unsigned long long)bbk_clustered_points(cl), (unsigned long long)bbk_clustered_pairs(cl),
-                 (unsigned long long)bbk_clustered_host_pairs(cl), base.c_str());
-            check(bbk_clustered_write(cl, (base + ".clustered.prd").c_str()), "bbk_clustered_write");
-            bbk_clustered_free(cl);
-        }
-        bbk_pairinfo_free(pi);
+        bbk_pairinfo_free(lib.pi);
     }
     bbk_edgeindex_free(ix);
     info("Paired info counting finished");

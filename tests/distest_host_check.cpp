@@ -16,7 +16,7 @@ int main() {
     for (unsigned long long s = 0; s < ns; ++s) {
         unsigned len, sc, c;
         if (scanf("%u %u %u", &len, &sc, &c) != 3) return 2;
-        seg[s] = len | (sc ? bbk::kDeSelfConj : 0u);
+        seg[s] = len | (sc ? bbk::kSegSelfConj : 0u);
         kc[s] = c;
     }
     for (unsigned long long j = 0; j < 4 * nl; ++j)
